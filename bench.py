@@ -5,6 +5,9 @@
   python bench.py --gpus N --steps K --warmup W
       N > 1 without a launcher environment: bench.py starts N worker processes itself (torch.distributed.run on
       127.0.0.1, one rank per GPU, RCCL); under the driver's own torch.distributed.run launch it is a rank.
+  python bench.py ... --dump-outputs DIR
+      also writes the latents the last timed step produced (float32) as DIR/latents.npy: equal arguments give equal inputs,
+      so two builds can be compared output for output.
 
 One "step" = one iteration of the captured loop for the rank's 32 utterances: replicate latents x7,
 denoiser forward, guidance combine, scheduler step.  Inputs are resident in HBM before the timed region.
@@ -485,9 +488,14 @@ def main():
     ap.add_argument("--headline-only", action="store_true", help="only the headline workload's launches (profiling passes): no zero-weight-chunk run, "
                     "no whole-run wall time, no other configurations, no CPU baseline")
     ap.add_argument("--selftest-cpu", action="store_true", help="exercise only the N-rank launch path on CPU (gloo); no measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what they computed -- the latents of the whole batch "
+                    "after the last timed step, float32 -- as DIR/latents.npy (rank 0; outside the timed region)")
     args = ap.parse_args()
     if args.headline_only:
         args.no_cpu_baseline = args.no_full_loop = args.no_secondary = True
+    # one run of the 1000-step schedule holds the warm-up and the timed iterations, and leaves one for the profiled forward
+    if args.steps < 1 or args.warmup < 0 or args.steps + args.warmup >= 1000:
+        ap.error(f"--steps {args.steps} --warmup {args.warmup}: need steps >= 1, warmup >= 0 and steps + warmup <= 999")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_ranks(args)          # does not return
@@ -521,7 +529,6 @@ def main():
     sch = scheduler.DDPMScheduler(num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012,
                                   beta_schedule="scaled_linear", variance_type="fixed_small", clip_sample=True)
     n_sched = 1000
-    assert args.steps + args.warmup < n_sched, "steps + warmup must leave one iteration of the 1000-step run for the profiled forward"
 
     def open_run(**kw):
         return SamplingRun(model, sch, mems, masks, B_PER_GPU, L, n_sched, guidance_scale=7.5, seed=0, first_utterance=rank * B_PER_GPU, **kw)
@@ -566,6 +573,15 @@ def main():
         assert torch.equal(total[rank * B_PER_GPU:(rank + 1) * B_PER_GPU], local)
     assert torch.isfinite(total).all()
     assert total.shape[0] == world * B_PER_GPU
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives: the latents [world * 32, L, 128] after iteration warmup + steps of the run
+        # (fixed seeds throughout -- weights, conditioning, Philox noise -- so equal arguments give equal inputs)
+        lat = total.detach().to("cpu", torch.float32).numpy()
+        cap = 64 << 20
+        if lat.nbytes > cap:      # (beyond 16 ranks) a fixed, seeded sample of the utterances, in batch order
+            lat = lat[np.sort(np.random.default_rng(0).choice(lat.shape[0], lat.shape[0] * cap // lat.nbytes, replace=False))]
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "latents.npy"), lat)
 
     # per-kernel-class timing with HIP events on the launch stream: ONE EAGER forward of the whole batch, every launch bracketed by
     # an event pair (cfd_profile_forward).  The brackets cost a few per cent (the classes sum to more than ms_per_step, which is

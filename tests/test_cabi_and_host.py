@@ -291,7 +291,7 @@ def test_no_kernel_of_the_library_uses_scratch_memory():
 
     def remarks(unit):
         with tempfile.TemporaryDirectory() as tmp:
-            r = subprocess.run(["/opt/rocm/bin/hipcc", *build.FLAGS, "-c", "-Rpass-analysis=kernel-resource-usage", os.path.join(build.CSRC, unit),
+            r = subprocess.run([build._hipcc(), *build.FLAGS, "-c", "-Rpass-analysis=kernel-resource-usage", os.path.join(build.CSRC, unit),
                                 "-o", os.path.join(tmp, "unit.o")], capture_output=True, text=True, timeout=900)
         assert r.returncode == 0, r.stderr[-2000:]
         return r.stderr

@@ -23,6 +23,7 @@ SYMBOLS = [
     "cfd_test_gemm", "cfd_debug_stop_stage", "cfd_debug_read", "cfd_bench_gemm", "cfd_linear_act",
     "cfd_layer_norm", "cfd_mha", "cfd_add", "cfd_zero_rows", "cfd_gemm_f32", "cfd_softmax", "cfd_softmax_bwd",
     "cfd_layer_norm_bwd", "cfd_ew", "cfd_weg_focus", "cfd_sample_write", "cfd_sample_inpaint", "cfd_weg_eval", "cfd_dyadic_steps",
+    "cfd_sample_census",
 ]
 
 
@@ -61,7 +62,17 @@ class SampleArgs(C.Structure):
                 ("preseq", C.c_void_p), ("preseq_len", C.c_int), ("mem", Memory * NUM_MEM),
                 ("skip_zero_weight_chunks", C.c_int), ("dynamic_memory_mask", C.c_int),
                 ("timesteps", C.c_void_p), ("num_timesteps", C.c_int), ("att_ring", C.c_void_p * NUM_MEM),
-                ("operand_policy", C.c_int)]
+                ("operand_policy", C.c_int), ("census_tau", C.c_float)]
+
+
+CENSUS_MAX_LAYERS = 16
+
+
+class Census(C.Structure):
+    """cfd_census: the attention-concentration census of a sampling run (cfd_sample_census)."""
+    _fields_ = [("tau", C.c_float), ("measured", C.c_int), ("iterations", C.c_int), ("worst_layer", C.c_int), ("peak_max", C.c_float),
+                ("rows_over", C.c_uint32), ("rows_seen", C.c_uint32), ("layer_peak", C.c_float * CENSUS_MAX_LAYERS),
+                ("layer_over", C.c_uint32 * CENSUS_MAX_LAYERS)]
 
 
 class WegArgs(C.Structure):
@@ -135,6 +146,7 @@ def load():
     lib.cfd_sample_steps.argtypes = [C.c_void_p, C.c_int]
     lib.cfd_sample_position.argtypes = [C.c_void_p]
     lib.cfd_sample_read.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    lib.cfd_sample_census.argtypes = [C.c_void_p, C.POINTER(Census)]
     lib.cfd_scheduler_step.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
     lib.cfd_add_noise.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,

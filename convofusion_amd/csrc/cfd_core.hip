@@ -110,6 +110,7 @@ extern "C" void cfd_destroy(cfd_handle c) {
   c->weg_io.release();
   c->weg_rt_ws.release();
   c->sat.release();
+  c->acen.release();
   for (auto& kv : c->raw) kv.second.release();
   DBuf* all[] = {&c->we_sp, &c->wp_sp, &c->wp_f, &c->ln_cd_p, &c->we_all, &c->be_all, &c->tsin, &c->weg_ws, &c->weg_tok, &c->latents, &c->coef, &c->inoise};
   for (DBuf* b : all) b->release();

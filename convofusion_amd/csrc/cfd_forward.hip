@@ -426,6 +426,11 @@ int enqueue_rows(Ctx* c, hipStream_t st, int row0, int Be) {
 #endif
       Bracket br(c, CFD_PROF_XATTN, st);
       if (p.att_fused) a.att = c->w->xa_att_desc.as<XaAtt>() + l;
+      if (c->acen_on && !p.att_fused) {   // the attention-concentration census of a sampling run (the ATT instance counts nothing)
+        a.census = c->acen.as<unsigned>() + (size_t)l * XA_CEN_SLOTS * XA_CEN_STRIDE;
+        a.census_tau = c->acen_tau;
+        c->acen_hits += 1;
+      }
       const int opf = p.att_fused ? 0 : p.xa_opf;
       const bool xa_db = XA_ALL_OPF ? c->xa_db != 0 : true;   // (developer builds: CFD_XA_DB=0 puts OPF 15 back on the three-barrier step)
       (void)xa_db;

@@ -199,6 +199,13 @@ struct cfd_handle_s {
   DBuf sat;
   bool memside_in_forward = false;   // the last enqueue_denoise ran memory-side projections itself (not hoisted): census still open
   bool run_counts = false;           // the open run's captured iteration contains launches that count into the census (per-step projections)
+  // attention-concentration census of the last sampling run (cfd_sample_args::census_tau, cfd_sample_census; xattn_fused.hpp, XAttnArgs::census):
+  // u32 [nl][XA_CEN_SLOTS][XA_CEN_STRIDE] per run, zeroed by cfd_sample_begin behind the warm-up iteration.  acen_on: only while cfd_sample_begin enqueues the run's
+  // iteration (the captured graph keeps the pointers); acen_hits: fused cross-attention launches that got a census slot.
+  DBuf acen;
+  bool acen_on = false, acen_valid = false, acen_measured = false;
+  int acen_hits = 0;
+  float acen_tau = 0.f;
   unsigned int* sat_mem() const { return sat.as<unsigned int>() + CFD_SAT_MEM; }
   unsigned int* sat_in() const { return sat.as<unsigned int>() + CFD_SAT_IN; }
   bool hoist_memside = true;

@@ -61,6 +61,9 @@ extern "C" int cfd_sample_begin(cfd_handle c, const cfd_sample_args* args, void*
   HIPCHK(hipSetDevice(c->cfg.device));
   c->hint_now = c->hint_same_mem = false;
   CHK(settle_deferred_census(c));
+  struct AcenOff { Ctx* c; ~AcenOff() { c->acen_on = false; } } acen_off{c};   // (the census slots go only into THIS run's launches)
+  c->acen_valid = c->acen_measured = false;
+  c->acen_hits = 0;
   const cfd_sample_args& s = *args;
   if (s.B < 1 || (s.G != 1 && s.G != 7 && (s.G < 1 || s.G > 8))) return fail(CFD_E_ARG, "bad B / G");
   if (s.scheduler != 0 && s.scheduler != 1) return fail(CFD_E_ARG, "scheduler must be 0 (DDPM) or 1 (DDIM)");
@@ -172,6 +175,10 @@ extern "C" int cfd_sample_begin(cfd_handle c, const cfd_sample_args* args, void*
     Problem& pb = c->w->pb;
     const bool fused_run = !pb.rt && c->fused_xattn && pb.xa_nwg > 0 && c->hoist_memside && !g_cfd_naive_gemm && !pb.att_fused && !s.dynamic_memory_mask;
     if (!fused_run) pb.xa_opf = 0;
+    // the attention-concentration census (cfd_sample_args::census_tau): the same runs as the operand policy -- the others keep pairs anyway
+    c->acen_tau = s.census_tau > 0.f ? s.census_tau : 0.f;
+    c->acen_on = fused_run && c->acen_tau > 0.f;
+    if (c->acen_on) CHK(c->acen.ensure((size_t)c->nl * XA_CEN_SLOTS * XA_CEN_STRIDE * sizeof(unsigned)));
   }
   // timesteps: (arange(N) * (T // N)).round()[::-1] (+ steps_offset for DDIM)
   std::vector<int32_t> ts(N);
@@ -222,6 +229,7 @@ extern "C" int cfd_sample_begin(cfd_handle c, const cfd_sample_args* args, void*
     HIPCHK(hipMemcpyAsync(c->latents.p, save_lat.p, lat_bytes, hipMemcpyDeviceToDevice, st));
     if (s.preseq) HIPCHK(hipMemcpyAsync(c->inoise.p, save_in.p, c->inoise.bytes, hipMemcpyDeviceToDevice, st));
     HIPCHK(hipMemsetAsync(c->w->d_step.p, 0, 16, st));
+    if (c->acen_on) HIPCHK(hipMemsetAsync(c->acen.p, 0, (size_t)c->nl * XA_CEN_SLOTS * XA_CEN_STRIDE * sizeof(unsigned), st));   // (the warm-up counted too)
     HIPCHK(hipStreamSynchronize(st));
     save_lat.release();
     save_in.release();
@@ -235,6 +243,8 @@ extern "C" int cfd_sample_begin(cfd_handle c, const cfd_sample_args* args, void*
   int r = enqueue_loop_iteration(c, cap);
   c->run_counts = c->memside_in_forward;   // (the hoisted / row-tile iteration has no counting launch: cfd_sample_read then skips the census read)
   c->memside_in_forward = false;
+  c->acen_measured = c->acen_on && c->acen_hits > 0;
+  c->acen_on = false;
   hipGraph_t g = nullptr;
   hipError_t e = hipStreamEndCapture(cap, &g);
   if (r != CFD_OK) { if (g) (void)hipGraphDestroy(g); return r; }
@@ -243,6 +253,38 @@ extern "C" int cfd_sample_begin(cfd_handle c, const cfd_sample_args* args, void*
   HIPCHK(hipGraphInstantiate(&c->gexec, c->graph, nullptr, nullptr, 0));
   c->run_open = true;
   c->run_pos = 0;
+  c->acen_valid = true;
+  return CFD_OK;
+}
+
+extern "C" int cfd_sample_census(cfd_handle c, cfd_census* out) {
+  if (!c || !out) return fail(CFD_E_ARG, "null argument");
+  if (!c->acen_valid) return fail(CFD_E_STATE, "no sampling run was opened on this handle");
+  memset(out, 0, sizeof(*out));
+  out->tau = c->acen_tau;
+  out->measured = c->acen_measured ? 1 : 0;
+  out->iterations = c->run_pos;
+  out->worst_layer = -1;
+  if (!c->acen_measured) return CFD_OK;
+  HIPCHK(hipSetDevice(c->cfg.device));
+  HIPCHK(hipStreamSynchronize(c->run_stream));
+  std::vector<unsigned> h((size_t)c->nl * XA_CEN_SLOTS * XA_CEN_STRIDE);
+  HIPCHK(hipMemcpy(h.data(), c->acen.p, h.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
+  for (int l = 0; l < c->nl; ++l) {
+    unsigned pk_bits = 0, over = 0, seen = 0;   // (positive floats order like their bits)
+    for (int sl = 0; sl < XA_CEN_SLOTS; ++sl) {
+      const unsigned* v = &h[((size_t)l * XA_CEN_SLOTS + sl) * XA_CEN_STRIDE];
+      pk_bits = std::max(pk_bits, v[0]);
+      over += v[1];
+      seen += v[2];
+    }
+    float pk;
+    memcpy(&pk, &pk_bits, 4);
+    if (l < CFD_CENSUS_MAX_LAYERS) { out->layer_peak[l] = pk; out->layer_over[l] = over; }
+    if (seen > 0 && (out->worst_layer < 0 || pk > out->peak_max)) { out->peak_max = pk; out->worst_layer = l; }
+    out->rows_over += over;
+    out->rows_seen += seen;
+  }
   return CFD_OK;
 }
 

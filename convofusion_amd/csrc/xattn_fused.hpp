@@ -76,6 +76,10 @@
 #define XA_CQOFF (XA_SEGOFF + XA_MAXSEG * 16)   // per wave: c_q partial sums [16 queries][5 memories], then sum_s P' [16][5]
 #define XA_CQW 640
 #define XA_LDS (XA_CQOFF + XA_WAVES * XA_CQW)
+// census slots per layer (XAttnArgs::census), each on a 128-byte line of its own: workgroup b counts into slot b % XA_CEN_SLOTS -- thousands of
+// waves' atomics on ONE address serialise in the L2 (+7 % kernel time at the headline shape, measured), spread over 64 lines they do not
+#define XA_CEN_SLOTS 64
+#define XA_CEN_STRIDE 32
 
 struct XaSeg {
   int j;        // memory 0..4
@@ -141,6 +145,14 @@ struct XAttnArgs {
   const float* one_rs;        // fp32 [U * one_sp]: the scale plane of this step (key 0 of instance u at u * one_sp)
   long long* stamps;          // XA_STAMP builds only (tools/xa_stamps.py): per wave, cycles per section of the kernel
   const XaAtt* att;           // the ATT instance: this layer's descriptor
+  // Attention-concentration census (non-ATT instances; DESIGN.md section 2 "census").  census: this launch's layer of the run's buffer,
+  // u32 [XA_CEN_SLOTS][XA_CEN_STRIDE], slot s = {peak_max (float bits, atomicMax), rows_over, rows_seen, ...}; the host combines the slots.
+  // null: off, nothing is counted.  At the end of every ONLINE
+  // segment of a long memory (>= XA_F16_MIN_KEYS padded keys) each live query row contributes its peak probability max_s p_s: it counts into
+  // rows_seen, into rows_over when the peak is > census_tau, and into peak_max.  Rows whose keys are all dead (NaN) are skipped.  Layer 0's
+  // de-duplicated first launch (dd_out) evaluates the long memory once per distinct (utterance, instance) pair and counts those rows, once each.
+  unsigned* census;
+  float census_tau;
 };
 
 // float32 copy of the value row of a one-key memory: out[(l * U + u) * 512 + f] = VA_l,u[f] (key 0 of V^T [nl][U][512][Sp], hi + lo)
@@ -978,6 +990,32 @@ __global__ void __launch_bounds__(XA_WAVES * 64, 2) xattn_fused_kernel(const XAt
     ++step;
     XA_T(9);
   };
+  // The census (XAttnArgs::census) of a finished online memory.  lsum is relative to mc_run = round(m log2 e), so the largest probability
+  // of the row is exp2(m log2 e - mc_run) / lsum: the same fma / exp2 the softmax gave its largest key.  The four lanes of a query hold the
+  // same m / lsum and both waves of the pair the same values: lanes 0 - 15 of the pair's first wave count.  The arguments are re-read from
+  // the kernel-argument segment like the flush's (nothing kept in SGPRs across the loop).
+  auto census_count = [&](float inv) __attribute__((always_inline)) {
+    const XAttnArgs* ka = reinterpret_cast<const XAttnArgs*>((unsigned long long)__builtin_amdgcn_kernarg_segment_ptr());
+    asm volatile("" : "+s"(ka));
+    unsigned* const cen = ka->census + (blockIdx.x % XA_CEN_SLOTS) * XA_CEN_STRIDE;
+    if (ka->census == nullptr || half != 0 || xa_sel(ka->Sp, cj) < XA_F16_MIN_KEYS) return;   // (wave-uniform)
+    constexpr float LOG2E = 1.44269504088896340736f;
+    const float pk = __builtin_amdgcn_exp2f(fmaf(m, LOG2E, -mc_run)) * inv;
+    const bool live = q4 == 0 && l15 < nq && pk == pk;      // (all keys dead: m = mc_run = -inf, pk = NaN)
+    float pmax = live ? pk : 0.f;
+    unsigned over = (live && pk > ka->census_tau) ? 1u : 0u, seen = live ? 1u : 0u;
+#pragma unroll
+    for (int d = 1; d < 16; d <<= 1) {
+      pmax = fmaxf(pmax, __shfl_xor(pmax, d, 16));
+      over += __shfl_xor(over, d, 16);
+      seen += __shfl_xor(seen, d, 16);
+    }
+    if (lane == 0 && seen > 0) {
+      atomicMax(cen, __float_as_uint(pmax));
+      if (over) atomicAdd(cen + 1, over);
+      atomicAdd(cen + 2, seen);
+    }
+  };
   // The segments [s0, s1) of the workgroup's list, all in the format `fc`.
   auto seg_loop = [&](auto fc, int s0, int s1) __attribute__((always_inline)) {
   for (int si = s0; si < s1; ++si) {
@@ -1005,6 +1043,7 @@ __global__ void __launch_bounds__(XA_WAVES * 64, 2) xattn_fused_kernel(const XAt
         for (int f = 0; f < 16; ++f) { o[f][0] *= inv; o[f][1] *= inv; o[f][2] *= inv; o[f][3] *= inv; }
         wsum *= inv;
         if constexpr (ATT) { if (att_on) att_finish(cj, mc_run, inv); }
+        if constexpr (!ATT) census_count(inv);
       }
       if (q4 == 0) wq_mine[l15 * 5 + cj] = wsum;
     }

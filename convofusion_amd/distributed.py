@@ -42,7 +42,9 @@ def gather_latents(local, total, group=None):
 
 def sample_sharded(sample_fn, encoder_hidden_states, cond_masks, total_utterances, chunks=7, group=None):
     """Run ``sample_fn(enc_shard, masks_shard, B=<local>, first_utterance=<global id>)`` on this rank's
-    utterances and return the gathered latents [total, L, 128] on every rank."""
+    utterances and return the gathered latents [total, L, 128] on every rank.  A ``sample_fn`` with ``operands="auto"`` decides PER RANK:
+    each rank's census sees its own utterances only, so one rank may fall back to ``operands=0`` while another keeps the default policy
+    (each shard's result is still bit for bit one of the two policies' for its utterances); no decision is all-reduced."""
     ws = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     a, b = shard_range(total_utterances, rank, ws)

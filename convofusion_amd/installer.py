@@ -61,7 +61,11 @@ def install(model, attention_steps="auto", operands=None):
 
     ``operands``: the run's operand policy for the fused cross-attention (``cfd_sample_args.operand_policy``; None = the default of
     ``convofusion_amd.sampler.OPERAND_POLICY`` for the model's scheduler: DDPM runs carry the long memories' folded keys / values as single
-    fp16).  ``operands=0`` keeps fp16 split pairs everywhere -- the precision escape, at ~8 % of the loop's throughput at the headline shape."""
+    fp16).  ``operands=0`` keeps fp16 split pairs everywhere -- the precision escape, at ~8 % of the loop's throughput at the headline shape.
+    ``operands="auto"`` (opt-in): the default policy while the run's attention-concentration census stays below
+    ``convofusion_amd.sampler.CENSUS_TAU``, a warning and a repeat of the loop with ``operands=0`` when it trips (``sampler.sample``)."""
+    from .sampler import check_operands
+    operands = check_operands(operands)
     _check_model(model)
     if attention_steps not in ("auto", "last", "all"):
         raise ValueError("attention_steps must be 'auto', 'last' or 'all'")

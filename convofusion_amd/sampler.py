@@ -9,6 +9,7 @@ replayed N times; nothing returns to the host between steps (the reference syncs
 """
 import ctypes as C
 import inspect
+import warnings
 
 import torch
 
@@ -27,8 +28,56 @@ CFG_CHUNKS = 7
 # throughput; the DDPM loop re-injects noise every step and does not amplify the perturbation.  DDIM (eta = 0) does -- the 50-step golden goes
 # from 1.4e-4 to 4.1e-4 -- and keeps pairs.  ``install(model, operands=0)`` /
 # ``sample(..., operands=0)`` is the precision escape for a checkpoint whose attention turns out to be less forgiving than the seeded weights
-# (the heavy-tailed stress weights: DESIGN.md section 2).
+# (the heavy-tailed stress weights: DESIGN.md section 2).  ``operands="auto"`` (opt-in) decides per run: the default policy with the
+# attention-concentration census on, and a restart with pairs from iteration 0 when the census trips (see CENSUS_TAU).
 OPERAND_POLICY = {0: 15, 1: 0}
+
+# Attention-concentration census (cfd_sample_args.census_tau, ``SamplingRun.census``): the fused cross-attention kernel reports, per layer, the
+# largest probability of every query row against a long memory and how many rows exceed CENSUS_TAU.  The single-fp16 operands are safe where
+# the attention against the 1500-key audio memory is spread out (the seeded goldens' peaks stay within a small factor of 1 / 1500), not where a
+# row concentrates on few keys (the heavy-tailed stress weights); CENSUS_TAU separates the two -- calibration table: DESIGN.md section 2.
+# ``operands="auto"`` reads the census every CENSUS_CHUNK iterations.
+CENSUS_TAU = 0.05
+CENSUS_CHUNK = 100
+
+
+class CensusTripped(Exception):
+    """Raised inside an ``operands="auto"`` run when its census counts a row above the threshold (caught by the loop entry points)."""
+
+    def __init__(self, census):
+        super().__init__(census)
+        self.census = census
+
+
+_AUTO_RUN = object()   # the first attempt of an "auto" loop (``_with_auto_operands``): a guarded run, not another "auto" loop
+
+
+def check_operands(operands):
+    """None, an operand policy (int), or "auto"; anything else is refused."""
+    if operands is None or operands is _AUTO_RUN or operands == "auto":
+        return operands
+    if isinstance(operands, (str, bytes, bool)):
+        raise ValueError(f"operands must be None, an operand policy (int) or 'auto', not {operands!r}")
+    try:
+        return int(operands)
+    except (TypeError, ValueError):
+        raise ValueError(f"operands must be None, an operand policy (int) or 'auto', not {operands!r}") from None
+
+
+def _with_auto_operands(fn, operands):
+    """``fn(operands)`` -- for ``operands="auto"`` first with the default policy and the census on; if the census trips, a warning and the
+    whole loop again from iteration 0 with ``operands=0`` (same seed, initial latents and step noise: the result is the policy-0 run's)."""
+    operands = check_operands(operands)
+    if operands != "auto":
+        return fn(operands)
+    try:
+        return fn(_AUTO_RUN)
+    except CensusTripped as e:
+        c = e.census
+        warnings.warn(f"operands='auto': the attention against a long memory concentrates (peak probability {c['peak_max']:.3g} in layer "
+                      f"{c['worst_layer']}, {c['rows_over']} rows above {c['tau']:g} within {c['iterations']} iterations): the run is repeated "
+                      "from iteration 0 with fp16 split-pair operands (operands=0)", UserWarning, stacklevel=3)
+        return fn(0)
 
 
 def _dedup_rows_exact(m, mk):
@@ -125,7 +174,7 @@ class SamplingRun:
     def __init__(self, denoiser, scheduler, encoder_hidden_states, cond_masks, B, L, num_inference_steps,
                  guidance_scale=7.5, guidance_chunks=CFG_CHUNKS, eta=0.0, init_latents=None, step_noise=None,
                  seed=0, first_utterance=0, preseq=None, dedup=True, skip_zero_weight_chunks=False, row_maps=None,
-                 dynamic_memories=(), side_engine=False, attention_ring=False, operands=None):
+                 dynamic_memories=(), side_engine=False, attention_ring=False, operands=None, census_tau=None):
         """attention_ring: keep the attention maps of the full-conditioning chunk of EVERY iteration (the reference's per-iteration dict,
         convofusion.py:517-523): the captured iteration stores them into ``self.att_ring`` -- five tensors [iterations, B, layers, L, S_j]
         -- with no extra forward and no host round trip (cfd_sample_args.att_ring: the row-tile kernels store them from their second
@@ -133,7 +182,10 @@ class SamplingRun:
         memories -- gets CFD_E_SHAPE and ``sample`` then takes the maps with one forward per iteration).  The ring is
         iterations x B x layers x L x keys floats: ``sample`` / ``diffusion_reverse`` ask for it only up to ATT_RING_MAX_BYTES.
         ``attention_dict()`` turns the ring into the dict.
-        operands: cfd_sample_args.operand_policy of this run (None: OPERAND_POLICY of the scheduler kind).
+        operands: cfd_sample_args.operand_policy of this run (None: OPERAND_POLICY of the scheduler kind).  "auto": that default with the
+        census on at CENSUS_TAU, and ``steps`` raises CensusTripped (checked every CENSUS_CHUNK iterations and at the last one) when it trips
+        -- the loop entry points (``sample``, ``sample_with_weg``) then repeat the run with ``operands=0``.
+        census_tau: cfd_sample_args.census_tau (None / 0: off unless operands="auto"); ``census()`` reads it.
         side_engine: open the run on the denoiser's second library handle (its own weights copy, workspace and stream), so that
         two runs on one module can be open at once (the attention forward of ``last_step_attention`` uses it for a plain forward).
         dynamic_memories: indices j of memories whose CONTENTS the caller rewrites between iterations (DyadicRun's partner
@@ -207,7 +259,16 @@ class SamplingRun:
         # the per-step attention maps it logs)
         a.skip_zero_weight_chunks = 1 if skip_zero_weight_chunks else 0
         a.dynamic_memory_mask = sum(1 << int(j) for j in set(dynamic_memories))
-        a.operand_policy = int(OPERAND_POLICY.get(scheduler.KIND, 0) if operands is None else operands)
+        operands = check_operands(operands)
+        default_policy = int(OPERAND_POLICY.get(scheduler.KIND, 0))
+        # "auto" with pairs as the default (DDIM) is exactly the default run: nothing to decide, no census
+        auto = operands is _AUTO_RUN or operands == "auto"
+        self._guard = auto and default_policy != 0
+        a.operand_policy = default_policy if (operands is None or auto) else operands
+        if self._guard and census_tau is None:
+            census_tau = CENSUS_TAU
+        a.census_tau = float(census_tau or 0.0)
+        self._checked = 0
         ts = (C.c_int32 * self.N)(*self.timesteps)
         self._keep.append(ts)
         a.timesteps, a.num_timesteps = C.cast(ts, C.c_void_p), self.N
@@ -227,9 +288,35 @@ class SamplingRun:
         self.open = True
 
     def steps(self, n):
+        n = int(n)
+        if n <= 0:   # (the library checks the run and the count)
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.cfd_sample_steps(self.handle, n))
+        while n > 0:
+            k = n
+            if self._guard:   # up to the next census check
+                k = min(n, self._checked + CENSUS_CHUNK - getattr(self, "_done", 0))
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.cfd_sample_steps(self.handle, k))
+            self._done = getattr(self, "_done", 0) + k
+            n -= k
+            if self._guard and (self._done - self._checked >= CENSUS_CHUNK or self._done == self.N):
+                self._checked = self._done
+                c = self.census()
+                if c["measured"] and c["rows_over"] > 0:
+                    raise CensusTripped(c)
+
+    def census(self):
+        """The run's attention-concentration census so far (cfd_sample_census; waits for the run's stream): dict with tau, measured,
+        iterations, worst_layer, peak_max, rows_over, rows_seen and the per-layer lists layer_peak / layer_over.  measured = False: nothing of
+        the run could count (census off, or a run without the fused cross-attention kernel: the row-tile path, att_ring, dynamic memories)."""
+        c = _lib.Census()
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.cfd_sample_steps(self.handle, int(n)))
-        self._done = getattr(self, "_done", 0) + int(n)
+            _lib.check(self.lib.cfd_sample_census(self.handle, C.byref(c)))
+        nl = min(_lib.CENSUS_MAX_LAYERS, int(self._keep[1].num_layers))
+        return dict(tau=float(c.tau), measured=bool(c.measured), iterations=int(c.iterations), worst_layer=int(c.worst_layer),
+                    peak_max=float(c.peak_max), rows_over=int(c.rows_over), rows_seen=int(c.rows_seen),
+                    layer_peak=[float(c.layer_peak[i]) for i in range(nl)], layer_over=[int(c.layer_over[i]) for i in range(nl)])
 
     def attention_dict(self, upto=None):
         """{timestep: [5 tensors [B, layers, L, S_j]]} of the iterations executed so far (views into the ring; read the latents first --
@@ -364,7 +451,14 @@ def sample(denoiser, scheduler, encoder_hidden_states, cond_masks=None, *, B, L=
     iteration's attention maps (``last_step_attention``), with ``return_attention="all"`` a dict {timestep: maps} over every
     iteration like the reference's: kept by the captured iteration itself (``SamplingRun(attention_ring=True)``) while the ring fits
     ATT_RING_MAX_BYTES, otherwise taken with one extra forward and one host round trip per step; ``return_attention="auto"`` always
-    returns a dict: every iteration's entries where the captured iteration keeps them itself, the last iteration's entry otherwise."""
+    returns a dict: every iteration's entries where the captured iteration keeps them itself, the last iteration's entry otherwise.
+    ``operands``: None (OPERAND_POLICY of the scheduler kind), an operand policy, or "auto": the default policy while the census
+    (CENSUS_TAU) finds no concentrated attention against a long memory; when it trips -- read every CENSUS_CHUNK iterations -- a
+    UserWarning, and the loop runs again from iteration 0 with ``operands=0``.  The result is then bit for bit the policy-0 run's (same
+    seed, initial latents and step noise), otherwise the default policy's; the worst case costs up to one extra partial run."""
+    if check_operands(operands) == "auto":
+        args = dict(locals())
+        return _with_auto_operands(lambda ops: sample(**dict(args, operands=ops)), "auto")
     run = _open_run(denoiser, scheduler, encoder_hidden_states, cond_masks, B, L, num_inference_steps, return_attention in ("all", "auto"),
                     guidance_scale=guidance_scale, guidance_chunks=guidance_chunks, eta=eta, init_latents=init_latents, step_noise=step_noise,
                     seed=seed, first_utterance=first_utterance, preseq=preseq, dedup=dedup, skip_zero_weight_chunks=skip_zero_weight_chunks,
@@ -425,7 +519,7 @@ def _loop_from_model(model, encoder_hidden_states, cond_masks, preseq, focus_ind
               # attention maps, so its forward is dead work: identical latents without it
               skip_zero_weight_chunks=True)
     kw["return_attention"] = attention
-    kw["operands"] = getattr(model, "_cfd_operands", None) if operands is None else operands
+    kw["operands"] = check_operands(getattr(model, "_cfd_operands", None) if operands is None else operands)
     if len(focus_indices) == 0:
         return sample(model.denoiser, model.scheduler, encoder_hidden_states, cond_masks, **kw)
     # ``weg_parameters`` given = the rollout (its constants are hard-coded and its scale table is fresh every iteration);
@@ -443,7 +537,11 @@ def sample_with_weg(denoiser, scheduler, encoder_hidden_states, cond_masks, focu
     max_refinement_steps (configs/assets.yaml:18-23).  ``carry_scale_range``: True reproduces ``_diffusion_reverse``, which
     re-assigns its ``scale_range`` table from the previous iteration's first two entries (convofusion.py:442-444: the step
     size stays ~scale_factor after iteration 0); False is the rollout, which takes a fresh 1.0 -> 0.5 table every
-    iteration (unbounded_synthesis.py:82-89).  See ``weg.scale_range_schedule``."""
+    iteration (unbounded_synthesis.py:82-89).  See ``weg.scale_range_schedule``.  ``operands="auto"`` (in ``kw``): as in ``sample``."""
+    if check_operands(kw.get("operands")) == "auto":
+        args = dict(locals())
+        rest = args.pop("kw")
+        return _with_auto_operands(lambda ops: sample_with_weg(**args, **dict(rest, operands=ops)), "auto")
     from . import weg
     G = guidance_chunks
     scheduler.set_timesteps(num_inference_steps)

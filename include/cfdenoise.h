@@ -161,6 +161,10 @@ typedef struct {
                                  keep pairs.  The reference is float32 throughout (cross_attention.py:593-652); which runs tolerate which bits
                                  is measured per scheduler in DESIGN.md section 2 -- convofusion_amd.sampler.OPERAND_POLICY holds the default
                                  per scheduler kind.  Ignored (pairs) on the row-tile path, with att_ring, and with a dynamic memory. */
+  float census_tau;           /* > 0: the run keeps an attention-concentration census of its long memories (cfd_sample_census): the fused
+                                 cross-attention kernel counts, per layer, the largest probability of every query row against a long memory
+                                 (>= 128 padded keys) and how many rows have one above census_tau.  0 (ctypes' zero-initialised default): off,
+                                 nothing is counted.  The field sits in what was the tail padding of this struct: its size is unchanged. */
 } cfd_sample_args;
 
 /* Opens a sampling run: builds the per-step coefficient and timestep-embedding tables, draws / copies
@@ -195,6 +199,25 @@ typedef struct {
 int cfd_dyadic_steps(cfd_handle side_a, cfd_handle side_b, const cfd_dyadic_proj* proj, int n);
 /* Copies the current latents to `out` (dev [B][L][128]); with close != 0 also ends the run. */
 int cfd_sample_read(cfd_handle h, float* out, int close);
+
+/* Attention-concentration census of the last sampling run opened on the handle (open or closed), over its iterations so far.  Each
+ * (query row, long memory) pair the fused cross-attention kernel evaluates contributes the row's largest probability max_s p_s.
+ * Layer 0 evaluates the long memory once per distinct (utterance, memory instance) pair and counts those rows once.  Waits for the run's
+ * stream.  measured = 0: nothing of the run could count -- census_tau was 0, or the run has no fused non-ATT cross-attention launch (the
+ * row-tile path, the three-launch path, a dynamic memory, att_ring); such runs use split pairs whatever the operand policy. */
+#define CFD_CENSUS_MAX_LAYERS 16
+typedef struct {
+  float tau;                                  /* cfd_sample_args.census_tau of the run */
+  int measured;
+  int iterations;                             /* iterations the census covers */
+  int worst_layer;                            /* layer with the largest peak (-1: none counted) */
+  float peak_max;                             /* largest peak probability over layers, rows and iterations (0: none counted) */
+  uint32_t rows_over;                         /* (row, long memory) pairs with a peak > tau, all layers and iterations */
+  uint32_t rows_seen;                         /* live (row, long memory) pairs counted */
+  float layer_peak[CFD_CENSUS_MAX_LAYERS];    /* per layer (layers beyond num_layers: 0) */
+  uint32_t layer_over[CFD_CENSUS_MAX_LAYERS];
+} cfd_census;
+int cfd_sample_census(cfd_handle h, cfd_census* out);
 
 /* Stand-alone scheduler ops on device tensors (diffusers 0.14.0 `scheduler.step(...).prev_sample` and
  * `add_noise`), for callers that drive their own loop (unbounded_synthesis.py:75,181). */

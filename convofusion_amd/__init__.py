@@ -5,6 +5,7 @@ Host-side mirror of the reference interfaces for the one hot path this package a
   convofusion_amd.denoiser.Denoiser          <- convofusion.models.architectures.denoiser.Denoiser
   convofusion_amd.scheduler.DDPMScheduler    <- diffusers.DDPMScheduler (0.14.0)
   convofusion_amd.scheduler.DDIMScheduler    <- diffusers.DDIMScheduler (0.14.0)
+  convofusion_amd.scheduler.DPMSolverMultistepScheduler <- diffusers.DPMSolverMultistepScheduler (0.14.0, DPM-Solver++ 2M defaults)
   convofusion_amd.sampler.diffusion_reverse  <- Convofusion._diffusion_reverse
   convofusion_amd.sampler.diffusion_reverse_forecast <- unbounded_synthesis.diffusion_reverse_forecast
   convofusion_amd.install(model) / patch_rollout(module): bind the two loop entry points without editing reference sources

@@ -275,6 +275,7 @@ struct cfd_handle_s {
   hipGraph_t graph = nullptr;
   hipGraphExec_t gexec = nullptr;
   DBuf latents, coef, inoise, mem_own[CFD_NMEM];
+  DBuf hist;   // DPM-Solver++ runs (scheduler kind 2): [B][L][128] the previous iteration's x0 (CfgStepArgs::hist)
   // Internal chunk order of a sampling run: chunk k of the caller's chunk-major batch lives at rows
   // chunk_pos[k] * B.  Chunks whose rows all use ONE shared copy of the largest memory (the unconditional audio
   // memory: 5 of the 7 guidance chunks, not adjacent in the reference's order) are moved next to each other, so
@@ -415,6 +416,18 @@ __global__ void sched_step_kernel(const float* eps, const float* noise, float* x
   float prev = (kind == 0) ? c.c0 * x0 + c.cx * xv : c.c0 * x0 + c.cx * e;
   if (c.use_noise != 0.f) prev = prev + c.sigma * noise[i];
   x[i] = prev;
+}
+// DPM-Solver++ (2M) step on its own (cfd_dpmsolver_step): x0_out = this step's data prediction (the caller's history for the next step),
+// x = the update; m_prev (the previous step's x0) is read by order-2 steps only
+template <int CFD_KI = 0>
+__global__ void dpmpp_step_kernel(const float* eps, const float* m_prev, float* x, float* x0_out, size_t n, StepCoef c) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float xv = x[i];
+  const float x0 = (xv - c.sb * eps[i]) / c.sa;
+  const float m1 = c.order == 2.0f ? m_prev[i] : 0.f;
+  x0_out[i] = x0;
+  x[i] = dpmpp_prev(c, xv, x0, m1);
 }
 template <int CFD_KI = 0>
 __global__ void add_noise_kernel(const float* x0, const float* noise, float* out, size_t n, float sa, float sb) {

@@ -18,7 +18,7 @@ static void ddpm_coef(const float* ac, int T, int n_inf, int t, StepCoef* o) {
   if (var < 1e-20f) var = 1e-20f;
   o->sigma = t > 0 ? sqrtf(var) : 0.0f;
   o->use_noise = t > 0 ? 1.0f : 0.0f;
-  o->pad0 = o->pad1 = 0.f;
+  o->order = o->r0inv = 0.f;
 }
 static void ddim_coef(const float* ac, int T, int n_inf, int t, float eta, int set_alpha_to_one, StepCoef* o) {
   const int prev_t = t - T / n_inf;
@@ -33,7 +33,51 @@ static void ddim_coef(const float* ac, int T, int n_inf, int t, float eta, int s
   o->cx = sqrtf(1.0f - ap_prev - std * std);
   o->sigma = std;
   o->use_noise = eta > 0.f ? 1.0f : 0.0f;
-  o->pad0 = o->pad1 = 0.f;
+  o->order = o->r0inv = 0.f;
+}
+
+// diffusers 0.14.0 DPMSolverMultistepScheduler (dpmsolver++, solver_order 2, midpoint, lower_order_final), float32 as its torch tables:
+// alpha_t = sqrt(abar), sigma_t = sqrt(1 - abar), lambda_t = log(alpha_t) - log(sigma_t).  Step at t towards prev_t; t_prev_model = the
+// timestep of the previous step's model output (its x0 is the history m1), or -1 for a first-order step.
+static float dpmpp_lambda(const float* ac, int t) { return logf(sqrtf(ac[t])) - logf(sqrtf(1.0f - ac[t])); }
+static void dpmpp_coef(const float* ac, int t, int prev_t, int t_prev_model, StepCoef* o) {
+  const float lam_t = dpmpp_lambda(ac, prev_t), lam_s0 = dpmpp_lambda(ac, t);
+  const float h = lam_t - lam_s0;
+  o->sb = sqrtf(1.0f - ac[t]);
+  o->sa = sqrtf(ac[t]);
+  o->c0 = sqrtf(1.0f - ac[prev_t]) / o->sb;
+  o->cx = sqrtf(ac[prev_t]) * (expf(-h) - 1.0f);
+  o->sigma = 0.f;
+  o->use_noise = 0.f;
+  if (t_prev_model >= 0) {
+    const float h_0 = lam_s0 - dpmpp_lambda(ac, t_prev_model);
+    const float r0 = h_0 / h;
+    o->r0inv = 1.0f / r0;
+    o->order = 2.f;
+  } else {
+    o->r0inv = 0.f;
+    o->order = 1.f;
+  }
+}
+
+// The per-iteration coefficient rows of a loop over the timestep table ts[0..N) (what cfd_sample_begin uploads).  Kind 2 needs the table
+// strictly decreasing in [1, T): iteration 0 is first order, the last one too when N < 15 (lower_order_final), all others second order.
+static int step_coefficients(int kind, const float* ac, int T, int n_inf, const int32_t* ts, int N, float eta, int set_alpha_to_one,
+                             StepCoef* coef) {
+  for (int i = 0; i < N; ++i) {
+    const int t = ts[i];
+    if (t < 0 || t >= T) return fail(CFD_E_ARG, "timestep %d out of range", t);
+    memset(&coef[i], 0, sizeof(StepCoef));
+    if (kind == 0) ddpm_coef(ac, T, n_inf, t, &coef[i]);
+    else if (kind == 1) ddim_coef(ac, T, n_inf, t, eta, set_alpha_to_one, &coef[i]);
+    else {
+      if (t < 1 || (i > 0 && t >= ts[i - 1]))
+        return fail(CFD_E_ARG, "DPM-Solver++: the timestep table must decrease strictly and stay in [1, %d) (entry %d is %d)", T, i, t);
+      const bool first = i == 0 || (i == N - 1 && N < 15);
+      dpmpp_coef(ac, t, i + 1 < N ? ts[i + 1] : 0, first ? -1 : ts[i - 1], &coef[i]);
+    }
+  }
+  return CFD_OK;
 }
 
 static int enqueue_loop_iteration(Ctx* c, hipStream_t st) {
@@ -47,7 +91,7 @@ static int enqueue_loop_iteration(Ctx* c, hipStream_t st) {
   memset(&ca, 0, sizeof(ca));
   ca.eps = c->w->eps.as<float>(); ca.latents = c->latents.as<float>(); ca.B = s.B; ca.L = s.L; ca.G = s.G;
   for (int k = 0; k < 8; ++k) { ca.w[k] = s.guidance_weight[k]; ca.pos[k] = c->chunk_pos[k]; }
-  ca.kind = s.scheduler; ca.clip = s.clip_sample; ca.coef = c->coef.as<StepCoef>(); ca.d_step = c->w->d_step.as<int>();
+  ca.kind = s.scheduler; ca.clip = s.clip_sample; ca.hist = c->hist.as<float>(); ca.coef = c->coef.as<StepCoef>(); ca.d_step = c->w->d_step.as<int>();
   ca.noise = s.step_noise; ca.seed = s.seed; ca.utt0 = s.first_utterance;
   const long long n4 = (long long)s.B * s.L * CFD_LAT / 4;
   ca.advance = c->w->d_step.as<int>();   // the last workgroup of cfg_step_kernel advances the loop index
@@ -66,7 +110,10 @@ extern "C" int cfd_sample_begin(cfd_handle c, const cfd_sample_args* args, void*
   c->acen_hits = 0;
   const cfd_sample_args& s = *args;
   if (s.B < 1 || (s.G != 1 && s.G != 7 && (s.G < 1 || s.G > 8))) return fail(CFD_E_ARG, "bad B / G");
-  if (s.scheduler != 0 && s.scheduler != 1) return fail(CFD_E_ARG, "scheduler must be 0 (DDPM) or 1 (DDIM)");
+  if (s.scheduler < 0 || s.scheduler > 2) return fail(CFD_E_ARG, "scheduler must be 0 (DDPM), 1 (DDIM) or 2 (DPM-Solver++ (2M))");
+  if (s.scheduler == 2 && !s.timesteps)
+    return fail(CFD_E_ARG, "DPM-Solver++: pass the scheduler's timestep table in cfd_sample_args.timesteps (the library does not build it)");
+  if (s.scheduler == 2 && s.clip_sample) return fail(CFD_E_ARG, "DPM-Solver++ has no clip_sample (clip_sample must be 0)");
   if (!s.alphas_cumprod || s.num_train_timesteps < 1 || s.num_inference_steps < 1 || s.num_inference_steps > s.num_train_timesteps)
     return fail(CFD_E_ARG, "bad scheduler tables");
   if (s.timesteps && (s.num_timesteps < 1 || s.num_timesteps > s.num_train_timesteps)) return fail(CFD_E_ARG, "bad num_timesteps");
@@ -180,17 +227,12 @@ extern "C" int cfd_sample_begin(cfd_handle c, const cfd_sample_args* args, void*
     c->acen_on = fused_run && c->acen_tau > 0.f;
     if (c->acen_on) CHK(c->acen.ensure((size_t)c->nl * XA_CEN_SLOTS * XA_CEN_STRIDE * sizeof(unsigned)));
   }
-  // timesteps: (arange(N) * (T // N)).round()[::-1] (+ steps_offset for DDIM)
+  // timesteps: the caller's table, or (arange(N) * (T // N)).round()[::-1] (+ steps_offset for DDIM)
   std::vector<int32_t> ts(N);
   std::vector<StepCoef> coef(N);
   const int ratio = T / n_inf;
-  for (int i = 0; i < N; ++i) {
-    int t = s.timesteps ? s.timesteps[i] : (N - 1 - i) * ratio + (s.scheduler == 1 ? s.steps_offset : 0);
-    if (t < 0 || t >= T) return fail(CFD_E_ARG, "timestep %d out of range", t);
-    ts[i] = t;
-    if (s.scheduler == 0) ddpm_coef(s.alphas_cumprod, T, n_inf, t, &coef[i]);
-    else ddim_coef(s.alphas_cumprod, T, n_inf, t, s.eta, s.set_alpha_to_one, &coef[i]);
-  }
+  for (int i = 0; i < N; ++i) ts[i] = s.timesteps ? s.timesteps[i] : (N - 1 - i) * ratio + (s.scheduler == 1 ? s.steps_offset : 0);
+  CHK(step_coefficients(s.scheduler, s.alphas_cumprod, T, n_inf, ts.data(), N, s.eta, s.set_alpha_to_one, coef.data()));
   CHK(c->coef.ensure((size_t)N * sizeof(StepCoef)));
   HIPCHK(hipMemcpyAsync(c->coef.p, coef.data(), (size_t)N * sizeof(StepCoef), hipMemcpyHostToDevice, st));
   HIPCHK(hipMemsetAsync(c->w->d_step.p, 0, 16, st));
@@ -205,6 +247,12 @@ extern "C" int cfd_sample_begin(cfd_handle c, const cfd_sample_args* args, void*
     HIPCHK(hipMemcpyAsync(c->latents.p, s.init_latents, lat_bytes, hipMemcpyDeviceToDevice, st));
   } else {
     CHK(enqueue_philox_fill(c->latents.as<float>(), s.B, s.L * CFD_LAT, (uint64_t)s.seed, 0u, s.first_utterance, 1u, 1.0f, st));
+  }
+  // DPM-Solver++: the x0 history of the run, zeroed.  Iteration 0 is first order and never reads it, so the eager warm-up iteration below,
+  // which runs as iteration 0 and writes its x0 here, needs no save / restore: the first replay overwrites that before anything reads it.
+  if (s.scheduler == 2) {
+    CHK(c->hist.ensure(lat_bytes));
+    HIPCHK(hipMemsetAsync(c->hist.p, 0, lat_bytes, st));
   }
   CHK(c->inoise.ensure(s.preseq ? (size_t)s.B * s.preseq_len * CFD_LAT * 4 : 16));
   if (s.preseq) {
@@ -369,14 +417,44 @@ extern "C" int cfd_scheduler_step(cfd_handle c, int scheduler, const float* ac, 
                                   int set_alpha_to_one, const float* model_output, const float* noise, float* sample_inout,
                                   size_t numel, float* pred_original_sample, void* stream) {
   if (!c || !ac || !model_output || !sample_inout || t < 0 || t >= T || n_inf < 1) return fail(CFD_E_ARG, "bad argument");
+  if (scheduler != 0 && scheduler != 1)
+    return fail(CFD_E_ARG, "cfd_scheduler_step: scheduler must be 0 (DDPM) or 1 (DDIM); DPM-Solver++ steps go through cfd_dpmsolver_step");
   HIPCHK(hipSetDevice(c->cfg.device));
   StepCoef k;
+  memset(&k, 0, sizeof(k));
   if (scheduler == 0) ddpm_coef(ac, T, n_inf, t, &k);
   else ddim_coef(ac, T, n_inf, t, eta, set_alpha_to_one, &k);
   if (k.use_noise != 0.f && !noise) return fail(CFD_E_ARG, "this step adds noise: pass the N(0,1) draw");
   hipLaunchKernelGGL(sched_step_kernel<>, dim3((unsigned)((numel + 255) / 256)), dim3(256), 0, (hipStream_t)stream, model_output, noise,
                      sample_inout, numel, k, scheduler, clip, pred_original_sample);
   HIPCHK(hipGetLastError());
+  return CFD_OK;
+}
+
+extern "C" int cfd_dpmsolver_step(cfd_handle c, const float* ac, int T, int t, int prev_t, int t_prev_model, const float* model_output,
+                                  const float* m_prev, float* sample_inout, float* x0_out, size_t numel, void* stream) {
+  if (!c || !ac || !model_output || !sample_inout || !x0_out) return fail(CFD_E_ARG, "null argument");
+  if (t < 1 || t >= T || prev_t < 0 || prev_t >= t || t_prev_model >= T || (t_prev_model >= 0 && t_prev_model <= t))
+    return fail(CFD_E_ARG, "cfd_dpmsolver_step: need T > t_prev_model > t > prev_t >= 0 (t_prev_model = -1: first order), t >= 1 "
+                           "(got %d, %d, %d, T = %d)", t_prev_model, t, prev_t, T);
+  if (t_prev_model >= 0 && !m_prev) return fail(CFD_E_ARG, "a second-order step reads the previous step's x0: pass m_prev");
+  HIPCHK(hipSetDevice(c->cfg.device));
+  StepCoef k;
+  dpmpp_coef(ac, t, prev_t, t_prev_model, &k);
+  hipLaunchKernelGGL(dpmpp_step_kernel<>, dim3((unsigned)((numel + 255) / 256)), dim3(256), 0, (hipStream_t)stream, model_output, m_prev,
+                     sample_inout, x0_out, numel, k);
+  HIPCHK(hipGetLastError());
+  return CFD_OK;
+}
+
+// ---- developer hook: the per-iteration coefficient table a sampling run uploads, on the host (no handle, no device) ----------------
+extern "C" int cfd_test_step_coefficients(int kind, const float* ac, int T, int n_inf, const int32_t* timesteps, int N, float eta,
+                                          int set_alpha_to_one, float* out) {
+  if (!ac || !timesteps || !out || kind < 0 || kind > 2 || T < 1 || N < 1 || n_inf < 1) return fail(CFD_E_ARG, "bad argument");
+  static_assert(sizeof(StepCoef) == 8 * sizeof(float), "StepCoef is one row of 8 floats");
+  std::vector<StepCoef> coef(N);
+  CHK(step_coefficients(kind, ac, T, n_inf, timesteps, N, eta, set_alpha_to_one, coef.data()));
+  memcpy(out, coef.data(), (size_t)N * sizeof(StepCoef));
   return CFD_OK;
 }
 

@@ -509,14 +509,27 @@ __global__ void fold_mv_kernel(const TA* A, long long sam, long long sak, const 
 // Sampler element-wise kernels
 // ------------------------------------------------------------------------------------------------
 struct StepCoef {   // one row per loop iteration i (timestep t_i), float32 as diffusers computes them
-  float sb;         // sqrt(1 - abar_t)
-  float sa;         // sqrt(abar_t)
-  float c0;         // DDPM: x0 coefficient            | DDIM: sqrt(abar_prev)
+  float sb;         // sqrt(1 - abar_t)                   (DPM++: sigma_t)
+  float sa;         // sqrt(abar_t)                       (DPM++: alpha_t)
+  float c0;         // DDPM: x0 coefficient            | DDIM: sqrt(abar_prev)  | DPM++: sigma_prev / sigma_t
   float cx;         // DDPM: current-sample coefficient | DDIM: direction coefficient sqrt(1-abar_prev-std^2)
+                    // | DPM++: alpha_prev * (exp(-h) - 1)
   float sigma;      // noise std (0 when no noise is added)
-  float use_noise;  // 1.0 if a N(0,1) draw is added at this step
-  float pad0, pad1;
+  float use_noise;  // 1.0 if a N(0,1) draw is added at this step (never for DPM++)
+  float order;      // DPM++: 1 or 2 (0 for DDPM / DDIM)
+  float r0inv;      // DPM++ order 2: 1 / r0 = h / h_0 (0 otherwise)
 };
+
+// DPM-Solver++ (2M) update of one element (diffusers 0.14.0 DPMSolverMultistepScheduler, midpoint, left-to-right evaluation as
+// there): x0 is this step's data prediction, m1 the previous step's.  Branches on the order: an order-1 step never reads m1 (the
+// history of iteration 0 is unset -- 0 * NaN would be NaN).
+__host__ __device__ __forceinline__ float dpmpp_prev(const StepCoef& c, float x, float x0, float m1) {
+  if (c.order == 2.0f) {
+    const float d1 = c.r0inv * (x0 - m1);
+    return (c.c0 * x - c.cx * x0) - (0.5f * c.cx) * d1;
+  }
+  return c.c0 * x - c.cx * x0;
+}
 
 // Philox4x32-10 (restated in oracle/philox_ref.py, checked there against the Random123 known answers)
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
@@ -603,15 +616,16 @@ __global__ void begin_step_kernel(const BeginArgs a) {
     sp_store8(a.sample_sp + (((long long)g * a.B + b) * a.L + l) * (CFD_LAT * 4), c, v);
 }
 
-// Modality-guidance combine (convofusion.py:527-541) + scheduler step (diffusers 0.14.0 DDPM / DDIM).
+// Modality-guidance combine (convofusion.py:527-541) + scheduler step (diffusers 0.14.0 DDPM / DDIM / DPMSolverMultistep).
 struct CfgStepArgs {
   const float* eps;      // [G*B][L][128]
   float* latents;        // [B][L][128] in/out
   int B, L, G;
   float w[8];            // guidance weight of chunk k (k >= 1); chunk 0 is the unconditional one
   int pos[8];            // chunk k's rows start at row pos[k] * B of eps (the engine may reorder chunks internally)
-  int kind;              // 0 DDPM, 1 DDIM
+  int kind;              // 0 DDPM, 1 DDIM, 2 DPM-Solver++ (2M)
   int clip;
+  float* hist;           // kind 2: [B][L][128] the previous iteration's x0 (read by order-2 steps), overwritten with this one's
   const StepCoef* coef;
   const int* d_step;
   int* advance;          // non-null: the last workgroup to finish advances the loop (d_step[0] += 1, d_step[2] = 0; d_step[3] is its ticket
@@ -638,6 +652,8 @@ __global__ void cfg_step_kernel(const CfgStepArgs a) {
 #pragma unroll
   for (int k = 0; k < 8; ++k) e4[k] = *reinterpret_cast<const float4*>(a.eps + (k < a.G ? a.pos[k] : a.pos[0]) * chunk + e0);   // (a select of two argument fields: indexed, pos[] is a dependent scalar load per chunk)
   float4 x4 = *reinterpret_cast<const float4*>(a.latents + e0);
+  float4 m4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (a.kind == 2 && c.order == 2.0f) m4 = *reinterpret_cast<const float4*>(a.hist + e0);
   const float u[4] = {e4[0].x, e4[0].y, e4[0].z, e4[0].w};
   float acc[4] = {0.f, 0.f, 0.f, 0.f};
   // reference association: ((((text + audio) + spk) + apb) + lsnid) + all, each = (g*w)*(e_k - e_0)
@@ -662,18 +678,23 @@ __global__ void cfg_step_kernel(const CfgStepArgs a) {
       z[0] = n4v.x; z[1] = n4v.y; z[2] = n4v.z; z[3] = n4v.w;
     }
   }
-  float o[4];
+  const float m1[4] = {m4.x, m4.y, m4.z, m4.w};
+  float o[4], x0v[4];
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const float eps = (a.G > 1) ? u[q] + acc[q] : u[q];
     float x0 = (x[q] - c.sb * eps) / c.sa;
     if (a.clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+    x0v[q] = x0;
     float prev;
     if (a.kind == 0) prev = c.c0 * x0 + c.cx * x[q];
+    else if (a.kind == 2) prev = dpmpp_prev(c, x[q], x0, m1[q]);
     else prev = c.c0 * x0 + c.cx * eps;
     if (c.use_noise != 0.f) prev = prev + c.sigma * z[q];
     o[q] = prev;
   }
+  // (kind 2: this element's history is read above and written here by the same thread -- in place, race-free)
+  if (a.kind == 2) *reinterpret_cast<float4*>(a.hist + e0) = make_float4(x0v[0], x0v[1], x0v[2], x0v[3]);
   *reinterpret_cast<float4*>(a.latents + e0) = make_float4(o[0], o[1], o[2], o[3]);
   }
   if (a.advance) {   // every thread of every workgroup has read the step index above before the last ticket is taken

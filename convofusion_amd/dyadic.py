@@ -51,6 +51,9 @@ class DyadicRun:
         iteration of the double batch per lock-step iteration instead of two of B (13.9 instead of 18 ms at B = 16 per side, L = 196).
         Without injected noise the sides then draw from the Philox streams of utterances ``first_utterance`` .. ``+ 2 B - 1`` of ONE seed
         (the two-handle form gives side B the seed ``seed + 1``)."""
+        if getattr(scheduler, "KIND", None) == 2:
+            raise NotImplementedError("DyadicRun runs with DDPMScheduler / DDIMScheduler; with DPMSolverMultistepScheduler the lock-step "
+                                      "dyadic loop has no reference trajectory to be checked against")
         self.merged = bool(shared_weights)
         if self.merged:
             if denoiser_b is not None and denoiser_b is not denoiser_a:

@@ -30,7 +30,7 @@ def _check_model(model):
                         "(INTEGRATION.md section 1) before installing the fused loop" % type(den).__name__)
     if getattr(getattr(model, "scheduler", None), "KIND", None) is None:
         raise TypeError("model.scheduler is %s: point configs/modules/scheduler.yaml at convofusion_amd.scheduler.DDPMScheduler / "
-                        "DDIMScheduler (INTEGRATION.md section 2)" % type(getattr(model, "scheduler", None)).__name__)
+                        "DDIMScheduler / DPMSolverMultistepScheduler (INTEGRATION.md section 2)" % type(getattr(model, "scheduler", None)).__name__)
 
 
 def _diffusion_reverse(self, encoder_hidden_states, lengths=None, cond_masks=dict(), focus_indices=[]):

@@ -20,7 +20,7 @@ from .denoiser import Denoiser
 CFG_CHUNKS = 7
 
 # Operand policy of a run's fused cross-attention (cfd_sample_args.operand_policy; 0 = fp16 split pairs everywhere), per scheduler kind
-# (scheduler.KIND: 0 DDPM, 1 DDIM).  Non-zero: the attention against the LONG memories (128 padded keys and more: the audio memory) runs on
+# (scheduler.KIND: 0 DDPM, 1 DDIM, 2 DPM-Solver++).  Non-zero: the attention against the LONG memories (128 padded keys and more: the audio memory) runs on
 # single-fp16 operands -- bits 0 / 1: their folded values / keys as single-fp16 tiles, bits 2 / 3: the probabilities / queries of those
 # products as one fp16 as well (1 MFMA per product instead of 3); the shipped library implements the four bits together (15).  Measured on
 # every DDPM golden (profiles/r06_xa_operands_*): the 1000-step DDPM run at the headline shape ends 2.3e-5 from the
@@ -30,7 +30,9 @@ CFG_CHUNKS = 7
 # ``sample(..., operands=0)`` is the precision escape for a checkpoint whose attention turns out to be less forgiving than the seeded weights
 # (the heavy-tailed stress weights: DESIGN.md section 2).  ``operands="auto"`` (opt-in) decides per run: the default policy with the
 # attention-concentration census on, and a restart with pairs from iteration 0 when the census trips (see CENSUS_TAU).
-OPERAND_POLICY = {0: 15, 1: 0}
+# DPM-Solver++ (kind 2) is deterministic like DDIM -- no noise re-injected, its multistep history carries a perturbation forward -- and keeps
+# pairs as well.
+OPERAND_POLICY = {0: 15, 1: 0, 2: 0}
 
 # Attention-concentration census (cfd_sample_args.census_tau, ``SamplingRun.census``): the fused cross-attention kernel reports, per layer, the
 # largest probability of every query row against a long memory and how many rows exceed CENSUS_TAU.  The single-fp16 operands are safe where
@@ -199,7 +201,7 @@ class SamplingRun:
         self.lib = _lib.load()
         self.device = dev
         if getattr(scheduler, "KIND", None) is None:
-            raise TypeError("scheduler must be a convofusion_amd.scheduler DDPMScheduler / DDIMScheduler")
+            raise TypeError("scheduler must be a convofusion_amd.scheduler DDPMScheduler / DDIMScheduler / DPMSolverMultistepScheduler")
         # the loop runs over scheduler.timesteps: DDPM clamps the count to the training schedule, and for a count that does not
         # divide it the (opt-in, unpinned) 0.14.0 table has more entries than the count (scheduler.timestep_table)
         num_inference_steps, table = scheduler.timestep_table(num_inference_steps)
@@ -234,7 +236,7 @@ class SamplingRun:
         a.scheduler = scheduler.KIND
         a.num_train_timesteps = scheduler.config.num_train_timesteps
         a.num_inference_steps = num_inference_steps
-        a.clip_sample = 1 if scheduler.config.clip_sample else 0
+        a.clip_sample = 1 if scheduler.config.get("clip_sample", False) else 0      # (DPM-Solver++ has none)
         a.eta = float(eta)
         a.set_alpha_to_one = 1 if scheduler.config.get("set_alpha_to_one", True) else 0
         a.steps_offset = int(scheduler.config.get("steps_offset", 0))
@@ -542,6 +544,10 @@ def sample_with_weg(denoiser, scheduler, encoder_hidden_states, cond_masks, focu
         args = dict(locals())
         rest = args.pop("kw")
         return _with_auto_operands(lambda ops: sample_with_weg(**args, **dict(rest, operands=ops)), "auto")
+    if getattr(scheduler, "KIND", None) == 2:
+        raise NotImplementedError("sample_with_weg: the word-excitation-guidance loop (focus_indices) runs with DDPMScheduler / DDIMScheduler; "
+                                  "with DPMSolverMultistepScheduler it has no reference trajectory to be checked against -- use sample() "
+                                  "without focus_indices")
     from . import weg
     G = guidance_chunks
     scheduler.set_timesteps(num_inference_steps)

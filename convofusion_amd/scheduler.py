@@ -4,7 +4,7 @@ convofusion/models/modeltype/convofusion.py:104-106,419-423,544,574 and unbounde
 
 diffusers is a third-party dependency that is neither vendored in the reference nor installed here;
 these classes restate its public surface for the epsilon-prediction / fixed_small / clip_sample
-configuration.  Tables are built with the same torch float32 ops diffusers uses; ``step`` and
+configuration, and DPMSolverMultistepScheduler in its default (DPM-Solver++ 2M) configuration.  Tables are built with the same torch float32 ops diffusers uses; ``step`` and
 ``add_noise`` run on the device through libcfdenoise (cfd_scheduler_step / cfd_add_noise).  The
 fused sampling loop (convofusion_amd.sampler) reads only the tables and config from these objects.
 """
@@ -190,3 +190,83 @@ class DDIMScheduler(_SchedulerBase):
             raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
         prev, x0 = self._step(model_output, timestep, sample, eta, variance_noise, generator)
         return SchedulerOutput(prev_sample=prev, pred_original_sample=x0) if return_dict else (prev,)
+
+
+class DPMSolverMultistepScheduler(_SchedulerBase):
+    """diffusers 0.14.0 DPMSolverMultistepScheduler in its default configuration: DPM-Solver++ (algorithm_type "dpmsolver++"), second
+    order multistep (solver_order 2, solver_type "midpoint"), first order at the last step of a run shorter than 15 steps
+    (lower_order_final), epsilon prediction, no thresholding.  Deterministic: ``step`` draws nothing.
+
+    ``set_timesteps(N)`` builds 0.14.0's table ``np.linspace(0, T - 1, N + 1).round()[::-1][:-1]`` with numpy itself (np.round takes
+    halves to even; the library is handed this table and never rebuilds it).  ``step`` keeps the previous step's data prediction x0 as a
+    device tensor (``model_outputs``) and runs on the device through cfd_dpmsolver_step; the fused loop (scheduler kind 2) keeps its own
+    history on the device and reads only the table and the config from this object."""
+    KIND = 2
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear", trained_betas=None,
+                 solver_order=2, prediction_type="epsilon", thresholding=False, dynamic_thresholding_ratio=0.995, sample_max_value=1.0,
+                 algorithm_type="dpmsolver++", solver_type="midpoint", lower_order_final=True):
+        for name, value, want in (("solver_order", solver_order, 2), ("algorithm_type", algorithm_type, "dpmsolver++"),
+                                  ("solver_type", solver_type, "midpoint"), ("lower_order_final", lower_order_final, True),
+                                  ("thresholding", thresholding, False), ("prediction_type", prediction_type, "epsilon")):
+            if value != want:
+                raise NotImplementedError(f"DPMSolverMultistepScheduler: only {name}={want!r} (diffusers 0.14.0's default) is implemented, "
+                                          f"not {value!r}")
+        self.config = _Config(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
+                              beta_schedule=beta_schedule, trained_betas=trained_betas, solver_order=solver_order,
+                              prediction_type=prediction_type, thresholding=thresholding,
+                              dynamic_thresholding_ratio=dynamic_thresholding_ratio, sample_max_value=sample_max_value,
+                              algorithm_type=algorithm_type, solver_type=solver_type, lower_order_final=lower_order_final)
+        self._init_tables(num_train_timesteps, beta_start, beta_end, beta_schedule, trained_betas)
+        self.alpha_t = torch.sqrt(self.alphas_cumprod)
+        self.sigma_t = torch.sqrt(1 - self.alphas_cumprod)
+        self.lambda_t = torch.log(self.alpha_t) - torch.log(self.sigma_t)
+        self.timesteps = torch.from_numpy(np.linspace(0, num_train_timesteps - 1, num_train_timesteps, dtype=np.float32)[::-1].copy())
+        self.model_outputs = [None] * solver_order
+        self.lower_order_nums = 0
+
+    def timestep_table(self, num_inference_steps):
+        """(step count, int64 timestep array) of ``set_timesteps`` without touching the scheduler's state.  N >= num_train_timesteps would
+        repeat entries, on which 0.14.0's ``step`` fails (its index lookup finds two): refused."""
+        n, T = int(num_inference_steps), self.config.num_train_timesteps
+        if n < 1 or n >= T:
+            raise ValueError(f"DPMSolverMultistepScheduler: num_inference_steps = {n} must be in [1, {T}) (num_train_timesteps = {T})")
+        return n, np.linspace(0, T - 1, n + 1).round()[::-1][:-1].copy().astype(np.int64)
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        """Also resets the solver's history: the next ``step`` is first order."""
+        self.num_inference_steps, timesteps = self.timestep_table(num_inference_steps)
+        self.timesteps = torch.from_numpy(timesteps).to(device)
+        self.model_outputs = [None] * self.config.solver_order
+        self.lower_order_nums = 0
+
+    def step(self, model_output, timestep, sample, return_dict=True):
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        if not sample.is_cuda:
+            raise RuntimeError("convofusion_amd schedulers operate on device tensors (no CPU fallback)")
+        ts = [int(v) for v in self.timesteps]
+        t = int(timestep)
+        n = len(ts)
+        i = ts.index(t) if t in ts else n - 1       # (0.14.0: the index by value; an unknown timestep counts as the last)
+        prev_t = 0 if i == n - 1 else ts[i + 1]
+        lower_order_final = i == n - 1 and self.config.lower_order_final and n < 15
+        second = not (self.lower_order_nums < 1 or lower_order_final)
+        t_prev_model = ts[i - 1] if second else -1
+        eps = model_output.detach().to(torch.float32).contiguous()
+        x = sample.detach().to(torch.float32).clone().contiguous()
+        m_prev = self.model_outputs[-1]
+        if second and (m_prev is None or m_prev.shape != x.shape or m_prev.device != x.device):
+            raise ValueError("DPMSolverMultistepScheduler.step: the previous step's output does not match this sample")
+        x0 = torch.empty_like(x)
+        acp, acp_p = self._acp_host()
+        lib = _lib.load()
+        with torch.cuda.device(x.device):
+            _lib.check(lib.cfd_dpmsolver_step(
+                _ops_handle(x.device), acp_p, self.config.num_train_timesteps, t, prev_t, t_prev_model, C.c_void_p(eps.data_ptr()),
+                C.c_void_p(m_prev.data_ptr()) if second else None, C.c_void_p(x.data_ptr()), C.c_void_p(x0.data_ptr()), x.numel(),
+                C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)))
+        self.model_outputs = self.model_outputs[1:] + [x0]
+        if self.lower_order_nums < self.config.solver_order:
+            self.lower_order_nums += 1
+        return SchedulerOutput(prev_sample=x) if return_dict else (x,)

@@ -109,7 +109,10 @@ typedef struct {
   int G;                      /* guidance chunks: 7 (clf_guidance_drops + 1, convofusion.py:60) or 1 */
   float guidance_weight[8];   /* weight of chunk k >= 1 in  e_0 + sum_k w_k (e_k - e_0)
                                  reference: {-, 7.5, 7.5, 7.5, 7.5, 7.5, 0}  (convofusion.py:529-541) */
-  int scheduler;              /* 0 = DDPMScheduler (fixed_small), 1 = DDIMScheduler */
+  int scheduler;              /* 0 = DDPMScheduler (fixed_small), 1 = DDIMScheduler, 2 = DPMSolverMultistepScheduler in diffusers 0.14.0's
+                                 default configuration (dpmsolver++, solver_order 2, midpoint, lower_order_final; no noise): needs
+                                 `timesteps` and clip_sample == 0; eta, set_alpha_to_one and steps_offset are ignored.  The run keeps
+                                 its own x0 history ([B][L][128] float32, allocated by cfd_sample_begin). */
   int num_train_timesteps;    /* 1000 */
   int num_inference_steps;    /* scheduler.set_timesteps(N) */
   int clip_sample;            /* configs/modules/scheduler.yaml:11 */
@@ -138,7 +141,11 @@ typedef struct {
                                  or NULL: (arange(N) * (T // N))[::-1] (+ steps_offset for DDIM), N = num_inference_steps.  The step
                                  formulas keep `prev_t = t - T // N` either way.  Needed for DDPM counts that do not divide T, where
                                  diffusers 0.14.0's table arange(0, T, T // N)[::-1] has MORE than N entries (unpinned, see
-                                 convofusion_amd/scheduler.py); the run then has num_timesteps iterations. */
+                                 convofusion_amd/scheduler.py); the run then has num_timesteps iterations.
+                                 Scheduler 2 (DPM-Solver++) REQUIRES the table -- np.linspace(0, T - 1, N + 1).round()[::-1][:-1], built by
+                                 the scheduler (numpy rounds halves to even; the library never rebuilds it) -- strictly decreasing and in
+                                 [1, T); each step goes to the next entry (to 0 after the last), and its second-order term uses the
+                                 previous entry. */
   int num_timesteps;
   float* att_ring[CFD_NUM_MEM];/* all NULL, or five dev buffers [iterations][B][num_layers][L][S_j] float32: the captured iteration
                                  stores the attention probabilities of the LAST guidance chunk (full conditioning) of iteration i into
@@ -220,13 +227,22 @@ typedef struct {
 int cfd_sample_census(cfd_handle h, cfd_census* out);
 
 /* Stand-alone scheduler ops on device tensors (diffusers 0.14.0 `scheduler.step(...).prev_sample` and
- * `add_noise`), for callers that drive their own loop (unbounded_synthesis.py:75,181). */
+ * `add_noise`), for callers that drive their own loop (unbounded_synthesis.py:75,181).  cfd_scheduler_step takes scheduler 0 (DDPM)
+ * or 1 (DDIM) and refuses any other kind with CFD_E_ARG: DPM-Solver++ keeps a history and has its own entry, cfd_dpmsolver_step. */
 int cfd_scheduler_step(cfd_handle h, int scheduler, const float* alphas_cumprod, int num_train_timesteps,
                        int num_inference_steps, int t, int clip_sample, float eta, int set_alpha_to_one,
                        const float* model_output, const float* noise, float* sample_inout, size_t numel,
                        float* pred_original_sample /* dev [numel] or NULL: the (clipped) x0 estimate the step forms,
                        SchedulerOutput.pred_original_sample (read at convofusion.py:619) */,
                        void* stream);
+/* Stand-alone DPM-Solver++ (2M) step (diffusers 0.14.0 DPMSolverMultistepScheduler.step, default configuration) on device tensors, for
+ * callers that drive their own loop; the caller keeps the history.  x0_out (dev [numel]) receives this step's data prediction
+ * x0 = (x - sigma_t eps) / alpha_t -- the m_prev of the next step -- and sample_inout the update from t to prev_t (0 after the last
+ * table entry).  t_prev_model: the timestep of the previous step (whose x0 is m_prev) for a second-order step, -1 for a first-order
+ * step (m_prev may then be NULL).  alphas_cumprod is HOST float32 [num_train_timesteps].  Shares its coefficients with the
+ * sampling loop's scheduler kind 2. */
+int cfd_dpmsolver_step(cfd_handle h, const float* alphas_cumprod, int num_train_timesteps, int t, int prev_t, int t_prev_model,
+                       const float* model_output, const float* m_prev, float* sample_inout, float* x0_out, size_t numel, void* stream);
 int cfd_add_noise(cfd_handle h, const float* alphas_cumprod_host, int t, const float* original,
                   const float* noise, float* out, size_t numel, void* stream);
 

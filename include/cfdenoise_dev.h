@@ -24,6 +24,12 @@ int cfd_debug_stop_stage(cfd_handle h, int stage);
 /* Micro-benchmark: average ms of `iters` launches of the [J x K] x [512 x K]^T residual GEMM (I must be 512). */
 int cfd_bench_gemm(cfd_handle h, int I, int J, int K, int tile_cfg, int iters, float* ms_out);
 int cfd_debug_read(cfd_handle h, const char* what, float* dst_dev, size_t numel);
+/* Test hook (no handle, no device): the per-iteration coefficient rows a sampling run of scheduler `kind` (cfd_sample_args.scheduler)
+ * over the HOST timestep table timesteps[0..N) uploads -- out HOST float32 [N][8], per row: sigma_t, alpha_t, c0, cx, sigma, use_noise,
+ * order, 1/r0 (csrc/rows.hpp StepCoef; kind 2: c0 = sigma_prev / sigma_t, cx = alpha_prev (exp(-h) - 1)).  alphas_cumprod HOST
+ * float32 [T]; n_inf: the count given to set_timesteps (DDPM / DDIM stride).  Fails with CFD_E_ARG where cfd_sample_begin would. */
+int cfd_test_step_coefficients(int kind, const float* alphas_cumprod, int T, int n_inf, const int32_t* timesteps, int N, float eta,
+                               int set_alpha_to_one, float* out);
 
 #ifdef __cplusplus
 }

@@ -23,7 +23,7 @@ SYMBOLS = [
     "cfd_test_gemm", "cfd_debug_stop_stage", "cfd_debug_read", "cfd_bench_gemm", "cfd_linear_act",
     "cfd_layer_norm", "cfd_mha", "cfd_add", "cfd_zero_rows", "cfd_gemm_f32", "cfd_softmax", "cfd_softmax_bwd",
     "cfd_layer_norm_bwd", "cfd_ew", "cfd_weg_focus", "cfd_sample_write", "cfd_sample_inpaint", "cfd_weg_eval", "cfd_dyadic_steps",
-    "cfd_sample_census", "cfd_dpmsolver_step", "cfd_test_step_coefficients",
+    "cfd_sample_census", "cfd_dpmsolver_step", "cfd_test_step_coefficients", "cfd_test_gemm_epi",
 ]
 
 
@@ -78,6 +78,18 @@ class Census(C.Structure):
 class WegArgs(C.Structure):
     _fields_ = [("B", C.c_int), ("L", C.c_int), ("timestep", C.c_int), ("latents", C.c_void_p), ("mem", Memory * NUM_MEM),
                 ("tok_off", C.c_void_p), ("tok_idx", C.c_void_p), ("last", C.c_int), ("kernel3", C.c_float * 3), ("reuse_memory_side", C.c_int)]
+
+
+# cfd_test_epi_args.kind (include/cfdenoise_dev.h)
+EPI_F32, EPI_SPLIT, EPI_RESID, EPI_RESID_STAT, EPI_QKVT, EPI_LN_F32, EPI_LN_SPLIT, EPI_LN_QKVT = range(8)
+
+
+class TestEpiArgs(C.Structure):
+    """cfd_test_epi_args: one launch of the split-pair GEMM with one of the product's epilogues (cfd_test_gemm_epi)."""
+    _fields_ = [("kind", C.c_int), ("I", C.c_int), ("J", C.c_int), ("K", C.c_int), ("tile_cfg", C.c_int), ("gelu", C.c_int),
+                ("perm32", C.c_int), ("natural", C.c_int), ("X", C.c_void_p), ("Y", C.c_void_p), ("y_sp", C.c_void_p),
+                ("bias", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("ln_stat", C.c_void_p), ("ln_eps", C.c_float),
+                ("x", C.c_void_p), ("out", C.c_void_p), ("out2", C.c_void_p), ("stat", C.c_void_p), ("tile_cfg_used", C.c_int)]
 
 
 _lib = None
@@ -160,6 +172,7 @@ def load():
     lib.cfd_profile_forward.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int)]
     lib.cfd_test_gemm.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                   C.c_int, C.c_void_p]
+    lib.cfd_test_gemm_epi.argtypes = [C.c_void_p, C.POINTER(TestEpiArgs), C.c_void_p]
     lib.cfd_bench_gemm.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]
     lib.cfd_linear_act.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                    C.c_void_p, C.c_void_p]

@@ -188,7 +188,7 @@ __global__ void __launch_bounds__(256) ln_fold_rows_kernel(const float* W, const
   }
   if (threadIdx.x == 0) { cvec[r] = (float)red[0][0]; dvec[r] = (float)red[1][0]; }
 }
-static int ln_fold_weight(Ctx* c, const float* W, int R, int K, const float* gamma, const float* beta, DBuf& tmp, DBuf& dst_sp, float* cvec, float* dvec) {
+int ln_fold_weight(Ctx* c, const float* W, int R, int K, const float* gamma, const float* beta, DBuf& tmp, DBuf& dst_sp, float* cvec, float* dvec) {
   CHK(tmp.ensure((size_t)R * K * 4));
   hipLaunchKernelGGL(ln_fold_rows_kernel<>, dim3(R), dim3(256), 0, 0, W, gamma, beta, tmp.as<float>(), cvec, dvec, K);
   HIPCHK(hipGetLastError());

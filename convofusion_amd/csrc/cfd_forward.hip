@@ -725,6 +725,114 @@ extern "C" int cfd_test_gemm(cfd_handle c, const float* X, const float* Y, float
   return CFD_OK;
 }
 
+// One launch of the split-pair GEMM with one of the product's epilogues (include/cfdenoise_dev.h).  Only instances the product launches
+// are used: the fold's producer and consumers go through launch_gemm_midsize, the other kinds through launch_gemm with any class.
+extern "C" int cfd_test_gemm_epi(cfd_handle c, cfd_test_epi_args* t, void* stream) {
+  if (!c || !t) return fail(CFD_E_ARG, "null argument");
+  const int kind = t->kind, I = t->I, J = t->J, K = t->K;
+  if (kind < CFD_EPI_F32 || kind > CFD_EPI_LN_QKVT) return fail(CFD_E_ARG, "unknown epilogue kind %d", kind);
+  const bool fold = kind >= CFD_EPI_LN_F32, qkvt = kind == CFD_EPI_QKVT || kind == CFD_EPI_LN_QKVT;
+  const bool resid = kind == CFD_EPI_RESID || kind == CFD_EPI_RESID_STAT, split = kind == CFD_EPI_SPLIT || kind == CFD_EPI_LN_SPLIT;
+  if (K < 32 || K % 32) return fail(CFD_E_ARG, "K = %d: a positive multiple of 32", K);
+  if (J < 1 || I < 4) return fail(CFD_E_ARG, "bad shape I = %d, J = %d", I, J);
+  if (!t->X || (!t->Y && !t->y_sp)) return fail(CFD_E_ARG, "null operand");
+  if (resid && I != CFD_D) return fail(CFD_E_ARG, "the residual epilogues have rows of %d features (I = %d)", CFD_D, I);
+  if (qkvt && I != 3 * CFD_D) return fail(CFD_E_ARG, "q | k | v^T has I = %d (I = %d)", 3 * CFD_D, I);
+  if (qkvt && J % 16) return fail(CFD_E_ARG, "q | k | v^T stores batch rows of 16 tokens (J = %d)", J);
+  if (split && I % 32) return fail(CFD_E_ARG, "split-pair rows are whole 32-column blocks (I = %d)", I);
+  if (I % 4) return fail(CFD_E_ARG, "the epilogues store 4 consecutive features (I = %d)", I);
+  if (resid ? !t->x || (kind == CFD_EPI_RESID_STAT && (!t->out || !t->stat)) : !t->out) return fail(CFD_E_ARG, "null output");
+  if (qkvt && (!t->out2 || !t->bias)) return fail(CFD_E_ARG, "q | k | v^T needs out2 and the bias");
+  if (fold && (!t->gamma || !t->beta || !t->ln_stat)) return fail(CFD_E_ARG, "the fold needs gamma, beta and ln_stat");
+  HIPCHK(hipSetDevice(c->cfg.device));
+  hipStream_t st = (hipStream_t)stream;
+  struct Tmp {
+    DBuf xs, ys, wf, cd;
+    ~Tmp() { xs.release(); ys.release(); wf.release(); cd.release(); }
+  } tmp;
+  if (fold) {   // the product's weight side: W' = W diag(gamma) as split pairs, c = W' 1, d = W beta
+    CHK(tmp.cd.ensure((size_t)2 * I * 4));
+    CHK(ln_fold_weight(c, t->X, I, K, t->gamma, t->beta, tmp.wf, tmp.xs, tmp.cd.as<float>(), tmp.cd.as<float>() + I));
+    HIPCHK(hipStreamSynchronize(nullptr));
+  } else {
+    CHK(tmp.xs.ensure((size_t)I * K * 4));
+    CHK(enqueue_to_split(c, CFD_PROF_OTHER, st, t->X, tmp.xs.as<char>(), (long long)I, K, (long long)K, (long long)K * 4, nullptr));
+  }
+  const char* y = reinterpret_cast<const char*>(t->y_sp);
+  if (!y) {
+    CHK(tmp.ys.ensure((size_t)J * K * 4));
+    CHK(enqueue_to_split(c, CFD_PROF_OTHER, st, t->Y, tmp.ys.as<char>(), (long long)J, K, (long long)K, (long long)K * 4, nullptr));
+    y = tmp.ys.as<char>();
+  }
+  GemmArgs a = gemm_args();
+  const int I0 = qkvt ? 2 * CFD_D : I;
+  a.X[0] = tmp.xs.as<char>(); a.ldx[0] = (long long)K * 4; a.I[0] = I0; a.Iclamp[0] = I0; a.kt[0] = K / 32;
+  if (qkvt) {
+    a.nslot = 2;
+    a.X[1] = tmp.xs.as<char>() + (size_t)I0 * K * 4; a.ldx[1] = (long long)K * 4; a.I[1] = CFD_D; a.Iclamp[1] = CFD_D; a.kt[1] = K / 32;
+  }
+  a.Y = y; a.ldy = (long long)K * 4; a.J = J; a.Jclamp = J;
+  const float* cd = tmp.cd.as<float>();
+  auto fold_of = [&](auto& el) {
+    el.ln_stat = t->ln_stat; el.ln_eps = t->ln_eps;
+    el.ln_c[0] = el.ln_c[1] = cd; el.ln_d[0] = el.ln_d[1] = cd + I;
+    if (qkvt) { el.ln_c[1] = cd + I0; el.ln_d[1] = cd + I + I0; }
+  };
+  auto plain = [&](const auto& e) -> hipError_t {
+    const int cfg = t->tile_cfg ? t->tile_cfg : gemm_auto_cfg<MODE_PLAIN>(a, 1, 1);
+    t->tile_cfg_used = g_cfd_naive_gemm ? 0 : (cfg == 1 || cfg == 6 || cfg == 19 || cfg == 20 || cfg == 24) ? cfg : 3;
+    return launch_gemm<MODE_PLAIN>(a, e, 1, 1, st, cfg);
+  };
+  EpiF32 ef;
+  memset(&ef, 0, sizeof(ef));
+  ef.out = reinterpret_cast<float*>(t->out); ef.ldo = I; ef.bias = t->bias;
+  EpiSplit es{reinterpret_cast<char*>(t->out), (long long)I * 4, 0, 0, t->bias, t->gelu, t->perm32};
+  EpiQkvT eq{reinterpret_cast<char*>(t->out), (long long)I0 * 4, t->bias, reinterpret_cast<char*>(t->out2), t->natural};
+  hipError_t err = hipSuccess;
+  switch (kind) {
+    case CFD_EPI_F32: err = plain(ef); break;
+    case CFD_EPI_SPLIT: err = plain(es); break;
+    case CFD_EPI_RESID: err = plain(EpiResid{t->x, 0, t->bias}); break;
+    case CFD_EPI_RESID_STAT:
+      t->tile_cfg_used = gemm_midsize_cfg<MODE_PLAIN>(a);
+      err = launch_gemm_midsize<MODE_PLAIN>(a, EpiResidStat{t->x, 0, t->bias, reinterpret_cast<char*>(t->out), t->stat}, st);
+      break;
+    case CFD_EPI_QKVT: {
+      const int cfg = t->tile_cfg ? t->tile_cfg : gemm_auto_cfg<MODE_GROUPED>(a, 1, 1);
+      t->tile_cfg_used = g_cfd_naive_gemm ? 0 : (cfg == 1 || cfg == 6 || cfg == 19 || cfg == 20 || cfg == 24) ? cfg : 3;
+      err = launch_gemm<MODE_GROUPED>(a, eq, 1, 1, st, cfg);
+      break;
+    }
+    case CFD_EPI_LN_F32: {
+      EpiLn<EpiF32> el;
+      static_cast<EpiF32&>(el) = ef;
+      fold_of(el);
+      t->tile_cfg_used = gemm_midsize_cfg<MODE_PLAIN>(a);
+      err = launch_gemm_midsize<MODE_PLAIN>(a, el, st);
+      break;
+    }
+    case CFD_EPI_LN_SPLIT: {
+      EpiLn<EpiSplit> el;
+      static_cast<EpiSplit&>(el) = es;
+      fold_of(el);
+      t->tile_cfg_used = gemm_midsize_cfg<MODE_PLAIN>(a);
+      err = launch_gemm_midsize<MODE_PLAIN>(a, el, st);
+      break;
+    }
+    default: {
+      EpiLn<EpiQkvT> el;
+      static_cast<EpiQkvT&>(el) = eq;
+      fold_of(el);
+      t->tile_cfg_used = gemm_midsize_cfg<MODE_GROUPED>(a);
+      err = launch_gemm_midsize<MODE_GROUPED>(a, el, st);
+      break;
+    }
+  }
+  if (err != hipSuccess) return fail(CFD_E_HIP, "gemm launch failed: %s", hipGetErrorString(err));
+  HIPCHK(hipStreamSynchronize(st));
+  return CFD_OK;
+}
+
 // Micro-benchmark hook: `iters` launches of the MFMA GEMM (EpiResid epilogue: x[j][i] += D + bias) on device-resident
 // SP operands filled from a float32 pattern; returns the average milliseconds per launch (HIP events).
 extern "C" int cfd_bench_gemm(cfd_handle c, int I, int J, int K, int tile_cfg, int iters, float* ms_out) {

@@ -440,6 +440,8 @@ __global__ void add_noise_kernel(const float* x0, const float* noise, float* out
 int to_sp(Ctx* c, const float* src, long long R, int K, DBuf& dst, long long dst_rows = -1);
 // float32 [R][K] (row pitch ld_src floats) -> split pairs (row pitch ld_dst bytes); `sat`: the census counter of the values' class, or null
 int enqueue_to_split(Ctx* c, int cls, hipStream_t st, const float* src, char* dst, long long R, int K, long long ld_src, long long ld_dst, unsigned int* sat);
+// the LayerNorm fold's weight side (cfd_core.hip, null stream): dst_sp = split(W diag(gamma)) [R][K], cvec = W' 1, dvec = W beta; tmp: scratch
+int ln_fold_weight(Ctx* c, const float* W, int R, int K, const float* gamma, const float* beta, DBuf& tmp, DBuf& dst_sp, float* cvec, float* dvec);
 // cfd_problem.hip: work lists, problem set-up, timestep tables, memory-side projections
 int build_xattn_worklist(Ctx* c, const cfd_memory mem[CFD_NMEM]);
 int build_xattn_layer0_lists(Ctx* c, const cfd_memory mem[CFD_NMEM]);

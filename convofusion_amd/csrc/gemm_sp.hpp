@@ -749,7 +749,8 @@ __device__ __forceinline__ void gemm_sp_body(const GemmArgs& a, const Epi& epi, 
       stage(1, 1);
       ln_finish(std::integral_constant<int, 2 * GPW>{});
       asm volatile("s_waitcnt vmcnt(%0)" ::"n"(GPW) : "memory");
-    } else {
+    } else {   // (one k-tile: the statistics are still put together, behind the one stage's requests)
+      ln_finish(std::integral_constant<int, GPW>{});
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     __builtin_amdgcn_s_barrier();
@@ -988,6 +989,31 @@ static hipError_t launch_cfg(GemmArgs a, const Epi& epi, int nb, int nz, hipStre
 //  24 = 128 x 64  (2 x 2 waves of 64 x 32, 3-stage)            small problems with more than 768 tiles of 64 x 64
 // The variants measured and rejected in round 1 (3-stage / software-pipelined / deep-prefetch / single-buffer loops,
 // 128 x 256, 256 x 128, 128 x 176 and 256 x 176 tiles, the tile-softmax epilogues) live in tools/experiments/gemm_sp_r01_variants.hpp.
+// The class launch_gemm takes for cfg = 0 (a.nslot >= 1).
+template <int MODE>
+static int gemm_auto_cfg(const GemmArgs& a, int nb, int nz) {
+  const int ng = (MODE == MODE_GROUPED) ? a.nslot : 1;
+  long long big_tiles = 0;
+  for (int g = 0; g < ng; ++g) big_tiles += (long long)((a.I[g] + 127) / 128) * ((a.J + 255) / 256);
+  big_tiles *= (long long)nb * nz;
+  int imax = 0;
+  for (int g = 0; g < ng; ++g) imax = a.I[g] > imax ? a.I[g] : imax;
+  int cfg;
+  if (a.J <= 16) cfg = 3;
+  else if (imax <= 64 && a.J >= 96) cfg = 20;
+  else if (a.J > 128 && a.J <= 224 && big_tiles * 2 >= 256) cfg = 6;
+  else if (big_tiles * 2 >= 384 && a.J >= 96) cfg = 1;
+  else cfg = 19;
+  // more 64 x 64 tiles than the chip holds at once (3 per CU) but too few for the 128 x 128 class: 128 x 64 tiles, one round of two per CU
+  // (the q | k and FFN1 products of 32 utterances at the product shape: 896 tiles -> 448; 21 -> 19 us in the captured step, round 5)
+  if (cfg == 19 && nb * nz == 1) {
+    long long t64 = 0;
+    for (int g = 0; g < ng; ++g) t64 += (long long)((a.I[g] + 63) / 64) * ((a.J + 63) / 64);
+    if (t64 > 768 && imax >= 128) cfg = 24;
+  }
+  return cfg;
+}
+
 template <int MODE, class Epi>
 static hipError_t launch_gemm(GemmArgs a, const Epi& epi, int nb, int nz, hipStream_t st, int cfg = 0) {
   if (a.nslot < 1) a.nslot = 1;
@@ -1001,26 +1027,7 @@ static hipError_t launch_gemm(GemmArgs a, const Epi& epi, int nb, int nz, hipStr
     }
     return hipGetLastError();
   }
-  if (cfg == 0) {
-    const int ng = (MODE == MODE_GROUPED) ? a.nslot : 1;
-    long long big_tiles = 0;
-    for (int g = 0; g < ng; ++g) big_tiles += (long long)((a.I[g] + 127) / 128) * ((a.J + 255) / 256);
-    big_tiles *= (long long)nb * nz;
-    int imax = 0;
-    for (int g = 0; g < ng; ++g) imax = a.I[g] > imax ? a.I[g] : imax;
-    if (a.J <= 16) cfg = 3;
-    else if (imax <= 64 && a.J >= 96) cfg = 20;
-    else if (a.J > 128 && a.J <= 224 && big_tiles * 2 >= 256) cfg = 6;
-    else if (big_tiles * 2 >= 384 && a.J >= 96) cfg = 1;
-    else cfg = 19;
-    // more 64 x 64 tiles than the chip holds at once (3 per CU) but too few for the 128 x 128 class: 128 x 64 tiles, one round of two per CU
-    // (the q | k and FFN1 products of 32 utterances at the product shape: 896 tiles -> 448; 21 -> 19 us in the captured step, round 5)
-    if (cfg == 19 && nb * nz == 1) {
-      long long t64 = 0;
-      for (int g = 0; g < ng; ++g) t64 += (long long)((a.I[g] + 63) / 64) * ((a.J + 63) / 64);
-      if (t64 > 768 && imax >= 128) cfg = 24;
-    }
-  }
+  if (cfg == 0) cfg = gemm_auto_cfg<MODE>(a, nb, nz);
   switch (cfg) {
     case 1: return launch_cfg<2, 2, 4, 4, 2, MODE, Epi>(a, epi, nb, nz, st);
     case 6: return launch_cfg<4, 1, 2, 7, 2, MODE, Epi>(a, epi, nb, nz, st);
@@ -1034,9 +1041,8 @@ static hipError_t launch_gemm(GemmArgs a, const Epi& epi, int nb, int nz, hipStr
 // The launches of the LayerNorm fold (EpiResidStat producers, EpiLn<E> consumers): un-batched mid-size problems, for which launch_gemm
 // above picks the 64 x 64 class or, with more than 768 such tiles, the 128 x 64 class (cfd_forward.hip checks the range) -- only these
 // two are instantiated for the fold's epilogues.
-template <int MODE, class Epi>
-static hipError_t launch_gemm_midsize(GemmArgs a, const Epi& epi, hipStream_t st) {
-  if (a.nslot < 1) a.nslot = 1;
+template <int MODE>
+static int gemm_midsize_cfg(const GemmArgs& a) {   // 24 (128 x 64) or 19 (64 x 64); a.nslot >= 1
   const int ng = (MODE == MODE_GROUPED) ? a.nslot : 1;
   long long t64 = 0;
   int imax = 0;
@@ -1044,6 +1050,11 @@ static hipError_t launch_gemm_midsize(GemmArgs a, const Epi& epi, hipStream_t st
     t64 += (long long)((a.I[g] + 63) / 64) * ((a.J + 63) / 64);
     imax = a.I[g] > imax ? a.I[g] : imax;
   }
-  if (t64 > 768 && imax >= 128) return launch_cfg<2, 2, 4, 2, 3, MODE, Epi>(a, epi, 1, 1, st);
+  return t64 > 768 && imax >= 128 ? 24 : 19;
+}
+template <int MODE, class Epi>
+static hipError_t launch_gemm_midsize(GemmArgs a, const Epi& epi, hipStream_t st) {
+  if (a.nslot < 1) a.nslot = 1;
+  if (gemm_midsize_cfg<MODE>(a) == 24) return launch_cfg<2, 2, 4, 2, 3, MODE, Epi>(a, epi, 1, 1, st);
   return launch_cfg<2, 2, 2, 2, 3, MODE, Epi>(a, epi, 1, 1, st);
 }

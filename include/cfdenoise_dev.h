@@ -11,11 +11,48 @@ extern "C" {
 
 /* Test hook: D[j][i] = sum_k X[i][k] Y[j][k] through the split-pair (fp16 hi/lo, 3 MFMAs per product) kernel.
  * X dev float32 [I][K], Y dev float32 [J][K], out dev float32 [J][I]; K % 32 == 0, I % 4 == 0.
- * tile_cfg: 0 = chosen from the shape; 1 = 128x128 (2-stage), 30 = 128x128 with the asymmetric ring (weights 2 stages,
- * activations 3 stages), 6 = 128x112, 19 = 64x64 (3-stage), 20 = 32x128 (3-stage), any other value = 128x16
- * (csrc/gemm_sp.hpp: launch_gemm). */
+ * tile_cfg: 0 = chosen from the shape; 1 = 128x128 (2-stage), 6 = 128x112 (2-stage), 19 = 64x64 (3-stage), 20 = 32x128 (3-stage),
+ * 24 = 128x64 (3-stage), any other value = 128x16 (2-stage) (csrc/gemm_sp.hpp: launch_gemm). */
 int cfd_test_gemm(cfd_handle h, const float* X, const float* Y, float* out, int I, int J, int K, int tile_cfg,
                   void* stream);
+
+/* Test hook: one launch of the split-pair GEMM D[j][i] = sum_k X[i][k] Y[j][k] with one of the product's epilogues (csrc/gemm_sp.hpp).
+ * The float32 operands are split as cfd_test_gemm splits them; split-pair outputs are returned as stored (per row and 32-column block:
+ * 64 bytes of hi, then 64 bytes of lo), not decoded.  Synchronizes before returning. */
+enum {
+  CFD_EPI_F32 = 0,         /* out f32 [J][I] = D + bias                                                                         */
+  CFD_EPI_SPLIT = 1,       /* out SP [J][I] = split(act(D + bias)); act = GELU if gelu; perm32: the P-fragment column order     */
+  CFD_EPI_RESID = 2,       /* x f32 [J][512] += D + bias                                                                        */
+  CFD_EPI_RESID_STAT = 3,  /* EPI_RESID + out SP [J][512] = split(x_new) + stat f32 [J][16][2] = (mean, M2) per 32-column slot  */
+  CFD_EPI_QKVT = 4,        /* grouped, I = 1536: rows 0..1023 of X -> out SP [J][1024] = split(D + bias); rows 1024..1535 ->
+                              out2 SP [J/16][512][32] = the value projection transposed (key order: natural, else 4q+r -> 8q+r) */
+  CFD_EPI_LN_F32 = 5,      /* the LayerNorm fold: D taken as X LN(y; gamma, beta), then EPI_F32                                */
+  CFD_EPI_LN_SPLIT = 6,    /* the fold, then EPI_SPLIT                                                                          */
+  CFD_EPI_LN_QKVT = 7      /* the fold (per group), then EPI_QKVT                                                               */
+};
+typedef struct cfd_test_epi_args {
+  int kind;                /* CFD_EPI_*                                                                                         */
+  int I, J, K;             /* K % 32 == 0; EPI_RESID*: I = 512; EPI_*QKVT: I = 1536, J % 16 == 0; split-pair outputs: I % 32 == 0;
+                              EPI_*F32: I % 4 == 0                                                                              */
+  int tile_cfg;            /* F32 / SPLIT / RESID / QKVT: the launch_gemm class (as cfd_test_gemm; 0 = the product's choice).
+                              RESID_STAT and the LN kinds ignore it: they go through launch_gemm_midsize, as in the product      */
+  int gelu, perm32, natural;
+  const float* X;          /* dev f32 [I][K]; LN kinds: W before the fold (the hook folds gamma / beta into it)                */
+  const float* Y;          /* dev f32 [J][K] (ignored if y_sp is set)                                                           */
+  const void* y_sp;        /* optional dev SP [J][K]: the column operand as stored, e.g. a RESID_STAT launch's out              */
+  const float* bias;       /* dev f32 [I] or null (EPI_*QKVT: required, [1024])                                                 */
+  const float* gamma;      /* LN kinds: dev f32 [K]                                                                             */
+  const float* beta;       /* LN kinds: dev f32 [K]                                                                             */
+  const float* ln_stat;    /* LN kinds: dev f32 [J][16][2] per-row slot statistics (as RESID_STAT writes them)                  */
+  float ln_eps;
+  float* x;                /* EPI_RESID*: dev f32 [J][512], updated in place                                                    */
+  void* out;               /* dev: see the kinds                                                                                */
+  void* out2;              /* EPI_*QKVT: dev SP [J/16][512][32]                                                                 */
+  float* stat;             /* EPI_RESID_STAT: dev f32 [J][16][2]                                                                */
+  int tile_cfg_used;       /* out: the class launched (1, 3, 6, 19, 20 or 24)                                                   */
+} cfd_test_epi_args;
+/* Fails with CFD_E_ARG, before any launch, where an argument breaks the constraints above. */
+int cfd_test_gemm_epi(cfd_handle h, cfd_test_epi_args* args, void* stream);
 
 /* Test hooks: stop the forward pipeline after tap point `stage` (0 = off; 1 = after the latent embedding;
  * 2+4l / 3+4l / 4+4l / 5+4l = layer l after self-attention / time block 1 / cross-attention / the layer),

@@ -41,6 +41,12 @@ def test_struct_layouts_match_header():
     assert _lib.SampleArgs.timesteps.offset == _lib.SampleArgs.mem.offset + 5 * 32 + 8   # (8-aligned pointer behind the two ints)
     assert _lib.SampleArgs.att_ring.offset == _lib.SampleArgs.timesteps.offset + 16      # (pointer, int, padding; then the five ring pointers)
     assert _lib.SampleArgs.operand_policy.offset == _lib.SampleArgs.att_ring.offset + 5 * 8   # (int + tail padding to the struct's 8-byte alignment)
+    E = _lib.TestEpiArgs                                                  # cfd_test_epi_args: eight ints, then 8-aligned pointers
+    assert [getattr(E, f).offset for f in ("kind", "natural", "X", "Y", "y_sp", "bias", "gamma", "beta", "ln_stat", "ln_eps")] == \
+        [0, 28, 32, 40, 48, 56, 64, 72, 80, 88]
+    assert [getattr(E, f).offset for f in ("x", "out", "out2", "stat", "tile_cfg_used")] == [96, 104, 112, 120, 128]   # (float + padding)
+    assert C.sizeof(E) == 136                                             # (int + tail padding)
+    assert (_lib.EPI_F32, _lib.EPI_RESID_STAT, _lib.EPI_LN_QKVT) == (0, 3, 7)
 
 
 def test_weg_host_logic():

@@ -1,8 +1,8 @@
 // Common types and helpers for the ConvoFusion denoising-loop kernels (gfx950 / CDNA4 only).
 //
 // Numeric format used by every GEMM operand ("split pair", SP): a float32 value v is carried as two 16-bit
-// floats hi = f16(v), lo = f16(v - hi) (fp16 by default, bf16 with -DCFD_SPLIT_F16=0); a product a*b is issued as
-// THREE MFMAs (a_lo*b_hi + a_hi*b_lo + a_hi*b_hi) with fp32 accumulation: ~2^-22 (fp16) / 2^-16 (bf16) relative
+// floats hi = f16(v), lo = f16(v - hi) (IEEE half); a product a*b is issued as
+// THREE MFMAs (a_lo*b_hi + a_hi*b_lo + a_hi*b_hi) with fp32 accumulation: ~2^-22 relative
 // operand error, i.e. fp32-class results from the 16-bit matrix cores.  (The reference's 1e-3 budget on the final
 // latents cannot be met with plain bf16 operands: SURVEY.md fact 8; measurements: DESIGN.md section 2.)
 //
@@ -21,19 +21,10 @@
 #define CFD_NMEM 5       // spkemb, alsn, tlsn, apb, lsnemb (denoiser.py:220)
 #define CFD_MAX_LAYERS 16
 
-// Element type of the split pair.  CFD_SPLIT_F16=1 (default): two IEEE half floats (11+11 significant
-// bits, ~2^-22 operand error; inputs are saturated to +-65504); CFD_SPLIT_F16=0: two bfloat16 (8+8 bits,
-// ~2^-16, full float32 range).  Both run on the same-rate v_mfma_f32_16x16x32_{f16,bf16}.
-#ifndef CFD_SPLIT_F16
-#define CFD_SPLIT_F16 1
-#endif
-#if CFD_SPLIT_F16
+// Element type of the split pair: two IEEE half floats (11+11 significant bits, ~2^-22 operand error; inputs are saturated
+// to +-65504).  A bfloat16 pair (8+8 bits, ~2^-16) runs at the same MFMA rate but misses the budget.
 typedef _Float16 sp_t;
 #define SP_MFMA __builtin_amdgcn_mfma_f32_16x16x32_f16
-#else
-typedef __bf16 sp_t;
-#define SP_MFMA __builtin_amdgcn_mfma_f32_16x16x32_bf16
-#endif
 typedef __attribute__((ext_vector_type(8))) sp_t spx8;   // 8 halves = one MFMA operand fragment per lane
 typedef __attribute__((ext_vector_type(4))) sp_t spx4;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
@@ -42,9 +33,7 @@ typedef const __attribute__((address_space(1))) void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
 
 __device__ __forceinline__ void split_f32(float v, sp_t& hi, sp_t& lo) {
-#if CFD_SPLIT_F16
   v = __builtin_amdgcn_fmed3f(v, -65504.0f, 65504.0f);
-#endif
   hi = (sp_t)v;
   lo = (sp_t)(v - (float)hi);
 }
@@ -92,31 +81,6 @@ __device__ __forceinline__ void sp_store8(char* row_base, int col, const float* 
   char* p = row_base + (size_t)(col >> 5) * 128 + (col & 31) * 2;
   *reinterpret_cast<spx8*>(p) = h;
   *reinterpret_cast<spx8*>(p + 64) = l;
-}
-
-// Developer experiment (-DCFD_SPLIT_SC1=1, round 5): the split-pair OUTPUT of a product stored write-through (`sc1`: the line leaves the
-// XCD's L2 instead of staying in it), to see whether the 2.17 x over-fetch of the N = 1024 products' operand panels is their own output
-// evicting them.  Off in the product.
-#ifndef CFD_SPLIT_SC1
-#define CFD_SPLIT_SC1 0
-#endif
-__device__ __forceinline__ void sp_store8_out(char* row_base, int col, const float* v) {
-#if CFD_SPLIT_SC1
-  typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
-  spx8 h, l;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    sp_t a, b;
-    split_f32(v[e], a, b);
-    h[e] = a;
-    l[e] = b;
-  }
-  char* p = row_base + (size_t)(col >> 5) * 128 + (col & 31) * 2;
-  asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(p), "v"(__builtin_bit_cast(u32x4_t, h)) : "memory");
-  asm volatile("global_store_dwordx4 %0, %1, off offset:64 sc1" ::"v"(p), "v"(__builtin_bit_cast(u32x4_t, l)) : "memory");
-#else
-  sp_store8(row_base, col, v);
-#endif
 }
 
 // sp_store8 for values that may legitimately be NaN (LayerNorm outputs and probabilities of a row whose softmax had nothing but masked

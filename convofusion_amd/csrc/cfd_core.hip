@@ -59,8 +59,6 @@ extern "C" int cfd_create(const cfd_config* cfg, cfd_handle* out) {
   if (env) c->xa_operands = atoi(env) & 15;
   env = getenv("CFD_LN_FOLD");
   if (env) c->ln_fold = atoi(env);
-  env = getenv("CFD_XA_DB");
-  if (env) c->xa_db = atoi(env) != 0;
   env = getenv("CFD_ONE_KEY");
   if (env) c->one_key = atoi(env) != 0;
   env = getenv("CFD_RT_NFB2_TILES");

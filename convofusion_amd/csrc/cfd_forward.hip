@@ -308,17 +308,9 @@ int enqueue_rows(Ctx* c, hipStream_t st, int row0, int Be) {
   static unsigned long long attr = 0;   // per device (one bit per ordinal): a process may hold handles on several GPUs
   if (!((attr >> (c->cfg.device & 63)) & 1ull)) {
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&self_attn_fused_kernel<>), hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&xattn_fused_kernel<false, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, XA_LDS));
-#if XA_ALL_OPF
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&xattn_fused_kernel<false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, XA_LDS));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&xattn_fused_kernel<false, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, XA_LDS));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&xattn_fused_kernel<false, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, XA_LDS));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&xattn_fused_kernel<false, 7>), hipFuncAttributeMaxDynamicSharedMemorySize, XA_LDS));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&xattn_fused_kernel<false, 11>), hipFuncAttributeMaxDynamicSharedMemorySize, XA_LDS));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&xattn_fused_kernel<false, 15>), hipFuncAttributeMaxDynamicSharedMemorySize, XA_LDS));
-#endif
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&xattn_fused_kernel<false, 15 | XA_DBUF>), hipFuncAttributeMaxDynamicSharedMemorySize, XA_LDS));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&xattn_fused_kernel<true, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, XA_LDS));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&xattn_fused_kernel<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, XA_LDS));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&xattn_fused_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, XA_LDS));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&xattn_fused_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, XA_LDS));
     attr |= 1ull << (c->cfg.device & 63);
   }
 
@@ -397,11 +389,11 @@ int enqueue_rows(Ctx* c, hipStream_t st, int row0, int Be) {
       a.x = c->w->x.as<float>(); a.ln_g = w.ln2g; a.ln_b = w.ln2b; a.bias = w.cross_bias.as<float>(); a.L = L;
       for (int j = 0; j < CFD_NMEM; ++j) {
         const size_t rows = (size_t)p.U[j] * p.Sp[j];
-        // (single-fp16 tiles of a long memory, Problem::xa_opf / xa_f16_mask: 32 KB per 32 keys = 1 KB per key, tile-major per (layer, instance))
-        const bool f16 = (p.xa_f16_mask >> j) & 1;
-        a.K[j] = (f16 && (p.xa_opf & XA_K16)) ? c->w->k16[j].as<char>() + (size_t)l * rows * 1024 : c->w->kall_sp[j].as<char>() + (size_t)l * rows * ROWB;
+        // (single-fp16 tiles of a long memory, Problem::xa_f16 / xa_f16_mask: 32 KB per 32 keys = 1 KB per key, tile-major per (layer, instance))
+        const bool f16 = p.xa_f16 && ((p.xa_f16_mask >> j) & 1);
+        a.K[j] = f16 ? c->w->k16[j].as<char>() + (size_t)l * rows * 1024 : c->w->kall_sp[j].as<char>() + (size_t)l * rows * ROWB;
         a.cb[j] = c->w->cb[j].as<float>() + (size_t)l * rows;
-        a.VT[j] = (f16 && (p.xa_opf & XA_V16)) ? c->w->v16[j].as<char>() + (size_t)l * rows * 1024 : c->w->vt_all[j].as<char>() + (size_t)l * rows * ROWB;
+        a.VT[j] = f16 ? c->w->v16[j].as<char>() + (size_t)l * rows * 1024 : c->w->vt_all[j].as<char>() + (size_t)l * rows * ROWB;
         a.Sp[j] = p.Sp[j];
         const bool stat = (p.static_mask >> j) & 1;
         a.rs_off[j] = (unsigned)((size_t)(nl - l) * rows * 4);
@@ -431,21 +423,10 @@ int enqueue_rows(Ctx* c, hipStream_t st, int row0, int Be) {
         a.census_tau = c->acen_tau;
         c->acen_hits += 1;
       }
-      const int opf = p.att_fused ? 0 : p.xa_opf;
-      const bool xa_db = XA_ALL_OPF ? c->xa_db != 0 : true;   // (developer builds: CFD_XA_DB=0 puts OPF 15 back on the three-barrier step)
-      (void)xa_db;
       auto launch_xa = [&](int nwg, const XAttnArgs& xa) {
-        if (p.att_fused) hipLaunchKernelGGL((xattn_fused_kernel<true, 0>), dim3(nwg), dim3(XA_WAVES * 64), XA_LDS, st, xa);
-#if XA_ALL_OPF
-        else if (opf == 1) hipLaunchKernelGGL((xattn_fused_kernel<false, 1>), dim3(nwg), dim3(XA_WAVES * 64), XA_LDS, st, xa);
-        else if (opf == 2) hipLaunchKernelGGL((xattn_fused_kernel<false, 2>), dim3(nwg), dim3(XA_WAVES * 64), XA_LDS, st, xa);
-        else if (opf == 3) hipLaunchKernelGGL((xattn_fused_kernel<false, 3>), dim3(nwg), dim3(XA_WAVES * 64), XA_LDS, st, xa);
-        else if (opf == 7) hipLaunchKernelGGL((xattn_fused_kernel<false, 7>), dim3(nwg), dim3(XA_WAVES * 64), XA_LDS, st, xa);
-        else if (opf == 11) hipLaunchKernelGGL((xattn_fused_kernel<false, 11>), dim3(nwg), dim3(XA_WAVES * 64), XA_LDS, st, xa);
-        else if (opf == 15 && !xa_db) hipLaunchKernelGGL((xattn_fused_kernel<false, 15>), dim3(nwg), dim3(XA_WAVES * 64), XA_LDS, st, xa);
-#endif
-        else if (opf == 15) hipLaunchKernelGGL((xattn_fused_kernel<false, 15 | XA_DBUF>), dim3(nwg), dim3(XA_WAVES * 64), XA_LDS, st, xa);
-        else hipLaunchKernelGGL((xattn_fused_kernel<false, 0>), dim3(nwg), dim3(XA_WAVES * 64), XA_LDS, st, xa);
+        if (p.att_fused) hipLaunchKernelGGL((xattn_fused_kernel<true, false>), dim3(nwg), dim3(XA_WAVES * 64), XA_LDS, st, xa);
+        else if (p.xa_f16) hipLaunchKernelGGL((xattn_fused_kernel<false, true>), dim3(nwg), dim3(XA_WAVES * 64), XA_LDS, st, xa);
+        else hipLaunchKernelGGL((xattn_fused_kernel<false, false>), dim3(nwg), dim3(XA_WAVES * 64), XA_LDS, st, xa);
       };
       if (l == 0 && share && p.xa0_nwg_a > 0) {   // layer-0 de-duplication (build_xattn_layer0_lists): the longest memory once per distinct (utterance, instance) ...
         XAttnArgs a0 = a;

@@ -97,9 +97,9 @@ struct Problem {
   int xa0_nwg_a = 0, xa0_nwg_b = 0;   // layer-0 de-duplication lists (build_xattn_layer0_lists); 0: one launch
   bool xa_flush = false;               // some work list flushes the accumulator between two online memories (XA_FLUSH): lock-step kernel only
   int xa_one = -1;                     // the one-key memory the fused cross-attention adds as a vector (xattn_fused.hpp, XAttnArgs::one_j), or -1
-  int xa_opf = 0;                      // operand format of the fused cross-attention's key tiles of LONG memories in this problem (XA_V16 | XA_K16; 0: split
-                                       // pairs).  Only a sampling run sets it (cfd_sample_args::operand_policy), and only when every memory is static and no
-                                       // maps are kept
+  bool xa_f16 = false;                 // the fused cross-attention's key / value tiles of LONG memories are single fp16 in this problem (its F16 instance;
+                                       // false: split pairs).  Only a sampling run sets it (cfd_sample_args::operand_policy), and only when every memory is
+                                       // static and no maps are kept
   int xa_f16_mask = 0;                 // bit j: memory j is long enough (XA_F16_MIN_KEYS) for single-fp16 tiles; its segments carry XA_F16
   // memories (bit j) whose folded projections were computed once for the run from the centred static part of the memory
   // (prepare_static_memside); per step they only get their per-key scale and bias (mem_scale_all_kernel)
@@ -149,7 +149,7 @@ struct Work {
   bool fwd_mask[CFD_NMEM] = {false, false, false, false, false}, fwd_map[CFD_NMEM] = {false, false, false, false, false};
   unsigned long long fwd_wver = 0;
   DBuf rt_vt, rt_cbt[CFD_NMEM];   // row-tile path: V^T of the self-attention, per-step key tables
-  DBuf k16[CFD_NMEM], v16[CFD_NMEM];   // single-fp16 key / value tiles of the static memories (xa_pack16_kernel), when pb.xa_opf asks for them
+  DBuf k16[CFD_NMEM], v16[CFD_NMEM];   // single-fp16 key / value tiles of the static memories (xa_pack16_kernel), when pb.xa_f16 asks for them
   DBuf rt_cur;                    // row-tile path, sampling run: this step's rows of every per-step table (rt_step_rows_kernel)
   // What the timestep-only tables of this workspace were built from: the table rows' timesteps and the weights' generation.  temb / AdaLN
   // rows (20 launches) and, per memory, A_l b_t / VV_l b_t (kbtab / vbtab: two products each) depend on nothing else, so a run that
@@ -216,9 +216,8 @@ struct cfd_handle_s {
   bool fused_xattn = true;
   int fused_xattn_min_wgs = 6;
   int one_key = 1;              // CFD_ONE_KEY=0: a one-key memory (lsnemb) keeps its 32-key tile step in the fused cross-attention
-  int want_opf = 0;             // cfd_sample_begin -> setup_problem: the operand policy the run asks for (0 everywhere else)
-  int xa_operands = -1;         // CFD_XA_OPERANDS=<0..3>: overrides cfd_sample_args.operand_policy (developer A/B of the fused cross-attention's tile formats)
-  int xa_db = -1;               // CFD_XA_DB=0 (developer builds, -DXA_ALL_OPF=1): operand policy 15 on the three-barrier step instead of the double-buffered one
+  bool want_f16 = false;        // cfd_sample_begin -> setup_problem: the run asks for single-fp16 tiles (non-zero operand policy; false everywhere else)
+  int xa_operands = -1;         // CFD_XA_OPERANDS=0 / 15: overrides cfd_sample_args.operand_policy (developer A/B of the fused cross-attention's tile formats)
   bool hint_same_mem = false;   // cfd_forward_same_memories: the promise for the NEXT cfd_forward ...
   bool hint_now = false;        // ... taken (and cleared) at that call's very first line, before anything can fail: a call that returns early
                                 // must not leave the promise standing for the call after it

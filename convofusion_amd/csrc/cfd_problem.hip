@@ -313,22 +313,17 @@ int setup_problem(Ctx* c, int Be, int L, const cfd_memory mem[CFD_NMEM], float* 
     p.att_slot[j] = 0;
     p.att_b0 = p.att_nb = 0;      // (a sampling run with an attention ring sets them after this call)
     p.att_fused = false;
-    p.xa_opf = 0; p.xa_f16_mask = 0;
+    p.xa_f16 = false; p.xa_f16_mask = 0;
   }
   p.Sp_tot = off;
   // The run's operand policy (cfd_sample_begin): which memories are long enough for single-fp16 tiles.  The work lists flag their segments
   // (XA_F16); whether the run really takes the single-fp16 kernel instance is decided when everything else about it is known
   // (cfd_sample_begin, prepare_static_memside) -- the pair instance ignores the flag.
-  p.xa_opf = c->want_opf;
-#if !XA_ALL_OPF
-  if (p.xa_opf) p.xa_opf = XA_V16 | XA_K16 | XA_P16 | XA_Q16;    // (the product builds ONE single-fp16 instance: all four bits; xattn_fused.hpp, XA_ALL_OPF)
-#else
-  if (p.xa_opf) p.xa_opf |= XA_V16 | XA_K16;                      // (developer builds: 3, 7, 11, 15 -- the tile formats always together)
-#endif
-  if (p.xa_opf)
+  p.xa_f16 = c->want_f16;
+  if (p.xa_f16)
     for (int j = 0; j < CFD_NMEM; ++j)
       if (p.Sp[j] >= XA_F16_MIN_KEYS) p.xa_f16_mask |= 1 << j;
-  if (!p.xa_f16_mask) p.xa_opf = 0;
+  if (!p.xa_f16_mask) p.xa_f16 = false;
   {  // memories without a key-padding mask get an all-zero one, so the softmax kernel needs no null test
     size_t need = (size_t)Be * L;   // (the un-fused self-attention softmax indexes it per batch row)
     for (int j = 0; j < CFD_NMEM; ++j) need = std::max(need, (size_t)p.U[j] * p.S[j]);
@@ -501,7 +496,7 @@ int prepare_static_memside(Ctx* c, hipStream_t st, int dynamic_mask, bool want_a
     CHK(r);
   }
   const bool fused = p.rt || (c->fused_xattn && p.xa_nwg > 0 && !want_att && !g_cfd_naive_gemm);
-  if (!fused || !c->hoist_memside || p.tmode != 0) { p.xa_opf = 0; return CFD_OK; }
+  if (!fused || !c->hoist_memside || p.tmode != 0) { p.xa_f16 = false; return CFD_OK; }
   const int T = p.T;
   if (c->w->b_tab.bytes < (size_t)T * CFD_D * 4 || c->w->b_sp.bytes < (size_t)T * CFD_D * 4 || c->w->bsq.bytes < (size_t)T * 4)
     c->w->tt_mem_mask = 0;       // (a table that is reallocated is an empty one)
@@ -566,19 +561,15 @@ int prepare_static_memside(Ctx* c, hipStream_t st, int dynamic_mask, bool want_a
     }
     p.static_mask |= 1 << j;
   }
-  if (p.xa_opf && (p.rt || p.static_mask != (1 << CFD_NMEM) - 1)) p.xa_opf = 0;   // (single-fp16 tiles: every memory static, tile kernels)
-  if (p.xa_opf) {   // this run's operand policy: the key / value tiles of the fused cross-attention as single fp16, packed tile by tile
+  if (p.xa_f16 && (p.rt || p.static_mask != (1 << CFD_NMEM) - 1)) p.xa_f16 = false;   // (single-fp16 tiles: every memory static, tile kernels)
+  if (p.xa_f16) {   // this run's operand policy: the key / value tiles of the fused cross-attention as single fp16, packed tile by tile
     for (int j = 0; j < CFD_NMEM; ++j) {
-      if (!((p.xa_f16_mask >> j) & 1)) continue;   // (short memories keep pairs: xattn_fused.hpp, OPF)
+      if (!((p.xa_f16_mask >> j) & 1)) continue;   // (short memories keep pairs: xattn_fused.hpp, F16)
       const long long tiles = (long long)nl * p.U[j] * (p.Sp[j] / XA_KEYS), chunks = tiles * 2048;
-      if (p.xa_opf & XA_V16) {
-        CHK(c->w->v16[j].ensure((size_t)tiles * 32768));
-        LAUNCH(CFD_PROF_ROWS, xa_pack16_kernel<>, dim3((unsigned)((chunks + 255) / 256)), dim3(256), st, c->w->vt_all[j].as<char>(), c->w->v16[j].as<char>(), chunks, p.Sp[j], 0);
-      }
-      if (p.xa_opf & XA_K16) {
-        CHK(c->w->k16[j].ensure((size_t)tiles * 32768));
-        LAUNCH(CFD_PROF_ROWS, xa_pack16_kernel<>, dim3((unsigned)((chunks + 255) / 256)), dim3(256), st, c->w->kall_sp[j].as<char>(), c->w->k16[j].as<char>(), chunks, p.Sp[j], 1);
-      }
+      CHK(c->w->v16[j].ensure((size_t)tiles * 32768));
+      LAUNCH(CFD_PROF_ROWS, xa_pack16_kernel<>, dim3((unsigned)((chunks + 255) / 256)), dim3(256), st, c->w->vt_all[j].as<char>(), c->w->v16[j].as<char>(), chunks, p.Sp[j], 0);
+      CHK(c->w->k16[j].ensure((size_t)tiles * 32768));
+      LAUNCH(CFD_PROF_ROWS, xa_pack16_kernel<>, dim3((unsigned)((chunks + 255) / 256)), dim3(256), st, c->w->kall_sp[j].as<char>(), c->w->k16[j].as<char>(), chunks, p.Sp[j], 1);
     }
   }
   if (p.xa_one >= 0 && !p.rt) {   // the one-key memory's value rows as float32 vectors (xattn_fused.hpp, XAttnArgs::one_va).  Also with `reuse`:

@@ -186,9 +186,9 @@ extern "C" int cfd_sample_begin(cfd_handle c, const cfd_sample_args* args, void*
   }
   // operand policy of the run (cfd_sample_args::operand_policy): single-fp16 key / value tiles of the long memories for the fused
   // cross-attention kernel -- only where that kernel runs on projections made once per run and keeps no maps
-  c->want_opf = (n_ring || s.dynamic_memory_mask) ? 0 : (c->xa_operands >= 0 ? c->xa_operands : (s.operand_policy & 15));
+  c->want_f16 = !n_ring && !s.dynamic_memory_mask && (c->xa_operands >= 0 ? c->xa_operands : (s.operand_policy & 15)) != 0;
   const int r_setup = setup_problem(c, Be, s.L, mem_in, nullptr, 0, N);
-  c->want_opf = 0;
+  c->want_f16 = false;
   CHK(r_setup);
   if (c->share0 && c->sargs.G > 1) c->w->pb.share_B = s.B;   // begin_step_kernel writes G identical copies of the B rows
   c->w->pb.att_nb = 0;
@@ -221,7 +221,7 @@ extern "C" int cfd_sample_begin(cfd_handle c, const cfd_sample_args* args, void*
   {   // (the rest of the operand policy's conditions; prepare_static_memside checks that every memory's projections are made once per run)
     Problem& pb = c->w->pb;
     const bool fused_run = !pb.rt && c->fused_xattn && pb.xa_nwg > 0 && c->hoist_memside && !g_cfd_naive_gemm && !pb.att_fused && !s.dynamic_memory_mask;
-    if (!fused_run) pb.xa_opf = 0;
+    if (!fused_run) pb.xa_f16 = false;
     // the attention-concentration census (cfd_sample_args::census_tau): the same runs as the operand policy -- the others keep pairs anyway
     c->acen_tau = s.census_tau > 0.f ? s.census_tau : 0.f;
     c->acen_on = fused_run && c->acen_tau > 0.f;

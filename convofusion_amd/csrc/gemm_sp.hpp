@@ -1,5 +1,5 @@
 // Split-pair "NT" GEMM for gfx950:  D[i][j] = sum_k X[i][k] * Y[j][k], every product issued as 3 MFMAs
-// (lo*hi + hi*lo + hi*hi of the fp16 -- or bf16 -- halves, fp32 accumulate; see cfd_common.hpp).
+// (lo*hi + hi*lo + hi*hi of the fp16 halves, fp32 accumulate; see cfd_common.hpp).
 //
 //   X ("row operand", MFMA A) and Y ("column operand", MFMA B) are SP matrices with K contiguous, so both
 //   fragments are 16-byte LDS reads.  The result tile is handed to an epilogue functor as 4 consecutive i for
@@ -26,18 +26,6 @@
 
 // s_waitcnt immediate (gfx9 encoding): vmcnt = N (bits 3:0 and 15:14), expcnt = 7 (no wait), lgkmcnt = 0
 #define WAIT_VM_LGKM0(N) ((((N) & 15) | 0x70 | ((((N) >> 4) & 3) << 14)))
-#ifndef CFD_WIDE_EPI
-#define CFD_WIDE_EPI 1
-#endif
-// hipcc moves part of a k-step's MFMAs below the barrier that ends the step (20 of 48 in the 128 x 128 kernel), i.e. in
-// front of the NEXT step's LDS-DMA requests: the requests are issued 320 cycles later and the vmcnt(0) wait at the barrier
-// is covered by fewer MFMAs.  A scheduling fence keeps the whole cluster in front of the barrier.
-#ifndef CFD_MFMA_FENCE
-#define CFD_MFMA_FENCE 1
-#endif
-#ifndef CFD_READS_FIRST
-#define CFD_READS_FIRST 1
-#endif
 #define GEMM_SLOTS 5
 enum { MODE_PLAIN = 0, MODE_GROUPED = 1, MODE_SEGK = 2 };
 
@@ -142,7 +130,7 @@ struct EpiSplit {  // out_sp[j][coloff + i] = split(act(v + bias[i]))
       sp_store4(row, c0, v[0], v[1], v[2], v[3]);
       sp_store4(row, c1, v[4], v[5], v[6], v[7]);
     } else {
-      sp_store8_out(row, i, v);
+      sp_store8(row, i, v);
     }
   }
 };
@@ -175,7 +163,7 @@ struct EpiQkvT {
   }
   __device__ __forceinline__ void store8(int g, int b, int z, int i, int j, f32x4 v0, f32x4 v1, float4 t0, float4 t1) const {
     const float v[8] = {v0[0] + t0.x, v0[1] + t0.y, v0[2] + t0.z, v0[3] + t0.w, v1[0] + t1.x, v1[1] + t1.y, v1[2] + t1.z, v1[3] + t1.w};
-    sp_store8_out(out_qk + (long long)j * ldo, i, v);
+    sp_store8(out_qk + (long long)j * ldo, i, v);
   }
   // feature i of the value projection, tokens jb + 8 h .. + 7 (jb % 16 == 0): 16 key positions = 32 bytes of the hi plane and of the lo plane
   __device__ __forceinline__ void store_t(int i, int jb, int h, const float* v) const {
@@ -602,9 +590,9 @@ __device__ __forceinline__ void gemm_sp_body(const GemmArgs& a, const Epi& epi, 
   struct NoPre {};
   typename std::conditional<Epi::kPrefetch, typename EpiPre<Epi>::type, NoPre>::type pre[TI][TJ];
   // Epilogue lane mapping.  Native MFMA layout: a lane owns 4 consecutive i of ONE row j, so a wave store touches 16
-  // rows x 64 B (16 half cache lines).  With CFD_WIDE_EPI the accumulator tile goes through LDS once and is handed
+  // rows x 64 B (16 half cache lines).  The wide mapping (TI = 2, 4, 8): the accumulator tile goes through LDS once and is handed
   // out again with LPR = 4*TI lanes per row: a wave store then covers 64/LPR rows x (TI*64) contiguous bytes.
-  constexpr bool WIDE = CFD_WIDE_EPI && (TI == 2 || TI == 4 || TI == 8);
+  constexpr bool WIDE = TI == 2 || TI == 4 || TI == 8;
   constexpr int LPR = TI * 4;            // lanes per output row (wide mapping)
   constexpr int RPI = 64 / LPR;          // rows per wave instruction
   constexpr int NIT = 16 / RPI;          // instructions per 16-row tile band
@@ -629,21 +617,15 @@ __device__ __forceinline__ void gemm_sp_body(const GemmArgs& a, const Epi& epi, 
   }
 
   // the bias of a lane's 8 output columns (split-pair stores): requested here, so that its round trip runs under the K loop -- it used
-  // to be the first thing the epilogue waited for.  (-DCFD_BIAS8_LATE=1: the old place, for the A/B.)
-#ifndef CFD_BIAS8_LATE
-#define CFD_BIAS8_LATE 0
-#endif
+  // to be the first thing the epilogue waited for.
   float4 s8_t0 = make_float4(0.f, 0.f, 0.f, 0.f), s8_t1 = s8_t0;
-  if constexpr (WIDE && !CFD_BIAS8_LATE && EpiHasStore8<Epi>::value && EpiHasBias8<Epi>::value) {
+  if constexpr (WIDE && EpiHasStore8<Epi>::value && EpiHasBias8<Epi>::value) {
     const int i8 = i0 + wi * TI * 16 + (lane % (TI * 2)) * 8;   // (a lane's columns do not depend on the band)
     epi.tile_bias8(min(i8, Ig - 8), s8_t0, s8_t1);
   }
 
   // LayerNorm fold (EpiLn): thread t < BJ requests the 16 (mean, M2) slots of row j0 + t now; ln_finish() -- called behind the first
   // stage requests -- puts them together and parks (mu, r_sigma) behind the staging ring, where the epilogue reads them.
-#ifndef LNF_ABL
-#define LNF_ABL 0   // developer timing experiments (results are garbage): 1 = no statistics loads / combine, 2 = no rescale, 4 = no c / d loads
-#endif
   constexpr bool LNF = EpiHasLnFold<Epi>::value;
   static_assert(!LNF || MODE != MODE_SEGK, "LayerNorm fold: plain or grouped launches");
   // The statistics are requested by inline assembly and waited for by hand in ln_finish: as ordinary loads hipcc drained the whole queue for them
@@ -652,7 +634,7 @@ __device__ __forceinline__ void gemm_sp_body(const GemmArgs& a, const Epi& epi, 
   f32x4 ln_raw[LNF ? LN_SLOTS / 2 : 1];
   float4 ln_c4[LNF ? TI : 1], ln_d4[LNF ? TI : 1];
   if constexpr (LNF) {
-    if (!(LNF_ABL & 1) && (int)threadIdx.x < BJ) {
+    if ((int)threadIdx.x < BJ) {
       const char* sp = reinterpret_cast<const char*>(epi.ln_stat + (long long)min(j0 + (int)threadIdx.x, a.J - 1) * (LN_SLOTS * 2));
 #pragma unroll
       for (int q = 0; q < LN_SLOTS / 2; ++q) {
@@ -666,8 +648,7 @@ __device__ __forceinline__ void gemm_sp_body(const GemmArgs& a, const Epi& epi, 
     const float* dg = g == 0 ? epi.ln_d[0] : epi.ln_d[1];
 #pragma unroll
     for (int ti = 0; ti < TI; ++ti) {
-      const int i = (LNF_ABL & 4) ? 0 : min(i0 + (wi * TI + ti) * 16 + q4 * 4, Ig - 4);
-      if (LNF_ABL & 4) { ln_c4[ti] = ln_d4[ti] = make_float4(0.f, 0.f, 0.f, 0.f); continue; }
+      const int i = min(i0 + (wi * TI + ti) * 16 + q4 * 4, Ig - 4);
       ln_c4[ti] = *reinterpret_cast<const float4*>(cg + i);
       ln_d4[ti] = *reinterpret_cast<const float4*>(dg + i);
     }
@@ -676,29 +657,27 @@ __device__ __forceinline__ void gemm_sp_body(const GemmArgs& a, const Epi& epi, 
   // `younger`: the vector-memory requests this wave has issued since (the stage requests in front of the call)
   auto ln_finish = [&](auto younger) __attribute__((always_inline)) {
     if constexpr (LNF) {
-      if constexpr (!(LNF_ABL & 1)) {
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(decltype(younger)::value) : "memory");
-        if ((int)threadIdx.x < BJ) {
+      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(decltype(younger)::value) : "memory");
+      if ((int)threadIdx.x < BJ) {
 #pragma unroll
-          for (int q = 0; q < LN_SLOTS / 2; ++q) asm volatile("" : "+v"(ln_raw[q]));
-          float ms = 0.f, m2 = 0.f;
+        for (int q = 0; q < LN_SLOTS / 2; ++q) asm volatile("" : "+v"(ln_raw[q]));
+        float ms = 0.f, m2 = 0.f;
 #pragma unroll
-          for (int q = 0; q < LN_SLOTS / 2; ++q) { ms += ln_raw[q][0] + ln_raw[q][2]; m2 += ln_raw[q][1] + ln_raw[q][3]; }
-          const float mu = ms * (1.0f / LN_SLOTS);
-          float dev = 0.f;
+        for (int q = 0; q < LN_SLOTS / 2; ++q) { ms += ln_raw[q][0] + ln_raw[q][2]; m2 += ln_raw[q][1] + ln_raw[q][3]; }
+        const float mu = ms * (1.0f / LN_SLOTS);
+        float dev = 0.f;
 #pragma unroll
-          for (int q = 0; q < LN_SLOTS / 2; ++q) {
-            const float d0 = ln_raw[q][0] - mu, d1 = ln_raw[q][2] - mu;
-            dev += d0 * d0 + d1 * d1;
-          }
-          const float var = (m2 + dev * 32.0f) * (1.0f / CFD_D);
-          // (an LDS write the compiler does not see: in front of one it does, it waits for EVERY pending LDS-DMA request -- it cannot tell that
-          //  the (mu, r_sigma) slots lie behind the staging ring -- and the first barrier would wait for both stages instead of the first)
-          typedef float f32x2_t __attribute__((ext_vector_type(2)));
-          const f32x2_t mr = {mu, 1.0f / sqrtf(var + epi.ln_eps)};
-          const unsigned la = (unsigned)(unsigned long long)(lptr_t)(smem + NSTAGE * STAGE + threadIdx.x * 8);
-          asm volatile("ds_write_b64 %0, %1" ::"v"(la), "v"(mr) : "memory");
+        for (int q = 0; q < LN_SLOTS / 2; ++q) {
+          const float d0 = ln_raw[q][0] - mu, d1 = ln_raw[q][2] - mu;
+          dev += d0 * d0 + d1 * d1;
         }
+        const float var = (m2 + dev * 32.0f) * (1.0f / CFD_D);
+        // (an LDS write the compiler does not see: in front of one it does, it waits for EVERY pending LDS-DMA request -- it cannot tell that
+        //  the (mu, r_sigma) slots lie behind the staging ring -- and the first barrier would wait for both stages instead of the first)
+        typedef float f32x2_t __attribute__((ext_vector_type(2)));
+        const f32x2_t mr = {mu, 1.0f / sqrtf(var + epi.ln_eps)};
+        const unsigned la = (unsigned)(unsigned long long)(lptr_t)(smem + NSTAGE * STAGE + threadIdx.x * 8);
+        asm volatile("ds_write_b64 %0, %1" ::"v"(la), "v"(mr) : "memory");
       }
     }
   };
@@ -715,9 +694,7 @@ __device__ __forceinline__ void gemm_sp_body(const GemmArgs& a, const Epi& epi, 
       yh[tj] = *reinterpret_cast<const spx8*>(sby + yoff_h + tj * 2048);
       yl[tj] = *reinterpret_cast<const spx8*>(sby + yoff_l + tj * 2048);
     }
-#if CFD_READS_FIRST
     __builtin_amdgcn_sched_barrier(0);   // all fragment reads of the k-step are issued before its first MFMA
-#endif
 #pragma unroll
     for (int ti = 0; ti < TI; ++ti)
 #pragma unroll
@@ -737,9 +714,10 @@ __device__ __forceinline__ void gemm_sp_body(const GemmArgs& a, const Epi& epi, 
       const int buf = kt & 1;
       if (kt + 1 < nkt) stage(kt + 1, buf ^ 1);
       compute(buf);
-#if CFD_MFMA_FENCE
+      // hipcc moves part of a k-step's MFMAs below the barrier that ends the step (20 of 48 in the 128 x 128 kernel), i.e. in
+      // front of the NEXT step's LDS-DMA requests: the requests are issued 320 cycles later and the vmcnt(0) wait at the barrier
+      // is covered by fewer MFMAs.  A scheduling fence keeps the whole cluster in front of the barrier.
       __builtin_amdgcn_sched_barrier(0);
-#endif
       __syncthreads();
     }
   } else {
@@ -768,7 +746,7 @@ __device__ __forceinline__ void gemm_sp_body(const GemmArgs& a, const Epi& epi, 
     }
   }
 
-  if constexpr (LNF && !(LNF_ABL & 2)) {   // acc <- r_sigma (acc - mu c) + d: lane (l15, q4) holds row (wj TJ + tj) 16 + l15, features (wi TI + ti) 16 + 4 q4 .. + 3
+  if constexpr (LNF) {   // acc <- r_sigma (acc - mu c) + d: lane (l15, q4) holds row (wj TJ + tj) 16 + l15, features (wi TI + ti) 16 + 4 q4 .. + 3
     const float2* sl = reinterpret_cast<const float2*>(smem + NSTAGE * STAGE);
 #pragma unroll
     for (int tj = 0; tj < TJ; ++tj) {
@@ -799,10 +777,6 @@ __device__ __forceinline__ void gemm_sp_body(const GemmArgs& a, const Epi& epi, 
         epi_ij(0, it, i, j);
         band_r[it] = epi.band_load(g, b, z, min(i, Ig - 4), min(j, a.J - 1));
       }
-    }
-    if constexpr (CFD_BIAS8_LATE && EpiHasStore8<Epi>::value && EpiHasBias8<Epi>::value) {
-      const int i8 = i0 + wi * TI * 16 + (lane % (TI * 2)) * 8;   // (a lane's columns do not depend on the band)
-      if (i8 + 8 <= Ig) epi.tile_bias8(i8, s8_t0, s8_t1);
     }
 #pragma unroll
     for (int tj = 0; tj < TJ; ++tj) {

@@ -66,7 +66,7 @@
 #define XA_TILES 4     // query tiles (of 16 queries) per workgroup
 #define XA_WAVES 8     // two waves per query tile
 #define XA_KEYS 32
-#define XA_F16_MIN_KEYS 128   // padded keys from which a memory counts as LONG for the operand policy (single-fp16 tiles; see OPF below)
+#define XA_F16_MIN_KEYS 128   // padded keys from which a memory counts as LONG for the operand policy (single-fp16 tiles; see F16 below)
 // LDS map: K tile | V^T tile (the epilogue strips alias these two and 2 KB more) | partial-score exchange | key bias of
 // two steps | the workgroup's segment list
 #define XA_XOFF 133120
@@ -87,7 +87,7 @@ struct XaSeg {
   int wmask;    // query tiles (bit t) whose batch row uses this instance
   int flags;    // XA_ONLINE | XA_FLUSH
 };
-enum { XA_ONLINE = 1, XA_FLUSH = 2, XA_F16 = 4 };   // XA_F16: the segment's memory has single-fp16 tiles in the formats the kernel instance's OPF names
+enum { XA_ONLINE = 1, XA_FLUSH = 2, XA_F16 = 4 };   // XA_F16: the segment's memory has single-fp16 tiles (read by the F16 instance)
 
 struct XaWg {
   int row[XA_TILES];   // effective-batch row of query tile t, or -1 (idle)
@@ -164,7 +164,7 @@ __global__ void __launch_bounds__(256) one_key_va_kernel(const char* vt, long lo
   out[i] = (float)*reinterpret_cast<const sp_t*>(p) + (float)*reinterpret_cast<const sp_t*>(p + 64);
 }
 
-// Single-fp16 key tiles for the fused kernel's OPF instances (once per run, from the split-pair projections; layouts: see the staging
+// Single-fp16 key / value tiles for the fused kernel's F16 instance (once per run, from the split-pair projections; layouts: see the staging
 // comment in the kernel).  One thread per 16-byte chunk (8 values: the `hi` halves, which are the values rounded to fp16).
 //   which = 0: V^T  in  SP [n_lu][512][Sp]      out [n_lu][T][512][64 B]
 //   which = 1: K    in  SP [n_lu * Sp][512]     out [n_lu][T][2][16][16][64 B]          (n_lu = layers x instances, T = Sp / 32)
@@ -213,57 +213,33 @@ __device__ __forceinline__ T xa_sel(const T (&arr)[CFD_NMEM], int j) {
 #else
 #define XA_T(k) do { } while (0)
 #endif
-#ifndef XA_ABLATE
-#define XA_ABLATE 0   // developer timing experiments, bit mask: 1 = no fills, 2 = no MFMAs, 4 = no fragment reads, 8 = no softmax (results are garbage)
-#endif
-#if XA_ABLATE & 2
-#define XA_MFMA(a_, b_, c_) ([&]() { asm volatile("" ::"v"(a_), "v"(b_)); return c_; }())
-#else
-#define XA_MFMA(a_, b_, c_) SP_MFMA(a_, b_, c_, 0, 0, 0)
-#endif
-#if XA_ABLATE & 4
-#define XA_FRAG(p_) ([&]() { spx8 z_; for (int e_ = 0; e_ < 8; ++e_) z_[e_] = (sp_t)(float)(lane + e_); asm volatile("" : "+v"(z_)); return z_; }())
-#else
-#define XA_FRAG(p_) (*reinterpret_cast<const spx8*>(p_))
-#endif
 #define XA_WAIT_VM(N) __builtin_amdgcn_s_waitcnt(((N) & 15) | 0x70 | (0xF << 8) | ((((N) >> 4) & 3) << 14))
 #define XA_WAIT_VM_LGKM0(N) __builtin_amdgcn_s_waitcnt(((N) & 15) | 0x70 | ((((N) >> 4) & 3) << 14))
 
 // ATT: the rows of XaAtt also store their attention maps.
-// OPF (operand format of the key tiles of LONG memories, round 6; DESIGN.md section 2 "operand policy"): the kernel is paced by the
+// F16 (operand format of the key tiles of LONG memories, round 6; DESIGN.md section 2 "operand policy"): the kernel is paced by the
 // L2 -> LDS fills of the K / V^T tiles (64 KB each as split pairs), so a run whose scheduler tolerates it may carry the tiles of its long
-// memories (segments flagged XA_F16 by the host: cfd_problem.hip, XA_F16_MIN_KEYS) as ONE fp16 per value:
-//   bit 0 (XA_V16): V^T tiles hold VA as single fp16 (32 KB per 32 keys); P' stays a pair, so P.V is 2 MFMAs per product
-//                   (VA_hi . P'_lo + VA_hi . P'_hi) -- the LINEAR path of the attention;
-//   bit 1 (XA_K16): K tiles hold KA as single fp16; Q stays a pair (2 MFMAs: KA_hi . q_lo + KA_hi . q_hi) -- the EXPONENTIATED path.
-//   bit 2 (XA_P16) / bit 3 (XA_Q16): with single-fp16 tiles, P' / the query fragments enter those products as ONE fp16 too (their `hi` half:
-//                   the value rounded to fp16): 1 MFMA per product -- plain fp16 attention against the long memories.
+// memories (segments flagged XA_F16 by the host: cfd_problem.hip, XA_F16_MIN_KEYS) as ONE fp16 per value: the folded keys KA and values VA
+// as single-fp16 tiles, and the query fragments and probabilities P' that meet them as one fp16 too (their `hi` half: the value rounded
+// to fp16) -- 1 MFMA per product instead of 3, plain fp16 attention against the long memories.
 // Why long memories only: the rounding of a value (2^-12 relative, independent signs) enters the output weighted by its probability, so
 // over N attended keys the absolute error falls like 1 / sqrt(N) -- for the 1500-key audio memory it is ~8x below that of a 24-key text
 // memory, whose tiles are 3 of a row's 50 anyway (measured: profiles/r06_xa_operands_*).  Segments without the flag run the split-pair
 // loop body; at a change of format between two segments the pipeline drains and is primed again (once per workgroup at the shipped shapes).
-// XA_DBUF (bit 4, with both tiles single fp16): a K and a V^T tile are 32 KB each, so the two 64 KB tile buffers hold TWO of each and the
-// long memories' steps run a double-buffered pipeline (kt_step_db: every fill a whole step ahead, two barriers per step instead of three).
-// Measured on one box, three interleaved rounds (profiles/r06_xa_dbuf_ab.log): with all four operands single fp16 (OPF 15) the kernel is
-// 1.0 % faster at the headline shape (3.575 -> 3.539 ms; 81.4 -> 81.9 steps/s) and 2.9 % at the product shape (0.371 -> 0.360 ms), whose
-// workgroups run a handful of steps each and wait on fill latency -- so the shipped single-fp16 instance is OPF 15 | XA_DBUF.  (With pairs
-// as the other operands, OPF 3, the same pipeline had measured 0.6 % SLOWER, profiles/r06_xa_double_buffer_ab.log: there the step is
-// paced by the matrix pipe and the softmax's vector work, which the two waves of a SIMD use one after the other.)
+// A K and a V^T tile are 32 KB each in this format, so the two 64 KB tile buffers hold TWO of each and the long memories' steps run a
+// double-buffered pipeline (kt_step_db: every fill a whole step ahead, two barriers per step instead of three).  Measured on one box, three
+// interleaved rounds (profiles/r06_xa_dbuf_ab.log): 1.0 % faster than the three-barrier step at the headline shape (3.575 -> 3.539 ms;
+// 81.4 -> 81.9 steps/s) and 2.9 % at the product shape (0.371 -> 0.360 ms), whose workgroups run a handful of steps each and wait on fill
+// latency.  (The partial formats -- single-fp16 tiles against pair queries / probabilities, 2 MFMAs per product -- were measured in round 6
+// and are dominated: 78.5 - 79.7 steps/s against 80.9, all at 2.3e-5 on the DDPM-1000 golden; on the double-buffered pipeline they were
+// 0.6 % SLOWER, profiles/r06_xa_double_buffer_ab.log, their step being paced by the matrix pipe and the softmax's vector work.  They and
+// the three-barrier single-fp16 step live in git history.)
 // The single-fp16 tiles come from xa_pack16_kernel (once per run, from the split-pair projections): tile-major and already in the LDS
 // image's order, so a fill is a linear copy of 1 KB pieces.  cfd_forward, DDIM runs, runs that keep attention maps and the memories of a
 // dynamic run keep pairs (cfd_sample.hip: operand policy of cfd_sample_begin).
-enum { XA_V16 = 1, XA_K16 = 2, XA_P16 = 4, XA_Q16 = 8, XA_DBUF = 16 };   // XA_DBUF (with XA_V16 | XA_K16): the double-buffered step, an instance of its own   // (XA_P16 / XA_Q16: with single-fp16 tiles, also the OTHER operand of the product as one fp16: 1 MFMA)
-#ifndef XA_ALL_OPF
-#define XA_ALL_OPF 0    // 1: developer builds also instantiate the partial combinations (OPF 1, 2, 3, 7, 11: measured in round 6 and dominated by
-                        // OPF 15 -- e.g. 78.5 / 79.7 / 79.5 steps/s for 3 / 7 / 11 against 80.9, all at 2.3e-5 on the DDPM-1000 golden -- and OPF 15 on the
-                        // three-barrier step, CFD_XA_DB=0: not shipped)
-#endif
-template <bool ATT, int OPF>
+template <bool ATT, bool F16>
 __global__ void __launch_bounds__(XA_WAVES * 64, 2) xattn_fused_kernel(const XAttnArgs a) {
-  static_assert(!ATT || OPF == 0, "attention maps: split-pair tiles");
-  static_assert(!(OPF & XA_DBUF) || (OPF & 3) == 3, "double-buffered step: both tiles single fp16");
-  typedef std::integral_constant<int, OPF> fmt_long;     // format tags of the loop-body instances: flagged segments / all others
-  typedef std::integral_constant<int, 0> fmt_pair;
+  static_assert(!ATT || !F16, "attention maps: split-pair tiles");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int KOFF = 0, VOFF = 65536;
 #if XA_STAMP
@@ -272,21 +248,12 @@ __global__ void __launch_bounds__(XA_WAVES * 64, 2) xattn_fused_kernel(const XAt
 #endif
   const int lane = threadIdx.x & 63;
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-#ifndef XA_PAIR_ADJACENT
-#define XA_PAIR_ADJACENT 1
-#endif
-#if XA_PAIR_ADJACENT
   // The pair of a query tile = waves (2 t, 2 t + 1): on DIFFERENT SIMDs.  With all four tiles busy a SIMD still hosts two waves (of two tiles),
   // which is what the main loop's accounting assumes; a short work list that gives a workgroup ONE tile (the product shape: make_xattn_worklist)
   // then has its two computing waves on two SIMDs instead of taking turns on one.
   const int tile = wid >> 1;     // query tile of the pair
   const int half = wid & 1;      // which half of the 512-long axes
   const int partner = wid ^ 1;
-#else
-  const int tile = wid & 3;      // query tile of the pair (w, w + 4): the two waves share a SIMD
-  const int half = wid >> 2;     // which half of the 512-long axes
-  const int partner = wid ^ 4;
-#endif
   const int l15 = lane & 15, q4 = lane >> 4, sw = l15 >> 1;
   const int cpos = lane & 7, rsub = lane >> 3;
 
@@ -316,9 +283,9 @@ __global__ void __launch_bounds__(XA_WAVES * 64, 2) xattn_fused_kernel(const XAt
   const int trow = a.d_step ? *a.d_step : 0;   // (null: kb / vb are this step's rows already -- no dependent scalar load in front of the A b request)
   // A b of the five memories (2 KB each) -> LDS by the LDS-DMA, issued before anything else so that its round trip runs under the
   // row loads and the LayerNorm below.  Parked in the part of the V^T tile buffer that is first filled after the first step's mid-A0
-  // barrier (Vb, row groups 16-31; an instance with single-fp16 V^T tiles: row groups 48-63, which belong to Vb in the pair format and
+  // barrier (Vb, row groups 16-31; the F16 instance: row groups 48-63, which belong to Vb in the pair format and
   // are beyond the 32 KB a single-fp16 tile takes); c_q is computed from there behind the first barrier.
-  constexpr int KBOFF = VOFF + ((OPF & XA_V16) ? 48 : 16) * 1024;
+  constexpr int KBOFF = VOFF + (F16 ? 48 : 16) * 1024;
   if (wid < CFD_NMEM) {
     const char* kp = reinterpret_cast<const char*>(xa_sel(a.kb, wid) + (long long)trow * xa_sel(a.kb_stride, wid)) + lane * 16;
     __builtin_amdgcn_global_load_lds((gptr_t)kp, (lptr_t)(smem + KBOFF + wid * 2048), 16, 0, 0);
@@ -436,14 +403,13 @@ __global__ void __launch_bounds__(XA_WAVES * 64, 2) xattn_fused_kernel(const XAt
   //      V^T tile LDS image: [feature 512][128 B]; Va = features [0,128) + [256,384), Vb = the rest.  Piece n of wave `wid`:
   //      8-row group g = wid + 8 (n&1) + 32 (n>>1) (+16 for Vb); swizzle ((f>>1)&7) = ((wid&1)<<2) | (rsub>>1)
   const int vsw = (cpos ^ (((wid & 1) << 2) | (rsub >> 1))) << 4;
-  //      Single-fp16 tiles (OPF): a tile is 32 KB, contiguous in memory and already in the LDS image's order (xa_pack16_kernel):
-  //        K  [half t 2][k-step 16][row i 16][64 B], row 16 t + i = key 8 (i>>2) + 4 t + (i&3) as above, 16-byte chunk c at (c ^ (i>>2)&3);
-  //           Ka / Kb = the two halves, 16 pieces each = 2 per wave (k-steps wid, wid + 8)
-  //        V^T [feature 512][64 B], chunk c at (c ^ (f>>2)&3); Va / Vb as above in 16-row groups: 2 pieces per wave (groups wid, wid + 16, + 8 for Vb)
-  //      so a piece's source is tile base + piece * 1 KB + lane * 16.
+  //      Single-fp16 tiles (F16): a tile is 32 KB, contiguous in memory and already in the LDS image's order (xa_pack16_kernel):
+  //        K  [half t 2][k-step 16][row i 16][64 B], row 16 t + i = key 8 (i>>2) + 4 t + (i&3) as above, 16-byte chunk c at (c ^ (i>>2)&3)
+  //        V^T [feature 512][64 B], chunk c at (c ^ (f>>2)&3)
+  //      so a piece's source is tile base + piece * 1 KB + lane * 16: 32 pieces per tile = 4 per wave (fill_k_full / fill_v_full).
   const unsigned lane16 = (unsigned)lane * 16u;
   // Per-lane addresses that depend on the FORMAT of the segment at hand live in one set of variables, set per segment (set_format below):
-  // an instance with two loop bodies (OPF != 0) otherwise keeps both bodies' loop invariants in registers at once and spills.
+  // the F16 instance has two loop bodies and otherwise keeps both bodies' loop invariants in registers at once and spills.
   unsigned kfill_lane = (unsigned)ksrc_lane;      // source offset of this lane inside a K piece
   const char *kf_a, *kf_b, *vf_a, *vf_b;          // fragment read bases: pairs: hi / lo chunk of the lane's row; single fp16: the chunk (b unused)
 
@@ -459,37 +425,25 @@ __global__ void __launch_bounds__(XA_WAVES * 64, 2) xattn_fused_kernel(const XAt
     wm = seg_field(si, 2); fl = seg_field(si, 3);
     const int Sp = xa_sel(a.Sp, j);
     T = Sp / XA_KEYS;
-    const bool f16 = OPF != 0 && (fl & XA_F16);     // (wave-uniform) this memory's tiles are single fp16 in the formats OPF names
-    t.k = xa_sel(a.K, j) + ((f16 && (OPF & XA_K16)) ? (long long)u * T * 32768 : (long long)u * Sp * (CFD_D * 4));
-    t.v = xa_sel(a.VT, j) + ((f16 && (OPF & XA_V16)) ? (long long)u * T * 32768 : (long long)u * CFD_D * Sp * 4);
+    const bool f16 = F16 && (fl & XA_F16);          // (wave-uniform) this memory's tiles are single fp16
+    t.k = xa_sel(a.K, j) + (f16 ? (long long)u * T * 32768 : (long long)u * Sp * (CFD_D * 4));
+    t.v = xa_sel(a.VT, j) + (f16 ? (long long)u * T * 32768 : (long long)u * CFD_D * Sp * 4);
     t.cb = xa_sel(a.cb, j) + (long long)u * Sp;
     t.rowb = (long long)Sp * 4;
-    t.vlane = (f16 && (OPF & XA_V16)) ? lane16 : (unsigned)((wid * 8 + rsub) * Sp * 4 + vsw);    // (512 rows x Sp x 4 B < 4 GiB)
+    t.vlane = f16 ? lane16 : (unsigned)((wid * 8 + rsub) * Sp * 4 + vsw);    // (512 rows x Sp x 4 B < 4 GiB)
     t.cblane = (unsigned)((lane & 31) * 4) + (lane >= 32 ? xa_sel(a.rs_off, j) : 0u);   // lanes 0-31: key bias, lanes 32-63: key scale
   };
   // fills: K half `hb` (0: Ka, 1: Kb) of tile `t`; with Ka travels the key bias and key scale of the tile (1 piece: 64 x 4 B:
   // 32 biases, 32 scales) into key-bias slot `slot`.  Every address is a wave-uniform 64-bit base
   // (SGPRs) + a loop-invariant 32-bit lane offset: no vector arithmetic per fill.  (The operands are made opaque at every
   // use: otherwise hipcc hoists base + lane offset out of the loop as a 64-bit per-lane pointer and pays vector adds per fill.)
-  auto fill_k = [&](auto fc, const Tile& t, int hb, int slot) __attribute__((always_inline)) {
-    constexpr bool K16 = (decltype(fc)::value & XA_K16) != 0;
-    if (XA_ABLATE & 1) return;
-    if constexpr (K16) {
+  auto fill_k = [&](const Tile& t, int hb, int slot) __attribute__((always_inline)) {
 #pragma unroll
-      for (int n = 0; n < 2; ++n) {
-        unsigned kl = kfill_lane;
-        const char* b = t.k + hb * 16384 + (wid + 8 * n) * 1024;
-        asm volatile("" : "+v"(kl), "+s"(b));
-        __builtin_amdgcn_global_load_lds((gptr_t)(b + kl), (lptr_t)(smem + KOFF + hb * 16384 + (wid + 8 * n) * 1024), 16, 0, 0);
-      }
-    } else {
-#pragma unroll
-      for (int n = 0; n < 4; ++n) {
-        unsigned kl = kfill_lane;
-        const char* b = t.k + hb * (4 * CFD_D * 4) + n * 512;
-        asm volatile("" : "+v"(kl), "+s"(b));
-        __builtin_amdgcn_global_load_lds((gptr_t)(b + kl), (lptr_t)(smem + kdst_wave + hb * 2048 + n * 16384), 16, 0, 0);
-      }
+    for (int n = 0; n < 4; ++n) {
+      unsigned kl = kfill_lane;
+      const char* b = t.k + hb * (4 * CFD_D * 4) + n * 512;
+      asm volatile("" : "+v"(kl), "+s"(b));
+      __builtin_amdgcn_global_load_lds((gptr_t)(b + kl), (lptr_t)(smem + kdst_wave + hb * 2048 + n * 16384), 16, 0, 0);
     }
     if (hb == 0) {
       unsigned cl = t.cblane;
@@ -497,27 +451,14 @@ __global__ void __launch_bounds__(XA_WAVES * 64, 2) xattn_fused_kernel(const XAt
       __builtin_amdgcn_global_load_lds((gptr_t)(reinterpret_cast<const char*>(t.cb) + cl), (lptr_t)(smem + XA_CBOFF + slot * 256), 4, 0, 0);
     }
   };
-  auto fill_v = [&](auto fc, const Tile& t, int hb) __attribute__((always_inline)) {
-    constexpr bool V16 = (decltype(fc)::value & XA_V16) != 0;
-    if (XA_ABLATE & 1) return;
-    if constexpr (V16) {
+  auto fill_v = [&](const Tile& t, int hb) __attribute__((always_inline)) {
 #pragma unroll
-      for (int n = 0; n < 2; ++n) {
-        unsigned vl = t.vlane;
-        const int g = wid + 16 * n + 8 * hb;                       // 16-row group (1 KB)
-        const char* b = t.v + g * 1024;
-        asm volatile("" : "+v"(vl), "+s"(b));
-        __builtin_amdgcn_global_load_lds((gptr_t)(b + vl), (lptr_t)(smem + VOFF + g * 1024), 16, 0, 0);
-      }
-    } else {
-#pragma unroll
-      for (int n = 0; n < 4; ++n) {
-        unsigned vl = t.vlane;
-        const int g = 8 * (n & 1) + 32 * (n >> 1) + 16 * hb;       // uniform part of the 8-row group index (+ wid per wave)
-        const char* b = t.v + (long long)g * 8 * t.rowb;
-        asm volatile("" : "+v"(vl), "+s"(b));
-        __builtin_amdgcn_global_load_lds((gptr_t)(b + vl), (lptr_t)(smem + VOFF + (wid + g) * 1024), 16, 0, 0);
-      }
+    for (int n = 0; n < 4; ++n) {
+      unsigned vl = t.vlane;
+      const int g = 8 * (n & 1) + 32 * (n >> 1) + 16 * hb;       // uniform part of the 8-row group index (+ wid per wave)
+      const char* b = t.v + (long long)g * 8 * t.rowb;
+      asm volatile("" : "+v"(vl), "+s"(b));
+      __builtin_amdgcn_global_load_lds((gptr_t)(b + vl), (lptr_t)(smem + VOFF + (wid + g) * 1024), 16, 0, 0);
     }
   };
 
@@ -613,70 +554,48 @@ __global__ void __launch_bounds__(XA_WAVES * 64, 2) xattn_fused_kernel(const XAt
   const char* xch_other = smem + XA_XOFF + partner * 2048 + lane * 16;
   // fragment reads: half `hf` (4 k-steps / 4 feature tiles) of a sub-phase -> 8 fragments (hi, lo alternating)
   // pairs: rows of 128 B, hi chunk q4 / lo chunk 4 + q4 of row l15 at (chunk ^ l15 >> 1); single fp16: rows of 64 B, chunk q4 at (q4 ^ (l15 >> 2) & 3)
-  auto set_format = [&](bool k16, bool v16) __attribute__((always_inline)) {
+  auto set_format = [&](bool f16) __attribute__((always_inline)) {
     int ln = lane;
-    if constexpr (OPF != 0) asm volatile("" : "+v"(ln));      // (opaque: computed where the segment starts, not hoisted for both formats)
+    if constexpr (F16) asm volatile("" : "+v"(ln));      // (opaque: computed where the segment starts, not hoisted for both formats)
     const int r15 = ln & 15, g4 = ln >> 4;
     const int s16 = (g4 ^ ((r15 >> 2) & 3)) << 4, sh = (g4 ^ (r15 >> 1)) << 4, sl = ((4 + g4) ^ (r15 >> 1)) << 4;
-    kf_a = smem + KOFF + (k16 ? (8 * half) * 1024 + r15 * 64 + s16 : (8 * half) * 4096 + r15 * 128 + sh);
+    kf_a = smem + KOFF + (f16 ? (8 * half) * 1024 + r15 * 64 + s16 : (8 * half) * 4096 + r15 * 128 + sh);
     kf_b = smem + KOFF + (8 * half) * 4096 + r15 * 128 + sl;
-    vf_a = smem + VOFF + (v16 ? (16 * half * 16 + r15) * 64 + s16 : (16 * half * 16 + r15) * 128 + sh);
+    vf_a = smem + VOFF + (f16 ? (16 * half * 16 + r15) * 64 + s16 : (16 * half * 16 + r15) * 128 + sh);
     vf_b = smem + VOFF + (16 * half * 16 + r15) * 128 + sl;
-    kfill_lane = k16 ? (unsigned)ln * 16u : (unsigned)ksrc_lane;
+    kfill_lane = f16 ? (unsigned)ln * 16u : (unsigned)ksrc_lane;   // (only fill_k reads it, pairs; hipcc's code for both instances depends on this form)
   };
-  set_format(false, false);
-  // (pairs: fr[2 i] = hi, fr[2 i + 1] = lo of fragment i; single fp16: fr[i] = the fragment, fr[4..7] unused)
-  auto read_k = [&](auto fc, spx8 (&fr)[8], int t, int hf) __attribute__((always_inline)) {
-    constexpr bool K16 = (decltype(fc)::value & XA_K16) != 0;
+  set_format(false);
+  // split pairs: fr[2 i] = hi, fr[2 i + 1] = lo of fragment i
+  auto read_k = [&](spx8 (&fr)[8], int t, int hf) __attribute__((always_inline)) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      if constexpr (K16) {
-        fr[i] = XA_FRAG(kf_a + t * 16384 + (4 * hf + i) * 1024);
-      } else {
-        fr[2 * i] = XA_FRAG(kf_a + (4 * hf + i) * 4096 + t * 2048);
-        fr[2 * i + 1] = XA_FRAG(kf_b + (4 * hf + i) * 4096 + t * 2048);
-      }
+      fr[2 * i] = *reinterpret_cast<const spx8*>(kf_a + (4 * hf + i) * 4096 + t * 2048);
+      fr[2 * i + 1] = *reinterpret_cast<const spx8*>(kf_b + (4 * hf + i) * 4096 + t * 2048);
     }
   };
-  auto read_v = [&](auto fc, spx8 (&fr)[8], int qf) __attribute__((always_inline)) {   // qf = 0..3: feature tiles 4 qf .. 4 qf + 3 of this half
-    constexpr bool V16 = (decltype(fc)::value & XA_V16) != 0;
+  auto read_v = [&](spx8 (&fr)[8], int qf) __attribute__((always_inline)) {   // qf = 0..3: feature tiles 4 qf .. 4 qf + 3 of this half
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      if constexpr (V16) {
-        fr[i] = XA_FRAG(vf_a + (4 * qf + i) * 1024);
-      } else {
-        fr[2 * i] = XA_FRAG(vf_a + (4 * qf + i) * 2048);
-        fr[2 * i + 1] = XA_FRAG(vf_b + (4 * qf + i) * 2048);
-      }
+      fr[2 * i] = *reinterpret_cast<const spx8*>(vf_a + (4 * qf + i) * 2048);
+      fr[2 * i + 1] = *reinterpret_cast<const spx8*>(vf_b + (4 * qf + i) * 2048);
     }
   };
-  auto mfma_k = [&](auto fc, f32x4& acc, const spx8 (&fr)[8], int hf) __attribute__((always_inline)) {
-    constexpr bool K16 = (decltype(fc)::value & XA_K16) != 0;
+  auto mfma_k = [&](f32x4& acc, const spx8 (&fr)[8], int hf) __attribute__((always_inline)) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      if constexpr (K16) {
-        if constexpr ((decltype(fc)::value & XA_Q16) == 0) acc = XA_MFMA(fr[i], ql[4 * hf + i], acc);
-        acc = XA_MFMA(fr[i], qh[4 * hf + i], acc);
-      } else {
-        acc = XA_MFMA(fr[2 * i + 1], qh[4 * hf + i], acc);
-        acc = XA_MFMA(fr[2 * i], ql[4 * hf + i], acc);
-        acc = XA_MFMA(fr[2 * i], qh[4 * hf + i], acc);
-      }
+      acc = SP_MFMA(fr[2 * i + 1], qh[4 * hf + i], acc, 0, 0, 0);
+      acc = SP_MFMA(fr[2 * i], ql[4 * hf + i], acc, 0, 0, 0);
+      acc = SP_MFMA(fr[2 * i], qh[4 * hf + i], acc, 0, 0, 0);
     }
   };
   spx8 ph, pl;
-  auto mfma_v = [&](auto fc, const spx8 (&fr)[8], int qf) __attribute__((always_inline)) {
-    constexpr bool V16 = (decltype(fc)::value & XA_V16) != 0;
+  auto mfma_v = [&](const spx8 (&fr)[8], int qf) __attribute__((always_inline)) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      if constexpr (V16) {
-        if constexpr ((decltype(fc)::value & XA_P16) == 0) o[4 * qf + i] = XA_MFMA(fr[i], pl, o[4 * qf + i]);
-        o[4 * qf + i] = XA_MFMA(fr[i], ph, o[4 * qf + i]);
-      } else {
-        o[4 * qf + i] = XA_MFMA(fr[2 * i + 1], ph, o[4 * qf + i]);
-        o[4 * qf + i] = XA_MFMA(fr[2 * i], pl, o[4 * qf + i]);
-        o[4 * qf + i] = XA_MFMA(fr[2 * i], ph, o[4 * qf + i]);
-      }
+      o[4 * qf + i] = SP_MFMA(fr[2 * i + 1], ph, o[4 * qf + i], 0, 0, 0);
+      o[4 * qf + i] = SP_MFMA(fr[2 * i], pl, o[4 * qf + i], 0, 0, 0);
+      o[4 * qf + i] = SP_MFMA(fr[2 * i], ph, o[4 * qf + i], 0, 0, 0);
     }
   };
   // softmax of one key tile from the pair's two partial score sets (this wave's s0 / s1 in registers, the partner's in the exchange area):
@@ -775,9 +694,8 @@ __global__ void __launch_bounds__(XA_WAVES * 64, 2) xattn_fused_kernel(const XAt
   int step = 0;
   Tile cur, nseg_t;
   int cT = 1, cmask = 0, cflags = 0, cj = 0, nT = 1, nmask = 0, nflags = 0, nj = 0;
-  // A whole single-fp16 K tile (+ its key-bias piece) / V^T tile into slot `sl` of its buffer: 4 (+1) / 4 pieces per wave (XA_DBUF instances)
+  // A whole single-fp16 K tile (+ its key-bias piece) / V^T tile into slot `sl` of its buffer: 4 (+1) / 4 pieces per wave (F16 instance)
   auto fill_k_full = [&](const Tile& t, int sl) __attribute__((always_inline)) {
-    if (XA_ABLATE & 1) return;
 #pragma unroll
     for (int n = 0; n < 4; ++n) {
       unsigned kl = lane16;
@@ -790,7 +708,6 @@ __global__ void __launch_bounds__(XA_WAVES * 64, 2) xattn_fused_kernel(const XAt
     __builtin_amdgcn_global_load_lds((gptr_t)(reinterpret_cast<const char*>(t.cb) + cl), (lptr_t)(smem + XA_CBOFF + sl * 256), 4, 0, 0);
   };
   auto fill_v_full = [&](const Tile& t, int sl) __attribute__((always_inline)) {
-    if (XA_ABLATE & 1) return;
 #pragma unroll
     for (int n = 0; n < 4; ++n) {
       unsigned vl = lane16;
@@ -800,7 +717,7 @@ __global__ void __launch_bounds__(XA_WAVES * 64, 2) xattn_fused_kernel(const XAt
     }
   };
   if (nseg > 0) seg_tile(0, cur, cT, cmask, cflags, cj);
-  if constexpr ((OPF & XA_DBUF) != 0) {
+  if constexpr (F16) {
     // the first tile of a list that starts with a long memory: requested HERE, in front of the rest of the prologue.  (Slot 0 of both tile
     // buffers: the parked A b / norm2 parameters sit beyond the V^T tile's 32 KB; nobody reads the tile buffers before the first step's B0.)
     if (nseg > 0 && wgp->n16 > 0) {
@@ -812,98 +729,96 @@ __global__ void __launch_bounds__(XA_WAVES * 64, 2) xattn_fused_kernel(const XAt
   XA_T(13);
   finish_queries();
   XA_T(0);
-  // One key-tile step in the format `fc` (fmt_long / fmt_pair): the tile `cur` and the tile after it, `nxt`, are BOTH in that format
-  // (the segment loop below sees to it), so every piece count behind a counted wait is a compile-time constant of the instance.
+  // One key-tile step with split-pair tiles: the tile `cur` and the tile after it, `nxt`, are BOTH split pairs (the segment loop below sees
+  // to it), so every piece count behind a counted wait is a constant: 4 pieces per wave and sub-buffer (+ the key-bias piece with Ka).
   bool in_seg = false, online = false;
   float cqh = 0.f;
-  auto kt_step = [&](auto fc, int kt) __attribute__((always_inline)) {
-    constexpr int F = decltype(fc)::value;
-    constexpr bool V16 = (F & XA_V16) != 0, K16 = (F & XA_K16) != 0;
-    constexpr int NKP = K16 ? 2 : 4, NVP = V16 ? 2 : 4;   // pieces per wave and sub-buffer: what the counted waits count
+  auto kt_step = [&](int kt) __attribute__((always_inline)) {
+    constexpr int NKP = 4, NVP = 4;   // pieces per wave and sub-buffer: what the counted waits count
     const bool last_in_seg = kt + 1 == cT;
     Tile nxt;   // the tile of the step after this one
-    nxt.k = last_in_seg ? nseg_t.k : cur.k + (K16 ? 32768 : XA_KEYS * CFD_D * 4);
-    nxt.v = last_in_seg ? nseg_t.v : cur.v + (V16 ? 32768 : 128);
+    nxt.k = last_in_seg ? nseg_t.k : cur.k + XA_KEYS * CFD_D * 4;
+    nxt.v = last_in_seg ? nseg_t.v : cur.v + 128;
     nxt.cb = last_in_seg ? nseg_t.cb : cur.cb + XA_KEYS;
     nxt.rowb = last_in_seg ? nseg_t.rowb : cur.rowb;
     nxt.vlane = last_in_seg ? nseg_t.vlane : cur.vlane;
     nxt.cblane = last_in_seg ? nseg_t.cblane : cur.cblane;
     const int slot = step & 1;
     if (!primed) {   // (re)start of the pipeline: Ka (+ key bias), Kb, Va of this step; Vb follows behind mid-A0
-      fill_k(fc, cur, 0, slot);
-      fill_k(fc, cur, 1, slot);
-      fill_v(fc, cur, 0);
+      fill_k(cur, 0, slot);
+      fill_k(cur, 1, slot);
+      fill_v(cur, 0);
       XA_WAIT_VM_LGKM0(NKP + NVP);       // Ka + key bias landed (Kb and Va are younger)
       __builtin_amdgcn_s_barrier();
-      read_k(fc, fa, 0, 0);
+      read_k(fa, 0, 0);
       primed = true;
       XA_T(0);
     }
     f32x4 s0 = f32x4{cqh, cqh, cqh, cqh}, s1 = s0;
     // ---- A0 (fa holds its first half) --------------------------------------------------------------------------------
-    read_k(fc, fb, 0, 1);
+    read_k(fb, 0, 1);
     __builtin_amdgcn_sched_barrier(0);
-    if (in_seg) mfma_k(fc, s0, fa, 0);
+    if (in_seg) mfma_k(s0, fa, 0);
     __builtin_amdgcn_sched_barrier(0);
     XA_T(1);
     XA_WAIT_VM_LGKM0(NVP);               // Kb landed (Va's pieces are younger); this wave's reads of Ka's first half are done
     __builtin_amdgcn_s_barrier();        // mid-A0: Kb ready; every wave is done with Vb
     XA_T(2);
-    fill_v(fc, cur, 1);
-    read_k(fc, fa, 1, 0);
+    fill_v(cur, 1);
+    read_k(fa, 1, 0);
     __builtin_amdgcn_sched_barrier(0);
     if (in_seg) {
-      mfma_k(fc, s0, fb, 1);
+      mfma_k(s0, fb, 1);
       *reinterpret_cast<f32x4*>(xch_mine) = s0;
     }
     __builtin_amdgcn_sched_barrier(0);
     // ---- A1 ---------------------------------------------------------------------------------------------------------
-    read_k(fc, fb, 1, 1);
+    read_k(fb, 1, 1);
     __builtin_amdgcn_sched_barrier(0);
-    if (in_seg) mfma_k(fc, s1, fa, 0);
+    if (in_seg) mfma_k(s1, fa, 0);
     __builtin_amdgcn_sched_barrier(0);
     if (in_seg) {
-      mfma_k(fc, s1, fb, 1);
+      mfma_k(s1, fb, 1);
       *reinterpret_cast<f32x4*>(xch_mine + 1024) = s1;
     }
     XA_T(3);
     XA_WAIT_VM_LGKM0(0);                 // Va and Vb landed (nothing younger is in flight); partial scores written
     __builtin_amdgcn_s_barrier();        // end of A1: the whole V^T tile ready, partial scores visible, every wave is done with Ka and Kb
     XA_T(4);
-    fill_k(fc, nxt, 0, slot ^ 1);
-    fill_k(fc, nxt, 1, slot ^ 1);
-    read_v(fc, fa, 0);
-    if (in_seg && !(XA_ABLATE & 8)) softmax_tile(s0, s1, slot, online, cj, kt);
+    fill_k(nxt, 0, slot ^ 1);
+    fill_k(nxt, 1, slot ^ 1);
+    read_v(fa, 0);
+    if (in_seg) softmax_tile(s0, s1, slot, online, cj, kt);
     // ---- B0 (fa holds its first half) --------------------------------------------------------------------------------
     XA_T(10);
-    read_v(fc, fb, 1);
+    read_v(fb, 1);
     __builtin_amdgcn_sched_barrier(0);
-    if (in_seg) mfma_v(fc, fa, 0);
+    if (in_seg) mfma_v(fa, 0);
     __builtin_amdgcn_sched_barrier(0);
     XA_T(5);
-    read_v(fc, fa, 2);
+    read_v(fa, 2);
     __builtin_amdgcn_sched_barrier(0);
-    if (in_seg) mfma_v(fc, fb, 1);
+    if (in_seg) mfma_v(fb, 1);
     __builtin_amdgcn_sched_barrier(0);
     // ---- B1 ---------------------------------------------------------------------------------------------------------
-    read_v(fc, fb, 3);
+    read_v(fb, 3);
     __builtin_amdgcn_sched_barrier(0);
-    if (in_seg) mfma_v(fc, fa, 2);
+    if (in_seg) mfma_v(fa, 2);
     __builtin_amdgcn_sched_barrier(0);
     XA_T(7);
     XA_WAIT_VM_LGKM0(NKP);               // next Ka + key bias landed (the next Kb's pieces are younger)
     __builtin_amdgcn_s_barrier();        // mid-B1: next Ka ready; every wave is done with Va
     XA_T(8);
-    fill_v(fc, nxt, 0);
-    read_k(fc, fa, 0, 0);                // first half of the next step's A0
+    fill_v(nxt, 0);
+    read_k(fa, 0, 0);                    // first half of the next step's A0
     __builtin_amdgcn_sched_barrier(0);
-    if (in_seg) mfma_v(fc, fb, 3);
+    if (in_seg) mfma_v(fb, 3);
     __builtin_amdgcn_sched_barrier(0);
     cur = nxt;
     ++step;
     XA_T(9);
   };
-  // One key-tile step with BOTH tiles as single fp16, double-buffered (instances with XA_DBUF).  A K tile and a V^T tile are 32 KB each, so
+  // One key-tile step with BOTH tiles as single fp16, double-buffered (the F16 instance).  A K tile and a V^T tile are 32 KB each, so
   // the two 64 KB tile buffers hold TWO of each: step n computes out of slot n & 1 while tile n + 1 lands in the other slot -- its K
   // requested behind the step's first barrier, its V^T behind the second, i.e. every fill has a whole step (four sub-phases) to land instead
   // of 1.5 - 2.5, and a step has TWO barriers instead of three:
@@ -928,13 +843,22 @@ __global__ void __launch_bounds__(XA_WAVES * 64, 2) xattn_fused_kernel(const XAt
     }
     const char* kb = kf_a + slot * 32768;
     const char* vb = vf_a + slot * 32768;
+    // single fp16: fr[i] = fragment i, fr[4..7] unused; the query fragments / probabilities enter as their `hi` half
     auto rd_k = [&](spx8 (&fr)[8], int t, int hf) __attribute__((always_inline)) {
 #pragma unroll
-      for (int i = 0; i < 4; ++i) fr[i] = XA_FRAG(kb + t * 16384 + (4 * hf + i) * 1024);
+      for (int i = 0; i < 4; ++i) fr[i] = *reinterpret_cast<const spx8*>(kb + t * 16384 + (4 * hf + i) * 1024);
     };
     auto rd_v = [&](spx8 (&fr)[8], int qf) __attribute__((always_inline)) {
 #pragma unroll
-      for (int i = 0; i < 4; ++i) fr[i] = XA_FRAG(vb + (4 * qf + i) * 1024);
+      for (int i = 0; i < 4; ++i) fr[i] = *reinterpret_cast<const spx8*>(vb + (4 * qf + i) * 1024);
+    };
+    auto mm_k = [&](f32x4& acc, const spx8 (&fr)[8], int hf) __attribute__((always_inline)) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) acc = SP_MFMA(fr[i], qh[4 * hf + i], acc, 0, 0, 0);
+    };
+    auto mm_v = [&](const spx8 (&fr)[8], int qf) __attribute__((always_inline)) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) o[4 * qf + i] = SP_MFMA(fr[i], ph, o[4 * qf + i], 0, 0, 0);
     };
     f32x4 s0 = f32x4{cqh, cqh, cqh, cqh}, s1 = s0;
     XA_T(1);
@@ -945,21 +869,21 @@ __global__ void __launch_bounds__(XA_WAVES * 64, 2) xattn_fused_kernel(const XAt
     rd_k(fb, 0, 1);
     fill_k_full(nxt, slot ^ 1);
     __builtin_amdgcn_sched_barrier(0);
-    if (in_seg) mfma_k(fmt_long{}, s0, fa, 0);
+    if (in_seg) mm_k(s0, fa, 0);
     __builtin_amdgcn_sched_barrier(0);
     rd_k(fa, 1, 0);
     __builtin_amdgcn_sched_barrier(0);
     if (in_seg) {
-      mfma_k(fmt_long{}, s0, fb, 1);
+      mm_k(s0, fb, 1);
       *reinterpret_cast<f32x4*>(xch_mine) = s0;
     }
     __builtin_amdgcn_sched_barrier(0);
     rd_k(fb, 1, 1);
     __builtin_amdgcn_sched_barrier(0);
-    if (in_seg) mfma_k(fmt_long{}, s1, fa, 0);
+    if (in_seg) mm_k(s1, fa, 0);
     __builtin_amdgcn_sched_barrier(0);
     if (in_seg) {
-      mfma_k(fmt_long{}, s1, fb, 1);
+      mm_k(s1, fb, 1);
       *reinterpret_cast<f32x4*>(xch_mine + 1024) = s1;
     }
     XA_T(3);
@@ -968,23 +892,23 @@ __global__ void __launch_bounds__(XA_WAVES * 64, 2) xattn_fused_kernel(const XAt
     XA_T(4);
     rd_v(fa, 0);
     fill_v_full(nxt, slot ^ 1);
-    if (in_seg && !(XA_ABLATE & 8)) softmax_tile(s0, s1, slot, online, cj, kt);
+    if (in_seg) softmax_tile(s0, s1, slot, online, cj, kt);
     XA_T(10);
     rd_v(fb, 1);
     __builtin_amdgcn_sched_barrier(0);
-    if (in_seg) mfma_v(fmt_long{}, fa, 0);
+    if (in_seg) mm_v(fa, 0);
     __builtin_amdgcn_sched_barrier(0);
     XA_T(5);
     rd_v(fa, 2);
     __builtin_amdgcn_sched_barrier(0);
-    if (in_seg) mfma_v(fmt_long{}, fb, 1);
+    if (in_seg) mm_v(fb, 1);
     __builtin_amdgcn_sched_barrier(0);
     rd_v(fb, 3);
     __builtin_amdgcn_sched_barrier(0);
-    if (in_seg) mfma_v(fmt_long{}, fa, 2);
+    if (in_seg) mm_v(fa, 2);
     __builtin_amdgcn_sched_barrier(0);
     XA_T(7);
-    if (in_seg) mfma_v(fmt_long{}, fb, 3);
+    if (in_seg) mm_v(fb, 3);
     __builtin_amdgcn_sched_barrier(0);
     cur = nxt;
     ++step;
@@ -1016,8 +940,8 @@ __global__ void __launch_bounds__(XA_WAVES * 64, 2) xattn_fused_kernel(const XAt
       atomicAdd(cen + 2, seen);
     }
   };
-  // The segments [s0, s1) of the workgroup's list, all in the format `fc`.
-  auto seg_loop = [&](auto fc, int s0, int s1) __attribute__((always_inline)) {
+  // The segments [s0, s1) of the workgroup's list, all with single-fp16 tiles (`f16`: std::true_type) or all split pairs.
+  auto seg_loop = [&](auto f16, int s0, int s1) __attribute__((always_inline)) {
   for (int si = s0; si < s1; ++si) {
     in_seg = active && ((cmask >> tile) & 1);   // wave-uniform, the same for both waves of a pair
     online = (cflags & XA_ONLINE) != 0;
@@ -1030,10 +954,10 @@ __global__ void __launch_bounds__(XA_WAVES * 64, 2) xattn_fused_kernel(const XAt
     // add up to S_raw + c_q (a + b = b + a: the same in both waves of the pair)
     cqh = cq_mine[l15 * 5 + cj];
     XA_T(11);
-    if constexpr ((decltype(fc)::value & XA_DBUF) != 0) {
+    if constexpr (decltype(f16)::value) {
       for (int kt = 0; kt < cT; ++kt) kt_step_db(kt);
     } else {
-      for (int kt = 0; kt < cT; ++kt) kt_step(fc, kt);
+      for (int kt = 0; kt < cT; ++kt) kt_step(kt);
     }
     if (in_seg) {
       float wsum = xlane_sum(wl);
@@ -1062,27 +986,27 @@ __global__ void __launch_bounds__(XA_WAVES * 64, 2) xattn_fused_kernel(const XAt
     cT = nT; cmask = nmask; cflags = nflags; cj = nj;   // (cur already points at the next segment's first tile)
   }
   };
-  if constexpr (OPF != 0) {
+  if constexpr (F16) {
     // The host lists a workgroup's long memories first (make_xattn_worklist): the segments with single-fp16 tiles are a PREFIX of the list,
     // n16 of them.  Two loops one behind the other -- not two bodies inside one loop, which hipcc could not fit into 256 registers -- with
     // the pipeline drained and primed again in between (once per workgroup).
     const int n16 = min(wgp->n16, nseg);
     if (n16 > 0) {
-      set_format((OPF & XA_K16) != 0, (OPF & XA_V16) != 0);
-      seg_loop(fmt_long{}, 0, n16);
+      set_format(true);
+      seg_loop(std::true_type{}, 0, n16);
     }
     if (n16 < nseg) {
       if (n16 > 0) {
         XA_WAIT_VM_LGKM0(0);
         __builtin_amdgcn_s_barrier();   // nothing of the other format in flight or in use when the pair pipeline starts
         primed = false;
-        set_format(false, false);
+        set_format(false);
         seg_tile(n16, cur, cT, cmask, cflags, cj);
       }
-      seg_loop(fmt_pair{}, n16, nseg);
+      seg_loop(std::false_type{}, n16, nseg);
     }
   } else {
-    seg_loop(fmt_pair{}, 0, nseg);
+    seg_loop(std::false_type{}, 0, nseg);
   }
   flush_request(true);
   XA_WAIT_VM_LGKM0(0);

@@ -157,15 +157,14 @@ typedef struct {
                                  cfd_sample_begin fails with CFD_E_SHAPE and the caller takes the maps with one cfd_forward per
                                  iteration).  The ring's size is the caller's business: iterations x B x layers x L x keys. */
   int operand_policy;         /* Operand format of the fused cross-attention's key / value tiles of the LONG memories (>= 128 padded keys: the
-                                 audio memory) in THIS run (csrc/xattn_fused.hpp, OPF):
+                                 audio memory) in THIS run (csrc/xattn_fused.hpp, F16):
                                  0 = fp16 split pairs everywhere (3 MFMAs per product, ~2^-22 operand error: what cfd_forward always uses);
-                                 bit 0 = their folded VALUES as single fp16 (the linear path of the attention; halves those tiles' L2 -> LDS
-                                 traffic); bit 1 = their folded KEYS as single fp16 (the exponentiated path); bit 2 / bit 3 = the
-                                 PROBABILITIES / the QUERIES of those products as one fp16 as well, i.e. plain fp16 attention against the long
-                                 memories (1 MFMA per product instead of 3).  The shipped library implements the four bits together (any
-                                 non-zero value = 15; the partial combinations were measured and are dominated: DESIGN.md section 2).
+                                 non-zero in bits 0 - 3 (15 by convention) = plain fp16 attention against the long memories: their folded
+                                 keys and values as single-fp16 tiles (half those tiles' L2 -> LDS traffic), the queries and probabilities
+                                 of those products as one fp16 as well (1 MFMA per product instead of 3).  Partial combinations were
+                                 measured and are dominated.
                                  Short memories (the text / speaker / activity memories: few keys, little averaging of the rounding) always
-                                 keep pairs.  The reference is float32 throughout (cross_attention.py:593-652); which runs tolerate which bits
+                                 keep pairs.  The reference is float32 throughout (cross_attention.py:593-652); which runs tolerate the format
                                  is measured per scheduler in DESIGN.md section 2 -- convofusion_amd.sampler.OPERAND_POLICY holds the default
                                  per scheduler kind.  Ignored (pairs) on the row-tile path, with att_ring, and with a dynamic memory. */
   float census_tau;           /* > 0: the run keeps an attention-concentration census of its long memories (cfd_sample_census): the fused

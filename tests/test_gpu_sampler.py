@@ -833,7 +833,7 @@ def test_tile_kernel_forms_agree_on_random_shapes():
 
 
 def test_operand_policies_of_the_fused_cross_attention():
-    """cfd_sample_args.operand_policy (xattn_fused.hpp, OPF): the folded values (bit 0) / keys (bit 1) of the LONG memories (>= 128 padded
+    """cfd_sample_args.operand_policy (xattn_fused.hpp, F16): the folded values (bit 0) / keys (bit 1) of the LONG memories (>= 128 padded
     keys) as single fp16 tiles.  Policy 0 is the split-pair kernel of every other test.  The single-fp16 instances read tiles that
     xa_pack16_kernel re-lays once per run (tile-major, pre-swizzled), run the long memories' segments in a loop of their own (other piece
     counts behind the counted waits; both formats: a double-buffered tile pipeline) and drain the pipeline before the short memories' pair

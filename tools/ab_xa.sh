@@ -1,6 +1,6 @@
 #!/bin/bash
 # Developer tool (GPU box): the operand policies of the fused cross-attention kernel (CFD_XA_OPERANDS = 0 pairs / 15 single-fp16 operands
-# against the long memories; developer builds with -DXA_ALL_OPF=1 also take 3 / 7 / 11; xattn_fused.hpp OPF) on the bench workload, interleaved on ONE box.  usage: tools/ab_xa.sh [rounds] [modes...]
+# against the long memories; xattn_fused.hpp F16) on the bench workload, interleaved on ONE box.  usage: tools/ab_xa.sh [rounds] [modes...]
 rounds=${1:-2}
 shift
 modes=${@:-0 15}

@@ -1,5 +1,5 @@
 """Developer tool (GPU box): the error table of the fused cross-attention's operand policies (cfd_sample_args.operand_policy:
-0 = fp16 split pairs, 1 = folded values single fp16, 2 = folded keys single fp16, 3 = both) on every DDPM golden, through the
+0 = fp16 split pairs, 15 = single fp16 against the long memories; any non-zero value means 15) on every DDPM golden, through the
 parity tests' own code (their printed errors are collected; a failed threshold is recorded, not raised).
 
   python tools/xa_operands_table.py            headline-shape goldens (B = 32, L = 196, 1500 audio keys): ddpm5 / ddpm1000 x {b32, skip, b1_shard},
@@ -16,7 +16,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 SMALL = "--small" in sys.argv
-MODES = [int(a) for a in sys.argv[1:] if a.isdigit()] or [0, 3, 7, 11, 15]
+MODES = [int(a) for a in sys.argv[1:] if a.isdigit()] or [0, 15]
 os.environ.setdefault("CFD_FUSED_XATTN_MIN_WGS", "0")
 if SMALL:
     os.environ["CFD_ROWTILE"] = "0"

@@ -2,8 +2,6 @@
 // folding and re-layout of cfd_finalize_weights.
 #include "cfd_internal.hpp"
 
-int g_cfd_naive_gemm = 0;
-
 static thread_local char g_err[1024] = "";
 int fail(int code, const char* fmt, ...) {
   va_list ap;
@@ -15,6 +13,12 @@ int fail(int code, const char* fmt, ...) {
 
 // ---- create / destroy -----------------------------------------------------------------------------
 extern "C" const char* cfd_last_error(void) { return g_err; }
+
+// a developer knob (Ctx): the variable's value read with atoll, or `dflt` when it is not set
+static long long env_int(const char* name, long long dflt) {
+  const char* v = getenv(name);
+  return v ? atoll(v) : dflt;
+}
 
 #ifndef CFD_SOURCE_HASH
 #define CFD_SOURCE_HASH "unknown"
@@ -42,45 +46,19 @@ extern "C" int cfd_create(const cfd_config* cfg, cfd_handle* out) {
   c->cfg = *cfg;
   c->nl = cfg->num_layers;
   c->lw.resize(c->nl);
-  const char* env = getenv("CFD_NAIVE_GEMM");
-  g_cfd_naive_gemm = (env && atoi(env) != 0) ? 1 : 0;
-  env = getenv("CFD_RUNS");
-  c->use_runs = !(env && atoi(env) == 0);
-  env = getenv("CFD_WEG_GRAPH");
-  c->weg_graph_on = !(env && atoi(env) == 0);
+  // the developer knobs (Ctx, cfd_internal.hpp)
+  c->rt_on = env_int("CFD_ROWTILE", 1) != 0;
+  c->rt_max_rows = env_int("CFD_ROWTILE_MAX_ROWS", c->rt_max_rows);
+  c->weg_rt_on = env_int("CFD_WEG_ROWTILE", 1) != 0;
+  c->weg_graph_on = env_int("CFD_WEG_GRAPH", 1) != 0;
+  c->fused_xattn = env_int("CFD_FUSED_XATTN", 1) != 0;
+  c->fused_xattn_min_wgs = (int)env_int("CFD_FUSED_XATTN_MIN_WGS", c->fused_xattn_min_wgs);
+  c->l0_dedup = env_int("CFD_L0_DEDUP", 1) != 0;
+  c->share0 = env_int("CFD_SHARE0", 1) != 0;
+  c->permute = env_int("CFD_PERMUTE", 1) != 0;
+  c->ln_fold = (int)env_int("CFD_LN_FOLD", -1);
+  c->xa_operands = getenv("CFD_XA_OPERANDS") ? (int)env_int("CFD_XA_OPERANDS", 0) & 15 : -1;
   (void)hipEventCreateWithFlags(&c->weg_ev, hipEventDisableTiming);
-  env = getenv("CFD_FUSED_XATTN");
-  c->fused_xattn = !(env && atoi(env) == 0);
-  env = getenv("CFD_FUSED_XATTN_MIN_WGS");
-  if (env) c->fused_xattn_min_wgs = atoi(env);
-  env = getenv("CFD_L0_DEDUP");
-  if (env) c->l0_dedup = atoi(env) != 0;
-  env = getenv("CFD_XA_OPERANDS");
-  if (env) c->xa_operands = atoi(env) & 15;
-  env = getenv("CFD_LN_FOLD");
-  if (env) c->ln_fold = atoi(env);
-  env = getenv("CFD_ONE_KEY");
-  if (env) c->one_key = atoi(env) != 0;
-  env = getenv("CFD_RT_NFB2_TILES");
-  if (env) c->rt_nfb2_tiles = atoi(env);
-  env = getenv("CFD_STEP_ROWS");
-  if (env) c->step_rows = atoi(env) != 0;
-  env = getenv("CFD_ATT_FUSED");
-  if (env) c->att_fused = atoi(env) != 0;
-  env = getenv("CFD_QKV_FUSED");
-  if (env) c->qkv_fused = atoi(env);
-  env = getenv("CFD_ROWTILE");
-  c->rt_on = !(env && atoi(env) == 0);
-  env = getenv("CFD_WEG_ROWTILE");
-  c->weg_rt_on = !(env && atoi(env) == 0);
-  env = getenv("CFD_ROWTILE_MAX_ROWS");
-  if (env) c->rt_max_rows = atoll(env);
-  env = getenv("CFD_HOIST_MEMSIDE");
-  c->hoist_memside = !(env && atoi(env) == 0);
-  env = getenv("CFD_PERMUTE");
-  c->permute = !(env && atoi(env) == 0);
-  env = getenv("CFD_SHARE0");
-  c->share0 = !(env && atoi(env) == 0);
   for (Work& wk : c->wk) {
     if (wk.d_step.ensure(16) != CFD_OK) { delete c; return CFD_E_HIP; }
     if (hipMemset(wk.d_step.p, 0, 16) != hipSuccess) { delete c; return fail(CFD_E_HIP, "memset"); }

@@ -79,8 +79,9 @@ int enqueue_rows_rt(Ctx* c, hipStream_t st, const RtSave* sv) {
   base.L = L; base.tpr = tpr;
   // Two 16-feature blocks per workgroup for the 512 x 512 residual products from two utterances on: half the workgroups, each normalising
   // its 16 rows once for two blocks (one utterance: 0.411 -> 0.421 s per 1000 steps, two: 0.544 -> 0.528, four: 0.882 -> 0.869; same sums
-  // in the same order, so bit-identical).  CFD_RT_NFB2_TILES=<token tiles> moves the threshold (read at cfd_create).
-  const bool nfb2 = ntile >= c->rt_nfb2_tiles && !sv;
+  // in the same order, so bit-identical).  Counted in token tiles: 14 are two utterances of 7 guidance rows at L = 16.
+  const int RT_NFB2_MIN_TILES = 14;
+  const bool nfb2 = ntile >= RT_NFB2_MIN_TILES && !sv;
 #define RT_LAUNCH(cls, PRO, EPI, NT, KT, NFB, nfeat, args)                                                        \
   do {                                                                                                          \
     Bracket _br(c, cls, st);                                                                                    \
@@ -226,8 +227,8 @@ int enqueue_rows(Ctx* c, hipStream_t st, int row0, int Be) {
     want_att = want_att || p.att[j];
   }
   if (p.att_fused) want_att = false;   // (the ring of a sampling run on the tile kernels: the fused kernel keeps the maps itself)
-  // one fused kernel per layer for the cross-attention block, unless att_mats are wanted (or the naive debug GEMMs)
-  const bool fused_x = c->fused_xattn && p.xa_nwg > 0 && !want_att && !g_cfd_naive_gemm && row0 == 0 && Be == p.Be;
+  // one fused kernel per layer for the cross-attention block, unless att_mats are wanted
+  const bool fused_x = c->fused_xattn && p.xa_nwg > 0 && !want_att && row0 == 0 && Be == p.Be;
 
   // rows that run the replica-independent head of the network (see Problem::share_B)
   const bool share = p.share_B > 0 && row0 == 0 && Be == p.Be && Be % p.share_B == 0 && Be > p.share_B && !c->stop_stage;
@@ -249,7 +250,7 @@ int enqueue_rows(Ctx* c, hipStream_t st, int row0, int Be) {
   const float* ss_now = c->w->ss_tab.as<float>();
   const float *kb_now[CFD_NMEM], *vb_now[CFD_NMEM];
   for (int j = 0; j < CFD_NMEM; ++j) { kb_now[j] = c->w->kbtab[j].as<float>(); vb_now[j] = c->w->vbtab[j].as<float>(); }
-  const bool rows_now = p.tmode == 0 && c->step_rows;
+  const bool rows_now = p.tmode == 0;
   if (rows_now && p.T > 1) {
     RtStepRowsArgs ra;
     memset(&ra, 0, sizeof(ra));
@@ -294,7 +295,7 @@ int enqueue_rows(Ctx* c, hipStream_t st, int row0, int Be) {
   // per-row slot statistics, and the consumer (q | k | v^T in one launch, FFN1, latent_proj) runs on W diag(gamma) and rescales its accumulators.
   // Range: the launches launch_gemm gives the 64 x 64 / 128 x 64 classes anyway (launch_gemm_midsize); above it a ln_rows launch costs less than
   // the producer's wider epilogue (measured at the headline shape: +25.8 us against 14).
-  const bool ln_fold = c->ln_fold != 0 && L == 16 && c->qkv_fused && !g_cfd_naive_gemm && !c->stop_stage && row0 == 0 && Be == p.Be &&
+  const bool ln_fold = c->ln_fold != 0 && L == 16 && !c->stop_stage && row0 == 0 && Be == p.Be &&
                        (c->ln_fold > 0 || (M >= 512 && M <= 3840));   // (below: the row-tile path or a handful of workgroups; above: launch_gemm's 128 x 128 class)
   if (ln_fold) CHK(c->w->ln_stat.ensure((size_t)M * LN_SLOTS * 2 * 4));
   auto token_gemm_resid_stat = [&](const DBuf& w, int K, const char* y, const float* bias, long long rows, char* xs) -> int {
@@ -337,12 +338,12 @@ int enqueue_rows(Ctx* c, hipStream_t st, int row0, int Be) {
       av.X[0] = c->w->h_sp.as<char>(); av.ldx[0] = ROWB; av.xbs[0] = (long long)L * ROWB; av.I[0] = Lv; av.Iclamp[0] = L; av.kt[0] = CFD_D / 32;
       av.Y = w.wv_sp.as<char>(); av.ldy = ROWB; av.J = CFD_D; av.Jclamp = CFD_D;
       EpiSplit ev{c->w->vts_sp.as<char>(), (long long)Lv * 4, (long long)CFD_D * Lv * 4, 0, nullptr, 0, 1};
-      if (L == 16 && c->qkv_fused && !g_cfd_naive_gemm) {
+      if (L == 16) {
         // batch rows of exactly 16 tokens: both in ONE grouped launch, the value projection stored transposed by the epilogue (EpiQkvT)
         GemmArgs ag = a;
         ag.nslot = 2;
         ag.X[1] = w.wv_sp.as<char>(); ag.ldx[1] = ROWB; ag.I[1] = CFD_D; ag.Iclamp[1] = CFD_D; ag.kt[1] = CFD_D / 32;
-        EpiQkvT eg{c->w->qk_sp.as<char>(), 2 * ROWB, w.bqk.as<float>(), c->w->vts_sp.as<char>(), c->qkv_fused == 1 ? 1 : 0};
+        EpiQkvT eg{c->w->qk_sp.as<char>(), 2 * ROWB, w.bqk.as<float>(), c->w->vts_sp.as<char>(), 1};
         if (h_raw) {   // (layers 1..: the previous layer's second FFN product left raw rows + statistics)
           EpiLn<EpiQkvT> el;
           static_cast<EpiQkvT&>(el) = eg;
@@ -358,7 +359,7 @@ int enqueue_rows(Ctx* c, hipStream_t st, int row0, int Be) {
       CHK((run_gemm<MODE_PLAIN>(c, CFD_PROF_GEMM_TOKEN, av, ev, Ba, 1, st)));
       }
     }
-    if (qkv_one_launch && c->qkv_fused == 1) {
+    if (qkv_one_launch) {
       // one query tile and one key tile per (row, head): the row-tile path's attention core (4 waves that all compute; V^T in natural key
       // order, which EpiQkvT wrote) instead of the flash kernel's 8-wave workgroup with one busy wave
       RtSelfArgs a{c->w->qk_sp.as<char>(), c->w->vts_sp.as<char>(), c->w->o_sp.as<char>(), L, 1};
@@ -631,8 +632,8 @@ extern "C" int cfd_forward(cfd_handle c, const float* sample, int Be, int L, con
   CHK(enqueue_denoise(c, st));
   HIPCHK(hipMemcpyAsync(out, c->w->eps.p, (size_t)c->w->pb.M * CFD_LAT * 4, hipMemcpyDeviceToDevice, st));
   if (c->memside_in_forward || !c->w->pb.static_mask) {
-    // Paths whose memory-side projections run INSIDE the forward (per-row timesteps, att_mats on the tile kernels, CFD_HOIST_MEMSIDE=0,
-    // the three-launch cross-attention): their census -- and the sample's, which no earlier wait has read on these paths -- is read here,
+    // Paths whose memory-side projections run INSIDE the forward (per-row timesteps, att_mats on the tile kernels, the three-launch
+    // cross-attention): their census -- and the sample's, which no earlier wait has read on these paths -- is read here,
     // so that a clamped projection fails THIS call instead of the next one (on these paths the call therefore returns with `out` complete).
     HIPCHK(hipStreamSynchronize(st));
     c->memside_in_forward = false;
@@ -759,9 +760,10 @@ extern "C" int cfd_test_gemm_epi(cfd_handle c, cfd_test_epi_args* t, void* strea
     el.ln_c[0] = el.ln_c[1] = cd; el.ln_d[0] = el.ln_d[1] = cd + I;
     if (qkvt) { el.ln_c[1] = cd + I0; el.ln_d[1] = cd + I + I0; }
   };
+  auto cfg_used = [](int cfg) { return cfg == 1 || cfg == 6 || cfg == 19 || cfg == 20 || cfg == 24 ? cfg : 3; };   // (launch_gemm's default: 3)
   auto plain = [&](const auto& e) -> hipError_t {
     const int cfg = t->tile_cfg ? t->tile_cfg : gemm_auto_cfg<MODE_PLAIN>(a, 1, 1);
-    t->tile_cfg_used = g_cfd_naive_gemm ? 0 : (cfg == 1 || cfg == 6 || cfg == 19 || cfg == 20 || cfg == 24) ? cfg : 3;
+    t->tile_cfg_used = cfg_used(cfg);
     return launch_gemm<MODE_PLAIN>(a, e, 1, 1, st, cfg);
   };
   EpiF32 ef;
@@ -780,7 +782,7 @@ extern "C" int cfd_test_gemm_epi(cfd_handle c, cfd_test_epi_args* t, void* strea
       break;
     case CFD_EPI_QKVT: {
       const int cfg = t->tile_cfg ? t->tile_cfg : gemm_auto_cfg<MODE_GROUPED>(a, 1, 1);
-      t->tile_cfg_used = g_cfd_naive_gemm ? 0 : (cfg == 1 || cfg == 6 || cfg == 19 || cfg == 20 || cfg == 24) ? cfg : 3;
+      t->tile_cfg_used = cfg_used(cfg);
       err = launch_gemm<MODE_GROUPED>(a, eq, 1, 1, st, cfg);
       break;
     }

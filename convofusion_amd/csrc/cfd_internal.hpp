@@ -137,7 +137,7 @@ struct Work {
   DBuf n_sp[CFD_NMEM], kall_sp[CFD_NMEM], cb[CFD_NMEM], vt_all[CFD_NMEM];
   DBuf temb_tab, h1_tab, ss_tab, trows, iota, long_rows, short_rows, zero_mask;
   // timestep-independent memory-side projections (rows.hpp mem_center_kernel): per memory the dot products c_l . a_s (ca), |a_s|^2 (asq)
-  // and, per table row t, A_l b_t / c_l . b_t (kbtab) and VV_l b_t (vbtab); b_t = centred timestep embedding.  CFD_HOIST_MEMSIDE=0: off.
+  // and, per table row t, A_l b_t / c_l . b_t (kbtab) and VV_l b_t (vbtab); b_t = centred timestep embedding.
   DBuf ca[CFD_NMEM], asq[CFD_NMEM], kbtab[CFD_NMEM], vbtab[CFD_NMEM], b_tab, b_sp, bsq, zeros512;
   DBuf xa_wgs, xa_segs, xa_stamps, xa0_wgs_a, xa0_segs_a, xa0_wgs_b, xa0_segs_b, xa_dedup, xa_one_va, xa_att_raw, xa_att_mc, xa_att_fin, xa_att_desc;
   DBuf d_step;  // [0] = loop index, [1] = constant 0, [2] = "this iteration's in-painting overwrite is done" (cfd_sample_inpaint)
@@ -208,50 +208,45 @@ struct cfd_handle_s {
   float acen_tau = 0.f;
   unsigned int* sat_mem() const { return sat.as<unsigned int>() + CFD_SAT_MEM; }
   unsigned int* sat_in() const { return sat.as<unsigned int>() + CFD_SAT_IN; }
-  bool hoist_memside = true;
-  bool use_runs = true;   // CFD_RUNS=0 disables the shared-memory run optimisation of the three-launch attention path
-  // The cross-attention block is one fused kernel (xattn_fused.hpp) unless the caller wants att_mats, which only the
-  // three-launch path (score products -> softmax_rows_kernel -> P.V products) materialises.  CFD_FUSED_XATTN=0 forces
-  // the three-launch path everywhere (parity A/B of the two paths).
-  bool fused_xattn = true;
-  int fused_xattn_min_wgs = 6;
-  int one_key = 1;              // CFD_ONE_KEY=0: a one-key memory (lsnemb) keeps its 32-key tile step in the fused cross-attention
   bool want_f16 = false;        // cfd_sample_begin -> setup_problem: the run asks for single-fp16 tiles (non-zero operand policy; false everywhere else)
-  int xa_operands = -1;         // CFD_XA_OPERANDS=0 / 15: overrides cfd_sample_args.operand_policy (developer A/B of the fused cross-attention's tile formats)
   bool hint_same_mem = false;   // cfd_forward_same_memories: the promise for the NEXT cfd_forward ...
   bool hint_now = false;        // ... taken (and cleared) at that call's very first line, before anything can fail: a call that returns early
                                 // must not leave the promise standing for the call after it
   bool census_pending = false;  // a cfd_weg_eval without loss_host left its census unread (it does not wait): settled by the next entry point
-  int rt_nfb2_tiles = 14;       // CFD_RT_NFB2_TILES=<token tiles>: from how many token tiles on the row-tile path's 512 x 512 residual products take two feature blocks per workgroup
-  int step_rows = 1;            // CFD_STEP_ROWS=0: the tile kernels index the per-step tables with the device step counter themselves
-  int att_fused = 1;            // CFD_ATT_FUSED=0: a forward that returns att_mats takes the three-launch cross-attention on the tile kernels (the fused
-                                // kernel's ATT instance keeps the maps otherwise: xattn_fused.hpp, XaAtt)
-  int ln_fold = -1;             // CFD_LN_FOLD: the algebraic LayerNorm fold of mid-size problems (cfd_forward.hip): -1 by shape, 0 off, 1 wherever the launches allow it
-  int qkv_fused = 1;            // CFD_QKV_FUSED=0: batch rows of 16 tokens keep the separate v^T product (EpiQkvT, gemm_sp.hpp); 2: one launch, but
-                                // the flash self-attention kernel behind it (1: the row-tile path's attention core)
-  int l0_dedup = 1;             // CFD_L0_DEDUP=0: layer 0's cross-attention as one launch over all rows (build_xattn_layer0_lists)
-  // Row-tile path for small problems (rowtile.hpp): chosen by SHAPE -- at most rt_max_rows token rows of at most RT_MAX_L tokens per batch
-  // row, one timestep for all rows, no dynamic memories.  CFD_ROWTILE=0 turns it off (parity A/B against the tile kernels),
-  // CFD_ROWTILE_MAX_ROWS moves the threshold.
-  bool rt_on = true;
+  // Developer knobs, read from the environment once per handle (cfd_create).  Each forces a path the library
+  // also takes by itself for some shape or call; the parity tests use them as baselines.
+  //   CFD_ROWTILE=0               no row-tile path (rowtile.hpp) for small problems: the tile kernels everywhere.  The row-tile path is
+  //                               chosen by shape: at most rt_max_rows token rows of at most RT_MAX_L tokens per batch row, one timestep
+  //                               for all rows, no dynamic memories
+  //   CFD_ROWTILE_MAX_ROWS=<n>    moves that threshold
+  //   CFD_WEG_ROWTILE=0           cfd_weg_eval keeps the float32 launch sequence of weg_eval.hpp instead of the row-tile one (weg_rt.hpp)
+  //   CFD_WEG_GRAPH=0             cfd_weg_eval always runs eagerly (weg_graph)
+  //   CFD_FUSED_XATTN=0           the three-launch cross-attention (score products -> softmax_rows_kernel -> P.V products) everywhere
+  //                               instead of the fused kernel (xattn_fused.hpp)
+  //   CFD_FUSED_XATTN_MIN_WGS=<n> the fewest workgroups a work list needs for the fused kernel
+  //   CFD_L0_DEDUP=0              layer 0's cross-attention as one launch over all rows (build_xattn_layer0_lists)
+  //   CFD_SHARE0=0                the pre-cross-attention part of layer 0 for every guidance replica (Problem::share_B)
+  //   CFD_PERMUTE=0               a sampling run keeps the caller's chunk order (chunk_pos)
+  //   CFD_LN_FOLD=0 / 1           the algebraic LayerNorm fold of mid-size problems (cfd_forward.hip) off / wherever the launches allow
+  //                               it; unset (-1): by shape
+  //   CFD_XA_OPERANDS=0 / 15      overrides cfd_sample_args.operand_policy (the fused cross-attention's tile formats); unset: -1
+  bool rt_on = true, weg_rt_on = true, weg_graph_on = true, fused_xattn = true, l0_dedup = true, share0 = true, permute = true;
   long long rt_max_rows = 700;    // measured crossover at the product shape (L = 16), seconds per 1000 steps, row-tile vs tile kernels (profiles/r05_rowtile_crossover.log:
                                   // the short cross-attention work lists of round 5 made the tile kernels faster): 5 utterances 1.04 / 1.22, 6: 1.18 / 1.24, 7: 1.34 / 1.23
-  bool share0 = true;       // CFD_SHARE0=0: evaluate the pre-cross-attention part of layer 0 for every guidance replica
+  int fused_xattn_min_wgs = 6, ln_fold = -1, xa_operands = -1;
   DBuf weg_ws, weg_tok;   // cfd_weg_eval: activation arena, focus-token tables
   // cfd_weg_eval replays its ~400 launches as a hipGraph.  A graph holds its kernels' arguments BY VALUE, so everything the
   // caller passes per call -- latents in, losses / max_att / grad out, the timestep's sinusoid row -- goes through fixed
   // staging buffers (weg_io); round 1's attempt captured the caller's own pointers, which are fresh torch tensors on every
   // call, and so replayed against stale addresses ("wrong gradients when interleaved with the sampling graph").
   // One graph per variant (full evaluation / memory-side results reused), keyed by everything else the launches depend on;
-  // a key is run eagerly once (function attributes, warm-up) and captured on its second use.  CFD_WEG_GRAPH=0: always eager.
+  // a key is run eagerly once (function attributes, warm-up) and captured on its second use.
   DBuf weg_io;
-  // Row-tile evaluation (weg_rt.hpp): the product path for small problems; CFD_WEG_ROWTILE=0 keeps the float32 launch sequence of weg_eval.hpp
-  bool weg_rt_on = true;
+  // Row-tile evaluation (weg_rt.hpp): the product path for small problems
   DBuf weg_rt_ws;
   WegRtState wrt;
   int weg_t_host = 0;   // the evaluation's timestep, copied to wk[1].trows in front of every launch sequence (one-row tables)
   int weg_dstep_host = 0;   // ... and the table row it selects, copied to wk[1].d_step (0 for one-row tables, the timestep for full tables)
-  bool weg_graph_on = true;
   struct WegGraph { std::vector<long long> key; int uses = 0; hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; };
   WegGraph weg_graph[2];
   hipEvent_t weg_ev = nullptr;
@@ -279,10 +274,9 @@ struct cfd_handle_s {
   // chunk_pos[k] * B.  Chunks whose rows all use ONE shared copy of the largest memory (the unconditional audio
   // memory: 5 of the 7 guidance chunks, not adjacent in the reference's order) are moved next to each other, so
   // their attention against it is one un-batched product instead of one per contiguous run.  Every per-row result
-  // is unchanged (rows are independent); the guidance combine reads chunk k at its position.  CFD_PERMUTE=0: off.
+  // is unchanged (rows are independent); the guidance combine reads chunk k at its position.
   int chunk_pos[8];
   DBuf perm_map[CFD_NMEM];
-  bool permute = true;
   int run_pos = 0;
 };
 typedef cfd_handle_s Ctx;
@@ -442,7 +436,7 @@ int enqueue_to_split(Ctx* c, int cls, hipStream_t st, const float* src, char* ds
 // the LayerNorm fold's weight side (cfd_core.hip, null stream): dst_sp = split(W diag(gamma)) [R][K], cvec = W' 1, dvec = W beta; tmp: scratch
 int ln_fold_weight(Ctx* c, const float* W, int R, int K, const float* gamma, const float* beta, DBuf& tmp, DBuf& dst_sp, float* cvec, float* dvec);
 // cfd_problem.hip: work lists, problem set-up, timestep tables, memory-side projections
-int build_xattn_worklist(Ctx* c, const cfd_memory mem[CFD_NMEM]);
+int build_xattn_worklist(Ctx* c, const cfd_memory mem[CFD_NMEM], bool one_key);
 int build_xattn_layer0_lists(Ctx* c, const cfd_memory mem[CFD_NMEM]);
 int setup_att_fused(Ctx* c);
 int setup_problem(Ctx* c, int Be, int L, const cfd_memory mem[CFD_NMEM], float* const att[CFD_NMEM], int tmode, int T);

@@ -135,7 +135,7 @@ static int upload_worklist(DBuf& dw, DBuf& ds, const std::vector<XaWg>& wgs, con
   return CFD_OK;
 }
 
-int build_xattn_worklist(Ctx* c, const cfd_memory mem[CFD_NMEM]) {
+int build_xattn_worklist(Ctx* c, const cfd_memory mem[CFD_NMEM], bool one_key) {
   Problem& p = c->w->pb;
   p.xa_nwg = 0; p.xa0_nwg_a = 0; p.xa0_nwg_b = 0; p.xa_flush = false;
   if (!c->fused_xattn) return CFD_OK;
@@ -143,8 +143,9 @@ int build_xattn_worklist(Ctx* c, const cfd_memory mem[CFD_NMEM]) {
   CHK(read_row_maps(c, mem, hm));
   // A memory of ONE key whose key no instance masks is added as a vector in the kernel's flush instead of walking a 32-key tile step
   // (xattn_fused.hpp, XAttnArgs::one_j): it gets no segments.  (With the key masked the reference's softmax is NaN: that stays a segment.)
+  // `one_key` false: every memory keeps its segments (a one-key memory rewritten between iterations, prepare_static_memside).
   p.xa_one = -1;
-  if (c->one_key && c->hoist_memside && p.tmode == 0) {
+  if (one_key && p.tmode == 0) {
     for (int j = CFD_NMEM - 1; j >= 0 && p.xa_one < 0; --j) {
       if (p.S[j] != 1) continue;
       bool alive = true;
@@ -337,7 +338,7 @@ int setup_problem(Ctx* c, int Be, int L, const cfd_memory mem[CFD_NMEM], float* 
     }
   }
   p.jbig = -1; p.nruns = 0; p.nlong = 0; p.nshort = Be;
-  if (c->use_runs && tmode == 0) {
+  if (tmode == 0) {
     int jb = 0;
     for (int j = 1; j < CFD_NMEM; ++j)
       if (p.Sp[j] > p.Sp[jb]) jb = j;
@@ -366,7 +367,7 @@ int setup_problem(Ctx* c, int Be, int L, const cfd_memory mem[CFD_NMEM], float* 
       }
     }
   }
-  p.rt = c->rt_on && tmode == 0 && !g_cfd_naive_gemm && L <= RT_MAX_L && p.M <= c->rt_max_rows && p.Sp_tot <= RT_MAX_KEYS && c->hoist_memside;
+  p.rt = c->rt_on && tmode == 0 && L <= RT_MAX_L && p.M <= c->rt_max_rows && p.Sp_tot <= RT_MAX_KEYS;
   if (p.rt) {
     if (!keep_lists) p.rt_use_inst = Be <= RT_ARG_ROWS;
     for (int j = 0; j < CFD_NMEM && p.rt_use_inst && !keep_lists; ++j) {
@@ -387,10 +388,10 @@ int setup_problem(Ctx* c, int Be, int L, const cfd_memory mem[CFD_NMEM], float* 
   {
     bool any_att = false;
     for (int j = 0; j < CFD_NMEM; ++j) any_att = any_att || p.att[j];
-    p.att_fused = any_att && !p.rt && tmode == 0 && c->att_fused && c->fused_xattn && c->hoist_memside && !g_cfd_naive_gemm;
+    p.att_fused = any_att && !p.rt && tmode == 0 && c->fused_xattn;
     if (p.att_fused) { p.att_b0 = 0; p.att_nb = Be; }
   }
-  if (!keep_lists) CHK(build_xattn_worklist(c, mem));
+  if (!keep_lists) CHK(build_xattn_worklist(c, mem, true));
   if (p.att_fused && p.xa_nwg <= 0) { p.att_fused = false; p.att_nb = 0; }   // (a list too short for the fused kernel: three-launch path)
   if (p.att_fused && !keep_lists) CHK(setup_att_fused(c));
   const long long M = p.M;
@@ -489,14 +490,10 @@ int prepare_static_memside(Ctx* c, hipStream_t st, int dynamic_mask, bool want_a
       mem[j].data = p.mem[j]; mem[j].U = p.U[j]; mem[j].S = p.S[j]; mem[j].row_map = p.map[j];
       mem[j].key_padding_mask = p.has_mask[j] ? p.mask[j] : nullptr;
     }
-    const int keep = c->one_key;
-    c->one_key = 0;
-    const int r = build_xattn_worklist(c, mem);
-    c->one_key = keep;
-    CHK(r);
+    CHK(build_xattn_worklist(c, mem, false));
   }
-  const bool fused = p.rt || (c->fused_xattn && p.xa_nwg > 0 && !want_att && !g_cfd_naive_gemm);
-  if (!fused || !c->hoist_memside || p.tmode != 0) { p.xa_f16 = false; return CFD_OK; }
+  const bool fused = p.rt || (c->fused_xattn && p.xa_nwg > 0 && !want_att);
+  if (!fused || p.tmode != 0) { p.xa_f16 = false; return CFD_OK; }
   const int T = p.T;
   if (c->w->b_tab.bytes < (size_t)T * CFD_D * 4 || c->w->b_sp.bytes < (size_t)T * CFD_D * 4 || c->w->bsq.bytes < (size_t)T * 4)
     c->w->tt_mem_mask = 0;       // (a table that is reallocated is an empty one)

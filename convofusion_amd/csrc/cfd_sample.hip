@@ -199,8 +199,8 @@ extern "C" int cfd_sample_begin(cfd_handle c, const cfd_sample_args* args, void*
     Problem& pb = c->w->pb;
     // ... and on the tile kernels the fused cross-attention kernel has them in its softmax: its ATT instance keeps them, att_fixup_kernel
     // normalises them once per step (xattn_fused.hpp, XaAtt).  What cannot keep them: a run without the fused kernel (memories made per
-    // step: dynamic memories; the developer switches that turn it off).
-    const bool fused_ok = c->fused_xattn && pb.xa_nwg > 0 && c->hoist_memside && !g_cfd_naive_gemm;
+    // step: dynamic memories; CFD_FUSED_XATTN=0).
+    const bool fused_ok = c->fused_xattn && pb.xa_nwg > 0;
     if ((!pb.rt && !fused_ok) || s.dynamic_memory_mask)
       return fail(CFD_E_SHAPE, "att_ring needs the row-tile path or the fused cross-attention kernel (one timestep per step, no dynamic memory): "
                                "this run has L = %d, %lld token rows; take the maps with one forward per iteration instead", s.L, (long long)Be * s.L);
@@ -213,14 +213,14 @@ extern "C" int cfd_sample_begin(cfd_handle c, const cfd_sample_args* args, void*
     if (!pb.rt) {
       pb.att_fused = true;
       CHK(setup_att_fused(c));
-      CHK(build_xattn_worklist(c, mem_in));   // (once more: the list now says which tiles keep their maps)
+      CHK(build_xattn_worklist(c, mem_in, true));   // (once more: the list now says which tiles keep their maps)
       if (pb.xa_nwg <= 0) return fail(CFD_E_SHAPE, "att_ring: the fused cross-attention work list is empty");
     }
   }
   CHK(build_xattn_layer0_lists(c, mem_in));
   {   // (the rest of the operand policy's conditions; prepare_static_memside checks that every memory's projections are made once per run)
     Problem& pb = c->w->pb;
-    const bool fused_run = !pb.rt && c->fused_xattn && pb.xa_nwg > 0 && c->hoist_memside && !g_cfd_naive_gemm && !pb.att_fused && !s.dynamic_memory_mask;
+    const bool fused_run = !pb.rt && c->fused_xattn && pb.xa_nwg > 0 && !pb.att_fused && !s.dynamic_memory_mask;
     if (!fused_run) pb.xa_f16 = false;
     // the attention-concentration census (cfd_sample_args::census_tau): the same runs as the operand policy -- the others keep pairs anyway
     c->acen_tau = s.census_tau > 0.f ? s.census_tau : 0.f;
@@ -404,9 +404,9 @@ extern "C" int cfd_sample_read(cfd_handle c, float* out, int close) {
   HIPCHK(hipMemcpyAsync(out, c->latents.p, lat_bytes, hipMemcpyDeviceToDevice, c->run_stream));
   HIPCHK(hipStreamSynchronize(c->run_stream));
   CHK(settle_deferred_census(c));
-  // the census of everything the run's iterations counted (per-step projections of a dynamic memory, CFD_HOIST_MEMSIDE=0): read on
-  // every read of a run whose captured iteration has such launches, BEFORE the run is closed -- a run that fails here stays open and can be
-  // inspected or closed by the caller
+  // the census of everything the run's iterations counted (per-step projections of a dynamic memory, the three-launch cross-attention):
+  // read on every read of a run whose captured iteration has such launches, BEFORE the run is closed -- a run that fails here stays open
+  // and can be inspected or closed by the caller
   if (c->run_counts) CHK(check_saturation(c, "sampling run (the per-step projections of a memory)"));
   if (close) c->run_open = false;
   return CFD_OK;

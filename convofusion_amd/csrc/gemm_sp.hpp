@@ -884,48 +884,10 @@ gemm_sp_kernel(const GemmArgs a, const Epi epi) {
                                                   (int)gridDim.x, (int)gridDim.y, (int)gridDim.z);
 }
 
-// Reference kernel with the same operands / epilogues, one thread per (4 i, 1 j): used by the
-// CFD_NAIVE_GEMM=1 debug switch to separate MFMA-path bugs from host-side plumbing bugs.
-__device__ __forceinline__ float sp_load(const char* row, int col) {
-  const char* p = row + (size_t)(col >> 5) * 128 + (col & 31) * 2;
-  return (float)*reinterpret_cast<const sp_t*>(p) + (float)*reinterpret_cast<const sp_t*>(p + 64);
-}
-
-template <int MODE, class Epi>
-__global__ void gemm_sp_naive_kernel(const GemmArgs a, const Epi epi, int g_fixed) {
-  const int b = a.brow ? a.brow[blockIdx.y] : blockIdx.y, z = blockIdx.z;
-  const int g = g_fixed;
-  const int Ig = a.I[g];
-  const int nq = Ig / 4;
-  const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= (long long)nq * a.J) return;
-  const int i = (int)(idx % nq) * 4, j = (int)(idx / nq);
-  const char* yrow = a.Y + (long long)b * a.ybs + (long long)z * a.yzs + (long long)min(j, a.Jclamp - 1) * a.ldy;
-  float acc[4] = {0.f, 0.f, 0.f, 0.f};
-  int kbase = 0;
-  const int s0 = (MODE == MODE_SEGK) ? 0 : g, s1 = (MODE == MODE_SEGK) ? a.nslot : g + 1;
-  for (int s = s0; s < s1; ++s) {
-    const long long bi = a.xmap[s] ? a.xmap[s][b] : b;
-    const char* xs = a.X[s] + bi * a.xbs[s] + (long long)z * a.xzs;
-    if (MODE == MODE_SEGK) kbase = a.yk0[s] * 32;
-    for (int k = 0; k < a.kt[s] * 32; ++k) {
-      const float yv = sp_load(yrow, kbase + k);
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        acc[e] += sp_load(xs + (long long)min(i + e, a.Iclamp[s] - 1) * a.ldx[s], k) * yv;
-    }
-    kbase += a.kt[s] * 32;
-  }
-  if constexpr (Epi::kPrefetch) epi(g, b, z, i, j, f32x4{acc[0], acc[1], acc[2], acc[3]}, epi.prefetch(g, b, z, i, j));
-  else epi(g, b, z, i, j, f32x4{acc[0], acc[1], acc[2], acc[3]});
-}
-
 // ------------------------------------------------------------------------------------------------
 // Host-side launcher
 // ------------------------------------------------------------------------------------------------
 struct GemmCfgSel { int wi, wj, ti, tj; };
-
-extern int g_cfd_naive_gemm;  // set from CFD_NAIVE_GEMM env at cfd_create
 
 template <int WI, int WJ, int TI, int TJ, int NSTAGE, int MODE, class Epi>
 static hipError_t launch_cfg(GemmArgs a, const Epi& epi, int nb, int nz, hipStream_t st) {
@@ -991,16 +953,6 @@ static int gemm_auto_cfg(const GemmArgs& a, int nb, int nz) {
 template <int MODE, class Epi>
 static hipError_t launch_gemm(GemmArgs a, const Epi& epi, int nb, int nz, hipStream_t st, int cfg = 0) {
   if (a.nslot < 1) a.nslot = 1;
-  if (g_cfd_naive_gemm) {
-    const int ng = (MODE == MODE_GROUPED) ? a.nslot : 1;
-    for (int g = 0; g < ng; ++g) {
-      const long long n = (long long)(a.I[g] / 4) * a.J;
-      if (n == 0) continue;
-      hipLaunchKernelGGL((gemm_sp_naive_kernel<MODE, Epi>), dim3((unsigned)((n + 255) / 256), nb, nz), dim3(256), 0, st,
-                         a, epi, g);
-    }
-    return hipGetLastError();
-  }
   if (cfg == 0) cfg = gemm_auto_cfg<MODE>(a, nb, nz);
   switch (cfg) {
     case 1: return launch_cfg<2, 2, 4, 4, 2, MODE, Epi>(a, epi, nb, nz, st);

@@ -14,7 +14,7 @@ struct WorkGuard {   // the launches of an evaluation address Ctx::wk[1]; everyt
 };
 
 static bool eligible(Ctx* c, const cfd_weg_args* a) {
-  if (!c->rt_on || !c->weg_rt_on || !c->hoist_memside || g_cfd_naive_gemm) return false;
+  if (!c->rt_on || !c->weg_rt_on) return false;
   if (a->L > RT_MAX_L || (long long)a->B * a->L > c->rt_max_rows) return false;
   int sp = 0;
   for (int j = 0; j < CFD_NMEM; ++j) sp += (a->mem[j].S + 31) / 32 * 32;

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Developer tool (GPU box): one environment knob at the product shape (R: 32 utterances; and 8 / 16 utterances through sample()), interleaved.
-#   tools/experiments/ab_knob_R.sh CFD_QKV_FUSED=0 [rounds]
+#   tools/experiments/ab_knob_R.sh CFD_L0_DEDUP=0 [rounds]
 knob=$1; rounds=${2:-2}
 for r in $(seq $rounds); do
 for k in "" "$knob"; do

@@ -35,7 +35,7 @@ with torch.no_grad():
 out = out.cpu().numpy()
 got = out if rows_only else out[idx]
 per_row = [rel_l2(got[c], g["out5"][c]) for c in range(7)]
-print({k: os.environ.get(k) for k in ("CFD_HOIST_MEMSIDE", "CFD_FUSED_XATTN", "ATT", "ROWS_ONLY", "CFD_L0_DEDUP", "CFD_ONE_KEY")}, f"rel {rel_l2(got, g['out5']):.2e}", "per chunk", [f"{e:.1e}" for e in per_row])
+print({k: os.environ.get(k) for k in ("CFD_FUSED_XATTN", "ATT", "ROWS_ONLY", "CFD_L0_DEDUP")}, f"rel {rel_l2(got, g['out5']):.2e}", "per chunk", [f"{e:.1e}" for e in per_row])
 
 if os.environ.get("TAPS"):
     # residual stream of the listener-id chunk's row (chunk 5) after every sub-block against the numpy oracle's taps (needs ROWS_ONLY=1)

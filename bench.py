@@ -3,15 +3,21 @@
 196-token latents, 1500 audio tokens, 1000-step DDPM schedule, 7-way guidance => denoiser batch 224).
 
   python bench.py --gpus N --steps K --warmup W
+      the headline figure and nothing else: set-up, W warm-up and K timed iterations, the result line.
       N > 1 without a launcher environment: bench.py starts N worker processes itself (torch.distributed.run on
       127.0.0.1, one rank per GPU, RCCL); under the driver's own torch.distributed.run launch it is a rank.
   python bench.py ... --dump-outputs DIR
       also writes the latents the last timed step produced (float32) as DIR/latents.npy: equal arguments give equal inputs,
       so two builds can be compared output for output.
+  python bench.py ... --full
+      also everything else the benchmark measures, after the timed steps (about a minute more): per-kernel-class times and the rooflines
+      from one profiled eager forward, GPU clock / power readings, the same job without the zero-weight chunk and with split
+      pairs everywhere, the whole 1000-step run, the other BASELINE configurations and the CPU baseline.  --headline-only,
+      --no-secondary, --no-full-loop and --no-cpu-baseline leave parts of that out.
 
 One "step" = one iteration of the captured loop for the rank's 32 utterances: replicate latents x7,
 denoiser forward, guidance combine, scheduler step.  Inputs are resident in HBM before the timed region.
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and `cpu_baseline`.
+Prints ONE JSON line on rank 0; `roofline`, `kernel_classes` and `cpu_baseline` are in it with --full.
 """
 import argparse
 import json
@@ -402,6 +408,107 @@ def secondary_configs(model, device):
     return out
 
 
+def roofline_figures(prof, policy, ms_step, canon, shape):
+    """The --full line's rooflines and per-kernel classes: the algorithmic FLOPs of what one iteration launches over the class times
+    of ``prof`` (run.profile(): one eager forward, every launch bracketed by HIP events), put on the timed region's clock
+    ``ms_step``."""
+    # MFMAs issued per algorithmic product in the fused cross-attention: 3 with split pairs; the long memories' score products take 2
+    # with single-f16 keys (policy bit 1), their P.V products 2 with single-f16 values (bit 0); memories below 128 padded keys keep 3
+    sp = [(x + 31) // 32 * 32 for x in S]
+    long_frac = sum(x for x in sp if x >= 128) / float(sum(x for x in sp if x > 32) + sum(x for x in sp[:4] if x <= 32)) if shape == "C2" else 0.0
+    # (scores: 3 with pairs, 2 with single-f16 keys, 1 with single-f16 queries too; P.V likewise with values / probabilities)
+    sc = 1.0 if (policy & 10) == 10 else (2.0 if policy & 2 else 3.0)
+    pv = 1.0 if (policy & 5) == 5 else (2.0 if policy & 1 else 3.0)
+    xa_issue = 3.0 - long_frac * (3.0 - 0.5 * (sc + pv))
+    Be = G * B_PER_GPU
+    U = [B_PER_GPU + 1] * 5
+    share0 = os.environ.get("CFD_SHARE0", "1") != "0"
+    # distinct (utterance, audio instance) pairs of the 7-chunk pattern of make_inputs: the unconditional tensor + the utterance's own
+    l0_pairs = 2 * B_PER_GPU if (share0 and os.environ.get("CFD_L0_DEDUP", "1") != "0" and os.environ.get("CFD_FUSED_XATTN", "1") != "0") else None
+    ex = executed_gemm_flops(Be, L, S, U, shared_rows=B_PER_GPU if share0 else None, l0_pairs=l0_pairs,
+                             one_key=os.environ.get("CFD_ONE_KEY", "1") != "0" and os.environ.get("CFD_FUSED_XATTN", "1") != "0")
+    classes = {k: {"ms": round(v[0], 4), "launches": v[1]} for k, v in prof.items()}
+    once_per_run = {k: round(ex[k] / 1e12, 4) for k in ex if prof[k][1] == 0 and ex[k] > 0}
+    for k in once_per_run:      # not launched inside an iteration (memory-side projections: made once at cfd_sample_begin)
+        ex[k] = 0.0
+    # dominant kernel = gemm_sp_kernel (the token-side and memory-side products: the largest share of a step); the fused
+    # attention kernels (self_attn_fused_kernel = class gemm_attn, xattn_fused_kernel = class xattn) are listed per class
+    gk = ("gemm_token", "gemm_mem")
+    dom_ms = sum(prof[k][0] for k in gk)
+    dom_n = sum(prof[k][1] for k in gk)
+    achieved = sum(ex[k] for k in gk) / (dom_ms * 1e-3) / 1e12 if dom_ms > 0 else 0.0
+    traffic = xa_traffic = None
+    tpath = os.path.join(ROOT, "profiles", "hbm_traffic_gemm.json")
+    if os.path.exists(tpath) and shape == "C2":
+        tj = json.load(open(tpath))
+        traffic, xa_traffic = tj.get("bytes_per_launch_mean"), tj.get("xattn_bytes_per_launch")
+    for k in ex:
+        classes[k]["algorithmic_tflop"] = round(ex[k] / 1e12, 4)
+        classes[k]["tflops_eager"] = round(ex[k] / (prof[k][0] * 1e-3) / 1e12, 1) if prof[k][0] > 0 else None
+    xa_ms, xa_n = prof["xattn"]
+    xa_ach = ex["xattn"] / (xa_ms * 1e-3) / 1e12 if xa_ms > 0 else 0.0
+    # The fractions are quoted on the REPLAYED graph's clock: a class's share of the eager, event-bracketed forward times
+    # ms_per_step (the timed region).  The brackets and eager launch gaps inflate the class times by a few per cent; the
+    # shares are what the committed rocprofv3 kernel stats of the same command agree with (profiles/rNN_roofline.json,
+    # tools/profile_post.py).  The eager figures stay as achieved_eager / frac_eager.
+    class_sum = sum(v[0] for v in prof.values())
+    scale = ms_step / class_sum if class_sum > 0 else 1.0
+    achieved_eager, xa_eager = achieved, xa_ach
+    achieved, xa_ach = achieved_eager / scale, xa_eager / scale
+    for k in classes:
+        classes[k]["ms_eager"] = classes[k].pop("ms")
+        classes[k]["ms"] = round(prof[k][0] * scale, 4)          # share of the timed region (replayed graph)
+    for k in ex:
+        classes[k]["tflops"] = round(ex[k] / (prof[k][0] * scale * 1e-3) / 1e12, 1) if prof[k][0] > 0 else None
+        classes[k]["frac_of_peak"] = round(classes[k]["tflops"] / PEAK_BF16_TFLOPS, 4) if classes[k]["tflops"] else None
+    xattn_roofline = {"bound": "mfma", "kernel": "xattn_fused_kernel (the largest single symbol of the trace: LayerNorm2, scores, softmax, "
+                                                 "P.V and residual update of a layer's five cross-attentions in one launch)",
+                      "achieved": xa_ach, "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": xa_ach / PEAK_BF16_TFLOPS,
+                      "frac_issued": xa_issue * xa_ach / PEAK_BF16_TFLOPS, "mfma_per_product": xa_issue,
+                      "frac_of_issued_peak_div3": xa_ach / (PEAK_BF16_TFLOPS / 3.0),
+                      "achieved_eager": xa_eager, "frac_eager": xa_eager / PEAK_BF16_TFLOPS,
+                      "algorithmic_tflop_per_step": ex["xattn"] / 1e12,
+                      "launches_per_step": xa_n, "avg_launch_ms": xa_ms * scale / max(xa_n, 1), "avg_launch_ms_eager": xa_ms / max(xa_n, 1),
+                      "traffic": xa_traffic, "traffic_source": "profiles/hbm_traffic_gemm.json" if xa_traffic else None}
+    mfma_ms = sum(prof[k][0] for k in ex) * scale
+    all_mfma = sum(ex.values()) / (mfma_ms * 1e-3) / 1e12 if mfma_ms > 0 else 0.0
+    executed = sum(ex.values())
+    step_roofline = {"bound": "mfma", "executed_tflop_per_step": executed / 1e12, "executed_tflops": executed / (ms_step * 1e-3) / 1e12,
+                     "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": executed / (ms_step * 1e-3) / 1e12 / PEAK_BF16_TFLOPS,
+                     "frac_issued": (3.0 * (executed - ex["xattn"]) + xa_issue * ex["xattn"]) / (ms_step * 1e-3) / 1e12 / PEAK_BF16_TFLOPS,
+                     "canonical_tflop_per_step": canon / 1e12, "canonical_tflops": canon / (ms_step * 1e-3) / 1e12,
+                     "note": "whole step on the timed region's clock: executed = algorithmic FLOPs of every product launched inside an iteration "
+                             "(after de-duplication: shared layer-0 head, layer-0 audio attention per distinct pair, no one-key tile step); "
+                             "canonical = the reference formulation's FLOPs for the same step (SURVEY.md 8d)"}
+    return {
+        "roofline": {"bound": "mfma", "kernel": "gemm_sp_kernel (the matrix products launched inside one iteration: token side; the memory-side "
+                                                        "projections run once per run since round 2)", "achieved": achieved,
+                     "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": achieved / PEAK_BF16_TFLOPS,
+                     "frac_issued": 3.0 * achieved / PEAK_BF16_TFLOPS,
+                     "peak_div3": PEAK_BF16_TFLOPS / 3.0, "frac_of_issued_peak_div3": achieved / (PEAK_BF16_TFLOPS / 3.0),
+                     "achieved_eager": achieved_eager, "frac_eager": achieved_eager / PEAK_BF16_TFLOPS,
+                     "eager_to_replay_scale": scale,
+                     "algorithmic_tflop_per_step": sum(ex[k] for k in gk) / 1e12,
+                     "traffic": traffic,
+                     "traffic_source": "profiles/hbm_traffic_gemm.json (a committed rocprofv3 FETCH_SIZE x 2 + WRITE_SIZE profile of this "
+                                       "command, not a quantity of this run)" if traffic else None,
+                     "launches_per_step": dom_n, "avg_launch_ms": dom_ms * scale / max(dom_n, 1), "avg_launch_ms_eager": dom_ms / max(dom_n, 1),
+                     "all_mfma_kernels_achieved": all_mfma, "all_mfma_kernels_frac": all_mfma / PEAK_BF16_TFLOPS,
+                     "note": "achieved / frac = algorithmic (single-product) FLOPs of the launched GEMMs / the class's share of ms_per_step "
+                             "(the timed region of replayed hipGraph iterations); the shares come from ONE EAGER forward with every launch "
+                             "bracketed by a HIP-event pair on the launch stream (cfd_profile_forward) -- its class times sum to more than "
+                             "ms_per_step (the brackets cost that: achieved_eager / frac_eager are the un-scaled figures), the shares are what "
+                             "the committed rocprofv3 kernel stats of this command give (profiles/rNN_roofline.json); "
+                             "each product is issued as 3 f16 MFMAs, so the MFMA pipe sees 3x this and the ceiling of the "
+                             "f16x3 instruction mix is peak / 3 = 833 TFLOP/s (frac_of_issued_peak_div3); traffic = mean HBM bytes "
+                             "per launch from rocprofv3 FETCH_SIZE (x2, gfx950) + WRITE_SIZE (profiles/)"},
+        "roofline_xattn": xattn_roofline,
+        "roofline_step": step_roofline,
+        "kernel_classes": classes,
+        "tflop_once_per_run_not_per_step": once_per_run,
+    }
+
+
 def gpu_state(device):
     """Clock / power / temperature of the GPU right now (amdsmi through torch.cuda; None where the box does not answer): recorded at
     both ends of the timed region, so that a +-3 % difference between two boxes of the pool -- or a power-capped box -- can be told from a
@@ -481,12 +588,15 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true", help="after the headline figure, also measure everything else: per-kernel-class times and "
+                    "rooflines (one profiled eager forward), GPU state, the zero-weight-chunk and split-pairs variants, the whole 1000-step run, "
+                    "the other BASELINE configurations and the CPU baseline (the options below leave parts of that out)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--shape", default="C2", choices=["C2", "R"])
     ap.add_argument("--no-full-loop", action="store_true", help="skip the secondary whole-1000-step-run wall time")
     ap.add_argument("--no-secondary", action="store_true", help="skip the other BASELINE configurations (R, C1, WEG, C4, C5) appended to the line")
-    ap.add_argument("--headline-only", action="store_true", help="only the headline workload's launches (profiling passes): no zero-weight-chunk run, "
-                    "no whole-run wall time, no other configurations, no CPU baseline")
+    ap.add_argument("--headline-only", action="store_true", help="with --full, only the headline workload's launches (profiling passes): "
+                    "no zero-weight-chunk run, no whole-run wall time, no other configurations, no CPU baseline")
     ap.add_argument("--selftest-cpu", action="store_true", help="exercise only the N-rank launch path on CPU (gloo); no measurement")
     ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what they computed -- the latents of the whole batch "
                     "after the last timed step, float32 -- as DIR/latents.npy (rank 0; outside the timed region)")
@@ -545,7 +655,7 @@ def main():
     if world > 1:
         gather_latents(warm, world * B_PER_GPU)   # untimed: the collective's first use sets up its channels
     torch.cuda.synchronize()
-    state0 = gpu_state(device) if rank == 0 else None
+    state0 = gpu_state(device) if rank == 0 and args.full else None
     barrier()
     t0 = time.perf_counter()
     run.steps(args.steps)
@@ -556,7 +666,7 @@ def main():
     t_gather = time.perf_counter() - t0 - t_steps
     barrier()
     dt = time.perf_counter() - t0
-    state1 = gpu_state(device) if rank == 0 else None
+    state1 = gpu_state(device) if rank == 0 and args.full else None
     rank_ms = [1000.0 * dt / args.steps]
     rank_steps_ms, rank_gather_ms = [1000.0 * t_steps / args.steps], [1000.0 * t_gather]
     if world > 1:
@@ -586,13 +696,13 @@ def main():
     # per-kernel-class timing with HIP events on the launch stream: ONE EAGER forward of the whole batch, every launch bracketed by
     # an event pair (cfd_profile_forward).  The brackets cost a few per cent (the classes sum to more than ms_per_step, which is
     # the replayed graph); the roofline objects below are built from these class times, i.e. slightly pessimistic.
-    prof = run.profile()
+    prof = run.profile() if args.full else None
     run.close()
 
     # secondary measurement (NOT the headline value): same job without evaluating the full-conditioning chunk,
     # whose guidance weight is 7.5 * 0 in the reference (convofusion.py:538) -- identical latents, 6/7 of the work
     dt_skip = None
-    if not args.headline_only:
+    if args.full and not args.headline_only:
         run2 = open_run(skip_zero_weight_chunks=True)
         run2.steps(args.warmup)
         run2.read()
@@ -607,7 +717,7 @@ def main():
     # secondary measurement (NOT the headline value): the same job with fp16 split pairs EVERYWHERE (operand policy 0: the fused
     # cross-attention's key / value tiles of the audio memory as pairs too, what every round before round 6 ran and what DDIM runs keep)
     dt_pairs = None
-    if not args.headline_only:
+    if args.full and not args.headline_only:
         run4 = open_run(operands=0)
         run4.steps(args.warmup)
         run4.read()
@@ -622,7 +732,7 @@ def main():
     # secondary measurement: the ENTIRE 1000-step run of the same job (set-up, capture, 1000 replays, read), wall clock;
     # puts the sustained clock on record next to the short timed window above
     full_loop_s = None
-    if not args.no_full_loop and args.shape == "C2":
+    if args.full and not args.no_full_loop and args.shape == "C2":
         torch.cuda.synchronize()
         barrier()
         t2 = time.perf_counter()
@@ -639,76 +749,8 @@ def main():
         policy = int(os.environ["CFD_XA_OPERANDS"]) & 15 if "CFD_XA_OPERANDS" in os.environ else int(_sampler.OPERAND_POLICY[0])
         if policy:
             policy = 15        # (the shipped library implements the four bits together)
-        # MFMAs issued per algorithmic product in the fused cross-attention: 3 with split pairs; the long memories' score products take 2
-        # with single-f16 keys (policy bit 1), their P.V products 2 with single-f16 values (bit 0); memories below 128 padded keys keep 3
-        sp = [(x + 31) // 32 * 32 for x in S]
-        long_frac = sum(x for x in sp if x >= 128) / float(sum(x for x in sp if x > 32) + sum(x for x in sp[:4] if x <= 32)) if args.shape == "C2" else 0.0
-        # (scores: 3 with pairs, 2 with single-f16 keys, 1 with single-f16 queries too; P.V likewise with values / probabilities)
-        sc = 1.0 if (policy & 10) == 10 else (2.0 if policy & 2 else 3.0)
-        pv = 1.0 if (policy & 5) == 5 else (2.0 if policy & 1 else 3.0)
-        xa_issue = 3.0 - long_frac * (3.0 - 0.5 * (sc + pv))
         Be = G * B_PER_GPU
-        U = [B_PER_GPU + 1] * 5
         canon = canonical_flops_per_step(Be, L, S)
-        share0 = os.environ.get("CFD_SHARE0", "1") != "0"
-        # distinct (utterance, audio instance) pairs of the 7-chunk pattern of make_inputs: the unconditional tensor + the utterance's own
-        l0_pairs = 2 * B_PER_GPU if (share0 and os.environ.get("CFD_L0_DEDUP", "1") != "0" and os.environ.get("CFD_FUSED_XATTN", "1") != "0") else None
-        ex = executed_gemm_flops(Be, L, S, U, shared_rows=B_PER_GPU if share0 else None, l0_pairs=l0_pairs,
-                                 one_key=os.environ.get("CFD_ONE_KEY", "1") != "0" and os.environ.get("CFD_FUSED_XATTN", "1") != "0")
-        classes = {k: {"ms": round(v[0], 4), "launches": v[1]} for k, v in prof.items()}
-        once_per_run = {k: round(ex[k] / 1e12, 4) for k in ex if prof[k][1] == 0 and ex[k] > 0}
-        for k in once_per_run:      # not launched inside an iteration (memory-side projections: made once at cfd_sample_begin)
-            ex[k] = 0.0
-        # dominant kernel = gemm_sp_kernel (the token-side and memory-side products: the largest share of a step); the fused
-        # attention kernels (self_attn_fused_kernel = class gemm_attn, xattn_fused_kernel = class xattn) are listed per class
-        gk = ("gemm_token", "gemm_mem")
-        dom_ms = sum(prof[k][0] for k in gk)
-        dom_n = sum(prof[k][1] for k in gk)
-        achieved = sum(ex[k] for k in gk) / (dom_ms * 1e-3) / 1e12 if dom_ms > 0 else 0.0
-        traffic = xa_traffic = None
-        tpath = os.path.join(ROOT, "profiles", "hbm_traffic_gemm.json")
-        if os.path.exists(tpath) and args.shape == "C2":
-            tj = json.load(open(tpath))
-            traffic, xa_traffic = tj.get("bytes_per_launch_mean"), tj.get("xattn_bytes_per_launch")
-        for k in ex:
-            classes[k]["algorithmic_tflop"] = round(ex[k] / 1e12, 4)
-            classes[k]["tflops_eager"] = round(ex[k] / (prof[k][0] * 1e-3) / 1e12, 1) if prof[k][0] > 0 else None
-        xa_ms, xa_n = prof["xattn"]
-        xa_ach = ex["xattn"] / (xa_ms * 1e-3) / 1e12 if xa_ms > 0 else 0.0
-        # The fractions are quoted on the REPLAYED graph's clock: a class's share of the eager, event-bracketed forward times
-        # ms_per_step (the timed region).  The brackets and eager launch gaps inflate the class times by a few per cent; the
-        # shares are what the committed rocprofv3 kernel stats of the same command agree with (profiles/rNN_roofline.json,
-        # tools/profile_post.py).  The eager figures stay as achieved_eager / frac_eager.
-        class_sum = sum(v[0] for v in prof.values())
-        ms_step = 1000.0 * dt / args.steps
-        scale = ms_step / class_sum if class_sum > 0 else 1.0
-        achieved_eager, xa_eager = achieved, xa_ach
-        achieved, xa_ach = achieved_eager / scale, xa_eager / scale
-        for k in classes:
-            classes[k]["ms_eager"] = classes[k].pop("ms")
-            classes[k]["ms"] = round(prof[k][0] * scale, 4)          # share of the timed region (replayed graph)
-        for k in ex:
-            classes[k]["tflops"] = round(ex[k] / (prof[k][0] * scale * 1e-3) / 1e12, 1) if prof[k][0] > 0 else None
-            classes[k]["frac_of_peak"] = round(classes[k]["tflops"] / PEAK_BF16_TFLOPS, 4) if classes[k]["tflops"] else None
-        xattn_roofline = {"bound": "mfma", "kernel": "xattn_fused_kernel (the largest single symbol of the trace: LayerNorm2, scores, softmax, "
-                                                     "P.V and residual update of a layer's five cross-attentions in one launch)",
-                          "achieved": xa_ach, "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": xa_ach / PEAK_BF16_TFLOPS,
-                          "frac_issued": xa_issue * xa_ach / PEAK_BF16_TFLOPS, "mfma_per_product": xa_issue,
-                          "frac_of_issued_peak_div3": xa_ach / (PEAK_BF16_TFLOPS / 3.0),
-                          "achieved_eager": xa_eager, "frac_eager": xa_eager / PEAK_BF16_TFLOPS,
-                          "algorithmic_tflop_per_step": ex["xattn"] / 1e12,
-                          "launches_per_step": xa_n, "avg_launch_ms": xa_ms * scale / max(xa_n, 1), "avg_launch_ms_eager": xa_ms / max(xa_n, 1),
-                          "traffic": xa_traffic, "traffic_source": "profiles/hbm_traffic_gemm.json" if xa_traffic else None}
-        mfma_ms = sum(prof[k][0] for k in ex) * scale
-        all_mfma = sum(ex.values()) / (mfma_ms * 1e-3) / 1e12 if mfma_ms > 0 else 0.0
-        executed = sum(ex.values())
-        step_roofline = {"bound": "mfma", "executed_tflop_per_step": executed / 1e12, "executed_tflops": executed / (ms_step * 1e-3) / 1e12,
-                         "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": executed / (ms_step * 1e-3) / 1e12 / PEAK_BF16_TFLOPS,
-                         "frac_issued": (3.0 * (executed - ex["xattn"]) + xa_issue * ex["xattn"]) / (ms_step * 1e-3) / 1e12 / PEAK_BF16_TFLOPS,
-                         "canonical_tflop_per_step": canon / 1e12, "canonical_tflops": canon / (ms_step * 1e-3) / 1e12,
-                         "note": "whole step on the timed region's clock: executed = algorithmic FLOPs of every product launched inside an iteration "
-                                 "(after de-duplication: shared layer-0 head, layer-0 audio attention per distinct pair, no one-key tile step); "
-                                 "canonical = the reference formulation's FLOPs for the same step (SURVEY.md 8d)"}
         out = {
             "metric": ("denoise-steps/sec (B=32 per GPU, 196-token latent, 1500 audio tokens, 1000-step DDPM schedule)" if args.shape == "C2" else
                        f"denoise-steps/sec at the product shape (NOT the BASELINE metric: B=32 per GPU, L={L}, S={S}, 1000-step DDPM schedule)"),
@@ -732,48 +774,25 @@ def main():
                        "shape": args.shape,
                        "parallelism": f"batch-shard x{world}, one all_gather of latents"},
             "utterance_steps_per_s": world * B_PER_GPU * args.steps / dt,
-            "value_without_zero_weight_chunk": (args.steps / dt_skip) if dt_skip else None,
-            "value_split_pairs_everywhere": (args.steps / dt_pairs) if dt_pairs else None,
-            "full_loop_s": full_loop_s,
-            "full_loop_steps_per_s": (n_sched / full_loop_s) if full_loop_s else None,
             "canonical_tflop_per_step": canon / 1e12,
             "canonical_tflops": world * canon * args.steps / dt / 1e12,
-            "roofline": {"bound": "mfma", "kernel": "gemm_sp_kernel (the matrix products launched inside one iteration: token side; the memory-side "
-                                                            "projections run once per run since round 2)", "achieved": achieved,
-                         "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": achieved / PEAK_BF16_TFLOPS,
-                         "frac_issued": 3.0 * achieved / PEAK_BF16_TFLOPS,
-                         "peak_div3": PEAK_BF16_TFLOPS / 3.0, "frac_of_issued_peak_div3": achieved / (PEAK_BF16_TFLOPS / 3.0),
-                         "achieved_eager": achieved_eager, "frac_eager": achieved_eager / PEAK_BF16_TFLOPS,
-                         "eager_to_replay_scale": scale,
-                         "algorithmic_tflop_per_step": sum(ex[k] for k in gk) / 1e12,
-                         "traffic": traffic,
-                         "traffic_source": "profiles/hbm_traffic_gemm.json (a committed rocprofv3 FETCH_SIZE x 2 + WRITE_SIZE profile of this "
-                                           "command, not a quantity of this run)" if traffic else None,
-                         "launches_per_step": dom_n, "avg_launch_ms": dom_ms * scale / max(dom_n, 1), "avg_launch_ms_eager": dom_ms / max(dom_n, 1),
-                         "all_mfma_kernels_achieved": all_mfma, "all_mfma_kernels_frac": all_mfma / PEAK_BF16_TFLOPS,
-                         "note": "achieved / frac = algorithmic (single-product) FLOPs of the launched GEMMs / the class's share of ms_per_step "
-                                 "(the timed region of replayed hipGraph iterations); the shares come from ONE EAGER forward with every launch "
-                                 "bracketed by a HIP-event pair on the launch stream (cfd_profile_forward) -- its class times sum to more than "
-                                 "ms_per_step (the brackets cost that: achieved_eager / frac_eager are the un-scaled figures), the shares are what "
-                                 "the committed rocprofv3 kernel stats of this command give (profiles/rNN_roofline.json); "
-                                 "each product is issued as 3 f16 MFMAs, so the MFMA pipe sees 3x this and the ceiling of the "
-                                 "f16x3 instruction mix is peak / 3 = 833 TFLOP/s (frac_of_issued_peak_div3); traffic = mean HBM bytes "
-                                 "per launch from rocprofv3 FETCH_SIZE (x2, gfx950) + WRITE_SIZE (profiles/)"},
-            "roofline_xattn": xattn_roofline,
-            "roofline_step": step_roofline,
-            "kernel_classes": classes,
-            "tflop_once_per_run_not_per_step": once_per_run,
-            "gpu_state": {"before_timed_region": state0, "after_timed_region": state1,
-                          "note": "amdsmi readings outside the timed region: the boxes of the pool differ by +-3 % on one binary"},
         }
-        if world == 1 and not args.no_secondary and args.shape == "C2":
-            try:                      # (secondary measurements never take the headline line down with them)
-                out["other_configs"] = secondary_configs(model, device)
-                out["c1_single_utterance"] = out["other_configs"].pop("c1_single_utterance")
-            except Exception as e:    # noqa: BLE001
-                out["other_configs"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(model)
+        if args.full:
+            out.update({"value_without_zero_weight_chunk": (args.steps / dt_skip) if dt_skip else None,
+                        "value_split_pairs_everywhere": (args.steps / dt_pairs) if dt_pairs else None,
+                        "full_loop_s": full_loop_s,
+                        "full_loop_steps_per_s": (n_sched / full_loop_s) if full_loop_s else None})
+            out.update(roofline_figures(prof, policy, out["ms_per_step"], canon, args.shape))
+            out["gpu_state"] = {"before_timed_region": state0, "after_timed_region": state1,
+                                "note": "amdsmi readings outside the timed region: two MI355X boards can differ by +-3 % on one binary"}
+            if world == 1 and not args.no_secondary and args.shape == "C2":
+                try:                      # (secondary measurements never take the headline line down with them)
+                    out["other_configs"] = secondary_configs(model, device)
+                    out["c1_single_utterance"] = out["other_configs"].pop("c1_single_utterance")
+                except Exception as e:    # noqa: BLE001
+                    out["other_configs"] = {"error": f"{type(e).__name__}: {e}"}
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(model)
         print(json.dumps(out))
     if world > 1:
         import torch.distributed as dist

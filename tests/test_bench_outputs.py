@@ -1,5 +1,5 @@
-"""bench.py's own arguments: --steps / --warmup are checked before anything starts (CPU), and --dump-outputs writes what the timed
-path computed (-m gpu)."""
+"""bench.py's own arguments: --steps / --warmup are checked before anything starts (CPU), --dump-outputs writes what the timed
+path computed, and a plain run's line holds the headline figure while --full adds the rest (-m gpu)."""
 import json
 import os
 import subprocess
@@ -48,3 +48,25 @@ def test_bench_dumps_the_latents_of_its_last_timed_step(tmp_path):
         run.steps(3)
         want = run.read().cpu().numpy()
     assert np.array_equal(got, want)
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_holds_the_headline_and_full_adds_the_rest():
+    """A plain `bench.py --steps K --warmup W` measures the headline figure and nothing else; the profiled forward behind
+    `kernel_classes` and the rooflines, the GPU state and the other measurements come with --full (--headline-only trims the latter)."""
+    def line(*extra):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", *extra],
+                           capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    profiled = {"roofline", "roofline_xattn", "roofline_step", "kernel_classes", "tflop_once_per_run_not_per_step", "gpu_state"}
+    other = {"value_without_zero_weight_chunk", "value_split_pairs_everywhere", "full_loop_s", "other_configs", "c1_single_utterance", "cpu_baseline"}
+    plain = line()
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= plain.keys()
+    assert plain["higher_is_better"] is True and plain["steps"] == 2 and plain["warmup"] == 1
+    assert abs(plain["value"] * plain["ms_per_step"] - 1000.0) < 1e-6
+    assert not (profiled | other) & plain.keys()
+    full = line("--full", "--headline-only")
+    assert profiled <= full.keys() and full["kernel_classes"]["xattn"]["launches"] > 0
+    assert full["value_without_zero_weight_chunk"] is None and full["full_loop_s"] is None
+    assert not {"other_configs", "c1_single_utterance", "cpu_baseline"} & full.keys()

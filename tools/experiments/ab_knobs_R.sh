@@ -3,7 +3,7 @@
 #   tools/experiments/ab_knobs_R.sh "CFD_QKV_CFG=1" "CFD_QKV_CFG=19" ...
 for r in 1 2; do
 for k in "" "$@"; do
-  env $k python bench.py --steps 40 --warmup 3 --shape R --headline-only 2>/dev/null | python -c "
+  env $k python bench.py --full --steps 40 --warmup 3 --shape R --headline-only 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('[$k] R', round(d['value'],2), 'steps/s', round(d['ms_per_step'],3), 'ms', {k:round(v['ms'],3) for k,v in d['kernel_classes'].items() if v['ms']})"

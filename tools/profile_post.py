@@ -108,7 +108,7 @@ def publish():
         json.dump({"bytes_per_launch_mean": tot / max(n, 1), "launches_in_trace": n,
                    "xattn_bytes_per_launch": xt or None, "xattn_launches_in_trace": xn,
                    "source": f"profiles/{tag}_bench_c2_hbm_traffic.csv (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate passes over "
-                             "`bench.py --steps 3 --warmup 1`; FETCH doubled per MI355X_MICROARCH.md HBM note for gfx950)"},
+                             "`bench.py --full --steps 3 --warmup 1 --headline-only`; FETCH doubled per MI355X_MICROARCH.md HBM note for gfx950)"},
                   open(os.path.join(PROF, "hbm_traffic_gemm.json"), "w"), indent=1)
     print("published:", sorted(os.listdir(PROF)))
 
@@ -183,7 +183,7 @@ def roofline():
                       "tflops": round(fl / (ms * 1e-3), 1) if fl and ms > 0 else None, "frac_of_2500": round(fl / (ms * 1e-3) / 2500.0, 4) if fl and ms > 0 else None}
     tot_ms = sum(r["ms_per_step"] for r in rows)
     ex = (d.get("roofline_step") or {}).get("executed_tflop_per_step")
-    out = {"source": f"rocprofv3 --kernel-trace of `bench.py --steps 20 --warmup 3 --headline-only` ({tag}); {n_iter} loop iterations + 1 eager profiled forward in the trace",
+    out = {"source": f"rocprofv3 --kernel-trace of `bench.py --full --steps 20 --warmup 3 --headline-only` ({tag}); {n_iter} loop iterations + 1 eager profiled forward in the trace",
            "bench_line": {"value": d.get("value"), "ms_per_step": d.get("ms_per_step"), "roofline_frac": (d.get("roofline") or {}).get("frac"),
                           "roofline_xattn_frac": (d.get("roofline_xattn") or {}).get("frac"), "roofline_step_frac": (d.get("roofline_step") or {}).get("frac")},
            "traced_kernel_ms_per_step": round(tot_ms, 4), "classes": classes,

@@ -1,6 +1,7 @@
 // libcfdenoise: float32 building blocks on device tensors -- the conditioning producers (cfd_linear_act) and the pieces of
-// ConvoFusionVae.decode (cfd_layer_norm, cfd_mha, cfd_add, cfd_zero_rows).
+// ConvoFusionVae.decode (cfd_layer_norm, cfd_mha, cfd_add, cfd_zero_rows) -- and ConvoFusionVae.encode in one launch (cfd_vae_encode).
 #include "cfd_internal.hpp"
+#include "vae_enc.hpp"
 
 // ---- conditioning producers ---------------------------------------------------------------------------------
 int enqueue_linear_act(const float* x, long long n_rows, int K, const float* W, const float* b, int N, int act, float* out, hipStream_t st) {
@@ -57,3 +58,72 @@ extern "C" int cfd_zero_rows(cfd_handle c, float* x, const uint8_t* keep, long l
   return CFD_OK;
 }
 
+
+// ---- ConvoFusionVae.encode (vae.py:162-266): csrc/vae_enc.hpp ----------------------------------------------------------------------
+template <int RT>
+static int launch_vae_encode(const VaeEncArgs& a, int groups, int lds, hipStream_t st) {
+  static bool attr_set = false;
+  if (!attr_set) {
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&vae_encode_kernel<RT>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(vae_encode_kernel<RT>, dim3((unsigned)groups, 2), dim3(256), lds, st, a);
+  HIPCHK(hipGetLastError());
+  return CFD_OK;
+}
+
+extern "C" int cfd_vae_encode(cfd_handle c, const float* wpack, int d_model, int num_heads, int ff_size, int num_layers, int latent_size,
+                              const float* features, int bs, int nframes, long long row_stride, const int* lengths, float* mu_logvar,
+                              float* feats_out, int seqs_per_group, void* stream) {
+  if (!c || !wpack || !features || !lengths || !mu_logvar || !feats_out) return fail(CFD_E_ARG, "bad argument (NULL pointer)");
+  if (d_model != VE_D || num_heads != 2 || ff_size != VE_FF || latent_size != 1 || num_layers < 1 || num_layers > VE_MAX_LAYERS || num_layers % 2 == 0)
+    return fail(CFD_E_ARG, "cfd_vae_encode implements d_model 128, 2 heads, ff 1024, latent_size 1 and odd num_layers <= %d only "
+                "(got %d, %d, %d, %d, %d)", VE_MAX_LAYERS, d_model, num_heads, ff_size, latent_size, num_layers);
+  if (seqs_per_group < 0 || seqs_per_group > 3) return fail(CFD_E_ARG, "seqs_per_group must be 0 (automatic) or 1 - 3");
+  if (bs < 1 || nframes < 16 || nframes % 16 || row_stride < VE_NFEATS)
+    return fail(CFD_E_SHAPE, "cfd_vae_encode needs bs >= 1, nframes a positive multiple of 16 and row_stride >= 189 (got %d, %d, %lld)", bs,
+                nframes, row_stride);
+  const long long n_seq = (long long)bs * (nframes / 16);
+  if (n_seq > (1LL << 30)) return fail(CFD_E_SHAPE, "too many sequences (%lld)", n_seq);
+  const int nb = (num_layers - 1) / 2;
+  HIPCHK(hipSetDevice(c->cfg.device));
+  // row tiles per workgroup: G = 16 RT / 18 sequences share one pass over the weights.  Automatic choice: the fewest row-tile passes per
+  // CU, counting padding rows, over the shapes whose LDS fits (smaller tiles give more workgroups at small batches).  Every shape holds
+  // more than 256 registers per lane (VGPRs + AGPRs), so one workgroup runs per CU whatever its LDS.
+  static int n_cu = 0;
+  if (!n_cu) HIPCHK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, c->cfg.device));
+  const int lds_max = 160 * 1024;
+  int rt = 0;
+  if (seqs_per_group) {
+    rt = seqs_per_group + 1;
+    if (ve_lds_bytes(rt, nb) > lds_max) return fail(CFD_E_SHAPE, "%d sequences per workgroup do not fit LDS at %d layers", seqs_per_group, num_layers);
+  } else {
+    long long best = 0;
+    for (int t = 4; t >= 2; --t) {
+      const int lds = ve_lds_bytes(t, nb);
+      if (lds > lds_max) continue;
+      const long long groups = 2 * ((n_seq + (16 * t / VE_T) - 1) / (16 * t / VE_T));
+      const long long cost = (groups + n_cu - 1) / n_cu * t;
+      if (!rt || cost < best) rt = t, best = cost;
+    }
+  }
+  const int G = 16 * rt / VE_T;
+  const long long groups = (n_seq + G - 1) / G;
+  VaeEncArgs a;
+  a.w = wpack;
+  a.stack_floats = ve_stack_floats(num_layers);
+  a.feats = features;
+  a.row_stride = row_stride;
+  a.lengths = lengths;
+  a.mulv = mu_logvar;
+  a.feats_out = feats_out;
+  a.nframes = nframes;
+  a.n_chunks = nframes / 16;
+  a.n_seq = (int)n_seq;
+  a.num_layers = num_layers;
+  const int lds = ve_lds_bytes(rt, nb);
+  hipStream_t st = (hipStream_t)stream;
+  if (rt == 4) return launch_vae_encode<4>(a, (int)groups, lds, st);
+  if (rt == 3) return launch_vae_encode<3>(a, (int)groups, lds, st);
+  return launch_vae_encode<2>(a, (int)groups, lds, st);
+}

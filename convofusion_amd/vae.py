@@ -1,21 +1,28 @@
-"""``ConvoFusionVae`` with the decoder on the HIP path.
+"""``ConvoFusionVae`` with the encoder and the decoder on the HIP path.
 
-Drop-in for ``convofusion.models.architectures.vae.ConvoFusionVae`` (reference vae.py:33-372) as far as the
-generation flow needs it: same constructor, same 337-entry state-dict layout (so ``motion_vae.*`` of a reference
-checkpoint loads strictly), and ``decode(z, lengths)`` -- the step right after the denoising loop
-(test.py / unbounded_synthesis.py: latents -> 189 motion features per frame).  ``encode`` / ``forward`` belong to
-training and evaluation and are not provided: they raise.
+Drop-in for ``convofusion.models.architectures.vae.ConvoFusionVae`` (reference vae.py:33-372) for generation and evaluation: same
+constructor, same 337-entry state-dict layout (so ``motion_vae.*`` of a reference checkpoint loads strictly), ``decode(z, lengths)`` --
+the step right after the denoising loop (test.py / unbounded_synthesis.py: latents -> 189 motion features per frame) -- and
+``encode(features, lengths)`` -- test.py's evaluation path (convofusion.py:1053-1057 encodes the ground truth and the generated motion).
+``forward`` belongs to training and is not provided: it raises (the reference's own forward cannot run either: it unpacks two values
+from the three ``encode`` returns).
 
 ``decode`` restates vae.py:268-372 for arch 'encoder_decoder' / PE_TYPE 'convofusion' with every arithmetic step in
 libcfdenoise float32 kernels (cfd_linear_act, cfd_layer_norm, cfd_mha, cfd_add, cfd_zero_rows); torch only slices,
 concatenates and allocates.  Two SkipTransformerDecoders (cross_attention.py:66-125) of pre-norm
 TransformerDecoderLayers (:361-382): d_model 128, 2 heads, ff 1024, 5 layers -- tiny next to the loop (a few ms per
 batch), so the kernels are plain and exact rather than tuned.
+
+``encode`` restates vae.py:162-266 in ONE launch for both SkipTransformerEncoders (cfd_vae_encode, csrc/vae_enc.hpp): chunking, root
+subtraction, skeleton embedding, global tokens, PE, mask, the encoder stacks and the final norm, exact float32.  torch then forms
+std = exp(logvar) ** 0.5 and draws ``Normal(mu, std).rsample()`` from the default generator exactly as the reference does.  The
+kernel reads a packed copy of the encoder weights that is rebuilt whenever a parameter changes (``load_state_dict``, ``.to``).
 """
 import ctypes as C
 
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from . import _lib
 from .conditioning import ACT_GELU, ACT_NONE, _engine_handle, linear_act
@@ -150,7 +157,8 @@ class ConvoFusionVae(nn.Module):
             raise ValueError("MLP_DIST=True is not supported by the HIP VAE mirror")
         self.latent_size, self.latent_dim = latent_dim[0], latent_dim[-1]
         self.body_nfeats, self.hands_nfeats = 23 * 3, 40 * 3                  # vae.py:53-54
-        self.arch, self.num_heads, self.num_layers = arch, num_heads, num_layers
+        self.arch, self.num_heads, self.num_layers, self.ff_size = arch, num_heads, num_layers, ff_size
+        self._enc_pack, self._enc_key = None, None
         d = self.latent_dim
         self.body_global_motion_token = nn.Parameter(torch.randn(self.latent_size * 2, d))
         self.hands_global_motion_token = nn.Parameter(torch.randn(self.latent_size * 2, d))
@@ -167,11 +175,87 @@ class ConvoFusionVae(nn.Module):
         self.hands_final_layer = nn.Linear(d, self.hands_nfeats)
 
     def forward(self, features, lengths=None):
-        raise NotImplementedError("convofusion_amd.vae.ConvoFusionVae provides decode() only (generation); training and "
-                                  "evaluation use the reference module")
+        raise NotImplementedError("convofusion_amd.vae.ConvoFusionVae provides encode() and decode() only; training uses the "
+                                  "reference module")
 
+    def _encoder_sources(self):
+        """(tensor, pad K to) in the order of the packed layout (csrc/vae_enc.hpp); pad None = a vector, 0 = a matrix as it is."""
+        src = []
+        for enc, emb, tok in ((self.body_encoder, self.body_skel_embedding, self.body_global_motion_token),
+                              (self.hands_encoder, self.hands_skel_embedding, self.hands_global_motion_token)):
+            src += [(emb.weight, ENC_D), (emb.bias, None), (tok, None), (self.query_pos_encoder.pe[:ENC_TOKENS], None)]
+            for blk in list(enc.input_blocks) + [enc.middle_block] + list(enc.output_blocks):
+                a = blk.self_attn
+                src += [(blk.norm1.weight, None), (blk.norm1.bias, None), (a.in_proj_weight, 0), (a.in_proj_bias, None),
+                        (a.out_proj.weight, 0), (a.out_proj.bias, None), (blk.norm2.weight, None), (blk.norm2.bias, None),
+                        (blk.linear1.weight, 0), (blk.linear1.bias, None), (blk.linear2.weight, 0), (blk.linear2.bias, None)]
+            for lin in enc.linear_blocks:
+                src += [(lin.weight, 0), (lin.bias, None)]
+            src += [(enc.norm.weight, None), (enc.norm.bias, None)]
+        return src
+
+    def _encoder_pack(self, dev):
+        """The packed encoder weights of both stacks on ``dev``; rebuilt when any source tensor was replaced or written."""
+        src = self._encoder_sources()
+        key = (str(dev),) + tuple((t.data_ptr(), t._version) for t, _ in src)
+        if self._enc_pack is None or self._enc_key != key:
+            parts = [_pack_w(t.detach().to(dev, torch.float32), k) if k is not None else t.detach().to(dev, torch.float32).reshape(-1)
+                     for t, k in src]
+            pack = torch.cat(parts).contiguous()
+            assert pack.numel() == 2 * encoder_pack_floats(self.num_layers), pack.numel()
+            self._enc_pack, self._enc_key = pack, key
+        return self._enc_pack
+
+    def _encode_spec_error(self):
+        if (self.latent_dim, self.num_heads, self.ff_size, self.latent_size) != (ENC_D, 2, 1024, 1) or self.num_layers > 9:
+            return (f"the HIP VAE encoder is specialised for latent_dim [1, 128], 2 heads, ff_size 1024 and odd num_layers <= 9 "
+                    f"(configs/modules/motion_vae.yaml); this module has latent_dim [{self.latent_size}, {self.latent_dim}], "
+                    f"{self.num_heads} heads, ff_size {self.ff_size}, {self.num_layers} layers")
+        return None
+
+    @torch.no_grad()
     def encode(self, features, lengths=None):
-        raise NotImplementedError("convofusion_amd.vae.ConvoFusionVae provides decode() only (generation)")
+        """features [bs, nframes, 189] (any strides), lengths: frames per sequence (list / tuple / 1-D tensor; None = all nframes)
+        -> (latent [2, bs, nframes / 16, 128], torch.distributions.Normal(mu, std) over [2, bs * nframes / 16, 128],
+        root-subtracted features [bs, nframes, 189])  (vae.py:162-266)."""
+        nf = self.body_nfeats + self.hands_nfeats
+        if features.dim() != 3 or features.shape[-1] != nf:
+            raise ValueError(f"features must be [bs, nframes, {nf}], got {tuple(features.shape)}")
+        bs, nframes, _ = features.shape
+        if lengths is None:
+            lens = [nframes] * bs                                                            # vae.py:168
+        else:
+            lens = [int(v) for v in (lengths.reshape(-1).tolist() if torch.is_tensor(lengths) else lengths)]
+        if bs < 1 or len(lens) != bs:
+            raise ValueError(f"{len(lens)} lengths for a batch of {bs}")
+        if nframes < 16 or nframes % 16:
+            raise ValueError(f"nframes must be a positive multiple of 16 (16-frame chunks, vae.py:178), got {nframes}")
+        if max(lens) != nframes or min(lens) < 0:
+            raise ValueError(f"max(lengths) must equal nframes = {nframes} (the reference's mask reshape, vae.py:189), got {max(lens)}")
+        err = self._encode_spec_error()
+        if err:
+            raise ValueError(err)
+        if features.device.type != "cuda":
+            raise NotImplementedError("the HIP VAE encoder runs on an MI355X only (move the module and the features to 'cuda'); "
+                                      "no CPU path")
+        dev = features.device
+        n_chunks = nframes // 16
+        x = features.detach().to(torch.float32)
+        if x.stride(2) != 1 or x.stride(0) != nframes * x.stride(1) or x.stride(1) < nf:
+            x = x.contiguous()                          # one row stride between all (sequence, frame) rows
+        pack = self._encoder_pack(dev)
+        lens_d = torch.tensor(lens, dtype=torch.int32, device=dev)
+        mulv = torch.empty(2, 2, bs * n_chunks, ENC_D, device=dev)
+        feats = torch.empty(bs, nframes, nf, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().cfd_vae_encode(_engine_handle(dev), _ptr(pack), self.latent_dim, self.num_heads, self.ff_size,
+                                                  self.num_layers, self.latent_size, _ptr(x), bs, nframes, x.stride(1), _ptr(lens_d),
+                                                  _ptr(mulv), _ptr(feats), 0, _stream(x)))
+        mu, logvar = mulv[0], mulv[1]                                                      # vae.py:250-253
+        std = logvar.exp().pow(0.5)                                                        # :256-258
+        dist = torch.distributions.Normal(mu, std)
+        latent = dist.rsample()
+        return latent.reshape(-1, bs, n_chunks, self.latent_dim), dist, feats
 
     @torch.no_grad()
     def decode(self, z, lengths):
@@ -201,20 +285,53 @@ class ConvoFusionVae(nn.Module):
         return out.permute(1, 0, 2)                                                           # :370
 
 
+def _mirror_of(vae, skip):
+    """A mirror built from a reference module's own hyper-parameters (read off its SkipTransformer ``skip``) and weights."""
+    nl = 2 * len(skip.input_blocks) + 1
+    attn = skip.middle_block.self_attn
+    from types import SimpleNamespace
+    m = ConvoFusionVae(ablation=SimpleNamespace(MLP_DIST=getattr(vae, "mlp_dist", False), PE_TYPE=getattr(vae, "pe_type", "convofusion")),
+                       nfeats=vae.body_nfeats + vae.hands_nfeats, latent_dim=[vae.latent_size, vae.latent_dim],
+                       ff_size=skip.middle_block.linear1.out_features, num_layers=nl, num_heads=attn.num_heads,
+                       arch=vae.arch, normalize_before=skip.middle_block.normalize_before, activation="gelu",
+                       position_embedding="sine")
+    m.load_state_dict(vae.state_dict(), strict=True)
+    return m.to(next(vae.parameters()).device).eval()
+
+
 def attach_hip_decode(vae):
     """Route ``vae.decode`` of a REFERENCE ``ConvoFusionVae`` instance (kept for encode / training) to the HIP path:
     builds the mirror from the module's own hyper-parameters and weights and replaces the bound method.  The mirror
     takes a snapshot of the weights: call again after loading a different checkpoint.  Returns the mirror."""
-    dec = vae.body_decoder
-    nl = 2 * len(dec.input_blocks) + 1
-    attn = dec.middle_block.self_attn
-    from types import SimpleNamespace
-    m = ConvoFusionVae(ablation=SimpleNamespace(MLP_DIST=getattr(vae, "mlp_dist", False), PE_TYPE=getattr(vae, "pe_type", "convofusion")),
-                       nfeats=vae.body_nfeats + vae.hands_nfeats, latent_dim=[vae.latent_size, vae.latent_dim],
-                       ff_size=dec.middle_block.linear1.out_features, num_layers=nl, num_heads=attn.num_heads,
-                       arch=vae.arch, normalize_before=dec.middle_block.normalize_before, activation="gelu",
-                       position_embedding="sine")
-    m.load_state_dict(vae.state_dict(), strict=True)
-    m = m.to(next(vae.parameters()).device).eval()
+    m = _mirror_of(vae, vae.body_decoder)
     vae.decode = m.decode
     return m
+
+
+def attach_hip_encode(vae):
+    """Route ``vae.encode`` of a REFERENCE ``ConvoFusionVae`` instance (kept for training) to the HIP path: builds the mirror from
+    the module's own hyper-parameters and weights and replaces the bound method.  The mirror takes a snapshot of the weights: call
+    again after loading a different checkpoint.  Returns the mirror."""
+    m = _mirror_of(vae, vae.body_encoder)
+    vae.encode = m.encode
+    return m
+
+
+ENC_D, ENC_TOKENS = 128, 18      # d_model, 2 global tokens + 16 frames per sequence
+
+
+def encoder_pack_floats(num_layers):
+    """Floats of one stack's block of the packed encoder weights (ve_stack_floats, csrc/vae_enc.hpp)."""
+    d, ff = ENC_D, 1024
+    layer = 4 * d + 3 * d * d + 3 * d + d * d + d + d * ff + ff + ff * d + d
+    return d * d + d + 2 * d + ENC_TOKENS * d + num_layers * layer + (num_layers - 1) // 2 * (2 * d * d + d) + 2 * d
+
+
+def _pack_w(w, k=0):
+    """W [N][K] (nn.Linear) in the kernel's MFMA-B order, K zero-padded to ``k``: float4 ((n/16 * K/16 + k/16) * 64 + lane), lane =
+    16 * ((k % 16) / 4) + n % 16, element k % 4."""
+    n, k0 = w.shape
+    if k and k != k0:
+        w = F.pad(w, (0, k - k0))
+    kk = w.shape[1]
+    return w.reshape(n // 16, 16, kk // 16, 4, 4).permute(0, 2, 3, 1, 4).reshape(-1)

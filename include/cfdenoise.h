@@ -270,6 +270,23 @@ int cfd_mha(cfd_handle h, const float* q, const float* k, const float* v, int Lq
 int cfd_add(cfd_handle h, float* x, const float* y, size_t numel, void* stream);
 int cfd_zero_rows(cfd_handle h, float* x, const uint8_t* keep, long long rows, int D, void* stream);
 
+/* Replaces ConvoFusionVae.encode (convofusion/models/architectures/vae.py:162-266: SkipTransformerEncoder cross_attention.py:18-64 of
+ * pre-norm TransformerEncoderLayers :288-300) up to the distribution's parameters, in ONE launch for both encoder stacks
+ * (csrc/vae_enc.hpp): the chunking into 16-frame sequences with frame 0's root x / z subtracted (:176-187), the skeleton embeddings,
+ * the 2 global motion tokens + query_pos_encoder.pe, the key-padding mask of `lengths`, both SkipTransformerEncoders, the final norm,
+ * and the first 2 tokens of each stack.  Exact float32 throughout.  std / the rsample stay with the caller (vae.py:256-258).
+ *   wpack       dev float32: the packed encoder weights of both stacks, layout in csrc/vae_enc.hpp (built by convofusion_amd/vae.py)
+ *   d_model, num_heads, ff_size, num_layers, latent_size: must be 128, 2, 1024, odd <= 9, 1 (CFD_E_ARG otherwise)
+ *   features    dev float32 rows (b * nframes + f) of >= 189 values, row_stride floats apart (vae.py:164, [bs, nframes, 189])
+ *   nframes     a positive multiple of 16 (CFD_E_SHAPE otherwise); every length must be <= nframes (the caller checks max == nframes)
+ *   lengths     dev int32 [bs]: frame f of chunk c of sequence b is a valid key iff 16 c + f < lengths[b]
+ *   mu_logvar   dev float32 [2 (mu, logvar)][2 (body, hands)][bs * nframes / 16][128]: mu = mu_logvar[0], logvar = mu_logvar[1]
+ *   feats_out   dev float32 [bs * nframes][189]: the root-subtracted features (the third return value), bit-identical to the reference
+ *   seqs_per_group  0 = automatic; 1 - 3 forces that many 18-token sequences per workgroup (measurement only) */
+int cfd_vae_encode(cfd_handle h, const float* wpack, int d_model, int num_heads, int ff_size, int num_layers, int latent_size,
+                   const float* features, int bs, int nframes, long long row_stride, const int* lengths, float* mu_logvar,
+                   float* feats_out, int seqs_per_group, void* stream);
+
 /* float32 pieces of word-excitation guidance (WEG): the attend-and-excite objective on the listener-text attention
  * maps and d(loss)/d(latents) through the denoiser -- what the reference gets from torch autograd over
  * Denoiser.forward (convofusion/models/modeltype/convofusion.py:437-496, iterative_refinement_step :298-388;

@@ -24,7 +24,7 @@ SYMBOLS = [
     "cfd_layer_norm", "cfd_mha", "cfd_add", "cfd_zero_rows", "cfd_gemm_f32", "cfd_softmax", "cfd_softmax_bwd",
     "cfd_layer_norm_bwd", "cfd_ew", "cfd_weg_focus", "cfd_sample_write", "cfd_sample_inpaint", "cfd_weg_eval", "cfd_dyadic_steps",
     "cfd_sample_census", "cfd_dpmsolver_step", "cfd_test_step_coefficients", "cfd_test_gemm_epi",
-    "cfd_vae_encode",
+    "cfd_vae_encode", "cfd_sample_begin_weighted",
 ]
 
 
@@ -156,6 +156,7 @@ def load():
     lib.cfd_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                 C.POINTER(Memory), C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p]
     lib.cfd_sample_begin.argtypes = [C.c_void_p, C.POINTER(SampleArgs), C.c_void_p]
+    lib.cfd_sample_begin_weighted.argtypes = [C.c_void_p, C.POINTER(SampleArgs), C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p]
     lib.cfd_sample_steps.argtypes = [C.c_void_p, C.c_int]
     lib.cfd_sample_position.argtypes = [C.c_void_p]
     lib.cfd_sample_read.argtypes = [C.c_void_p, C.c_void_p, C.c_int]

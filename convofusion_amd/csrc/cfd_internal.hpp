@@ -277,6 +277,11 @@ struct cfd_handle_s {
   // is unchanged (rows are independent); the guidance combine reads chunk k at its position.
   int chunk_pos[8];
   DBuf perm_map[CFD_NMEM];
+  // Weighted run (cfd_sample_begin_weighted): the guidance weights come from wtab [iterations][B][8] (indexed by the caller's chunk
+  // order) and wpos[k] is the row position of chunk k, or chunk 0's for a chunk the run does not evaluate.
+  bool run_weighted = false;
+  int wpos[8];
+  DBuf wtab;
   int run_pos = 0;
 };
 typedef cfd_handle_s Ctx;

@@ -80,6 +80,8 @@ static int step_coefficients(int kind, const float* ac, int T, int n_inf, const 
   return CFD_OK;
 }
 
+static void (*const cfg_step_kernel_weighted)(const CfgStepArgsW) = cfg_step_kernel<0, true>;   // (one macro argument for LAUNCH)
+
 static int enqueue_loop_iteration(Ctx* c, hipStream_t st) {
   const cfd_sample_args& s = c->sargs;
   const long long n8 = (long long)s.B * s.L * (CFD_LAT / 8);
@@ -95,11 +97,77 @@ static int enqueue_loop_iteration(Ctx* c, hipStream_t st) {
   ca.noise = s.step_noise; ca.seed = s.seed; ca.utt0 = s.first_utterance;
   const long long n4 = (long long)s.B * s.L * CFD_LAT / 4;
   ca.advance = c->w->d_step.as<int>();   // the last workgroup of cfg_step_kernel advances the loop index
+  if (c->run_weighted) {   // the caller's 7 chunks, weights from the run's table (those of a chunk it does not evaluate are all 0)
+    CfgStepArgsW cw;
+    static_cast<CfgStepArgs&>(cw) = ca;
+    cw.G = 7;
+    for (int k = 0; k < 8; ++k) cw.pos[k] = c->wpos[k];
+    cw.wtab = c->wtab.as<float>();
+    LAUNCH(CFD_PROF_OTHER, cfg_step_kernel_weighted, dim3((unsigned)std::min<long long>((n4 + 255) / 256, 256)), dim3(256), st, cw);
+    return CFD_OK;
+  }
   LAUNCH(CFD_PROF_OTHER, cfg_step_kernel<>, dim3((unsigned)std::min<long long>((n4 + 255) / 256, 256)), dim3(256), st, ca);
   return CFD_OK;
 }
 
+// Chunks of a weighted run (cfd_sample_begin_weighted): uploads the weight table, decides which chunks are evaluated (prune: every chunk
+// k >= 1 whose column is 0 throughout is not, except the last one when the run keeps its attention maps) and compacts the memories' row
+// maps to the evaluated chunks, in the caller's order (a memory without a map gets the identity map first).  keep_idx[k]: the compacted
+// index of chunk k, or -1.  c->sargs.G becomes the number of evaluated chunks.
+static int weighted_chunks(Ctx* c, const float* wtab, int prune, int N, bool keep_last, cfd_memory mem_in[CFD_NMEM], int keep_idx[8],
+                           hipStream_t st) {
+  const cfd_sample_args& s = c->sargs;
+  const int B = s.B, G = s.G;
+  const size_t n = (size_t)N * B * 8;
+  for (size_t e = 0; e < n; ++e)
+    if (e % 8 != 0 && !std::isfinite(wtab[e]))
+      return fail(CFD_E_ARG, "weights[%zu][%zu][%zu] is not finite", e / 8 / B, e / 8 % B, e % 8);
+  bool keep[8] = {true, false, false, false, false, false, false, false};
+  for (int k = 1; k < G; ++k) {
+    keep[k] = !prune || (keep_last && k == G - 1);
+    for (size_t r = 0; r < (size_t)N * B && !keep[k]; ++r) keep[k] = wtab[r * 8 + k] != 0.0f;
+  }
+  int ge = 0;
+  for (int k = 0; k < 8; ++k) keep_idx[k] = (k < G && keep[k]) ? ge++ : -1;
+  CHK(c->wtab.ensure(n * sizeof(float)));
+  HIPCHK(hipMemcpyAsync(c->wtab.p, wtab, n * sizeof(float), hipMemcpyHostToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));   // (the caller's host table is not kept beyond the call)
+  c->sargs.G = ge;
+  if (ge == G) return CFD_OK;
+  const int Be = G * B, Bc = ge * B;
+  std::vector<int> hm(Be), cm(Bc);
+  for (int j = 0; j < CFD_NMEM; ++j) {
+    if (mem_in[j].row_map) {
+      HIPCHK(hipMemcpy(hm.data(), mem_in[j].row_map, (size_t)Be * 4, hipMemcpyDeviceToHost));
+    } else {
+      if (mem_in[j].U != Be) return fail(CFD_E_ARG, "memory %s: U = %d != G * B = %d without a row_map", MEM_NAMES[j], mem_in[j].U, Be);
+      for (int r = 0; r < Be; ++r) hm[r] = r;
+    }
+    for (int k = 0; k < G; ++k)
+      if (keep_idx[k] >= 0)
+        for (int u = 0; u < B; ++u) cm[(size_t)keep_idx[k] * B + u] = hm[(size_t)k * B + u];
+    CHK(c->perm_map[j].ensure((size_t)Be * 4));
+    HIPCHK(hipMemcpy(c->perm_map[j].p, cm.data(), (size_t)Bc * 4, hipMemcpyHostToDevice));
+    mem_in[j].row_map = c->perm_map[j].as<int32_t>();
+  }
+  return CFD_OK;
+}
+
+static int sample_begin(Ctx* c, const cfd_sample_args* args, void* stream, const float* wtab, int prune, int* chunks_evaluated);
+
 extern "C" int cfd_sample_begin(cfd_handle c, const cfd_sample_args* args, void* stream) {
+  return sample_begin(c, args, stream, nullptr, 0, nullptr);
+}
+
+extern "C" int cfd_sample_begin_weighted(cfd_handle c, const cfd_sample_args* args, const float* weights, int prune, int* chunks_evaluated,
+                                         void* stream) {
+  if (!c || !args) return fail(CFD_E_ARG, "null argument");
+  if (!weights) return fail(CFD_E_ARG, "cfd_sample_begin_weighted: the weight table is NULL");
+  if (args->G != 7) return fail(CFD_E_ARG, "cfd_sample_begin_weighted needs the 7-chunk guidance batch (G = %d)", args->G);
+  return sample_begin(c, args, stream, weights, prune, chunks_evaluated);
+}
+
+static int sample_begin(Ctx* c, const cfd_sample_args* args, void* stream, const float* wtab, int prune, int* chunks_evaluated) {
   if (!c || !args) return fail(CFD_E_ARG, "null argument");
   if (c->run_open) return fail(CFD_E_STATE, "a sampling run is already open");
   HIPCHK(hipSetDevice(c->cfg.device));
@@ -108,6 +176,13 @@ extern "C" int cfd_sample_begin(cfd_handle c, const cfd_sample_args* args, void*
   struct AcenOff { Ctx* c; ~AcenOff() { c->acen_on = false; } } acen_off{c};   // (the census slots go only into THIS run's launches)
   c->acen_valid = c->acen_measured = false;
   c->acen_hits = 0;
+  cfd_sample_args s_w;
+  if (wtab) {   // a weighted run ignores guidance_weight and skip_zero_weight_chunks (its table says which chunks count)
+    s_w = *args;
+    s_w.skip_zero_weight_chunks = 0;
+    args = &s_w;
+  }
+  c->run_weighted = false;
   const cfd_sample_args& s = *args;
   if (s.B < 1 || (s.G != 1 && s.G != 7 && (s.G < 1 || s.G > 8))) return fail(CFD_E_ARG, "bad B / G");
   if (s.scheduler < 0 || s.scheduler > 2) return fail(CFD_E_ARG, "scheduler must be 0 (DDPM), 1 (DDIM) or 2 (DPM-Solver++ (2M))");
@@ -135,24 +210,27 @@ extern "C" int cfd_sample_begin(cfd_handle c, const cfd_sample_args* args, void*
     while (c->sargs.G > 1 && s.guidance_weight[c->sargs.G - 1] == 0.0f) c->sargs.G -= 1;
   // N = loop iterations (the length of scheduler.timesteps); n_inf = the count given to set_timesteps, which fixes the
   // stride `prev_t = t - T // n_inf` of the step formulas.  They differ only for a caller-supplied table.
-  const int Be = c->sargs.G * s.B, n_inf = s.num_inference_steps, N = s.timesteps ? s.num_timesteps : n_inf, T = s.num_train_timesteps;
+  const int n_inf = s.num_inference_steps, N = s.timesteps ? s.num_timesteps : n_inf, T = s.num_train_timesteps;
   c->sargs.timesteps = nullptr;   // (host pointer: not kept beyond this call)
   c->run_iters = N;
   for (int k = 0; k < 8; ++k) c->chunk_pos[k] = k;
   cfd_memory mem_in[CFD_NMEM];
   for (int j = 0; j < CFD_NMEM; ++j) mem_in[j] = s.mem[j];
+  int keep_idx[8];
+  if (wtab) CHK(weighted_chunks(c, wtab, prune, N, n_ring != 0, mem_in, keep_idx, st));
+  const int Be = c->sargs.G * s.B;
   {
     // chunk permutation (see chunk_pos): group the chunks that use one shared copy of the largest memory
     const int G = c->sargs.G, B = s.B;
     bool all_maps = c->permute && G > 2;
     int jb = 0;
     for (int j = 0; j < CFD_NMEM; ++j) {
-      if (!s.mem[j].row_map) all_maps = false;
+      if (!mem_in[j].row_map) all_maps = false;
       if (s.mem[j].S > s.mem[jb].S) jb = j;
     }
     if (all_maps) {
       std::vector<int> hm(Be);
-      HIPCHK(hipMemcpy(hm.data(), s.mem[jb].row_map, (size_t)Be * 4, hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(hm.data(), mem_in[jb].row_map, (size_t)Be * 4, hipMemcpyDeviceToHost));
       std::vector<int> key(G);   // the shared memory index of a uniform chunk, or -1
       for (int g = 0; g < G; ++g) {
         key[g] = hm[(size_t)g * B];
@@ -174,7 +252,7 @@ extern "C" int cfd_sample_begin(cfd_handle c, const cfd_sample_args* args, void*
         for (int pnum = 0; pnum < G; ++pnum) c->chunk_pos[order[pnum]] = pnum;
         std::vector<int> pm(Be);
         for (int j = 0; j < CFD_NMEM; ++j) {
-          HIPCHK(hipMemcpy(hm.data(), s.mem[j].row_map, (size_t)Be * 4, hipMemcpyDeviceToHost));
+          HIPCHK(hipMemcpy(hm.data(), mem_in[j].row_map, (size_t)Be * 4, hipMemcpyDeviceToHost));
           for (int pnum = 0; pnum < G; ++pnum)
             for (int u = 0; u < B; ++u) pm[(size_t)pnum * B + u] = hm[(size_t)order[pnum] * B + u];
           CHK(c->perm_map[j].ensure((size_t)Be * 4));
@@ -183,6 +261,11 @@ extern "C" int cfd_sample_begin(cfd_handle c, const cfd_sample_args* args, void*
         }
       }
     }
+  }
+  if (wtab) {
+    for (int k = 0; k < 8; ++k) c->wpos[k] = c->chunk_pos[keep_idx[k] >= 0 ? keep_idx[k] : 0];
+    c->run_weighted = true;
+    if (chunks_evaluated) *chunks_evaluated = c->sargs.G;
   }
   // operand policy of the run (cfd_sample_args::operand_policy): single-fp16 key / value tiles of the long memories for the fused
   // cross-attention kernel -- only where that kernel runs on projections made once per run and keeps no maps

@@ -634,9 +634,18 @@ struct CfgStepArgs {
   unsigned long long seed;
   unsigned int utt0;
 };
+// The weighted instance's arguments (cfd_sample_begin_weighted): the weight of chunk k for utterance b in iteration *d_step is
+// wtab[(*d_step * B + b) * 8 + k] instead of w[k].  G is 7, and pos[k] of a chunk the run does not evaluate is pos[0]: its weight is 0
+// everywhere, so its term is 0 * (e_0 - e_0), a zero that leaves the sum as it is.  Same terms, same order as the default instance, whose
+// arguments (and code) stay those of CfgStepArgs.
+struct CfgStepArgsW : CfgStepArgs {
+  const float* wtab;     // [iterations][B][8]
+};
+template <bool WTAB>
+using CfgStepArgsOf = typename std::conditional<WTAB, CfgStepArgsW, CfgStepArgs>::type;
 
-template <int CFD_KI = 0>
-__global__ void cfg_step_kernel(const CfgStepArgs a) {
+template <int CFD_KI = 0, bool WTAB = false>
+__global__ void cfg_step_kernel(const CfgStepArgsOf<WTAB> a) {
   const int per_utt = a.L * CFD_LAT;
   const long long n4 = (long long)a.B * per_utt / 4;
   const int i = *a.d_step;
@@ -656,13 +665,16 @@ __global__ void cfg_step_kernel(const CfgStepArgs a) {
   if (a.kind == 2 && c.order == 2.0f) m4 = *reinterpret_cast<const float4*>(a.hist + e0);
   const float u[4] = {e4[0].x, e4[0].y, e4[0].z, e4[0].w};
   float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  const float* wrow = nullptr;
+  if constexpr (WTAB) wrow = a.wtab + ((long long)i * a.B + e0 / per_utt) * 8;   // (a group of 4 never straddles two utterances)
   // reference association: ((((text + audio) + spk) + apb) + lsnid) + all, each = (g*w)*(e_k - e_0)
 #pragma unroll
   for (int k = 1; k < 8; ++k) {
     const float e[4] = {e4[k].x, e4[k].y, e4[k].z, e4[k].w};
+    const float wk = WTAB ? (k < 7 ? wrow[k] : 0.f) : a.w[k];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      const float term = a.w[k] * (e[q] - u[q]);
+      const float term = wk * (e[q] - u[q]);
       acc[q] = (k == 1) ? (a.G > 1 ? term : 0.f) : (k < a.G ? acc[q] + term : acc[q]);
     }
   }

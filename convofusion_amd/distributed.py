@@ -40,15 +40,37 @@ def gather_latents(local, total, group=None):
     return torch.cat([o[: b - a] for o, (a, b) in zip(out, sizes)], dim=0)
 
 
-def sample_sharded(sample_fn, encoder_hidden_states, cond_masks, total_utterances, chunks=7, group=None):
+def shard_modality_weights(modality_weights, start, stop, total):
+    """The utterances [start, stop) of per-modality guidance weights (``sampler.check_modality_weights``): a dict, a [6] row and an
+    [N, 1, 6] table apply to every utterance and are returned as they are; [total, 6] and [N, total, 6] are sliced on the utterance axis."""
+    if modality_weights is None or isinstance(modality_weights, dict):
+        return modality_weights
+    shape = tuple(modality_weights.shape)
+    if len(shape) == 2:
+        if shape[0] != total:
+            raise ValueError(f"modality_weights [B, 6] has {shape[0]} rows for {total} utterances")
+        return modality_weights[start:stop]
+    if len(shape) == 3 and shape[1] != 1:
+        if shape[1] != total:
+            raise ValueError(f"modality_weights [N, B, 6] has {shape[1]} utterances, the batch {total}")
+        return modality_weights[:, start:stop]
+    return modality_weights
+
+
+def sample_sharded(sample_fn, encoder_hidden_states, cond_masks, total_utterances, chunks=7, group=None, modality_weights=None):
     """Run ``sample_fn(enc_shard, masks_shard, B=<local>, first_utterance=<global id>)`` on this rank's
     utterances and return the gathered latents [total, L, 128] on every rank.  A ``sample_fn`` with ``operands="auto"`` decides PER RANK:
     each rank's census sees its own utterances only, so one rank may fall back to ``operands=0`` while another keeps the default policy
-    (each shard's result is still bit for bit one of the two policies' for its utterances); no decision is all-reduced."""
+    (each shard's result is still bit for bit one of the two policies' for its utterances); no decision is all-reduced.
+    ``modality_weights`` (optional): per-modality guidance weights of the whole batch; ``sample_fn`` then also gets
+    ``modality_weights=`` with this rank's utterances (``shard_modality_weights``)."""
     ws = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     a, b = shard_range(total_utterances, rank, ws)
     enc = [shard_cfg_batch(m, a, b, total_utterances, chunks) for m in encoder_hidden_states]
     masks = {k: shard_cfg_batch(v, a, b, total_utterances, chunks) for k, v in (cond_masks or {}).items()}
-    local = sample_fn(enc, masks, B=b - a, first_utterance=a)
+    extra = {}
+    if modality_weights is not None:
+        extra["modality_weights"] = shard_modality_weights(modality_weights, a, b, total_utterances)
+    local = sample_fn(enc, masks, B=b - a, first_utterance=a, **extra)
     return gather_latents(local, total_utterances, group)

@@ -47,7 +47,7 @@ def diffusion_reverse_forecast(model, encoder_hidden_states, lengths=None, prese
     return impl(model, encoder_hidden_states, lengths, preseq, cond_masks, focus_indices)
 
 
-def install(model, attention_steps="auto", operands=None):
+def install(model, attention_steps="auto", operands=None, modality_weights=None):
     """Bind the fused loop as ``model._diffusion_reverse``.  Returns the model.  ``uninstall`` removes the binding.
 
     ``attention_steps``: which entries the returned attention-matrix dict holds.  The reference keeps the full-conditioning
@@ -63,14 +63,20 @@ def install(model, attention_steps="auto", operands=None):
     ``convofusion_amd.sampler.OPERAND_POLICY`` for the model's scheduler: DDPM runs carry the long memories' folded keys / values as single
     fp16).  ``operands=0`` keeps fp16 split pairs everywhere -- the precision escape, at ~8 % of the loop's throughput at the headline shape.
     ``operands="auto"`` (opt-in): the default policy while the run's attention-concentration census stays below
-    ``convofusion_amd.sampler.CENSUS_TAU``, a warning and a repeat of the loop with ``operands=0`` when it trips (``sampler.sample``)."""
-    from .sampler import check_operands
+    ``convofusion_amd.sampler.CENSUS_TAU``, a warning and a repeat of the loop with ``operands=0`` when it trips (``sampler.sample``).
+
+    ``modality_weights``: per-modality guidance weights w_c in place of the reference's 1, 1, 1, 1, 1, 0 (convofusion.py:527-541) -- a dict
+    over text / audio / spk / apb / lsnid / all (missing keys keep the reference's value) or a tensor [6], [B, 6] or [N, B, 6]
+    (``convofusion_amd.sampler.check_modality_weights``); a chunk whose weight is 0 throughout is not evaluated.  None: the reference's."""
+    from .sampler import check_modality_weights, check_operands
     operands = check_operands(operands)
+    modality_weights = check_modality_weights(modality_weights)
     _check_model(model)
     if attention_steps not in ("auto", "last", "all"):
         raise ValueError("attention_steps must be 'auto', 'last' or 'all'")
     model._cfd_attention_steps = attention_steps
     model._cfd_operands = operands
+    model._cfd_modality_weights = modality_weights
     model._diffusion_reverse = types.MethodType(_diffusion_reverse, model)
     return model
 
@@ -81,6 +87,7 @@ def uninstall(model):
         del model._diffusion_reverse
     vars(model).pop("_cfd_attention_steps", None)
     vars(model).pop("_cfd_operands", None)
+    vars(model).pop("_cfd_modality_weights", None)
     return model
 
 

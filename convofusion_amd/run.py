@@ -21,6 +21,8 @@ What it binds, in this process, before the script's first line runs (nothing has
    A script without ``main()`` is run with ``runpy`` as ``__main__`` with bindings 1 and 2 only.
 
 ``CFD_RUN_ATTENTION_STEPS`` = auto | last | all selects ``install``'s attention dict (default auto).
+``CFD_RUN_MODALITY_WEIGHTS`` = e.g. ``text=2,audio=0.5`` sets ``install``'s per-modality guidance weights (keys: text, audio, spk, apb,
+lsnid, all; the others keep the reference's 1, 1, 1, 1, 1, 0).  Unset or empty: the reference's weights.
 """
 import importlib
 import importlib.util
@@ -56,7 +58,31 @@ def redirect_targets():
     return bound
 
 
-def wrap_get_model(attention_steps="auto"):
+def parse_modality_weights(text):
+    """``CFD_RUN_MODALITY_WEIGHTS``: "text=2,audio=0.5" -> {"text": 2.0, "audio": 0.5}; None or blank -> None.  Raises ValueError on a
+    malformed entry, an unknown key, a repeated key or a non-finite value."""
+    if text is None or not text.strip():
+        return None
+    from .sampler import check_modality_weights
+    out = {}
+    for item in text.split(","):
+        if not item.strip():
+            continue
+        key, sep, val = item.partition("=")
+        key = key.strip()
+        if not sep or not key:
+            raise ValueError(f"CFD_RUN_MODALITY_WEIGHTS: {item.strip()!r} is not key=value")
+        if key in out:
+            raise ValueError(f"CFD_RUN_MODALITY_WEIGHTS: {key!r} given twice")
+        try:
+            out[key] = float(val)
+        except ValueError:
+            raise ValueError(f"CFD_RUN_MODALITY_WEIGHTS: {item.strip()!r}: {val.strip()!r} is not a number") from None
+    check_modality_weights(out)
+    return out
+
+
+def wrap_get_model(attention_steps="auto", modality_weights=None):
     """Binding 2: ``get_model`` returns a model with the fused loop installed.  Returns True if the reference module was found."""
     try:
         mod = importlib.import_module(REF_GET_MODEL_MODULE)
@@ -68,7 +94,7 @@ def wrap_get_model(attention_steps="auto"):
 
     def get_model(*args, **kwargs):
         from .installer import install
-        return install(original(*args, **kwargs), attention_steps=attention_steps)
+        return install(original(*args, **kwargs), attention_steps=attention_steps, modality_weights=modality_weights)
 
     get_model.__cfd_wrapped__ = True
     get_model.__wrapped__ = original
@@ -86,8 +112,9 @@ def run_script(path, argv):
     script_dir = os.path.dirname(path)
     if script_dir not in sys.path:
         sys.path.insert(0, script_dir)           # what `python script.py` does: the script's directory first
+    modality_weights = parse_modality_weights(os.environ.get("CFD_RUN_MODALITY_WEIGHTS"))
     redirect_targets()
-    found = wrap_get_model(os.environ.get("CFD_RUN_ATTENTION_STEPS", "auto"))
+    found = wrap_get_model(os.environ.get("CFD_RUN_ATTENTION_STEPS", "auto"), modality_weights)
     if not found:
         print("convofusion_amd.run: convofusion.models.get_model is not importable from here (run from the reference checkout); "
               "the denoiser / scheduler targets are redirected, the fused loop is not installed", file=sys.stderr)

@@ -42,6 +42,73 @@ OPERAND_POLICY = {0: 15, 1: 0, 2: 0}
 CENSUS_TAU = 0.05
 CENSUS_CHUNK = 100
 
+# Modality guidance weights w_c of the guidance chunks 1 - 6, by the reference's variable names (convofusion.py:527-541: "w_c for each
+# modality is kept 1 as a standard"), and the reference's values.  Chunk 0 is the unconditional prediction.
+MODALITY_NAMES = ("text", "audio", "spk", "apb", "lsnid", "all")
+REFERENCE_MODALITY_WEIGHTS = dict(text=1.0, audio=1.0, spk=1.0, apb=1.0, lsnid=1.0, all=0.0)
+
+
+def check_modality_weights(modality_weights):
+    """The form of ``modality_weights`` without the run's sizes: None, a dict over MODALITY_NAMES (missing keys: the reference's values), or
+    a tensor / array of shape [6], [B, 6] or [N, B, 6] (N = len(scheduler.timesteps); [N, 1, 6] broadcasts over utterances), all finite.
+    Returns None, the completed dict, or a float64 numpy array.  Anything else raises ValueError."""
+    import numpy as np
+    if modality_weights is None:
+        return None
+    if isinstance(modality_weights, dict):
+        unknown = set(modality_weights) - set(MODALITY_NAMES)
+        if unknown:
+            raise ValueError(f"modality_weights: unknown keys {sorted(map(str, unknown))} (known: {', '.join(MODALITY_NAMES)})")
+        w = dict(REFERENCE_MODALITY_WEIGHTS)
+        for k, v in modality_weights.items():
+            try:
+                w[k] = float(v)
+            except (TypeError, ValueError):
+                raise ValueError(f"modality_weights[{k!r}] = {v!r} is not a number") from None
+        if not all(np.isfinite(v) for v in w.values()):
+            raise ValueError(f"modality_weights: non-finite weight in {w}")
+        return w
+    if isinstance(modality_weights, torch.Tensor):
+        arr = modality_weights.detach().to("cpu", torch.float64).numpy()
+    elif isinstance(modality_weights, (str, bytes)):
+        raise ValueError(f"modality_weights must be a dict or a tensor / array, not {modality_weights!r}")
+    else:
+        try:
+            arr = np.asarray(modality_weights, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"modality_weights must be a dict or a tensor / array, not {type(modality_weights).__name__}") from None
+    if arr.ndim not in (1, 2, 3) or arr.shape[-1] != len(MODALITY_NAMES):
+        raise ValueError(f"modality_weights must have shape [6], [B, 6] or [N, B, 6], not {list(arr.shape)}")
+    if not np.isfinite(arr).all():
+        raise ValueError("modality_weights: non-finite weight")
+    return arr
+
+
+def modality_weight_table(modality_weights, guidance_scale, N, B, guidance_chunks=CFG_CHUNKS):
+    """The weight table of cfd_sample_begin_weighted: float32 [N, B, 8], entry [i, b, c] = float32(guidance_scale * w_c) with the product
+    taken in double -- what the reference computes with w_c edited (``self.guidance_scale * w_c * (e_c - e_0)``, convofusion.py:533-538)
+    -- for the guidance chunks c = 1 - 6; column 0 is 0.  ``modality_weights``: see ``check_modality_weights``."""
+    import numpy as np
+    if int(guidance_chunks) != CFG_CHUNKS:
+        raise ValueError(f"modality_weights need the {CFG_CHUNKS}-chunk guidance batch (guidance_chunks = {guidance_chunks})")
+    w = check_modality_weights(modality_weights)
+    if w is None:
+        raise ValueError("modality_weights is None: the run takes the default path")
+    if isinstance(w, dict):
+        w = np.array([w[k] for k in MODALITY_NAMES], dtype=np.float64)
+    if w.ndim == 2 and w.shape[0] != B:
+        raise ValueError(f"modality_weights [B, 6] has {w.shape[0]} rows for B = {B} utterances")
+    if w.ndim == 3 and (w.shape[0] != N or w.shape[1] not in (1, B)):
+        raise ValueError(f"modality_weights [N, B, 6] has shape {list(w.shape)}; the run has N = {N} iterations (len(scheduler.timesteps)) "
+                         f"and B = {B} utterances ([N, 1, 6] broadcasts over them)")
+    full = np.broadcast_to(w, (N, B, len(MODALITY_NAMES)))
+    table = np.zeros((N, B, 8), dtype=np.float32)
+    with np.errstate(over="ignore"):
+        table[:, :, 1:1 + len(MODALITY_NAMES)] = (float(guidance_scale) * full).astype(np.float32)
+    if not np.isfinite(table).all():
+        raise ValueError(f"modality_weights: guidance_scale * w overflows float32 (guidance_scale = {guidance_scale})")
+    return table
+
 
 class CensusTripped(Exception):
     """Raised inside an ``operands="auto"`` run when its census counts a row above the threshold (caught by the loop entry points)."""
@@ -176,7 +243,8 @@ class SamplingRun:
     def __init__(self, denoiser, scheduler, encoder_hidden_states, cond_masks, B, L, num_inference_steps,
                  guidance_scale=7.5, guidance_chunks=CFG_CHUNKS, eta=0.0, init_latents=None, step_noise=None,
                  seed=0, first_utterance=0, preseq=None, dedup=True, skip_zero_weight_chunks=False, row_maps=None,
-                 dynamic_memories=(), side_engine=False, attention_ring=False, operands=None, census_tau=None):
+                 dynamic_memories=(), side_engine=False, attention_ring=False, operands=None, census_tau=None, modality_weights=None,
+                 prune_zero_weight_chunks=True):
         """attention_ring: keep the attention maps of the full-conditioning chunk of EVERY iteration (the reference's per-iteration dict,
         convofusion.py:517-523): the captured iteration stores them into ``self.att_ring`` -- five tensors [iterations, B, layers, L, S_j]
         -- with no extra forward and no host round trip (cfd_sample_args.att_ring: the row-tile kernels store them from their second
@@ -188,6 +256,11 @@ class SamplingRun:
         census on at CENSUS_TAU, and ``steps`` raises CensusTripped (checked every CENSUS_CHUNK iterations and at the last one) when it trips
         -- the loop entry points (``sample``, ``sample_with_weg``) then repeat the run with ``operands=0``.
         census_tau: cfd_sample_args.census_tau (None / 0: off unless operands="auto"); ``census()`` reads it.
+        modality_weights: per-modality guidance weights w_c (``check_modality_weights``: a dict over MODALITY_NAMES, or [6] / [B, 6] /
+        [N, B, 6]); the combine is then e_0 + sum_c float32(guidance_scale * w_c) (e_c - e_0) with that table (cfd_sample_begin_weighted),
+        and skip_zero_weight_chunks is ignored.  None: the default path (the reference's w_c).  prune_zero_weight_chunks (weighted runs): a
+        chunk whose weight is 0 in every iteration for every utterance is not evaluated -- same latents, fewer denoiser rows.
+        ``chunks_evaluated``: guidance chunks the run's denoiser evaluates per iteration.
         side_engine: open the run on the denoiser's second library handle (its own weights copy, workspace and stream), so that
         two runs on one module can be open at once (the attention forward of ``last_step_attention`` uses it for a plain forward).
         dynamic_memories: indices j of memories whose CONTENTS the caller rewrites between iterations (DyadicRun's partner
@@ -208,6 +281,8 @@ class SamplingRun:
         self.timesteps = [int(t) for t in table]
         self.B, self.L, self.N = B, L, len(self.timesteps)     # N = loop iterations
         G = guidance_chunks
+        # the weighted run's table [N, B, 8] (cfd_sample_begin_weighted), or None: the default path
+        self.modality_weights = None if modality_weights is None else modality_weight_table(modality_weights, guidance_scale, self.N, B, G)
         if row_maps is not None:       # already-distinct memories + maps (build_guidance_batch)
             if any(int(m.numel()) != G * B for m in row_maps):
                 raise ValueError(f"row_maps must have G*B = {G * B} entries")
@@ -286,7 +361,16 @@ class SamplingRun:
         stream = torch.cuda.current_stream(dev).cuda_stream
         with torch.cuda.device(dev):
             torch.cuda.current_stream(dev).synchronize()
-            _lib.check(self.lib.cfd_sample_begin(self.handle, C.byref(a), C.c_void_p(stream)))
+            if self.modality_weights is None:
+                _lib.check(self.lib.cfd_sample_begin(self.handle, C.byref(a), C.c_void_p(stream)))
+                self.chunks_evaluated = G
+                while skip_zero_weight_chunks and self.chunks_evaluated > 1 and w[self.chunks_evaluated - 1] == 0.0:
+                    self.chunks_evaluated -= 1       # (the library's rule: trailing zero-weight chunks)
+            else:
+                g_eval = C.c_int(0)
+                _lib.check(self.lib.cfd_sample_begin_weighted(self.handle, C.byref(a), self.modality_weights.ctypes.data_as(C.c_void_p),
+                                                              1 if prune_zero_weight_chunks else 0, C.byref(g_eval), C.c_void_p(stream)))
+                self.chunks_evaluated = int(g_eval.value)
         self.open = True
 
     def steps(self, n):
@@ -448,7 +532,8 @@ def _open_run(denoiser, scheduler, encoder_hidden_states, cond_masks, B, L, num_
 
 def sample(denoiser, scheduler, encoder_hidden_states, cond_masks=None, *, B, L=16, num_inference_steps=1000,
            guidance_scale=7.5, guidance_chunks=CFG_CHUNKS, eta=0.0, init_latents=None, step_noise=None, seed=0,
-           first_utterance=0, preseq=None, dedup=True, skip_zero_weight_chunks=False, row_maps=None, return_attention=False, operands=None):
+           first_utterance=0, preseq=None, dedup=True, skip_zero_weight_chunks=False, row_maps=None, return_attention=False, operands=None,
+           modality_weights=None, prune_zero_weight_chunks=True):
     """Run the whole loop; returns latents [B, L, 128] (batch-first); with ``return_attention=True`` also the last
     iteration's attention maps (``last_step_attention``), with ``return_attention="all"`` a dict {timestep: maps} over every
     iteration like the reference's: kept by the captured iteration itself (``SamplingRun(attention_ring=True)``) while the ring fits
@@ -457,14 +542,15 @@ def sample(denoiser, scheduler, encoder_hidden_states, cond_masks=None, *, B, L=
     ``operands``: None (OPERAND_POLICY of the scheduler kind), an operand policy, or "auto": the default policy while the census
     (CENSUS_TAU) finds no concentrated attention against a long memory; when it trips -- read every CENSUS_CHUNK iterations -- a
     UserWarning, and the loop runs again from iteration 0 with ``operands=0``.  The result is then bit for bit the policy-0 run's (same
-    seed, initial latents and step noise), otherwise the default policy's; the worst case costs up to one extra partial run."""
+    seed, initial latents and step noise), otherwise the default policy's; the worst case costs up to one extra partial run.
+    ``modality_weights`` / ``prune_zero_weight_chunks``: per-modality guidance weights, as in ``SamplingRun``."""
     if check_operands(operands) == "auto":
         args = dict(locals())
         return _with_auto_operands(lambda ops: sample(**dict(args, operands=ops)), "auto")
     run = _open_run(denoiser, scheduler, encoder_hidden_states, cond_masks, B, L, num_inference_steps, return_attention in ("all", "auto"),
                     guidance_scale=guidance_scale, guidance_chunks=guidance_chunks, eta=eta, init_latents=init_latents, step_noise=step_noise,
                     seed=seed, first_utterance=first_utterance, preseq=preseq, dedup=dedup, skip_zero_weight_chunks=skip_zero_weight_chunks,
-                    row_maps=row_maps, operands=operands)
+                    row_maps=row_maps, operands=operands, modality_weights=modality_weights, prune_zero_weight_chunks=prune_zero_weight_chunks)
     try:
         if not return_attention:
             run.steps(run.N)
@@ -522,6 +608,9 @@ def _loop_from_model(model, encoder_hidden_states, cond_masks, preseq, focus_ind
               skip_zero_weight_chunks=True)
     kw["return_attention"] = attention
     kw["operands"] = check_operands(getattr(model, "_cfd_operands", None) if operands is None else operands)
+    mw = getattr(model, "_cfd_modality_weights", None)
+    if mw is not None:     # install(model, modality_weights=...)
+        kw["modality_weights"] = mw
     if len(focus_indices) == 0:
         return sample(model.denoiser, model.scheduler, encoder_hidden_states, cond_masks, **kw)
     # ``weg_parameters`` given = the rollout (its constants are hard-coded and its scale table is fresh every iteration);
@@ -539,7 +628,8 @@ def sample_with_weg(denoiser, scheduler, encoder_hidden_states, cond_masks, focu
     max_refinement_steps (configs/assets.yaml:18-23).  ``carry_scale_range``: True reproduces ``_diffusion_reverse``, which
     re-assigns its ``scale_range`` table from the previous iteration's first two entries (convofusion.py:442-444: the step
     size stays ~scale_factor after iteration 0); False is the rollout, which takes a fresh 1.0 -> 0.5 table every
-    iteration (unbounded_synthesis.py:82-89).  See ``weg.scale_range_schedule``.  ``operands="auto"`` (in ``kw``): as in ``sample``."""
+    iteration (unbounded_synthesis.py:82-89).  See ``weg.scale_range_schedule``.  ``operands="auto"`` and ``modality_weights`` (in ``kw``):
+    as in ``sample``."""
     if check_operands(kw.get("operands")) == "auto":
         args = dict(locals())
         rest = args.pop("kw")

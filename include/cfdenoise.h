@@ -177,6 +177,17 @@ typedef struct {
  * the initial latents and captures ONE loop iteration (replicate -> denoiser -> guidance -> scheduler
  * step) as a hipGraph on `stream`. */
 int cfd_sample_begin(cfd_handle h, const cfd_sample_args* args, void* stream);
+/* cfd_sample_begin with per-modality guidance weights that may change over the schedule and differ per utterance (the reference's
+ * w_c, convofusion.py:527-541, "kept 1 as a standard").  `weights`: HOST float32 [iterations][B][8], copied once; entry [i][b][k] is the
+ * whole factor of chunk k >= 1 for utterance b in iteration i -- guidance_scale * w_c as the reference would compute it -- and [i][b][0]
+ * is ignored.  The combine is the default run's term for term: e_0 + ((((w_1 (e_1 - e_0) + w_2 (e_2 - e_0)) + ...) + w_6 (e_6 - e_0)).
+ * args->guidance_weight and args->skip_zero_weight_chunks are ignored; args->G must be 7.  A NULL table or a non-finite entry:
+ * CFD_E_ARG.  prune != 0: every chunk k >= 1 whose weight is exactly 0 in all iterations and for all utterances is not evaluated (its
+ * term is a zero that leaves the float32 sum unchanged): the memories' row maps are compacted to the evaluated chunks in stream order
+ * (a memory without a row map gets the identity map), so the denoiser runs G_eval * B rows; the full-conditioning chunk is kept when the
+ * run has att_ring (its maps come from it).  *chunks_evaluated (may be NULL) receives G_eval. */
+int cfd_sample_begin_weighted(cfd_handle h, const cfd_sample_args* args, const float* weights, int prune, int* chunks_evaluated,
+                              void* stream);
 /* Replays the captured iteration `n` more times (asynchronously on the run's stream). */
 int cfd_sample_steps(cfd_handle h, int n);
 /* Number of iterations executed so far in the open run. */

@@ -24,7 +24,7 @@ SYMBOLS = [
     "cfd_layer_norm", "cfd_mha", "cfd_add", "cfd_zero_rows", "cfd_gemm_f32", "cfd_softmax", "cfd_softmax_bwd",
     "cfd_layer_norm_bwd", "cfd_ew", "cfd_weg_focus", "cfd_sample_write", "cfd_sample_inpaint", "cfd_weg_eval", "cfd_dyadic_steps",
     "cfd_sample_census", "cfd_dpmsolver_step", "cfd_test_step_coefficients", "cfd_test_gemm_epi",
-    "cfd_vae_encode", "cfd_sample_begin_weighted",
+    "cfd_vae_encode", "cfd_sample_begin_weighted", "cfd_sample_begin_edit",
 ]
 
 
@@ -67,6 +67,11 @@ class SampleArgs(C.Structure):
 
 
 CENSUS_MAX_LAYERS = 16
+
+
+class EditArgs(C.Structure):
+    """cfd_edit_args: the source latents (dev [B][L][128]), the keep mask (dev uint8 [B][L] or NULL) and the first iteration k0."""
+    _fields_ = [("source", C.c_void_p), ("keep", C.c_void_p), ("first_iteration", C.c_int)]
 
 
 class Census(C.Structure):
@@ -157,6 +162,8 @@ def load():
                                 C.POINTER(Memory), C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p]
     lib.cfd_sample_begin.argtypes = [C.c_void_p, C.POINTER(SampleArgs), C.c_void_p]
     lib.cfd_sample_begin_weighted.argtypes = [C.c_void_p, C.POINTER(SampleArgs), C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p]
+    lib.cfd_sample_begin_edit.argtypes = [C.c_void_p, C.POINTER(SampleArgs), C.POINTER(EditArgs), C.c_void_p, C.c_int, C.POINTER(C.c_int),
+                                          C.c_void_p]
     lib.cfd_sample_steps.argtypes = [C.c_void_p, C.c_int]
     lib.cfd_sample_position.argtypes = [C.c_void_p]
     lib.cfd_sample_read.argtypes = [C.c_void_p, C.c_void_p, C.c_int]

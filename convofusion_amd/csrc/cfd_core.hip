@@ -88,7 +88,7 @@ extern "C" void cfd_destroy(cfd_handle c) {
   c->sat.release();
   c->acen.release();
   for (auto& kv : c->raw) kv.second.release();
-  DBuf* all[] = {&c->we_sp, &c->wp_sp, &c->wp_f, &c->ln_cd_p, &c->we_all, &c->be_all, &c->tsin, &c->weg_ws, &c->weg_tok, &c->latents, &c->coef, &c->inoise, &c->hist, &c->wtab};
+  DBuf* all[] = {&c->we_sp, &c->wp_sp, &c->wp_f, &c->ln_cd_p, &c->we_all, &c->be_all, &c->tsin, &c->weg_ws, &c->weg_tok, &c->latents, &c->coef, &c->inoise, &c->hist, &c->wtab, &c->esrc, &c->enoise, &c->ekeep};
   for (DBuf* b : all) b->release();
   c->wk[0].release();
   c->wk[1].release();

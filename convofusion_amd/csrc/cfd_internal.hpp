@@ -282,6 +282,12 @@ struct cfd_handle_s {
   bool run_weighted = false;
   int wpos[8];
   DBuf wtab;
+  // Edit run (cfd_sample_begin_edit): the run starts at iteration run_k0 of the full table (d_step[0] starts there; run_pos and run_iters
+  // count executed iterations).  run_edit: the edit instances of begin_step_kernel / inpaint_now_kernel overwrite the tokens of ekeep
+  // [B][L] with coef[i].sa * esrc + coef[i].sb * enoise ([B][L][128] each: the source latents and the run's initial noise).
+  int run_k0 = 0;
+  bool run_edit = false;
+  DBuf esrc, enoise, ekeep;
   int run_pos = 0;
 };
 typedef cfd_handle_s Ctx;

@@ -61,9 +61,10 @@ static void dpmpp_coef(const float* ac, int t, int prev_t, int t_prev_model, Ste
 }
 
 // The per-iteration coefficient rows of a loop over the timestep table ts[0..N) (what cfd_sample_begin uploads).  Kind 2 needs the table
-// strictly decreasing in [1, T): iteration 0 is first order, the last one too when N < 15 (lower_order_final), all others second order.
+// strictly decreasing in [1, T): the first executed iteration k0 is first order (diffusers' lower_order_nums is 0 there: no history), the
+// last one too when N < 15 (lower_order_final, from the full table's length), all others second order.
 static int step_coefficients(int kind, const float* ac, int T, int n_inf, const int32_t* ts, int N, float eta, int set_alpha_to_one,
-                             StepCoef* coef) {
+                             StepCoef* coef, int k0 = 0) {
   for (int i = 0; i < N; ++i) {
     const int t = ts[i];
     if (t < 0 || t >= T) return fail(CFD_E_ARG, "timestep %d out of range", t);
@@ -73,7 +74,7 @@ static int step_coefficients(int kind, const float* ac, int T, int n_inf, const 
     else {
       if (t < 1 || (i > 0 && t >= ts[i - 1]))
         return fail(CFD_E_ARG, "DPM-Solver++: the timestep table must decrease strictly and stay in [1, %d) (entry %d is %d)", T, i, t);
-      const bool first = i == 0 || (i == N - 1 && N < 15);
+      const bool first = i <= k0 || (i == N - 1 && N < 15);
       dpmpp_coef(ac, t, i + 1 < N ? ts[i + 1] : 0, first ? -1 : ts[i - 1], &coef[i]);
     }
   }
@@ -82,12 +83,29 @@ static int step_coefficients(int kind, const float* ac, int T, int n_inf, const 
 
 static void (*const cfg_step_kernel_weighted)(const CfgStepArgsW) = cfg_step_kernel<0, true>;   // (one macro argument for LAUNCH)
 
+static void (*const begin_step_kernel_edit)(const BeginArgsE) = begin_step_kernel<0, true>;   // (one macro argument for LAUNCH)
+
+static BeginArgsE edit_begin_args(Ctx* c) {
+  const cfd_sample_args& s = c->sargs;
+  BeginArgsE be;
+  static_cast<BeginArgs&>(be) = BeginArgs{c->latents.as<float>(), c->w->sample_sp.as<char>(), s.B, s.L, s.G, nullptr, nullptr, 0,
+                                          c->coef.as<StepCoef>(), c->w->d_step.as<int>()};
+  be.keep = c->ekeep.as<uint8_t>();
+  be.src = c->esrc.as<float>();
+  be.eps = c->enoise.as<float>();
+  return be;
+}
+
 static int enqueue_loop_iteration(Ctx* c, hipStream_t st) {
   const cfd_sample_args& s = c->sargs;
   const long long n8 = (long long)s.B * s.L * (CFD_LAT / 8);
-  BeginArgs ba{c->latents.as<float>(), c->w->sample_sp.as<char>(), s.B, s.L, s.G, s.preseq, c->inoise.as<float>(), s.preseq_len,
-               c->coef.as<StepCoef>(), c->w->d_step.as<int>()};
-  LAUNCH(CFD_PROF_OTHER, begin_step_kernel<>, dim3((unsigned)((n8 + 255) / 256)), dim3(256), st, ba);
+  if (c->run_edit) {
+    LAUNCH(CFD_PROF_OTHER, begin_step_kernel_edit, dim3((unsigned)((n8 + 255) / 256)), dim3(256), st, edit_begin_args(c));
+  } else {
+    BeginArgs ba{c->latents.as<float>(), c->w->sample_sp.as<char>(), s.B, s.L, s.G, s.preseq, c->inoise.as<float>(), s.preseq_len,
+                 c->coef.as<StepCoef>(), c->w->d_step.as<int>()};
+    LAUNCH(CFD_PROF_OTHER, begin_step_kernel<>, dim3((unsigned)((n8 + 255) / 256)), dim3(256), st, ba);
+  }
   CHK(enqueue_denoise(c, st));
   CfgStepArgs ca;
   memset(&ca, 0, sizeof(ca));
@@ -153,10 +171,22 @@ static int weighted_chunks(Ctx* c, const float* wtab, int prune, int N, bool kee
   return CFD_OK;
 }
 
-static int sample_begin(Ctx* c, const cfd_sample_args* args, void* stream, const float* wtab, int prune, int* chunks_evaluated);
+static int sample_begin(Ctx* c, const cfd_sample_args* args, void* stream, const float* wtab, int prune, int* chunks_evaluated,
+                        const cfd_edit_args* edit = nullptr);
 
 extern "C" int cfd_sample_begin(cfd_handle c, const cfd_sample_args* args, void* stream) {
   return sample_begin(c, args, stream, nullptr, 0, nullptr);
+}
+
+extern "C" int cfd_sample_begin_edit(cfd_handle c, const cfd_sample_args* args, const cfd_edit_args* e, const float* weights, int prune,
+                                     int* chunks_evaluated, void* stream) {
+  if (!c || !args || !e) return fail(CFD_E_ARG, "null argument");
+  if (!e->source) return fail(CFD_E_ARG, "cfd_sample_begin_edit: the source latents are NULL");
+  if (args->preseq) return fail(CFD_E_ARG, "cfd_sample_begin_edit: an edit run has no preseq (the rollout's prefix in-painting)");
+  if (weights && args->G != 7) return fail(CFD_E_ARG, "cfd_sample_begin_edit: a weight table needs the 7-chunk guidance batch (G = %d)", args->G);
+  const int r = sample_begin(c, args, stream, weights, weights ? prune : 0, weights ? chunks_evaluated : nullptr, e);
+  if (r == CFD_OK && !weights && chunks_evaluated) *chunks_evaluated = c->sargs.G;
+  return r;
 }
 
 extern "C" int cfd_sample_begin_weighted(cfd_handle c, const cfd_sample_args* args, const float* weights, int prune, int* chunks_evaluated,
@@ -167,7 +197,8 @@ extern "C" int cfd_sample_begin_weighted(cfd_handle c, const cfd_sample_args* ar
   return sample_begin(c, args, stream, weights, prune, chunks_evaluated);
 }
 
-static int sample_begin(Ctx* c, const cfd_sample_args* args, void* stream, const float* wtab, int prune, int* chunks_evaluated) {
+static int sample_begin(Ctx* c, const cfd_sample_args* args, void* stream, const float* wtab, int prune, int* chunks_evaluated,
+                        const cfd_edit_args* edit) {
   if (!c || !args) return fail(CFD_E_ARG, "null argument");
   if (c->run_open) return fail(CFD_E_STATE, "a sampling run is already open");
   HIPCHK(hipSetDevice(c->cfg.device));
@@ -183,6 +214,8 @@ static int sample_begin(Ctx* c, const cfd_sample_args* args, void* stream, const
     args = &s_w;
   }
   c->run_weighted = false;
+  c->run_edit = false;
+  c->run_k0 = 0;
   const cfd_sample_args& s = *args;
   if (s.B < 1 || (s.G != 1 && s.G != 7 && (s.G < 1 || s.G > 8))) return fail(CFD_E_ARG, "bad B / G");
   if (s.scheduler < 0 || s.scheduler > 2) return fail(CFD_E_ARG, "scheduler must be 0 (DDPM), 1 (DDIM) or 2 (DPM-Solver++ (2M))");
@@ -197,6 +230,18 @@ static int sample_begin(Ctx* c, const cfd_sample_args* args, void* stream, const
                            "counts differs between diffusers releases (unpinned); pass the scheduler's table in cfd_sample_args.timesteps",
                 s.num_inference_steps, s.num_train_timesteps);
   if (s.preseq && (s.preseq_len < 1 || s.preseq_len > s.L)) return fail(CFD_E_ARG, "bad preseq_len");
+  const int n_iter = s.timesteps ? s.num_timesteps : s.num_inference_steps;
+  const int k0 = edit ? edit->first_iteration : 0;
+  std::vector<uint8_t> hkeep;
+  if (edit) {
+    if (k0 < 0 || k0 >= n_iter) return fail(CFD_E_ARG, "cfd_sample_begin_edit: first_iteration = %d is not in [0, %d)", k0, n_iter);
+    if (edit->keep) {
+      hkeep.resize((size_t)s.B * s.L);
+      HIPCHK(hipMemcpy(hkeep.data(), edit->keep, hkeep.size(), hipMemcpyDeviceToHost));
+      for (size_t e = 0; e < hkeep.size(); ++e)
+        if (hkeep[e] > 1) return fail(CFD_E_ARG, "cfd_sample_begin_edit: keep[%zu][%zu] = %d is not 0 or 1", e / s.L, e % s.L, (int)hkeep[e]);
+    }
+  }
   hipStream_t st = (hipStream_t)stream;
   c->sargs = s;
   c->run_stream = st;
@@ -290,8 +335,9 @@ static int sample_begin(Ctx* c, const cfd_sample_args* args, void* stream, const
     pb.att_b0 = c->chunk_pos[c->sargs.G - 1] * s.B;
     pb.att_nb = s.B;
     for (int j = 0; j < CFD_NMEM; ++j) {
-      pb.att[j] = s.att_ring[j];
       pb.att_slot[j] = (long long)s.B * c->nl * s.L * pb.S[j];
+      // slot *d_step of the ring base: an edit run's d_step starts at k0 and executed iteration j goes to the caller's slot j
+      pb.att[j] = s.att_ring[j] - (long long)k0 * pb.att_slot[j];
     }
     if (!pb.rt) {
       pb.att_fused = true;
@@ -315,7 +361,7 @@ static int sample_begin(Ctx* c, const cfd_sample_args* args, void* stream, const
   std::vector<StepCoef> coef(N);
   const int ratio = T / n_inf;
   for (int i = 0; i < N; ++i) ts[i] = s.timesteps ? s.timesteps[i] : (N - 1 - i) * ratio + (s.scheduler == 1 ? s.steps_offset : 0);
-  CHK(step_coefficients(s.scheduler, s.alphas_cumprod, T, n_inf, ts.data(), N, s.eta, s.set_alpha_to_one, coef.data()));
+  CHK(step_coefficients(s.scheduler, s.alphas_cumprod, T, n_inf, ts.data(), N, s.eta, s.set_alpha_to_one, coef.data(), k0));
   CHK(c->coef.ensure((size_t)N * sizeof(StepCoef)));
   HIPCHK(hipMemcpyAsync(c->coef.p, coef.data(), (size_t)N * sizeof(StepCoef), hipMemcpyHostToDevice, st));
   HIPCHK(hipMemsetAsync(c->w->d_step.p, 0, 16, st));
@@ -331,8 +377,28 @@ static int sample_begin(Ctx* c, const cfd_sample_args* args, void* stream, const
   } else {
     CHK(enqueue_philox_fill(c->latents.as<float>(), s.B, s.L * CFD_LAT, (uint64_t)s.seed, 0u, s.first_utterance, 1u, 1.0f, st));
   }
-  // DPM-Solver++: the x0 history of the run, zeroed.  Iteration 0 is first order and never reads it, so the eager warm-up iteration below,
-  // which runs as iteration 0 and writes its x0 here, needs no save / restore: the first replay overwrites that before anything reads it.
+  if (edit) {   // the run's noise eps = the initial draw, the source, the mask; k0 > 0: every token starts at sa_k0 * source + sb_k0 * eps
+    CHK(c->enoise.ensure(lat_bytes));
+    CHK(c->esrc.ensure(lat_bytes));
+    CHK(c->ekeep.ensure((size_t)s.B * s.L));
+    HIPCHK(hipMemcpyAsync(c->enoise.p, c->latents.p, lat_bytes, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(c->esrc.p, edit->source, lat_bytes, hipMemcpyDeviceToDevice, st));
+    if (edit->keep) HIPCHK(hipMemcpyAsync(c->ekeep.p, hkeep.data(), hkeep.size(), hipMemcpyHostToDevice, st));
+    else HIPCHK(hipMemsetAsync(c->ekeep.p, 0, (size_t)s.B * s.L, st));
+    if (k0 > 0) {
+      const long long n8 = (long long)s.B * s.L * (CFD_LAT / 8);
+      hipLaunchKernelGGL(edit_init_kernel<>, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, st, c->latents.as<float>(), c->esrc.as<float>(),
+                         c->enoise.as<float>(), n8, c->coef.as<StepCoef>(), k0);
+      HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipStreamSynchronize(st));   // (hkeep goes out of scope)
+    c->run_edit = true;
+    c->run_k0 = k0;
+    c->run_iters = N - k0;
+  }
+  // DPM-Solver++: the x0 history of the run, zeroed.  The first executed iteration is first order and never reads it, so the eager warm-up
+  // iteration below, which runs as that iteration and writes its x0 here, needs no save / restore: the first replay overwrites that before
+  // anything reads it.
   if (s.scheduler == 2) {
     CHK(c->hist.ensure(lat_bytes));
     HIPCHK(hipMemsetAsync(c->hist.p, 0, lat_bytes, st));
@@ -355,11 +421,13 @@ static int sample_begin(Ctx* c, const cfd_sample_args* args, void* stream, const
       CHK(save_in.ensure(c->inoise.bytes));
       HIPCHK(hipMemcpyAsync(save_in.p, c->inoise.p, c->inoise.bytes, hipMemcpyDeviceToDevice, st));
     }
+    if (k0) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)c->w->d_step.p, k0, 1, st));   // (d_step[0] = k0: coefficients, tables, ring slot 0)
     int r = enqueue_loop_iteration(c, st);
     if (r != CFD_OK) return r;
     HIPCHK(hipMemcpyAsync(c->latents.p, save_lat.p, lat_bytes, hipMemcpyDeviceToDevice, st));
     if (s.preseq) HIPCHK(hipMemcpyAsync(c->inoise.p, save_in.p, c->inoise.bytes, hipMemcpyDeviceToDevice, st));
     HIPCHK(hipMemsetAsync(c->w->d_step.p, 0, 16, st));
+    if (k0) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)c->w->d_step.p, k0, 1, st));
     if (c->acen_on) HIPCHK(hipMemsetAsync(c->acen.p, 0, (size_t)c->nl * XA_CEN_SLOTS * XA_CEN_STRIDE * sizeof(unsigned), st));   // (the warm-up counted too)
     HIPCHK(hipStreamSynchronize(st));
     save_lat.release();
@@ -566,10 +634,21 @@ extern "C" int cfd_philox_normal(cfd_handle c, float* out, int B, int per_utt, u
   return enqueue_philox_fill(out, B, per_utt, seed, step, first_utt, stream_id, 1.0f, (hipStream_t)stream);
 }
 
+static void (*const inpaint_now_kernel_edit)(const BeginArgsE, int*) = inpaint_now_kernel<0, true>;
+
 extern "C" int cfd_sample_inpaint(cfd_handle c) {
   if (!c) return fail(CFD_E_ARG, "null handle");
   if (!c->run_open) return fail(CFD_E_STATE, "no sampling run open");
   const cfd_sample_args& s = c->sargs;
+  if (c->run_edit) {   // the edit instance: the kept tokens of this iteration, then the captured iteration skips its overwrite
+    if (c->run_pos >= c->run_iters) return fail(CFD_E_STATE, "cfd_sample_inpaint: the run has no iteration left");
+    HIPCHK(hipSetDevice(c->cfg.device));
+    const long long n8 = (long long)s.B * s.L * (CFD_LAT / 8);
+    hipLaunchKernelGGL(inpaint_now_kernel_edit, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, c->run_stream, edit_begin_args(c),
+                       c->w->d_step.as<int>());
+    HIPCHK(hipGetLastError());
+    return CFD_OK;
+  }
   if (!s.preseq || s.preseq_len < 1) return CFD_OK;
   HIPCHK(hipSetDevice(c->cfg.device));
   BeginArgs ba{c->latents.as<float>(), c->w->sample_sp.as<char>(), s.B, s.L, s.G, s.preseq, c->inoise.as<float>(), s.preseq_len,

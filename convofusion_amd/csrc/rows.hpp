@@ -587,9 +587,34 @@ struct BeginArgs {
   const StepCoef* coef;
   const int* d_step;
 };
+// The edit instance's arguments (cfd_sample_begin_edit): instead of the first `pl` tokens, every token (b, l) with keep[b * L + l] = 1 is
+// overwritten at the start of iteration i with fl(fl(sa_i * src) + fl(sb_i * eps)) (no fused multiply-add: the value is the float32
+// expression a host or torch computes).  eps is the run's initial N(0,1) draw, never rewritten (the rollout's i == 0 aliasing is not
+// reproduced).  preseq / inoise / pl are unused.  The default instances keep BeginArgs and their code.
+struct BeginArgsE : BeginArgs {
+  const uint8_t* keep;   // [B][L] 0 / 1
+  const float* src;      // [B][L][128] source latents
+  const float* eps;      // [B][L][128] the run's initial noise
+};
+template <bool EDIT>
+using BeginArgsOf = typename std::conditional<EDIT, BeginArgsE, BeginArgs>::type;
 
-template <int CFD_KI = 0>
-__global__ void begin_step_kernel(const BeginArgs a) {
+// 8 consecutive elements of sa * src + sb * eps, each product and the sum rounded on its own
+__device__ __forceinline__ void edit_mix8(float sa, float sb, const float* src, const float* eps, float v[8]) {
+  const float4 s0 = *reinterpret_cast<const float4*>(src), s1 = *reinterpret_cast<const float4*>(src + 4);
+  const float4 e0 = *reinterpret_cast<const float4*>(eps), e1 = *reinterpret_cast<const float4*>(eps + 4);
+  const float s[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
+  const float e[8] = {e0.x, e0.y, e0.z, e0.w, e1.x, e1.y, e1.z, e1.w};
+#pragma unroll
+  for (int q = 0; q < 8; ++q) v[q] = __fadd_rn(__fmul_rn(sa, s[q]), __fmul_rn(sb, e[q]));
+}
+__device__ __forceinline__ void store8(float* p, const float v[8]) {
+  *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+  *reinterpret_cast<float4*>(p + 4) = make_float4(v[4], v[5], v[6], v[7]);
+}
+
+template <int CFD_KI = 0, bool EDIT = false>
+__global__ void begin_step_kernel(const BeginArgsOf<EDIT> a) {
   const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;  // one thread = 8 elements
   const long long n8 = (long long)a.B * a.L * (CFD_LAT / 8);
   if (idx >= n8) return;
@@ -598,7 +623,16 @@ __global__ void begin_step_kernel(const BeginArgs a) {
   const int l = (int)(bl % a.L), b = (int)(bl / a.L);
   float* lp = a.latents + bl * CFD_LAT + c;
   float v[8];
-  if (a.preseq && l < a.pl && a.d_step[2] == 0) {   // d_step[2] != 0: cfd_sample_inpaint already did this iteration's overwrite
+  if constexpr (EDIT) {
+    if (a.keep[bl] && a.d_step[2] == 0) {   // d_step[2] != 0: cfd_sample_inpaint already did this iteration's overwrite
+      const int i = *a.d_step;
+      edit_mix8(a.coef[i].sa, a.coef[i].sb, a.src + bl * CFD_LAT + c, a.eps + bl * CFD_LAT + c, v);
+      store8(lp, v);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] = lp[e];
+    }
+  } else if (a.preseq && l < a.pl && a.d_step[2] == 0) {   // d_step[2] != 0: cfd_sample_inpaint already did this iteration's overwrite
     const int i = *a.d_step;
     const float sa = a.coef[i].sa, sb = a.coef[i].sb;
     const long long po = ((long long)b * a.pl + l) * CFD_LAT + c;
@@ -723,11 +757,35 @@ __global__ void cfg_step_kernel(const CfgStepArgsOf<WTAB> a) {
   }
 }
 
+// Start of an edit run at iteration k0 > 0 (cfd_sample_begin_edit, img2img): every token = fl(fl(sa * src) + fl(sb * eps)) with coef row
+// k0; one thread = 8 elements.
+template <int CFD_KI = 0>
+__global__ void edit_init_kernel(float* latents, const float* src, const float* eps, long long n8, const StepCoef* coef, int k0) {
+  const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n8) return;
+  float v[8];
+  edit_mix8(coef[k0].sa, coef[k0].sb, src + idx * 8, eps + idx * 8, v);
+  store8(latents + idx * 8, v);
+}
+
 // The in-painting overwrite of begin_step_kernel alone, ahead of the captured iteration (cfd_sample_inpaint): the WEG
 // branch of the rollout alters the latents AFTER the overwrite and BEFORE the replication (unbounded_synthesis.py:70-143).
-template <int CFD_KI = 0>
-__global__ void inpaint_now_kernel(const BeginArgs a, int* d_step) {
+template <int CFD_KI = 0, bool EDIT = false>
+__global__ void inpaint_now_kernel(const BeginArgsOf<EDIT> a, int* d_step) {
   const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if constexpr (EDIT) {   // one thread = 8 elements of one token, kept tokens only
+    const long long n8 = (long long)a.B * a.L * (CFD_LAT / 8);
+    if (idx == 0) d_step[2] = 1;
+    if (idx >= n8) return;
+    const long long bl = idx / (CFD_LAT / 8);
+    if (!a.keep[bl]) return;
+    const long long o = bl * CFD_LAT + (idx % (CFD_LAT / 8)) * 8;
+    const int i = *a.d_step;
+    float v[8];
+    edit_mix8(a.coef[i].sa, a.coef[i].sb, a.src + o, a.eps + o, v);
+    store8(a.latents + o, v);
+    return;
+  }
   const long long n = (long long)a.B * a.pl * CFD_LAT;
   if (idx == 0) d_step[2] = 1;
   if (idx >= n) return;

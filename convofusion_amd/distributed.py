@@ -57,13 +57,15 @@ def shard_modality_weights(modality_weights, start, stop, total):
     return modality_weights
 
 
-def sample_sharded(sample_fn, encoder_hidden_states, cond_masks, total_utterances, chunks=7, group=None, modality_weights=None):
+def sample_sharded(sample_fn, encoder_hidden_states, cond_masks, total_utterances, chunks=7, group=None, modality_weights=None,
+                   source_latents=None, keep_mask=None):
     """Run ``sample_fn(enc_shard, masks_shard, B=<local>, first_utterance=<global id>)`` on this rank's
     utterances and return the gathered latents [total, L, 128] on every rank.  A ``sample_fn`` with ``operands="auto"`` decides PER RANK:
     each rank's census sees its own utterances only, so one rank may fall back to ``operands=0`` while another keeps the default policy
     (each shard's result is still bit for bit one of the two policies' for its utterances); no decision is all-reduced.
     ``modality_weights`` (optional): per-modality guidance weights of the whole batch; ``sample_fn`` then also gets
-    ``modality_weights=`` with this rank's utterances (``shard_modality_weights``)."""
+    ``modality_weights=`` with this rank's utterances (``shard_modality_weights``).  ``source_latents`` [total, L, 128] / ``keep_mask``
+    [total, L] (optional, an edit run): ``sample_fn`` gets this rank's rows of each under the same names."""
     ws = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     a, b = shard_range(total_utterances, rank, ws)
@@ -72,5 +74,10 @@ def sample_sharded(sample_fn, encoder_hidden_states, cond_masks, total_utterance
     extra = {}
     if modality_weights is not None:
         extra["modality_weights"] = shard_modality_weights(modality_weights, a, b, total_utterances)
+    for name, t in (("source_latents", source_latents), ("keep_mask", keep_mask)):
+        if t is not None:
+            if t.shape[0] != total_utterances:
+                raise ValueError(f"{name} has {t.shape[0]} rows for {total_utterances} utterances")
+            extra[name] = t[a:b]
     local = sample_fn(enc, masks, B=b - a, first_utterance=a, **extra)
     return gather_latents(local, total_utterances, group)

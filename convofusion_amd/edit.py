@@ -1,0 +1,102 @@
+"""Motion editing with the fused loop: token-masked in-painting and img2img strength (``SamplingRun(source_latents=, keep_mask=,
+strength=)``, cfd_sample_begin_edit).
+
+The loop's 16 latent tokens are 8 time chunks x {body, hands}: token 2c + p is 16-frame chunk c, part p (the reference's reshape of the
+loop's latents into the VAE's [2, B, T, 128], convofusion.py:1028-1030), and frame f of a 128-frame window lies in chunk f // 16.  One
+[B, L] keep mask therefore selects time spans, body parts or both:
+
+    keep the body, regenerate the hands   token_mask(B, keep_parts=("body",))
+    in-betweening                         token_mask(B, keep_frames=[(0, 32), (96, 128)])
+    variation of the whole gesture        no mask, strength 0.5
+
+``edit_motion`` runs the whole edit: HIP ``encode`` of the source motion, the fused edit loop, HIP ``decode``.
+"""
+import inspect
+
+import torch
+
+from .sampler import check_operands, sample
+from .vae import LATENT_PARTS
+
+FRAMES_PER_CHUNK = 16   # vae.py:178
+
+
+def part_index(part):
+    """Index p of a body part on the VAE latent's first axis, which is also its place in a token pair (token 2c + p)."""
+    if part not in LATENT_PARTS:
+        raise ValueError(f"unknown body part {part!r} (known: {', '.join(LATENT_PARTS)})")
+    return LATENT_PARTS.index(part)
+
+
+def token_mask(B, keep_frames=None, keep_parts=("body", "hands"), L=16):
+    """bool [B, L] keep mask of the loop's tokens (the same for every utterance; stack or index rows for per-utterance masks).
+    keep_frames: None (every frame) or half-open frame spans [(start, stop), ...] within the L / 2 * 16 frames of the window; a chunk is
+    kept when a span covers any of its frames (masks are not finer than a 16-frame chunk).  keep_parts: the parts kept in those chunks."""
+    if L < 2 or L % 2:
+        raise ValueError(f"L = {L}: the loop's tokens come in (body, hands) pairs")
+    T = L // 2
+    parts = [keep_parts] if isinstance(keep_parts, str) else list(keep_parts)
+    chunks = torch.zeros(T, dtype=torch.bool)
+    if keep_frames is None:
+        chunks[:] = True
+    else:
+        for span in keep_frames:
+            try:
+                start, stop = (int(v) for v in span)
+            except (TypeError, ValueError):
+                raise ValueError(f"keep_frames: {span!r} is not a (start, stop) frame span") from None
+            if not 0 <= start < stop <= T * FRAMES_PER_CHUNK:
+                raise ValueError(f"keep_frames: span ({start}, {stop}) is not inside the window's {T * FRAMES_PER_CHUNK} frames")
+            chunks[start // FRAMES_PER_CHUNK:(stop - 1) // FRAMES_PER_CHUNK + 1] = True
+    mask = torch.zeros(T, 2, dtype=torch.bool)
+    for part in parts:
+        mask[:, part_index(part)] = chunks
+    return mask.reshape(1, L).expand(int(B), L).clone()
+
+
+def vae_to_loop(z):
+    """VAE latent [2, B, T, D] (body | hands) -> loop latents [B, 2T, D]: the reference's permute(1, 2, 0, 3) (convofusion.py:725) and
+    reshape(bs, t * bh, dim) (:558)."""
+    two, B, T, D = z.shape
+    return z.permute(1, 2, 0, 3).reshape(B, T * two, D)
+
+
+def loop_to_vae(z):
+    """Loop latents [B, L, D] -> VAE latent [2, B, L / 2, D]: the reference's permute(1, 0, 2) (convofusion.py:548), then
+    reshape(ntokens // 2, 2, bs, dim) and permute(1, 2, 0, 3) (:1027-1030)."""
+    z = z.permute(1, 0, 2)
+    ntokens, bs, dim = z.shape
+    return z.reshape(ntokens // 2, 2, bs, dim).permute(1, 2, 0, 3)
+
+
+def edit_motion(model, feats, lengths, encoder_hidden_states, cond_masks=None, *, keep_mask=None, strength=1.0, seed=0,
+                sample_posterior=False, modality_weights=None, operands=None):
+    """Edit motions with the fused loop.  ``model``: a Convofusion-like object (reads vae / denoiser / scheduler / cfg / guidance_scale /
+    clf_guidance_drops / do_classifier_free_guidance as ``sampler.diffusion_reverse`` does); ``model.vae`` encodes and decodes on the HIP
+    path (``convofusion_amd.vae.ConvoFusionVae``, or a reference module after ``attach_hip_encode`` / ``attach_hip_decode``).
+    feats [B, nframes, 189], lengths: the source motions; encoder_hidden_states / cond_masks: the guidance batch as for the loop.
+    The source latents are the posterior mean (``sample_posterior=True``: encode's draw from the default generator), the loop's initial
+    noise and step noise come from Philox with ``seed``; keep_mask [B, nframes / 8] (``token_mask``), strength, modality_weights, operands:
+    as in ``sampler.sample``.  Returns (features [B, nframes, 189], loop latents [B, nframes / 8, 128])."""
+    if not model.do_classifier_free_guidance:
+        raise NameError("guidance_bs_mulitplier: the reference loop requires classifier-free guidance")
+    latent, dist, _ = model.vae.encode(feats, lengths)
+    z = latent if sample_posterior else dist.mean.reshape(latent.shape)
+    source = vae_to_loop(z)
+    B, L = int(source.shape[0]), int(source.shape[1])
+    G = model.clf_guidance_drops + 1
+    if encoder_hidden_states[0].shape[0] != G * B:
+        raise ValueError(f"the guidance batch has {encoder_hidden_states[0].shape[0]} rows for {B} motions and {G} chunks")
+    sch = model.scheduler
+    eta = 0.0
+    if "eta" in set(inspect.signature(sch.step).parameters.keys()):          # convofusion.py:427-429
+        eta = model.cfg.model.scheduler.eta
+    if modality_weights is None:
+        modality_weights = getattr(model, "_cfd_modality_weights", None)
+    lat = sample(model.denoiser, sch, encoder_hidden_states, cond_masks, B=B, L=L,
+                 num_inference_steps=model.cfg.model.scheduler.num_inference_timesteps, guidance_scale=model.guidance_scale,
+                 guidance_chunks=G, eta=eta, seed=seed, skip_zero_weight_chunks=True,
+                 operands=check_operands(getattr(model, "_cfd_operands", None) if operands is None else operands),
+                 modality_weights=modality_weights, source_latents=source, keep_mask=keep_mask, strength=strength)
+    out = model.vae.decode(loop_to_vae(lat), lengths)
+    return out, lat

@@ -110,6 +110,54 @@ def modality_weight_table(modality_weights, guidance_scale, N, B, guidance_chunk
     return table
 
 
+def edit_first_iteration(strength, N):
+    """The first iteration k0 of an edit run over a table of N iterations at img2img ``strength`` -- diffusers' img2img convention
+    (``get_timesteps``): k = min(int(N * strength), N) iterations are executed, k0 = N - k.  strength outside (0, 1], or one that executes
+    no iteration (k == 0), raises ValueError."""
+    try:
+        st = float(strength)
+    except (TypeError, ValueError):
+        raise ValueError(f"strength must be a number in (0, 1], not {strength!r}") from None
+    if not 0.0 < st <= 1.0:
+        raise ValueError(f"strength = {strength!r} is not in (0, 1]")
+    k = min(int(N * st), N)
+    if k == 0:
+        raise ValueError(f"strength = {strength!r} executes no iteration of the {N}-iteration schedule (int({N} * strength) = 0)")
+    return N - k
+
+
+def check_edit(source_latents, keep_mask, strength, B, L, N, preseq=None, device=None):
+    """The edit arguments of a run (``SamplingRun``): None when the run is no edit (no source, strength 1), else (source float32 [B, L, 128]
+    contiguous on ``device``, keep mask uint8 [B, L] on ``device`` or None, k0).  Refusals (ValueError): keep_mask or strength < 1 without
+    source_latents, preseq together with an edit, a source other than a floating-point [B, L, 128] tensor, a keep mask other than a bool or
+    integer [B, L] tensor of 0 / 1, strength outside (0, 1] or executing no iteration (``edit_first_iteration``)."""
+    k0 = edit_first_iteration(strength, N)
+    if source_latents is None:
+        if keep_mask is not None:
+            raise ValueError("keep_mask needs source_latents: the kept tokens are re-noised from them")
+        if k0 != 0:
+            raise ValueError(f"strength = {strength!r} < 1 needs source_latents: the run starts part-way down the schedule from them")
+        return None
+    if preseq is not None:
+        raise ValueError("preseq (the rollout's prefix in-painting) and an edit (source_latents) do not go together: give the prefix as a "
+                         "keep_mask over its tokens instead")
+    if not isinstance(source_latents, torch.Tensor) or not source_latents.is_floating_point():
+        raise ValueError("source_latents must be a floating-point tensor [B, L, 128]")
+    if tuple(source_latents.shape) != (B, L, 128):
+        raise ValueError(f"source_latents must be [B, L, 128] = [{B}, {L}, 128], not {list(source_latents.shape)}")
+    src = source_latents.detach().to(device=device, dtype=torch.float32).contiguous()
+    keep = None
+    if keep_mask is not None:
+        if not isinstance(keep_mask, torch.Tensor) or keep_mask.is_floating_point() or keep_mask.is_complex():
+            raise ValueError("keep_mask must be a bool or integer (0 / 1) tensor [B, L]")
+        if tuple(keep_mask.shape) != (B, L):
+            raise ValueError(f"keep_mask must be [B, L] = [{B}, {L}], not {list(keep_mask.shape)}")
+        if keep_mask.dtype != torch.bool and bool(((keep_mask != 0) & (keep_mask != 1)).any()):
+            raise ValueError("keep_mask holds values other than 0 and 1")
+        keep = keep_mask.detach().to(device=device, dtype=torch.uint8).contiguous()
+    return src, keep, k0
+
+
 class CensusTripped(Exception):
     """Raised inside an ``operands="auto"`` run when its census counts a row above the threshold (caught by the loop entry points)."""
 
@@ -244,7 +292,7 @@ class SamplingRun:
                  guidance_scale=7.5, guidance_chunks=CFG_CHUNKS, eta=0.0, init_latents=None, step_noise=None,
                  seed=0, first_utterance=0, preseq=None, dedup=True, skip_zero_weight_chunks=False, row_maps=None,
                  dynamic_memories=(), side_engine=False, attention_ring=False, operands=None, census_tau=None, modality_weights=None,
-                 prune_zero_weight_chunks=True):
+                 prune_zero_weight_chunks=True, source_latents=None, keep_mask=None, strength=1.0):
         """attention_ring: keep the attention maps of the full-conditioning chunk of EVERY iteration (the reference's per-iteration dict,
         convofusion.py:517-523): the captured iteration stores them into ``self.att_ring`` -- five tensors [iterations, B, layers, L, S_j]
         -- with no extra forward and no host round trip (cfd_sample_args.att_ring: the row-tile kernels store them from their second
@@ -265,7 +313,12 @@ class SamplingRun:
         two runs on one module can be open at once (the attention forward of ``last_step_attention`` uses it for a plain forward).
         dynamic_memories: indices j of memories whose CONTENTS the caller rewrites between iterations (DyadicRun's partner
         projection).  All others are constants of the run, as in the reference loop, and the library computes the
-        timestep-independent part of their projections once (cfd_sample_args.dynamic_memory_mask)."""
+        timestep-independent part of their projections once (cfd_sample_args.dynamic_memory_mask).
+        source_latents / keep_mask / strength: an edit run (cfd_sample_begin_edit, ``check_edit``; ``convofusion_amd.edit``).  At the start
+        of every iteration i the tokens with keep_mask = 1 are set to sa_i * source + sb_i * eps (eps = the run's initial draw), the rollout's
+        in-painting with a token mask; strength < 1 starts at iteration k0 = N - min(int(N * strength), N) of the scheduler's table from
+        sa_k0 * source + sb_k0 * eps.  ``timesteps`` / ``N`` are then the executed iterations, ``first_iteration`` is k0; step_noise and
+        modality_weights [N, ...] still cover the full table (iteration i keeps its full-table index)."""
         if not isinstance(denoiser, Denoiser):
             raise TypeError("denoiser must be a convofusion_amd.denoiser.Denoiser")
         dev = encoder_hidden_states[0].device
@@ -278,11 +331,14 @@ class SamplingRun:
         # the loop runs over scheduler.timesteps: DDPM clamps the count to the training schedule, and for a count that does not
         # divide it the (opt-in, unpinned) 0.14.0 table has more entries than the count (scheduler.timestep_table)
         num_inference_steps, table = scheduler.timestep_table(num_inference_steps)
-        self.timesteps = [int(t) for t in table]
-        self.B, self.L, self.N = B, L, len(self.timesteps)     # N = loop iterations
+        n_full = len(table)
+        edit = check_edit(source_latents, keep_mask, strength, B, L, n_full, preseq, dev)
+        self.first_iteration = edit[2] if edit is not None else 0
+        self.timesteps = [int(t) for t in table][self.first_iteration:]
+        self.B, self.L, self.N = B, L, len(self.timesteps)     # N = loop iterations executed
         G = guidance_chunks
         # the weighted run's table [N, B, 8] (cfd_sample_begin_weighted), or None: the default path
-        self.modality_weights = None if modality_weights is None else modality_weight_table(modality_weights, guidance_scale, self.N, B, G)
+        self.modality_weights = None if modality_weights is None else modality_weight_table(modality_weights, guidance_scale, n_full, B, G)
         if row_maps is not None:       # already-distinct memories + maps (build_guidance_batch)
             if any(int(m.numel()) != G * B for m in row_maps):
                 raise ValueError(f"row_maps must have G*B = {G * B} entries")
@@ -325,7 +381,7 @@ class SamplingRun:
                 setattr(a, name, t.data_ptr())
         if init_latents is not None and tuple(init_latents.shape) != (B, L, 128):
             raise ValueError("init_latents must be [B, L, 128]")
-        if step_noise is not None and tuple(step_noise.shape) != (self.N, B, L, 128):
+        if step_noise is not None and tuple(step_noise.shape) != (n_full, B, L, 128):
             raise ValueError("step_noise must be [len(scheduler.timesteps), B, L, 128]")
         a.preseq_len = int(preseq.shape[1]) if preseq is not None else 0
         a.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
@@ -346,9 +402,9 @@ class SamplingRun:
             census_tau = CENSUS_TAU
         a.census_tau = float(census_tau or 0.0)
         self._checked = 0
-        ts = (C.c_int32 * self.N)(*self.timesteps)
+        ts = (C.c_int32 * n_full)(*[int(t) for t in table])
         self._keep.append(ts)
-        a.timesteps, a.num_timesteps = C.cast(ts, C.c_void_p), self.N
+        a.timesteps, a.num_timesteps = C.cast(ts, C.c_void_p), n_full
         self.att_ring = None
         if attention_ring:
             if skip_zero_weight_chunks:
@@ -361,7 +417,16 @@ class SamplingRun:
         stream = torch.cuda.current_stream(dev).cuda_stream
         with torch.cuda.device(dev):
             torch.cuda.current_stream(dev).synchronize()
-            if self.modality_weights is None:
+            if edit is not None:
+                e = _lib.EditArgs()
+                e.source, e.keep, e.first_iteration = edit[0].data_ptr(), (edit[1].data_ptr() if edit[1] is not None else None), edit[2]
+                self._keep += [edit[0], edit[1], e]
+                g_eval = C.c_int(0)
+                w_ptr = self.modality_weights.ctypes.data_as(C.c_void_p) if self.modality_weights is not None else None
+                _lib.check(self.lib.cfd_sample_begin_edit(self.handle, C.byref(a), C.byref(e), w_ptr, 1 if prune_zero_weight_chunks else 0,
+                                                          C.byref(g_eval), C.c_void_p(stream)))
+                self.chunks_evaluated = int(g_eval.value)
+            elif self.modality_weights is None:
                 _lib.check(self.lib.cfd_sample_begin(self.handle, C.byref(a), C.c_void_p(stream)))
                 self.chunks_evaluated = G
                 while skip_zero_weight_chunks and self.chunks_evaluated > 1 and w[self.chunks_evaluated - 1] == 0.0:
@@ -510,6 +575,8 @@ def _open_run(denoiser, scheduler, encoder_hidden_states, cond_masks, B, L, num_
     CFD_E_SHAPE from cfd_sample_begin -- a plain run, and the caller takes the maps with one forward per iteration (``last_step_attention``)."""
     if want_ring:
         n_it = len(scheduler.timestep_table(num_inference_steps)[1])
+        if kw.get("source_latents") is not None:      # an edit run executes the iterations from k0 on (its ring has that many slots)
+            n_it -= edit_first_iteration(kw.get("strength", 1.0), n_it)
         keys = sum(int(m.shape[1]) for m in encoder_hidden_states)
         budget = ATT_RING_MAX_BYTES
         dev = encoder_hidden_states[0].device
@@ -533,7 +600,7 @@ def _open_run(denoiser, scheduler, encoder_hidden_states, cond_masks, B, L, num_
 def sample(denoiser, scheduler, encoder_hidden_states, cond_masks=None, *, B, L=16, num_inference_steps=1000,
            guidance_scale=7.5, guidance_chunks=CFG_CHUNKS, eta=0.0, init_latents=None, step_noise=None, seed=0,
            first_utterance=0, preseq=None, dedup=True, skip_zero_weight_chunks=False, row_maps=None, return_attention=False, operands=None,
-           modality_weights=None, prune_zero_weight_chunks=True):
+           modality_weights=None, prune_zero_weight_chunks=True, source_latents=None, keep_mask=None, strength=1.0):
     """Run the whole loop; returns latents [B, L, 128] (batch-first); with ``return_attention=True`` also the last
     iteration's attention maps (``last_step_attention``), with ``return_attention="all"`` a dict {timestep: maps} over every
     iteration like the reference's: kept by the captured iteration itself (``SamplingRun(attention_ring=True)``) while the ring fits
@@ -543,14 +610,17 @@ def sample(denoiser, scheduler, encoder_hidden_states, cond_masks=None, *, B, L=
     (CENSUS_TAU) finds no concentrated attention against a long memory; when it trips -- read every CENSUS_CHUNK iterations -- a
     UserWarning, and the loop runs again from iteration 0 with ``operands=0``.  The result is then bit for bit the policy-0 run's (same
     seed, initial latents and step noise), otherwise the default policy's; the worst case costs up to one extra partial run.
-    ``modality_weights`` / ``prune_zero_weight_chunks``: per-modality guidance weights, as in ``SamplingRun``."""
+    ``modality_weights`` / ``prune_zero_weight_chunks``: per-modality guidance weights, as in ``SamplingRun``.
+    ``source_latents`` / ``keep_mask`` / ``strength``: an edit run (token-masked in-painting, img2img strength), as in ``SamplingRun``; the
+    attention dict then holds the executed iterations."""
     if check_operands(operands) == "auto":
         args = dict(locals())
         return _with_auto_operands(lambda ops: sample(**dict(args, operands=ops)), "auto")
     run = _open_run(denoiser, scheduler, encoder_hidden_states, cond_masks, B, L, num_inference_steps, return_attention in ("all", "auto"),
                     guidance_scale=guidance_scale, guidance_chunks=guidance_chunks, eta=eta, init_latents=init_latents, step_noise=step_noise,
                     seed=seed, first_utterance=first_utterance, preseq=preseq, dedup=dedup, skip_zero_weight_chunks=skip_zero_weight_chunks,
-                    row_maps=row_maps, operands=operands, modality_weights=modality_weights, prune_zero_weight_chunks=prune_zero_weight_chunks)
+                    row_maps=row_maps, operands=operands, modality_weights=modality_weights, prune_zero_weight_chunks=prune_zero_weight_chunks,
+                    source_latents=source_latents, keep_mask=keep_mask, strength=strength)
     try:
         if not return_attention:
             run.steps(run.N)
@@ -628,8 +698,9 @@ def sample_with_weg(denoiser, scheduler, encoder_hidden_states, cond_masks, focu
     max_refinement_steps (configs/assets.yaml:18-23).  ``carry_scale_range``: True reproduces ``_diffusion_reverse``, which
     re-assigns its ``scale_range`` table from the previous iteration's first two entries (convofusion.py:442-444: the step
     size stays ~scale_factor after iteration 0); False is the rollout, which takes a fresh 1.0 -> 0.5 table every
-    iteration (unbounded_synthesis.py:82-89).  See ``weg.scale_range_schedule``.  ``operands="auto"`` and ``modality_weights`` (in ``kw``):
-    as in ``sample``."""
+    iteration (unbounded_synthesis.py:82-89).  See ``weg.scale_range_schedule``.  ``operands="auto"``, ``modality_weights`` and the edit
+    arguments ``source_latents`` / ``keep_mask`` / ``strength`` (in ``kw``): as in ``sample``; an edit's masked overwrite goes in before the
+    WEG update (``run.inpaint``), and the WEG schedule is indexed by the full table's iteration."""
     if check_operands(kw.get("operands")) == "auto":
         args = dict(locals())
         rest = args.pop("kw")
@@ -655,6 +726,7 @@ def sample_with_weg(denoiser, scheduler, encoder_hidden_states, cond_masks, focu
             text_masks = {k: (v.chunk(G)[1].to(torch.uint8).contiguous() if v is not None else v) for k, v in (cond_masks or {}).items()}  # :448
         thresholds = dict(weg_parameters["thresholds"])
         timesteps = run.timesteps
+        k0, n_full = run.first_iteration, run.first_iteration + len(run.timesteps)   # (an edit run starts at iteration k0 of the table)
         carry = [weg_parameters["scale_range"][0], weg_parameters["scale_range"][1]] if carry_scale_range else None   # :395
         guided = 0                            # evaluations of the objective so far (their conditioning never changes inside the loop)
         ring = run.att_ring is not None       # every iteration's maps are kept by the captured iteration itself
@@ -664,17 +736,17 @@ def sample_with_weg(denoiser, scheduler, encoder_hidden_states, cond_masks, focu
         def maps(t):
             return last_step_attention(run, denoiser, t, encoder_hidden_states, cond_masks, G, kw.get("row_maps"))
 
-        for i, t in enumerate(timesteps):
-            last = i == len(timesteps) - 1
+        for i, t in enumerate(timesteps, start=k0):
+            last = i == n_full - 1
             # past max_iter_to_alter the reference still evaluates the objective but only acts on it at a threshold step
             if i >= weg_parameters["max_iter_to_alter"] and i not in thresholds:
                 if not any(k > i for k in thresholds) and not every:
                     break
                 if carry is not None:   # the skipped iteration still re-assigns the table (convofusion.py:442-444)
-                    weg.scale_range_schedule(weg_parameters, len(timesteps), i, carry)
+                    weg.scale_range_schedule(weg_parameters, n_full, i, carry)
             else:
-                run.inpaint()   # rollout: the re-noised previous window goes in before the WEG update (unbounded_synthesis.py:70-76)
-                lat, _ = weg.weg_update(denoiser, run.read(), i, t, text_states, text_masks, focus_indices, weg_parameters, len(timesteps),
+                run.inpaint()   # rollout / edit: the re-noised tokens go in before the WEG update (unbounded_synthesis.py:70-76)
+                lat, _ = weg.weg_update(denoiser, run.read(), i, t, text_states, text_masks, focus_indices, weg_parameters, n_full,
                                         scale_carry=carry, same_memories=guided > 0)
                 guided += 1
                 run.write(lat)

@@ -27,6 +27,10 @@ import torch.nn.functional as F
 from . import _lib
 from .conditioning import ACT_GELU, ACT_NONE, _engine_handle, linear_act
 
+# The body part of stack s of the latent's first axis: encode's kernel runs the body stack as stack 0 and the hands stack as stack 1
+# (csrc/vae_enc.hpp: blockIdx.y, the packed weights' body block first, ``_encoder_sources``), decode reads z[0] with the body decoder.
+LATENT_PARTS = ("body", "hands")
+
 
 def _ptr(t):
     return C.c_void_p(t.data_ptr())

@@ -188,6 +188,32 @@ int cfd_sample_begin(cfd_handle h, const cfd_sample_args* args, void* stream);
  * run has att_ring (its maps come from it).  *chunks_evaluated (may be NULL) receives G_eval. */
 int cfd_sample_begin_weighted(cfd_handle h, const cfd_sample_args* args, const float* weights, int prune, int* chunks_evaluated,
                               void* stream);
+/* Motion editing (token-masked in-painting, img2img strength).  The 16 loop tokens are 8 time chunks x {body, hands}: token 2c + p is
+ * 16-frame chunk c, part p (convofusion.py:1028), so one [B][L] mask selects time spans, body parts or both. */
+typedef struct {
+  const float* source;        /* dev [B][L][128] float32: the latents to edit (e.g. the VAE encoder's posterior mean in loop layout).
+                                 Copied at begin: the run does not read it afterwards.  NULL: CFD_E_ARG. */
+  const uint8_t* keep;        /* dev [B][L] uint8, each 0 or 1 (another value: CFD_E_ARG), or NULL (= all 0).  At the start of every
+                                 executed iteration i the tokens with keep = 1 are set to sa_i * source + sb_i * eps -- the reference
+                                 rollout's add_noise (unbounded_synthesis.py:70-76) with the mask in place of `l < preseq_len`; sa_i /
+                                 sb_i = sqrt(abar_t), sqrt(1 - abar_t) of iteration i's timestep; each product and the sum rounded to
+                                 float32 on its own.  eps = the run's initial N(0,1) draw (init_latents, or Philox stream 1), kept for the
+                                 whole run and never rewritten.  cfd_sample_inpaint does this overwrite ahead of the captured iteration. */
+  int first_iteration;        /* k0 in [0, iterations): the run executes iterations k0 .. iterations - 1 of the full timestep table
+                                 (img2img strength: k0 = iterations - min(int(iterations * strength), iterations)).  k0 > 0: every token
+                                 starts at sa_k0 * source + sb_k0 * eps; k0 = 0: the initial latents are eps unchanged.  Iteration i keeps
+                                 its full-table index everywhere: step coefficients, Philox step-noise index i, step_noise row i,
+                                 the weight table's row i.  DPM-Solver++: the first executed step is first order (no history yet) and
+                                 lower_order_final follows the full table's length, as diffusers 0.14.0 decides them.
+                                 cfd_sample_position and cfd_sample_steps count executed iterations (iterations - k0 in all); att_ring
+                                 slot j holds executed iteration k0 + j, so the ring needs iterations - k0 slots. */
+} cfd_edit_args;
+/* cfd_sample_begin / cfd_sample_begin_weighted (weights != NULL, with `prune` and `chunks_evaluated` as there; weights == NULL: the
+ * default combine with args->guidance_weight, `prune` ignored and *chunks_evaluated = the evaluated chunks) for an edit run.  CFD_E_ARG:
+ * e == NULL, e->source == NULL, e->first_iteration outside [0, iterations), a keep value other than 0 / 1, args->preseq together with
+ * an edit.  With first_iteration = 0 and keep all 0 / NULL the run computes what cfd_sample_begin(_weighted) computes, bit for bit. */
+int cfd_sample_begin_edit(cfd_handle h, const cfd_sample_args* args, const cfd_edit_args* e, const float* weights, int prune,
+                          int* chunks_evaluated, void* stream);
 /* Replays the captured iteration `n` more times (asynchronously on the run's stream). */
 int cfd_sample_steps(cfd_handle h, int n);
 /* Number of iterations executed so far in the open run. */

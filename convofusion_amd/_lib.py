@@ -24,7 +24,7 @@ SYMBOLS = [
     "cfd_layer_norm", "cfd_mha", "cfd_add", "cfd_zero_rows", "cfd_gemm_f32", "cfd_softmax", "cfd_softmax_bwd",
     "cfd_layer_norm_bwd", "cfd_ew", "cfd_weg_focus", "cfd_sample_write", "cfd_sample_inpaint", "cfd_weg_eval", "cfd_dyadic_steps",
     "cfd_sample_census", "cfd_dpmsolver_step", "cfd_test_step_coefficients", "cfd_test_gemm_epi",
-    "cfd_vae_encode", "cfd_sample_begin_weighted", "cfd_sample_begin_edit",
+    "cfd_vae_encode", "cfd_sample_begin_weighted", "cfd_sample_begin_edit", "cfd_sample_begin_invert", "cfd_sample_begin_anchored",
 ]
 
 
@@ -72,6 +72,11 @@ CENSUS_MAX_LAYERS = 16
 class EditArgs(C.Structure):
     """cfd_edit_args: the source latents (dev [B][L][128]), the keep mask (dev uint8 [B][L] or NULL) and the first iteration k0."""
     _fields_ = [("source", C.c_void_p), ("keep", C.c_void_p), ("first_iteration", C.c_int)]
+
+
+class AnchorArgs(C.Structure):
+    """cfd_anchor_args: an inversion trajectory (dev [steps + 1][B][L][128]), its steps / B / L, and the keep mask (dev uint8 [B][L] or NULL)."""
+    _fields_ = [("trajectory", C.c_void_p), ("steps", C.c_int), ("B", C.c_int), ("L", C.c_int), ("keep", C.c_void_p)]
 
 
 class Census(C.Structure):
@@ -164,6 +169,9 @@ def load():
     lib.cfd_sample_begin_weighted.argtypes = [C.c_void_p, C.POINTER(SampleArgs), C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p]
     lib.cfd_sample_begin_edit.argtypes = [C.c_void_p, C.POINTER(SampleArgs), C.POINTER(EditArgs), C.c_void_p, C.c_int, C.POINTER(C.c_int),
                                           C.c_void_p]
+    lib.cfd_sample_begin_invert.argtypes = [C.c_void_p, C.POINTER(SampleArgs), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p]
+    lib.cfd_sample_begin_anchored.argtypes = [C.c_void_p, C.POINTER(SampleArgs), C.POINTER(AnchorArgs), C.c_void_p, C.c_int,
+                                              C.POINTER(C.c_int), C.c_void_p]
     lib.cfd_sample_steps.argtypes = [C.c_void_p, C.c_int]
     lib.cfd_sample_position.argtypes = [C.c_void_p]
     lib.cfd_sample_read.argtypes = [C.c_void_p, C.c_void_p, C.c_int]

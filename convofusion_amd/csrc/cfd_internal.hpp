@@ -288,6 +288,13 @@ struct cfd_handle_s {
   int run_k0 = 0;
   bool run_edit = false;
   DBuf esrc, enoise, ekeep;
+  // DDIM inversion run (scheduler kind 3) with a trajectory (cfd_sample_begin_invert): the caller's ring [iterations + 1][B][L][128]; the
+  // trajectory instance of cfg_step_kernel stores the latents after iteration i into slot i + 1.  Anchored run (cfd_sample_begin_anchored):
+  // the anchored instances of begin_step_kernel / inpaint_now_kernel set the tokens of ekeep to anchor_ring[anchor_n - i].
+  float* run_traj = nullptr;
+  bool run_anchor = false;
+  const float* anchor_ring = nullptr;
+  int anchor_n = 0;
   int run_pos = 0;
 };
 typedef cfd_handle_s Ctx;

@@ -36,6 +36,21 @@ static void ddim_coef(const float* ac, int T, int n_inf, int t, float eta, int s
   o->order = o->r0inv = 0.f;
 }
 
+// DDIM inversion (prompt-to-prompt's next_step, scheduler kind 3): the step at t moves from t_cur = t - T // n_inf to t.  Kind 1's row
+// shape: sa / sb from a_cur (x0 = (x - sb eps) / sa), c0 / cx from a_nxt (x = c0 x0 + cx eps); deterministic (no eta, no noise).
+static void ddim_inverse_coef(const float* ac, int T, int n_inf, int t, int set_alpha_to_one, StepCoef* o) {
+  const int t_cur = t - T / n_inf;
+  const float a_cur = t_cur >= 0 ? ac[t_cur] : (set_alpha_to_one ? 1.0f : ac[0]);
+  const float a_nxt = ac[t];
+  o->sb = sqrtf(1.0f - a_cur);
+  o->sa = sqrtf(a_cur);
+  o->c0 = sqrtf(a_nxt);
+  o->cx = sqrtf(1.0f - a_nxt);
+  o->sigma = 0.f;
+  o->use_noise = 0.f;
+  o->order = o->r0inv = 0.f;
+}
+
 // diffusers 0.14.0 DPMSolverMultistepScheduler (dpmsolver++, solver_order 2, midpoint, lower_order_final), float32 as its torch tables:
 // alpha_t = sqrt(abar), sigma_t = sqrt(1 - abar), lambda_t = log(alpha_t) - log(sigma_t).  Step at t towards prev_t; t_prev_model = the
 // timestep of the previous step's model output (its x0 is the history m1), or -1 for a first-order step.
@@ -62,7 +77,8 @@ static void dpmpp_coef(const float* ac, int t, int prev_t, int t_prev_model, Ste
 
 // The per-iteration coefficient rows of a loop over the timestep table ts[0..N) (what cfd_sample_begin uploads).  Kind 2 needs the table
 // strictly decreasing in [1, T): the first executed iteration k0 is first order (diffusers' lower_order_nums is 0 there: no history), the
-// last one too when N < 15 (lower_order_final, from the full table's length), all others second order.
+// last one too when N < 15 (lower_order_final, from the full table's length), all others second order.  Kind 3 (DDIM inversion) needs the
+// table strictly increasing.
 static int step_coefficients(int kind, const float* ac, int T, int n_inf, const int32_t* ts, int N, float eta, int set_alpha_to_one,
                              StepCoef* coef, int k0 = 0) {
   for (int i = 0; i < N; ++i) {
@@ -71,7 +87,11 @@ static int step_coefficients(int kind, const float* ac, int T, int n_inf, const 
     memset(&coef[i], 0, sizeof(StepCoef));
     if (kind == 0) ddpm_coef(ac, T, n_inf, t, &coef[i]);
     else if (kind == 1) ddim_coef(ac, T, n_inf, t, eta, set_alpha_to_one, &coef[i]);
-    else {
+    else if (kind == 3) {
+      if (i > 0 && t <= ts[i - 1])
+        return fail(CFD_E_ARG, "DDIM inversion: the timestep table must increase strictly (entry %d is %d after %d)", i, t, ts[i - 1]);
+      ddim_inverse_coef(ac, T, n_inf, t, set_alpha_to_one, &coef[i]);
+    } else {
       if (t < 1 || (i > 0 && t >= ts[i - 1]))
         return fail(CFD_E_ARG, "DPM-Solver++: the timestep table must decrease strictly and stay in [1, %d) (entry %d is %d)", T, i, t);
       const bool first = i <= k0 || (i == N - 1 && N < 15);
@@ -84,6 +104,9 @@ static int step_coefficients(int kind, const float* ac, int T, int n_inf, const 
 static void (*const cfg_step_kernel_weighted)(const CfgStepArgsW) = cfg_step_kernel<0, true>;   // (one macro argument for LAUNCH)
 
 static void (*const begin_step_kernel_edit)(const BeginArgsE) = begin_step_kernel<0, true>;   // (one macro argument for LAUNCH)
+static void (*const begin_step_kernel_anchor)(const BeginArgsA) = begin_step_kernel<0, false, true>;
+static void (*const cfg_step_kernel_traj)(const CfgStepArgsT<CfgStepArgs>) = cfg_step_kernel<0, false, true>;
+static void (*const cfg_step_kernel_weighted_traj)(const CfgStepArgsT<CfgStepArgsW>) = cfg_step_kernel<0, true, true>;
 
 static BeginArgsE edit_begin_args(Ctx* c) {
   const cfd_sample_args& s = c->sargs;
@@ -96,11 +119,25 @@ static BeginArgsE edit_begin_args(Ctx* c) {
   return be;
 }
 
+static BeginArgsA anchor_begin_args(Ctx* c) {
+  const cfd_sample_args& s = c->sargs;
+  BeginArgsA ba;
+  static_cast<BeginArgs&>(ba) = BeginArgs{c->latents.as<float>(), c->w->sample_sp.as<char>(), s.B, s.L, s.G, nullptr, nullptr, 0,
+                                          c->coef.as<StepCoef>(), c->w->d_step.as<int>()};
+  ba.keep = c->ekeep.as<uint8_t>();
+  ba.ring = c->anchor_ring;
+  ba.slot = (long long)s.B * s.L * CFD_LAT;
+  ba.n = c->anchor_n;
+  return ba;
+}
+
 static int enqueue_loop_iteration(Ctx* c, hipStream_t st) {
   const cfd_sample_args& s = c->sargs;
   const long long n8 = (long long)s.B * s.L * (CFD_LAT / 8);
   if (c->run_edit) {
     LAUNCH(CFD_PROF_OTHER, begin_step_kernel_edit, dim3((unsigned)((n8 + 255) / 256)), dim3(256), st, edit_begin_args(c));
+  } else if (c->run_anchor) {
+    LAUNCH(CFD_PROF_OTHER, begin_step_kernel_anchor, dim3((unsigned)((n8 + 255) / 256)), dim3(256), st, anchor_begin_args(c));
   } else {
     BeginArgs ba{c->latents.as<float>(), c->w->sample_sp.as<char>(), s.B, s.L, s.G, s.preseq, c->inoise.as<float>(), s.preseq_len,
                  c->coef.as<StepCoef>(), c->w->d_step.as<int>()};
@@ -121,7 +158,21 @@ static int enqueue_loop_iteration(Ctx* c, hipStream_t st) {
     cw.G = 7;
     for (int k = 0; k < 8; ++k) cw.pos[k] = c->wpos[k];
     cw.wtab = c->wtab.as<float>();
+    if (c->run_traj) {
+      CfgStepArgsT<CfgStepArgsW> ct;
+      static_cast<CfgStepArgsW&>(ct) = cw;
+      ct.traj = c->run_traj;
+      LAUNCH(CFD_PROF_OTHER, cfg_step_kernel_weighted_traj, dim3((unsigned)std::min<long long>((n4 + 255) / 256, 256)), dim3(256), st, ct);
+      return CFD_OK;
+    }
     LAUNCH(CFD_PROF_OTHER, cfg_step_kernel_weighted, dim3((unsigned)std::min<long long>((n4 + 255) / 256, 256)), dim3(256), st, cw);
+    return CFD_OK;
+  }
+  if (c->run_traj) {   // (an inversion run recording its trajectory: the step also stores into slot *d_step + 1)
+    CfgStepArgsT<CfgStepArgs> ct;
+    static_cast<CfgStepArgs&>(ct) = ca;
+    ct.traj = c->run_traj;
+    LAUNCH(CFD_PROF_OTHER, cfg_step_kernel_traj, dim3((unsigned)std::min<long long>((n4 + 255) / 256, 256)), dim3(256), st, ct);
     return CFD_OK;
   }
   LAUNCH(CFD_PROF_OTHER, cfg_step_kernel<>, dim3((unsigned)std::min<long long>((n4 + 255) / 256, 256)), dim3(256), st, ca);
@@ -172,7 +223,7 @@ static int weighted_chunks(Ctx* c, const float* wtab, int prune, int N, bool kee
 }
 
 static int sample_begin(Ctx* c, const cfd_sample_args* args, void* stream, const float* wtab, int prune, int* chunks_evaluated,
-                        const cfd_edit_args* edit = nullptr);
+                        const cfd_edit_args* edit = nullptr, float* traj = nullptr, const cfd_anchor_args* anchor = nullptr);
 
 extern "C" int cfd_sample_begin(cfd_handle c, const cfd_sample_args* args, void* stream) {
   return sample_begin(c, args, stream, nullptr, 0, nullptr);
@@ -189,6 +240,36 @@ extern "C" int cfd_sample_begin_edit(cfd_handle c, const cfd_sample_args* args, 
   return r;
 }
 
+extern "C" int cfd_sample_begin_invert(cfd_handle c, const cfd_sample_args* args, float* trajectory, const float* weights, int prune,
+                                       int* chunks_evaluated, void* stream) {
+  if (!c || !args) return fail(CFD_E_ARG, "null argument");
+  if (!trajectory) return fail(CFD_E_ARG, "cfd_sample_begin_invert: the trajectory is NULL");
+  if (args->scheduler != 3) return fail(CFD_E_ARG, "cfd_sample_begin_invert: scheduler must be 3 (DDIM inversion), not %d", args->scheduler);
+  if (weights && args->G != 7) return fail(CFD_E_ARG, "cfd_sample_begin_invert: a weight table needs the 7-chunk guidance batch (G = %d)", args->G);
+  const int r = sample_begin(c, args, stream, weights, weights ? prune : 0, weights ? chunks_evaluated : nullptr, nullptr, trajectory);
+  if (r == CFD_OK && !weights && chunks_evaluated) *chunks_evaluated = c->sargs.G;
+  return r;
+}
+
+extern "C" int cfd_sample_begin_anchored(cfd_handle c, const cfd_sample_args* args, const cfd_anchor_args* an, const float* weights,
+                                         int prune, int* chunks_evaluated, void* stream) {
+  if (!c || !args || !an) return fail(CFD_E_ARG, "null argument");
+  if (!an->trajectory) return fail(CFD_E_ARG, "cfd_sample_begin_anchored: the trajectory is NULL");
+  if (args->scheduler != 1) return fail(CFD_E_ARG, "cfd_sample_begin_anchored: an anchored run is a DDIM run (scheduler 1, not %d)", args->scheduler);
+  if (args->eta != 0.f || args->clip_sample)
+    return fail(CFD_E_ARG, "cfd_sample_begin_anchored: the DDIM run must be deterministic and unclipped (eta = %g, clip_sample = %d)",
+                (double)args->eta, args->clip_sample);
+  if (args->preseq) return fail(CFD_E_ARG, "cfd_sample_begin_anchored: an anchored run has no preseq");
+  const int n_iter = args->timesteps ? args->num_timesteps : args->num_inference_steps;
+  if (an->steps != n_iter || an->B != args->B || an->L != args->L)
+    return fail(CFD_E_ARG, "cfd_sample_begin_anchored: the trajectory is [%d + 1][%d][%d][128], this run has %d iterations of [%d][%d][128]",
+                an->steps, an->B, an->L, n_iter, args->B, args->L);
+  if (weights && args->G != 7) return fail(CFD_E_ARG, "cfd_sample_begin_anchored: a weight table needs the 7-chunk guidance batch (G = %d)", args->G);
+  const int r = sample_begin(c, args, stream, weights, weights ? prune : 0, weights ? chunks_evaluated : nullptr, nullptr, nullptr, an);
+  if (r == CFD_OK && !weights && chunks_evaluated) *chunks_evaluated = c->sargs.G;
+  return r;
+}
+
 extern "C" int cfd_sample_begin_weighted(cfd_handle c, const cfd_sample_args* args, const float* weights, int prune, int* chunks_evaluated,
                                          void* stream) {
   if (!c || !args) return fail(CFD_E_ARG, "null argument");
@@ -198,7 +279,7 @@ extern "C" int cfd_sample_begin_weighted(cfd_handle c, const cfd_sample_args* ar
 }
 
 static int sample_begin(Ctx* c, const cfd_sample_args* args, void* stream, const float* wtab, int prune, int* chunks_evaluated,
-                        const cfd_edit_args* edit) {
+                        const cfd_edit_args* edit, float* traj, const cfd_anchor_args* anchor) {
   if (!c || !args) return fail(CFD_E_ARG, "null argument");
   if (c->run_open) return fail(CFD_E_STATE, "a sampling run is already open");
   HIPCHK(hipSetDevice(c->cfg.device));
@@ -216,9 +297,22 @@ static int sample_begin(Ctx* c, const cfd_sample_args* args, void* stream, const
   c->run_weighted = false;
   c->run_edit = false;
   c->run_k0 = 0;
+  c->run_traj = nullptr;
+  c->run_anchor = false;
+  c->anchor_ring = nullptr;
+  c->anchor_n = 0;
   const cfd_sample_args& s = *args;
   if (s.B < 1 || (s.G != 1 && s.G != 7 && (s.G < 1 || s.G > 8))) return fail(CFD_E_ARG, "bad B / G");
-  if (s.scheduler < 0 || s.scheduler > 2) return fail(CFD_E_ARG, "scheduler must be 0 (DDPM), 1 (DDIM) or 2 (DPM-Solver++ (2M))");
+  if (s.scheduler < 0 || s.scheduler > 3)
+    return fail(CFD_E_ARG, "scheduler must be 0 (DDPM), 1 (DDIM), 2 (DPM-Solver++ (2M)) or 3 (DDIM inversion)");
+  if (s.scheduler == 3) {
+    if (!s.timesteps) return fail(CFD_E_ARG, "DDIM inversion: pass the ascending timestep table in cfd_sample_args.timesteps");
+    if (s.eta != 0.f) return fail(CFD_E_ARG, "DDIM inversion is deterministic: eta must be 0 (got %g)", (double)s.eta);
+    if (s.clip_sample) return fail(CFD_E_ARG, "DDIM inversion: clip_sample must be 0 (a clipped x0 is not invertible)");
+    if (s.preseq) return fail(CFD_E_ARG, "DDIM inversion takes no preseq (the rollout's prefix in-painting)");
+    if (s.dynamic_memory_mask) return fail(CFD_E_ARG, "DDIM inversion takes no dynamic memories (dynamic_memory_mask = %d)", s.dynamic_memory_mask);
+    if (edit) return fail(CFD_E_ARG, "DDIM inversion does not go together with an edit (cfd_sample_begin_edit)");
+  }
   if (s.scheduler == 2 && !s.timesteps)
     return fail(CFD_E_ARG, "DPM-Solver++: pass the scheduler's timestep table in cfd_sample_args.timesteps (the library does not build it)");
   if (s.scheduler == 2 && s.clip_sample) return fail(CFD_E_ARG, "DPM-Solver++ has no clip_sample (clip_sample must be 0)");
@@ -233,14 +327,14 @@ static int sample_begin(Ctx* c, const cfd_sample_args* args, void* stream, const
   const int n_iter = s.timesteps ? s.num_timesteps : s.num_inference_steps;
   const int k0 = edit ? edit->first_iteration : 0;
   std::vector<uint8_t> hkeep;
-  if (edit) {
-    if (k0 < 0 || k0 >= n_iter) return fail(CFD_E_ARG, "cfd_sample_begin_edit: first_iteration = %d is not in [0, %d)", k0, n_iter);
-    if (edit->keep) {
-      hkeep.resize((size_t)s.B * s.L);
-      HIPCHK(hipMemcpy(hkeep.data(), edit->keep, hkeep.size(), hipMemcpyDeviceToHost));
-      for (size_t e = 0; e < hkeep.size(); ++e)
-        if (hkeep[e] > 1) return fail(CFD_E_ARG, "cfd_sample_begin_edit: keep[%zu][%zu] = %d is not 0 or 1", e / s.L, e % s.L, (int)hkeep[e]);
-    }
+  if (edit && (k0 < 0 || k0 >= n_iter)) return fail(CFD_E_ARG, "cfd_sample_begin_edit: first_iteration = %d is not in [0, %d)", k0, n_iter);
+  const uint8_t* keep_in = edit ? edit->keep : anchor ? anchor->keep : nullptr;
+  if (keep_in) {
+    const char* who = edit ? "cfd_sample_begin_edit" : "cfd_sample_begin_anchored";
+    hkeep.resize((size_t)s.B * s.L);
+    HIPCHK(hipMemcpy(hkeep.data(), keep_in, hkeep.size(), hipMemcpyDeviceToHost));
+    for (size_t e = 0; e < hkeep.size(); ++e)
+      if (hkeep[e] > 1) return fail(CFD_E_ARG, "%s: keep[%zu][%zu] = %d is not 0 or 1", who, e / s.L, e % s.L, (int)hkeep[e]);
   }
   hipStream_t st = (hipStream_t)stream;
   c->sargs = s;
@@ -395,6 +489,20 @@ static int sample_begin(Ctx* c, const cfd_sample_args* args, void* stream, const
     c->run_edit = true;
     c->run_k0 = k0;
     c->run_iters = N - k0;
+  }
+  if (traj) {   // slot 0 of the trajectory: the initial latents (the source of the inversion)
+    HIPCHK(hipMemcpyAsync(traj, c->latents.p, lat_bytes, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    c->run_traj = traj;
+  }
+  if (anchor) {   // the keep mask; the ring is the caller's and is read in place
+    CHK(c->ekeep.ensure((size_t)s.B * s.L));
+    if (anchor->keep) HIPCHK(hipMemcpyAsync(c->ekeep.p, hkeep.data(), hkeep.size(), hipMemcpyHostToDevice, st));
+    else HIPCHK(hipMemsetAsync(c->ekeep.p, 0, (size_t)s.B * s.L, st));
+    HIPCHK(hipStreamSynchronize(st));   // (hkeep goes out of scope)
+    c->run_anchor = true;
+    c->anchor_ring = anchor->trajectory;
+    c->anchor_n = anchor->steps;
   }
   // DPM-Solver++: the x0 history of the run, zeroed.  The first executed iteration is first order and never reads it, so the eager warm-up
   // iteration below, which runs as that iteration and writes its x0 here, needs no save / restore: the first replay overwrites that before
@@ -568,12 +676,16 @@ extern "C" int cfd_scheduler_step(cfd_handle c, int scheduler, const float* ac, 
                                   int set_alpha_to_one, const float* model_output, const float* noise, float* sample_inout,
                                   size_t numel, float* pred_original_sample, void* stream) {
   if (!c || !ac || !model_output || !sample_inout || t < 0 || t >= T || n_inf < 1) return fail(CFD_E_ARG, "bad argument");
-  if (scheduler != 0 && scheduler != 1)
-    return fail(CFD_E_ARG, "cfd_scheduler_step: scheduler must be 0 (DDPM) or 1 (DDIM); DPM-Solver++ steps go through cfd_dpmsolver_step");
+  if (scheduler != 0 && scheduler != 1 && scheduler != 3)
+    return fail(CFD_E_ARG, "cfd_scheduler_step: scheduler must be 0 (DDPM), 1 (DDIM) or 3 (DDIM inversion); DPM-Solver++ steps go through "
+                           "cfd_dpmsolver_step");
+  if (scheduler == 3 && (eta != 0.f || clip))
+    return fail(CFD_E_ARG, "cfd_scheduler_step: DDIM inversion needs eta = 0 and clip_sample = 0 (got %g, %d)", (double)eta, clip);
   HIPCHK(hipSetDevice(c->cfg.device));
   StepCoef k;
   memset(&k, 0, sizeof(k));
   if (scheduler == 0) ddpm_coef(ac, T, n_inf, t, &k);
+  else if (scheduler == 3) ddim_inverse_coef(ac, T, n_inf, t, set_alpha_to_one, &k);
   else ddim_coef(ac, T, n_inf, t, eta, set_alpha_to_one, &k);
   if (k.use_noise != 0.f && !noise) return fail(CFD_E_ARG, "this step adds noise: pass the N(0,1) draw");
   hipLaunchKernelGGL(sched_step_kernel<>, dim3((unsigned)((numel + 255) / 256)), dim3(256), 0, (hipStream_t)stream, model_output, noise,
@@ -601,7 +713,7 @@ extern "C" int cfd_dpmsolver_step(cfd_handle c, const float* ac, int T, int t, i
 // ---- developer hook: the per-iteration coefficient table a sampling run uploads, on the host (no handle, no device) ----------------
 extern "C" int cfd_test_step_coefficients(int kind, const float* ac, int T, int n_inf, const int32_t* timesteps, int N, float eta,
                                           int set_alpha_to_one, float* out) {
-  if (!ac || !timesteps || !out || kind < 0 || kind > 2 || T < 1 || N < 1 || n_inf < 1) return fail(CFD_E_ARG, "bad argument");
+  if (!ac || !timesteps || !out || kind < 0 || kind > 3 || T < 1 || N < 1 || n_inf < 1) return fail(CFD_E_ARG, "bad argument");
   static_assert(sizeof(StepCoef) == 8 * sizeof(float), "StepCoef is one row of 8 floats");
   std::vector<StepCoef> coef(N);
   CHK(step_coefficients(kind, ac, T, n_inf, timesteps, N, eta, set_alpha_to_one, coef.data()));
@@ -635,6 +747,7 @@ extern "C" int cfd_philox_normal(cfd_handle c, float* out, int B, int per_utt, u
 }
 
 static void (*const inpaint_now_kernel_edit)(const BeginArgsE, int*) = inpaint_now_kernel<0, true>;
+static void (*const inpaint_now_kernel_anchor)(const BeginArgsA, int*) = inpaint_now_kernel<0, false, true>;
 
 extern "C" int cfd_sample_inpaint(cfd_handle c) {
   if (!c) return fail(CFD_E_ARG, "null handle");
@@ -645,6 +758,15 @@ extern "C" int cfd_sample_inpaint(cfd_handle c) {
     HIPCHK(hipSetDevice(c->cfg.device));
     const long long n8 = (long long)s.B * s.L * (CFD_LAT / 8);
     hipLaunchKernelGGL(inpaint_now_kernel_edit, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, c->run_stream, edit_begin_args(c),
+                       c->w->d_step.as<int>());
+    HIPCHK(hipGetLastError());
+    return CFD_OK;
+  }
+  if (c->run_anchor) {   // the anchored instance: the kept tokens of this iteration from the trajectory
+    if (c->run_pos >= c->run_iters) return fail(CFD_E_STATE, "cfd_sample_inpaint: the run has no iteration left");
+    HIPCHK(hipSetDevice(c->cfg.device));
+    const long long n8 = (long long)s.B * s.L * (CFD_LAT / 8);
+    hipLaunchKernelGGL(inpaint_now_kernel_anchor, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, c->run_stream, anchor_begin_args(c),
                        c->w->d_step.as<int>());
     HIPCHK(hipGetLastError());
     return CFD_OK;
@@ -662,6 +784,7 @@ extern "C" int cfd_sample_inpaint(cfd_handle c) {
 extern "C" int cfd_sample_write(cfd_handle c, const float* latents) {
   if (!c || !latents) return fail(CFD_E_ARG, "null argument");
   if (!c->run_open) return fail(CFD_E_STATE, "no sampling run open");
+  if (c->sargs.scheduler == 3) return fail(CFD_E_ARG, "cfd_sample_write: a DDIM inversion run takes no WEG update (its latents are its own)");
   HIPCHK(hipSetDevice(c->cfg.device));
   const size_t lat_bytes = (size_t)c->sargs.B * c->sargs.L * CFD_LAT * 4;
   HIPCHK(hipMemcpyAsync(c->latents.p, latents, lat_bytes, hipMemcpyDeviceToDevice, c->run_stream));

@@ -596,8 +596,17 @@ struct BeginArgsE : BeginArgs {
   const float* src;      // [B][L][128] source latents
   const float* eps;      // [B][L][128] the run's initial noise
 };
-template <bool EDIT>
-using BeginArgsOf = typename std::conditional<EDIT, BeginArgsE, BeginArgs>::type;
+// The anchored instance's arguments (cfd_sample_begin_anchored): every token (b, l) with keep[b * L + l] = 1 is set at the start of
+// iteration i to ring[n - i][b][l] -- the recorded inversion trajectory ([n + 1][B][L][128], slot j = the latents after j inversion
+// iterations) at the level iteration i starts from.  preseq / inoise / pl are unused.
+struct BeginArgsA : BeginArgs {
+  const uint8_t* keep;   // [B][L] 0 / 1
+  const float* ring;     // [n + 1][B][L][128]
+  long long slot;        // B * L * 128: floats per ring slot
+  int n;                 // iterations of the inversion (= of this run)
+};
+template <bool EDIT, bool ANCHOR = false>
+using BeginArgsOf = typename std::conditional<ANCHOR, BeginArgsA, typename std::conditional<EDIT, BeginArgsE, BeginArgs>::type>::type;
 
 // 8 consecutive elements of sa * src + sb * eps, each product and the sum rounded on its own
 __device__ __forceinline__ void edit_mix8(float sa, float sb, const float* src, const float* eps, float v[8]) {
@@ -613,8 +622,14 @@ __device__ __forceinline__ void store8(float* p, const float v[8]) {
   *reinterpret_cast<float4*>(p + 4) = make_float4(v[4], v[5], v[6], v[7]);
 }
 
-template <int CFD_KI = 0, bool EDIT = false>
-__global__ void begin_step_kernel(const BeginArgsOf<EDIT> a) {
+// 8 consecutive floats (vector loads)
+__device__ __forceinline__ void load8(const float* p, float v[8]) {
+  const float4 a0 = *reinterpret_cast<const float4*>(p), a1 = *reinterpret_cast<const float4*>(p + 4);
+  v[0] = a0.x; v[1] = a0.y; v[2] = a0.z; v[3] = a0.w; v[4] = a1.x; v[5] = a1.y; v[6] = a1.z; v[7] = a1.w;
+}
+
+template <int CFD_KI = 0, bool EDIT = false, bool ANCHOR = false>
+__global__ void begin_step_kernel(const BeginArgsOf<EDIT, ANCHOR> a) {
   const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;  // one thread = 8 elements
   const long long n8 = (long long)a.B * a.L * (CFD_LAT / 8);
   if (idx >= n8) return;
@@ -623,7 +638,15 @@ __global__ void begin_step_kernel(const BeginArgsOf<EDIT> a) {
   const int l = (int)(bl % a.L), b = (int)(bl / a.L);
   float* lp = a.latents + bl * CFD_LAT + c;
   float v[8];
-  if constexpr (EDIT) {
+  if constexpr (ANCHOR) {
+    if (a.keep[bl] && a.d_step[2] == 0) {   // d_step[2] != 0: cfd_sample_inpaint already did this iteration's overwrite
+      load8(a.ring + (long long)(a.n - *a.d_step) * a.slot + bl * CFD_LAT + c, v);
+      store8(lp, v);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] = lp[e];
+    }
+  } else if constexpr (EDIT) {
     if (a.keep[bl] && a.d_step[2] == 0) {   // d_step[2] != 0: cfd_sample_inpaint already did this iteration's overwrite
       const int i = *a.d_step;
       edit_mix8(a.coef[i].sa, a.coef[i].sb, a.src + bl * CFD_LAT + c, a.eps + bl * CFD_LAT + c, v);
@@ -675,11 +698,18 @@ struct CfgStepArgs {
 struct CfgStepArgsW : CfgStepArgs {
   const float* wtab;     // [iterations][B][8]
 };
-template <bool WTAB>
-using CfgStepArgsOf = typename std::conditional<WTAB, CfgStepArgsW, CfgStepArgs>::type;
+// The trajectory instances' arguments (cfd_sample_begin_invert): the stepped element is also stored into slot *d_step + 1 of the
+// caller's ring [iterations + 1][B][L][128] (slot 0 is the run's initial latents, written at begin), by the thread that steps it.
+template <class Args>
+struct CfgStepArgsT : Args {
+  float* traj;
+};
+template <bool WTAB, bool TRAJ = false>
+using CfgStepArgsOf = typename std::conditional<TRAJ, CfgStepArgsT<typename std::conditional<WTAB, CfgStepArgsW, CfgStepArgs>::type>,
+                                                typename std::conditional<WTAB, CfgStepArgsW, CfgStepArgs>::type>::type;
 
-template <int CFD_KI = 0, bool WTAB = false>
-__global__ void cfg_step_kernel(const CfgStepArgsOf<WTAB> a) {
+template <int CFD_KI = 0, bool WTAB = false, bool TRAJ = false>
+__global__ void cfg_step_kernel(const CfgStepArgsOf<WTAB, TRAJ> a) {
   const int per_utt = a.L * CFD_LAT;
   const long long n4 = (long long)a.B * per_utt / 4;
   const int i = *a.d_step;
@@ -742,6 +772,7 @@ __global__ void cfg_step_kernel(const CfgStepArgsOf<WTAB> a) {
   // (kind 2: this element's history is read above and written here by the same thread -- in place, race-free)
   if (a.kind == 2) *reinterpret_cast<float4*>(a.hist + e0) = make_float4(x0v[0], x0v[1], x0v[2], x0v[3]);
   *reinterpret_cast<float4*>(a.latents + e0) = make_float4(o[0], o[1], o[2], o[3]);
+  if constexpr (TRAJ) *reinterpret_cast<float4*>(a.traj + (long long)(i + 1) * chunk + e0) = make_float4(o[0], o[1], o[2], o[3]);
   }
   if (a.advance) {   // every thread of every workgroup has read the step index above before the last ticket is taken
     __syncthreads();
@@ -770,10 +801,21 @@ __global__ void edit_init_kernel(float* latents, const float* src, const float* 
 
 // The in-painting overwrite of begin_step_kernel alone, ahead of the captured iteration (cfd_sample_inpaint): the WEG
 // branch of the rollout alters the latents AFTER the overwrite and BEFORE the replication (unbounded_synthesis.py:70-143).
-template <int CFD_KI = 0, bool EDIT = false>
-__global__ void inpaint_now_kernel(const BeginArgsOf<EDIT> a, int* d_step) {
+template <int CFD_KI = 0, bool EDIT = false, bool ANCHOR = false>
+__global__ void inpaint_now_kernel(const BeginArgsOf<EDIT, ANCHOR> a, int* d_step) {
   const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if constexpr (EDIT) {   // one thread = 8 elements of one token, kept tokens only
+  if constexpr (ANCHOR) {   // one thread = 8 elements of one token, kept tokens only
+    const long long n8 = (long long)a.B * a.L * (CFD_LAT / 8);
+    if (idx == 0) d_step[2] = 1;
+    if (idx >= n8) return;
+    const long long bl = idx / (CFD_LAT / 8);
+    if (!a.keep[bl]) return;
+    const long long o = bl * CFD_LAT + (idx % (CFD_LAT / 8)) * 8;
+    float v[8];
+    load8(a.ring + (long long)(a.n - *a.d_step) * a.slot + o, v);
+    store8(a.latents + o, v);
+    return;
+  } else if constexpr (EDIT) {   // one thread = 8 elements of one token, kept tokens only
     const long long n8 = (long long)a.B * a.L * (CFD_LAT / 8);
     if (idx == 0) d_step[2] = 1;
     if (idx >= n8) return;

@@ -10,12 +10,17 @@ loop's latents into the VAE's [2, B, T, 128], convofusion.py:1028-1030), and fra
     variation of the whole gesture        no mask, strength 0.5
 
 ``edit_motion`` runs the whole edit: HIP ``encode`` of the source motion, the fused edit loop, HIP ``decode``.
+
+``reperform_motion`` re-conditions a recorded motion ("the same gesture, re-performed to new speech"): deterministic DDIM inversion of its
+latents under the source conditioning (``sampler.invert``), then a DDIM regeneration from the inverted noise under the target
+conditioning, with the kept tokens anchored to the inversion's trajectory.  Whether re-performed motions look right under a trained
+checkpoint is not measured here: the weights of the tests are seeded.
 """
 import inspect
 
 import torch
 
-from .sampler import check_operands, sample
+from .sampler import check_operands, invert, sample
 from .vae import LATENT_PARTS
 
 FRAMES_PER_CHUNK = 16   # vae.py:178
@@ -100,3 +105,43 @@ def edit_motion(model, feats, lengths, encoder_hidden_states, cond_masks=None, *
                  modality_weights=modality_weights, source_latents=source, keep_mask=keep_mask, strength=strength)
     out = model.vae.decode(loop_to_vae(lat), lengths)
     return out, lat
+
+
+def reperform_motion(model, feats, lengths, source_conditioning, target_conditioning, *, source_masks=None, target_masks=None,
+                     num_inference_steps=50, keep_mask=None, inversion_weights=None, modality_weights=None, operands=None):
+    """Re-perform motions under new conditioning.  ``model`` / ``feats`` / ``lengths``: as in ``edit_motion``; source_conditioning /
+    target_conditioning (+ their masks): the 7-chunk guidance batches of the recorded motion's conditioning and of the new one.
+      1. HIP encode of the source to its posterior mean (loop layout);
+      2. DDIM inversion under the source conditioning (``sampler.invert``, N = num_inference_steps): ``inversion_weights`` None inverts with
+         the conditional prediction alone (guidance_scale 1), otherwise with those weights at model.guidance_scale;
+      3. DDIM regeneration (a DDIMScheduler with the model scheduler's betas, set_alpha_to_one and steps_offset; eta 0, no clipping) from
+         the inverted latents under the target conditioning at model.guidance_scale with ``modality_weights`` (None: the model's installed
+         weights, else the reference's); the tokens of ``keep_mask`` [B, L] are anchored to the inversion's trajectory;
+      4. HIP decode.
+    Returns (features [B, nframes, 189], loop latents [B, L, 128], inverted latents [B, L, 128])."""
+    from .scheduler import DDIMInverseScheduler, DDIMScheduler
+    if not model.do_classifier_free_guidance:
+        raise NameError("guidance_bs_mulitplier: the reference loop requires classifier-free guidance")
+    latent, dist, _ = model.vae.encode(feats, lengths)
+    source = vae_to_loop(dist.mean.reshape(latent.shape))
+    B, L = int(source.shape[0]), int(source.shape[1])
+    G = model.clf_guidance_drops + 1
+    for name, cond in (("source_conditioning", source_conditioning), ("target_conditioning", target_conditioning)):
+        if cond[0].shape[0] != G * B:
+            raise ValueError(f"{name} has {cond[0].shape[0]} rows for {B} motions and {G} chunks")
+    sch = model.scheduler
+    kw = dict(num_train_timesteps=sch.config.num_train_timesteps, trained_betas=sch.betas.tolist(), clip_sample=False,
+              set_alpha_to_one=sch.config.get("set_alpha_to_one", True), steps_offset=sch.config.get("steps_offset", 0))
+    ops = check_operands(getattr(model, "_cfd_operands", None) if operands is None else operands)
+    anchored = keep_mask is not None
+    inv = invert(model.denoiser, DDIMInverseScheduler(**kw), source_conditioning, source_masks, source_latents=source,
+                 num_inference_steps=num_inference_steps, guidance_scale=1.0 if inversion_weights is None else model.guidance_scale,
+                 modality_weights=inversion_weights, return_trajectory=anchored, operands=ops)
+    inverted, traj = inv if anchored else (inv, None)
+    if modality_weights is None:
+        modality_weights = getattr(model, "_cfd_modality_weights", None)
+    lat = sample(model.denoiser, DDIMScheduler(**kw), target_conditioning, target_masks, B=B, L=L, num_inference_steps=num_inference_steps,
+                 guidance_scale=model.guidance_scale, guidance_chunks=G, eta=0.0, init_latents=inverted, skip_zero_weight_chunks=True,
+                 operands=ops, modality_weights=modality_weights, anchor_trajectory=traj, keep_mask=keep_mask)
+    out = model.vae.decode(loop_to_vae(lat), lengths)
+    return out, lat, inverted

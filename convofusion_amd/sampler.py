@@ -31,8 +31,8 @@ CFG_CHUNKS = 7
 # (the heavy-tailed stress weights: DESIGN.md section 2).  ``operands="auto"`` (opt-in) decides per run: the default policy with the
 # attention-concentration census on, and a restart with pairs from iteration 0 when the census trips (see CENSUS_TAU).
 # DPM-Solver++ (kind 2) is deterministic like DDIM -- no noise re-injected, its multistep history carries a perturbation forward -- and keeps
-# pairs as well.
-OPERAND_POLICY = {0: 15, 1: 0, 2: 0}
+# pairs as well, and so does DDIM inversion (kind 3, DDIMInverseScheduler), for the same reason.
+OPERAND_POLICY = {0: 15, 1: 0, 2: 0, 3: 0}
 
 # Attention-concentration census (cfd_sample_args.census_tau, ``SamplingRun.census``): the fused cross-attention kernel reports, per layer, the
 # largest probability of every query row against a long memory and how many rows exceed CENSUS_TAU.  The single-fp16 operands are safe where
@@ -156,6 +156,43 @@ def check_edit(source_latents, keep_mask, strength, B, L, N, preseq=None, device
             raise ValueError("keep_mask holds values other than 0 and 1")
         keep = keep_mask.detach().to(device=device, dtype=torch.uint8).contiguous()
     return src, keep, k0
+
+
+def check_inversion(scheduler, table, eta=0.0):
+    """The arguments of a DDIM inversion run (scheduler kind 3, ``DDIMInverseScheduler``): the timestep table strictly increasing in
+    [0, T), eta 0 and no clipping (the step is deterministic; a clipped x0 is not invertible).  Anything else raises ValueError."""
+    import numpy as np
+    T = int(scheduler.config.num_train_timesteps)
+    ts = np.asarray(table, dtype=np.int64).reshape(-1)
+    if ts.size < 1 or (ts.size > 1 and not bool((np.diff(ts) > 0).all())) or int(ts.min()) < 0 or int(ts.max()) >= T:
+        raise ValueError(f"DDIM inversion needs a strictly increasing timestep table in [0, {T}), not {ts.tolist()[:8]}...")
+    if float(eta) != 0.0:
+        raise ValueError(f"DDIM inversion is deterministic: eta must be 0, not {eta!r}")
+    if scheduler.config.get("clip_sample", False):
+        raise ValueError("DDIM inversion runs without clip_sample (a clipped x0 is not invertible)")
+
+
+def check_anchor(trajectory, keep_mask, B, L, N, device=None):
+    """The anchor of a re-conditioning run (``SamplingRun(anchor_trajectory=)``): (trajectory float32 [N + 1, B, L, 128] contiguous on
+    ``device``, keep mask uint8 [B, L] on ``device`` or None).  Refusals (ValueError): a trajectory other than a floating-point
+    [N + 1, B, L, 128] tensor (N = the run's iterations: the inversion must have as many), a keep mask other than a bool or integer [B, L]
+    tensor of 0 / 1."""
+    if not isinstance(trajectory, torch.Tensor) or not trajectory.is_floating_point():
+        raise ValueError("anchor_trajectory must be a floating-point tensor [N + 1, B, L, 128]")
+    if tuple(trajectory.shape) != (N + 1, B, L, 128):
+        raise ValueError(f"anchor_trajectory must be [N + 1, B, L, 128] = [{N + 1}, {B}, {L}, 128] (an inversion with the run's N = {N} "
+                         f"iterations, B and L), not {list(trajectory.shape)}")
+    keep = None
+    if keep_mask is not None:
+        if not isinstance(keep_mask, torch.Tensor) or keep_mask.is_floating_point() or keep_mask.is_complex():
+            raise ValueError("keep_mask must be a bool or integer (0 / 1) tensor [B, L]")
+        if tuple(keep_mask.shape) != (B, L):
+            raise ValueError(f"keep_mask must be [B, L] = [{B}, {L}], not {list(keep_mask.shape)}")
+        if keep_mask.dtype != torch.bool and bool(((keep_mask != 0) & (keep_mask != 1)).any()):
+            raise ValueError("keep_mask holds values other than 0 and 1")
+        keep = keep_mask.detach().to(device=device, dtype=torch.uint8).contiguous()
+    traj = trajectory.detach().to(device=device, dtype=torch.float32).contiguous()
+    return traj, keep
 
 
 class CensusTripped(Exception):
@@ -292,7 +329,8 @@ class SamplingRun:
                  guidance_scale=7.5, guidance_chunks=CFG_CHUNKS, eta=0.0, init_latents=None, step_noise=None,
                  seed=0, first_utterance=0, preseq=None, dedup=True, skip_zero_weight_chunks=False, row_maps=None,
                  dynamic_memories=(), side_engine=False, attention_ring=False, operands=None, census_tau=None, modality_weights=None,
-                 prune_zero_weight_chunks=True, source_latents=None, keep_mask=None, strength=1.0):
+                 prune_zero_weight_chunks=True, source_latents=None, keep_mask=None, strength=1.0, trajectory=False,
+                 anchor_trajectory=None):
         """attention_ring: keep the attention maps of the full-conditioning chunk of EVERY iteration (the reference's per-iteration dict,
         convofusion.py:517-523): the captured iteration stores them into ``self.att_ring`` -- five tensors [iterations, B, layers, L, S_j]
         -- with no extra forward and no host round trip (cfd_sample_args.att_ring: the row-tile kernels store them from their second
@@ -318,7 +356,15 @@ class SamplingRun:
         of every iteration i the tokens with keep_mask = 1 are set to sa_i * source + sb_i * eps (eps = the run's initial draw), the rollout's
         in-painting with a token mask; strength < 1 starts at iteration k0 = N - min(int(N * strength), N) of the scheduler's table from
         sa_k0 * source + sb_k0 * eps.  ``timesteps`` / ``N`` are then the executed iterations, ``first_iteration`` is k0; step_noise and
-        modality_weights [N, ...] still cover the full table (iteration i keeps its full-table index)."""
+        modality_weights [N, ...] still cover the full table (iteration i keeps its full-table index).
+        trajectory (DDIMInverseScheduler only): record the inversion's trajectory (cfd_sample_begin_invert) into ``self.trajectory``
+        [N + 1, B, L, 128]: slot 0 the initial latents (the source), slot j the latents after j iterations, stored by the captured
+        iteration's scheduler step.  A DDIM inversion run (scheduler kind 3, ``check_inversion``) refuses preseq, an edit, dynamic memories
+        and WEG.
+        anchor_trajectory / keep_mask (DDIMScheduler, eta 0, no clipping): a re-conditioning run over a recorded inversion trajectory
+        (cfd_sample_begin_anchored, ``check_anchor``): at the start of iteration i the tokens with keep_mask = 1 are set to
+        anchor_trajectory[N - i], the inverted latents at the level the iteration starts from.  The trajectory is read in place: the run
+        keeps a reference to it."""
         if not isinstance(denoiser, Denoiser):
             raise TypeError("denoiser must be a convofusion_amd.denoiser.Denoiser")
         dev = encoder_hidden_states[0].device
@@ -327,11 +373,28 @@ class SamplingRun:
         self.lib = _lib.load()
         self.device = dev
         if getattr(scheduler, "KIND", None) is None:
-            raise TypeError("scheduler must be a convofusion_amd.scheduler DDPMScheduler / DDIMScheduler / DPMSolverMultistepScheduler")
+            raise TypeError("scheduler must be a convofusion_amd.scheduler DDPMScheduler / DDIMScheduler / DPMSolverMultistepScheduler / "
+                            "DDIMInverseScheduler")
         # the loop runs over scheduler.timesteps: DDPM clamps the count to the training schedule, and for a count that does not
         # divide it the (opt-in, unpinned) 0.14.0 table has more entries than the count (scheduler.timestep_table)
         num_inference_steps, table = scheduler.timestep_table(num_inference_steps)
         n_full = len(table)
+        inverse = scheduler.KIND == 3
+        if inverse:
+            check_inversion(scheduler, table, eta)
+            if preseq is not None or source_latents is not None or anchor_trajectory is not None or dynamic_memories:
+                raise ValueError("a DDIM inversion run takes no preseq, edit (source_latents / keep_mask / strength), anchor_trajectory or "
+                                 "dynamic memories: give the source as init_latents")
+        elif trajectory:
+            raise ValueError("trajectory=True records a DDIM inversion: it needs a DDIMInverseScheduler")
+        anchor = None
+        if anchor_trajectory is not None:
+            if scheduler.KIND != 1 or float(eta) != 0.0 or scheduler.config.get("clip_sample", False):
+                raise ValueError("an anchored run is a deterministic, unclipped DDIM run: DDIMScheduler(clip_sample=False) and eta = 0")
+            if source_latents is not None or preseq is not None or float(strength) != 1.0:
+                raise ValueError("an anchored run takes no source_latents, strength or preseq (its kept tokens come from the trajectory)")
+            anchor = check_anchor(anchor_trajectory, keep_mask, B, L, n_full, dev)
+            keep_mask = None
         edit = check_edit(source_latents, keep_mask, strength, B, L, n_full, preseq, dev)
         self.first_iteration = edit[2] if edit is not None else 0
         self.timesteps = [int(t) for t in table][self.first_iteration:]
@@ -406,6 +469,9 @@ class SamplingRun:
         self._keep.append(ts)
         a.timesteps, a.num_timesteps = C.cast(ts, C.c_void_p), n_full
         self.att_ring = None
+        self.trajectory = None
+        if trajectory:     # torch.empty: slot 0 is written at begin, slot j by iteration j - 1
+            self.trajectory = torch.empty((n_full + 1, B, L, 128), dtype=torch.float32, device=dev)
         if attention_ring:
             if skip_zero_weight_chunks:
                 raise ValueError("attention_ring keeps the last guidance chunk's maps: that chunk must be evaluated (skip_zero_weight_chunks=False)")
@@ -417,7 +483,21 @@ class SamplingRun:
         stream = torch.cuda.current_stream(dev).cuda_stream
         with torch.cuda.device(dev):
             torch.cuda.current_stream(dev).synchronize()
-            if edit is not None:
+            w_ptr = self.modality_weights.ctypes.data_as(C.c_void_p) if self.modality_weights is not None else None
+            if self.trajectory is not None or anchor is not None:
+                g_eval = C.c_int(0)
+                if self.trajectory is not None:
+                    _lib.check(self.lib.cfd_sample_begin_invert(self.handle, C.byref(a), C.c_void_p(self.trajectory.data_ptr()), w_ptr,
+                                                                1 if prune_zero_weight_chunks else 0, C.byref(g_eval), C.c_void_p(stream)))
+                else:
+                    an = _lib.AnchorArgs()
+                    an.trajectory, an.steps, an.B, an.L = anchor[0].data_ptr(), n_full, B, L
+                    an.keep = anchor[1].data_ptr() if anchor[1] is not None else None
+                    self._keep += [anchor[0], anchor[1], an]
+                    _lib.check(self.lib.cfd_sample_begin_anchored(self.handle, C.byref(a), C.byref(an), w_ptr,
+                                                                  1 if prune_zero_weight_chunks else 0, C.byref(g_eval), C.c_void_p(stream)))
+                self.chunks_evaluated = int(g_eval.value)
+            elif edit is not None:
                 e = _lib.EditArgs()
                 e.source, e.keep, e.first_iteration = edit[0].data_ptr(), (edit[1].data_ptr() if edit[1] is not None else None), edit[2]
                 self._keep += [edit[0], edit[1], e]
@@ -600,7 +680,7 @@ def _open_run(denoiser, scheduler, encoder_hidden_states, cond_masks, B, L, num_
 def sample(denoiser, scheduler, encoder_hidden_states, cond_masks=None, *, B, L=16, num_inference_steps=1000,
            guidance_scale=7.5, guidance_chunks=CFG_CHUNKS, eta=0.0, init_latents=None, step_noise=None, seed=0,
            first_utterance=0, preseq=None, dedup=True, skip_zero_weight_chunks=False, row_maps=None, return_attention=False, operands=None,
-           modality_weights=None, prune_zero_weight_chunks=True, source_latents=None, keep_mask=None, strength=1.0):
+           modality_weights=None, prune_zero_weight_chunks=True, source_latents=None, keep_mask=None, strength=1.0, anchor_trajectory=None):
     """Run the whole loop; returns latents [B, L, 128] (batch-first); with ``return_attention=True`` also the last
     iteration's attention maps (``last_step_attention``), with ``return_attention="all"`` a dict {timestep: maps} over every
     iteration like the reference's: kept by the captured iteration itself (``SamplingRun(attention_ring=True)``) while the ring fits
@@ -612,7 +692,9 @@ def sample(denoiser, scheduler, encoder_hidden_states, cond_masks=None, *, B, L=
     seed, initial latents and step noise), otherwise the default policy's; the worst case costs up to one extra partial run.
     ``modality_weights`` / ``prune_zero_weight_chunks``: per-modality guidance weights, as in ``SamplingRun``.
     ``source_latents`` / ``keep_mask`` / ``strength``: an edit run (token-masked in-painting, img2img strength), as in ``SamplingRun``; the
-    attention dict then holds the executed iterations."""
+    attention dict then holds the executed iterations.  ``anchor_trajectory`` / ``keep_mask``: a re-conditioning run over a recorded DDIM
+    inversion (``invert``), as in ``SamplingRun``.  With a ``DDIMInverseScheduler`` and ``init_latents`` = the source the loop is a DDIM
+    inversion: the same latents as ``invert`` with the same guidance."""
     if check_operands(operands) == "auto":
         args = dict(locals())
         return _with_auto_operands(lambda ops: sample(**dict(args, operands=ops)), "auto")
@@ -620,7 +702,7 @@ def sample(denoiser, scheduler, encoder_hidden_states, cond_masks=None, *, B, L=
                     guidance_scale=guidance_scale, guidance_chunks=guidance_chunks, eta=eta, init_latents=init_latents, step_noise=step_noise,
                     seed=seed, first_utterance=first_utterance, preseq=preseq, dedup=dedup, skip_zero_weight_chunks=skip_zero_weight_chunks,
                     row_maps=row_maps, operands=operands, modality_weights=modality_weights, prune_zero_weight_chunks=prune_zero_weight_chunks,
-                    source_latents=source_latents, keep_mask=keep_mask, strength=strength)
+                    source_latents=source_latents, keep_mask=keep_mask, strength=strength, anchor_trajectory=anchor_trajectory)
     try:
         if not return_attention:
             run.steps(run.N)
@@ -645,6 +727,34 @@ def sample(denoiser, scheduler, encoder_hidden_states, cond_masks=None, *, B, L=
         return (lat, {int(run.timesteps[-1]): att}) if return_attention == "auto" else (lat, att)
     finally:
         run.close()     # an exception must not leave the run open on the denoiser's handle
+
+
+# Guidance of an inversion by default: the conditional prediction alone, eps = e_0 + 1 * (e_full - e_0) at guidance_scale 1 (the
+# full-conditioning chunk is the last one); a pruned run evaluates 2 of the 7 chunks.
+INVERSION_WEIGHTS = dict(text=0.0, audio=0.0, spk=0.0, apb=0.0, lsnid=0.0, all=1.0)
+
+
+def invert(denoiser, scheduler, encoder_hidden_states, cond_masks=None, *, source_latents, num_inference_steps=50, guidance_scale=1.0,
+           modality_weights=None, return_trajectory=False, operands=None):
+    """Deterministic DDIM inversion of ``source_latents`` [B, L, 128] on the fused loop (scheduler kind 3): the noise that the DDIM loop
+    with the same table and guidance maps back onto the source.  ``scheduler``: a ``DDIMInverseScheduler``; encoder_hidden_states /
+    cond_masks: the 7-chunk guidance batch, as for ``sample``.  The guidance is the weighted combine with ``modality_weights`` at
+    ``guidance_scale`` (any table ``modality_weight_table`` accepts); None: INVERSION_WEIGHTS at guidance_scale 1, the conditional prediction
+    alone.  Returns the inverted latents [B, L, 128], and with ``return_trajectory=True`` also the trajectory [N + 1, B, L, 128] (slot 0 the
+    source, slot j the latents after j iterations), recorded by the captured iteration itself -- the ``anchor_trajectory`` of a
+    re-conditioning run (``sample(..., anchor_trajectory=, keep_mask=)``)."""
+    if getattr(scheduler, "KIND", None) != 3:
+        raise TypeError("invert needs a convofusion_amd.scheduler.DDIMInverseScheduler")
+    if not isinstance(source_latents, torch.Tensor) or source_latents.dim() != 3 or int(source_latents.shape[2]) != 128:
+        raise ValueError("source_latents must be a tensor [B, L, 128]")
+    B, L = int(source_latents.shape[0]), int(source_latents.shape[1])
+    weights = INVERSION_WEIGHTS if modality_weights is None else modality_weights
+    with SamplingRun(denoiser, scheduler, encoder_hidden_states, cond_masks, B, L, num_inference_steps, guidance_scale=guidance_scale,
+                     guidance_chunks=CFG_CHUNKS, init_latents=source_latents, modality_weights=weights, operands=check_operands(operands),
+                     trajectory=bool(return_trajectory)) as run:
+        run.steps(run.N)
+        lat = run.read(close=True)
+        return (lat, run.trajectory) if return_trajectory else lat
 
 
 # the WEG constants diffusion_reverse_forecast hard-codes instead of reading cfg.model.weg_parameters (unbounded_synthesis.py:80-84)
@@ -705,6 +815,9 @@ def sample_with_weg(denoiser, scheduler, encoder_hidden_states, cond_masks, focu
         args = dict(locals())
         rest = args.pop("kw")
         return _with_auto_operands(lambda ops: sample_with_weg(**args, **dict(rest, operands=ops)), "auto")
+    if getattr(scheduler, "KIND", None) == 3:
+        raise NotImplementedError("sample_with_weg: a DDIM inversion (DDIMInverseScheduler) takes no word-excitation guidance -- its latents "
+                                  "are its own; use invert() or sample() without focus_indices")
     if getattr(scheduler, "KIND", None) == 2:
         raise NotImplementedError("sample_with_weg: the word-excitation-guidance loop (focus_indices) runs with DDPMScheduler / DDIMScheduler; "
                                   "with DPMSolverMultistepScheduler it has no reference trajectory to be checked against -- use sample() "

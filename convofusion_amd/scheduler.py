@@ -4,7 +4,8 @@ convofusion/models/modeltype/convofusion.py:104-106,419-423,544,574 and unbounde
 
 diffusers is a third-party dependency that is neither vendored in the reference nor installed here;
 these classes restate its public surface for the epsilon-prediction / fixed_small / clip_sample
-configuration, and DPMSolverMultistepScheduler in its default (DPM-Solver++ 2M) configuration.  Tables are built with the same torch float32 ops diffusers uses; ``step`` and
+configuration, DPMSolverMultistepScheduler in its default (DPM-Solver++ 2M) configuration, and DDIMInverseScheduler (deterministic DDIM
+inversion, beyond the reference).  Tables are built with the same torch float32 ops diffusers uses; ``step`` and
 ``add_noise`` run on the device through libcfdenoise (cfd_scheduler_step / cfd_add_noise).  The
 fused sampling loop (convofusion_amd.sampler) reads only the tables and config from these objects.
 """
@@ -189,6 +190,51 @@ class DDIMScheduler(_SchedulerBase):
         if self.num_inference_steps is None:
             raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
         prev, x0 = self._step(model_output, timestep, sample, eta, variance_noise, generator)
+        return SchedulerOutput(prev_sample=prev, pred_original_sample=x0) if return_dict else (prev,)
+
+
+class DDIMInverseScheduler(_SchedulerBase):
+    """Deterministic DDIM inversion (prompt-to-prompt's ``next_step``; scheduler kind 3): the DDIM step run backwards, from clean latents
+    towards the noise that the DDIM loop maps back onto them.  Same constructor kwargs as ``DDIMScheduler``.
+
+    ``set_timesteps(N)`` builds the DDIM table reversed, so it ascends: ``0, T // N, ..., T - T // N`` (+ steps_offset).  The step at t
+    evaluates the model at t -- the level it moves TO -- and moves from t_cur = t - T // N (abar = final_alpha_cumprod when t_cur < 0):
+    x0 = (x - sqrt(1 - abar[t_cur]) eps) / sqrt(abar[t_cur]), x = sqrt(abar[t]) x0 + sqrt(1 - abar[t]) eps.
+
+    The inversion never clips x0 and draws no noise: a clipped x0 is not invertible (the reference's yaml sets clip_sample: true for its
+    DDPM scheduler), so ``clip_sample`` is accepted for kwarg compatibility and ignored -- ``config.clip_sample`` is always False and the
+    library is handed 0.  eta does not exist here (0)."""
+    KIND = 3
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear",
+                 trained_betas=None, clip_sample=True, set_alpha_to_one=True, steps_offset=0,
+                 prediction_type="epsilon", **kwargs):
+        if prediction_type != "epsilon":
+            raise NotImplementedError("only prediction_type='epsilon'")
+        self.config = _Config(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
+                              beta_schedule=beta_schedule, clip_sample=False, set_alpha_to_one=set_alpha_to_one,
+                              steps_offset=steps_offset, prediction_type=prediction_type)
+        self._init_tables(num_train_timesteps, beta_start, beta_end, beta_schedule, trained_betas)
+        self.final_alpha_cumprod = torch.tensor(1.0) if set_alpha_to_one else self.alphas_cumprod[0]
+        self.timesteps = torch.from_numpy(np.arange(0, num_train_timesteps).copy())
+
+    def timestep_table(self, num_inference_steps):
+        """(step count, int64 ascending timestep array) of ``set_timesteps`` without touching the scheduler's state."""
+        n = int(num_inference_steps)
+        if n < 1 or n > self.config.num_train_timesteps:
+            raise ValueError(f"DDIMInverseScheduler: num_inference_steps = {n} must be in [1, {self.config.num_train_timesteps}]")
+        step_ratio = self.config.num_train_timesteps // n
+        return n, (np.arange(0, n) * step_ratio).round().astype(np.int64) + self.config.steps_offset
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        self.num_inference_steps, timesteps = self.timestep_table(num_inference_steps)
+        self.timesteps = torch.from_numpy(timesteps).to(device)
+
+    def step(self, model_output, timestep, sample, return_dict=True):
+        """One inversion step at ``timestep`` (the level it moves to) through cfd_scheduler_step (kind 3)."""
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        prev, x0 = self._step(model_output, timestep, sample, 0.0, None, None)
         return SchedulerOutput(prev_sample=prev, pred_original_sample=x0) if return_dict else (prev,)
 
 

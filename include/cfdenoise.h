@@ -112,7 +112,15 @@ typedef struct {
   int scheduler;              /* 0 = DDPMScheduler (fixed_small), 1 = DDIMScheduler, 2 = DPMSolverMultistepScheduler in diffusers 0.14.0's
                                  default configuration (dpmsolver++, solver_order 2, midpoint, lower_order_final; no noise): needs
                                  `timesteps` and clip_sample == 0; eta, set_alpha_to_one and steps_offset are ignored.  The run keeps
-                                 its own x0 history ([B][L][128] float32, allocated by cfd_sample_begin). */
+                                 its own x0 history ([B][L][128] float32, allocated by cfd_sample_begin).
+                                 3 = deterministic DDIM inversion (prompt-to-prompt's next_step): runs the DDIM step backwards, from
+                                 clean latents towards noise.  Needs `timesteps`, strictly increasing in [0, T) (the DDIM table
+                                 reversed), eta == 0 and clip_sample == 0 (a clipped x0 is not invertible).  Iteration i at t:
+                                 eps = the combine evaluated at t; a_cur = abar[t - T // N] (t - T // N < 0: 1 with set_alpha_to_one,
+                                 else abar[0]), a_nxt = abar[t]; x0 = (x - sqrt(1 - a_cur) eps) / sqrt(a_cur),
+                                 x = sqrt(a_nxt) x0 + sqrt(1 - a_nxt) eps -- kind 1's step with these coefficients.  CFD_E_ARG with
+                                 preseq, a dynamic memory, an edit (cfd_sample_begin_edit / _anchored) or a WEG update
+                                 (cfd_sample_write). */
   int num_train_timesteps;    /* 1000 */
   int num_inference_steps;    /* scheduler.set_timesteps(N) */
   int clip_sample;            /* configs/modules/scheduler.yaml:11 */
@@ -214,6 +222,28 @@ typedef struct {
  * an edit.  With first_iteration = 0 and keep all 0 / NULL the run computes what cfd_sample_begin(_weighted) computes, bit for bit. */
 int cfd_sample_begin_edit(cfd_handle h, const cfd_sample_args* args, const cfd_edit_args* e, const float* weights, int prune,
                           int* chunks_evaluated, void* stream);
+/* DDIM inversion with its trajectory: cfd_sample_begin / cfd_sample_begin_weighted (weights != NULL, with `prune` and `chunks_evaluated`
+ * as there; weights == NULL: the default combine, *chunks_evaluated = the evaluated chunks) for a scheduler-3 run that also records
+ * `trajectory`: dev float32 [iterations + 1][B][L][128], owned by the caller and written by the run.  Slot 0 receives the initial
+ * latents (the source) at begin; the captured iteration's scheduler step stores the latents after iteration i into slot i + 1 (no extra
+ * launch).  CFD_E_ARG: trajectory == NULL, args->scheduler != 3, and every kind-3 refusal. */
+int cfd_sample_begin_invert(cfd_handle h, const cfd_sample_args* args, float* trajectory, const float* weights, int prune,
+                            int* chunks_evaluated, void* stream);
+/* Re-conditioning over a recorded inversion trajectory (cfd_sample_begin_invert). */
+typedef struct {
+  const float* trajectory;    /* dev float32 [steps + 1][B][L][128]: the ring of an inversion run.  Read, not copied: it must stay
+                                 unchanged until the run is closed. */
+  int steps;                  /* iterations of that inversion; must equal this run's iterations */
+  int B, L;                   /* the ring's utterances and tokens; must equal args->B / args->L */
+  const uint8_t* keep;        /* dev [B][L] uint8, each 0 or 1, or NULL (= all 0): at the start of iteration i the tokens with keep = 1
+                                 are set to trajectory[steps - i] -- the inverted latents at the level iteration i starts from. */
+} cfd_anchor_args;
+/* An anchored DDIM run: args->scheduler == 1, eta == 0, clip_sample == 0, no preseq.  Weights / prune / chunks_evaluated as in
+ * cfd_sample_begin_edit.  With keep all 0 / NULL the run computes what cfd_sample_begin(_weighted) computes, bit for bit.  CFD_E_ARG:
+ * a NULL argument or trajectory, another scheduler, eta != 0, clip_sample != 0, preseq, steps / B / L other than the run's, a keep
+ * value other than 0 / 1. */
+int cfd_sample_begin_anchored(cfd_handle h, const cfd_sample_args* args, const cfd_anchor_args* a, const float* weights, int prune,
+                              int* chunks_evaluated, void* stream);
 /* Replays the captured iteration `n` more times (asynchronously on the run's stream). */
 int cfd_sample_steps(cfd_handle h, int n);
 /* Number of iterations executed so far in the open run. */
@@ -263,8 +293,9 @@ typedef struct {
 int cfd_sample_census(cfd_handle h, cfd_census* out);
 
 /* Stand-alone scheduler ops on device tensors (diffusers 0.14.0 `scheduler.step(...).prev_sample` and
- * `add_noise`), for callers that drive their own loop (unbounded_synthesis.py:75,181).  cfd_scheduler_step takes scheduler 0 (DDPM)
- * or 1 (DDIM) and refuses any other kind with CFD_E_ARG: DPM-Solver++ keeps a history and has its own entry, cfd_dpmsolver_step. */
+ * `add_noise`), for callers that drive their own loop (unbounded_synthesis.py:75,181).  cfd_scheduler_step takes scheduler 0 (DDPM),
+ * 1 (DDIM) or 3 (DDIM inversion: `t` is the level the step moves to; eta and clip_sample must be 0) and refuses any other kind with
+ * CFD_E_ARG: DPM-Solver++ keeps a history and has its own entry, cfd_dpmsolver_step. */
 int cfd_scheduler_step(cfd_handle h, int scheduler, const float* alphas_cumprod, int num_train_timesteps,
                        int num_inference_steps, int t, int clip_sample, float eta, int set_alpha_to_one,
                        const float* model_output, const float* noise, float* sample_inout, size_t numel,

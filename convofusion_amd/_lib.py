@@ -25,6 +25,7 @@ SYMBOLS = [
     "cfd_layer_norm_bwd", "cfd_ew", "cfd_weg_focus", "cfd_sample_write", "cfd_sample_inpaint", "cfd_weg_eval", "cfd_dyadic_steps",
     "cfd_sample_census", "cfd_dpmsolver_step", "cfd_test_step_coefficients", "cfd_test_gemm_epi",
     "cfd_vae_encode", "cfd_sample_begin_weighted", "cfd_sample_begin_edit", "cfd_sample_begin_invert", "cfd_sample_begin_anchored",
+    "cfd_sample_begin_tied",
 ]
 
 
@@ -72,6 +73,11 @@ CENSUS_MAX_LAYERS = 16
 class EditArgs(C.Structure):
     """cfd_edit_args: the source latents (dev [B][L][128]), the keep mask (dev uint8 [B][L] or NULL) and the first iteration k0."""
     _fields_ = [("source", C.c_void_p), ("keep", C.c_void_p), ("first_iteration", C.c_int)]
+
+
+class TieArgs(C.Structure):
+    """cfd_tie_args: the tie table (dev int32 [B][L]: -1 or the flat index b' * L + l' of the token's source in the same run)."""
+    _fields_ = [("tie", C.c_void_p)]
 
 
 class AnchorArgs(C.Structure):
@@ -169,6 +175,8 @@ def load():
     lib.cfd_sample_begin_weighted.argtypes = [C.c_void_p, C.POINTER(SampleArgs), C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p]
     lib.cfd_sample_begin_edit.argtypes = [C.c_void_p, C.POINTER(SampleArgs), C.POINTER(EditArgs), C.c_void_p, C.c_int, C.POINTER(C.c_int),
                                           C.c_void_p]
+    lib.cfd_sample_begin_tied.argtypes = [C.c_void_p, C.POINTER(SampleArgs), C.POINTER(EditArgs), C.POINTER(TieArgs), C.c_void_p, C.c_int,
+                                          C.POINTER(C.c_int), C.c_void_p]
     lib.cfd_sample_begin_invert.argtypes = [C.c_void_p, C.POINTER(SampleArgs), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p]
     lib.cfd_sample_begin_anchored.argtypes = [C.c_void_p, C.POINTER(SampleArgs), C.POINTER(AnchorArgs), C.c_void_p, C.c_int,
                                               C.POINTER(C.c_int), C.c_void_p]

@@ -295,6 +295,12 @@ struct cfd_handle_s {
   bool run_anchor = false;
   const float* anchor_ring = nullptr;
   int anchor_n = 0;
+  // Tied run (cfd_sample_begin_tied): the tied instances of begin_step_kernel / inpaint_now_kernel copy token etie[b][l] (-1: none) of
+  // the run's own latents into token (b, l) at the start of every iteration, next to the edit instance's kept tokens; tie_final: the
+  // copy after the last iteration (tie_copy_kernel, enqueued by the first cfd_sample_read that finds the run finished) has been done.
+  bool run_tie = false;
+  bool tie_final = false;
+  DBuf etie;
   int run_pos = 0;
 };
 typedef cfd_handle_s Ctx;

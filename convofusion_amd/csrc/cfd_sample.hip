@@ -105,6 +105,7 @@ static void (*const cfg_step_kernel_weighted)(const CfgStepArgsW) = cfg_step_ker
 
 static void (*const begin_step_kernel_edit)(const BeginArgsE) = begin_step_kernel<0, true>;   // (one macro argument for LAUNCH)
 static void (*const begin_step_kernel_anchor)(const BeginArgsA) = begin_step_kernel<0, false, true>;
+static void (*const begin_step_kernel_tied)(const BeginArgsT) = begin_step_kernel<0, true, false, true>;
 static void (*const cfg_step_kernel_traj)(const CfgStepArgsT<CfgStepArgs>) = cfg_step_kernel<0, false, true>;
 static void (*const cfg_step_kernel_weighted_traj)(const CfgStepArgsT<CfgStepArgsW>) = cfg_step_kernel<0, true, true>;
 
@@ -117,6 +118,13 @@ static BeginArgsE edit_begin_args(Ctx* c) {
   be.src = c->esrc.as<float>();
   be.eps = c->enoise.as<float>();
   return be;
+}
+
+static BeginArgsT tied_begin_args(Ctx* c) {
+  BeginArgsT bt;
+  static_cast<BeginArgsE&>(bt) = edit_begin_args(c);
+  bt.tie = c->etie.as<int32_t>();
+  return bt;
 }
 
 static BeginArgsA anchor_begin_args(Ctx* c) {
@@ -134,7 +142,9 @@ static BeginArgsA anchor_begin_args(Ctx* c) {
 static int enqueue_loop_iteration(Ctx* c, hipStream_t st) {
   const cfd_sample_args& s = c->sargs;
   const long long n8 = (long long)s.B * s.L * (CFD_LAT / 8);
-  if (c->run_edit) {
+  if (c->run_tie) {
+    LAUNCH(CFD_PROF_OTHER, begin_step_kernel_tied, dim3((unsigned)((n8 + 255) / 256)), dim3(256), st, tied_begin_args(c));
+  } else if (c->run_edit) {
     LAUNCH(CFD_PROF_OTHER, begin_step_kernel_edit, dim3((unsigned)((n8 + 255) / 256)), dim3(256), st, edit_begin_args(c));
   } else if (c->run_anchor) {
     LAUNCH(CFD_PROF_OTHER, begin_step_kernel_anchor, dim3((unsigned)((n8 + 255) / 256)), dim3(256), st, anchor_begin_args(c));
@@ -223,7 +233,8 @@ static int weighted_chunks(Ctx* c, const float* wtab, int prune, int N, bool kee
 }
 
 static int sample_begin(Ctx* c, const cfd_sample_args* args, void* stream, const float* wtab, int prune, int* chunks_evaluated,
-                        const cfd_edit_args* edit = nullptr, float* traj = nullptr, const cfd_anchor_args* anchor = nullptr);
+                        const cfd_edit_args* edit = nullptr, float* traj = nullptr, const cfd_anchor_args* anchor = nullptr,
+                        const cfd_tie_args* tie = nullptr);
 
 extern "C" int cfd_sample_begin(cfd_handle c, const cfd_sample_args* args, void* stream) {
   return sample_begin(c, args, stream, nullptr, 0, nullptr);
@@ -236,6 +247,24 @@ extern "C" int cfd_sample_begin_edit(cfd_handle c, const cfd_sample_args* args, 
   if (args->preseq) return fail(CFD_E_ARG, "cfd_sample_begin_edit: an edit run has no preseq (the rollout's prefix in-painting)");
   if (weights && args->G != 7) return fail(CFD_E_ARG, "cfd_sample_begin_edit: a weight table needs the 7-chunk guidance batch (G = %d)", args->G);
   const int r = sample_begin(c, args, stream, weights, weights ? prune : 0, weights ? chunks_evaluated : nullptr, e);
+  if (r == CFD_OK && !weights && chunks_evaluated) *chunks_evaluated = c->sargs.G;
+  return r;
+}
+
+extern "C" int cfd_sample_begin_tied(cfd_handle c, const cfd_sample_args* args, const cfd_edit_args* e, const cfd_tie_args* t,
+                                     const float* weights, int prune, int* chunks_evaluated, void* stream) {
+  if (!c || !args || !t) return fail(CFD_E_ARG, "null argument");
+  if (!t->tie) return fail(CFD_E_ARG, "cfd_sample_begin_tied: the tie table is NULL");
+  if (e && !e->source) return fail(CFD_E_ARG, "cfd_sample_begin_tied: the source latents of the edit are NULL");
+  if (e && e->first_iteration != 0)
+    return fail(CFD_E_ARG, "cfd_sample_begin_tied: a tied run starts at iteration 0 (first_iteration = %d: no strength)", e->first_iteration);
+  if (args->scheduler == 3) return fail(CFD_E_ARG, "cfd_sample_begin_tied: DDIM inversion (scheduler 3) takes no ties");
+  if (args->preseq) return fail(CFD_E_ARG, "cfd_sample_begin_tied: a tied run has no preseq (give the prefix as kept tokens of an edit)");
+  if (args->dynamic_memory_mask)
+    return fail(CFD_E_ARG, "cfd_sample_begin_tied: a tied run takes no dynamic memories (dynamic_memory_mask = %d: dyadic runs)",
+                args->dynamic_memory_mask);
+  if (weights && args->G != 7) return fail(CFD_E_ARG, "cfd_sample_begin_tied: a weight table needs the 7-chunk guidance batch (G = %d)", args->G);
+  const int r = sample_begin(c, args, stream, weights, weights ? prune : 0, weights ? chunks_evaluated : nullptr, e, nullptr, nullptr, t);
   if (r == CFD_OK && !weights && chunks_evaluated) *chunks_evaluated = c->sargs.G;
   return r;
 }
@@ -279,7 +308,7 @@ extern "C" int cfd_sample_begin_weighted(cfd_handle c, const cfd_sample_args* ar
 }
 
 static int sample_begin(Ctx* c, const cfd_sample_args* args, void* stream, const float* wtab, int prune, int* chunks_evaluated,
-                        const cfd_edit_args* edit, float* traj, const cfd_anchor_args* anchor) {
+                        const cfd_edit_args* edit, float* traj, const cfd_anchor_args* anchor, const cfd_tie_args* tie) {
   if (!c || !args) return fail(CFD_E_ARG, "null argument");
   if (c->run_open) return fail(CFD_E_STATE, "a sampling run is already open");
   HIPCHK(hipSetDevice(c->cfg.device));
@@ -301,6 +330,8 @@ static int sample_begin(Ctx* c, const cfd_sample_args* args, void* stream, const
   c->run_anchor = false;
   c->anchor_ring = nullptr;
   c->anchor_n = 0;
+  c->run_tie = false;
+  c->tie_final = false;
   const cfd_sample_args& s = *args;
   if (s.B < 1 || (s.G != 1 && s.G != 7 && (s.G < 1 || s.G > 8))) return fail(CFD_E_ARG, "bad B / G");
   if (s.scheduler < 0 || s.scheduler > 3)
@@ -335,6 +366,27 @@ static int sample_begin(Ctx* c, const cfd_sample_args* args, void* stream, const
     HIPCHK(hipMemcpy(hkeep.data(), keep_in, hkeep.size(), hipMemcpyDeviceToHost));
     for (size_t e = 0; e < hkeep.size(); ++e)
       if (hkeep[e] > 1) return fail(CFD_E_ARG, "%s: keep[%zu][%zu] = %d is not 0 or 1", who, e / s.L, e % s.L, (int)hkeep[e]);
+  }
+  std::vector<int32_t> htie;
+  if (tie) {   // the tie table on the host: range, no self-tie, a source is free (neither tied nor kept), no token both kept and tied
+    if (s.L < 1) return fail(CFD_E_ARG, "bad L");
+    const long long nt = (long long)s.B * s.L;
+    htie.resize((size_t)nt);
+    HIPCHK(hipMemcpy(htie.data(), tie->tie, htie.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    for (long long e = 0; e < nt; ++e) {
+      const long long t = htie[(size_t)e];
+      const int b = (int)(e / s.L), l = (int)(e % s.L);
+      if (t == -1) continue;
+      if (t < -1 || t >= nt) return fail(CFD_E_ARG, "cfd_sample_begin_tied: tie[%d][%d] = %lld is not -1 or a token in [0, %lld)", b, l, t, nt);
+      if (t == e) return fail(CFD_E_ARG, "cfd_sample_begin_tied: tie[%d][%d] = %lld ties the token to itself", b, l, t);
+      if (htie[(size_t)t] != -1)
+        return fail(CFD_E_ARG, "cfd_sample_begin_tied: tie[%d][%d] = %lld names a source (%lld, %lld) that is itself tied (no chains)", b, l, t,
+                    t / s.L, t % s.L);
+      if (!hkeep.empty() && hkeep[(size_t)t])
+        return fail(CFD_E_ARG, "cfd_sample_begin_tied: tie[%d][%d] = %lld names a source (%lld, %lld) that is kept (a source must be free)", b, l,
+                    t, t / s.L, t % s.L);
+      if (!hkeep.empty() && hkeep[(size_t)e]) return fail(CFD_E_ARG, "cfd_sample_begin_tied: token (%d, %d) is both kept and tied", b, l);
+    }
   }
   hipStream_t st = (hipStream_t)stream;
   c->sargs = s;
@@ -470,6 +522,21 @@ static int sample_begin(Ctx* c, const cfd_sample_args* args, void* stream, const
     HIPCHK(hipMemcpyAsync(c->latents.p, s.init_latents, lat_bytes, hipMemcpyDeviceToDevice, st));
   } else {
     CHK(enqueue_philox_fill(c->latents.as<float>(), s.B, s.L * CFD_LAT, (uint64_t)s.seed, 0u, s.first_utterance, 1u, 1.0f, st));
+  }
+  // A tied run.  The scheduler step still steps a tied token (from the copied value and the token's own prediction) and, for DPM-Solver++,
+  // keeps its x0 history; neither survives: the token is overwritten with its source at the start of the next iteration and once more
+  // after the last (cfd_sample_read), and the history of a token feeds that token's step alone.
+  if (tie) {   // the run's own copy of the table; without an edit: no kept token (the source and noise buffers are never read)
+    CHK(c->etie.ensure(htie.size() * sizeof(int32_t)));
+    HIPCHK(hipMemcpyAsync(c->etie.p, htie.data(), htie.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if (!edit) {
+      CHK(c->enoise.ensure(lat_bytes));
+      CHK(c->esrc.ensure(lat_bytes));
+      CHK(c->ekeep.ensure((size_t)s.B * s.L));
+      HIPCHK(hipMemsetAsync(c->ekeep.p, 0, (size_t)s.B * s.L, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));   // (htie goes out of scope)
+    c->run_tie = true;
   }
   if (edit) {   // the run's noise eps = the initial draw, the source, the mask; k0 > 0: every token starts at sa_k0 * source + sb_k0 * eps
     CHK(c->enoise.ensure(lat_bytes));
@@ -612,6 +679,7 @@ extern "C" int cfd_dyadic_steps(cfd_handle a, cfd_handle b, const cfd_dyadic_pro
   if (!pr->w1 || !pr->b1 || !pr->w2 || !pr->b2 || !pr->spk_a || !pr->spk_b || !pr->tmp || pr->hidden < 1 || pr->out_dim != CFD_D)
     return fail(CFD_E_ARG, "bad partner projection");
   const cfd_sample_args& sa = a->sargs;
+  if (a->run_tie || (b && b->run_tie)) return fail(CFD_E_ARG, "a tied run takes no dyadic steps");
   if (!(sa.dynamic_memory_mask & 1) || (b && !(b->sargs.dynamic_memory_mask & 1)))
     return fail(CFD_E_STATE, "the speaker memory of the run(s) must be declared dynamic");
   if (b && (sa.B != b->sargs.B || sa.L != b->sargs.L || a->cfg.device != b->cfg.device)) return fail(CFD_E_ARG, "the two sides differ in batch, length or device");
@@ -660,6 +728,13 @@ extern "C" int cfd_sample_read(cfd_handle c, float* out, int close) {
   if (!c->run_open) return fail(CFD_E_STATE, "no sampling run open");
   HIPCHK(hipSetDevice(c->cfg.device));
   const size_t lat_bytes = (size_t)c->sargs.B * c->sargs.L * CFD_LAT * 4;
+  if (c->run_tie && !c->tie_final && c->run_pos == c->run_iters) {   // a finished tied run: the tie copy once more (mid-run reads: as stepped)
+    const long long n8 = (long long)c->sargs.B * c->sargs.L * (CFD_LAT / 8);
+    hipLaunchKernelGGL(tie_copy_kernel<>, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, c->run_stream, c->latents.as<float>(),
+                       c->etie.as<int32_t>(), n8);
+    HIPCHK(hipGetLastError());
+    c->tie_final = true;
+  }
   HIPCHK(hipMemcpyAsync(out, c->latents.p, lat_bytes, hipMemcpyDeviceToDevice, c->run_stream));
   HIPCHK(hipStreamSynchronize(c->run_stream));
   CHK(settle_deferred_census(c));
@@ -748,11 +823,21 @@ extern "C" int cfd_philox_normal(cfd_handle c, float* out, int B, int per_utt, u
 
 static void (*const inpaint_now_kernel_edit)(const BeginArgsE, int*) = inpaint_now_kernel<0, true>;
 static void (*const inpaint_now_kernel_anchor)(const BeginArgsA, int*) = inpaint_now_kernel<0, false, true>;
+static void (*const inpaint_now_kernel_tied)(const BeginArgsT, int*) = inpaint_now_kernel<0, true, false, true>;
 
 extern "C" int cfd_sample_inpaint(cfd_handle c) {
   if (!c) return fail(CFD_E_ARG, "null handle");
   if (!c->run_open) return fail(CFD_E_STATE, "no sampling run open");
   const cfd_sample_args& s = c->sargs;
+  if (c->run_tie) {   // the tied instance: the tied and the kept tokens of this iteration, then the captured iteration skips both
+    if (c->run_pos >= c->run_iters) return fail(CFD_E_STATE, "cfd_sample_inpaint: the run has no iteration left");
+    HIPCHK(hipSetDevice(c->cfg.device));
+    const long long n8 = (long long)s.B * s.L * (CFD_LAT / 8);
+    hipLaunchKernelGGL(inpaint_now_kernel_tied, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, c->run_stream, tied_begin_args(c),
+                       c->w->d_step.as<int>());
+    HIPCHK(hipGetLastError());
+    return CFD_OK;
+  }
   if (c->run_edit) {   // the edit instance: the kept tokens of this iteration, then the captured iteration skips its overwrite
     if (c->run_pos >= c->run_iters) return fail(CFD_E_STATE, "cfd_sample_inpaint: the run has no iteration left");
     HIPCHK(hipSetDevice(c->cfg.device));

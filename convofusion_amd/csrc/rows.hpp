@@ -605,8 +605,16 @@ struct BeginArgsA : BeginArgs {
   long long slot;        // B * L * 128: floats per ring slot
   int n;                 // iterations of the inversion (= of this run)
 };
-template <bool EDIT, bool ANCHOR = false>
-using BeginArgsOf = typename std::conditional<ANCHOR, BeginArgsA, typename std::conditional<EDIT, BeginArgsE, BeginArgs>::type>::type;
+// The tied instance's arguments (cfd_sample_begin_tied): the edit instance's, and a tie table.  Token (b, l) with tie[b * L + l] = s >= 0
+// takes the current value of token s (a flat index b' * L + l' of the same run) at the start of every iteration; -1: a free token (or a
+// kept one, as in BeginArgsE).  No race: the host refuses a source that is itself tied or kept (cfd_sample_begin_tied), so the tokens a
+// launch reads as sources are tokens none of its threads writes.
+struct BeginArgsT : BeginArgsE {
+  const int32_t* tie;    // [B][L] -1 or the source token
+};
+template <bool EDIT, bool ANCHOR = false, bool TIE = false>
+using BeginArgsOf = typename std::conditional<TIE, BeginArgsT,
+    typename std::conditional<ANCHOR, BeginArgsA, typename std::conditional<EDIT, BeginArgsE, BeginArgs>::type>::type>::type;
 
 // 8 consecutive elements of sa * src + sb * eps, each product and the sum rounded on its own
 __device__ __forceinline__ void edit_mix8(float sa, float sb, const float* src, const float* eps, float v[8]) {
@@ -628,8 +636,8 @@ __device__ __forceinline__ void load8(const float* p, float v[8]) {
   v[0] = a0.x; v[1] = a0.y; v[2] = a0.z; v[3] = a0.w; v[4] = a1.x; v[5] = a1.y; v[6] = a1.z; v[7] = a1.w;
 }
 
-template <int CFD_KI = 0, bool EDIT = false, bool ANCHOR = false>
-__global__ void begin_step_kernel(const BeginArgsOf<EDIT, ANCHOR> a) {
+template <int CFD_KI = 0, bool EDIT = false, bool ANCHOR = false, bool TIE = false>
+__global__ void begin_step_kernel(const BeginArgsOf<EDIT, ANCHOR, TIE> a) {
   const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;  // one thread = 8 elements
   const long long n8 = (long long)a.B * a.L * (CFD_LAT / 8);
   if (idx >= n8) return;
@@ -638,7 +646,21 @@ __global__ void begin_step_kernel(const BeginArgsOf<EDIT, ANCHOR> a) {
   const int l = (int)(bl % a.L), b = (int)(bl / a.L);
   float* lp = a.latents + bl * CFD_LAT + c;
   float v[8];
-  if constexpr (ANCHOR) {
+  if constexpr (TIE) {   // (the edit instance's arguments: a token is tied, kept or free)
+    const int ts = a.tie[bl];
+    const bool todo = a.d_step[2] == 0;     // d_step[2] != 0: cfd_sample_inpaint already did this iteration's overwrite
+    if (ts >= 0 && todo) {                  // the source token as the previous iteration's scheduler step left it (never written here)
+      load8(a.latents + (long long)ts * CFD_LAT + c, v);
+      store8(lp, v);
+    } else if (ts < 0 && a.keep[bl] && todo) {
+      const int i = *a.d_step;
+      edit_mix8(a.coef[i].sa, a.coef[i].sb, a.src + bl * CFD_LAT + c, a.eps + bl * CFD_LAT + c, v);
+      store8(lp, v);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] = lp[e];
+    }
+  } else if constexpr (ANCHOR) {
     if (a.keep[bl] && a.d_step[2] == 0) {   // d_step[2] != 0: cfd_sample_inpaint already did this iteration's overwrite
       load8(a.ring + (long long)(a.n - *a.d_step) * a.slot + bl * CFD_LAT + c, v);
       store8(lp, v);
@@ -799,12 +821,45 @@ __global__ void edit_init_kernel(float* latents, const float* src, const float* 
   store8(latents + idx * 8, v);
 }
 
+// The tie copy alone, once after the last iteration of a tied run (cfd_sample_read): every tied token becomes bit for bit its source as the
+// last scheduler step left it.  No kept token is touched (there is no iteration left to re-noise it for).  One thread = 8 elements.
+template <int CFD_KI = 0>
+__global__ void tie_copy_kernel(float* latents, const int32_t* tie, long long n8) {
+  const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n8) return;
+  const long long bl = idx / (CFD_LAT / 8);
+  const int c = (int)(idx % (CFD_LAT / 8)) * 8;
+  const int ts = tie[bl];
+  if (ts < 0) return;
+  float v[8];
+  load8(latents + (long long)ts * CFD_LAT + c, v);
+  store8(latents + bl * CFD_LAT + c, v);
+}
+
 // The in-painting overwrite of begin_step_kernel alone, ahead of the captured iteration (cfd_sample_inpaint): the WEG
 // branch of the rollout alters the latents AFTER the overwrite and BEFORE the replication (unbounded_synthesis.py:70-143).
-template <int CFD_KI = 0, bool EDIT = false, bool ANCHOR = false>
-__global__ void inpaint_now_kernel(const BeginArgsOf<EDIT, ANCHOR> a, int* d_step) {
+template <int CFD_KI = 0, bool EDIT = false, bool ANCHOR = false, bool TIE = false>
+__global__ void inpaint_now_kernel(const BeginArgsOf<EDIT, ANCHOR, TIE> a, int* d_step) {
   const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if constexpr (ANCHOR) {   // one thread = 8 elements of one token, kept tokens only
+  if constexpr (TIE) {   // one thread = 8 elements of one token, tied and kept tokens only
+    const long long n8 = (long long)a.B * a.L * (CFD_LAT / 8);
+    if (idx == 0) d_step[2] = 1;
+    if (idx >= n8) return;
+    const long long bl = idx / (CFD_LAT / 8);
+    const int c = (int)(idx % (CFD_LAT / 8)) * 8;
+    const int ts = a.tie[bl];
+    float v[8];
+    if (ts >= 0) {
+      load8(a.latents + (long long)ts * CFD_LAT + c, v);
+    } else if (a.keep[bl]) {
+      const int i = *a.d_step;
+      edit_mix8(a.coef[i].sa, a.coef[i].sb, a.src + bl * CFD_LAT + c, a.eps + bl * CFD_LAT + c, v);
+    } else {
+      return;
+    }
+    store8(a.latents + bl * CFD_LAT + c, v);
+    return;
+  } else if constexpr (ANCHOR) {   // one thread = 8 elements of one token, kept tokens only
     const long long n8 = (long long)a.B * a.L * (CFD_LAT / 8);
     if (idx == 0) d_step[2] = 1;
     if (idx >= n8) return;

@@ -57,15 +57,34 @@ def shard_modality_weights(modality_weights, start, stop, total):
     return modality_weights
 
 
+def shard_tie(tie, start, stop, total):
+    """The rows [start, stop) of a tie table [total, L] (``sampler.check_tie``) for a rank that runs those rows alone, renumbered to the
+    slice (entry v >= 0 becomes v - start * L).  Ties cross rows and shards do not talk: a tied token of the slice whose source lies in
+    another rank's rows raises ValueError."""
+    if tuple(tie.shape[:1]) != (total,) or tie.dim() != 2:
+        raise ValueError(f"tie has shape {list(tie.shape)} for {total} utterances: it must be [total, L]")
+    L = int(tie.shape[1])
+    local = tie[start:stop].to(torch.int64)
+    tied = local >= 0
+    outside = tied & ((local < start * L) | (local >= stop * L))
+    if bool(outside.any()):
+        b, l = (int(v) for v in torch.nonzero(outside)[0])
+        raise ValueError(f"tie[{start + b}][{l}] = {int(local[b, l])} crosses this rank's rows [{start}, {stop}): a tie must stay inside one "
+                         "rank's slice (shards do not communicate)")
+    return torch.where(tied, local - start * L, local).to(tie.dtype)
+
+
 def sample_sharded(sample_fn, encoder_hidden_states, cond_masks, total_utterances, chunks=7, group=None, modality_weights=None,
-                   source_latents=None, keep_mask=None):
+                   source_latents=None, keep_mask=None, tie=None):
     """Run ``sample_fn(enc_shard, masks_shard, B=<local>, first_utterance=<global id>)`` on this rank's
     utterances and return the gathered latents [total, L, 128] on every rank.  A ``sample_fn`` with ``operands="auto"`` decides PER RANK:
     each rank's census sees its own utterances only, so one rank may fall back to ``operands=0`` while another keeps the default policy
     (each shard's result is still bit for bit one of the two policies' for its utterances); no decision is all-reduced.
     ``modality_weights`` (optional): per-modality guidance weights of the whole batch; ``sample_fn`` then also gets
     ``modality_weights=`` with this rank's utterances (``shard_modality_weights``).  ``source_latents`` [total, L, 128] / ``keep_mask``
-    [total, L] (optional, an edit run): ``sample_fn`` gets this rank's rows of each under the same names."""
+    [total, L] (optional, an edit run): ``sample_fn`` gets this rank's rows of each under the same names.  ``tie`` [total, L] (optional,
+    a tied run): ``sample_fn`` gets ``tie=`` with this rank's rows renumbered to its slice (``shard_tie``); a tie that crosses the slice is
+    refused -- keep the rows that are tied to each other (the windows of one utterance) on one rank."""
     ws = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     a, b = shard_range(total_utterances, rank, ws)
@@ -79,5 +98,7 @@ def sample_sharded(sample_fn, encoder_hidden_states, cond_masks, total_utterance
             if t.shape[0] != total_utterances:
                 raise ValueError(f"{name} has {t.shape[0]} rows for {total_utterances} utterances")
             extra[name] = t[a:b]
+    if tie is not None:
+        extra["tie"] = shard_tie(tie, a, b, total_utterances)
     local = sample_fn(enc, masks, B=b - a, first_utterance=a, **extra)
     return gather_latents(local, total_utterances, group)

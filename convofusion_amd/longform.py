@@ -1,0 +1,173 @@
+"""Long-form synthesis with the fused loop: the half-overlapping 128-frame windows of an utterance as rows of ONE tied run
+(``SamplingRun(tie=)``, cfd_sample_begin_tied).
+
+The reference makes a motion longer than one window with its rollout (unbounded_synthesis.py:244-512): 2 * parts - 1 half-overlapping
+windows, one full sampling run after another, each in-painting its first 8 tokens (``preseq``) from the finished last 8 of the window
+before.  Here all windows of an utterance are rows of one batch at the same noise level, and the first half of window w is *tied* to the
+second half of window w - 1: at the start of every iteration (and once more after the last) those tokens take the value the previous
+window's tokens have at that moment.  The tie is causal -- window w - 1 never reads window w -- and replaces the tokens rather than
+averaging them: the synchronous form of the rollout's ``preseq`` in-painting (batched long-form schemes of this kind: PriorMDM's
+DoubleTake for motion, Gen-L-Video for video).  It is NOT a reference feature, and whether tied windows look right under a trained
+checkpoint is not measured here: the weights of the tests are seeded.
+
+Rows are ordered utterance-major: row u * W + w is window w of utterance u, and that global index is also the row's Philox stream, so a
+window draws the same noise whichever run it lands in.  The loop's 16 tokens are 8 time chunks x {body, hands} (token 2c + p,
+``convofusion_amd.edit``): the first L / 2 tokens of a window are its first 4 chunks (64 frames), body and hands.
+
+Grouping (``max_rows``) is part of the call's meaning, not a tuning knob.  Windows that share a run are tied (both still noisy, denoised
+together); the first window of a later run *keeps* its first half from the finished second half of the window before it, re-noised every
+iteration through the edit instance's ``keep`` / ``source`` -- the reference's ``preseq`` in-painting per row, without the rollout's
+noise-aliasing quirk.  One run of all windows is the tied scheme, runs of one window are a rollout in the reference's manner, anything
+between mixes the two, and the three give different motions.
+"""
+import inspect
+
+import torch
+
+from .distributed import shard_cfg_batch, shard_modality_weights
+from .edit import loop_to_vae
+from .sampler import CFG_CHUNKS, check_operands, sample
+
+WINDOW_FRAMES = 128     # unbounded_synthesis.py:272 (motion_len)
+
+
+def window_ties(n_utterances, n_windows, L=16):
+    """The tie table [U * W, L] (int32) of U utterances x W half-overlapping windows: token l < L / 2 of row u * W + w, w > 0, is tied to
+    token l + L / 2 of row u * W + w - 1; every other entry is -1 (W = 1: all of them)."""
+    U, W, L = int(n_utterances), int(n_windows), int(L)
+    if U < 1 or W < 1 or L < 2 or L % 2:
+        raise ValueError(f"window_ties: need n_utterances >= 1, n_windows >= 1 and an even L >= 2 (got {U}, {W}, {L})")
+    tie = torch.full((U, W, L), -1, dtype=torch.int32)
+    rows = torch.arange(U * W, dtype=torch.int32).reshape(U, W)
+    half = torch.arange(L // 2, dtype=torch.int32)
+    tie[:, 1:, :L // 2] = (rows[:, :-1, None] * L + half + L // 2)
+    return tie.reshape(U * W, L)
+
+
+def window_groups(n_utterances, n_windows, max_rows=None):
+    """The runs of a long-form synthesis as half-open ranges [start, stop) of global rows (row u * W + w), each contiguous so that the run's
+    ``first_utterance`` = start gives every row its global Philox stream.  max_rows None or >= U * W: one run.  max_rows >= W: whole
+    utterances, max_rows // W of them per run (utterances are independent: nothing is carried).  max_rows < W: every utterance on its own,
+    in groups of max_rows consecutive windows (the first window of a later group keeps its first half from the group before)."""
+    U, W = int(n_utterances), int(n_windows)
+    if max_rows is None or int(max_rows) >= U * W:
+        return [(0, U * W)]
+    m = int(max_rows)
+    if m < 1:
+        raise ValueError(f"max_rows = {max_rows!r} must be at least 1")
+    if m >= W:
+        k = m // W
+        return [(u * W, min(u + k, U) * W) for u in range(0, U, k)]
+    return [(u * W + w, u * W + min(w + m, W)) for u in range(U) for w in range(0, W, m)]
+
+
+def group_ties(start, stop, n_windows, L=16):
+    """The tie table [stop - start, L] of the run over global rows [start, stop), numbered inside the run, and the bool [stop - start, L]
+    mask of the tokens whose source window lies before the run: those are kept from the finished window instead (``synthesize_latents``)."""
+    rows = torch.arange(start, stop)
+    tie = torch.full((stop - start, L), -1, dtype=torch.int32)
+    carried = torch.zeros((stop - start, L), dtype=torch.bool)
+    later = rows % n_windows > 0
+    inside = later & (rows - 1 >= start)
+    half = torch.arange(L // 2)
+    tie[inside, :L // 2] = ((rows[inside] - 1 - start)[:, None] * L + half + L // 2).to(torch.int32)
+    carried[later & ~inside, :L // 2] = True
+    return tie, carried
+
+
+def stitch_tokens(windows):
+    """[U, W, L, 128] windows -> the token sequence [U, (W + 1) * L / 2, 128]: window 0 whole, then every later window's second half
+    (token t of the sequence is token t of window 0 for t < L, else token L / 2 + (t - L) % (L / 2) of window 1 + (t - L) // (L / 2))."""
+    U, W, L, D = windows.shape
+    return torch.cat([windows[:, 0], windows[:, 1:, L // 2:].reshape(U, (W - 1) * (L // 2), D)], dim=1)
+
+
+def synthesize_latents(model_or_denoiser, scheduler, encoder_hidden_states, cond_masks=None, *, n_utterances, n_windows, L=16,
+                       num_inference_steps=1000, guidance_scale=7.5, guidance_chunks=CFG_CHUNKS, eta=0.0, seed=0, max_rows=None,
+                       carry=None, skip_zero_weight_chunks=True, operands=None, modality_weights=None):
+    """The latents of U = n_utterances motions of W = n_windows half-overlapping windows each.  ``model_or_denoiser``: the HIP ``Denoiser``
+    or an object with a ``.denoiser``.  encoder_hidden_states / cond_masks: the guidance batch of ``sample`` for B = U * W rows in the
+    order u * W + w (chunk-major, G * B rows per memory), every row conditioned on its own window of the audio and text as the caller
+    sliced them (the reference's per-window data work, unbounded_synthesis.py:290-330).  modality_weights: as in ``sample`` over those rows.
+    Noise: Philox with ``seed``, row u * W + w on stream u * W + w.
+    max_rows: the most rows one run may have (``window_groups``); windows of one run are tied, a later run's first window keeps its first
+    half from the finished window before it -- the grouping changes the result.  carry [U, L / 2, 128] (optional): the finished second half
+    of the window before window 0 of every utterance (streaming: the previous call's ``windows[:, -1, L // 2:]``); window 0 then keeps
+    its first half from it in the same way.
+    Returns (windows [U, W, L, 128], sequence [U, (W + 1) * L / 2, 128] = ``stitch_tokens(windows)``)."""
+    denoiser = getattr(model_or_denoiser, "denoiser", model_or_denoiser)
+    U, W, L = int(n_utterances), int(n_windows), int(L)
+    B, G = U * W, int(guidance_chunks)
+    window_ties(U, W, L)      # (checks U, W, L)
+    if encoder_hidden_states[0].shape[0] != G * B:
+        raise ValueError(f"the guidance batch has {encoder_hidden_states[0].shape[0]} rows for {U} utterances x {W} windows and {G} chunks")
+    if carry is not None and tuple(carry.shape) != (U, L // 2, 128):
+        raise ValueError(f"carry must be [U, L / 2, 128] = [{U}, {L // 2}, 128], not {list(carry.shape)}")
+    operands = check_operands(operands)
+    dev = encoder_hidden_states[0].device
+    out = torch.empty((B, L, 128), dtype=torch.float32, device=dev)
+    for start, stop in window_groups(U, W, max_rows):
+        n = stop - start
+        tie, carried = group_ties(start, stop, W, L)
+        src = keep = None
+        for b in range(n):
+            u, w = divmod(start + b, W)
+            prev = out[start + b - 1, L // 2:] if carried[b].any() else (carry[u] if carry is not None and w == 0 else None)
+            if prev is None:
+                continue
+            if src is None:
+                src = torch.zeros((n, L, 128), dtype=torch.float32, device=dev)
+                keep = torch.zeros((n, L), dtype=torch.bool, device=dev)
+            src[b, :L // 2] = prev.to(device=dev, dtype=torch.float32)
+            keep[b, :L // 2] = True
+        enc = [shard_cfg_batch(m, start, stop, B, G) for m in encoder_hidden_states]
+        masks = {k: shard_cfg_batch(v, start, stop, B, G) for k, v in (cond_masks or {}).items()}
+        out[start:stop] = sample(denoiser, scheduler, enc, masks, B=n, L=L, num_inference_steps=num_inference_steps,
+                                 guidance_scale=guidance_scale, guidance_chunks=G, eta=eta, seed=seed, first_utterance=start,
+                                 skip_zero_weight_chunks=skip_zero_weight_chunks, operands=operands,
+                                 modality_weights=shard_modality_weights(modality_weights, start, stop, B), source_latents=src,
+                                 keep_mask=keep, tie=tie.to(dev) if bool((tie >= 0).any()) else None)
+    windows = out.reshape(U, W, L, 128)
+    return windows, stitch_tokens(windows)
+
+
+def stitch_frames(feats):
+    """[U, W, F, nfeats] decoded windows -> [U, (W + 1) * F / 2, nfeats], the reference's frame stitching (unbounded_synthesis.py:460-468):
+    window 0 whole; every later window has its root x / z translation (features 0 and 2) moved so that its first frame sits where the
+    first frame of the previous (already moved) window's second half does, and contributes its second half."""
+    U, W, F, _ = feats.shape
+    xz = torch.tensor([1.0, 0.0, 1.0], dtype=feats.dtype, device=feats.device)
+    pieces = [feats[:, 0]]
+    prev = feats[:, 0, F // 2:]
+    for w in range(1, W):
+        f = feats[:, w].clone()
+        f[:, :, :3] = f[:, :, :3] - f[:, :1, :3] * xz
+        f[:, :, :3] = f[:, :, :3] + prev[:, :1, :3] * xz
+        prev = f[:, F // 2:]
+        pieces.append(prev)
+    return torch.cat(pieces, dim=1)
+
+
+def synthesize_motion(model, encoder_hidden_states, cond_masks=None, *, n_utterances, n_windows, seed=0, max_rows=None, carry=None,
+                      modality_weights=None, operands=None):
+    """Long-form motions from a Convofusion-like ``model`` (reads vae / denoiser / scheduler / cfg / guidance_scale / clf_guidance_drops /
+    do_classifier_free_guidance as ``edit.edit_motion`` does; ``model.vae`` decodes on the HIP path): ``synthesize_latents``, one HIP
+    ``decode`` of all U * W windows, the reference's frame stitching (``stitch_frames``) in torch on the device.
+    Returns (features [U, (W + 1) * 64, nfeats], windows [U, W, L, 128], token sequence [U, (W + 1) * L / 2, 128])."""
+    if not model.do_classifier_free_guidance:
+        raise NameError("guidance_bs_mulitplier: the reference loop requires classifier-free guidance")
+    U, W = int(n_utterances), int(n_windows)
+    sch = model.scheduler
+    eta = 0.0
+    if "eta" in set(inspect.signature(sch.step).parameters.keys()):          # convofusion.py:427-429
+        eta = model.cfg.model.scheduler.eta
+    if modality_weights is None:
+        modality_weights = getattr(model, "_cfd_modality_weights", None)
+    L = WINDOW_FRAMES // 8
+    windows, tokens = synthesize_latents(
+        model.denoiser, sch, encoder_hidden_states, cond_masks, n_utterances=U, n_windows=W, L=L,
+        num_inference_steps=model.cfg.model.scheduler.num_inference_timesteps, guidance_scale=model.guidance_scale,
+        guidance_chunks=model.clf_guidance_drops + 1, eta=eta, seed=seed, max_rows=max_rows, carry=carry,
+        operands=getattr(model, "_cfd_operands", None) if operands is None else operands, modality_weights=modality_weights)
+    feats = model.vae.decode(loop_to_vae(windows.reshape(U * W, L, 128)), [WINDOW_FRAMES] * (U * W))
+    return stitch_frames(feats.reshape(U, W, WINDOW_FRAMES, feats.shape[-1])), windows, tokens

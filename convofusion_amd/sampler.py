@@ -195,6 +195,52 @@ def check_anchor(trajectory, keep_mask, B, L, N, device=None):
     return traj, keep
 
 
+def check_tie(tie, keep_mask, B, L, device=None, *, preseq=None, strength=1.0, scheduler_kind=None, anchored=False, dynamic_memories=()):
+    """The tie table of a tied run (``SamplingRun(tie=)``, cfd_sample_begin_tied): None when the run has none, else the table as int32
+    [B, L] contiguous on ``device``.  Entry [b, l] is -1 (a free token) or the flat index b' * L + l' of the token whose value token (b, l)
+    takes at the start of every iteration and once more after the last.  Refusals (ValueError), each before any device work and each
+    naming the first offending (b, l): a table other than an integer [B, L] tensor, an entry outside [-1, B * L), a token tied to itself, a
+    source that is itself tied (no chains, so no cycles), a source that ``keep_mask`` keeps, a token both kept and tied; and the runs that
+    take no ties: preseq, strength < 1, DDIM inversion (scheduler kind 3), an anchored run, dynamic memories (dyadic runs)."""
+    if tie is None:
+        return None
+    if scheduler_kind == 3:
+        raise ValueError("tie: a DDIM inversion run (DDIMInverseScheduler) takes no tied tokens")
+    if anchored:
+        raise ValueError("tie: an anchored run (anchor_trajectory) takes no tied tokens")
+    if preseq is not None:
+        raise ValueError("tie: preseq (the rollout's prefix in-painting) and tied tokens do not go together: give the prefix as kept "
+                         "tokens (source_latents / keep_mask)")
+    if float(strength) != 1.0:
+        raise ValueError(f"tie: a tied run starts at iteration 0 (strength = {strength!r} is not 1)")
+    if dynamic_memories:
+        raise ValueError("tie: a run with dynamic memories (a dyadic run) takes no tied tokens")
+    if not isinstance(tie, torch.Tensor) or tie.is_floating_point() or tie.is_complex() or tie.dtype == torch.bool:
+        raise ValueError("tie must be an integer tensor [B, L] (-1, or the flat index b' * L + l' of the source token)")
+    if tuple(tie.shape) != (B, L):
+        raise ValueError(f"tie must be [B, L] = [{B}, {L}], not {list(tie.shape)}")
+    t = tie.detach().to("cpu", torch.int64).reshape(-1)
+    keep = None
+    if keep_mask is not None:
+        if not isinstance(keep_mask, torch.Tensor) or tuple(keep_mask.shape) != (B, L):
+            raise ValueError(f"keep_mask must be a tensor [B, L] = [{B}, {L}]")
+        keep = (keep_mask.detach().to("cpu") != 0).reshape(-1)
+    n = B * L
+    for e in torch.nonzero(t != -1).reshape(-1).tolist():
+        v, b, l = int(t[e]), e // L, e % L
+        if v < -1 or v >= n:
+            raise ValueError(f"tie[{b}][{l}] = {v} is not -1 or a token in [0, {n})")
+        if v == e:
+            raise ValueError(f"tie[{b}][{l}] = {v} ties the token to itself")
+        if int(t[v]) != -1:
+            raise ValueError(f"tie[{b}][{l}] = {v} names a source ({v // L}, {v % L}) that is itself tied (no chains)")
+        if keep is not None and bool(keep[v]):
+            raise ValueError(f"tie[{b}][{l}] = {v} names a source ({v // L}, {v % L}) that keep_mask keeps (a source must be free)")
+        if keep is not None and bool(keep[e]):
+            raise ValueError(f"token ({b}, {l}) is both kept (keep_mask) and tied")
+    return tie.detach().to(device=device, dtype=torch.int32).contiguous()
+
+
 class CensusTripped(Exception):
     """Raised inside an ``operands="auto"`` run when its census counts a row above the threshold (caught by the loop entry points)."""
 
@@ -330,7 +376,7 @@ class SamplingRun:
                  seed=0, first_utterance=0, preseq=None, dedup=True, skip_zero_weight_chunks=False, row_maps=None,
                  dynamic_memories=(), side_engine=False, attention_ring=False, operands=None, census_tau=None, modality_weights=None,
                  prune_zero_weight_chunks=True, source_latents=None, keep_mask=None, strength=1.0, trajectory=False,
-                 anchor_trajectory=None):
+                 anchor_trajectory=None, tie=None):
         """attention_ring: keep the attention maps of the full-conditioning chunk of EVERY iteration (the reference's per-iteration dict,
         convofusion.py:517-523): the captured iteration stores them into ``self.att_ring`` -- five tensors [iterations, B, layers, L, S_j]
         -- with no extra forward and no host round trip (cfd_sample_args.att_ring: the row-tile kernels store them from their second
@@ -364,7 +410,12 @@ class SamplingRun:
         anchor_trajectory / keep_mask (DDIMScheduler, eta 0, no clipping): a re-conditioning run over a recorded inversion trajectory
         (cfd_sample_begin_anchored, ``check_anchor``): at the start of iteration i the tokens with keep_mask = 1 are set to
         anchor_trajectory[N - i], the inverted latents at the level the iteration starts from.  The trajectory is read in place: the run
-        keeps a reference to it."""
+        keeps a reference to it.
+        tie: a tied run (cfd_sample_begin_tied, ``check_tie``; ``convofusion_amd.longform``): int tensor [B, L], -1 or the flat index
+        b' * L + l' of the token that token (b, l) copies at the start of every iteration (the source as the previous iteration left it)
+        and once more after the last one: ``read()`` of the finished run has every tied token bit-identical to its source, ``read()``
+        before that the latents as the scheduler left them.  Goes with source_latents / keep_mask at strength 1, modality_weights, the
+        attention ring and every scheduler but the inverse one; ``write`` (WEG) is refused.  None: the run's usual entry point."""
         if not isinstance(denoiser, Denoiser):
             raise TypeError("denoiser must be a convofusion_amd.denoiser.Denoiser")
         dev = encoder_hidden_states[0].device
@@ -395,6 +446,8 @@ class SamplingRun:
                 raise ValueError("an anchored run takes no source_latents, strength or preseq (its kept tokens come from the trajectory)")
             anchor = check_anchor(anchor_trajectory, keep_mask, B, L, n_full, dev)
             keep_mask = None
+        self.tie = check_tie(tie, keep_mask, B, L, dev, preseq=preseq, strength=strength, scheduler_kind=scheduler.KIND,
+                             anchored=anchor_trajectory is not None, dynamic_memories=dynamic_memories)
         edit = check_edit(source_latents, keep_mask, strength, B, L, n_full, preseq, dev)
         self.first_iteration = edit[2] if edit is not None else 0
         self.timesteps = [int(t) for t in table][self.first_iteration:]
@@ -484,7 +537,20 @@ class SamplingRun:
         with torch.cuda.device(dev):
             torch.cuda.current_stream(dev).synchronize()
             w_ptr = self.modality_weights.ctypes.data_as(C.c_void_p) if self.modality_weights is not None else None
-            if self.trajectory is not None or anchor is not None:
+            if self.tie is not None:
+                ta = _lib.TieArgs()
+                ta.tie = self.tie.data_ptr()
+                e = None
+                if edit is not None:
+                    e = _lib.EditArgs()
+                    e.source, e.keep, e.first_iteration = edit[0].data_ptr(), (edit[1].data_ptr() if edit[1] is not None else None), edit[2]
+                    self._keep += [edit[0], edit[1], e]
+                self._keep.append(ta)
+                g_eval = C.c_int(0)
+                _lib.check(self.lib.cfd_sample_begin_tied(self.handle, C.byref(a), C.byref(e) if e is not None else None, C.byref(ta), w_ptr,
+                                                          1 if prune_zero_weight_chunks else 0, C.byref(g_eval), C.c_void_p(stream)))
+                self.chunks_evaluated = int(g_eval.value)
+            elif self.trajectory is not None or anchor is not None:
                 g_eval = C.c_int(0)
                 if self.trajectory is not None:
                     _lib.check(self.lib.cfd_sample_begin_invert(self.handle, C.byref(a), C.c_void_p(self.trajectory.data_ptr()), w_ptr,
@@ -571,6 +637,8 @@ class SamplingRun:
 
     def write(self, latents):
         """Overwrite the current latents of the open run (the WEG update between two iterations)."""
+        if self.tie is not None:
+            raise ValueError("a tied run takes no WEG update (write): its tied tokens are overwritten from their sources every iteration")
         if tuple(latents.shape) != (self.B, self.L, 128):
             raise ValueError(f"latents must be [{self.B}, {self.L}, 128]")
         lat = latents.detach().to(device=self.device, dtype=torch.float32).contiguous()
@@ -680,7 +748,8 @@ def _open_run(denoiser, scheduler, encoder_hidden_states, cond_masks, B, L, num_
 def sample(denoiser, scheduler, encoder_hidden_states, cond_masks=None, *, B, L=16, num_inference_steps=1000,
            guidance_scale=7.5, guidance_chunks=CFG_CHUNKS, eta=0.0, init_latents=None, step_noise=None, seed=0,
            first_utterance=0, preseq=None, dedup=True, skip_zero_weight_chunks=False, row_maps=None, return_attention=False, operands=None,
-           modality_weights=None, prune_zero_weight_chunks=True, source_latents=None, keep_mask=None, strength=1.0, anchor_trajectory=None):
+           modality_weights=None, prune_zero_weight_chunks=True, source_latents=None, keep_mask=None, strength=1.0, anchor_trajectory=None,
+           tie=None):
     """Run the whole loop; returns latents [B, L, 128] (batch-first); with ``return_attention=True`` also the last
     iteration's attention maps (``last_step_attention``), with ``return_attention="all"`` a dict {timestep: maps} over every
     iteration like the reference's: kept by the captured iteration itself (``SamplingRun(attention_ring=True)``) while the ring fits
@@ -694,7 +763,8 @@ def sample(denoiser, scheduler, encoder_hidden_states, cond_masks=None, *, B, L=
     ``source_latents`` / ``keep_mask`` / ``strength``: an edit run (token-masked in-painting, img2img strength), as in ``SamplingRun``; the
     attention dict then holds the executed iterations.  ``anchor_trajectory`` / ``keep_mask``: a re-conditioning run over a recorded DDIM
     inversion (``invert``), as in ``SamplingRun``.  With a ``DDIMInverseScheduler`` and ``init_latents`` = the source the loop is a DDIM
-    inversion: the same latents as ``invert`` with the same guidance."""
+    inversion: the same latents as ``invert`` with the same guidance.  ``tie``: tied tokens (int [B, L], ``check_tie``), as in ``SamplingRun``;
+    None changes nothing."""
     if check_operands(operands) == "auto":
         args = dict(locals())
         return _with_auto_operands(lambda ops: sample(**dict(args, operands=ops)), "auto")
@@ -702,7 +772,8 @@ def sample(denoiser, scheduler, encoder_hidden_states, cond_masks=None, *, B, L=
                     guidance_scale=guidance_scale, guidance_chunks=guidance_chunks, eta=eta, init_latents=init_latents, step_noise=step_noise,
                     seed=seed, first_utterance=first_utterance, preseq=preseq, dedup=dedup, skip_zero_weight_chunks=skip_zero_weight_chunks,
                     row_maps=row_maps, operands=operands, modality_weights=modality_weights, prune_zero_weight_chunks=prune_zero_weight_chunks,
-                    source_latents=source_latents, keep_mask=keep_mask, strength=strength, anchor_trajectory=anchor_trajectory)
+                    source_latents=source_latents, keep_mask=keep_mask, strength=strength, anchor_trajectory=anchor_trajectory,
+                    **({} if tie is None else dict(tie=tie)))
     try:
         if not return_attention:
             run.steps(run.N)

@@ -222,6 +222,29 @@ typedef struct {
  * an edit.  With first_iteration = 0 and keep all 0 / NULL the run computes what cfd_sample_begin(_weighted) computes, bit for bit. */
 int cfd_sample_begin_edit(cfd_handle h, const cfd_sample_args* args, const cfd_edit_args* e, const float* weights, int prune,
                           int* chunks_evaluated, void* stream);
+/* Tied tokens: a token of the run that takes its value from another token of the same run in every iteration.  Long-form synthesis runs
+ * the half-overlapping 128-frame windows of an utterance as rows of one batch at the same noise level and ties the first half of window w
+ * to the second half of window w - 1 (the synchronous form of the reference rollout's preseq in-painting). */
+typedef struct {
+  const int32_t* tie;         /* dev [B][L] int32: -1 (a free token) or the flat index b' * L + l' of the token's source in the same run.
+                                 At the start of every iteration, before the replication into the denoiser's input,
+                                 latents[b][l] = latents[b'][l'] -- the source as the previous iteration's scheduler step left it (at
+                                 iteration 0: its initial noise) -- and once more after the last iteration, so that cfd_sample_read of a
+                                 finished run returns every tied token bit-identical to its source; a read before that returns the
+                                 latents as the scheduler step left them.  cfd_sample_inpaint does the copy (and an edit's overwrite)
+                                 ahead of the captured iteration.  A source must be free: not tied itself (no chains, no cycles, no
+                                 self-tie) and not kept by the edit, so no launch reads a token it writes.  Copied at begin (and checked
+                                 on the host copy): the run does not read the caller's table afterwards. */
+} cfd_tie_args;
+/* cfd_sample_begin_edit (edit != NULL: its kept tokens next to the tied ones; first_iteration must be 0) or cfd_sample_begin /
+ * cfd_sample_begin_weighted (edit == NULL: no kept token, no source needed) for a tied run; weights / prune / chunks_evaluated as in
+ * cfd_sample_begin_edit.  Schedulers 0, 1 and 2, with or without att_ring, either operand policy.  With a table of -1 throughout the run
+ * computes what the same call without ties computes, bit for bit.  CFD_E_ARG, with the first offending (b, l) in cfd_last_error: an entry
+ * outside [-1, B * L), a token tied to itself, a source that is itself tied, a source that is kept, a token both kept and tied; also a NULL
+ * tie or table, a NULL edit source, first_iteration != 0 (no strength), scheduler 3 (DDIM inversion), preseq, dynamic memories (dyadic
+ * runs; cfd_dyadic_steps refuses a tied run as well).  An anchored run has no tied form. */
+int cfd_sample_begin_tied(cfd_handle h, const cfd_sample_args* args, const cfd_edit_args* edit, const cfd_tie_args* tie,
+                          const float* weights, int prune, int* chunks_evaluated, void* stream);
 /* DDIM inversion with its trajectory: cfd_sample_begin / cfd_sample_begin_weighted (weights != NULL, with `prune` and `chunks_evaluated`
  * as there; weights == NULL: the default combine, *chunks_evaluated = the evaluated chunks) for a scheduler-3 run that also records
  * `trajectory`: dev float32 [iterations + 1][B][L][128], owned by the caller and written by the run.  Slot 0 receives the initial

@@ -1,5 +1,5 @@
 """Developer tool: do the loop's existing kernel instances keep their gfx950 code?  Compares the instruction lists of begin_step_kernel,
-inpaint_now_kernel and cfg_step_kernel (default / edit / weighted instances) in two device-assembly listings of cfd_sample.hip, labels and
+inpaint_now_kernel and cfg_step_kernel (default / edit / anchored / weighted / trajectory instances) in two device-assembly listings of cfd_sample.hip, labels and
 comments aside.  A new trailing template parameter with a default changes an instance's name, not its code: the pairs below map the
 old names onto the new ones.
 
@@ -12,13 +12,18 @@ import re
 import subprocess
 import sys
 
-# (name before, name after): the instances as the parent commit names them and as the trajectory / anchored instances' commit does
-PAIRS = [("begin_step_kernel<0, false>(", "begin_step_kernel<0, false, false>("),
-         ("begin_step_kernel<0, true>(", "begin_step_kernel<0, true, false>("),
-         ("inpaint_now_kernel<0, false>(", "inpaint_now_kernel<0, false, false>("),
-         ("inpaint_now_kernel<0, true>(", "inpaint_now_kernel<0, true, false>("),
-         ("cfg_step_kernel<0, false>(", "cfg_step_kernel<0, false, false>("),
-         ("cfg_step_kernel<0, true>(", "cfg_step_kernel<0, true, false>("),
+# (name before, name after): the instances as the parent commit names them and as the tied instances' commit does (begin_step_kernel and
+# inpaint_now_kernel got a fourth parameter; the other kernels keep their names)
+PAIRS = [("begin_step_kernel<0, false, false>(", "begin_step_kernel<0, false, false, false>("),
+         ("begin_step_kernel<0, true, false>(", "begin_step_kernel<0, true, false, false>("),
+         ("begin_step_kernel<0, false, true>(", "begin_step_kernel<0, false, true, false>("),
+         ("inpaint_now_kernel<0, false, false>(", "inpaint_now_kernel<0, false, false, false>("),
+         ("inpaint_now_kernel<0, true, false>(", "inpaint_now_kernel<0, true, false, false>("),
+         ("inpaint_now_kernel<0, false, true>(", "inpaint_now_kernel<0, false, true, false>("),
+         ("cfg_step_kernel<0, false, false>(", "cfg_step_kernel<0, false, false>("),
+         ("cfg_step_kernel<0, true, false>(", "cfg_step_kernel<0, true, false>("),
+         ("cfg_step_kernel<0, false, true>(", "cfg_step_kernel<0, false, true>("),
+         ("cfg_step_kernel<0, true, true>(", "cfg_step_kernel<0, true, true>("),
          ("edit_init_kernel<0>(", "edit_init_kernel<0>("),
          ("sched_step_kernel<0>(", "sched_step_kernel<0>(")]
 

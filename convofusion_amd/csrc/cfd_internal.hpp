@@ -173,6 +173,31 @@ struct Work {
   }
 };
 
+// The kind of the open sampling run: which instances of begin_step_kernel / inpaint_now_kernel / cfg_step_kernel it launches
+// (cfd_sample.hip: with_begin_args, enqueue_loop_iteration).  sample_begin starts every run from RunMode{}: a new field needs no reset.
+struct RunMode {
+  // Weighted run (cfd_sample_begin_weighted): the guidance weights come from Ctx::wtab instead of cfd_sample_args::guidance_weight.
+  bool weighted = false;
+  // Edit run (cfd_sample_begin_edit): the run starts at iteration k0 of the full table (d_step[0] starts there; run_pos and run_iters
+  // count executed iterations).  edit: the edit instances of begin_step_kernel / inpaint_now_kernel overwrite the tokens of ekeep
+  // [B][L] with coef[i].sa * esrc + coef[i].sb * enoise.
+  int k0 = 0;
+  bool edit = false;
+  // DDIM inversion run (scheduler kind 3) with a trajectory (cfd_sample_begin_invert): the caller's ring [iterations + 1][B][L][128]; the
+  // trajectory instance of cfg_step_kernel stores the latents after iteration i into slot i + 1.
+  float* traj = nullptr;
+  // Anchored run (cfd_sample_begin_anchored): the anchored instances of begin_step_kernel / inpaint_now_kernel set the tokens of ekeep
+  // to anchor_ring[anchor_n - i] (the caller's ring, read in place).
+  bool anchor = false;
+  const float* anchor_ring = nullptr;
+  int anchor_n = 0;
+  // Tied run (cfd_sample_begin_tied): the tied instances of begin_step_kernel / inpaint_now_kernel copy token etie[b][l] (-1: none) of
+  // the run's own latents into token (b, l) at the start of every iteration, next to the edit instance's kept tokens; tie_final: the
+  // copy after the last iteration (tie_copy_kernel, enqueued by the first cfd_sample_read that finds the run finished) has been done.
+  bool tie = false;
+  bool tie_final = false;
+};
+
 struct cfd_handle_s {
   cfd_config cfg;
   int nl = 0;
@@ -277,30 +302,12 @@ struct cfd_handle_s {
   // is unchanged (rows are independent); the guidance combine reads chunk k at its position.
   int chunk_pos[8];
   DBuf perm_map[CFD_NMEM];
-  // Weighted run (cfd_sample_begin_weighted): the guidance weights come from wtab [iterations][B][8] (indexed by the caller's chunk
-  // order) and wpos[k] is the row position of chunk k, or chunk 0's for a chunk the run does not evaluate.
-  bool run_weighted = false;
+  // The open run's mode and the buffers its instances read.  Weighted run: wtab [iterations][B][8] (indexed by the caller's chunk order);
+  // wpos[k] is the row position of chunk k, or chunk 0's for a chunk the run does not evaluate.  esrc / enoise [B][L][128]: an edit's source
+  // latents and the run's initial noise; ekeep [B][L]: the kept tokens of an edit, tied or anchored run; etie [B][L]: the tie table.
+  RunMode run;
   int wpos[8];
-  DBuf wtab;
-  // Edit run (cfd_sample_begin_edit): the run starts at iteration run_k0 of the full table (d_step[0] starts there; run_pos and run_iters
-  // count executed iterations).  run_edit: the edit instances of begin_step_kernel / inpaint_now_kernel overwrite the tokens of ekeep
-  // [B][L] with coef[i].sa * esrc + coef[i].sb * enoise ([B][L][128] each: the source latents and the run's initial noise).
-  int run_k0 = 0;
-  bool run_edit = false;
-  DBuf esrc, enoise, ekeep;
-  // DDIM inversion run (scheduler kind 3) with a trajectory (cfd_sample_begin_invert): the caller's ring [iterations + 1][B][L][128]; the
-  // trajectory instance of cfg_step_kernel stores the latents after iteration i into slot i + 1.  Anchored run (cfd_sample_begin_anchored):
-  // the anchored instances of begin_step_kernel / inpaint_now_kernel set the tokens of ekeep to anchor_ring[anchor_n - i].
-  float* run_traj = nullptr;
-  bool run_anchor = false;
-  const float* anchor_ring = nullptr;
-  int anchor_n = 0;
-  // Tied run (cfd_sample_begin_tied): the tied instances of begin_step_kernel / inpaint_now_kernel copy token etie[b][l] (-1: none) of
-  // the run's own latents into token (b, l) at the start of every iteration, next to the edit instance's kept tokens; tie_final: the
-  // copy after the last iteration (tie_copy_kernel, enqueued by the first cfd_sample_read that finds the run finished) has been done.
-  bool run_tie = false;
-  bool tie_final = false;
-  DBuf etie;
+  DBuf wtab, esrc, enoise, ekeep, etie;
   int run_pos = 0;
 };
 typedef cfd_handle_s Ctx;

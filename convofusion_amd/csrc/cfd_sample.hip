@@ -102,18 +102,37 @@ static int step_coefficients(int kind, const float* ac, int T, int n_inf, const 
 }
 
 static void (*const cfg_step_kernel_weighted)(const CfgStepArgsW) = cfg_step_kernel<0, true>;   // (one macro argument for LAUNCH)
-
-static void (*const begin_step_kernel_edit)(const BeginArgsE) = begin_step_kernel<0, true>;   // (one macro argument for LAUNCH)
-static void (*const begin_step_kernel_anchor)(const BeginArgsA) = begin_step_kernel<0, false, true>;
-static void (*const begin_step_kernel_tied)(const BeginArgsT) = begin_step_kernel<0, true, false, true>;
 static void (*const cfg_step_kernel_traj)(const CfgStepArgsT<CfgStepArgs>) = cfg_step_kernel<0, false, true>;
 static void (*const cfg_step_kernel_weighted_traj)(const CfgStepArgsT<CfgStepArgsW>) = cfg_step_kernel<0, true, true>;
 
-static BeginArgsE edit_begin_args(Ctx* c) {
+// The instances of begin_step_kernel / inpaint_now_kernel that take the argument struct Args (rows.hpp: BeginArgsOf, the other way round)
+template <class Args>
+struct BeginInst {
+  static constexpr bool EDIT = std::is_base_of<BeginArgsE, Args>::value, ANCHOR = std::is_same<Args, BeginArgsA>::value,
+                        TIE = std::is_same<Args, BeginArgsT>::value;
+  static_assert(std::is_same<Args, BeginArgsOf<EDIT, ANCHOR, TIE>>::value, "not an argument struct of begin_step_kernel");
+  static constexpr auto begin_step = begin_step_kernel<0, EDIT, ANCHOR, TIE>;
+  static constexpr auto inpaint_now = inpaint_now_kernel<0, EDIT, ANCHOR, TIE>;
+};
+
+// What every instance's arguments start with (preseq / inoise / pl are the default instance's alone: default_begin_args)
+static BeginArgs base_begin_args(Ctx* c) {
   const cfd_sample_args& s = c->sargs;
+  return BeginArgs{c->latents.as<float>(), c->w->sample_sp.as<char>(), s.B, s.L, s.G, nullptr, nullptr, 0, c->coef.as<StepCoef>(),
+                   c->w->d_step.as<int>()};
+}
+
+static BeginArgs default_begin_args(Ctx* c) {
+  BeginArgs ba = base_begin_args(c);
+  ba.preseq = c->sargs.preseq;
+  ba.inoise = c->inoise.as<float>();
+  ba.pl = c->sargs.preseq_len;
+  return ba;
+}
+
+static BeginArgsE edit_begin_args(Ctx* c) {
   BeginArgsE be;
-  static_cast<BeginArgs&>(be) = BeginArgs{c->latents.as<float>(), c->w->sample_sp.as<char>(), s.B, s.L, s.G, nullptr, nullptr, 0,
-                                          c->coef.as<StepCoef>(), c->w->d_step.as<int>()};
+  static_cast<BeginArgs&>(be) = base_begin_args(c);
   be.keep = c->ekeep.as<uint8_t>();
   be.src = c->esrc.as<float>();
   be.eps = c->enoise.as<float>();
@@ -128,64 +147,63 @@ static BeginArgsT tied_begin_args(Ctx* c) {
 }
 
 static BeginArgsA anchor_begin_args(Ctx* c) {
-  const cfd_sample_args& s = c->sargs;
   BeginArgsA ba;
-  static_cast<BeginArgs&>(ba) = BeginArgs{c->latents.as<float>(), c->w->sample_sp.as<char>(), s.B, s.L, s.G, nullptr, nullptr, 0,
-                                          c->coef.as<StepCoef>(), c->w->d_step.as<int>()};
+  static_cast<BeginArgs&>(ba) = base_begin_args(c);
   ba.keep = c->ekeep.as<uint8_t>();
-  ba.ring = c->anchor_ring;
-  ba.slot = (long long)s.B * s.L * CFD_LAT;
-  ba.n = c->anchor_n;
+  ba.ring = c->run.anchor_ring;
+  ba.slot = (long long)c->sargs.B * c->sargs.L * CFD_LAT;
+  ba.n = c->run.anchor_n;
   return ba;
+}
+
+// Which overwrite the open run does at the start of an iteration: f(that instance's arguments), the instance being BeginInst<> of their
+// type.  The one place that maps RunMode to an instance of begin_step_kernel / inpaint_now_kernel.
+template <class F>
+static int with_begin_args(Ctx* c, F&& f) {
+  if (c->run.tie) return f(tied_begin_args(c));      // the tied and the kept tokens
+  if (c->run.edit) return f(edit_begin_args(c));     // the kept tokens, re-noised from the source
+  if (c->run.anchor) return f(anchor_begin_args(c)); // the kept tokens, from the trajectory
+  return f(default_begin_args(c));                   // the first preseq_len tokens, if the run has a preseq
+}
+
+template <class Args>   // the trajectory instance's arguments: those of the instance without, and the ring
+static CfgStepArgsT<Args> with_traj(const Args& a, float* traj) {
+  CfgStepArgsT<Args> t;
+  static_cast<Args&>(t) = a;
+  t.traj = traj;
+  return t;
 }
 
 static int enqueue_loop_iteration(Ctx* c, hipStream_t st) {
   const cfd_sample_args& s = c->sargs;
+  const RunMode& m = c->run;
   const long long n8 = (long long)s.B * s.L * (CFD_LAT / 8);
-  if (c->run_tie) {
-    LAUNCH(CFD_PROF_OTHER, begin_step_kernel_tied, dim3((unsigned)((n8 + 255) / 256)), dim3(256), st, tied_begin_args(c));
-  } else if (c->run_edit) {
-    LAUNCH(CFD_PROF_OTHER, begin_step_kernel_edit, dim3((unsigned)((n8 + 255) / 256)), dim3(256), st, edit_begin_args(c));
-  } else if (c->run_anchor) {
-    LAUNCH(CFD_PROF_OTHER, begin_step_kernel_anchor, dim3((unsigned)((n8 + 255) / 256)), dim3(256), st, anchor_begin_args(c));
-  } else {
-    BeginArgs ba{c->latents.as<float>(), c->w->sample_sp.as<char>(), s.B, s.L, s.G, s.preseq, c->inoise.as<float>(), s.preseq_len,
-                 c->coef.as<StepCoef>(), c->w->d_step.as<int>()};
-    LAUNCH(CFD_PROF_OTHER, begin_step_kernel<>, dim3((unsigned)((n8 + 255) / 256)), dim3(256), st, ba);
-  }
+  CHK(with_begin_args(c, [&](auto a) {
+    using I = BeginInst<decltype(a)>;
+    LAUNCH(CFD_PROF_OTHER, I::begin_step, dim3((unsigned)((n8 + 255) / 256)), dim3(256), st, a);
+    return (int)CFD_OK;
+  }));
   CHK(enqueue_denoise(c, st));
-  CfgStepArgs ca;
-  memset(&ca, 0, sizeof(ca));
-  ca.eps = c->w->eps.as<float>(); ca.latents = c->latents.as<float>(); ca.B = s.B; ca.L = s.L; ca.G = s.G;
-  for (int k = 0; k < 8; ++k) { ca.w[k] = s.guidance_weight[k]; ca.pos[k] = c->chunk_pos[k]; }
-  ca.kind = s.scheduler; ca.clip = s.clip_sample; ca.hist = c->hist.as<float>(); ca.coef = c->coef.as<StepCoef>(); ca.d_step = c->w->d_step.as<int>();
-  ca.noise = s.step_noise; ca.seed = s.seed; ca.utt0 = s.first_utterance;
-  const long long n4 = (long long)s.B * s.L * CFD_LAT / 4;
-  ca.advance = c->w->d_step.as<int>();   // the last workgroup of cfg_step_kernel advances the loop index
-  if (c->run_weighted) {   // the caller's 7 chunks, weights from the run's table (those of a chunk it does not evaluate are all 0)
-    CfgStepArgsW cw;
-    static_cast<CfgStepArgs&>(cw) = ca;
+  CfgStepArgsW cw;   // (the default instance takes its CfgStepArgs part)
+  memset(&cw, 0, sizeof(cw));
+  cw.eps = c->w->eps.as<float>(); cw.latents = c->latents.as<float>(); cw.B = s.B; cw.L = s.L; cw.G = s.G;
+  for (int k = 0; k < 8; ++k) { cw.w[k] = s.guidance_weight[k]; cw.pos[k] = c->chunk_pos[k]; }
+  cw.kind = s.scheduler; cw.clip = s.clip_sample; cw.hist = c->hist.as<float>(); cw.coef = c->coef.as<StepCoef>(); cw.d_step = c->w->d_step.as<int>();
+  cw.noise = s.step_noise; cw.seed = s.seed; cw.utt0 = s.first_utterance;
+  cw.advance = c->w->d_step.as<int>();   // the last workgroup of cfg_step_kernel advances the loop index
+  if (m.weighted) {   // the caller's 7 chunks, weights from the run's table (those of a chunk it does not evaluate are all 0)
     cw.G = 7;
     for (int k = 0; k < 8; ++k) cw.pos[k] = c->wpos[k];
     cw.wtab = c->wtab.as<float>();
-    if (c->run_traj) {
-      CfgStepArgsT<CfgStepArgsW> ct;
-      static_cast<CfgStepArgsW&>(ct) = cw;
-      ct.traj = c->run_traj;
-      LAUNCH(CFD_PROF_OTHER, cfg_step_kernel_weighted_traj, dim3((unsigned)std::min<long long>((n4 + 255) / 256, 256)), dim3(256), st, ct);
-      return CFD_OK;
-    }
-    LAUNCH(CFD_PROF_OTHER, cfg_step_kernel_weighted, dim3((unsigned)std::min<long long>((n4 + 255) / 256, 256)), dim3(256), st, cw);
-    return CFD_OK;
   }
-  if (c->run_traj) {   // (an inversion run recording its trajectory: the step also stores into slot *d_step + 1)
-    CfgStepArgsT<CfgStepArgs> ct;
-    static_cast<CfgStepArgs&>(ct) = ca;
-    ct.traj = c->run_traj;
-    LAUNCH(CFD_PROF_OTHER, cfg_step_kernel_traj, dim3((unsigned)std::min<long long>((n4 + 255) / 256, 256)), dim3(256), st, ct);
-    return CFD_OK;
-  }
-  LAUNCH(CFD_PROF_OTHER, cfg_step_kernel<>, dim3((unsigned)std::min<long long>((n4 + 255) / 256, 256)), dim3(256), st, ca);
+  const CfgStepArgs& ca = cw;
+  const long long n4 = (long long)s.B * s.L * CFD_LAT / 4;
+  const dim3 grid((unsigned)std::min<long long>((n4 + 255) / 256, 256)), block(256);
+  // (m.traj: an inversion run recording its trajectory: the step also stores into slot *d_step + 1)
+  if (m.weighted && m.traj) LAUNCH(CFD_PROF_OTHER, cfg_step_kernel_weighted_traj, grid, block, st, with_traj(cw, m.traj));
+  else if (m.weighted) LAUNCH(CFD_PROF_OTHER, cfg_step_kernel_weighted, grid, block, st, cw);
+  else if (m.traj) LAUNCH(CFD_PROF_OTHER, cfg_step_kernel_traj, grid, block, st, with_traj(ca, m.traj));
+  else LAUNCH(CFD_PROF_OTHER, cfg_step_kernel<>, grid, block, st, ca);
   return CFD_OK;
 }
 
@@ -232,84 +250,36 @@ static int weighted_chunks(Ctx* c, const float* wtab, int prune, int N, bool kee
   return CFD_OK;
 }
 
-static int sample_begin(Ctx* c, const cfd_sample_args* args, void* stream, const float* wtab, int prune, int* chunks_evaluated,
-                        const cfd_edit_args* edit = nullptr, float* traj = nullptr, const cfd_anchor_args* anchor = nullptr,
-                        const cfd_tie_args* tie = nullptr);
-
-extern "C" int cfd_sample_begin(cfd_handle c, const cfd_sample_args* args, void* stream) {
-  return sample_begin(c, args, stream, nullptr, 0, nullptr);
+// The run's keep mask on the device: the validated host copy (the caller waits for the stream before hkeep goes out of scope), or,
+// with an empty hkeep (no mask given), no kept token.
+static int upload_keep_mask(Ctx* c, const std::vector<uint8_t>& hkeep, size_t n, hipStream_t st) {
+  CHK(c->ekeep.ensure(n));
+  if (!hkeep.empty()) HIPCHK(hipMemcpyAsync(c->ekeep.p, hkeep.data(), n, hipMemcpyHostToDevice, st));
+  else HIPCHK(hipMemsetAsync(c->ekeep.p, 0, n, st));
+  return CFD_OK;
 }
 
-extern "C" int cfd_sample_begin_edit(cfd_handle c, const cfd_sample_args* args, const cfd_edit_args* e, const float* weights, int prune,
-                                     int* chunks_evaluated, void* stream) {
-  if (!c || !args || !e) return fail(CFD_E_ARG, "null argument");
-  if (!e->source) return fail(CFD_E_ARG, "cfd_sample_begin_edit: the source latents are NULL");
-  if (args->preseq) return fail(CFD_E_ARG, "cfd_sample_begin_edit: an edit run has no preseq (the rollout's prefix in-painting)");
-  if (weights && args->G != 7) return fail(CFD_E_ARG, "cfd_sample_begin_edit: a weight table needs the 7-chunk guidance batch (G = %d)", args->G);
-  const int r = sample_begin(c, args, stream, weights, weights ? prune : 0, weights ? chunks_evaluated : nullptr, e);
-  if (r == CFD_OK && !weights && chunks_evaluated) *chunks_evaluated = c->sargs.G;
-  return r;
-}
+// What an opener adds to cfd_sample_begin's run; every field is optional.  weights (with prune / chunks_evaluated as in
+// cfd_sample_begin_weighted; NULL: the default guidance weights, chunks_evaluated then gets the run's G on success), edit, traj (the
+// inversion's trajectory ring), anchor, tie.  A new run kind adds its field here, its RunMode field and its row in with_begin_args.
+struct BeginExt {
+  const char* opener = "cfd_sample_begin";
+  const float* weights = nullptr;
+  int prune = 0;
+  int* chunks_evaluated = nullptr;
+  const cfd_edit_args* edit = nullptr;
+  float* traj = nullptr;
+  const cfd_anchor_args* anchor = nullptr;
+  const cfd_tie_args* tie = nullptr;
+};
 
-extern "C" int cfd_sample_begin_tied(cfd_handle c, const cfd_sample_args* args, const cfd_edit_args* e, const cfd_tie_args* t,
-                                     const float* weights, int prune, int* chunks_evaluated, void* stream) {
-  if (!c || !args || !t) return fail(CFD_E_ARG, "null argument");
-  if (!t->tie) return fail(CFD_E_ARG, "cfd_sample_begin_tied: the tie table is NULL");
-  if (e && !e->source) return fail(CFD_E_ARG, "cfd_sample_begin_tied: the source latents of the edit are NULL");
-  if (e && e->first_iteration != 0)
-    return fail(CFD_E_ARG, "cfd_sample_begin_tied: a tied run starts at iteration 0 (first_iteration = %d: no strength)", e->first_iteration);
-  if (args->scheduler == 3) return fail(CFD_E_ARG, "cfd_sample_begin_tied: DDIM inversion (scheduler 3) takes no ties");
-  if (args->preseq) return fail(CFD_E_ARG, "cfd_sample_begin_tied: a tied run has no preseq (give the prefix as kept tokens of an edit)");
-  if (args->dynamic_memory_mask)
-    return fail(CFD_E_ARG, "cfd_sample_begin_tied: a tied run takes no dynamic memories (dynamic_memory_mask = %d: dyadic runs)",
-                args->dynamic_memory_mask);
-  if (weights && args->G != 7) return fail(CFD_E_ARG, "cfd_sample_begin_tied: a weight table needs the 7-chunk guidance batch (G = %d)", args->G);
-  const int r = sample_begin(c, args, stream, weights, weights ? prune : 0, weights ? chunks_evaluated : nullptr, e, nullptr, nullptr, t);
-  if (r == CFD_OK && !weights && chunks_evaluated) *chunks_evaluated = c->sargs.G;
-  return r;
-}
-
-extern "C" int cfd_sample_begin_invert(cfd_handle c, const cfd_sample_args* args, float* trajectory, const float* weights, int prune,
-                                       int* chunks_evaluated, void* stream) {
+static int sample_begin(Ctx* c, const cfd_sample_args* args, void* stream, const BeginExt& x) {
   if (!c || !args) return fail(CFD_E_ARG, "null argument");
-  if (!trajectory) return fail(CFD_E_ARG, "cfd_sample_begin_invert: the trajectory is NULL");
-  if (args->scheduler != 3) return fail(CFD_E_ARG, "cfd_sample_begin_invert: scheduler must be 3 (DDIM inversion), not %d", args->scheduler);
-  if (weights && args->G != 7) return fail(CFD_E_ARG, "cfd_sample_begin_invert: a weight table needs the 7-chunk guidance batch (G = %d)", args->G);
-  const int r = sample_begin(c, args, stream, weights, weights ? prune : 0, weights ? chunks_evaluated : nullptr, nullptr, trajectory);
-  if (r == CFD_OK && !weights && chunks_evaluated) *chunks_evaluated = c->sargs.G;
-  return r;
-}
-
-extern "C" int cfd_sample_begin_anchored(cfd_handle c, const cfd_sample_args* args, const cfd_anchor_args* an, const float* weights,
-                                         int prune, int* chunks_evaluated, void* stream) {
-  if (!c || !args || !an) return fail(CFD_E_ARG, "null argument");
-  if (!an->trajectory) return fail(CFD_E_ARG, "cfd_sample_begin_anchored: the trajectory is NULL");
-  if (args->scheduler != 1) return fail(CFD_E_ARG, "cfd_sample_begin_anchored: an anchored run is a DDIM run (scheduler 1, not %d)", args->scheduler);
-  if (args->eta != 0.f || args->clip_sample)
-    return fail(CFD_E_ARG, "cfd_sample_begin_anchored: the DDIM run must be deterministic and unclipped (eta = %g, clip_sample = %d)",
-                (double)args->eta, args->clip_sample);
-  if (args->preseq) return fail(CFD_E_ARG, "cfd_sample_begin_anchored: an anchored run has no preseq");
-  const int n_iter = args->timesteps ? args->num_timesteps : args->num_inference_steps;
-  if (an->steps != n_iter || an->B != args->B || an->L != args->L)
-    return fail(CFD_E_ARG, "cfd_sample_begin_anchored: the trajectory is [%d + 1][%d][%d][128], this run has %d iterations of [%d][%d][128]",
-                an->steps, an->B, an->L, n_iter, args->B, args->L);
-  if (weights && args->G != 7) return fail(CFD_E_ARG, "cfd_sample_begin_anchored: a weight table needs the 7-chunk guidance batch (G = %d)", args->G);
-  const int r = sample_begin(c, args, stream, weights, weights ? prune : 0, weights ? chunks_evaluated : nullptr, nullptr, nullptr, an);
-  if (r == CFD_OK && !weights && chunks_evaluated) *chunks_evaluated = c->sargs.G;
-  return r;
-}
-
-extern "C" int cfd_sample_begin_weighted(cfd_handle c, const cfd_sample_args* args, const float* weights, int prune, int* chunks_evaluated,
-                                         void* stream) {
-  if (!c || !args) return fail(CFD_E_ARG, "null argument");
-  if (!weights) return fail(CFD_E_ARG, "cfd_sample_begin_weighted: the weight table is NULL");
-  if (args->G != 7) return fail(CFD_E_ARG, "cfd_sample_begin_weighted needs the 7-chunk guidance batch (G = %d)", args->G);
-  return sample_begin(c, args, stream, weights, prune, chunks_evaluated);
-}
-
-static int sample_begin(Ctx* c, const cfd_sample_args* args, void* stream, const float* wtab, int prune, int* chunks_evaluated,
-                        const cfd_edit_args* edit, float* traj, const cfd_anchor_args* anchor, const cfd_tie_args* tie) {
-  if (!c || !args) return fail(CFD_E_ARG, "null argument");
+  const float* wtab = x.weights;
+  const cfd_edit_args* edit = x.edit;
+  const cfd_anchor_args* anchor = x.anchor;
+  const cfd_tie_args* tie = x.tie;
+  if (wtab && args->G != 7) return fail(CFD_E_ARG, "%s: a weight table needs the 7-chunk guidance batch (G = %d)", x.opener, args->G);
   if (c->run_open) return fail(CFD_E_STATE, "a sampling run is already open");
   HIPCHK(hipSetDevice(c->cfg.device));
   c->hint_now = c->hint_same_mem = false;
@@ -323,15 +293,7 @@ static int sample_begin(Ctx* c, const cfd_sample_args* args, void* stream, const
     s_w.skip_zero_weight_chunks = 0;
     args = &s_w;
   }
-  c->run_weighted = false;
-  c->run_edit = false;
-  c->run_k0 = 0;
-  c->run_traj = nullptr;
-  c->run_anchor = false;
-  c->anchor_ring = nullptr;
-  c->anchor_n = 0;
-  c->run_tie = false;
-  c->tie_final = false;
+  c->run = RunMode{};
   const cfd_sample_args& s = *args;
   if (s.B < 1 || (s.G != 1 && s.G != 7 && (s.G < 1 || s.G > 8))) return fail(CFD_E_ARG, "bad B / G");
   if (s.scheduler < 0 || s.scheduler > 3)
@@ -408,7 +370,7 @@ static int sample_begin(Ctx* c, const cfd_sample_args* args, void* stream, const
   cfd_memory mem_in[CFD_NMEM];
   for (int j = 0; j < CFD_NMEM; ++j) mem_in[j] = s.mem[j];
   int keep_idx[8];
-  if (wtab) CHK(weighted_chunks(c, wtab, prune, N, n_ring != 0, mem_in, keep_idx, st));
+  if (wtab) CHK(weighted_chunks(c, wtab, x.prune, N, n_ring != 0, mem_in, keep_idx, st));
   const int Be = c->sargs.G * s.B;
   {
     // chunk permutation (see chunk_pos): group the chunks that use one shared copy of the largest memory
@@ -455,8 +417,8 @@ static int sample_begin(Ctx* c, const cfd_sample_args* args, void* stream, const
   }
   if (wtab) {
     for (int k = 0; k < 8; ++k) c->wpos[k] = c->chunk_pos[keep_idx[k] >= 0 ? keep_idx[k] : 0];
-    c->run_weighted = true;
-    if (chunks_evaluated) *chunks_evaluated = c->sargs.G;
+    c->run.weighted = true;
+    if (x.chunks_evaluated) *x.chunks_evaluated = c->sargs.G;
   }
   // operand policy of the run (cfd_sample_args::operand_policy): single-fp16 key / value tiles of the long memories for the fused
   // cross-attention kernel -- only where that kernel runs on projections made once per run and keeps no maps
@@ -532,20 +494,17 @@ static int sample_begin(Ctx* c, const cfd_sample_args* args, void* stream, const
     if (!edit) {
       CHK(c->enoise.ensure(lat_bytes));
       CHK(c->esrc.ensure(lat_bytes));
-      CHK(c->ekeep.ensure((size_t)s.B * s.L));
-      HIPCHK(hipMemsetAsync(c->ekeep.p, 0, (size_t)s.B * s.L, st));
+      CHK(upload_keep_mask(c, hkeep, (size_t)s.B * s.L, st));   // (hkeep is empty here)
     }
     HIPCHK(hipStreamSynchronize(st));   // (htie goes out of scope)
-    c->run_tie = true;
+    c->run.tie = true;
   }
   if (edit) {   // the run's noise eps = the initial draw, the source, the mask; k0 > 0: every token starts at sa_k0 * source + sb_k0 * eps
     CHK(c->enoise.ensure(lat_bytes));
     CHK(c->esrc.ensure(lat_bytes));
-    CHK(c->ekeep.ensure((size_t)s.B * s.L));
     HIPCHK(hipMemcpyAsync(c->enoise.p, c->latents.p, lat_bytes, hipMemcpyDeviceToDevice, st));
     HIPCHK(hipMemcpyAsync(c->esrc.p, edit->source, lat_bytes, hipMemcpyDeviceToDevice, st));
-    if (edit->keep) HIPCHK(hipMemcpyAsync(c->ekeep.p, hkeep.data(), hkeep.size(), hipMemcpyHostToDevice, st));
-    else HIPCHK(hipMemsetAsync(c->ekeep.p, 0, (size_t)s.B * s.L, st));
+    CHK(upload_keep_mask(c, hkeep, (size_t)s.B * s.L, st));
     if (k0 > 0) {
       const long long n8 = (long long)s.B * s.L * (CFD_LAT / 8);
       hipLaunchKernelGGL(edit_init_kernel<>, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, st, c->latents.as<float>(), c->esrc.as<float>(),
@@ -553,23 +512,21 @@ static int sample_begin(Ctx* c, const cfd_sample_args* args, void* stream, const
       HIPCHK(hipGetLastError());
     }
     HIPCHK(hipStreamSynchronize(st));   // (hkeep goes out of scope)
-    c->run_edit = true;
-    c->run_k0 = k0;
+    c->run.edit = true;
+    c->run.k0 = k0;
     c->run_iters = N - k0;
   }
-  if (traj) {   // slot 0 of the trajectory: the initial latents (the source of the inversion)
-    HIPCHK(hipMemcpyAsync(traj, c->latents.p, lat_bytes, hipMemcpyDeviceToDevice, st));
+  if (x.traj) {   // slot 0 of the trajectory: the initial latents (the source of the inversion)
+    HIPCHK(hipMemcpyAsync(x.traj, c->latents.p, lat_bytes, hipMemcpyDeviceToDevice, st));
     HIPCHK(hipStreamSynchronize(st));
-    c->run_traj = traj;
+    c->run.traj = x.traj;
   }
   if (anchor) {   // the keep mask; the ring is the caller's and is read in place
-    CHK(c->ekeep.ensure((size_t)s.B * s.L));
-    if (anchor->keep) HIPCHK(hipMemcpyAsync(c->ekeep.p, hkeep.data(), hkeep.size(), hipMemcpyHostToDevice, st));
-    else HIPCHK(hipMemsetAsync(c->ekeep.p, 0, (size_t)s.B * s.L, st));
+    CHK(upload_keep_mask(c, hkeep, (size_t)s.B * s.L, st));
     HIPCHK(hipStreamSynchronize(st));   // (hkeep goes out of scope)
-    c->run_anchor = true;
-    c->anchor_ring = anchor->trajectory;
-    c->anchor_n = anchor->steps;
+    c->run.anchor = true;
+    c->run.anchor_ring = anchor->trajectory;
+    c->run.anchor_n = anchor->steps;
   }
   // DPM-Solver++: the x0 history of the run, zeroed.  The first executed iteration is first order and never reads it, so the eager warm-up
   // iteration below, which runs as that iteration and writes its x0 here, needs no save / restore: the first replay overwrites that before
@@ -628,7 +585,77 @@ static int sample_begin(Ctx* c, const cfd_sample_args* args, void* stream, const
   c->run_open = true;
   c->run_pos = 0;
   c->acen_valid = true;
+  if (!wtab && x.chunks_evaluated) *x.chunks_evaluated = c->sargs.G;
   return CFD_OK;
+}
+
+// The openers: each checks what its kind of run needs, then says what it adds to the plain run (BeginExt).
+extern "C" int cfd_sample_begin(cfd_handle c, const cfd_sample_args* args, void* stream) {
+  return sample_begin(c, args, stream, BeginExt{});
+}
+
+extern "C" int cfd_sample_begin_weighted(cfd_handle c, const cfd_sample_args* args, const float* weights, int prune, int* chunks_evaluated,
+                                         void* stream) {
+  if (!c || !args) return fail(CFD_E_ARG, "null argument");
+  if (!weights) return fail(CFD_E_ARG, "cfd_sample_begin_weighted: the weight table is NULL");
+  if (args->G != 7) return fail(CFD_E_ARG, "cfd_sample_begin_weighted needs the 7-chunk guidance batch (G = %d)", args->G);
+  return sample_begin(c, args, stream, BeginExt{"cfd_sample_begin_weighted", weights, prune, chunks_evaluated});
+}
+
+extern "C" int cfd_sample_begin_edit(cfd_handle c, const cfd_sample_args* args, const cfd_edit_args* e, const float* weights, int prune,
+                                     int* chunks_evaluated, void* stream) {
+  if (!c || !args || !e) return fail(CFD_E_ARG, "null argument");
+  if (!e->source) return fail(CFD_E_ARG, "cfd_sample_begin_edit: the source latents are NULL");
+  if (args->preseq) return fail(CFD_E_ARG, "cfd_sample_begin_edit: an edit run has no preseq (the rollout's prefix in-painting)");
+  BeginExt x{"cfd_sample_begin_edit", weights, prune, chunks_evaluated};
+  x.edit = e;
+  return sample_begin(c, args, stream, x);
+}
+
+extern "C" int cfd_sample_begin_tied(cfd_handle c, const cfd_sample_args* args, const cfd_edit_args* e, const cfd_tie_args* t,
+                                     const float* weights, int prune, int* chunks_evaluated, void* stream) {
+  if (!c || !args || !t) return fail(CFD_E_ARG, "null argument");
+  if (!t->tie) return fail(CFD_E_ARG, "cfd_sample_begin_tied: the tie table is NULL");
+  if (e && !e->source) return fail(CFD_E_ARG, "cfd_sample_begin_tied: the source latents of the edit are NULL");
+  if (e && e->first_iteration != 0)
+    return fail(CFD_E_ARG, "cfd_sample_begin_tied: a tied run starts at iteration 0 (first_iteration = %d: no strength)", e->first_iteration);
+  if (args->scheduler == 3) return fail(CFD_E_ARG, "cfd_sample_begin_tied: DDIM inversion (scheduler 3) takes no ties");
+  if (args->preseq) return fail(CFD_E_ARG, "cfd_sample_begin_tied: a tied run has no preseq (give the prefix as kept tokens of an edit)");
+  if (args->dynamic_memory_mask)
+    return fail(CFD_E_ARG, "cfd_sample_begin_tied: a tied run takes no dynamic memories (dynamic_memory_mask = %d: dyadic runs)",
+                args->dynamic_memory_mask);
+  BeginExt x{"cfd_sample_begin_tied", weights, prune, chunks_evaluated};
+  x.edit = e;
+  x.tie = t;
+  return sample_begin(c, args, stream, x);
+}
+
+extern "C" int cfd_sample_begin_invert(cfd_handle c, const cfd_sample_args* args, float* trajectory, const float* weights, int prune,
+                                       int* chunks_evaluated, void* stream) {
+  if (!c || !args) return fail(CFD_E_ARG, "null argument");
+  if (!trajectory) return fail(CFD_E_ARG, "cfd_sample_begin_invert: the trajectory is NULL");
+  if (args->scheduler != 3) return fail(CFD_E_ARG, "cfd_sample_begin_invert: scheduler must be 3 (DDIM inversion), not %d", args->scheduler);
+  BeginExt x{"cfd_sample_begin_invert", weights, prune, chunks_evaluated};
+  x.traj = trajectory;
+  return sample_begin(c, args, stream, x);
+}
+
+extern "C" int cfd_sample_begin_anchored(cfd_handle c, const cfd_sample_args* args, const cfd_anchor_args* an, const float* weights,
+                                         int prune, int* chunks_evaluated, void* stream) {
+  if (!c || !args || !an) return fail(CFD_E_ARG, "null argument");
+  if (!an->trajectory) return fail(CFD_E_ARG, "cfd_sample_begin_anchored: the trajectory is NULL");
+  if (args->scheduler != 1) return fail(CFD_E_ARG, "cfd_sample_begin_anchored: an anchored run is a DDIM run (scheduler 1, not %d)", args->scheduler);
+  if (args->eta != 0.f || args->clip_sample)
+    return fail(CFD_E_ARG, "cfd_sample_begin_anchored: the DDIM run must be deterministic and unclipped (eta = %g, clip_sample = %d)",
+                (double)args->eta, args->clip_sample);
+  if (args->preseq) return fail(CFD_E_ARG, "cfd_sample_begin_anchored: an anchored run has no preseq");
+  const int n_iter = args->timesteps ? args->num_timesteps : args->num_inference_steps;
+  if (an->steps != n_iter || an->B != args->B || an->L != args->L)
+    return fail(CFD_E_ARG, "cfd_sample_begin_anchored: the trajectory is [%d + 1][%d][%d][128], this run has %d iterations of [%d][%d][128]",
+                an->steps, an->B, an->L, n_iter, args->B, args->L);
+  BeginExt x{"cfd_sample_begin_anchored", weights, prune, chunks_evaluated};
+  x.anchor = an;
+  return sample_begin(c, args, stream, x);
 }
 
 extern "C" int cfd_sample_census(cfd_handle c, cfd_census* out) {
@@ -679,7 +706,7 @@ extern "C" int cfd_dyadic_steps(cfd_handle a, cfd_handle b, const cfd_dyadic_pro
   if (!pr->w1 || !pr->b1 || !pr->w2 || !pr->b2 || !pr->spk_a || !pr->spk_b || !pr->tmp || pr->hidden < 1 || pr->out_dim != CFD_D)
     return fail(CFD_E_ARG, "bad partner projection");
   const cfd_sample_args& sa = a->sargs;
-  if (a->run_tie || (b && b->run_tie)) return fail(CFD_E_ARG, "a tied run takes no dyadic steps");
+  if (a->run.tie || (b && b->run.tie)) return fail(CFD_E_ARG, "a tied run takes no dyadic steps");
   if (!(sa.dynamic_memory_mask & 1) || (b && !(b->sargs.dynamic_memory_mask & 1)))
     return fail(CFD_E_STATE, "the speaker memory of the run(s) must be declared dynamic");
   if (b && (sa.B != b->sargs.B || sa.L != b->sargs.L || a->cfg.device != b->cfg.device)) return fail(CFD_E_ARG, "the two sides differ in batch, length or device");
@@ -728,12 +755,12 @@ extern "C" int cfd_sample_read(cfd_handle c, float* out, int close) {
   if (!c->run_open) return fail(CFD_E_STATE, "no sampling run open");
   HIPCHK(hipSetDevice(c->cfg.device));
   const size_t lat_bytes = (size_t)c->sargs.B * c->sargs.L * CFD_LAT * 4;
-  if (c->run_tie && !c->tie_final && c->run_pos == c->run_iters) {   // a finished tied run: the tie copy once more (mid-run reads: as stepped)
+  if (c->run.tie && !c->run.tie_final && c->run_pos == c->run_iters) {   // a finished tied run: the tie copy once more (mid-run reads: as stepped)
     const long long n8 = (long long)c->sargs.B * c->sargs.L * (CFD_LAT / 8);
     hipLaunchKernelGGL(tie_copy_kernel<>, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, c->run_stream, c->latents.as<float>(),
                        c->etie.as<int32_t>(), n8);
     HIPCHK(hipGetLastError());
-    c->tie_final = true;
+    c->run.tie_final = true;
   }
   HIPCHK(hipMemcpyAsync(out, c->latents.p, lat_bytes, hipMemcpyDeviceToDevice, c->run_stream));
   HIPCHK(hipStreamSynchronize(c->run_stream));
@@ -821,49 +848,23 @@ extern "C" int cfd_philox_normal(cfd_handle c, float* out, int B, int per_utt, u
   return enqueue_philox_fill(out, B, per_utt, seed, step, first_utt, stream_id, 1.0f, (hipStream_t)stream);
 }
 
-static void (*const inpaint_now_kernel_edit)(const BeginArgsE, int*) = inpaint_now_kernel<0, true>;
-static void (*const inpaint_now_kernel_anchor)(const BeginArgsA, int*) = inpaint_now_kernel<0, false, true>;
-static void (*const inpaint_now_kernel_tied)(const BeginArgsT, int*) = inpaint_now_kernel<0, true, false, true>;
-
 extern "C" int cfd_sample_inpaint(cfd_handle c) {
   if (!c) return fail(CFD_E_ARG, "null handle");
   if (!c->run_open) return fail(CFD_E_STATE, "no sampling run open");
   const cfd_sample_args& s = c->sargs;
-  if (c->run_tie) {   // the tied instance: the tied and the kept tokens of this iteration, then the captured iteration skips both
-    if (c->run_pos >= c->run_iters) return fail(CFD_E_STATE, "cfd_sample_inpaint: the run has no iteration left");
-    HIPCHK(hipSetDevice(c->cfg.device));
-    const long long n8 = (long long)s.B * s.L * (CFD_LAT / 8);
-    hipLaunchKernelGGL(inpaint_now_kernel_tied, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, c->run_stream, tied_begin_args(c),
-                       c->w->d_step.as<int>());
-    HIPCHK(hipGetLastError());
-    return CFD_OK;
-  }
-  if (c->run_edit) {   // the edit instance: the kept tokens of this iteration, then the captured iteration skips its overwrite
-    if (c->run_pos >= c->run_iters) return fail(CFD_E_STATE, "cfd_sample_inpaint: the run has no iteration left");
-    HIPCHK(hipSetDevice(c->cfg.device));
-    const long long n8 = (long long)s.B * s.L * (CFD_LAT / 8);
-    hipLaunchKernelGGL(inpaint_now_kernel_edit, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, c->run_stream, edit_begin_args(c),
-                       c->w->d_step.as<int>());
-    HIPCHK(hipGetLastError());
-    return CFD_OK;
-  }
-  if (c->run_anchor) {   // the anchored instance: the kept tokens of this iteration from the trajectory
-    if (c->run_pos >= c->run_iters) return fail(CFD_E_STATE, "cfd_sample_inpaint: the run has no iteration left");
-    HIPCHK(hipSetDevice(c->cfg.device));
-    const long long n8 = (long long)s.B * s.L * (CFD_LAT / 8);
-    hipLaunchKernelGGL(inpaint_now_kernel_anchor, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, c->run_stream, anchor_begin_args(c),
-                       c->w->d_step.as<int>());
-    HIPCHK(hipGetLastError());
-    return CFD_OK;
-  }
-  if (!s.preseq || s.preseq_len < 1) return CFD_OK;
+  // a tied, edit or anchored run: that instance does the tied / kept tokens of this iteration (one thread = 8 elements of any token), then
+  // the captured iteration skips its overwrite; the default instance: the preseq tokens, if the run has any
+  const bool by_token = c->run.tie || c->run.edit || c->run.anchor;
+  if (by_token && c->run_pos >= c->run_iters) return fail(CFD_E_STATE, "cfd_sample_inpaint: the run has no iteration left");
+  if (!by_token && (!s.preseq || s.preseq_len < 1)) return CFD_OK;
   HIPCHK(hipSetDevice(c->cfg.device));
-  BeginArgs ba{c->latents.as<float>(), c->w->sample_sp.as<char>(), s.B, s.L, s.G, s.preseq, c->inoise.as<float>(), s.preseq_len,
-               c->coef.as<StepCoef>(), c->w->d_step.as<int>()};
-  const long long n = (long long)s.B * s.preseq_len * CFD_LAT;
-  hipLaunchKernelGGL(inpaint_now_kernel<>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->run_stream, ba, c->w->d_step.as<int>());
-  HIPCHK(hipGetLastError());
-  return CFD_OK;
+  const long long n = by_token ? (long long)s.B * s.L * (CFD_LAT / 8) : (long long)s.B * s.preseq_len * CFD_LAT;
+  return with_begin_args(c, [&](auto a) {
+    hipLaunchKernelGGL(BeginInst<decltype(a)>::inpaint_now, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->run_stream, a,
+                       c->w->d_step.as<int>());
+    HIPCHK(hipGetLastError());
+    return (int)CFD_OK;
+  });
 }
 
 extern "C" int cfd_sample_write(cfd_handle c, const float* latents) {

@@ -126,6 +126,20 @@ def edit_first_iteration(strength, N):
     return N - k
 
 
+def _check_keep_mask(keep_mask, B, L, device):
+    """The keep mask of an edit or an anchored run as uint8 [B, L] on ``device`` (None stays None); ValueError for anything but a bool or
+    integer [B, L] tensor of 0 / 1."""
+    if keep_mask is None:
+        return None
+    if not isinstance(keep_mask, torch.Tensor) or keep_mask.is_floating_point() or keep_mask.is_complex():
+        raise ValueError("keep_mask must be a bool or integer (0 / 1) tensor [B, L]")
+    if tuple(keep_mask.shape) != (B, L):
+        raise ValueError(f"keep_mask must be [B, L] = [{B}, {L}], not {list(keep_mask.shape)}")
+    if keep_mask.dtype != torch.bool and bool(((keep_mask != 0) & (keep_mask != 1)).any()):
+        raise ValueError("keep_mask holds values other than 0 and 1")
+    return keep_mask.detach().to(device=device, dtype=torch.uint8).contiguous()
+
+
 def check_edit(source_latents, keep_mask, strength, B, L, N, preseq=None, device=None):
     """The edit arguments of a run (``SamplingRun``): None when the run is no edit (no source, strength 1), else (source float32 [B, L, 128]
     contiguous on ``device``, keep mask uint8 [B, L] on ``device`` or None, k0).  Refusals (ValueError): keep_mask or strength < 1 without
@@ -146,16 +160,7 @@ def check_edit(source_latents, keep_mask, strength, B, L, N, preseq=None, device
     if tuple(source_latents.shape) != (B, L, 128):
         raise ValueError(f"source_latents must be [B, L, 128] = [{B}, {L}, 128], not {list(source_latents.shape)}")
     src = source_latents.detach().to(device=device, dtype=torch.float32).contiguous()
-    keep = None
-    if keep_mask is not None:
-        if not isinstance(keep_mask, torch.Tensor) or keep_mask.is_floating_point() or keep_mask.is_complex():
-            raise ValueError("keep_mask must be a bool or integer (0 / 1) tensor [B, L]")
-        if tuple(keep_mask.shape) != (B, L):
-            raise ValueError(f"keep_mask must be [B, L] = [{B}, {L}], not {list(keep_mask.shape)}")
-        if keep_mask.dtype != torch.bool and bool(((keep_mask != 0) & (keep_mask != 1)).any()):
-            raise ValueError("keep_mask holds values other than 0 and 1")
-        keep = keep_mask.detach().to(device=device, dtype=torch.uint8).contiguous()
-    return src, keep, k0
+    return src, _check_keep_mask(keep_mask, B, L, device), k0
 
 
 def check_inversion(scheduler, table, eta=0.0):
@@ -182,17 +187,7 @@ def check_anchor(trajectory, keep_mask, B, L, N, device=None):
     if tuple(trajectory.shape) != (N + 1, B, L, 128):
         raise ValueError(f"anchor_trajectory must be [N + 1, B, L, 128] = [{N + 1}, {B}, {L}, 128] (an inversion with the run's N = {N} "
                          f"iterations, B and L), not {list(trajectory.shape)}")
-    keep = None
-    if keep_mask is not None:
-        if not isinstance(keep_mask, torch.Tensor) or keep_mask.is_floating_point() or keep_mask.is_complex():
-            raise ValueError("keep_mask must be a bool or integer (0 / 1) tensor [B, L]")
-        if tuple(keep_mask.shape) != (B, L):
-            raise ValueError(f"keep_mask must be [B, L] = [{B}, {L}], not {list(keep_mask.shape)}")
-        if keep_mask.dtype != torch.bool and bool(((keep_mask != 0) & (keep_mask != 1)).any()):
-            raise ValueError("keep_mask holds values other than 0 and 1")
-        keep = keep_mask.detach().to(device=device, dtype=torch.uint8).contiguous()
-    traj = trajectory.detach().to(device=device, dtype=torch.float32).contiguous()
-    return traj, keep
+    return trajectory.detach().to(device=device, dtype=torch.float32).contiguous(), _check_keep_mask(keep_mask, B, L, device)
 
 
 def check_tie(tie, keep_mask, B, L, device=None, *, preseq=None, strength=1.0, scheduler_kind=None, anchored=False, dynamic_memories=()):
@@ -467,7 +462,8 @@ class SamplingRun:
             mems, maps, masks = list(encoder_hidden_states), None, dict(cond_masks or {})
         self.handle = denoiser.engine(dev, mem_len=max(int(m.shape[1]) for m in mems), side=bool(side_engine))
         marr, keep = Denoiser.pack_memories(mems, masks, maps)
-        self._keep = [keep, denoiser]
+        self._denoiser = denoiser
+        self._keep = [keep]     # everything the library reads after this call returns
         a = _lib.SampleArgs()
         a.B, a.L, a.G = B, L, G
         # e_0 + sum_k w_k (e_k - e_0); the full-conditioning chunk has weight guidance_scale * 0 (:538)
@@ -517,7 +513,7 @@ class SamplingRun:
         if self._guard and census_tau is None:
             census_tau = CENSUS_TAU
         a.census_tau = float(census_tau or 0.0)
-        self._checked = 0
+        self._checked = self._done = 0
         ts = (C.c_int32 * n_full)(*[int(t) for t in table])
         self._keep.append(ts)
         a.timesteps, a.num_timesteps = C.cast(ts, C.c_void_p), n_full
@@ -534,54 +530,43 @@ class SamplingRun:
             a.att_ring = (C.c_void_p * _lib.NUM_MEM)(*[t.data_ptr() for t in self.att_ring])
         self._args = a
         stream = torch.cuda.current_stream(dev).cuda_stream
+        # the optional parts of the run, each built once (the anchor trajectory is read in place for the whole run: _keep) ...
+        w_ptr = self.modality_weights.ctypes.data_as(C.c_void_p) if self.modality_weights is not None else None
+        e = an = ta = None
+        if edit is not None:
+            e = _lib.EditArgs()
+            e.source, e.keep, e.first_iteration = edit[0].data_ptr(), (edit[1].data_ptr() if edit[1] is not None else None), edit[2]
+            self._keep += [edit[0], edit[1], e]
+        if anchor is not None:
+            an = _lib.AnchorArgs()
+            an.trajectory, an.steps, an.B, an.L = anchor[0].data_ptr(), n_full, B, L
+            an.keep = anchor[1].data_ptr() if anchor[1] is not None else None
+            self._keep += [anchor[0], anchor[1], an]
+        if self.tie is not None:
+            ta = _lib.TieArgs()
+            ta.tie = self.tie.data_ptr()
+            self._keep.append(ta)
+        # ... and the opener that takes them: a tie first (with or without an edit), then a trajectory / an anchor, then an edit
+        if ta is not None:
+            opener, extra = self.lib.cfd_sample_begin_tied, (C.byref(e) if e is not None else None, C.byref(ta))
+        elif self.trajectory is not None:
+            opener, extra = self.lib.cfd_sample_begin_invert, (C.c_void_p(self.trajectory.data_ptr()),)
+        elif an is not None:
+            opener, extra = self.lib.cfd_sample_begin_anchored, (C.byref(an),)
+        elif e is not None:
+            opener, extra = self.lib.cfd_sample_begin_edit, (C.byref(e),)
+        else:
+            opener, extra = (self.lib.cfd_sample_begin if w_ptr is None else self.lib.cfd_sample_begin_weighted), ()
+        # the plain opener takes no table and reports no count: the library's rule (trailing zero-weight chunks) is restated here
+        plain = opener is self.lib.cfd_sample_begin
+        g_eval = C.c_int(G)
+        while plain and skip_zero_weight_chunks and g_eval.value > 1 and w[g_eval.value - 1] == 0.0:
+            g_eval.value -= 1
+        table_args = () if plain else (w_ptr, 1 if prune_zero_weight_chunks else 0, C.byref(g_eval))
         with torch.cuda.device(dev):
             torch.cuda.current_stream(dev).synchronize()
-            w_ptr = self.modality_weights.ctypes.data_as(C.c_void_p) if self.modality_weights is not None else None
-            if self.tie is not None:
-                ta = _lib.TieArgs()
-                ta.tie = self.tie.data_ptr()
-                e = None
-                if edit is not None:
-                    e = _lib.EditArgs()
-                    e.source, e.keep, e.first_iteration = edit[0].data_ptr(), (edit[1].data_ptr() if edit[1] is not None else None), edit[2]
-                    self._keep += [edit[0], edit[1], e]
-                self._keep.append(ta)
-                g_eval = C.c_int(0)
-                _lib.check(self.lib.cfd_sample_begin_tied(self.handle, C.byref(a), C.byref(e) if e is not None else None, C.byref(ta), w_ptr,
-                                                          1 if prune_zero_weight_chunks else 0, C.byref(g_eval), C.c_void_p(stream)))
-                self.chunks_evaluated = int(g_eval.value)
-            elif self.trajectory is not None or anchor is not None:
-                g_eval = C.c_int(0)
-                if self.trajectory is not None:
-                    _lib.check(self.lib.cfd_sample_begin_invert(self.handle, C.byref(a), C.c_void_p(self.trajectory.data_ptr()), w_ptr,
-                                                                1 if prune_zero_weight_chunks else 0, C.byref(g_eval), C.c_void_p(stream)))
-                else:
-                    an = _lib.AnchorArgs()
-                    an.trajectory, an.steps, an.B, an.L = anchor[0].data_ptr(), n_full, B, L
-                    an.keep = anchor[1].data_ptr() if anchor[1] is not None else None
-                    self._keep += [anchor[0], anchor[1], an]
-                    _lib.check(self.lib.cfd_sample_begin_anchored(self.handle, C.byref(a), C.byref(an), w_ptr,
-                                                                  1 if prune_zero_weight_chunks else 0, C.byref(g_eval), C.c_void_p(stream)))
-                self.chunks_evaluated = int(g_eval.value)
-            elif edit is not None:
-                e = _lib.EditArgs()
-                e.source, e.keep, e.first_iteration = edit[0].data_ptr(), (edit[1].data_ptr() if edit[1] is not None else None), edit[2]
-                self._keep += [edit[0], edit[1], e]
-                g_eval = C.c_int(0)
-                w_ptr = self.modality_weights.ctypes.data_as(C.c_void_p) if self.modality_weights is not None else None
-                _lib.check(self.lib.cfd_sample_begin_edit(self.handle, C.byref(a), C.byref(e), w_ptr, 1 if prune_zero_weight_chunks else 0,
-                                                          C.byref(g_eval), C.c_void_p(stream)))
-                self.chunks_evaluated = int(g_eval.value)
-            elif self.modality_weights is None:
-                _lib.check(self.lib.cfd_sample_begin(self.handle, C.byref(a), C.c_void_p(stream)))
-                self.chunks_evaluated = G
-                while skip_zero_weight_chunks and self.chunks_evaluated > 1 and w[self.chunks_evaluated - 1] == 0.0:
-                    self.chunks_evaluated -= 1       # (the library's rule: trailing zero-weight chunks)
-            else:
-                g_eval = C.c_int(0)
-                _lib.check(self.lib.cfd_sample_begin_weighted(self.handle, C.byref(a), self.modality_weights.ctypes.data_as(C.c_void_p),
-                                                              1 if prune_zero_weight_chunks else 0, C.byref(g_eval), C.c_void_p(stream)))
-                self.chunks_evaluated = int(g_eval.value)
+            _lib.check(opener(self.handle, C.byref(a), *extra, *table_args, C.c_void_p(stream)))
+        self.chunks_evaluated = int(g_eval.value)
         self.open = True
 
     def steps(self, n):
@@ -592,10 +577,10 @@ class SamplingRun:
         while n > 0:
             k = n
             if self._guard:   # up to the next census check
-                k = min(n, self._checked + CENSUS_CHUNK - getattr(self, "_done", 0))
+                k = min(n, self._checked + CENSUS_CHUNK - self._done)
             with torch.cuda.device(self.device):
                 _lib.check(self.lib.cfd_sample_steps(self.handle, k))
-            self._done = getattr(self, "_done", 0) + k
+            self._done += k
             n -= k
             if self._guard and (self._done - self._checked >= CENSUS_CHUNK or self._done == self.N):
                 self._checked = self._done
@@ -610,7 +595,7 @@ class SamplingRun:
         c = _lib.Census()
         with torch.cuda.device(self.device):
             _lib.check(self.lib.cfd_sample_census(self.handle, C.byref(c)))
-        nl = min(_lib.CENSUS_MAX_LAYERS, int(self._keep[1].num_layers))
+        nl = min(_lib.CENSUS_MAX_LAYERS, int(self._denoiser.num_layers))
         return dict(tau=float(c.tau), measured=bool(c.measured), iterations=int(c.iterations), worst_layer=int(c.worst_layer),
                     peak_max=float(c.peak_max), rows_over=int(c.rows_over), rows_seen=int(c.rows_seen),
                     layer_peak=[float(c.layer_peak[i]) for i in range(nl)], layer_over=[int(c.layer_over[i]) for i in range(nl)])
@@ -620,7 +605,7 @@ class SamplingRun:
         ``read`` waits for the run's stream)."""
         if self.att_ring is None:
             raise RuntimeError("the run was opened without attention_ring=True")
-        n = getattr(self, "_done", 0) if upto is None else int(upto)     # (also valid after the run has been closed)
+        n = self._done if upto is None else int(upto)     # (also valid after the run has been closed)
         return {int(t): [r[i] for r in self.att_ring] for i, t in enumerate(self.timesteps[:n])}
 
     @property

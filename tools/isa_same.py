@@ -1,31 +1,18 @@
-"""Developer tool: do the loop's existing kernel instances keep their gfx950 code?  Compares the instruction lists of begin_step_kernel,
-inpaint_now_kernel and cfg_step_kernel (default / edit / anchored / weighted / trajectory instances) in two device-assembly listings of cfd_sample.hip, labels and
-comments aside.  A new trailing template parameter with a default changes an instance's name, not its code: the pairs below map the
-old names onto the new ones.
+"""Developer tool: do the kernels of a translation unit keep their gfx950 code?  Compares the instruction lists of every kernel that appears
+in either of two device-assembly listings (of cfd_sample.hip: the instances of begin_step_kernel, inpaint_now_kernel and cfg_step_kernel and
+the small kernels next to them), labels and comments aside, each under its own demangled name; a kernel in one listing only is MISSING.
+A new trailing template parameter with a default changes an instance's name, not its code: --rename OLD=NEW (repeatable) maps a part of
+a name before onto its spelling after, e.g. --rename "begin_step_kernel<0, true, false>(=begin_step_kernel<0, true, false, false>(".
 
 Make a listing (in convofusion_amd/csrc/ of each tree):
   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC --cuda-device-only -S -DCFD_SOURCE_HASH='"x"' cfd_sample.hip -o X.s
 
-Usage:  python tools/isa_same.py BEFORE.s AFTER.s      (exit status 1 when an instance differs or is missing)
+Usage:  python tools/isa_same.py [--rename OLD=NEW ...] BEFORE.s AFTER.s      (exit status 1 when a kernel differs or is missing)
 """
+import argparse
 import re
 import subprocess
 import sys
-
-# (name before, name after): the instances as the parent commit names them and as the tied instances' commit does (begin_step_kernel and
-# inpaint_now_kernel got a fourth parameter; the other kernels keep their names)
-PAIRS = [("begin_step_kernel<0, false, false>(", "begin_step_kernel<0, false, false, false>("),
-         ("begin_step_kernel<0, true, false>(", "begin_step_kernel<0, true, false, false>("),
-         ("begin_step_kernel<0, false, true>(", "begin_step_kernel<0, false, true, false>("),
-         ("inpaint_now_kernel<0, false, false>(", "inpaint_now_kernel<0, false, false, false>("),
-         ("inpaint_now_kernel<0, true, false>(", "inpaint_now_kernel<0, true, false, false>("),
-         ("inpaint_now_kernel<0, false, true>(", "inpaint_now_kernel<0, false, true, false>("),
-         ("cfg_step_kernel<0, false, false>(", "cfg_step_kernel<0, false, false>("),
-         ("cfg_step_kernel<0, true, false>(", "cfg_step_kernel<0, true, false>("),
-         ("cfg_step_kernel<0, false, true>(", "cfg_step_kernel<0, false, true>("),
-         ("cfg_step_kernel<0, true, true>(", "cfg_step_kernel<0, true, true>("),
-         ("edit_init_kernel<0>(", "edit_init_kernel<0>("),
-         ("sched_step_kernel<0>(", "sched_step_kernel<0>(")]
 
 
 def functions(path):
@@ -48,19 +35,31 @@ def functions(path):
     return {d: out[k] for k, d in zip(out, names)}
 
 
+def short(name):
+    """A kernel's name without its 'void' and its argument list."""
+    return re.sub(r"^void ", "", name).split("(")[0]
+
+
 def main():
-    before, after = functions(sys.argv[1]), functions(sys.argv[2])
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--rename", action="append", default=[], metavar="OLD=NEW", help="a part of a kernel's name before, and after")
+    ap.add_argument("before")
+    ap.add_argument("after")
+    a = ap.parse_args()
+    before, after = functions(a.before), functions(a.after)
+    for r in a.rename:
+        old, new = r.split("=", 1)
+        before = {k.replace(old, new): v for k, v in before.items()}
     bad = 0
-    for old, new in PAIRS:
-        a = [k for k in before if old in k]
-        b = [k for k in after if new in k]
-        if len(a) != 1 or len(b) != 1:
-            print(f"MISSING {old[:-1]} / {new[:-1]}")
+    for name in sorted(set(before) | set(after)):
+        if name not in before or name not in after:
+            print(f"MISSING {'before' if name not in before else 'after'}: {short(name)}")
             bad += 1
             continue
-        same = before[a[0]] == after[b[0]]
+        same = before[name] == after[name]
         bad += not same
-        print(f"{'SAME' if same else 'DIFF'} {len(before[a[0]])} vs {len(after[b[0]])} instructions: {old[:-1]} -> {new[:-1]}")
+        print(f"{'SAME' if same else 'DIFF'} {len(before[name])} vs {len(after[name])} instructions: {short(name)}")
+    print(f"{len(set(before) | set(after))} kernels, {bad} DIFF or MISSING")
     return 1 if bad else 0
 
 

@@ -25,7 +25,7 @@ SYMBOLS = [
     "cfd_layer_norm_bwd", "cfd_ew", "cfd_weg_focus", "cfd_sample_write", "cfd_sample_inpaint", "cfd_weg_eval", "cfd_dyadic_steps",
     "cfd_sample_census", "cfd_dpmsolver_step", "cfd_test_step_coefficients", "cfd_test_gemm_epi",
     "cfd_vae_encode", "cfd_sample_begin_weighted", "cfd_sample_begin_edit", "cfd_sample_begin_invert", "cfd_sample_begin_anchored",
-    "cfd_sample_begin_tied",
+    "cfd_sample_begin_tied", "cfd_ddpm_invert", "cfd_sample_begin_replay",
 ]
 
 
@@ -83,6 +83,21 @@ class TieArgs(C.Structure):
 class AnchorArgs(C.Structure):
     """cfd_anchor_args: an inversion trajectory (dev [steps + 1][B][L][128]), its steps / B / L, and the keep mask (dev uint8 [B][L] or NULL)."""
     _fields_ = [("trajectory", C.c_void_p), ("steps", C.c_int), ("B", C.c_int), ("L", C.c_int), ("keep", C.c_void_p)]
+
+
+class DdpmInvertArgs(C.Structure):
+    """cfd_ddpm_invert_args: source (dev [B][L][128]), HOST weight table [N][B][8] or NULL with prune, level noise (dev [N][B][L][128] or
+    NULL: Philox stream 2), the outputs trajectory (dev [N + 1][B][L][128]) and noise (dev [N][B][L][128]), levels per batch (0: from the
+    workspace budget in bytes, 0: 4 GiB)."""
+    _fields_ = [("source", C.c_void_p), ("weights", C.c_void_p), ("prune", C.c_int), ("level_noise", C.c_void_p), ("trajectory", C.c_void_p),
+                ("noise", C.c_void_p), ("levels_per_batch", C.c_int), ("workspace_bytes", C.c_size_t)]
+
+
+class ReplayArgs(C.Structure):
+    """cfd_replay_args: a recorded noise space (trajectory dev [steps + 1][B][L][128], noise dev [steps][B][L][128]), its steps / B / L, the
+    keep mask (dev uint8 [B][L] or NULL) and the first iteration k0."""
+    _fields_ = [("trajectory", C.c_void_p), ("noise", C.c_void_p), ("steps", C.c_int), ("B", C.c_int), ("L", C.c_int), ("keep", C.c_void_p),
+                ("first_iteration", C.c_int)]
 
 
 class Census(C.Structure):
@@ -180,6 +195,10 @@ def load():
     lib.cfd_sample_begin_invert.argtypes = [C.c_void_p, C.POINTER(SampleArgs), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p]
     lib.cfd_sample_begin_anchored.argtypes = [C.c_void_p, C.POINTER(SampleArgs), C.POINTER(AnchorArgs), C.c_void_p, C.c_int,
                                               C.POINTER(C.c_int), C.c_void_p]
+    lib.cfd_ddpm_invert.argtypes = [C.c_void_p, C.POINTER(SampleArgs), C.POINTER(DdpmInvertArgs), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                    C.c_void_p]
+    lib.cfd_sample_begin_replay.argtypes = [C.c_void_p, C.POINTER(SampleArgs), C.POINTER(ReplayArgs), C.c_void_p, C.c_int,
+                                            C.POINTER(C.c_int), C.c_void_p]
     lib.cfd_sample_steps.argtypes = [C.c_void_p, C.c_int]
     lib.cfd_sample_position.argtypes = [C.c_void_p]
     lib.cfd_sample_read.argtypes = [C.c_void_p, C.c_void_p, C.c_int]

@@ -94,6 +94,7 @@ extern "C" void cfd_destroy(cfd_handle c) {
   c->wk[1].release();
   for (int j = 0; j < CFD_NMEM; ++j) {
     c->wk_all_sp[j].release(); c->wv_all_sp[j].release(); c->mem_own[j].release(); c->perm_map[j].release();
+    c->lv_map[j].release(); c->lv_mask[j].release();
   }
   for (auto& l : c->lw) {
     DBuf* lb[] = {&l.wqk_f, &l.wv_f, &l.w1_f, &l.ln_cd, &l.wqk_sp, &l.bqk, &l.wv_sp, &l.wo_sp, &l.bo2, &l.wtb1_sp, &l.wtb2_sp, &l.w1_sp, &l.w2_sp, &l.cross_bias};

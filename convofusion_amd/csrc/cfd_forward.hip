@@ -213,6 +213,7 @@ int enqueue_rows(Ctx* c, hipStream_t st, int row0, int Be) {
   const Problem& p = c->w->pb;
   const int nl = c->nl, L = p.L;
   const long long M = (long long)Be * L;
+  if (p.tmode == 2 && (row0 != 0 || Be != p.Be)) return fail(CFD_E_ARG, "a level batch runs as one chunk (rows %d + %d of %d)", row0, Be, p.Be);
   const int* dstep = p.tmode ? c->w->d_step.as<int>() + 1 : c->w->d_step.as<int>();
   const long long ROWB = CFD_D * 4;  // bytes per SP row of 512
   const dim3 blk(256);
@@ -273,7 +274,8 @@ int enqueue_rows(Ctx* c, hipStream_t st, int row0, int Be) {
   }
   auto ln = [&](const float* g, const float* b, int adaln, int tbidx, char* out, long long rows) -> int {
     LnArgs a{c->w->x.as<float>(), out, rows, g, b, adaln, (rows_now ? ss_now : c->w->ss_tab.as<float>()) + (size_t)tbidx * 2 * CFD_D,
-             (long long)nl * 2 * 2 * CFD_D, rows_now ? nullptr : dstep, p.tmode, L, row0};
+             (long long)nl * 2 * 2 * CFD_D, rows_now ? nullptr : dstep, p.tmode, p.tmode == 2 ? L * p.lv_rows : L,
+             p.tmode == 2 ? p.lv_i0 : row0};   // (a level batch, always one chunk: table row lv_i0 + level, Problem::lv_rows rows per level)
     LAUNCH(CFD_PROF_ROWS, ln_rows_kernel<>, dim3((unsigned)((rows + 3) / 4)), blk, st, a);
     return CFD_OK;
   };

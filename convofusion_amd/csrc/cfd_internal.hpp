@@ -80,7 +80,11 @@ struct Problem {
   bool prev_same = false;       // setup_problem: the workspace still holds the previous cfd_forward's projections of memories of these shapes
   bool att_fused = false;       // the ring is written by the fused cross-attention kernel's ATT instance + att_fixup_kernel (tile kernels)
   long long att_slot[CFD_NMEM] = {0, 0, 0, 0, 0};
-  int tmode = 0;  // 0: all rows share the timestep of table row *d_step ; 1: row b uses table row b
+  int tmode = 0;  // 0: all rows share the timestep of table row *d_step ; 1: row b uses table row b ; 2: a level batch (below)
+  // Level batch (cfd_ddpm_invert, tmode 2): the batch is J levels of lv_rows rows each, level-major; every row of level lv uses table row
+  // lv_i0 + lv, and memory j's U[j] = J * lv_U[j] instances are the caller's lv_U[j] distinct memories once per level (instance
+  // lv * lv_U[j] + u: memory u at level lv's timestep), reached through level row maps.
+  int lv_rows = 0, lv_i0 = 0, lv_U[CFD_NMEM] = {0, 0, 0, 0, 0};
   // Sampling loop only: the effective batch is G replicas (chunk-major) of the same B latent rows, so everything
   // before the first cross-attention -- embedding, layer 0's self-attention and first time block -- is identical
   // for the G replicas of an utterance (same input, same timestep; the memories enter only at the cross-attention).
@@ -196,6 +200,9 @@ struct RunMode {
   // copy after the last iteration (tie_copy_kernel, enqueued by the first cfd_sample_read that finds the run finished) has been done.
   bool tie = false;
   bool tie_final = false;
+  // Replay of a recorded DDPM noise space (cfd_sample_begin_replay): the anchored instances over the caller's trajectory (anchor,
+  // anchor_ring, anchor_n as above), the run's step noise = the caller's noise ring (sargs.step_noise), and a start at iteration k0.
+  bool replay = false;
 };
 
 struct cfd_handle_s {
@@ -308,6 +315,7 @@ struct cfd_handle_s {
   RunMode run;
   int wpos[8];
   DBuf wtab, esrc, enoise, ekeep, etie;
+  DBuf lv_map[CFD_NMEM], lv_mask[CFD_NMEM];   // cfd_ddpm_invert: the level row maps and the key-padding masks once per level
   int run_pos = 0;
 };
 typedef cfd_handle_s Ctx;

@@ -618,9 +618,15 @@ int enqueue_memside(Ctx* c, hipStream_t st) {
   // 2. memories: + temb + condition id + PE, normalise           (denoiser.py:223-261,332-353)
   for (int j = 0; j < CFD_NMEM; ++j) {
     if ((p.static_mask >> j) & 1) continue;
+    const long long rows = (long long)p.U[j] * p.Sp[j];
+    if (p.tmode == 2) {   // a level batch: distinct memory u % lv_U at the timestep of level u / lv_U
+      MemPrepLevelArgs la{p.mem[j], p.lv_U[j], p.U[j], p.S[j], p.Sp[j], c->w->temb_tab.as<float>(), p.lv_i0,
+                          rawp(c, "condition_embedding.weight") + (size_t)j * CFD_D, rawp(c, "mem_pos.pe"), c->w->n_sp[j].as<char>()};
+      LAUNCH(CFD_PROF_ROWS, mem_prep_level_kernel<>, dim3((unsigned)((rows + 3) / 4)), blk, st, la);
+      continue;
+    }
     MemPrepArgs a{p.mem[j], p.U[j], p.S[j], p.Sp[j], c->w->temb_tab.as<float>(), dstep, p.tmode,
                   rawp(c, "condition_embedding.weight") + (size_t)j * CFD_D, rawp(c, "mem_pos.pe"), c->w->n_sp[j].as<char>()};
-    const long long rows = (long long)p.U[j] * p.Sp[j];
     LAUNCH(CFD_PROF_ROWS, mem_prep_kernel<>, dim3((unsigned)((rows + 3) / 4)), blk, st, a);
   }
   // 3. memory-side projections for ALL layers at once: folded keys (+ key bias) and folded values^T

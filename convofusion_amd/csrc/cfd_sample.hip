@@ -261,7 +261,8 @@ static int upload_keep_mask(Ctx* c, const std::vector<uint8_t>& hkeep, size_t n,
 
 // What an opener adds to cfd_sample_begin's run; every field is optional.  weights (with prune / chunks_evaluated as in
 // cfd_sample_begin_weighted; NULL: the default guidance weights, chunks_evaluated then gets the run's G on success), edit, traj (the
-// inversion's trajectory ring), anchor, tie.  A new run kind adds its field here, its RunMode field and its row in with_begin_args.
+// inversion's trajectory ring), anchor, tie, replay (a DDPM noise space: the anchored instance over its trajectory, a start at its
+// first_iteration).  A new run kind adds its field here, its RunMode field and its row in with_begin_args.
 struct BeginExt {
   const char* opener = "cfd_sample_begin";
   const float* weights = nullptr;
@@ -271,6 +272,7 @@ struct BeginExt {
   float* traj = nullptr;
   const cfd_anchor_args* anchor = nullptr;
   const cfd_tie_args* tie = nullptr;
+  const cfd_replay_args* replay = nullptr;
 };
 
 static int sample_begin(Ctx* c, const cfd_sample_args* args, void* stream, const BeginExt& x) {
@@ -279,6 +281,7 @@ static int sample_begin(Ctx* c, const cfd_sample_args* args, void* stream, const
   const cfd_edit_args* edit = x.edit;
   const cfd_anchor_args* anchor = x.anchor;
   const cfd_tie_args* tie = x.tie;
+  const cfd_replay_args* replay = x.replay;
   if (wtab && args->G != 7) return fail(CFD_E_ARG, "%s: a weight table needs the 7-chunk guidance batch (G = %d)", x.opener, args->G);
   if (c->run_open) return fail(CFD_E_STATE, "a sampling run is already open");
   HIPCHK(hipSetDevice(c->cfg.device));
@@ -318,12 +321,13 @@ static int sample_begin(Ctx* c, const cfd_sample_args* args, void* stream, const
                 s.num_inference_steps, s.num_train_timesteps);
   if (s.preseq && (s.preseq_len < 1 || s.preseq_len > s.L)) return fail(CFD_E_ARG, "bad preseq_len");
   const int n_iter = s.timesteps ? s.num_timesteps : s.num_inference_steps;
-  const int k0 = edit ? edit->first_iteration : 0;
+  const int k0 = edit ? edit->first_iteration : replay ? replay->first_iteration : 0;
   std::vector<uint8_t> hkeep;
   if (edit && (k0 < 0 || k0 >= n_iter)) return fail(CFD_E_ARG, "cfd_sample_begin_edit: first_iteration = %d is not in [0, %d)", k0, n_iter);
-  const uint8_t* keep_in = edit ? edit->keep : anchor ? anchor->keep : nullptr;
+  if (replay && (k0 < 0 || k0 >= n_iter)) return fail(CFD_E_ARG, "cfd_sample_begin_replay: first_iteration = %d is not in [0, %d)", k0, n_iter);
+  const uint8_t* keep_in = edit ? edit->keep : anchor ? anchor->keep : replay ? replay->keep : nullptr;
   if (keep_in) {
-    const char* who = edit ? "cfd_sample_begin_edit" : "cfd_sample_begin_anchored";
+    const char* who = edit ? "cfd_sample_begin_edit" : anchor ? "cfd_sample_begin_anchored" : "cfd_sample_begin_replay";
     hkeep.resize((size_t)s.B * s.L);
     HIPCHK(hipMemcpy(hkeep.data(), keep_in, hkeep.size(), hipMemcpyDeviceToHost));
     for (size_t e = 0; e < hkeep.size(); ++e)
@@ -528,6 +532,15 @@ static int sample_begin(Ctx* c, const cfd_sample_args* args, void* stream, const
     c->run.anchor_ring = anchor->trajectory;
     c->run.anchor_n = anchor->steps;
   }
+  if (replay) {   // the anchored instance over the noise space's trajectory; the opener pointed init_latents / step_noise into the rings
+    CHK(upload_keep_mask(c, hkeep, (size_t)s.B * s.L, st));
+    HIPCHK(hipStreamSynchronize(st));   // (hkeep goes out of scope)
+    c->run.anchor = c->run.replay = true;
+    c->run.anchor_ring = replay->trajectory;
+    c->run.anchor_n = replay->steps;
+    c->run.k0 = k0;
+    c->run_iters = N - k0;
+  }
   // DPM-Solver++: the x0 history of the run, zeroed.  The first executed iteration is first order and never reads it, so the eager warm-up
   // iteration below, which runs as that iteration and writes its x0 here, needs no save / restore: the first replay overwrites that before
   // anything reads it.
@@ -656,6 +669,174 @@ extern "C" int cfd_sample_begin_anchored(cfd_handle c, const cfd_sample_args* ar
   BeginExt x{"cfd_sample_begin_anchored", weights, prune, chunks_evaluated};
   x.anchor = an;
   return sample_begin(c, args, stream, x);
+}
+
+extern "C" int cfd_sample_begin_replay(cfd_handle c, const cfd_sample_args* args, const cfd_replay_args* r, const float* weights, int prune,
+                                       int* chunks_evaluated, void* stream) {
+  if (!c || !args || !r) return fail(CFD_E_ARG, "null argument");
+  if (!r->trajectory || !r->noise) return fail(CFD_E_ARG, "cfd_sample_begin_replay: the trajectory or the noise is NULL");
+  if (args->scheduler != 0) return fail(CFD_E_ARG, "cfd_sample_begin_replay: a noise space is replayed by a DDPM run (scheduler 0, not %d)", args->scheduler);
+  if (args->preseq) return fail(CFD_E_ARG, "cfd_sample_begin_replay: a replay has no preseq");
+  if (args->dynamic_memory_mask)
+    return fail(CFD_E_ARG, "cfd_sample_begin_replay: a replay takes no dynamic memories (dynamic_memory_mask = %d)", args->dynamic_memory_mask);
+  const int n_iter = args->timesteps ? args->num_timesteps : args->num_inference_steps;
+  if (r->steps != n_iter || r->B != args->B || r->L != args->L)
+    return fail(CFD_E_ARG, "cfd_sample_begin_replay: the noise space is [%d][%d][%d][128], this run has %d iterations of [%d][%d][128]", r->steps,
+                r->B, r->L, n_iter, args->B, args->L);
+  if (r->first_iteration < 0 || r->first_iteration >= n_iter)
+    return fail(CFD_E_ARG, "cfd_sample_begin_replay: first_iteration = %d is not in [0, %d)", r->first_iteration, n_iter);
+  cfd_sample_args s = *args;   // the run starts from the level iteration k0 enters and takes the recorded noise as its step noise
+  s.init_latents = r->trajectory + (size_t)(n_iter - r->first_iteration) * args->B * args->L * CFD_LAT;
+  s.step_noise = r->noise;
+  BeginExt x{"cfd_sample_begin_replay", weights, prune, chunks_evaluated};
+  x.replay = r;
+  return sample_begin(c, &s, stream, x);
+}
+
+// ---- edit-friendly DDPM inversion: every level of the table in a few level-batched forwards (cfdenoise.h: cfd_ddpm_invert) ----------
+static void (*const ddpm_extract_kernel_weighted)(const ExtractArgs) = ddpm_extract_kernel<0, true>;   // (one macro argument for LAUNCH)
+
+extern "C" int cfd_ddpm_invert(cfd_handle c, const cfd_sample_args* args, const cfd_ddpm_invert_args* inv, int* chunks_evaluated,
+                               int* levels_per_batch_used, void* stream) {
+  if (!c || !args || !inv) return fail(CFD_E_ARG, "null argument");
+  if (!inv->source || !inv->trajectory || !inv->noise) return fail(CFD_E_ARG, "cfd_ddpm_invert: the source, the trajectory or the noise is NULL");
+  if (args->scheduler != 0) return fail(CFD_E_ARG, "cfd_ddpm_invert: the noise space is a DDPM run's (scheduler 0, not %d)", args->scheduler);
+  if (args->preseq) return fail(CFD_E_ARG, "cfd_ddpm_invert takes no preseq (the rollout's prefix in-painting)");
+  if (args->dynamic_memory_mask) return fail(CFD_E_ARG, "cfd_ddpm_invert takes no dynamic memories (dynamic_memory_mask = %d)", args->dynamic_memory_mask);
+  for (int j = 0; j < CFD_NMEM; ++j)
+    if (args->att_ring[j]) return fail(CFD_E_ARG, "cfd_ddpm_invert keeps no attention maps (att_ring)");
+  if (inv->levels_per_batch < 0) return fail(CFD_E_ARG, "cfd_ddpm_invert: levels_per_batch = %d", inv->levels_per_batch);
+  if (c->run_open) return fail(CFD_E_STATE, "a sampling run is open on this handle");
+  const float* wtab = inv->weights;
+  if (wtab && args->G != 7) return fail(CFD_E_ARG, "cfd_ddpm_invert: a weight table needs the 7-chunk guidance batch (G = %d)", args->G);
+  const cfd_sample_args& s = *args;
+  if (s.B < 1 || s.L < 2 || s.G < 1 || s.G > 8) return fail(CFD_E_ARG, "bad B / L / G");
+  if (!s.alphas_cumprod || s.num_train_timesteps < 1 || s.num_inference_steps < 1 || s.num_inference_steps > s.num_train_timesteps)
+    return fail(CFD_E_ARG, "bad scheduler tables");
+  if (s.timesteps && (s.num_timesteps < 1 || s.num_timesteps > s.num_train_timesteps)) return fail(CFD_E_ARG, "bad num_timesteps");
+  if (!s.timesteps && s.num_train_timesteps % s.num_inference_steps)
+    return fail(CFD_E_ARG, "DDPM: num_inference_steps = %d does not divide num_train_timesteps = %d; pass the scheduler's table in "
+                           "cfd_sample_args.timesteps", s.num_inference_steps, s.num_train_timesteps);
+  HIPCHK(hipSetDevice(c->cfg.device));
+  c->hint_now = c->hint_same_mem = false;
+  CHK(settle_deferred_census(c));
+  hipStream_t st = (hipStream_t)stream;
+  const int B = s.B, L = s.L, n_inf = s.num_inference_steps, N = s.timesteps ? s.num_timesteps : n_inf, T = s.num_train_timesteps;
+  // the evaluated chunks and their memories' row maps, as a run with these arguments would have them (weighted_chunks works on c->sargs)
+  c->sargs = s;
+  c->sargs.timesteps = nullptr;
+  cfd_memory mem_in[CFD_NMEM];
+  for (int j = 0; j < CFD_NMEM; ++j) mem_in[j] = s.mem[j];
+  ExtractArgs xa;
+  memset(&xa, 0, sizeof(xa));
+  if (wtab) {
+    int keep_idx[8];
+    CHK(weighted_chunks(c, wtab, inv->prune, N, false, mem_in, keep_idx, st));
+    for (int k = 0; k < 8; ++k) xa.pos[k] = keep_idx[k] >= 0 ? keep_idx[k] : 0;
+    xa.Gc = 7;
+    xa.wtab = c->wtab.as<float>();
+  } else {
+    if (s.skip_zero_weight_chunks)
+      while (c->sargs.G > 1 && s.guidance_weight[c->sargs.G - 1] == 0.0f) c->sargs.G -= 1;
+    for (int k = 0; k < 8; ++k) { xa.pos[k] = k < c->sargs.G ? k : 0; xa.w[k] = s.guidance_weight[k]; }
+    xa.Gc = c->sargs.G;
+  }
+  const int Ge = c->sargs.G, R = Ge * B;   // rows of a level
+  // J from the workspace budget: what setup_problem allocates per level (token rows and the memories' per-forward projections)
+  size_t per_level = 0;
+  {
+    int sp_tot = 0;
+    for (int j = 0; j < CFD_NMEM; ++j) {
+      if (mem_in[j].U < 1 || mem_in[j].S < 1) return fail(CFD_E_ARG, "memory %s: null/empty", MEM_NAMES[j]);
+      const size_t sp = (size_t)(mem_in[j].S + 31) / 32 * 32;
+      sp_tot += (int)sp;
+      per_level += (size_t)mem_in[j].U * sp * ((size_t)CFD_D * 4 * (1 + 2 * c->nl) + 4 * (c->nl + 1));
+    }
+    per_level += (size_t)R * L * ((size_t)CFD_D * 4 * 6 + (size_t)CFD_FF * 4 + (size_t)sp_tot * 8 + CFD_LAT * 8) +
+                 (size_t)R * ((size_t)CFD_D * 64 * 4 + (size_t)CFD_NHEAD * L * ((L + 31) / 32 * 32) * 8);
+  }
+  // (default 4 GiB: at the product shape ~150 levels for one utterance, ~40 for eight; measured 0.042 s at J = 100 against 0.059 s at
+  //  J = 41 and 0.187 s at J = 40 against 0.279 s at J = 8 for N = 1000, profiles/r13_ddpm_inversion_time.json.  per_level is an estimate
+  //  of what setup_problem allocates, not an enforced cap)
+  const size_t budget = inv->workspace_bytes ? inv->workspace_bytes : (size_t)4 << 30;
+  long long J = inv->levels_per_batch ? inv->levels_per_batch : (long long)(budget / per_level);
+  J = std::max<long long>(1, std::min<long long>({J, (long long)N, 32768 / R > 0 ? 32768 / R : 1}));   // (a launch's grid: at most 32768 batch rows)
+  const int Be = (int)J * R;
+  // the level batch's memories: instance lv * U + u = the caller's memory u at level lv, through level row maps; masks once per level
+  cfd_memory vm[CFD_NMEM];
+  {
+    std::vector<int> hm(R), lm((size_t)Be);
+    for (int j = 0; j < CFD_NMEM; ++j) {
+      const int U = mem_in[j].U;
+      if (mem_in[j].row_map) {
+        HIPCHK(hipMemcpy(hm.data(), mem_in[j].row_map, (size_t)R * 4, hipMemcpyDeviceToHost));
+      } else {
+        if (U != R) return fail(CFD_E_ARG, "memory %s: U = %d != G * B = %d without a row_map", MEM_NAMES[j], U, R);
+        for (int r = 0; r < R; ++r) hm[r] = r;
+      }
+      for (int r = 0; r < R; ++r)
+        if (hm[r] < 0 || hm[r] >= U) return fail(CFD_E_ARG, "memory %s: row_map[%d] = %d outside [0, %d)", MEM_NAMES[j], r, hm[r], U);
+      for (int lv = 0; lv < (int)J; ++lv)
+        for (int r = 0; r < R; ++r) lm[(size_t)lv * R + r] = lv * U + hm[r];
+      CHK(c->lv_map[j].ensure((size_t)Be * 4));
+      HIPCHK(hipMemcpy(c->lv_map[j].p, lm.data(), (size_t)Be * 4, hipMemcpyHostToDevice));
+      vm[j] = mem_in[j];
+      vm[j].row_map = c->lv_map[j].as<int32_t>();
+      vm[j].U = (int)J * U;
+      if (mem_in[j].key_padding_mask) {
+        const size_t mb = (size_t)U * mem_in[j].S;
+        CHK(c->lv_mask[j].ensure(mb * (size_t)J));
+        for (int lv = 0; lv < (int)J; ++lv)
+          HIPCHK(hipMemcpy(c->lv_mask[j].as<uint8_t>() + (size_t)lv * mb, mem_in[j].key_padding_mask, mb, hipMemcpyDeviceToDevice));
+        vm[j].key_padding_mask = c->lv_mask[j].as<uint8_t>();
+      }
+    }
+  }
+  c->want_f16 = false;   // (operands are split pairs throughout)
+  CHK(setup_problem(c, Be, L, vm, nullptr, 2, N));
+  Problem& pb = c->w->pb;
+  pb.lv_rows = R;
+  pb.lv_i0 = 0;
+  for (int j = 0; j < CFD_NMEM; ++j) pb.lv_U[j] = mem_in[j].U;
+  std::vector<int32_t> ts(N);
+  std::vector<StepCoef> coef(N);
+  for (int i = 0; i < N; ++i) ts[i] = s.timesteps ? s.timesteps[i] : (N - 1 - i) * (T / n_inf);
+  CHK(step_coefficients(0, s.alphas_cumprod, T, n_inf, ts.data(), N, 0.f, 1, coef.data()));
+  CHK(c->coef.ensure((size_t)N * sizeof(StepCoef)));
+  HIPCHK(hipMemcpyAsync(c->coef.p, coef.data(), (size_t)N * sizeof(StepCoef), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemsetAsync(c->w->d_step.p, 0, 16, st));
+  CHK(sat_begin(c, st));
+  CHK(build_time_tables(c, ts.data(), N, st));   // every level's rows, once (a replay over the same table finds them built)
+  CHK(prepare_static_memside(c, st, 0, false));  // (tmode 2: the scale planes only; the projections are made per level in the forward)
+  HIPCHK(hipStreamSynchronize(st));              // ts / coef host vectors go out of scope
+  const size_t lat_bytes = (size_t)B * L * CFD_LAT * 4;
+  HIPCHK(hipMemcpyAsync(inv->trajectory, inv->source, lat_bytes, hipMemcpyDeviceToDevice, st));   // slot 0: the source
+  LevelArgs la{inv->source, inv->level_noise, inv->trajectory, c->w->sample_sp.as<char>(), c->coef.as<StepCoef>(), B, L, Ge, N, 0, (int)J,
+               (unsigned long long)s.seed, s.first_utterance};
+  xa.eps = c->w->eps.as<float>(); xa.traj = inv->trajectory; xa.noise = inv->noise; xa.coef = c->coef.as<StepCoef>();
+  xa.B = B; xa.L = L; xa.G = Ge; xa.N = N; xa.J = (int)J; xa.clip = s.clip_sample;
+  const long long n8 = (long long)J * B * L * (CFD_LAT / 8);
+  const dim3 grid((unsigned)((n8 + 255) / 256)), block(256);
+  // Batches from the noisiest levels' end of the table downwards: the noise of iteration i needs slot N - i - 1, the level of iteration
+  // i + 1 (the source for the last one), which the batch before has built.  The last batch starts at iteration 0 whatever N % J is, so
+  // that one problem set-up and one work list serve every batch: the levels it shares with the batch before are evaluated again and
+  // their rows written again -- the trajectory slots to the same bits, the noise rows to the re-association between two batch
+  // compositions (measured 4e-7); what stays is the last batch's.
+  for (int hi = N; hi > 0; hi -= (int)J) {
+    const int i0 = std::max(hi - (int)J, 0);
+    pb.lv_i0 = la.i0 = xa.i0 = i0;
+    LAUNCH(CFD_PROF_OTHER, ddpm_level_kernel<>, grid, block, st, la);
+    CHK(enqueue_denoise(c, st));
+    if (wtab) LAUNCH(CFD_PROF_OTHER, ddpm_extract_kernel_weighted, grid, block, st, xa);
+    else LAUNCH(CFD_PROF_OTHER, ddpm_extract_kernel<>, grid, block, st, xa);
+  }
+  // the per-level projections count into the handle's census: read here, so that a clamped projection fails THIS call
+  HIPCHK(hipStreamSynchronize(st));
+  c->memside_in_forward = false;
+  CHK(check_saturation(c, "cfd_ddpm_invert (source levels, memories / their per-level projections)"));
+  if (chunks_evaluated) *chunks_evaluated = Ge;
+  if (levels_per_batch_used) *levels_per_batch_used = (int)J;
+  return CFD_OK;
 }
 
 extern "C" int cfd_sample_census(cfd_handle c, cfd_census* out) {
@@ -871,6 +1052,7 @@ extern "C" int cfd_sample_write(cfd_handle c, const float* latents) {
   if (!c || !latents) return fail(CFD_E_ARG, "null argument");
   if (!c->run_open) return fail(CFD_E_STATE, "no sampling run open");
   if (c->sargs.scheduler == 3) return fail(CFD_E_ARG, "cfd_sample_write: a DDIM inversion run takes no WEG update (its latents are its own)");
+  if (c->run.replay) return fail(CFD_E_ARG, "cfd_sample_write: the replay of a noise space takes no WEG update (its noise was solved for the recorded levels)");
   HIPCHK(hipSetDevice(c->cfg.device));
   const size_t lat_bytes = (size_t)c->sargs.B * c->sargs.L * CFD_LAT * 4;
   HIPCHK(hipMemcpyAsync(c->latents.p, latents, lat_bytes, hipMemcpyDeviceToDevice, c->run_stream));

@@ -82,6 +82,24 @@ struct MemPrepArgs {
   char* n_sp;         // SP [U*Sp][512]
 };
 
+// A live row of the memory preparation, shared by mem_prep_kernel and mem_prep_level_kernel (which differ only in which raw instance and
+// which table row an output instance reads): lane's 8 floats of normalise(raw + temb + cond + pe).
+__device__ __forceinline__ void mem_prep_vals(const float* r, const float* te, const float* ce, const float* pe, float v[8]) {
+  float sum = 0.f;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    v[e] = ((te[e] + r[e]) + ce[e]) + pe[e];
+    sum += v[e];
+  }
+  const float mean = wave_sum(sum) * (1.0f / CFD_D);
+  float ss = 0.f;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) { v[e] -= mean; ss += v[e] * v[e]; }
+  const float rstd = 1.0f / sqrtf(wave_sum(ss) * (1.0f / CFD_D) + 1e-5f);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) v[e] *= rstd;
+}
+
 template <int CFD_KI = 0>
 __global__ void __launch_bounds__(256) mem_prep_kernel(const MemPrepArgs a) {
   const int lane = threadIdx.x & 63;
@@ -97,19 +115,7 @@ __global__ void __launch_bounds__(256) mem_prep_kernel(const MemPrepArgs a) {
     const float* te = a.temb + (long long)(a.tmode ? u : *a.d_step) * CFD_D + lane * 8;
     const float* ce = a.cond + lane * 8;
     const float* pe = a.pe + (long long)s * CFD_D + lane * 8;
-    float sum = 0.f;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      v[e] = ((te[e] + r[e]) + ce[e]) + pe[e];
-      sum += v[e];
-    }
-    const float mean = wave_sum(sum) * (1.0f / CFD_D);
-    float ss = 0.f;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { v[e] -= mean; ss += v[e] * v[e]; }
-    const float rstd = 1.0f / sqrtf(wave_sum(ss) * (1.0f / CFD_D) + 1e-5f);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] *= rstd;
+    mem_prep_vals(r, te, ce, pe, v);
   }
   sp_store8(a.n_sp + row * (CFD_D * 4), lane * 8, v);
 }
@@ -531,6 +537,15 @@ __host__ __device__ __forceinline__ float dpmpp_prev(const StepCoef& c, float x,
   return c.c0 * x - c.cx * x0;
 }
 
+// The deterministic part of a scheduler step, shared by the loop's step (cfg_step_kernel) and its inverse (ddpm_extract_kernel): the x0
+// estimate with its optional clip, and DDPM's posterior mean.  One definition, so the two cannot drift apart.
+__host__ __device__ __forceinline__ float step_x0(const StepCoef& c, int clip, float x, float eps) {
+  float x0 = (x - c.sb * eps) / c.sa;
+  if (clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+  return x0;
+}
+__host__ __device__ __forceinline__ float ddpm_mu(const StepCoef& c, float x0, float x) { return c.c0 * x0 + c.cx * x; }
+
 // Philox4x32-10 (restated in oracle/philox_ref.py, checked there against the Random123 known answers)
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
                                               uint32_t k1, uint32_t out[4]) {
@@ -781,11 +796,10 @@ __global__ void cfg_step_kernel(const CfgStepArgsOf<WTAB, TRAJ> a) {
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const float eps = (a.G > 1) ? u[q] + acc[q] : u[q];
-    float x0 = (x[q] - c.sb * eps) / c.sa;
-    if (a.clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+    const float x0 = step_x0(c, a.clip, x[q], eps);
     x0v[q] = x0;
     float prev;
-    if (a.kind == 0) prev = c.c0 * x0 + c.cx * x[q];
+    if (a.kind == 0) prev = ddpm_mu(c, x0, x[q]);
     else if (a.kind == 2) prev = dpmpp_prev(c, x[q], x0, m1[q]);
     else prev = c.c0 * x0 + c.cx * eps;
     if (c.use_noise != 0.f) prev = prev + c.sigma * z[q];
@@ -808,6 +822,130 @@ __global__ void cfg_step_kernel(const CfgStepArgsOf<WTAB, TRAJ> a) {
       }
     }
   }
+}
+
+// ---- edit-friendly DDPM inversion (cfd_ddpm_invert) ---------------------------------------------------------------------------------
+// Level construction for the J levels i0 .. i0 + J - 1 of a batch: slot N - i of the trajectory = fl(fl(sa_i * src) + fl(sb_i * eps_i))
+// (edit_mix8's arithmetic: a replay that starts at level k0 starts from what an edit run at k0 with the same draw starts from), and the
+// value replicated G times into the split-pair denoiser input, level-major: row ((lv * G + g) * B + b) * L + l.  eps_i: the caller's
+// [N][B][L][128], or Philox stream 2 with step index i.  One thread = 8 elements.
+struct LevelArgs {
+  const float* src;      // [B][L][128]
+  const float* eps;      // [N][B][L][128] or null
+  float* traj;           // [N + 1][B][L][128]
+  char* sample_sp;       // SP [J * G * B * L][128]
+  const StepCoef* coef;  // [N]
+  int B, L, G, N, i0, J;
+  unsigned long long seed;
+  unsigned int utt0;
+};
+template <int CFD_KI = 0>
+__global__ void ddpm_level_kernel(const LevelArgs a) {
+  const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long long n8 = (long long)a.B * a.L * (CFD_LAT / 8);
+  if (idx >= n8 * a.J) return;
+  const int lv = (int)(idx / n8), i = a.i0 + lv;
+  const long long r = idx % n8, bl = r / (CFD_LAT / 8);
+  const int c = (int)(r % (CFD_LAT / 8)) * 8;
+  const int l = (int)(bl % a.L), b = (int)(bl / a.L);
+  const long long chunk = n8 * 8, o = bl * CFD_LAT + c;
+  float s[8], e[8], v[8];
+  load8(a.src + o, s);
+  if (a.eps) {
+    load8(a.eps + (long long)i * chunk + o, e);
+  } else {
+    const uint32_t g = (uint32_t)((l * CFD_LAT + c) / 4);
+    const float4 z0 = philox_normal4(a.seed, g, (uint32_t)i, a.utt0 + b, 2u), z1 = philox_normal4(a.seed, g + 1, (uint32_t)i, a.utt0 + b, 2u);
+    e[0] = z0.x; e[1] = z0.y; e[2] = z0.z; e[3] = z0.w; e[4] = z1.x; e[5] = z1.y; e[6] = z1.z; e[7] = z1.w;
+  }
+  const float sa = a.coef[i].sa, sb = a.coef[i].sb;
+#pragma unroll
+  for (int q = 0; q < 8; ++q) v[q] = __fadd_rn(__fmul_rn(sa, s[q]), __fmul_rn(sb, e[q]));
+  store8(a.traj + (long long)(a.N - i) * chunk + o, v);
+  for (int g = 0; g < a.G; ++g)
+    sp_store8(a.sample_sp + ((((long long)lv * a.G + g) * a.B + b) * a.L + l) * (CFD_LAT * 4), c, v);
+}
+
+// Noise extraction for the J levels of a batch, from the G predictions of every level (level-major rows, as ddpm_level_kernel wrote the
+// input): the guidance combine term for term as cfg_step_kernel's, x0 / clip / mu through step_x0 / ddpm_mu, then
+// z_i = (slot[N - i - 1] - mu) / sigma_i, or exactly 0 where the DDPM row adds no noise.  WTAB: weights from the table row i.  One thread =
+// 8 elements.
+struct ExtractArgs {
+  const float* eps;      // [J][G][B][L][128]
+  const float* traj;     // [N + 1][B][L][128]
+  float* noise;          // [N][B][L][128]
+  const StepCoef* coef;
+  int B, L, G, N, i0, J;
+  int Gc;                // chunks of the combine (7 for a weighted run, else G)
+  float w[8];
+  int pos[8];            // chunk k's rows within a level start at row pos[k] * B
+  int clip;
+  const float* wtab;     // WTAB: [N][B][8]
+};
+template <int CFD_KI = 0, bool WTAB = false>
+__global__ void ddpm_extract_kernel(const ExtractArgs a) {
+  const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long long n8 = (long long)a.B * a.L * (CFD_LAT / 8);
+  if (idx >= n8 * a.J) return;
+  const int lv = (int)(idx / n8), i = a.i0 + lv;
+  const long long o = (idx % n8) * 8, chunk = n8 * 8;
+  const StepCoef c = a.coef[i];
+  const float* lev = a.eps + (long long)lv * a.G * chunk + o;
+  float u[8], acc[8], x[8], nx[8], z[8];
+  load8(lev + (long long)a.pos[0] * chunk, u);
+  load8(a.traj + (long long)(a.N - i) * chunk + o, x);
+  load8(a.traj + (long long)(a.N - i - 1) * chunk + o, nx);
+  const float* wrow = nullptr;
+  if constexpr (WTAB) wrow = a.wtab + ((long long)i * a.B + o / ((long long)a.L * CFD_LAT)) * 8;   // (8 elements never straddle two utterances)
+#pragma unroll
+  for (int q = 0; q < 8; ++q) acc[q] = 0.f;
+  // reference association: ((((text + audio) + spk) + apb) + lsnid) + all, each = (g*w)*(e_k - e_0)
+  for (int k = 1; k < a.Gc; ++k) {
+    float e[8];
+    load8(lev + (long long)a.pos[k] * chunk, e);
+    const float wk = WTAB ? wrow[k] : a.w[k];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const float term = wk * (e[q] - u[q]);
+      acc[q] = (k == 1) ? term : acc[q] + term;
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 8; ++q) {
+    const float eps = (a.Gc > 1) ? u[q] + acc[q] : u[q];
+    const float mu = ddpm_mu(c, step_x0(c, a.clip, x[q], eps), x[q]);
+    z[q] = c.use_noise != 0.f ? (nx[q] - mu) / c.sigma : 0.f;
+  }
+  store8(a.noise + (long long)i * chunk + o, z);
+}
+
+// mem_prep_kernel for a level batch (Problem::tmode 2): instance u of the launch is distinct memory u % U0 of the caller's U0 at level
+// u / U0 of the batch, whose timestep embedding is table row trow0 + u / U0.  The memory-side work of a level is thus done once per
+// distinct instance; the level's rows reach it through the level row maps.
+struct MemPrepLevelArgs {
+  const float* raw;   // [U0][S][512]
+  int U0, U, S, Sp;   // U = J * U0
+  const float* temb;  // [T][512]
+  int trow0;
+  const float* cond;
+  const float* pe;
+  char* n_sp;         // SP [U * Sp][512]
+};
+template <int CFD_KI = 0>
+__global__ void __launch_bounds__(256) mem_prep_level_kernel(const MemPrepLevelArgs a) {
+  const int lane = threadIdx.x & 63;
+  const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= (long long)a.U * a.Sp) return;
+  const int u = (int)(row / a.Sp), s = (int)(row % a.Sp);
+  float v[8];
+  if (s >= a.S) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = 0.f;
+  } else {
+    mem_prep_vals(a.raw + ((long long)(u % a.U0) * a.S + s) * CFD_D + lane * 8, a.temb + (long long)(a.trow0 + u / a.U0) * CFD_D + lane * 8,
+                  a.cond + lane * 8, a.pe + (long long)s * CFD_D + lane * 8, v);
+  }
+  sp_store8(a.n_sp + row * (CFD_D * 4), lane * 8, v);
 }
 
 // Start of an edit run at iteration k0 > 0 (cfd_sample_begin_edit, img2img): every token = fl(fl(sa * src) + fl(sb * eps)) with coef row

@@ -74,8 +74,18 @@ def shard_tie(tie, start, stop, total):
     return torch.where(tied, local - start * L, local).to(tie.dtype)
 
 
+def shard_noise_space(noise_space, start, stop, total):
+    """The utterances [start, stop) of a noise space (trajectory [N + 1, total, L, 128], noise [N, total, L, 128]): both rings sliced on
+    the utterance axis, contiguous."""
+    trajectory, noise = noise_space
+    for name, t in (("trajectory", trajectory), ("noise", noise)):
+        if t.dim() != 4 or t.shape[1] != total:
+            raise ValueError(f"noise_space: {name} has shape {list(t.shape)} for {total} utterances")
+    return trajectory[:, start:stop].contiguous(), noise[:, start:stop].contiguous()
+
+
 def sample_sharded(sample_fn, encoder_hidden_states, cond_masks, total_utterances, chunks=7, group=None, modality_weights=None,
-                   source_latents=None, keep_mask=None, tie=None):
+                   source_latents=None, keep_mask=None, tie=None, noise_space=None):
     """Run ``sample_fn(enc_shard, masks_shard, B=<local>, first_utterance=<global id>)`` on this rank's
     utterances and return the gathered latents [total, L, 128] on every rank.  A ``sample_fn`` with ``operands="auto"`` decides PER RANK:
     each rank's census sees its own utterances only, so one rank may fall back to ``operands=0`` while another keeps the default policy
@@ -84,7 +94,9 @@ def sample_sharded(sample_fn, encoder_hidden_states, cond_masks, total_utterance
     ``modality_weights=`` with this rank's utterances (``shard_modality_weights``).  ``source_latents`` [total, L, 128] / ``keep_mask``
     [total, L] (optional, an edit run): ``sample_fn`` gets this rank's rows of each under the same names.  ``tie`` [total, L] (optional,
     a tied run): ``sample_fn`` gets ``tie=`` with this rank's rows renumbered to its slice (``shard_tie``); a tie that crosses the slice is
-    refused -- keep the rows that are tied to each other (the windows of one utterance) on one rank."""
+    refused -- keep the rows that are tied to each other (the windows of one utterance) on one rank.  ``noise_space`` (optional, the
+    replay of an edit-friendly DDPM noise space): the pair (trajectory [N + 1, total, L, 128], noise [N, total, L, 128]); ``sample_fn`` gets
+    ``noise_space=`` with this rank's rows of both rings (``shard_noise_space``), next to its rows of ``keep_mask``."""
     ws = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     a, b = shard_range(total_utterances, rank, ws)
@@ -100,5 +112,7 @@ def sample_sharded(sample_fn, encoder_hidden_states, cond_masks, total_utterance
             extra[name] = t[a:b]
     if tie is not None:
         extra["tie"] = shard_tie(tie, a, b, total_utterances)
+    if noise_space is not None:
+        extra["noise_space"] = shard_noise_space(noise_space, a, b, total_utterances)
     local = sample_fn(enc, masks, B=b - a, first_utterance=a, **extra)
     return gather_latents(local, total_utterances, group)

@@ -108,7 +108,8 @@ def edit_motion(model, feats, lengths, encoder_hidden_states, cond_masks=None, *
 
 
 def reperform_motion(model, feats, lengths, source_conditioning, target_conditioning, *, source_masks=None, target_masks=None,
-                     num_inference_steps=50, keep_mask=None, inversion_weights=None, modality_weights=None, operands=None):
+                     num_inference_steps=50, keep_mask=None, inversion_weights=None, modality_weights=None, operands=None,
+                     method="ddim", strength=1.0, seed=0, levels_per_batch=None):
     """Re-perform motions under new conditioning.  ``model`` / ``feats`` / ``lengths``: as in ``edit_motion``; source_conditioning /
     target_conditioning (+ their masks): the 7-chunk guidance batches of the recorded motion's conditioning and of the new one.
       1. HIP encode of the source to its posterior mean (loop layout);
@@ -118,8 +119,16 @@ def reperform_motion(model, feats, lengths, source_conditioning, target_conditio
          the inverted latents under the target conditioning at model.guidance_scale with ``modality_weights`` (None: the model's installed
          weights, else the reference's); the tokens of ``keep_mask`` [B, L] are anchored to the inversion's trajectory;
       4. HIP decode.
-    Returns (features [B, nframes, 189], loop latents [B, L, 128], inverted latents [B, L, 128])."""
+    Returns (features [B, nframes, 189], loop latents [B, L, 128], inverted latents [B, L, 128]).
+    ``method="ddpm"``: the edit-friendly DDPM noise space instead, with the model's OWN scheduler (DDPM, clip_sample as configured) and
+    its own step count (cfg.model.scheduler.num_inference_timesteps; num_inference_steps is not used): ``sampler.invert_ddpm`` under the
+    source conditioning (``seed`` keys the level draws, ``levels_per_batch`` as there), then the replay under the target conditioning with
+    ``keep_mask`` / ``strength`` (``sample(..., noise_space=)``, split-pair operands).  The third return value is then the noisiest level,
+    trajectory[N].  Under the source conditioning the replay reproduces the source up to the last step, which adds no noise and returns
+    the model's own x0 estimate.  ``method="ddim"`` (the default) is unchanged."""
     from .scheduler import DDIMInverseScheduler, DDIMScheduler
+    if method not in ("ddim", "ddpm"):
+        raise ValueError(f"method must be 'ddim' or 'ddpm', not {method!r}")
     if not model.do_classifier_free_guidance:
         raise NameError("guidance_bs_mulitplier: the reference loop requires classifier-free guidance")
     latent, dist, _ = model.vae.encode(feats, lengths)
@@ -130,6 +139,22 @@ def reperform_motion(model, feats, lengths, source_conditioning, target_conditio
         if cond[0].shape[0] != G * B:
             raise ValueError(f"{name} has {cond[0].shape[0]} rows for {B} motions and {G} chunks")
     sch = model.scheduler
+    if method == "ddpm":
+        from .sampler import invert_ddpm
+        if getattr(sch, "KIND", None) != 0:
+            raise TypeError("reperform_motion(method='ddpm') needs the model's scheduler to be a convofusion_amd.scheduler.DDPMScheduler")
+        n = model.cfg.model.scheduler.num_inference_timesteps
+        space = invert_ddpm(model.denoiser, sch, source_conditioning, source_masks, source_latents=source, num_inference_steps=n,
+                            guidance_scale=1.0 if inversion_weights is None else model.guidance_scale, modality_weights=inversion_weights,
+                            seed=seed, levels_per_batch=levels_per_batch)
+        if modality_weights is None:
+            modality_weights = getattr(model, "_cfd_modality_weights", None)
+        lat = sample(model.denoiser, sch, target_conditioning, target_masks, B=B, L=L, num_inference_steps=n,
+                     guidance_scale=model.guidance_scale, guidance_chunks=G, skip_zero_weight_chunks=True, operands=operands,
+                     modality_weights=modality_weights, noise_space=space, keep_mask=keep_mask, strength=strength)
+        return model.vae.decode(loop_to_vae(lat), lengths), lat, space[0][-1]
+    if float(strength) != 1.0:
+        raise ValueError("strength belongs to method='ddpm' (the DDIM path regenerates from the fully inverted latents)")
     kw = dict(num_train_timesteps=sch.config.num_train_timesteps, trained_betas=sch.betas.tolist(), clip_sample=False,
               set_alpha_to_one=sch.config.get("set_alpha_to_one", True), steps_offset=sch.config.get("steps_offset", 0))
     ops = check_operands(getattr(model, "_cfd_operands", None) if operands is None else operands)

@@ -190,6 +190,35 @@ def check_anchor(trajectory, keep_mask, B, L, N, device=None):
     return trajectory.detach().to(device=device, dtype=torch.float32).contiguous(), _check_keep_mask(keep_mask, B, L, device)
 
 
+def check_noise_space(noise_space, keep_mask, strength, B, L, N, device=None, *, scheduler_kind=0, preseq=None, source_latents=None,
+                      anchor_trajectory=None, tie=None, dynamic_memories=()):
+    """The noise space of a replay run (``SamplingRun(noise_space=)``, cfd_sample_begin_replay): (trajectory float32 [N + 1, B, L, 128] and
+    noise float32 [N, B, L, 128] contiguous on ``device``, keep mask uint8 [B, L] or None, k0 = ``edit_first_iteration(strength, N)``).
+    Refusals (ValueError), each before any device work: a scheduler other than DDPM, preseq, source_latents, anchor_trajectory, tie or
+    dynamic memories next to it, a pair other than two floating-point tensors of those shapes (N = the run's iterations: the inversion must
+    have as many), a keep mask other than a bool or integer [B, L] tensor of 0 / 1, a strength outside (0, 1]."""
+    if scheduler_kind != 0:
+        raise ValueError("noise_space: an edit-friendly DDPM noise space is replayed by a DDPMScheduler run")
+    for name, v in (("preseq", preseq), ("source_latents", source_latents), ("anchor_trajectory", anchor_trajectory), ("tie", tie)):
+        if v is not None:
+            raise ValueError(f"noise_space and {name} do not go together (the replay's kept tokens and its start come from the trajectory)")
+    if dynamic_memories:
+        raise ValueError("noise_space: a replay takes no dynamic memories (a dyadic run)")
+    try:
+        trajectory, noise = noise_space
+    except (TypeError, ValueError):
+        raise ValueError("noise_space must be the pair (trajectory, noise) of invert_ddpm") from None
+    for name, t, shape in (("trajectory", trajectory, (N + 1, B, L, 128)), ("noise", noise, (N, B, L, 128))):
+        if not isinstance(t, torch.Tensor) or not t.is_floating_point():
+            raise ValueError(f"noise_space: {name} must be a floating-point tensor {list(shape)}")
+        if tuple(t.shape) != shape:
+            raise ValueError(f"noise_space: {name} must be {list(shape)} (an inversion with the run's N = {N} iterations, B and L), not "
+                             f"{list(t.shape)}")
+    k0 = edit_first_iteration(strength, N)
+    return (trajectory.detach().to(device=device, dtype=torch.float32).contiguous(),
+            noise.detach().to(device=device, dtype=torch.float32).contiguous(), _check_keep_mask(keep_mask, B, L, device), k0)
+
+
 def check_tie(tie, keep_mask, B, L, device=None, *, preseq=None, strength=1.0, scheduler_kind=None, anchored=False, dynamic_memories=()):
     """The tie table of a tied run (``SamplingRun(tie=)``, cfd_sample_begin_tied): None when the run has none, else the table as int32
     [B, L] contiguous on ``device``.  Entry [b, l] is -1 (a free token) or the flat index b' * L + l' of the token whose value token (b, l)
@@ -371,7 +400,7 @@ class SamplingRun:
                  seed=0, first_utterance=0, preseq=None, dedup=True, skip_zero_weight_chunks=False, row_maps=None,
                  dynamic_memories=(), side_engine=False, attention_ring=False, operands=None, census_tau=None, modality_weights=None,
                  prune_zero_weight_chunks=True, source_latents=None, keep_mask=None, strength=1.0, trajectory=False,
-                 anchor_trajectory=None, tie=None):
+                 anchor_trajectory=None, tie=None, noise_space=None):
         """attention_ring: keep the attention maps of the full-conditioning chunk of EVERY iteration (the reference's per-iteration dict,
         convofusion.py:517-523): the captured iteration stores them into ``self.att_ring`` -- five tensors [iterations, B, layers, L, S_j]
         -- with no extra forward and no host round trip (cfd_sample_args.att_ring: the row-tile kernels store them from their second
@@ -410,7 +439,13 @@ class SamplingRun:
         b' * L + l' of the token that token (b, l) copies at the start of every iteration (the source as the previous iteration left it)
         and once more after the last one: ``read()`` of the finished run has every tied token bit-identical to its source, ``read()``
         before that the latents as the scheduler left them.  Goes with source_latents / keep_mask at strength 1, modality_weights, the
-        attention ring and every scheduler but the inverse one; ``write`` (WEG) is refused.  None: the run's usual entry point."""
+        attention ring and every scheduler but the inverse one; ``write`` (WEG) is refused.  None: the run's usual entry point.
+        noise_space / keep_mask / strength (DDPMScheduler): the replay of an edit-friendly DDPM noise space (``invert_ddpm``,
+        cfd_sample_begin_replay, ``check_noise_space``): the pair (trajectory [N + 1, B, L, 128], noise [N, B, L, 128]).  The run starts
+        from trajectory[N - k0] (k0 from ``strength`` as for an edit: the paper's T_skip), iteration i takes noise[i] as its step noise, and
+        the tokens with keep_mask = 1 are set to trajectory[N - i] at the start of iteration i.  init_latents / step_noise are not taken.
+        ``operands`` None or "auto" means 0 here whatever OPERAND_POLICY says: the inversion ran on split pairs, and a replay on single-fp16
+        audio tiles would not close.  Both rings are read in place: the run keeps references.  ``write`` (WEG) is refused."""
         if not isinstance(denoiser, Denoiser):
             raise TypeError("denoiser must be a convofusion_amd.denoiser.Denoiser")
         dev = encoder_hidden_states[0].device
@@ -443,8 +478,20 @@ class SamplingRun:
             keep_mask = None
         self.tie = check_tie(tie, keep_mask, B, L, dev, preseq=preseq, strength=strength, scheduler_kind=scheduler.KIND,
                              anchored=anchor_trajectory is not None, dynamic_memories=dynamic_memories)
+        replay = None
+        if noise_space is not None:
+            if init_latents is not None or step_noise is not None:
+                raise ValueError("noise_space: the replay takes its initial latents and step noise from the noise space (no init_latents / "
+                                 "step_noise)")
+            replay = check_noise_space(noise_space, keep_mask, strength, B, L, n_full, dev, scheduler_kind=scheduler.KIND, preseq=preseq,
+                                       source_latents=source_latents, anchor_trajectory=anchor_trajectory, tie=tie,
+                                       dynamic_memories=dynamic_memories)
+            keep_mask, strength = None, 1.0
+            if operands is None or operands is _AUTO_RUN or operands == "auto":
+                operands = 0
+        self.replay = replay is not None
         edit = check_edit(source_latents, keep_mask, strength, B, L, n_full, preseq, dev)
-        self.first_iteration = edit[2] if edit is not None else 0
+        self.first_iteration = edit[2] if edit is not None else (replay[3] if replay is not None else 0)
         self.timesteps = [int(t) for t in table][self.first_iteration:]
         self.B, self.L, self.N = B, L, len(self.timesteps)     # N = loop iterations executed
         G = guidance_chunks
@@ -532,7 +579,12 @@ class SamplingRun:
         stream = torch.cuda.current_stream(dev).cuda_stream
         # the optional parts of the run, each built once (the anchor trajectory is read in place for the whole run: _keep) ...
         w_ptr = self.modality_weights.ctypes.data_as(C.c_void_p) if self.modality_weights is not None else None
-        e = an = ta = None
+        e = an = ta = rp = None
+        if replay is not None:
+            rp = _lib.ReplayArgs()
+            rp.trajectory, rp.noise, rp.steps, rp.B, rp.L = replay[0].data_ptr(), replay[1].data_ptr(), n_full, B, L
+            rp.keep, rp.first_iteration = (replay[2].data_ptr() if replay[2] is not None else None), replay[3]
+            self._keep += [replay[0], replay[1], replay[2], rp]
         if edit is not None:
             e = _lib.EditArgs()
             e.source, e.keep, e.first_iteration = edit[0].data_ptr(), (edit[1].data_ptr() if edit[1] is not None else None), edit[2]
@@ -553,6 +605,8 @@ class SamplingRun:
             opener, extra = self.lib.cfd_sample_begin_invert, (C.c_void_p(self.trajectory.data_ptr()),)
         elif an is not None:
             opener, extra = self.lib.cfd_sample_begin_anchored, (C.byref(an),)
+        elif rp is not None:
+            opener, extra = self.lib.cfd_sample_begin_replay, (C.byref(rp),)
         elif e is not None:
             opener, extra = self.lib.cfd_sample_begin_edit, (C.byref(e),)
         else:
@@ -624,6 +678,8 @@ class SamplingRun:
         """Overwrite the current latents of the open run (the WEG update between two iterations)."""
         if self.tie is not None:
             raise ValueError("a tied run takes no WEG update (write): its tied tokens are overwritten from their sources every iteration")
+        if self.replay:
+            raise ValueError("a replay of a noise space takes no WEG update (write): its noise was solved for the recorded levels")
         if tuple(latents.shape) != (self.B, self.L, 128):
             raise ValueError(f"latents must be [{self.B}, {self.L}, 128]")
         lat = latents.detach().to(device=self.device, dtype=torch.float32).contiguous()
@@ -708,7 +764,7 @@ def _open_run(denoiser, scheduler, encoder_hidden_states, cond_masks, B, L, num_
     CFD_E_SHAPE from cfd_sample_begin -- a plain run, and the caller takes the maps with one forward per iteration (``last_step_attention``)."""
     if want_ring:
         n_it = len(scheduler.timestep_table(num_inference_steps)[1])
-        if kw.get("source_latents") is not None:      # an edit run executes the iterations from k0 on (its ring has that many slots)
+        if kw.get("source_latents") is not None or kw.get("noise_space") is not None:      # an edit run / a replay executes the iterations from k0 on (its ring has that many slots)
             n_it -= edit_first_iteration(kw.get("strength", 1.0), n_it)
         keys = sum(int(m.shape[1]) for m in encoder_hidden_states)
         budget = ATT_RING_MAX_BYTES
@@ -734,7 +790,7 @@ def sample(denoiser, scheduler, encoder_hidden_states, cond_masks=None, *, B, L=
            guidance_scale=7.5, guidance_chunks=CFG_CHUNKS, eta=0.0, init_latents=None, step_noise=None, seed=0,
            first_utterance=0, preseq=None, dedup=True, skip_zero_weight_chunks=False, row_maps=None, return_attention=False, operands=None,
            modality_weights=None, prune_zero_weight_chunks=True, source_latents=None, keep_mask=None, strength=1.0, anchor_trajectory=None,
-           tie=None):
+           tie=None, noise_space=None):
     """Run the whole loop; returns latents [B, L, 128] (batch-first); with ``return_attention=True`` also the last
     iteration's attention maps (``last_step_attention``), with ``return_attention="all"`` a dict {timestep: maps} over every
     iteration like the reference's: kept by the captured iteration itself (``SamplingRun(attention_ring=True)``) while the ring fits
@@ -749,7 +805,11 @@ def sample(denoiser, scheduler, encoder_hidden_states, cond_masks=None, *, B, L=
     attention dict then holds the executed iterations.  ``anchor_trajectory`` / ``keep_mask``: a re-conditioning run over a recorded DDIM
     inversion (``invert``), as in ``SamplingRun``.  With a ``DDIMInverseScheduler`` and ``init_latents`` = the source the loop is a DDIM
     inversion: the same latents as ``invert`` with the same guidance.  ``tie``: tied tokens (int [B, L], ``check_tie``), as in ``SamplingRun``;
-    None changes nothing."""
+    None changes nothing.  ``noise_space`` = (trajectory, noise) of ``invert_ddpm`` with ``keep_mask`` / ``strength``: the replay of an
+    edit-friendly DDPM noise space, as in ``SamplingRun``; ``operands`` None or "auto" is then 0.  It goes with ``modality_weights`` and
+    pruning and ``return_attention``; tie, preseq, anchor_trajectory, source_latents, init_latents and step_noise are refused."""
+    if noise_space is not None and (operands is None or check_operands(operands) == "auto"):
+        operands = 0
     if check_operands(operands) == "auto":
         args = dict(locals())
         return _with_auto_operands(lambda ops: sample(**dict(args, operands=ops)), "auto")
@@ -758,7 +818,7 @@ def sample(denoiser, scheduler, encoder_hidden_states, cond_masks=None, *, B, L=
                     seed=seed, first_utterance=first_utterance, preseq=preseq, dedup=dedup, skip_zero_weight_chunks=skip_zero_weight_chunks,
                     row_maps=row_maps, operands=operands, modality_weights=modality_weights, prune_zero_weight_chunks=prune_zero_weight_chunks,
                     source_latents=source_latents, keep_mask=keep_mask, strength=strength, anchor_trajectory=anchor_trajectory,
-                    **({} if tie is None else dict(tie=tie)))
+                    **({} if tie is None else dict(tie=tie)), **({} if noise_space is None else dict(noise_space=noise_space)))
     try:
         if not return_attention:
             run.steps(run.N)
@@ -811,6 +871,92 @@ def invert(denoiser, scheduler, encoder_hidden_states, cond_masks=None, *, sourc
         run.steps(run.N)
         lat = run.read(close=True)
         return (lat, run.trajectory) if return_trajectory else lat
+
+
+# Philox stream of the level draws of ``invert_ddpm`` (0: step noise, 1: initial latents)
+LEVEL_NOISE_STREAM = 2
+
+
+def invert_ddpm(denoiser, scheduler, enc, masks=None, *, source_latents, num_inference_steps=1000, guidance_scale=1.0, modality_weights=None,
+                seed=0, level_noise=None, levels_per_batch=None, first_utterance=0, dedup=True, row_maps=None, workspace_bytes=None):
+    """Edit-friendly DDPM inversion (Huberman-Spiegelglas et al., CVPR 2024) of ``source_latents`` [B, L, 128] (cfd_ddpm_invert): for every
+    iteration i of the DDPM table an independent level x_i = sqrt(abar_i) source + sqrt(1 - abar_i) eps_i, the guided prediction at every
+    level under the conditioning ``enc`` / ``masks`` (the 7-chunk guidance batch, as for ``sample``), and the step noise
+    z_i = (x_{i+1} - mu_i(x_i)) / sigma_i that makes the DDPM loop walk these levels.  The N evaluations are independent and run as a few
+    large forwards of ``levels_per_batch`` levels each (None: chosen from a workspace budget, ``workspace_bytes``, 4 GiB by default), on
+    split-pair operands.  ``scheduler``: a ``DDPMScheduler`` (clip_sample honoured).  The guidance is the weighted combine with
+    ``modality_weights`` at ``guidance_scale``; None: INVERSION_WEIGHTS at guidance_scale 1, as for ``invert``.  ``level_noise``
+    [N, B, L, 128]: the eps_i; None: Philox stream LEVEL_NOISE_STREAM keyed by ``seed``, step index i, utterance first_utterance + b.
+    Returns (trajectory [N + 1, B, L, 128], noise [N, B, L, 128]): slot 0 of the trajectory is the source, slot N - i the level entering
+    iteration i; noise[i] is iteration i's step noise, exactly 0 for the last iteration (t = 0 adds none).  Pass the pair to
+    ``sample(..., noise_space=, keep_mask=, strength=)``.  ``invert_ddpm.last`` holds dict(chunks_evaluated, levels_per_batch) of the
+    last call."""
+    if not isinstance(denoiser, Denoiser):
+        raise TypeError("denoiser must be a convofusion_amd.denoiser.Denoiser")
+    if getattr(scheduler, "KIND", None) != 0:
+        raise TypeError("invert_ddpm needs a convofusion_amd.scheduler.DDPMScheduler")
+    if not isinstance(source_latents, torch.Tensor) or not source_latents.is_floating_point() or source_latents.dim() != 3 \
+            or int(source_latents.shape[2]) != 128:
+        raise ValueError("source_latents must be a floating-point tensor [B, L, 128]")
+    B, L = int(source_latents.shape[0]), int(source_latents.shape[1])
+    num_inference_steps, table = scheduler.timestep_table(num_inference_steps)
+    N = len(table)
+    if levels_per_batch is not None and (isinstance(levels_per_batch, bool) or int(levels_per_batch) != levels_per_batch
+                                         or int(levels_per_batch) < 1):
+        raise ValueError(f"levels_per_batch must be a positive integer or None, not {levels_per_batch!r}")
+    if level_noise is not None and (not isinstance(level_noise, torch.Tensor) or not level_noise.is_floating_point()
+                                    or tuple(level_noise.shape) != (N, B, L, 128)):
+        raise ValueError(f"level_noise must be a floating-point tensor [N, B, L, 128] = [{N}, {B}, {L}, 128]")
+    weights = modality_weight_table(INVERSION_WEIGHTS if modality_weights is None else modality_weights, guidance_scale, N, B, CFG_CHUNKS)
+    dev = enc[0].device
+    if dev.type != "cuda":
+        raise RuntimeError("the fused sampler runs on an MI355X only (no CPU fallback)")
+    G = CFG_CHUNKS
+    if row_maps is not None:
+        if any(int(m.numel()) != G * B for m in row_maps):
+            raise ValueError(f"row_maps must have G*B = {G * B} entries")
+        mems, maps, mks = list(enc), list(row_maps), dict(masks or {})
+    elif enc[0].shape[0] != G * B:
+        raise ValueError(f"conditioning batch is {enc[0].shape[0]} rows, expected G*B = {G * B}")
+    elif dedup:
+        mems, maps, mks = dedup_memories(enc, masks)
+    else:
+        mems, maps, mks = list(enc), None, dict(masks or {})
+    lib = _lib.load()
+    handle = denoiser.engine(dev, mem_len=max(int(m.shape[1]) for m in mems))
+    marr, keep = Denoiser.pack_memories(mems, mks, maps)
+    a = _lib.SampleArgs()
+    a.B, a.L, a.G = B, L, G
+    a.scheduler = 0
+    a.num_train_timesteps = scheduler.config.num_train_timesteps
+    a.num_inference_steps = num_inference_steps
+    a.clip_sample = 1 if scheduler.config.get("clip_sample", False) else 0
+    acp = scheduler.alphas_cumprod.detach().to("cpu", torch.float32).contiguous()
+    a.alphas_cumprod = acp.data_ptr()
+    a.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    a.first_utterance = int(first_utterance)
+    a.mem = marr
+    ts = (C.c_int32 * N)(*[int(t) for t in table])
+    a.timesteps, a.num_timesteps = C.cast(ts, C.c_void_p), N
+    src = source_latents.detach().to(device=dev, dtype=torch.float32).contiguous()
+    eps = level_noise.detach().to(device=dev, dtype=torch.float32).contiguous() if level_noise is not None else None
+    trajectory = torch.empty((N + 1, B, L, 128), dtype=torch.float32, device=dev)
+    noise = torch.empty((N, B, L, 128), dtype=torch.float32, device=dev)
+    iv = _lib.DdpmInvertArgs()
+    iv.source, iv.weights, iv.prune = src.data_ptr(), weights.ctypes.data_as(C.c_void_p), 1
+    iv.level_noise = eps.data_ptr() if eps is not None else None
+    iv.trajectory, iv.noise = trajectory.data_ptr(), noise.data_ptr()
+    iv.levels_per_batch = int(levels_per_batch or 0)
+    iv.workspace_bytes = int(workspace_bytes or 0)
+    g_eval, j_used = C.c_int(0), C.c_int(0)
+    with torch.cuda.device(dev):
+        torch.cuda.current_stream(dev).synchronize()
+        _lib.check(lib.cfd_ddpm_invert(handle, C.byref(a), C.byref(iv), C.byref(g_eval), C.byref(j_used),
+                                       C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    del keep, acp, ts
+    _lib.wrote(trajectory, noise)
+    invert_ddpm.last = dict(chunks_evaluated=int(g_eval.value), levels_per_batch=int(j_used.value))
+    return trajectory, noise
 
 
 # the WEG constants diffusion_reverse_forecast hard-codes instead of reading cfg.model.weg_parameters (unbounded_synthesis.py:80-84)
@@ -871,6 +1017,8 @@ def sample_with_weg(denoiser, scheduler, encoder_hidden_states, cond_masks, focu
         args = dict(locals())
         rest = args.pop("kw")
         return _with_auto_operands(lambda ops: sample_with_weg(**args, **dict(rest, operands=ops)), "auto")
+    if kw.get("noise_space") is not None:
+        raise NotImplementedError("sample_with_weg: the replay of a noise space (noise_space) takes no word-excitation guidance")
     if getattr(scheduler, "KIND", None) == 3:
         raise NotImplementedError("sample_with_weg: a DDIM inversion (DDIMInverseScheduler) takes no word-excitation guidance -- its latents "
                                   "are its own; use invert() or sample() without focus_indices")

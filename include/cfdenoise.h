@@ -267,6 +267,53 @@ typedef struct {
  * value other than 0 / 1. */
 int cfd_sample_begin_anchored(cfd_handle h, const cfd_sample_args* args, const cfd_anchor_args* a, const float* weights, int prune,
                               int* chunks_evaluated, void* stream);
+/* Edit-friendly DDPM inversion (Huberman-Spiegelglas et al., CVPR 2024): the noise space of a DDPM run that reproduces `source`.  For
+ * every iteration i of the DDPM table (timestep t_i, N entries) an INDEPENDENT level x_i = fl(fl(sa_i * source) + fl(sb_i * eps_i)) is
+ * drawn, the guided prediction is evaluated at every level under the run's conditioning, and the DDPM step is solved for its noise:
+ *   z_i = (x_{i+1} - mu_i(x_i, eps_hat_i)) / sigma_i        (x_N = source; z_i = 0 exactly where the step adds none: t_i = 0)
+ * with mu_i = c0 * x0 + cx * x_i, x0 = clip((x_i - sb * eps_hat) / sa), evaluated as the DDPM loop's step evaluates them.  The N
+ * evaluations do not depend on each other: they run as ceil(N / J) denoiser forwards of J levels each (J * G_eval * B * L token rows with
+ * per-level timesteps), enqueued on `stream` with no host synchronisation between them; the memory-side work of a forward is done once
+ * per (level, distinct memory instance) -- the rows of a level reach their instance through the run's row maps. */
+typedef struct {
+  const float* source;        /* dev [B][L][128] float32 */
+  const float* weights;       /* HOST float32 [N][B][8] or NULL, with `prune`: as in cfd_sample_begin_weighted (NULL: args->guidance_weight
+                                 and args->skip_zero_weight_chunks) */
+  int prune;
+  const float* level_noise;   /* dev [N][B][L][128] eps_i, or NULL: Philox stream 2, step index i, utterance first_utterance + b (a draw
+                                 per level, independent of the others and of streams 0 / 1) */
+  float* trajectory;          /* out, dev [N + 1][B][L][128]: slot 0 the source, slot N - i the level x_i ENTERING iteration i (slot N the
+                                 noisiest) -- the convention of cfd_sample_begin_invert's ring */
+  float* noise;               /* out, dev [N][B][L][128]: row i = z_i, the step noise of iteration i */
+  int levels_per_batch;       /* J; 0: chosen from workspace_bytes */
+  size_t workspace_bytes;     /* budget of the level batch's workspace (0: 4 GiB); J is the largest count the library's estimate of a level's
+                                 workspace fits into it, at least 1 */
+} cfd_ddpm_invert_args;
+/* `args`: the cfd_sample_args of the DDPM run (scheduler 0, its timestep table, memories with row maps, clip_sample honoured;
+ * init_latents / step_noise / att_ring unused).  *chunks_evaluated / *levels_per_batch_used (may be NULL) receive G_eval and J.
+ * CFD_E_ARG: a scheduler other than 0, preseq, a dynamic memory, att_ring, a NULL source / trajectory / noise, a weight table with a
+ * non-finite entry.  CFD_E_STATE: a sampling run is open on the handle. */
+int cfd_ddpm_invert(cfd_handle h, const cfd_sample_args* args, const cfd_ddpm_invert_args* inv, int* chunks_evaluated,
+                    int* levels_per_batch_used, void* stream);
+/* Replay of a recorded noise space (cfd_ddpm_invert). */
+typedef struct {
+  const float* trajectory;    /* dev [steps + 1][B][L][128]; read in place until the run is closed */
+  const float* noise;         /* dev [steps][B][L][128]; read in place: iteration i takes noise[i] as its step noise */
+  int steps;                  /* iterations of the inversion; must equal this run's iterations */
+  int B;                      /* must equal args->B */
+  int L;                      /* must equal args->L */
+  const uint8_t* keep;        /* dev [B][L] uint8 0 / 1 or NULL (= all 0): at the start of iteration i the tokens with keep = 1 are set
+                                 to trajectory[steps - i] */
+  int first_iteration;        /* k0 in [0, steps): the paper's T_skip.  The run starts from trajectory[steps - k0] and executes iterations
+                                 k0 .. steps - 1; counting (cfd_sample_position, weight-table row, att_ring slot) as in cfd_edit_args */
+} cfd_replay_args;
+/* A DDPM run (args->scheduler == 0) over a recorded noise space; args->init_latents / step_noise are ignored (they come from the rings).
+ * Weights / prune / chunks_evaluated as in cfd_sample_begin_edit.  With keep all 0 / NULL and first_iteration = 0 the run computes what
+ * cfd_sample_begin(_weighted) with init_latents = trajectory[steps] and step_noise = noise computes, bit for bit.  CFD_E_ARG: a NULL
+ * argument, trajectory or noise, another scheduler, steps / B / L other than the run's, first_iteration outside [0, steps), preseq, a
+ * dynamic memory, a keep value other than 0 / 1.  A replay has no tied form, and cfd_sample_write (a WEG update) refuses it. */
+int cfd_sample_begin_replay(cfd_handle h, const cfd_sample_args* args, const cfd_replay_args* r, const float* weights, int prune,
+                            int* chunks_evaluated, void* stream);
 /* Replays the captured iteration `n` more times (asynchronously on the run's stream). */
 int cfd_sample_steps(cfd_handle h, int n);
 /* Number of iterations executed so far in the open run. */

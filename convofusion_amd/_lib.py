@@ -25,7 +25,7 @@ SYMBOLS = [
     "cfd_layer_norm_bwd", "cfd_ew", "cfd_weg_focus", "cfd_sample_write", "cfd_sample_inpaint", "cfd_weg_eval", "cfd_dyadic_steps",
     "cfd_sample_census", "cfd_dpmsolver_step", "cfd_test_step_coefficients", "cfd_test_gemm_epi",
     "cfd_vae_encode", "cfd_sample_begin_weighted", "cfd_sample_begin_edit", "cfd_sample_begin_invert", "cfd_sample_begin_anchored",
-    "cfd_sample_begin_tied", "cfd_ddpm_invert", "cfd_sample_begin_replay",
+    "cfd_sample_begin_tied", "cfd_ddpm_invert", "cfd_sample_begin_replay", "cfd_sample_parallel", "cfd_test_picard_stride",
 ]
 
 
@@ -91,6 +91,19 @@ class DdpmInvertArgs(C.Structure):
     workspace budget in bytes, 0: 4 GiB)."""
     _fields_ = [("source", C.c_void_p), ("weights", C.c_void_p), ("prune", C.c_int), ("level_noise", C.c_void_p), ("trajectory", C.c_void_p),
                 ("noise", C.c_void_p), ("levels_per_batch", C.c_int), ("workspace_bytes", C.c_size_t)]
+
+
+class ParallelArgs(C.Structure):
+    """cfd_parallel_args: HOST weight table [N][B][8] or NULL with prune, the tolerance, levels per batch (0: from the workspace budget in
+    bytes, 0: 4 GiB), max_sweeps (0: N), the outputs latents (dev [B][L][128]) and trajectory (dev [N + 1][B][L][128] or NULL)."""
+    _fields_ = [("weights", C.c_void_p), ("prune", C.c_int), ("tolerance", C.c_float), ("levels_per_batch", C.c_int),
+                ("workspace_bytes", C.c_size_t), ("max_sweeps", C.c_int), ("latents", C.c_void_p), ("trajectory", C.c_void_p)]
+
+
+class ParallelStats(C.Structure):
+    """cfd_parallel_stats: J, G_eval and the sweeps of a cfd_sample_parallel call; strides: HOST int32 [strides_capacity] or NULL."""
+    _fields_ = [("levels_per_batch", C.c_int), ("chunks_evaluated", C.c_int), ("sweeps", C.c_int), ("strides", C.c_void_p),
+                ("strides_capacity", C.c_int)]
 
 
 class ReplayArgs(C.Structure):
@@ -197,6 +210,7 @@ def load():
                                               C.POINTER(C.c_int), C.c_void_p]
     lib.cfd_ddpm_invert.argtypes = [C.c_void_p, C.POINTER(SampleArgs), C.POINTER(DdpmInvertArgs), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                     C.c_void_p]
+    lib.cfd_sample_parallel.argtypes = [C.c_void_p, C.POINTER(SampleArgs), C.POINTER(ParallelArgs), C.POINTER(ParallelStats), C.c_void_p]
     lib.cfd_sample_begin_replay.argtypes = [C.c_void_p, C.POINTER(SampleArgs), C.POINTER(ReplayArgs), C.c_void_p, C.c_int,
                                             C.POINTER(C.c_int), C.c_void_p]
     lib.cfd_sample_steps.argtypes = [C.c_void_p, C.c_int]
@@ -209,6 +223,7 @@ def load():
                                        C.c_void_p, C.c_size_t, C.c_void_p]
     lib.cfd_test_step_coefficients.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_int,
                                                C.POINTER(C.c_float)]
+    lib.cfd_test_picard_stride.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_int]
     lib.cfd_add_noise.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_size_t, C.c_void_p]
     lib.cfd_philox_normal.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint32,

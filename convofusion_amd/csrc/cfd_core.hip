@@ -96,6 +96,7 @@ extern "C" void cfd_destroy(cfd_handle c) {
     c->wk_all_sp[j].release(); c->wv_all_sp[j].release(); c->mem_own[j].release(); c->perm_map[j].release();
     c->lv_map[j].release(); c->lv_mask[j].release();
   }
+  c->pic_s.release(); c->pic_part.release(); c->pic_err.release();
   for (auto& l : c->lw) {
     DBuf* lb[] = {&l.wqk_f, &l.wv_f, &l.w1_f, &l.ln_cd, &l.wqk_sp, &l.bqk, &l.wv_sp, &l.wo_sp, &l.bo2, &l.wtb1_sp, &l.wtb2_sp, &l.w1_sp, &l.w2_sp, &l.cross_bias};
     for (DBuf* b : lb) b->release();

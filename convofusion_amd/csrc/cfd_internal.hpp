@@ -315,7 +315,8 @@ struct cfd_handle_s {
   RunMode run;
   int wpos[8];
   DBuf wtab, esrc, enoise, ekeep, etie;
-  DBuf lv_map[CFD_NMEM], lv_mask[CFD_NMEM];   // cfd_ddpm_invert: the level row maps and the key-padding masks once per level
+  DBuf lv_map[CFD_NMEM], lv_mask[CFD_NMEM];   // level batches: the level row maps and the key-padding masks once per level
+  DBuf pic_s, pic_part, pic_err;              // cfd_sample_parallel: the levels' steps [J][B][L][128], the error partials and sums
   int run_pos = 0;
 };
 typedef cfd_handle_s Ctx;

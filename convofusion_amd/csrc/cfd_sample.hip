@@ -693,23 +693,37 @@ extern "C" int cfd_sample_begin_replay(cfd_handle c, const cfd_sample_args* args
   return sample_begin(c, &s, stream, x);
 }
 
-// ---- edit-friendly DDPM inversion: every level of the table in a few level-batched forwards (cfdenoise.h: cfd_ddpm_invert) ----------
+// ---- level batches: J noise levels of one run as one forward (Problem::tmode 2; cfd_ddpm_invert, cfd_sample_parallel) ----------------
 static void (*const ddpm_extract_kernel_weighted)(const ExtractArgs) = ddpm_extract_kernel<0, true>;   // (one macro argument for LAUNCH)
+static void (*const picard_step_kernel_weighted)(const PicardStepArgs) = picard_step_kernel<0, true>;
 
-extern "C" int cfd_ddpm_invert(cfd_handle c, const cfd_sample_args* args, const cfd_ddpm_invert_args* inv, int* chunks_evaluated,
-                               int* levels_per_batch_used, void* stream) {
-  if (!c || !args || !inv) return fail(CFD_E_ARG, "null argument");
-  if (!inv->source || !inv->trajectory || !inv->noise) return fail(CFD_E_ARG, "cfd_ddpm_invert: the source, the trajectory or the noise is NULL");
-  if (args->scheduler != 0) return fail(CFD_E_ARG, "cfd_ddpm_invert: the noise space is a DDPM run's (scheduler 0, not %d)", args->scheduler);
-  if (args->preseq) return fail(CFD_E_ARG, "cfd_ddpm_invert takes no preseq (the rollout's prefix in-painting)");
-  if (args->dynamic_memory_mask) return fail(CFD_E_ARG, "cfd_ddpm_invert takes no dynamic memories (dynamic_memory_mask = %d)", args->dynamic_memory_mask);
+// What a level batch's callers refuse alike (`who`: the entry point, for the message)
+static int level_batch_refusals(Ctx* c, const cfd_sample_args* args, const char* who, const char* why0, int levels_per_batch) {
+  if (args->scheduler != 0) return fail(CFD_E_ARG, "%s: %s (scheduler 0, not %d)", who, why0, args->scheduler);
+  if (args->preseq) return fail(CFD_E_ARG, "%s takes no preseq (the rollout's prefix in-painting)", who);
+  if (args->dynamic_memory_mask) return fail(CFD_E_ARG, "%s takes no dynamic memories (dynamic_memory_mask = %d)", who, args->dynamic_memory_mask);
   for (int j = 0; j < CFD_NMEM; ++j)
-    if (args->att_ring[j]) return fail(CFD_E_ARG, "cfd_ddpm_invert keeps no attention maps (att_ring)");
-  if (inv->levels_per_batch < 0) return fail(CFD_E_ARG, "cfd_ddpm_invert: levels_per_batch = %d", inv->levels_per_batch);
+    if (args->att_ring[j]) return fail(CFD_E_ARG, "%s keeps no attention maps (att_ring)", who);
+  if (levels_per_batch < 0) return fail(CFD_E_ARG, "%s: levels_per_batch = %d", who, levels_per_batch);
   if (c->run_open) return fail(CFD_E_STATE, "a sampling run is open on this handle");
-  const float* wtab = inv->weights;
-  if (wtab && args->G != 7) return fail(CFD_E_ARG, "cfd_ddpm_invert: a weight table needs the 7-chunk guidance batch (G = %d)", args->G);
-  const cfd_sample_args& s = *args;
+  return CFD_OK;
+}
+
+// The guidance combine of a level batch and its sizes, as level_batch_setup leaves them
+struct LevelBatch {
+  int B, L, N, Ge, J;
+  int Gc;                // chunks of the combine (7 for a weighted run, else Ge)
+  float w[8];
+  int pos[8];            // chunk k's rows within a level start at row pos[k] * B
+  const float* wtab;     // dev [N][B][8] or null
+};
+
+// Everything a level batch needs before its first forward: the evaluated chunks and their row maps, J from the workspace budget, the
+// level row maps and masks, the problem (tmode 2, table of N rows), the step coefficients and the time tables; the saturation census is
+// opened and the stream waited for.  The caller sets Problem::lv_i0 per batch and reads the census at its end.
+static int level_batch_setup(Ctx* c, const cfd_sample_args& s, const char* who, const float* wtab, int prune, int levels_per_batch,
+                             size_t workspace_bytes, hipStream_t st, LevelBatch* lb) {
+  if (wtab && s.G != 7) return fail(CFD_E_ARG, "%s: a weight table needs the 7-chunk guidance batch (G = %d)", who, s.G);
   if (s.B < 1 || s.L < 2 || s.G < 1 || s.G > 8) return fail(CFD_E_ARG, "bad B / L / G");
   if (!s.alphas_cumprod || s.num_train_timesteps < 1 || s.num_inference_steps < 1 || s.num_inference_steps > s.num_train_timesteps)
     return fail(CFD_E_ARG, "bad scheduler tables");
@@ -720,26 +734,24 @@ extern "C" int cfd_ddpm_invert(cfd_handle c, const cfd_sample_args* args, const 
   HIPCHK(hipSetDevice(c->cfg.device));
   c->hint_now = c->hint_same_mem = false;
   CHK(settle_deferred_census(c));
-  hipStream_t st = (hipStream_t)stream;
   const int B = s.B, L = s.L, n_inf = s.num_inference_steps, N = s.timesteps ? s.num_timesteps : n_inf, T = s.num_train_timesteps;
   // the evaluated chunks and their memories' row maps, as a run with these arguments would have them (weighted_chunks works on c->sargs)
   c->sargs = s;
   c->sargs.timesteps = nullptr;
   cfd_memory mem_in[CFD_NMEM];
   for (int j = 0; j < CFD_NMEM; ++j) mem_in[j] = s.mem[j];
-  ExtractArgs xa;
-  memset(&xa, 0, sizeof(xa));
+  memset(lb, 0, sizeof(*lb));
   if (wtab) {
     int keep_idx[8];
-    CHK(weighted_chunks(c, wtab, inv->prune, N, false, mem_in, keep_idx, st));
-    for (int k = 0; k < 8; ++k) xa.pos[k] = keep_idx[k] >= 0 ? keep_idx[k] : 0;
-    xa.Gc = 7;
-    xa.wtab = c->wtab.as<float>();
+    CHK(weighted_chunks(c, wtab, prune, N, false, mem_in, keep_idx, st));
+    for (int k = 0; k < 8; ++k) lb->pos[k] = keep_idx[k] >= 0 ? keep_idx[k] : 0;
+    lb->Gc = 7;
+    lb->wtab = c->wtab.as<float>();
   } else {
     if (s.skip_zero_weight_chunks)
       while (c->sargs.G > 1 && s.guidance_weight[c->sargs.G - 1] == 0.0f) c->sargs.G -= 1;
-    for (int k = 0; k < 8; ++k) { xa.pos[k] = k < c->sargs.G ? k : 0; xa.w[k] = s.guidance_weight[k]; }
-    xa.Gc = c->sargs.G;
+    for (int k = 0; k < 8; ++k) { lb->pos[k] = k < c->sargs.G ? k : 0; lb->w[k] = s.guidance_weight[k]; }
+    lb->Gc = c->sargs.G;
   }
   const int Ge = c->sargs.G, R = Ge * B;   // rows of a level
   // J from the workspace budget: what setup_problem allocates per level (token rows and the memories' per-forward projections)
@@ -758,8 +770,8 @@ extern "C" int cfd_ddpm_invert(cfd_handle c, const cfd_sample_args* args, const 
   // (default 4 GiB: at the product shape ~150 levels for one utterance, ~40 for eight; measured 0.042 s at J = 100 against 0.059 s at
   //  J = 41 and 0.187 s at J = 40 against 0.279 s at J = 8 for N = 1000, profiles/r13_ddpm_inversion_time.json.  per_level is an estimate
   //  of what setup_problem allocates, not an enforced cap)
-  const size_t budget = inv->workspace_bytes ? inv->workspace_bytes : (size_t)4 << 30;
-  long long J = inv->levels_per_batch ? inv->levels_per_batch : (long long)(budget / per_level);
+  const size_t budget = workspace_bytes ? workspace_bytes : (size_t)4 << 30;
+  long long J = levels_per_batch ? levels_per_batch : (long long)(budget / per_level);
   J = std::max<long long>(1, std::min<long long>({J, (long long)N, 32768 / R > 0 ? 32768 / R : 1}));   // (a launch's grid: at most 32768 batch rows)
   const int Be = (int)J * R;
   // the level batch's memories: instance lv * U + u = the caller's memory u at level lv, through level row maps; masks once per level
@@ -809,12 +821,33 @@ extern "C" int cfd_ddpm_invert(cfd_handle c, const cfd_sample_args* args, const 
   CHK(build_time_tables(c, ts.data(), N, st));   // every level's rows, once (a replay over the same table finds them built)
   CHK(prepare_static_memside(c, st, 0, false));  // (tmode 2: the scale planes only; the projections are made per level in the forward)
   HIPCHK(hipStreamSynchronize(st));              // ts / coef host vectors go out of scope
+  lb->B = B; lb->L = L; lb->N = N; lb->Ge = Ge; lb->J = (int)J;
+  return CFD_OK;
+}
+
+// ---- edit-friendly DDPM inversion: every level of the table in a few level-batched forwards (cfdenoise.h: cfd_ddpm_invert) ----------
+extern "C" int cfd_ddpm_invert(cfd_handle c, const cfd_sample_args* args, const cfd_ddpm_invert_args* inv, int* chunks_evaluated,
+                               int* levels_per_batch_used, void* stream) {
+  if (!c || !args || !inv) return fail(CFD_E_ARG, "null argument");
+  if (!inv->source || !inv->trajectory || !inv->noise) return fail(CFD_E_ARG, "cfd_ddpm_invert: the source, the trajectory or the noise is NULL");
+  CHK(level_batch_refusals(c, args, "cfd_ddpm_invert", "the noise space is a DDPM run's", inv->levels_per_batch));
+  const cfd_sample_args& s = *args;
+  hipStream_t st = (hipStream_t)stream;
+  LevelBatch lb;
+  CHK(level_batch_setup(c, s, "cfd_ddpm_invert", inv->weights, inv->prune, inv->levels_per_batch, inv->workspace_bytes, st, &lb));
+  const int B = lb.B, L = lb.L, N = lb.N, Ge = lb.Ge, J = lb.J;
+  Problem& pb = c->w->pb;
+  ExtractArgs xa;
+  memset(&xa, 0, sizeof(xa));
+  for (int k = 0; k < 8; ++k) { xa.pos[k] = lb.pos[k]; xa.w[k] = lb.w[k]; }
+  xa.Gc = lb.Gc;
+  xa.wtab = lb.wtab;
   const size_t lat_bytes = (size_t)B * L * CFD_LAT * 4;
   HIPCHK(hipMemcpyAsync(inv->trajectory, inv->source, lat_bytes, hipMemcpyDeviceToDevice, st));   // slot 0: the source
-  LevelArgs la{inv->source, inv->level_noise, inv->trajectory, c->w->sample_sp.as<char>(), c->coef.as<StepCoef>(), B, L, Ge, N, 0, (int)J,
+  LevelArgs la{inv->source, inv->level_noise, inv->trajectory, c->w->sample_sp.as<char>(), c->coef.as<StepCoef>(), B, L, Ge, N, 0, J,
                (unsigned long long)s.seed, s.first_utterance};
   xa.eps = c->w->eps.as<float>(); xa.traj = inv->trajectory; xa.noise = inv->noise; xa.coef = c->coef.as<StepCoef>();
-  xa.B = B; xa.L = L; xa.G = Ge; xa.N = N; xa.J = (int)J; xa.clip = s.clip_sample;
+  xa.B = B; xa.L = L; xa.G = Ge; xa.N = N; xa.J = J; xa.clip = s.clip_sample;
   const long long n8 = (long long)J * B * L * (CFD_LAT / 8);
   const dim3 grid((unsigned)((n8 + 255) / 256)), block(256);
   // Batches from the noisiest levels' end of the table downwards: the noise of iteration i needs slot N - i - 1, the level of iteration
@@ -822,12 +855,12 @@ extern "C" int cfd_ddpm_invert(cfd_handle c, const cfd_sample_args* args, const 
   // that one problem set-up and one work list serve every batch: the levels it shares with the batch before are evaluated again and
   // their rows written again -- the trajectory slots to the same bits, the noise rows to the re-association between two batch
   // compositions (measured 4e-7); what stays is the last batch's.
-  for (int hi = N; hi > 0; hi -= (int)J) {
-    const int i0 = std::max(hi - (int)J, 0);
+  for (int hi = N; hi > 0; hi -= J) {
+    const int i0 = std::max(hi - J, 0);
     pb.lv_i0 = la.i0 = xa.i0 = i0;
     LAUNCH(CFD_PROF_OTHER, ddpm_level_kernel<>, grid, block, st, la);
     CHK(enqueue_denoise(c, st));
-    if (wtab) LAUNCH(CFD_PROF_OTHER, ddpm_extract_kernel_weighted, grid, block, st, xa);
+    if (lb.wtab) LAUNCH(CFD_PROF_OTHER, ddpm_extract_kernel_weighted, grid, block, st, xa);
     else LAUNCH(CFD_PROF_OTHER, ddpm_extract_kernel<>, grid, block, st, xa);
   }
   // the per-level projections count into the handle's census: read here, so that a clamped projection fails THIS call
@@ -835,7 +868,115 @@ extern "C" int cfd_ddpm_invert(cfd_handle c, const cfd_sample_args* args, const 
   c->memside_in_forward = false;
   CHK(check_saturation(c, "cfd_ddpm_invert (source levels, memories / their per-level projections)"));
   if (chunks_evaluated) *chunks_evaluated = Ge;
-  if (levels_per_batch_used) *levels_per_batch_used = (int)J;
+  if (levels_per_batch_used) *levels_per_batch_used = J;
+  return CFD_OK;
+}
+
+// The stride of a sweep (cfdenoise.h: cfd_sample_parallel): the largest s in [1, p] with err[k][b] / (L * 128) <= tau^2 * v(i0 + k) for
+// every 1 <= k < s and every b; err[k][b]: the squared change of X(i0 + k), v(i) = sigma_i^2 (an iteration that adds no noise: the value
+// of the iteration before it).  A NaN fails the comparison: the window then moves by the levels in front of it.
+static int picard_stride(const float* err, int B, int p, int i0, const StepCoef* coef, float tau, int L) {
+  int s = 1;
+  for (; s < p; ++s) {
+    int iv = i0 + s;
+    if (coef[iv].use_noise == 0.f && iv > 0) iv -= 1;
+    const float bound = tau * tau * (coef[iv].sigma * coef[iv].sigma);
+    for (int b = 0; b < B; ++b)
+      if (!(err[(size_t)s * B + b] / (float)(L * CFD_LAT) <= bound)) return s;
+  }
+  return s;
+}
+
+// ---- parallel-in-time DDPM sampling: Picard sweeps over level batches (cfdenoise.h: cfd_sample_parallel) ---------------------------
+extern "C" int cfd_sample_parallel(cfd_handle c, const cfd_sample_args* args, const cfd_parallel_args* par, cfd_parallel_stats* stats,
+                                   void* stream) {
+  if (!c || !args || !par) return fail(CFD_E_ARG, "null argument");
+  if (!par->latents) return fail(CFD_E_ARG, "cfd_sample_parallel: the output latents are NULL");
+  if (!(par->tolerance >= 0.f) || !std::isfinite(par->tolerance))
+    return fail(CFD_E_ARG, "cfd_sample_parallel: tolerance = %g is not a finite number >= 0", (double)par->tolerance);
+  if (par->max_sweeps < 0) return fail(CFD_E_ARG, "cfd_sample_parallel: max_sweeps = %d", par->max_sweeps);
+  CHK(level_batch_refusals(c, args, "cfd_sample_parallel", "the window is a DDPM chain's", par->levels_per_batch));
+  const cfd_sample_args& s = *args;
+  hipStream_t st = (hipStream_t)stream;
+  LevelBatch lb;
+  CHK(level_batch_setup(c, s, "cfd_sample_parallel", par->weights, par->prune, par->levels_per_batch, par->workspace_bytes, st, &lb));
+  const int B = lb.B, L = lb.L, N = lb.N, Ge = lb.Ge, J = lb.J;
+  Problem& pb = c->w->pb;
+  std::vector<StepCoef> coef(N);   // (the stride rule's sigma: the rows level_batch_setup uploaded)
+  HIPCHK(hipMemcpy(coef.data(), c->coef.p, (size_t)N * sizeof(StepCoef), hipMemcpyDeviceToHost));
+  const long long chunk = (long long)B * L * CFD_LAT;
+  // the ring: the caller's trajectory, or J + 1 slots of the handle (the window's p + 1 latents; at the end of the table, where the batch
+  // starts in front of the window, the J + 1 latents N - J .. N)
+  PicardRing ring{par->trajectory, N + 1, N, chunk};
+  if (!ring.x) {
+    ring.slots = J + 1;
+    CHK(c->latents.ensure((size_t)ring.slots * chunk * 4));
+    ring.x = c->latents.as<float>();
+  }
+  const int nblk = (L * (CFD_LAT / 4) + 255) / 256;
+  DBuf &sbuf = c->pic_s, &part = c->pic_part, &err = c->pic_err;
+  CHK(sbuf.ensure((size_t)J * chunk * 4));
+  CHK(part.ensure((size_t)J * B * nblk * 4));
+  CHK(err.ensure((size_t)J * B * 4));
+  std::vector<float> herr((size_t)J * B);
+  if (s.init_latents) HIPCHK(hipMemcpyAsync(ring.at(0), s.init_latents, (size_t)chunk * 4, hipMemcpyDeviceToDevice, st));
+  else CHK(enqueue_philox_fill(ring.at(0), B, L * CFD_LAT, (uint64_t)s.seed, 0u, s.first_utterance, 1u, 1.0f, st));
+  const long long n8 = chunk / 8;
+  const dim3 block(256), grid_lv((unsigned)((n8 * J + 255) / 256));
+  auto fill = [&](int src, int lo, int hi) -> int {
+    if (hi < lo) return CFD_OK;
+    LAUNCH(CFD_PROF_OTHER, picard_fill_kernel<>, dim3((unsigned)((n8 * (hi - lo + 1) + 255) / 256)), block, st, ring, src, lo, hi);
+    return CFD_OK;
+  };
+  CHK(fill(0, 1, J));   // every latent of the first window starts from X(0)
+  PicardLoadArgs la{ring, c->w->sample_sp.as<char>(), B, L, Ge, 0, J};
+  PicardStepArgs sa;
+  memset(&sa, 0, sizeof(sa));
+  sa.eps = c->w->eps.as<float>(); sa.ring = ring; sa.s = sbuf.as<float>(); sa.coef = c->coef.as<StepCoef>();
+  sa.B = B; sa.L = L; sa.G = Ge; sa.J = J; sa.Gc = lb.Gc; sa.clip = s.clip_sample; sa.wtab = lb.wtab;
+  for (int k = 0; k < 8; ++k) { sa.w[k] = lb.w[k]; sa.pos[k] = lb.pos[k]; }
+  sa.noise = s.step_noise; sa.seed = s.seed; sa.utt0 = s.first_utterance;
+  PicardScanArgs ca{sbuf.as<float>(), ring, part.as<float>(), L, 0, 0, J};
+  const int max_sweeps = par->max_sweeps ? par->max_sweeps : N;
+  int sweeps = 0;
+  auto sweep = [&](int base, int off) -> int {
+    pb.lv_i0 = la.base = sa.base = ca.base = base;
+    sa.off = ca.off = off;
+    LAUNCH(CFD_PROF_OTHER, picard_load_kernel<>, grid_lv, block, st, la);
+    CHK(enqueue_denoise(c, st));
+    if (lb.wtab) LAUNCH(CFD_PROF_OTHER, picard_step_kernel_weighted, grid_lv, block, st, sa);
+    else LAUNCH(CFD_PROF_OTHER, picard_step_kernel<>, grid_lv, block, st, sa);
+    LAUNCH(CFD_PROF_OTHER, picard_scan_kernel<>, dim3((unsigned)nblk, (unsigned)B), block, st, ca);
+    LAUNCH(CFD_PROF_OTHER, picard_err_kernel<>, dim3((unsigned)((J * B + 255) / 256)), block, st, part.as<float>(), err.as<float>(), J, B, nblk,
+           J - off);
+    HIPCHK(hipMemcpyAsync(herr.data(), err.p, herr.size() * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));   // the one wait of a sweep: the stride is decided on the host
+    return CFD_OK;
+  };
+  for (int i0 = 0; i0 < N;) {
+    if (sweeps >= max_sweeps) {
+      (void)hipStreamSynchronize(st);
+      c->memside_in_forward = false;
+      (void)check_saturation(c, "cfd_sample_parallel");
+      return fail(CFD_E_STATE, "cfd_sample_parallel: max_sweeps = %d reached with %d of %d levels final (tolerance %g, %d levels per batch)",
+                  max_sweeps, i0, N, (double)par->tolerance, J);
+    }
+    const int base = std::min(i0, N - J), off = i0 - base, p = J - off;   // (J <= N; p = min(J, N - i0))
+    CHK(sweep(base, off));
+    const int stride = picard_stride(herr.data(), B, p, i0, coef.data(), par->tolerance, L);
+    if (stats && stats->strides && sweeps < stats->strides_capacity) stats->strides[sweeps] = stride;
+    sweeps += 1;
+    // the levels that enter the window start from its last value, X(i0 + p)
+    const int i1 = i0 + stride;
+    CHK(fill(i0 + p, i0 + p + 1, i1 + std::min(J, N - i1)));
+    i0 = i1;
+  }
+  HIPCHK(hipMemcpyAsync(par->latents, ring.at(N), (size_t)chunk * 4, hipMemcpyDeviceToDevice, st));
+  // the per-level projections count into the handle's census: read here, so that a clamped projection fails THIS call
+  HIPCHK(hipStreamSynchronize(st));
+  c->memside_in_forward = false;
+  CHK((check_saturation(c, "cfd_sample_parallel (window levels, memories / their per-level projections)")));
+  if (stats) { stats->levels_per_batch = J; stats->chunks_evaluated = Ge; stats->sweeps = sweeps; }
   return CFD_OK;
 }
 
@@ -991,6 +1132,13 @@ extern "C" int cfd_dpmsolver_step(cfd_handle c, const float* ac, int T, int t, i
                      sample_inout, x0_out, numel, k);
   HIPCHK(hipGetLastError());
   return CFD_OK;
+}
+
+// ---- developer hook: the stride rule of cfd_sample_parallel, on the host (no handle, no device) --------------------------------------
+extern "C" int cfd_test_picard_stride(const float* err, int B, int p, int i0, const float* coef, int N, float tolerance, int L) {
+  if (!err || !coef || B < 1 || p < 1 || i0 < 0 || i0 + p > N || L < 1 || !(tolerance >= 0.f)) return fail(CFD_E_ARG, "bad argument");
+  static_assert(sizeof(StepCoef) == 8 * sizeof(float), "StepCoef is one row of 8 floats");
+  return picard_stride(err, B, p, i0, reinterpret_cast<const StepCoef*>(coef), tolerance, L);
 }
 
 // ---- developer hook: the per-iteration coefficient table a sampling run uploads, on the host (no handle, no device) ----------------

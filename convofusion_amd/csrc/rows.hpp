@@ -919,6 +919,179 @@ __global__ void ddpm_extract_kernel(const ExtractArgs a) {
   store8(a.noise + (long long)i * chunk + o, z);
 }
 
+// ---- parallel-in-time DDPM sampling (cfd_sample_parallel) ----------------------------------------------------------------------------
+// X(i), the current estimate of the latent entering iteration i, lives in slot (N - i) % slots of a ring of [B][L][128] slots: the
+// caller's trajectory (slots = N + 1: the ring convention of ddpm_level_kernel) or the call's own J + 1 slots.  A batch is the J levels
+// base .. base + J - 1; its first `off` levels are final already (base < i0 only at the end of the table, where fewer than J levels
+// remain: the batch keeps its size and its table rows stay in range) and their outputs are ignored.
+struct PicardRing {
+  float* x;
+  int slots, N;
+  long long chunk;       // B * L * 128
+  __host__ __device__ __forceinline__ float* at(int i) const { return x + (long long)((N - i) % slots) * chunk; }
+};
+
+// X(base + lv) replicated G times into the split-pair denoiser input, level-major (the rows ddpm_level_kernel writes).  One thread = 8
+// elements.
+struct PicardLoadArgs {
+  PicardRing ring;
+  char* sample_sp;       // SP [J * G * B * L][128]
+  int B, L, G, base, J;
+};
+template <int CFD_KI = 0>
+__global__ void picard_load_kernel(const PicardLoadArgs a) {
+  const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long long n8 = (long long)a.B * a.L * (CFD_LAT / 8);
+  if (idx >= n8 * a.J) return;
+  const int lv = (int)(idx / n8);
+  const long long r = idx % n8, bl = r / (CFD_LAT / 8);
+  const int c = (int)(r % (CFD_LAT / 8)) * 8;
+  const int l = (int)(bl % a.L), b = (int)(bl / a.L);
+  float v[8];
+  load8(a.ring.at(a.base + lv) + bl * CFD_LAT + c, v);
+  for (int g = 0; g < a.G; ++g)
+    sp_store8(a.sample_sp + ((((long long)lv * a.G + g) * a.B + b) * a.L + l) * (CFD_LAT * 4), c, v);
+}
+
+// The DDPM step of every live level of a batch, from the G predictions of every level: the guidance combine term for term as
+// cfg_step_kernel's / ddpm_extract_kernel's, then s = ddpm_mu(c, step_x0(c, clip, x, eps), x) (+ c.sigma * z where the row adds noise; z:
+// the caller's row i, or Philox stream 0 with step index i as cfg_step_kernel draws it).  WTAB: weights from the table row i.  One
+// thread = 8 elements of one level.
+struct PicardStepArgs {
+  const float* eps;      // [J][G][B][L][128]
+  PicardRing ring;
+  float* s;              // [J][B][L][128]: s of level lv (levels below `off` are not written)
+  const StepCoef* coef;
+  int B, L, G, base, off, J;
+  int Gc;                // chunks of the combine (7 for a weighted run, else G)
+  float w[8];
+  int pos[8];            // chunk k's rows within a level start at row pos[k] * B
+  int clip;
+  const float* wtab;     // WTAB: [N][B][8]
+  const float* noise;    // [N][B][L][128] or null -> Philox
+  unsigned long long seed;
+  unsigned int utt0;
+};
+template <int CFD_KI = 0, bool WTAB = false>
+__global__ void picard_step_kernel(const PicardStepArgs a) {
+  const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long long n8 = (long long)a.B * a.L * (CFD_LAT / 8);
+  if (idx >= n8 * a.J) return;
+  const int lv = (int)(idx / n8), i = a.base + lv;
+  if (lv < a.off) return;
+  const long long o = (idx % n8) * 8, chunk = n8 * 8;
+  const int per_utt = a.L * CFD_LAT;
+  const StepCoef c = a.coef[i];
+  const float* lev = a.eps + (long long)lv * a.G * chunk + o;
+  float u[8], acc[8], x[8], z[8], s[8];
+  load8(lev + (long long)a.pos[0] * chunk, u);
+  load8(a.ring.at(i) + o, x);
+  const float* wrow = nullptr;
+  if constexpr (WTAB) wrow = a.wtab + ((long long)i * a.B + o / per_utt) * 8;   // (8 elements never straddle two utterances)
+#pragma unroll
+  for (int q = 0; q < 8; ++q) acc[q] = z[q] = 0.f;
+  // reference association: ((((text + audio) + spk) + apb) + lsnid) + all, each = (g*w)*(e_k - e_0)
+  for (int k = 1; k < a.Gc; ++k) {
+    float e[8];
+    load8(lev + (long long)a.pos[k] * chunk, e);
+    const float wk = WTAB ? wrow[k] : a.w[k];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const float term = wk * (e[q] - u[q]);
+      acc[q] = (k == 1) ? term : acc[q] + term;
+    }
+  }
+  if (c.use_noise != 0.f) {
+    if (a.noise) {
+      load8(a.noise + (long long)i * chunk + o, z);
+    } else {
+      const uint32_t b = (uint32_t)(o / per_utt), g = (uint32_t)((o % per_utt) / 4);
+      const float4 z0 = philox_normal4(a.seed, g, (uint32_t)i, a.utt0 + b, 0u), z1 = philox_normal4(a.seed, g + 1, (uint32_t)i, a.utt0 + b, 0u);
+      z[0] = z0.x; z[1] = z0.y; z[2] = z0.z; z[3] = z0.w; z[4] = z1.x; z[5] = z1.y; z[6] = z1.z; z[7] = z1.w;
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 8; ++q) {
+    const float eps = (a.Gc > 1) ? u[q] + acc[q] : u[q];
+    float prev = ddpm_mu(c, step_x0(c, a.clip, x[q], eps), x[q]);
+    if (c.use_noise != 0.f) prev = prev + c.sigma * z[q];
+    s[q] = prev;
+  }
+  store8(a.s + (long long)lv * chunk + o, s);
+}
+
+// The re-propagation of a sweep through the live levels of the batch (i0 = base + off): Xn(i0) = X(i0), Xn(j + 1) = fl(s_j + fl(Xn(j) -
+// X(j))), each operation rounded on its own -- a level whose predecessor did not change gets exactly s_j.  One thread owns 4 elements
+// across all levels and updates the ring in place (it alone reads and writes them: race-free).  Alongside, the squared change of every
+// window position k = 1 .. (lv - off + 1), summed in a fixed order: wave (xor butterfly), the workgroup's 4 waves through LDS, one
+// partial per workgroup; picard_err_kernel adds the partials in index order.  grid = (workgroups per utterance, B).
+struct PicardScanArgs {
+  const float* s;        // [J][B][L][128]
+  PicardRing ring;
+  float* part;           // [J][B][gridDim.x]: position k's partial of this workgroup (k < J)
+  int L, base, off, J;
+};
+template <int CFD_KI = 0>
+__global__ void __launch_bounds__(256) picard_scan_kernel(const PicardScanArgs a) {
+  __shared__ float red[2][4];
+  const int per4 = a.L * (CFD_LAT / 4), b = blockIdx.y, B = gridDim.y;
+  const int e4 = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool live = e4 < per4;
+  const long long o = (long long)b * per4 * 4 + (long long)(live ? e4 : 0) * 4;
+  const int wave = threadIdx.x >> 6;
+  float4 d = make_float4(0.f, 0.f, 0.f, 0.f);   // Xn(j) - X(j); the window's first level is final
+  // (level lv + 1's operands are requested before level lv's store and barrier: they are other addresses, and nobody else writes them)
+  float4 s_nx = *reinterpret_cast<const float4*>(a.s + (long long)a.off * a.ring.chunk + o);
+  float4 x_nx = *reinterpret_cast<const float4*>(a.ring.at(a.base + a.off + 1) + o);
+  for (int lv = a.off; lv < a.J; ++lv) {
+    const int i = a.base + lv, k = lv - a.off + 1;
+    const float4 s = s_nx, xn_old = x_nx;
+    float* nx = a.ring.at(i + 1) + o;
+    if (lv + 1 < a.J) {
+      s_nx = *reinterpret_cast<const float4*>(a.s + (long long)(lv + 1) * a.ring.chunk + o);
+      x_nx = *reinterpret_cast<const float4*>(a.ring.at(i + 2) + o);
+    }
+    const float4 xn = make_float4(__fadd_rn(s.x, d.x), __fadd_rn(s.y, d.y), __fadd_rn(s.z, d.z), __fadd_rn(s.w, d.w));
+    d = make_float4(__fsub_rn(xn.x, xn_old.x), __fsub_rn(xn.y, xn_old.y), __fsub_rn(xn.z, xn_old.z), __fsub_rn(xn.w, xn_old.w));
+    if (live) *reinterpret_cast<float4*>(nx) = xn;
+    float e = 0.f;
+    if (live) e = __fadd_rn(__fadd_rn(__fmul_rn(d.x, d.x), __fmul_rn(d.y, d.y)), __fadd_rn(__fmul_rn(d.z, d.z), __fmul_rn(d.w, d.w)));
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) e = __fadd_rn(e, __shfl_xor(e, m));
+    if ((threadIdx.x & 63) == 0) red[lv & 1][wave] = e;
+    __syncthreads();   // (one per level: the next level writes the other half of `red`)
+    if (threadIdx.x == 0 && k < a.J)
+      a.part[((long long)k * B + b) * gridDim.x + blockIdx.x] =
+          __fadd_rn(__fadd_rn(red[lv & 1][0], red[lv & 1][1]), __fadd_rn(red[lv & 1][2], red[lv & 1][3]));
+  }
+}
+
+// err[k][b] = the workgroups' partials of window position k added in index order; 0 for the positions the sweep did not move (k = 0:
+// the final first level; k > p: beyond the live levels).  One thread per (k, b).
+template <int CFD_KI = 0>
+__global__ void picard_err_kernel(const float* part, float* err, int J, int B, int nblk, int p) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= J * B) return;
+  const int k = idx / B;
+  float e = 0.f;
+  if (k >= 1 && k <= p)
+    for (int g = 0; g < nblk; ++g) e = __fadd_rn(e, part[(long long)idx * nblk + g]);
+  err[idx] = e;
+}
+
+// X(i) = X(src) for the iterations lo .. hi that enter the window.  One thread = 8 elements of one level.
+template <int CFD_KI = 0>
+__global__ void picard_fill_kernel(const PicardRing ring, int src, int lo, int hi) {
+  const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long long n8 = ring.chunk / 8;
+  if (idx >= n8 * (hi - lo + 1)) return;
+  const int i = lo + (int)(idx / n8);
+  const long long o = (idx % n8) * 8;
+  float v[8];
+  load8(ring.at(src) + o, v);
+  store8(ring.at(i) + o, v);
+}
+
 // mem_prep_kernel for a level batch (Problem::tmode 2): instance u of the launch is distinct memory u % U0 of the caller's U0 at level
 // u / U0 of the batch, whose timestep embedding is table row trow0 + u / U0.  The memory-side work of a level is thus done once per
 // distinct instance; the level's rows reach it through the level row maps.

@@ -877,6 +877,42 @@ def invert(denoiser, scheduler, encoder_hidden_states, cond_masks=None, *, sourc
 LEVEL_NOISE_STREAM = 2
 
 
+def _level_batch_args(denoiser, scheduler, enc, masks, B, L, num_inference_steps, table, seed, first_utterance, dedup, row_maps):
+    """What the level-batched DDPM calls (``invert_ddpm``, ``sample_parallel``) share: the de-duplicated memories of the 7-chunk guidance
+    batch on the denoiser's engine and the DDPM run's cfd_sample_args over ``table``.  Returns (lib, handle, device, args, keep-alive)."""
+    dev = enc[0].device
+    if dev.type != "cuda":
+        raise RuntimeError("the fused sampler runs on an MI355X only (no CPU fallback)")
+    G, N = CFG_CHUNKS, len(table)
+    if row_maps is not None:
+        if any(int(m.numel()) != G * B for m in row_maps):
+            raise ValueError(f"row_maps must have G*B = {G * B} entries")
+        mems, maps, mks = list(enc), list(row_maps), dict(masks or {})
+    elif enc[0].shape[0] != G * B:
+        raise ValueError(f"conditioning batch is {enc[0].shape[0]} rows, expected G*B = {G * B}")
+    elif dedup:
+        mems, maps, mks = dedup_memories(enc, masks)
+    else:
+        mems, maps, mks = list(enc), None, dict(masks or {})
+    lib = _lib.load()
+    handle = denoiser.engine(dev, mem_len=max(int(m.shape[1]) for m in mems))
+    marr, keep = Denoiser.pack_memories(mems, mks, maps)
+    a = _lib.SampleArgs()
+    a.B, a.L, a.G = B, L, G
+    a.scheduler = 0
+    a.num_train_timesteps = scheduler.config.num_train_timesteps
+    a.num_inference_steps = num_inference_steps
+    a.clip_sample = 1 if scheduler.config.get("clip_sample", False) else 0
+    acp = scheduler.alphas_cumprod.detach().to("cpu", torch.float32).contiguous()
+    a.alphas_cumprod = acp.data_ptr()
+    a.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    a.first_utterance = int(first_utterance)
+    a.mem = marr
+    ts = (C.c_int32 * N)(*[int(t) for t in table])
+    a.timesteps, a.num_timesteps = C.cast(ts, C.c_void_p), N
+    return lib, handle, dev, a, (keep, acp, ts)
+
+
 def invert_ddpm(denoiser, scheduler, enc, masks=None, *, source_latents, num_inference_steps=1000, guidance_scale=1.0, modality_weights=None,
                 seed=0, level_noise=None, levels_per_batch=None, first_utterance=0, dedup=True, row_maps=None, workspace_bytes=None):
     """Edit-friendly DDPM inversion (Huberman-Spiegelglas et al., CVPR 2024) of ``source_latents`` [B, L, 128] (cfd_ddpm_invert): for every
@@ -908,36 +944,8 @@ def invert_ddpm(denoiser, scheduler, enc, masks=None, *, source_latents, num_inf
                                     or tuple(level_noise.shape) != (N, B, L, 128)):
         raise ValueError(f"level_noise must be a floating-point tensor [N, B, L, 128] = [{N}, {B}, {L}, 128]")
     weights = modality_weight_table(INVERSION_WEIGHTS if modality_weights is None else modality_weights, guidance_scale, N, B, CFG_CHUNKS)
-    dev = enc[0].device
-    if dev.type != "cuda":
-        raise RuntimeError("the fused sampler runs on an MI355X only (no CPU fallback)")
-    G = CFG_CHUNKS
-    if row_maps is not None:
-        if any(int(m.numel()) != G * B for m in row_maps):
-            raise ValueError(f"row_maps must have G*B = {G * B} entries")
-        mems, maps, mks = list(enc), list(row_maps), dict(masks or {})
-    elif enc[0].shape[0] != G * B:
-        raise ValueError(f"conditioning batch is {enc[0].shape[0]} rows, expected G*B = {G * B}")
-    elif dedup:
-        mems, maps, mks = dedup_memories(enc, masks)
-    else:
-        mems, maps, mks = list(enc), None, dict(masks or {})
-    lib = _lib.load()
-    handle = denoiser.engine(dev, mem_len=max(int(m.shape[1]) for m in mems))
-    marr, keep = Denoiser.pack_memories(mems, mks, maps)
-    a = _lib.SampleArgs()
-    a.B, a.L, a.G = B, L, G
-    a.scheduler = 0
-    a.num_train_timesteps = scheduler.config.num_train_timesteps
-    a.num_inference_steps = num_inference_steps
-    a.clip_sample = 1 if scheduler.config.get("clip_sample", False) else 0
-    acp = scheduler.alphas_cumprod.detach().to("cpu", torch.float32).contiguous()
-    a.alphas_cumprod = acp.data_ptr()
-    a.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-    a.first_utterance = int(first_utterance)
-    a.mem = marr
-    ts = (C.c_int32 * N)(*[int(t) for t in table])
-    a.timesteps, a.num_timesteps = C.cast(ts, C.c_void_p), N
+    lib, handle, dev, a, keep = _level_batch_args(denoiser, scheduler, enc, masks, B, L, num_inference_steps, table, seed, first_utterance,
+                                                  dedup, row_maps)
     src = source_latents.detach().to(device=dev, dtype=torch.float32).contiguous()
     eps = level_noise.detach().to(device=dev, dtype=torch.float32).contiguous() if level_noise is not None else None
     trajectory = torch.empty((N + 1, B, L, 128), dtype=torch.float32, device=dev)
@@ -953,10 +961,90 @@ def invert_ddpm(denoiser, scheduler, enc, masks=None, *, source_latents, num_inf
         torch.cuda.current_stream(dev).synchronize()
         _lib.check(lib.cfd_ddpm_invert(handle, C.byref(a), C.byref(iv), C.byref(g_eval), C.byref(j_used),
                                        C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-    del keep, acp, ts
+    del keep
     _lib.wrote(trajectory, noise)
     invert_ddpm.last = dict(chunks_evaluated=int(g_eval.value), levels_per_batch=int(j_used.value))
     return trajectory, noise
+
+
+class ParallelStats:
+    """What a ``sample_parallel`` call did: ``sweeps`` level-batched forwards, the window's advance after each (``strides``, summing to the
+    iterations of the table), the levels per batch J (``levels_per_batch``) and the guidance chunks evaluated (``chunks_evaluated``)."""
+
+    def __init__(self, sweeps, strides, levels_per_batch, chunks_evaluated):
+        self.sweeps, self.strides = int(sweeps), [int(v) for v in strides]
+        self.levels_per_batch, self.chunks_evaluated = int(levels_per_batch), int(chunks_evaluated)
+
+    def __repr__(self):
+        mean = sum(self.strides) / max(len(self.strides), 1)
+        return (f"ParallelStats(sweeps={self.sweeps}, mean stride={mean:.2f}, levels_per_batch={self.levels_per_batch}, "
+                f"chunks_evaluated={self.chunks_evaluated})")
+
+
+def sample_parallel(denoiser, scheduler, enc, masks=None, *, B, L=16, num_inference_steps=1000, tolerance=0.1, levels_per_batch=None,
+                    workspace_bytes=None, guidance_scale=7.5, modality_weights=None, init_latents=None, step_noise=None, seed=0,
+                    trajectory=False, max_sweeps=None, first_utterance=0, dedup=True, row_maps=None):
+    """Parallel-in-time DDPM sampling (ParaDiGMS, Shih et al., NeurIPS 2023; cfd_sample_parallel): Picard sweeps over a sliding window of
+    ``levels_per_batch`` consecutive latents of the DDPM chain, each sweep one level-batched forward on split-pair operands (the batch of
+    ``invert_ddpm``; None: chosen from ``workspace_bytes``, 4 GiB by default).  ``tolerance`` 0 computes the sequential chain (in at most N
+    sweeps); a larger one lets the window slide past levels whose change in a sweep is within tolerance^2 of the step's noise variance per
+    element.  ``scheduler``: a ``DDPMScheduler`` (clip_sample honoured); ``enc`` / ``masks``: the 7-chunk guidance batch, as for ``sample``.
+    ``modality_weights`` None: the reference's guidance at ``guidance_scale`` (the zero-weight full-conditioning chunk is not evaluated);
+    else the weighted combine, as for ``sample``.  ``init_latents`` [B, L, 128] / ``step_noise`` [N, B, L, 128]: as for ``sample``; None: the
+    Philox draws ``sample`` makes with the same ``seed``.  Returns (latents [B, L, 128], ParallelStats), and with ``trajectory=True``
+    (latents, trajectory [N + 1, B, L, 128], ParallelStats): slot N - i of the trajectory is the latent entering iteration i, slot 0 the
+    result.  ``max_sweeps``: None (N, always enough) or a cap; a run that needs more raises ``_lib.CfdError``."""
+    if not isinstance(denoiser, Denoiser):
+        raise TypeError("denoiser must be a convofusion_amd.denoiser.Denoiser")
+    if getattr(scheduler, "KIND", None) != 0:
+        raise TypeError("sample_parallel needs a convofusion_amd.scheduler.DDPMScheduler")
+    for name, v in (("B", B), ("L", L)):
+        if isinstance(v, bool) or int(v) != v or int(v) < 1:
+            raise ValueError(f"{name} must be a positive integer, not {v!r}")
+    B, L = int(B), int(L)
+    try:
+        tol = float(tolerance)
+    except (TypeError, ValueError):
+        raise ValueError(f"tolerance must be a finite number >= 0, not {tolerance!r}") from None
+    if not (tol >= 0.0) or tol == float("inf"):
+        raise ValueError(f"tolerance must be a finite number >= 0, not {tolerance!r}")
+    num_inference_steps, table = scheduler.timestep_table(num_inference_steps)
+    N = len(table)
+    for name, v in (("levels_per_batch", levels_per_batch), ("max_sweeps", max_sweeps)):
+        if v is not None and (isinstance(v, bool) or int(v) != v or int(v) < 1):
+            raise ValueError(f"{name} must be a positive integer or None, not {v!r}")
+    for name, t, shape in (("init_latents", init_latents, (B, L, 128)), ("step_noise", step_noise, (N, B, L, 128))):
+        if t is not None and (not isinstance(t, torch.Tensor) or not t.is_floating_point() or tuple(t.shape) != shape):
+            raise ValueError(f"{name} must be a floating-point tensor {list(shape)}")
+    weights = None if modality_weights is None else modality_weight_table(modality_weights, guidance_scale, N, B, CFG_CHUNKS)
+    lib, handle, dev, a, keep = _level_batch_args(denoiser, scheduler, enc, masks, B, L, num_inference_steps, table, seed, first_utterance,
+                                                  dedup, row_maps)
+    # the default combine: e_0 + sum_k w_k (e_k - e_0), the full-conditioning chunk at guidance_scale * 0 (convofusion.py:538) and skipped
+    w = [0.0] + [float(guidance_scale) * 1] * 5 + [float(guidance_scale) * 0, 0.0]
+    a.guidance_weight = (C.c_float * 8)(*w)
+    a.skip_zero_weight_chunks = 1
+    init = init_latents.detach().to(device=dev, dtype=torch.float32).contiguous() if init_latents is not None else None
+    noise = step_noise.detach().to(device=dev, dtype=torch.float32).contiguous() if step_noise is not None else None
+    a.init_latents = init.data_ptr() if init is not None else None
+    a.step_noise = noise.data_ptr() if noise is not None else None
+    latents = torch.empty((B, L, 128), dtype=torch.float32, device=dev)
+    traj = torch.empty((N + 1, B, L, 128), dtype=torch.float32, device=dev) if trajectory else None
+    pa = _lib.ParallelArgs()
+    pa.weights, pa.prune = (weights.ctypes.data_as(C.c_void_p) if weights is not None else None), 1
+    pa.tolerance = tol
+    pa.levels_per_batch, pa.workspace_bytes, pa.max_sweeps = int(levels_per_batch or 0), int(workspace_bytes or 0), int(max_sweeps or 0)
+    pa.latents, pa.trajectory = latents.data_ptr(), (traj.data_ptr() if traj is not None else None)
+    strides = (C.c_int32 * N)()
+    ps = _lib.ParallelStats()
+    ps.strides, ps.strides_capacity = C.cast(strides, C.c_void_p), N
+    with torch.cuda.device(dev):
+        torch.cuda.current_stream(dev).synchronize()
+        _lib.check(lib.cfd_sample_parallel(handle, C.byref(a), C.byref(pa), C.byref(ps),
+                                           C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    del keep
+    _lib.wrote(latents, traj)
+    stats = ParallelStats(ps.sweeps, strides[:ps.sweeps], ps.levels_per_batch, ps.chunks_evaluated)
+    return (latents, traj, stats) if trajectory else (latents, stats)
 
 
 # the WEG constants diffusion_reverse_forecast hard-codes instead of reading cfg.model.weg_parameters (unbounded_synthesis.py:80-84)

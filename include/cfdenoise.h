@@ -295,6 +295,45 @@ typedef struct {
  * non-finite entry.  CFD_E_STATE: a sampling run is open on the handle. */
 int cfd_ddpm_invert(cfd_handle h, const cfd_sample_args* args, const cfd_ddpm_invert_args* inv, int* chunks_evaluated,
                     int* levels_per_batch_used, void* stream);
+/* Parallel-in-time DDPM sampling (ParaDiGMS, Shih et al., NeurIPS 2023): Picard sweeps over a sliding window of J consecutive latents of
+ * the DDPM chain.  X(i) is the current estimate of the latent ENTERING iteration i; the window is iterations i0 .. i0 + p - 1,
+ * p = min(J, N - i0); X(i0) is final.  One sweep evaluates the guided prediction at every X(j) of the window in ONE level-batched forward
+ * (the batch of cfd_ddpm_invert), takes the DDPM step s_j = mu_j(X(j), eps_hat_j) [+ sigma_j z_j] of every level, and re-propagates
+ *   Xn(i0) = X(i0),   Xn(j + 1) = fl(s_j + fl(Xn(j) - X(j)))
+ * serially per element.  A level whose predecessor did not change receives exactly s_j, and X(i0 + 1) is exact after every sweep: at
+ * tolerance 0 the call computes the sequential chain, in at most N sweeps.  After a sweep the host reads, per window position
+ * k = 1 .. p - 1 and utterance b, e[k][b] = sum_{l,d} (Xn(i0 + k) - X(i0 + k))^2 (reduced in a fixed order, no float atomics: two calls
+ * on the same inputs take the same strides and return the same bits) and slides the window by the largest stride s in [1, p] with
+ *   e[k][b] / (L * 128) <= tolerance^2 * v(i0 + k)   for every 1 <= k < s and every b
+ * where v(i) = sigma_i^2 of iteration i's step (an iteration that adds no noise takes the value of the iteration before it).  The
+ * levels that enter the window start from the last window value.  One host synchronisation per sweep. */
+typedef struct {
+  const float* weights;       /* HOST float32 [N][B][8] or NULL, with `prune`: as in cfd_ddpm_invert_args */
+  int prune;
+  float tolerance;            /* tau >= 0 (0: the sequential chain) */
+  int levels_per_batch;       /* J; 0: chosen from workspace_bytes as cfd_ddpm_invert chooses it */
+  size_t workspace_bytes;     /* as in cfd_ddpm_invert_args (0: 4 GiB) */
+  int max_sweeps;             /* 0: N (always enough); a run that needs more fails with CFD_E_STATE */
+  float* latents;             /* out, dev [B][L][128] */
+  float* trajectory;          /* out or NULL, dev [N + 1][B][L][128]: slot N - i the latent entering iteration i, slot 0 the result (the
+                                 ring convention of cfd_sample_begin_invert / cfd_ddpm_invert).  The call works in place in it; a slot is
+                                 never written again once its latent is final.  NULL: the call keeps J + 1 slots of its own. */
+} cfd_parallel_args;
+typedef struct {
+  int levels_per_batch;       /* J as used */
+  int chunks_evaluated;       /* G_eval */
+  int sweeps;                 /* level-batched forwards executed */
+  int* strides;               /* HOST int32 [strides_capacity] or NULL: the advance of sweep k (they sum to N); sweeps beyond the
+                                 capacity are not recorded */
+  int strides_capacity;
+} cfd_parallel_stats;
+/* `args`: the cfd_sample_args of the DDPM run (scheduler 0; clip_sample, timesteps, the memories with their row maps, guidance_weight /
+ * skip_zero_weight_chunks, seed and first_utterance honoured; init_latents / step_noise as in cfd_sample_begin -- NULL: Philox stream 1
+ * and stream 0 with step index i, the draws of the captured loop with the same seed).  `stats` may be NULL; its `strides` / capacity are
+ * inputs.  A self-contained call: it opens no run.  Operands are split pairs.  CFD_E_ARG: a scheduler other than 0, preseq, a dynamic
+ * memory, att_ring, a negative or non-finite tolerance, a negative levels_per_batch or max_sweeps, a NULL `latents`.  CFD_E_STATE: a
+ * sampling run is open on the handle; max_sweeps reached before the last level was final. */
+int cfd_sample_parallel(cfd_handle h, const cfd_sample_args* args, const cfd_parallel_args* par, cfd_parallel_stats* stats, void* stream);
 /* Replay of a recorded noise space (cfd_ddpm_invert). */
 typedef struct {
   const float* trajectory;    /* dev [steps + 1][B][L][128]; read in place until the run is closed */

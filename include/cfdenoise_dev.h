@@ -67,6 +67,10 @@ int cfd_debug_read(cfd_handle h, const char* what, float* dst_dev, size_t numel)
  * float32 [T]; n_inf: the count given to set_timesteps (DDPM / DDIM stride).  Fails with CFD_E_ARG where cfd_sample_begin would. */
 int cfd_test_step_coefficients(int kind, const float* alphas_cumprod, int T, int n_inf, const int32_t* timesteps, int N, float eta,
                                int set_alpha_to_one, float* out);
+/* Test hook (no handle, no device): the stride cfd_sample_parallel takes after a sweep.  err HOST float32 [p][B] (row k: the squared change
+ * of X(i0 + k); row 0 is not read), coef HOST float32 [N][8] rows as cfd_test_step_coefficients writes them (sigma and use_noise are read),
+ * the window i0 .. i0 + p - 1 inside the N iterations.  Returns the stride in [1, p], or CFD_E_ARG. */
+int cfd_test_picard_stride(const float* err, int B, int p, int i0, const float* coef, int N, float tolerance, int L);
 
 #ifdef __cplusplus
 }

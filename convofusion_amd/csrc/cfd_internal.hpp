@@ -178,7 +178,8 @@ struct Work {
 };
 
 // The kind of the open sampling run: which instances of begin_step_kernel / inpaint_now_kernel / cfg_step_kernel it launches
-// (cfd_sample.hip: with_begin_args, enqueue_loop_iteration).  sample_begin starts every run from RunMode{}: a new field needs no reset.
+// (cfd_sample.hip: with_begin_args, enqueue_loop_iteration).  sample_begin starts every run from RunMode{}: a new field needs no reset;
+// it is filled from its BeginExt field in init_latents_and_kind (the comment on BeginExt lists every place a new run kind touches).
 struct RunMode {
   // Weighted run (cfd_sample_begin_weighted): the guidance weights come from Ctx::wtab instead of cfd_sample_args::guidance_weight.
   bool weighted = false;

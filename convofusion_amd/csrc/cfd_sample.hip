@@ -207,6 +207,66 @@ static int enqueue_loop_iteration(Ctx* c, hipStream_t st) {
   return CFD_OK;
 }
 
+// A memory's row map on the host (`rows` = G * B entries): the caller's map downloaded, or the identity for a memory without one (it then
+// has one instance per row).  The entries are not range-checked here: level_batch_memories checks them for a level batch; a sampling
+// run's (cfd_sample_begin and its kin) never were at this point -- setup_problem checks the maps it is given.
+static int host_row_map(const cfd_memory& mem, int rows, const char* name, std::vector<int>& out) {
+  out.resize((size_t)rows);
+  if (mem.row_map) {
+    HIPCHK(hipMemcpy(out.data(), mem.row_map, (size_t)rows * 4, hipMemcpyDeviceToHost));
+    return CFD_OK;
+  }
+  if (mem.U != rows) return fail(CFD_E_ARG, "memory %s: U = %d != G * B = %d without a row_map", name, mem.U, rows);
+  for (int r = 0; r < rows; ++r) out[r] = r;
+  return CFD_OK;
+}
+
+// What every set-up starts with: the device, no forward hints, the census an earlier call deferred
+static int setup_preamble(Ctx* c) {
+  HIPCHK(hipSetDevice(c->cfg.device));
+  c->hint_now = c->hint_same_mem = false;
+  return settle_deferred_census(c);
+}
+
+// The refusals about the scheduler's tables that do not depend on the kind of run (`who`: the entry point, for the message)
+static int check_scheduler_tables(const cfd_sample_args& s, const char* who) {
+  if (!s.alphas_cumprod || s.num_train_timesteps < 1 || s.num_inference_steps < 1 || s.num_inference_steps > s.num_train_timesteps)
+    return fail(CFD_E_ARG, "bad scheduler tables");
+  if (s.timesteps && (s.num_timesteps < 1 || s.num_timesteps > s.num_train_timesteps)) return fail(CFD_E_ARG, "bad num_timesteps");
+  if (!s.timesteps && s.scheduler == 0 && s.num_train_timesteps % s.num_inference_steps)
+    return fail(CFD_E_ARG, "%s: DDPM: num_inference_steps = %d does not divide num_train_timesteps = %d: the loop's timestep table for such "
+                           "counts differs between diffusers releases (unpinned); pass the scheduler's table in cfd_sample_args.timesteps",
+                who, s.num_inference_steps, s.num_train_timesteps);
+  return CFD_OK;
+}
+
+// skip_zero_weight_chunks: the batch is chunk-major, so dropping trailing zero-weight chunks = using the first G' * B rows (c->sargs.G)
+static void trim_zero_weight_chunks(Ctx* c, const cfd_sample_args& s) {
+  if (s.skip_zero_weight_chunks)
+    while (c->sargs.G > 1 && s.guidance_weight[c->sargs.G - 1] == 0.0f) c->sargs.G -= 1;
+}
+
+// The tables of a run over N iterations, on the stream: the timestep table (the caller's, or (arange(N) * (T // n_inf)).round()[::-1],
+// + steps_offset for DDIM), its step coefficients (k0: the first executed iteration), the step index cleared, the saturation census
+// opened (what the caller reads next counts THIS call's launches only), the time tables and the memories' once-per-run work; then the one
+// wait (the host tables go out of scope).  coef_out: the coefficient rows for a caller that reads them on the host.
+static int upload_run_tables(Ctx* c, const cfd_sample_args& s, int N, int k0, hipStream_t st, std::vector<StepCoef>* coef_out = nullptr) {
+  const int n_inf = s.num_inference_steps, T = s.num_train_timesteps, ratio = T / n_inf;
+  std::vector<int32_t> ts(N);
+  std::vector<StepCoef> coef(N);
+  for (int i = 0; i < N; ++i) ts[i] = s.timesteps ? s.timesteps[i] : (N - 1 - i) * ratio + (s.scheduler == 1 ? s.steps_offset : 0);
+  CHK(step_coefficients(s.scheduler, s.alphas_cumprod, T, n_inf, ts.data(), N, s.eta, s.set_alpha_to_one, coef.data(), k0));
+  CHK(c->coef.ensure((size_t)N * sizeof(StepCoef)));
+  HIPCHK(hipMemcpyAsync(c->coef.p, coef.data(), (size_t)N * sizeof(StepCoef), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemsetAsync(c->w->d_step.p, 0, 16, st));
+  CHK(sat_begin(c, st));
+  CHK(build_time_tables(c, ts.data(), N, st));   // (a run over the same table finds them built)
+  CHK(prepare_static_memside(c, st, s.dynamic_memory_mask, false));
+  HIPCHK(hipStreamSynchronize(st));
+  if (coef_out) coef_out->swap(coef);
+  return CFD_OK;
+}
+
 // Chunks of a weighted run (cfd_sample_begin_weighted): uploads the weight table, decides which chunks are evaluated (prune: every chunk
 // k >= 1 whose column is 0 throughout is not, except the last one when the run keeps its attention maps) and compacts the memories' row
 // maps to the evaluated chunks, in the caller's order (a memory without a map gets the identity map first).  keep_idx[k]: the compacted
@@ -232,14 +292,9 @@ static int weighted_chunks(Ctx* c, const float* wtab, int prune, int N, bool kee
   c->sargs.G = ge;
   if (ge == G) return CFD_OK;
   const int Be = G * B, Bc = ge * B;
-  std::vector<int> hm(Be), cm(Bc);
+  std::vector<int> hm, cm(Bc);
   for (int j = 0; j < CFD_NMEM; ++j) {
-    if (mem_in[j].row_map) {
-      HIPCHK(hipMemcpy(hm.data(), mem_in[j].row_map, (size_t)Be * 4, hipMemcpyDeviceToHost));
-    } else {
-      if (mem_in[j].U != Be) return fail(CFD_E_ARG, "memory %s: U = %d != G * B = %d without a row_map", MEM_NAMES[j], mem_in[j].U, Be);
-      for (int r = 0; r < Be; ++r) hm[r] = r;
-    }
+    CHK(host_row_map(mem_in[j], Be, MEM_NAMES[j], hm));
     for (int k = 0; k < G; ++k)
       if (keep_idx[k] >= 0)
         for (int u = 0; u < B; ++u) cm[(size_t)keep_idx[k] * B + u] = hm[(size_t)k * B + u];
@@ -262,7 +317,10 @@ static int upload_keep_mask(Ctx* c, const std::vector<uint8_t>& hkeep, size_t n,
 // What an opener adds to cfd_sample_begin's run; every field is optional.  weights (with prune / chunks_evaluated as in
 // cfd_sample_begin_weighted; NULL: the default guidance weights, chunks_evaluated then gets the run's G on success), edit, traj (the
 // inversion's trajectory ring), anchor, tie, replay (a DDPM noise space: the anchored instance over its trajectory, a start at its
-// first_iteration).  A new run kind adds its field here, its RunMode field and its row in with_begin_args.
+// first_iteration).  A new run kind touches four places: its field here, its RunMode field (cfd_internal.hpp), its block in
+// init_latents_and_kind, which turns the one into the other, and -- if it overwrites tokens at the start of an iteration -- its row in
+// with_begin_args.  What it refuses goes into its opener, or into check_run_args where it depends on the other fields; a host table it
+// brings is fetched next to fetch_keep_mask / fetch_tie_table.
 struct BeginExt {
   const char* opener = "cfd_sample_begin";
   const float* weights = nullptr;
@@ -275,29 +333,24 @@ struct BeginExt {
   const cfd_replay_args* replay = nullptr;
 };
 
-static int sample_begin(Ctx* c, const cfd_sample_args* args, void* stream, const BeginExt& x) {
-  if (!c || !args) return fail(CFD_E_ARG, "null argument");
-  const float* wtab = x.weights;
-  const cfd_edit_args* edit = x.edit;
-  const cfd_anchor_args* anchor = x.anchor;
-  const cfd_tie_args* tie = x.tie;
-  const cfd_replay_args* replay = x.replay;
-  if (wtab && args->G != 7) return fail(CFD_E_ARG, "%s: a weight table needs the 7-chunk guidance batch (G = %d)", x.opener, args->G);
-  if (c->run_open) return fail(CFD_E_STATE, "a sampling run is already open");
-  HIPCHK(hipSetDevice(c->cfg.device));
-  c->hint_now = c->hint_same_mem = false;
-  CHK(settle_deferred_census(c));
-  struct AcenOff { Ctx* c; ~AcenOff() { c->acen_on = false; } } acen_off{c};   // (the census slots go only into THIS run's launches)
-  c->acen_valid = c->acen_measured = false;
-  c->acen_hits = 0;
-  cfd_sample_args s_w;
-  if (wtab) {   // a weighted run ignores guidance_weight and skip_zero_weight_chunks (its table says which chunks count)
-    s_w = *args;
-    s_w.skip_zero_weight_chunks = 0;
-    args = &s_w;
-  }
-  c->run = RunMode{};
-  const cfd_sample_args& s = *args;
+// What the stages of sample_begin hand to each other
+struct BeginState {
+  Ctx* c;
+  const cfd_sample_args& s;   // the caller's arguments (c->sargs: the run's copy, G = the evaluated chunks, no host pointers)
+  const BeginExt& x;
+  hipStream_t st;
+  int N;                      // loop iterations (the length of scheduler.timesteps)
+  int k0;                     // the first executed iteration (an edit's or a replay's first_iteration)
+  int n_ring = 0;             // attention rings given (0 or CFD_NMEM)
+  size_t lat_bytes;
+  std::vector<uint8_t> hkeep; // the keep mask and the tie table on the host, validated (empty: none given)
+  std::vector<int32_t> htie;
+  cfd_memory mem_in[CFD_NMEM];
+  int keep_idx[8];            // weighted run: the compacted index of chunk k, or -1
+};
+
+static int check_run_args(const BeginState& r) {
+  const cfd_sample_args& s = r.s;
   if (s.B < 1 || (s.G != 1 && s.G != 7 && (s.G < 1 || s.G > 8))) return fail(CFD_E_ARG, "bad B / G");
   if (s.scheduler < 0 || s.scheduler > 3)
     return fail(CFD_E_ARG, "scheduler must be 0 (DDPM), 1 (DDIM), 2 (DPM-Solver++ (2M)) or 3 (DDIM inversion)");
@@ -307,279 +360,292 @@ static int sample_begin(Ctx* c, const cfd_sample_args* args, void* stream, const
     if (s.clip_sample) return fail(CFD_E_ARG, "DDIM inversion: clip_sample must be 0 (a clipped x0 is not invertible)");
     if (s.preseq) return fail(CFD_E_ARG, "DDIM inversion takes no preseq (the rollout's prefix in-painting)");
     if (s.dynamic_memory_mask) return fail(CFD_E_ARG, "DDIM inversion takes no dynamic memories (dynamic_memory_mask = %d)", s.dynamic_memory_mask);
-    if (edit) return fail(CFD_E_ARG, "DDIM inversion does not go together with an edit (cfd_sample_begin_edit)");
+    if (r.x.edit) return fail(CFD_E_ARG, "DDIM inversion does not go together with an edit (cfd_sample_begin_edit)");
   }
   if (s.scheduler == 2 && !s.timesteps)
     return fail(CFD_E_ARG, "DPM-Solver++: pass the scheduler's timestep table in cfd_sample_args.timesteps (the library does not build it)");
   if (s.scheduler == 2 && s.clip_sample) return fail(CFD_E_ARG, "DPM-Solver++ has no clip_sample (clip_sample must be 0)");
-  if (!s.alphas_cumprod || s.num_train_timesteps < 1 || s.num_inference_steps < 1 || s.num_inference_steps > s.num_train_timesteps)
-    return fail(CFD_E_ARG, "bad scheduler tables");
-  if (s.timesteps && (s.num_timesteps < 1 || s.num_timesteps > s.num_train_timesteps)) return fail(CFD_E_ARG, "bad num_timesteps");
-  if (!s.timesteps && s.scheduler == 0 && s.num_train_timesteps % s.num_inference_steps)
-    return fail(CFD_E_ARG, "DDPM: num_inference_steps = %d does not divide num_train_timesteps = %d: the loop's timestep table for such "
-                           "counts differs between diffusers releases (unpinned); pass the scheduler's table in cfd_sample_args.timesteps",
-                s.num_inference_steps, s.num_train_timesteps);
+  CHK(check_scheduler_tables(s, r.x.opener));
   if (s.preseq && (s.preseq_len < 1 || s.preseq_len > s.L)) return fail(CFD_E_ARG, "bad preseq_len");
-  const int n_iter = s.timesteps ? s.num_timesteps : s.num_inference_steps;
-  const int k0 = edit ? edit->first_iteration : replay ? replay->first_iteration : 0;
-  std::vector<uint8_t> hkeep;
-  if (edit && (k0 < 0 || k0 >= n_iter)) return fail(CFD_E_ARG, "cfd_sample_begin_edit: first_iteration = %d is not in [0, %d)", k0, n_iter);
-  if (replay && (k0 < 0 || k0 >= n_iter)) return fail(CFD_E_ARG, "cfd_sample_begin_replay: first_iteration = %d is not in [0, %d)", k0, n_iter);
-  const uint8_t* keep_in = edit ? edit->keep : anchor ? anchor->keep : replay ? replay->keep : nullptr;
-  if (keep_in) {
-    const char* who = edit ? "cfd_sample_begin_edit" : anchor ? "cfd_sample_begin_anchored" : "cfd_sample_begin_replay";
-    hkeep.resize((size_t)s.B * s.L);
-    HIPCHK(hipMemcpy(hkeep.data(), keep_in, hkeep.size(), hipMemcpyDeviceToHost));
-    for (size_t e = 0; e < hkeep.size(); ++e)
-      if (hkeep[e] > 1) return fail(CFD_E_ARG, "%s: keep[%zu][%zu] = %d is not 0 or 1", who, e / s.L, e % s.L, (int)hkeep[e]);
+  if (r.x.edit && (r.k0 < 0 || r.k0 >= r.N))   // (a replay's: its opener)
+    return fail(CFD_E_ARG, "cfd_sample_begin_edit: first_iteration = %d is not in [0, %d)", r.k0, r.N);
+  return CFD_OK;
+}
+
+// The keep mask of an edit, anchored or replay run on the host, every entry 0 or 1
+static int fetch_keep_mask(BeginState& r) {
+  const BeginExt& x = r.x;
+  const uint8_t* keep_in = x.edit ? x.edit->keep : x.anchor ? x.anchor->keep : x.replay ? x.replay->keep : nullptr;
+  if (!keep_in) return CFD_OK;
+  const char* who = x.edit ? "cfd_sample_begin_edit" : x.anchor ? "cfd_sample_begin_anchored" : "cfd_sample_begin_replay";
+  r.hkeep.resize((size_t)r.s.B * r.s.L);
+  HIPCHK(hipMemcpy(r.hkeep.data(), keep_in, r.hkeep.size(), hipMemcpyDeviceToHost));
+  for (size_t e = 0; e < r.hkeep.size(); ++e)
+    if (r.hkeep[e] > 1) return fail(CFD_E_ARG, "%s: keep[%zu][%zu] = %d is not 0 or 1", who, e / r.s.L, e % r.s.L, (int)r.hkeep[e]);
+  return CFD_OK;
+}
+
+// The tie table on the host: range, no self-tie, a source is free (neither tied nor kept), no token both kept and tied
+static int fetch_tie_table(BeginState& r) {
+  if (!r.x.tie) return CFD_OK;
+  const cfd_sample_args& s = r.s;
+  const std::vector<uint8_t>& hkeep = r.hkeep;
+  std::vector<int32_t>& htie = r.htie;
+  if (s.L < 1) return fail(CFD_E_ARG, "bad L");
+  const long long nt = (long long)s.B * s.L;
+  htie.resize((size_t)nt);
+  HIPCHK(hipMemcpy(htie.data(), r.x.tie->tie, htie.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+  for (long long e = 0; e < nt; ++e) {
+    const long long t = htie[(size_t)e];
+    const int b = (int)(e / s.L), l = (int)(e % s.L);
+    if (t == -1) continue;
+    if (t < -1 || t >= nt) return fail(CFD_E_ARG, "cfd_sample_begin_tied: tie[%d][%d] = %lld is not -1 or a token in [0, %lld)", b, l, t, nt);
+    if (t == e) return fail(CFD_E_ARG, "cfd_sample_begin_tied: tie[%d][%d] = %lld ties the token to itself", b, l, t);
+    if (htie[(size_t)t] != -1)
+      return fail(CFD_E_ARG, "cfd_sample_begin_tied: tie[%d][%d] = %lld names a source (%lld, %lld) that is itself tied (no chains)", b, l, t,
+                  t / s.L, t % s.L);
+    if (!hkeep.empty() && hkeep[(size_t)t])
+      return fail(CFD_E_ARG, "cfd_sample_begin_tied: tie[%d][%d] = %lld names a source (%lld, %lld) that is kept (a source must be free)", b, l,
+                  t, t / s.L, t % s.L);
+    if (!hkeep.empty() && hkeep[(size_t)e]) return fail(CFD_E_ARG, "cfd_sample_begin_tied: token (%d, %d) is both kept and tied", b, l);
   }
-  std::vector<int32_t> htie;
-  if (tie) {   // the tie table on the host: range, no self-tie, a source is free (neither tied nor kept), no token both kept and tied
-    if (s.L < 1) return fail(CFD_E_ARG, "bad L");
-    const long long nt = (long long)s.B * s.L;
-    htie.resize((size_t)nt);
-    HIPCHK(hipMemcpy(htie.data(), tie->tie, htie.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-    for (long long e = 0; e < nt; ++e) {
-      const long long t = htie[(size_t)e];
-      const int b = (int)(e / s.L), l = (int)(e % s.L);
-      if (t == -1) continue;
-      if (t < -1 || t >= nt) return fail(CFD_E_ARG, "cfd_sample_begin_tied: tie[%d][%d] = %lld is not -1 or a token in [0, %lld)", b, l, t, nt);
-      if (t == e) return fail(CFD_E_ARG, "cfd_sample_begin_tied: tie[%d][%d] = %lld ties the token to itself", b, l, t);
-      if (htie[(size_t)t] != -1)
-        return fail(CFD_E_ARG, "cfd_sample_begin_tied: tie[%d][%d] = %lld names a source (%lld, %lld) that is itself tied (no chains)", b, l, t,
-                    t / s.L, t % s.L);
-      if (!hkeep.empty() && hkeep[(size_t)t])
-        return fail(CFD_E_ARG, "cfd_sample_begin_tied: tie[%d][%d] = %lld names a source (%lld, %lld) that is kept (a source must be free)", b, l,
-                    t, t / s.L, t % s.L);
-      if (!hkeep.empty() && hkeep[(size_t)e]) return fail(CFD_E_ARG, "cfd_sample_begin_tied: token (%d, %d) is both kept and tied", b, l);
-    }
-  }
-  hipStream_t st = (hipStream_t)stream;
+  return CFD_OK;
+}
+
+// The run's copy of the arguments and its evaluated chunks: the trailing zero-weight chunks trimmed, or a weighted run's table
+static int select_chunks(BeginState& r) {
+  Ctx* c = r.c;
+  const cfd_sample_args& s = r.s;
   c->sargs = s;
-  c->run_stream = st;
+  c->run_stream = r.st;
   c->setup_launches = 0;
-  int n_ring = 0;
-  for (int j = 0; j < CFD_NMEM; ++j) n_ring += s.att_ring[j] != nullptr;
-  if (n_ring != 0 && n_ring != CFD_NMEM) return fail(CFD_E_ARG, "att_ring: give all five buffers or none");
-  if (n_ring && s.skip_zero_weight_chunks && s.G > 1 && s.guidance_weight[s.G - 1] == 0.0f)
+  for (int j = 0; j < CFD_NMEM; ++j) r.n_ring += s.att_ring[j] != nullptr;
+  if (r.n_ring != 0 && r.n_ring != CFD_NMEM) return fail(CFD_E_ARG, "att_ring: give all five buffers or none");
+  if (r.n_ring && s.skip_zero_weight_chunks && s.G > 1 && s.guidance_weight[s.G - 1] == 0.0f)
     return fail(CFD_E_ARG, "att_ring keeps the maps of the LAST guidance chunk: it must be evaluated (skip_zero_weight_chunks = 0)");
-  if (s.skip_zero_weight_chunks)   // chunk-major batch: dropping trailing chunks = using the first G' * B rows
-    while (c->sargs.G > 1 && s.guidance_weight[c->sargs.G - 1] == 0.0f) c->sargs.G -= 1;
-  // N = loop iterations (the length of scheduler.timesteps); n_inf = the count given to set_timesteps, which fixes the
-  // stride `prev_t = t - T // n_inf` of the step formulas.  They differ only for a caller-supplied table.
-  const int n_inf = s.num_inference_steps, N = s.timesteps ? s.num_timesteps : n_inf, T = s.num_train_timesteps;
+  trim_zero_weight_chunks(c, s);
   c->sargs.timesteps = nullptr;   // (host pointer: not kept beyond this call)
-  c->run_iters = N;
+  c->run_iters = r.N;
   for (int k = 0; k < 8; ++k) c->chunk_pos[k] = k;
-  cfd_memory mem_in[CFD_NMEM];
-  for (int j = 0; j < CFD_NMEM; ++j) mem_in[j] = s.mem[j];
-  int keep_idx[8];
-  if (wtab) CHK(weighted_chunks(c, wtab, x.prune, N, n_ring != 0, mem_in, keep_idx, st));
-  const int Be = c->sargs.G * s.B;
-  {
-    // chunk permutation (see chunk_pos): group the chunks that use one shared copy of the largest memory
-    const int G = c->sargs.G, B = s.B;
-    bool all_maps = c->permute && G > 2;
-    int jb = 0;
-    for (int j = 0; j < CFD_NMEM; ++j) {
-      if (!mem_in[j].row_map) all_maps = false;
-      if (s.mem[j].S > s.mem[jb].S) jb = j;
-    }
-    if (all_maps) {
-      std::vector<int> hm(Be);
-      HIPCHK(hipMemcpy(hm.data(), mem_in[jb].row_map, (size_t)Be * 4, hipMemcpyDeviceToHost));
-      std::vector<int> key(G);   // the shared memory index of a uniform chunk, or -1
-      for (int g = 0; g < G; ++g) {
-        key[g] = hm[(size_t)g * B];
-        for (int u = 1; u < B; ++u)
-          if (hm[(size_t)g * B + u] != key[g]) { key[g] = -1; break; }
-      }
-      std::vector<int> order;   // order[position] = original chunk: uniform chunks grouped by key, first occurrence first
-      std::vector<char> used(G, 0);
-      for (int g = 0; g < G; ++g) {
-        if (used[g] || key[g] < 0) continue;
-        for (int h = g; h < G; ++h)
-          if (!used[h] && key[h] == key[g]) { order.push_back(h); used[h] = 1; }
-      }
-      for (int g = 0; g < G; ++g)
-        if (!used[g]) order.push_back(g);
-      bool ident = true;
-      for (int pnum = 0; pnum < G; ++pnum) ident = ident && order[pnum] == pnum;
-      if (!ident) {
-        for (int pnum = 0; pnum < G; ++pnum) c->chunk_pos[order[pnum]] = pnum;
-        std::vector<int> pm(Be);
-        for (int j = 0; j < CFD_NMEM; ++j) {
-          HIPCHK(hipMemcpy(hm.data(), mem_in[j].row_map, (size_t)Be * 4, hipMemcpyDeviceToHost));
-          for (int pnum = 0; pnum < G; ++pnum)
-            for (int u = 0; u < B; ++u) pm[(size_t)pnum * B + u] = hm[(size_t)order[pnum] * B + u];
-          CHK(c->perm_map[j].ensure((size_t)Be * 4));
-          HIPCHK(hipMemcpy(c->perm_map[j].p, pm.data(), (size_t)Be * 4, hipMemcpyHostToDevice));
-          mem_in[j].row_map = c->perm_map[j].as<int32_t>();
-        }
-      }
-    }
+  for (int j = 0; j < CFD_NMEM; ++j) r.mem_in[j] = s.mem[j];
+  if (r.x.weights) CHK(weighted_chunks(c, r.x.weights, r.x.prune, r.N, r.n_ring != 0, r.mem_in, r.keep_idx, r.st));
+  return CFD_OK;
+}
+
+// Chunk permutation (see chunk_pos): group the chunks that use one shared copy of the largest memory
+static int permute_chunks(BeginState& r) {
+  Ctx* c = r.c;
+  const int G = c->sargs.G, B = r.s.B, Be = G * B;
+  bool all_maps = c->permute && G > 2;
+  int jb = 0;
+  for (int j = 0; j < CFD_NMEM; ++j) {
+    if (!r.mem_in[j].row_map) all_maps = false;
+    if (r.s.mem[j].S > r.s.mem[jb].S) jb = j;
   }
-  if (wtab) {
-    for (int k = 0; k < 8; ++k) c->wpos[k] = c->chunk_pos[keep_idx[k] >= 0 ? keep_idx[k] : 0];
-    c->run.weighted = true;
-    if (x.chunks_evaluated) *x.chunks_evaluated = c->sargs.G;
+  if (!all_maps) return CFD_OK;
+  std::vector<int> hm;
+  CHK(host_row_map(r.mem_in[jb], Be, MEM_NAMES[jb], hm));
+  std::vector<int> key(G);   // the shared memory index of a uniform chunk, or -1
+  for (int g = 0; g < G; ++g) {
+    key[g] = hm[(size_t)g * B];
+    for (int u = 1; u < B; ++u)
+      if (hm[(size_t)g * B + u] != key[g]) { key[g] = -1; break; }
   }
-  // operand policy of the run (cfd_sample_args::operand_policy): single-fp16 key / value tiles of the long memories for the fused
-  // cross-attention kernel -- only where that kernel runs on projections made once per run and keeps no maps
-  c->want_f16 = !n_ring && !s.dynamic_memory_mask && (c->xa_operands >= 0 ? c->xa_operands : (s.operand_policy & 15)) != 0;
-  const int r_setup = setup_problem(c, Be, s.L, mem_in, nullptr, 0, N);
+  std::vector<int> order;   // order[position] = original chunk: uniform chunks grouped by key, first occurrence first
+  std::vector<char> used(G, 0);
+  for (int g = 0; g < G; ++g) {
+    if (used[g] || key[g] < 0) continue;
+    for (int h = g; h < G; ++h)
+      if (!used[h] && key[h] == key[g]) { order.push_back(h); used[h] = 1; }
+  }
+  for (int g = 0; g < G; ++g)
+    if (!used[g]) order.push_back(g);
+  bool ident = true;
+  for (int pnum = 0; pnum < G; ++pnum) ident = ident && order[pnum] == pnum;
+  if (ident) return CFD_OK;
+  for (int pnum = 0; pnum < G; ++pnum) c->chunk_pos[order[pnum]] = pnum;
+  std::vector<int> pm(Be);
+  for (int j = 0; j < CFD_NMEM; ++j) {
+    CHK(host_row_map(r.mem_in[j], Be, MEM_NAMES[j], hm));
+    for (int pnum = 0; pnum < G; ++pnum)
+      for (int u = 0; u < B; ++u) pm[(size_t)pnum * B + u] = hm[(size_t)order[pnum] * B + u];
+    CHK(c->perm_map[j].ensure((size_t)Be * 4));
+    HIPCHK(hipMemcpy(c->perm_map[j].p, pm.data(), (size_t)Be * 4, hipMemcpyHostToDevice));
+    r.mem_in[j].row_map = c->perm_map[j].as<int32_t>();
+  }
+  return CFD_OK;
+}
+
+// The problem of the run's forward.  Operand policy of the run (cfd_sample_args::operand_policy): single-fp16 key / value tiles of the
+// long memories for the fused cross-attention kernel -- only where that kernel runs on projections made once per run and keeps no maps;
+// want_f16 says so to setup_problem alone.
+static int setup_run_problem(BeginState& r) {
+  Ctx* c = r.c;
+  const cfd_sample_args& s = r.s;
+  c->want_f16 = !r.n_ring && !s.dynamic_memory_mask && (c->xa_operands >= 0 ? c->xa_operands : (s.operand_policy & 15)) != 0;
+  const int r_setup = setup_problem(c, c->sargs.G * s.B, s.L, r.mem_in, nullptr, 0, r.N);
   c->want_f16 = false;
   CHK(r_setup);
   if (c->share0 && c->sargs.G > 1) c->w->pb.share_B = s.B;   // begin_step_kernel writes G identical copies of the B rows
-  c->w->pb.att_nb = 0;
-  if (n_ring) {
-    // The reference keeps att_mats of the full-conditioning chunk of EVERY iteration (convofusion.py:517-523).  On the row-tile path the
-    // second cross-attention launch has the probabilities in registers anyway: the rows of the last chunk store them into slot *d_step
-    // of the caller's ring, inside the captured iteration -- no second forward, no host round trip.
-    Problem& pb = c->w->pb;
-    // ... and on the tile kernels the fused cross-attention kernel has them in its softmax: its ATT instance keeps them, att_fixup_kernel
-    // normalises them once per step (xattn_fused.hpp, XaAtt).  What cannot keep them: a run without the fused kernel (memories made per
-    // step: dynamic memories; CFD_FUSED_XATTN=0).
-    const bool fused_ok = c->fused_xattn && pb.xa_nwg > 0;
-    if ((!pb.rt && !fused_ok) || s.dynamic_memory_mask)
-      return fail(CFD_E_SHAPE, "att_ring needs the row-tile path or the fused cross-attention kernel (one timestep per step, no dynamic memory): "
-                               "this run has L = %d, %lld token rows; take the maps with one forward per iteration instead", s.L, (long long)Be * s.L);
-    pb.att_b0 = c->chunk_pos[c->sargs.G - 1] * s.B;
-    pb.att_nb = s.B;
-    for (int j = 0; j < CFD_NMEM; ++j) {
-      pb.att_slot[j] = (long long)s.B * c->nl * s.L * pb.S[j];
-      // slot *d_step of the ring base: an edit run's d_step starts at k0 and executed iteration j goes to the caller's slot j
-      pb.att[j] = s.att_ring[j] - (long long)k0 * pb.att_slot[j];
-    }
-    if (!pb.rt) {
-      pb.att_fused = true;
-      CHK(setup_att_fused(c));
-      CHK(build_xattn_worklist(c, mem_in, true));   // (once more: the list now says which tiles keep their maps)
-      if (pb.xa_nwg <= 0) return fail(CFD_E_SHAPE, "att_ring: the fused cross-attention work list is empty");
-    }
+  return CFD_OK;
+}
+
+// The reference keeps att_mats of the full-conditioning chunk of EVERY iteration (convofusion.py:517-523).  On the row-tile path the
+// second cross-attention launch has the probabilities in registers anyway: the rows of the last chunk store them into slot *d_step
+// of the caller's ring, inside the captured iteration -- no second forward, no host round trip.
+static int wire_att_ring(BeginState& r) {
+  Ctx* c = r.c;
+  const cfd_sample_args& s = r.s;
+  Problem& pb = c->w->pb;
+  pb.att_nb = 0;
+  if (!r.n_ring) return CFD_OK;
+  // ... and on the tile kernels the fused cross-attention kernel has them in its softmax: its ATT instance keeps them, att_fixup_kernel
+  // normalises them once per step (xattn_fused.hpp, XaAtt).  What cannot keep them: a run without the fused kernel (memories made per
+  // step: dynamic memories; CFD_FUSED_XATTN=0).
+  const bool fused_ok = c->fused_xattn && pb.xa_nwg > 0;
+  if ((!pb.rt && !fused_ok) || s.dynamic_memory_mask)
+    return fail(CFD_E_SHAPE, "att_ring needs the row-tile path or the fused cross-attention kernel (one timestep per step, no dynamic memory): "
+                             "this run has L = %d, %lld token rows; take the maps with one forward per iteration instead", s.L,
+                (long long)c->sargs.G * s.B * s.L);
+  pb.att_b0 = c->chunk_pos[c->sargs.G - 1] * s.B;
+  pb.att_nb = s.B;
+  for (int j = 0; j < CFD_NMEM; ++j) {
+    pb.att_slot[j] = (long long)s.B * c->nl * s.L * pb.S[j];
+    // slot *d_step of the ring base: an edit run's d_step starts at k0 and executed iteration j goes to the caller's slot j
+    pb.att[j] = s.att_ring[j] - (long long)r.k0 * pb.att_slot[j];
   }
-  CHK(build_xattn_layer0_lists(c, mem_in));
-  {   // (the rest of the operand policy's conditions; prepare_static_memside checks that every memory's projections are made once per run)
-    Problem& pb = c->w->pb;
-    const bool fused_run = !pb.rt && c->fused_xattn && pb.xa_nwg > 0 && !pb.att_fused && !s.dynamic_memory_mask;
-    if (!fused_run) pb.xa_f16 = false;
-    // the attention-concentration census (cfd_sample_args::census_tau): the same runs as the operand policy -- the others keep pairs anyway
-    c->acen_tau = s.census_tau > 0.f ? s.census_tau : 0.f;
-    c->acen_on = fused_run && c->acen_tau > 0.f;
-    if (c->acen_on) CHK(c->acen.ensure((size_t)c->nl * XA_CEN_SLOTS * XA_CEN_STRIDE * sizeof(unsigned)));
+  if (!pb.rt) {
+    pb.att_fused = true;
+    CHK(setup_att_fused(c));
+    CHK(build_xattn_worklist(c, r.mem_in, true));   // (once more: the list now says which tiles keep their maps)
+    if (pb.xa_nwg <= 0) return fail(CFD_E_SHAPE, "att_ring: the fused cross-attention work list is empty");
   }
-  // timesteps: the caller's table, or (arange(N) * (T // N)).round()[::-1] (+ steps_offset for DDIM)
-  std::vector<int32_t> ts(N);
-  std::vector<StepCoef> coef(N);
-  const int ratio = T / n_inf;
-  for (int i = 0; i < N; ++i) ts[i] = s.timesteps ? s.timesteps[i] : (N - 1 - i) * ratio + (s.scheduler == 1 ? s.steps_offset : 0);
-  CHK(step_coefficients(s.scheduler, s.alphas_cumprod, T, n_inf, ts.data(), N, s.eta, s.set_alpha_to_one, coef.data(), k0));
-  CHK(c->coef.ensure((size_t)N * sizeof(StepCoef)));
-  HIPCHK(hipMemcpyAsync(c->coef.p, coef.data(), (size_t)N * sizeof(StepCoef), hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemsetAsync(c->w->d_step.p, 0, 16, st));
-  CHK(sat_begin(c, st));    // the census this call reads below counts ITS launches only
-  CHK(build_time_tables(c, ts.data(), N, st));
-  CHK(prepare_static_memside(c, st, s.dynamic_memory_mask, false));
-  HIPCHK(hipStreamSynchronize(st));  // ts / coef host vectors go out of scope
-  CHK(check_saturation(c, "cfd_sample_begin (memories / their once-per-run projections)"));
-  const size_t lat_bytes = (size_t)s.B * s.L * CFD_LAT * 4;
-  CHK(c->latents.ensure(lat_bytes));
-  if (s.init_latents) {
-    HIPCHK(hipMemcpyAsync(c->latents.p, s.init_latents, lat_bytes, hipMemcpyDeviceToDevice, st));
-  } else {
-    CHK(enqueue_philox_fill(c->latents.as<float>(), s.B, s.L * CFD_LAT, (uint64_t)s.seed, 0u, s.first_utterance, 1u, 1.0f, st));
+  return CFD_OK;
+}
+
+// The rest of the operand policy's conditions (prepare_static_memside checks that every memory's projections are made once per run),
+// and the attention-concentration census (cfd_sample_args::census_tau): the same runs -- the others keep pairs anyway
+static int operand_policy_and_census(BeginState& r) {
+  Ctx* c = r.c;
+  CHK(build_xattn_layer0_lists(c, r.mem_in));
+  Problem& pb = c->w->pb;
+  const bool fused_run = !pb.rt && c->fused_xattn && pb.xa_nwg > 0 && !pb.att_fused && !r.s.dynamic_memory_mask;
+  if (!fused_run) pb.xa_f16 = false;
+  c->acen_tau = r.s.census_tau > 0.f ? r.s.census_tau : 0.f;
+  c->acen_on = fused_run && c->acen_tau > 0.f;
+  if (c->acen_on) CHK(c->acen.ensure((size_t)c->nl * XA_CEN_SLOTS * XA_CEN_STRIDE * sizeof(unsigned)));
+  return CFD_OK;
+}
+
+// The source, noise and mask buffers of the edit instances.  source: the edit's (the noise eps = the initial draw, now in the latents);
+// NULL, a tied run without an edit: no kept token, the source and noise buffers are never read.
+static int edit_buffers(BeginState& r, const float* source) {
+  Ctx* c = r.c;
+  CHK(c->enoise.ensure(r.lat_bytes));
+  CHK(c->esrc.ensure(r.lat_bytes));
+  if (source) {
+    HIPCHK(hipMemcpyAsync(c->enoise.p, c->latents.p, r.lat_bytes, hipMemcpyDeviceToDevice, r.st));
+    HIPCHK(hipMemcpyAsync(c->esrc.p, source, r.lat_bytes, hipMemcpyDeviceToDevice, r.st));
   }
+  return upload_keep_mask(c, r.hkeep, (size_t)r.s.B * r.s.L, r.st);
+}
+
+// The anchored instance over a caller's ring of `steps` + 1 slots, read in place, and the keep mask
+static int anchor_over(BeginState& r, const float* ring, int steps) {
+  CHK(upload_keep_mask(r.c, r.hkeep, (size_t)r.s.B * r.s.L, r.st));
+  HIPCHK(hipStreamSynchronize(r.st));   // (hkeep goes out of scope)
+  r.c->run.anchor = true;
+  r.c->run.anchor_ring = ring;
+  r.c->run.anchor_n = steps;
+  return CFD_OK;
+}
+
+// The run's initial latents and what its kind adds: one block per field of BeginExt, each filling its part of RunMode
+static int init_latents_and_kind(BeginState& r) {
+  Ctx* c = r.c;
+  const cfd_sample_args& s = r.s;
+  const BeginExt& x = r.x;
+  hipStream_t st = r.st;
+  CHK(c->latents.ensure(r.lat_bytes));
+  if (s.init_latents) HIPCHK(hipMemcpyAsync(c->latents.p, s.init_latents, r.lat_bytes, hipMemcpyDeviceToDevice, st));
+  else CHK(enqueue_philox_fill(c->latents.as<float>(), s.B, s.L * CFD_LAT, (uint64_t)s.seed, 0u, s.first_utterance, 1u, 1.0f, st));
   // A tied run.  The scheduler step still steps a tied token (from the copied value and the token's own prediction) and, for DPM-Solver++,
   // keeps its x0 history; neither survives: the token is overwritten with its source at the start of the next iteration and once more
   // after the last (cfd_sample_read), and the history of a token feeds that token's step alone.
-  if (tie) {   // the run's own copy of the table; without an edit: no kept token (the source and noise buffers are never read)
-    CHK(c->etie.ensure(htie.size() * sizeof(int32_t)));
-    HIPCHK(hipMemcpyAsync(c->etie.p, htie.data(), htie.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    if (!edit) {
-      CHK(c->enoise.ensure(lat_bytes));
-      CHK(c->esrc.ensure(lat_bytes));
-      CHK(upload_keep_mask(c, hkeep, (size_t)s.B * s.L, st));   // (hkeep is empty here)
-    }
+  if (x.tie) {   // the run's own copy of the table
+    CHK(c->etie.ensure(r.htie.size() * sizeof(int32_t)));
+    HIPCHK(hipMemcpyAsync(c->etie.p, r.htie.data(), r.htie.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if (!x.edit) CHK(edit_buffers(r, nullptr));   // (hkeep is empty here)
     HIPCHK(hipStreamSynchronize(st));   // (htie goes out of scope)
     c->run.tie = true;
   }
-  if (edit) {   // the run's noise eps = the initial draw, the source, the mask; k0 > 0: every token starts at sa_k0 * source + sb_k0 * eps
-    CHK(c->enoise.ensure(lat_bytes));
-    CHK(c->esrc.ensure(lat_bytes));
-    HIPCHK(hipMemcpyAsync(c->enoise.p, c->latents.p, lat_bytes, hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipMemcpyAsync(c->esrc.p, edit->source, lat_bytes, hipMemcpyDeviceToDevice, st));
-    CHK(upload_keep_mask(c, hkeep, (size_t)s.B * s.L, st));
-    if (k0 > 0) {
+  if (x.edit) {   // k0 > 0: every token starts at sa_k0 * source + sb_k0 * eps
+    CHK(edit_buffers(r, x.edit->source));
+    if (r.k0 > 0) {
       const long long n8 = (long long)s.B * s.L * (CFD_LAT / 8);
       hipLaunchKernelGGL(edit_init_kernel<>, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, st, c->latents.as<float>(), c->esrc.as<float>(),
-                         c->enoise.as<float>(), n8, c->coef.as<StepCoef>(), k0);
+                         c->enoise.as<float>(), n8, c->coef.as<StepCoef>(), r.k0);
       HIPCHK(hipGetLastError());
     }
     HIPCHK(hipStreamSynchronize(st));   // (hkeep goes out of scope)
     c->run.edit = true;
-    c->run.k0 = k0;
-    c->run_iters = N - k0;
   }
   if (x.traj) {   // slot 0 of the trajectory: the initial latents (the source of the inversion)
-    HIPCHK(hipMemcpyAsync(x.traj, c->latents.p, lat_bytes, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(x.traj, c->latents.p, r.lat_bytes, hipMemcpyDeviceToDevice, st));
     HIPCHK(hipStreamSynchronize(st));
     c->run.traj = x.traj;
   }
-  if (anchor) {   // the keep mask; the ring is the caller's and is read in place
-    CHK(upload_keep_mask(c, hkeep, (size_t)s.B * s.L, st));
-    HIPCHK(hipStreamSynchronize(st));   // (hkeep goes out of scope)
-    c->run.anchor = true;
-    c->run.anchor_ring = anchor->trajectory;
-    c->run.anchor_n = anchor->steps;
+  if (x.anchor) CHK(anchor_over(r, x.anchor->trajectory, x.anchor->steps));
+  if (x.replay) {   // the anchored instance over the noise space's trajectory; the opener pointed init_latents / step_noise into the rings
+    CHK(anchor_over(r, x.replay->trajectory, x.replay->steps));
+    c->run.replay = true;
   }
-  if (replay) {   // the anchored instance over the noise space's trajectory; the opener pointed init_latents / step_noise into the rings
-    CHK(upload_keep_mask(c, hkeep, (size_t)s.B * s.L, st));
-    HIPCHK(hipStreamSynchronize(st));   // (hkeep goes out of scope)
-    c->run.anchor = c->run.replay = true;
-    c->run.anchor_ring = replay->trajectory;
-    c->run.anchor_n = replay->steps;
-    c->run.k0 = k0;
-    c->run_iters = N - k0;
-  }
+  c->run.k0 = r.k0;   // (0 but for an edit or a replay that starts later)
+  c->run_iters = r.N - r.k0;
   // DPM-Solver++: the x0 history of the run, zeroed.  The first executed iteration is first order and never reads it, so the eager warm-up
-  // iteration below, which runs as that iteration and writes its x0 here, needs no save / restore: the first replay overwrites that before
+  // iteration, which runs as that iteration and writes its x0 here, needs no save / restore: the first replay overwrites that before
   // anything reads it.
   if (s.scheduler == 2) {
-    CHK(c->hist.ensure(lat_bytes));
-    HIPCHK(hipMemsetAsync(c->hist.p, 0, lat_bytes, st));
+    CHK(c->hist.ensure(r.lat_bytes));
+    HIPCHK(hipMemsetAsync(c->hist.p, 0, r.lat_bytes, st));
   }
   CHK(c->inoise.ensure(s.preseq ? (size_t)s.B * s.preseq_len * CFD_LAT * 4 : 16));
   if (s.preseq) {
     HIPCHK(hipMemcpy2DAsync(c->inoise.p, (size_t)s.preseq_len * CFD_LAT * 4, c->latents.p, (size_t)s.L * CFD_LAT * 4,
                             (size_t)s.preseq_len * CFD_LAT * 4, s.B, hipMemcpyDeviceToDevice, st));
   }
-  // capture one loop iteration
-  if (c->gexec) { (void)hipGraphExecDestroy(c->gexec); c->gexec = nullptr; }
-  if (c->graph) { (void)hipGraphDestroy(c->graph); c->graph = nullptr; }
-  // eager warm-up of every kernel variant (sets function attributes outside capture); the iteration is
-  // idempotent on the workspace and we restore the state it mutates (latents, in-paint noise, step index).
-  {
-    DBuf save_lat, save_in;
-    CHK(save_lat.ensure(lat_bytes));
-    HIPCHK(hipMemcpyAsync(save_lat.p, c->latents.p, lat_bytes, hipMemcpyDeviceToDevice, st));
-    if (s.preseq) {
-      CHK(save_in.ensure(c->inoise.bytes));
-      HIPCHK(hipMemcpyAsync(save_in.p, c->inoise.p, c->inoise.bytes, hipMemcpyDeviceToDevice, st));
-    }
-    if (k0) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)c->w->d_step.p, k0, 1, st));   // (d_step[0] = k0: coefficients, tables, ring slot 0)
-    int r = enqueue_loop_iteration(c, st);
-    if (r != CFD_OK) return r;
-    HIPCHK(hipMemcpyAsync(c->latents.p, save_lat.p, lat_bytes, hipMemcpyDeviceToDevice, st));
-    if (s.preseq) HIPCHK(hipMemcpyAsync(c->inoise.p, save_in.p, c->inoise.bytes, hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipMemsetAsync(c->w->d_step.p, 0, 16, st));
-    if (k0) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)c->w->d_step.p, k0, 1, st));
-    if (c->acen_on) HIPCHK(hipMemsetAsync(c->acen.p, 0, (size_t)c->nl * XA_CEN_SLOTS * XA_CEN_STRIDE * sizeof(unsigned), st));   // (the warm-up counted too)
-    HIPCHK(hipStreamSynchronize(st));
-    save_lat.release();
-    save_in.release();
+  return CFD_OK;
+}
+
+// Eager warm-up of every kernel variant (sets function attributes outside capture); the iteration is idempotent on the workspace and
+// the state it mutates (latents, in-paint noise, step index) is restored.
+static int warm_up_iteration(BeginState& r) {
+  Ctx* c = r.c;
+  hipStream_t st = r.st;
+  const bool preseq = r.s.preseq != nullptr;
+  DBuf save_lat, save_in;
+  CHK(save_lat.ensure(r.lat_bytes));
+  HIPCHK(hipMemcpyAsync(save_lat.p, c->latents.p, r.lat_bytes, hipMemcpyDeviceToDevice, st));
+  if (preseq) {
+    CHK(save_in.ensure(c->inoise.bytes));
+    HIPCHK(hipMemcpyAsync(save_in.p, c->inoise.p, c->inoise.bytes, hipMemcpyDeviceToDevice, st));
   }
-  // capture and replay on the handle's own stream (the legacy default stream cannot be captured); all
-  // set-up work above was enqueued on the caller's stream and has been waited for.
+  if (r.k0) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)c->w->d_step.p, r.k0, 1, st));   // (d_step[0] = k0: coefficients, tables, ring slot 0)
+  CHK(enqueue_loop_iteration(c, st));
+  HIPCHK(hipMemcpyAsync(c->latents.p, save_lat.p, r.lat_bytes, hipMemcpyDeviceToDevice, st));
+  if (preseq) HIPCHK(hipMemcpyAsync(c->inoise.p, save_in.p, c->inoise.bytes, hipMemcpyDeviceToDevice, st));
+  HIPCHK(hipMemsetAsync(c->w->d_step.p, 0, 16, st));
+  if (r.k0) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)c->w->d_step.p, r.k0, 1, st));
+  if (c->acen_on) HIPCHK(hipMemsetAsync(c->acen.p, 0, (size_t)c->nl * XA_CEN_SLOTS * XA_CEN_STRIDE * sizeof(unsigned), st));   // (the warm-up counted too)
+  HIPCHK(hipStreamSynchronize(st));
+  save_lat.release();
+  save_in.release();
+  return CFD_OK;
+}
+
+// Capture and replay on the handle's own stream (the legacy default stream cannot be captured); all set-up work was enqueued on the
+// caller's stream and has been waited for.
+static int capture_iteration(Ctx* c) {
   hipStream_t cap = c->own_stream;
   c->run_stream = cap;
   c->memside_in_forward = false;
@@ -595,10 +661,54 @@ static int sample_begin(Ctx* c, const cfd_sample_args* args, void* stream, const
   if (e != hipSuccess) return fail(CFD_E_HIP, "stream capture failed: %s", hipGetErrorString(e));
   c->graph = g;
   HIPCHK(hipGraphInstantiate(&c->gexec, c->graph, nullptr, nullptr, 0));
+  return CFD_OK;
+}
+
+// Opens a sampling run: the stages above, in the order the stream sees them
+static int sample_begin(Ctx* c, const cfd_sample_args* args, void* stream, const BeginExt& x) {
+  if (!c || !args) return fail(CFD_E_ARG, "null argument");
+  if (x.weights && args->G != 7) return fail(CFD_E_ARG, "%s: a weight table needs the 7-chunk guidance batch (G = %d)", x.opener, args->G);
+  if (c->run_open) return fail(CFD_E_STATE, "a sampling run is already open");
+  CHK(setup_preamble(c));
+  struct AcenOff { Ctx* c; ~AcenOff() { c->acen_on = false; } } acen_off{c};   // (the census slots go only into THIS run's launches)
+  c->acen_valid = c->acen_measured = false;
+  c->acen_hits = 0;
+  cfd_sample_args s_w;
+  if (x.weights) {   // a weighted run ignores guidance_weight and skip_zero_weight_chunks (its table says which chunks count)
+    s_w = *args;
+    s_w.skip_zero_weight_chunks = 0;
+    args = &s_w;
+  }
+  c->run = RunMode{};
+  // N = loop iterations (the length of scheduler.timesteps); num_inference_steps = the count given to set_timesteps, which fixes the
+  // stride `prev_t = t - T // n_inf` of the step formulas.  They differ only for a caller-supplied table.
+  BeginState r{c, *args, x, (hipStream_t)stream, args->timesteps ? args->num_timesteps : args->num_inference_steps,
+               x.edit ? x.edit->first_iteration : x.replay ? x.replay->first_iteration : 0};
+  r.lat_bytes = (size_t)args->B * args->L * CFD_LAT * 4;
+  CHK(check_run_args(r));
+  CHK(fetch_keep_mask(r));
+  CHK(fetch_tie_table(r));
+  CHK(select_chunks(r));
+  CHK(permute_chunks(r));
+  if (x.weights) {
+    for (int k = 0; k < 8; ++k) c->wpos[k] = c->chunk_pos[r.keep_idx[k] >= 0 ? r.keep_idx[k] : 0];
+    c->run.weighted = true;
+    if (x.chunks_evaluated) *x.chunks_evaluated = c->sargs.G;
+  }
+  CHK(setup_run_problem(r));
+  CHK(wire_att_ring(r));
+  CHK(operand_policy_and_census(r));
+  CHK(upload_run_tables(c, r.s, r.N, r.k0, r.st));
+  CHK(check_saturation(c, "cfd_sample_begin (memories / their once-per-run projections)"));
+  CHK(init_latents_and_kind(r));
+  if (c->gexec) { (void)hipGraphExecDestroy(c->gexec); c->gexec = nullptr; }
+  if (c->graph) { (void)hipGraphDestroy(c->graph); c->graph = nullptr; }
+  CHK(warm_up_iteration(r));
+  CHK(capture_iteration(c));
   c->run_open = true;
   c->run_pos = 0;
   c->acen_valid = true;
-  if (!wtab && x.chunks_evaluated) *x.chunks_evaluated = c->sargs.G;
+  if (!x.weights && x.chunks_evaluated) *x.chunks_evaluated = c->sargs.G;
   return CFD_OK;
 }
 
@@ -683,7 +793,7 @@ extern "C" int cfd_sample_begin_replay(cfd_handle c, const cfd_sample_args* args
   if (r->steps != n_iter || r->B != args->B || r->L != args->L)
     return fail(CFD_E_ARG, "cfd_sample_begin_replay: the noise space is [%d][%d][%d][128], this run has %d iterations of [%d][%d][128]", r->steps,
                 r->B, r->L, n_iter, args->B, args->L);
-  if (r->first_iteration < 0 || r->first_iteration >= n_iter)
+  if (r->first_iteration < 0 || r->first_iteration >= n_iter)   // (here, not in check_run_args: init_latents below is computed from it)
     return fail(CFD_E_ARG, "cfd_sample_begin_replay: first_iteration = %d is not in [0, %d)", r->first_iteration, n_iter);
   cfd_sample_args s = *args;   // the run starts from the level iteration k0 enters and takes the recorded noise as its step noise
   s.init_latents = r->trajectory + (size_t)(n_iter - r->first_iteration) * args->B * args->L * CFD_LAT;
@@ -712,117 +822,101 @@ static int level_batch_refusals(Ctx* c, const cfd_sample_args* args, const char*
 // The guidance combine of a level batch and its sizes, as level_batch_setup leaves them
 struct LevelBatch {
   int B, L, N, Ge, J;
-  int Gc;                // chunks of the combine (7 for a weighted run, else Ge)
-  float w[8];
-  int pos[8];            // chunk k's rows within a level start at row pos[k] * B
-  const float* wtab;     // dev [N][B][8] or null
+  Combine g;             // Gc: 7 for a weighted run, else Ge; wtab: dev [N][B][8] or null
 };
 
+// J, the levels of a batch: the caller's count, or what the workspace budget holds of what setup_problem allocates per level (token rows
+// and the memories' per-forward projections; an estimate, not an enforced cap); at most N, and at most 32768 batch rows (a launch's grid).
+// (default 4 GiB: at the product shape ~150 levels for one utterance, ~40 for eight; measured 0.042 s at J = 100 against 0.059 s at
+//  J = 41 and 0.187 s at J = 40 against 0.279 s at J = 8 for N = 1000, profiles/r13_ddpm_inversion_time.json)
+static int levels_per_batch_of(Ctx* c, const cfd_memory mem_in[CFD_NMEM], int R, int L, int N, int levels_per_batch, size_t workspace_bytes,
+                               int* J_out) {
+  size_t per_level = 0;
+  int sp_tot = 0;
+  for (int j = 0; j < CFD_NMEM; ++j) {
+    if (mem_in[j].U < 1 || mem_in[j].S < 1) return fail(CFD_E_ARG, "memory %s: null/empty", MEM_NAMES[j]);
+    const size_t sp = (size_t)(mem_in[j].S + 31) / 32 * 32;
+    sp_tot += (int)sp;
+    per_level += (size_t)mem_in[j].U * sp * ((size_t)CFD_D * 4 * (1 + 2 * c->nl) + 4 * (c->nl + 1));
+  }
+  per_level += (size_t)R * L * ((size_t)CFD_D * 4 * 6 + (size_t)CFD_FF * 4 + (size_t)sp_tot * 8 + CFD_LAT * 8) +
+               (size_t)R * ((size_t)CFD_D * 64 * 4 + (size_t)CFD_NHEAD * L * ((L + 31) / 32 * 32) * 8);
+  const size_t budget = workspace_bytes ? workspace_bytes : (size_t)4 << 30;
+  const long long J = levels_per_batch ? levels_per_batch : (long long)(budget / per_level);
+  *J_out = (int)std::max<long long>(1, std::min<long long>({J, (long long)N, 32768 / R > 0 ? 32768 / R : 1}));
+  return CFD_OK;
+}
+
+// The level batch's memories: instance lv * U + u = the caller's memory u at level lv, through level row maps (R rows per level, their
+// entries range-checked here); masks once per level
+static int level_batch_memories(Ctx* c, const cfd_memory mem_in[CFD_NMEM], int R, int J, cfd_memory vm[CFD_NMEM]) {
+  const int Be = J * R;
+  std::vector<int> hm, lm((size_t)Be);
+  for (int j = 0; j < CFD_NMEM; ++j) {
+    const int U = mem_in[j].U;
+    CHK(host_row_map(mem_in[j], R, MEM_NAMES[j], hm));
+    for (int r = 0; r < R; ++r)
+      if (hm[r] < 0 || hm[r] >= U) return fail(CFD_E_ARG, "memory %s: row_map[%d] = %d outside [0, %d)", MEM_NAMES[j], r, hm[r], U);
+    for (int lv = 0; lv < J; ++lv)
+      for (int r = 0; r < R; ++r) lm[(size_t)lv * R + r] = lv * U + hm[r];
+    CHK(c->lv_map[j].ensure((size_t)Be * 4));
+    HIPCHK(hipMemcpy(c->lv_map[j].p, lm.data(), (size_t)Be * 4, hipMemcpyHostToDevice));
+    vm[j] = mem_in[j];
+    vm[j].row_map = c->lv_map[j].as<int32_t>();
+    vm[j].U = J * U;
+    if (mem_in[j].key_padding_mask) {
+      const size_t mb = (size_t)U * mem_in[j].S;
+      CHK(c->lv_mask[j].ensure(mb * (size_t)J));
+      for (int lv = 0; lv < J; ++lv)
+        HIPCHK(hipMemcpy(c->lv_mask[j].as<uint8_t>() + (size_t)lv * mb, mem_in[j].key_padding_mask, mb, hipMemcpyDeviceToDevice));
+      vm[j].key_padding_mask = c->lv_mask[j].as<uint8_t>();
+    }
+  }
+  return CFD_OK;
+}
+
 // Everything a level batch needs before its first forward: the evaluated chunks and their row maps, J from the workspace budget, the
-// level row maps and masks, the problem (tmode 2, table of N rows), the step coefficients and the time tables; the saturation census is
-// opened and the stream waited for.  The caller sets Problem::lv_i0 per batch and reads the census at its end.
+// level row maps and masks, the problem (tmode 2, table of N rows) and the run's tables (upload_run_tables: the saturation census is
+// opened and the stream waited for).  The caller sets Problem::lv_i0 per batch and reads the census at its end.  coef_out: the
+// coefficient rows on the host.
 static int level_batch_setup(Ctx* c, const cfd_sample_args& s, const char* who, const float* wtab, int prune, int levels_per_batch,
-                             size_t workspace_bytes, hipStream_t st, LevelBatch* lb) {
+                             size_t workspace_bytes, hipStream_t st, LevelBatch* lb, std::vector<StepCoef>* coef_out = nullptr) {
   if (wtab && s.G != 7) return fail(CFD_E_ARG, "%s: a weight table needs the 7-chunk guidance batch (G = %d)", who, s.G);
   if (s.B < 1 || s.L < 2 || s.G < 1 || s.G > 8) return fail(CFD_E_ARG, "bad B / L / G");
-  if (!s.alphas_cumprod || s.num_train_timesteps < 1 || s.num_inference_steps < 1 || s.num_inference_steps > s.num_train_timesteps)
-    return fail(CFD_E_ARG, "bad scheduler tables");
-  if (s.timesteps && (s.num_timesteps < 1 || s.num_timesteps > s.num_train_timesteps)) return fail(CFD_E_ARG, "bad num_timesteps");
-  if (!s.timesteps && s.num_train_timesteps % s.num_inference_steps)
-    return fail(CFD_E_ARG, "DDPM: num_inference_steps = %d does not divide num_train_timesteps = %d; pass the scheduler's table in "
-                           "cfd_sample_args.timesteps", s.num_inference_steps, s.num_train_timesteps);
-  HIPCHK(hipSetDevice(c->cfg.device));
-  c->hint_now = c->hint_same_mem = false;
-  CHK(settle_deferred_census(c));
-  const int B = s.B, L = s.L, n_inf = s.num_inference_steps, N = s.timesteps ? s.num_timesteps : n_inf, T = s.num_train_timesteps;
+  CHK(check_scheduler_tables(s, who));
+  CHK(setup_preamble(c));
+  const int N = s.timesteps ? s.num_timesteps : s.num_inference_steps;
   // the evaluated chunks and their memories' row maps, as a run with these arguments would have them (weighted_chunks works on c->sargs)
   c->sargs = s;
   c->sargs.timesteps = nullptr;
-  cfd_memory mem_in[CFD_NMEM];
+  cfd_memory mem_in[CFD_NMEM], vm[CFD_NMEM];
   for (int j = 0; j < CFD_NMEM; ++j) mem_in[j] = s.mem[j];
   memset(lb, 0, sizeof(*lb));
   if (wtab) {
     int keep_idx[8];
     CHK(weighted_chunks(c, wtab, prune, N, false, mem_in, keep_idx, st));
-    for (int k = 0; k < 8; ++k) lb->pos[k] = keep_idx[k] >= 0 ? keep_idx[k] : 0;
-    lb->Gc = 7;
-    lb->wtab = c->wtab.as<float>();
+    for (int k = 0; k < 8; ++k) lb->g.pos[k] = keep_idx[k] >= 0 ? keep_idx[k] : 0;
+    lb->g.Gc = 7;
+    lb->g.wtab = c->wtab.as<float>();
   } else {
-    if (s.skip_zero_weight_chunks)
-      while (c->sargs.G > 1 && s.guidance_weight[c->sargs.G - 1] == 0.0f) c->sargs.G -= 1;
-    for (int k = 0; k < 8; ++k) { lb->pos[k] = k < c->sargs.G ? k : 0; lb->w[k] = s.guidance_weight[k]; }
-    lb->Gc = c->sargs.G;
+    trim_zero_weight_chunks(c, s);
+    for (int k = 0; k < 8; ++k) { lb->g.pos[k] = k < c->sargs.G ? k : 0; lb->g.w[k] = s.guidance_weight[k]; }
+    lb->g.Gc = c->sargs.G;
   }
-  const int Ge = c->sargs.G, R = Ge * B;   // rows of a level
-  // J from the workspace budget: what setup_problem allocates per level (token rows and the memories' per-forward projections)
-  size_t per_level = 0;
-  {
-    int sp_tot = 0;
-    for (int j = 0; j < CFD_NMEM; ++j) {
-      if (mem_in[j].U < 1 || mem_in[j].S < 1) return fail(CFD_E_ARG, "memory %s: null/empty", MEM_NAMES[j]);
-      const size_t sp = (size_t)(mem_in[j].S + 31) / 32 * 32;
-      sp_tot += (int)sp;
-      per_level += (size_t)mem_in[j].U * sp * ((size_t)CFD_D * 4 * (1 + 2 * c->nl) + 4 * (c->nl + 1));
-    }
-    per_level += (size_t)R * L * ((size_t)CFD_D * 4 * 6 + (size_t)CFD_FF * 4 + (size_t)sp_tot * 8 + CFD_LAT * 8) +
-                 (size_t)R * ((size_t)CFD_D * 64 * 4 + (size_t)CFD_NHEAD * L * ((L + 31) / 32 * 32) * 8);
-  }
-  // (default 4 GiB: at the product shape ~150 levels for one utterance, ~40 for eight; measured 0.042 s at J = 100 against 0.059 s at
-  //  J = 41 and 0.187 s at J = 40 against 0.279 s at J = 8 for N = 1000, profiles/r13_ddpm_inversion_time.json.  per_level is an estimate
-  //  of what setup_problem allocates, not an enforced cap)
-  const size_t budget = workspace_bytes ? workspace_bytes : (size_t)4 << 30;
-  long long J = levels_per_batch ? levels_per_batch : (long long)(budget / per_level);
-  J = std::max<long long>(1, std::min<long long>({J, (long long)N, 32768 / R > 0 ? 32768 / R : 1}));   // (a launch's grid: at most 32768 batch rows)
-  const int Be = (int)J * R;
-  // the level batch's memories: instance lv * U + u = the caller's memory u at level lv, through level row maps; masks once per level
-  cfd_memory vm[CFD_NMEM];
-  {
-    std::vector<int> hm(R), lm((size_t)Be);
-    for (int j = 0; j < CFD_NMEM; ++j) {
-      const int U = mem_in[j].U;
-      if (mem_in[j].row_map) {
-        HIPCHK(hipMemcpy(hm.data(), mem_in[j].row_map, (size_t)R * 4, hipMemcpyDeviceToHost));
-      } else {
-        if (U != R) return fail(CFD_E_ARG, "memory %s: U = %d != G * B = %d without a row_map", MEM_NAMES[j], U, R);
-        for (int r = 0; r < R; ++r) hm[r] = r;
-      }
-      for (int r = 0; r < R; ++r)
-        if (hm[r] < 0 || hm[r] >= U) return fail(CFD_E_ARG, "memory %s: row_map[%d] = %d outside [0, %d)", MEM_NAMES[j], r, hm[r], U);
-      for (int lv = 0; lv < (int)J; ++lv)
-        for (int r = 0; r < R; ++r) lm[(size_t)lv * R + r] = lv * U + hm[r];
-      CHK(c->lv_map[j].ensure((size_t)Be * 4));
-      HIPCHK(hipMemcpy(c->lv_map[j].p, lm.data(), (size_t)Be * 4, hipMemcpyHostToDevice));
-      vm[j] = mem_in[j];
-      vm[j].row_map = c->lv_map[j].as<int32_t>();
-      vm[j].U = (int)J * U;
-      if (mem_in[j].key_padding_mask) {
-        const size_t mb = (size_t)U * mem_in[j].S;
-        CHK(c->lv_mask[j].ensure(mb * (size_t)J));
-        for (int lv = 0; lv < (int)J; ++lv)
-          HIPCHK(hipMemcpy(c->lv_mask[j].as<uint8_t>() + (size_t)lv * mb, mem_in[j].key_padding_mask, mb, hipMemcpyDeviceToDevice));
-        vm[j].key_padding_mask = c->lv_mask[j].as<uint8_t>();
-      }
-    }
-  }
+  lb->g.clip = s.clip_sample;
+  lb->B = s.B; lb->L = s.L; lb->N = N; lb->Ge = c->sargs.G;
+  const int R = lb->Ge * s.B;   // rows of a level
+  CHK(levels_per_batch_of(c, mem_in, R, s.L, N, levels_per_batch, workspace_bytes, &lb->J));
+  CHK(level_batch_memories(c, mem_in, R, lb->J, vm));
   c->want_f16 = false;   // (operands are split pairs throughout)
-  CHK(setup_problem(c, Be, L, vm, nullptr, 2, N));
+  CHK(setup_problem(c, lb->J * R, s.L, vm, nullptr, 2, N));
   Problem& pb = c->w->pb;
   pb.lv_rows = R;
   pb.lv_i0 = 0;
   for (int j = 0; j < CFD_NMEM; ++j) pb.lv_U[j] = mem_in[j].U;
-  std::vector<int32_t> ts(N);
-  std::vector<StepCoef> coef(N);
-  for (int i = 0; i < N; ++i) ts[i] = s.timesteps ? s.timesteps[i] : (N - 1 - i) * (T / n_inf);
-  CHK(step_coefficients(0, s.alphas_cumprod, T, n_inf, ts.data(), N, 0.f, 1, coef.data()));
-  CHK(c->coef.ensure((size_t)N * sizeof(StepCoef)));
-  HIPCHK(hipMemcpyAsync(c->coef.p, coef.data(), (size_t)N * sizeof(StepCoef), hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemsetAsync(c->w->d_step.p, 0, 16, st));
-  CHK(sat_begin(c, st));
-  CHK(build_time_tables(c, ts.data(), N, st));   // every level's rows, once (a replay over the same table finds them built)
-  CHK(prepare_static_memside(c, st, 0, false));  // (tmode 2: the scale planes only; the projections are made per level in the forward)
-  HIPCHK(hipStreamSynchronize(st));              // ts / coef host vectors go out of scope
-  lb->B = B; lb->L = L; lb->N = N; lb->Ge = Ge; lb->J = (int)J;
-  return CFD_OK;
+  // (time tables: every level's rows, once; prepare_static_memside, tmode 2: the scale planes only, the projections are made per level
+  //  in the forward)
+  return upload_run_tables(c, s, N, 0, st, coef_out);
 }
 
 // ---- edit-friendly DDPM inversion: every level of the table in a few level-batched forwards (cfdenoise.h: cfd_ddpm_invert) ----------
@@ -839,15 +933,13 @@ extern "C" int cfd_ddpm_invert(cfd_handle c, const cfd_sample_args* args, const 
   Problem& pb = c->w->pb;
   ExtractArgs xa;
   memset(&xa, 0, sizeof(xa));
-  for (int k = 0; k < 8; ++k) { xa.pos[k] = lb.pos[k]; xa.w[k] = lb.w[k]; }
-  xa.Gc = lb.Gc;
-  xa.wtab = lb.wtab;
+  xa.g = lb.g;
   const size_t lat_bytes = (size_t)B * L * CFD_LAT * 4;
   HIPCHK(hipMemcpyAsync(inv->trajectory, inv->source, lat_bytes, hipMemcpyDeviceToDevice, st));   // slot 0: the source
   LevelArgs la{inv->source, inv->level_noise, inv->trajectory, c->w->sample_sp.as<char>(), c->coef.as<StepCoef>(), B, L, Ge, N, 0, J,
                (unsigned long long)s.seed, s.first_utterance};
   xa.eps = c->w->eps.as<float>(); xa.traj = inv->trajectory; xa.noise = inv->noise; xa.coef = c->coef.as<StepCoef>();
-  xa.B = B; xa.L = L; xa.G = Ge; xa.N = N; xa.J = J; xa.clip = s.clip_sample;
+  xa.B = B; xa.L = L; xa.G = Ge; xa.N = N; xa.J = J;
   const long long n8 = (long long)J * B * L * (CFD_LAT / 8);
   const dim3 grid((unsigned)((n8 + 255) / 256)), block(256);
   // Batches from the noisiest levels' end of the table downwards: the noise of iteration i needs slot N - i - 1, the level of iteration
@@ -860,7 +952,7 @@ extern "C" int cfd_ddpm_invert(cfd_handle c, const cfd_sample_args* args, const 
     pb.lv_i0 = la.i0 = xa.i0 = i0;
     LAUNCH(CFD_PROF_OTHER, ddpm_level_kernel<>, grid, block, st, la);
     CHK(enqueue_denoise(c, st));
-    if (lb.wtab) LAUNCH(CFD_PROF_OTHER, ddpm_extract_kernel_weighted, grid, block, st, xa);
+    if (lb.g.wtab) LAUNCH(CFD_PROF_OTHER, ddpm_extract_kernel_weighted, grid, block, st, xa);
     else LAUNCH(CFD_PROF_OTHER, ddpm_extract_kernel<>, grid, block, st, xa);
   }
   // the per-level projections count into the handle's census: read here, so that a clamped projection fails THIS call
@@ -899,11 +991,10 @@ extern "C" int cfd_sample_parallel(cfd_handle c, const cfd_sample_args* args, co
   const cfd_sample_args& s = *args;
   hipStream_t st = (hipStream_t)stream;
   LevelBatch lb;
-  CHK(level_batch_setup(c, s, "cfd_sample_parallel", par->weights, par->prune, par->levels_per_batch, par->workspace_bytes, st, &lb));
+  std::vector<StepCoef> coef;   // (the stride rule's sigma)
+  CHK(level_batch_setup(c, s, "cfd_sample_parallel", par->weights, par->prune, par->levels_per_batch, par->workspace_bytes, st, &lb, &coef));
   const int B = lb.B, L = lb.L, N = lb.N, Ge = lb.Ge, J = lb.J;
   Problem& pb = c->w->pb;
-  std::vector<StepCoef> coef(N);   // (the stride rule's sigma: the rows level_batch_setup uploaded)
-  HIPCHK(hipMemcpy(coef.data(), c->coef.p, (size_t)N * sizeof(StepCoef), hipMemcpyDeviceToHost));
   const long long chunk = (long long)B * L * CFD_LAT;
   // the ring: the caller's trajectory, or J + 1 slots of the handle (the window's p + 1 latents; at the end of the table, where the batch
   // starts in front of the window, the J + 1 latents N - J .. N)
@@ -933,8 +1024,7 @@ extern "C" int cfd_sample_parallel(cfd_handle c, const cfd_sample_args* args, co
   PicardStepArgs sa;
   memset(&sa, 0, sizeof(sa));
   sa.eps = c->w->eps.as<float>(); sa.ring = ring; sa.s = sbuf.as<float>(); sa.coef = c->coef.as<StepCoef>();
-  sa.B = B; sa.L = L; sa.G = Ge; sa.J = J; sa.Gc = lb.Gc; sa.clip = s.clip_sample; sa.wtab = lb.wtab;
-  for (int k = 0; k < 8; ++k) { sa.w[k] = lb.w[k]; sa.pos[k] = lb.pos[k]; }
+  sa.B = B; sa.L = L; sa.G = Ge; sa.J = J; sa.g = lb.g;
   sa.noise = s.step_noise; sa.seed = s.seed; sa.utt0 = s.first_utterance;
   PicardScanArgs ca{sbuf.as<float>(), ring, part.as<float>(), L, 0, 0, J};
   const int max_sweeps = par->max_sweeps ? par->max_sweeps : N;
@@ -944,7 +1034,7 @@ extern "C" int cfd_sample_parallel(cfd_handle c, const cfd_sample_args* args, co
     sa.off = ca.off = off;
     LAUNCH(CFD_PROF_OTHER, picard_load_kernel<>, grid_lv, block, st, la);
     CHK(enqueue_denoise(c, st));
-    if (lb.wtab) LAUNCH(CFD_PROF_OTHER, picard_step_kernel_weighted, grid_lv, block, st, sa);
+    if (lb.g.wtab) LAUNCH(CFD_PROF_OTHER, picard_step_kernel_weighted, grid_lv, block, st, sa);
     else LAUNCH(CFD_PROF_OTHER, picard_step_kernel<>, grid_lv, block, st, sa);
     LAUNCH(CFD_PROF_OTHER, picard_scan_kernel<>, dim3((unsigned)nblk, (unsigned)B), block, st, ca);
     LAUNCH(CFD_PROF_OTHER, picard_err_kernel<>, dim3((unsigned)((J * B + 255) / 256)), block, st, part.as<float>(), err.as<float>(), J, B, nblk,
@@ -1137,7 +1227,6 @@ extern "C" int cfd_dpmsolver_step(cfd_handle c, const float* ac, int T, int t, i
 // ---- developer hook: the stride rule of cfd_sample_parallel, on the host (no handle, no device) --------------------------------------
 extern "C" int cfd_test_picard_stride(const float* err, int B, int p, int i0, const float* coef, int N, float tolerance, int L) {
   if (!err || !coef || B < 1 || p < 1 || i0 < 0 || i0 + p > N || L < 1 || !(tolerance >= 0.f)) return fail(CFD_E_ARG, "bad argument");
-  static_assert(sizeof(StepCoef) == 8 * sizeof(float), "StepCoef is one row of 8 floats");
   return picard_stride(err, B, p, i0, reinterpret_cast<const StepCoef*>(coef), tolerance, L);
 }
 
@@ -1145,7 +1234,6 @@ extern "C" int cfd_test_picard_stride(const float* err, int B, int p, int i0, co
 extern "C" int cfd_test_step_coefficients(int kind, const float* ac, int T, int n_inf, const int32_t* timesteps, int N, float eta,
                                           int set_alpha_to_one, float* out) {
   if (!ac || !timesteps || !out || kind < 0 || kind > 3 || T < 1 || N < 1 || n_inf < 1) return fail(CFD_E_ARG, "bad argument");
-  static_assert(sizeof(StepCoef) == 8 * sizeof(float), "StepCoef is one row of 8 floats");
   std::vector<StepCoef> coef(N);
   CHK(step_coefficients(kind, ac, T, n_inf, timesteps, N, eta, set_alpha_to_one, coef.data()));
   memcpy(out, coef.data(), (size_t)N * sizeof(StepCoef));

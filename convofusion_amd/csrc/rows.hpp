@@ -525,6 +525,7 @@ struct StepCoef {   // one row per loop iteration i (timestep t_i), float32 as d
   float order;      // DPM++: 1 or 2 (0 for DDPM / DDIM)
   float r0inv;      // DPM++ order 2: 1 / r0 = h / h_0 (0 otherwise)
 };
+static_assert(sizeof(StepCoef) == 8 * sizeof(float), "StepCoef is one row of 8 floats (the developer hooks hand it over as float rows)");
 
 // DPM-Solver++ (2M) update of one element (diffusers 0.14.0 DPMSolverMultistepScheduler, midpoint, left-to-right evaluation as
 // there): x0 is this step's data prediction, m1 the previous step's.  Branches on the order: an order-1 step never reads m1 (the
@@ -839,33 +840,55 @@ struct LevelArgs {
   unsigned long long seed;
   unsigned int utt0;
 };
+// A thread's 8 elements of a level batch of [B][L][128] levels (n8 = B * L * 16 threads per level): level lv of the batch, token (b, l),
+// iteration i = i0 + lv, first element c of the token; o: their offset within the level.
+struct LevelIdx {
+  int lv, i, b, l, c;
+  long long o, chunk;    // chunk = B * L * 128
+};
+__device__ __forceinline__ LevelIdx level_idx(long long idx, long long n8, int L, int i0) {
+  const int lv = (int)(idx / n8), i = i0 + lv;
+  const long long r = idx % n8, bl = r / (CFD_LAT / 8);
+  const int c = (int)(r % (CFD_LAT / 8)) * 8;
+  const int l = (int)(bl % L), b = (int)(bl / L);
+  return LevelIdx{lv, i, b, l, c, bl * CFD_LAT + c, n8 * 8};
+}
+// v replicated G times into the split-pair denoiser input, level-major: row ((lv * G + g) * B + b) * L + l
+__device__ __forceinline__ void replicate_sp8(char* sample_sp, const LevelIdx& x, int G, int B, int L, const float v[8]) {
+  for (int g = 0; g < G; ++g)
+    sp_store8(sample_sp + ((((long long)x.lv * G + g) * B + x.b) * L + x.l) * (CFD_LAT * 4), x.c, v);
+}
+
 template <int CFD_KI = 0>
 __global__ void ddpm_level_kernel(const LevelArgs a) {
   const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const long long n8 = (long long)a.B * a.L * (CFD_LAT / 8);
   if (idx >= n8 * a.J) return;
-  const int lv = (int)(idx / n8), i = a.i0 + lv;
-  const long long r = idx % n8, bl = r / (CFD_LAT / 8);
-  const int c = (int)(r % (CFD_LAT / 8)) * 8;
-  const int l = (int)(bl % a.L), b = (int)(bl / a.L);
-  const long long chunk = n8 * 8, o = bl * CFD_LAT + c;
+  const LevelIdx x = level_idx(idx, n8, a.L, a.i0);
+  const int i = x.i;
   float s[8], e[8], v[8];
-  load8(a.src + o, s);
-  if (a.eps) {
-    load8(a.eps + (long long)i * chunk + o, e);
-  } else {
-    const uint32_t g = (uint32_t)((l * CFD_LAT + c) / 4);
-    const float4 z0 = philox_normal4(a.seed, g, (uint32_t)i, a.utt0 + b, 2u), z1 = philox_normal4(a.seed, g + 1, (uint32_t)i, a.utt0 + b, 2u);
+  load8(a.src + x.o, s);
+  if (a.eps) load8(a.eps + (long long)i * x.chunk + x.o, e);
+  else {
+    const uint32_t g = (uint32_t)((x.l * CFD_LAT + x.c) / 4);
+    const float4 z0 = philox_normal4(a.seed, g, (uint32_t)i, a.utt0 + x.b, 2u), z1 = philox_normal4(a.seed, g + 1, (uint32_t)i, a.utt0 + x.b, 2u);
     e[0] = z0.x; e[1] = z0.y; e[2] = z0.z; e[3] = z0.w; e[4] = z1.x; e[5] = z1.y; e[6] = z1.z; e[7] = z1.w;
   }
   const float sa = a.coef[i].sa, sb = a.coef[i].sb;
 #pragma unroll
   for (int q = 0; q < 8; ++q) v[q] = __fadd_rn(__fmul_rn(sa, s[q]), __fmul_rn(sb, e[q]));
-  store8(a.traj + (long long)(a.N - i) * chunk + o, v);
-  for (int g = 0; g < a.G; ++g)
-    sp_store8(a.sample_sp + ((((long long)lv * a.G + g) * a.B + b) * a.L + l) * (CFD_LAT * 4), c, v);
+  store8(a.traj + (long long)(a.N - i) * x.chunk + x.o, v);
+  replicate_sp8(a.sample_sp, x, a.G, a.B, a.L, v);
 }
 
+// The guidance combine of a level batch (filled once on the host: cfd_sample.hip, LevelBatch)
+struct Combine {
+  int Gc;                // chunks of the combine (7 for a weighted run, else the evaluated chunks)
+  float w[8];
+  int pos[8];            // chunk k's rows within a level start at row pos[k] * B
+  int clip;
+  const float* wtab;     // WTAB: [N][B][8]
+};
 // Noise extraction for the J levels of a batch, from the G predictions of every level (level-major rows, as ddpm_level_kernel wrote the
 // input): the guidance combine term for term as cfg_step_kernel's, x0 / clip / mu through step_x0 / ddpm_mu, then
 // z_i = (slot[N - i - 1] - mu) / sigma_i, or exactly 0 where the DDPM row adds no noise.  WTAB: weights from the table row i.  One thread =
@@ -876,11 +899,7 @@ struct ExtractArgs {
   float* noise;          // [N][B][L][128]
   const StepCoef* coef;
   int B, L, G, N, i0, J;
-  int Gc;                // chunks of the combine (7 for a weighted run, else G)
-  float w[8];
-  int pos[8];            // chunk k's rows within a level start at row pos[k] * B
-  int clip;
-  const float* wtab;     // WTAB: [N][B][8]
+  Combine g;
 };
 template <int CFD_KI = 0, bool WTAB = false>
 __global__ void ddpm_extract_kernel(const ExtractArgs a) {
@@ -892,18 +911,18 @@ __global__ void ddpm_extract_kernel(const ExtractArgs a) {
   const StepCoef c = a.coef[i];
   const float* lev = a.eps + (long long)lv * a.G * chunk + o;
   float u[8], acc[8], x[8], nx[8], z[8];
-  load8(lev + (long long)a.pos[0] * chunk, u);
+  load8(lev + (long long)a.g.pos[0] * chunk, u);
   load8(a.traj + (long long)(a.N - i) * chunk + o, x);
   load8(a.traj + (long long)(a.N - i - 1) * chunk + o, nx);
   const float* wrow = nullptr;
-  if constexpr (WTAB) wrow = a.wtab + ((long long)i * a.B + o / ((long long)a.L * CFD_LAT)) * 8;   // (8 elements never straddle two utterances)
+  if constexpr (WTAB) wrow = a.g.wtab + ((long long)i * a.B + o / ((long long)a.L * CFD_LAT)) * 8;   // (8 elements never straddle two utterances)
 #pragma unroll
   for (int q = 0; q < 8; ++q) acc[q] = 0.f;
   // reference association: ((((text + audio) + spk) + apb) + lsnid) + all, each = (g*w)*(e_k - e_0)
-  for (int k = 1; k < a.Gc; ++k) {
+  for (int k = 1; k < a.g.Gc; ++k) {
     float e[8];
-    load8(lev + (long long)a.pos[k] * chunk, e);
-    const float wk = WTAB ? wrow[k] : a.w[k];
+    load8(lev + (long long)a.g.pos[k] * chunk, e);
+    const float wk = WTAB ? wrow[k] : a.g.w[k];
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
       const float term = wk * (e[q] - u[q]);
@@ -912,8 +931,8 @@ __global__ void ddpm_extract_kernel(const ExtractArgs a) {
   }
 #pragma unroll
   for (int q = 0; q < 8; ++q) {
-    const float eps = (a.Gc > 1) ? u[q] + acc[q] : u[q];
-    const float mu = ddpm_mu(c, step_x0(c, a.clip, x[q], eps), x[q]);
+    const float eps = (a.g.Gc > 1) ? u[q] + acc[q] : u[q];
+    const float mu = ddpm_mu(c, step_x0(c, a.g.clip, x[q], eps), x[q]);
     z[q] = c.use_noise != 0.f ? (nx[q] - mu) / c.sigma : 0.f;
   }
   store8(a.noise + (long long)i * chunk + o, z);
@@ -943,14 +962,10 @@ __global__ void picard_load_kernel(const PicardLoadArgs a) {
   const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const long long n8 = (long long)a.B * a.L * (CFD_LAT / 8);
   if (idx >= n8 * a.J) return;
-  const int lv = (int)(idx / n8);
-  const long long r = idx % n8, bl = r / (CFD_LAT / 8);
-  const int c = (int)(r % (CFD_LAT / 8)) * 8;
-  const int l = (int)(bl % a.L), b = (int)(bl / a.L);
+  const LevelIdx x = level_idx(idx, n8, a.L, a.base);
   float v[8];
-  load8(a.ring.at(a.base + lv) + bl * CFD_LAT + c, v);
-  for (int g = 0; g < a.G; ++g)
-    sp_store8(a.sample_sp + ((((long long)lv * a.G + g) * a.B + b) * a.L + l) * (CFD_LAT * 4), c, v);
+  load8(a.ring.at(x.i) + x.o, v);
+  replicate_sp8(a.sample_sp, x, a.G, a.B, a.L, v);
 }
 
 // The DDPM step of every live level of a batch, from the G predictions of every level: the guidance combine term for term as
@@ -963,11 +978,7 @@ struct PicardStepArgs {
   float* s;              // [J][B][L][128]: s of level lv (levels below `off` are not written)
   const StepCoef* coef;
   int B, L, G, base, off, J;
-  int Gc;                // chunks of the combine (7 for a weighted run, else G)
-  float w[8];
-  int pos[8];            // chunk k's rows within a level start at row pos[k] * B
-  int clip;
-  const float* wtab;     // WTAB: [N][B][8]
+  Combine g;
   const float* noise;    // [N][B][L][128] or null -> Philox
   unsigned long long seed;
   unsigned int utt0;
@@ -984,17 +995,17 @@ __global__ void picard_step_kernel(const PicardStepArgs a) {
   const StepCoef c = a.coef[i];
   const float* lev = a.eps + (long long)lv * a.G * chunk + o;
   float u[8], acc[8], x[8], z[8], s[8];
-  load8(lev + (long long)a.pos[0] * chunk, u);
+  load8(lev + (long long)a.g.pos[0] * chunk, u);
   load8(a.ring.at(i) + o, x);
   const float* wrow = nullptr;
-  if constexpr (WTAB) wrow = a.wtab + ((long long)i * a.B + o / per_utt) * 8;   // (8 elements never straddle two utterances)
+  if constexpr (WTAB) wrow = a.g.wtab + ((long long)i * a.B + o / per_utt) * 8;   // (8 elements never straddle two utterances)
 #pragma unroll
   for (int q = 0; q < 8; ++q) acc[q] = z[q] = 0.f;
   // reference association: ((((text + audio) + spk) + apb) + lsnid) + all, each = (g*w)*(e_k - e_0)
-  for (int k = 1; k < a.Gc; ++k) {
+  for (int k = 1; k < a.g.Gc; ++k) {
     float e[8];
-    load8(lev + (long long)a.pos[k] * chunk, e);
-    const float wk = WTAB ? wrow[k] : a.w[k];
+    load8(lev + (long long)a.g.pos[k] * chunk, e);
+    const float wk = WTAB ? wrow[k] : a.g.w[k];
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
       const float term = wk * (e[q] - u[q]);
@@ -1012,8 +1023,8 @@ __global__ void picard_step_kernel(const PicardStepArgs a) {
   }
 #pragma unroll
   for (int q = 0; q < 8; ++q) {
-    const float eps = (a.Gc > 1) ? u[q] + acc[q] : u[q];
-    float prev = ddpm_mu(c, step_x0(c, a.clip, x[q], eps), x[q]);
+    const float eps = (a.g.Gc > 1) ? u[q] + acc[q] : u[q];
+    float prev = ddpm_mu(c, step_x0(c, a.g.clip, x[q], eps), x[q]);
     if (c.use_noise != 0.f) prev = prev + c.sigma * z[q];
     s[q] = prev;
   }

@@ -438,3 +438,52 @@ def test_reperform_motion_ddpm_end_to_end():
 def sampler_run(denoiser, sch, enc, masks, B, n, space):
     from convofusion_amd.sampler import INVERSION_WEIGHTS, SamplingRun
     return SamplingRun(denoiser, sch, enc, masks, B, 16, n, guidance_scale=1.0, modality_weights=INVERSION_WEIGHTS, noise_space=space)
+
+
+# levels_per_batch 2 against 3 at the shape of test_identity_row_map_equals_none (rel. L2 of the noise rows): 4 x the figure measured on
+# an MI355X on the commit before the three row-map sites shared one helper.  Two batch compositions may re-associate the forward's sums
+# (4.3e-7 at the golden's shape, test_noise_matches_reference); at B = 2, L = 2, N = 4 that commit's two compositions give the same bits:
+# the figure is 0.0, and so is the bound.
+PARENT_LPB_2_VS_3 = 0.0
+LPB_BOUND = 4 * PARENT_LPB_2_VS_3
+
+
+def test_identity_row_map_equals_none():
+    """Memories with U = 7 * B and no row_map against the same memories with an explicit identity row_map, through a pruned weighted level
+    batch (the audio column 0 throughout: 6 of the 7 chunks are evaluated) at the level batches' smallest shape, B = 2, L = 2, N = 4:
+    cfd_ddpm_invert with levels_per_batch 2 and 3 (N % J != 0: the last batch overlaps the one before) and cfd_sample_parallel at tolerance
+    0 agree bit for bit between the two forms.  levels_per_batch 2 against 3: the trajectory bit for bit, the noise rows within LPB_BOUND
+    (measured on an MI355X: 0.0 on the commit before, 0.0 on this one)."""
+    import torch
+    from convofusion_amd.sampler import invert_ddpm, sample_parallel
+    from tests.gpu_helpers import hip_denoiser, to_dev
+    B, L, N = 2, 2, 4
+    m = hip_denoiser(1234, 1.0)
+    cb = inputs.make_cfg_batch(seed=5, B=B, L=L, S=(6, 20, 6, 8, 1), pad_tail=(2, 0, 1, 0, 0))
+    mems, masks = [to_dev(x) for x in cb["memories"]], {k: to_dev(v) for k, v in cb["masks"].items()}
+    assert all(int(x.shape[0]) == 7 * B for x in mems)
+    ident = [torch.arange(7 * B, dtype=torch.int32, device="cuda") for _ in mems]
+    w = dict(text=1.0, audio=0.0, spk=0.5, apb=1.5, lsnid=1.0, all=0.25)
+    src = to_dev((0.8 * philox_ref.normal_tensor(11, 0, range(B), 2, L)).astype(np.float32))
+    forms = (dict(dedup=False), dict(row_maps=ident))
+    noise_of = {}
+    for J in (2, 3):
+        got = []
+        for form in forms:
+            got.append(invert_ddpm(m, _sched(), mems, masks, source_latents=src, num_inference_steps=N, guidance_scale=2.0,
+                                   modality_weights=w, seed=3, levels_per_batch=J, **form))
+            assert invert_ddpm.last == dict(chunks_evaluated=6, levels_per_batch=J)
+        assert torch.equal(got[0][0], got[1][0]) and torch.equal(got[0][1], got[1][1]), J
+        assert bool(torch.isfinite(got[0][1]).all()) and bool(got[0][1][:N - 1].any())
+        noise_of[J] = got[0]
+    assert torch.equal(noise_of[2][0], noise_of[3][0])
+    e = rel_l2(noise_of[3][1].cpu().numpy(), noise_of[2][1].cpu().numpy())
+    print(f"levels_per_batch 3 vs 2, noise rows: {e:.3e} (bound {LPB_BOUND:.3e})")
+    lat = []
+    for form in forms:
+        x, stats = sample_parallel(m, _sched(), mems, masks, B=B, L=L, num_inference_steps=N, tolerance=0.0, guidance_scale=2.0,
+                                   modality_weights=w, seed=3, levels_per_batch=2, **form)
+        assert stats.chunks_evaluated == 6 and stats.levels_per_batch == 2
+        lat.append(x)
+    assert torch.equal(lat[0], lat[1]) and bool(torch.isfinite(lat[0]).all())
+    assert e <= LPB_BOUND, (e, LPB_BOUND)

@@ -26,6 +26,7 @@ SYMBOLS = [
     "cfd_sample_census", "cfd_dpmsolver_step", "cfd_test_step_coefficients", "cfd_test_gemm_epi",
     "cfd_vae_encode", "cfd_sample_begin_weighted", "cfd_sample_begin_edit", "cfd_sample_begin_invert", "cfd_sample_begin_anchored",
     "cfd_sample_begin_tied", "cfd_ddpm_invert", "cfd_sample_begin_replay", "cfd_sample_parallel", "cfd_test_picard_stride",
+    "cfd_test_picard_sweep",
 ]
 
 
@@ -137,6 +138,20 @@ class TestEpiArgs(C.Structure):
                 ("x", C.c_void_p), ("out", C.c_void_p), ("out2", C.c_void_p), ("stat", C.c_void_p), ("tile_cfg_used", C.c_int)]
 
 
+# cfd_test_picard_args.stages (include/cfdenoise_dev.h)
+PICARD_FILL, PICARD_LOAD, PICARD_STEP, PICARD_SCAN = 1, 2, 4, 8
+
+
+class TestPicardArgs(C.Structure):
+    """cfd_test_picard_args: the kernels of a cfd_sample_parallel sweep around the forward, on the caller's predictions
+    (cfd_test_picard_sweep)."""
+    _fields_ = [("stages", C.c_int), ("B", C.c_int), ("L", C.c_int), ("G", C.c_int), ("N", C.c_int), ("slots", C.c_int), ("base", C.c_int),
+                ("off", C.c_int), ("J", C.c_int), ("ring", C.c_void_p), ("fill_src", C.c_int), ("fill_lo", C.c_int), ("fill_hi", C.c_int),
+                ("sample_sp", C.c_void_p), ("eps", C.c_void_p), ("coef", C.c_void_p), ("Gc", C.c_int), ("pos", C.c_int * 8),
+                ("w", C.c_float * 8), ("clip", C.c_int), ("wtab", C.c_void_p), ("noise", C.c_void_p), ("seed", C.c_uint64),
+                ("first_utterance", C.c_uint32), ("s", C.c_void_p), ("err", C.c_void_p)]
+
+
 _lib = None
 
 
@@ -224,6 +239,7 @@ def load():
     lib.cfd_test_step_coefficients.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_int,
                                                C.POINTER(C.c_float)]
     lib.cfd_test_picard_stride.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_int]
+    lib.cfd_test_picard_sweep.argtypes = [C.c_void_p, C.POINTER(TestPicardArgs), C.c_void_p]
     lib.cfd_add_noise.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_size_t, C.c_void_p]
     lib.cfd_philox_normal.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint32,

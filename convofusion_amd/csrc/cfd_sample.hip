@@ -1230,6 +1230,77 @@ extern "C" int cfd_test_picard_stride(const float* err, int B, int p, int i0, co
   return picard_stride(err, B, p, i0, reinterpret_cast<const StepCoef*>(coef), tolerance, L);
 }
 
+// ---- developer hook: the kernels of a sweep around the forward, on the caller's predictions (include/cfdenoise_dev.h) ---------------
+// The instances, grids and blocks of cfd_sample_parallel's `fill` and `sweep` above; the partials start as NaN, so that a partial the
+// scan did not write shows in err.
+extern "C" int cfd_test_picard_sweep(cfd_handle c, const cfd_test_picard_args* t, void* stream) {
+  if (!c || !t) return fail(CFD_E_ARG, "null argument");
+  const int B = t->B, L = t->L, G = t->G, N = t->N, J = t->J, base = t->base, off = t->off;
+  const bool do_fill = t->stages & CFD_PICARD_FILL, do_load = t->stages & CFD_PICARD_LOAD, do_step = t->stages & CFD_PICARD_STEP,
+             do_scan = t->stages & CFD_PICARD_SCAN;
+  if (!t->stages || (t->stages & ~15)) return fail(CFD_E_ARG, "cfd_test_picard_sweep: stages = %d", t->stages);
+  if (!t->ring) return fail(CFD_E_ARG, "cfd_test_picard_sweep: the ring is NULL");
+  if (B < 1 || L < 1 || G < 1 || G > 8 || N < 1 || J < 1) return fail(CFD_E_ARG, "cfd_test_picard_sweep: bad B / L / G / N / J");
+  if (off < 0 || off >= J) return fail(CFD_E_ARG, "cfd_test_picard_sweep: off = %d is not in [0, J = %d)", off, J);
+  if (base < 0 || base + J > N) return fail(CFD_E_ARG, "cfd_test_picard_sweep: the batch %d .. %d leaves the %d iterations", base, base + J - 1, N);
+  if (t->slots < J + 1 || t->slots > N + 1) return fail(CFD_E_ARG, "cfd_test_picard_sweep: slots = %d is not in [J + 1, N + 1]", t->slots);
+  const long long chunk = (long long)B * L * CFD_LAT, n8 = chunk / 8;
+  if (n8 * std::max(J, t->slots) > (1ll << 30)) return fail(CFD_E_ARG, "cfd_test_picard_sweep: too many elements for one launch");
+  if (do_fill && (t->fill_src < 0 || t->fill_src > N || t->fill_lo < 0 || t->fill_hi > N || t->fill_hi - t->fill_lo + 1 >= t->slots))
+    return fail(CFD_E_ARG, "cfd_test_picard_sweep: fill %d -> %d .. %d", t->fill_src, t->fill_lo, t->fill_hi);
+  if (do_load && !t->sample_sp) return fail(CFD_E_ARG, "cfd_test_picard_sweep: sample_sp is NULL");
+  if (do_step) {
+    if (!t->eps || !t->coef || !t->s) return fail(CFD_E_ARG, "cfd_test_picard_sweep: eps, coef or s is NULL");
+    if (t->Gc < 1 || t->Gc > 8) return fail(CFD_E_ARG, "cfd_test_picard_sweep: Gc = %d", t->Gc);
+    for (int k = 0; k < t->Gc; ++k)
+      if (t->pos[k] < 0 || t->pos[k] >= G) return fail(CFD_E_ARG, "cfd_test_picard_sweep: pos[%d] = %d is not in [0, G = %d)", k, t->pos[k], G);
+  }
+  if (do_scan && (!t->s || !t->err)) return fail(CFD_E_ARG, "cfd_test_picard_sweep: s or err is NULL");
+  HIPCHK(hipSetDevice(c->cfg.device));
+  hipStream_t st = (hipStream_t)stream;
+  const PicardRing ring{t->ring, t->slots, N, chunk};
+  const int nblk = (L * (CFD_LAT / 4) + 255) / 256;
+  const dim3 block(256), grid_lv((unsigned)((n8 * J + 255) / 256));
+  DBuf coef, part;
+  auto run = [&]() -> int {
+    if (do_fill && t->fill_hi >= t->fill_lo)
+      LAUNCH(CFD_PROF_OTHER, picard_fill_kernel<>, dim3((unsigned)((n8 * (t->fill_hi - t->fill_lo + 1) + 255) / 256)), block, st, ring,
+             t->fill_src, t->fill_lo, t->fill_hi);
+    if (do_load) {
+      const PicardLoadArgs la{ring, (char*)t->sample_sp, B, L, G, base, J};
+      LAUNCH(CFD_PROF_OTHER, picard_load_kernel<>, grid_lv, block, st, la);
+    }
+    if (do_step) {
+      CHK(coef.ensure((size_t)N * sizeof(StepCoef)));
+      HIPCHK(hipMemcpyAsync(coef.p, t->coef, (size_t)N * sizeof(StepCoef), hipMemcpyHostToDevice, st));
+      PicardStepArgs sa;
+      memset(&sa, 0, sizeof(sa));
+      sa.eps = t->eps; sa.ring = ring; sa.s = t->s; sa.coef = coef.as<StepCoef>();
+      sa.B = B; sa.L = L; sa.G = G; sa.base = base; sa.off = off; sa.J = J;
+      sa.g.Gc = t->Gc; sa.g.clip = t->clip; sa.g.wtab = t->wtab;
+      for (int k = 0; k < 8; ++k) { sa.g.w[k] = t->w[k]; sa.g.pos[k] = k < t->Gc ? t->pos[k] : 0; }
+      sa.noise = t->noise; sa.seed = t->seed; sa.utt0 = t->first_utterance;
+      if (t->wtab) LAUNCH(CFD_PROF_OTHER, picard_step_kernel_weighted, grid_lv, block, st, sa);
+      else LAUNCH(CFD_PROF_OTHER, picard_step_kernel<>, grid_lv, block, st, sa);
+    }
+    if (do_scan) {
+      CHK(part.ensure((size_t)J * B * nblk * 4));
+      HIPCHK(hipMemsetAsync(part.p, 0xFF, (size_t)J * B * nblk * 4, st));
+      const PicardScanArgs ca{t->s, ring, part.as<float>(), L, base, off, J};
+      LAUNCH(CFD_PROF_OTHER, picard_scan_kernel<>, dim3((unsigned)nblk, (unsigned)B), block, st, ca);
+      LAUNCH(CFD_PROF_OTHER, picard_err_kernel<>, dim3((unsigned)((J * B + 255) / 256)), block, st, part.as<float>(), t->err, J, B, nblk, J - off);
+    }
+    return CFD_OK;
+  };
+  const int r = run();
+  const hipError_t e = hipStreamSynchronize(st);   // (before the hook's own buffers go)
+  coef.release();
+  part.release();
+  CHK(r);
+  if (e != hipSuccess) return fail(CFD_E_HIP, "cfd_test_picard_sweep: %s", hipGetErrorString(e));
+  return CFD_OK;
+}
+
 // ---- developer hook: the per-iteration coefficient table a sampling run uploads, on the host (no handle, no device) ----------------
 extern "C" int cfd_test_step_coefficients(int kind, const float* ac, int T, int n_inf, const int32_t* timesteps, int N, float eta,
                                           int set_alpha_to_one, float* out) {

@@ -72,6 +72,50 @@ int cfd_test_step_coefficients(int kind, const float* alphas_cumprod, int T, int
  * the window i0 .. i0 + p - 1 inside the N iterations.  Returns the stride in [1, p], or CFD_E_ARG. */
 int cfd_test_picard_stride(const float* err, int B, int p, int i0, const float* coef, int N, float tolerance, int L);
 
+/* Test hook: the kernels of a cfd_sample_parallel sweep around the forward, on the caller's predictions -- the product's own kernel
+ * instances with the grids and blocks the call itself launches them with; no weights, no run.  X(i), the latent entering iteration i,
+ * is slot (N - i) % slots of the ring (slots = N + 1: a caller's trajectory; slots = J + 1: the call's own ring).  The batch is the J
+ * levels base .. base + J - 1, its first `off` levels final already.  The stages of `stages` run in the order of the bits. */
+enum {
+  CFD_PICARD_FILL = 1,     /* X(i) = X(fill_src) for i = fill_lo .. fill_hi (fill_hi < fill_lo: no launch, as the call skips it)        */
+  CFD_PICARD_LOAD = 2,     /* sample_sp row ((lv * G + g) * B + b) * L + l = split(X(base + lv)[b][l]), every g < G                      */
+  CFD_PICARD_STEP = 4,     /* s[lv] = the DDPM step of X(base + lv) under the combined prediction, lv >= off (others not written)       */
+  CFD_PICARD_SCAN = 8      /* X(i0 + k) = fl(s + fl(Xn - X)) for k = 1 .. J - off (i0 = base + off), in place; err[k][b] = the squared
+                              change of X(i0 + k) for 1 <= k <= min(J - off, J - 1), 0 in every other row                               */
+};
+typedef struct {
+  int stages;              /* CFD_PICARD_* bits                                                                                         */
+  int B;
+  int L;
+  int G;                   /* the evaluated chunks of a level                                                                           */
+  int N;
+  int slots;               /* J + 1 <= slots <= N + 1                                                                                   */
+  int base;
+  int off;                 /* 0 <= off < J                                                                                              */
+  int J;                   /* base + J <= N                                                                                             */
+  float* ring;             /* dev f32 [slots][B][L][128], updated in place (FILL, SCAN)                                                 */
+  int fill_src;            /* FILL: iterations in [0, N]                                                                                */
+  int fill_lo;
+  int fill_hi;
+  void* sample_sp;         /* LOAD out: dev SP [J * G * B * L][128], as stored (cfd_test_gemm_epi: per row and 32-column block 64 bytes
+                              of hi, then 64 bytes of lo)                                                                               */
+  const float* eps;        /* STEP: dev f32 [J][G][B][L][128]                                                                           */
+  const float* coef;       /* STEP: HOST f32 [N][8], rows as cfd_test_step_coefficients writes them (uploaded by the hook)              */
+  int Gc;                  /* STEP: the chunks of the combine, 1 <= Gc <= 8                                                             */
+  int pos[8];              /* STEP: chunk k < Gc of the combine is evaluated chunk pos[k] < G                                           */
+  float w[8];              /* STEP: guidance weights (read without a weight table)                                                      */
+  int clip;
+  const float* wtab;       /* STEP: optional dev f32 [N][B][8]: the weighted kernel instance                                            */
+  const float* noise;      /* STEP: dev f32 [N][B][L][128], or NULL: Philox stream 0 with step index i under seed / first_utterance     */
+  unsigned long long seed;
+  unsigned int first_utterance;
+  float* s;                /* STEP out, SCAN in: dev f32 [J][B][L][128]                                                                 */
+  float* err;              /* SCAN out: dev f32 [J][B]                                                                                  */
+} cfd_test_picard_args;
+/* Fails with CFD_E_ARG, before any launch, on a null pointer a requested stage needs or a size outside the constraints above.
+ * Synchronizes before returning. */
+int cfd_test_picard_sweep(cfd_handle h, const cfd_test_picard_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -53,6 +53,19 @@ def stride(err, p, i0, v, tau, n_el):
     return s
 
 
+def stride_ratios(err, p, i0, v, tau, n_el):
+    """The err / bound ratios ``stride`` evaluates (float64 of its float32 operands), every utterance of every window position up to and
+    including the one that stops the window; empty at tau = 0.  A ratio near 1 is a stride that a last-bit difference can change."""
+    err = np.asarray(err, F32)
+    s = stride(err, p, i0, v, tau, n_el)
+    out = []
+    for k in range(1, min(s + 1, p)):
+        bound = F32(F32(tau) * F32(tau)) * v[i0 + k]
+        if bound > 0:
+            out.extend(float(q) for q in (err[k] / F32(n_el)).astype(np.float64) / np.float64(bound))
+    return out
+
+
 def sequential(eps_fn, scheduler, init_latents, step_noise, num_inference_steps):
     """The DDPM loop; returns the trajectory [N + 1, B, L, 128] (slot N - i: the latent entering iteration i; slot 0: the result)."""
     scheduler.set_timesteps(num_inference_steps)
@@ -67,8 +80,12 @@ def sequential(eps_fn, scheduler, init_latents, step_noise, num_inference_steps)
     return traj
 
 
-def sample_parallel(eps_fn, scheduler, init_latents, step_noise, num_inference_steps, levels_per_batch, tolerance, max_sweeps=None):
-    """Returns (latents [B, L, 128], trajectory [N + 1, B, L, 128], strides).  Raises RuntimeError when max_sweeps is reached."""
+def sample_parallel(eps_fn, scheduler, init_latents, step_noise, num_inference_steps, levels_per_batch, tolerance, max_sweeps=None,
+                    ratios=None, drop_carry=False, fill_from_next_window=False):
+    """Returns (latents [B, L, 128], trajectory [N + 1, B, L, 128], strides).  Raises RuntimeError when max_sweeps is reached.
+    ratios: a list that receives ``stride_ratios`` of every sweep.  Planted bugs, for the sensitivity of the tests that compare with this
+    loop: drop_carry -- the scan forgets Xn(j) - X(j) (Xn(j + 1) = s_j); fill_from_next_window -- the entering levels start from
+    X(i1), the next window's first latent, instead of X(i0 + p).  Both keep the sequential chain as the fixed point at tolerance 0."""
     scheduler.set_timesteps(num_inference_steps)
     ts = [int(t) for t in scheduler.timesteps]
     N = len(ts)
@@ -87,15 +104,17 @@ def sample_parallel(eps_fn, scheduler, init_latents, step_noise, num_inference_s
         err = np.zeros((p + 1, x0.shape[0]), F32)
         d = np.zeros_like(x0)
         for k in range(1, p + 1):
-            xn = (s[k - 1] + d).astype(F32)
+            xn = s[k - 1].astype(F32) if drop_carry else (s[k - 1] + d).astype(F32)
             d = (xn - X[i0 + k]).astype(F32)
             err[k] = np.sum((d * d).astype(F32), axis=(1, 2), dtype=F32)
             X[i0 + k] = xn
         st = stride(err, p, i0, v, tolerance, n_el)
         strides.append(st)
+        if ratios is not None:
+            ratios.extend(stride_ratios(err, p, i0, v, tolerance, n_el))
         i1 = i0 + st
         hi = i1 + min(J, N - i1)
-        X[i0 + p + 1:hi + 1] = X[i0 + p]
+        X[i0 + p + 1:hi + 1] = X[i1] if fill_from_next_window else X[i0 + p]
         i0 = i1
     traj = X[::-1].copy()
     return traj[0].copy(), traj, strides

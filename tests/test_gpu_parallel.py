@@ -3,6 +3,7 @@
 Tolerance 0 against the trajectories made with the REFERENCE denoiser (tests/golden/traj_ddpm20_b2, traj_ddpm1000, traj_modality_ddpm20;
 inputs loaded as tests/test_gpu_sampler.py::test_sampler_matches_reference_trajectory loads them), the Philox draws against the tensors
 passed in, run-to-run determinism, the bookkeeping, the refusals, and cfd_ddpm_invert around a parallel call on the same handle.
+Tolerance > 0 against the restated sweeps (tests/parallel_ref) on the HIP forward of single levels, with planted-bug sensitivity.
 Distances and sweep counts are printed.
 
 Measured on an MI355X: tolerance 0 is 1.05e-5 / 9.05e-6 / 6.90e-6 from the goldens' final latents (ddpm20_b2 /
@@ -151,13 +152,81 @@ def test_stats_and_max_sweeps(small):
 
 
 def test_tolerance_on_the_thousand_step_chain():
-    """tau = 0.1 on the ddpm1000 inputs: a finite result; its sweeps and its distance from the golden are printed (no gate on either)."""
+    """tau = 0.1 on the ddpm1000 inputs: a finite result whose strides stay within the batch; its sweeps and its distance from the golden
+    are printed (no gate on either: nobody has measured what quality the tolerance buys)."""
     import torch
     c = _case("ddpm1000")
     lat, st = _par(c, tolerance=0.1)
     d = rel_l2(lat.permute(1, 0, 2).cpu().numpy(), c["g"]["latents"])
     print(f"parallel tau=0.1 ddpm1000: {st}, mean stride {c['N'] / st.sweeps:.2f}, vs golden {d:.2e}")
     assert bool(torch.isfinite(lat).all()) and sum(st.strides) == c["N"] and st.sweeps <= c["N"]
+    assert max(st.strides) <= st.levels_per_batch
+
+
+# B, L, N, J, tau, whether a fill from the wrong slot moves the result of the case (the third is blind to it)
+RESTATED = [(2, 20, 20, 6, 0.3, True), (1, 4, 20, 7, 0.3, True), (3, 16, 10, 4, 0.5, False)]
+GUARD_BAND = (0.95, 1.05)
+ERR_GPU_GATE = 4 * 8.17e-6      # 4 x the largest err_gpu measured on an MI355X (the docstring below has the three)
+
+
+@pytest.mark.parametrize("B,L,N,J,tau,fill_visible", RESTATED)
+def test_tolerance_runs_match_the_restated_sweeps(B, L, N, J, tau, fill_visible):
+    """tau > 0 against tests/parallel_ref.sample_parallel: scan, error sums, stride rule and fill in numpy, the guided prediction of a
+    level from the HIP Denoiser forward on the 7-chunk batch (tested against the reference on its own) under
+    oracle.sampler_ref.cfg_combine.  Asserted: the same strides -- fair because every err / bound ratio the restated rule evaluated lies
+    outside GUARD_BAND (the device's predictions of a level-batched and a single forward differ in the last bits); the final latents and
+    every trajectory slot within ERR_GPU_GATE (relative L2; err_gpu: the largest of them); the restated loop with the scan's carry
+    dropped, and (first two cases) with the entering levels filled from X(i1), further than 10 err_gpu from the correct one, the carry
+    mutant with other strides than the library's; and the call without a trajectory (the private J + 1 ring) bit-identical to the one
+    with it, at L = 20 and L = 4.
+
+    Measured on an MI355X, in the order of RESTATED: err_gpu 5.25e-6 / 5.96e-6 / 8.17e-6 (the gate: 4 x the
+    largest; the tolerance 0 distance from the sequential run is up to 7e-6); the nearest err / bound ratios 1.095 / 1.127 / 0.785;
+    strides 1 2 2 3 3 2 2 2 1 1 1 (twice) and 1 2 2 1 2 1 1; the carry mutant moves the result 1.12e-2 / 9.13e-3 / 5.03e-2 with strides
+    all 1, the fill mutant 4.00e-3 / 6.28e-3."""
+    import torch
+    from oracle.sampler_ref import cfg_combine
+    from oracle.scheduler_ref import DDPMSchedulerRef
+    from tests import parallel_ref as ref
+    from tests.gpu_helpers import hip_denoiser, to_dev
+    seed = 11
+    cb = inputs.make_cfg_batch(seed=seed, B=B, L=L, S=(6, 20, 12, 8, 1), pad_tail=(2, 0, 3, 0, 0))
+    init = philox_ref.normal_tensor(seed, 0, range(B), 1, L)
+    noise = np.stack([philox_ref.normal_tensor(seed, i, range(B), 0, L) for i in range(N)])
+    c = dict(B=B, L=L, N=N, mems=[to_dev(x) for x in cb["memories"]], masks={k: to_dev(v) for k, v in cb["masks"].items()}, init=to_dev(init),
+             noise=to_dev(noise), weights=None)
+    m = hip_denoiser(1234, 1.0)
+
+    def eps_fn(x, i, t):
+        with torch.no_grad():
+            out = m(to_dev(np.concatenate([x] * 7, axis=0)), torch.tensor(int(t)), c["mems"], mem_mask_dict=c["masks"])[0]
+        return cfg_combine(out.cpu().numpy(), 7.5)
+
+    ratios = []
+    want_lat, want_traj, want_strides = ref.sample_parallel(eps_fn, DDPMSchedulerRef(), init, noise, N, J, tau, ratios=ratios)
+    lat, traj, stats = _par(c, tolerance=tau, levels_per_batch=J, trajectory=True)
+    ratios = np.array(ratios)
+    nearest = float(ratios[np.argmin(np.abs(np.log(np.maximum(ratios, 1e-300))))])
+    slots = [rel_l2(traj[k].cpu().numpy(), want_traj[k]) for k in range(N + 1)]
+    err_gpu = max(slots + [rel_l2(lat.cpu().numpy(), want_lat)])
+    mutants = {"carry": ref.sample_parallel(eps_fn, DDPMSchedulerRef(), init, noise, N, J, tau, drop_carry=True)}
+    if fill_visible:
+        mutants["fill"] = ref.sample_parallel(eps_fn, DDPMSchedulerRef(), init, noise, N, J, tau, fill_from_next_window=True)
+    moved = {k: rel_l2(v[0], want_lat) for k, v in mutants.items()}
+    print(f"\nparallel tau={tau} B={B} L={L} N={N} J={J}: strides {stats.strides} (restated {want_strides}), nearest err/bound ratio "
+          f"{nearest:.3f}, err_gpu {err_gpu:.2e} (final {rel_l2(lat.cpu().numpy(), want_lat):.2e}), mutants moved "
+          + ", ".join(f"{k} {v:.2e} strides {mutants[k][2]}" for k, v in moved.items()))
+    assert stats.levels_per_batch == J and stats.chunks_evaluated == 6
+    assert not ((ratios >= GUARD_BAND[0]) & (ratios <= GUARD_BAND[1])).any(), sorted(ratios, key=lambda q: abs(np.log(max(q, 1e-300))))[:4]
+    assert stats.strides == want_strides
+    assert max(want_strides) > 1 and torch.equal(traj[0], lat) and torch.equal(traj[N], c["init"])
+    assert err_gpu <= ERR_GPU_GATE, (err_gpu, slots)
+    for k, v in moved.items():
+        assert v > 10 * err_gpu, (k, v, err_gpu)
+    assert mutants["carry"][2] != stats.strides
+    if L in (20, 4):
+        lat2, stats2 = _par(c, tolerance=tau, levels_per_batch=J)
+        assert torch.equal(lat2, lat) and stats2.strides == stats.strides
 
 
 def _raw(c):

@@ -184,7 +184,17 @@ def test_header_entries_and_struct_layout():
     assert C.sizeof(P) == 56 and (P.weights.offset, P.prune.offset, P.tolerance.offset, P.levels_per_batch.offset) == (0, 8, 12, 16)
     assert (P.workspace_bytes.offset, P.max_sweeps.offset, P.latents.offset, P.trajectory.offset) == (24, 32, 40, 48)
     assert C.sizeof(S) == 32 and (S.sweeps.offset, S.strides.offset, S.strides_capacity.offset) == (8, 16, 24)
+    # the sweep-kernel hook: one declaration per field in the header, in the binding's order; enum values; LP64 offsets
+    dev = open(HEADER_DEV).read()
+    T = _lib.TestPicardArgs
+    assert "cfd_test_picard_sweep" in _lib.SYMBOLS and re.search(r"\bint cfd_test_picard_sweep\(cfd_handle h, const cfd_test_picard_args\* args,", dev)
+    assert _struct_fields(dev, "cfd_test_picard_args") == [f for f, _ in T._fields_]
+    for name, val in (("FILL", 1), ("LOAD", 2), ("STEP", 4), ("SCAN", 8)):
+        assert re.search(r"\bCFD_PICARD_%s = %d\b" % (name, val), dev) and getattr(_lib, "PICARD_" + name) == val
+    assert [getattr(T, f).offset for f, _ in T._fields_] == [0, 4, 8, 12, 16, 20, 24, 28, 32, 40, 48, 52, 56, 64, 72, 80, 88, 92, 124, 156, 160,
+                                                            168, 176, 184, 192, 200] and C.sizeof(T) == 208
+    assert (T.pos.size, T.w.size, T.seed.size, T.first_utterance.size) == (32, 32, 8, 4)
     blob = open(_lib.LIB_PATH, "rb").read()      # the built library exports them, with the kernels of a sweep
-    for name in (b"cfd_sample_parallel", b"cfd_test_picard_stride", b"picard_load_kernel", b"picard_step_kernel", b"picard_scan_kernel",
+    for name in (b"cfd_sample_parallel", b"cfd_test_picard_stride", b"cfd_test_picard_sweep", b"picard_load_kernel", b"picard_step_kernel", b"picard_scan_kernel",
                  b"picard_err_kernel", b"picard_fill_kernel"):
         assert name in blob, name

@@ -26,7 +26,7 @@ SYMBOLS = [
     "cfd_sample_census", "cfd_dpmsolver_step", "cfd_test_step_coefficients", "cfd_test_gemm_epi",
     "cfd_vae_encode", "cfd_sample_begin_weighted", "cfd_sample_begin_edit", "cfd_sample_begin_invert", "cfd_sample_begin_anchored",
     "cfd_sample_begin_tied", "cfd_ddpm_invert", "cfd_sample_begin_replay", "cfd_sample_parallel", "cfd_test_picard_stride",
-    "cfd_test_picard_sweep",
+    "cfd_test_picard_sweep", "cfd_debug_weg_stop", "cfd_debug_weg_fill",
 ]
 
 
@@ -274,6 +274,8 @@ def load():
     lib.cfd_dyadic_steps.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(DyadicProj), C.c_int]
     lib.cfd_debug_stop_stage.argtypes = [C.c_void_p, C.c_int]
     lib.cfd_debug_read.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t]
+    lib.cfd_debug_weg_stop.argtypes = [C.c_void_p, C.c_int]
+    lib.cfd_debug_weg_fill.argtypes = [C.c_void_p, C.c_float]
     for name in SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("cfd_last_error", "cfd_destroy", "cfd_source_hash"):

@@ -9,6 +9,56 @@ extern "C" int cfd_debug_stop_stage(cfd_handle c, int stage) {
   return CFD_OK;
 }
 
+extern "C" int cfd_debug_weg_stop(cfd_handle c, int stop) {
+  if (!c) return fail(CFD_E_ARG, "null handle");
+  if (stop != 0) {
+    if (!c->rt_on || !c->weg_rt_on) return fail(CFD_E_STATE, "cfd_debug_weg_stop: this handle does not evaluate on the row-tile path");
+    const int l = stop / 16, k = stop % 16;
+    const bool ok = stop > 0 && ((l < c->nl && k >= 1 && k <= 9 && !(l == c->nl - 1 && k < 5)) || stop == 10);
+    if (!ok) return fail(CFD_E_ARG, "cfd_debug_weg_stop: %d names no launch of the reverse sweep (16 l + k, k = 1 .. 9; the top layer has no B1 .. B4; 10 = the embedding)", stop);
+  }
+  c->wrt.stop = stop;
+  return CFD_OK;
+}
+
+// the buffers of the row-tile WEG evaluation's arena (include/cfdenoise_dev.h: cfd_debug_weg_stop)
+static int weg_debug_buffer(Ctx* c, const char* what, float** p, size_t* n) {
+  WegRtState& s = c->wrt;
+  if (s.sig.empty() || !s.B) return fail(CFD_E_STATE, "'%s': no row-tile WEG evaluation has run on this handle", what);
+  const size_t M = (size_t)s.B * s.L;
+  int l = -1, k = -1;
+  if (!strcmp(what, "weg.g")) {
+    if (s.stop_gi < 0) return fail(CFD_E_STATE, "weg.g: the sweep has not written a running gradient yet");
+    *p = s.G[s.stop_gi]; *n = M * CFD_D;
+  } else if (!strcmp(what, "weg.g0") || !strcmp(what, "weg.g1") || !strcmp(what, "weg.g2")) { *p = s.G[what[5] - '0']; *n = M * CFD_D; }
+  else if (!strcmp(what, "weg.dh")) { *p = s.dh; *n = M * CFD_FF; }
+  else if (!strcmp(what, "weg.dy")) { *p = s.dy; *n = M * CFD_D; }
+  else if (!strcmp(what, "weg.dz")) { *p = s.dz; *n = M * CFD_D; }
+  else if (!strcmp(what, "weg.dO")) { *p = s.dO; *n = M * CFD_D; }
+  else if (!strcmp(what, "weg.dqkv")) { *p = s.dqkv; *n = M * 3 * CFD_D; }
+  else if (!strcmp(what, "weg.dP")) { *p = s.dP; *n = M * (size_t)s.Sp_tot; }
+  else if (!strcmp(what, "weg.att")) { *p = s.att; *n = M * (size_t)c->nl * s.St; }
+  else if (!strcmp(what, "weg.d_att")) { *p = s.d_att; *n = M * (size_t)c->nl * s.St; }
+  else if (sscanf(what, "weg.x.%d.%d", &l, &k) == 2 && l >= 0 && l <= c->nl && k >= 0 && k < 5) { *p = s.sv.x[l][k]; *n = M * CFD_D; }
+  else return fail(CFD_E_ARG, "unknown buffer '%s'", what);
+  return CFD_OK;
+}
+
+extern "C" int cfd_debug_weg_fill(cfd_handle c, float value) {
+  if (!c) return fail(CFD_E_ARG, "null handle");
+  HIPCHK(hipSetDevice(c->cfg.device));
+  static const char* const names[] = {"weg.g0", "weg.g1", "weg.g2", "weg.dh", "weg.dy", "weg.dz", "weg.dO", "weg.dqkv", "weg.dP"};
+  HIPCHK(hipDeviceSynchronize());
+  for (const char* nm : names) {
+    float* p = nullptr;
+    size_t n = 0;
+    CHK(weg_debug_buffer(c, nm, &p, &n));
+    std::vector<float> v(n, value);
+    HIPCHK(hipMemcpy(p, v.data(), n * 4, hipMemcpyHostToDevice));
+  }
+  return CFD_OK;
+}
+
 extern "C" int cfd_debug_read(cfd_handle c, const char* what, float* dst_dev, size_t numel) {
   if (!c || !what || !dst_dev) return fail(CFD_E_ARG, "null argument");
   HIPCHK(hipSetDevice(c->cfg.device));
@@ -34,6 +84,21 @@ extern "C" int cfd_debug_read(cfd_handle c, const char* what, float* dst_dev, si
     return CFD_OK;
   }
 #endif
+  if (!strcmp(what, "weg.info")) {   // the last row-tile WEG evaluation: launches, Sp_tot, rt_xbwd_dy_kernel instance (keys), objective kernel (1: weg_focus_kernel), G index
+    if (numel < 5) return fail(CFD_E_ARG, "weg.info needs 5 floats");
+    const float f[5] = {(float)c->wrt.launches, (float)c->wrt.Sp_tot, (float)c->wrt.dy_keys, (float)c->wrt.focus_large, (float)c->wrt.stop_gi};
+    HIPCHK(hipMemcpy(dst_dev, f, sizeof(f), hipMemcpyHostToDevice));
+    return CFD_OK;
+  }
+  if (!strncmp(what, "weg.", 4)) {
+    float* p = nullptr;
+    size_t n = 0;
+    CHK(weg_debug_buffer(c, what, &p, &n));
+    if (numel > n) return fail(CFD_E_ARG, "buffer '%s' holds %zu floats, asked for %zu", what, n, numel);
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(dst_dev, p, numel * 4, hipMemcpyDeviceToDevice));
+    return CFD_OK;
+  }
   const DBuf* b = nullptr;
   if (!strcmp(what, "x")) b = &c->w->x;
   else if (!strcmp(what, "temb")) b = &c->w->temb_tab;

@@ -131,6 +131,11 @@ struct WegRtState {
         *dh = nullptr, *dO = nullptr, *dqkv = nullptr;
   int launches = 0;
   int T = 1;                    // rows of wk[1]'s per-timestep tables: 1 (this evaluation's timestep) or every timestep (cfd_weg_args::reuse_memory_side == 2)
+  // test hook (cfd_debug_weg_stop): leave wegrt::enqueue after launch 16 l + k (k = 1 .. 9: B1 .. B9 of layer l; 16 * 0 + 10: the embedding's
+  // backward); 0 = run everything.  stop_gi: which of G[0..2] held the running gradient when enqueue returned (-1: none written yet)
+  int stop = 0, stop_gi = -1;
+  int B = 0, L = 0, Sp_tot = 0, St = 0;   // the shapes of the last enqueue (cfd_debug_read sizes its buffers by them)
+  int dy_keys = 0, focus_large = 0;       // the rt_xbwd_dy_kernel instance (512 / RT_MAX_KEYS) and the objective kernel (1: weg_focus_kernel) it launched
 };
 
 // One problem's device workspace: everything setup_problem / prepare_static_memside allocate and the launches of a forward touch.

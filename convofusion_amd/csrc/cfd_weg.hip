@@ -96,6 +96,8 @@ extern "C" int cfd_weg_eval(cfd_handle c, const cfd_weg_args* a, float* losses, 
   }
   for (int t = 0; t < n_tok; ++t)
     if (a->tok_idx[t] < 1 || a->tok_idx[t] > a->last - 1) return fail(CFD_E_ARG, "focus index %d is outside the text slice [1, %d)", a->tok_idx[t], a->last);
+  // test hook (cfd_debug_weg_stop): a stop names a launch of the row-tile reverse sweep, so the evaluation must take that path
+  if (c->wrt.stop && !wegrt::eligible(c, a)) return fail(CFD_E_STATE, "cfd_debug_weg_stop is set, but this evaluation is not eligible for the row-tile path");
   HIPCHK(hipSetDevice(c->cfg.device));
   c->hint_now = c->hint_same_mem = false;
   CHK(settle_deferred_census(c));
@@ -195,6 +197,14 @@ extern "C" int cfd_weg_eval(cfd_handle c, const cfd_weg_args* a, float* losses, 
   }
   for (int k = 0; k < 3; ++k) { long long bits = 0; memcpy(&bits, &a->kernel3[k], 4); key.push_back(bits); }
   auto& wg = c->weg_graph[x.reuse ? 1 : 0];
+  if (c->wrt.stop) {                                  // test hook: eager, and neither a use of a graph key nor a change of one
+    CHK(run_eval());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    c->weg_launches = x.launches;
+    c->weg_sig = sig;
+    return CFD_OK;                                    // (losses / max_att / grad are not delivered: the sweep was left early)
+  }
   if (wg.key != key) {
     if (wg.exec) { (void)hipGraphExecDestroy(wg.exec); wg.exec = nullptr; }
     if (wg.graph) { (void)hipGraphDestroy(wg.graph); wg.graph = nullptr; }

@@ -106,10 +106,12 @@ static int enqueue(Ctx* c, hipStream_t st, bool full, const EvalArgs& e) {
   WorkGuard guard(c);
   WegRtState& s = c->wrt;
   s.launches = 0;
+  s.stop_gi = -1;
   Work* w = c->w;
   const Problem& p = w->pb;
   const int nl = c->nl, B = p.Be, L = p.L, tpr = (L + 15) / 16, ntile = B * tpr, St = p.S[2];
   const long long M = p.M;
+  s.B = B; s.L = L; s.Sp_tot = p.Sp_tot; s.St = St;
   if (full) {
     w->tt_key.clear();     // (this workspace's timestep-only tables are rebuilt from w->trows, whatever they held: cfd_problem.hip, build_time_tables)
     w->tt_mem_mask = 0;
@@ -126,6 +128,8 @@ static int enqueue(Ctx* c, hipStream_t st, bool full, const EvalArgs& e) {
   }
   CHK(enqueue_rows_rt(c, st, &s.sv));
   s.launches += 2 + 9 * nl - 3;
+  s.focus_large = !(L * (e.last - 1) <= WEG_SMALL_CELLS && e.nt_max <= WEG_SMALL_TOK && L <= 64);
+  s.dy_keys = p.Sp_tot <= 512 ? 512 : RT_MAX_KEYS;
   if (L * (e.last - 1) <= WEG_SMALL_CELLS && e.nt_max <= WEG_SMALL_TOK && L <= 64)
     hipLaunchKernelGGL(weg_focus_small_kernel<>, dim3((unsigned)B), dim3(256), 0, st, s.att, e.tok_off, e.tok_idx, B, nl, L, St, e.last, e.k3[0], e.k3[1],
                        e.k3[2], e.losses, e.max_att, s.d_att);
@@ -167,6 +171,8 @@ static int enqueue(Ctx* c, hipStream_t st, bool full, const EvalArgs& e) {
   int gi = 0;                 // G[gi] holds the running gradient (valid once have_g)
   bool have_g = false;
   const float* dy1 = nullptr; // gradient at the next layer's norm1 output
+  // test hook (cfd_debug_weg_stop): leave behind launch B<k> of layer l, remembering where the running gradient is
+#define WEG_STOP_AT(k) do { if (s.stop == 16 * l + (k)) { s.stop_gi = have_g || l < nl - 1 ? gi : -1; return CFD_OK; } } while (0)
   for (int l = nl - 1; l >= 0; --l) {
     const LayerW& lw = c->lw[l];
     RtXBwdArgs x5 = xb;
@@ -187,11 +193,13 @@ static int enqueue(Ctx* c, hipStream_t st, bool full, const EvalArgs& e) {
         CHK((bwd_gemm<RT_BPRO_LN, RT_BEPI_GELU, 16>(c, st, a, CFD_FF, ntile)));
         gi = (gi + 1) % 3;
       }
+      WEG_STOP_AT(1);
       {   // B2: linear1
         RtBwdArgs a = base;
         a.K = CFD_FF; a.a = s.dh; a.w = Wraw(l, "linear1.weight"); a.ldw = CFD_D; a.out = s.dy; a.ldo = CFD_D;
         CHK((bwd_gemm<RT_BPRO_ROWS, RT_BEPI_F32, 32>(c, st, a, CFD_D, ntile)));
       }
+      WEG_STOP_AT(2);
       {   // B3: norm3, then time block 2's projection
         RtBwdArgs a = base;
         a.K = CFD_D; a.a = s.dy; a.g = s.G[gi]; a.x = s.sv.x[l][4]; a.gamma = lw.ln3g; a.gout = s.G[(gi + 1) % 3];
@@ -199,6 +207,7 @@ static int enqueue(Ctx* c, hipStream_t st, bool full, const EvalArgs& e) {
         CHK((bwd_gemm<RT_BPRO_LN, RT_BEPI_F32, 16>(c, st, a, CFD_D, ntile)));
         gi = (gi + 1) % 3;
       }
+      WEG_STOP_AT(3);
       {   // B4: time block 2's SiLU / modulation / norm, then the probabilities' gradient
         RtXBwdArgs a = x5;
         a.dz = s.dz; a.g = s.G[gi]; a.x = s.sv.x[l][3]; a.gamma = lw.tb2g; a.beta = lw.tb2b;
@@ -208,6 +217,7 @@ static int enqueue(Ctx* c, hipStream_t st, bool full, const EvalArgs& e) {
         ++s.launches;
         gi = (gi + 1) % 3;
       }
+      WEG_STOP_AT(4);
     }
     {   // B5: softmax backward and the folded keys
       RtXBwdArgs a = x5;
@@ -217,6 +227,7 @@ static int enqueue(Ctx* c, hipStream_t st, bool full, const EvalArgs& e) {
       HIPCHK(hipGetLastError());
       ++s.launches;
     }
+    WEG_STOP_AT(5);
     {   // B6: norm2, then time block 1's projection
       RtBwdArgs a = base;
       a.K = CFD_D; a.a = s.dy; a.g = (l < nl - 1) ? s.G[gi] : nullptr; a.x = s.sv.x[l][2]; a.gamma = lw.ln2g; a.gout = s.G[(gi + 1) % 3];
@@ -225,6 +236,7 @@ static int enqueue(Ctx* c, hipStream_t st, bool full, const EvalArgs& e) {
       gi = (gi + 1) % 3;
       have_g = true;
     }
+    WEG_STOP_AT(6);
     {   // B7: time block 1, then the attention's output projection
       RtBwdArgs a = base;
       a.K = CFD_D; a.a = s.dz; a.g = s.G[gi]; a.x = s.sv.x[l][1]; a.gamma = lw.tb1g; a.beta = lw.tb1b;
@@ -233,24 +245,29 @@ static int enqueue(Ctx* c, hipStream_t st, bool full, const EvalArgs& e) {
       CHK((bwd_gemm<RT_BPRO_TB, RT_BEPI_F32, 16>(c, st, a, CFD_D, ntile)));
       gi = (gi + 1) % 3;
     }
+    WEG_STOP_AT(7);
     {   // B8: attention core
       RtSelfBwdArgs a{s.sv.qk[l], s.sv.vt[l], s.dO, s.dqkv, L, (float)std::sqrt(1.0 / (double)CFD_HD)};
       hipLaunchKernelGGL(rt_selfattn_bwd_kernel<>, dim3(CFD_NHEAD, B), dim3(256), lds_sa, st, a);
       HIPCHK(hipGetLastError());
       ++s.launches;
     }
+    WEG_STOP_AT(8);
     {   // B9: packed in-projection
       RtBwdArgs a = base;
       a.K = 3 * CFD_D; a.a = s.dqkv; a.w = Wraw(l, "self_attn.in_proj_weight"); a.ldw = CFD_D; a.out = s.dy; a.ldo = CFD_D;
       CHK((bwd_gemm<RT_BPRO_ROWS, RT_BEPI_F32, 48>(c, st, a, CFD_D, ntile)));
       dy1 = s.dy;
     }
+    WEG_STOP_AT(9);
   }
+#undef WEG_STOP_AT
   {   // through layer 0's norm1 and the latent embedding
     RtBwdArgs a = base;
     a.K = CFD_D; a.a = dy1; a.g = s.G[gi]; a.x = s.sv.x[0][0]; a.gamma = c->lw[0].ln1g; a.gout = s.G[(gi + 1) % 3];
     a.w = rawp(c, "latent_embd.weight"); a.ldw = CFD_LAT; a.out = e.grad; a.ldo = CFD_LAT;
     CHK((bwd_gemm<RT_BPRO_LN, RT_BEPI_F32, 16>(c, st, a, CFD_LAT, ntile)));
+    s.stop_gi = (gi + 1) % 3;   // the gradient at the embedding's output
   }
   return CFD_OK;
 }

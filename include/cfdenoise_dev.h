@@ -61,6 +61,43 @@ int cfd_debug_stop_stage(cfd_handle h, int stage);
 /* Micro-benchmark: average ms of `iters` launches of the [J x K] x [512 x K]^T residual GEMM (I must be 512). */
 int cfd_bench_gemm(cfd_handle h, int I, int J, int K, int tile_cfg, int iters, float* ms_out);
 int cfd_debug_read(cfd_handle h, const char* what, float* dst_dev, size_t numel);
+
+/* Test hook: stop the reverse sweep of a row-tile cfd_weg_eval (csrc/weg_rt.hpp, csrc/rowtile_bwd.hpp) behind one launch.
+ * stop = 0: off.  stop = 16 l + k, k = 1 .. 9: behind launch B<k> of layer l (the top layer has no B1 .. B4); stop = 10: behind the
+ * embedding's backward, the last launch.  Anything else: CFD_E_ARG.  CFD_E_STATE on a handle that has the row-tile evaluation off.
+ * With a stop set, cfd_weg_eval
+ *   - fails with CFD_E_STATE before any launch where its arguments are not eligible for the row-tile path;
+ *   - enqueues its launches eagerly -- no capture, no replay, and the call does not count as a use of its graph key -- leaves the
+ *     sweep behind the named launch, synchronizes, and delivers neither losses, max_att, grad nor *loss_host;
+ *   - remembers which of its three rotating buffers holds the running gradient ("weg.g").
+ * With stop = 0 the launch sequence and the graph keys are what they are without the hook.
+ *
+ * cfd_debug_read then reads the buffers of the evaluation's workspace, all float32 with the M = B * L token rows (b, t) -> b * L + t
+ * dense (tiles are ragged in the kernels, not in memory):
+ *   "weg.g"          [M][512]   the running gradient at the residual stream: behind B1 at the layer's output (= the next layer's
+ *                               input), B3 after time block 2, B4 after the cross-attention, B6 after time block 1, B7 after the
+ *                               self-attention, the embedding's backward at the embedding's output; CFD_E_STATE before the top
+ *                               layer's B6 has written the first one.  "weg.g0" .. "weg.g2": the three buffers themselves
+ *   "weg.dh"         [M][1024]  B1: gradient at the FFN pre-activation
+ *   "weg.dy"         [M][512]   B2 / B5 / B9: gradient at the norm3 / norm2 / norm1 output
+ *   "weg.dz"         [M][512]   B3 / B6: gradient at the SiLU output of time block 2 / 1 (the input of its last linear layer)
+ *   "weg.dO"         [M][512]   B7: gradient at the self-attention core's output, before out_proj
+ *   "weg.dqkv"       [M][1536]  B8: dq | dk | dv at the packed in-projection's output (dq at the UNSCALED query), heads side by side
+ *   "weg.dP"         [M][Sp_tot] B4: gradient at the cross-attention probabilities.  Memory j owns the columns off_j .. off_j + Sp_j - 1,
+ *                               Sp_j = S_j rounded up to 32, off_j = Sp_0 + .. + Sp_(j-1), Sp_tot = their sum; in B4's grid that is
+ *                               16-key blocks in memory order.  Folded formulation: per (row, memory) the values differ from the
+ *                               unfolded gradient by one constant (the value bias), which the softmax backward removes.  Columns
+ *                               S_j .. Sp_j - 1 and masked keys hold finite values that B5 multiplies with probability 0
+ *   "weg.x.<l>.<k>"  [M][512]   the saved residual stream: layer l's input (k = 0), after self-attention (1), time block 1 (2),
+ *                               cross-attention (3), time block 2 (4).  The saved forward ends at the last layer's cross-attention:
+ *                               points behind it are not written
+ *   "weg.att" / "weg.d_att" [B][layers][L][S_tlsn]  the listener-text probabilities and the objective's gradient at them
+ *   "weg.info"       [5]        launches of the last evaluation, Sp_tot, the rt_xbwd_dy_kernel instance (512 / 1024 keys), the objective
+ *                               kernel (0: weg_focus_small_kernel, 1: weg_focus_kernel), the index of the buffer behind "weg.g" (-1: none)
+ * cfd_debug_weg_fill sets the gradient buffers (g0 .. g2, dh, dy, dz, dO, dqkv, dP) to `value`, e.g. a NaN: what a stopped sweep has
+ * not written yet must still hold it.  Needs a completed row-tile evaluation (the workspace exists from then on). */
+int cfd_debug_weg_stop(cfd_handle h, int stop);
+int cfd_debug_weg_fill(cfd_handle h, float value);
 /* Test hook (no handle, no device): the per-iteration coefficient rows a sampling run of scheduler `kind` (cfd_sample_args.scheduler)
  * over the HOST timestep table timesteps[0..N) uploads -- out HOST float32 [N][8], per row: sigma_t, alpha_t, c0, cx, sigma, use_noise,
  * order, 1/r0 (csrc/rows.hpp StepCoef; kind 2: c0 = sigma_prev / sigma_t, cx = alpha_prev (exp(-h) - 1)).  alphas_cumprod HOST

@@ -265,14 +265,10 @@ def test_gradient_at_the_synthetic_shape_matches_oracle():
     np.testing.assert_allclose([float(v) for s in mx for v in s], [float(v) for s in mo for v in s], rtol=2e-5)
 
 
-def test_gradient_on_random_small_shapes_matches_oracle():
-    """The row-tile evaluation (cfd_weg_eval's path for small problems) on random shapes inside its eligibility -- batch 1 .. 3, even
-    L <= 32 including ragged tiles, memory lengths with padded tails, several focus tokens -- against the numpy oracle's backward."""
-    from convofusion_amd import weg
-    from tests.gpu_helpers import dev_inputs, hip_denoiser, to_dev
+def _random_small_cases():
+    """Six random shapes inside the row-tile evaluation's eligibility: batch 1 .. 3, even L <= 32 including ragged tiles, memory lengths
+    with padded tails, several focus tokens.  Yields (case, B, L, S, pad, t, inputs, eot, neot, focus)."""
     rng = np.random.Generator(np.random.PCG64(77))
-    sd = state_dict(1234, 1.0)
-    m = hip_denoiser(1234, 1.0)
     for case in range(6):
         B = (1, 2, 1, 3, 1, 2)[case]
         L = int(rng.choice([4, 10, 16, 20, 32]))
@@ -285,6 +281,17 @@ def test_gradient_on_random_small_shapes_matches_oracle():
         neot = B == 1     # (the end-of-text normalisation needs batch 1, like the reference: word_excitation_guidance.py:25)
         top = int(eot.min()) if neot else St - 1
         focus = [sorted(set(int(v) for v in rng.integers(1, max(2, top), size=int(rng.integers(1, 4))))) for b in range(B)]
+        yield case, B, L, S, pad, t, inp, eot, neot, focus
+
+
+def test_gradient_on_random_small_shapes_matches_oracle():
+    """The row-tile evaluation (cfd_weg_eval's path for small problems) on random shapes inside its eligibility -- batch 1 .. 3, even
+    L <= 32 including ragged tiles, memory lengths with padded tails, several focus tokens -- against the numpy oracle's backward."""
+    from convofusion_amd import weg
+    from tests.gpu_helpers import dev_inputs, hip_denoiser, to_dev
+    sd = state_dict(1234, 1.0)
+    m = hip_denoiser(1234, 1.0)
+    for case, B, L, S, pad, t, inp, eot, neot, focus in _random_small_cases():
         lo, _, mo, go = weg_ref.loss_and_grad(sd, inp["sample"], t, inp["memories"], inp["masks"], focus, neot, eot)
         mems, masks = dev_inputs(inp)
         loss, _, mx, grad = weg.loss_and_grad(m, to_dev(inp["sample"]), t, mems, masks, focus, neot, to_dev(eot))
@@ -292,6 +299,148 @@ def test_gradient_on_random_small_shapes_matches_oracle():
         print(f"case {case}: B={B} L={L} S={S} pad={pad} t={t} focus={focus}: loss {float(loss):.6f} (oracle {float(lo):.6f}), grad {e:.2e}")
         assert abs(float(loss) - float(lo)) < 2e-6 and e < 1e-3
         np.testing.assert_allclose([float(v) for s in mx for v in s], [float(v) for s in mo for v in s], rtol=2e-5)
+
+
+# ----------------------------------------------------------------------------- shapes the product path takes other kernels for, against float64
+# The end gradient against tests/weg_bwd_ref.py at float64: (relative L2 over [B][L][128], worst token row over the RMS row norm).
+# 4 x the largest value measured on the MI355X over the cases below, and within the caps of the tap tests (2e-4 / 2e-3:
+# tests/test_gpu_weg_backward.py); figures in profiles/r17_weg_backward_taps.txt.
+F64_GRAD_GATE = (4 * 1.36e-5, 4 * 8.65e-5)      # measured: 1.36e-5 (two tokens per row), 8.65e-5 (21 x 32 rows)
+assert F64_GRAD_GATE[0] <= 2e-4 and F64_GRAD_GATE[1] <= 2e-3
+
+
+def _holes_case():
+    """B = 3, masks with holes on all five memories (the pattern of test_key_padding_masks_with_holes): the first key, isolated keys, a
+    whole 32-key block, one row without masked keys."""
+    B, L, S = 3, 16, (24, 161, 24, 8, 2)
+    inp = inputs.make_plain_batch(seed=909, Be=B, L=L, S=S)
+    rng = np.random.Generator(np.random.PCG64(13))
+    for j, name in enumerate(inputs.MEM_NAMES):
+        mk = rng.random((B, S[j])) < 0.3
+        mk[0, 0] = True
+        if S[j] > 64:
+            mk[1, 32:64] = True
+        mk[2, :] = False
+        mk[:, S[j] - 1] = False
+        inp["masks"][name] = mk
+    return inp, 321, [[1, 5, 22], [2, 9], [3, 17, 20]]
+
+
+def _shape_case(name):
+    """(inputs, timestep, focus, weight memory length) of a product-level case; no end-of-text normalisation (last = S_tlsn - 1)."""
+    if name == "big_keys":                               # 672 padded keys: rt_xbwd_dy_kernel<RT_MAX_KEYS> (and rt_xpv_kernel<RT_MAX_KEYS>)
+        return inputs.make_plain_batch(seed=31, Be=1, L=16, S=(24, 530, 24, 8, 1)), 250, [[3, 9, 22]]
+    if name == "large_focus":                            # 32 x 38 cells > 1024: weg_focus_kernel with the workspace inside the row-tile arena
+        return inputs.make_plain_batch(seed=32, Be=1, L=32, S=(6, 20, 40, 8, 1), pad_tail=(2, 3, 0, 0, 0)), 700, [[1, 17, 30, 38]]
+    if name == "tiles_b21":                              # 672 rows, 42 tiles
+        return inputs.make_plain_batch(seed=33, Be=21, L=32, S=(3, 5, 6, 2, 1)), 450, [[1 + (b + k) % 4 for k in range(1 + b % 3)] for b in range(21)]
+    if name == "tiles_b43":                              # 688 rows, 43 tiles
+        return inputs.make_plain_batch(seed=34, Be=43, L=16, S=(3, 5, 6, 2, 1), pad_tail=(0, 1, 0, 0, 0)), 80, [[1 + b % 4, 4 - b % 3] for b in range(43)]
+    if name == "len2":                                   # the lower length edge
+        return inputs.make_plain_batch(seed=35, Be=2, L=2, S=(6, 20, 12, 8, 1), pad_tail=(2, 0, 0, 0, 0)), 5, [[2, 10], [1]]
+    assert name == "holes"
+    return _holes_case()
+
+
+_f64 = {}
+
+
+def _float64_result(key, inp, t, focus, neot=False, eot=()):
+    from tests import weg_bwd_ref
+    if key not in _f64:
+        _f64[key] = weg_bwd_ref.loss_and_grad_taps(state_dict(1234, 1.0), inp["sample"], t, inp["memories"], inp["masks"], focus, neot, eot)
+    return _f64[key]
+
+
+def _f32_sequence_model():
+    """A model whose handle evaluates on the float32 launch sequence (weg_eval.hpp) whatever the shape: CFD_WEG_ROWTILE is read when the
+    handle is created."""
+    import os
+    import torch
+    from convofusion_amd.denoiser import Denoiser
+    from tests.gpu_helpers import ABL, DENOISER_KW, hip_denoiser
+    if "m" not in _f32_sequence_model.__dict__:
+        os.environ["CFD_WEG_ROWTILE"] = "0"
+        try:
+            m = Denoiser(ablation=ABL, **DENOISER_KW)
+            m.load_state_dict(hip_denoiser(1234, 1.0).state_dict(), strict=True)
+            m = m.cuda().eval()
+            m.engine(torch.device("cuda"))
+        finally:
+            del os.environ["CFD_WEG_ROWTILE"]
+        _f32_sequence_model.m = m
+    return _f32_sequence_model.m
+
+
+def _check_against_float64(label, m, inp, t, focus, r64, neot=False, eot=None, row_tile=True):
+    """One product evaluation against the float64 restatement: losses 2e-6, max_att 2e-5, the gradient at F64_GRAD_GATE in both measures;
+    the text attention exactly 0 in masked columns, the objective's gradient at the maps exactly 0 outside the text slice."""
+    import torch
+    from convofusion_amd import weg
+    from tests import weg_bwd_ref
+    from tests.gpu_helpers import dev_inputs, read_debug, to_dev
+    mems, masks = dev_inputs(inp)
+    eot_dev = to_dev(np.asarray(eot)) if eot is not None else torch.zeros(1, dtype=torch.long)
+    loss, losses, mx, grad = weg.loss_and_grad(m, to_dev(inp["sample"]), t, mems, masks, focus, neot, eot_dev)
+    l64, ls64, mx64, g64, _, att64, datt64 = r64
+    B, L, _ = inp["sample"].shape
+    St = inp["memories"][2].shape[1]
+    g = grad.cpu().numpy()
+    e, er = weg_bwd_ref.tap_errors(g.reshape(B * L, -1), g64.reshape(B * L, -1))
+    info = read_debug(m, "weg.info", (5,))
+    print(f"{label}: B={B} L={L} loss {float(loss):.6f} (float64 {float(l64):.6f}); grad vs float64 rel L2 {e:.2e} worst row {er:.2e}; "
+          f"row-tile launches {int(info[0])}, Sp_tot {int(info[1])}, rt_xbwd_dy_kernel<{int(info[2])}>, objective kernel {'large' if info[3] else 'small'}")
+    assert abs(float(loss) - float(l64)) < 2e-6
+    np.testing.assert_allclose(losses.cpu().numpy(), ls64, atol=2e-6)
+    np.testing.assert_allclose([float(v) for s in mx for v in s], [float(v) for s in mx64 for v in s], rtol=2e-5)
+    assert e <= F64_GRAD_GATE[0] and er <= F64_GRAD_GATE[1]
+    last = int(eot[0]) if neot else St - 1
+    mk = inp["masks"]["tlsn"]
+    if row_tile:
+        assert int(info[1]) == sum((int(x.shape[1]) + 31) // 32 * 32 for x in inp["memories"])
+        att, datt = read_debug(m, "weg.att", (B, 9, L, St)), read_debug(m, "weg.d_att", (B, 9, L, St))
+    else:      # the launch-by-launch form of the float32 sequence: the same kernels, its maps and their gradient in the caller's hands
+        a, _ = weg.forward_saved(m, to_dev(inp["sample"]), t, mems, masks)
+        _, _, _, d = weg.attention_focus_loss(m, a, focus, neot, eot_dev)
+        att, datt = a.cpu().numpy(), d.cpu().numpy()
+    if mk is not None:
+        assert np.all(att[np.broadcast_to(mk[:, None, None, :], att.shape)] == 0)
+    assert np.abs(att - att64).max() < 1e-5
+    assert not datt[..., 0].any() and not datt[..., last:].any()     # (inside the slice the reference's own gradient at a masked column is not 0)
+    assert rel_l2(datt, datt64) < 1e-4
+    return g, info
+
+
+@pytest.mark.parametrize("name", ["big_keys", "large_focus", "tiles_b21", "tiles_b43", "len2", "holes"])
+def test_gradient_at_row_tile_shape_edges_matches_float64(name):
+    """Shapes at which the row-tile evaluation takes a kernel instance or a grid no other WEG case reaches, end to end against float64:
+    more than 512 padded keys, the large objective kernel, 42 and 43 token tiles, two tokens per row, key-padding masks with holes."""
+    from tests.gpu_helpers import hip_denoiser
+    inp, t, focus = _shape_case(name)
+    _, info = _check_against_float64(name, hip_denoiser(1234, 1.0), inp, t, focus, _float64_result(name, inp, t, focus))
+    assert int(info[2]) == (1024 if name == "big_keys" else 512)
+    assert int(info[3]) == (1 if name == "large_focus" else 0)
+
+
+def test_float32_launch_sequence_with_batches_matches_float64_and_the_row_tile_path():
+    """The float32 launch sequence (weg_eval.hpp: every evaluation outside the row-tile path's eligibility) with more than one batch row
+    -- the random shapes with B = 2 and 3 and the masks with holes, on a handle created with CFD_WEG_ROWTILE=0 -- against float64 and
+    against the row-tile path's gradient for the same inputs."""
+    from tests import weg_bwd_ref
+    from tests.gpu_helpers import hip_denoiser
+    m32, mrt = _f32_sequence_model(), hip_denoiser(1234, 1.0)
+    todo = [(f"random{case}", inp, t, focus, neot, eot) for case, B, L, S, pad, t, inp, eot, neot, focus in _random_small_cases() if B > 1]
+    todo.append(("holes",) + _shape_case("holes") + (False, None))
+    for label, inp, t, focus, neot, eot in todo:
+        r64 = _float64_result(label, inp, t, focus, neot, eot if eot is not None else ())
+        g_rt, info = _check_against_float64(label + " row-tile", mrt, inp, t, focus, r64, neot, eot)
+        assert info[0] > 0
+        g_32, info = _check_against_float64(label + " float32 sequence", m32, inp, t, focus, r64, neot, eot, row_tile=False)
+        assert info[0] == 0 and info[1] == 0          # no row-tile evaluation ever ran on this handle
+        B, L, _ = inp["sample"].shape
+        e, er = weg_bwd_ref.tap_errors(g_32.reshape(B * L, -1), g_rt.reshape(B * L, -1))
+        print(f"{label}: float32 sequence vs row-tile rel L2 {e:.2e} worst row {er:.2e}")
+        assert e <= F64_GRAD_GATE[0] and er <= F64_GRAD_GATE[1]
 
 
 def test_eval_rejects_what_the_reference_cannot_run():

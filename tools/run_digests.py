@@ -1,0 +1,127 @@
+"""Developer tool (GPU box): does a change of the host code that opens sampling runs leave every run kind as it was?  Opens each kind at the
+small test shape (B = 2, L = 16, memories S = (6, 20, 6, 8, 1) with pad tails (2, 0, 1, 0, 0), 4 iterations, 6 for DPM-Solver++, fixed
+seeds, the seeded test weights) and prints one line per run: the SHA-256 of the final latents' bytes, of ``read()`` after every iteration
+(``steps``), of the trajectory, the noise and the attention ring where the run has them, and N, first_iteration, chunks_evaluated and the
+non-pointer fields of the run's cfd_sample_args.  The runs are deterministic: the outputs of two trees are compared with ``diff``, and a
+line that differs is a change of behaviour.
+
+Usage (once in each tree):  python tools/run_digests.py > digests.txt
+"""
+import hashlib
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from convofusion_amd import sampler, scheduler  # noqa: E402
+from convofusion_amd.longform import window_ties  # noqa: E402
+from oracle import inputs  # noqa: E402
+from tests.gpu_helpers import SCHED_KW, hip_denoiser, to_dev  # noqa: E402
+
+B, L, S, PAD, N_IT, SEED = 2, 16, (6, 20, 6, 8, 1), (2, 0, 1, 0, 0), 4, 7
+ARG_FIELDS = ("B", "L", "G", "guidance_weight", "scheduler", "num_train_timesteps", "num_inference_steps", "clip_sample", "eta",
+              "set_alpha_to_one", "steps_offset", "preseq_len", "seed", "first_utterance", "skip_zero_weight_chunks", "dynamic_memory_mask",
+              "operand_policy", "census_tau", "num_timesteps")
+YAML = {k: v for k, v in SCHED_KW.items() if k != "clip_sample"}
+
+
+def sha(*tensors):
+    h = hashlib.sha256()
+    for t in tensors:
+        h.update(np.ascontiguousarray(t.detach().cpu().numpy()).tobytes())
+    return h.hexdigest()
+
+
+def args_text(a):
+    vals = {f: getattr(a, f) for f in ARG_FIELDS}
+    vals["guidance_weight"] = [float(v) for v in vals["guidance_weight"]]
+    return " ".join(f"{k}={v!r}" for k, v in vals.items())
+
+
+def line(name, **parts):
+    print(name + ": " + " ".join(f"{k}={v}" for k, v in parts.items()), flush=True)
+
+
+def run_line(name, sch, mems, masks, n=N_IT, **kw):
+    """One SamplingRun, stepped one iteration at a time; returns the closed run and its final latents."""
+    run = sampler.SamplingRun(hip_denoiser(1234, 1.0), sch, mems, masks, B, L, n, seed=SEED, **kw)
+    parts = {}
+    try:
+        h = hashlib.sha256()
+        for _ in range(run.N):
+            run.steps(1)
+            h.update(run.read().cpu().numpy().tobytes())
+        lat = run.read(close=True)
+        parts["final"], parts["steps"] = sha(lat), h.hexdigest()
+    except sampler.CensusTripped as e:
+        lat = None
+        parts["census_tripped"] = e.census["iterations"]
+    finally:
+        run.close()
+    if run.trajectory is not None:
+        parts["trajectory"] = sha(run.trajectory)
+    if run.att_ring is not None:
+        parts["att_ring"] = sha(*run.att_ring)
+    line(name, **parts, N=run.N, first_iteration=run.first_iteration, chunks_evaluated=run.chunks_evaluated, timesteps=run.timesteps,
+         guard=run._guard, args=args_text(run._args))
+    return run, lat
+
+
+def main():
+    cb = inputs.make_cfg_batch(seed=1, B=B, L=L, S=S, pad_tail=PAD)
+    mems, masks = [to_dev(x) for x in cb["memories"]], {k: to_dev(v) for k, v in cb["masks"].items()}
+    m = hip_denoiser(1234, 1.0)
+    g = torch.Generator().manual_seed(11)
+    source = torch.randn((B, L, 128), generator=g).cuda()
+    keep = torch.zeros((B, L), dtype=torch.bool)
+    keep[:, :L // 2] = True
+    keep = keep.cuda()
+    ddpm = lambda: scheduler.DDPMScheduler(variance_type="fixed_small", **SCHED_KW)  # noqa: E731
+    ddim = lambda **k: scheduler.DDIMScheduler(**dict(SCHED_KW, **k))  # noqa: E731
+
+    run_line("ddpm", ddpm(), mems, masks)
+    run_line("ddpm skip_zero_weight_chunks", ddpm(), mems, masks, skip_zero_weight_chunks=True)
+    for prune in (True, False):
+        run_line(f"ddpm modality_weights apb=0 lsnid=0 prune={prune}", ddpm(), mems, masks, modality_weights=dict(apb=0.0, lsnid=0.0),
+                 prune_zero_weight_chunks=prune)
+    run_line("ddim", ddim(), mems, masks)
+    run_line("dpm-solver++", scheduler.DPMSolverMultistepScheduler(**YAML), mems, masks, n=6)
+    run_line("ddpm preseq 4", ddpm(), mems, masks, preseq=source[:, :4].contiguous())
+    run_line("edit keep_mask strength=0.5", ddpm(), mems, masks, source_latents=source, keep_mask=keep, strength=0.5)
+    tie = window_ties(1, B, L).cuda()
+    run_line("tied", ddpm(), mems, masks, tie=tie)
+    tkeep = torch.zeros((B, L), dtype=torch.bool)
+    tkeep[0, :4] = tkeep[1, 12:] = True
+    run_line("tied with edit", ddpm(), mems, masks, tie=tie, source_latents=source, keep_mask=tkeep.cuda())
+
+    inv = scheduler.DDIMInverseScheduler(**SCHED_KW)
+    lat, traj = sampler.invert(m, inv, mems, masks, source_latents=source, num_inference_steps=N_IT, return_trajectory=True)
+    line("invert return_trajectory", final=sha(lat), trajectory=sha(traj))
+    run_line("ddim inverse run trajectory=True", inv, mems, masks, init_latents=source, trajectory=True,
+             modality_weights=sampler.INVERSION_WEIGHTS, guidance_scale=1.0)
+    run_line("anchored over the inversion's trajectory", ddim(clip_sample=False), mems, masks, anchor_trajectory=traj, keep_mask=keep)
+
+    traj, noise = sampler.invert_ddpm(m, ddpm(), mems, masks, source_latents=source, num_inference_steps=N_IT, seed=SEED)
+    line("invert_ddpm", trajectory=sha(traj), noise=sha(noise), last=sampler.invert_ddpm.last)
+    run_line("replay strength=0.5", ddpm(), mems, masks, noise_space=(traj, noise), keep_mask=keep, strength=0.5)
+
+    lat, ptraj, stats = sampler.sample_parallel(m, ddpm(), mems, masks, B=B, L=L, num_inference_steps=N_IT, tolerance=0, levels_per_batch=2,
+                                                seed=SEED, trajectory=True)
+    line("sample_parallel tolerance=0 levels_per_batch=2", final=sha(lat), trajectory=sha(ptraj), sweeps=stats.sweeps, strides=stats.strides,
+         levels_per_batch=stats.levels_per_batch, chunks_evaluated=stats.chunks_evaluated)
+
+    run_line("attention_ring", ddpm(), mems, masks, attention_ring=True)
+    uq = [to_dev(u) for u in cb["unique"]]
+    cm = {k: (v[6 * B:] if v is not None else None) for k, v in masks.items()}      # chunk 6 = full conditioning
+    um = {k: (v[:1] if v is not None else None) for k, v in masks.items()}          # chunk 0 = all dropped
+    u_mems, maps, u_masks = sampler.build_guidance_batch([u[1:] for u in uq], [u[:1] for u in uq], cm, um)
+    run_line("build_guidance_batch row_maps", ddpm(), u_mems, u_masks, dedup=False, row_maps=maps)
+    run_line("dedup=False dynamic_memories=(0,)", ddpm(), [x.clone() for x in mems], masks, dedup=False, dynamic_memories=(0,))
+    run_line("operands=0", ddpm(), mems, masks, operands=0)
+    run_line("operands=auto", ddpm(), mems, masks, operands="auto")
+
+
+if __name__ == "__main__":
+    main()

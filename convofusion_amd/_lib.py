@@ -26,8 +26,11 @@ SYMBOLS = [
     "cfd_sample_census", "cfd_dpmsolver_step", "cfd_test_step_coefficients", "cfd_test_gemm_epi",
     "cfd_vae_encode", "cfd_sample_begin_weighted", "cfd_sample_begin_edit", "cfd_sample_begin_invert", "cfd_sample_begin_anchored",
     "cfd_sample_begin_tied", "cfd_ddpm_invert", "cfd_sample_begin_replay", "cfd_sample_parallel", "cfd_test_picard_stride",
-    "cfd_test_picard_sweep", "cfd_debug_weg_stop", "cfd_debug_weg_fill",
+    "cfd_test_picard_sweep", "cfd_debug_weg_stop", "cfd_debug_weg_fill", "cfd_scheduler_step_pred", "cfd_dpmsolver_step_pred",
 ]
+
+# cfd_sample_args.prediction_type / the _pred entry points, by the schedulers' config string
+PREDICTION_TYPES = {"epsilon": 0, "sample": 1}
 
 
 class CfdError(RuntimeError):
@@ -64,7 +67,8 @@ class SampleArgs(C.Structure):
                 ("step_noise", C.c_void_p), ("seed", C.c_uint64), ("first_utterance", C.c_uint32),
                 ("preseq", C.c_void_p), ("preseq_len", C.c_int), ("mem", Memory * NUM_MEM),
                 ("skip_zero_weight_chunks", C.c_int), ("dynamic_memory_mask", C.c_int),
-                ("timesteps", C.c_void_p), ("num_timesteps", C.c_int), ("att_ring", C.c_void_p * NUM_MEM),
+                ("timesteps", C.c_void_p), ("num_timesteps", C.c_int), ("prediction_type", C.c_int),   # (in the padding in front of att_ring)
+                ("att_ring", C.c_void_p * NUM_MEM),
                 ("operand_policy", C.c_int), ("census_tau", C.c_float)]
 
 
@@ -236,6 +240,10 @@ def load():
                                        C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
     lib.cfd_dpmsolver_step.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.cfd_scheduler_step_pred.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    lib.cfd_dpmsolver_step_pred.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     lib.cfd_test_step_coefficients.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_int,
                                                C.POINTER(C.c_float)]
     lib.cfd_test_picard_stride.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_int]

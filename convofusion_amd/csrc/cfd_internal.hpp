@@ -444,26 +444,26 @@ __global__ void fill_f32_kernel(float* p, long long n, float v) {
 }
 
 
-template <int CFD_KI = 0>
+// PRED: what `eps` holds (cfd_scheduler_step_pred: 0 the noise, 1 the clean latent -- rows.hpp, step_x0_of / step_eps_of)
+template <int CFD_KI = 0, int PRED = 0>
 __global__ void sched_step_kernel(const float* eps, const float* noise, float* x, size_t n, StepCoef c, int kind, int clip, float* x0_out) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const float e = eps[i], xv = x[i];
-  float x0 = (xv - c.sb * e) / c.sa;
-  if (clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+  const float x0 = step_x0_of<PRED>(c, clip, xv, e);
   if (x0_out) x0_out[i] = x0;
-  float prev = (kind == 0) ? c.c0 * x0 + c.cx * xv : c.c0 * x0 + c.cx * e;
+  float prev = (kind == 0) ? c.c0 * x0 + c.cx * xv : c.c0 * x0 + c.cx * step_eps_of<PRED>(c, xv, e);
   if (c.use_noise != 0.f) prev = prev + c.sigma * noise[i];
   x[i] = prev;
 }
 // DPM-Solver++ (2M) step on its own (cfd_dpmsolver_step): x0_out = this step's data prediction (the caller's history for the next step),
-// x = the update; m_prev (the previous step's x0) is read by order-2 steps only
-template <int CFD_KI = 0>
+// x = the update; m_prev (the previous step's x0) is read by order-2 steps only.  PRED 1: the model output is the data prediction.
+template <int CFD_KI = 0, int PRED = 0>
 __global__ void dpmpp_step_kernel(const float* eps, const float* m_prev, float* x, float* x0_out, size_t n, StepCoef c) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const float xv = x[i];
-  const float x0 = (xv - c.sb * eps[i]) / c.sa;
+  const float x0 = step_x0_of<PRED>(c, 0, xv, eps[i]);   // (no clip_sample in this scheduler)
   const float m1 = c.order == 2.0f ? m_prev[i] : 0.f;
   x0_out[i] = x0;
   x[i] = dpmpp_prev(c, xv, x0, m1);

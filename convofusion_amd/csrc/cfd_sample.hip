@@ -104,6 +104,9 @@ static int step_coefficients(int kind, const float* ac, int T, int n_inf, const 
 static void (*const cfg_step_kernel_weighted)(const CfgStepArgsW) = cfg_step_kernel<0, true>;   // (one macro argument for LAUNCH)
 static void (*const cfg_step_kernel_traj)(const CfgStepArgsT<CfgStepArgs>) = cfg_step_kernel<0, false, true>;
 static void (*const cfg_step_kernel_weighted_traj)(const CfgStepArgsT<CfgStepArgsW>) = cfg_step_kernel<0, true, true>;
+// prediction_type 1 ("sample"): the combine is x0.  No trajectory instance: inversion refuses the type (check_run_args)
+static void (*const cfg_step_kernel_x0)(const CfgStepArgs) = cfg_step_kernel<0, false, false, 1>;
+static void (*const cfg_step_kernel_weighted_x0)(const CfgStepArgsW) = cfg_step_kernel<0, true, false, 1>;
 
 // The instances of begin_step_kernel / inpaint_now_kernel that take the argument struct Args (rows.hpp: BeginArgsOf, the other way round)
 template <class Args>
@@ -200,7 +203,9 @@ static int enqueue_loop_iteration(Ctx* c, hipStream_t st) {
   const long long n4 = (long long)s.B * s.L * CFD_LAT / 4;
   const dim3 grid((unsigned)std::min<long long>((n4 + 255) / 256, 256)), block(256);
   // (m.traj: an inversion run recording its trajectory: the step also stores into slot *d_step + 1)
-  if (m.weighted && m.traj) LAUNCH(CFD_PROF_OTHER, cfg_step_kernel_weighted_traj, grid, block, st, with_traj(cw, m.traj));
+  if (s.prediction_type == 1 && m.weighted) LAUNCH(CFD_PROF_OTHER, cfg_step_kernel_weighted_x0, grid, block, st, cw);
+  else if (s.prediction_type == 1) LAUNCH(CFD_PROF_OTHER, cfg_step_kernel_x0, grid, block, st, ca);
+  else if (m.weighted && m.traj) LAUNCH(CFD_PROF_OTHER, cfg_step_kernel_weighted_traj, grid, block, st, with_traj(cw, m.traj));
   else if (m.weighted) LAUNCH(CFD_PROF_OTHER, cfg_step_kernel_weighted, grid, block, st, cw);
   else if (m.traj) LAUNCH(CFD_PROF_OTHER, cfg_step_kernel_traj, grid, block, st, with_traj(ca, m.traj));
   else LAUNCH(CFD_PROF_OTHER, cfg_step_kernel<>, grid, block, st, ca);
@@ -361,6 +366,13 @@ static int check_run_args(const BeginState& r) {
     if (s.preseq) return fail(CFD_E_ARG, "DDIM inversion takes no preseq (the rollout's prefix in-painting)");
     if (s.dynamic_memory_mask) return fail(CFD_E_ARG, "DDIM inversion takes no dynamic memories (dynamic_memory_mask = %d)", s.dynamic_memory_mask);
     if (r.x.edit) return fail(CFD_E_ARG, "DDIM inversion does not go together with an edit (cfd_sample_begin_edit)");
+  }
+  if (s.prediction_type != 0 && s.prediction_type != 1)
+    return fail(CFD_E_ARG, "%s: prediction_type = %d is not 0 (epsilon) or 1 (sample)", r.x.opener, s.prediction_type);
+  if (s.prediction_type == 1) {   // no trajectory to check these against (as DPM-Solver++'s refusals)
+    if (s.scheduler == 3) return fail(CFD_E_ARG, "%s: DDIM inversion needs prediction_type = 0 (epsilon): inverting an x0-predicting model is not implemented", r.x.opener);
+    if (r.x.anchor) return fail(CFD_E_ARG, "%s: an anchored run needs prediction_type = 0 (epsilon): its trajectory is an epsilon inversion's", r.x.opener);
+    if (r.x.replay) return fail(CFD_E_ARG, "%s: the replay of a noise space needs prediction_type = 0 (epsilon): cfd_ddpm_invert solves it for an epsilon model", r.x.opener);
   }
   if (s.scheduler == 2 && !s.timesteps)
     return fail(CFD_E_ARG, "DPM-Solver++: pass the scheduler's timestep table in cfd_sample_args.timesteps (the library does not build it)");
@@ -810,6 +822,8 @@ static void (*const picard_step_kernel_weighted)(const PicardStepArgs) = picard_
 // What a level batch's callers refuse alike (`who`: the entry point, for the message)
 static int level_batch_refusals(Ctx* c, const cfd_sample_args* args, const char* who, const char* why0, int levels_per_batch) {
   if (args->scheduler != 0) return fail(CFD_E_ARG, "%s: %s (scheduler 0, not %d)", who, why0, args->scheduler);
+  if (args->prediction_type != 0)
+    return fail(CFD_E_ARG, "%s needs prediction_type = 0 (epsilon), not %d: its level kernels step an epsilon model", who, args->prediction_type);
   if (args->preseq) return fail(CFD_E_ARG, "%s takes no preseq (the rollout's prefix in-painting)", who);
   if (args->dynamic_memory_mask) return fail(CFD_E_ARG, "%s takes no dynamic memories (dynamic_memory_mask = %d)", who, args->dynamic_memory_mask);
   for (int j = 0; j < CFD_NMEM; ++j)
@@ -1186,15 +1200,19 @@ extern "C" int cfd_sample_read(cfd_handle c, float* out, int close) {
 }
 
 // ---- stand-alone scheduler ops ----------------------------------------------------------------------------
-extern "C" int cfd_scheduler_step(cfd_handle c, int scheduler, const float* ac, int T, int n_inf, int t, int clip, float eta,
-                                  int set_alpha_to_one, const float* model_output, const float* noise, float* sample_inout,
-                                  size_t numel, float* pred_original_sample, void* stream) {
+extern "C" int cfd_scheduler_step_pred(cfd_handle c, int scheduler, const float* ac, int T, int n_inf, int t, int clip, float eta,
+                                       int set_alpha_to_one, int prediction_type, const float* model_output, const float* noise,
+                                       float* sample_inout, size_t numel, float* pred_original_sample, void* stream) {
   if (!c || !ac || !model_output || !sample_inout || t < 0 || t >= T || n_inf < 1) return fail(CFD_E_ARG, "bad argument");
+  if (prediction_type != 0 && prediction_type != 1)
+    return fail(CFD_E_ARG, "cfd_scheduler_step_pred: prediction_type = %d is not 0 (epsilon) or 1 (sample)", prediction_type);
+  if (scheduler == 3 && prediction_type != 0)
+    return fail(CFD_E_ARG, "cfd_scheduler_step_pred: DDIM inversion needs prediction_type = 0 (epsilon)");
   if (scheduler != 0 && scheduler != 1 && scheduler != 3)
-    return fail(CFD_E_ARG, "cfd_scheduler_step: scheduler must be 0 (DDPM), 1 (DDIM) or 3 (DDIM inversion); DPM-Solver++ steps go through "
-                           "cfd_dpmsolver_step");
+    return fail(CFD_E_ARG, "cfd_scheduler_step[_pred]: scheduler must be 0 (DDPM), 1 (DDIM) or 3 (DDIM inversion); DPM-Solver++ steps go "
+                           "through cfd_dpmsolver_step[_pred]");
   if (scheduler == 3 && (eta != 0.f || clip))
-    return fail(CFD_E_ARG, "cfd_scheduler_step: DDIM inversion needs eta = 0 and clip_sample = 0 (got %g, %d)", (double)eta, clip);
+    return fail(CFD_E_ARG, "cfd_scheduler_step[_pred]: DDIM inversion needs eta = 0 and clip_sample = 0 (got %g, %d)", (double)eta, clip);
   HIPCHK(hipSetDevice(c->cfg.device));
   StepCoef k;
   memset(&k, 0, sizeof(k));
@@ -1202,26 +1220,49 @@ extern "C" int cfd_scheduler_step(cfd_handle c, int scheduler, const float* ac, 
   else if (scheduler == 3) ddim_inverse_coef(ac, T, n_inf, t, set_alpha_to_one, &k);
   else ddim_coef(ac, T, n_inf, t, eta, set_alpha_to_one, &k);
   if (k.use_noise != 0.f && !noise) return fail(CFD_E_ARG, "this step adds noise: pass the N(0,1) draw");
-  hipLaunchKernelGGL(sched_step_kernel<>, dim3((unsigned)((numel + 255) / 256)), dim3(256), 0, (hipStream_t)stream, model_output, noise,
-                     sample_inout, numel, k, scheduler, clip, pred_original_sample);
+  const dim3 grid((unsigned)((numel + 255) / 256)), block(256);
+  if (prediction_type == 1)
+    hipLaunchKernelGGL((sched_step_kernel<0, 1>), grid, block, 0, (hipStream_t)stream, model_output, noise, sample_inout, numel, k, scheduler,
+                       clip, pred_original_sample);
+  else
+    hipLaunchKernelGGL(sched_step_kernel<>, grid, block, 0, (hipStream_t)stream, model_output, noise, sample_inout, numel, k, scheduler, clip,
+                       pred_original_sample);
+  HIPCHK(hipGetLastError());
+  return CFD_OK;
+}
+
+extern "C" int cfd_scheduler_step(cfd_handle c, int scheduler, const float* ac, int T, int n_inf, int t, int clip, float eta,
+                                  int set_alpha_to_one, const float* model_output, const float* noise, float* sample_inout,
+                                  size_t numel, float* pred_original_sample, void* stream) {
+  return cfd_scheduler_step_pred(c, scheduler, ac, T, n_inf, t, clip, eta, set_alpha_to_one, 0, model_output, noise, sample_inout, numel,
+                                 pred_original_sample, stream);
+}
+
+extern "C" int cfd_dpmsolver_step_pred(cfd_handle c, const float* ac, int T, int t, int prev_t, int t_prev_model, int prediction_type,
+                                       const float* model_output, const float* m_prev, float* sample_inout, float* x0_out, size_t numel,
+                                       void* stream) {
+  if (!c || !ac || !model_output || !sample_inout || !x0_out) return fail(CFD_E_ARG, "null argument");
+  if (prediction_type != 0 && prediction_type != 1)
+    return fail(CFD_E_ARG, "cfd_dpmsolver_step_pred: prediction_type = %d is not 0 (epsilon) or 1 (sample)", prediction_type);
+  if (t < 1 || t >= T || prev_t < 0 || prev_t >= t || t_prev_model >= T || (t_prev_model >= 0 && t_prev_model <= t))
+    return fail(CFD_E_ARG, "cfd_dpmsolver_step[_pred]: need T > t_prev_model > t > prev_t >= 0 (t_prev_model = -1: first order), t >= 1 "
+                           "(got %d, %d, %d, T = %d)", t_prev_model, t, prev_t, T);
+  if (t_prev_model >= 0 && !m_prev) return fail(CFD_E_ARG, "a second-order step reads the previous step's x0: pass m_prev");
+  HIPCHK(hipSetDevice(c->cfg.device));
+  StepCoef k;
+  dpmpp_coef(ac, t, prev_t, t_prev_model, &k);
+  const dim3 grid((unsigned)((numel + 255) / 256)), block(256);
+  if (prediction_type == 1)
+    hipLaunchKernelGGL((dpmpp_step_kernel<0, 1>), grid, block, 0, (hipStream_t)stream, model_output, m_prev, sample_inout, x0_out, numel, k);
+  else
+    hipLaunchKernelGGL(dpmpp_step_kernel<>, grid, block, 0, (hipStream_t)stream, model_output, m_prev, sample_inout, x0_out, numel, k);
   HIPCHK(hipGetLastError());
   return CFD_OK;
 }
 
 extern "C" int cfd_dpmsolver_step(cfd_handle c, const float* ac, int T, int t, int prev_t, int t_prev_model, const float* model_output,
                                   const float* m_prev, float* sample_inout, float* x0_out, size_t numel, void* stream) {
-  if (!c || !ac || !model_output || !sample_inout || !x0_out) return fail(CFD_E_ARG, "null argument");
-  if (t < 1 || t >= T || prev_t < 0 || prev_t >= t || t_prev_model >= T || (t_prev_model >= 0 && t_prev_model <= t))
-    return fail(CFD_E_ARG, "cfd_dpmsolver_step: need T > t_prev_model > t > prev_t >= 0 (t_prev_model = -1: first order), t >= 1 "
-                           "(got %d, %d, %d, T = %d)", t_prev_model, t, prev_t, T);
-  if (t_prev_model >= 0 && !m_prev) return fail(CFD_E_ARG, "a second-order step reads the previous step's x0: pass m_prev");
-  HIPCHK(hipSetDevice(c->cfg.device));
-  StepCoef k;
-  dpmpp_coef(ac, t, prev_t, t_prev_model, &k);
-  hipLaunchKernelGGL(dpmpp_step_kernel<>, dim3((unsigned)((numel + 255) / 256)), dim3(256), 0, (hipStream_t)stream, model_output, m_prev,
-                     sample_inout, x0_out, numel, k);
-  HIPCHK(hipGetLastError());
-  return CFD_OK;
+  return cfd_dpmsolver_step_pred(c, ac, T, t, prev_t, t_prev_model, 0, model_output, m_prev, sample_inout, x0_out, numel, stream);
 }
 
 // ---- developer hook: the stride rule of cfd_sample_parallel, on the host (no handle, no device) --------------------------------------

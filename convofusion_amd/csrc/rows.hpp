@@ -547,6 +547,21 @@ __host__ __device__ __forceinline__ float step_x0(const StepCoef& c, int clip, f
 }
 __host__ __device__ __forceinline__ float ddpm_mu(const StepCoef& c, float x0, float x) { return c.c0 * x0 + c.cx * x; }
 
+// What the denoiser predicts (cfd_sample_args.prediction_type): PRED 0 the noise (epsilon), PRED 1 the clean latent ("sample").  The
+// step's x0 and the DDIM direction term for either, next to step_x0 so that every kernel that steps takes them from one place.  PRED 1:
+// x0 is the (clipped) output itself -- no division by sa -- and the direction is the noise the UNCLIPPED output implies,
+// eps_hat = (x - sa * out) / sb (sb = sqrt(1 - abar_t) > 0 at every table entry).  PRED 0 is step_x0 and the output itself.
+template <int PRED>
+__host__ __device__ __forceinline__ float step_x0_of(const StepCoef& c, int clip, float x, float out) {
+  if constexpr (PRED == 0) return step_x0(c, clip, x, out);
+  else return clip ? fminf(fmaxf(out, -1.0f), 1.0f) : out;
+}
+template <int PRED>
+__host__ __device__ __forceinline__ float step_eps_of(const StepCoef& c, float x, float out) {
+  if constexpr (PRED == 0) return out;
+  else return (x - c.sa * out) / c.sb;
+}
+
 // Philox4x32-10 (restated in oracle/philox_ref.py, checked there against the Random123 known answers)
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
                                               uint32_t k1, uint32_t out[4]) {
@@ -746,7 +761,9 @@ template <bool WTAB, bool TRAJ = false>
 using CfgStepArgsOf = typename std::conditional<TRAJ, CfgStepArgsT<typename std::conditional<WTAB, CfgStepArgsW, CfgStepArgs>::type>,
                                                 typename std::conditional<WTAB, CfgStepArgsW, CfgStepArgs>::type>::type;
 
-template <int CFD_KI = 0, bool WTAB = false, bool TRAJ = false>
+// PRED (cfd_sample_args.prediction_type): 0 the combine is the noise, 1 it is x0 (step_x0_of / step_eps_of); the combine itself and the
+// argument structs are the same for both.
+template <int CFD_KI = 0, bool WTAB = false, bool TRAJ = false, int PRED = 0>
 __global__ void cfg_step_kernel(const CfgStepArgsOf<WTAB, TRAJ> a) {
   const int per_utt = a.L * CFD_LAT;
   const long long n4 = (long long)a.B * per_utt / 4;
@@ -797,12 +814,12 @@ __global__ void cfg_step_kernel(const CfgStepArgsOf<WTAB, TRAJ> a) {
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const float eps = (a.G > 1) ? u[q] + acc[q] : u[q];
-    const float x0 = step_x0(c, a.clip, x[q], eps);
+    const float x0 = step_x0_of<PRED>(c, a.clip, x[q], eps);   // (eps: the combine -- the noise, or x0 itself for PRED 1)
     x0v[q] = x0;
     float prev;
     if (a.kind == 0) prev = ddpm_mu(c, x0, x[q]);
     else if (a.kind == 2) prev = dpmpp_prev(c, x[q], x0, m1[q]);
-    else prev = c.c0 * x0 + c.cx * eps;
+    else prev = c.c0 * x0 + c.cx * step_eps_of<PRED>(c, x[q], eps);
     if (c.use_noise != 0.f) prev = prev + c.sigma * z[q];
     o[q] = prev;
   }

@@ -20,7 +20,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-from .sampler import SamplingRun, build_guidance_batch
+from .sampler import SamplingRun, build_guidance_batch, refuse_sample_prediction
 
 
 def _cat_masks(ma, mb, B, S_of, dev):
@@ -54,6 +54,7 @@ class DyadicRun:
         if getattr(scheduler, "KIND", None) == 2:
             raise NotImplementedError("DyadicRun runs with DDPMScheduler / DDIMScheduler; with DPMSolverMultistepScheduler the lock-step "
                                       "dyadic loop has no reference trajectory to be checked against")
+        refuse_sample_prediction(scheduler, "DyadicRun (the lock-step dyadic loop) runs")
         self.merged = bool(shared_weights)
         if self.merged:
             if denoiser_b is not None and denoiser_b is not denoiser_a:

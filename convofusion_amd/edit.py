@@ -20,7 +20,7 @@ import inspect
 
 import torch
 
-from .sampler import check_operands, invert, sample
+from .sampler import check_operands, invert, refuse_sample_prediction, sample
 from .vae import LATENT_PARTS
 
 FRAMES_PER_CHUNK = 16   # vae.py:178
@@ -129,6 +129,7 @@ def reperform_motion(model, feats, lengths, source_conditioning, target_conditio
     from .scheduler import DDIMInverseScheduler, DDIMScheduler
     if method not in ("ddim", "ddpm"):
         raise ValueError(f"method must be 'ddim' or 'ddpm', not {method!r}")
+    refuse_sample_prediction(model.scheduler, "reperform_motion (inversion and regeneration) runs")
     if not model.do_classifier_free_guidance:
         raise NameError("guidance_bs_mulitplier: the reference loop requires classifier-free guidance")
     latent, dist, _ = model.vae.encode(feats, lengths)

@@ -161,6 +161,19 @@ def check_tie(tie, keep_mask, B, L, device=None, *, preseq=None, strength=1.0, s
     return tie.detach().to(device=device, dtype=torch.int32).contiguous()
 
 
+def sample_prediction(scheduler):
+    """Whether the scheduler's denoiser predicts the clean latent (``prediction_type="sample"``) rather than the noise."""
+    return (getattr(scheduler, "config", None) or {}).get("prediction_type", "epsilon") == "sample"
+
+
+def refuse_sample_prediction(scheduler, what):
+    """NotImplementedError when ``scheduler`` has ``prediction_type="sample"``: ``what`` (the start of the message) is built and checked for
+    epsilon-predicting models only -- there is no trajectory of an x0-predicting model to check it against."""
+    if sample_prediction(scheduler):
+        raise NotImplementedError(f"{what} with prediction_type='epsilon' only: with prediction_type='sample' it has no reference "
+                                  "trajectory to be checked against")
+
+
 _AUTO_RUN = object()   # the first attempt of an "auto" loop (``_with_auto_operands``): a guarded run, not another "auto" loop
 
 
@@ -184,7 +197,7 @@ class RunKind(typing.NamedTuple):
     tie: typing.Optional[torch.Tensor]   # the tie table: ``check_tie``
     first_iteration: int               # k0 of an edit or a replay, else 0
     trajectory: bool                   # a DDIM inversion that records its trajectory
-    operands: object                   # as given; a replay turns None / "auto" into 0
+    operands: object                   # as given; a replay and a prediction_type="sample" run turn None / "auto" into 0
 
 
 def resolve_run_kind(scheduler, table, eta=0.0, *, B, L, preseq=None, source_latents=None, keep_mask=None, strength=1.0, trajectory=False,
@@ -192,8 +205,20 @@ def resolve_run_kind(scheduler, table, eta=0.0, *, B, L, preseq=None, source_lat
                      operands=None, device=None):
     """Which kind of run the arguments of ``SamplingRun`` describe, over the scheduler's full ``table``: every refusal between kinds and
     the leaf checks (``check_inversion`` / ``check_anchor`` / ``check_tie`` / ``check_noise_space`` / ``check_edit``), in the order
-    inversion, anchor, tie, replay, edit: where two refusals apply, the earlier one is raised.  A new kind adds its block here."""
+    prediction type, inversion, anchor, tie, replay, edit: where two refusals apply, the earlier one is raised.  A new kind adds its
+    block here.  ``prediction_type="sample"`` (the scheduler's config) goes with the plain, weighted, edit, tied and preseq runs of DDPM,
+    DDIM and DPM-Solver++; inversion, an anchored run, a replay and dynamic memories (dyadic runs) refuse it, and its default operand
+    policy is 0 (None / "auto" become 0: the single-fp16 policy was adopted on epsilon trajectories)."""
     n_full, kind = len(table), scheduler.KIND
+    if sample_prediction(scheduler):
+        for what, given in (("a DDIM inversion run (DDIMInverseScheduler) runs", kind == 3),
+                            ("an anchored run (anchor_trajectory) runs", anchor_trajectory is not None),
+                            ("the replay of a noise space (noise_space) runs", noise_space is not None),
+                            ("a run with dynamic memories (a dyadic run) runs", bool(dynamic_memories))):
+            if given:
+                refuse_sample_prediction(scheduler, what)
+        if operands is None or operands is _AUTO_RUN or operands == "auto":
+            operands = 0
     if kind == 3:
         check_inversion(scheduler, table, eta)
         if preseq is not None or source_latents is not None or anchor_trajectory is not None or dynamic_memories:

@@ -17,7 +17,7 @@ from . import _lib
 from .denoiser import Denoiser
 # the pure half of opening a run: the argument checks of every kind and the kind of a run (importable from here as before)
 from .run_kind import (_AUTO_RUN, RunKind, check_anchor, check_edit, check_inversion, check_noise_space,  # noqa: F401
-                       check_operands, check_tie, edit_first_iteration, resolve_run_kind)
+                       check_operands, check_tie, edit_first_iteration, refuse_sample_prediction, resolve_run_kind, sample_prediction)
 
 # which guidance chunk carries which conditional memory (reference convofusion.py:909-929, 527-541)
 CFG_CHUNKS = 7
@@ -34,7 +34,9 @@ CFG_CHUNKS = 7
 # (the heavy-tailed stress weights: DESIGN.md section 2).  ``operands="auto"`` (opt-in) decides per run: the default policy with the
 # attention-concentration census on, and a restart with pairs from iteration 0 when the census trips (see CENSUS_TAU).
 # DPM-Solver++ (kind 2) is deterministic like DDIM -- no noise re-injected, its multistep history carries a perturbation forward -- and keeps
-# pairs as well, and so does DDIM inversion (kind 3, DDIMInverseScheduler), for the same reason.
+# pairs as well, and so does DDIM inversion (kind 3, DDIMInverseScheduler), for the same reason.  A run whose scheduler has
+# prediction_type="sample" keeps pairs whatever its kind (``resolve_run_kind``): the policy's error enters an x0 step through other
+# coefficients than an epsilon step, and nobody has measured that case; an explicit ``operands=`` still wins.
 OPERAND_POLICY = {0: 15, 1: 0, 2: 0, 3: 0}
 
 # Attention-concentration census (cfd_sample_args.census_tau, ``SamplingRun.census``): the fused cross-attention kernel reports, per layer, the
@@ -240,8 +242,9 @@ def select_memories(encoder_hidden_states, cond_masks, G, B, dedup=True, row_map
 
 
 def fill_scheduler_args(a, scheduler, num_inference_steps, table, eta=0.0):
-    """The scheduler part of cfd_sample_args ``a``: kind, counts, clip_sample, eta, set_alpha_to_one, steps_offset, alphas_cumprod and the
-    timestep table.  Returns the two host buffers the library reads through ``a``: the caller keeps them alive as long as it does."""
+    """The scheduler part of cfd_sample_args ``a``: kind, counts, clip_sample, eta, set_alpha_to_one, steps_offset, prediction_type,
+    alphas_cumprod and the timestep table.  Returns the two host buffers the library reads through ``a``: the caller keeps them alive as
+    long as it does."""
     a.scheduler = scheduler.KIND
     a.num_train_timesteps = scheduler.config.num_train_timesteps
     a.num_inference_steps = num_inference_steps
@@ -249,6 +252,7 @@ def fill_scheduler_args(a, scheduler, num_inference_steps, table, eta=0.0):
     a.eta = float(eta)
     a.set_alpha_to_one = 1 if scheduler.config.get("set_alpha_to_one", True) else 0
     a.steps_offset = int(scheduler.config.get("steps_offset", 0))
+    a.prediction_type = _lib.PREDICTION_TYPES[scheduler.config.get("prediction_type", "epsilon")]
     acp = scheduler.alphas_cumprod.detach().to("cpu", torch.float32).contiguous()
     a.alphas_cumprod = acp.data_ptr()
     ts = (C.c_int32 * len(table))(*[int(t) for t in table])
@@ -682,7 +686,7 @@ def sample(denoiser, scheduler, encoder_hidden_states, cond_masks=None, *, B, L=
     None changes nothing.  ``noise_space`` = (trajectory, noise) of ``invert_ddpm`` with ``keep_mask`` / ``strength``: the replay of an
     edit-friendly DDPM noise space, as in ``SamplingRun``; ``operands`` None or "auto" is then 0.  It goes with ``modality_weights`` and
     pruning and ``return_attention``; tie, preseq, anchor_trajectory, source_latents, init_latents and step_noise are refused."""
-    if noise_space is not None and (operands is None or check_operands(operands) == "auto"):
+    if (noise_space is not None or sample_prediction(scheduler)) and (operands is None or check_operands(operands) == "auto"):
         operands = 0
     if check_operands(operands) == "auto":
         args = dict(locals())
@@ -789,6 +793,7 @@ def invert_ddpm(denoiser, scheduler, enc, masks=None, *, source_latents, num_inf
         raise TypeError("denoiser must be a convofusion_amd.denoiser.Denoiser")
     if getattr(scheduler, "KIND", None) != 0:
         raise TypeError("invert_ddpm needs a convofusion_amd.scheduler.DDPMScheduler")
+    refuse_sample_prediction(scheduler, "invert_ddpm (the edit-friendly DDPM noise space) runs")
     if not isinstance(source_latents, torch.Tensor) or not source_latents.is_floating_point() or source_latents.dim() != 3 \
             or int(source_latents.shape[2]) != 128:
         raise ValueError("source_latents must be a floating-point tensor [B, L, 128]")
@@ -856,6 +861,7 @@ def sample_parallel(denoiser, scheduler, enc, masks=None, *, B, L=16, num_infere
         raise TypeError("denoiser must be a convofusion_amd.denoiser.Denoiser")
     if getattr(scheduler, "KIND", None) != 0:
         raise TypeError("sample_parallel needs a convofusion_amd.scheduler.DDPMScheduler")
+    refuse_sample_prediction(scheduler, "sample_parallel (Picard sweeps over level batches) runs")
     for name, v in (("B", B), ("L", L)):
         if isinstance(v, bool) or int(v) != v or int(v) < 1:
             raise ValueError(f"{name} must be a positive integer, not {v!r}")
@@ -971,6 +977,7 @@ def sample_with_weg(denoiser, scheduler, encoder_hidden_states, cond_masks, focu
         raise NotImplementedError("sample_with_weg: the word-excitation-guidance loop (focus_indices) runs with DDPMScheduler / DDIMScheduler; "
                                   "with DPMSolverMultistepScheduler it has no reference trajectory to be checked against -- use sample() "
                                   "without focus_indices")
+    refuse_sample_prediction(scheduler, "sample_with_weg: the word-excitation-guidance loop (focus_indices) runs")
     from . import weg
     G = guidance_chunks
     scheduler.set_timesteps(num_inference_steps)

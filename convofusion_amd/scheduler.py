@@ -3,8 +3,8 @@
 convofusion/models/modeltype/convofusion.py:104-106,419-423,544,574 and unbounded_synthesis.py:49-75).
 
 diffusers is a third-party dependency that is neither vendored in the reference nor installed here;
-these classes restate its public surface for the epsilon-prediction / fixed_small / clip_sample
-configuration, DPMSolverMultistepScheduler in its default (DPM-Solver++ 2M) configuration, and DDIMInverseScheduler (deterministic DDIM
+these classes restate its public surface for the fixed_small / clip_sample configuration with
+prediction_type "epsilon" or "sample" (TRAIN.ABLATION.PREDICT_EPSILON, convofusion.py:101-103), DPMSolverMultistepScheduler in its default (DPM-Solver++ 2M) configuration, and DDIMInverseScheduler (deterministic DDIM
 inversion, beyond the reference).  Tables are built with the same torch float32 ops diffusers uses; ``step`` and
 ``add_noise`` run on the device through libcfdenoise (cfd_scheduler_step / cfd_add_noise).  The
 fused sampling loop (convofusion_amd.sampler) reads only the tables and config from these objects.
@@ -37,6 +37,15 @@ class SchedulerOutput:
 
 class _Config(dict):
     __getattr__ = dict.__getitem__
+
+
+def _check_prediction_type(cls, prediction_type):
+    """"epsilon" or "sample" (the denoiser predicts the noise, or the clean latent: the reference's PREDICT_EPSILON switch);
+    "v_prediction" -- which the reference cannot train -- and anything else raise NotImplementedError."""
+    if not isinstance(prediction_type, str) or prediction_type not in _lib.PREDICTION_TYPES:
+        raise NotImplementedError(f"{cls}: only prediction_type='epsilon' or 'sample' (TRAIN.ABLATION.PREDICT_EPSILON) is implemented, "
+                                  f"not {prediction_type!r}")
+    return prediction_type
 
 
 class _SchedulerBase:
@@ -102,16 +111,18 @@ class _SchedulerBase:
         x0 = torch.empty_like(x)     # the x0 estimate the step forms on the way (diffusers: SchedulerOutput.pred_original_sample)
         lib = _lib.load()
         with torch.cuda.device(x.device):
-            _lib.check(lib.cfd_scheduler_step(
+            _lib.check(lib.cfd_scheduler_step_pred(
                 _ops_handle(x.device), self.KIND, acp_p, self.config.num_train_timesteps, n_inf, t,
                 1 if self.config.clip_sample else 0, float(eta), 1 if self.config.get("set_alpha_to_one", True) else 0,
-                C.c_void_p(eps.data_ptr()), C.c_void_p(noise.data_ptr()) if noise is not None else None,
+                _lib.PREDICTION_TYPES[self.config.prediction_type], C.c_void_p(eps.data_ptr()), C.c_void_p(noise.data_ptr()) if noise is not None else None,
                 C.c_void_p(x.data_ptr()), x.numel(), C.c_void_p(x0.data_ptr()), C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)))
         return x, x0
 
 
 class DDPMScheduler(_SchedulerBase):
-    """diffusers 0.14.0 DDPMScheduler (epsilon prediction, variance_type fixed_small)."""
+    """diffusers 0.14.0 DDPMScheduler (variance_type fixed_small; prediction_type "epsilon" or "sample").  With "sample" the model output
+    is x0: clipped with clip_sample, then the posterior mean and the noise as for "epsilon"; ``step(...).pred_original_sample`` is the
+    (clipped) model output."""
     KIND = 0
 
     def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear",
@@ -119,8 +130,7 @@ class DDPMScheduler(_SchedulerBase):
                  allow_unpinned_timesteps=False, **kwargs):
         if variance_type != "fixed_small":
             raise NotImplementedError("only variance_type='fixed_small' (configs/modules/scheduler.yaml:10)")
-        if prediction_type != "epsilon":
-            raise NotImplementedError("only prediction_type='epsilon' (TRAIN.ABLATION.PREDICT_EPSILON)")
+        _check_prediction_type("DDPMScheduler", prediction_type)
         self.config = _Config(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
                               beta_schedule=beta_schedule, variance_type=variance_type, clip_sample=clip_sample,
                               prediction_type=prediction_type, allow_unpinned_timesteps=bool(allow_unpinned_timesteps))
@@ -159,14 +169,19 @@ class DDPMScheduler(_SchedulerBase):
 
 
 class DDIMScheduler(_SchedulerBase):
-    """diffusers 0.14.0 DDIMScheduler (epsilon prediction)."""
+    """diffusers 0.14.0 DDIMScheduler (prediction_type "epsilon" or "sample").
+
+    With "sample" the model output is x0, and the step is x' = sqrt(abar_prev) clip(x0) + sqrt(1 - abar_prev - std^2) eps_hat (+ std z)
+    with eps_hat = (x - sqrt(abar_t) x0) / sqrt(1 - abar_t) from the UNCLIPPED output -- the form of later diffusers releases.  0.14.0's
+    published source is believed to put the model output itself into the direction term for "sample", which is no DDIM step for an
+    x0-predicting model; the package is not available here to pin either form (parity of DDIM with "sample" is unpinned, like
+    ``DDPMScheduler(allow_unpinned_timesteps=True)``).  The reference's scheduler is DDPM, which has no such caveat."""
     KIND = 1
 
     def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear",
                  trained_betas=None, clip_sample=True, set_alpha_to_one=True, steps_offset=0,
                  prediction_type="epsilon", **kwargs):
-        if prediction_type != "epsilon":
-            raise NotImplementedError("only prediction_type='epsilon'")
+        _check_prediction_type("DDIMScheduler", prediction_type)
         self.config = _Config(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
                               beta_schedule=beta_schedule, clip_sample=clip_sample, set_alpha_to_one=set_alpha_to_one,
                               steps_offset=steps_offset, prediction_type=prediction_type)
@@ -210,7 +225,8 @@ class DDIMInverseScheduler(_SchedulerBase):
                  trained_betas=None, clip_sample=True, set_alpha_to_one=True, steps_offset=0,
                  prediction_type="epsilon", **kwargs):
         if prediction_type != "epsilon":
-            raise NotImplementedError("only prediction_type='epsilon'")
+            raise NotImplementedError(f"DDIMInverseScheduler: only prediction_type='epsilon', not {prediction_type!r}: inverting an "
+                                      "x0-predicting model has no trajectory to be checked against")
         self.config = _Config(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
                               beta_schedule=beta_schedule, clip_sample=False, set_alpha_to_one=set_alpha_to_one,
                               steps_offset=steps_offset, prediction_type=prediction_type)
@@ -241,7 +257,8 @@ class DDIMInverseScheduler(_SchedulerBase):
 class DPMSolverMultistepScheduler(_SchedulerBase):
     """diffusers 0.14.0 DPMSolverMultistepScheduler in its default configuration: DPM-Solver++ (algorithm_type "dpmsolver++"), second
     order multistep (solver_order 2, solver_type "midpoint"), first order at the last step of a run shorter than 15 steps
-    (lower_order_final), epsilon prediction, no thresholding.  Deterministic: ``step`` draws nothing.
+    (lower_order_final), prediction_type "epsilon" or "sample" (the model output is then the data prediction x0 itself, 0.14.0's
+    ``convert_model_output`` under dpmsolver++), no thresholding.  Deterministic: ``step`` draws nothing.
 
     ``set_timesteps(N)`` builds 0.14.0's table ``np.linspace(0, T - 1, N + 1).round()[::-1][:-1]`` with numpy itself (np.round takes
     halves to even; the library is handed this table and never rebuilds it).  ``step`` keeps the previous step's data prediction x0 as a
@@ -254,10 +271,11 @@ class DPMSolverMultistepScheduler(_SchedulerBase):
                  algorithm_type="dpmsolver++", solver_type="midpoint", lower_order_final=True):
         for name, value, want in (("solver_order", solver_order, 2), ("algorithm_type", algorithm_type, "dpmsolver++"),
                                   ("solver_type", solver_type, "midpoint"), ("lower_order_final", lower_order_final, True),
-                                  ("thresholding", thresholding, False), ("prediction_type", prediction_type, "epsilon")):
+                                  ("thresholding", thresholding, False)):
             if value != want:
                 raise NotImplementedError(f"DPMSolverMultistepScheduler: only {name}={want!r} (diffusers 0.14.0's default) is implemented, "
                                           f"not {value!r}")
+        _check_prediction_type("DPMSolverMultistepScheduler", prediction_type)
         self.config = _Config(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
                               beta_schedule=beta_schedule, trained_betas=trained_betas, solver_order=solver_order,
                               prediction_type=prediction_type, thresholding=thresholding,
@@ -308,8 +326,9 @@ class DPMSolverMultistepScheduler(_SchedulerBase):
         acp, acp_p = self._acp_host()
         lib = _lib.load()
         with torch.cuda.device(x.device):
-            _lib.check(lib.cfd_dpmsolver_step(
-                _ops_handle(x.device), acp_p, self.config.num_train_timesteps, t, prev_t, t_prev_model, C.c_void_p(eps.data_ptr()),
+            _lib.check(lib.cfd_dpmsolver_step_pred(
+                _ops_handle(x.device), acp_p, self.config.num_train_timesteps, t, prev_t, t_prev_model,
+                _lib.PREDICTION_TYPES[self.config.prediction_type], C.c_void_p(eps.data_ptr()),
                 C.c_void_p(m_prev.data_ptr()) if second else None, C.c_void_p(x.data_ptr()), C.c_void_p(x0.data_ptr()), x.numel(),
                 C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)))
         self.model_outputs = self.model_outputs[1:] + [x0]

@@ -155,6 +155,15 @@ typedef struct {
                                  [1, T); each step goes to the next entry (to 0 after the last), and its second-order term uses the
                                  previous entry. */
   int num_timesteps;
+  int prediction_type;        /* what the denoiser predicts (the schedulers' prediction_type; TRAIN.ABLATION.PREDICT_EPSILON of the
+                                 reference, convofusion.py:101-103): 0 = the noise ("epsilon"; ctypes' zero-initialised default), 1 = the
+                                 clean latent ("sample").  With 1 the guidance combine `out` is read as x0 (clipped to [-1, 1] with
+                                 clip_sample): scheduler 0 steps ddpm_mu(x0, x) + sigma z, scheduler 2 takes it as its data prediction,
+                                 scheduler 1 steps c0 x0 + cx eps_hat (+ sigma z) with eps_hat = (x - sqrt(abar_t) out) / sqrt(1 - abar_t)
+                                 from the UNCLIPPED output (the form of later diffusers releases; 0.14.0's DDIM is unpinned here).  Any
+                                 other value is CFD_E_ARG.  1 is refused (CFD_E_ARG) by scheduler 3, cfd_sample_begin_anchored,
+                                 cfd_sample_begin_replay, cfd_ddpm_invert and cfd_sample_parallel.  The field sits in what was 4 bytes of
+                                 padding in front of att_ring: no other field moves and the struct's size is unchanged. */
   float* att_ring[CFD_NUM_MEM];/* all NULL, or five dev buffers [iterations][B][num_layers][L][S_j] float32: the captured iteration
                                  stores the attention probabilities of the LAST guidance chunk (full conditioning) of iteration i into
                                  slot i -- the reference's per-iteration dict attention_matrices[t] = att_mats of the last chunk
@@ -419,6 +428,15 @@ int cfd_scheduler_step(cfd_handle h, int scheduler, const float* alphas_cumprod,
  * sampling loop's scheduler kind 2. */
 int cfd_dpmsolver_step(cfd_handle h, const float* alphas_cumprod, int num_train_timesteps, int t, int prev_t, int t_prev_model,
                        const float* model_output, const float* m_prev, float* sample_inout, float* x0_out, size_t numel, void* stream);
+/* cfd_scheduler_step / cfd_dpmsolver_step with the model's prediction type (cfd_sample_args.prediction_type: 0 = epsilon, what the two
+ * calls above pass; 1 = sample: model_output is x0 -- pred_original_sample / x0_out is then the (clipped) model output; any other value
+ * and 1 with scheduler 3 are CFD_E_ARG). */
+int cfd_scheduler_step_pred(cfd_handle h, int scheduler, const float* alphas_cumprod, int num_train_timesteps, int num_inference_steps,
+                            int t, int clip_sample, float eta, int set_alpha_to_one, int prediction_type, const float* model_output,
+                            const float* noise, float* sample_inout, size_t numel, float* pred_original_sample, void* stream);
+int cfd_dpmsolver_step_pred(cfd_handle h, const float* alphas_cumprod, int num_train_timesteps, int t, int prev_t, int t_prev_model,
+                            int prediction_type, const float* model_output, const float* m_prev, float* sample_inout, float* x0_out,
+                            size_t numel, void* stream);
 int cfd_add_noise(cfd_handle h, const float* alphas_cumprod_host, int t, const float* original,
                   const float* noise, float* out, size_t numel, void* stream);
 

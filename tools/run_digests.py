@@ -121,6 +121,12 @@ def main():
     run_line("dedup=False dynamic_memories=(0,)", ddpm(), [x.clone() for x in mems], masks, dedup=False, dynamic_memories=(0,))
     run_line("operands=0", ddpm(), mems, masks, operands=0)
     run_line("operands=auto", ddpm(), mems, masks, operands="auto")
+    # prediction_type="sample" (new lines only: ARG_FIELDS stays, so that every line above compares with older trees)
+    for name, sch in (("ddpm", scheduler.DDPMScheduler(variance_type="fixed_small", prediction_type="sample", **SCHED_KW)),
+                      ("ddim", scheduler.DDIMScheduler(prediction_type="sample", **SCHED_KW)),
+                      ("dpm-solver++", scheduler.DPMSolverMultistepScheduler(prediction_type="sample", **YAML))):
+        run, _ = run_line(f"{name} prediction_type=sample", sch, mems, masks, n=6 if sch.KIND == 2 else N_IT)
+        assert run._args.prediction_type == 1
 
 
 if __name__ == "__main__":

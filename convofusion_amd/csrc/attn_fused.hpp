@@ -5,26 +5,47 @@
 //
 // MFMA orientation (v_mfma_f32_16x16x32, split-pair operands, 3 MFMAs per product):
 //   S^T[key][q] = sum_d K[key][d] Q[q][d]      K tile from LDS (A operand), Q fragments in registers (B operand)
-//   O^T[f][q]  += sum_key V^T[f][key] P[q][key] V^T tile from LDS (A operand), P straight from the S accumulators
+//   O^T[f][q]  += sum_key V^T[f][key] P[q][key] V^T fragments from LDS (A operand), P straight from the S accumulators
 // A lane (q = lane&15, g = lane>>4) ends the first product holding S[q][16t + 4g + r] (t = 0..1, r = 0..3).  Feeding those
 // registers as the B operand of the second product means k-slot (8g + e) of 32-key step s is key
-// 32s + 16(e>>2) + 4g + (e&3): the V^T tile must list its keys in that order, which the V^T GEMM's epilogue
-// produces for free (EpiSplit::perm32) -- no transpose, no LDS round trip for P.
+// 32s + 16(e>>2) + 4g + (e&3).  V stays TOKEN-major, as the q | k | v projection launch wrote it (one row per token, no V^T product):
+// the tile sits in LDS as [key][feature] and the A fragment is made by the transposed LDS read ds_read_b64_tr_b16, which hands a
+// group of 16 lanes a block of 4 keys x 16 features column-major -- lane group g reading keys 4g .. 4g+3 and then 16+4g .. 16+4g+3
+// of 16 features receives exactly that k-slot order.  No transpose pass, no LDS round trip for P.
+//
+// LDS image of the V half of a stage (16 KB): 16 pieces of 1 KB, piece ks*4 + n = SP line ks (features 32ks .. 32ks+31 of the head)
+// of keys 8n .. 8n+7.  Inside a piece, key r (0..7) of plane pl (0 = hi, 1 = lo) owns the 64-byte slot pl*8 + r, and the slot's two
+// 32-byte halves (features 0..15 | 16..31 of the line) are swapped when r >= 4.  A transposed read of one 32-lane half then takes
+// 8 keys x 32 B at (r&3)*64 + (c ^ (r>>2))*32 (mod 256): 32 different 8-byte bank groups, conflict-free; every lane's address is
+// 8-byte aligned (the read returns the wrong data otherwise).  The swizzle is applied on the per-lane SOURCE address of the LDS-DMA
+// fill (4 consecutive lanes fetch the 64 contiguous bytes of one key's plane), the image itself is lane-linear.
 #pragma once
 #include "cfd_common.hpp"
 
 struct SelfAttnArgs {
-  const char* qk;   // SP [M][1024]: q at columns h*128.., k at columns 512 + h*128..
-  const char* vts;  // SP [Be][512][Lv]: V^T per batch row, keys permuted inside every 32-block, Lv = roundup(L, 32)
+  const char* qkv;  // SP [M][ldq / 4]: q at columns h*128.., k at columns 512 + h*128.., v at columns 1024 + h*128..
   char* o;          // SP [M][512]
-  int L, Lv;
+  long long ldq;    // bytes per qkv row (1536 columns: 6144)
+  int L;
 };
+
+typedef __fp16 sa_tr4 __attribute__((__vector_size__(4 * sizeof(__fp16))));   // what the transposed-read builtin returns
+// One MFMA A fragment from a [key][feature] image: keys 4g .. 4g+3 from `p`, keys 16+4g .. 16+4g+3 from two pieces (2 KB) further on.
+// EXEC must be all ones (the gather crosses lanes): the callers are wave-uniform.
+__device__ __forceinline__ spx8 sa_tr_frag(const char* p) {
+  const sa_tr4 a = __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) sa_tr4*)(lptr_t)p);
+  const sa_tr4 b = __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) sa_tr4*)(lptr_t)(p + 2048));
+  spx8 r;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) { r[e] = (sp_t)a[e]; r[4 + e] = (sp_t)b[e]; }
+  return r;
+}
 
 #define SELF_ATTN_WAVES 8
 #define SA_WAIT_VM_LGKM0(N) __builtin_amdgcn_s_waitcnt(((N) & 15) | 0x70 | ((((N) >> 4) & 3) << 14))
 template <int CFD_KI = 0>
 __global__ void __launch_bounds__(SELF_ATTN_WAVES * 64, 4) self_attn_fused_kernel(const SelfAttnArgs a) {
-  // two stages of (K tile 16 KB | V^T tile 16 KB): keys are consumed in tiles of 32; the LDS-DMA fill of tile kt + 1 runs
+  // two stages of (K tile 16 KB | V tile 16 KB): keys are consumed in tiles of 32; the LDS-DMA fill of tile kt + 1 runs
   // under the MFMAs of tile kt (one barrier per tile), and two workgroups per CU cover each other's softmax sections
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int STAGE = 32768, VOFF = 16384;
@@ -37,11 +58,14 @@ __global__ void __launch_bounds__(SELF_ATTN_WAVES * 64, 4) self_attn_fused_kerne
   // A wave whose 16 queries all lie beyond L (the second workgroup of L = 196 has three) only helps with staging.
   const bool wave_active = (int)(blockIdx.x * (SELF_ATTN_WAVES * 16)) + wid * 16 < a.L;   // wave-uniform
   const int qc = qvalid ? q : a.L - 1;
-  const long long ROW = 4096;  // bytes per qk row (1024 columns)
+  const long long ROW = a.ldq;
 
   const int cpos = lane & 7, rsub = lane >> 3;
   const int nkv = (a.L + 31) / 32;
-  // fill of tile kt into stage kt & 1: 32 pieces of 1 KB (8 rows x 128 B), 4 per wave -- K: 4 k-steps x 4 row groups; V^T: 16 row groups
+  // fill of tile kt into stage kt & 1: 32 pieces of 1 KB (8 keys x 128 B), 4 per wave -- K and V alike: 4 SP lines x 4 key groups, from the
+  // same 32 token rows.  Keys beyond L - 1 (last tile) are clamped copies of row L - 1 in both halves: their probabilities are exactly 0
+  // (masked to -inf below), so all that matters is that the operands are finite, which a real row's are.
+  const int vpl = lane >> 5, vr = (lane >> 2) & 7, vch = vpl * 4 + ((((lane >> 1) & 1) ^ (vr >> 2)) << 1) + (lane & 1);   // V image (header)
   auto fill = [&](int kt) __attribute__((always_inline)) {
     char* st = smem + (kt & 1) * STAGE;
 #pragma unroll
@@ -49,15 +73,15 @@ __global__ void __launch_bounds__(SELF_ATTN_WAVES * 64, 4) self_attn_fused_kerne
       const int g = wid + SELF_ATTN_WAVES * n, ks = g >> 2, rg = g & 3;
       const int r = rg * 8 + rsub;
       const int key = min(kt * 32 + r, a.L - 1);
-      const char* src = a.qk + ((long long)b * a.L + key) * ROW + (long long)(16 + h * 4 + ks) * 128 + ((cpos ^ ((r >> 1) & 7)) << 4);
+      const char* src = a.qkv + ((long long)b * a.L + key) * ROW + (long long)(16 + h * 4 + ks) * 128 + ((cpos ^ ((r >> 1) & 7)) << 4);
       __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(st + ks * 4096 + rg * 1024), 16, 0, 0);
     }
 #pragma unroll
     for (int n = 0; n < 2; ++n) {
-      const int rg = wid + SELF_ATTN_WAVES * n;
-      const int r = rg * 8 + rsub;
-      const char* src = a.vts + ((long long)b * CFD_D + h * 128 + r) * ((long long)a.Lv * 4) + (long long)kt * 128 + ((cpos ^ ((r >> 1) & 7)) << 4);
-      __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(st + VOFF + rg * 1024), 16, 0, 0);
+      const int g = wid + SELF_ATTN_WAVES * n, ks = g >> 2, rg = g & 3;
+      const int key = min(kt * 32 + rg * 8 + vr, a.L - 1);
+      const char* src = a.qkv + ((long long)b * a.L + key) * ROW + (long long)(32 + h * 4 + ks) * 128 + (vch << 4);
+      __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(st + VOFF + g * 1024), 16, 0, 0);
     }
   };
   fill(0);
@@ -65,7 +89,7 @@ __global__ void __launch_bounds__(SELF_ATTN_WAVES * 64, 4) self_attn_fused_kerne
   // Q fragments (B operand): lane holds d = 32*ks + 8*q4 .. +7 of its query
   spx8 qh[4], ql[4];
   {
-    const char* qp = a.qk + ((long long)b * a.L + qc) * ROW + (long long)(h * 4) * 128 + q4 * 16;
+    const char* qp = a.qkv + ((long long)b * a.L + qc) * ROW + (long long)(h * 4) * 128 + q4 * 16;
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
       qh[ks] = *reinterpret_cast<const spx8*>(qp + ks * 128);
@@ -132,7 +156,7 @@ __global__ void __launch_bounds__(SELF_ATTN_WAVES * 64, 4) self_attn_fused_kerne
 #pragma unroll
       for (int f = 0; f < 8; ++f) { o[f][0] *= scale; o[f][1] *= scale; o[f][2] *= scale; o[f][3] *= scale; }
     }
-    // O^T += V^T P^T : P fragments come straight out of the S registers (k-slot order matches perm32)
+    // O^T += V^T P^T : P fragments come straight out of the S registers; the V^T fragments in the matching k-slot order by transposed reads
     spx8 ph, pl;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
@@ -141,20 +165,21 @@ __global__ void __launch_bounds__(SELF_ATTN_WAVES * 64, 4) self_attn_fused_kerne
       ph[e] = hi;
       pl[e] = lo;
     }
+    // lane (group q4, q = l15 >> 2, p = l15 & 3) addresses key 4 q4 + q (piece q4 >> 1, slot r = 4 (q4 & 1) + q), features 4p .. 4p+3 of the 16
 #pragma unroll
     for (int f = 0; f < 8; ++f) {
-      const char* vp = st + VOFF + (f * 16 + l15) * 128;
-      const spx8 xh = *reinterpret_cast<const spx8*>(vp + ((q4 ^ sw) << 4));
-      const spx8 xl = *reinterpret_cast<const spx8*>(vp + (((4 + q4) ^ sw) << 4));
+      const char* vp = st + VOFF + (f >> 1) * 4096 + (q4 >> 1) * 1024 + ((q4 & 1) * 4 + (l15 >> 2)) * 64 + (((f & 1) ^ (q4 & 1)) << 5) + (l15 & 3) * 8;
+      const spx8 xh = sa_tr_frag(vp);
+      const spx8 xl = sa_tr_frag(vp + 512);
       o[f] = SP_MFMA(xl, ph, o[f], 0, 0, 0);
       o[f] = SP_MFMA(xh, pl, o[f], 0, 0, 0);
       o[f] = SP_MFMA(xh, ph, o[f], 0, 0, 0);
     }
   }
   // Epilogue.  The MFMA layout gives a lane 4 features of one query: 8-byte stores in 32-byte row segments.  Each
-  // wave re-lays its 16 x 128 block through a private LDS strip instead (the K / V^T tiles are free now) and stores
+  // wave re-lays its 16 x 128 block through a private LDS strip instead (the K / V tiles are free now) and stores
   // 8 consecutive features per lane, 64 features per pass: 8 lanes cover a query, 8 queries per instruction.
-  __syncthreads();   // every wave is done with the last K / V^T tile
+  __syncthreads();   // every wave is done with the last K / V tile
   {
     constexpr int RS = 64 * 4 + 16;   // strip row stride in bytes (+16: conflict-free 16-byte writes); 64 features per pass
     char* strip = smem + wid * (16 * RS);

@@ -98,7 +98,7 @@ extern "C" void cfd_destroy(cfd_handle c) {
   }
   c->pic_s.release(); c->pic_part.release(); c->pic_err.release();
   for (auto& l : c->lw) {
-    DBuf* lb[] = {&l.wqk_f, &l.wv_f, &l.w1_f, &l.ln_cd, &l.wqk_sp, &l.bqk, &l.wv_sp, &l.wo_sp, &l.bo2, &l.wtb1_sp, &l.wtb2_sp, &l.w1_sp, &l.w2_sp, &l.cross_bias};
+    DBuf* lb[] = {&l.wqk_f, &l.wv_f, &l.w1_f, &l.ln_cd, &l.wqkv_sp, &l.bqk, &l.wo_sp, &l.bo2, &l.wtb1_sp, &l.wtb2_sp, &l.w1_sp, &l.w2_sp, &l.cross_bias};
     for (DBuf* b : lb) b->release();
   }
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -234,11 +234,15 @@ extern "C" int cfd_finalize_weights(cfd_handle c) {
     hipLaunchKernelGGL(scale_copy_kernel<>, grid1((long long)D * D), blk, 0, 0, ipw, tf, (long long)D * D, qs);
     hipLaunchKernelGGL(scale_copy_kernel<>, grid1((long long)D * D), blk, 0, 0, ipw + (size_t)D * D, tf + (size_t)D * D,
                        (long long)D * D, 1.0f);
-    CHK(to_sp(c, tf, 2 * D, D, w.wqk_sp));
-    CHK(w.bqk.ensure(2 * D * 4));
+    // [Wq; Wk; Wv] as ONE split-pair matrix of 1536 rows: the tile kernels' q | k | v product reads all of it, the grouped launch of
+    // 16-token batch rows and the row-tile path its first 1024 and last 512 rows.  bqk: the q | k bias followed by 512 zeros (the value
+    // bias is folded into the out-projection's, below).
+    HIPCHK(hipMemcpy(tf + (size_t)2 * D * D, ipw + (size_t)2 * D * D, (size_t)D * D * 4, hipMemcpyDeviceToDevice));
+    CHK(to_sp(c, tf, 3 * D, D, w.wqkv_sp));
+    CHK(w.bqk.ensure(3 * D * 4));
+    HIPCHK(hipMemset(w.bqk.as<float>() + 2 * D, 0, D * 4));
     hipLaunchKernelGGL(scale_copy_kernel<>, grid1(D), blk, 0, 0, ipb, w.bqk.as<float>(), (long long)D, qs);
     hipLaunchKernelGGL(scale_copy_kernel<>, grid1(D), blk, 0, 0, ipb + D, w.bqk.as<float>() + D, (long long)D, 1.0f);
-    CHK(to_sp(c, ipw + (size_t)2 * D * D, D, D, w.wv_sp));
     CHK(to_sp(c, ow, D, D, w.wo_sp));
     // softmax rows sum to one, so the value bias passes straight through: bo' = bo + Wo bv
     CHK(w.bo2.ensure(D * 4));

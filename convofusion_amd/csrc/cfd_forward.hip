@@ -121,13 +121,13 @@ int enqueue_rows_rt(Ctx* c, hipStream_t st, const RtSave* sv) {
   xa.att_step = p.att_nb > 0 ? c->w->d_step.as<int>() : nullptr;
   for (int l = 0; l < nl; ++l) {
     const LayerW& w = c->lw[l];
-    char* qk = sv ? sv->qk[l] : c->w->qk_sp.as<char>();
+    char* qk = sv ? sv->qk[l] : c->w->qkv_sp.as<char>();
     char* vt = sv ? sv->vt[l] : c->w->rt_vt.as<char>();
     // ---- a. self attention: x += Wo softmax(q k^T) v                         (cross_attention.py:568-572)
     {
       RtGemmArgs a = base;   // norm1 + q | k | v^T projections
       a.x = X(l, 0);
-      a.g = w.ln1g; a.b = w.ln1b; a.w = w.wqk_sp.as<char>(); a.w2 = w.wv_sp.as<char>(); a.nfb_qk = 2 * CFD_D / 16;
+      a.g = w.ln1g; a.b = w.ln1b; a.w = w.wqkv_sp.as<char>(); a.w2 = w.wqkv_sp.as<char>() + (size_t)2 * CFD_D * CFD_D * 4; a.nfb_qk = 2 * CFD_D / 16;
       a.bias = w.bqk.as<float>(); a.o_sp = qk; a.ld_o = 2 * CFD_D * 4; a.vt = vt;
       RT_LAUNCH(CFD_PROF_GEMM_TOKEN, RT_PRO_LN, RT_EPI_QKV, 512, CFD_D / 32, 3, 3 * CFD_D, a);
     }
@@ -328,24 +328,21 @@ int enqueue_rows(Ctx* c, hipStream_t st, int row0, int Be) {
     if (!h_ready) CHK(ln(w.ln1g, w.ln1b, 0, 0, c->w->h_sp.as<char>(), Ma));
     h_ready = false;
     bool qkv_one_launch = false;
-    const int Lv = (L + 31) / 32 * 32;   // (whole 32-key blocks: at L = 16 a 64-key pitch made the v^T product twice the work of the q | k one)
     {
-      // q (pre-scaled) and k, token-major ...
+      // q (pre-scaled), k and v, token-major, in ONE product against [Wq; Wk; Wv] (cfd_finalize_weights): qkv_sp [M][1536], the 12 column
+      // tiles of a token panel consecutive on one XCD (gemm_sp_body's block order), so h_sp is fetched once.  The bias covers q | k; its
+      // last 512 entries are zeros (the value bias is folded into the out-projection's).
       GemmArgs a = gemm_args();
-      a.X[0] = w.wqk_sp.as<char>(); a.ldx[0] = ROWB; a.I[0] = 2 * CFD_D; a.Iclamp[0] = 2 * CFD_D; a.kt[0] = CFD_D / 32;
+      a.X[0] = w.wqkv_sp.as<char>(); a.ldx[0] = ROWB; a.I[0] = 3 * CFD_D; a.Iclamp[0] = 3 * CFD_D; a.kt[0] = CFD_D / 32;
       a.Y = c->w->h_sp.as<char>(); a.ldy = ROWB; a.J = (int)Ma; a.Jclamp = (int)Ma;
-      EpiSplit e{c->w->qk_sp.as<char>(), 2 * ROWB, 0, 0, w.bqk.as<float>(), 0, 0};
-      // ... and v^T per batch row: vts[b][f][l] (keys in P-fragment order for the fused kernel)
-      GemmArgs av = gemm_args();
-      av.X[0] = c->w->h_sp.as<char>(); av.ldx[0] = ROWB; av.xbs[0] = (long long)L * ROWB; av.I[0] = Lv; av.Iclamp[0] = L; av.kt[0] = CFD_D / 32;
-      av.Y = w.wv_sp.as<char>(); av.ldy = ROWB; av.J = CFD_D; av.Jclamp = CFD_D;
-      EpiSplit ev{c->w->vts_sp.as<char>(), (long long)Lv * 4, (long long)CFD_D * Lv * 4, 0, nullptr, 0, 1};
+      EpiSplit e{c->w->qkv_sp.as<char>(), 3 * ROWB, 0, 0, w.bqk.as<float>(), 0, 0};
       if (L == 16) {
-        // batch rows of exactly 16 tokens: both in ONE grouped launch, the value projection stored transposed by the epilogue (EpiQkvT)
+        // batch rows of exactly 16 tokens: q | k and v in ONE grouped launch, the value projection stored transposed by the epilogue (EpiQkvT)
         GemmArgs ag = a;
         ag.nslot = 2;
-        ag.X[1] = w.wv_sp.as<char>(); ag.ldx[1] = ROWB; ag.I[1] = CFD_D; ag.Iclamp[1] = CFD_D; ag.kt[1] = CFD_D / 32;
-        EpiQkvT eg{c->w->qk_sp.as<char>(), 2 * ROWB, w.bqk.as<float>(), c->w->vts_sp.as<char>(), 1};
+        ag.I[0] = 2 * CFD_D; ag.Iclamp[0] = 2 * CFD_D;
+        ag.X[1] = w.wqkv_sp.as<char>() + 2 * CFD_D * ROWB; ag.ldx[1] = ROWB; ag.I[1] = CFD_D; ag.Iclamp[1] = CFD_D; ag.kt[1] = CFD_D / 32;
+        EpiQkvT eg{c->w->qkv_sp.as<char>(), 2 * ROWB, w.bqk.as<float>(), c->w->vts_sp.as<char>(), 1};
         if (h_raw) {   // (layers 1..: the previous layer's second FFN product left raw rows + statistics)
           EpiLn<EpiQkvT> el;
           static_cast<EpiQkvT&>(el) = eg;
@@ -358,18 +355,17 @@ int enqueue_rows(Ctx* c, hipStream_t st, int row0, int Be) {
         qkv_one_launch = true;
       } else {
       CHK((run_gemm<MODE_PLAIN>(c, CFD_PROF_GEMM_TOKEN, a, e, 1, 1, st)));
-      CHK((run_gemm<MODE_PLAIN>(c, CFD_PROF_GEMM_TOKEN, av, ev, Ba, 1, st)));
       }
     }
     if (qkv_one_launch) {
       // one query tile and one key tile per (row, head): the row-tile path's attention core (4 waves that all compute; V^T in natural key
       // order, which EpiQkvT wrote) instead of the flash kernel's 8-wave workgroup with one busy wave
-      RtSelfArgs a{c->w->qk_sp.as<char>(), c->w->vts_sp.as<char>(), c->w->o_sp.as<char>(), L, 1};
+      RtSelfArgs a{c->w->qkv_sp.as<char>(), c->w->vts_sp.as<char>(), c->w->o_sp.as<char>(), L, 1};
       Bracket br(c, CFD_PROF_GEMM_ATTN, st);
       hipLaunchKernelGGL(rt_selfattn_kernel<>, dim3(CFD_NHEAD, Ba), dim3(256), 40 * 1024, st, a);
       HIPCHK(hipGetLastError());
     } else {
-      SelfAttnArgs a{c->w->qk_sp.as<char>(), c->w->vts_sp.as<char>(), c->w->o_sp.as<char>(), L, Lv};
+      SelfAttnArgs a{c->w->qkv_sp.as<char>(), c->w->o_sp.as<char>(), 3 * ROWB, L};
       Bracket br(c, CFD_PROF_GEMM_ATTN, st);
       hipLaunchKernelGGL(self_attn_fused_kernel<>, dim3((L + SELF_ATTN_WAVES * 16 - 1) / (SELF_ATTN_WAVES * 16), CFD_NHEAD, Ba), dim3(SELF_ATTN_WAVES * 64), 65536, st, a);
       HIPCHK(hipGetLastError());

@@ -58,7 +58,7 @@ struct DBuf {
 };
 
 struct LayerW {
-  DBuf wqk_sp, bqk, wv_sp, wo_sp, bo2, wtb1_sp, wtb2_sp, w1_sp, w2_sp, cross_bias;
+  DBuf wqkv_sp, bqk, wo_sp, bo2, wtb1_sp, wtb2_sp, w1_sp, w2_sp, cross_bias;
   // the LayerNorm fold's operands (gemm_sp.hpp EpiLn): W' = W diag(gamma) as split pairs for q | k, v and FFN1, and per output feature
   // c = W' 1, d = W beta in ln_cd: [c_qk 1024][d_qk 1024][c_v 512][d_v 512][c_1 1024][d_1 1024]
   DBuf wqk_f, wv_f, w1_f, ln_cd;
@@ -141,7 +141,9 @@ struct WegRtState {
 // One problem's device workspace: everything setup_problem / prepare_static_memside allocate and the launches of a forward touch.
 struct Work {
   Problem pb;
-  DBuf x, h_sp, qk_sp, vts_sp, ssc, sp_sp, o_sp, u_sp, sc, p_sp, eps, sample_sp;
+  // qkv_sp: SP rows of q | k | v (1536 columns) on the tile kernels at L != 16; q | k (1024 columns) for batch rows of 16 tokens and on the
+  // row-tile path, whose V^T per batch row lives in vts_sp / rt_vt
+  DBuf x, h_sp, qkv_sp, vts_sp, ssc, sp_sp, o_sp, u_sp, sc, p_sp, eps, sample_sp;
   DBuf ln_stat;                 // LayerNorm fold: per row 16 slots of (mean, M2) written by the producing residual product (EpiResidStat)
   DBuf n_sp[CFD_NMEM], kall_sp[CFD_NMEM], cb[CFD_NMEM], vt_all[CFD_NMEM];
   DBuf temb_tab, h1_tab, ss_tab, trows, iota, long_rows, short_rows, zero_mask;
@@ -172,7 +174,7 @@ struct Work {
   const float* now_kb[CFD_NMEM] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   const float* now_vb[CFD_NMEM] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   void release() {
-    DBuf* all[] = {&x, &h_sp, &qk_sp, &vts_sp, &ssc, &sp_sp, &o_sp, &u_sp, &sc, &p_sp, &eps, &sample_sp, &temb_tab, &h1_tab, &ss_tab, &trows, &iota,
+    DBuf* all[] = {&x, &h_sp, &qkv_sp, &vts_sp, &ssc, &sp_sp, &o_sp, &u_sp, &sc, &p_sp, &eps, &sample_sp, &temb_tab, &h1_tab, &ss_tab, &trows, &iota,
                    &long_rows, &short_rows, &zero_mask, &ln_stat, &b_tab, &b_sp, &bsq, &zeros512, &xa_wgs, &xa_segs, &xa_stamps, &xa0_wgs_a, &xa0_segs_a, &xa0_wgs_b, &xa0_segs_b, &xa_dedup, &xa_one_va, &xa_att_raw, &xa_att_mc, &xa_att_fin, &xa_att_desc, &d_step, &rt_vt, &rt_cur};
     for (DBuf* b : all) b->release();
     for (int j = 0; j < CFD_NMEM; ++j) {

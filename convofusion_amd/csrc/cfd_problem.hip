@@ -398,8 +398,9 @@ int setup_problem(Ctx* c, int Be, int L, const cfd_memory mem[CFD_NMEM], float* 
   const int nl = c->nl;
   CHK(c->w->x.ensure((size_t)M * CFD_D * 4));
   CHK(c->w->h_sp.ensure((size_t)M * CFD_D * 4));
-  CHK(c->w->qk_sp.ensure((size_t)M * 2 * CFD_D * 4));
-  CHK(c->w->vts_sp.ensure((size_t)Be * CFD_D * ((L + 63) / 64 * 64) * 4));
+  // q | k | v rows of the tile kernels' one projection launch; batch rows of 16 tokens and the row-tile path keep q | k rows + V^T per batch row
+  CHK(c->w->qkv_sp.ensure((size_t)M * (L == 16 ? 2 : 3) * CFD_D * 4));
+  if (L == 16) CHK(c->w->vts_sp.ensure((size_t)Be * CFD_D * 64 * 4));
   CHK(c->w->ssc.ensure((size_t)Be * CFD_NHEAD * L * p.Lp * 4));
   CHK(c->w->sp_sp.ensure((size_t)Be * CFD_NHEAD * L * p.Lp * 4));
   CHK(c->w->o_sp.ensure((size_t)M * CFD_D * 4));

@@ -170,10 +170,11 @@ def roofline():
     MiB = 2.0**20
     comp = {"EpiResid N=512 (Wo, TB1, TB2: K=512; FFN2: K=1024)": {"read_MiB": "%.1f (K=512) / %.1f (K=1024)" % ((M * 512 * 4 * 2 + 512 * 512 * 4) / MiB, (M * 1024 * 4 + M * 512 * 4 + 512 * 1024 * 4) / MiB),
                                                                    "write_MiB": round(M * 512 * 4 / MiB, 1)},
-            "EpiSplit N=1024 (q|k, FFN1)": {"read_MiB": round((M * 512 * 4 + 1024 * 512 * 4) / MiB, 1), "write_MiB": round(M * 1024 * 4 / MiB, 1)},
-            "EpiSplit N=512 (v^T)": {"read_MiB": round((M * 512 * 4 + 512 * 512 * 4) / MiB, 1), "write_MiB": round(M * 512 * 4 / MiB, 1)},
+            "EpiSplit N=1024 (FFN1; q|k in the profiles up to r06)": {"read_MiB": round((M * 512 * 4 + 1024 * 512 * 4) / MiB, 1), "write_MiB": round(M * 1024 * 4 / MiB, 1)},
+            "EpiSplit N=1536 (q|k|v, one launch)": {"read_MiB": round((M * 512 * 4 + 1536 * 512 * 4) / MiB, 1), "write_MiB": round(M * 1536 * 4 / MiB, 1)},
+            "EpiSplit N=512 (v^T; profiles up to r06 and the parent's)": {"read_MiB": round((M * 512 * 4 + 512 * 512 * 4) / MiB, 1), "write_MiB": round(M * 512 * 4 / MiB, 1)},
             "xattn_fused_kernel": {"read_MiB": "x rows twice (LayerNorm2 + flush) %.1f + K / V^T tiles once per XCD that streams them" % (2 * M * 512 * 4 / MiB), "write_MiB": round(M * 512 * 4 / MiB, 1)},
-            "self_attn_fused_kernel": {"read_MiB": round((M * 1024 * 4 + M * 512 * 4) / MiB, 1), "write_MiB": round(M * 512 * 4 / MiB, 1)},
+            "self_attn_fused_kernel": {"read_MiB": round(M * 1536 * 4 / MiB, 1), "write_MiB": round(M * 512 * 4 / MiB, 1)},
             "ln_rows_kernel": {"read_MiB": round(M * 512 * 4 / MiB, 1), "write_MiB": round(M * 512 * 4 / MiB, 1)}}
     kc = d.get("kernel_classes", {})
     classes = {}

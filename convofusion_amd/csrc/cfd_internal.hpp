@@ -404,12 +404,14 @@ static inline GemmArgs gemm_args() {
   return a;
 }
 
-#define LAUNCH(cls, kernel, grid, block, st, ...)                                              \
+#define LAUNCH(cls, kernel, grid, block, st, ...) LAUNCH_AS(cls, #kernel, kernel, grid, block, st, __VA_ARGS__)
+// (name: what a failed launch is called in the error -- for a kernel chosen through a template, whose expression names no instance)
+#define LAUNCH_AS(cls, name, kernel, grid, block, st, ...)                                     \
   do {                                                                                         \
     Bracket _br(c, cls, st);                                                                   \
     hipLaunchKernelGGL(kernel, grid, block, 0, st, __VA_ARGS__);                               \
     hipError_t _e = hipGetLastError();                                                         \
-    if (_e != hipSuccess) return fail(CFD_E_HIP, "%s launch failed: %s", #kernel, hipGetErrorString(_e)); \
+    if (_e != hipSuccess) return fail(CFD_E_HIP, "%s launch failed: %s", name, hipGetErrorString(_e)); \
   } while (0)
 
 // ---- small kernels of the host code itself (templates: each unit instantiates what it launches) -----------

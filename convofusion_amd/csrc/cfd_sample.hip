@@ -101,12 +101,31 @@ static int step_coefficients(int kind, const float* ac, int T, int n_inf, const 
   return CFD_OK;
 }
 
-static void (*const cfg_step_kernel_weighted)(const CfgStepArgsW) = cfg_step_kernel<0, true>;   // (one macro argument for LAUNCH)
-static void (*const cfg_step_kernel_traj)(const CfgStepArgsT<CfgStepArgs>) = cfg_step_kernel<0, false, true>;
-static void (*const cfg_step_kernel_weighted_traj)(const CfgStepArgsT<CfgStepArgsW>) = cfg_step_kernel<0, true, true>;
-// prediction_type 1 ("sample"): the combine is x0.  No trajectory instance: inversion refuses the type (check_run_args)
-static void (*const cfg_step_kernel_x0)(const CfgStepArgs) = cfg_step_kernel<0, false, false, 1>;
-static void (*const cfg_step_kernel_weighted_x0)(const CfgStepArgsW) = cfg_step_kernel<0, true, false, 1>;
+// f(PRED) for the stand-alone step kernels: prediction_type 1 ("sample") is PRED 1, everything else PRED 0 (the callers refuse other values)
+template <class F>
+static void with_pred(int prediction_type, F&& f) { prediction_type == 1 ? f(std::integral_constant<int, 1>{}) : f(std::integral_constant<int, 0>{}); }
+
+// An instance of cfg_step_kernel and its arguments, cut from the weighted instance's (and the trajectory ring)
+template <bool WTAB, bool TRAJ, int PRED>
+struct StepInst {
+  static constexpr auto kernel = cfg_step_kernel<0, WTAB, TRAJ, PRED>;
+  static CfgStepArgsOf<WTAB, TRAJ> args(const CfgStepArgsW& cw, float* traj) {
+    CfgStepArgsOf<WTAB, TRAJ> a;
+    static_cast<CfgStepArgsOf<WTAB, false>&>(a) = cw;   // (the default instance takes its CfgStepArgs part)
+    if constexpr (TRAJ) a.traj = traj;
+    return a;
+  }
+};
+// The one place that maps (weighted, trajectory, prediction_type) to an instance of cfg_step_kernel, f(StepInst<>{}, its name in a launch
+// error): six of them -- prediction_type 1 ("sample": the combine is x0) has no trajectory instance, inversion refuses the type
+// (check_run_args); traj: an inversion run recording its trajectory, the step also stores into slot *d_step + 1.
+template <class F>
+static int with_step_inst(bool weighted, bool traj, int prediction_type, F&& f) {
+  if (prediction_type == 1)
+    return weighted ? f(StepInst<true, false, 1>{}, "cfg_step_kernel_weighted_x0") : f(StepInst<false, false, 1>{}, "cfg_step_kernel_x0");
+  if (traj) return weighted ? f(StepInst<true, true, 0>{}, "cfg_step_kernel_weighted_traj") : f(StepInst<false, true, 0>{}, "cfg_step_kernel_traj");
+  return weighted ? f(StepInst<true, false, 0>{}, "cfg_step_kernel_weighted") : f(StepInst<false, false, 0>{}, "cfg_step_kernel<>");
+}
 
 // The instances of begin_step_kernel / inpaint_now_kernel that take the argument struct Args (rows.hpp: BeginArgsOf, the other way round)
 template <class Args>
@@ -169,14 +188,6 @@ static int with_begin_args(Ctx* c, F&& f) {
   return f(default_begin_args(c));                   // the first preseq_len tokens, if the run has a preseq
 }
 
-template <class Args>   // the trajectory instance's arguments: those of the instance without, and the ring
-static CfgStepArgsT<Args> with_traj(const Args& a, float* traj) {
-  CfgStepArgsT<Args> t;
-  static_cast<Args&>(t) = a;
-  t.traj = traj;
-  return t;
-}
-
 static int enqueue_loop_iteration(Ctx* c, hipStream_t st) {
   const cfd_sample_args& s = c->sargs;
   const RunMode& m = c->run;
@@ -187,7 +198,7 @@ static int enqueue_loop_iteration(Ctx* c, hipStream_t st) {
     return (int)CFD_OK;
   }));
   CHK(enqueue_denoise(c, st));
-  CfgStepArgsW cw;   // (the default instance takes its CfgStepArgs part)
+  CfgStepArgsW cw;
   memset(&cw, 0, sizeof(cw));
   cw.eps = c->w->eps.as<float>(); cw.latents = c->latents.as<float>(); cw.B = s.B; cw.L = s.L; cw.G = s.G;
   for (int k = 0; k < 8; ++k) { cw.w[k] = s.guidance_weight[k]; cw.pos[k] = c->chunk_pos[k]; }
@@ -199,17 +210,12 @@ static int enqueue_loop_iteration(Ctx* c, hipStream_t st) {
     for (int k = 0; k < 8; ++k) cw.pos[k] = c->wpos[k];
     cw.wtab = c->wtab.as<float>();
   }
-  const CfgStepArgs& ca = cw;
   const long long n4 = (long long)s.B * s.L * CFD_LAT / 4;
   const dim3 grid((unsigned)std::min<long long>((n4 + 255) / 256, 256)), block(256);
-  // (m.traj: an inversion run recording its trajectory: the step also stores into slot *d_step + 1)
-  if (s.prediction_type == 1 && m.weighted) LAUNCH(CFD_PROF_OTHER, cfg_step_kernel_weighted_x0, grid, block, st, cw);
-  else if (s.prediction_type == 1) LAUNCH(CFD_PROF_OTHER, cfg_step_kernel_x0, grid, block, st, ca);
-  else if (m.weighted && m.traj) LAUNCH(CFD_PROF_OTHER, cfg_step_kernel_weighted_traj, grid, block, st, with_traj(cw, m.traj));
-  else if (m.weighted) LAUNCH(CFD_PROF_OTHER, cfg_step_kernel_weighted, grid, block, st, cw);
-  else if (m.traj) LAUNCH(CFD_PROF_OTHER, cfg_step_kernel_traj, grid, block, st, with_traj(ca, m.traj));
-  else LAUNCH(CFD_PROF_OTHER, cfg_step_kernel<>, grid, block, st, ca);
-  return CFD_OK;
+  return with_step_inst(m.weighted, m.traj != nullptr, s.prediction_type, [&](auto inst, const char* name) {
+    LAUNCH_AS(CFD_PROF_OTHER, name, inst.kernel, grid, block, st, inst.args(cw, m.traj));
+    return (int)CFD_OK;
+  });
 }
 
 // A memory's row map on the host (`rows` = G * B entries): the caller's map downloaded, or the identity for a memory without one (it then
@@ -322,10 +328,10 @@ static int upload_keep_mask(Ctx* c, const std::vector<uint8_t>& hkeep, size_t n,
 // What an opener adds to cfd_sample_begin's run; every field is optional.  weights (with prune / chunks_evaluated as in
 // cfd_sample_begin_weighted; NULL: the default guidance weights, chunks_evaluated then gets the run's G on success), edit, traj (the
 // inversion's trajectory ring), anchor, tie, replay (a DDPM noise space: the anchored instance over its trajectory, a start at its
-// first_iteration).  A new run kind touches four places: its field here, its RunMode field (cfd_internal.hpp), its block in
-// init_latents_and_kind, which turns the one into the other, and -- if it overwrites tokens at the start of an iteration -- its row in
-// with_begin_args.  What it refuses goes into its opener, or into check_run_args where it depends on the other fields; a host table it
-// brings is fetched next to fetch_keep_mask / fetch_tie_table.
+// first_iteration).  A new run kind touches: its field here, its RunMode field (cfd_internal.hpp), its block in init_latents_and_kind,
+// which turns the one into the other, and -- if it overwrites tokens at the start of an iteration -- its row in with_begin_args and its
+// branch in BOTH begin_step_kernel and inpaint_now_kernel (rows.hpp).  What it refuses goes into its opener, or into
+// check_run_args where it depends on the other fields; a host table it brings is fetched next to fetch_keep_mask / fetch_tie_table.
 struct BeginExt {
   const char* opener = "cfd_sample_begin";
   const float* weights = nullptr;
@@ -993,6 +999,41 @@ static int picard_stride(const float* err, int B, int p, int i0, const StepCoef*
   return s;
 }
 
+// The launches of a Picard sweep, once for cfd_sample_parallel and the developer hook cfd_test_picard_sweep: the ring, the sizes, the
+// grids, the kernels' argument structs and the choice of the step instance, one function per stage.
+struct PicardSweep {
+  Ctx* c;
+  hipStream_t st;
+  PicardStepArgs sa;     // ring, B, L, G, J: set here; eps / s / coef / g / noise / seed / utt0: the caller's, before step()
+  int nblk;              // the scan's workgroups per utterance
+  PicardSweep(Ctx* c_, hipStream_t st_, const PicardRing& ring, int B, int L, int G, int J) : c(c_), st(st_), nblk((L * (CFD_LAT / 4) + 255) / 256) {
+    memset(&sa, 0, sizeof(sa));
+    sa.ring = ring; sa.B = B; sa.L = L; sa.G = G; sa.J = J;
+  }
+  dim3 grid(int levels) const { return dim3((unsigned)((sa.ring.chunk / 8 * levels + 255) / 256)); }   // one thread = 8 elements of a level
+  size_t part_bytes() const { return (size_t)sa.J * sa.B * nblk * 4; }
+  int fill(int src, int lo, int hi) {   // X(i) = X(src) for the iterations lo .. hi (none: no launch)
+    if (hi >= lo) LAUNCH(CFD_PROF_OTHER, picard_fill_kernel<>, grid(hi - lo + 1), dim3(256), st, sa.ring, src, lo, hi);
+    return CFD_OK;
+  }
+  int load(int base, char* sample_sp) {
+    LAUNCH(CFD_PROF_OTHER, picard_load_kernel<>, grid(sa.J), dim3(256), st, PicardLoadArgs{sa.ring, sample_sp, sa.B, sa.L, sa.G, base, sa.J});
+    return CFD_OK;
+  }
+  int step(int base, int off) {   // the weighted instance where the combine has a table
+    sa.base = base; sa.off = off;
+    if (sa.g.wtab) LAUNCH(CFD_PROF_OTHER, picard_step_kernel_weighted, grid(sa.J), dim3(256), st, sa);
+    else LAUNCH(CFD_PROF_OTHER, picard_step_kernel<>, grid(sa.J), dim3(256), st, sa);
+    return CFD_OK;
+  }
+  int scan_err(int base, int off, float* part, float* err) {
+    LAUNCH(CFD_PROF_OTHER, picard_scan_kernel<>, dim3((unsigned)nblk, (unsigned)sa.B), dim3(256), st,
+           PicardScanArgs{sa.s, sa.ring, part, sa.L, base, off, sa.J});
+    LAUNCH(CFD_PROF_OTHER, picard_err_kernel<>, dim3((unsigned)((sa.J * sa.B + 255) / 256)), dim3(256), st, part, err, sa.J, sa.B, nblk, sa.J - off);
+    return CFD_OK;
+  }
+};
+
 // ---- parallel-in-time DDPM sampling: Picard sweeps over level batches (cfdenoise.h: cfd_sample_parallel) ---------------------------
 extern "C" int cfd_sample_parallel(cfd_handle c, const cfd_sample_args* args, const cfd_parallel_args* par, cfd_parallel_stats* stats,
                                    void* stream) {
@@ -1018,45 +1059,19 @@ extern "C" int cfd_sample_parallel(cfd_handle c, const cfd_sample_args* args, co
     CHK(c->latents.ensure((size_t)ring.slots * chunk * 4));
     ring.x = c->latents.as<float>();
   }
-  const int nblk = (L * (CFD_LAT / 4) + 255) / 256;
+  PicardSweep sw(c, st, ring, B, L, Ge, J);
   DBuf &sbuf = c->pic_s, &part = c->pic_part, &err = c->pic_err;
   CHK(sbuf.ensure((size_t)J * chunk * 4));
-  CHK(part.ensure((size_t)J * B * nblk * 4));
+  CHK(part.ensure(sw.part_bytes()));
   CHK(err.ensure((size_t)J * B * 4));
   std::vector<float> herr((size_t)J * B);
   if (s.init_latents) HIPCHK(hipMemcpyAsync(ring.at(0), s.init_latents, (size_t)chunk * 4, hipMemcpyDeviceToDevice, st));
   else CHK(enqueue_philox_fill(ring.at(0), B, L * CFD_LAT, (uint64_t)s.seed, 0u, s.first_utterance, 1u, 1.0f, st));
-  const long long n8 = chunk / 8;
-  const dim3 block(256), grid_lv((unsigned)((n8 * J + 255) / 256));
-  auto fill = [&](int src, int lo, int hi) -> int {
-    if (hi < lo) return CFD_OK;
-    LAUNCH(CFD_PROF_OTHER, picard_fill_kernel<>, dim3((unsigned)((n8 * (hi - lo + 1) + 255) / 256)), block, st, ring, src, lo, hi);
-    return CFD_OK;
-  };
-  CHK(fill(0, 1, J));   // every latent of the first window starts from X(0)
-  PicardLoadArgs la{ring, c->w->sample_sp.as<char>(), B, L, Ge, 0, J};
-  PicardStepArgs sa;
-  memset(&sa, 0, sizeof(sa));
-  sa.eps = c->w->eps.as<float>(); sa.ring = ring; sa.s = sbuf.as<float>(); sa.coef = c->coef.as<StepCoef>();
-  sa.B = B; sa.L = L; sa.G = Ge; sa.J = J; sa.g = lb.g;
-  sa.noise = s.step_noise; sa.seed = s.seed; sa.utt0 = s.first_utterance;
-  PicardScanArgs ca{sbuf.as<float>(), ring, part.as<float>(), L, 0, 0, J};
+  CHK(sw.fill(0, 1, J));   // every latent of the first window starts from X(0)
+  sw.sa.eps = c->w->eps.as<float>(); sw.sa.s = sbuf.as<float>(); sw.sa.coef = c->coef.as<StepCoef>(); sw.sa.g = lb.g;
+  sw.sa.noise = s.step_noise; sw.sa.seed = s.seed; sw.sa.utt0 = s.first_utterance;
   const int max_sweeps = par->max_sweeps ? par->max_sweeps : N;
   int sweeps = 0;
-  auto sweep = [&](int base, int off) -> int {
-    pb.lv_i0 = la.base = sa.base = ca.base = base;
-    sa.off = ca.off = off;
-    LAUNCH(CFD_PROF_OTHER, picard_load_kernel<>, grid_lv, block, st, la);
-    CHK(enqueue_denoise(c, st));
-    if (lb.g.wtab) LAUNCH(CFD_PROF_OTHER, picard_step_kernel_weighted, grid_lv, block, st, sa);
-    else LAUNCH(CFD_PROF_OTHER, picard_step_kernel<>, grid_lv, block, st, sa);
-    LAUNCH(CFD_PROF_OTHER, picard_scan_kernel<>, dim3((unsigned)nblk, (unsigned)B), block, st, ca);
-    LAUNCH(CFD_PROF_OTHER, picard_err_kernel<>, dim3((unsigned)((J * B + 255) / 256)), block, st, part.as<float>(), err.as<float>(), J, B, nblk,
-           J - off);
-    HIPCHK(hipMemcpyAsync(herr.data(), err.p, herr.size() * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));   // the one wait of a sweep: the stride is decided on the host
-    return CFD_OK;
-  };
   for (int i0 = 0; i0 < N;) {
     if (sweeps >= max_sweeps) {
       (void)hipStreamSynchronize(st);
@@ -1066,13 +1081,19 @@ extern "C" int cfd_sample_parallel(cfd_handle c, const cfd_sample_args* args, co
                   max_sweeps, i0, N, (double)par->tolerance, J);
     }
     const int base = std::min(i0, N - J), off = i0 - base, p = J - off;   // (J <= N; p = min(J, N - i0))
-    CHK(sweep(base, off));
+    pb.lv_i0 = base;
+    CHK(sw.load(base, c->w->sample_sp.as<char>()));
+    CHK(enqueue_denoise(c, st));
+    CHK(sw.step(base, off));
+    CHK(sw.scan_err(base, off, part.as<float>(), err.as<float>()));
+    HIPCHK(hipMemcpyAsync(herr.data(), err.p, herr.size() * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));   // the one wait of a sweep: the stride is decided on the host
     const int stride = picard_stride(herr.data(), B, p, i0, coef.data(), par->tolerance, L);
     if (stats && stats->strides && sweeps < stats->strides_capacity) stats->strides[sweeps] = stride;
     sweeps += 1;
     // the levels that enter the window start from its last value, X(i0 + p)
     const int i1 = i0 + stride;
-    CHK(fill(i0 + p, i0 + p + 1, i1 + std::min(J, N - i1)));
+    CHK(sw.fill(i0 + p, i0 + p + 1, i1 + std::min(J, N - i1)));
     i0 = i1;
   }
   HIPCHK(hipMemcpyAsync(par->latents, ring.at(N), (size_t)chunk * 4, hipMemcpyDeviceToDevice, st));
@@ -1221,12 +1242,10 @@ extern "C" int cfd_scheduler_step_pred(cfd_handle c, int scheduler, const float*
   else ddim_coef(ac, T, n_inf, t, eta, set_alpha_to_one, &k);
   if (k.use_noise != 0.f && !noise) return fail(CFD_E_ARG, "this step adds noise: pass the N(0,1) draw");
   const dim3 grid((unsigned)((numel + 255) / 256)), block(256);
-  if (prediction_type == 1)
-    hipLaunchKernelGGL((sched_step_kernel<0, 1>), grid, block, 0, (hipStream_t)stream, model_output, noise, sample_inout, numel, k, scheduler,
-                       clip, pred_original_sample);
-  else
-    hipLaunchKernelGGL(sched_step_kernel<>, grid, block, 0, (hipStream_t)stream, model_output, noise, sample_inout, numel, k, scheduler, clip,
-                       pred_original_sample);
+  with_pred(prediction_type, [&](auto pred) {
+    hipLaunchKernelGGL((sched_step_kernel<0, decltype(pred)::value>), grid, block, 0, (hipStream_t)stream, model_output, noise, sample_inout, numel, k,
+                       scheduler, clip, pred_original_sample);
+  });
   HIPCHK(hipGetLastError());
   return CFD_OK;
 }
@@ -1252,10 +1271,10 @@ extern "C" int cfd_dpmsolver_step_pred(cfd_handle c, const float* ac, int T, int
   StepCoef k;
   dpmpp_coef(ac, t, prev_t, t_prev_model, &k);
   const dim3 grid((unsigned)((numel + 255) / 256)), block(256);
-  if (prediction_type == 1)
-    hipLaunchKernelGGL((dpmpp_step_kernel<0, 1>), grid, block, 0, (hipStream_t)stream, model_output, m_prev, sample_inout, x0_out, numel, k);
-  else
-    hipLaunchKernelGGL(dpmpp_step_kernel<>, grid, block, 0, (hipStream_t)stream, model_output, m_prev, sample_inout, x0_out, numel, k);
+  with_pred(prediction_type, [&](auto pred) {
+    hipLaunchKernelGGL((dpmpp_step_kernel<0, decltype(pred)::value>), grid, block, 0, (hipStream_t)stream, model_output, m_prev, sample_inout, x0_out,
+                       numel, k);
+  });
   HIPCHK(hipGetLastError());
   return CFD_OK;
 }
@@ -1272,8 +1291,8 @@ extern "C" int cfd_test_picard_stride(const float* err, int B, int p, int i0, co
 }
 
 // ---- developer hook: the kernels of a sweep around the forward, on the caller's predictions (include/cfdenoise_dev.h) ---------------
-// The instances, grids and blocks of cfd_sample_parallel's `fill` and `sweep` above; the partials start as NaN, so that a partial the
-// scan did not write shows in err.
+// The stages of cfd_sample_parallel's own PicardSweep, those the mask names; the partials start as NaN, so that a partial the scan did
+// not write shows in err.
 extern "C" int cfd_test_picard_sweep(cfd_handle c, const cfd_test_picard_args* t, void* stream) {
   if (!c || !t) return fail(CFD_E_ARG, "null argument");
   const int B = t->B, L = t->L, G = t->G, N = t->N, J = t->J, base = t->base, off = t->off;
@@ -1299,37 +1318,26 @@ extern "C" int cfd_test_picard_sweep(cfd_handle c, const cfd_test_picard_args* t
   if (do_scan && (!t->s || !t->err)) return fail(CFD_E_ARG, "cfd_test_picard_sweep: s or err is NULL");
   HIPCHK(hipSetDevice(c->cfg.device));
   hipStream_t st = (hipStream_t)stream;
-  const PicardRing ring{t->ring, t->slots, N, chunk};
-  const int nblk = (L * (CFD_LAT / 4) + 255) / 256;
-  const dim3 block(256), grid_lv((unsigned)((n8 * J + 255) / 256));
+  PicardSweep sw(c, st, PicardRing{t->ring, t->slots, N, chunk}, B, L, G, J);
   DBuf coef, part;
   auto run = [&]() -> int {
-    if (do_fill && t->fill_hi >= t->fill_lo)
-      LAUNCH(CFD_PROF_OTHER, picard_fill_kernel<>, dim3((unsigned)((n8 * (t->fill_hi - t->fill_lo + 1) + 255) / 256)), block, st, ring,
-             t->fill_src, t->fill_lo, t->fill_hi);
-    if (do_load) {
-      const PicardLoadArgs la{ring, (char*)t->sample_sp, B, L, G, base, J};
-      LAUNCH(CFD_PROF_OTHER, picard_load_kernel<>, grid_lv, block, st, la);
-    }
+    if (do_fill) CHK(sw.fill(t->fill_src, t->fill_lo, t->fill_hi));
+    if (do_load) CHK(sw.load(base, (char*)t->sample_sp));
+    sw.sa.s = t->s;
     if (do_step) {
       CHK(coef.ensure((size_t)N * sizeof(StepCoef)));
       HIPCHK(hipMemcpyAsync(coef.p, t->coef, (size_t)N * sizeof(StepCoef), hipMemcpyHostToDevice, st));
-      PicardStepArgs sa;
-      memset(&sa, 0, sizeof(sa));
-      sa.eps = t->eps; sa.ring = ring; sa.s = t->s; sa.coef = coef.as<StepCoef>();
-      sa.B = B; sa.L = L; sa.G = G; sa.base = base; sa.off = off; sa.J = J;
+      PicardStepArgs& sa = sw.sa;
+      sa.eps = t->eps; sa.coef = coef.as<StepCoef>();
       sa.g.Gc = t->Gc; sa.g.clip = t->clip; sa.g.wtab = t->wtab;
       for (int k = 0; k < 8; ++k) { sa.g.w[k] = t->w[k]; sa.g.pos[k] = k < t->Gc ? t->pos[k] : 0; }
       sa.noise = t->noise; sa.seed = t->seed; sa.utt0 = t->first_utterance;
-      if (t->wtab) LAUNCH(CFD_PROF_OTHER, picard_step_kernel_weighted, grid_lv, block, st, sa);
-      else LAUNCH(CFD_PROF_OTHER, picard_step_kernel<>, grid_lv, block, st, sa);
+      CHK(sw.step(base, off));
     }
     if (do_scan) {
-      CHK(part.ensure((size_t)J * B * nblk * 4));
-      HIPCHK(hipMemsetAsync(part.p, 0xFF, (size_t)J * B * nblk * 4, st));
-      const PicardScanArgs ca{t->s, ring, part.as<float>(), L, base, off, J};
-      LAUNCH(CFD_PROF_OTHER, picard_scan_kernel<>, dim3((unsigned)nblk, (unsigned)B), block, st, ca);
-      LAUNCH(CFD_PROF_OTHER, picard_err_kernel<>, dim3((unsigned)((J * B + 255) / 256)), block, st, part.as<float>(), t->err, J, B, nblk, J - off);
+      CHK(part.ensure(sw.part_bytes()));
+      HIPCHK(hipMemsetAsync(part.p, 0xFF, sw.part_bytes(), st));
+      CHK(sw.scan_err(base, off, part.as<float>(), t->err));
     }
     return CFD_OK;
   };

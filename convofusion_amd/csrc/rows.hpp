@@ -592,6 +592,12 @@ __device__ __forceinline__ float4 philox_normal4(uint64_t seed, uint32_t group, 
   return make_float4(r0 * cosf(t0), r0 * sinf(t0), r1 * cosf(t1), r1 * sinf(t1));
 }
 
+// 8 consecutive draws: groups g and g + 1
+__device__ __forceinline__ void philox_normal8(uint64_t seed, uint32_t g, uint32_t step, uint32_t utt, uint32_t stream, float z[8]) {
+  const float4 z0 = philox_normal4(seed, g, step, utt, stream), z1 = philox_normal4(seed, g + 1, step, utt, stream);
+  z[0] = z0.x; z[1] = z0.y; z[2] = z0.z; z[3] = z0.w; z[4] = z1.x; z[5] = z1.y; z[6] = z1.z; z[7] = z1.w;
+}
+
 // fill [B][L*128] with N(0,1): stream 1 = initial latents (convofusion.py:412-419)
 template <int CFD_KI = 0>
 __global__ void philox_fill_kernel(float* out, int B, int per_utt, uint64_t seed, uint32_t step, uint32_t utt0,
@@ -647,14 +653,17 @@ template <bool EDIT, bool ANCHOR = false, bool TIE = false>
 using BeginArgsOf = typename std::conditional<TIE, BeginArgsT,
     typename std::conditional<ANCHOR, BeginArgsA, typename std::conditional<EDIT, BeginArgsE, BeginArgs>::type>::type>::type;
 
-// 8 consecutive elements of sa * src + sb * eps, each product and the sum rounded on its own
+// 8 elements of sa * s + sb * e, each product and the sum rounded on its own; edit_mix8: of 8 consecutive elements in memory
+__device__ __forceinline__ void mix8(float sa, float sb, const float s[8], const float e[8], float v[8]) {
+#pragma unroll
+  for (int q = 0; q < 8; ++q) v[q] = __fadd_rn(__fmul_rn(sa, s[q]), __fmul_rn(sb, e[q]));
+}
 __device__ __forceinline__ void edit_mix8(float sa, float sb, const float* src, const float* eps, float v[8]) {
   const float4 s0 = *reinterpret_cast<const float4*>(src), s1 = *reinterpret_cast<const float4*>(src + 4);
   const float4 e0 = *reinterpret_cast<const float4*>(eps), e1 = *reinterpret_cast<const float4*>(eps + 4);
   const float s[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
   const float e[8] = {e0.x, e0.y, e0.z, e0.w, e1.x, e1.y, e1.z, e1.w};
-#pragma unroll
-  for (int q = 0; q < 8; ++q) v[q] = __fadd_rn(__fmul_rn(sa, s[q]), __fmul_rn(sb, e[q]));
+  mix8(sa, sb, s, e, v);
 }
 __device__ __forceinline__ void store8(float* p, const float v[8]) {
   *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
@@ -886,14 +895,8 @@ __global__ void ddpm_level_kernel(const LevelArgs a) {
   float s[8], e[8], v[8];
   load8(a.src + x.o, s);
   if (a.eps) load8(a.eps + (long long)i * x.chunk + x.o, e);
-  else {
-    const uint32_t g = (uint32_t)((x.l * CFD_LAT + x.c) / 4);
-    const float4 z0 = philox_normal4(a.seed, g, (uint32_t)i, a.utt0 + x.b, 2u), z1 = philox_normal4(a.seed, g + 1, (uint32_t)i, a.utt0 + x.b, 2u);
-    e[0] = z0.x; e[1] = z0.y; e[2] = z0.z; e[3] = z0.w; e[4] = z1.x; e[5] = z1.y; e[6] = z1.z; e[7] = z1.w;
-  }
-  const float sa = a.coef[i].sa, sb = a.coef[i].sb;
-#pragma unroll
-  for (int q = 0; q < 8; ++q) v[q] = __fadd_rn(__fmul_rn(sa, s[q]), __fmul_rn(sb, e[q]));
+  else philox_normal8(a.seed, (uint32_t)((x.l * CFD_LAT + x.c) / 4), (uint32_t)i, a.utt0 + x.b, 2u, e);
+  mix8(a.coef[i].sa, a.coef[i].sb, s, e, v);
   store8(a.traj + (long long)(a.N - i) * x.chunk + x.o, v);
   replicate_sp8(a.sample_sp, x, a.G, a.B, a.L, v);
 }
@@ -906,8 +909,34 @@ struct Combine {
   int clip;
   const float* wtab;     // WTAB: [N][B][8]
 };
+// The guided prediction of a thread's 8 elements of iteration i, utterance b (lev: the level's first chunk at the thread's offset; WTAB:
+// weights from the table row i), shared by ddpm_extract_kernel and picard_step_kernel.  cfg_step_kernel keeps its own text (all eight
+// chunk loads before the first use, groups of 4); that it is the same association -- ((((text + audio) + spk) + apb) + lsnid) + all, each
+// = (g*w)*(e_k - e_0) -- holds by construction of tests/picard_ref.py and the trajectory tests, not by shared text.
+template <bool WTAB>
+__device__ __forceinline__ void level_combine8(const Combine& g, const float* lev, long long chunk, int i, int B, int b, float eps[8]) {
+  float u[8], acc[8];
+  load8(lev + (long long)g.pos[0] * chunk, u);
+  const float* wrow = nullptr;
+  if constexpr (WTAB) wrow = g.wtab + ((long long)i * B + b) * 8;
+#pragma unroll
+  for (int q = 0; q < 8; ++q) acc[q] = 0.f;
+  for (int k = 1; k < g.Gc; ++k) {
+    float e[8];
+    load8(lev + (long long)g.pos[k] * chunk, e);
+    const float wk = WTAB ? wrow[k] : g.w[k];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const float term = wk * (e[q] - u[q]);
+      acc[q] = (k == 1) ? term : acc[q] + term;
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 8; ++q) eps[q] = (g.Gc > 1) ? u[q] + acc[q] : u[q];
+}
+
 // Noise extraction for the J levels of a batch, from the G predictions of every level (level-major rows, as ddpm_level_kernel wrote the
-// input): the guidance combine term for term as cfg_step_kernel's, x0 / clip / mu through step_x0 / ddpm_mu, then
+// input): the guidance combine (level_combine8, shared with picard_step_kernel), x0 / clip / mu through step_x0 / ddpm_mu, then
 // z_i = (slot[N - i - 1] - mu) / sigma_i, or exactly 0 where the DDPM row adds no noise.  WTAB: weights from the table row i.  One thread =
 // 8 elements.
 struct ExtractArgs {
@@ -923,36 +952,19 @@ __global__ void ddpm_extract_kernel(const ExtractArgs a) {
   const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const long long n8 = (long long)a.B * a.L * (CFD_LAT / 8);
   if (idx >= n8 * a.J) return;
-  const int lv = (int)(idx / n8), i = a.i0 + lv;
-  const long long o = (idx % n8) * 8, chunk = n8 * 8;
+  const LevelIdx x = level_idx(idx, n8, a.L, a.i0);
+  const int i = x.i;
   const StepCoef c = a.coef[i];
-  const float* lev = a.eps + (long long)lv * a.G * chunk + o;
-  float u[8], acc[8], x[8], nx[8], z[8];
-  load8(lev + (long long)a.g.pos[0] * chunk, u);
-  load8(a.traj + (long long)(a.N - i) * chunk + o, x);
-  load8(a.traj + (long long)(a.N - i - 1) * chunk + o, nx);
-  const float* wrow = nullptr;
-  if constexpr (WTAB) wrow = a.g.wtab + ((long long)i * a.B + o / ((long long)a.L * CFD_LAT)) * 8;   // (8 elements never straddle two utterances)
-#pragma unroll
-  for (int q = 0; q < 8; ++q) acc[q] = 0.f;
-  // reference association: ((((text + audio) + spk) + apb) + lsnid) + all, each = (g*w)*(e_k - e_0)
-  for (int k = 1; k < a.g.Gc; ++k) {
-    float e[8];
-    load8(lev + (long long)a.g.pos[k] * chunk, e);
-    const float wk = WTAB ? wrow[k] : a.g.w[k];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      const float term = wk * (e[q] - u[q]);
-      acc[q] = (k == 1) ? term : acc[q] + term;
-    }
-  }
+  float eps[8], xv[8], nx[8], z[8];
+  level_combine8<WTAB>(a.g, a.eps + (long long)x.lv * a.G * x.chunk + x.o, x.chunk, i, a.B, x.b, eps);
+  load8(a.traj + (long long)(a.N - i) * x.chunk + x.o, xv);
+  load8(a.traj + (long long)(a.N - i - 1) * x.chunk + x.o, nx);
 #pragma unroll
   for (int q = 0; q < 8; ++q) {
-    const float eps = (a.g.Gc > 1) ? u[q] + acc[q] : u[q];
-    const float mu = ddpm_mu(c, step_x0(c, a.g.clip, x[q], eps), x[q]);
+    const float mu = ddpm_mu(c, step_x0(c, a.g.clip, xv[q], eps[q]), xv[q]);
     z[q] = c.use_noise != 0.f ? (nx[q] - mu) / c.sigma : 0.f;
   }
-  store8(a.noise + (long long)i * chunk + o, z);
+  store8(a.noise + (long long)i * x.chunk + x.o, z);
 }
 
 // ---- parallel-in-time DDPM sampling (cfd_sample_parallel) ----------------------------------------------------------------------------
@@ -985,8 +997,8 @@ __global__ void picard_load_kernel(const PicardLoadArgs a) {
   replicate_sp8(a.sample_sp, x, a.G, a.B, a.L, v);
 }
 
-// The DDPM step of every live level of a batch, from the G predictions of every level: the guidance combine term for term as
-// cfg_step_kernel's / ddpm_extract_kernel's, then s = ddpm_mu(c, step_x0(c, clip, x, eps), x) (+ c.sigma * z where the row adds noise; z:
+// The DDPM step of every live level of a batch, from the G predictions of every level: the guidance combine (level_combine8, shared with
+// ddpm_extract_kernel), then s = ddpm_mu(c, step_x0(c, clip, x, eps), x) (+ c.sigma * z where the row adds noise; z:
 // the caller's row i, or Philox stream 0 with step index i as cfg_step_kernel draws it).  WTAB: weights from the table row i.  One
 // thread = 8 elements of one level.
 struct PicardStepArgs {
@@ -1005,47 +1017,26 @@ __global__ void picard_step_kernel(const PicardStepArgs a) {
   const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const long long n8 = (long long)a.B * a.L * (CFD_LAT / 8);
   if (idx >= n8 * a.J) return;
-  const int lv = (int)(idx / n8), i = a.base + lv;
-  if (lv < a.off) return;
-  const long long o = (idx % n8) * 8, chunk = n8 * 8;
-  const int per_utt = a.L * CFD_LAT;
+  const LevelIdx x = level_idx(idx, n8, a.L, a.base);
+  const int i = x.i;
+  if (x.lv < a.off) return;
   const StepCoef c = a.coef[i];
-  const float* lev = a.eps + (long long)lv * a.G * chunk + o;
-  float u[8], acc[8], x[8], z[8], s[8];
-  load8(lev + (long long)a.g.pos[0] * chunk, u);
-  load8(a.ring.at(i) + o, x);
-  const float* wrow = nullptr;
-  if constexpr (WTAB) wrow = a.g.wtab + ((long long)i * a.B + o / per_utt) * 8;   // (8 elements never straddle two utterances)
+  float eps[8], xv[8], z[8], s[8];
+  level_combine8<WTAB>(a.g, a.eps + (long long)x.lv * a.G * x.chunk + x.o, x.chunk, i, a.B, x.b, eps);
+  load8(a.ring.at(i) + x.o, xv);
 #pragma unroll
-  for (int q = 0; q < 8; ++q) acc[q] = z[q] = 0.f;
-  // reference association: ((((text + audio) + spk) + apb) + lsnid) + all, each = (g*w)*(e_k - e_0)
-  for (int k = 1; k < a.g.Gc; ++k) {
-    float e[8];
-    load8(lev + (long long)a.g.pos[k] * chunk, e);
-    const float wk = WTAB ? wrow[k] : a.g.w[k];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      const float term = wk * (e[q] - u[q]);
-      acc[q] = (k == 1) ? term : acc[q] + term;
-    }
-  }
+  for (int q = 0; q < 8; ++q) z[q] = 0.f;
   if (c.use_noise != 0.f) {
-    if (a.noise) {
-      load8(a.noise + (long long)i * chunk + o, z);
-    } else {
-      const uint32_t b = (uint32_t)(o / per_utt), g = (uint32_t)((o % per_utt) / 4);
-      const float4 z0 = philox_normal4(a.seed, g, (uint32_t)i, a.utt0 + b, 0u), z1 = philox_normal4(a.seed, g + 1, (uint32_t)i, a.utt0 + b, 0u);
-      z[0] = z0.x; z[1] = z0.y; z[2] = z0.z; z[3] = z0.w; z[4] = z1.x; z[5] = z1.y; z[6] = z1.z; z[7] = z1.w;
-    }
+    if (a.noise) load8(a.noise + (long long)i * x.chunk + x.o, z);
+    else philox_normal8(a.seed, (uint32_t)((x.l * CFD_LAT + x.c) / 4), (uint32_t)i, a.utt0 + x.b, 0u, z);
   }
 #pragma unroll
   for (int q = 0; q < 8; ++q) {
-    const float eps = (a.g.Gc > 1) ? u[q] + acc[q] : u[q];
-    float prev = ddpm_mu(c, step_x0(c, a.g.clip, x[q], eps), x[q]);
+    float prev = ddpm_mu(c, step_x0(c, a.g.clip, xv[q], eps[q]), xv[q]);
     if (c.use_noise != 0.f) prev = prev + c.sigma * z[q];
     s[q] = prev;
   }
-  store8(a.s + (long long)lv * chunk + o, s);
+  store8(a.s + (long long)x.lv * x.chunk + x.o, s);
 }
 
 // The re-propagation of a sweep through the live levels of the batch (i0 = base + off): Xn(i0) = X(i0), Xn(j + 1) = fl(s_j + fl(Xn(j) -

@@ -32,6 +32,13 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef const __attribute__((address_space(1))) void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
 
+// The folded memory-side weights A, c and VV are stored as split pairs of CFD_MEMW_SCALE x their value, and the
+// epilogues of the products against them (EpiMemK, EpiMemV, EpiF32S) scale the float32 accumulators back -- both exact, a power of two.
+// Their elements are ~2e-3, so the `lo` half of the unscaled value (2^-11 of it) is an fp16 SUBNORMAL with an absolute step of 2^-24:
+// the pair then holds 16 - 17 significant bits, not 22 (measured block by block: tests/test_gpu_xattn_block.py; 2.2e-6 of the block's
+// 2.5e-6 against float64).  x 64 brings elements from 2e-3 on to full width and leaves a factor 1000 to the saturation bound for weights of 1.
+#define CFD_MEMW_SCALE 64.0f
+
 __device__ __forceinline__ void split_f32(float v, sp_t& hi, sp_t& lo) {
   v = __builtin_amdgcn_fmed3f(v, -65504.0f, 65504.0f);
   hi = (sp_t)v;

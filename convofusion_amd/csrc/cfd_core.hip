@@ -292,18 +292,19 @@ extern "C" int cfd_finalize_weights(cfd_handle c) {
       CHK(need(c, p + MEM_NAMES[j] + "_norm.bias", D, &bet));
       const float *Wq = ipw, *Wk = ipw + (size_t)D * D, *Wv = ipw + (size_t)2 * D * D;
       const float *bq = ipb, *bv = ipb + 2 * D;
+      // (A, c and VV are stored x CFD_MEMW_SCALE, which the epilogues of their products take out again: cfd_common.hpp)
       // key side:  A[o][i] = cs * gamma[i] * sum_r Wq[r][o] Wk[r][i]      (scores = y . (A n))
       hipLaunchKernelGGL((fold_mm_kernel<float, float, float>), grid1((long long)D * D), blk, 0, 0, Wq, 1LL, (long long)D, Wk,
-                         (long long)D, 1LL, wk_f[j].as<float>() + (size_t)l * D * D, (long long)D, D, D, D, cs, gam);
+                         (long long)D, 1LL, wk_f[j].as<float>() + (size_t)l * D * D, (long long)D, D, D, D, cs * CFD_MEMW_SCALE, gam);
       //            c[i]  = cs * gamma[i] * sum_r Wk[r][i] bq[r]          (key-dependent part of the q-bias term)
       hipLaunchKernelGGL((fold_mv_kernel<float, float, float>), grid1(D), blk, 0, 0, Wk, 1LL, (long long)D, bq,
-                         (const double*)nullptr, (const float*)nullptr, wk_f[j].as<float>() + (size_t)(kfeat + l) * D, D, D, cs, gam);
+                         (const double*)nullptr, (const float*)nullptr, wk_f[j].as<float>() + (size_t)(kfeat + l) * D, D, D, cs * CFD_MEMW_SCALE, gam);
       // value side: VV = Wf_j Wo Wv diag(gamma)
       hipLaunchKernelGGL((fold_mm_kernel<float, float, double>), grid1((long long)D * D), blk, 0, 0, ow, (long long)D, 1LL, Wv,
                          (long long)D, 1LL, tmpd1.as<double>(), (long long)D, D, D, D, 1.0, (const float*)nullptr);
       hipLaunchKernelGGL((fold_mm_kernel<float, double, float>), grid1((long long)D * D), blk, 0, 0, fw + (size_t)j * D,
                          (long long)5 * D, 1LL, tmpd1.as<double>(), (long long)D, 1LL, wv_f[j].as<float>() + (size_t)l * D * D,
-                         (long long)D, D, D, D, 1.0, gam);
+                         (long long)D, D, D, D, (double)CFD_MEMW_SCALE, gam);
       // constant: acc += Wf_j ( Wo (Wv beta + bv) + bo )
       hipLaunchKernelGGL((fold_mv_kernel<float, float, double>), grid1(D), blk, 0, 0, Wv, (long long)D, 1LL, bet,
                          (const double*)nullptr, bv, vd1.as<double>(), D, D, 1.0, (const float*)nullptr);

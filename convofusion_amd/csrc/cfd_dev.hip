@@ -9,6 +9,15 @@ extern "C" int cfd_debug_stop_stage(cfd_handle c, int stage) {
   return CFD_OK;
 }
 
+extern "C" int cfd_debug_forward_operands(cfd_handle c, int policy) {
+  if (!c) return fail(CFD_E_ARG, "null handle");
+  if (policy != 0 && policy != 15) return fail(CFD_E_ARG, "cfd_debug_forward_operands: policy %d (0: split pairs, 15: single-fp16 tiles of the long memories)", policy);
+  if (c->run_open) return fail(CFD_E_STATE, "a sampling run is open on this handle");
+  if (policy != c->fwd_operands) c->wk[0].fwd_mem_valid = false;   // the work lists carry XA_F16 and k16 / v16 are made per call: nothing of the last forward is reused
+  c->fwd_operands = policy;
+  return CFD_OK;
+}
+
 extern "C" int cfd_debug_weg_stop(cfd_handle c, int stop) {
   if (!c) return fail(CFD_E_ARG, "null handle");
   if (stop != 0) {
@@ -87,6 +96,13 @@ extern "C" int cfd_debug_read(cfd_handle c, const char* what, float* dst_dev, si
   if (!strcmp(what, "weg.info")) {   // the last row-tile WEG evaluation: launches, Sp_tot, rt_xbwd_dy_kernel instance (keys), objective kernel (1: weg_focus_kernel), G index
     if (numel < 5) return fail(CFD_E_ARG, "weg.info needs 5 floats");
     const float f[5] = {(float)c->wrt.launches, (float)c->wrt.Sp_tot, (float)c->wrt.dy_keys, (float)c->wrt.focus_large, (float)c->wrt.stop_gi};
+    HIPCHK(hipMemcpy(dst_dev, f, sizeof(f), hipMemcpyHostToDevice));
+    return CFD_OK;
+  }
+  if (!strcmp(what, "xa.info")) {   // the last cfd_forward's cross-attention: kernel instance, work-list form
+    if (numel < 7) return fail(CFD_E_ARG, "xa.info needs 7 floats");
+    const Problem& p = c->wk[0].pb;
+    const float f[7] = {(float)c->xa_inst, (float)p.xa_nwg, (float)p.xa_tpw, (float)p.xa_n16, (float)p.xa_nseg, p.xa_flush ? 1.f : 0.f, (float)p.xa_one};
     HIPCHK(hipMemcpy(dst_dev, f, sizeof(f), hipMemcpyHostToDevice));
     return CFD_OK;
   }

@@ -422,6 +422,7 @@ int enqueue_rows(Ctx* c, hipStream_t st, int row0, int Be) {
         a.census_tau = c->acen_tau;
         c->acen_hits += 1;
       }
+      c->xa_inst = p.att_fused ? 1 : p.xa_f16 ? 2 : 0;
       auto launch_xa = [&](int nwg, const XAttnArgs& xa) {
         if (p.att_fused) hipLaunchKernelGGL((xattn_fused_kernel<true, false>), dim3(nwg), dim3(XA_WAVES * 64), XA_LDS, st, xa);
         else if (p.xa_f16) hipLaunchKernelGGL((xattn_fused_kernel<false, true>), dim3(nwg), dim3(XA_WAVES * 64), XA_LDS, st, xa);
@@ -609,7 +610,15 @@ extern "C" int cfd_forward(cfd_handle c, const float* sample, int Be, int L, con
   if (n_t != 1 && n_t != Be) return fail(CFD_E_ARG, "n_t must be 1 or Be");
   hipStream_t st = (hipStream_t)stream;
   const int tmode = (n_t == 1) ? 0 : 1;
-  CHK(setup_problem(c, Be, L, mem, att, tmode, n_t));
+  c->xa_inst = -1;
+  {  // (test hook cfd_debug_forward_operands: the single-fp16 tiles of a sampling run's operand policy, asked for as setup_run_problem asks)
+    bool any_att = false;
+    for (int j = 0; j < CFD_NMEM; ++j) any_att = any_att || (att && att[j]);
+    c->want_f16 = c->fwd_operands != 0 && tmode == 0 && !any_att;
+    const int r_setup = setup_problem(c, Be, L, mem, att, tmode, n_t);
+    c->want_f16 = false;
+    CHK(r_setup);
+  }
   CHK(sat_begin(c, st));
   // tmode 0 reads table row d_step[0] which must be 0 outside a sampling run
   HIPCHK(hipMemsetAsync(c->w->d_step.p, 0, 16, st));

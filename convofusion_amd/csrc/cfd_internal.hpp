@@ -102,9 +102,10 @@ struct Problem {
   bool xa_flush = false;               // some work list flushes the accumulator between two online memories (XA_FLUSH): lock-step kernel only
   int xa_one = -1;                     // the one-key memory the fused cross-attention adds as a vector (xattn_fused.hpp, XAttnArgs::one_j), or -1
   bool xa_f16 = false;                 // the fused cross-attention's key / value tiles of LONG memories are single fp16 in this problem (its F16 instance;
-                                       // false: split pairs).  Only a sampling run sets it (cfd_sample_args::operand_policy), and only when every memory is
-                                       // static and no maps are kept
+                                       // false: split pairs).  Only a sampling run sets it (cfd_sample_args::operand_policy) -- and a cfd_forward under the
+                                       // developer hook cfd_debug_forward_operands -- and only when every memory is static and no maps are kept
   int xa_f16_mask = 0;                 // bit j: memory j is long enough (XA_F16_MIN_KEYS) for single-fp16 tiles; its segments carry XA_F16
+  int xa_tpw = 0, xa_n16 = 0, xa_nseg = 0;   // of the work list (build_xattn_worklist): the most query tiles, XA_F16 segments and segments of a workgroup ("xa.info")
   // memories (bit j) whose folded projections were computed once for the run from the centred static part of the memory
   // (prepare_static_memside); per step they only get their per-key scale and bias (mem_scale_all_kernel)
   int static_mask = 0;
@@ -249,6 +250,8 @@ struct cfd_handle_s {
   unsigned int* sat_mem() const { return sat.as<unsigned int>() + CFD_SAT_MEM; }
   unsigned int* sat_in() const { return sat.as<unsigned int>() + CFD_SAT_IN; }
   bool want_f16 = false;        // cfd_sample_begin -> setup_problem: the run asks for single-fp16 tiles (non-zero operand policy; false everywhere else)
+  int fwd_operands = 0;         // test hook (cfd_debug_forward_operands): 15 = cfd_forward asks setup_problem for single-fp16 tiles as a run would; 0 = pairs
+  int xa_inst = -1;             // test read-out ("xa.info"): the xattn_fused_kernel instance the last enqueue_rows launched (0 pairs, 1 ATT, 2 F16; -1: none)
   bool hint_same_mem = false;   // cfd_forward_same_memories: the promise for the NEXT cfd_forward ...
   bool hint_now = false;        // ... taken (and cleared) at that call's very first line, before anything can fail: a call that returns early
                                 // must not leave the promise standing for the call after it

@@ -138,6 +138,7 @@ static int upload_worklist(DBuf& dw, DBuf& ds, const std::vector<XaWg>& wgs, con
 int build_xattn_worklist(Ctx* c, const cfd_memory mem[CFD_NMEM], bool one_key) {
   Problem& p = c->w->pb;
   p.xa_nwg = 0; p.xa0_nwg_a = 0; p.xa0_nwg_b = 0; p.xa_flush = false;
+  p.xa_tpw = p.xa_n16 = p.xa_nseg = 0;
   if (!c->fused_xattn) return CFD_OK;
   std::vector<std::vector<int>> hm;
   CHK(read_row_maps(c, mem, hm));
@@ -180,6 +181,11 @@ int build_xattn_worklist(Ctx* c, const cfd_memory mem[CFD_NMEM], bool one_key) {
   (void)n_active;
   CHK(upload_worklist(c->w->xa_wgs, c->w->xa_segs, wgs, segs));
   p.xa_nwg = (int)wgs.size();
+  for (const XaWg& w : wgs) {   // (read-out only: "xa.info")
+    int tiles = 0;
+    for (int k = 0; k < XA_TILES; ++k) tiles += w.row[k] >= 0;
+    p.xa_tpw = std::max(p.xa_tpw, tiles); p.xa_n16 = std::max(p.xa_n16, w.n16); p.xa_nseg = std::max(p.xa_nseg, w.nseg);
+  }
   return CFD_OK;
 }
 
@@ -541,19 +547,19 @@ int prepare_static_memside(Ctx* c, hipStream_t st, int dynamic_mask, bool want_a
       GemmArgs a = gemm_args();
       a.X[0] = c->wk_all_sp[j].as<char>(); a.ldx[0] = ROWB; a.I[0] = NK; a.Iclamp[0] = NK; a.kt[0] = CFD_D / 32;
       a.Y = c->w->b_sp.as<char>(); a.ldy = ROWB; a.J = T; a.Jclamp = T;
-      EpiF32 e;
+      EpiF32S e;
       memset(&e, 0, sizeof(e));
       e.out = c->w->kbtab[j].as<float>(); e.ldo = NK;
-      CHK(run_gemm_plain_f32(c, CFD_PROF_GEMM_MEM, a, e, 1, 1, st));
+      CHK((run_gemm<MODE_PLAIN>(c, CFD_PROF_GEMM_MEM, a, e, 1, 1, st)));
     }
     if (!have_tb) {  // vbtab[t][:] = VV_l b_t for all l
       GemmArgs a = gemm_args();
       a.X[0] = c->wv_all_sp[j].as<char>(); a.ldx[0] = ROWB; a.I[0] = nl * CFD_D; a.Iclamp[0] = nl * CFD_D; a.kt[0] = CFD_D / 32;
       a.Y = c->w->b_sp.as<char>(); a.ldy = ROWB; a.J = T; a.Jclamp = T;
-      EpiF32 e;
+      EpiF32S e;
       memset(&e, 0, sizeof(e));
       e.out = c->w->vbtab[j].as<float>(); e.ldo = nl * CFD_D;
-      CHK(run_gemm_plain_f32(c, CFD_PROF_GEMM_MEM, a, e, 1, 1, st));
+      CHK((run_gemm<MODE_PLAIN>(c, CFD_PROF_GEMM_MEM, a, e, 1, 1, st)));
       c->w->tt_mem_mask |= 1 << j;
       c->setup_launches += 2;
     }

@@ -88,6 +88,12 @@ struct EpiF32 {  // out_f32[j][goff+i] = v (+ bias[i] | + key-bias of group g)
   }
 };
 
+struct EpiF32S : EpiF32 {  // EpiF32 of a product against the scaled memory-side weights (cfd_common.hpp: CFD_MEMW_SCALE): A b, c . b, VV b
+  __device__ __forceinline__ void operator()(int g, int b, int z, int i, int j, f32x4 v, const Pre& t) const {
+    EpiF32::operator()(g, b, z, i, j, v * (1.0f / CFD_MEMW_SCALE), t);
+  }
+};
+
 struct EpiSplit {  // out_sp[j][coloff + i] = split(act(v + bias[i]))
   char* out;
   long long ldo, obs, ozs;  // bytes
@@ -343,7 +349,8 @@ struct EpiMemK {  // i < nfeat: K_layer[i/512][j][i%512] = split(v)  (one contig
   static constexpr bool kPrefetch = false;
   static constexpr bool kStore8 = true;
   __device__ __forceinline__ void store8(int g, int b, int z, int i, int j, f32x4 v0, f32x4 v1) const {
-    if (i + 8 <= nfeat) {   // (nfeat is a multiple of 512: 8 consecutive features never straddle a layer)
+    if (i + 8 <= nfeat) {
+      v0 *= 1.0f / CFD_MEMW_SCALE; v1 *= 1.0f / CFD_MEMW_SCALE;   // (the weights are stored scaled: cfd_common.hpp)   // (nfeat is a multiple of 512: 8 consecutive features never straddle a layer)
       const int layer = i >> 9, o = i & (CFD_D - 1);
       const float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
       sat_note<8>(sat, v);
@@ -354,6 +361,7 @@ struct EpiMemK {  // i < nfeat: K_layer[i/512][j][i%512] = split(v)  (one contig
     }
   }
   __device__ __forceinline__ void operator()(int g, int b, int z, int i, int j, f32x4 v) const {
+    v *= 1.0f / CFD_MEMW_SCALE;
     if (i < nfeat) {
       const int layer = i >> 9, o = i & (CFD_D - 1);
       const float vv[4] = {v[0], v[1], v[2], v[3]};
@@ -378,6 +386,7 @@ struct EpiMemV {  // V^T_layer_u[j/512][i/Sp][j%512][i%Sp] = split(v): one conti
   __device__ __forceinline__ void store8(int g, int b, int z, int i, int j, f32x4 v0, f32x4 v1) const {
     const int layer = j >> 9, f = j & (CFD_D - 1);
     const int u = i / Sp, s = i - u * Sp;   // (Sp is a multiple of 32: 8 consecutive rows belong to one memory)
+    v0 *= 1.0f / CFD_MEMW_SCALE; v1 *= 1.0f / CFD_MEMW_SCALE;   // (the weights are stored scaled: cfd_common.hpp)
     const float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
     sat_note<8>(sat, v);
     sp_store8(vt + (((long long)layer * U + u) * CFD_D + f) * ((long long)Sp * 4), s, v);
@@ -385,6 +394,7 @@ struct EpiMemV {  // V^T_layer_u[j/512][i/Sp][j%512][i%Sp] = split(v): one conti
   __device__ __forceinline__ void operator()(int g, int b, int z, int i, int j, f32x4 v) const {
     const int layer = j >> 9, f = j & (CFD_D - 1);
     const int u = i / Sp, s = i - u * Sp;
+    v *= 1.0f / CFD_MEMW_SCALE;
     const float vv[4] = {v[0], v[1], v[2], v[3]};
     sat_note<4>(sat, vv);
     sp_store4(vt + (((long long)layer * U + u) * CFD_D + f) * ((long long)Sp * 4), s, v[0], v[1], v[2], v[3]);

@@ -56,8 +56,22 @@ int cfd_test_gemm_epi(cfd_handle h, cfd_test_epi_args* args, void* stream);
 
 /* Test hooks: stop the forward pipeline after tap point `stage` (0 = off; 1 = after the latent embedding;
  * 2+4l / 3+4l / 4+4l / 5+4l = layer l after self-attention / time block 1 / cross-attention / the layer),
- * and read an internal float32 buffer ("x" residual stream [M][512], "temb", "ss", "eps", "sc", "ssc"). */
+ * and read an internal float32 buffer ("x" residual stream [M][512], "temb", "ss", "eps", "sc", "ssc").
+ *   "xa.info"  [7]  the cross-attention of the last cfd_forward: the xattn_fused_kernel instance its layers launched (0: split pairs,
+ *                   1: ATT, keeps the maps, 2: F16, single-fp16 tiles; -1: none -- the three-launch path, the row-tile path, or a stop
+ *                   stage in front of the first block), then of its work list: workgroups (0: no list), the most query tiles of a
+ *                   workgroup (1, 2 or 4), the most single-fp16 segments (n16) and the most segments (nseg) of a workgroup, whether a
+ *                   list flushes the accumulator between two online memories (0 / 1), and the one-key memory added as a vector (-1: none) */
 int cfd_debug_stop_stage(cfd_handle h, int stage);
+/* Test hook: the operand policy of the handle's cfd_forward calls (a sampling run has cfd_sample_args.operand_policy; nothing else reads
+ * this).  policy = 0 (the default): split pairs, the launch sequence and every kernel are what they are without the hook.  policy = 15:
+ * cfd_forward asks for the single-fp16 key / value tiles of its long memories exactly as cfd_sample_begin does, so the fused cross-attention
+ * runs its F16 instance (csrc/xattn_fused.hpp) on tiles xa_pack16_kernel packs in that call -- under the product's own conditions: one
+ * timestep for all rows, no attention maps wanted, every memory's projections made once per call on the tile kernels (no row-tile path),
+ * a non-empty fused work list, some memory of at least 128 padded keys.  Where one fails the forward silently runs split pairs, as a
+ * sampling run would: read "xa.info".  Any other value: CFD_E_ARG; CFD_E_STATE while a sampling run is open.  A change of the value drops
+ * what cfd_forward_same_memories would let the next call reuse (the work lists carry the tile format). */
+int cfd_debug_forward_operands(cfd_handle h, int policy);
 /* Micro-benchmark: average ms of `iters` launches of the [J x K] x [512 x K]^T residual GEMM (I must be 512). */
 int cfd_bench_gemm(cfd_handle h, int I, int J, int K, int tile_cfg, int iters, float* ms_out);
 int cfd_debug_read(cfd_handle h, const char* what, float* dst_dev, size_t numel);

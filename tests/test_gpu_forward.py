@@ -598,27 +598,13 @@ def test_the_cross_attention_block_is_float32_exact_on_the_ill_conditioned_chunk
     m = m.cuda().eval()
     m.return_attention = False
     layer, chunk = 4, 5
-    p = f"decoder.layers.{layer}."
-    sd64 = {k: v.astype(np.float64) for k, v in sd.items() if k.startswith(p)}
-
-    def ln64(x, w, b):
-        xc = x - x.mean(-1, keepdims=True)
-        return xc / np.sqrt((xc * xc).mean(-1, keepdims=True) + 1e-5) * w + b
+    # the block in float64, reference formulation (tests/xattn_ref.py), on this chunk's memories
+    from tests.xattn_ref import block_unfolded
+    mem_taps = {"mem." + name: taps["mem." + name][:, chunk:chunk + 1] for name in inputs.MEM_NAMES}
+    chunk_masks = {k: (None if v is None else np.asarray(v)[chunk:chunk + 1]) for k, v in masks.items()}
 
     def cross64(x):
-        q_in = ln64(x, sd64[p + "norm2.weight"], sd64[p + "norm2.bias"])
-        outs = []
-        for name in ("spkemb", "alsn", "tlsn", "apb", "lsnemb"):
-            mn = ln64(taps["mem." + name][:, chunk].astype(np.float64), sd64[p + name + "_norm.weight"], sd64[p + name + "_norm.bias"])
-            a = p + "multihead_attn_" + name
-            w, b = sd64[a + ".in_proj_weight"], sd64[a + ".in_proj_bias"]
-            sc = ((q_in @ w[:512].T + b[:512]) / np.sqrt(512.0)) @ (mn @ w[512:1024].T + b[512:1024]).T
-            if masks.get(name) is not None:
-                sc = np.where(np.asarray(masks[name][chunk], dtype=bool)[None, :], -np.inf, sc)
-            pr = np.exp(sc - sc.max(-1, keepdims=True))
-            pr = pr / pr.sum(-1, keepdims=True)
-            outs.append((pr @ (mn @ w[1024:].T + b[1024:])) @ sd64[a + ".out_proj.weight"].T + sd64[a + ".out_proj.bias"])
-        return np.concatenate(outs, -1) @ sd64[p + "att_fuser.weight"].T + sd64[p + "att_fuser.bias"]
+        return block_unfolded(sd, layer, x[None], mem_taps, chunk_masks)[0][0]
 
     lib = _lib.load()
     hip = {}

@@ -9,7 +9,32 @@
 int enqueue_denoise(Ctx* c, hipStream_t st) {
   CHK(enqueue_memside(c, st));
   if (c->w->pb.rt) return enqueue_rows_rt(c, st);
-  return enqueue_rows(c, st, 0, c->w->pb.Be);
+  return enqueue_rows(c, st);
+}
+
+// This step's rows of per-step tables for a sampling run: ONE launch at the start of the iteration copies row *dstep of every listed table
+// to a fixed place in rt_cur (64-float4 granules, in list order) and every `now` -- a table's base -- is redirected to its copy, so that no
+// launch of the iteration has the step index as a dependent scalar load in front of its operand loads.
+struct StepTab { const float** now; int nfloat; };
+static int refresh_step_rows(Ctx* c, hipStream_t st, const int* dstep, const std::vector<StepTab>& tabs) {
+  if (tabs.size() > RT_NTAB) return fail(CFD_E_ARG, "%d per-step tables, rt_step_rows_kernel takes %d", (int)tabs.size(), RT_NTAB);
+  auto granules = [](const StepTab& t) { return (size_t)(t.nfloat / 4 + 63) / 64 * 64; };
+  size_t off4 = 0;
+  for (const StepTab& t : tabs) off4 += granules(t);
+  CHK(c->w->rt_cur.ensure(off4 * 16));
+  RtStepRowsArgs ra;
+  memset(&ra, 0, sizeof(ra));
+  off4 = 0;
+  int nwg = 0;
+  for (const StepTab& t : tabs) {
+    float* dst = c->w->rt_cur.as<float>() + off4 * 4;
+    ra.src[ra.ntab] = *t.now; ra.dst[ra.ntab] = dst; ra.n4[ra.ntab] = t.nfloat / 4; ra.first[ra.ntab] = nwg;
+    nwg += (t.nfloat / 4 + 255) / 256; off4 += granules(t); ++ra.ntab;
+    *t.now = dst;
+  }
+  ra.first[ra.ntab] = nwg; ra.d_step = dstep;
+  LAUNCH(CFD_PROF_OTHER, rt_step_rows_kernel<>, dim3(nwg), dim3(256), st, ra);
+  return CFD_OK;
 }
 
 // The forward for small problems: launches of 16-token x 16-feature workgroups (rowtile.hpp); same buffers, same tap points.
@@ -48,29 +73,16 @@ int enqueue_rows_rt(Ctx* c, hipStream_t st, const RtSave* sv) {
   float* const hw = c->w->h_sp.as<float>();   // (the tile-kernel path's LayerNorm output: same bytes, unused here)
   auto X = [&](int l, int k) -> float* { return sv ? sv->x[l][k] : ((k == 2 || k == 4) ? hw : xw); };
   // This step's rows of the per-step tables.  One table row (cfd_forward, the WEG evaluation): the tables themselves.  A sampling
-  // run: fixed buffers refreshed by ONE launch at the start of the iteration, so that no launch of the iteration has the step index
-  // as a dependent scalar load in front of its operand loads.
+  // run: their copies in rt_cur (refresh_step_rows).
   const float* ss_now = c->w->ss_tab.as<float>();
   const float *kb_now[CFD_NMEM], *vb_now[CFD_NMEM], *cbt_now[CFD_NMEM];
   for (int j = 0; j < CFD_NMEM; ++j) { kb_now[j] = c->w->kbtab[j].as<float>(); vb_now[j] = c->w->vbtab[j].as<float>(); cbt_now[j] = c->w->rt_cbt[j].as<float>(); }
   if (p.T > 1) {
-    RtStepRowsArgs ra;
-    memset(&ra, 0, sizeof(ra));
-    size_t off4 = 0;
-    int nt = 0, nwg = 0;
-    auto add = [&](const float*& now, int nfloat) {
-      float* dst = c->w->rt_cur.as<float>() + off4 * 4;
-      ra.src[nt] = now; ra.dst[nt] = dst; ra.n4[nt] = nfloat / 4; ra.first[nt] = nwg;
-      nwg += (nfloat / 4 + 255) / 256; off4 += (size_t)(nfloat / 4 + 63) / 64 * 64; ++nt;
-      now = dst;
-    };
-    size_t need4 = (size_t)(nl * 4 * CFD_D / 4 + 64);
-    for (int j = 0; j < CFD_NMEM; ++j) need4 += (size_t)((nl * CFD_D + 32) / 4 + 64) + (size_t)(nl * CFD_D / 4 + 64) + (size_t)((nl + 1) * p.U[j] * p.Sp[j] / 4 + 64);
-    CHK(c->w->rt_cur.ensure(need4 * 16));
-    add(ss_now, nl * 4 * CFD_D);
-    for (int j = 0; j < CFD_NMEM; ++j) { add(kb_now[j], nl * CFD_D + 32); add(vb_now[j], nl * CFD_D); add(cbt_now[j], (nl + 1) * p.U[j] * p.Sp[j]); }
-    ra.ntab = nt; ra.first[nt] = nwg; ra.d_step = dstep;
-    LAUNCH(CFD_PROF_OTHER, rt_step_rows_kernel<>, dim3(nwg), dim3(256), st, ra);
+    std::vector<StepTab> tabs{{&ss_now, nl * 4 * CFD_D}};
+    for (int j = 0; j < CFD_NMEM; ++j) {
+      tabs.push_back({&kb_now[j], nl * CFD_D + 32}); tabs.push_back({&vb_now[j], nl * CFD_D}); tabs.push_back({&cbt_now[j], (nl + 1) * p.U[j] * p.Sp[j]});
+    }
+    CHK(refresh_step_rows(c, st, dstep, tabs));
   }
   c->w->now_ss = ss_now;
   for (int j = 0; j < CFD_NMEM; ++j) { c->w->now_kb[j] = kb_now[j]; c->w->now_vb[j] = vb_now[j]; }
@@ -209,80 +221,57 @@ int enqueue_rows_rt(Ctx* c, hipStream_t st, const RtSave* sv) {
   return CFD_OK;
 }
 
-int enqueue_rows(Ctx* c, hipStream_t st, int row0, int Be) {
+int enqueue_rows(Ctx* c, hipStream_t st) {
   const Problem& p = c->w->pb;
-  const int nl = c->nl, L = p.L;
-  const long long M = (long long)Be * L;
-  if (p.tmode == 2 && (row0 != 0 || Be != p.Be)) return fail(CFD_E_ARG, "a level batch runs as one chunk (rows %d + %d of %d)", row0, Be, p.Be);
+  const int nl = c->nl, L = p.L, Be = p.Be;
+  const long long M = p.M;
   const int* dstep = p.tmode ? c->w->d_step.as<int>() + 1 : c->w->d_step.as<int>();
   const long long ROWB = CFD_D * 4;  // bytes per SP row of 512
   const dim3 blk(256);
-  const char* sample_sp = c->w->sample_sp.as<char>() + (size_t)row0 * L * CFD_LAT * 4;
-  float* eps_out = c->w->eps.as<float>() + (size_t)row0 * L * CFD_LAT;
-  const int* mapj[CFD_NMEM];
-  float* attj[CFD_NMEM];
   bool want_att = false;
-  for (int j = 0; j < CFD_NMEM; ++j) {
-    mapj[j] = p.map[j] + row0;
-    attj[j] = p.att[j] ? p.att[j] + (size_t)row0 * nl * L * p.S[j] : nullptr;
-    want_att = want_att || p.att[j];
-  }
+  for (int j = 0; j < CFD_NMEM; ++j) want_att = want_att || p.att[j];
   if (p.att_fused) want_att = false;   // (the ring of a sampling run on the tile kernels: the fused kernel keeps the maps itself)
   // one fused kernel per layer for the cross-attention block, unless att_mats are wanted
-  const bool fused_x = c->fused_xattn && p.xa_nwg > 0 && !want_att && row0 == 0 && Be == p.Be;
+  const bool fused_x = c->fused_xattn && p.xa_nwg > 0 && !want_att;
 
   // rows that run the replica-independent head of the network (see Problem::share_B)
-  const bool share = p.share_B > 0 && row0 == 0 && Be == p.Be && Be % p.share_B == 0 && Be > p.share_B && !c->stop_stage;
+  const bool share = p.share_B > 0 && Be % p.share_B == 0 && Be > p.share_B && !c->stop_stage;
   const int Bs = share ? p.share_B : Be;
   const long long Ms = (long long)Bs * L;
   // 1. latent embedding + body/hand embedding + query PE          (denoiser.py:187,316-326)
   {
     GemmArgs a = gemm_args();
-    a.X[0] = c->we_sp.as<char>(); a.ldx[0] = CFD_LAT * 4; a.I[0] = CFD_D; a.Iclamp[0] = CFD_D; a.kt[0] = CFD_LAT / 32;
-    a.Y = sample_sp; a.ldy = CFD_LAT * 4; a.J = (int)Ms; a.Jclamp = (int)Ms;
+    gemm_x(a, 0, c->we_sp.as<char>(), CFD_D, CFD_LAT, CFD_LAT * 4);
+    gemm_y(a, c->w->sample_sp.as<char>(), (int)Ms, CFD_LAT * 4);
     EpiEmbed e{c->w->x.as<float>(), rawp(c, "latent_embd.bias"), rawp(c, "bh_embedding.weight"), rawp(c, "query_pos.pe"), L};
     CHK((run_gemm<MODE_PLAIN>(c, CFD_PROF_GEMM_TOKEN, a, e, 1, 1, st)));
   }
   if (c->stop_stage == 1) return CFD_OK;
   // This step's rows of the per-step tables (as on the row-tile path, enqueue_rows_rt): with one timestep for all rows, a sampling run
-  // refreshes fixed buffers with ONE launch at the start of the iteration and cfd_forward points at its single table row, so that no
-  // launch has the step index as a dependent scalar load in front of its operand loads (a load that misses in every XCD's L2 after the
-  // previous iteration's last workgroup has written it: ~1 us on 18 AdaLN launches and 9 cross-attention prologues per step).
+  // reads their copies in rt_cur (refresh_step_rows) and cfd_forward points at its single table row, so that no launch has the step
+  // index as a dependent scalar load in front of its operand loads (a load that misses in every XCD's L2 after the previous
+  // iteration's last workgroup has written it: ~1 us on 18 AdaLN launches and 9 cross-attention prologues per step).
   const float* ss_now = c->w->ss_tab.as<float>();
   const float *kb_now[CFD_NMEM], *vb_now[CFD_NMEM];
   for (int j = 0; j < CFD_NMEM; ++j) { kb_now[j] = c->w->kbtab[j].as<float>(); vb_now[j] = c->w->vbtab[j].as<float>(); }
   const bool rows_now = p.tmode == 0;
   if (rows_now && p.T > 1) {
-    RtStepRowsArgs ra;
-    memset(&ra, 0, sizeof(ra));
-    size_t off4 = 0;
-    int nt = 0, nwg = 0;
-    auto add = [&](const float*& now, int nfloat) {
-      float* dst = c->w->rt_cur.as<float>() + off4 * 4;
-      ra.src[nt] = now; ra.dst[nt] = dst; ra.n4[nt] = nfloat / 4; ra.first[nt] = nwg;
-      nwg += (nfloat / 4 + 255) / 256; off4 += (size_t)(nfloat / 4 + 63) / 64 * 64; ++nt;
-      now = dst;
-    };
-    size_t need4 = (size_t)(nl * 4 * CFD_D / 4 + 64);
-    for (int j = 0; j < CFD_NMEM; ++j) need4 += (size_t)((nl * CFD_D + 32) / 4 + 64) + (size_t)(nl * CFD_D / 4 + 64);
-    CHK(c->w->rt_cur.ensure(need4 * 16));
-    add(ss_now, nl * 4 * CFD_D);
+    std::vector<StepTab> tabs{{&ss_now, nl * 4 * CFD_D}};
     for (int j = 0; j < CFD_NMEM; ++j)
-      if ((p.static_mask >> j) & 1) { add(kb_now[j], nl * CFD_D + 32); add(vb_now[j], nl * CFD_D); }
-    ra.ntab = nt; ra.first[nt] = nwg; ra.d_step = dstep;
-    LAUNCH(CFD_PROF_OTHER, rt_step_rows_kernel<>, dim3(nwg), dim3(256), st, ra);
+      if ((p.static_mask >> j) & 1) { tabs.push_back({&kb_now[j], nl * CFD_D + 32}); tabs.push_back({&vb_now[j], nl * CFD_D}); }
+    CHK(refresh_step_rows(c, st, dstep, tabs));
   }
   auto ln = [&](const float* g, const float* b, int adaln, int tbidx, char* out, long long rows) -> int {
     LnArgs a{c->w->x.as<float>(), out, rows, g, b, adaln, (rows_now ? ss_now : c->w->ss_tab.as<float>()) + (size_t)tbidx * 2 * CFD_D,
              (long long)nl * 2 * 2 * CFD_D, rows_now ? nullptr : dstep, p.tmode, p.tmode == 2 ? L * p.lv_rows : L,
-             p.tmode == 2 ? p.lv_i0 : row0};   // (a level batch, always one chunk: table row lv_i0 + level, Problem::lv_rows rows per level)
+             p.tmode == 2 ? p.lv_i0 : 0};   // (a level batch: table row lv_i0 + level, Problem::lv_rows rows per level)
     LAUNCH(CFD_PROF_ROWS, ln_rows_kernel<>, dim3((unsigned)((rows + 3) / 4)), blk, st, a);
     return CFD_OK;
   };
   auto token_gemm_resid = [&](const DBuf& w, int K, const char* y, const float* bias, long long rows) -> int {
     GemmArgs a = gemm_args();
-    a.X[0] = w.as<char>(); a.ldx[0] = (long long)K * 4; a.I[0] = CFD_D; a.Iclamp[0] = CFD_D; a.kt[0] = K / 32;
-    a.Y = y; a.ldy = (long long)K * 4; a.J = (int)rows; a.Jclamp = (int)rows;
+    gemm_x(a, 0, w.as<char>(), CFD_D, K, (long long)K * 4);
+    gemm_y(a, y, (int)rows, (long long)K * 4);
     EpiResid e{c->w->x.as<float>(), 0, bias};
     return run_gemm<MODE_PLAIN>(c, CFD_PROF_GEMM_TOKEN, a, e, 1, 1, st);
   };
@@ -297,13 +286,13 @@ int enqueue_rows(Ctx* c, hipStream_t st, int row0, int Be) {
   // per-row slot statistics, and the consumer (q | k | v^T in one launch, FFN1, latent_proj) runs on W diag(gamma) and rescales its accumulators.
   // Range: the launches launch_gemm gives the 64 x 64 / 128 x 64 classes anyway (launch_gemm_midsize); above it a ln_rows launch costs less than
   // the producer's wider epilogue (measured at the headline shape: +25.8 us against 14).
-  const bool ln_fold = c->ln_fold != 0 && L == 16 && !c->stop_stage && row0 == 0 && Be == p.Be &&
+  const bool ln_fold = c->ln_fold != 0 && L == 16 && !c->stop_stage &&
                        (c->ln_fold > 0 || (M >= 512 && M <= 3840));   // (below: the row-tile path or a handful of workgroups; above: launch_gemm's 128 x 128 class)
   if (ln_fold) CHK(c->w->ln_stat.ensure((size_t)M * LN_SLOTS * 2 * 4));
   auto token_gemm_resid_stat = [&](const DBuf& w, int K, const char* y, const float* bias, long long rows, char* xs) -> int {
     GemmArgs a = gemm_args();
-    a.X[0] = w.as<char>(); a.ldx[0] = (long long)K * 4; a.I[0] = CFD_D; a.Iclamp[0] = CFD_D; a.kt[0] = K / 32;
-    a.Y = y; a.ldy = (long long)K * 4; a.J = (int)rows; a.Jclamp = (int)rows;
+    gemm_x(a, 0, w.as<char>(), CFD_D, K, (long long)K * 4);
+    gemm_y(a, y, (int)rows, (long long)K * 4);
     EpiResidStat e{c->w->x.as<float>(), 0, bias, xs, c->w->ln_stat.as<float>()};
     return run_gemm_midsize<MODE_PLAIN>(c, CFD_PROF_GEMM_TOKEN, a, e, st);
   };
@@ -333,23 +322,20 @@ int enqueue_rows(Ctx* c, hipStream_t st, int row0, int Be) {
       // tiles of a token panel consecutive on one XCD (gemm_sp_body's block order), so h_sp is fetched once.  The bias covers q | k; its
       // last 512 entries are zeros (the value bias is folded into the out-projection's).
       GemmArgs a = gemm_args();
-      a.X[0] = w.wqkv_sp.as<char>(); a.ldx[0] = ROWB; a.I[0] = 3 * CFD_D; a.Iclamp[0] = 3 * CFD_D; a.kt[0] = CFD_D / 32;
-      a.Y = c->w->h_sp.as<char>(); a.ldy = ROWB; a.J = (int)Ma; a.Jclamp = (int)Ma;
+      gemm_x(a, 0, w.wqkv_sp.as<char>(), 3 * CFD_D, CFD_D, ROWB);
+      gemm_y(a, c->w->h_sp.as<char>(), (int)Ma, ROWB);
       EpiSplit e{c->w->qkv_sp.as<char>(), 3 * ROWB, 0, 0, w.bqk.as<float>(), 0, 0};
       if (L == 16) {
         // batch rows of exactly 16 tokens: q | k and v in ONE grouped launch, the value projection stored transposed by the epilogue (EpiQkvT)
         GemmArgs ag = a;
         ag.nslot = 2;
-        ag.I[0] = 2 * CFD_D; ag.Iclamp[0] = 2 * CFD_D;
-        ag.X[1] = w.wqkv_sp.as<char>() + 2 * CFD_D * ROWB; ag.ldx[1] = ROWB; ag.I[1] = CFD_D; ag.Iclamp[1] = CFD_D; ag.kt[1] = CFD_D / 32;
+        gemm_x(ag, 0, w.wqkv_sp.as<char>(), 2 * CFD_D, CFD_D, ROWB);
+        gemm_x(ag, 1, w.wqkv_sp.as<char>() + 2 * CFD_D * ROWB, CFD_D, CFD_D, ROWB);
         EpiQkvT eg{c->w->qkv_sp.as<char>(), 2 * ROWB, w.bqk.as<float>(), c->w->vts_sp.as<char>(), 1};
         if (h_raw) {   // (layers 1..: the previous layer's second FFN product left raw rows + statistics)
-          EpiLn<EpiQkvT> el;
-          static_cast<EpiQkvT&>(el) = eg;
           const float* cd = w.ln_cd.as<float>();
-          el.ln_stat = c->w->ln_stat.as<float>(); el.ln_c[0] = cd; el.ln_d[0] = cd + 1024; el.ln_c[1] = cd + 2048; el.ln_d[1] = cd + 2560; el.ln_eps = 1e-5f;
           ag.X[0] = w.wqk_f.as<char>(); ag.X[1] = w.wv_f.as<char>();
-          CHK((run_gemm_midsize<MODE_GROUPED>(c, CFD_PROF_GEMM_TOKEN, ag, el, st)));
+          CHK((run_gemm_midsize<MODE_GROUPED>(c, CFD_PROF_GEMM_TOKEN, ag, epi_ln(eg, c->w->ln_stat.as<float>(), cd, cd + 1024, cd + 2048, cd + 2560, 1e-5f), st)));
         } else
         CHK((run_gemm<MODE_GROUPED>(c, CFD_PROF_GEMM_TOKEN, ag, eg, 1, 1, st)));
         qkv_one_launch = true;
@@ -449,7 +435,7 @@ int enqueue_rows(Ctx* c, hipStream_t st, int row0, int Be) {
     // Three-launch path (att_mats wanted): scores against the folded keys of every memory.  Long memories and short
     // (<= 64 keys) memories go to different tile shapes; rows in a shared-memory run of the largest memory use one
     // un-batched product per run.
-    const bool runs = p.nruns > 0 && row0 == 0 && Be == p.Be;
+    const bool runs = p.nruns > 0;
     auto scores_grouped = [&](bool small, int skip_j, const int* brow, int nb) -> int {
       GemmArgs a = gemm_args();
       EpiF32 e;
@@ -457,15 +443,15 @@ int enqueue_rows(Ctx* c, hipStream_t st, int row0, int Be) {
       int n = 0;
       for (int j = 0; j < CFD_NMEM; ++j) {
         if ((p.Sp[j] <= 64) != small || j == skip_j) continue;
-        a.X[n] = c->w->kall_sp[j].as<char>() + (size_t)l * p.U[j] * p.Sp[j] * ROWB; a.ldx[n] = ROWB;
-        a.xbs[n] = (long long)p.Sp[j] * ROWB; a.xmap[n] = mapj[j];
-        a.I[n] = p.Sp[j]; a.Iclamp[n] = p.Sp[j]; a.kt[n] = CFD_D / 32;
-        e.goff[n] = p.off[j]; e.gbias[n] = c->w->cb[j].as<float>() + (size_t)l * p.U[j] * p.Sp[j]; e.gmap[n] = mapj[j]; e.gstride[n] = p.Sp[j];
+        gemm_x(a, n, c->w->kall_sp[j].as<char>() + (size_t)l * p.U[j] * p.Sp[j] * ROWB, p.Sp[j], CFD_D, ROWB);
+        a.xbs[n] = (long long)p.Sp[j] * ROWB; a.xmap[n] = p.map[j];
+        e.goff[n] = p.off[j]; e.gbias[n] = c->w->cb[j].as<float>() + (size_t)l * p.U[j] * p.Sp[j]; e.gmap[n] = p.map[j]; e.gstride[n] = p.Sp[j];
         ++n;
       }
       if (!n || nb <= 0) return CFD_OK;
       a.nslot = n; a.brow = brow;
-      a.Y = c->w->h_sp.as<char>(); a.ldy = ROWB; a.ybs = (long long)L * ROWB; a.J = L; a.Jclamp = L;
+      gemm_y(a, c->w->h_sp.as<char>(), L, ROWB);
+      a.ybs = (long long)L * ROWB;
       e.out = c->w->sc.as<float>(); e.ldo = p.Sp_tot; e.obs = (long long)L * p.Sp_tot;
       return run_gemm<MODE_GROUPED>(c, CFD_PROF_GEMM_ATTN, a, e, nb, 1, st);
     };
@@ -478,9 +464,8 @@ int enqueue_rows(Ctx* c, hipStream_t st, int row0, int Be) {
       const int j = p.jbig;
       for (int r = 0; r < p.nruns; ++r) {
         GemmArgs a = gemm_args();
-        a.X[0] = c->w->kall_sp[j].as<char>() + ((size_t)l * p.U[j] + p.run_u[r]) * p.Sp[j] * ROWB; a.ldx[0] = ROWB;
-        a.I[0] = p.Sp[j]; a.Iclamp[0] = p.Sp[j]; a.kt[0] = CFD_D / 32;
-        a.Y = c->w->h_sp.as<char>() + (size_t)p.run_row0[r] * L * ROWB; a.ldy = ROWB; a.J = p.run_len[r] * L; a.Jclamp = a.J;
+        gemm_x(a, 0, c->w->kall_sp[j].as<char>() + ((size_t)l * p.U[j] + p.run_u[r]) * p.Sp[j] * ROWB, p.Sp[j], CFD_D, ROWB);
+        gemm_y(a, c->w->h_sp.as<char>() + (size_t)p.run_row0[r] * L * ROWB, p.run_len[r] * L, ROWB);
         EpiF32 e;
         memset(&e, 0, sizeof(e));
         e.out = c->w->sc.as<float>() + (size_t)p.run_row0[r] * L * p.Sp_tot; e.ldo = p.Sp_tot; e.goff[0] = p.off[j];
@@ -493,7 +478,7 @@ int enqueue_rows(Ctx* c, hipStream_t st, int row0, int Be) {
       memset(&a, 0, sizeof(a));
       a.sc = c->w->sc.as<float>(); a.P = c->w->p_sp.as<char>(); a.ld = p.Sp_tot; a.rows = M; a.rows_per_b = L; a.nseg = CFD_NMEM;
       for (int j = 0; j < CFD_NMEM; ++j) {
-        a.off[j] = p.off[j]; a.S[j] = p.S[j]; a.Sp[j] = p.Sp[j]; a.mask[j] = p.mask[j]; a.has_mask[j] = p.has_mask[j]; a.map[j] = mapj[j]; a.att[j] = attj[j];
+        a.off[j] = p.off[j]; a.S[j] = p.S[j]; a.Sp[j] = p.Sp[j]; a.mask[j] = p.mask[j]; a.has_mask[j] = p.has_mask[j]; a.map[j] = p.map[j]; a.att[j] = p.att[j];
       }
       a.layer = l; a.nl = nl;
       LAUNCH(CFD_PROF_ROWS, softmax_rows_kernel<>, dim3((unsigned)((M + 3) / 4)), blk, st, a);
@@ -505,14 +490,14 @@ int enqueue_rows(Ctx* c, hipStream_t st, int row0, int Be) {
       int n = 0;
       for (int j = 0; j < CFD_NMEM; ++j) {
         if (j == skip_j) continue;
-        a.X[n] = c->w->vt_all[j].as<char>() + (size_t)l * p.U[j] * CFD_D * p.Sp[j] * 4; a.ldx[n] = (long long)p.Sp[j] * 4;
-        a.xbs[n] = (long long)CFD_D * p.Sp[j] * 4; a.xmap[n] = mapj[j];
-        a.kt[n] = p.Sp[j] / 32; a.yk0[n] = p.off[j] / 32;
-        a.I[n] = CFD_D; a.Iclamp[n] = CFD_D;
+        gemm_x(a, n, c->w->vt_all[j].as<char>() + (size_t)l * p.U[j] * CFD_D * p.Sp[j] * 4, CFD_D, p.Sp[j], (long long)p.Sp[j] * 4);
+        a.xbs[n] = (long long)CFD_D * p.Sp[j] * 4; a.xmap[n] = p.map[j];
+        a.yk0[n] = p.off[j] / 32;
         ++n;
       }
       a.nslot = n; a.brow = brow;
-      a.Y = c->w->p_sp.as<char>(); a.ldy = (long long)p.Sp_tot * 4; a.ybs = (long long)L * p.Sp_tot * 4; a.J = L; a.Jclamp = L;
+      gemm_y(a, c->w->p_sp.as<char>(), L, (long long)p.Sp_tot * 4);
+      a.ybs = (long long)L * p.Sp_tot * 4;
       EpiResid e{c->w->x.as<float>(), (long long)L * CFD_D, w.cross_bias.as<float>()};
       return run_gemm<MODE_SEGK>(c, CFD_PROF_GEMM_ATTN, a, e, nb, 1, st);
     };
@@ -524,10 +509,8 @@ int enqueue_rows(Ctx* c, hipStream_t st, int row0, int Be) {
       const int j = p.jbig;
       for (int r = 0; r < p.nruns; ++r) {   // ... then the shared audio memory, run by run (disjoint rows)
         GemmArgs a = gemm_args();
-        a.X[0] = c->w->vt_all[j].as<char>() + ((size_t)l * p.U[j] + p.run_u[r]) * CFD_D * p.Sp[j] * 4; a.ldx[0] = (long long)p.Sp[j] * 4;
-        a.I[0] = CFD_D; a.Iclamp[0] = CFD_D; a.kt[0] = p.Sp[j] / 32;
-        a.Y = c->w->p_sp.as<char>() + (size_t)p.run_row0[r] * L * p.Sp_tot * 4 + (size_t)(p.off[j] / 32) * 128;
-        a.ldy = (long long)p.Sp_tot * 4; a.J = p.run_len[r] * L; a.Jclamp = a.J;
+        gemm_x(a, 0, c->w->vt_all[j].as<char>() + ((size_t)l * p.U[j] + p.run_u[r]) * CFD_D * p.Sp[j] * 4, CFD_D, p.Sp[j], (long long)p.Sp[j] * 4);
+        gemm_y(a, c->w->p_sp.as<char>() + (size_t)p.run_row0[r] * L * p.Sp_tot * 4 + (size_t)(p.off[j] / 32) * 128, p.run_len[r] * L, (long long)p.Sp_tot * 4);
         EpiResid e{c->w->x.as<float>() + (size_t)p.run_row0[r] * L * CFD_D, 0, nullptr};
         CHK((run_gemm<MODE_PLAIN>(c, CFD_PROF_GEMM_ATTN, a, e, 1, 1, st)));
       }
@@ -542,16 +525,13 @@ int enqueue_rows(Ctx* c, hipStream_t st, int row0, int Be) {
     // ---- g. FFN                                                                 (:659-661)
     {
       GemmArgs a = gemm_args();
-      a.X[0] = w.w1_sp.as<char>(); a.ldx[0] = ROWB; a.I[0] = CFD_FF; a.Iclamp[0] = CFD_FF; a.kt[0] = CFD_D / 32;
-      a.Y = c->w->h_sp.as<char>(); a.ldy = ROWB; a.J = (int)M; a.Jclamp = (int)M;
+      gemm_x(a, 0, w.w1_sp.as<char>(), CFD_FF, CFD_D, ROWB);
+      gemm_y(a, c->w->h_sp.as<char>(), (int)M, ROWB);
       EpiSplit e{c->w->u_sp.as<char>(), (long long)CFD_FF * 4, 0, 0, w.b1, 1, 0};
       if (ln_fold) {
-        EpiLn<EpiSplit> el;
-        static_cast<EpiSplit&>(el) = e;
         const float* cd = w.ln_cd.as<float>();
-        el.ln_stat = c->w->ln_stat.as<float>(); el.ln_c[0] = el.ln_c[1] = cd + 3072; el.ln_d[0] = el.ln_d[1] = cd + 4096; el.ln_eps = 1e-5f;
         a.X[0] = w.w1_f.as<char>(); a.Y = c->w->o_sp.as<char>();
-        CHK((run_gemm_midsize<MODE_PLAIN>(c, CFD_PROF_GEMM_TOKEN, a, el, st)));
+        CHK((run_gemm_midsize<MODE_PLAIN>(c, CFD_PROF_GEMM_TOKEN, a, epi_ln(e, c->w->ln_stat.as<float>(), cd + 3072, cd + 4096, cd + 3072, cd + 4096, 1e-5f), st)));
       } else
       CHK((run_gemm<MODE_PLAIN>(c, CFD_PROF_GEMM_TOKEN, a, e, 1, 1, st)));
     }
@@ -568,18 +548,15 @@ int enqueue_rows(Ctx* c, hipStream_t st, int row0, int Be) {
   // 7. final norm (made above) + latent projection                                (cross_attention.py:238-239, denoiser.py:382)
   {
     GemmArgs a = gemm_args();
-    a.X[0] = c->wp_sp.as<char>(); a.ldx[0] = ROWB; a.I[0] = CFD_LAT; a.Iclamp[0] = CFD_LAT; a.kt[0] = CFD_D / 32;
-    a.Y = c->w->h_sp.as<char>(); a.ldy = ROWB; a.J = (int)M; a.Jclamp = (int)M;
+    gemm_x(a, 0, c->wp_sp.as<char>(), CFD_LAT, CFD_D, ROWB);
+    gemm_y(a, c->w->h_sp.as<char>(), (int)M, ROWB);
     EpiF32 e;
     memset(&e, 0, sizeof(e));
-    e.out = eps_out; e.ldo = CFD_LAT; e.bias = rawp(c, "latent_proj.bias");
+    e.out = c->w->eps.as<float>(); e.ldo = CFD_LAT; e.bias = rawp(c, "latent_proj.bias");
     if (h_raw) {
-      EpiLn<EpiF32> el;
-      static_cast<EpiF32&>(el) = e;
       const float* cd = c->ln_cd_p.as<float>();
-      el.ln_stat = c->w->ln_stat.as<float>(); el.ln_c[0] = el.ln_c[1] = cd; el.ln_d[0] = el.ln_d[1] = cd + CFD_LAT; el.ln_eps = 1e-5f;
       a.X[0] = c->wp_f.as<char>();
-      CHK((run_gemm_midsize<MODE_PLAIN>(c, CFD_PROF_GEMM_TOKEN, a, el, st)));
+      CHK((run_gemm_midsize<MODE_PLAIN>(c, CFD_PROF_GEMM_TOKEN, a, epi_ln(e, c->w->ln_stat.as<float>(), cd, cd + CFD_LAT, cd, cd + CFD_LAT, 1e-5f), st)));
     } else
     CHK((run_gemm<MODE_PLAIN>(c, CFD_PROF_GEMM_TOKEN, a, e, 1, 1, st)));
   }
@@ -591,10 +568,6 @@ int enqueue_rows(Ctx* c, hipStream_t st, int row0, int Be) {
     LAUNCH(CFD_PROF_ROWS, att_fixup_kernel<>, dim3((unsigned)(p.att_nb * L), nl), dim3(256), st, f);
   }
   return CFD_OK;
-}
-
-int run_gemm_plain_f32(Ctx* c, int cls, const GemmArgs& a, const EpiF32& e, int nb, int nz, hipStream_t st) {
-  return run_gemm<MODE_PLAIN>(c, cls, a, e, nb, nz, st);
 }
 
 // ---- cfd_forward ---------------------------------------------------------------------------------------
@@ -694,15 +667,13 @@ extern "C" int cfd_test_gemm(cfd_handle c, const float* X, const float* Y, float
   DBuf xs, ys;
   CHK(xs.ensure((size_t)I * K * 4));
   CHK(ys.ensure((size_t)J * K * 4));
-  long long n = (long long)I * (K / 8);
   CHK(enqueue_to_split(c, CFD_PROF_OTHER, st, X, xs.as<char>(), (long long)I, K, (long long)K,
                      (long long)K * 4, nullptr));
-  n = (long long)J * (K / 8);
   CHK(enqueue_to_split(c, CFD_PROF_OTHER, st, Y, ys.as<char>(), (long long)J, K, (long long)K,
                      (long long)K * 4, nullptr));
   GemmArgs a = gemm_args();
-  a.X[0] = xs.as<char>(); a.ldx[0] = (long long)K * 4; a.I[0] = I; a.Iclamp[0] = I; a.kt[0] = K / 32;
-  a.Y = ys.as<char>(); a.ldy = (long long)K * 4; a.J = J; a.Jclamp = J;
+  gemm_x(a, 0, xs.as<char>(), I, K, (long long)K * 4);
+  gemm_y(a, ys.as<char>(), J, (long long)K * 4);
   EpiF32 e;
   memset(&e, 0, sizeof(e));
   e.out = out; e.ldo = I;
@@ -755,17 +726,16 @@ extern "C" int cfd_test_gemm_epi(cfd_handle c, cfd_test_epi_args* t, void* strea
   }
   GemmArgs a = gemm_args();
   const int I0 = qkvt ? 2 * CFD_D : I;
-  a.X[0] = tmp.xs.as<char>(); a.ldx[0] = (long long)K * 4; a.I[0] = I0; a.Iclamp[0] = I0; a.kt[0] = K / 32;
+  gemm_x(a, 0, tmp.xs.as<char>(), I0, K, (long long)K * 4);
   if (qkvt) {
     a.nslot = 2;
-    a.X[1] = tmp.xs.as<char>() + (size_t)I0 * K * 4; a.ldx[1] = (long long)K * 4; a.I[1] = CFD_D; a.Iclamp[1] = CFD_D; a.kt[1] = K / 32;
+    gemm_x(a, 1, tmp.xs.as<char>() + (size_t)I0 * K * 4, CFD_D, K, (long long)K * 4);
   }
-  a.Y = y; a.ldy = (long long)K * 4; a.J = J; a.Jclamp = J;
+  gemm_y(a, y, J, (long long)K * 4);
   const float* cd = tmp.cd.as<float>();
-  auto fold_of = [&](auto& el) {
-    el.ln_stat = t->ln_stat; el.ln_eps = t->ln_eps;
-    el.ln_c[0] = el.ln_c[1] = cd; el.ln_d[0] = el.ln_d[1] = cd + I;
-    if (qkvt) { el.ln_c[1] = cd + I0; el.ln_d[1] = cd + I + I0; }
+  auto fold_of = [&](const auto& e) {   // (q | k | v^T: group 1 is the value projection, rows I0.. of the weight)
+    const int g1 = qkvt ? I0 : 0;
+    return epi_ln(e, t->ln_stat, cd, cd + I, cd + g1, cd + I + g1, t->ln_eps);
   };
   auto cfg_used = [](int cfg) { return cfg == 1 || cfg == 6 || cfg == 19 || cfg == 20 || cfg == 24 ? cfg : 3; };   // (launch_gemm's default: 3)
   auto plain = [&](const auto& e) -> hipError_t {
@@ -794,27 +764,18 @@ extern "C" int cfd_test_gemm_epi(cfd_handle c, cfd_test_epi_args* t, void* strea
       break;
     }
     case CFD_EPI_LN_F32: {
-      EpiLn<EpiF32> el;
-      static_cast<EpiF32&>(el) = ef;
-      fold_of(el);
       t->tile_cfg_used = gemm_midsize_cfg<MODE_PLAIN>(a);
-      err = launch_gemm_midsize<MODE_PLAIN>(a, el, st);
+      err = launch_gemm_midsize<MODE_PLAIN>(a, fold_of(ef), st);
       break;
     }
     case CFD_EPI_LN_SPLIT: {
-      EpiLn<EpiSplit> el;
-      static_cast<EpiSplit&>(el) = es;
-      fold_of(el);
       t->tile_cfg_used = gemm_midsize_cfg<MODE_PLAIN>(a);
-      err = launch_gemm_midsize<MODE_PLAIN>(a, el, st);
+      err = launch_gemm_midsize<MODE_PLAIN>(a, fold_of(es), st);
       break;
     }
     default: {
-      EpiLn<EpiQkvT> el;
-      static_cast<EpiQkvT&>(el) = eq;
-      fold_of(el);
       t->tile_cfg_used = gemm_midsize_cfg<MODE_GROUPED>(a);
-      err = launch_gemm_midsize<MODE_GROUPED>(a, el, st);
+      err = launch_gemm_midsize<MODE_GROUPED>(a, fold_of(eq), st);
       break;
     }
   }
@@ -835,21 +796,17 @@ extern "C" int cfd_bench_gemm(cfd_handle c, int I, int J, int K, int tile_cfg, i
   CHK(ys.ensure((size_t)J * K * 4));
   CHK(out.ensure((size_t)J * I * 4));
   HIPCHK(hipMemset(out.p, 0, (size_t)J * I * 4));
-  long long n = (long long)I * K / 4;
   CHK(enqueue_philox_fill(xf.as<float>(), 1, I * K, 1ull, 0u, 0u, 3u, 0.05f, 0));
-  n = (long long)J * K / 4;
   CHK(enqueue_philox_fill(yf.as<float>(), 1, (int)((long long)J * K), 2ull, 0u, 0u, 3u, 1.0f, 0));
   if (getenv("CFD_BENCH_ZERO")) {   // power/clock probe: all-zero operands
     HIPCHK(hipMemset(xf.p, 0, (size_t)I * K * 4));
     HIPCHK(hipMemset(yf.p, 0, (size_t)J * K * 4));
   }
-  n = (long long)I * (K / 8);
   CHK(enqueue_to_split(c, CFD_PROF_OTHER, 0, xf.as<float>(), xs.as<char>(), (long long)I, K, (long long)K, (long long)K * 4, nullptr));
-  n = (long long)J * (K / 8);
   CHK(enqueue_to_split(c, CFD_PROF_OTHER, 0, yf.as<float>(), ys.as<char>(), (long long)J, K, (long long)K, (long long)K * 4, nullptr));
   GemmArgs a = gemm_args();
-  a.X[0] = xs.as<char>(); a.ldx[0] = (long long)K * 4; a.I[0] = I; a.Iclamp[0] = I; a.kt[0] = K / 32;
-  a.Y = ys.as<char>(); a.ldy = (long long)K * 4; a.J = J; a.Jclamp = J;
+  gemm_x(a, 0, xs.as<char>(), I, K, (long long)K * 4);
+  gemm_y(a, ys.as<char>(), J, (long long)K * 4);
   EpiResid e{out.as<float>(), 0, nullptr};
   EpiNull en{out.as<float>()};
   EpiF32 ef;

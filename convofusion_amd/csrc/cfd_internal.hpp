@@ -406,6 +406,13 @@ static inline GemmArgs gemm_args() {
   a.nslot = 1;
   return a;
 }
+// Operand slot n of X: I rows of K columns (split pairs, row pitch ldx bytes), every row valid; the Y operand: J rows, likewise.
+static inline void gemm_x(GemmArgs& a, int n, const char* X, int I, int K, long long ldx) {
+  a.X[n] = X; a.ldx[n] = ldx; a.I[n] = I; a.Iclamp[n] = I; a.kt[n] = K / 32;
+}
+static inline void gemm_y(GemmArgs& a, const char* Y, int J, long long ldy) {
+  a.Y = Y; a.ldy = ldy; a.J = J; a.Jclamp = J;
+}
 
 #define LAUNCH(cls, kernel, grid, block, st, ...) LAUNCH_AS(cls, #kernel, kernel, grid, block, st, __VA_ARGS__)
 // (name: what a failed launch is called in the error -- for a kernel chosen through a template, whose expression names no instance)
@@ -498,10 +505,9 @@ int enqueue_time_tables(Ctx* c, int T, hipStream_t st);
 int prepare_static_memside(Ctx* c, hipStream_t st, int dynamic_mask, bool want_att, bool reuse = false);
 int enqueue_memside(Ctx* c, hipStream_t st);
 // cfd_forward.hip: the launches of one denoiser forward
-int enqueue_rows(Ctx* c, hipStream_t st, int row0, int nrows);
+int enqueue_rows(Ctx* c, hipStream_t st);
 int enqueue_rows_rt(Ctx* c, hipStream_t st, const RtSave* sv = nullptr);
 int enqueue_denoise(Ctx* c, hipStream_t st);
-int run_gemm_plain_f32(Ctx* c, int cls, const GemmArgs& a, const EpiF32& e, int nb, int nz, hipStream_t st);   // (the unit that holds the EpiF32 instances)
 // cfd_sample.hip
 int enqueue_philox_fill(float* out, int B, int per_utt, uint64_t seed, uint32_t step, uint32_t utt0, uint32_t stream_id, float scale, hipStream_t st);
 // cfd_blocks.hip

@@ -472,6 +472,28 @@ int enqueue_time_tables(Ctx* c, int T, hipStream_t st) {
   return CFD_OK;
 }
 
+// Folded keys and folded values^T of memory j for ALL layers, from its normalised rows n_sp[j]: KA = A n (+ per layer c_l . n into `ck`,
+// -inf on dead keys) and VA^T.  Their epilogues count into the handle's census.
+static int enqueue_mem_kv(Ctx* c, hipStream_t st, int j, float* ck) {
+  const Problem& p = c->w->pb;
+  const int nl = c->nl, rows = p.U[j] * p.Sp[j];
+  const long long ROWB = CFD_D * 4;
+  {
+    GemmArgs a = gemm_args();
+    gemm_x(a, 0, c->wk_all_sp[j].as<char>(), nl * CFD_D + 32, CFD_D, ROWB);
+    gemm_y(a, c->w->n_sp[j].as<char>(), rows, ROWB);
+    a.super_i = 8; a.super_j = 8;
+    EpiMemK e{c->w->kall_sp[j].as<char>(), (long long)rows, ck, nl * CFD_D, nl, p.mask[j], p.S[j], p.Sp[j], c->sat_mem()};
+    CHK((run_gemm<MODE_PLAIN>(c, CFD_PROF_GEMM_MEM, a, e, 1, 1, st)));
+  }
+  GemmArgs a = gemm_args();
+  gemm_x(a, 0, c->w->n_sp[j].as<char>(), rows, CFD_D, ROWB);
+  gemm_y(a, c->wv_all_sp[j].as<char>(), nl * CFD_D, ROWB);
+  a.super_i = 8; a.super_j = 8;
+  EpiMemV e{c->w->vt_all[j].as<char>(), p.Sp[j], p.U[j], c->sat_mem()};
+  return run_gemm<MODE_PLAIN>(c, CFD_PROF_GEMM_MEM, a, e, 1, 1, st);
+}
+
 // Once per cfd_forward / sampling run, after the time tables: the part of the memory-side work that does not depend on the
 // timestep (see rows.hpp, mem_center_kernel, and xattn_fused.hpp).  Memories in `dynamic_mask` (contents rewritten between the
 // iterations of a run: the dyadic rollout's partner projection) keep their per-step projections, and so does every memory when
@@ -508,7 +530,6 @@ int prepare_static_memside(Ctx* c, hipStream_t st, int dynamic_mask, bool want_a
   CHK(c->w->b_sp.ensure((size_t)T * CFD_D * 4));
   CHK(c->w->bsq.ensure((size_t)T * 4));
   if (c->w->tt_mem_mask == 0) {
-    c->w->tt_mem_mask = 0;
     LAUNCH(CFD_PROF_OTHER, temb_center_kernel<>, dim3((unsigned)((T + 3) / 4)), dim3(256), st, c->w->temb_tab.as<float>(), T, c->w->b_tab.as<float>(),
            c->w->b_sp.as<char>(), c->w->bsq.as<float>());
     c->setup_launches += 1;
@@ -526,27 +547,14 @@ int prepare_static_memside(Ctx* c, hipStream_t st, int dynamic_mask, bool want_a
     MemCenterArgs ma{p.mem[j], p.U[j], p.S[j], p.Sp[j], rawp(c, "condition_embedding.weight") + (size_t)j * CFD_D, rawp(c, "mem_pos.pe"),
                      c->w->n_sp[j].as<char>(), c->w->asq[j].as<float>(), c->sat_mem()};
     // (`reuse`: the previous cfd_forward's memories again, cfd_forward_same_memories -- a_s, KA, ca and VA^T are in place)
-    if (!reuse) LAUNCH(CFD_PROF_ROWS, mem_center_kernel<>, dim3((unsigned)((rows + 3) / 4)), dim3(256), st, ma);
-    if (!reuse) {  // KA = A a_s for all layers, ca = c_l . a_s (-inf on dead keys)
-      GemmArgs a = gemm_args();
-      a.X[0] = c->wk_all_sp[j].as<char>(); a.ldx[0] = ROWB; a.I[0] = NK; a.Iclamp[0] = NK; a.kt[0] = CFD_D / 32;
-      a.Y = c->w->n_sp[j].as<char>(); a.ldy = ROWB; a.J = rows; a.Jclamp = rows;
-      a.super_i = 8; a.super_j = 8;
-      EpiMemK e{c->w->kall_sp[j].as<char>(), (long long)rows, c->w->ca[j].as<float>(), nl * CFD_D, nl, p.mask[j], p.S[j], p.Sp[j], c->sat_mem()};
-      CHK((run_gemm<MODE_PLAIN>(c, CFD_PROF_GEMM_MEM, a, e, 1, 1, st)));
-    }
-    if (!reuse) {  // VA^T
-      GemmArgs a = gemm_args();
-      a.X[0] = c->w->n_sp[j].as<char>(); a.ldx[0] = ROWB; a.I[0] = rows; a.Iclamp[0] = rows; a.kt[0] = CFD_D / 32;
-      a.Y = c->wv_all_sp[j].as<char>(); a.ldy = ROWB; a.J = nl * CFD_D; a.Jclamp = nl * CFD_D;
-      a.super_i = 8; a.super_j = 8;
-      EpiMemV e{c->w->vt_all[j].as<char>(), p.Sp[j], p.U[j], c->sat_mem()};
-      CHK((run_gemm<MODE_PLAIN>(c, CFD_PROF_GEMM_MEM, a, e, 1, 1, st)));
+    if (!reuse) {   // a_s, then KA = A a_s and VA^T for all layers, ca = c_l . a_s
+      LAUNCH(CFD_PROF_ROWS, mem_center_kernel<>, dim3((unsigned)((rows + 3) / 4)), dim3(256), st, ma);
+      CHK(enqueue_mem_kv(c, st, j, c->w->ca[j].as<float>()));
     }
     if (!have_tb) {  // kbtab[t][:] = [A_l b_t for all l | c_l . b_t]
       GemmArgs a = gemm_args();
-      a.X[0] = c->wk_all_sp[j].as<char>(); a.ldx[0] = ROWB; a.I[0] = NK; a.Iclamp[0] = NK; a.kt[0] = CFD_D / 32;
-      a.Y = c->w->b_sp.as<char>(); a.ldy = ROWB; a.J = T; a.Jclamp = T;
+      gemm_x(a, 0, c->wk_all_sp[j].as<char>(), NK, CFD_D, ROWB);
+      gemm_y(a, c->w->b_sp.as<char>(), T, ROWB);
       EpiF32S e;
       memset(&e, 0, sizeof(e));
       e.out = c->w->kbtab[j].as<float>(); e.ldo = NK;
@@ -554,8 +562,8 @@ int prepare_static_memside(Ctx* c, hipStream_t st, int dynamic_mask, bool want_a
     }
     if (!have_tb) {  // vbtab[t][:] = VV_l b_t for all l
       GemmArgs a = gemm_args();
-      a.X[0] = c->wv_all_sp[j].as<char>(); a.ldx[0] = ROWB; a.I[0] = nl * CFD_D; a.Iclamp[0] = nl * CFD_D; a.kt[0] = CFD_D / 32;
-      a.Y = c->w->b_sp.as<char>(); a.ldy = ROWB; a.J = T; a.Jclamp = T;
+      gemm_x(a, 0, c->wv_all_sp[j].as<char>(), nl * CFD_D, CFD_D, ROWB);
+      gemm_y(a, c->w->b_sp.as<char>(), T, ROWB);
       EpiF32S e;
       memset(&e, 0, sizeof(e));
       e.out = c->w->vbtab[j].as<float>(); e.ldo = nl * CFD_D;
@@ -595,13 +603,12 @@ int prepare_static_memside(Ctx* c, hipStream_t st, int dynamic_mask, bool want_a
   return CFD_OK;
 }
 
-// memory-side work of one forward: shared by every row chunk
+// memory-side work of one forward, in front of its token-side launches (enqueue_rows)
 int enqueue_memside(Ctx* c, hipStream_t st) {
   const Problem& p = c->w->pb;
   if (p.rt) return CFD_OK;   // every memory is static and its per-step scalars are tabulated (prepare_static_memside)
   const int nl = c->nl;
   const int* dstep = p.tmode ? c->w->d_step.as<int>() + 1 : c->w->d_step.as<int>();
-  const long long ROWB = CFD_D * 4;
   const dim3 blk(256);
   // memories whose projections were made once for the run: this step's per-key scale and key bias
   {
@@ -639,24 +646,8 @@ int enqueue_memside(Ctx* c, hipStream_t st) {
   // 3. memory-side projections for ALL layers at once: folded keys (+ key bias) and folded values^T
   for (int j = 0; j < CFD_NMEM; ++j) {
     if ((p.static_mask >> j) & 1) continue;
-    const int rows = p.U[j] * p.Sp[j];
     c->memside_in_forward = true;   // these epilogues count into the handle's census: whoever waits for this stream next reads it
-    {
-      GemmArgs a = gemm_args();
-      a.X[0] = c->wk_all_sp[j].as<char>(); a.ldx[0] = ROWB; a.I[0] = nl * CFD_D + 32; a.Iclamp[0] = nl * CFD_D + 32; a.kt[0] = CFD_D / 32;
-      a.Y = c->w->n_sp[j].as<char>(); a.ldy = ROWB; a.J = rows; a.Jclamp = rows;
-      a.super_i = 8; a.super_j = 8;
-      EpiMemK e{c->w->kall_sp[j].as<char>(), (long long)rows, c->w->cb[j].as<float>(), nl * CFD_D, nl, p.mask[j], p.S[j], p.Sp[j], c->sat_mem()};
-      CHK((run_gemm<MODE_PLAIN>(c, CFD_PROF_GEMM_MEM, a, e, 1, 1, st)));
-    }
-    {
-      GemmArgs a = gemm_args();
-      a.X[0] = c->w->n_sp[j].as<char>(); a.ldx[0] = ROWB; a.I[0] = rows; a.Iclamp[0] = rows; a.kt[0] = CFD_D / 32;
-      a.Y = c->wv_all_sp[j].as<char>(); a.ldy = ROWB; a.J = nl * CFD_D; a.Jclamp = nl * CFD_D;
-      a.super_i = 8; a.super_j = 8;
-      EpiMemV e{c->w->vt_all[j].as<char>(), p.Sp[j], p.U[j], c->sat_mem()};
-      CHK((run_gemm<MODE_PLAIN>(c, CFD_PROF_GEMM_MEM, a, e, 1, 1, st)));
-    }
+    CHK(enqueue_mem_kv(c, st, j, c->w->cb[j].as<float>()));
   }
 
   return CFD_OK;

@@ -303,6 +303,11 @@ struct EpiLn : E {
   float ln_eps;
   static constexpr bool kLnFold = true;
 };
+// E wrapped for the fold; a one-group launch passes the same (c, d) pair twice
+template <class E>
+static inline EpiLn<E> epi_ln(const E& e, const float* ln_stat, const float* c0, const float* d0, const float* c1, const float* d1, float eps) {
+  return EpiLn<E>{e, ln_stat, {c0, c1}, {d0, d1}, eps};
+}
 
 struct EpiNull {  // timing experiments only: keeps the accumulators live, stores nothing
   static constexpr bool kPrefetch = false;

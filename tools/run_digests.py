@@ -1,8 +1,9 @@
 """Developer tool (GPU box): does a change of the host code that opens sampling runs leave every run kind as it was?  Opens each kind at the
 small test shape (B = 2, L = 16, memories S = (6, 20, 6, 8, 1) with pad tails (2, 0, 1, 0, 0), 4 iterations, 6 for DPM-Solver++, fixed
 seeds, the seeded test weights) and prints one line per run: the SHA-256 of the final latents' bytes, of ``read()`` after every iteration
-(``steps``), of the trajectory, the noise and the attention ring where the run has them, and N, first_iteration, chunks_evaluated and the
-non-pointer fields of the run's cfd_sample_args.  The runs are deterministic: the outputs of two trees are compared with ``diff``, and a
+(``steps``), of the trajectory, the noise and the attention ring where the run has them (``refused=`` with the library's message for a run it does not open), and N, first_iteration, chunks_evaluated and the
+non-pointer fields of the run's cfd_sample_args; then the launches of one iteration per class and the SHA-256 of three single forwards
+(``Denoiser.forward``: output and att_mats).  The runs are deterministic: the outputs of two trees are compared with ``diff``, and a
 line that differs is a change of behaviour.
 
 Usage (once in each tree):  python tools/run_digests.py > digests.txt
@@ -15,7 +16,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from convofusion_amd import sampler, scheduler  # noqa: E402
+from convofusion_amd import _lib, sampler, scheduler  # noqa: E402
 from convofusion_amd.longform import window_ties  # noqa: E402
 from oracle import inputs  # noqa: E402
 from tests.gpu_helpers import SCHED_KW, hip_denoiser, to_dev  # noqa: E402
@@ -46,7 +47,11 @@ def line(name, **parts):
 
 def run_line(name, sch, mems, masks, n=N_IT, **kw):
     """One SamplingRun, stepped one iteration at a time; returns the closed run and its final latents."""
-    run = sampler.SamplingRun(hip_denoiser(1234, 1.0), sch, mems, masks, B, L, n, seed=SEED, **kw)
+    try:
+        run = sampler.SamplingRun(hip_denoiser(1234, 1.0), sch, mems, masks, B, L, n, seed=SEED, **kw)
+    except _lib.CfdError as e:   # (a kind the developer knobs in force rule out: the attention ring on the three-launch cross-attention)
+        line(name, refused=e)
+        return None, None
     parts = {}
     try:
         h = hashlib.sha256()
@@ -127,6 +132,17 @@ def main():
                       ("dpm-solver++", scheduler.DPMSolverMultistepScheduler(prediction_type="sample", **YAML))):
         run, _ = run_line(f"{name} prediction_type=sample", sch, mems, masks, n=6 if sch.KIND == 2 else N_IT)
         assert run._args.prediction_type == 1
+    # the launches of one iteration, per class, and single forwards (new lines only, as above)
+    with sampler.SamplingRun(hip_denoiser(1234, 1.0), ddpm(), mems, masks, B, L, N_IT, seed=SEED) as run:
+        run.steps(1)
+        line("ddpm launches per iteration", **{k: n for k, (_, n) in run.profile().items()})
+    Be = 7 * B
+    for name, Lf, t in (("one timestep, att_mats", L, torch.tensor(500)), ("per-row timesteps", L, (torch.arange(Be) * 71 + 3) % 1000),
+                        ("L=24", 24, torch.tensor(500))):
+        x = torch.randn((Be, Lf, 128), generator=torch.Generator().manual_seed(12)).cuda()
+        with torch.no_grad():
+            out, att = m(x, t, mems, mem_mask_dict=masks)
+        line(f"forward {name}", out=sha(out), att_mats=sha(*att))
 
 
 if __name__ == "__main__":

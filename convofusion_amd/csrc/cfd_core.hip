@@ -78,17 +78,12 @@ extern "C" void cfd_destroy(cfd_handle c) {
   (void)hipDeviceSynchronize();
   if (c->gexec) (void)hipGraphExecDestroy(c->gexec);
   if (c->graph) (void)hipGraphDestroy(c->graph);
-  for (auto& wg : c->weg_graph) {
-    if (wg.exec) (void)hipGraphExecDestroy(wg.exec);
-    if (wg.graph) (void)hipGraphDestroy(wg.graph);
-  }
+  c->weg.release();
   if (c->weg_ev) (void)hipEventDestroy(c->weg_ev);
-  c->weg_io.release();
-  c->weg_rt_ws.release();
   c->sat.release();
   c->acen.release();
   for (auto& kv : c->raw) kv.second.release();
-  DBuf* all[] = {&c->we_sp, &c->wp_sp, &c->wp_f, &c->ln_cd_p, &c->we_all, &c->be_all, &c->tsin, &c->weg_ws, &c->weg_tok, &c->latents, &c->coef, &c->inoise, &c->hist, &c->wtab, &c->esrc, &c->enoise, &c->ekeep};
+  DBuf* all[] = {&c->we_sp, &c->wp_sp, &c->wp_f, &c->ln_cd_p, &c->we_all, &c->be_all, &c->tsin, &c->latents, &c->coef, &c->inoise, &c->hist, &c->wtab, &c->esrc, &c->enoise, &c->ekeep};
   for (DBuf* b : all) b->release();
   c->wk[0].release();
   c->wk[1].release();
@@ -116,7 +111,7 @@ extern "C" int cfd_load_tensor(cfd_handle c, const char* name, const float* data
   HIPCHK(hipMemcpy(b.p, data, numel * sizeof(float), is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
   c->raw_numel[name] = numel;
   c->finalized = false;
-  c->weg_sig.clear();
+  c->weg.invalidate();
   return CFD_OK;
 }
 

@@ -46,10 +46,10 @@ int enqueue_rows_rt(Ctx* c, hipStream_t st, const RtSave* sv) {
   const Problem& p = c->w->pb;
   const int nl = c->nl, L = p.L, tpr = (L + 15) / 16, ntile = p.Be * tpr;
   const int* dstep = c->w->d_step.as<int>();
-  const int lds_xpv = (p.Sp_tot / 32) * 2048 + 8 * (p.Sp_tot <= 512 ? 2 : 4) * 2048 + 16 * 32 * 16 + 512 + 2048;
+  const int lds_xpv = rt_xpv_lds(p.Sp_tot, p.Sp_tot <= 512 ? 512 : RT_MAX_KEYS);
 #define RT_SET_LDS(kernel, bytes) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes))
-  static unsigned long long attr = 0;
-  if (!((attr >> (c->cfg.device & 63)) & 1ull)) {
+  static unsigned long long attr_done = 0;
+  CHK(once_per_device(attr_done, c->cfg.device, [&]() -> int {
     RT_SET_LDS((rt_gemm_kernel<RT_PRO_SP, RT_EPI_EMBED, 256, CFD_LAT / 32, 1>), rt_gemm_lds(RT_PRO_SP, 256, CFD_LAT / 32, 1));
     RT_SET_LDS((rt_gemm_kernel<RT_PRO_LN, RT_EPI_QKV, 512, CFD_D / 32, 3>), rt_gemm_lds(RT_PRO_LN, 512, CFD_D / 32, 3));
     RT_SET_LDS((rt_gemm_kernel<RT_PRO_SP, RT_EPI_RESID, 256, CFD_D / 32, 1>), rt_gemm_lds(RT_PRO_SP, 256, CFD_D / 32, 1));
@@ -60,10 +60,10 @@ int enqueue_rows_rt(Ctx* c, hipStream_t st, const RtSave* sv) {
     RT_SET_LDS((rt_gemm_kernel<RT_PRO_SP, RT_EPI_RESID, 256, CFD_D / 32, 2>), rt_gemm_lds(RT_PRO_SP, 256, CFD_D / 32, 2));
     RT_SET_LDS((rt_gemm_kernel<RT_PRO_ADALN, RT_EPI_RESID, 512, CFD_D / 32, 2>), rt_gemm_lds(RT_PRO_ADALN, 512, CFD_D / 32, 2));
     RT_SET_LDS(rt_xscore_kernel<>, RT_XS_LDS);
-    RT_SET_LDS(rt_xpv_kernel<512>, (512 / 32) * 2048 + 8 * 2 * 2048 + 16 * 32 * 16 + 512 + 2048);
-    RT_SET_LDS(rt_xpv_kernel<RT_MAX_KEYS>, (RT_MAX_KEYS / 32) * 2048 + 8 * 4 * 2048 + 16 * 32 * 16 + 512 + 2048);
-    attr |= 1ull << (c->cfg.device & 63);
-  }
+    RT_SET_LDS(rt_xpv_kernel<512>, rt_xpv_lds(512, 512));
+    RT_SET_LDS(rt_xpv_kernel<RT_MAX_KEYS>, rt_xpv_lds(RT_MAX_KEYS, RT_MAX_KEYS));
+    return CFD_OK;
+  }));
 #undef RT_SET_LDS
   // The residual stream alternates between two buffers: a time block's workgroups read COMPLETE rows (LayerNorm prologue) while the
   // other workgroups of the tile write their 16 features of the sum, so it must not run in place.  x -> (time block 1) -> h ->
@@ -297,14 +297,14 @@ int enqueue_rows(Ctx* c, hipStream_t st) {
     return run_gemm_midsize<MODE_PLAIN>(c, CFD_PROF_GEMM_TOKEN, a, e, st);
   };
   bool h_raw = false;     // h_sp holds the split pairs of the raw rows + ln_stat their statistics (ln_fold), not norm1(x)
-  static unsigned long long attr = 0;   // per device (one bit per ordinal): a process may hold handles on several GPUs
-  if (!((attr >> (c->cfg.device & 63)) & 1ull)) {
+  static unsigned long long attr_done = 0;
+  CHK(once_per_device(attr_done, c->cfg.device, [&]() -> int {
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&self_attn_fused_kernel<>), hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&xattn_fused_kernel<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, XA_LDS));
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&xattn_fused_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, XA_LDS));
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&xattn_fused_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, XA_LDS));
-    attr |= 1ull << (c->cfg.device & 63);
-  }
+    return CFD_OK;
+  }));
 
   bool h_ready = false;   // h_sp already holds norm1(x) of the layer that starts
   for (int l = 0; l < nl; ++l) {

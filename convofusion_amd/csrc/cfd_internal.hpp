@@ -139,6 +139,44 @@ struct WegRtState {
   int dy_keys = 0, focus_large = 0;       // the rt_xbwd_dy_kernel instance (512 / RT_MAX_KEYS) and the objective kernel (1: weg_focus_kernel) it launched
 };
 
+// What cfd_weg_eval (cfd_weg.hip) keeps on the handle from one evaluation to the next.
+struct WegState {
+  DBuf ws, tok;   // the float32 launch sequence's activation arena; the focus-token tables
+  // cfd_weg_eval replays its launches (~400 of the float32 launch sequence, ~160 on the row-tile path) as a hipGraph.  A graph holds
+  // its kernels' arguments BY VALUE, so everything the caller passes per call -- latents in, losses / max_att / grad out, the
+  // timestep's sinusoid row -- goes through fixed staging buffers (io); round 1's attempt captured the caller's own pointers, which
+  // are fresh torch tensors on every call, and so replayed against stale addresses ("wrong gradients when interleaved with the
+  // sampling graph").  One graph per variant (full evaluation / memory-side results reused), keyed by everything else the launches
+  // depend on; a key is run eagerly once (function attributes, warm-up) and captured on its second use.
+  DBuf io;
+  struct Graph {
+    std::vector<long long> key;
+    int uses = 0;
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    void reset(const std::vector<long long>& new_key = {}) {   // drop the graph; start counting the uses of `new_key`
+      if (exec) (void)hipGraphExecDestroy(exec);
+      if (graph) (void)hipGraphDestroy(graph);
+      *this = Graph{new_key};
+    }
+  };
+  Graph graph[2];               // [0] full evaluation, [1] memory-side results reused
+  // Row-tile evaluation (weg_rt.hpp): the product path for small problems
+  DBuf rt_ws;
+  WegRtState rt;
+  int t_host = 0;               // the evaluation's timestep, copied to wk[1].trows in front of every launch sequence (one-row tables)
+  int dstep_host = 0;           // ... and the table row it selects, copied to wk[1].d_step (0 for one-row tables, the timestep for full tables)
+  long long tok_version = 0;    // counts the uploads of the focus-token tables (part of a graph's key)
+  std::vector<int32_t> tok_host;
+  std::vector<long long> sig;   // timestep, shapes, memory pointers and arena of the last evaluation (reuse_memory_side)
+  int launches = 0;
+  void release() {              // cfd_destroy
+    for (Graph& g : graph) g.reset();
+    ws.release(); tok.release(); io.release(); rt_ws.release();
+  }
+  void invalidate() { sig.clear(); }   // cfd_load_tensor: the next evaluation reuses no memory-side result
+};
+
 // One problem's device workspace: everything setup_problem / prepare_static_memside allocate and the launches of a forward touch.
 struct Work {
   Problem pb;
@@ -263,7 +301,7 @@ struct cfd_handle_s {
   //                               for all rows, no dynamic memories
   //   CFD_ROWTILE_MAX_ROWS=<n>    moves that threshold
   //   CFD_WEG_ROWTILE=0           cfd_weg_eval keeps the float32 launch sequence of weg_eval.hpp instead of the row-tile one (weg_rt.hpp)
-  //   CFD_WEG_GRAPH=0             cfd_weg_eval always runs eagerly (weg_graph)
+  //   CFD_WEG_GRAPH=0             cfd_weg_eval always runs eagerly (WegState::graph)
   //   CFD_FUSED_XATTN=0           the three-launch cross-attention (score products -> softmax_rows_kernel -> P.V products) everywhere
   //                               instead of the fused kernel (xattn_fused.hpp)
   //   CFD_FUSED_XATTN_MIN_WGS=<n> the fewest workgroups a work list needs for the fused kernel
@@ -277,26 +315,8 @@ struct cfd_handle_s {
   long long rt_max_rows = 700;    // measured crossover at the product shape (L = 16), seconds per 1000 steps, row-tile vs tile kernels (profiles/r05_rowtile_crossover.log:
                                   // the short cross-attention work lists of round 5 made the tile kernels faster): 5 utterances 1.04 / 1.22, 6: 1.18 / 1.24, 7: 1.34 / 1.23
   int fused_xattn_min_wgs = 6, ln_fold = -1, xa_operands = -1;
-  DBuf weg_ws, weg_tok;   // cfd_weg_eval: activation arena, focus-token tables
-  // cfd_weg_eval replays its ~400 launches as a hipGraph.  A graph holds its kernels' arguments BY VALUE, so everything the
-  // caller passes per call -- latents in, losses / max_att / grad out, the timestep's sinusoid row -- goes through fixed
-  // staging buffers (weg_io); round 1's attempt captured the caller's own pointers, which are fresh torch tensors on every
-  // call, and so replayed against stale addresses ("wrong gradients when interleaved with the sampling graph").
-  // One graph per variant (full evaluation / memory-side results reused), keyed by everything else the launches depend on;
-  // a key is run eagerly once (function attributes, warm-up) and captured on its second use.
-  DBuf weg_io;
-  // Row-tile evaluation (weg_rt.hpp): the product path for small problems
-  DBuf weg_rt_ws;
-  WegRtState wrt;
-  int weg_t_host = 0;   // the evaluation's timestep, copied to wk[1].trows in front of every launch sequence (one-row tables)
-  int weg_dstep_host = 0;   // ... and the table row it selects, copied to wk[1].d_step (0 for one-row tables, the timestep for full tables)
-  struct WegGraph { std::vector<long long> key; int uses = 0; hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; };
-  WegGraph weg_graph[2];
-  hipEvent_t weg_ev = nullptr;
-  long long weg_tok_version = 0;
-  std::vector<int32_t> weg_tok_host;
-  std::vector<long long> weg_sig;   // timestep, shapes, memory pointers and arena of the last evaluation (reuse_memory_side)
-  int weg_launches = 0;
+  WegState weg;                 // cfd_weg_eval's state between two evaluations (cfd_weg.hip)
+  hipEvent_t weg_ev = nullptr;  // cross-stream hand-over of cfd_weg_eval, and of cfd_dyadic_steps
   // profiling
   bool prof = false;
   hipEvent_t pev[2] = {nullptr, nullptr};
@@ -362,6 +382,17 @@ static inline int settle_deferred_census(Ctx* c) {
 static inline const float* rawp(Ctx* c, const std::string& name) {
   auto it = c->raw.find(name);
   return it == c->raw.end() ? nullptr : it->second.as<float>();
+}
+
+// Work done once per device (function attributes): `done` holds one bit per device ordinal -- a process may hold handles on several
+// GPUs -- and the bit is set when `fn` has succeeded.
+template <class Fn>
+static inline int once_per_device(unsigned long long& done, int device, Fn&& fn) {
+  const unsigned long long bit = 1ull << (device & 63);
+  if (done & bit) return CFD_OK;
+  CHK(fn());
+  done |= bit;
+  return CFD_OK;
 }
 
 // ---- profiling brackets ---------------------------------------------------------------------------

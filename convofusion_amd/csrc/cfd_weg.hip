@@ -71,7 +71,30 @@ extern "C" int cfd_weg_focus(cfd_handle c, const float* att, int B, int NL, int 
   return CFD_OK;
 }
 
-extern "C" int cfd_weg_eval(cfd_handle c, const cfd_weg_args* a, float* losses, float* max_att, float* grad, float* loss_host, void* stream) {
+// The staging buffer (WegState::io) in floats: [latents | timestep row | losses | max_att | grad], losses and max_att rounded up to 64
+struct WegStaging {
+  size_t n_lat, n_max, o_lat = 0, o_trow, o_loss, o_max, o_grad, n_io;
+  WegStaging(int B, int L, int D, int n_tok)
+      : n_lat((size_t)B * L * CFD_LAT), n_max((size_t)std::max(1, n_tok)), o_trow(n_lat), o_loss(o_trow + (size_t)D),
+        o_max(o_loss + (size_t)((B + 63) / 64 * 64)), o_grad(o_max + (n_max + 63) / 64 * 64), n_io(o_grad + n_lat) {}
+};
+
+struct WegEval {   // one evaluation, handed from stage to stage
+  Ctx* c;
+  const cfd_weg_args* a;
+  hipStream_t caller, st;     // the caller's stream; the handle's own, which the evaluation runs on
+  int B, L, D, n_tok, nt_max;
+  WegStaging lay;
+  float* io = nullptr;
+  weg::Args args{};           // what the launches read and write: staged addresses only
+  bool use_rt = false, reuse = false;   // the row-tile path (weg_rt.hpp), else the float32 launch sequence; the memory side is skipped
+  const void* arena = nullptr;
+  weg::Ctx x{};               // the float32 launch sequence's pass
+  std::vector<long long> sig, key;
+};
+
+// Every refusal, before anything is touched; yields the most focus tokens of a batch row.
+static int check_args(Ctx* c, const cfd_weg_args* a, const float* losses, const float* max_att, const float* grad, int* nt_max_out) {
   if (!c || !a || !a->latents || !a->tok_off || !losses || !max_att || !grad) return fail(CFD_E_ARG, "null argument");
   if (!c->finalized) return fail(CFD_E_STATE, "weights not finalized");
   const int B = a->B, L = a->L, D = c->cfg.text_encoded_dim;
@@ -97,156 +120,184 @@ extern "C" int cfd_weg_eval(cfd_handle c, const cfd_weg_args* a, float* losses, 
   for (int t = 0; t < n_tok; ++t)
     if (a->tok_idx[t] < 1 || a->tok_idx[t] > a->last - 1) return fail(CFD_E_ARG, "focus index %d is outside the text slice [1, %d)", a->tok_idx[t], a->last);
   // test hook (cfd_debug_weg_stop): a stop names a launch of the row-tile reverse sweep, so the evaluation must take that path
-  if (c->wrt.stop && !wegrt::eligible(c, a)) return fail(CFD_E_STATE, "cfd_debug_weg_stop is set, but this evaluation is not eligible for the row-tile path");
-  HIPCHK(hipSetDevice(c->cfg.device));
-  c->hint_now = c->hint_same_mem = false;
-  CHK(settle_deferred_census(c));
-  hipStream_t caller = (hipStream_t)stream;
-  // the evaluation runs on the handle's own stream (capturable, and the one the sampling graph replays on: the two
-  // serialise); it starts behind whatever the caller has queued on `stream`
-  hipStream_t st = c->own_stream;
-  HIPCHK(hipEventRecord(c->weg_ev, caller));
-  HIPCHK(hipStreamWaitEvent(st, c->weg_ev, 0));
-  std::vector<int32_t> tok(a->tok_off, a->tok_off + B + 1);
-  tok.insert(tok.end(), a->tok_idx, a->tok_idx + n_tok);
-  if (tok != c->weg_tok_host) {                       // focus-token tables to the device (the stream may still read the old copy)
-    HIPCHK(hipStreamSynchronize(st));
-    CHK(c->weg_tok.ensure((size_t)(B + 1 + std::max(1, n_tok)) * 4));
-    HIPCHK(hipMemcpy(c->weg_tok.p, tok.data(), tok.size() * 4, hipMemcpyHostToDevice));
-    c->weg_tok_host = tok;
-    ++c->weg_tok_version;
-  }
-  // staging: [latents | timestep row | losses | max_att | grad]
-  const size_t n_lat = (size_t)B * L * CFD_LAT, n_max = (size_t)std::max(1, n_tok);
-  const size_t o_lat = 0, o_trow = o_lat + n_lat, o_loss = o_trow + (size_t)D, o_max = o_loss + (size_t)((B + 63) / 64 * 64),
-               o_grad = o_max + (n_max + 63) / 64 * 64, n_io = o_grad + n_lat;
-  if (n_io * 4 > c->weg_io.bytes) {
-    HIPCHK(hipStreamSynchronize(st));
-    CHK(c->weg_io.ensure(n_io * 4));
-  }
-  float* io = c->weg_io.as<float>();
-  HIPCHK(hipMemcpyAsync(io + o_lat, a->latents, n_lat * 4, hipMemcpyDeviceToDevice, st));
-  HIPCHK(hipMemcpyAsync(io + o_trow, c->tsin.as<float>() + (size_t)a->timestep * D, (size_t)D * 4, hipMemcpyDeviceToDevice, st));
-  weg::Args wa{io + o_lat, io + o_trow, a->mem, c->weg_tok.as<int32_t>(), c->weg_tok.as<int32_t>() + B + 1,
-               a->last, nt_max, {a->kernel3[0], a->kernel3[1], a->kernel3[2]}, io + o_loss, io + o_max, io + o_grad};
-  // what the memory-side / time-only part of an evaluation depends on: with args->reuse_memory_side the caller states that the
-  // memories' CONTENTS are unchanged too (a refinement loop at one timestep), and those launches are skipped
-  // What the memory-side / time-only part of an evaluation depends on.  With args->reuse_memory_side the caller states that the
-  // memories' CONTENTS are unchanged too, and those launches are skipped: 1 = same timestep as well (a refinement loop at one
-  // timestep), 2 = the timestep may differ (the guided sampling loop: one evaluation per iteration, same conditioning).  The
-  // row-tile path serves 2 from tables over ALL timesteps, built at the first such call (row t = timestep t, one launch per
-  // evaluation copies the row); the float32 launch sequence treats 2 with a new timestep as 0.
-  const bool use_rt = wegrt::eligible(c, a);
-  std::vector<long long> sig = {B, L};
-  for (int j = 0; j < CFD_NMEM; ++j) {
-    sig.push_back(a->mem[j].S);
-    sig.push_back((long long)(size_t)a->mem[j].data);
-    sig.push_back((long long)(size_t)a->mem[j].key_padding_mask);   // (wegrt::prepare rebuilds the problem when a mask pointer changes: no reuse then)
-  }
-  weg::Ctx x{c, st, true, reinterpret_cast<char*>(256), 0, B, L, D, D, CFD_OK, std::string(), 0};
-  // small problems (the product shape) run on the row-tile kernels, everything else on the float32 launch sequence of weg_eval.hpp
-  const void* arena = nullptr;
-  bool reuse = false;
-  if (use_rt) {
-    const bool had_full = c->wrt.T > 1;
+  if (c->weg.rt.stop && !wegrt::eligible(c, a)) return fail(CFD_E_STATE, "cfd_debug_weg_stop is set, but this evaluation is not eligible for the row-tile path");
+  *nt_max_out = nt_max;
+  return CFD_OK;
+}
+
+// The focus-token tables go to the device when they change (the stream may still read the old copy).
+static int upload_focus_tokens(WegEval& e) {
+  WegState& w = e.c->weg;
+  std::vector<int32_t> tok(e.a->tok_off, e.a->tok_off + e.B + 1);
+  tok.insert(tok.end(), e.a->tok_idx, e.a->tok_idx + e.n_tok);
+  if (tok == w.tok_host) return CFD_OK;
+  HIPCHK(hipStreamSynchronize(e.st));
+  CHK(w.tok.ensure((size_t)(e.B + 1 + std::max(1, e.n_tok)) * 4));
+  HIPCHK(hipMemcpy(w.tok.p, tok.data(), tok.size() * 4, hipMemcpyHostToDevice));
+  w.tok_host = tok;
+  ++w.tok_version;
+  return CFD_OK;
+}
+
+// Latents and the timestep's sinusoid row into the staging buffer; from here on the launches see staged addresses only.
+static int stage_inputs(WegEval& e) {
+  Ctx* c = e.c;
+  const cfd_weg_args* a = e.a;
+  const WegStaging& y = e.lay;
+  if (y.n_io * 4 > c->weg.io.bytes) HIPCHK(hipStreamSynchronize(e.st));
+  CHK(c->weg.io.ensure(y.n_io * 4));
+  float* io = e.io = c->weg.io.as<float>();
+  HIPCHK(hipMemcpyAsync(io + y.o_lat, a->latents, y.n_lat * 4, hipMemcpyDeviceToDevice, e.st));
+  HIPCHK(hipMemcpyAsync(io + y.o_trow, c->tsin.as<float>() + (size_t)a->timestep * e.D, (size_t)e.D * 4, hipMemcpyDeviceToDevice, e.st));
+  const int32_t* tok = c->weg.tok.as<int32_t>();
+  e.args = weg::Args{io + y.o_lat, io + y.o_trow, a->mem, tok, tok + e.B + 1, a->last, e.nt_max, {a->kernel3[0], a->kernel3[1], a->kernel3[2]},
+                     io + y.o_loss, io + y.o_max, io + y.o_grad};
+  return CFD_OK;
+}
+
+// The path -- small problems (the product shape) run on the row-tile kernels, everything else on the float32 launch sequence of
+// weg_eval.hpp -- its arena, and whether the memory side can be reused.
+// `sig` is what the memory-side / time-only part of an evaluation depends on.  With args->reuse_memory_side the caller states that the
+// memories' CONTENTS are unchanged too, and those launches are skipped: 1 = same timestep as well (a refinement loop at one
+// timestep), 2 = the timestep may differ (the guided sampling loop: one evaluation per iteration, same conditioning).  The
+// row-tile path serves 2 from tables over ALL timesteps, built at the first such call (row t = timestep t, one launch per
+// evaluation copies the row); the float32 launch sequence treats 2 with a new timestep as 0.
+static int choose_path_and_reuse(WegEval& e) {
+  Ctx* c = e.c;
+  const cfd_weg_args* a = e.a;
+  WegState& w = c->weg;
+  e.use_rt = wegrt::eligible(c, a);
+  e.sig = {e.B, e.L};
+  weg::append_memories(e.sig, a->mem);   // (wegrt::prepare rebuilds the problem when a mask pointer changes: no reuse then)
+  if (e.use_rt) {
+    const bool had_full = w.rt.T > 1;
     // tables over all timesteps stay while the caller keeps stating that the conditioning is unchanged
     const int T = a->reuse_memory_side == 2 || (a->reuse_memory_side == 1 && had_full) ? c->tsin_rows : 1;
-    CHK(wegrt::prepare(c, a, T, st));
-    arena = c->weg_rt_ws.p;
-    sig.push_back((long long)(size_t)arena);
-    sig.push_back(-(long long)T);
-    if (T == 1) sig.push_back(a->timestep);
-    reuse = a->reuse_memory_side != 0 && sig == c->weg_sig;
-    c->wrt.T = T;
-    c->weg_t_host = a->timestep;                     // in front of the launch sequence, outside any captured graph
-    c->weg_dstep_host = T > 1 ? a->timestep : 0;
-    if (T == 1) HIPCHK(hipMemcpyAsync(c->wk[1].trows.p, &c->weg_t_host, 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(c->wk[1].d_step.p, &c->weg_dstep_host, 4, hipMemcpyHostToDevice, st));
-  } else {
-    sig.push_back(a->timestep);
-    weg::run(x, wa);                                 // sizing pass
-    if (x.err) return fail(x.err, "missing tensor '%s' (state-dict key denoiser.%s)", x.missing.c_str(), x.missing.c_str());
-    if (x.off > c->weg_ws.bytes) HIPCHK(hipStreamSynchronize(st));
-    CHK(c->weg_ws.ensure(x.off));
-    arena = c->weg_ws.p;
-    sig.push_back((long long)(size_t)arena);
-    sig.push_back((long long)x.off);
-    reuse = a->reuse_memory_side != 0 && sig == c->weg_sig;
+    CHK(wegrt::prepare(c, a, T, e.st));
+    e.arena = w.rt_ws.p;
+    e.sig.insert(e.sig.end(), {(long long)(size_t)e.arena, -(long long)T});
+    if (T == 1) e.sig.push_back(a->timestep);
+    e.reuse = a->reuse_memory_side != 0 && e.sig == w.sig;
+    w.rt.T = T;
+    w.t_host = a->timestep;                       // in front of the launch sequence, outside any captured graph
+    w.dstep_host = T > 1 ? a->timestep : 0;
+    if (T == 1) HIPCHK(hipMemcpyAsync(c->wk[1].trows.p, &w.t_host, 4, hipMemcpyHostToDevice, e.st));
+    HIPCHK(hipMemcpyAsync(c->wk[1].d_step.p, &w.dstep_host, 4, hipMemcpyHostToDevice, e.st));
+    return CFD_OK;
   }
-  x.dry = false;
-  x.base = c->weg_ws.as<char>();
-  x.off = 0;
-  x.launches = 0;
-  x.reuse = reuse;
-  c->weg_sig.clear();
-  const wegrt::EvalArgs ea{io + o_lat, c->weg_tok.as<int32_t>(), c->weg_tok.as<int32_t>() + B + 1, a->last, nt_max,
-                           {a->kernel3[0], a->kernel3[1], a->kernel3[2]}, io + o_loss, io + o_max, io + o_grad};
-  auto run_eval = [&]() -> int {                     // the evaluation's launches (this is what a graph captures)
-    if (!use_rt) { weg::run(x, wa); return CFD_OK; }
-    const int r = wegrt::enqueue(c, st, !x.reuse, ea);
-    x.launches = c->wrt.launches;
-    return r;
-  };
-  // everything the launch sequence and its (by-value) kernel arguments depend on, the timestep excepted (its row is staged)
-  std::vector<long long> key = {B, L, a->last, nt_max, c->weg_tok_version, (long long)(size_t)c->weg_tok.p, (long long)(size_t)io, (long long)n_io,
-                                (long long)(size_t)arena, (long long)x.reuse, (long long)use_rt, (long long)(use_rt ? c->wrt.T : 0)};
-  for (int j = 0; j < CFD_NMEM; ++j) {
-    key.push_back(a->mem[j].S);
-    key.push_back((long long)(size_t)a->mem[j].data);
-    key.push_back((long long)(size_t)a->mem[j].key_padding_mask);
-  }
-  for (int k = 0; k < 3; ++k) { long long bits = 0; memcpy(&bits, &a->kernel3[k], 4); key.push_back(bits); }
-  auto& wg = c->weg_graph[x.reuse ? 1 : 0];
-  if (c->wrt.stop) {                                  // test hook: eager, and neither a use of a graph key nor a change of one
-    CHK(run_eval());
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(st));
-    c->weg_launches = x.launches;
-    c->weg_sig = sig;
-    return CFD_OK;                                    // (losses / max_att / grad are not delivered: the sweep was left early)
-  }
-  if (wg.key != key) {
-    if (wg.exec) { (void)hipGraphExecDestroy(wg.exec); wg.exec = nullptr; }
-    if (wg.graph) { (void)hipGraphDestroy(wg.graph); wg.graph = nullptr; }
-    wg.key = key;
-    wg.uses = 0;
-  }
-  if (c->weg_graph_on && wg.exec) {
-    HIPCHK(hipGraphLaunch(wg.exec, st));
-    x.launches = c->weg_launches;
-  } else if (c->weg_graph_on && wg.uses >= 1) {       // second use of this key: capture, instantiate, launch
+  e.sig.push_back(a->timestep);
+  e.x = weg::Ctx::sizing_pass(c, e.st, e.B, e.L, e.D);
+  weg::run(e.x, e.args);
+  if (e.x.err) return fail(e.x.err, "missing tensor '%s' (state-dict key denoiser.%s)", e.x.missing.c_str(), e.x.missing.c_str());
+  if (e.x.off > w.ws.bytes) HIPCHK(hipStreamSynchronize(e.st));
+  CHK(w.ws.ensure(e.x.off));
+  e.arena = w.ws.p;
+  e.sig.insert(e.sig.end(), {(long long)(size_t)e.arena, (long long)e.x.off});
+  e.reuse = a->reuse_memory_side != 0 && e.sig == w.sig;
+  e.x.real_pass(w.ws.as<char>(), e.reuse);
+  return CFD_OK;
+}
+
+// Everything the launch sequence and its (by-value) kernel arguments depend on, the timestep excepted (its row is staged).
+static void build_graph_key(WegEval& e) {
+  const WegState& w = e.c->weg;
+  e.key = {e.B, e.L, e.a->last, e.nt_max, w.tok_version, (long long)(size_t)w.tok.p, (long long)(size_t)e.io, (long long)e.lay.n_io,
+           (long long)(size_t)e.arena, (long long)e.reuse, (long long)e.use_rt, (long long)(e.use_rt ? w.rt.T : 0)};
+  weg::append_memories(e.key, e.a->mem);
+  for (int k = 0; k < 3; ++k) { long long bits = 0; memcpy(&bits, &e.a->kernel3[k], 4); e.key.push_back(bits); }
+}
+
+// The evaluation's launches (this is what a graph captures; a replay leaves WegState::launches as the captured sequence's).
+static int enqueue_eval(WegEval& e) {
+  WegState& w = e.c->weg;
+  if (e.use_rt) CHK(wegrt::enqueue(e.c, e.st, !e.reuse, e.args));
+  else weg::run(e.x, e.args);
+  w.launches = e.use_rt ? w.rt.launches : e.x.launches;
+  return CFD_OK;
+}
+
+// One graph variant's life: a new key drops the graph of the old one; a key runs eagerly at its first use, is captured and
+// instantiated at its second, and replayed from then on.
+static int run_through_graph(WegEval& e, WegState::Graph& g) {
+  hipStream_t st = e.st;
+  if (g.key != e.key) g.reset(e.key);
+  const bool on = e.c->weg_graph_on;
+  if (on && g.exec) {
+    HIPCHK(hipGraphLaunch(g.exec, st));
+  } else if (on && g.uses >= 1) {
     HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-    const int rr = run_eval();
-    hipGraph_t g = nullptr;
-    hipError_t e = hipStreamEndCapture(st, &g);
-    if (rr != CFD_OK) { if (g) (void)hipGraphDestroy(g); return rr; }
-    if (e != hipSuccess) return fail(CFD_E_HIP, "capturing the WEG evaluation failed: %s", hipGetErrorString(e));
-    wg.graph = g;
-    HIPCHK(hipGraphInstantiate(&wg.exec, wg.graph, nullptr, nullptr, 0));
-    HIPCHK(hipGraphLaunch(wg.exec, st));
+    const int rr = enqueue_eval(e);
+    hipGraph_t captured = nullptr;
+    hipError_t err = hipStreamEndCapture(st, &captured);
+    if (rr != CFD_OK) { if (captured) (void)hipGraphDestroy(captured); return rr; }
+    if (err != hipSuccess) return fail(CFD_E_HIP, "capturing the WEG evaluation failed: %s", hipGetErrorString(err));
+    g.graph = captured;
+    HIPCHK(hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0));
+    HIPCHK(hipGraphLaunch(g.exec, st));
   } else {
-    CHK(run_eval());
+    CHK(enqueue_eval(e));
   }
-  ++wg.uses;
+  ++g.uses;
   HIPCHK(hipGetLastError());
-  c->weg_launches = x.launches;
-  c->weg_sig = sig;
-  HIPCHK(hipMemcpyAsync(losses, io + o_loss, (size_t)B * 4, hipMemcpyDeviceToDevice, st));
-  HIPCHK(hipMemcpyAsync(max_att, io + o_max, n_max * 4, hipMemcpyDeviceToDevice, st));
-  HIPCHK(hipMemcpyAsync(grad, io + o_grad, n_lat * 4, hipMemcpyDeviceToDevice, st));
+  return CFD_OK;
+}
+
+// Eagerly under the stop hook -- neither a use of a graph key nor a change of one -- and through the variant's graph otherwise.
+static int run(WegEval& e) {
+  WegState& w = e.c->weg;
+  w.sig.clear();                                  // (an evaluation that fails leaves nothing to reuse)
+  if (w.rt.stop) {
+    CHK(enqueue_eval(e));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(e.st));
+  } else {
+    CHK(run_through_graph(e, w.graph[e.reuse ? 1 : 0]));
+  }
+  w.sig = e.sig;
+  return CFD_OK;
+}
+
+// Results to the caller; with loss_host the call waits and reads its census, without it the caller's stream continues behind the evaluation.
+static int deliver(WegEval& e, float* losses, float* max_att, float* grad, float* loss_host) {
+  Ctx* c = e.c;
+  const WegStaging& y = e.lay;
+  const int B = e.B;
+  HIPCHK(hipMemcpyAsync(losses, e.io + y.o_loss, (size_t)B * 4, hipMemcpyDeviceToDevice, e.st));
+  HIPCHK(hipMemcpyAsync(max_att, e.io + y.o_max, y.n_max * 4, hipMemcpyDeviceToDevice, e.st));
+  HIPCHK(hipMemcpyAsync(grad, e.io + y.o_grad, y.n_lat * 4, hipMemcpyDeviceToDevice, e.st));
   if (loss_host) {                                   // torch.mean(losses) over the batch (word_excitation_guidance.py:80)
     std::vector<float> l(B);
-    HIPCHK(hipMemcpyAsync(l.data(), io + o_loss, (size_t)B * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipMemcpyAsync(l.data(), e.io + y.o_loss, (size_t)B * 4, hipMemcpyDeviceToHost, e.st));
+    HIPCHK(hipStreamSynchronize(e.st));
     CHK(check_saturation(c, "cfd_weg_eval (latents, memories / their projections)"));   // (without loss_host: read by the next call that waits on this handle)
     float sum = 0.f;
     for (int b = 0; b < B; ++b) sum += l[b];
     *loss_host = sum / (float)B;
-  } else {                                           // the caller's stream continues behind the evaluation
+  } else {
     c->census_pending = true;                        // (read by the handle's next entry point: settle_deferred_census)
-    HIPCHK(hipEventRecord(c->weg_ev, st));
-    HIPCHK(hipStreamWaitEvent(caller, c->weg_ev, 0));
+    HIPCHK(hipEventRecord(c->weg_ev, e.st));
+    HIPCHK(hipStreamWaitEvent(e.caller, c->weg_ev, 0));
   }
   return CFD_OK;
 }
 
+extern "C" int cfd_weg_eval(cfd_handle c, const cfd_weg_args* a, float* losses, float* max_att, float* grad, float* loss_host, void* stream) {
+  int nt_max = 0;
+  CHK(check_args(c, a, losses, max_att, grad, &nt_max));
+  HIPCHK(hipSetDevice(c->cfg.device));
+  c->hint_now = c->hint_same_mem = false;
+  CHK(settle_deferred_census(c));
+  const int D = c->cfg.text_encoded_dim, n_tok = a->tok_off[a->B];
+  // the evaluation runs on the handle's own stream (capturable, and the one the sampling graph replays on: the two
+  // serialise); it starts behind whatever the caller has queued on `stream`
+  WegEval e{c, a, (hipStream_t)stream, c->own_stream, a->B, a->L, D, n_tok, nt_max, WegStaging(a->B, a->L, D, n_tok)};
+  HIPCHK(hipEventRecord(c->weg_ev, e.caller));
+  HIPCHK(hipStreamWaitEvent(e.st, c->weg_ev, 0));
+  CHK(upload_focus_tokens(e));
+  CHK(stage_inputs(e));
+  CHK(choose_path_and_reuse(e));
+  build_graph_key(e);
+  CHK(run(e));
+  if (c->weg.rt.stop) return CFD_OK;               // test hook: losses / max_att / grad are not delivered, the sweep was left early
+  return deliver(e, losses, max_att, grad, loss_host);
+}

@@ -700,8 +700,10 @@ __global__ void __launch_bounds__(512) rt_xscore_kernel(const RtXArgs a) {
 // Cross-attention, second half: P' = p rs from the cells' statistics, x += sum_j (VA_j^T P'_j + (sum P'_j) VV_j b_t) + bias for 16
 // features.  MAXKEYS: capacity in padded keys (512: the product shape's 320 keys; 1024).  Thread (row pr, lane plr) owns the 4-key
 // chunks plr + 32 n: 16-byte loads contiguous across the row's lanes.
-// dynamic LDS: P' image (Sp_tot / 32) x 2 KB | 8 x MAXN x 2 KB staging | cell statistics [16][32] float4 | sum_s P'_s [16][8]
 // ------------------------------------------------------------------------------------------------
+// dynamic LDS of rt_xpv_kernel<maxkeys> at Sp_tot padded keys: P' image (Sp_tot / 32) x 2 KB | 8 x MAXN x 2 KB staging | cell statistics
+// [16][32] float4 | sum_s P'_s [16][8] | 2 KB
+constexpr int rt_xpv_lds(int sp_tot, int maxkeys) { return (sp_tot / 32) * 2048 + 8 * (maxkeys / 32 / 8) * 2048 + 16 * 32 * 16 + 512 + 2048; }
 template <int MAXKEYS>
 __global__ void __launch_bounds__(512) rt_xpv_kernel(const RtXArgs a) {
   constexpr int NW = 8;

@@ -140,8 +140,9 @@ __device__ __forceinline__ f32x4 rt_reduce1(char* red, int wid, int lane, f32x4 
 
 // ------------------------------------------------------------------------------------------------
 // out[16 tokens][16 outputs] = A[16][K] . W[K][n0 .. n0 + 15]      (B1, B2, B3, B6, B7, B9, the embedding's backward)
-// grid (N / 16, tiles), 512 threads; dynamic LDS = 16 * (K + 2) * 4 + 8 KB
+// grid (N / 16, tiles), 512 threads; dynamic LDS: the operand image + 8 KB (reduction)
 // ------------------------------------------------------------------------------------------------
+constexpr int rt_bwd_gemm_lds(int K) { return 16 * RT_BSTRIDE(K) * 4 + 8 * 1024; }
 template <int PRO, int EPI, int MAXSTEP>
 __global__ void __launch_bounds__(512) rt_bwd_gemm_kernel(const RtBwdArgs a) {
   constexpr int NW = 8;
@@ -259,6 +260,8 @@ struct RtXBwdArgs {
   float* dy;                    // B5 output [M][512]
 };
 
+// dynamic LDS of rt_xbwd_dp_kernel
+constexpr int rt_xbwd_dp_lds() { return 16 * RT_BSTRIDE(CFD_D) * 4 + 8 * 1024 + 64; }
 template <int CFD_KI = 0>
 __global__ void __launch_bounds__(512) rt_xbwd_dp_kernel(const RtXBwdArgs a) {
   constexpr int NW = 8, K = CFD_D, RS = RT_BSTRIDE(CFD_D), NSTEP = K / (4 * NW);
@@ -357,8 +360,9 @@ __global__ void __launch_bounds__(512) rt_xbwd_dp_kernel(const RtXBwdArgs a) {
 // ------------------------------------------------------------------------------------------------
 // B5: softmax backward per memory, dS' = dS rs, and the gradient at the LayerNorm2 output
 //   dy[token][f] = sum_j ( sum_s dS'_s KA_j[s][f] + (sum_s dS'_s) (A b_t)_j[f] )
-// grid (32, tiles); dynamic LDS = 16 * (Sp_tot + 2) * 4 (dS image) + 8 KB (reduction) + 512 (sums) + 8 KB (cell statistics) + 1 KB (per-memory statistics)
+// grid (32, tiles); dynamic LDS: dS image + 8 KB (reduction) + 512 (sums) + 8 KB (cell statistics) + 1 KB (per-memory statistics)
 // ------------------------------------------------------------------------------------------------
+constexpr int rt_xbwd_dy_lds(int sp_tot) { return 16 * RT_BSTRIDE(sp_tot) * 4 + 8 * 1024 + 512 + 16 * 32 * 16 + 16 * 8 * 8; }
 template <int MAXKEYS>
 __global__ void __launch_bounds__(512) rt_xbwd_dy_kernel(const RtXBwdArgs a) {
   constexpr int NW = 8, LPR = 32;
@@ -545,6 +549,8 @@ struct RtSelfBwdArgs {
   float qscale;       // 1 / sqrt(head_dim): dq is handed on as the gradient at the UNSCALED query projection (the forward's weights carry the scale)
 };
 
+// dynamic LDS of rt_selfattn_bwd_kernel: Q, K, V, dO [32][129] and two [32][33] squares
+constexpr int rt_selfattn_bwd_lds() { return (4 * RT_MAX_L * (CFD_HD + 1) + 2 * RT_MAX_L * (RT_MAX_L + 1)) * 4; }
 template <int CFD_KI = 0>
 __global__ void __launch_bounds__(256) rt_selfattn_bwd_kernel(const RtSelfBwdArgs a) {
   constexpr int HD = CFD_HD, RSD = HD + 1;

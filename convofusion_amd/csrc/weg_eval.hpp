@@ -48,6 +48,15 @@ struct Ctx {
   bool reuse = false;      // the memory-side / time-only results of the previous evaluation are still in the arena: skip their launches
   bool suppress = false;
 
+  // The sizing pass: same control flow as the real one over a fake non-null base that is never dereferenced; it leaves the arena's bytes in `off`.
+  static Ctx sizing_pass(cfd_handle c, hipStream_t st, int B, int L, int D) {
+    Ctx x{};
+    x.c = c; x.st = st; x.dry = true; x.base = reinterpret_cast<char*>(256); x.B = B; x.L = L; x.D = D; x.E = D; x.err = CFD_OK;
+    return x;
+  }
+  // ... and the switch to the real pass over the arena at `arena`
+  void real_pass(char* arena, bool reuse_memory_side) { dry = false; base = arena; off = 0; launches = 0; reuse = reuse_memory_side; }
+
   float* alloc(size_t n) {
     const size_t bytes = (n * 4 + 255) & ~(size_t)255;
     float* p = reinterpret_cast<float*>(base + off);   // sizing pass: a fake non-null base, never dereferenced (same control flow)
@@ -366,6 +375,8 @@ static void time_block_embeddings(Ctx& x, const float* temb, int n_layers, std::
   }
 }
 
+// What an evaluation's launches read and write, for both paths (the row-tile path, weg_rt.hpp, ignores trow and mem: it has its
+// timestep tables and its problem)
 struct Args {
   const float* latents;        // dev [B][L][latent]
   const float* trow;           // dev: the timestep's row of the sinusoid table (get_timestep_embedding)
@@ -375,6 +386,16 @@ struct Args {
   float k3[3];
   float *losses, *max_att, *grad;    // dev outputs
 };
+
+// A memory set's signature, appended to `v`: per memory S, the data pointer and the mask pointer.  Part of everything that decides
+// whether an evaluation may reuse what the previous one left (cfd_weg_eval's signature and graph key, wegrt::prepare's).
+static void append_memories(std::vector<long long>& v, const cfd_memory* mem) {
+  for (int j = 0; j < CFD_NMEM; ++j) {
+    v.push_back(mem[j].S);
+    v.push_back((long long)(size_t)mem[j].data);
+    v.push_back((long long)(size_t)mem[j].key_padding_mask);
+  }
+}
 
 // One pass over the whole evaluation; with x.dry it only sizes the workspace.
 static void run(Ctx& x, const Args& a) {

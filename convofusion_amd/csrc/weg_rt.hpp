@@ -13,26 +13,24 @@ struct WorkGuard {   // the launches of an evaluation address Ctx::wk[1]; everyt
   ~WorkGuard() { c->w = &c->wk[0]; }
 };
 
+static int padded_keys(const cfd_memory* mem) {   // of all five memories together, each padded to 32
+  int sp = 0;
+  for (int j = 0; j < CFD_NMEM; ++j) sp += (mem[j].S + 31) / 32 * 32;
+  return sp;
+}
+
 static bool eligible(Ctx* c, const cfd_weg_args* a) {
   if (!c->rt_on || !c->weg_rt_on) return false;
   if (a->L > RT_MAX_L || (long long)a->B * a->L > c->rt_max_rows) return false;
-  int sp = 0;
-  for (int j = 0; j < CFD_NMEM; ++j) sp += (a->mem[j].S + 31) / 32 * 32;
-  return sp <= RT_MAX_KEYS;
+  return padded_keys(a->mem) <= RT_MAX_KEYS;
 }
 
 // (Re)build the evaluation's problem and arena when shapes or pointers change.  Host work only (allocations, row maps): never captured.
 static int prepare(Ctx* c, const cfd_weg_args* a, int T, hipStream_t st) {
-  WegRtState& s = c->wrt;
-  const int B = a->B, L = a->L, nl = c->nl;
+  WegRtState& s = c->weg.rt;
+  const int B = a->B, L = a->L, nl = c->nl, spt = padded_keys(a->mem);
   std::vector<long long> sig = {B, L, nl, T};
-  int spt = 0;
-  for (int j = 0; j < CFD_NMEM; ++j) {
-    sig.push_back(a->mem[j].S);
-    sig.push_back((long long)(size_t)a->mem[j].data);
-    sig.push_back((long long)(size_t)a->mem[j].key_padding_mask);
-    spt += (a->mem[j].S + 31) / 32 * 32;
-  }
+  weg::append_memories(sig, a->mem);
   if (sig == s.sig) return CFD_OK;
   HIPCHK(hipStreamSynchronize(st));
   s.sig.clear();
@@ -44,8 +42,8 @@ static int prepare(Ctx* c, const cfd_weg_args* a, int T, hipStream_t st) {
   n += (size_t)(nl + 1) * 5 * n_x + (size_t)nl * (n_qk + n_vt + n_sc + n_pre + n_cst);
   const size_t n_att = al((size_t)B * nl * L * St), n_fws = al((size_t)B * (3 * (size_t)L * St + 3 * St + 64));
   n += 2 * n_att + n_fws + n_sc + 3 * n_x + 2 * n_x + n_pre + n_x + al(M * 3 * CFD_D);
-  CHK(c->weg_rt_ws.ensure(n * 4));
-  float* p = c->weg_rt_ws.as<float>();
+  CHK(c->weg.rt_ws.ensure(n * 4));
+  float* p = c->weg.rt_ws.as<float>();
   auto take = [&](size_t k) { float* r = p; p += k; return r; };
   for (int l = 0; l <= nl; ++l)
     for (int k = 0; k < 5; ++k) s.sv.x[l][k] = take(n_x);
@@ -77,60 +75,62 @@ static int prepare(Ctx* c, const cfd_weg_args* a, int T, hipStream_t st) {
   return CFD_OK;
 }
 
-struct EvalArgs {
-  const float* latents;        // dev [B][L][128] (staged)
-  const int32_t *tok_off, *tok_idx;
-  int last, nt_max;
-  float k3[3];
-  float *losses, *max_att, *grad;
-};
-
-template <int PRO, int EPI, int MAXSTEP>
-static int bwd_gemm(Ctx* c, hipStream_t st, const RtBwdArgs& a, int N, int ntile) {
-  const int lds = 16 * RT_BSTRIDE(a.K) * 4 + 8 * 1024;
-  static unsigned long long attr = 0;
-  if (!((attr >> (c->cfg.device & 63)) & 1ull)) {
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&rt_bwd_gemm_kernel<PRO, EPI, MAXSTEP>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               16 * RT_BSTRIDE(MAXSTEP * 32) * 4 + 8 * 1024));
-    attr |= 1ull << (c->cfg.device & 63);
-  }
-  if (a.K != MAXSTEP * 32) return fail(CFD_E_ARG, "backward product: K = %d does not match the kernel instance (%d)", a.K, MAXSTEP * 32);
-  hipLaunchKernelGGL((rt_bwd_gemm_kernel<PRO, EPI, MAXSTEP>), dim3(N / 16, ntile), dim3(512), lds, st, a);
+// One launch of the reverse sweep: launch, check, count.
+template <class Kernel, class Args>
+static int sweep_launch(Ctx* c, hipStream_t st, Kernel kernel, dim3 grid, int threads, int lds, const Args& a) {
+  hipLaunchKernelGGL(kernel, grid, dim3(threads), lds, st, a);
   HIPCHK(hipGetLastError());
-  ++c->wrt.launches;
+  ++c->weg.rt.launches;
   return CFD_OK;
 }
 
-// Launches only (capturable): [time tables + memory side when `full`], forward, objective, reverse sweep.
-static int enqueue(Ctx* c, hipStream_t st, bool full, const EvalArgs& e) {
-  WorkGuard guard(c);
-  WegRtState& s = c->wrt;
-  s.launches = 0;
-  s.stop_gi = -1;
+template <int PRO, int EPI, int MAXSTEP>
+static int bwd_gemm(Ctx* c, hipStream_t st, const RtBwdArgs& a, int N, int ntile) {
+  static unsigned long long attr_done = 0;
+  CHK(once_per_device(attr_done, c->cfg.device, [&]() -> int {
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&rt_bwd_gemm_kernel<PRO, EPI, MAXSTEP>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               rt_bwd_gemm_lds(MAXSTEP * 32)));
+    return CFD_OK;
+  }));
+  if (a.K != MAXSTEP * 32) return fail(CFD_E_ARG, "backward product: K = %d does not match the kernel instance (%d)", a.K, MAXSTEP * 32);
+  return sweep_launch(c, st, rt_bwd_gemm_kernel<PRO, EPI, MAXSTEP>, dim3(N / 16, ntile), 512, rt_bwd_gemm_lds(a.K), a);
+}
+
+// The launches "weg.info" reports for the callees that do not count their own:
+//   enqueue_time_tables (cfd_problem.hip): two products of the time embedding + one per time block, two blocks per layer;
+//   prepare_static_memside (cfd_problem.hip): per memory mem_center_kernel, the two folded products (enqueue_mem_kv), the two table
+//     products (kbtab, vbtab) and mem_scale_table_kernel, + temb_center_kernel + 1.  (The callee also fills a scale plane per memory;
+//     the figure is compared between trees and stays what it has always been.)
+//   to_split_kernel + enqueue_rows_rt with saved activations (cfd_forward.hip): the embedding + nine launches per layer, less the
+//     three of the top layer behind its cross-attention.
+static int memory_side_launches(int nl) { return (2 + 2 * nl) + (6 * CFD_NMEM + 2); }
+static int forward_launches(int nl) { return 1 + 1 + 9 * nl - 3; }
+
+// [time tables + memory side]: what an evaluation that reuses the memory side skips
+static int enqueue_memory_side(Ctx* c, hipStream_t st) {
   Work* w = c->w;
-  const Problem& p = w->pb;
-  const int nl = c->nl, B = p.Be, L = p.L, tpr = (L + 15) / 16, ntile = B * tpr, St = p.S[2];
-  const long long M = p.M;
-  s.B = B; s.L = L; s.Sp_tot = p.Sp_tot; s.St = St;
-  if (full) {
-    w->tt_key.clear();     // (this workspace's timestep-only tables are rebuilt from w->trows, whatever they held: cfd_problem.hip, build_time_tables)
-    w->tt_mem_mask = 0;
-    CHK(enqueue_time_tables(c, p.T, st));      // one row: the timestep index is in w->trows (copied in front of the launch sequence); full tables: row t = timestep t
-    CHK(prepare_static_memside(c, st, 0, true));
-    if (!p.rt) return fail(CFD_E_STATE, "row-tile WEG evaluation lost its path");
-    s.launches += 20 + 5 * 6 + 2;
-  }
-  {
-    const long long n = M * (CFD_LAT / 8);
-    hipLaunchKernelGGL(to_split_kernel<>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, e.latents, w->sample_sp.as<char>(), M, CFD_LAT,
-                       (long long)CFD_LAT, (long long)CFD_LAT * 4, c->sat_in());
-    HIPCHK(hipGetLastError());
-  }
+  w->tt_key.clear();     // (this workspace's timestep-only tables are rebuilt from w->trows, whatever they held: cfd_problem.hip, build_time_tables)
+  w->tt_mem_mask = 0;
+  CHK(enqueue_time_tables(c, w->pb.T, st));      // one row: the timestep index is in w->trows (copied in front of the launch sequence); full tables: row t = timestep t
+  CHK(prepare_static_memside(c, st, 0, true));
+  if (!w->pb.rt) return fail(CFD_E_STATE, "row-tile WEG evaluation lost its path");
+  c->weg.rt.launches += memory_side_launches(c->nl);
+  return CFD_OK;
+}
+
+// forward with saved activations (rowtile.hpp), then the objective and its gradient at the nine maps
+static int enqueue_forward_and_objective(Ctx* c, hipStream_t st, const weg::Args& e) {
+  WegRtState& s = c->weg.rt;
+  Work* w = c->w;
+  const int nl = c->nl, B = s.B, L = s.L, St = s.St;
+  const long long M = w->pb.M, n = M * (CFD_LAT / 8);
+  hipLaunchKernelGGL(to_split_kernel<>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, e.latents, w->sample_sp.as<char>(), M, CFD_LAT,
+                     (long long)CFD_LAT, (long long)CFD_LAT * 4, c->sat_in());
+  HIPCHK(hipGetLastError());
   CHK(enqueue_rows_rt(c, st, &s.sv));
-  s.launches += 2 + 9 * nl - 3;
+  s.launches += forward_launches(nl);
   s.focus_large = !(L * (e.last - 1) <= WEG_SMALL_CELLS && e.nt_max <= WEG_SMALL_TOK && L <= 64);
-  s.dy_keys = p.Sp_tot <= 512 ? 512 : RT_MAX_KEYS;
-  if (L * (e.last - 1) <= WEG_SMALL_CELLS && e.nt_max <= WEG_SMALL_TOK && L <= 64)
+  if (!s.focus_large)
     hipLaunchKernelGGL(weg_focus_small_kernel<>, dim3((unsigned)B), dim3(256), 0, st, s.att, e.tok_off, e.tok_idx, B, nl, L, St, e.last, e.k3[0], e.k3[1],
                        e.k3[2], e.losses, e.max_att, s.d_att);
   else
@@ -138,20 +138,25 @@ static int enqueue(Ctx* c, hipStream_t st, bool full, const EvalArgs& e) {
                        e.k3[2], s.fws, e.losses, e.max_att, s.d_att);
   HIPCHK(hipGetLastError());
   ++s.launches;
+  return CFD_OK;
+}
 
-  // ---- reverse sweep (rowtile_bwd.hpp) -----------------------------------------------------------------------
-  static unsigned long long attr = 0;
-  const int lds_dp = 16 * RT_BSTRIDE(CFD_D) * 4 + 8 * 1024 + 64;
-  const int lds_dy = 16 * RT_BSTRIDE(p.Sp_tot) * 4 + 8 * 1024 + 512 + 16 * 32 * 16 + 16 * 8 * 8;
-  const int lds_sa = (4 * RT_MAX_L * (CFD_HD + 1) + 2 * RT_MAX_L * (RT_MAX_L + 1)) * 4;
-  if (!((attr >> (c->cfg.device & 63)) & 1ull)) {
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&rt_xbwd_dy_kernel<512>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               16 * RT_BSTRIDE(512) * 4 + 8 * 1024 + 512 + 16 * 32 * 16 + 16 * 8 * 8));
+// reverse sweep (rowtile_bwd.hpp): B1 .. B9 per layer from the top, then the embedding's backward into `grad`
+static int enqueue_reverse_sweep(Ctx* c, hipStream_t st, float* grad) {
+  WegRtState& s = c->weg.rt;
+  Work* w = c->w;
+  const Problem& p = w->pb;
+  const int nl = c->nl, B = s.B, L = s.L, tpr = (L + 15) / 16, ntile = B * tpr;
+  s.dy_keys = p.Sp_tot <= 512 ? 512 : RT_MAX_KEYS;
+  const auto dy_kernel = s.dy_keys == 512 ? rt_xbwd_dy_kernel<512> : rt_xbwd_dy_kernel<RT_MAX_KEYS>;
+  static unsigned long long attr_done = 0;
+  CHK(once_per_device(attr_done, c->cfg.device, [&]() -> int {
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&rt_xbwd_dy_kernel<512>), hipFuncAttributeMaxDynamicSharedMemorySize, rt_xbwd_dy_lds(512)));
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&rt_xbwd_dy_kernel<RT_MAX_KEYS>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               16 * RT_BSTRIDE(RT_MAX_KEYS) * 4 + 8 * 1024 + 512 + 16 * 32 * 16 + 16 * 8 * 8));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&rt_selfattn_bwd_kernel<>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_sa));
-    attr |= 1ull << (c->cfg.device & 63);
-  }
+                               rt_xbwd_dy_lds(RT_MAX_KEYS)));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&rt_selfattn_bwd_kernel<>), hipFuncAttributeMaxDynamicSharedMemorySize, rt_selfattn_bwd_lds()));
+    return CFD_OK;
+  }));
   RtBwdArgs base;
   memset(&base, 0, sizeof(base));
   base.L = L; base.tpr = tpr;
@@ -212,9 +217,7 @@ static int enqueue(Ctx* c, hipStream_t st, bool full, const EvalArgs& e) {
         RtXBwdArgs a = x5;
         a.dz = s.dz; a.g = s.G[gi]; a.x = s.sv.x[l][3]; a.gamma = lw.tb2g; a.beta = lw.tb2b;
         a.ss = w->now_ss + (size_t)(2 * l + 1) * 2 * CFD_D; a.gout = s.G[(gi + 1) % 3];
-        hipLaunchKernelGGL(rt_xbwd_dp_kernel<>, dim3(nkb, ntile), dim3(512), lds_dp, st, a);
-        HIPCHK(hipGetLastError());
-        ++s.launches;
+        CHK(sweep_launch(c, st, rt_xbwd_dp_kernel<>, dim3(nkb, ntile), 512, rt_xbwd_dp_lds(), a));
         gi = (gi + 1) % 3;
       }
       WEG_STOP_AT(4);
@@ -222,10 +225,7 @@ static int enqueue(Ctx* c, hipStream_t st, bool full, const EvalArgs& e) {
     {   // B5: softmax backward and the folded keys
       RtXBwdArgs a = x5;
       a.dp_from_datt = have_g || l < nl - 1 ? 0 : 1;
-      if (p.Sp_tot <= 512) hipLaunchKernelGGL(rt_xbwd_dy_kernel<512>, dim3(CFD_D / 16, ntile), dim3(512), lds_dy, st, a);
-      else hipLaunchKernelGGL(rt_xbwd_dy_kernel<RT_MAX_KEYS>, dim3(CFD_D / 16, ntile), dim3(512), lds_dy, st, a);
-      HIPCHK(hipGetLastError());
-      ++s.launches;
+      CHK(sweep_launch(c, st, dy_kernel, dim3(CFD_D / 16, ntile), 512, rt_xbwd_dy_lds(p.Sp_tot), a));
     }
     WEG_STOP_AT(5);
     {   // B6: norm2, then time block 1's projection
@@ -248,9 +248,7 @@ static int enqueue(Ctx* c, hipStream_t st, bool full, const EvalArgs& e) {
     WEG_STOP_AT(7);
     {   // B8: attention core
       RtSelfBwdArgs a{s.sv.qk[l], s.sv.vt[l], s.dO, s.dqkv, L, (float)std::sqrt(1.0 / (double)CFD_HD)};
-      hipLaunchKernelGGL(rt_selfattn_bwd_kernel<>, dim3(CFD_NHEAD, B), dim3(256), lds_sa, st, a);
-      HIPCHK(hipGetLastError());
-      ++s.launches;
+      CHK(sweep_launch(c, st, rt_selfattn_bwd_kernel<>, dim3(CFD_NHEAD, B), 256, rt_selfattn_bwd_lds(), a));
     }
     WEG_STOP_AT(8);
     {   // B9: packed in-projection
@@ -265,11 +263,24 @@ static int enqueue(Ctx* c, hipStream_t st, bool full, const EvalArgs& e) {
   {   // through layer 0's norm1 and the latent embedding
     RtBwdArgs a = base;
     a.K = CFD_D; a.a = dy1; a.g = s.G[gi]; a.x = s.sv.x[0][0]; a.gamma = c->lw[0].ln1g; a.gout = s.G[(gi + 1) % 3];
-    a.w = rawp(c, "latent_embd.weight"); a.ldw = CFD_LAT; a.out = e.grad; a.ldo = CFD_LAT;
+    a.w = rawp(c, "latent_embd.weight"); a.ldw = CFD_LAT; a.out = grad; a.ldo = CFD_LAT;
     CHK((bwd_gemm<RT_BPRO_LN, RT_BEPI_F32, 16>(c, st, a, CFD_LAT, ntile)));
     s.stop_gi = (gi + 1) % 3;   // the gradient at the embedding's output
   }
   return CFD_OK;
+}
+
+// Launches only (capturable): [time tables + memory side when `full`], forward and objective, reverse sweep.
+static int enqueue(Ctx* c, hipStream_t st, bool full, const weg::Args& e) {
+  WorkGuard guard(c);
+  WegRtState& s = c->weg.rt;
+  const Problem& p = c->w->pb;
+  s.launches = 0;
+  s.stop_gi = -1;
+  s.B = p.Be; s.L = p.L; s.Sp_tot = p.Sp_tot; s.St = p.S[2];
+  if (full) CHK(enqueue_memory_side(c, st));
+  CHK(enqueue_forward_and_objective(c, st, e));
+  return enqueue_reverse_sweep(c, st, e.grad);
 }
 
 }  // namespace wegrt

@@ -352,36 +352,50 @@ def _float64_result(key, inp, t, focus, neot=False, eot=()):
     return _f64[key]
 
 
-def _f32_sequence_model():
-    """A model whose handle evaluates on the float32 launch sequence (weg_eval.hpp) whatever the shape: CFD_WEG_ROWTILE is read when the
-    handle is created."""
+def _knob_model(knob):
+    """A model with the weights of hip_denoiser(1234, 1.0) whose handle was created under ``knob``=0 (the developer knobs are read when the
+    handle is created); one per knob for the session."""
     import os
     import torch
     from convofusion_amd.denoiser import Denoiser
     from tests.gpu_helpers import ABL, DENOISER_KW, hip_denoiser
-    if "m" not in _f32_sequence_model.__dict__:
-        os.environ["CFD_WEG_ROWTILE"] = "0"
+    if knob not in _knob_model.__dict__:
+        os.environ[knob] = "0"
         try:
             m = Denoiser(ablation=ABL, **DENOISER_KW)
             m.load_state_dict(hip_denoiser(1234, 1.0).state_dict(), strict=True)
             m = m.cuda().eval()
             m.engine(torch.device("cuda"))
         finally:
-            del os.environ["CFD_WEG_ROWTILE"]
-        _f32_sequence_model.m = m
-    return _f32_sequence_model.m
+            del os.environ[knob]
+        _knob_model.__dict__[knob] = m
+    return _knob_model.__dict__[knob]
 
 
-def _check_against_float64(label, m, inp, t, focus, r64, neot=False, eot=None, row_tile=True):
+def _f32_sequence_model():
+    """A model whose handle evaluates on the float32 launch sequence (weg_eval.hpp) whatever the shape."""
+    return _knob_model("CFD_WEG_ROWTILE")
+
+
+def _eager_model():
+    """A model whose handle never captures or replays an evaluation (CFD_WEG_GRAPH=0)."""
+    return _knob_model("CFD_WEG_GRAPH")
+
+
+def _check_against_float64(label, m, inp, t, focus, r64, neot=False, eot=None, row_tile=True, same_conditioning=False, dev=None, raw=None):
     """One product evaluation against the float64 restatement: losses 2e-6, max_att 2e-5, the gradient at F64_GRAD_GATE in both measures;
-    the text attention exactly 0 in masked columns, the objective's gradient at the maps exactly 0 outside the text slice."""
+    the text attention exactly 0 in masked columns, the objective's gradient at the maps exactly 0 outside the text slice.
+    ``dev``: the memories and masks already on the device (the library reuses memory-side work only for unchanged pointers);
+    ``raw``: a list that receives what ``weg.loss_and_grad`` returned."""
     import torch
     from convofusion_amd import weg
     from tests import weg_bwd_ref
     from tests.gpu_helpers import dev_inputs, read_debug, to_dev
-    mems, masks = dev_inputs(inp)
+    mems, masks = dev if dev is not None else dev_inputs(inp)
     eot_dev = to_dev(np.asarray(eot)) if eot is not None else torch.zeros(1, dtype=torch.long)
-    loss, losses, mx, grad = weg.loss_and_grad(m, to_dev(inp["sample"]), t, mems, masks, focus, neot, eot_dev)
+    loss, losses, mx, grad = weg.loss_and_grad(m, to_dev(inp["sample"]), t, mems, masks, focus, neot, eot_dev, same_conditioning=same_conditioning)
+    if raw is not None:
+        raw.append((loss, losses, mx, grad))
     l64, ls64, mx64, g64, _, att64, datt64 = r64
     B, L, _ = inp["sample"].shape
     St = inp["memories"][2].shape[1]
@@ -467,13 +481,11 @@ def test_graph_replayed_evaluation_interleaved_with_the_sampling_graph_equals_ea
     the Python side passes fresh tensors on every call.  With the inputs and outputs staged through fixed buffers the replayed
     evaluation must equal the eager one (CFD_WEG_GRAPH=0) bit for bit -- here with a new latents tensor (new address) per
     call, both graph variants (full / memory side reused), and replays of the sampling graph in between."""
-    import os
     import torch
     from convofusion_amd import weg
-    from convofusion_amd.denoiser import Denoiser
     from convofusion_amd.sampler import SamplingRun, sample_with_weg
     from convofusion_amd import scheduler
-    from tests.gpu_helpers import ABL, DENOISER_KW, SCHED_KW, hip_denoiser, to_dev
+    from tests.gpu_helpers import SCHED_KW, hip_denoiser, to_dev
     B, L, S, pad = 1, 16, (6, 20, 12, 8, 1), (2, 0, 3, 0, 0)
     cb = inputs.make_cfg_batch(seed=23, B=B, L=L, S=S, pad_tail=pad)
     mems = [to_dev(x) for x in cb["memories"]]
@@ -482,15 +494,7 @@ def test_graph_replayed_evaluation_interleaved_with_the_sampling_graph_equals_ea
     text_masks = {k: (v.chunk(7)[1].to(torch.uint8).contiguous() if v is not None else None) for k, v in masks.items()}
     eot = torch.argmax(text_masks["tlsn"].int(), dim=1) - 1
     focus = [[2, 5]]
-    m_graph = hip_denoiser(1234, 1.0)
-    os.environ["CFD_WEG_GRAPH"] = "0"
-    try:
-        m_eager = Denoiser(ablation=ABL, **DENOISER_KW)
-        m_eager.load_state_dict(m_graph.state_dict(), strict=True)
-        m_eager = m_eager.cuda().eval()
-        m_eager.engine(torch.device("cuda"))          # the knob is read when the handle is created
-    finally:
-        del os.environ["CFD_WEG_GRAPH"]
+    m_graph, m_eager = hip_denoiser(1234, 1.0), _eager_model()          # (the knob is read when the handle is created)
     sch = scheduler.DDPMScheduler(variance_type="fixed_small", **SCHED_KW)
     run = SamplingRun(m_graph, sch, mems, masks, B, L, 20, guidance_scale=7.5, seed=3)
     g = torch.Generator(device="cuda").manual_seed(5)
@@ -511,3 +515,58 @@ def test_graph_replayed_evaluation_interleaved_with_the_sampling_graph_equals_ea
     la = sample_with_weg(m_graph, sch, mems, masks, focus, params, B=B, L=L, num_inference_steps=5, guidance_scale=7.5, init_latents=init, seed=2)
     lb = sample_with_weg(m_eager, sch, mems, masks, focus, params, B=B, L=L, num_inference_steps=5, guidance_scale=7.5, init_latents=init, seed=2)
     assert torch.equal(la, lb)
+
+
+# The state machine of cfd_weg_eval on one handle: (inputs, timestep, focus, same_conditioning) per call, in order.
+#   1-2  "memories" at 500, 499: tables over all timesteps, the second call reuses the memory side at a new timestep
+#   3    True at 499: the tables stay full because the handle had them
+#   4    False at 500: back to one-row tables
+#   5-7  True at 500: eager, the second use of that key captured, then replayed
+#   8    another focus list with True: a new token-table version and graph key, the memory side still reused
+#   9    L = 32 inputs with False: the arena and the problem are rebuilt
+#   10   back to the L = 16 inputs with False
+STATE_WALK_FOCUS = {"f1": [[2, 5]], "f2": [[3, 6, 7]]}
+STATE_WALK = [("L16", 500, "f1", "memories"), ("L16", 499, "f1", "memories"), ("L16", 499, "f1", True), ("L16", 500, "f1", False),
+              ("L16", 500, "f1", True), ("L16", 500, "f1", True), ("L16", 500, "f1", True), ("L16", 500, "f2", True),
+              ("L32", 500, "f1", False), ("L16", 500, "f1", False)]
+
+
+def state_walk_inputs():
+    """{name: (inputs, device memories, device masks as uint8, eot)} of the walk: B = 1, S = (6, 20, 12, 8, 1) with pad tails
+    (2, 0, 3, 0, 0) -- the graph test's shape -- at L = 16 and L = 32.  The device tensors are made once: their addresses are part of
+    what the library compares."""
+    import torch
+    from tests.gpu_helpers import dev_inputs
+    out = {}
+    for name, L in (("L16", 16), ("L32", 32)):
+        inp = inputs.make_plain_batch(seed=23 + L, Be=1, L=L, S=(6, 20, 12, 8, 1), pad_tail=(2, 0, 3, 0, 0))
+        mems, masks = dev_inputs(inp)
+        masks = {k: (v.to(torch.uint8).contiguous() if v is not None else None) for k, v in masks.items()}
+        out[name] = (inp, mems, masks, np.argmax(inp["masks"]["tlsn"].astype(np.int64), axis=1) - 1)
+    return out
+
+
+def test_state_machine_walk_matches_float64_and_the_eager_handle():
+    """One handle through cfd_weg_eval's state machine (STATE_WALK): every reuse mode, one-row and full tables, capture and replay of
+    an evaluation, a new focus-token table, a shape change and back.  Every call on a freshly allocated latents tensor, against
+    float64 at the gates of _check_against_float64 and bit for bit against the same call on a handle that never captures
+    (CFD_WEG_GRAPH=0); then the same walk on the float32 launch sequence (CFD_WEG_ROWTILE=0) against float64."""
+    import torch
+    from tests.gpu_helpers import hip_denoiser
+    data = state_walk_inputs()
+    m_graph, m_eager, m_f32 = hip_denoiser(1234, 1.0), _eager_model(), _f32_sequence_model()
+    for m, row_tile in ((m_graph, True), (m_f32, False)):
+        for n, (name, t, fk, same) in enumerate(STATE_WALK, 1):
+            inp, mems, masks, eot = data[name]
+            focus = STATE_WALK_FOCUS[fk]
+            r64 = _float64_result(("walk", name, t, fk), inp, t, focus, True, eot)
+            kw = dict(neot=True, eot=eot, same_conditioning=same, dev=(mems, masks))
+            a = []
+            _check_against_float64(f"walk {n} {'row-tile' if row_tile else 'float32 sequence'} {name} t={t} {fk} same={same}", m, inp, t,
+                                   focus, r64, row_tile=row_tile, raw=a, **kw)
+            if row_tile:
+                b = []
+                _check_against_float64(f"walk {n} eager", m_eager, inp, t, focus, r64, raw=b, **kw)
+                (la, lsa, mxa, ga), (lb, lsb, mxb, gb) = a[0], b[0]
+                assert float(la) == float(lb) and torch.equal(lsa, lsb) and torch.equal(ga, gb), n
+                assert all(torch.equal(x, y) for ra, rb in zip(mxa, mxb) for x, y in zip(ra, rb)), n

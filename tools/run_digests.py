@@ -3,7 +3,7 @@ small test shape (B = 2, L = 16, memories S = (6, 20, 6, 8, 1) with pad tails (2
 seeds, the seeded test weights) and prints one line per run: the SHA-256 of the final latents' bytes, of ``read()`` after every iteration
 (``steps``), of the trajectory, the noise and the attention ring where the run has them (``refused=`` with the library's message for a run it does not open), and N, first_iteration, chunks_evaluated and the
 non-pointer fields of the run's cfd_sample_args; then the launches of one iteration per class and the SHA-256 of three single forwards
-(``Denoiser.forward``: output and att_mats).  The runs are deterministic: the outputs of two trees are compared with ``diff``, and a
+(``Denoiser.forward``: output and att_mats), and the word-excitation-guidance lines of ``weg_lines``.  The runs are deterministic: the outputs of two trees are compared with ``diff``, and a
 line that differs is a change of behaviour.
 
 Usage (once in each tree):  python tools/run_digests.py > digests.txt
@@ -143,6 +143,29 @@ def main():
         with torch.no_grad():
             out, att = m(x, t, mems, mem_mask_dict=masks)
         line(f"forward {name}", out=sha(out), att_mats=sha(*att))
+    weg_lines(m)
+
+
+def weg_lines(m):
+    """Word-excitation guidance (new lines only, as above): the state-machine walk of tests/test_gpu_weg.py, one line per cfd_weg_eval
+    -- results, loss and "weg.info" -- and the latents of a five-iteration guided loop at the same shape."""
+    from convofusion_amd import weg
+    from oracle import philox_ref
+    from tests.gpu_helpers import read_debug
+    from tests.test_gpu_weg import STATE_WALK, STATE_WALK_FOCUS, state_walk_inputs
+    data = state_walk_inputs()
+    for n, (name, t, fk, same) in enumerate(STATE_WALK, 1):
+        inp, wmems, wmasks, eot = data[name]
+        loss, losses, mx, grad = weg.loss_and_grad(m, to_dev(inp["sample"]), t, wmems, wmasks, STATE_WALK_FOCUS[fk], True, to_dev(eot),
+                                                   same_conditioning=same)
+        line(f"weg walk {n} {name} t={t} {fk} same_conditioning={same}", results=sha(losses, torch.stack([v for r in mx for v in r]), grad),
+             loss=repr(float(loss)), info=[float(v) for v in read_debug(m, "weg.info", (5,))])
+    cb = inputs.make_cfg_batch(seed=23, B=1, L=16, S=(6, 20, 12, 8, 1), pad_tail=(2, 0, 3, 0, 0))
+    params = dict(scale_factor=1000, scale_range=[1.0, 0.5], max_iter_to_alter=3, thresholds={1: 0.16}, max_refinement_steps=3)
+    lat = sampler.sample_with_weg(m, scheduler.DDPMScheduler(variance_type="fixed_small", **SCHED_KW), [to_dev(x) for x in cb["memories"]],
+                                  {k: to_dev(v) for k, v in cb["masks"].items()}, [[2, 5]], params, B=1, L=16, num_inference_steps=5,
+                                  guidance_scale=7.5, init_latents=to_dev(philox_ref.normal_tensor(23, 0, range(1), 1, 16)), seed=2)
+    line("sample_with_weg 5 iterations", final=sha(lat))
 
 
 if __name__ == "__main__":

@@ -40,7 +40,7 @@ static int refresh_step_rows(Ctx* c, hipStream_t st, const int* dstep, const std
 // The forward for small problems: launches of 16-token x 16-feature workgroups (rowtile.hpp); same buffers, same tap points.
 // With `sv` (the WEG evaluation, weg_rt.hpp) every residual update goes to a buffer of its own, the self-attention operands, the
 // cross-attention scores and the FFN pre-activations of every layer are kept, and the pass ends behind the last layer's
-// cross-attention (nothing above it reaches the objective).
+// cross-attention (nothing above it reaches the objective) -- unless sv->whole (cfd_denoise_vjp: the sweep starts at the output).
 
 int enqueue_rows_rt(Ctx* c, hipStream_t st, const RtSave* sv) {
   const Problem& p = c->w->pb;
@@ -190,7 +190,7 @@ int enqueue_rows_rt(Ctx* c, hipStream_t st, const RtSave* sv) {
       }
     }
     if (c->stop_stage == 4 + 4 * l) return CFD_OK;
-    if (sv && l == nl - 1) return CFD_OK;
+    if (sv && !sv->whole && l == nl - 1) return CFD_OK;
     // ---- f. time block 2                                                        (:655)
     CHK(time_block(w.wtb2_sp, w.tb2g, w.tb2b, w.btb2, 2 * l + 1, X(l, 3), X(l, 4)));
     // ---- g. FFN                                                                 (:659-661)

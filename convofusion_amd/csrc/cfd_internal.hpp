@@ -122,11 +122,12 @@ struct RtSave {
   float* sc[CFD_MAX_LAYERS];    // e_s of the cross-attention (rowtile.hpp: rt_xscore_kernel) ...
   float* cst[CFD_MAX_LAYERS];   // ... and its cell statistics
   float* pre[CFD_MAX_LAYERS];
+  bool whole = false;           // run the WHOLE network (cfd_denoise_vjp: the sweep is seeded at the output); false: stop behind the top layer's cross-attention
 };
 
 // cfd_weg_eval on the row-tile kernels (weg_rt.hpp): the arena of saved activations and gradient buffers
 struct WegRtState {
-  std::vector<long long> sig;   // shapes and pointers the arena and the problem of wk[1] were prepared for
+  std::vector<long long> sig;   // the caller (cfd_weg_eval / cfd_denoise_vjp), shapes and pointers the arena and the problem of wk[1] were prepared for
   RtSave sv;
   float *att = nullptr, *d_att = nullptr, *fws = nullptr, *dP = nullptr, *G[3] = {nullptr, nullptr, nullptr}, *dz = nullptr, *dy = nullptr,
         *dh = nullptr, *dO = nullptr, *dqkv = nullptr;

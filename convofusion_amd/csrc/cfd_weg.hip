@@ -1,5 +1,6 @@
 // libcfdenoise: word-excitation guidance -- the launch-by-launch float32 pieces (cfd_gemm_f32 ... cfd_weg_focus) and cfd_weg_eval: one evaluation of the word-excitation-guidance objective and its gradient, all launches enqueued from C++
-// (float32 launch sequence: weg_eval.hpp; small problems on the row-tile kernels: rowtile_bwd.hpp, weg_rt.hpp).
+// (float32 launch sequence: weg_eval.hpp; small problems on the row-tile kernels: rowtile_bwd.hpp, weg_rt.hpp) -- and cfd_denoise_vjp, the
+// vector-Jacobian product of one forward with respect to its sample on the same row-tile kernels.
 #include "cfd_internal.hpp"
 #include "grad.hpp"
 
@@ -173,7 +174,7 @@ static int choose_path_and_reuse(WegEval& e) {
     const bool had_full = w.rt.T > 1;
     // tables over all timesteps stay while the caller keeps stating that the conditioning is unchanged
     const int T = a->reuse_memory_side == 2 || (a->reuse_memory_side == 1 && had_full) ? c->tsin_rows : 1;
-    CHK(wegrt::prepare(c, a, T, e.st));
+    CHK(wegrt::prepare(c, wegrt::FOR_WEG, a->B, a->L, a->mem, T, e.st));
     e.arena = w.rt_ws.p;
     e.sig.insert(e.sig.end(), {(long long)(size_t)e.arena, -(long long)T});
     if (T == 1) e.sig.push_back(a->timestep);
@@ -300,4 +301,76 @@ extern "C" int cfd_weg_eval(cfd_handle c, const cfd_weg_args* a, float* losses, 
   CHK(run(e));
   if (c->weg.rt.stop) return CFD_OK;               // test hook: losses / max_att / grad are not delivered, the sweep was left early
   return deliver(e, losses, max_att, grad, loss_host);
+}
+
+// ---- cfd_denoise_vjp: d_out^T . d(out)/d(sample) of one denoiser forward on the row-tile kernels --------------------------------
+// Every refusal, before anything is touched; the row maps come back as the host sees them (part of what the problem is prepared for).
+static int check_vjp_args(Ctx* c, const cfd_vjp_args* a, const float* d_out, const float* grad, std::vector<long long>* maps) {
+  if (!c || !a || !a->sample || !d_out || !grad) return fail(CFD_E_ARG, "null argument");
+  if (!c->finalized) return fail(CFD_E_STATE, "weights not finalized");
+  const int Be = a->Be, L = a->L;
+  if (Be < 1 || L < 2) return fail(CFD_E_ARG, "bad batch / length");
+  if (L % 2) return fail(CFD_E_SHAPE, "latent length %d is odd (reference: broadcasting error at position_encoding.py:160-161)", L);
+  if (L / 2 > c->qpe_rows) return fail(CFD_E_SHAPE, "L/2 = %d exceeds the query PE buffer (%d rows)", L / 2, c->qpe_rows);
+  if (a->timestep < 0 || a->timestep >= c->tsin_rows) return fail(CFD_E_ARG, "timestep %d outside the timestep table (%d rows)", a->timestep, c->tsin_rows);
+  for (int j = 0; j < CFD_NMEM; ++j) {
+    const cfd_memory& m = a->mem[j];
+    if (!m.data || m.S < 1 || m.U < 1) return fail(CFD_E_ARG, "memory %s missing", MEM_NAMES[j]);
+    if (!m.row_map && m.U != Be) return fail(CFD_E_ARG, "memory %s: U = %d != Be = %d without a row_map", MEM_NAMES[j], m.U, Be);
+    if (m.S > c->mpe_rows) return fail(CFD_E_SHAPE, "memory %s has %d tokens, the memory PE buffer %d rows", MEM_NAMES[j], m.S, c->mpe_rows);
+  }
+  // the eligibility of the row-tile path (wegrt::eligible), limit by limit
+  if (!c->rt_on || !c->weg_rt_on) return fail(CFD_E_ARG, "cfd_denoise_vjp runs on the row-tile path, which this handle has switched off (CFD_ROWTILE / CFD_WEG_ROWTILE)");
+  if (L > RT_MAX_L) return fail(CFD_E_ARG, "cfd_denoise_vjp: L = %d exceeds RT_MAX_L = %d tokens per batch row", L, RT_MAX_L);
+  if ((long long)Be * L > c->rt_max_rows)
+    return fail(CFD_E_ARG, "cfd_denoise_vjp: Be * L = %lld token rows exceed rt_max_rows = %lld", (long long)Be * L, c->rt_max_rows);
+  if (wegrt::padded_keys(a->mem) > RT_MAX_KEYS)
+    return fail(CFD_E_ARG, "cfd_denoise_vjp: %d padded keys of the five memories together exceed RT_MAX_KEYS = %d", wegrt::padded_keys(a->mem), RT_MAX_KEYS);
+  if (c->weg.rt.stop) return fail(CFD_E_STATE, "cfd_debug_weg_stop is set: it names a launch of cfd_weg_eval's sweep");
+  HIPCHK(hipSetDevice(c->cfg.device));
+  std::vector<int32_t> hm(Be);
+  for (int j = 0; j < CFD_NMEM; ++j) {
+    const cfd_memory& m = a->mem[j];
+    maps->push_back(m.U);
+    maps->push_back((long long)(size_t)m.row_map);
+    if (!m.row_map) continue;
+    HIPCHK(hipMemcpy(hm.data(), m.row_map, (size_t)Be * 4, hipMemcpyDeviceToHost));
+    for (int b = 0; b < Be; ++b) {
+      if (hm[b] < 0 || hm[b] >= m.U) return fail(CFD_E_ARG, "memory %s: row_map[%d] = %d outside [0, %d)", MEM_NAMES[j], b, hm[b], m.U);
+      maps->push_back(hm[b]);
+    }
+  }
+  return CFD_OK;
+}
+
+extern "C" int cfd_denoise_vjp(cfd_handle c, const cfd_vjp_args* a, const float* d_out, float* out, float* grad, void* stream) {
+  std::vector<long long> maps;
+  CHK(check_vjp_args(c, a, d_out, grad, &maps));
+  c->hint_now = c->hint_same_mem = false;
+  CHK(settle_deferred_census(c));
+  WegState& w = c->weg;
+  // like cfd_weg_eval: on the handle's own stream (the one an open run's graph replays on: the two serialise), behind whatever the
+  // caller has queued on `stream`, in wk[1] (wegrt::WorkGuard): an open sampling run keeps wk[0] and its bits
+  hipStream_t caller = (hipStream_t)stream, st = c->own_stream;
+  HIPCHK(hipEventRecord(c->weg_ev, caller));
+  HIPCHK(hipStreamWaitEvent(st, c->weg_ev, 0));
+  // The call overwrites wk[1]'s problem and tables and the arena: nothing of an earlier cfd_weg_eval may be reused behind it -- neither
+  // its memory-side results (WegState::sig) nor its captured launches, whose arguments hold addresses that set-up may move.
+  w.sig.clear();
+  for (WegState::Graph& g : w.graph)
+    if (g.exec) { HIPCHK(hipStreamSynchronize(st)); g.reset(); }
+  CHK(wegrt::prepare(c, wegrt::FOR_VJP, a->Be, a->L, a->mem, 1, st, maps));
+  w.rt.T = 1;
+  w.t_host = a->timestep;
+  w.dstep_host = 0;
+  HIPCHK(hipMemcpyAsync(c->wk[1].trows.p, &w.t_host, 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(c->wk[1].d_step.p, &w.dstep_host, 4, hipMemcpyHostToDevice, st));
+  const int r = wegrt::enqueue_vjp(c, st, a->sample, d_out, grad);
+  w.launches = w.rt.launches;
+  if (r == CFD_OK && out)
+    HIPCHK(hipMemcpyAsync(out, c->wk[1].eps.p, (size_t)a->Be * a->L * CFD_LAT * 4, hipMemcpyDeviceToDevice, st));
+  // the call returns with `grad` (and `out`) complete: its census is read here, so a clamped sample or memory fails THIS call
+  HIPCHK(hipStreamSynchronize(st));
+  CHK(r);
+  return check_saturation(c, "cfd_denoise_vjp (sample, memories / their projections)");
 }

@@ -22,6 +22,8 @@
 //   B8  self-attention core backward per (row, head): dq | dk | dv                     [16 x 1536]
 //   B9  dy1 = [dq | dk | dv] Wqkv                                                      [16 x 512]
 // and at the bottom  grad = (g_d + LN1'(dy1)) We  [16 x 128].
+// cfd_denoise_vjp seeds the same sweep at the forward's output: dyN = d_out Wp  [16 x 512] (the rows prologue with K = 128), and the top
+// layer's B1 then reads dyN through decoder.norm with no running gradient yet (weg_rt.hpp, SweepSeed).
 #pragma once
 #include "rowtile.hpp"
 
@@ -36,7 +38,7 @@ enum { RT_BEPI_F32 = 0, RT_BEPI_GELU = 1 };
 
 struct RtBwdArgs {
   int L, tpr;
-  int K;                 // contraction length: 512 (LN / TB prologues), 1024, 1536
+  int K;                 // contraction length: 512 (LN / TB prologues), 1024, 1536; 128 (cfd_denoise_vjp's seed: d_out . latent_proj.weight)
   // prologue inputs
   const float* a;        // ROWS: the operand rows fp32 [M][K];  LN / TB: dy, the gradient at the LayerNorm's / the TimeBlock linear's output [M][512]
   const float* g;        // LN / TB: running gradient rows [M][512] (null: zero)

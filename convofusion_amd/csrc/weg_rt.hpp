@@ -2,6 +2,8 @@
 // word-excitation-guidance evaluation for small problems (the reference needs test batch size 1 for WEG, word_excitation_guidance.py:25).
 // ~160 launches of ~5 us instead of weg_eval.hpp's ~400 launches of ~10 us, in the folded formulation the sampling loop itself uses.
 // The evaluation has a workspace of its own (Ctx::wk[1]): it runs between two replays of an open sampling run's captured graph.
+// cfd_denoise_vjp (the vector-Jacobian product of the forward with respect to its sample) runs the same forward through the whole network
+// and the same sweep from a seed at the output, in the same arena and workspace (enqueue_vjp).
 // Included by cfd_weg.hip after weg_eval.hpp.
 #pragma once
 
@@ -19,22 +21,30 @@ static int padded_keys(const cfd_memory* mem) {   // of all five memories togeth
   return sp;
 }
 
-static bool eligible(Ctx* c, const cfd_weg_args* a) {
+static bool eligible(Ctx* c, int B, int L, const cfd_memory* mem) {
   if (!c->rt_on || !c->weg_rt_on) return false;
-  if (a->L > RT_MAX_L || (long long)a->B * a->L > c->rt_max_rows) return false;
-  return padded_keys(a->mem) <= RT_MAX_KEYS;
+  if (L > RT_MAX_L || (long long)B * L > c->rt_max_rows) return false;
+  return padded_keys(mem) <= RT_MAX_KEYS;
 }
+static bool eligible(Ctx* c, const cfd_weg_args* a) { return eligible(c, a->B, a->L, a->mem); }
 
-// (Re)build the evaluation's problem and arena when shapes or pointers change.  Host work only (allocations, row maps): never captured.
-static int prepare(Ctx* c, const cfd_weg_args* a, int T, hipStream_t st) {
+// Who prepared wk[1] and the arena: the two callers share both, and what one of them left is never reused by the other.
+enum { FOR_WEG = 0, FOR_VJP = 1 };
+
+// (Re)build the evaluation's problem and arena when the caller, shapes or pointers change.  Host work only (allocations, row maps):
+// never captured.  B rows of L tokens; `more`: what else of the caller's arguments the problem depends on (cfd_denoise_vjp: the
+// instance counts and row maps).  FOR_WEG keeps the text maps (att) for the objective; FOR_VJP keeps none, runs the whole network and
+// leaves d_att zero: the sweep's kernels add it to the text memory's dP as they are.
+static int prepare(Ctx* c, int who, int B, int L, const cfd_memory* mem_in, int T, hipStream_t st, const std::vector<long long>& more = {}) {
   WegRtState& s = c->weg.rt;
-  const int B = a->B, L = a->L, nl = c->nl, spt = padded_keys(a->mem);
-  std::vector<long long> sig = {B, L, nl, T};
-  weg::append_memories(sig, a->mem);
+  const int nl = c->nl, spt = padded_keys(mem_in);
+  std::vector<long long> sig = {who, B, L, nl, T};
+  weg::append_memories(sig, mem_in);
+  sig.insert(sig.end(), more.begin(), more.end());
   if (sig == s.sig) return CFD_OK;
   HIPCHK(hipStreamSynchronize(st));
   s.sig.clear();
-  const size_t M = (size_t)B * L, St = (size_t)a->mem[2].S;
+  const size_t M = (size_t)B * L, St = (size_t)mem_in[2].S;
   auto al = [](size_t n) { return (n + 63) & ~(size_t)63; };   // floats, 256-byte granules
   size_t n = 0;
   const size_t n_x = al(M * CFD_D), n_qk = al(M * 2 * CFD_D), n_vt = al((size_t)B * CFD_D * RT_MAX_L), n_sc = al(M * spt), n_pre = al(M * CFD_FF);
@@ -58,18 +68,20 @@ static int prepare(Ctx* c, const cfd_weg_args* a, int T, hipStream_t st) {
   s.att = take(n_att); s.d_att = take(n_att); s.fws = take(n_fws); s.dP = take(n_sc);
   for (int k = 0; k < 3; ++k) s.G[k] = take(n_x);
   s.dz = take(n_x); s.dy = take(n_x); s.dh = take(n_pre); s.dO = take(n_x); s.dqkv = take(al(M * 3 * CFD_D));
+  s.sv.whole = who == FOR_VJP;
+  if (who == FOR_VJP) HIPCHK(hipMemset(s.d_att, 0, n_att * 4));
   {
     WorkGuard guard(c);
     cfd_memory mem[CFD_NMEM];
-    float* att[CFD_NMEM] = {nullptr, nullptr, s.att, nullptr, nullptr};
-    for (int j = 0; j < CFD_NMEM; ++j) mem[j] = a->mem[j];
+    float* att[CFD_NMEM] = {nullptr, nullptr, who == FOR_WEG ? s.att : nullptr, nullptr, nullptr};
+    for (int j = 0; j < CFD_NMEM; ++j) mem[j] = mem_in[j];
     CHK(setup_problem(c, B, L, mem, att, 0, T));
     if (T > 1) {   // full tables: row t belongs to timestep t
       std::vector<int32_t> iota(T);
       for (int t = 0; t < T; ++t) iota[t] = t;
       HIPCHK(hipMemcpy(c->w->trows.p, iota.data(), (size_t)T * 4, hipMemcpyHostToDevice));
     }
-    if (!c->w->pb.rt) return fail(CFD_E_STATE, "row-tile WEG evaluation: the problem does not qualify for the row-tile path");
+    if (!c->w->pb.rt) return fail(CFD_E_STATE, "row-tile evaluation: the problem does not qualify for the row-tile path");
   }
   s.sig = sig;
   return CFD_OK;
@@ -102,9 +114,9 @@ static int bwd_gemm(Ctx* c, hipStream_t st, const RtBwdArgs& a, int N, int ntile
 //     products (kbtab, vbtab) and mem_scale_table_kernel, + temb_center_kernel + 1.  (The callee also fills a scale plane per memory;
 //     the figure is compared between trees and stays what it has always been.)
 //   to_split_kernel + enqueue_rows_rt with saved activations (cfd_forward.hip): the embedding + nine launches per layer, less the
-//     three of the top layer behind its cross-attention.
+//     three of the top layer behind its cross-attention; the whole network (cfd_denoise_vjp) has them and the latent projection.
 static int memory_side_launches(int nl) { return (2 + 2 * nl) + (6 * CFD_NMEM + 2); }
-static int forward_launches(int nl) { return 1 + 1 + 9 * nl - 3; }
+static int forward_launches(int nl, bool whole = false) { return whole ? 1 + 1 + 9 * nl + 1 : 1 + 1 + 9 * nl - 3; }
 
 // [time tables + memory side]: what an evaluation that reuses the memory side skips
 static int enqueue_memory_side(Ctx* c, hipStream_t st) {
@@ -118,17 +130,24 @@ static int enqueue_memory_side(Ctx* c, hipStream_t st) {
   return CFD_OK;
 }
 
-// forward with saved activations (rowtile.hpp), then the objective and its gradient at the nine maps
-static int enqueue_forward_and_objective(Ctx* c, hipStream_t st, const weg::Args& e) {
+// forward with saved activations (rowtile.hpp) from `latents` [M][128]
+static int enqueue_forward_saved(Ctx* c, hipStream_t st, const float* latents) {
   WegRtState& s = c->weg.rt;
   Work* w = c->w;
-  const int nl = c->nl, B = s.B, L = s.L, St = s.St;
   const long long M = w->pb.M, n = M * (CFD_LAT / 8);
-  hipLaunchKernelGGL(to_split_kernel<>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, e.latents, w->sample_sp.as<char>(), M, CFD_LAT,
+  hipLaunchKernelGGL(to_split_kernel<>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, latents, w->sample_sp.as<char>(), M, CFD_LAT,
                      (long long)CFD_LAT, (long long)CFD_LAT * 4, c->sat_in());
   HIPCHK(hipGetLastError());
   CHK(enqueue_rows_rt(c, st, &s.sv));
-  s.launches += forward_launches(nl);
+  s.launches += forward_launches(c->nl, s.sv.whole);
+  return CFD_OK;
+}
+
+// forward with saved activations, then the objective and its gradient at the nine maps
+static int enqueue_forward_and_objective(Ctx* c, hipStream_t st, const weg::Args& e) {
+  WegRtState& s = c->weg.rt;
+  const int nl = c->nl, B = s.B, L = s.L, St = s.St;
+  CHK(enqueue_forward_saved(c, st, e.latents));
   s.focus_large = !(L * (e.last - 1) <= WEG_SMALL_CELLS && e.nt_max <= WEG_SMALL_TOK && L <= 64);
   if (!s.focus_large)
     hipLaunchKernelGGL(weg_focus_small_kernel<>, dim3((unsigned)B), dim3(256), 0, st, s.att, e.tok_off, e.tok_idx, B, nl, L, St, e.last, e.k3[0], e.k3[1],
@@ -141,8 +160,16 @@ static int enqueue_forward_and_objective(Ctx* c, hipStream_t st, const weg::Args
   return CFD_OK;
 }
 
+// Where the reverse sweep starts.  d_out == null (cfd_weg_eval): at the text maps -- the top layer's B5 takes d_att alone, nothing above
+// its cross-attention reaches the objective.  d_out (cfd_denoise_vjp): the cotangent at the forward's output [M][128] -- one product
+// through latent_proj, then the top layer's B1 .. B4 like every other layer's, with decoder.norm where a lower layer has the next
+// layer's norm1 (and d_att all zero: the objective contributes nothing).
+struct SweepSeed {
+  const float* d_out = nullptr;
+};
+
 // reverse sweep (rowtile_bwd.hpp): B1 .. B9 per layer from the top, then the embedding's backward into `grad`
-static int enqueue_reverse_sweep(Ctx* c, hipStream_t st, float* grad) {
+static int enqueue_reverse_sweep(Ctx* c, hipStream_t st, const SweepSeed& seed, float* grad) {
   WegRtState& s = c->weg.rt;
   Work* w = c->w;
   const Problem& p = w->pb;
@@ -175,9 +202,15 @@ static int enqueue_reverse_sweep(Ctx* c, hipStream_t st, float* grad) {
   auto Wraw = [&](int l, const char* name) -> const float* { return rawp(c, "decoder.layers." + std::to_string(l) + "." + name); };
   int gi = 0;                 // G[gi] holds the running gradient (valid once have_g)
   bool have_g = false;
-  const float* dy1 = nullptr; // gradient at the next layer's norm1 output
+  const float* dy1 = nullptr; // gradient at the next layer's norm1 output (the top layer under an output seed: at decoder.norm's)
+  if (seed.d_out) {           // d_out . latent_proj.weight
+    RtBwdArgs a = base;
+    a.K = CFD_LAT; a.a = seed.d_out; a.w = rawp(c, "latent_proj.weight"); a.ldw = CFD_D; a.out = s.dy; a.ldo = CFD_D;
+    CHK((bwd_gemm<RT_BPRO_ROWS, RT_BEPI_F32, CFD_LAT / 32>(c, st, a, CFD_D, ntile)));
+    dy1 = s.dy;
+  }
   // test hook (cfd_debug_weg_stop): leave behind launch B<k> of layer l, remembering where the running gradient is
-#define WEG_STOP_AT(k) do { if (s.stop == 16 * l + (k)) { s.stop_gi = have_g || l < nl - 1 ? gi : -1; return CFD_OK; } } while (0)
+#define WEG_STOP_AT(k) do { if (s.stop == 16 * l + (k)) { s.stop_gi = have_g ? gi : -1; return CFD_OK; } } while (0)
   for (int l = nl - 1; l >= 0; --l) {
     const LayerW& lw = c->lw[l];
     RtXBwdArgs x5 = xb;
@@ -189,14 +222,15 @@ static int enqueue_reverse_sweep(Ctx* c, hipStream_t st, float* grad) {
       x5.kb[j] = w->now_kb[j] + (size_t)l * CFD_D;
       x5.vb[j] = w->now_vb[j] + (size_t)l * CFD_D;
     }
-    if (l < nl - 1) {
-      const LayerW& up = c->lw[l + 1];
-      {   // B1: through the next layer's norm1 into this layer's output, then linear2 and the GELU
+    if (l < nl - 1 || seed.d_out) {
+      {   // B1: through the next layer's norm1 (the top layer: decoder.norm) into this layer's output, then linear2 and the GELU
         RtBwdArgs a = base;
-        a.K = CFD_D; a.a = dy1; a.g = s.G[gi]; a.x = s.sv.x[l + 1][0]; a.gamma = up.ln1g; a.gout = s.G[(gi + 1) % 3];
+        a.K = CFD_D; a.a = dy1; a.g = have_g ? s.G[gi] : nullptr; a.x = s.sv.x[l + 1][0]; a.gout = s.G[(gi + 1) % 3];
+        a.gamma = l < nl - 1 ? c->lw[l + 1].ln1g : rawp(c, "decoder.norm.weight");
         a.w = Wraw(l, "linear2.weight"); a.ldw = CFD_FF; a.out = s.dh; a.ldo = CFD_FF; a.pre = s.sv.pre[l];
         CHK((bwd_gemm<RT_BPRO_LN, RT_BEPI_GELU, 16>(c, st, a, CFD_FF, ntile)));
         gi = (gi + 1) % 3;
+        have_g = true;
       }
       WEG_STOP_AT(1);
       {   // B2: linear1
@@ -224,13 +258,13 @@ static int enqueue_reverse_sweep(Ctx* c, hipStream_t st, float* grad) {
     }
     {   // B5: softmax backward and the folded keys
       RtXBwdArgs a = x5;
-      a.dp_from_datt = have_g || l < nl - 1 ? 0 : 1;
+      a.dp_from_datt = have_g ? 0 : 1;
       CHK(sweep_launch(c, st, dy_kernel, dim3(CFD_D / 16, ntile), 512, rt_xbwd_dy_lds(p.Sp_tot), a));
     }
     WEG_STOP_AT(5);
     {   // B6: norm2, then time block 1's projection
       RtBwdArgs a = base;
-      a.K = CFD_D; a.a = s.dy; a.g = (l < nl - 1) ? s.G[gi] : nullptr; a.x = s.sv.x[l][2]; a.gamma = lw.ln2g; a.gout = s.G[(gi + 1) % 3];
+      a.K = CFD_D; a.a = s.dy; a.g = have_g ? s.G[gi] : nullptr; a.x = s.sv.x[l][2]; a.gamma = lw.ln2g; a.gout = s.G[(gi + 1) % 3];
       a.w = Wraw(l, "time_block1.out_layers.2.weight"); a.ldw = CFD_D; a.out = s.dz; a.ldo = CFD_D;
       CHK((bwd_gemm<RT_BPRO_LN, RT_BEPI_F32, 16>(c, st, a, CFD_D, ntile)));
       gi = (gi + 1) % 3;
@@ -280,7 +314,21 @@ static int enqueue(Ctx* c, hipStream_t st, bool full, const weg::Args& e) {
   s.B = p.Be; s.L = p.L; s.Sp_tot = p.Sp_tot; s.St = p.S[2];
   if (full) CHK(enqueue_memory_side(c, st));
   CHK(enqueue_forward_and_objective(c, st, e));
-  return enqueue_reverse_sweep(c, st, e.grad);
+  return enqueue_reverse_sweep(c, st, SweepSeed{}, e.grad);
+}
+
+// cfd_denoise_vjp's launches: time tables and memory side, the whole forward with saved activations, the sweep from the output
+static int enqueue_vjp(Ctx* c, hipStream_t st, const float* sample, const float* d_out, float* grad) {
+  WorkGuard guard(c);
+  WegRtState& s = c->weg.rt;
+  const Problem& p = c->w->pb;
+  s.launches = 0;
+  s.stop_gi = -1;
+  s.B = p.Be; s.L = p.L; s.Sp_tot = p.Sp_tot; s.St = p.S[2];
+  s.focus_large = 0;
+  CHK(enqueue_memory_side(c, st));
+  CHK(enqueue_forward_saved(c, st, sample));
+  return enqueue_reverse_sweep(c, st, SweepSeed{d_out}, grad);
 }
 
 }  // namespace wegrt

@@ -6,7 +6,14 @@ Same constructor signature (reference convofusion/models/architectures/denoiser.
 section 8b), so ``instantiate_from_config`` (convofusion/config.py:24-31) can point at it by
 changing ``target`` in configs/modules/denoiser.yaml, and ``model.load_state_dict`` of a reference
 checkpoint loads strictly.  The torch modules below are parameter CONTAINERS only: the forward is
-the HIP path.  Inference only (no autograd through the kernels).
+the HIP path.
+
+Autograd: ``forward`` is differentiable with respect to ``sample`` -- and nothing else.  Under grad mode with
+``sample.requires_grad`` the returned output carries a ``grad_fn`` (``_DenoiseVjp``, once differentiable): its
+forward is the inference path (bit-identical output), its backward one ``cfd_denoise_vjp`` call, which recomputes the
+forward with saved activations and runs the reverse sweep of the row-tile kernels, so no activation state outlives a
+call.  The attention maps come back detached; no gradient reaches parameters or memories (one that requires grad is
+refused), and shapes beyond the row-tile path (``vjp_refusal``) and per-row timesteps are refused before any device work.
 """
 import copy
 import ctypes as C
@@ -76,6 +83,53 @@ def _contents_signature(tensors, force_checksum=False):
         for i, g in zip(todo, got):
             sums[i] = tuple(g)
     return list(zip(vers, sums))
+
+
+# The limits of the differentiable forward: those of the row-tile path of the library (csrc/rowtile.hpp RT_MAX_L / RT_MAX_KEYS; the
+# handle's rt_max_rows, which the developer knob CFD_ROWTILE_MAX_ROWS moves).
+VJP_MAX_L = 32
+VJP_MAX_KEYS = 1024
+VJP_MAX_ROWS = 700
+
+
+def vjp_max_rows():
+    try:
+        return int(os.environ.get("CFD_ROWTILE_MAX_ROWS", VJP_MAX_ROWS))
+    except ValueError:
+        return VJP_MAX_ROWS
+
+
+def vjp_refusal(Be, L, S, max_rows=None):
+    """Why ``Denoiser.forward`` cannot be differentiated at batch ``Be``, ``L`` tokens per row and memory lengths ``S`` (five ints), or
+    None when it can: the message names the limit that is exceeded.  Pure: no library, no device."""
+    max_rows = vjp_max_rows() if max_rows is None else int(max_rows)
+    if L > VJP_MAX_L:
+        return f"L = {L} tokens per batch row exceed the row-tile path's {VJP_MAX_L}"
+    if Be * L > max_rows:
+        return f"Be * L = {Be * L} token rows exceed the row-tile path's {max_rows}"
+    keys = sum((int(s) + 31) // 32 * 32 for s in S)
+    if keys > VJP_MAX_KEYS:
+        return f"{keys} padded keys of the five memories together (each length rounded up to 32) exceed the row-tile path's {VJP_MAX_KEYS}"
+    return None
+
+
+class _DenoiseVjp(torch.autograd.Function):
+    """``out`` of ``Denoiser._forward_hip`` as a function of ``sample``; backward: cfd_denoise_vjp on the saved INPUTS."""
+
+    @staticmethod
+    def forward(ctx, sample, denoiser, timestep, encoder_hidden_states, mem_mask_dict, kwargs):
+        out, att = denoiser._forward_hip(sample, timestep, encoder_hidden_states, mem_mask_dict, kwargs)
+        ctx.denoiser, ctx.t, ctx.side = denoiser, int(torch.as_tensor(timestep).reshape(-1)[0].item()), bool(kwargs.get("side_engine", False))
+        ctx.mems, ctx.masks = list(encoder_hidden_states), dict(mem_mask_dict or {})
+        ctx.save_for_backward(sample)
+        ctx.mark_non_differentiable(*att)
+        return (out, *att)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_out, *d_att):
+        (sample,) = ctx.saved_tensors
+        return ctx.denoiser.vjp(sample, ctx.t, ctx.mems, ctx.masks, d_out, side_engine=ctx.side)[1], None, None, None, None, None
 
 
 class _PE(nn.Module):
@@ -284,14 +338,58 @@ class Denoiser(nn.Module):
             arr[j] = _lib.Memory(m.data_ptr(), rm, mp, m.shape[0], m.shape[1])
         return arr, keep
 
+    # ---- the vector-Jacobian product ---------------------------------------------------------------
+    def vjp(self, sample, timestep, encoder_hidden_states, mem_mask_dict, d_out, *, row_maps=None, side_engine=False, want_out=True):
+        """(out or None, d_out^T . d(out)/d(sample)) of one forward: the direct ``cfd_denoise_vjp`` call (the backward of the
+        differentiable ``forward``).  ``row_maps``: as in ``pack_memories`` -- distinct memories with one int32 map [Be] each."""
+        Be, L, _ = sample.shape
+        why = vjp_refusal(Be, L, [int(m.shape[1]) for m in encoder_hidden_states])
+        if why is not None:
+            raise NotImplementedError(f"the gradient of the HIP denoiser with respect to its sample runs on the row-tile path only: {why}")
+        lib = _lib.load()
+        h = self.engine(sample.device, mem_len=max(int(m.shape[1]) for m in encoder_hidden_states), side=bool(side_engine))
+        x = sample.detach().to(torch.float32).contiguous()
+        d = d_out.detach().to(device=x.device, dtype=torch.float32).contiguous()
+        if tuple(d.shape) != tuple(x.shape):
+            raise ValueError(f"d_out must have the sample's shape {list(x.shape)}")
+        mems, keep = self.pack_memories(encoder_hidden_states, mem_mask_dict, row_maps)
+        a = _lib.VjpArgs()
+        a.Be, a.L, a.timestep, a.sample, a.mem = Be, L, int(timestep), x.data_ptr(), mems
+        out = torch.empty_like(x) if want_out else None
+        grad = torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            _lib.check(lib.cfd_denoise_vjp(h, C.byref(a), C.c_void_p(d.data_ptr()), C.c_void_p(out.data_ptr()) if want_out else None,
+                                           C.c_void_p(grad.data_ptr()), C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)))
+        del keep
+        return out, grad
+
     # ---- forward -------------------------------------------------------------------------------
     def forward(self, sample, timestep, encoder_hidden_states, lengths=None, mem_mask_dict=dict(), **kwargs):
         """``kwargs['side_engine']=True`` (extension): run on the second handle, for calls made while a sampling run is
-        open on the first; every other keyword (``return_dict`` ...) is ignored like the reference does."""
-        if torch.is_grad_enabled() and sample.requires_grad:
-            raise NotImplementedError("the HIP denoiser is inference-only: call it under torch.no_grad()")
+        open on the first; every other keyword (``return_dict`` ...) is ignored like the reference does.
+        Under grad mode with ``sample.requires_grad`` the output is differentiable with respect to ``sample`` (module docstring)."""
         if sample.dim() != 3 or sample.shape[-1] != self.latent_dim:
             raise ValueError(f"sample must be [batch, tokens, {self.latent_dim}]")
+        if not (torch.is_grad_enabled() and sample.requires_grad):
+            return self._forward_hip(sample, timestep, encoder_hidden_states, mem_mask_dict, kwargs)
+        # every refusal of the differentiable forward, before any device work
+        for name, m in zip(MEM_NAMES, encoder_hidden_states):
+            if m.requires_grad:
+                raise NotImplementedError(f"the HIP denoiser has no gradient with respect to its memories ({name} requires grad): detach it")
+        for name, m in (mem_mask_dict or {}).items():
+            if m is not None and m.requires_grad:
+                raise NotImplementedError(f"the HIP denoiser has no gradient with respect to a key-padding mask ({name} requires grad)")
+        if torch.as_tensor(timestep).numel() != 1:
+            raise NotImplementedError("the gradient of the HIP denoiser with respect to its sample needs one timestep for all rows "
+                                      "(a per-row timestep vector is not on the row-tile path)")
+        why = vjp_refusal(sample.shape[0], sample.shape[1], [int(m.shape[1]) for m in encoder_hidden_states])
+        if why is not None:
+            raise NotImplementedError(f"the gradient of the HIP denoiser with respect to its sample runs on the row-tile path only: {why}")
+        out, *att = _DenoiseVjp.apply(sample, self, timestep, encoder_hidden_states, mem_mask_dict, kwargs)
+        return (out, list(att))
+
+    def _forward_hip(self, sample, timestep, encoder_hidden_states, mem_mask_dict, kwargs):
+        """The inference path: one cfd_forward."""
         lib = _lib.load()
         Be, L, _ = sample.shape
         h = self.engine(sample.device, mem_len=max(int(m.shape[1]) for m in encoder_hidden_states), side=bool(kwargs.get("side_engine", False)))

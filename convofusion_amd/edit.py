@@ -59,6 +59,23 @@ def token_mask(B, keep_frames=None, keep_parts=("body", "hands"), L=16):
     return mask.reshape(1, L).expand(int(B), L).clone()
 
 
+def keyframe_loss(target, mask):
+    """The loss of soft key-pose constraints for ``sampler.sample_with_loss_guidance``: a function x0 [B, L, 128] -> the mean-square
+    error against ``target`` [B, L, 128] over the tokens of ``mask`` (bool / 0-1 [B, L], e.g. ``token_mask``).  Where ``edit_motion``
+    REPLACES the kept tokens every iteration, the guided loop pulls the predicted clean latents towards them and leaves the denoiser
+    free to reconcile the rest."""
+    m = (mask != 0)
+    n = int(m.sum().item()) * int(target.shape[-1])
+    if tuple(m.shape) != tuple(target.shape[:2]) or n == 0:
+        raise ValueError("keyframe_loss: mask must be [B, L] like target [B, L, 128] and keep at least one token")
+
+    def loss(x0):
+        w = m.to(device=x0.device, dtype=x0.dtype).unsqueeze(-1)
+        d = (x0 - target.to(device=x0.device, dtype=x0.dtype)) * w
+        return (d * d).sum() / n
+    return loss
+
+
 def vae_to_loop(z):
     """VAE latent [2, B, T, D] (body | hands) -> loop latents [B, 2T, D]: the reference's permute(1, 2, 0, 3) (convofusion.py:725) and
     reshape(bs, t * bh, dim) (:558)."""

@@ -16,8 +16,9 @@ import torch
 from . import _lib
 from .denoiser import Denoiser
 # the pure half of opening a run: the argument checks of every kind and the kind of a run (importable from here as before)
-from .run_kind import (_AUTO_RUN, RunKind, check_anchor, check_edit, check_inversion, check_noise_space,  # noqa: F401
-                       check_operands, check_tie, edit_first_iteration, refuse_sample_prediction, resolve_run_kind, sample_prediction)
+from .run_kind import (_AUTO_RUN, RunKind, check_anchor, check_edit, check_inversion, check_loss_guidance,  # noqa: F401
+                       check_noise_space, check_operands, check_tie, edit_first_iteration, refuse_sample_prediction, resolve_run_kind,
+                       sample_prediction)
 
 # which guidance chunk carries which conditional memory (reference convofusion.py:909-929, 527-541)
 CFG_CHUNKS = 7
@@ -1039,6 +1040,95 @@ def sample_with_weg(denoiser, scheduler, encoder_hidden_states, cond_masks, focu
     finally:
         run.close()     # an exception (bad focus index, CfdError ...) must not leave the run open on the denoiser's handle
     return (lat, att) if return_attention else lat
+
+
+def guided_chunks(weights):
+    """The guidance chunks a combine e_0 + sum_k w_k (e_k - e_0) needs: chunk 0 and every k whose weight is not 0 somewhere in
+    ``weights`` [..., 8] (a run's default weights or its table)."""
+    import numpy as np
+    w = np.asarray(weights, dtype=np.float64).reshape(-1, 8)
+    return [0] + [k for k in range(1, 8) if bool((w[:, k] != 0).any())]
+
+
+def _loss_guidance_step_size(step_size, i, t):
+    if callable(step_size):
+        return float(step_size(i, t))
+    try:
+        return float(step_size[i])
+    except TypeError:
+        return float(step_size)
+
+
+def sample_with_loss_guidance(denoiser, scheduler, encoder_hidden_states, cond_masks, loss_fn, step_size, *, B, L=16,
+                              num_inference_steps=1000, guidance_scale=7.5, guidance_chunks=CFG_CHUNKS, guided_iterations=None, **kw):
+    """The loop with guidance by any differentiable loss of the predicted clean latents: before iteration i of ``guided_iterations``
+    (an iterable of indices into the scheduler's full table; None: every iteration) the latents move by
+    -step_size_i * d loss / d latents, then the captured guided step runs as usual (the shape of ``sample_with_weg``).
+    loss = loss_fn(x0_hat) with x0_hat = (x - sqrt(1 - acp_t) eps_guided(x)) / sqrt(acp_t); eps_guided is the run's own guidance
+    combine e_0 + sum_k w_k (e_k - e_0) (``default_guidance_weights`` or the ``modality_weights`` table) of the chunks whose weight is
+    not 0, evaluated through the differentiable ``Denoiser.forward`` on the denoiser's second engine (the run owns the first).
+    ``loss_fn``: any torch function [B, L, 128] -> scalar (``edit.keyframe_loss``: soft key-pose constraints).  ``step_size``: a
+    number, a sequence indexed by iteration, or a callable (i, t).  With step_size 0 the result is ``sample``'s, bit for bit.
+    DDPMScheduler and DDIMScheduler with epsilon prediction; every refusal: ``check_loss_guidance``.  The evaluated chunks times B
+    rows must fit the differentiable forward (``denoiser.vjp_refusal``).  Other keywords: as in ``sample`` (no ``operands="auto"``)."""
+    from .denoiser import vjp_refusal
+    check_loss_guidance(scheduler, noise_space=kw.get("noise_space"), anchor_trajectory=kw.get("anchor_trajectory"), tie=kw.get("tie"))
+    if check_operands(kw.get("operands")) == "auto":
+        raise NotImplementedError("sample_with_loss_guidance: operands='auto' restarts a run whose census trips; give an operand policy")
+    if not callable(loss_fn):
+        raise TypeError("loss_fn must be a callable [B, L, 128] -> scalar")
+    G = guidance_chunks
+    n_full = len(scheduler.timestep_table(num_inference_steps)[1])
+    mw = kw.get("modality_weights")
+    wtab = modality_weight_table(mw, guidance_scale, n_full, B, G) if mw is not None else None      # [n_full, B, 8]
+    chunks = guided_chunks(wtab if wtab is not None else default_guidance_weights(G, guidance_scale))
+    why = vjp_refusal(len(chunks) * B, L, [int(m.shape[1]) for m in encoder_hidden_states])
+    if why is not None:
+        raise NotImplementedError(f"sample_with_loss_guidance: the gradient of the {len(chunks)} evaluated guidance chunks runs on the "
+                                  f"row-tile path only: {why}")
+    guided = None if guided_iterations is None else {int(i) for i in guided_iterations}
+    scheduler.set_timesteps(num_inference_steps)
+    run = _open_run(denoiser, scheduler, encoder_hidden_states, cond_masks, B, L, num_inference_steps, False,
+                    guidance_scale=guidance_scale, guidance_chunks=G, **kw)
+    keep_att = denoiser.return_attention
+    try:
+        dev = run.device
+        rm = kw.get("row_maps")
+        if rm is not None:       # distinct memories + row maps (build_guidance_batch): gather the evaluated chunks' rows
+            idx = [torch.cat([m[c * B:(c + 1) * B] for c in chunks]).long() for m in rm]
+            states = [e.index_select(0, i.to(e.device)).detach().contiguous() for e, i in zip(encoder_hidden_states, idx)]
+            masks = {k: (v.index_select(0, idx[_lib.MEM_NAMES.index(k)].to(v.device)).contiguous() if v is not None else v)
+                     for k, v in (cond_masks or {}).items()}
+        else:
+            states = [torch.cat([e.chunk(G)[c] for c in chunks]).detach().contiguous() for e in encoder_hidden_states]
+            masks = {k: (torch.cat([v.chunk(G)[c] for c in chunks]).contiguous() if v is not None else v) for k, v in (cond_masks or {}).items()}
+        w_default = torch.tensor(default_guidance_weights(G, guidance_scale), dtype=torch.float32, device=dev)
+        acp = scheduler.alphas_cumprod.detach().to("cpu", torch.float64)
+        denoiser.return_attention = False
+        for i, t in enumerate(run.timesteps, start=run.first_iteration):
+            if guided is None or i in guided:
+                run.inpaint()    # rollout / edit: the re-noised tokens go in before the update, as in sample_with_weg
+                x = run.read().requires_grad_(True)
+                w = torch.from_numpy(wtab[i]).to(dev) if wtab is not None else w_default.expand(B, 8)      # [B, 8]
+                with torch.enable_grad():
+                    out, _ = denoiser(sample=x.repeat(len(chunks), 1, 1), timestep=int(t), encoder_hidden_states=states, mem_mask_dict=masks,
+                                      side_engine=True)
+                    e = out.view(len(chunks), B, L, out.shape[-1])
+                    eps = e[0]
+                    for n, c in enumerate(chunks[1:], start=1):
+                        eps = eps + w[:, c].view(B, 1, 1) * (e[n] - e[0])
+                    a_t = float(acp[int(t)])
+                    x0 = (x - (1.0 - a_t) ** 0.5 * eps) / a_t ** 0.5
+                    loss = loss_fn(x0)
+                    (g,) = torch.autograd.grad(loss, x)
+                # (the side engine ran on torch's current stream, the captured iteration replays on the run's own: ``write`` waits for
+                #  the former, so the two never execute side by side)
+                run.write(x.detach() - _loss_guidance_step_size(step_size, i, int(t)) * g)
+            run.steps(1)
+        return run.read(close=True)
+    finally:
+        denoiser.return_attention = keep_att
+        run.close()     # an exception must not leave the run open on the denoiser's handle
 
 
 def diffusion_reverse(model, encoder_hidden_states, lengths=None, cond_masks=dict(), focus_indices=[], *,

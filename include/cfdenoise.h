@@ -543,6 +543,26 @@ typedef struct {
                                        evaluation selects its row; larger problems treat a new timestep like 0. */
 } cfd_weg_args;
 int cfd_weg_eval(cfd_handle h, const cfd_weg_args* args, float* losses, float* max_att, float* grad, float* loss_host, void* stream);
+/* The vector-Jacobian product of one denoiser forward with respect to its sample: replaces
+ *   sample.requires_grad_(True); out, _ = denoiser(sample, t, encoder_hidden_states, ...); torch.autograd.grad(out, sample, d_out)
+ * for any cotangent d_out at the output (cfd_weg_eval's gradient is hard-wired to the attention-focus objective of the text maps).
+ * One call runs the forward with saved activations through the whole network and the reverse sweep of cfd_weg_eval's row-tile path
+ * seeded at the output: d_out . latent_proj.weight, decoder.norm, then every layer from the top; no term from the attention maps, no
+ * gradients to weights or memories.  It launches eagerly on the handle's own stream behind `stream` and returns with its results
+ * complete.  It shares the row-tile arena and workspace with cfd_weg_eval: a cfd_weg_eval after it reuses nothing
+ * (reuse_memory_side is then ignored once), and the bits of a sampling run that is open on the handle are unchanged.
+ *   d_out dev [Be][L][128]   the cotangent at the forward's output
+ *   out   dev [Be][L][128]   or NULL: the forward's output as this call computed it (cfd_forward's, bit for bit, on the same path)
+ *   grad  dev [Be][L][128]   d_out^T . d(out)/d(sample)
+ * Limits (those of the row-tile path; CFD_E_ARG names the one exceeded): L <= 32, Be * L <= 700 token rows (CFD_ROWTILE_MAX_ROWS), the
+ * padded keys of the five memories together (each length rounded up to 32) <= 1024, one timestep for all rows. */
+typedef struct {
+  int Be, L;
+  int timestep;
+  const float* sample;           /* dev [Be][L][128] */
+  cfd_memory mem[CFD_NUM_MEM];   /* as in cfd_forward: U distinct memories, an optional row_map [Be], key-padding masks */
+} cfd_vjp_args;
+int cfd_denoise_vjp(cfd_handle h, const cfd_vjp_args* args, const float* d_out, float* out, float* grad, void* stream);
 int cfd_sample_write(cfd_handle h, const float* latents);
 int cfd_sample_inpaint(cfd_handle h);
 

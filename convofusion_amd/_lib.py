@@ -27,7 +27,7 @@ SYMBOLS = [
     "cfd_vae_encode", "cfd_sample_begin_weighted", "cfd_sample_begin_edit", "cfd_sample_begin_invert", "cfd_sample_begin_anchored",
     "cfd_sample_begin_tied", "cfd_ddpm_invert", "cfd_sample_begin_replay", "cfd_sample_parallel", "cfd_test_picard_stride",
     "cfd_test_picard_sweep", "cfd_debug_weg_stop", "cfd_debug_weg_fill", "cfd_scheduler_step_pred", "cfd_dpmsolver_step_pred",
-    "cfd_debug_forward_operands", "cfd_denoise_vjp",
+    "cfd_debug_forward_operands", "cfd_denoise_vjp", "cfd_debug_live_buffers",
 ]
 
 # cfd_sample_args.prediction_type / the _pred entry points, by the schedulers' config string
@@ -292,6 +292,7 @@ def load():
     lib.cfd_debug_weg_stop.argtypes = [C.c_void_p, C.c_int]
     lib.cfd_debug_forward_operands.argtypes = [C.c_void_p, C.c_int]
     lib.cfd_debug_weg_fill.argtypes = [C.c_void_p, C.c_float]
+    lib.cfd_debug_live_buffers.argtypes = [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
     for name in SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("cfd_last_error", "cfd_destroy", "cfd_source_hash"):

@@ -10,6 +10,7 @@ int fail(int code, const char* fmt, ...) {
   va_end(ap);
   return code;
 }
+std::atomic<long long> g_dbuf_live{0}, g_dbuf_live_bytes{0};   // live device buffers of the process (owned.hpp: DBuf::ensure / release)
 
 // ---- create / destroy -----------------------------------------------------------------------------
 extern "C" const char* cfd_last_error(void) { return g_err; }
@@ -76,29 +77,6 @@ extern "C" void cfd_destroy(cfd_handle c) {
   if (!c) return;
   (void)hipSetDevice(c->cfg.device);
   (void)hipDeviceSynchronize();
-  if (c->gexec) (void)hipGraphExecDestroy(c->gexec);
-  if (c->graph) (void)hipGraphDestroy(c->graph);
-  c->weg.release();
-  if (c->weg_ev) (void)hipEventDestroy(c->weg_ev);
-  c->sat.release();
-  c->acen.release();
-  for (auto& kv : c->raw) kv.second.release();
-  DBuf* all[] = {&c->we_sp, &c->wp_sp, &c->wp_f, &c->ln_cd_p, &c->we_all, &c->be_all, &c->tsin, &c->latents, &c->coef, &c->inoise, &c->hist, &c->wtab, &c->esrc, &c->enoise, &c->ekeep};
-  for (DBuf* b : all) b->release();
-  c->wk[0].release();
-  c->wk[1].release();
-  for (int j = 0; j < CFD_NMEM; ++j) {
-    c->wk_all_sp[j].release(); c->wv_all_sp[j].release(); c->mem_own[j].release(); c->perm_map[j].release();
-    c->lv_map[j].release(); c->lv_mask[j].release();
-  }
-  c->pic_s.release(); c->pic_part.release(); c->pic_err.release();
-  for (auto& l : c->lw) {
-    DBuf* lb[] = {&l.wqk_f, &l.wv_f, &l.w1_f, &l.ln_cd, &l.wqkv_sp, &l.bqk, &l.wo_sp, &l.bo2, &l.wtb1_sp, &l.wtb2_sp, &l.w1_sp, &l.w2_sp, &l.cross_bias};
-    for (DBuf* b : lb) b->release();
-  }
-  if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-  if (c->pev[0]) (void)hipEventDestroy(c->pev[0]);
-  if (c->pev[1]) (void)hipEventDestroy(c->pev[1]);
   delete c;
 }
 
@@ -328,8 +306,6 @@ extern "C" int cfd_finalize_weights(cfd_handle c) {
   }
   HIPCHK(hipDeviceSynchronize());
   CHK(check_saturation(c, "cfd_finalize_weights (a weight or a folded weight product)"));
-  for (int j = 0; j < CFD_NMEM; ++j) { wk_f[j].release(); wv_f[j].release(); }
-  tmpf.release(); tmpd1.release(); tmpd2.release(); vd1.release(); vd2.release(); accd.release(); tmpfold.release();
   c->finalized = true;
   ++c->wver;
   return CFD_OK;

@@ -12,9 +12,15 @@ extern "C" int cfd_debug_stop_stage(cfd_handle c, int stage) {
 extern "C" int cfd_debug_forward_operands(cfd_handle c, int policy) {
   if (!c) return fail(CFD_E_ARG, "null handle");
   if (policy != 0 && policy != 15) return fail(CFD_E_ARG, "cfd_debug_forward_operands: policy %d (0: split pairs, 15: single-fp16 tiles of the long memories)", policy);
-  if (c->run_open) return fail(CFD_E_STATE, "a sampling run is open on this handle");
+  if (c->run.open) return fail(CFD_E_STATE, "a sampling run is open on this handle");
   if (policy != c->fwd_operands) c->wk[0].fwd_mem_valid = false;   // the work lists carry XA_F16 and k16 / v16 are made per call: nothing of the last forward is reused
   c->fwd_operands = policy;
+  return CFD_OK;
+}
+
+extern "C" int cfd_debug_live_buffers(long long* count, long long* bytes) {
+  if (!count || !bytes) return fail(CFD_E_ARG, "null argument");
+  *count = g_dbuf_live; *bytes = g_dbuf_live_bytes;
   return CFD_OK;
 }
 

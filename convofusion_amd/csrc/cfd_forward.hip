@@ -403,10 +403,10 @@ int enqueue_rows(Ctx* c, hipStream_t st) {
 #endif
       Bracket br(c, CFD_PROF_XATTN, st);
       if (p.att_fused) a.att = c->w->xa_att_desc.as<XaAtt>() + l;
-      if (c->acen_on && !p.att_fused) {   // the attention-concentration census of a sampling run (the ATT instance counts nothing)
-        a.census = c->acen.as<unsigned>() + (size_t)l * XA_CEN_SLOTS * XA_CEN_STRIDE;
-        a.census_tau = c->acen_tau;
-        c->acen_hits += 1;
+      if (c->acen.on && !p.att_fused) {   // the attention-concentration census of a sampling run (the ATT instance counts nothing)
+        a.census = c->acen.buf.as<unsigned>() + (size_t)l * XA_CEN_SLOTS * XA_CEN_STRIDE;
+        a.census_tau = c->acen.tau;
+        c->acen.hits += 1;
       }
       c->xa_inst = p.att_fused ? 1 : p.xa_f16 ? 2 : 0;
       auto launch_xa = [&](int nwg, const XAttnArgs& xa) {
@@ -577,7 +577,7 @@ extern "C" int cfd_forward(cfd_handle c, const float* sample, int Be, int L, con
   c->hint_now = c->hint_same_mem;   // the promise covers THIS call only, however it ends
   c->hint_same_mem = false;
   if (!sample || !timesteps || !mem || !out) return fail(CFD_E_ARG, "null argument");
-  if (c->run_open) return fail(CFD_E_STATE, "a sampling run is open on this handle");
+  if (c->run.open) return fail(CFD_E_STATE, "a sampling run is open on this handle");
   HIPCHK(hipSetDevice(c->cfg.device));
   CHK(settle_deferred_census(c));
   if (n_t != 1 && n_t != Be) return fail(CFD_E_ARG, "n_t must be 1 or Be");
@@ -645,9 +645,9 @@ extern "C" int cfd_profile_forward(cfd_handle c, float ms[CFD_PROF_NCLASS], int 
   if (!c || !ms || !launches) return fail(CFD_E_ARG, "null argument");
   if (c->w->pb.Be == 0) return fail(CFD_E_STATE, "no problem configured (call cfd_forward or cfd_sample_begin first)");
   HIPCHK(hipSetDevice(c->cfg.device));
-  if (c->run_open && c->run_pos >= c->run_iters)
+  if (c->run.open && c->run.pos >= c->run.iters)
     return fail(CFD_E_STATE, "sampling run is complete; profile before the last iteration");
-  hipStream_t st = c->run_open ? c->run_stream : nullptr;
+  hipStream_t st = c->run.open ? c->run.stream : nullptr;
   HIPCHK(hipStreamSynchronize(st));
   for (int k = 0; k < CFD_PROF_NCLASS; ++k) { c->prof_ms[k] = 0.f; c->prof_n[k] = 0; }
   c->prof = true;
@@ -680,8 +680,6 @@ extern "C" int cfd_test_gemm(cfd_handle c, const float* X, const float* Y, float
   hipError_t err = launch_gemm<MODE_PLAIN, EpiF32>(a, e, 1, 1, st, tile_cfg);
   if (err != hipSuccess) return fail(CFD_E_HIP, "gemm launch failed: %s", hipGetErrorString(err));
   HIPCHK(hipStreamSynchronize(st));
-  xs.release();
-  ys.release();
   return CFD_OK;
 }
 
@@ -706,36 +704,33 @@ extern "C" int cfd_test_gemm_epi(cfd_handle c, cfd_test_epi_args* t, void* strea
   if (fold && (!t->gamma || !t->beta || !t->ln_stat)) return fail(CFD_E_ARG, "the fold needs gamma, beta and ln_stat");
   HIPCHK(hipSetDevice(c->cfg.device));
   hipStream_t st = (hipStream_t)stream;
-  struct Tmp {
-    DBuf xs, ys, wf, cd;
-    ~Tmp() { xs.release(); ys.release(); wf.release(); cd.release(); }
-  } tmp;
+  DBuf xs, ys, wf, cd;
   if (fold) {   // the product's weight side: W' = W diag(gamma) as split pairs, c = W' 1, d = W beta
-    CHK(tmp.cd.ensure((size_t)2 * I * 4));
-    CHK(ln_fold_weight(c, t->X, I, K, t->gamma, t->beta, tmp.wf, tmp.xs, tmp.cd.as<float>(), tmp.cd.as<float>() + I));
+    CHK(cd.ensure((size_t)2 * I * 4));
+    CHK(ln_fold_weight(c, t->X, I, K, t->gamma, t->beta, wf, xs, cd.as<float>(), cd.as<float>() + I));
     HIPCHK(hipStreamSynchronize(nullptr));
   } else {
-    CHK(tmp.xs.ensure((size_t)I * K * 4));
-    CHK(enqueue_to_split(c, CFD_PROF_OTHER, st, t->X, tmp.xs.as<char>(), (long long)I, K, (long long)K, (long long)K * 4, nullptr));
+    CHK(xs.ensure((size_t)I * K * 4));
+    CHK(enqueue_to_split(c, CFD_PROF_OTHER, st, t->X, xs.as<char>(), (long long)I, K, (long long)K, (long long)K * 4, nullptr));
   }
   const char* y = reinterpret_cast<const char*>(t->y_sp);
   if (!y) {
-    CHK(tmp.ys.ensure((size_t)J * K * 4));
-    CHK(enqueue_to_split(c, CFD_PROF_OTHER, st, t->Y, tmp.ys.as<char>(), (long long)J, K, (long long)K, (long long)K * 4, nullptr));
-    y = tmp.ys.as<char>();
+    CHK(ys.ensure((size_t)J * K * 4));
+    CHK(enqueue_to_split(c, CFD_PROF_OTHER, st, t->Y, ys.as<char>(), (long long)J, K, (long long)K, (long long)K * 4, nullptr));
+    y = ys.as<char>();
   }
   GemmArgs a = gemm_args();
   const int I0 = qkvt ? 2 * CFD_D : I;
-  gemm_x(a, 0, tmp.xs.as<char>(), I0, K, (long long)K * 4);
+  gemm_x(a, 0, xs.as<char>(), I0, K, (long long)K * 4);
   if (qkvt) {
     a.nslot = 2;
-    gemm_x(a, 1, tmp.xs.as<char>() + (size_t)I0 * K * 4, CFD_D, K, (long long)K * 4);
+    gemm_x(a, 1, xs.as<char>() + (size_t)I0 * K * 4, CFD_D, K, (long long)K * 4);
   }
   gemm_y(a, y, J, (long long)K * 4);
-  const float* cd = tmp.cd.as<float>();
+  const float* cdp = cd.as<float>();
   auto fold_of = [&](const auto& e) {   // (q | k | v^T: group 1 is the value projection, rows I0.. of the weight)
     const int g1 = qkvt ? I0 : 0;
-    return epi_ln(e, t->ln_stat, cd, cd + I, cd + g1, cd + I + g1, t->ln_eps);
+    return epi_ln(e, t->ln_stat, cdp, cdp + I, cdp + g1, cdp + I + g1, t->ln_eps);
   };
   auto cfg_used = [](int cfg) { return cfg == 1 || cfg == 6 || cfg == 19 || cfg == 20 || cfg == 24 ? cfg : 3; };   // (launch_gemm's default: 3)
   auto plain = [&](const auto& e) -> hipError_t {
@@ -834,7 +829,6 @@ extern "C" int cfd_bench_gemm(cfd_handle c, int I, int J, int K, int tile_cfg, i
   float ms = 0.f;
   HIPCHK(hipEventElapsedTime(&ms, c->pev[0], c->pev[1]));
   *ms_out = ms / iters;
-  xf.release(); yf.release(); xs.release(); ys.release(); out.release();
   return CFD_OK;
 }
 

@@ -16,46 +16,14 @@
 
 #include "../../include/cfdenoise.h"
 #include "../../include/cfdenoise_dev.h"
+#include "owned.hpp"
 #include "gemm_sp.hpp"
 #include "rows.hpp"
 #include "attn_fused.hpp"
 #include "xattn_fused.hpp"
 #include "rowtile.hpp"
 
-
-int fail(int code, const char* fmt, ...);      // cfd_core.hip: formats the thread's last-error text (cfd_last_error) and returns `code`
-#define HIPCHK(expr)                                                                               \
-  do {                                                                                             \
-    hipError_t _e = (expr);                                                                        \
-    if (_e != hipSuccess) return fail(CFD_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-  } while (0)
-#define CHK(expr)            \
-  do {                       \
-    int _r = (expr);         \
-    if (_r != CFD_OK) return _r; \
-  } while (0)
-
 static const char* MEM_NAMES[CFD_NMEM] = {"spkemb", "alsn", "tlsn", "apb", "lsnemb"};
-
-struct DBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-  int ensure(size_t n) {
-    if (n <= bytes) return CFD_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    bytes = 0;
-    HIPCHK(hipMalloc(&p, n));
-    bytes = n;
-    return CFD_OK;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    bytes = 0;
-  }
-  template <class T> T* as() const { return reinterpret_cast<T*>(p); }
-};
 
 struct LayerW {
   DBuf wqkv_sp, bqk, wo_sp, bo2, wtb1_sp, wtb2_sp, w1_sp, w2_sp, cross_bias;
@@ -153,13 +121,8 @@ struct WegState {
   struct Graph {
     std::vector<long long> key;
     int uses = 0;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    void reset(const std::vector<long long>& new_key = {}) {   // drop the graph; start counting the uses of `new_key`
-      if (exec) (void)hipGraphExecDestroy(exec);
-      if (graph) (void)hipGraphDestroy(graph);
-      *this = Graph{new_key};
-    }
+    GraphExec gx;
+    void reset(const std::vector<long long>& new_key = {}) { *this = Graph{new_key}; }   // drop the graph; start counting the uses of `new_key`
   };
   Graph graph[2];               // [0] full evaluation, [1] memory-side results reused
   // Row-tile evaluation (weg_rt.hpp): the product path for small problems
@@ -171,10 +134,6 @@ struct WegState {
   std::vector<int32_t> tok_host;
   std::vector<long long> sig;   // timestep, shapes, memory pointers and arena of the last evaluation (reuse_memory_side)
   int launches = 0;
-  void release() {              // cfd_destroy
-    for (Graph& g : graph) g.reset();
-    ws.release(); tok.release(); io.release(); rt_ws.release();
-  }
   void invalidate() { sig.clear(); }   // cfd_load_tensor: the next evaluation reuses no memory-side result
 };
 
@@ -213,24 +172,15 @@ struct Work {
   const float* now_ss = nullptr;
   const float* now_kb[CFD_NMEM] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   const float* now_vb[CFD_NMEM] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  void release() {
-    DBuf* all[] = {&x, &h_sp, &qkv_sp, &vts_sp, &ssc, &sp_sp, &o_sp, &u_sp, &sc, &p_sp, &eps, &sample_sp, &temb_tab, &h1_tab, &ss_tab, &trows, &iota,
-                   &long_rows, &short_rows, &zero_mask, &ln_stat, &b_tab, &b_sp, &bsq, &zeros512, &xa_wgs, &xa_segs, &xa_stamps, &xa0_wgs_a, &xa0_segs_a, &xa0_wgs_b, &xa0_segs_b, &xa_dedup, &xa_one_va, &xa_att_raw, &xa_att_mc, &xa_att_fin, &xa_att_desc, &d_step, &rt_vt, &rt_cur};
-    for (DBuf* b : all) b->release();
-    for (int j = 0; j < CFD_NMEM; ++j) {
-      n_sp[j].release(); kall_sp[j].release(); cb[j].release(); vt_all[j].release(); ca[j].release(); asq[j].release(); kbtab[j].release();
-      vbtab[j].release(); rt_cbt[j].release(); k16[j].release(); v16[j].release();
-    }
-  }
 };
 
 // The kind of the open sampling run: which instances of begin_step_kernel / inpaint_now_kernel / cfg_step_kernel it launches
 // (cfd_sample.hip: with_begin_args, enqueue_loop_iteration).  sample_begin starts every run from RunMode{}: a new field needs no reset;
 // it is filled from its BeginExt field in init_latents_and_kind (the comment on BeginExt lists every place a new run kind touches).
 struct RunMode {
-  // Weighted run (cfd_sample_begin_weighted): the guidance weights come from Ctx::wtab instead of cfd_sample_args::guidance_weight.
+  // Weighted run (cfd_sample_begin_weighted): the guidance weights come from SampleRun::wtab instead of cfd_sample_args::guidance_weight.
   bool weighted = false;
-  // Edit run (cfd_sample_begin_edit): the run starts at iteration k0 of the full table (d_step[0] starts there; run_pos and run_iters
+  // Edit run (cfd_sample_begin_edit): the run starts at iteration k0 of the full table (d_step[0] starts there; SampleRun::pos and iters
   // count executed iterations).  edit: the edit instances of begin_step_kernel / inpaint_now_kernel overwrite the tokens of ekeep
   // [B][L] with coef[i].sa * esrc + coef[i].sb * enoise.
   int k0 = 0;
@@ -249,8 +199,45 @@ struct RunMode {
   bool tie = false;
   bool tie_final = false;
   // Replay of a recorded DDPM noise space (cfd_sample_begin_replay): the anchored instances over the caller's trajectory (anchor,
-  // anchor_ring, anchor_n as above), the run's step noise = the caller's noise ring (sargs.step_noise), and a start at iteration k0.
+  // anchor_ring, anchor_n as above), the run's step noise = the caller's noise ring (args.step_noise), and a start at iteration k0.
   bool replay = false;
+};
+
+// The open sampling run (cfd_sample.hip): what sample_begin sets up, the captured iteration replays on and cfd_sample_read / _end
+// settle.  While no run is open the level-batch calls (cfd_ddpm_invert, cfd_sample_parallel) use args, coef, wtab and latents as
+// their scratch; their own buffers (lv_*, pic_*) are the handle's.
+struct SampleRun {
+  bool open = false;
+  int pos = 0, iters = 0;            // executed iterations; loop iterations of the open run (= length of the timestep table)
+  hipStream_t stream = nullptr;
+  bool counts = false;               // the captured iteration contains launches that count into the saturation census (per-step projections)
+  cfd_sample_args args;              // the run's copy of the caller's arguments: G = the evaluated chunks, no host pointers
+  GraphExec graph;                   // the captured iteration
+  DBuf latents, coef, inoise;
+  DBuf hist;   // DPM-Solver++ runs (scheduler kind 2): [B][L][128] the previous iteration's x0 (CfgStepArgs::hist)
+  // Internal chunk order of a sampling run: chunk k of the caller's chunk-major batch lives at rows
+  // chunk_pos[k] * B.  Chunks whose rows all use ONE shared copy of the largest memory (the unconditional audio
+  // memory: 5 of the 7 guidance chunks, not adjacent in the reference's order) are moved next to each other, so
+  // their attention against it is one un-batched product instead of one per contiguous run.  Every per-row result
+  // is unchanged (rows are independent); the guidance combine reads chunk k at its position.
+  int chunk_pos[8];
+  DBuf perm_map[CFD_NMEM];
+  // The open run's mode and the buffers its instances read.  Weighted run: wtab [iterations][B][8] (indexed by the caller's chunk order);
+  // wpos[k] is the row position of chunk k, or chunk 0's for a chunk the run does not evaluate.  esrc / enoise [B][L][128]: an edit's source
+  // latents and the run's initial noise; ekeep [B][L]: the kept tokens of an edit, tied or anchored run; etie [B][L]: the tie table.
+  RunMode mode;
+  int wpos[8];
+  DBuf wtab, esrc, enoise, ekeep, etie;
+};
+
+// Attention-concentration census of the last sampling run (cfd_sample_args::census_tau, cfd_sample_census; xattn_fused.hpp, XAttnArgs::census):
+// buf is u32 [nl][XA_CEN_SLOTS][XA_CEN_STRIDE] per run, zeroed by cfd_sample_begin behind the warm-up iteration.  on: only while cfd_sample_begin
+// enqueues the run's iteration (the captured graph keeps the pointers); hits: fused cross-attention launches that got a census slot.
+struct AttnCensus {
+  DBuf buf;
+  bool on = false, valid = false, measured = false;
+  int hits = 0;
+  float tau = 0.f;
 };
 
 struct cfd_handle_s {
@@ -278,14 +265,7 @@ struct cfd_handle_s {
   // sample / latents handed to an entry point.  Zeroed at the entry of the calls that count, read at their end.
   DBuf sat;
   bool memside_in_forward = false;   // the last enqueue_denoise ran memory-side projections itself (not hoisted): census still open
-  bool run_counts = false;           // the open run's captured iteration contains launches that count into the census (per-step projections)
-  // attention-concentration census of the last sampling run (cfd_sample_args::census_tau, cfd_sample_census; xattn_fused.hpp, XAttnArgs::census):
-  // u32 [nl][XA_CEN_SLOTS][XA_CEN_STRIDE] per run, zeroed by cfd_sample_begin behind the warm-up iteration.  acen_on: only while cfd_sample_begin enqueues the run's
-  // iteration (the captured graph keeps the pointers); acen_hits: fused cross-attention launches that got a census slot.
-  DBuf acen;
-  bool acen_on = false, acen_valid = false, acen_measured = false;
-  int acen_hits = 0;
-  float acen_tau = 0.f;
+  AttnCensus acen;
   unsigned int* sat_mem() const { return sat.as<unsigned int>() + CFD_SAT_MEM; }
   unsigned int* sat_in() const { return sat.as<unsigned int>() + CFD_SAT_IN; }
   bool want_f16 = false;        // cfd_sample_begin -> setup_problem: the run asks for single-fp16 tiles (non-zero operand policy; false everywhere else)
@@ -324,32 +304,18 @@ struct cfd_handle_s {
   float prof_ms[CFD_PROF_NCLASS];
   int prof_n[CFD_PROF_NCLASS];
   int stop_stage = 0;  // test hook: leave enqueue_denoise after this tap point (0 = run everything)
-  int run_iters = 0;                 // loop iterations of the open run (= length of the timestep table)
   hipStream_t own_stream = nullptr;  // non-blocking stream the captured loop iteration replays on
-  // sampling run
-  bool run_open = false;
-  cfd_sample_args sargs;
-  hipStream_t run_stream = nullptr;
-  hipGraph_t graph = nullptr;
-  hipGraphExec_t gexec = nullptr;
-  DBuf latents, coef, inoise, mem_own[CFD_NMEM];
-  DBuf hist;   // DPM-Solver++ runs (scheduler kind 2): [B][L][128] the previous iteration's x0 (CfgStepArgs::hist)
-  // Internal chunk order of a sampling run: chunk k of the caller's chunk-major batch lives at rows
-  // chunk_pos[k] * B.  Chunks whose rows all use ONE shared copy of the largest memory (the unconditional audio
-  // memory: 5 of the 7 guidance chunks, not adjacent in the reference's order) are moved next to each other, so
-  // their attention against it is one un-batched product instead of one per contiguous run.  Every per-row result
-  // is unchanged (rows are independent); the guidance combine reads chunk k at its position.
-  int chunk_pos[8];
-  DBuf perm_map[CFD_NMEM];
-  // The open run's mode and the buffers its instances read.  Weighted run: wtab [iterations][B][8] (indexed by the caller's chunk order);
-  // wpos[k] is the row position of chunk k, or chunk 0's for a chunk the run does not evaluate.  esrc / enoise [B][L][128]: an edit's source
-  // latents and the run's initial noise; ekeep [B][L]: the kept tokens of an edit, tied or anchored run; etie [B][L]: the tie table.
-  RunMode run;
-  int wpos[8];
-  DBuf wtab, esrc, enoise, ekeep, etie;
+  SampleRun run;                     // the sampling run (one at a time)
   DBuf lv_map[CFD_NMEM], lv_mask[CFD_NMEM];   // level batches: the level row maps and the key-padding masks once per level
   DBuf pic_s, pic_part, pic_err;              // cfd_sample_parallel: the levels' steps [J][B][L][128], the error partials and sums
-  int run_pos = 0;
+  // (cfd_destroy has waited for the device.)  The graphs go first, then the stream they replay on and the events; every buffer frees itself.
+  ~cfd_handle_s() {
+    run.graph.reset();
+    for (WegState::Graph& g : weg.graph) g.reset();
+    if (weg_ev) (void)hipEventDestroy(weg_ev);
+    if (own_stream) (void)hipStreamDestroy(own_stream);
+    for (hipEvent_t e : pev) if (e) (void)hipEventDestroy(e);
+  }
 };
 typedef cfd_handle_s Ctx;
 

@@ -139,42 +139,42 @@ struct BeginInst {
 
 // What every instance's arguments start with (preseq / inoise / pl are the default instance's alone: default_begin_args)
 static BeginArgs base_begin_args(Ctx* c) {
-  const cfd_sample_args& s = c->sargs;
-  return BeginArgs{c->latents.as<float>(), c->w->sample_sp.as<char>(), s.B, s.L, s.G, nullptr, nullptr, 0, c->coef.as<StepCoef>(),
+  const cfd_sample_args& s = c->run.args;
+  return BeginArgs{c->run.latents.as<float>(), c->w->sample_sp.as<char>(), s.B, s.L, s.G, nullptr, nullptr, 0, c->run.coef.as<StepCoef>(),
                    c->w->d_step.as<int>()};
 }
 
 static BeginArgs default_begin_args(Ctx* c) {
   BeginArgs ba = base_begin_args(c);
-  ba.preseq = c->sargs.preseq;
-  ba.inoise = c->inoise.as<float>();
-  ba.pl = c->sargs.preseq_len;
+  ba.preseq = c->run.args.preseq;
+  ba.inoise = c->run.inoise.as<float>();
+  ba.pl = c->run.args.preseq_len;
   return ba;
 }
 
 static BeginArgsE edit_begin_args(Ctx* c) {
   BeginArgsE be;
   static_cast<BeginArgs&>(be) = base_begin_args(c);
-  be.keep = c->ekeep.as<uint8_t>();
-  be.src = c->esrc.as<float>();
-  be.eps = c->enoise.as<float>();
+  be.keep = c->run.ekeep.as<uint8_t>();
+  be.src = c->run.esrc.as<float>();
+  be.eps = c->run.enoise.as<float>();
   return be;
 }
 
 static BeginArgsT tied_begin_args(Ctx* c) {
   BeginArgsT bt;
   static_cast<BeginArgsE&>(bt) = edit_begin_args(c);
-  bt.tie = c->etie.as<int32_t>();
+  bt.tie = c->run.etie.as<int32_t>();
   return bt;
 }
 
 static BeginArgsA anchor_begin_args(Ctx* c) {
   BeginArgsA ba;
   static_cast<BeginArgs&>(ba) = base_begin_args(c);
-  ba.keep = c->ekeep.as<uint8_t>();
-  ba.ring = c->run.anchor_ring;
-  ba.slot = (long long)c->sargs.B * c->sargs.L * CFD_LAT;
-  ba.n = c->run.anchor_n;
+  ba.keep = c->run.ekeep.as<uint8_t>();
+  ba.ring = c->run.mode.anchor_ring;
+  ba.slot = (long long)c->run.args.B * c->run.args.L * CFD_LAT;
+  ba.n = c->run.mode.anchor_n;
   return ba;
 }
 
@@ -182,15 +182,15 @@ static BeginArgsA anchor_begin_args(Ctx* c) {
 // type.  The one place that maps RunMode to an instance of begin_step_kernel / inpaint_now_kernel.
 template <class F>
 static int with_begin_args(Ctx* c, F&& f) {
-  if (c->run.tie) return f(tied_begin_args(c));      // the tied and the kept tokens
-  if (c->run.edit) return f(edit_begin_args(c));     // the kept tokens, re-noised from the source
-  if (c->run.anchor) return f(anchor_begin_args(c)); // the kept tokens, from the trajectory
+  if (c->run.mode.tie) return f(tied_begin_args(c));      // the tied and the kept tokens
+  if (c->run.mode.edit) return f(edit_begin_args(c));     // the kept tokens, re-noised from the source
+  if (c->run.mode.anchor) return f(anchor_begin_args(c)); // the kept tokens, from the trajectory
   return f(default_begin_args(c));                   // the first preseq_len tokens, if the run has a preseq
 }
 
 static int enqueue_loop_iteration(Ctx* c, hipStream_t st) {
-  const cfd_sample_args& s = c->sargs;
-  const RunMode& m = c->run;
+  const cfd_sample_args& s = c->run.args;
+  const RunMode& m = c->run.mode;
   const long long n8 = (long long)s.B * s.L * (CFD_LAT / 8);
   CHK(with_begin_args(c, [&](auto a) {
     using I = BeginInst<decltype(a)>;
@@ -200,15 +200,15 @@ static int enqueue_loop_iteration(Ctx* c, hipStream_t st) {
   CHK(enqueue_denoise(c, st));
   CfgStepArgsW cw;
   memset(&cw, 0, sizeof(cw));
-  cw.eps = c->w->eps.as<float>(); cw.latents = c->latents.as<float>(); cw.B = s.B; cw.L = s.L; cw.G = s.G;
-  for (int k = 0; k < 8; ++k) { cw.w[k] = s.guidance_weight[k]; cw.pos[k] = c->chunk_pos[k]; }
-  cw.kind = s.scheduler; cw.clip = s.clip_sample; cw.hist = c->hist.as<float>(); cw.coef = c->coef.as<StepCoef>(); cw.d_step = c->w->d_step.as<int>();
+  cw.eps = c->w->eps.as<float>(); cw.latents = c->run.latents.as<float>(); cw.B = s.B; cw.L = s.L; cw.G = s.G;
+  for (int k = 0; k < 8; ++k) { cw.w[k] = s.guidance_weight[k]; cw.pos[k] = c->run.chunk_pos[k]; }
+  cw.kind = s.scheduler; cw.clip = s.clip_sample; cw.hist = c->run.hist.as<float>(); cw.coef = c->run.coef.as<StepCoef>(); cw.d_step = c->w->d_step.as<int>();
   cw.noise = s.step_noise; cw.seed = s.seed; cw.utt0 = s.first_utterance;
   cw.advance = c->w->d_step.as<int>();   // the last workgroup of cfg_step_kernel advances the loop index
   if (m.weighted) {   // the caller's 7 chunks, weights from the run's table (those of a chunk it does not evaluate are all 0)
     cw.G = 7;
-    for (int k = 0; k < 8; ++k) cw.pos[k] = c->wpos[k];
-    cw.wtab = c->wtab.as<float>();
+    for (int k = 0; k < 8; ++k) cw.pos[k] = c->run.wpos[k];
+    cw.wtab = c->run.wtab.as<float>();
   }
   const long long n4 = (long long)s.B * s.L * CFD_LAT / 4;
   const dim3 grid((unsigned)std::min<long long>((n4 + 255) / 256, 256)), block(256);
@@ -251,10 +251,10 @@ static int check_scheduler_tables(const cfd_sample_args& s, const char* who) {
   return CFD_OK;
 }
 
-// skip_zero_weight_chunks: the batch is chunk-major, so dropping trailing zero-weight chunks = using the first G' * B rows (c->sargs.G)
+// skip_zero_weight_chunks: the batch is chunk-major, so dropping trailing zero-weight chunks = using the first G' * B rows (c->run.args.G)
 static void trim_zero_weight_chunks(Ctx* c, const cfd_sample_args& s) {
   if (s.skip_zero_weight_chunks)
-    while (c->sargs.G > 1 && s.guidance_weight[c->sargs.G - 1] == 0.0f) c->sargs.G -= 1;
+    while (c->run.args.G > 1 && s.guidance_weight[c->run.args.G - 1] == 0.0f) c->run.args.G -= 1;
 }
 
 // The tables of a run over N iterations, on the stream: the timestep table (the caller's, or (arange(N) * (T // n_inf)).round()[::-1],
@@ -267,8 +267,8 @@ static int upload_run_tables(Ctx* c, const cfd_sample_args& s, int N, int k0, hi
   std::vector<StepCoef> coef(N);
   for (int i = 0; i < N; ++i) ts[i] = s.timesteps ? s.timesteps[i] : (N - 1 - i) * ratio + (s.scheduler == 1 ? s.steps_offset : 0);
   CHK(step_coefficients(s.scheduler, s.alphas_cumprod, T, n_inf, ts.data(), N, s.eta, s.set_alpha_to_one, coef.data(), k0));
-  CHK(c->coef.ensure((size_t)N * sizeof(StepCoef)));
-  HIPCHK(hipMemcpyAsync(c->coef.p, coef.data(), (size_t)N * sizeof(StepCoef), hipMemcpyHostToDevice, st));
+  CHK(c->run.coef.ensure((size_t)N * sizeof(StepCoef)));
+  HIPCHK(hipMemcpyAsync(c->run.coef.p, coef.data(), (size_t)N * sizeof(StepCoef), hipMemcpyHostToDevice, st));
   HIPCHK(hipMemsetAsync(c->w->d_step.p, 0, 16, st));
   CHK(sat_begin(c, st));
   CHK(build_time_tables(c, ts.data(), N, st));   // (a run over the same table finds them built)
@@ -281,10 +281,10 @@ static int upload_run_tables(Ctx* c, const cfd_sample_args& s, int N, int k0, hi
 // Chunks of a weighted run (cfd_sample_begin_weighted): uploads the weight table, decides which chunks are evaluated (prune: every chunk
 // k >= 1 whose column is 0 throughout is not, except the last one when the run keeps its attention maps) and compacts the memories' row
 // maps to the evaluated chunks, in the caller's order (a memory without a map gets the identity map first).  keep_idx[k]: the compacted
-// index of chunk k, or -1.  c->sargs.G becomes the number of evaluated chunks.
+// index of chunk k, or -1.  c->run.args.G becomes the number of evaluated chunks.
 static int weighted_chunks(Ctx* c, const float* wtab, int prune, int N, bool keep_last, cfd_memory mem_in[CFD_NMEM], int keep_idx[8],
                            hipStream_t st) {
-  const cfd_sample_args& s = c->sargs;
+  const cfd_sample_args& s = c->run.args;
   const int B = s.B, G = s.G;
   const size_t n = (size_t)N * B * 8;
   for (size_t e = 0; e < n; ++e)
@@ -297,10 +297,10 @@ static int weighted_chunks(Ctx* c, const float* wtab, int prune, int N, bool kee
   }
   int ge = 0;
   for (int k = 0; k < 8; ++k) keep_idx[k] = (k < G && keep[k]) ? ge++ : -1;
-  CHK(c->wtab.ensure(n * sizeof(float)));
-  HIPCHK(hipMemcpyAsync(c->wtab.p, wtab, n * sizeof(float), hipMemcpyHostToDevice, st));
+  CHK(c->run.wtab.ensure(n * sizeof(float)));
+  HIPCHK(hipMemcpyAsync(c->run.wtab.p, wtab, n * sizeof(float), hipMemcpyHostToDevice, st));
   HIPCHK(hipStreamSynchronize(st));   // (the caller's host table is not kept beyond the call)
-  c->sargs.G = ge;
+  c->run.args.G = ge;
   if (ge == G) return CFD_OK;
   const int Be = G * B, Bc = ge * B;
   std::vector<int> hm, cm(Bc);
@@ -309,9 +309,9 @@ static int weighted_chunks(Ctx* c, const float* wtab, int prune, int N, bool kee
     for (int k = 0; k < G; ++k)
       if (keep_idx[k] >= 0)
         for (int u = 0; u < B; ++u) cm[(size_t)keep_idx[k] * B + u] = hm[(size_t)k * B + u];
-    CHK(c->perm_map[j].ensure((size_t)Be * 4));
-    HIPCHK(hipMemcpy(c->perm_map[j].p, cm.data(), (size_t)Bc * 4, hipMemcpyHostToDevice));
-    mem_in[j].row_map = c->perm_map[j].as<int32_t>();
+    CHK(c->run.perm_map[j].ensure((size_t)Be * 4));
+    HIPCHK(hipMemcpy(c->run.perm_map[j].p, cm.data(), (size_t)Bc * 4, hipMemcpyHostToDevice));
+    mem_in[j].row_map = c->run.perm_map[j].as<int32_t>();
   }
   return CFD_OK;
 }
@@ -319,9 +319,9 @@ static int weighted_chunks(Ctx* c, const float* wtab, int prune, int N, bool kee
 // The run's keep mask on the device: the validated host copy (the caller waits for the stream before hkeep goes out of scope), or,
 // with an empty hkeep (no mask given), no kept token.
 static int upload_keep_mask(Ctx* c, const std::vector<uint8_t>& hkeep, size_t n, hipStream_t st) {
-  CHK(c->ekeep.ensure(n));
-  if (!hkeep.empty()) HIPCHK(hipMemcpyAsync(c->ekeep.p, hkeep.data(), n, hipMemcpyHostToDevice, st));
-  else HIPCHK(hipMemsetAsync(c->ekeep.p, 0, n, st));
+  CHK(c->run.ekeep.ensure(n));
+  if (!hkeep.empty()) HIPCHK(hipMemcpyAsync(c->run.ekeep.p, hkeep.data(), n, hipMemcpyHostToDevice, st));
+  else HIPCHK(hipMemsetAsync(c->run.ekeep.p, 0, n, st));
   return CFD_OK;
 }
 
@@ -347,7 +347,7 @@ struct BeginExt {
 // What the stages of sample_begin hand to each other
 struct BeginState {
   Ctx* c;
-  const cfd_sample_args& s;   // the caller's arguments (c->sargs: the run's copy, G = the evaluated chunks, no host pointers)
+  const cfd_sample_args& s;   // the caller's arguments (c->run.args: the run's copy, G = the evaluated chunks, no host pointers)
   const BeginExt& x;
   hipStream_t st;
   int N;                      // loop iterations (the length of scheduler.timesteps)
@@ -434,17 +434,17 @@ static int fetch_tie_table(BeginState& r) {
 static int select_chunks(BeginState& r) {
   Ctx* c = r.c;
   const cfd_sample_args& s = r.s;
-  c->sargs = s;
-  c->run_stream = r.st;
+  c->run.args = s;
+  c->run.stream = r.st;
   c->setup_launches = 0;
   for (int j = 0; j < CFD_NMEM; ++j) r.n_ring += s.att_ring[j] != nullptr;
   if (r.n_ring != 0 && r.n_ring != CFD_NMEM) return fail(CFD_E_ARG, "att_ring: give all five buffers or none");
   if (r.n_ring && s.skip_zero_weight_chunks && s.G > 1 && s.guidance_weight[s.G - 1] == 0.0f)
     return fail(CFD_E_ARG, "att_ring keeps the maps of the LAST guidance chunk: it must be evaluated (skip_zero_weight_chunks = 0)");
   trim_zero_weight_chunks(c, s);
-  c->sargs.timesteps = nullptr;   // (host pointer: not kept beyond this call)
-  c->run_iters = r.N;
-  for (int k = 0; k < 8; ++k) c->chunk_pos[k] = k;
+  c->run.args.timesteps = nullptr;   // (host pointer: not kept beyond this call)
+  c->run.iters = r.N;
+  for (int k = 0; k < 8; ++k) c->run.chunk_pos[k] = k;
   for (int j = 0; j < CFD_NMEM; ++j) r.mem_in[j] = s.mem[j];
   if (r.x.weights) CHK(weighted_chunks(c, r.x.weights, r.x.prune, r.N, r.n_ring != 0, r.mem_in, r.keep_idx, r.st));
   return CFD_OK;
@@ -453,7 +453,7 @@ static int select_chunks(BeginState& r) {
 // Chunk permutation (see chunk_pos): group the chunks that use one shared copy of the largest memory
 static int permute_chunks(BeginState& r) {
   Ctx* c = r.c;
-  const int G = c->sargs.G, B = r.s.B, Be = G * B;
+  const int G = c->run.args.G, B = r.s.B, Be = G * B;
   bool all_maps = c->permute && G > 2;
   int jb = 0;
   for (int j = 0; j < CFD_NMEM; ++j) {
@@ -481,15 +481,15 @@ static int permute_chunks(BeginState& r) {
   bool ident = true;
   for (int pnum = 0; pnum < G; ++pnum) ident = ident && order[pnum] == pnum;
   if (ident) return CFD_OK;
-  for (int pnum = 0; pnum < G; ++pnum) c->chunk_pos[order[pnum]] = pnum;
+  for (int pnum = 0; pnum < G; ++pnum) c->run.chunk_pos[order[pnum]] = pnum;
   std::vector<int> pm(Be);
   for (int j = 0; j < CFD_NMEM; ++j) {
     CHK(host_row_map(r.mem_in[j], Be, MEM_NAMES[j], hm));
     for (int pnum = 0; pnum < G; ++pnum)
       for (int u = 0; u < B; ++u) pm[(size_t)pnum * B + u] = hm[(size_t)order[pnum] * B + u];
-    CHK(c->perm_map[j].ensure((size_t)Be * 4));
-    HIPCHK(hipMemcpy(c->perm_map[j].p, pm.data(), (size_t)Be * 4, hipMemcpyHostToDevice));
-    r.mem_in[j].row_map = c->perm_map[j].as<int32_t>();
+    CHK(c->run.perm_map[j].ensure((size_t)Be * 4));
+    HIPCHK(hipMemcpy(c->run.perm_map[j].p, pm.data(), (size_t)Be * 4, hipMemcpyHostToDevice));
+    r.mem_in[j].row_map = c->run.perm_map[j].as<int32_t>();
   }
   return CFD_OK;
 }
@@ -501,10 +501,10 @@ static int setup_run_problem(BeginState& r) {
   Ctx* c = r.c;
   const cfd_sample_args& s = r.s;
   c->want_f16 = !r.n_ring && !s.dynamic_memory_mask && (c->xa_operands >= 0 ? c->xa_operands : (s.operand_policy & 15)) != 0;
-  const int r_setup = setup_problem(c, c->sargs.G * s.B, s.L, r.mem_in, nullptr, 0, r.N);
+  const int r_setup = setup_problem(c, c->run.args.G * s.B, s.L, r.mem_in, nullptr, 0, r.N);
   c->want_f16 = false;
   CHK(r_setup);
-  if (c->share0 && c->sargs.G > 1) c->w->pb.share_B = s.B;   // begin_step_kernel writes G identical copies of the B rows
+  if (c->share0 && c->run.args.G > 1) c->w->pb.share_B = s.B;   // begin_step_kernel writes G identical copies of the B rows
   return CFD_OK;
 }
 
@@ -524,8 +524,8 @@ static int wire_att_ring(BeginState& r) {
   if ((!pb.rt && !fused_ok) || s.dynamic_memory_mask)
     return fail(CFD_E_SHAPE, "att_ring needs the row-tile path or the fused cross-attention kernel (one timestep per step, no dynamic memory): "
                              "this run has L = %d, %lld token rows; take the maps with one forward per iteration instead", s.L,
-                (long long)c->sargs.G * s.B * s.L);
-  pb.att_b0 = c->chunk_pos[c->sargs.G - 1] * s.B;
+                (long long)c->run.args.G * s.B * s.L);
+  pb.att_b0 = c->run.chunk_pos[c->run.args.G - 1] * s.B;
   pb.att_nb = s.B;
   for (int j = 0; j < CFD_NMEM; ++j) {
     pb.att_slot[j] = (long long)s.B * c->nl * s.L * pb.S[j];
@@ -549,9 +549,9 @@ static int operand_policy_and_census(BeginState& r) {
   Problem& pb = c->w->pb;
   const bool fused_run = !pb.rt && c->fused_xattn && pb.xa_nwg > 0 && !pb.att_fused && !r.s.dynamic_memory_mask;
   if (!fused_run) pb.xa_f16 = false;
-  c->acen_tau = r.s.census_tau > 0.f ? r.s.census_tau : 0.f;
-  c->acen_on = fused_run && c->acen_tau > 0.f;
-  if (c->acen_on) CHK(c->acen.ensure((size_t)c->nl * XA_CEN_SLOTS * XA_CEN_STRIDE * sizeof(unsigned)));
+  c->acen.tau = r.s.census_tau > 0.f ? r.s.census_tau : 0.f;
+  c->acen.on = fused_run && c->acen.tau > 0.f;
+  if (c->acen.on) CHK(c->acen.buf.ensure((size_t)c->nl * XA_CEN_SLOTS * XA_CEN_STRIDE * sizeof(unsigned)));
   return CFD_OK;
 }
 
@@ -559,11 +559,11 @@ static int operand_policy_and_census(BeginState& r) {
 // NULL, a tied run without an edit: no kept token, the source and noise buffers are never read.
 static int edit_buffers(BeginState& r, const float* source) {
   Ctx* c = r.c;
-  CHK(c->enoise.ensure(r.lat_bytes));
-  CHK(c->esrc.ensure(r.lat_bytes));
+  CHK(c->run.enoise.ensure(r.lat_bytes));
+  CHK(c->run.esrc.ensure(r.lat_bytes));
   if (source) {
-    HIPCHK(hipMemcpyAsync(c->enoise.p, c->latents.p, r.lat_bytes, hipMemcpyDeviceToDevice, r.st));
-    HIPCHK(hipMemcpyAsync(c->esrc.p, source, r.lat_bytes, hipMemcpyDeviceToDevice, r.st));
+    HIPCHK(hipMemcpyAsync(c->run.enoise.p, c->run.latents.p, r.lat_bytes, hipMemcpyDeviceToDevice, r.st));
+    HIPCHK(hipMemcpyAsync(c->run.esrc.p, source, r.lat_bytes, hipMemcpyDeviceToDevice, r.st));
   }
   return upload_keep_mask(c, r.hkeep, (size_t)r.s.B * r.s.L, r.st);
 }
@@ -572,9 +572,9 @@ static int edit_buffers(BeginState& r, const float* source) {
 static int anchor_over(BeginState& r, const float* ring, int steps) {
   CHK(upload_keep_mask(r.c, r.hkeep, (size_t)r.s.B * r.s.L, r.st));
   HIPCHK(hipStreamSynchronize(r.st));   // (hkeep goes out of scope)
-  r.c->run.anchor = true;
-  r.c->run.anchor_ring = ring;
-  r.c->run.anchor_n = steps;
+  r.c->run.mode.anchor = true;
+  r.c->run.mode.anchor_ring = ring;
+  r.c->run.mode.anchor_n = steps;
   return CFD_OK;
 }
 
@@ -584,52 +584,52 @@ static int init_latents_and_kind(BeginState& r) {
   const cfd_sample_args& s = r.s;
   const BeginExt& x = r.x;
   hipStream_t st = r.st;
-  CHK(c->latents.ensure(r.lat_bytes));
-  if (s.init_latents) HIPCHK(hipMemcpyAsync(c->latents.p, s.init_latents, r.lat_bytes, hipMemcpyDeviceToDevice, st));
-  else CHK(enqueue_philox_fill(c->latents.as<float>(), s.B, s.L * CFD_LAT, (uint64_t)s.seed, 0u, s.first_utterance, 1u, 1.0f, st));
+  CHK(c->run.latents.ensure(r.lat_bytes));
+  if (s.init_latents) HIPCHK(hipMemcpyAsync(c->run.latents.p, s.init_latents, r.lat_bytes, hipMemcpyDeviceToDevice, st));
+  else CHK(enqueue_philox_fill(c->run.latents.as<float>(), s.B, s.L * CFD_LAT, (uint64_t)s.seed, 0u, s.first_utterance, 1u, 1.0f, st));
   // A tied run.  The scheduler step still steps a tied token (from the copied value and the token's own prediction) and, for DPM-Solver++,
   // keeps its x0 history; neither survives: the token is overwritten with its source at the start of the next iteration and once more
   // after the last (cfd_sample_read), and the history of a token feeds that token's step alone.
   if (x.tie) {   // the run's own copy of the table
-    CHK(c->etie.ensure(r.htie.size() * sizeof(int32_t)));
-    HIPCHK(hipMemcpyAsync(c->etie.p, r.htie.data(), r.htie.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    CHK(c->run.etie.ensure(r.htie.size() * sizeof(int32_t)));
+    HIPCHK(hipMemcpyAsync(c->run.etie.p, r.htie.data(), r.htie.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
     if (!x.edit) CHK(edit_buffers(r, nullptr));   // (hkeep is empty here)
     HIPCHK(hipStreamSynchronize(st));   // (htie goes out of scope)
-    c->run.tie = true;
+    c->run.mode.tie = true;
   }
   if (x.edit) {   // k0 > 0: every token starts at sa_k0 * source + sb_k0 * eps
     CHK(edit_buffers(r, x.edit->source));
     if (r.k0 > 0) {
       const long long n8 = (long long)s.B * s.L * (CFD_LAT / 8);
-      hipLaunchKernelGGL(edit_init_kernel<>, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, st, c->latents.as<float>(), c->esrc.as<float>(),
-                         c->enoise.as<float>(), n8, c->coef.as<StepCoef>(), r.k0);
+      hipLaunchKernelGGL(edit_init_kernel<>, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, st, c->run.latents.as<float>(), c->run.esrc.as<float>(),
+                         c->run.enoise.as<float>(), n8, c->run.coef.as<StepCoef>(), r.k0);
       HIPCHK(hipGetLastError());
     }
     HIPCHK(hipStreamSynchronize(st));   // (hkeep goes out of scope)
-    c->run.edit = true;
+    c->run.mode.edit = true;
   }
   if (x.traj) {   // slot 0 of the trajectory: the initial latents (the source of the inversion)
-    HIPCHK(hipMemcpyAsync(x.traj, c->latents.p, r.lat_bytes, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(x.traj, c->run.latents.p, r.lat_bytes, hipMemcpyDeviceToDevice, st));
     HIPCHK(hipStreamSynchronize(st));
-    c->run.traj = x.traj;
+    c->run.mode.traj = x.traj;
   }
   if (x.anchor) CHK(anchor_over(r, x.anchor->trajectory, x.anchor->steps));
   if (x.replay) {   // the anchored instance over the noise space's trajectory; the opener pointed init_latents / step_noise into the rings
     CHK(anchor_over(r, x.replay->trajectory, x.replay->steps));
-    c->run.replay = true;
+    c->run.mode.replay = true;
   }
-  c->run.k0 = r.k0;   // (0 but for an edit or a replay that starts later)
-  c->run_iters = r.N - r.k0;
+  c->run.mode.k0 = r.k0;   // (0 but for an edit or a replay that starts later)
+  c->run.iters = r.N - r.k0;
   // DPM-Solver++: the x0 history of the run, zeroed.  The first executed iteration is first order and never reads it, so the eager warm-up
   // iteration, which runs as that iteration and writes its x0 here, needs no save / restore: the first replay overwrites that before
   // anything reads it.
   if (s.scheduler == 2) {
-    CHK(c->hist.ensure(r.lat_bytes));
-    HIPCHK(hipMemsetAsync(c->hist.p, 0, r.lat_bytes, st));
+    CHK(c->run.hist.ensure(r.lat_bytes));
+    HIPCHK(hipMemsetAsync(c->run.hist.p, 0, r.lat_bytes, st));
   }
-  CHK(c->inoise.ensure(s.preseq ? (size_t)s.B * s.preseq_len * CFD_LAT * 4 : 16));
+  CHK(c->run.inoise.ensure(s.preseq ? (size_t)s.B * s.preseq_len * CFD_LAT * 4 : 16));
   if (s.preseq) {
-    HIPCHK(hipMemcpy2DAsync(c->inoise.p, (size_t)s.preseq_len * CFD_LAT * 4, c->latents.p, (size_t)s.L * CFD_LAT * 4,
+    HIPCHK(hipMemcpy2DAsync(c->run.inoise.p, (size_t)s.preseq_len * CFD_LAT * 4, c->run.latents.p, (size_t)s.L * CFD_LAT * 4,
                             (size_t)s.preseq_len * CFD_LAT * 4, s.B, hipMemcpyDeviceToDevice, st));
   }
   return CFD_OK;
@@ -643,21 +643,19 @@ static int warm_up_iteration(BeginState& r) {
   const bool preseq = r.s.preseq != nullptr;
   DBuf save_lat, save_in;
   CHK(save_lat.ensure(r.lat_bytes));
-  HIPCHK(hipMemcpyAsync(save_lat.p, c->latents.p, r.lat_bytes, hipMemcpyDeviceToDevice, st));
+  HIPCHK(hipMemcpyAsync(save_lat.p, c->run.latents.p, r.lat_bytes, hipMemcpyDeviceToDevice, st));
   if (preseq) {
-    CHK(save_in.ensure(c->inoise.bytes));
-    HIPCHK(hipMemcpyAsync(save_in.p, c->inoise.p, c->inoise.bytes, hipMemcpyDeviceToDevice, st));
+    CHK(save_in.ensure(c->run.inoise.bytes));
+    HIPCHK(hipMemcpyAsync(save_in.p, c->run.inoise.p, c->run.inoise.bytes, hipMemcpyDeviceToDevice, st));
   }
   if (r.k0) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)c->w->d_step.p, r.k0, 1, st));   // (d_step[0] = k0: coefficients, tables, ring slot 0)
   CHK(enqueue_loop_iteration(c, st));
-  HIPCHK(hipMemcpyAsync(c->latents.p, save_lat.p, r.lat_bytes, hipMemcpyDeviceToDevice, st));
-  if (preseq) HIPCHK(hipMemcpyAsync(c->inoise.p, save_in.p, c->inoise.bytes, hipMemcpyDeviceToDevice, st));
+  HIPCHK(hipMemcpyAsync(c->run.latents.p, save_lat.p, r.lat_bytes, hipMemcpyDeviceToDevice, st));
+  if (preseq) HIPCHK(hipMemcpyAsync(c->run.inoise.p, save_in.p, c->run.inoise.bytes, hipMemcpyDeviceToDevice, st));
   HIPCHK(hipMemsetAsync(c->w->d_step.p, 0, 16, st));
   if (r.k0) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)c->w->d_step.p, r.k0, 1, st));
-  if (c->acen_on) HIPCHK(hipMemsetAsync(c->acen.p, 0, (size_t)c->nl * XA_CEN_SLOTS * XA_CEN_STRIDE * sizeof(unsigned), st));   // (the warm-up counted too)
+  if (c->acen.on) HIPCHK(hipMemsetAsync(c->acen.buf.p, 0, (size_t)c->nl * XA_CEN_SLOTS * XA_CEN_STRIDE * sizeof(unsigned), st));   // (the warm-up counted too)
   HIPCHK(hipStreamSynchronize(st));
-  save_lat.release();
-  save_in.release();
   return CFD_OK;
 }
 
@@ -665,20 +663,18 @@ static int warm_up_iteration(BeginState& r) {
 // caller's stream and has been waited for.
 static int capture_iteration(Ctx* c) {
   hipStream_t cap = c->own_stream;
-  c->run_stream = cap;
+  c->run.stream = cap;
   c->memside_in_forward = false;
   HIPCHK(hipStreamBeginCapture(cap, hipStreamCaptureModeThreadLocal));
   int r = enqueue_loop_iteration(c, cap);
-  c->run_counts = c->memside_in_forward;   // (the hoisted / row-tile iteration has no counting launch: cfd_sample_read then skips the census read)
+  c->run.counts = c->memside_in_forward;   // (the hoisted / row-tile iteration has no counting launch: cfd_sample_read then skips the census read)
   c->memside_in_forward = false;
-  c->acen_measured = c->acen_on && c->acen_hits > 0;
-  c->acen_on = false;
-  hipGraph_t g = nullptr;
-  hipError_t e = hipStreamEndCapture(cap, &g);
-  if (r != CFD_OK) { if (g) (void)hipGraphDestroy(g); return r; }
+  c->acen.measured = c->acen.on && c->acen.hits > 0;
+  c->acen.on = false;
+  hipError_t e = hipStreamEndCapture(cap, &c->run.graph.graph);   // (sample_begin has emptied the holder)
+  if (r != CFD_OK) { c->run.graph.reset(); return r; }
   if (e != hipSuccess) return fail(CFD_E_HIP, "stream capture failed: %s", hipGetErrorString(e));
-  c->graph = g;
-  HIPCHK(hipGraphInstantiate(&c->gexec, c->graph, nullptr, nullptr, 0));
+  HIPCHK(hipGraphInstantiate(&c->run.graph.exec, c->run.graph.graph, nullptr, nullptr, 0));
   return CFD_OK;
 }
 
@@ -686,18 +682,18 @@ static int capture_iteration(Ctx* c) {
 static int sample_begin(Ctx* c, const cfd_sample_args* args, void* stream, const BeginExt& x) {
   if (!c || !args) return fail(CFD_E_ARG, "null argument");
   if (x.weights && args->G != 7) return fail(CFD_E_ARG, "%s: a weight table needs the 7-chunk guidance batch (G = %d)", x.opener, args->G);
-  if (c->run_open) return fail(CFD_E_STATE, "a sampling run is already open");
+  if (c->run.open) return fail(CFD_E_STATE, "a sampling run is already open");
   CHK(setup_preamble(c));
-  struct AcenOff { Ctx* c; ~AcenOff() { c->acen_on = false; } } acen_off{c};   // (the census slots go only into THIS run's launches)
-  c->acen_valid = c->acen_measured = false;
-  c->acen_hits = 0;
+  struct AcenOff { Ctx* c; ~AcenOff() { c->acen.on = false; } } acen_off{c};   // (the census slots go only into THIS run's launches)
+  c->acen.valid = c->acen.measured = false;
+  c->acen.hits = 0;
   cfd_sample_args s_w;
   if (x.weights) {   // a weighted run ignores guidance_weight and skip_zero_weight_chunks (its table says which chunks count)
     s_w = *args;
     s_w.skip_zero_weight_chunks = 0;
     args = &s_w;
   }
-  c->run = RunMode{};
+  c->run.mode = RunMode{};
   // N = loop iterations (the length of scheduler.timesteps); num_inference_steps = the count given to set_timesteps, which fixes the
   // stride `prev_t = t - T // n_inf` of the step formulas.  They differ only for a caller-supplied table.
   BeginState r{c, *args, x, (hipStream_t)stream, args->timesteps ? args->num_timesteps : args->num_inference_steps,
@@ -709,9 +705,9 @@ static int sample_begin(Ctx* c, const cfd_sample_args* args, void* stream, const
   CHK(select_chunks(r));
   CHK(permute_chunks(r));
   if (x.weights) {
-    for (int k = 0; k < 8; ++k) c->wpos[k] = c->chunk_pos[r.keep_idx[k] >= 0 ? r.keep_idx[k] : 0];
-    c->run.weighted = true;
-    if (x.chunks_evaluated) *x.chunks_evaluated = c->sargs.G;
+    for (int k = 0; k < 8; ++k) c->run.wpos[k] = c->run.chunk_pos[r.keep_idx[k] >= 0 ? r.keep_idx[k] : 0];
+    c->run.mode.weighted = true;
+    if (x.chunks_evaluated) *x.chunks_evaluated = c->run.args.G;
   }
   CHK(setup_run_problem(r));
   CHK(wire_att_ring(r));
@@ -719,14 +715,13 @@ static int sample_begin(Ctx* c, const cfd_sample_args* args, void* stream, const
   CHK(upload_run_tables(c, r.s, r.N, r.k0, r.st));
   CHK(check_saturation(c, "cfd_sample_begin (memories / their once-per-run projections)"));
   CHK(init_latents_and_kind(r));
-  if (c->gexec) { (void)hipGraphExecDestroy(c->gexec); c->gexec = nullptr; }
-  if (c->graph) { (void)hipGraphDestroy(c->graph); c->graph = nullptr; }
+  c->run.graph.reset();
   CHK(warm_up_iteration(r));
   CHK(capture_iteration(c));
-  c->run_open = true;
-  c->run_pos = 0;
-  c->acen_valid = true;
-  if (!x.weights && x.chunks_evaluated) *x.chunks_evaluated = c->sargs.G;
+  c->run.open = true;
+  c->run.pos = 0;
+  c->acen.valid = true;
+  if (!x.weights && x.chunks_evaluated) *x.chunks_evaluated = c->run.args.G;
   return CFD_OK;
 }
 
@@ -835,7 +830,7 @@ static int level_batch_refusals(Ctx* c, const cfd_sample_args* args, const char*
   for (int j = 0; j < CFD_NMEM; ++j)
     if (args->att_ring[j]) return fail(CFD_E_ARG, "%s keeps no attention maps (att_ring)", who);
   if (levels_per_batch < 0) return fail(CFD_E_ARG, "%s: levels_per_batch = %d", who, levels_per_batch);
-  if (c->run_open) return fail(CFD_E_STATE, "a sampling run is open on this handle");
+  if (c->run.open) return fail(CFD_E_STATE, "a sampling run is open on this handle");
   return CFD_OK;
 }
 
@@ -906,9 +901,9 @@ static int level_batch_setup(Ctx* c, const cfd_sample_args& s, const char* who, 
   CHK(check_scheduler_tables(s, who));
   CHK(setup_preamble(c));
   const int N = s.timesteps ? s.num_timesteps : s.num_inference_steps;
-  // the evaluated chunks and their memories' row maps, as a run with these arguments would have them (weighted_chunks works on c->sargs)
-  c->sargs = s;
-  c->sargs.timesteps = nullptr;
+  // the evaluated chunks and their memories' row maps, as a run with these arguments would have them (weighted_chunks works on c->run.args)
+  c->run.args = s;
+  c->run.args.timesteps = nullptr;
   cfd_memory mem_in[CFD_NMEM], vm[CFD_NMEM];
   for (int j = 0; j < CFD_NMEM; ++j) mem_in[j] = s.mem[j];
   memset(lb, 0, sizeof(*lb));
@@ -917,14 +912,14 @@ static int level_batch_setup(Ctx* c, const cfd_sample_args& s, const char* who, 
     CHK(weighted_chunks(c, wtab, prune, N, false, mem_in, keep_idx, st));
     for (int k = 0; k < 8; ++k) lb->g.pos[k] = keep_idx[k] >= 0 ? keep_idx[k] : 0;
     lb->g.Gc = 7;
-    lb->g.wtab = c->wtab.as<float>();
+    lb->g.wtab = c->run.wtab.as<float>();
   } else {
     trim_zero_weight_chunks(c, s);
-    for (int k = 0; k < 8; ++k) { lb->g.pos[k] = k < c->sargs.G ? k : 0; lb->g.w[k] = s.guidance_weight[k]; }
-    lb->g.Gc = c->sargs.G;
+    for (int k = 0; k < 8; ++k) { lb->g.pos[k] = k < c->run.args.G ? k : 0; lb->g.w[k] = s.guidance_weight[k]; }
+    lb->g.Gc = c->run.args.G;
   }
   lb->g.clip = s.clip_sample;
-  lb->B = s.B; lb->L = s.L; lb->N = N; lb->Ge = c->sargs.G;
+  lb->B = s.B; lb->L = s.L; lb->N = N; lb->Ge = c->run.args.G;
   const int R = lb->Ge * s.B;   // rows of a level
   CHK(levels_per_batch_of(c, mem_in, R, s.L, N, levels_per_batch, workspace_bytes, &lb->J));
   CHK(level_batch_memories(c, mem_in, R, lb->J, vm));
@@ -956,9 +951,9 @@ extern "C" int cfd_ddpm_invert(cfd_handle c, const cfd_sample_args* args, const 
   xa.g = lb.g;
   const size_t lat_bytes = (size_t)B * L * CFD_LAT * 4;
   HIPCHK(hipMemcpyAsync(inv->trajectory, inv->source, lat_bytes, hipMemcpyDeviceToDevice, st));   // slot 0: the source
-  LevelArgs la{inv->source, inv->level_noise, inv->trajectory, c->w->sample_sp.as<char>(), c->coef.as<StepCoef>(), B, L, Ge, N, 0, J,
+  LevelArgs la{inv->source, inv->level_noise, inv->trajectory, c->w->sample_sp.as<char>(), c->run.coef.as<StepCoef>(), B, L, Ge, N, 0, J,
                (unsigned long long)s.seed, s.first_utterance};
-  xa.eps = c->w->eps.as<float>(); xa.traj = inv->trajectory; xa.noise = inv->noise; xa.coef = c->coef.as<StepCoef>();
+  xa.eps = c->w->eps.as<float>(); xa.traj = inv->trajectory; xa.noise = inv->noise; xa.coef = c->run.coef.as<StepCoef>();
   xa.B = B; xa.L = L; xa.G = Ge; xa.N = N; xa.J = J;
   const long long n8 = (long long)J * B * L * (CFD_LAT / 8);
   const dim3 grid((unsigned)((n8 + 255) / 256)), block(256);
@@ -1056,8 +1051,8 @@ extern "C" int cfd_sample_parallel(cfd_handle c, const cfd_sample_args* args, co
   PicardRing ring{par->trajectory, N + 1, N, chunk};
   if (!ring.x) {
     ring.slots = J + 1;
-    CHK(c->latents.ensure((size_t)ring.slots * chunk * 4));
-    ring.x = c->latents.as<float>();
+    CHK(c->run.latents.ensure((size_t)ring.slots * chunk * 4));
+    ring.x = c->run.latents.as<float>();
   }
   PicardSweep sw(c, st, ring, B, L, Ge, J);
   DBuf &sbuf = c->pic_s, &part = c->pic_part, &err = c->pic_err;
@@ -1068,7 +1063,7 @@ extern "C" int cfd_sample_parallel(cfd_handle c, const cfd_sample_args* args, co
   if (s.init_latents) HIPCHK(hipMemcpyAsync(ring.at(0), s.init_latents, (size_t)chunk * 4, hipMemcpyDeviceToDevice, st));
   else CHK(enqueue_philox_fill(ring.at(0), B, L * CFD_LAT, (uint64_t)s.seed, 0u, s.first_utterance, 1u, 1.0f, st));
   CHK(sw.fill(0, 1, J));   // every latent of the first window starts from X(0)
-  sw.sa.eps = c->w->eps.as<float>(); sw.sa.s = sbuf.as<float>(); sw.sa.coef = c->coef.as<StepCoef>(); sw.sa.g = lb.g;
+  sw.sa.eps = c->w->eps.as<float>(); sw.sa.s = sbuf.as<float>(); sw.sa.coef = c->run.coef.as<StepCoef>(); sw.sa.g = lb.g;
   sw.sa.noise = s.step_noise; sw.sa.seed = s.seed; sw.sa.utt0 = s.first_utterance;
   const int max_sweeps = par->max_sweeps ? par->max_sweeps : N;
   int sweeps = 0;
@@ -1107,17 +1102,17 @@ extern "C" int cfd_sample_parallel(cfd_handle c, const cfd_sample_args* args, co
 
 extern "C" int cfd_sample_census(cfd_handle c, cfd_census* out) {
   if (!c || !out) return fail(CFD_E_ARG, "null argument");
-  if (!c->acen_valid) return fail(CFD_E_STATE, "no sampling run was opened on this handle");
+  if (!c->acen.valid) return fail(CFD_E_STATE, "no sampling run was opened on this handle");
   memset(out, 0, sizeof(*out));
-  out->tau = c->acen_tau;
-  out->measured = c->acen_measured ? 1 : 0;
-  out->iterations = c->run_pos;
+  out->tau = c->acen.tau;
+  out->measured = c->acen.measured ? 1 : 0;
+  out->iterations = c->run.pos;
   out->worst_layer = -1;
-  if (!c->acen_measured) return CFD_OK;
+  if (!c->acen.measured) return CFD_OK;
   HIPCHK(hipSetDevice(c->cfg.device));
-  HIPCHK(hipStreamSynchronize(c->run_stream));
+  HIPCHK(hipStreamSynchronize(c->run.stream));
   std::vector<unsigned> h((size_t)c->nl * XA_CEN_SLOTS * XA_CEN_STRIDE);
-  HIPCHK(hipMemcpy(h.data(), c->acen.p, h.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(h.data(), c->acen.buf.p, h.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
   for (int l = 0; l < c->nl; ++l) {
     unsigned pk_bits = 0, over = 0, seen = 0;   // (positive floats order like their bits)
     for (int sl = 0; sl < XA_CEN_SLOTS; ++sl) {
@@ -1138,34 +1133,34 @@ extern "C" int cfd_sample_census(cfd_handle c, cfd_census* out) {
 
 extern "C" int cfd_sample_steps(cfd_handle c, int n) {
   if (!c) return fail(CFD_E_ARG, "null handle");
-  if (!c->run_open) return fail(CFD_E_STATE, "no sampling run open");
-  if (n < 0 || c->run_pos + n > c->run_iters)
-    return fail(CFD_E_ARG, "run has %d of %d iterations done; cannot run %d more", c->run_pos, c->run_iters, n);
+  if (!c->run.open) return fail(CFD_E_STATE, "no sampling run open");
+  if (n < 0 || c->run.pos + n > c->run.iters)
+    return fail(CFD_E_ARG, "run has %d of %d iterations done; cannot run %d more", c->run.pos, c->run.iters, n);
   HIPCHK(hipSetDevice(c->cfg.device));
-  for (int i = 0; i < n; ++i) HIPCHK(hipGraphLaunch(c->gexec, c->run_stream));
-  c->run_pos += n;
+  for (int i = 0; i < n; ++i) HIPCHK(hipGraphLaunch(c->run.graph.exec, c->run.stream));
+  c->run.pos += n;
   return CFD_OK;
 }
 
 extern "C" int cfd_dyadic_steps(cfd_handle a, cfd_handle b, const cfd_dyadic_proj* pr, int n) {
   if (!a || !pr || a == b) return fail(CFD_E_ARG, "side A's handle, the projection and (two-handle form) a distinct side B handle are needed");
-  if (!a->run_open || (b && !b->run_open)) return fail(CFD_E_STATE, "both sides need an open sampling run");
+  if (!a->run.open || (b && !b->run.open)) return fail(CFD_E_STATE, "both sides need an open sampling run");
   if (!pr->w1 || !pr->b1 || !pr->w2 || !pr->b2 || !pr->spk_a || !pr->spk_b || !pr->tmp || pr->hidden < 1 || pr->out_dim != CFD_D)
     return fail(CFD_E_ARG, "bad partner projection");
-  const cfd_sample_args& sa = a->sargs;
-  if (a->run.tie || (b && b->run.tie)) return fail(CFD_E_ARG, "a tied run takes no dyadic steps");
-  if (!(sa.dynamic_memory_mask & 1) || (b && !(b->sargs.dynamic_memory_mask & 1)))
+  const cfd_sample_args& sa = a->run.args;
+  if (a->run.mode.tie || (b && b->run.mode.tie)) return fail(CFD_E_ARG, "a tied run takes no dyadic steps");
+  if (!(sa.dynamic_memory_mask & 1) || (b && !(b->run.args.dynamic_memory_mask & 1)))
     return fail(CFD_E_STATE, "the speaker memory of the run(s) must be declared dynamic");
-  if (b && (sa.B != b->sargs.B || sa.L != b->sargs.L || a->cfg.device != b->cfg.device)) return fail(CFD_E_ARG, "the two sides differ in batch, length or device");
+  if (b && (sa.B != b->run.args.B || sa.L != b->run.args.L || a->cfg.device != b->cfg.device)) return fail(CFD_E_ARG, "the two sides differ in batch, length or device");
   if (!b && sa.B % 2) return fail(CFD_E_ARG, "merged form: the run holds side A's utterances followed by side B's (even batch)");
-  if (n < 0 || a->run_pos + n > a->run_iters || (b && b->run_pos + n > b->run_iters))
-    return fail(CFD_E_ARG, "run has %d of %d iterations done; cannot run %d more", a->run_pos, a->run_iters, n);
+  if (n < 0 || a->run.pos + n > a->run.iters || (b && b->run.pos + n > b->run.iters))
+    return fail(CFD_E_ARG, "run has %d of %d iterations done; cannot run %d more", a->run.pos, a->run.iters, n);
   HIPCHK(hipSetDevice(a->cfg.device));
-  hipStream_t st = a->run_stream;
+  hipStream_t st = a->run.stream;
   if (b) {
     // side B's stream may still hold its set-up or an earlier read: everything below is ordered behind it, and side B's later reads
     // behind everything below (events, no host wait)
-    HIPCHK(hipEventRecord(b->weg_ev, b->run_stream));
+    HIPCHK(hipEventRecord(b->weg_ev, b->run.stream));
     HIPCHK(hipStreamWaitEvent(st, b->weg_ev, 0));
   }
   const int Bs = b ? sa.B : sa.B / 2;                  // utterances per side
@@ -1177,46 +1172,46 @@ extern "C" int cfd_dyadic_steps(cfd_handle a, cfd_handle b, const cfd_dyadic_pro
     (void)enqueue_linear_act(lat, rows, CFD_LAT, pr->w1, pr->b1, pr->hidden, 1, pr->tmp, st);
     (void)enqueue_linear_act((const float*)pr->tmp, rows, pr->hidden, pr->w2, pr->b2, pr->out_dim, 1, spk, st);
   };
-  const float* lat_a = a->latents.as<float>();
-  const float* lat_b = b ? b->latents.as<float>() : lat_a + rows * CFD_LAT;
+  const float* lat_a = a->run.latents.as<float>();
+  const float* lat_b = b ? b->run.latents.as<float>() : lat_a + rows * CFD_LAT;
   for (int i = 0; i < n; ++i) {
     project(lat_b, pr->spk_a);                         // A attends to B's latents as they stand at the start of the iteration ...
     project(lat_a, pr->spk_b);                         // ... and B to A's
     HIPCHK(hipGetLastError());
-    HIPCHK(hipGraphLaunch(a->gexec, st));
-    if (b) HIPCHK(hipGraphLaunch(b->gexec, st));       // same queue, one after the other: no two-queue overlap
+    HIPCHK(hipGraphLaunch(a->run.graph.exec, st));
+    if (b) HIPCHK(hipGraphLaunch(b->run.graph.exec, st));       // same queue, one after the other: no two-queue overlap
   }
-  a->run_pos += n;
+  a->run.pos += n;
   if (b) {
-    b->run_pos += n;
+    b->run.pos += n;
     HIPCHK(hipEventRecord(a->weg_ev, st));
-    HIPCHK(hipStreamWaitEvent(b->run_stream, a->weg_ev, 0));
+    HIPCHK(hipStreamWaitEvent(b->run.stream, a->weg_ev, 0));
   }
   return CFD_OK;
 }
 
-extern "C" int cfd_sample_position(cfd_handle c) { return (c && c->run_open) ? c->run_pos : -1; }
+extern "C" int cfd_sample_position(cfd_handle c) { return (c && c->run.open) ? c->run.pos : -1; }
 
 extern "C" int cfd_sample_read(cfd_handle c, float* out, int close) {
   if (!c || !out) return fail(CFD_E_ARG, "null argument");
-  if (!c->run_open) return fail(CFD_E_STATE, "no sampling run open");
+  if (!c->run.open) return fail(CFD_E_STATE, "no sampling run open");
   HIPCHK(hipSetDevice(c->cfg.device));
-  const size_t lat_bytes = (size_t)c->sargs.B * c->sargs.L * CFD_LAT * 4;
-  if (c->run.tie && !c->run.tie_final && c->run_pos == c->run_iters) {   // a finished tied run: the tie copy once more (mid-run reads: as stepped)
-    const long long n8 = (long long)c->sargs.B * c->sargs.L * (CFD_LAT / 8);
-    hipLaunchKernelGGL(tie_copy_kernel<>, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, c->run_stream, c->latents.as<float>(),
-                       c->etie.as<int32_t>(), n8);
+  const size_t lat_bytes = (size_t)c->run.args.B * c->run.args.L * CFD_LAT * 4;
+  if (c->run.mode.tie && !c->run.mode.tie_final && c->run.pos == c->run.iters) {   // a finished tied run: the tie copy once more (mid-run reads: as stepped)
+    const long long n8 = (long long)c->run.args.B * c->run.args.L * (CFD_LAT / 8);
+    hipLaunchKernelGGL(tie_copy_kernel<>, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, c->run.stream, c->run.latents.as<float>(),
+                       c->run.etie.as<int32_t>(), n8);
     HIPCHK(hipGetLastError());
-    c->run.tie_final = true;
+    c->run.mode.tie_final = true;
   }
-  HIPCHK(hipMemcpyAsync(out, c->latents.p, lat_bytes, hipMemcpyDeviceToDevice, c->run_stream));
-  HIPCHK(hipStreamSynchronize(c->run_stream));
+  HIPCHK(hipMemcpyAsync(out, c->run.latents.p, lat_bytes, hipMemcpyDeviceToDevice, c->run.stream));
+  HIPCHK(hipStreamSynchronize(c->run.stream));
   CHK(settle_deferred_census(c));
   // the census of everything the run's iterations counted (per-step projections of a dynamic memory, the three-launch cross-attention):
   // read on every read of a run whose captured iteration has such launches, BEFORE the run is closed -- a run that fails here stays open
   // and can be inspected or closed by the caller
-  if (c->run_counts) CHK(check_saturation(c, "sampling run (the per-step projections of a memory)"));
-  if (close) c->run_open = false;
+  if (c->run.counts) CHK(check_saturation(c, "sampling run (the per-step projections of a memory)"));
+  if (close) c->run.open = false;
   return CFD_OK;
 }
 
@@ -1319,34 +1314,26 @@ extern "C" int cfd_test_picard_sweep(cfd_handle c, const cfd_test_picard_args* t
   HIPCHK(hipSetDevice(c->cfg.device));
   hipStream_t st = (hipStream_t)stream;
   PicardSweep sw(c, st, PicardRing{t->ring, t->slots, N, chunk}, B, L, G, J);
-  DBuf coef, part;
-  auto run = [&]() -> int {
-    if (do_fill) CHK(sw.fill(t->fill_src, t->fill_lo, t->fill_hi));
-    if (do_load) CHK(sw.load(base, (char*)t->sample_sp));
-    sw.sa.s = t->s;
-    if (do_step) {
-      CHK(coef.ensure((size_t)N * sizeof(StepCoef)));
-      HIPCHK(hipMemcpyAsync(coef.p, t->coef, (size_t)N * sizeof(StepCoef), hipMemcpyHostToDevice, st));
-      PicardStepArgs& sa = sw.sa;
-      sa.eps = t->eps; sa.coef = coef.as<StepCoef>();
-      sa.g.Gc = t->Gc; sa.g.clip = t->clip; sa.g.wtab = t->wtab;
-      for (int k = 0; k < 8; ++k) { sa.g.w[k] = t->w[k]; sa.g.pos[k] = k < t->Gc ? t->pos[k] : 0; }
-      sa.noise = t->noise; sa.seed = t->seed; sa.utt0 = t->first_utterance;
-      CHK(sw.step(base, off));
-    }
-    if (do_scan) {
-      CHK(part.ensure(sw.part_bytes()));
-      HIPCHK(hipMemsetAsync(part.p, 0xFF, sw.part_bytes(), st));
-      CHK(sw.scan_err(base, off, part.as<float>(), t->err));
-    }
-    return CFD_OK;
-  };
-  const int r = run();
-  const hipError_t e = hipStreamSynchronize(st);   // (before the hook's own buffers go)
-  coef.release();
-  part.release();
-  CHK(r);
-  if (e != hipSuccess) return fail(CFD_E_HIP, "cfd_test_picard_sweep: %s", hipGetErrorString(e));
+  DBuf coef, part;   // (a return in front of the wait frees them too: hipFree waits for the device)
+  if (do_fill) CHK(sw.fill(t->fill_src, t->fill_lo, t->fill_hi));
+  if (do_load) CHK(sw.load(base, (char*)t->sample_sp));
+  sw.sa.s = t->s;
+  if (do_step) {
+    CHK(coef.ensure((size_t)N * sizeof(StepCoef)));
+    HIPCHK(hipMemcpyAsync(coef.p, t->coef, (size_t)N * sizeof(StepCoef), hipMemcpyHostToDevice, st));
+    PicardStepArgs& sa = sw.sa;
+    sa.eps = t->eps; sa.coef = coef.as<StepCoef>();
+    sa.g.Gc = t->Gc; sa.g.clip = t->clip; sa.g.wtab = t->wtab;
+    for (int k = 0; k < 8; ++k) { sa.g.w[k] = t->w[k]; sa.g.pos[k] = k < t->Gc ? t->pos[k] : 0; }
+    sa.noise = t->noise; sa.seed = t->seed; sa.utt0 = t->first_utterance;
+    CHK(sw.step(base, off));
+  }
+  if (do_scan) {
+    CHK(part.ensure(sw.part_bytes()));
+    HIPCHK(hipMemsetAsync(part.p, 0xFF, sw.part_bytes(), st));
+    CHK(sw.scan_err(base, off, part.as<float>(), t->err));
+  }
+  HIPCHK(hipStreamSynchronize(st));
   return CFD_OK;
 }
 
@@ -1387,17 +1374,17 @@ extern "C" int cfd_philox_normal(cfd_handle c, float* out, int B, int per_utt, u
 
 extern "C" int cfd_sample_inpaint(cfd_handle c) {
   if (!c) return fail(CFD_E_ARG, "null handle");
-  if (!c->run_open) return fail(CFD_E_STATE, "no sampling run open");
-  const cfd_sample_args& s = c->sargs;
+  if (!c->run.open) return fail(CFD_E_STATE, "no sampling run open");
+  const cfd_sample_args& s = c->run.args;
   // a tied, edit or anchored run: that instance does the tied / kept tokens of this iteration (one thread = 8 elements of any token), then
   // the captured iteration skips its overwrite; the default instance: the preseq tokens, if the run has any
-  const bool by_token = c->run.tie || c->run.edit || c->run.anchor;
-  if (by_token && c->run_pos >= c->run_iters) return fail(CFD_E_STATE, "cfd_sample_inpaint: the run has no iteration left");
+  const bool by_token = c->run.mode.tie || c->run.mode.edit || c->run.mode.anchor;
+  if (by_token && c->run.pos >= c->run.iters) return fail(CFD_E_STATE, "cfd_sample_inpaint: the run has no iteration left");
   if (!by_token && (!s.preseq || s.preseq_len < 1)) return CFD_OK;
   HIPCHK(hipSetDevice(c->cfg.device));
   const long long n = by_token ? (long long)s.B * s.L * (CFD_LAT / 8) : (long long)s.B * s.preseq_len * CFD_LAT;
   return with_begin_args(c, [&](auto a) {
-    hipLaunchKernelGGL(BeginInst<decltype(a)>::inpaint_now, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->run_stream, a,
+    hipLaunchKernelGGL(BeginInst<decltype(a)>::inpaint_now, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->run.stream, a,
                        c->w->d_step.as<int>());
     HIPCHK(hipGetLastError());
     return (int)CFD_OK;
@@ -1406,13 +1393,13 @@ extern "C" int cfd_sample_inpaint(cfd_handle c) {
 
 extern "C" int cfd_sample_write(cfd_handle c, const float* latents) {
   if (!c || !latents) return fail(CFD_E_ARG, "null argument");
-  if (!c->run_open) return fail(CFD_E_STATE, "no sampling run open");
-  if (c->sargs.scheduler == 3) return fail(CFD_E_ARG, "cfd_sample_write: a DDIM inversion run takes no WEG update (its latents are its own)");
-  if (c->run.replay) return fail(CFD_E_ARG, "cfd_sample_write: the replay of a noise space takes no WEG update (its noise was solved for the recorded levels)");
+  if (!c->run.open) return fail(CFD_E_STATE, "no sampling run open");
+  if (c->run.args.scheduler == 3) return fail(CFD_E_ARG, "cfd_sample_write: a DDIM inversion run takes no WEG update (its latents are its own)");
+  if (c->run.mode.replay) return fail(CFD_E_ARG, "cfd_sample_write: the replay of a noise space takes no WEG update (its noise was solved for the recorded levels)");
   HIPCHK(hipSetDevice(c->cfg.device));
-  const size_t lat_bytes = (size_t)c->sargs.B * c->sargs.L * CFD_LAT * 4;
-  HIPCHK(hipMemcpyAsync(c->latents.p, latents, lat_bytes, hipMemcpyDeviceToDevice, c->run_stream));
-  HIPCHK(hipStreamSynchronize(c->run_stream));
+  const size_t lat_bytes = (size_t)c->run.args.B * c->run.args.L * CFD_LAT * 4;
+  HIPCHK(hipMemcpyAsync(c->run.latents.p, latents, lat_bytes, hipMemcpyDeviceToDevice, c->run.stream));
+  HIPCHK(hipStreamSynchronize(c->run.stream));
   return CFD_OK;
 }
 

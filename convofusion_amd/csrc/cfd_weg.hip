@@ -223,18 +223,17 @@ static int run_through_graph(WegEval& e, WegState::Graph& g) {
   hipStream_t st = e.st;
   if (g.key != e.key) g.reset(e.key);
   const bool on = e.c->weg_graph_on;
-  if (on && g.exec) {
-    HIPCHK(hipGraphLaunch(g.exec, st));
+  if (on && g.gx.exec) {
+    HIPCHK(hipGraphLaunch(g.gx.exec, st));
   } else if (on && g.uses >= 1) {
+    g.gx.reset();   // (a graph whose instantiation failed last time)
     HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
     const int rr = enqueue_eval(e);
-    hipGraph_t captured = nullptr;
-    hipError_t err = hipStreamEndCapture(st, &captured);
-    if (rr != CFD_OK) { if (captured) (void)hipGraphDestroy(captured); return rr; }
+    hipError_t err = hipStreamEndCapture(st, &g.gx.graph);
+    if (rr != CFD_OK) { g.gx.reset(); return rr; }
     if (err != hipSuccess) return fail(CFD_E_HIP, "capturing the WEG evaluation failed: %s", hipGetErrorString(err));
-    g.graph = captured;
-    HIPCHK(hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0));
-    HIPCHK(hipGraphLaunch(g.exec, st));
+    HIPCHK(hipGraphInstantiate(&g.gx.exec, g.gx.graph, nullptr, nullptr, 0));
+    HIPCHK(hipGraphLaunch(g.gx.exec, st));
   } else {
     CHK(enqueue_eval(e));
   }
@@ -358,7 +357,7 @@ extern "C" int cfd_denoise_vjp(cfd_handle c, const cfd_vjp_args* a, const float*
   // its memory-side results (WegState::sig) nor its captured launches, whose arguments hold addresses that set-up may move.
   w.sig.clear();
   for (WegState::Graph& g : w.graph)
-    if (g.exec) { HIPCHK(hipStreamSynchronize(st)); g.reset(); }
+    if (g.gx.exec) { HIPCHK(hipStreamSynchronize(st)); g.reset(); }
   CHK(wegrt::prepare(c, wegrt::FOR_VJP, a->Be, a->L, a->mem, 1, st, maps));
   w.rt.T = 1;
   w.t_host = a->timestep;

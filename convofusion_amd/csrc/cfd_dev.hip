@@ -108,7 +108,7 @@ extern "C" int cfd_debug_read(cfd_handle c, const char* what, float* dst_dev, si
   if (!strcmp(what, "xa.info")) {   // the last cfd_forward's cross-attention: kernel instance, work-list form
     if (numel < 7) return fail(CFD_E_ARG, "xa.info needs 7 floats");
     const Problem& p = c->wk[0].pb;
-    const float f[7] = {(float)c->xa_inst, (float)p.xa_nwg, (float)p.xa_tpw, (float)p.xa_n16, (float)p.xa_nseg, p.xa_flush ? 1.f : 0.f, (float)p.xa_one};
+    const float f[7] = {(float)(p.path.xa_reached ? p.path.xa_inst : XA_INST_NONE), (float)p.xa_nwg, (float)p.xa_tpw, (float)p.xa_n16, (float)p.xa_nseg, p.xa_flush ? 1.f : 0.f, (float)p.xa_one};
     HIPCHK(hipMemcpy(dst_dev, f, sizeof(f), hipMemcpyHostToDevice));
     return CFD_OK;
   }

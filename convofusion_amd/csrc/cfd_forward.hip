@@ -1,5 +1,6 @@
 // libcfdenoise: the launches of one denoiser forward (tile kernels: enqueue_rows; small problems: enqueue_rows_rt), cfd_forward and the
-// per-class profiling hook.
+// per-class profiling hook.  Which of them run, and in which form, is Problem::path (decided in setup_problem, cfd_problem.hip): the
+// launch sequences read it and decide nothing themselves.
 #include "cfd_internal.hpp"
 
 // ---- the denoiser forward: Denoiser.forward (denoiser.py:173-386) --------------------------------------
@@ -8,7 +9,7 @@
 
 int enqueue_denoise(Ctx* c, hipStream_t st) {
   CHK(enqueue_memside(c, st));
-  if (c->w->pb.rt) return enqueue_rows_rt(c, st);
+  if (c->w->pb.path.rt) return enqueue_rows_rt(c, st);
   return enqueue_rows(c, st);
 }
 
@@ -45,7 +46,7 @@ static int refresh_step_rows(Ctx* c, hipStream_t st, const int* dstep, const std
 int enqueue_rows_rt(Ctx* c, hipStream_t st, const RtSave* sv) {
   const Problem& p = c->w->pb;
   const int nl = c->nl, L = p.L, tpr = (L + 15) / 16, ntile = p.Be * tpr;
-  const int* dstep = c->w->d_step.as<int>();
+  const int* dstep = c->w->d_step.as<int>() + p.path.dstep_slot;
   const int lds_xpv = rt_xpv_lds(p.Sp_tot, p.Sp_tot <= 512 ? 512 : RT_MAX_KEYS);
 #define RT_SET_LDS(kernel, bytes) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes))
   static unsigned long long attr_done = 0;
@@ -225,18 +226,14 @@ int enqueue_rows(Ctx* c, hipStream_t st) {
   const Problem& p = c->w->pb;
   const int nl = c->nl, L = p.L, Be = p.Be;
   const long long M = p.M;
-  const int* dstep = p.tmode ? c->w->d_step.as<int>() + 1 : c->w->d_step.as<int>();
+  const int* dstep = c->w->d_step.as<int>() + p.path.dstep_slot;
   const long long ROWB = CFD_D * 4;  // bytes per SP row of 512
   const dim3 blk(256);
-  bool want_att = false;
-  for (int j = 0; j < CFD_NMEM; ++j) want_att = want_att || p.att[j];
-  if (p.att_fused) want_att = false;   // (the ring of a sampling run on the tile kernels: the fused kernel keeps the maps itself)
-  // one fused kernel per layer for the cross-attention block, unless att_mats are wanted
-  const bool fused_x = c->fused_xattn && p.xa_nwg > 0 && !want_att;
-
-  // rows that run the replica-independent head of the network (see Problem::share_B)
-  const bool share = p.share_B > 0 && Be % p.share_B == 0 && Be > p.share_B && !c->stop_stage;
-  const int Bs = share ? p.share_B : Be;
+  // one fused kernel per layer for the cross-attention block, or the three launches (path.xattn)
+  const bool fused_x = p.path.xattn == XATTN_FUSED;
+  // rows that run the replica-independent head of the network (path.share)
+  const bool share = p.path.share;
+  const int Bs = share ? p.path.share_rows : Be;
   const long long Ms = (long long)Bs * L;
   // 1. latent embedding + body/hand embedding + query PE          (denoiser.py:187,316-326)
   {
@@ -254,11 +251,11 @@ int enqueue_rows(Ctx* c, hipStream_t st) {
   const float* ss_now = c->w->ss_tab.as<float>();
   const float *kb_now[CFD_NMEM], *vb_now[CFD_NMEM];
   for (int j = 0; j < CFD_NMEM; ++j) { kb_now[j] = c->w->kbtab[j].as<float>(); vb_now[j] = c->w->vbtab[j].as<float>(); }
-  const bool rows_now = p.tmode == 0;
+  const bool rows_now = p.path.rows_now;
   if (rows_now && p.T > 1) {
     std::vector<StepTab> tabs{{&ss_now, nl * 4 * CFD_D}};
     for (int j = 0; j < CFD_NMEM; ++j)
-      if ((p.static_mask >> j) & 1) { tabs.push_back({&kb_now[j], nl * CFD_D + 32}); tabs.push_back({&vb_now[j], nl * CFD_D}); }
+      if ((p.path.static_mask >> j) & 1) { tabs.push_back({&kb_now[j], nl * CFD_D + 32}); tabs.push_back({&vb_now[j], nl * CFD_D}); }
     CHK(refresh_step_rows(c, st, dstep, tabs));
   }
   auto ln = [&](const float* g, const float* b, int adaln, int tbidx, char* out, long long rows) -> int {
@@ -286,8 +283,7 @@ int enqueue_rows(Ctx* c, hipStream_t st) {
   // per-row slot statistics, and the consumer (q | k | v^T in one launch, FFN1, latent_proj) runs on W diag(gamma) and rescales its accumulators.
   // Range: the launches launch_gemm gives the 64 x 64 / 128 x 64 classes anyway (launch_gemm_midsize); above it a ln_rows launch costs less than
   // the producer's wider epilogue (measured at the headline shape: +25.8 us against 14).
-  const bool ln_fold = c->ln_fold != 0 && L == 16 && !c->stop_stage &&
-                       (c->ln_fold > 0 || (M >= 512 && M <= 3840));   // (below: the row-tile path or a handful of workgroups; above: launch_gemm's 128 x 128 class)
+  const bool ln_fold = p.path.ln_fold;
   if (ln_fold) CHK(c->w->ln_stat.ensure((size_t)M * LN_SLOTS * 2 * 4));
   auto token_gemm_resid_stat = [&](const DBuf& w, int K, const char* y, const float* bias, long long rows, char* xs) -> int {
     GemmArgs a = gemm_args();
@@ -336,11 +332,12 @@ int enqueue_rows(Ctx* c, hipStream_t st) {
           const float* cd = w.ln_cd.as<float>();
           ag.X[0] = w.wqk_f.as<char>(); ag.X[1] = w.wv_f.as<char>();
           CHK((run_gemm_midsize<MODE_GROUPED>(c, CFD_PROF_GEMM_TOKEN, ag, epi_ln(eg, c->w->ln_stat.as<float>(), cd, cd + 1024, cd + 2048, cd + 2560, 1e-5f), st)));
-        } else
-        CHK((run_gemm<MODE_GROUPED>(c, CFD_PROF_GEMM_TOKEN, ag, eg, 1, 1, st)));
+        } else {
+          CHK((run_gemm<MODE_GROUPED>(c, CFD_PROF_GEMM_TOKEN, ag, eg, 1, 1, st)));
+        }
         qkv_one_launch = true;
       } else {
-      CHK((run_gemm<MODE_PLAIN>(c, CFD_PROF_GEMM_TOKEN, a, e, 1, 1, st)));
+        CHK((run_gemm<MODE_PLAIN>(c, CFD_PROF_GEMM_TOKEN, a, e, 1, 1, st)));
       }
     }
     if (qkv_one_launch) {
@@ -374,13 +371,13 @@ int enqueue_rows(Ctx* c, hipStream_t st) {
       a.x = c->w->x.as<float>(); a.ln_g = w.ln2g; a.ln_b = w.ln2b; a.bias = w.cross_bias.as<float>(); a.L = L;
       for (int j = 0; j < CFD_NMEM; ++j) {
         const size_t rows = (size_t)p.U[j] * p.Sp[j];
-        // (single-fp16 tiles of a long memory, Problem::xa_f16 / xa_f16_mask: 32 KB per 32 keys = 1 KB per key, tile-major per (layer, instance))
-        const bool f16 = p.xa_f16 && ((p.xa_f16_mask >> j) & 1);
+        // (single-fp16 tiles of a long memory, the F16 instance's path.f16_mask: 32 KB per 32 keys = 1 KB per key, tile-major per (layer, instance))
+        const bool f16 = (p.path.f16_mask >> j) & 1;
         a.K[j] = f16 ? c->w->k16[j].as<char>() + (size_t)l * rows * 1024 : c->w->kall_sp[j].as<char>() + (size_t)l * rows * ROWB;
         a.cb[j] = c->w->cb[j].as<float>() + (size_t)l * rows;
         a.VT[j] = f16 ? c->w->v16[j].as<char>() + (size_t)l * rows * 1024 : c->w->vt_all[j].as<char>() + (size_t)l * rows * ROWB;
         a.Sp[j] = p.Sp[j];
-        const bool stat = (p.static_mask >> j) & 1;
+        const bool stat = (p.path.static_mask >> j) & 1;
         a.rs_off[j] = (unsigned)((size_t)(nl - l) * rows * 4);
         a.kb[j] = stat ? kb_now[j] + (size_t)l * CFD_D : c->w->zeros512.as<float>();
         a.kb_stride[j] = stat ? nl * CFD_D + 32 : 0;
@@ -402,16 +399,16 @@ int enqueue_rows(Ctx* c, hipStream_t st) {
       a.stamps = c->w->xa_stamps.as<long long>();
 #endif
       Bracket br(c, CFD_PROF_XATTN, st);
-      if (p.att_fused) a.att = c->w->xa_att_desc.as<XaAtt>() + l;
-      if (c->acen.on && !p.att_fused) {   // the attention-concentration census of a sampling run (the ATT instance counts nothing)
+      const int inst = p.path.xa_inst;
+      if (inst == XA_INST_ATT) a.att = c->w->xa_att_desc.as<XaAtt>() + l;
+      if (c->acen.on && inst != XA_INST_ATT) {   // the attention-concentration census of a sampling run (the ATT instance counts nothing)
         a.census = c->acen.buf.as<unsigned>() + (size_t)l * XA_CEN_SLOTS * XA_CEN_STRIDE;
         a.census_tau = c->acen.tau;
         c->acen.hits += 1;
       }
-      c->xa_inst = p.att_fused ? 1 : p.xa_f16 ? 2 : 0;
       auto launch_xa = [&](int nwg, const XAttnArgs& xa) {
-        if (p.att_fused) hipLaunchKernelGGL((xattn_fused_kernel<true, false>), dim3(nwg), dim3(XA_WAVES * 64), XA_LDS, st, xa);
-        else if (p.xa_f16) hipLaunchKernelGGL((xattn_fused_kernel<false, true>), dim3(nwg), dim3(XA_WAVES * 64), XA_LDS, st, xa);
+        if (inst == XA_INST_ATT) hipLaunchKernelGGL((xattn_fused_kernel<true, false>), dim3(nwg), dim3(XA_WAVES * 64), XA_LDS, st, xa);
+        else if (inst == XA_INST_F16) hipLaunchKernelGGL((xattn_fused_kernel<false, true>), dim3(nwg), dim3(XA_WAVES * 64), XA_LDS, st, xa);
         else hipLaunchKernelGGL((xattn_fused_kernel<false, false>), dim3(nwg), dim3(XA_WAVES * 64), XA_LDS, st, xa);
       };
       if (l == 0 && share && p.xa0_nwg_a > 0) {   // layer-0 de-duplication (build_xattn_layer0_lists): the longest memory once per distinct (utterance, instance) ...
@@ -532,8 +529,9 @@ int enqueue_rows(Ctx* c, hipStream_t st) {
         const float* cd = w.ln_cd.as<float>();
         a.X[0] = w.w1_f.as<char>(); a.Y = c->w->o_sp.as<char>();
         CHK((run_gemm_midsize<MODE_PLAIN>(c, CFD_PROF_GEMM_TOKEN, a, epi_ln(e, c->w->ln_stat.as<float>(), cd + 3072, cd + 4096, cd + 3072, cd + 4096, 1e-5f), st)));
-      } else
-      CHK((run_gemm<MODE_PLAIN>(c, CFD_PROF_GEMM_TOKEN, a, e, 1, 1, st)));
+      } else {
+        CHK((run_gemm<MODE_PLAIN>(c, CFD_PROF_GEMM_TOKEN, a, e, 1, 1, st)));
+      }
     }
     // second FFN product + residual, then the next layer's norm1 (or the decoder's final norm)   (:661, :568; :238-239)
     {
@@ -557,10 +555,11 @@ int enqueue_rows(Ctx* c, hipStream_t st) {
       const float* cd = c->ln_cd_p.as<float>();
       a.X[0] = c->wp_f.as<char>();
       CHK((run_gemm_midsize<MODE_PLAIN>(c, CFD_PROF_GEMM_TOKEN, a, epi_ln(e, c->w->ln_stat.as<float>(), cd, cd + CFD_LAT, cd, cd + CFD_LAT, 1e-5f), st)));
-    } else
-    CHK((run_gemm<MODE_PLAIN>(c, CFD_PROF_GEMM_TOKEN, a, e, 1, 1, st)));
+    } else {
+      CHK((run_gemm<MODE_PLAIN>(c, CFD_PROF_GEMM_TOKEN, a, e, 1, 1, st)));
+    }
   }
-  if (p.att_fused && fused_x) {   // this step's maps: from what the nine cross-attention launches kept, into slot *d_step of the ring
+  if (p.path.keeps_maps()) {   // this step's maps: from what the nine cross-attention launches kept, into slot *d_step of the ring
     XaFixArgs f;
     memset(&f, 0, sizeof(f));
     f.att = c->w->xa_att_desc.as<XaAtt>(); f.nl = nl; f.L = L; f.one_j = p.xa_one; f.d_step = c->w->d_step.as<int>();
@@ -583,35 +582,26 @@ extern "C" int cfd_forward(cfd_handle c, const float* sample, int Be, int L, con
   if (n_t != 1 && n_t != Be) return fail(CFD_E_ARG, "n_t must be 1 or Be");
   hipStream_t st = (hipStream_t)stream;
   const int tmode = (n_t == 1) ? 0 : 1;
-  c->xa_inst = -1;
-  {  // (test hook cfd_debug_forward_operands: the single-fp16 tiles of a sampling run's operand policy, asked for as setup_run_problem asks)
-    bool any_att = false;
-    for (int j = 0; j < CFD_NMEM; ++j) any_att = any_att || (att && att[j]);
-    c->want_f16 = c->fwd_operands != 0 && tmode == 0 && !any_att;
-    const int r_setup = setup_problem(c, Be, L, mem, att, tmode, n_t);
-    c->want_f16 = false;
-    CHK(r_setup);
-  }
+  PathAsk ask;
+  for (int j = 0; j < CFD_NMEM; ++j) ask.att_out = ask.att_out || (att && att[j]);
+  // (test hook cfd_debug_forward_operands: the single-fp16 tiles of a sampling run's operand policy, asked for as setup_run_problem asks)
+  ask.f16 = c->fwd_operands != 0 && tmode == 0 && !ask.att_out;
+  CHK(setup_problem(c, Be, L, mem, nullptr, att, ask, tmode, n_t));
   CHK(sat_begin(c, st));
   // tmode 0 reads table row d_step[0] which must be 0 outside a sampling run
   HIPCHK(hipMemsetAsync(c->w->d_step.p, 0, 16, st));
   CHK(build_time_tables(c, timesteps, n_t, st));
   // (the sample is split in front of the once-per-call projections, so that ONE wait reads the census of both)
   CHK(enqueue_to_split(c, CFD_PROF_OTHER, st, sample, c->w->sample_sp.as<char>(), c->w->pb.M, CFD_LAT, (long long)CFD_LAT, (long long)CFD_LAT * 4, c->sat_in()));
-  {
-    bool want_att = false;
-    for (int j = 0; j < CFD_NMEM; ++j) want_att = want_att || (att && att[j]);
-    const bool reuse = c->hint_now && c->w->pb.prev_same;
-    CHK(prepare_static_memside(c, st, 0, want_att && !c->w->pb.att_fused, reuse));
-    if (c->w->pb.static_mask) {   // once-per-call projections of the caller's memories: the census is read before they are used
-      HIPCHK(hipStreamSynchronize(st));
-      CHK(check_saturation(c, "cfd_forward (sample, memories / their projections)"));
-    }
+  CHK(prepare_static_memside(c, st, c->hint_now && c->w->pb.prev_same));
+  if (c->w->pb.path.static_mask) {   // once-per-call projections of the caller's memories: the census is read before they are used
+    HIPCHK(hipStreamSynchronize(st));
+    CHK(check_saturation(c, "cfd_forward (sample, memories / their projections)"));
   }
   c->memside_in_forward = false;
   CHK(enqueue_denoise(c, st));
   HIPCHK(hipMemcpyAsync(out, c->w->eps.p, (size_t)c->w->pb.M * CFD_LAT * 4, hipMemcpyDeviceToDevice, st));
-  if (c->memside_in_forward || !c->w->pb.static_mask) {
+  if (c->memside_in_forward || !c->w->pb.path.static_mask) {
     // Paths whose memory-side projections run INSIDE the forward (per-row timesteps, att_mats on the tile kernels, the three-launch
     // cross-attention): their census -- and the sample's, which no earlier wait has read on these paths -- is read here,
     // so that a clamped projection fails THIS call instead of the next one (on these paths the call therefore returns with `out` complete).
@@ -622,12 +612,11 @@ extern "C" int cfd_forward(cfd_handle c, const float* sample, int Be, int L, con
   {   // what the next call may reuse (cfd_forward_same_memories): all five memories' timestep-independent projections are in the workspace
     Work* w = c->w;
     const Problem& p = w->pb;
-    w->fwd_mem_valid = p.tmode == 0 && p.static_mask == (1 << CFD_NMEM) - 1;
+    w->fwd_mem_valid = p.tmode == 0 && p.path.static_mask == (1 << CFD_NMEM) - 1;
     w->fwd_wver = (unsigned long long)c->wver;
     w->fwd_Be = p.Be;
     w->fwd_L = p.L;
-    w->fwd_att = false;
-    for (int j = 0; j < CFD_NMEM; ++j) w->fwd_att = w->fwd_att || (att && att[j]);
+    w->fwd_att = ask.att_out;
     for (int j = 0; j < CFD_NMEM; ++j) {
       w->fwd_U[j] = p.U[j]; w->fwd_S[j] = p.S[j]; w->fwd_mask[j] = mem[j].key_padding_mask != nullptr; w->fwd_map[j] = mem[j].row_map != nullptr;
     }

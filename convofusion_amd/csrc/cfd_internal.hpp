@@ -17,6 +17,7 @@
 #include "../../include/cfdenoise.h"
 #include "../../include/cfdenoise_dev.h"
 #include "owned.hpp"
+#include "forward_path.hpp"
 #include "gemm_sp.hpp"
 #include "rows.hpp"
 #include "attn_fused.hpp"
@@ -33,7 +34,19 @@ struct LayerW {
   const float *ln1g, *ln1b, *tb1g, *tb1b, *btb1, *ln2g, *ln2b, *tb2g, *tb2b, *btb2, *ln3g, *ln3b, *b1, *b2;
 };
 
+// The five row maps of a problem on the host (fetch_row_maps, cfd_problem.hip): memory j's instance of batch row b, range-checked
+struct HostMaps {
+  std::vector<int> m[CFD_NMEM];
+};
+static_assert(FP_NMEM == CFD_NMEM, "forward_path.hpp counts the memories itself");
+
+// One problem: shapes, pointers and -- `path` -- how its forward runs.  setup_problem (cfd_problem.hip) fills it, path included
+// (decide_forward_path, forward_path.hpp: the only place where the conditions are written, from the knobs, the shapes and what the caller
+// asks for); the work lists are built for that path, and every launch sequence only reads it: path.rt picks enqueue_rows_rt or enqueue_rows,
+// path.xattn the cross-attention block of enqueue_rows, path.xa_inst the fused kernel's instance ("xa.info"), path.static_mask the
+// memories whose projections prepare_static_memside makes once.  Nothing changes the path after setup_problem.
 struct Problem {
+  ForwardPath path;
   int Be = 0, L = 0, Lp = 0;
   long long M = 0;
   int U[CFD_NMEM], S[CFD_NMEM], Sp[CFD_NMEM], off[CFD_NMEM], Sp_tot = 0;
@@ -44,20 +57,18 @@ struct Problem {
   float* att[CFD_NMEM];
   // attention ring of a sampling run (cfd_sample_args::att_ring): only the batch rows [att_b0, att_b0 + att_nb) write their maps, into
   // slot *d_step of att[j] (att_slot[j] floats per slot), as rows 0 .. att_nb - 1 of that slot.  att_nb == 0: att[j] is one [Be][nl][L][S_j] block.
+  // (path.keeps_maps(): the fused cross-attention kernel's ATT instance + att_fixup_kernel write them; every row's for cfd_forward's att)
   int att_b0 = 0, att_nb = 0;
   bool prev_same = false;       // setup_problem: the workspace still holds the previous cfd_forward's projections of memories of these shapes
-  bool att_fused = false;       // the ring is written by the fused cross-attention kernel's ATT instance + att_fixup_kernel (tile kernels)
   long long att_slot[CFD_NMEM] = {0, 0, 0, 0, 0};
   int tmode = 0;  // 0: all rows share the timestep of table row *d_step ; 1: row b uses table row b ; 2: a level batch (below)
   // Level batch (cfd_ddpm_invert, tmode 2): the batch is J levels of lv_rows rows each, level-major; every row of level lv uses table row
   // lv_i0 + lv, and memory j's U[j] = J * lv_U[j] instances are the caller's lv_U[j] distinct memories once per level (instance
   // lv * lv_U[j] + u: memory u at level lv's timestep), reached through level row maps.
   int lv_rows = 0, lv_i0 = 0, lv_U[CFD_NMEM] = {0, 0, 0, 0, 0};
-  // Sampling loop only: the effective batch is G replicas (chunk-major) of the same B latent rows, so everything
-  // before the first cross-attention -- embedding, layer 0's self-attention and first time block -- is identical
-  // for the G replicas of an utterance (same input, same timestep; the memories enter only at the cross-attention).
-  // It is computed for the first B rows and copied to the other chunks.  0 = off (cfd_forward: arbitrary rows).
-  int share_B = 0;
+  // (path.share, sampling loop only: the batch is G replicas (chunk-major) of the same B latent rows, so everything before the first
+  //  cross-attention -- embedding, layer 0's self-attention and first time block -- is identical for the G replicas of an utterance; it is
+  //  computed for the first path.share_rows = B rows and copied to the other chunks.)
   int T = 1;      // rows in the temb tables
   // Rows that share one memory of the LARGEST memory type in long consecutive runs (the guidance batch repeats
   // the unconditional audio memory for 5 of its 7 chunks): their attention against that memory is one big
@@ -69,16 +80,9 @@ struct Problem {
   int xa0_nwg_a = 0, xa0_nwg_b = 0;   // layer-0 de-duplication lists (build_xattn_layer0_lists); 0: one launch
   bool xa_flush = false;               // some work list flushes the accumulator between two online memories (XA_FLUSH): lock-step kernel only
   int xa_one = -1;                     // the one-key memory the fused cross-attention adds as a vector (xattn_fused.hpp, XAttnArgs::one_j), or -1
-  bool xa_f16 = false;                 // the fused cross-attention's key / value tiles of LONG memories are single fp16 in this problem (its F16 instance;
-                                       // false: split pairs).  Only a sampling run sets it (cfd_sample_args::operand_policy) -- and a cfd_forward under the
-                                       // developer hook cfd_debug_forward_operands -- and only when every memory is static and no maps are kept
-  int xa_f16_mask = 0;                 // bit j: memory j is long enough (XA_F16_MIN_KEYS) for single-fp16 tiles; its segments carry XA_F16
   int xa_tpw = 0, xa_n16 = 0, xa_nseg = 0;   // of the work list (build_xattn_worklist): the most query tiles, XA_F16 segments and segments of a workgroup ("xa.info")
-  // memories (bit j) whose folded projections were computed once for the run from the centred static part of the memory
-  // (prepare_static_memside); per step they only get their per-key scale and bias (mem_scale_all_kernel)
-  int static_mask = 0;
-  // small problems (rowtile.hpp): every launch of the forward is a grid of 16-token x 16-feature workgroups; needs every memory static
-  bool rt = false;
+  // (path.static_mask: memories whose folded projections are computed once for the run from the centred static part of the memory,
+  //  prepare_static_memside; per step they only get their per-key scale and bias, mem_scale_all_kernel)
   int rt_use_inst = 0;                              // the row maps fit the kernel arguments (<= RT_ARG_ROWS rows, instances < 256)
   unsigned char rt_inst[CFD_NMEM][RT_ARG_ROWS];
 };
@@ -268,9 +272,7 @@ struct cfd_handle_s {
   AttnCensus acen;
   unsigned int* sat_mem() const { return sat.as<unsigned int>() + CFD_SAT_MEM; }
   unsigned int* sat_in() const { return sat.as<unsigned int>() + CFD_SAT_IN; }
-  bool want_f16 = false;        // cfd_sample_begin -> setup_problem: the run asks for single-fp16 tiles (non-zero operand policy; false everywhere else)
   int fwd_operands = 0;         // test hook (cfd_debug_forward_operands): 15 = cfd_forward asks setup_problem for single-fp16 tiles as a run would; 0 = pairs
-  int xa_inst = -1;             // test read-out ("xa.info"): the xattn_fused_kernel instance the last enqueue_rows launched (0 pairs, 1 ATT, 2 F16; -1: none)
   bool hint_same_mem = false;   // cfd_forward_same_memories: the promise for the NEXT cfd_forward ...
   bool hint_now = false;        // ... taken (and cleared) at that call's very first line, before anything can fail: a call that returns early
                                 // must not leave the promise standing for the call after it
@@ -287,7 +289,7 @@ struct cfd_handle_s {
   //                               instead of the fused kernel (xattn_fused.hpp)
   //   CFD_FUSED_XATTN_MIN_WGS=<n> the fewest workgroups a work list needs for the fused kernel
   //   CFD_L0_DEDUP=0              layer 0's cross-attention as one launch over all rows (build_xattn_layer0_lists)
-  //   CFD_SHARE0=0                the pre-cross-attention part of layer 0 for every guidance replica (Problem::share_B)
+  //   CFD_SHARE0=0                the pre-cross-attention part of layer 0 for every guidance replica (ForwardPath::share)
   //   CFD_PERMUTE=0               a sampling run keeps the caller's chunk order (chunk_pos)
   //   CFD_LN_FOLD=0 / 1           the algebraic LayerNorm fold of mid-size problems (cfd_forward.hip) off / wherever the launches allow
   //                               it; unset (-1): by shape
@@ -296,7 +298,15 @@ struct cfd_handle_s {
   long long rt_max_rows = 700;    // measured crossover at the product shape (L = 16), seconds per 1000 steps, row-tile vs tile kernels (profiles/r05_rowtile_crossover.log:
                                   // the short cross-attention work lists of round 5 made the tile kernels faster): 5 utterances 1.04 / 1.22, 6: 1.18 / 1.24, 7: 1.34 / 1.23
   int fused_xattn_min_wgs = 6, ln_fold = -1, xa_operands = -1;
-  WegState weg;                 // cfd_weg_eval's state between two evaluations (cfd_weg.hip)
+  // what decide_forward_path (forward_path.hpp) reads of the handle
+  PathKnobs path_knobs() const {
+    PathKnobs k;
+    k.rt_on = rt_on; k.rt_max_rows = rt_max_rows; k.fused_xattn = fused_xattn; k.min_wgs = fused_xattn_min_wgs; k.share0 = share0;
+    k.ln_fold = ln_fold; k.stop_stage = stop_stage;
+    k.rt_max_l = RT_MAX_L; k.rt_max_keys = RT_MAX_KEYS; k.xa_tiles = XA_TILES; k.f16_min_keys = XA_F16_MIN_KEYS;
+    return k;
+  }
+  WegState weg;                // cfd_weg_eval's state between two evaluations (cfd_weg.hip)
   hipEvent_t weg_ev = nullptr;  // cross-stream hand-over of cfd_weg_eval, and of cfd_dyadic_steps
   // profiling
   bool prof = false;
@@ -494,13 +504,16 @@ int enqueue_to_split(Ctx* c, int cls, hipStream_t st, const float* src, char* ds
 // the LayerNorm fold's weight side (cfd_core.hip, null stream): dst_sp = split(W diag(gamma)) [R][K], cvec = W' 1, dvec = W beta; tmp: scratch
 int ln_fold_weight(Ctx* c, const float* W, int R, int K, const float* gamma, const float* beta, DBuf& tmp, DBuf& dst_sp, float* cvec, float* dvec);
 // cfd_problem.hip: work lists, problem set-up, timestep tables, memory-side projections
-int build_xattn_worklist(Ctx* c, const cfd_memory mem[CFD_NMEM], bool one_key);
-int build_xattn_layer0_lists(Ctx* c, const cfd_memory mem[CFD_NMEM]);
-int setup_att_fused(Ctx* c);
-int setup_problem(Ctx* c, int Be, int L, const cfd_memory mem[CFD_NMEM], float* const att[CFD_NMEM], int tmode, int T);
+// the memories' row maps on the host, `rows` entries each (rows_name: what the caller calls that count, for the message): the one place that
+// downloads a row map.  A memory without a map gets the identity and must have one instance per row; every entry is checked against U.
+int fetch_row_maps(const cfd_memory mem[CFD_NMEM], int rows, const char* rows_name, HostMaps& hm);
+// maps: the host copy of mem[].row_map where the caller has it already (null: fetched here, unless cfd_forward keeps the previous call's lists);
+// att: attention outputs [Be][nl][L][S_j] or null; ask: what else the caller asks of the forwards (forward_path.hpp)
+int setup_problem(Ctx* c, int Be, int L, const cfd_memory mem[CFD_NMEM], const HostMaps* maps, float* const att[CFD_NMEM], const PathAsk& ask,
+                  int tmode, int T);
 int build_time_tables(Ctx* c, const int32_t* trows_host, int T, hipStream_t st);
 int enqueue_time_tables(Ctx* c, int T, hipStream_t st);
-int prepare_static_memside(Ctx* c, hipStream_t st, int dynamic_mask, bool want_att, bool reuse = false);
+int prepare_static_memside(Ctx* c, hipStream_t st, bool reuse = false);
 int enqueue_memside(Ctx* c, hipStream_t st);
 // cfd_forward.hip: the launches of one denoiser forward
 int enqueue_rows(Ctx* c, hipStream_t st);

@@ -1,6 +1,7 @@
-// libcfdenoise: everything that is decided or computed once per problem -- the fused cross-attention's work lists, the workspace of a
-// problem (setup_problem), the timestep-only tables, the memory-side projections made once per run (prepare_static_memside) -- and the
-// memory-side launches of a forward that still run per step (enqueue_memside).
+// libcfdenoise: everything that is decided or computed once per problem -- the memories' row maps on the host (fetch_row_maps), how the
+// problem's forward runs (setup_problem: Problem::path = decide_forward_path, forward_path.hpp), the fused cross-attention's work lists
+// built for that path, the workspace, the timestep-only tables, the memory-side projections made once per run (prepare_static_memside)
+// -- and the memory-side launches of a forward that still run per step (enqueue_memside).  The path is decided here and nowhere else.
 #include "cfd_internal.hpp"
 
 // ---- problem setup ----------------------------------------------------------------------------------
@@ -18,7 +19,7 @@ struct XaRow {      // one row of a work list
   int inst[CFD_NMEM]; // memory instance per memory
   int aux;            // row of xa_dedup this row's tiles store to / add (-1: none)
   int one;            // instance of the one-key memory (Problem::xa_one), or -1
-  int att;            // row of the attention-map blocks this row's tiles store to (Problem::att_fused), or -1
+  int att;            // row of the attention-map blocks this row's tiles store to (path.keeps_maps()), or -1
 };
 
 static void make_xattn_worklist(const Problem& p, const std::vector<XaRow>& rows, int mem_mask, std::vector<XaWg>& wgs, std::vector<XaSeg>& segs,
@@ -77,7 +78,7 @@ static void make_xattn_worklist(const Problem& p, const std::vector<XaRow>& rows
         for (int k = 0; k < XA_TILES; ++k) {
           if (vr[k] < 0 || (done >> k) & 1) continue;
           XaSeg sg;
-          sg.j = j; sg.u = rows[vr[k]].inst[j]; sg.wmask = 0; sg.flags = (online ? XA_ONLINE : 0) | (((p.xa_f16_mask >> j) & 1) ? XA_F16 : 0);
+          sg.j = j; sg.u = rows[vr[k]].inst[j]; sg.wmask = 0; sg.flags = (online ? XA_ONLINE : 0) | (((p.path.f16_mask >> j) & 1) ? XA_F16 : 0);
           for (int k2 = k; k2 < XA_TILES; ++k2)
             if (vr[k2] >= 0 && rows[vr[k2]].inst[j] == sg.u) sg.wmask |= 1 << k2;
           done |= sg.wmask;
@@ -115,14 +116,15 @@ static void make_xattn_worklist(const Problem& p, const std::vector<XaRow>& rows
   }
 }
 
-static int read_row_maps(Ctx* c, const cfd_memory mem[CFD_NMEM], std::vector<std::vector<int>>& hm) {
-  const Problem& p = c->w->pb;
-  hm.assign(CFD_NMEM, std::vector<int>(p.Be));
+int fetch_row_maps(const cfd_memory mem[CFD_NMEM], int rows, const char* rows_name, HostMaps& hm) {
   for (int j = 0; j < CFD_NMEM; ++j) {
-    if (mem[j].row_map) HIPCHK(hipMemcpy(hm[j].data(), mem[j].row_map, (size_t)p.Be * 4, hipMemcpyDeviceToHost));
-    else for (int b = 0; b < p.Be; ++b) hm[j][b] = b;
-    for (int b = 0; b < p.Be; ++b)
-      if (hm[j][b] < 0 || hm[j][b] >= p.U[j]) return fail(CFD_E_ARG, "memory %s: row_map[%d] = %d outside [0, %d)", MEM_NAMES[j], b, hm[j][b], p.U[j]);
+    std::vector<int>& m = hm.m[j];
+    m.resize((size_t)rows);
+    if (mem[j].row_map) HIPCHK(hipMemcpy(m.data(), mem[j].row_map, (size_t)rows * 4, hipMemcpyDeviceToHost));
+    else if (mem[j].U != rows) return fail(CFD_E_ARG, "memory %s: U = %d != %s = %d without a row_map", MEM_NAMES[j], mem[j].U, rows_name, rows);
+    else for (int b = 0; b < rows; ++b) m[b] = b;
+    for (int b = 0; b < rows; ++b)
+      if (m[b] < 0 || m[b] >= mem[j].U) return fail(CFD_E_ARG, "memory %s: row_map[%d] = %d outside [0, %d)", MEM_NAMES[j], b, m[b], mem[j].U);
   }
   return CFD_OK;
 }
@@ -135,33 +137,37 @@ static int upload_worklist(DBuf& dw, DBuf& ds, const std::vector<XaWg>& wgs, con
   return CFD_OK;
 }
 
-int build_xattn_worklist(Ctx* c, const cfd_memory mem[CFD_NMEM], bool one_key) {
+// The work list of the whole batch (layers 1.., and layer 0 without the lists below), where the path has one (path.xa_list).
+// dynamic_mask: memories rewritten between the forwards of a run; one_dynamic: the one-key memory is among them.
+static int build_xattn_worklist(Ctx* c, const HostMaps& maps, int dynamic_mask, bool* one_dynamic) {
   Problem& p = c->w->pb;
+  const std::vector<int>* hm = maps.m;
   p.xa_nwg = 0; p.xa0_nwg_a = 0; p.xa0_nwg_b = 0; p.xa_flush = false;
   p.xa_tpw = p.xa_n16 = p.xa_nseg = 0;
-  if (!c->fused_xattn) return CFD_OK;
-  std::vector<std::vector<int>> hm;
-  CHK(read_row_maps(c, mem, hm));
+  p.xa_one = -1;
+  *one_dynamic = false;
+  if (!p.path.xa_list) return CFD_OK;
   // A memory of ONE key whose key no instance masks is added as a vector in the kernel's flush instead of walking a 32-key tile step
   // (xattn_fused.hpp, XAttnArgs::one_j): it gets no segments.  (With the key masked the reference's softmax is NaN: that stays a segment.)
-  // `one_key` false: every memory keeps its segments (a one-key memory rewritten between iterations, prepare_static_memside).
-  p.xa_one = -1;
-  if (one_key && p.tmode == 0) {
+  // A one-key memory rewritten between iterations keeps its segments, as every memory then does.
+  if (p.tmode == 0) {
     for (int j = CFD_NMEM - 1; j >= 0 && p.xa_one < 0; --j) {
       if (p.S[j] != 1) continue;
       bool alive = true;
-      if (mem[j].key_padding_mask) {
+      if (p.has_mask[j]) {
         std::vector<uint8_t> mk(p.U[j]);
-        HIPCHK(hipMemcpy(mk.data(), mem[j].key_padding_mask, (size_t)p.U[j], hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(mk.data(), p.mask[j], (size_t)p.U[j], hipMemcpyDeviceToHost));
         for (uint8_t v : mk) alive = alive && v == 0;
       }
       if (alive) p.xa_one = j;
     }
+    *one_dynamic = p.xa_one >= 0 && ((dynamic_mask >> p.xa_one) & 1);
+    if (*one_dynamic) p.xa_one = -1;
   }
   std::vector<XaRow> rows(p.Be);
   for (int b = 0; b < p.Be; ++b) {
     rows[b].xrow = b; rows[b].aux = -1; rows[b].one = p.xa_one >= 0 ? hm[p.xa_one][b] : -1;
-    rows[b].att = (p.att_fused && b >= p.att_b0 && b < p.att_b0 + p.att_nb) ? b - p.att_b0 : -1;
+    rows[b].att = (p.path.keeps_maps() && b >= p.att_b0 && b < p.att_b0 + p.att_nb) ? b - p.att_b0 : -1;
     for (int j = 0; j < CFD_NMEM; ++j) rows[b].inst[j] = hm[j][b];
   }
   const int all_mems = ((1 << CFD_NMEM) - 1) & ~(p.xa_one >= 0 ? 1 << p.xa_one : 0);
@@ -170,14 +176,13 @@ int build_xattn_worklist(Ctx* c, const cfd_memory mem[CFD_NMEM], bool one_key) {
   size_t n_active = 0;
   make_xattn_worklist(p, rows, all_mems, wgs, segs, n_active, p.xa_flush);
   if (wgs.empty() || segs.empty()) return CFD_OK;
-  // A handful of workgroups cannot hide their serial walk over the key tiles (3 barriers and a fill round trip per 32 keys
-  // with nothing else on the chip).  Round-2 measurements at the product shape, 1000 steps, since the memory-side projections
-  // left the loop (the three-launch path still makes them per step): one utterance (2 workgroups) 1.342 s fused against
-  // 1.318 s three-launch, four utterances (7 workgroups) 1.370 against 1.404, 16 (28 workgroups, one shard of the product-shape
-  // benchmark) 470 against 465 steps/s.  Below 6 workgroups the three-launch path stays (CFD_FUSED_XATTN_MIN_WGS overrides;
-  // the test suite sets 0 and runs its small cases through the fused kernel).
-  // (counted in workgroups of four query tiles, as measured -- the list itself may deal fewer tiles per workgroup: make_xattn_worklist)
-  if ((int)(((size_t)p.Be * ((p.L + 15) / 16) + XA_TILES - 1) / XA_TILES) < c->fused_xattn_min_wgs) return CFD_OK;
+  // (The list's length gate is part of path.xa_list, decide_forward_path.  What it was measured on: a handful of workgroups cannot hide
+  // their serial walk over the key tiles -- 3 barriers and a fill round trip per 32 keys with nothing else on the chip.  Round 2 at the
+  // product shape, 1000 steps, since the memory-side projections left the loop (the three-launch path still makes them per step): one
+  // utterance (2 workgroups) 1.342 s fused against 1.318 s three-launch, four utterances (7 workgroups) 1.370 against 1.404, 16 (28
+  // workgroups, one shard of the product-shape benchmark) 470 against 465 steps/s.  Below 6 workgroups the three-launch path stays
+  // (CFD_FUSED_XATTN_MIN_WGS overrides; the test suite sets 0 and runs its small cases through the fused kernel); counted in workgroups
+  // of four query tiles, as measured -- the list itself may deal fewer tiles per workgroup: make_xattn_worklist.)
   (void)n_active;
   CHK(upload_worklist(c->w->xa_wgs, c->w->xa_segs, wgs, segs));
   p.xa_nwg = (int)wgs.size();
@@ -190,7 +195,7 @@ int build_xattn_worklist(Ctx* c, const cfd_memory mem[CFD_NMEM], bool one_key) {
 }
 
 // Layer 0 of the sampling loop: the G guidance chunks of an utterance enter the first cross-attention with the SAME state (the
-// replica-independent head, Problem::share_B), so the attention of that state against one memory instance is the same in every
+// replica-independent head, path.share), so the attention of that state against one memory instance is the same in every
 // chunk that uses the instance.  For the longest memory (audio: 1 500 of the 1 573 keys at the benchmark shape) the 7 chunks of an
 // utterance use 2 instances -- its own and the shared unconditional one -- so 2 evaluations replace 7:
 //   list A  one row per distinct (utterance, instance of the longest memory): that memory only, result (incl. its rank-one
@@ -199,13 +204,12 @@ int build_xattn_worklist(Ctx* c, const cfd_memory mem[CFD_NMEM], bool one_key) {
 // Exact in real arithmetic; the summation order over the memories differs from the one-launch form (CFD_L0_DEDUP=0), so the G
 // chunks of an utterance still leave layer 0 bit-identical where their memories are identical, but a run differs from the
 // one-launch form by rounding (measured 2e-5 relative on final latents).
-int build_xattn_layer0_lists(Ctx* c, const cfd_memory mem[CFD_NMEM]) {
+static int build_xattn_layer0_lists(Ctx* c, const HostMaps& maps) {
   Problem& p = c->w->pb;
+  const std::vector<int>* hm = maps.m;
   p.xa0_nwg_a = p.xa0_nwg_b = 0;
-  if (!c->l0_dedup || p.xa_nwg == 0 || p.share_B <= 0 || p.Be % p.share_B || p.Be == p.share_B) return CFD_OK;
-  const int B = p.share_B, G = p.Be / B;
-  std::vector<std::vector<int>> hm;
-  CHK(read_row_maps(c, mem, hm));
+  if (!c->l0_dedup || p.xa_nwg == 0 || !p.path.share) return CFD_OK;
+  const int B = p.path.share_rows, G = p.Be / B;
   int jg = 0;
   for (int j = 1; j < CFD_NMEM; ++j)
     if (p.Sp[j] > p.Sp[jg]) jg = j;
@@ -224,7 +228,7 @@ int build_xattn_layer0_lists(Ctx* c, const cfd_memory mem[CFD_NMEM]) {
         XaRow r;
         r.xrow = row; r.aux = idx; r.one = -1;
         // (every chunk of the utterance enters layer 0 with the same state: the full-conditioning chunk's map against this instance is this row's)
-        r.att = (p.att_fused && p.att_b0 + b < p.Be && hm[jg][p.att_b0 + b] == u) ? b : -1;
+        r.att = (p.path.keeps_maps() && p.att_b0 + b < p.Be && hm[jg][p.att_b0 + b] == u) ? b : -1;
         for (int j = 0; j < CFD_NMEM; ++j) r.inst[j] = hm[j][row];
         ra.push_back(r);
         seen.emplace_back(u, idx);
@@ -235,7 +239,7 @@ int build_xattn_layer0_lists(Ctx* c, const cfd_memory mem[CFD_NMEM]) {
   if (ra.size() * 2 > (size_t)p.Be) return CFD_OK;   // too little repetition
   for (int b = 0; b < p.Be; ++b) {
     rb[b].xrow = b; rb[b].aux = aux_of[b]; rb[b].one = p.xa_one >= 0 ? hm[p.xa_one][b] : -1;
-    rb[b].att = (p.att_fused && b >= p.att_b0 && b < p.att_b0 + p.att_nb) ? b - p.att_b0 : -1;
+    rb[b].att = (p.path.keeps_maps() && b >= p.att_b0 && b < p.att_b0 + p.att_nb) ? b - p.att_b0 : -1;
     for (int j = 0; j < CFD_NMEM; ++j) rb[b].inst[j] = hm[j][b];
   }
   std::vector<XaWg> wa, wb;
@@ -252,8 +256,8 @@ int build_xattn_layer0_lists(Ctx* c, const cfd_memory mem[CFD_NMEM]) {
   return CFD_OK;
 }
 
-// Buffers and per-layer descriptors of the attention maps the fused cross-attention kernel keeps (Problem::att_fused; rows att_nb, set by the caller)
-int setup_att_fused(Ctx* c) {
+// Buffers and per-layer descriptors of the attention maps the fused cross-attention kernel keeps (path.keeps_maps(); rows att_nb)
+static int setup_att_fused(Ctx* c) {
   Problem& pb = c->w->pb;
   XaAtt d;
   memset(&d, 0, sizeof(d));
@@ -274,7 +278,8 @@ int setup_att_fused(Ctx* c) {
   return CFD_OK;
 }
 
-int setup_problem(Ctx* c, int Be, int L, const cfd_memory mem[CFD_NMEM], float* const att[CFD_NMEM], int tmode, int T) {
+int setup_problem(Ctx* c, int Be, int L, const cfd_memory mem[CFD_NMEM], const HostMaps* maps, float* const att[CFD_NMEM], const PathAsk& ask,
+                  int tmode, int T) {
   // (whatever this call is and however it ends, it may overwrite the memory-side buffers: the previous forward's projections are current
   //  only if cfd_forward says so again at its end)
   const bool mem_was_valid = c->w->fwd_mem_valid;
@@ -298,11 +303,8 @@ int setup_problem(Ctx* c, int Be, int L, const cfd_memory mem[CFD_NMEM], float* 
   p.prev_same = prev_same;
   // ... and with the caller's promise that they ARE the same memories (cfd_forward_same_memories covers the row maps and masks), the work
   // lists and instance tables made from them -- several device-to-host reads per call -- are kept as well
-  bool any_att_in = false;
-  for (int j = 0; j < CFD_NMEM; ++j) any_att_in = any_att_in || (att && att[j]);
-  const bool keep_lists = prev_same && c->hint_now && c->w->fwd_L == L && c->w->fwd_att == any_att_in;
+  const bool keep_lists = prev_same && c->hint_now && c->w->fwd_L == L && c->w->fwd_att == ask.att_out;
   p.Be = Be; p.L = L; p.Lp = (L + 31) / 32 * 32; p.M = (long long)Be * L; p.tmode = tmode; p.T = T;
-  p.share_B = 0;
   if (p.Lp > SM_MAX_CHUNKS * 512) return fail(CFD_E_SHAPE, "L = %d exceeds the in-register softmax limit (%d)", L, SM_MAX_CHUNKS * 512);
   int off = 0;
   for (int j = 0; j < CFD_NMEM; ++j) {
@@ -317,20 +319,26 @@ int setup_problem(Ctx* c, int Be, int L, const cfd_memory mem[CFD_NMEM], float* 
     if (p.Sp[j] > SM_MAX_CHUNKS * 512) return fail(CFD_E_SHAPE, "memory %s: %d keys exceed the in-register softmax limit", MEM_NAMES[j], m.S);
     p.mem[j] = m.data; p.map[j] = m.row_map ? m.row_map : c->w->iota.as<int>(); p.mask[j] = m.key_padding_mask;
     p.att[j] = att ? att[j] : nullptr;
-    p.att_slot[j] = 0;
-    p.att_b0 = p.att_nb = 0;      // (a sampling run with an attention ring sets them after this call)
-    p.att_fused = false;
-    p.xa_f16 = false; p.xa_f16_mask = 0;
+    p.att_slot[j] = 0;        // (a sampling run with an attention ring wires att and att_slot after this call: wire_att_ring)
   }
   p.Sp_tot = off;
-  // The run's operand policy (cfd_sample_begin): which memories are long enough for single-fp16 tiles.  The work lists flag their segments
-  // (XA_F16); whether the run really takes the single-fp16 kernel instance is decided when everything else about it is known
-  // (cfd_sample_begin, prepare_static_memside) -- the pair instance ignores the flag.
-  p.xa_f16 = c->want_f16;
-  if (p.xa_f16)
-    for (int j = 0; j < CFD_NMEM; ++j)
-      if (p.Sp[j] >= XA_F16_MIN_KEYS) p.xa_f16_mask |= 1 << j;
-  if (!p.xa_f16_mask) p.xa_f16 = false;
+  // How the forward runs: decided here, once, from everything that bears on it.  The rows that keep their attention maps follow: a
+  // run's ring rows, or every row where the fused kernel's ATT instance serves cfd_forward's att.
+  PathKnobs knobs = c->path_knobs();
+  PathShape shape;
+  shape.Be = Be; shape.L = L; shape.tmode = tmode;
+  for (int j = 0; j < CFD_NMEM; ++j) shape.S[j] = p.S[j];
+  auto decide = [&]() {
+    p.path = decide_forward_path(knobs, shape, ask);
+    p.att_b0 = ask.ring_row0; p.att_nb = ask.ring_rows;
+    if (!ask.ring_rows && p.path.keeps_maps()) p.att_nb = Be;
+  };
+  decide();
+  HostMaps fetched;
+  if (!maps && !keep_lists) {
+    CHK(fetch_row_maps(mem, Be, "Be", fetched));
+    maps = &fetched;
+  }
   {  // memories without a key-padding mask get an all-zero one, so the softmax kernel needs no null test
     size_t need = (size_t)Be * L;   // (the un-fused self-attention softmax indexes it per batch row)
     for (int j = 0; j < CFD_NMEM; ++j) need = std::max(need, (size_t)p.U[j] * p.S[j]);
@@ -343,16 +351,19 @@ int setup_problem(Ctx* c, int Be, int L, const cfd_memory mem[CFD_NMEM], float* 
       if (!p.mask[j]) p.mask[j] = c->w->zero_mask.as<uint8_t>();
     }
   }
-  p.jbig = -1; p.nruns = 0; p.nlong = 0; p.nshort = Be;
-  if (tmode == 0) {
+  // Everything made from the row maps, from their one host copy (cfd_forward_same_memories with the lists kept: nothing is read, the
+  // previous call's runs, instance table and lists stand)
+  bool one_dynamic = false;
+  if (maps) {
+    p.jbig = -1; p.nruns = 0; p.nlong = 0; p.nshort = Be;
     int jb = 0;
     for (int j = 1; j < CFD_NMEM; ++j)
       if (p.Sp[j] > p.Sp[jb]) jb = j;
     // worth it only for long latents and long memories (measured: 20.6 vs 21.2 ms at L=196 / 1500 keys, but
     // 3.60 vs 3.15 ms at L=16 / 161 keys, where the extra launches dominate)
-    if (p.Sp[jb] >= 256 && L >= 64 && mem[jb].row_map) {
-      std::vector<int> hmap(Be), lrows, srows;
-      HIPCHK(hipMemcpy(hmap.data(), mem[jb].row_map, (size_t)Be * 4, hipMemcpyDeviceToHost));
+    if (tmode == 0 && p.Sp[jb] >= 256 && L >= 64 && mem[jb].row_map) {
+      const std::vector<int>& hmap = maps->m[jb];
+      std::vector<int> lrows, srows;
       for (int b0 = 0; b0 < Be;) {
         int b1 = b0 + 1;
         while (b1 < Be && hmap[b1] == hmap[b0]) ++b1;
@@ -372,34 +383,29 @@ int setup_problem(Ctx* c, int Be, int L, const cfd_memory mem[CFD_NMEM], float* 
         if (!srows.empty()) HIPCHK(hipMemcpy(c->w->short_rows.p, srows.data(), srows.size() * 4, hipMemcpyHostToDevice));
       }
     }
-  }
-  p.rt = c->rt_on && tmode == 0 && L <= RT_MAX_L && p.M <= c->rt_max_rows && p.Sp_tot <= RT_MAX_KEYS;
-  if (p.rt) {
-    if (!keep_lists) p.rt_use_inst = Be <= RT_ARG_ROWS;
-    for (int j = 0; j < CFD_NMEM && p.rt_use_inst && !keep_lists; ++j) {
-      std::vector<int> hm(Be);
-      if (mem[j].row_map) HIPCHK(hipMemcpy(hm.data(), mem[j].row_map, (size_t)Be * 4, hipMemcpyDeviceToHost));
-      else for (int b = 0; b < Be; ++b) hm[b] = b;
-      for (int b = 0; b < Be; ++b) {
-        if (hm[b] < 0 || hm[b] >= p.U[j]) return fail(CFD_E_ARG, "memory %s: row_map[%d] = %d outside [0, %d)", MEM_NAMES[j], b, hm[b], p.U[j]);
-        if (hm[b] > 255) p.rt_use_inst = 0;
-        p.rt_inst[j][b] = (unsigned char)hm[b];
-      }
+    if (p.path.rt) {   // the instances travel in the kernel arguments where they fit
+      p.rt_use_inst = Be <= RT_ARG_ROWS;
+      for (int j = 0; j < CFD_NMEM && p.rt_use_inst; ++j)
+        for (int b = 0; b < Be; ++b) {
+          if (maps->m[j][b] > 255) p.rt_use_inst = 0;
+          p.rt_inst[j][b] = (unsigned char)maps->m[j][b];
+        }
     }
+    CHK(build_xattn_worklist(c, *maps, ask.dynamic_mask, &one_dynamic));
+  }
+  if (p.path.xa_list && p.xa_nwg == 0) {   // (a list that came out empty all the same: decided again without the fused kernel)
+    knobs.fused_xattn = false;
+    decide();
+  }
+  if (maps) {
+    // (a one-key memory rewritten between iterations: layer 0 keeps its one launch, as it always has)
+    if (!one_dynamic) CHK(build_xattn_layer0_lists(c, *maps));
+    if (p.path.keeps_maps()) CHK(setup_att_fused(c));
+  }
+  if (p.path.rt) {
     CHK(c->w->rt_vt.ensure((size_t)Be * CFD_D * RT_MAX_L * 4));
     HIPCHK(hipMemset(c->w->rt_vt.p, 0, (size_t)Be * CFD_D * RT_MAX_L * 4));   // keys beyond L stay zero
   }
-  // A forward that returns att_mats, beyond the row-tile path: the fused cross-attention kernel keeps every row's maps itself (its ATT
-  // instance + att_fixup_kernel) instead of the three-launch path with its per-call memory-side projections.
-  {
-    bool any_att = false;
-    for (int j = 0; j < CFD_NMEM; ++j) any_att = any_att || p.att[j];
-    p.att_fused = any_att && !p.rt && tmode == 0 && c->fused_xattn;
-    if (p.att_fused) { p.att_b0 = 0; p.att_nb = Be; }
-  }
-  if (!keep_lists) CHK(build_xattn_worklist(c, mem, true));
-  if (p.att_fused && p.xa_nwg <= 0) { p.att_fused = false; p.att_nb = 0; }   // (a list too short for the fused kernel: three-launch path)
-  if (p.att_fused && !keep_lists) CHK(setup_att_fused(c));
   const long long M = p.M;
   const int nl = c->nl;
   CHK(c->w->x.ensure((size_t)M * CFD_D * 4));
@@ -495,14 +501,13 @@ static int enqueue_mem_kv(Ctx* c, hipStream_t st, int j, float* ck) {
 }
 
 // Once per cfd_forward / sampling run, after the time tables: the part of the memory-side work that does not depend on the
-// timestep (see rows.hpp, mem_center_kernel, and xattn_fused.hpp).  Memories in `dynamic_mask` (contents rewritten between the
-// iterations of a run: the dyadic rollout's partner projection) keep their per-step projections, and so does every memory when
-// the fused cross-attention kernel is not the one that runs (att_mats wanted, small problems, per-row timesteps).
-int prepare_static_memside(Ctx* c, hipStream_t st, int dynamic_mask, bool want_att, bool reuse) {
-  Problem& p = c->w->pb;
+// timestep (see rows.hpp, mem_center_kernel, and xattn_fused.hpp), for the memories of path.static_mask.  The others -- memories
+// whose contents are rewritten between the iterations of a run (the dyadic rollout's partner projection), and every memory when
+// neither the row-tile nor the fused cross-attention runs or the rows have timesteps of their own -- keep their per-step projections.
+int prepare_static_memside(Ctx* c, hipStream_t st, bool reuse) {
+  const Problem& p = c->w->pb;
   const int nl = c->nl;
   const long long ROWB = CFD_D * 4;
-  p.static_mask = 0;
   for (int j = 0; j < CFD_NMEM; ++j) {   // scale plane = 1 unless mem_scale_all_kernel writes it
     const long long rows = (long long)p.U[j] * p.Sp[j];
     LAUNCH(CFD_PROF_OTHER, fill_f32_kernel<>, dim3((unsigned)((rows + 255) / 256)), dim3(256), st, c->w->cb[j].as<float>() + (size_t)nl * rows, rows, 1.0f);
@@ -511,18 +516,7 @@ int prepare_static_memside(Ctx* c, hipStream_t st, int dynamic_mask, bool want_a
     CHK(c->w->zeros512.ensure(CFD_D * 4));
     HIPCHK(hipMemsetAsync(c->w->zeros512.p, 0, CFD_D * 4, st));
   }
-  if (dynamic_mask) p.rt = false;   // (a memory rewritten between iterations keeps its per-step projections: tile-kernel path)
-  if (p.xa_one >= 0 && ((dynamic_mask >> p.xa_one) & 1)) {   // the one-key memory is rewritten between iterations: it needs its segments back
-    cfd_memory mem[CFD_NMEM];
-    memset(mem, 0, sizeof(mem));
-    for (int j = 0; j < CFD_NMEM; ++j) {
-      mem[j].data = p.mem[j]; mem[j].U = p.U[j]; mem[j].S = p.S[j]; mem[j].row_map = p.map[j];
-      mem[j].key_padding_mask = p.has_mask[j] ? p.mask[j] : nullptr;
-    }
-    CHK(build_xattn_worklist(c, mem, false));
-  }
-  const bool fused = p.rt || (c->fused_xattn && p.xa_nwg > 0 && !want_att);
-  if (!fused || p.tmode != 0) { p.xa_f16 = false; return CFD_OK; }
+  if (p.path.xattn == XATTN_THREE || p.tmode != 0) return CFD_OK;
   const int T = p.T;
   if (c->w->b_tab.bytes < (size_t)T * CFD_D * 4 || c->w->b_sp.bytes < (size_t)T * CFD_D * 4 || c->w->bsq.bytes < (size_t)T * 4)
     c->w->tt_mem_mask = 0;       // (a table that is reallocated is an empty one)
@@ -535,7 +529,7 @@ int prepare_static_memside(Ctx* c, hipStream_t st, int dynamic_mask, bool want_a
     c->setup_launches += 1;
   }
   for (int j = 0; j < CFD_NMEM; ++j) {
-    if ((dynamic_mask >> j) & 1) continue;
+    if (!((p.path.static_mask >> j) & 1)) continue;
     const int rows = p.U[j] * p.Sp[j];
     const int NK = nl * CFD_D + 32;
     CHK(c->w->ca[j].ensure((size_t)rows * nl * 4));
@@ -571,12 +565,10 @@ int prepare_static_memside(Ctx* c, hipStream_t st, int dynamic_mask, bool want_a
       c->w->tt_mem_mask |= 1 << j;
       c->setup_launches += 2;
     }
-    p.static_mask |= 1 << j;
   }
-  if (p.xa_f16 && (p.rt || p.static_mask != (1 << CFD_NMEM) - 1)) p.xa_f16 = false;   // (single-fp16 tiles: every memory static, tile kernels)
-  if (p.xa_f16) {   // this run's operand policy: the key / value tiles of the fused cross-attention as single fp16, packed tile by tile
+  if (p.path.xa_inst == XA_INST_F16) {   // this run's operand policy: the key / value tiles of the fused cross-attention as single fp16, packed tile by tile
     for (int j = 0; j < CFD_NMEM; ++j) {
-      if (!((p.xa_f16_mask >> j) & 1)) continue;   // (short memories keep pairs: xattn_fused.hpp, F16)
+      if (!((p.path.f16_mask >> j) & 1)) continue;   // (short memories keep pairs: xattn_fused.hpp, F16)
       const long long tiles = (long long)nl * p.U[j] * (p.Sp[j] / XA_KEYS), chunks = tiles * 2048;
       CHK(c->w->v16[j].ensure((size_t)tiles * 32768));
       LAUNCH(CFD_PROF_ROWS, xa_pack16_kernel<>, dim3((unsigned)((chunks + 255) / 256)), dim3(256), st, c->w->vt_all[j].as<char>(), c->w->v16[j].as<char>(), chunks, p.Sp[j], 0);
@@ -584,14 +576,14 @@ int prepare_static_memside(Ctx* c, hipStream_t st, int dynamic_mask, bool want_a
       LAUNCH(CFD_PROF_ROWS, xa_pack16_kernel<>, dim3((unsigned)((chunks + 255) / 256)), dim3(256), st, c->w->kall_sp[j].as<char>(), c->w->k16[j].as<char>(), chunks, p.Sp[j], 1);
     }
   }
-  if (p.xa_one >= 0 && !p.rt) {   // the one-key memory's value rows as float32 vectors (xattn_fused.hpp, XAttnArgs::one_va).  Also with `reuse`:
+  if (p.xa_one >= 0 && !p.path.rt) {   // the one-key memory's value rows as float32 vectors (xattn_fused.hpp, XAttnArgs::one_va).  Also with `reuse`:
                                   // the previous forward of these memories may have had another L or the row-tile path and never made them (one tiny launch)
     const int j = p.xa_one;
     const long long n = (long long)nl * p.U[j] * CFD_D;
     CHK(c->w->xa_one_va.ensure((size_t)n * 4));
     LAUNCH(CFD_PROF_ROWS, one_key_va_kernel<>, dim3((unsigned)((n + 255) / 256)), dim3(256), st, c->w->vt_all[j].as<char>(), n, p.Sp[j], c->w->xa_one_va.as<float>());
   }
-  if (p.rt) {   // per-key scale and key bias of every step of the run (the tile-kernel path makes one step's per iteration: mem_scale_all_kernel)
+  if (p.path.rt) {   // per-key scale and key bias of every step of the run (the tile-kernel path makes one step's per iteration: mem_scale_all_kernel)
     for (int j = 0; j < CFD_NMEM; ++j) {
       const long long rows = (long long)p.U[j] * p.Sp[j];
       CHK(c->w->rt_cbt[j].ensure((size_t)T * (nl + 1) * rows * 4));
@@ -606,9 +598,9 @@ int prepare_static_memside(Ctx* c, hipStream_t st, int dynamic_mask, bool want_a
 // memory-side work of one forward, in front of its token-side launches (enqueue_rows)
 int enqueue_memside(Ctx* c, hipStream_t st) {
   const Problem& p = c->w->pb;
-  if (p.rt) return CFD_OK;   // every memory is static and its per-step scalars are tabulated (prepare_static_memside)
+  if (p.path.rt) return CFD_OK;   // every memory is static and its per-step scalars are tabulated (prepare_static_memside)
   const int nl = c->nl;
-  const int* dstep = p.tmode ? c->w->d_step.as<int>() + 1 : c->w->d_step.as<int>();
+  const int* dstep = c->w->d_step.as<int>() + p.path.dstep_slot;
   const dim3 blk(256);
   // memories whose projections were made once for the run: this step's per-key scale and key bias
   {
@@ -616,7 +608,7 @@ int enqueue_memside(Ctx* c, hipStream_t st) {
     memset(&g, 0, sizeof(g));
     int nwg = 0;
     for (int j = 0; j < CFD_NMEM; ++j) {
-      if (!((p.static_mask >> j) & 1)) continue;
+      if (!((p.path.static_mask >> j) & 1)) continue;
       const long long rows = (long long)p.U[j] * p.Sp[j];
       const int NK = nl * CFD_D + 32;
       g.m[g.n] = MemScaleArgs{c->w->n_sp[j].as<char>(), c->w->asq[j].as<float>(), rows, c->w->b_tab.as<float>(), c->w->bsq.as<float>(), c->w->ca[j].as<float>(),
@@ -631,7 +623,7 @@ int enqueue_memside(Ctx* c, hipStream_t st) {
   }
   // 2. memories: + temb + condition id + PE, normalise           (denoiser.py:223-261,332-353)
   for (int j = 0; j < CFD_NMEM; ++j) {
-    if ((p.static_mask >> j) & 1) continue;
+    if ((p.path.static_mask >> j) & 1) continue;
     const long long rows = (long long)p.U[j] * p.Sp[j];
     if (p.tmode == 2) {   // a level batch: distinct memory u % lv_U at the timestep of level u / lv_U
       MemPrepLevelArgs la{p.mem[j], p.lv_U[j], p.U[j], p.S[j], p.Sp[j], c->w->temb_tab.as<float>(), p.lv_i0,
@@ -645,7 +637,7 @@ int enqueue_memside(Ctx* c, hipStream_t st) {
   }
   // 3. memory-side projections for ALL layers at once: folded keys (+ key bias) and folded values^T
   for (int j = 0; j < CFD_NMEM; ++j) {
-    if ((p.static_mask >> j) & 1) continue;
+    if ((p.path.static_mask >> j) & 1) continue;
     c->memside_in_forward = true;   // these epilogues count into the handle's census: whoever waits for this stream next reads it
     CHK(enqueue_mem_kv(c, st, j, c->w->cb[j].as<float>()));
   }

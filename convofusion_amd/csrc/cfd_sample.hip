@@ -218,20 +218,6 @@ static int enqueue_loop_iteration(Ctx* c, hipStream_t st) {
   });
 }
 
-// A memory's row map on the host (`rows` = G * B entries): the caller's map downloaded, or the identity for a memory without one (it then
-// has one instance per row).  The entries are not range-checked here: level_batch_memories checks them for a level batch; a sampling
-// run's (cfd_sample_begin and its kin) never were at this point -- setup_problem checks the maps it is given.
-static int host_row_map(const cfd_memory& mem, int rows, const char* name, std::vector<int>& out) {
-  out.resize((size_t)rows);
-  if (mem.row_map) {
-    HIPCHK(hipMemcpy(out.data(), mem.row_map, (size_t)rows * 4, hipMemcpyDeviceToHost));
-    return CFD_OK;
-  }
-  if (mem.U != rows) return fail(CFD_E_ARG, "memory %s: U = %d != G * B = %d without a row_map", name, mem.U, rows);
-  for (int r = 0; r < rows; ++r) out[r] = r;
-  return CFD_OK;
-}
-
 // What every set-up starts with: the device, no forward hints, the census an earlier call deferred
 static int setup_preamble(Ctx* c) {
   HIPCHK(hipSetDevice(c->cfg.device));
@@ -272,18 +258,17 @@ static int upload_run_tables(Ctx* c, const cfd_sample_args& s, int N, int k0, hi
   HIPCHK(hipMemsetAsync(c->w->d_step.p, 0, 16, st));
   CHK(sat_begin(c, st));
   CHK(build_time_tables(c, ts.data(), N, st));   // (a run over the same table finds them built)
-  CHK(prepare_static_memside(c, st, s.dynamic_memory_mask, false));
+  CHK(prepare_static_memside(c, st));
   HIPCHK(hipStreamSynchronize(st));
   if (coef_out) coef_out->swap(coef);
   return CFD_OK;
 }
 
 // Chunks of a weighted run (cfd_sample_begin_weighted): uploads the weight table, decides which chunks are evaluated (prune: every chunk
-// k >= 1 whose column is 0 throughout is not, except the last one when the run keeps its attention maps) and compacts the memories' row
-// maps to the evaluated chunks, in the caller's order (a memory without a map gets the identity map first).  keep_idx[k]: the compacted
-// index of chunk k, or -1.  c->run.args.G becomes the number of evaluated chunks.
-static int weighted_chunks(Ctx* c, const float* wtab, int prune, int N, bool keep_last, cfd_memory mem_in[CFD_NMEM], int keep_idx[8],
-                           hipStream_t st) {
+// k >= 1 whose column is 0 throughout is not, except the last one when the run keeps its attention maps) and compacts the host copy of
+// the memories' row maps (G * B entries each) to the evaluated chunks, in the caller's order.  keep_idx[k]: the compacted index of chunk
+// k, or -1.  c->run.args.G becomes the number of evaluated chunks.
+static int weighted_chunks(Ctx* c, const float* wtab, int prune, int N, bool keep_last, HostMaps& hm, int keep_idx[8], hipStream_t st) {
   const cfd_sample_args& s = c->run.args;
   const int B = s.B, G = s.G;
   const size_t n = (size_t)N * B * 8;
@@ -302,16 +287,11 @@ static int weighted_chunks(Ctx* c, const float* wtab, int prune, int N, bool kee
   HIPCHK(hipStreamSynchronize(st));   // (the caller's host table is not kept beyond the call)
   c->run.args.G = ge;
   if (ge == G) return CFD_OK;
-  const int Be = G * B, Bc = ge * B;
-  std::vector<int> hm, cm(Bc);
-  for (int j = 0; j < CFD_NMEM; ++j) {
-    CHK(host_row_map(mem_in[j], Be, MEM_NAMES[j], hm));
+  for (std::vector<int>& m : hm.m) {   // (keep_idx[k] <= k: in place)
     for (int k = 0; k < G; ++k)
       if (keep_idx[k] >= 0)
-        for (int u = 0; u < B; ++u) cm[(size_t)keep_idx[k] * B + u] = hm[(size_t)k * B + u];
-    CHK(c->run.perm_map[j].ensure((size_t)Be * 4));
-    HIPCHK(hipMemcpy(c->run.perm_map[j].p, cm.data(), (size_t)Bc * 4, hipMemcpyHostToDevice));
-    mem_in[j].row_map = c->run.perm_map[j].as<int32_t>();
+        for (int u = 0; u < B; ++u) m[(size_t)keep_idx[k] * B + u] = m[(size_t)k * B + u];
+    m.resize((size_t)ge * B);
   }
   return CFD_OK;
 }
@@ -357,6 +337,8 @@ struct BeginState {
   std::vector<uint8_t> hkeep; // the keep mask and the tie table on the host, validated (empty: none given)
   std::vector<int32_t> htie;
   cfd_memory mem_in[CFD_NMEM];
+  HostMaps hm;                // the memories' row maps on the host: fetched once (select_chunks), compacted and permuted here, uploaded once
+  bool maps_new = false;      // ... they are no longer the caller's: setup_run_problem uploads them (SampleRun::perm_map)
   int keep_idx[8];            // weighted run: the compacted index of chunk k, or -1
 };
 
@@ -446,7 +428,9 @@ static int select_chunks(BeginState& r) {
   c->run.iters = r.N;
   for (int k = 0; k < 8; ++k) c->run.chunk_pos[k] = k;
   for (int j = 0; j < CFD_NMEM; ++j) r.mem_in[j] = s.mem[j];
-  if (r.x.weights) CHK(weighted_chunks(c, r.x.weights, r.x.prune, r.N, r.n_ring != 0, r.mem_in, r.keep_idx, r.st));
+  CHK(fetch_row_maps(r.mem_in, c->run.args.G * s.B, r.x.weights ? "G * B" : "Be", r.hm));
+  if (r.x.weights) CHK(weighted_chunks(c, r.x.weights, r.x.prune, r.N, r.n_ring != 0, r.hm, r.keep_idx, r.st));
+  r.maps_new = c->run.args.G != s.G && r.x.weights;
   return CFD_OK;
 }
 
@@ -457,12 +441,11 @@ static int permute_chunks(BeginState& r) {
   bool all_maps = c->permute && G > 2;
   int jb = 0;
   for (int j = 0; j < CFD_NMEM; ++j) {
-    if (!r.mem_in[j].row_map) all_maps = false;
+    if (!r.mem_in[j].row_map && !r.maps_new) all_maps = false;   // (a weighted run's compacted maps count as maps)
     if (r.s.mem[j].S > r.s.mem[jb].S) jb = j;
   }
   if (!all_maps) return CFD_OK;
-  std::vector<int> hm;
-  CHK(host_row_map(r.mem_in[jb], Be, MEM_NAMES[jb], hm));
+  const std::vector<int>& hm = r.hm.m[jb];
   std::vector<int> key(G);   // the shared memory index of a uniform chunk, or -1
   for (int g = 0; g < G; ++g) {
     key[g] = hm[(size_t)g * B];
@@ -483,29 +466,38 @@ static int permute_chunks(BeginState& r) {
   if (ident) return CFD_OK;
   for (int pnum = 0; pnum < G; ++pnum) c->run.chunk_pos[order[pnum]] = pnum;
   std::vector<int> pm(Be);
-  for (int j = 0; j < CFD_NMEM; ++j) {
-    CHK(host_row_map(r.mem_in[j], Be, MEM_NAMES[j], hm));
+  for (std::vector<int>& m : r.hm.m) {
     for (int pnum = 0; pnum < G; ++pnum)
-      for (int u = 0; u < B; ++u) pm[(size_t)pnum * B + u] = hm[(size_t)order[pnum] * B + u];
-    CHK(c->run.perm_map[j].ensure((size_t)Be * 4));
-    HIPCHK(hipMemcpy(c->run.perm_map[j].p, pm.data(), (size_t)Be * 4, hipMemcpyHostToDevice));
-    r.mem_in[j].row_map = c->run.perm_map[j].as<int32_t>();
+      for (int u = 0; u < B; ++u) pm[(size_t)pnum * B + u] = m[(size_t)order[pnum] * B + u];
+    m = pm;
+  }
+  r.maps_new = true;
+  return CFD_OK;
+}
+
+// The run's row maps on the device where the stages above changed them, each uploaded once
+static int upload_run_maps(Ctx* c, const HostMaps& hm, cfd_memory mem_in[CFD_NMEM]) {
+  for (int j = 0; j < CFD_NMEM; ++j) {
+    CHK(c->run.perm_map[j].ensure(hm.m[j].size() * 4));
+    HIPCHK(hipMemcpy(c->run.perm_map[j].p, hm.m[j].data(), hm.m[j].size() * 4, hipMemcpyHostToDevice));
+    mem_in[j].row_map = c->run.perm_map[j].as<int32_t>();
   }
   return CFD_OK;
 }
 
-// The problem of the run's forward.  Operand policy of the run (cfd_sample_args::operand_policy): single-fp16 key / value tiles of the
-// long memories for the fused cross-attention kernel -- only where that kernel runs on projections made once per run and keeps no maps;
-// want_f16 says so to setup_problem alone.
+// The problem of the run's forward, and everything the run asks of it (PathAsk, forward_path.hpp): the rows of an attention ring -- the
+// full-conditioning chunk's, at its position --, the memories rewritten between iterations, the operand policy (single-fp16 key / value
+// tiles of the long memories wanted) and that the batch is G replicas of the run's B rows (begin_step_kernel writes G identical copies).
 static int setup_run_problem(BeginState& r) {
   Ctx* c = r.c;
   const cfd_sample_args& s = r.s;
-  c->want_f16 = !r.n_ring && !s.dynamic_memory_mask && (c->xa_operands >= 0 ? c->xa_operands : (s.operand_policy & 15)) != 0;
-  const int r_setup = setup_problem(c, c->run.args.G * s.B, s.L, r.mem_in, nullptr, 0, r.N);
-  c->want_f16 = false;
-  CHK(r_setup);
-  if (c->share0 && c->run.args.G > 1) c->w->pb.share_B = s.B;   // begin_step_kernel writes G identical copies of the B rows
-  return CFD_OK;
+  if (r.maps_new) CHK(upload_run_maps(c, r.hm, r.mem_in));
+  PathAsk ask;
+  if (r.n_ring) { ask.ring_row0 = c->run.chunk_pos[c->run.args.G - 1] * s.B; ask.ring_rows = s.B; }
+  ask.dynamic_mask = s.dynamic_memory_mask;
+  ask.f16 = (c->xa_operands >= 0 ? c->xa_operands : (s.operand_policy & 15)) != 0;
+  ask.chunk_rows = s.B;
+  return setup_problem(c, c->run.args.G * s.B, s.L, r.mem_in, &r.hm, nullptr, ask, 0, r.N);
 }
 
 // The reference keeps att_mats of the full-conditioning chunk of EVERY iteration (convofusion.py:517-523).  On the row-tile path the
@@ -515,40 +507,28 @@ static int wire_att_ring(BeginState& r) {
   Ctx* c = r.c;
   const cfd_sample_args& s = r.s;
   Problem& pb = c->w->pb;
-  pb.att_nb = 0;
   if (!r.n_ring) return CFD_OK;
   // ... and on the tile kernels the fused cross-attention kernel has them in its softmax: its ATT instance keeps them, att_fixup_kernel
   // normalises them once per step (xattn_fused.hpp, XaAtt).  What cannot keep them: a run without the fused kernel (memories made per
   // step: dynamic memories; CFD_FUSED_XATTN=0).
-  const bool fused_ok = c->fused_xattn && pb.xa_nwg > 0;
-  if ((!pb.rt && !fused_ok) || s.dynamic_memory_mask)
+  if ((!pb.path.rt && !pb.path.keeps_maps()) || s.dynamic_memory_mask)
     return fail(CFD_E_SHAPE, "att_ring needs the row-tile path or the fused cross-attention kernel (one timestep per step, no dynamic memory): "
                              "this run has L = %d, %lld token rows; take the maps with one forward per iteration instead", s.L,
                 (long long)c->run.args.G * s.B * s.L);
-  pb.att_b0 = c->run.chunk_pos[c->run.args.G - 1] * s.B;
-  pb.att_nb = s.B;
   for (int j = 0; j < CFD_NMEM; ++j) {
     pb.att_slot[j] = (long long)s.B * c->nl * s.L * pb.S[j];
     // slot *d_step of the ring base: an edit run's d_step starts at k0 and executed iteration j goes to the caller's slot j
     pb.att[j] = s.att_ring[j] - (long long)r.k0 * pb.att_slot[j];
   }
-  if (!pb.rt) {
-    pb.att_fused = true;
-    CHK(setup_att_fused(c));
-    CHK(build_xattn_worklist(c, r.mem_in, true));   // (once more: the list now says which tiles keep their maps)
-    if (pb.xa_nwg <= 0) return fail(CFD_E_SHAPE, "att_ring: the fused cross-attention work list is empty");
-  }
   return CFD_OK;
 }
 
-// The rest of the operand policy's conditions (prepare_static_memside checks that every memory's projections are made once per run),
-// and the attention-concentration census (cfd_sample_args::census_tau): the same runs -- the others keep pairs anyway
-static int operand_policy_and_census(BeginState& r) {
+// The attention-concentration census (cfd_sample_args::census_tau): the runs of the fused kernel's pair and F16 instances on projections
+// made once per run -- the runs the operand policy is about
+static int attention_census(BeginState& r) {
   Ctx* c = r.c;
-  CHK(build_xattn_layer0_lists(c, r.mem_in));
-  Problem& pb = c->w->pb;
-  const bool fused_run = !pb.rt && c->fused_xattn && pb.xa_nwg > 0 && !pb.att_fused && !r.s.dynamic_memory_mask;
-  if (!fused_run) pb.xa_f16 = false;
+  const ForwardPath& path = c->w->pb.path;
+  const bool fused_run = path.xattn == XATTN_FUSED && !path.keeps_maps() && !r.s.dynamic_memory_mask;
   c->acen.tau = r.s.census_tau > 0.f ? r.s.census_tau : 0.f;
   c->acen.on = fused_run && c->acen.tau > 0.f;
   if (c->acen.on) CHK(c->acen.buf.ensure((size_t)c->nl * XA_CEN_SLOTS * XA_CEN_STRIDE * sizeof(unsigned)));
@@ -711,7 +691,7 @@ static int sample_begin(Ctx* c, const cfd_sample_args* args, void* stream, const
   }
   CHK(setup_run_problem(r));
   CHK(wire_att_ring(r));
-  CHK(operand_policy_and_census(r));
+  CHK(attention_census(r));
   CHK(upload_run_tables(c, r.s, r.N, r.k0, r.st));
   CHK(check_saturation(c, "cfd_sample_begin (memories / their once-per-run projections)"));
   CHK(init_latents_and_kind(r));
@@ -862,18 +842,16 @@ static int levels_per_batch_of(Ctx* c, const cfd_memory mem_in[CFD_NMEM], int R,
   return CFD_OK;
 }
 
-// The level batch's memories: instance lv * U + u = the caller's memory u at level lv, through level row maps (R rows per level, their
-// entries range-checked here); masks once per level
-static int level_batch_memories(Ctx* c, const cfd_memory mem_in[CFD_NMEM], int R, int J, cfd_memory vm[CFD_NMEM]) {
+// The level batch's memories: instance lv * U + u = the caller's memory u at level lv, through level row maps made from the host copy `hm`
+// of the caller's maps (R rows per level; hm becomes the level maps, J * R rows); masks once per level
+static int level_batch_memories(Ctx* c, const cfd_memory mem_in[CFD_NMEM], int R, int J, HostMaps& hm, cfd_memory vm[CFD_NMEM]) {
   const int Be = J * R;
-  std::vector<int> hm, lm((size_t)Be);
   for (int j = 0; j < CFD_NMEM; ++j) {
     const int U = mem_in[j].U;
-    CHK(host_row_map(mem_in[j], R, MEM_NAMES[j], hm));
-    for (int r = 0; r < R; ++r)
-      if (hm[r] < 0 || hm[r] >= U) return fail(CFD_E_ARG, "memory %s: row_map[%d] = %d outside [0, %d)", MEM_NAMES[j], r, hm[r], U);
-    for (int lv = 0; lv < J; ++lv)
-      for (int r = 0; r < R; ++r) lm[(size_t)lv * R + r] = lv * U + hm[r];
+    std::vector<int>& lm = hm.m[j];
+    lm.resize((size_t)Be);
+    for (int lv = 1; lv < J; ++lv)
+      for (int r = 0; r < R; ++r) lm[(size_t)lv * R + r] = lv * U + lm[r];
     CHK(c->lv_map[j].ensure((size_t)Be * 4));
     HIPCHK(hipMemcpy(c->lv_map[j].p, lm.data(), (size_t)Be * 4, hipMemcpyHostToDevice));
     vm[j] = mem_in[j];
@@ -907,14 +885,16 @@ static int level_batch_setup(Ctx* c, const cfd_sample_args& s, const char* who, 
   cfd_memory mem_in[CFD_NMEM], vm[CFD_NMEM];
   for (int j = 0; j < CFD_NMEM; ++j) mem_in[j] = s.mem[j];
   memset(lb, 0, sizeof(*lb));
+  HostMaps hm;
+  if (!wtab) trim_zero_weight_chunks(c, s);
+  CHK(fetch_row_maps(mem_in, c->run.args.G * s.B, "G * B", hm));
   if (wtab) {
     int keep_idx[8];
-    CHK(weighted_chunks(c, wtab, prune, N, false, mem_in, keep_idx, st));
+    CHK(weighted_chunks(c, wtab, prune, N, false, hm, keep_idx, st));
     for (int k = 0; k < 8; ++k) lb->g.pos[k] = keep_idx[k] >= 0 ? keep_idx[k] : 0;
     lb->g.Gc = 7;
     lb->g.wtab = c->run.wtab.as<float>();
   } else {
-    trim_zero_weight_chunks(c, s);
     for (int k = 0; k < 8; ++k) { lb->g.pos[k] = k < c->run.args.G ? k : 0; lb->g.w[k] = s.guidance_weight[k]; }
     lb->g.Gc = c->run.args.G;
   }
@@ -922,9 +902,8 @@ static int level_batch_setup(Ctx* c, const cfd_sample_args& s, const char* who, 
   lb->B = s.B; lb->L = s.L; lb->N = N; lb->Ge = c->run.args.G;
   const int R = lb->Ge * s.B;   // rows of a level
   CHK(levels_per_batch_of(c, mem_in, R, s.L, N, levels_per_batch, workspace_bytes, &lb->J));
-  CHK(level_batch_memories(c, mem_in, R, lb->J, vm));
-  c->want_f16 = false;   // (operands are split pairs throughout)
-  CHK(setup_problem(c, lb->J * R, s.L, vm, nullptr, 2, N));
+  CHK(level_batch_memories(c, mem_in, R, lb->J, hm, vm));
+  CHK(setup_problem(c, lb->J * R, s.L, vm, &hm, nullptr, PathAsk{}, 2, N));   // (operands are split pairs throughout)
   Problem& pb = c->w->pb;
   pb.lv_rows = R;
   pb.lv_i0 = 0;

@@ -304,7 +304,7 @@ extern "C" int cfd_weg_eval(cfd_handle c, const cfd_weg_args* a, float* losses, 
 
 // ---- cfd_denoise_vjp: d_out^T . d(out)/d(sample) of one denoiser forward on the row-tile kernels --------------------------------
 // Every refusal, before anything is touched; the row maps come back as the host sees them (part of what the problem is prepared for).
-static int check_vjp_args(Ctx* c, const cfd_vjp_args* a, const float* d_out, const float* grad, std::vector<long long>* maps) {
+static int check_vjp_args(Ctx* c, const cfd_vjp_args* a, const float* d_out, const float* grad, std::vector<long long>* maps, HostMaps* hm) {
   if (!c || !a || !a->sample || !d_out || !grad) return fail(CFD_E_ARG, "null argument");
   if (!c->finalized) return fail(CFD_E_STATE, "weights not finalized");
   const int Be = a->Be, L = a->L;
@@ -327,24 +327,20 @@ static int check_vjp_args(Ctx* c, const cfd_vjp_args* a, const float* d_out, con
     return fail(CFD_E_ARG, "cfd_denoise_vjp: %d padded keys of the five memories together exceed RT_MAX_KEYS = %d", wegrt::padded_keys(a->mem), RT_MAX_KEYS);
   if (c->weg.rt.stop) return fail(CFD_E_STATE, "cfd_debug_weg_stop is set: it names a launch of cfd_weg_eval's sweep");
   HIPCHK(hipSetDevice(c->cfg.device));
-  std::vector<int32_t> hm(Be);
+  CHK(fetch_row_maps(a->mem, Be, "Be", *hm));
   for (int j = 0; j < CFD_NMEM; ++j) {
     const cfd_memory& m = a->mem[j];
     maps->push_back(m.U);
     maps->push_back((long long)(size_t)m.row_map);
-    if (!m.row_map) continue;
-    HIPCHK(hipMemcpy(hm.data(), m.row_map, (size_t)Be * 4, hipMemcpyDeviceToHost));
-    for (int b = 0; b < Be; ++b) {
-      if (hm[b] < 0 || hm[b] >= m.U) return fail(CFD_E_ARG, "memory %s: row_map[%d] = %d outside [0, %d)", MEM_NAMES[j], b, hm[b], m.U);
-      maps->push_back(hm[b]);
-    }
+    if (m.row_map) maps->insert(maps->end(), hm->m[j].begin(), hm->m[j].end());
   }
   return CFD_OK;
 }
 
 extern "C" int cfd_denoise_vjp(cfd_handle c, const cfd_vjp_args* a, const float* d_out, float* out, float* grad, void* stream) {
   std::vector<long long> maps;
-  CHK(check_vjp_args(c, a, d_out, grad, &maps));
+  HostMaps hm;
+  CHK(check_vjp_args(c, a, d_out, grad, &maps, &hm));
   c->hint_now = c->hint_same_mem = false;
   CHK(settle_deferred_census(c));
   WegState& w = c->weg;
@@ -358,7 +354,7 @@ extern "C" int cfd_denoise_vjp(cfd_handle c, const cfd_vjp_args* a, const float*
   w.sig.clear();
   for (WegState::Graph& g : w.graph)
     if (g.gx.exec) { HIPCHK(hipStreamSynchronize(st)); g.reset(); }
-  CHK(wegrt::prepare(c, wegrt::FOR_VJP, a->Be, a->L, a->mem, 1, st, maps));
+  CHK(wegrt::prepare(c, wegrt::FOR_VJP, a->Be, a->L, a->mem, 1, st, maps, &hm));
   w.rt.T = 1;
   w.t_host = a->timestep;
   w.dstep_host = 0;

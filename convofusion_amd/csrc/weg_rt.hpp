@@ -34,8 +34,9 @@ enum { FOR_WEG = 0, FOR_VJP = 1 };
 // (Re)build the evaluation's problem and arena when the caller, shapes or pointers change.  Host work only (allocations, row maps):
 // never captured.  B rows of L tokens; `more`: what else of the caller's arguments the problem depends on (cfd_denoise_vjp: the
 // instance counts and row maps).  FOR_WEG keeps the text maps (att) for the objective; FOR_VJP keeps none, runs the whole network and
-// leaves d_att zero: the sweep's kernels add it to the text memory's dP as they are.
-static int prepare(Ctx* c, int who, int B, int L, const cfd_memory* mem_in, int T, hipStream_t st, const std::vector<long long>& more = {}) {
+// leaves d_att zero: the sweep's kernels add it to the text memory's dP as they are.  maps: the host copy of the row maps, or null.
+static int prepare(Ctx* c, int who, int B, int L, const cfd_memory* mem_in, int T, hipStream_t st, const std::vector<long long>& more = {},
+                   const HostMaps* maps = nullptr) {
   WegRtState& s = c->weg.rt;
   const int nl = c->nl, spt = padded_keys(mem_in);
   std::vector<long long> sig = {who, B, L, nl, T};
@@ -75,13 +76,15 @@ static int prepare(Ctx* c, int who, int B, int L, const cfd_memory* mem_in, int 
     cfd_memory mem[CFD_NMEM];
     float* att[CFD_NMEM] = {nullptr, nullptr, who == FOR_WEG ? s.att : nullptr, nullptr, nullptr};
     for (int j = 0; j < CFD_NMEM; ++j) mem[j] = mem_in[j];
-    CHK(setup_problem(c, B, L, mem, att, 0, T));
+    PathAsk ask;
+    ask.att_out = who == FOR_WEG;
+    CHK(setup_problem(c, B, L, mem, maps, att, ask, 0, T));
     if (T > 1) {   // full tables: row t belongs to timestep t
       std::vector<int32_t> iota(T);
       for (int t = 0; t < T; ++t) iota[t] = t;
       HIPCHK(hipMemcpy(c->w->trows.p, iota.data(), (size_t)T * 4, hipMemcpyHostToDevice));
     }
-    if (!c->w->pb.rt) return fail(CFD_E_STATE, "row-tile evaluation: the problem does not qualify for the row-tile path");
+    if (!c->w->pb.path.rt) return fail(CFD_E_STATE, "row-tile evaluation: the problem does not qualify for the row-tile path");
   }
   s.sig = sig;
   return CFD_OK;
@@ -124,8 +127,8 @@ static int enqueue_memory_side(Ctx* c, hipStream_t st) {
   w->tt_key.clear();     // (this workspace's timestep-only tables are rebuilt from w->trows, whatever they held: cfd_problem.hip, build_time_tables)
   w->tt_mem_mask = 0;
   CHK(enqueue_time_tables(c, w->pb.T, st));      // one row: the timestep index is in w->trows (copied in front of the launch sequence); full tables: row t = timestep t
-  CHK(prepare_static_memside(c, st, 0, true));
-  if (!w->pb.rt) return fail(CFD_E_STATE, "row-tile WEG evaluation lost its path");
+  CHK(prepare_static_memside(c, st));
+  if (!w->pb.path.rt) return fail(CFD_E_STATE, "row-tile WEG evaluation lost its path");
   c->weg.rt.launches += memory_side_launches(c->nl);
   return CFD_OK;
 }

@@ -127,7 +127,6 @@ extern "C" int cfd_debug_read(cfd_handle c, const char* what, float* dst_dev, si
   else if (!strcmp(what, "ss")) b = &c->w->ss_tab;
   else if (!strcmp(what, "eps")) b = &c->w->eps;
   else if (!strcmp(what, "sc")) b = &c->w->sc;
-  else if (!strcmp(what, "ssc")) b = &c->w->ssc;
   else if (!strcmp(what, "xa_stamps")) b = &c->w->xa_stamps;
   else return fail(CFD_E_ARG, "unknown buffer '%s'", what);
   if (numel * 4 > b->bytes) return fail(CFD_E_ARG, "buffer '%s' holds %zu bytes, asked for %zu", what, b->bytes, numel * 4);

@@ -13,27 +13,54 @@ int enqueue_denoise(Ctx* c, hipStream_t st) {
   return enqueue_rows(c, st);
 }
 
-// This step's rows of per-step tables for a sampling run: ONE launch at the start of the iteration copies row *dstep of every listed table
-// to a fixed place in rt_cur (64-float4 granules, in list order) and every `now` -- a table's base -- is redirected to its copy, so that no
-// launch of the iteration has the step index as a dependent scalar load in front of its operand loads.
+// This step's rows of the per-step tables: Work::now_* point at the tables themselves (one table row: cfd_forward, the WEG evaluation;
+// per-row timesteps and level batches, whose launches take the step index), or -- a sampling run with one timestep for all rows -- ONE
+// launch at the start of the iteration copies row *dstep of every listed table to a fixed place in rt_cur (64-float4 granules, in list
+// order) and redirects its `now` to the copy, so that no launch of the iteration has the step index as a dependent scalar load in front
+// of its operand loads (a load that misses in every XCD's L2 after the previous iteration's last workgroup has written it: ~1 us on 18
+// AdaLN launches and 9 cross-attention prologues per step).  The list: the AdaLN rows, A b / VV b of the memories whose projections
+// are made once, the row-tile path's key tables.
 struct StepTab { const float** now; int nfloat; };
-static int refresh_step_rows(Ctx* c, hipStream_t st, const int* dstep, const std::vector<StepTab>& tabs) {
-  if (tabs.size() > RT_NTAB) return fail(CFD_E_ARG, "%d per-step tables, rt_step_rows_kernel takes %d", (int)tabs.size(), RT_NTAB);
-  auto granules = [](const StepTab& t) { return (size_t)(t.nfloat / 4 + 63) / 64 * 64; };
+static std::vector<StepTab> step_tabs(Ctx* c) {
+  Work* w = c->w;
+  const Problem& p = w->pb;
+  const int nl = c->nl;
+  std::vector<StepTab> tabs{{&w->now_ss, nl * 4 * CFD_D}};
+  for (int j = 0; j < CFD_NMEM; ++j) {
+    if ((p.path.static_mask >> j) & 1) { tabs.push_back({&w->now_kb[j], nl * CFD_D + 32}); tabs.push_back({&w->now_vb[j], nl * CFD_D}); }
+    if (p.path.rt) tabs.push_back({&w->now_cbt[j], (nl + 1) * p.U[j] * p.Sp[j]});
+  }
+  return tabs;
+}
+static size_t step_granules(const StepTab& t) { return (size_t)(t.nfloat / 4 + 63) / 64 * 64; }
+
+size_t step_rows_bytes(Ctx* c) {
+  if (!c->w->pb.path.rows_now || c->w->pb.T <= 1) return 0;
   size_t off4 = 0;
-  for (const StepTab& t : tabs) off4 += granules(t);
-  CHK(c->w->rt_cur.ensure(off4 * 16));
+  for (const StepTab& t : step_tabs(c)) off4 += step_granules(t);
+  return off4 * 16;
+}
+
+static int refresh_step_rows(Ctx* c, hipStream_t st) {
+  Work* w = c->w;
+  w->now_ss = w->ss_tab.as<float>();
+  for (int j = 0; j < CFD_NMEM; ++j) { w->now_kb[j] = w->kbtab[j].as<float>(); w->now_vb[j] = w->vbtab[j].as<float>(); w->now_cbt[j] = w->rt_cbt[j].as<float>(); }
+  const size_t bytes = step_rows_bytes(c);
+  if (!bytes) return CFD_OK;
+  const std::vector<StepTab> tabs = step_tabs(c);
+  if (tabs.size() > RT_NTAB) return fail(CFD_E_ARG, "%d per-step tables, rt_step_rows_kernel takes %d", (int)tabs.size(), RT_NTAB);
+  if (bytes > w->rt_cur.bytes) return fail(CFD_E_STATE, "rt_cur holds %zu bytes, this step's table rows take %zu", w->rt_cur.bytes, bytes);
   RtStepRowsArgs ra;
   memset(&ra, 0, sizeof(ra));
-  off4 = 0;
+  size_t off4 = 0;
   int nwg = 0;
   for (const StepTab& t : tabs) {
-    float* dst = c->w->rt_cur.as<float>() + off4 * 4;
+    float* dst = w->rt_cur.as<float>() + off4 * 4;
     ra.src[ra.ntab] = *t.now; ra.dst[ra.ntab] = dst; ra.n4[ra.ntab] = t.nfloat / 4; ra.first[ra.ntab] = nwg;
-    nwg += (t.nfloat / 4 + 255) / 256; off4 += granules(t); ++ra.ntab;
+    nwg += (t.nfloat / 4 + 255) / 256; off4 += step_granules(t); ++ra.ntab;
     *t.now = dst;
   }
-  ra.first[ra.ntab] = nwg; ra.d_step = dstep;
+  ra.first[ra.ntab] = nwg; ra.d_step = w->d_step.as<int>() + w->pb.path.dstep_slot;
   LAUNCH(CFD_PROF_OTHER, rt_step_rows_kernel<>, dim3(nwg), dim3(256), st, ra);
   return CFD_OK;
 }
@@ -46,7 +73,6 @@ static int refresh_step_rows(Ctx* c, hipStream_t st, const int* dstep, const std
 int enqueue_rows_rt(Ctx* c, hipStream_t st, const RtSave* sv) {
   const Problem& p = c->w->pb;
   const int nl = c->nl, L = p.L, tpr = (L + 15) / 16, ntile = p.Be * tpr;
-  const int* dstep = c->w->d_step.as<int>() + p.path.dstep_slot;
   const int lds_xpv = rt_xpv_lds(p.Sp_tot, p.Sp_tot <= 512 ? 512 : RT_MAX_KEYS);
 #define RT_SET_LDS(kernel, bytes) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes))
   static unsigned long long attr_done = 0;
@@ -73,20 +99,7 @@ int enqueue_rows_rt(Ctx* c, hipStream_t st, const RtSave* sv) {
   float* const xw = c->w->x.as<float>();
   float* const hw = c->w->h_sp.as<float>();   // (the tile-kernel path's LayerNorm output: same bytes, unused here)
   auto X = [&](int l, int k) -> float* { return sv ? sv->x[l][k] : ((k == 2 || k == 4) ? hw : xw); };
-  // This step's rows of the per-step tables.  One table row (cfd_forward, the WEG evaluation): the tables themselves.  A sampling
-  // run: their copies in rt_cur (refresh_step_rows).
-  const float* ss_now = c->w->ss_tab.as<float>();
-  const float *kb_now[CFD_NMEM], *vb_now[CFD_NMEM], *cbt_now[CFD_NMEM];
-  for (int j = 0; j < CFD_NMEM; ++j) { kb_now[j] = c->w->kbtab[j].as<float>(); vb_now[j] = c->w->vbtab[j].as<float>(); cbt_now[j] = c->w->rt_cbt[j].as<float>(); }
-  if (p.T > 1) {
-    std::vector<StepTab> tabs{{&ss_now, nl * 4 * CFD_D}};
-    for (int j = 0; j < CFD_NMEM; ++j) {
-      tabs.push_back({&kb_now[j], nl * CFD_D + 32}); tabs.push_back({&vb_now[j], nl * CFD_D}); tabs.push_back({&cbt_now[j], (nl + 1) * p.U[j] * p.Sp[j]});
-    }
-    CHK(refresh_step_rows(c, st, dstep, tabs));
-  }
-  c->w->now_ss = ss_now;
-  for (int j = 0; j < CFD_NMEM; ++j) { c->w->now_kb[j] = kb_now[j]; c->w->now_vb[j] = vb_now[j]; }
+  CHK(refresh_step_rows(c, st));   // Work::now_*: this step's rows of the per-step tables
   RtGemmArgs base;
   memset(&base, 0, sizeof(base));
   base.L = L; base.tpr = tpr;
@@ -113,7 +126,7 @@ int enqueue_rows_rt(Ctx* c, hipStream_t st, const RtSave* sv) {
   auto time_block = [&](const DBuf& w, const float* g, const float* b, const float* bias, int tbidx, const float* xin, float* xout) -> int {
     RtGemmArgs a = base;
     a.x = xin; a.xr = xin; a.xo = xout;
-    a.g = g; a.b = b; a.ss = ss_now + (size_t)tbidx * 2 * CFD_D; a.w = w.as<char>(); a.bias = bias;
+    a.g = g; a.b = b; a.ss = c->w->now_ss + (size_t)tbidx * 2 * CFD_D; a.w = w.as<char>(); a.bias = bias;
     if (nfb2) RT_LAUNCH(CFD_PROF_GEMM_TOKEN, RT_PRO_ADALN, RT_EPI_RESID, 512, CFD_D / 32, 2, CFD_D, a);
     else RT_LAUNCH(CFD_PROF_GEMM_TOKEN, RT_PRO_ADALN, RT_EPI_RESID, 512, CFD_D / 32, 1, CFD_D, a);
     return CFD_OK;
@@ -124,7 +137,7 @@ int enqueue_rows_rt(Ctx* c, hipStream_t st, const RtSave* sv) {
   int nkb = 0;
   for (int j = 0; j < CFD_NMEM; ++j) {
     xa.map[j] = p.map[j]; xa.rows[j] = p.U[j] * p.Sp[j]; xa.S[j] = p.S[j]; xa.Sp[j] = p.Sp[j]; xa.off[j] = p.off[j];
-    xa.cbt[j] = cbt_now[j]; xa.att[j] = p.att[j]; xa.att_slot[j] = p.att_slot[j];
+    xa.cbt[j] = c->w->now_cbt[j]; xa.att[j] = p.att[j]; xa.att_slot[j] = p.att_slot[j];
     memcpy(xa.inst[j], p.rt_inst[j], RT_ARG_ROWS);
     xa.blk0[j] = nkb; nkb += p.Sp[j] / 16;
   }
@@ -169,14 +182,14 @@ int enqueue_rows_rt(Ctx* c, hipStream_t st, const RtSave* sv) {
       RtXArgs a = xa;
       a.x = X(l, 2); a.xo = X(l, 3);
       a.sc = sv ? sv->sc[l] : c->w->sc.as<float>();
-      a.cst = sv ? sv->cst[l] : c->w->ssc.as<float>();   // (the tile-kernel path's self-attention score buffer: >= M x 32 float4, unused here)
+      a.cst = sv ? sv->cst[l] : c->w->rt_cst.as<float>();
       a.ln_g = w.ln2g; a.ln_b = w.ln2b; a.bias = w.cross_bias.as<float>(); a.layer = l;
       for (int j = 0; j < CFD_NMEM; ++j) {
         const size_t rows = (size_t)p.U[j] * p.Sp[j];
         a.K[j] = c->w->kall_sp[j].as<char>() + (size_t)l * rows * CFD_D * 4;
         a.VT[j] = c->w->vt_all[j].as<char>() + (size_t)l * rows * CFD_D * 4;
-        a.kb[j] = kb_now[j] + (size_t)l * CFD_D;
-        a.vb[j] = vb_now[j] + (size_t)l * CFD_D;
+        a.kb[j] = c->w->now_kb[j] + (size_t)l * CFD_D;
+        a.vb[j] = c->w->now_vb[j] + (size_t)l * CFD_D;
       }
       {
         Bracket br(c, CFD_PROF_XATTN, st);
@@ -244,22 +257,11 @@ int enqueue_rows(Ctx* c, hipStream_t st) {
     CHK((run_gemm<MODE_PLAIN>(c, CFD_PROF_GEMM_TOKEN, a, e, 1, 1, st)));
   }
   if (c->stop_stage == 1) return CFD_OK;
-  // This step's rows of the per-step tables (as on the row-tile path, enqueue_rows_rt): with one timestep for all rows, a sampling run
-  // reads their copies in rt_cur (refresh_step_rows) and cfd_forward points at its single table row, so that no launch has the step
-  // index as a dependent scalar load in front of its operand loads (a load that misses in every XCD's L2 after the previous
-  // iteration's last workgroup has written it: ~1 us on 18 AdaLN launches and 9 cross-attention prologues per step).
-  const float* ss_now = c->w->ss_tab.as<float>();
-  const float *kb_now[CFD_NMEM], *vb_now[CFD_NMEM];
-  for (int j = 0; j < CFD_NMEM; ++j) { kb_now[j] = c->w->kbtab[j].as<float>(); vb_now[j] = c->w->vbtab[j].as<float>(); }
+  // Work::now_*: this step's rows of the per-step tables; with path.rows_now no launch takes the step index
+  CHK(refresh_step_rows(c, st));
   const bool rows_now = p.path.rows_now;
-  if (rows_now && p.T > 1) {
-    std::vector<StepTab> tabs{{&ss_now, nl * 4 * CFD_D}};
-    for (int j = 0; j < CFD_NMEM; ++j)
-      if ((p.path.static_mask >> j) & 1) { tabs.push_back({&kb_now[j], nl * CFD_D + 32}); tabs.push_back({&vb_now[j], nl * CFD_D}); }
-    CHK(refresh_step_rows(c, st, dstep, tabs));
-  }
   auto ln = [&](const float* g, const float* b, int adaln, int tbidx, char* out, long long rows) -> int {
-    LnArgs a{c->w->x.as<float>(), out, rows, g, b, adaln, (rows_now ? ss_now : c->w->ss_tab.as<float>()) + (size_t)tbidx * 2 * CFD_D,
+    LnArgs a{c->w->x.as<float>(), out, rows, g, b, adaln, c->w->now_ss + (size_t)tbidx * 2 * CFD_D,
              (long long)nl * 2 * 2 * CFD_D, rows_now ? nullptr : dstep, p.tmode, p.tmode == 2 ? L * p.lv_rows : L,
              p.tmode == 2 ? p.lv_i0 : 0};   // (a level batch: table row lv_i0 + level, Problem::lv_rows rows per level)
     LAUNCH(CFD_PROF_ROWS, ln_rows_kernel<>, dim3((unsigned)((rows + 3) / 4)), blk, st, a);
@@ -284,7 +286,6 @@ int enqueue_rows(Ctx* c, hipStream_t st) {
   // Range: the launches launch_gemm gives the 64 x 64 / 128 x 64 classes anyway (launch_gemm_midsize); above it a ln_rows launch costs less than
   // the producer's wider epilogue (measured at the headline shape: +25.8 us against 14).
   const bool ln_fold = p.path.ln_fold;
-  if (ln_fold) CHK(c->w->ln_stat.ensure((size_t)M * LN_SLOTS * 2 * 4));
   auto token_gemm_resid_stat = [&](const DBuf& w, int K, const char* y, const float* bias, long long rows, char* xs) -> int {
     GemmArgs a = gemm_args();
     gemm_x(a, 0, w.as<char>(), CFD_D, K, (long long)K * 4);
@@ -379,9 +380,9 @@ int enqueue_rows(Ctx* c, hipStream_t st) {
         a.Sp[j] = p.Sp[j];
         const bool stat = (p.path.static_mask >> j) & 1;
         a.rs_off[j] = (unsigned)((size_t)(nl - l) * rows * 4);
-        a.kb[j] = stat ? kb_now[j] + (size_t)l * CFD_D : c->w->zeros512.as<float>();
+        a.kb[j] = stat ? c->w->now_kb[j] + (size_t)l * CFD_D : c->w->zeros512.as<float>();
         a.kb_stride[j] = stat ? nl * CFD_D + 32 : 0;
-        a.vb[j] = stat ? vb_now[j] + (size_t)l * CFD_D : c->w->zeros512.as<float>();
+        a.vb[j] = stat ? c->w->now_vb[j] + (size_t)l * CFD_D : c->w->zeros512.as<float>();
         a.vb_stride[j] = stat ? nl * CFD_D : 0;
       }
       a.d_step = rows_now ? nullptr : dstep;

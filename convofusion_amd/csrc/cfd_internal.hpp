@@ -47,7 +47,7 @@ static_assert(FP_NMEM == CFD_NMEM, "forward_path.hpp counts the memories itself"
 // memories whose projections prepare_static_memside makes once.  Nothing changes the path after setup_problem.
 struct Problem {
   ForwardPath path;
-  int Be = 0, L = 0, Lp = 0;
+  int Be = 0, L = 0;
   long long M = 0;
   int U[CFD_NMEM], S[CFD_NMEM], Sp[CFD_NMEM], off[CFD_NMEM], Sp_tot = 0;
   const float* mem[CFD_NMEM];
@@ -78,7 +78,7 @@ struct Problem {
   // fused cross-attention (xattn_fused.hpp): workgroups of the work list, 0 = the list was not built
   int xa_nwg = 0;
   int xa0_nwg_a = 0, xa0_nwg_b = 0;   // layer-0 de-duplication lists (build_xattn_layer0_lists); 0: one launch
-  bool xa_flush = false;               // some work list flushes the accumulator between two online memories (XA_FLUSH): lock-step kernel only
+  bool xa_flush = false;               // some work list flushes the accumulator between two online memories (XA_FLUSH)
   int xa_one = -1;                     // the one-key memory the fused cross-attention adds as a vector (xattn_fused.hpp, XAttnArgs::one_j), or -1
   int xa_tpw = 0, xa_n16 = 0, xa_nseg = 0;   // of the work list (build_xattn_worklist): the most query tiles, XA_F16 segments and segments of a workgroup ("xa.info")
   // (path.static_mask: memories whose folded projections are computed once for the run from the centred static part of the memory,
@@ -141,12 +141,19 @@ struct WegState {
   void invalidate() { sig.clear(); }   // cfd_load_tensor: the next evaluation reuses no memory-side result
 };
 
-// One problem's device workspace: everything setup_problem / prepare_static_memside allocate and the launches of a forward touch.
+// One problem's device workspace: what the launches of a forward touch.  setup_problem sizes it at its end, from the problem's path
+// (buffers only grow: what an earlier problem's path needed stays); prepare_static_memside adds the once-per-run projections.
+//   every path                      x, h_sp, o_sp, u_sp, eps, sample_sp, qkv_sp, n_sp / kall_sp / cb / vt_all, temb_tab / h1_tab / ss_tab / trows
+//   path.xattn == XATTN_THREE       sc, p_sp (scores, probabilities)
+//   path.rt                         sc, p_sp (e_s, the keys' scales), rt_cst, rt_vt
+//   tile kernels at L == 16         vts_sp
+//   path.ln_fold                    ln_stat
+//   path.rows_now in a run (T > 1)  rt_cur
 struct Work {
   Problem pb;
   // qkv_sp: SP rows of q | k | v (1536 columns) on the tile kernels at L != 16; q | k (1024 columns) for batch rows of 16 tokens and on the
   // row-tile path, whose V^T per batch row lives in vts_sp / rt_vt
-  DBuf x, h_sp, qkv_sp, vts_sp, ssc, sp_sp, o_sp, u_sp, sc, p_sp, eps, sample_sp;
+  DBuf x, h_sp, qkv_sp, vts_sp, o_sp, u_sp, sc, p_sp, eps, sample_sp;
   DBuf ln_stat;                 // LayerNorm fold: per row 16 slots of (mean, M2) written by the producing residual product (EpiResidStat)
   DBuf n_sp[CFD_NMEM], kall_sp[CFD_NMEM], cb[CFD_NMEM], vt_all[CFD_NMEM];
   DBuf temb_tab, h1_tab, ss_tab, trows, iota, long_rows, short_rows, zero_mask;
@@ -163,19 +170,22 @@ struct Work {
   bool fwd_mask[CFD_NMEM] = {false, false, false, false, false}, fwd_map[CFD_NMEM] = {false, false, false, false, false};
   unsigned long long fwd_wver = 0;
   DBuf rt_vt, rt_cbt[CFD_NMEM];   // row-tile path: V^T of the self-attention, per-step key tables
-  DBuf k16[CFD_NMEM], v16[CFD_NMEM];   // single-fp16 key / value tiles of the static memories (xa_pack16_kernel), when pb.xa_f16 asks for them
-  DBuf rt_cur;                    // row-tile path, sampling run: this step's rows of every per-step table (rt_step_rows_kernel)
+  DBuf rt_cst;                    // row-tile path: the cross-attention's cell statistics, float4 [M][Sp_tot / 32] (rowtile.hpp, RtXArgs::cst)
+  DBuf k16[CFD_NMEM], v16[CFD_NMEM];   // single-fp16 key / value tiles of the static memories (xa_pack16_kernel), for the memories of path.f16_mask
+  DBuf rt_cur;                    // sampling run with one timestep for all rows: this step's rows of every per-step table (refresh_step_rows)
   // What the timestep-only tables of this workspace were built from: the table rows' timesteps and the weights' generation.  temb / AdaLN
   // rows (20 launches) and, per memory, A_l b_t / VV_l b_t (kbtab / vbtab: two products each) depend on nothing else, so a run that
   // finds them built for its own timestep list skips them (the rollout opens eleven 1000-step runs per sample, unbounded_synthesis.py:285-468).
   std::vector<int32_t> tt_key;
   long long tt_wver = -1;
   int tt_mem_mask = 0;            // bit j: kbtab[j] / vbtab[j] (and b_tab / b_sp / bsq) hold the products for tt_key
-  // row-tile path: where the launches of the current problem find this step's AdaLN rows and A b / VV b vectors (the tables themselves
-  // when they have one row, rt_cur otherwise); set by enqueue_rows_rt, read by the WEG reverse sweep (weg_rt.hpp)
+  // Where the launches of the current problem find this step's AdaLN rows, A b / VV b vectors and row-tile key tables (the tables
+  // themselves, or their rows' copies in rt_cur); set by refresh_step_rows at the start of a launch sequence, read by both sequences and
+  // the WEG reverse sweep (weg_rt.hpp)
   const float* now_ss = nullptr;
   const float* now_kb[CFD_NMEM] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   const float* now_vb[CFD_NMEM] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  const float* now_cbt[CFD_NMEM] = {nullptr, nullptr, nullptr, nullptr, nullptr};
 };
 
 // The kind of the open sampling run: which instances of begin_step_kernel / inpaint_now_kernel / cfg_step_kernel it launches
@@ -519,6 +529,7 @@ int enqueue_memside(Ctx* c, hipStream_t st);
 int enqueue_rows(Ctx* c, hipStream_t st);
 int enqueue_rows_rt(Ctx* c, hipStream_t st, const RtSave* sv = nullptr);
 int enqueue_denoise(Ctx* c, hipStream_t st);
+size_t step_rows_bytes(Ctx* c);   // what refresh_step_rows needs of Work::rt_cur for the current problem (0: its forwards refresh nothing)
 // cfd_sample.hip
 int enqueue_philox_fill(float* out, int B, int per_utt, uint64_t seed, uint32_t step, uint32_t utt0, uint32_t stream_id, float scale, hipStream_t st);
 // cfd_blocks.hip

@@ -23,9 +23,9 @@ struct XaRow {      // one row of a work list
 };
 
 static void make_xattn_worklist(const Problem& p, const std::vector<XaRow>& rows, int mem_mask, std::vector<XaWg>& wgs, std::vector<XaSeg>& segs,
-                                size_t& n_active, bool& has_flush) {
+                                bool& has_flush) {
   const int L = p.L, nqt = (L + 15) / 16;
-  wgs.clear(); segs.clear(); n_active = 0;
+  wgs.clear(); segs.clear();
   // memory order: long (online) memories first, longest first; then the single-tile ones
   int order[CFD_NMEM], n_mem = 0, n_online = 0;
   for (int j = 0; j < CFD_NMEM; ++j)
@@ -112,7 +112,6 @@ static void make_xattn_worklist(const Problem& p, const std::vector<XaRow>& rows
   wgs.assign(qlen * 8, idle);
   for (int x = 0; x < 8; ++x) {
     for (size_t i = 0; i < queue[x].size(); ++i) wgs[i * 8 + x] = queue[x][i];
-    n_active += queue[x].size();
   }
 }
 
@@ -173,8 +172,7 @@ static int build_xattn_worklist(Ctx* c, const HostMaps& maps, int dynamic_mask, 
   const int all_mems = ((1 << CFD_NMEM) - 1) & ~(p.xa_one >= 0 ? 1 << p.xa_one : 0);
   std::vector<XaWg> wgs;
   std::vector<XaSeg> segs;
-  size_t n_active = 0;
-  make_xattn_worklist(p, rows, all_mems, wgs, segs, n_active, p.xa_flush);
+  make_xattn_worklist(p, rows, all_mems, wgs, segs, p.xa_flush);
   if (wgs.empty() || segs.empty()) return CFD_OK;
   // (The list's length gate is part of path.xa_list, decide_forward_path.  What it was measured on: a handful of workgroups cannot hide
   // their serial walk over the key tiles -- 3 barriers and a fill round trip per 32 keys with nothing else on the chip.  Round 2 at the
@@ -183,7 +181,6 @@ static int build_xattn_worklist(Ctx* c, const HostMaps& maps, int dynamic_mask, 
   // workgroups, one shard of the product-shape benchmark) 470 against 465 steps/s.  Below 6 workgroups the three-launch path stays
   // (CFD_FUSED_XATTN_MIN_WGS overrides; the test suite sets 0 and runs its small cases through the fused kernel); counted in workgroups
   // of four query tiles, as measured -- the list itself may deal fewer tiles per workgroup: make_xattn_worklist.)
-  (void)n_active;
   CHK(upload_worklist(c->w->xa_wgs, c->w->xa_segs, wgs, segs));
   p.xa_nwg = (int)wgs.size();
   for (const XaWg& w : wgs) {   // (read-out only: "xa.info")
@@ -244,9 +241,8 @@ static int build_xattn_layer0_lists(Ctx* c, const HostMaps& maps) {
   }
   std::vector<XaWg> wa, wb;
   std::vector<XaSeg> sa, sb;
-  size_t na = 0, nb = 0;
-  make_xattn_worklist(p, ra, 1 << jg, wa, sa, na, p.xa_flush);
-  make_xattn_worklist(p, rb, ((1 << CFD_NMEM) - 1) & ~(1 << jg) & ~(p.xa_one >= 0 ? 1 << p.xa_one : 0), wb, sb, nb, p.xa_flush);
+  make_xattn_worklist(p, ra, 1 << jg, wa, sa, p.xa_flush);
+  make_xattn_worklist(p, rb, ((1 << CFD_NMEM) - 1) & ~(1 << jg) & ~(p.xa_one >= 0 ? 1 << p.xa_one : 0), wb, sb, p.xa_flush);
   if (wa.empty() || wb.empty()) return CFD_OK;
   CHK(upload_worklist(c->w->xa0_wgs_a, c->w->xa0_segs_a, wa, sa));
   CHK(upload_worklist(c->w->xa0_wgs_b, c->w->xa0_segs_b, wb, sb));
@@ -304,8 +300,8 @@ int setup_problem(Ctx* c, int Be, int L, const cfd_memory mem[CFD_NMEM], const H
   // ... and with the caller's promise that they ARE the same memories (cfd_forward_same_memories covers the row maps and masks), the work
   // lists and instance tables made from them -- several device-to-host reads per call -- are kept as well
   const bool keep_lists = prev_same && c->hint_now && c->w->fwd_L == L && c->w->fwd_att == ask.att_out;
-  p.Be = Be; p.L = L; p.Lp = (L + 31) / 32 * 32; p.M = (long long)Be * L; p.tmode = tmode; p.T = T;
-  if (p.Lp > SM_MAX_CHUNKS * 512) return fail(CFD_E_SHAPE, "L = %d exceeds the in-register softmax limit (%d)", L, SM_MAX_CHUNKS * 512);
+  p.Be = Be; p.L = L; p.M = (long long)Be * L; p.tmode = tmode; p.T = T;
+  if ((L + 31) / 32 * 32 > SM_MAX_CHUNKS * 512) return fail(CFD_E_SHAPE, "L = %d exceeds the in-register softmax limit (%d)", L, SM_MAX_CHUNKS * 512);
   int off = 0;
   for (int j = 0; j < CFD_NMEM; ++j) {
     const cfd_memory& m = mem[j];
@@ -340,7 +336,7 @@ int setup_problem(Ctx* c, int Be, int L, const cfd_memory mem[CFD_NMEM], const H
     maps = &fetched;
   }
   {  // memories without a key-padding mask get an all-zero one, so the softmax kernel needs no null test
-    size_t need = (size_t)Be * L;   // (the un-fused self-attention softmax indexes it per batch row)
+    size_t need = (size_t)Be * L;
     for (int j = 0; j < CFD_NMEM; ++j) need = std::max(need, (size_t)p.U[j] * p.S[j]);
     if (need > c->w->zero_mask.bytes) {
       CHK(c->w->zero_mask.ensure(need));
@@ -402,23 +398,30 @@ int setup_problem(Ctx* c, int Be, int L, const cfd_memory mem[CFD_NMEM], const H
     if (!one_dynamic) CHK(build_xattn_layer0_lists(c, *maps));
     if (p.path.keeps_maps()) CHK(setup_att_fused(c));
   }
+  // The workspace, sized for the path (the table on struct Work): no launch sequence allocates.  First what the path owns ...
+  const long long M = p.M;
+  const int nl = c->nl;
   if (p.path.rt) {
     CHK(c->w->rt_vt.ensure((size_t)Be * CFD_D * RT_MAX_L * 4));
     HIPCHK(hipMemset(c->w->rt_vt.p, 0, (size_t)Be * CFD_D * RT_MAX_L * 4));   // keys beyond L stay zero
+    // (float4 [token][Sp_tot / 32]: rt_xscore_kernel writes and rt_xpv_kernel reads the rows of tokens below M only)
+    CHK(c->w->rt_cst.ensure((size_t)M * (p.Sp_tot / 32) * 16));
+  } else if (L == 16) {
+    CHK(c->w->vts_sp.ensure((size_t)Be * CFD_D * 64 * 4));
   }
-  const long long M = p.M;
-  const int nl = c->nl;
+  if (p.path.rt || p.path.xattn == XATTN_THREE) {   // (a WEG evaluation redirects sc into its arena; it reads p_sp here)
+    CHK(c->w->sc.ensure((size_t)M * p.Sp_tot * 4));
+    CHK(c->w->p_sp.ensure((size_t)M * p.Sp_tot * 4));
+  }
+  if (p.path.ln_fold) CHK(c->w->ln_stat.ensure((size_t)M * LN_SLOTS * 2 * 4));
+  CHK(c->w->rt_cur.ensure(step_rows_bytes(c)));
+  // ... then what every path addresses
   CHK(c->w->x.ensure((size_t)M * CFD_D * 4));
   CHK(c->w->h_sp.ensure((size_t)M * CFD_D * 4));
   // q | k | v rows of the tile kernels' one projection launch; batch rows of 16 tokens and the row-tile path keep q | k rows + V^T per batch row
   CHK(c->w->qkv_sp.ensure((size_t)M * (L == 16 ? 2 : 3) * CFD_D * 4));
-  if (L == 16) CHK(c->w->vts_sp.ensure((size_t)Be * CFD_D * 64 * 4));
-  CHK(c->w->ssc.ensure((size_t)Be * CFD_NHEAD * L * p.Lp * 4));
-  CHK(c->w->sp_sp.ensure((size_t)Be * CFD_NHEAD * L * p.Lp * 4));
   CHK(c->w->o_sp.ensure((size_t)M * CFD_D * 4));
   CHK(c->w->u_sp.ensure((size_t)M * CFD_FF * 4));
-  CHK(c->w->sc.ensure((size_t)M * p.Sp_tot * 4));
-  CHK(c->w->p_sp.ensure((size_t)M * p.Sp_tot * 4));
   CHK(c->w->eps.ensure((size_t)M * CFD_LAT * 4));
   CHK(c->w->sample_sp.ensure((size_t)M * CFD_LAT * 4));
   for (int j = 0; j < CFD_NMEM; ++j) {

@@ -820,8 +820,10 @@ struct LevelBatch {
   Combine g;             // Gc: 7 for a weighted run, else Ge; wtab: dev [N][B][8] or null
 };
 
-// J, the levels of a batch: the caller's count, or what the workspace budget holds of what setup_problem allocates per level (token rows
-// and the memories' per-forward projections; an estimate, not an enforced cap); at most N, and at most 32768 batch rows (a launch's grid).
+// J, the levels of a batch: the caller's count, or the workspace budget divided by the budget's unit -- per_level, the bytes setup_problem
+// allocated per level when the default was measured (token rows, the memories' per-forward projections, and score buffers the workspace
+// no longer holds), not what is allocated today: the formula defines the default J, and with it the GEMM tile classes of the timings
+// below, so it stays as it is; an estimate, not an enforced cap.  At most N, and at most 32768 batch rows (a launch's grid).
 // (default 4 GiB: at the product shape ~150 levels for one utterance, ~40 for eight; measured 0.042 s at J = 100 against 0.059 s at
 //  J = 41 and 0.187 s at J = 40 against 0.279 s at J = 8 for N = 1000, profiles/r13_ddpm_inversion_time.json)
 static int levels_per_batch_of(Ctx* c, const cfd_memory mem_in[CFD_NMEM], int R, int L, int N, int levels_per_batch, size_t workspace_bytes,

@@ -488,17 +488,6 @@ __global__ void __launch_bounds__(256) softmax_bwd_f32_grouped_kernel(const Soft
 
 enum { EW_SILU = 0, EW_GELU = 1, EW_SILU_BWD = 2, EW_GELU_BWD = 3, EW_AXPY = 4, EW_ADD_BCAST = 5, EW_MODULATE = 6, EW_MODULATE_BWD = 7, EW_NOPS = 8 };
 
-// TimeBlock backward between its output projection and its LayerNorm in one pass: out = a * SiLU'(h) * (1 + e[d])
-// (h the modulated LayerNorm output kept by the forward, e the block's [scale | shift] row)
-template <int CFD_KI = 0>
-__global__ void __launch_bounds__(256) tb_bwd_f32_kernel(const float* a, const float* h, const float* e, float* out, long long n, int D) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const float y = h[i], sg = 1.0f / (1.0f + expf(-y));
-  out[i] = a[i] * (sg * (1.0f + y * (1.0f - sg))) * (1.0f + e[i % D]);
-}
-
-
 // Element-wise pieces of the forward / backward pass over a [R0][R1][D] tensor (index i -> d = i % D, r1 = (i / D) % R1,
 // r0 = i / (D R1)):
 //   SILU / GELU          out = act(a)                                  (nn.SiLU, exact-erf nn.GELU)

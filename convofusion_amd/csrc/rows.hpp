@@ -413,21 +413,6 @@ __global__ void __launch_bounds__(256) softmax_rows_kernel(const SoftmaxArgs a) 
   }
 }
 
-// Per-tile softmax statistics (EpiTileSoftmax) -> fold weights of the tile-relative P.V product:
-//   m = max_t m_t ;  l = sum_t l_t exp(m_t - m) ;  alpha_t = exp(m_t - m) / l
-// (a row whose keys are all masked gives 0 / 0 = NaN, as the reference's softmax does)
-template <int CFD_KI = 0>
-__global__ void attn_alpha_kernel(const float2* stats, float* alpha, long long rows, int ntiles) {
-  const long long row = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (row >= rows) return;
-  const float2* st = stats + row * ntiles;
-  float m = -INFINITY;
-  for (int t = 0; t < ntiles; ++t) m = fmaxf(m, st[t].x);
-  float l = 0.f;
-  for (int t = 0; t < ntiles; ++t) l += (st[t].x == -INFINITY) ? 0.f : st[t].y * __expf(st[t].x - m);
-  for (int t = 0; t < ntiles; ++t) alpha[row * ntiles + t] = (st[t].x == -INFINITY) ? 0.f / l : __expf(st[t].x - m) / l;
-}
-
 // ------------------------------------------------------------------------------------------------
 // fp32 [R][K] -> SP [R][K]   (K % 8 == 0); used for weights at load time
 // ------------------------------------------------------------------------------------------------

@@ -56,7 +56,8 @@ int cfd_test_gemm_epi(cfd_handle h, cfd_test_epi_args* args, void* stream);
 
 /* Test hooks: stop the forward pipeline after tap point `stage` (0 = off; 1 = after the latent embedding;
  * 2+4l / 3+4l / 4+4l / 5+4l = layer l after self-attention / time block 1 / cross-attention / the layer),
- * and read an internal float32 buffer ("x" residual stream [M][512], "temb", "ss", "eps", "sc", "ssc").
+ * and read an internal float32 buffer ("x" residual stream [M][512], "temb", "ss", "eps", "sc": the scores of
+ * the three-launch and row-tile cross-attention, which only those paths allocate).
  *   "xa.info"  [7]  the cross-attention of the last cfd_forward: the xattn_fused_kernel instance its layers launched (0: split pairs,
  *                   1: ATT, keeps the maps, 2: F16, single-fp16 tiles; -1: none -- the three-launch path, the row-tile path, or a stop
  *                   stage in front of the first block), then of its work list: workgroups (0: no list), the most query tiles of a

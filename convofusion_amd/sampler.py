@@ -599,22 +599,28 @@ class SamplingRun:
             pass
 
 
+def guidance_chunk_rows(encoder_hidden_states, cond_masks, chunks, G, B, row_maps=None):
+    """(memories, masks) of the guidance chunks ``chunks`` of a chunk-major guidance batch of G chunks x B utterances, in list order:
+    slices of the replicated batch, or -- with ``row_maps`` (``build_guidance_batch``) -- the distinct memories gathered through the
+    maps' rows c * B .. (c + 1) * B of every listed chunk.  A mask goes by its memory's index in ``_lib.MEM_NAMES``; None stays None."""
+    def rows(x, j):
+        if row_maps is not None:
+            return x.index_select(0, torch.cat([row_maps[j][c * B:(c + 1) * B] for c in chunks]).long().to(x.device))
+        parts = [x.chunk(G)[c] for c in chunks]
+        return parts[0] if len(parts) == 1 else torch.cat(parts)
+    return ([rows(e, j) for j, e in enumerate(encoder_hidden_states)],
+            {k: (rows(v, _lib.MEM_NAMES.index(k)) if v is not None else None) for k, v in (cond_masks or {}).items()})
+
+
 def last_step_attention(run, denoiser, timestep, encoder_hidden_states, cond_masks, guidance_chunks=CFG_CHUNKS, row_maps=None):
     """The attention maps the reference keeps from an iteration: ``att_mats`` of the LAST guidance chunk (full
     conditioning) of the denoiser call (convofusion.py:517-523, unbounded_synthesis.py:159-161) -- 5 tensors
     [B, layers, L, S_j].  Call it right before ``run.steps(1)`` of that iteration: the in-painting overwrite of the rollout
     is pulled in front (``run.inpaint``), the maps come from one extra forward of the B full-conditioning rows on the
     denoiser's second engine (the run owns the first), so a loop that skips the zero-weight chunk still returns them."""
-    B, G = run.B, guidance_chunks
     run.inpaint()
     lat = run.read()
-    if row_maps is not None:   # distinct memories + row maps: gather the last chunk's rows
-        idx = [m[(G - 1) * B:].long() for m in row_maps]
-        enc = [e.index_select(0, i.to(e.device)) for e, i in zip(encoder_hidden_states, idx)]
-        masks = {k: (v.index_select(0, idx[_lib.MEM_NAMES.index(k)].to(v.device)) if v is not None else None) for k, v in (cond_masks or {}).items()}
-    else:
-        enc = [e.chunk(G)[-1] for e in encoder_hidden_states]
-        masks = {k: (v.chunk(G)[-1] if v is not None else None) for k, v in (cond_masks or {}).items()}
+    enc, masks = guidance_chunk_rows(encoder_hidden_states, cond_masks, [guidance_chunks - 1], guidance_chunks, run.B, row_maps)
     keep = denoiser.return_attention
     denoiser.return_attention = True
     try:
@@ -665,6 +671,59 @@ def _open_run(denoiser, scheduler, encoder_hidden_states, cond_masks, B, L, num_
     return SamplingRun(denoiser, scheduler, encoder_hidden_states, cond_masks, B, L, num_inference_steps, **kw)
 
 
+DONE = object()     # an ``update``'s answer (``_drive``): not this iteration and none after it
+
+
+def _drive(run, denoiser, encoder_hidden_states, cond_masks, G, row_maps, return_attention, update=None):
+    """Every iteration of the open ``run``, the final read and the close (also on an exception): what ``sample`` and the guided loops
+    share.  Returns the latents, with ``return_attention`` (latents, maps) as ``sample`` describes them.
+    ``update(i, t, latents) -> new latents | None | DONE`` is what a guided loop does before iteration i of the scheduler's full table
+    (timestep t): ``latents()`` pulls the iteration's in-painting overwrite in front (``run.inpaint``; rollout / edit: the re-noised
+    tokens go in before the update, unbounded_synthesis.py:70-76) and reads the current latents, and what ``update`` returns is written
+    back; None leaves the iteration as it is (nothing read), DONE this one and every later one.  An iteration that is changed, or whose
+    maps are taken, is replayed at once; the un-changed ones before it go out as one ``steps`` call."""
+    try:
+        ring = run.att_ring is not None and return_attention in ("all", "auto")   # the captured iteration keeps every iteration's maps
+        every = return_attention == "all" and not ring     # the reference's dict (convofusion.py:517-523): one extra forward + sync per step
+        last = run.first_iteration + run.N - 1
+        atts, idle = {}, 0         # idle: un-changed iterations not replayed yet (they go out as one ``steps(idle)``)
+
+        def replay(n):
+            if n:
+                run.steps(n)
+            return 0
+
+        def latents():
+            nonlocal idle
+            idle = replay(idle)
+            run.inpaint()
+            return run.read()
+
+        for i, t in enumerate(run.timesteps, start=run.first_iteration):
+            new = update(i, t, latents) if update is not None else None
+            if new is DONE:
+                update = new = None
+            maps = every or (return_attention and not ring and i == last)
+            if new is None and not maps:
+                idle += 1
+                continue
+            idle = replay(idle)
+            if new is not None:
+                run.write(new)
+            if maps:
+                atts[int(t)] = last_step_attention(run, denoiser, t, encoder_hidden_states, cond_masks, G, row_maps)
+            run.steps(1)
+        replay(idle)
+        lat = run.read(close=not ring)
+        if ring:
+            atts = run.attention_dict()
+        if not return_attention:
+            return lat
+        return (lat, atts) if return_attention in ("all", "auto") else (lat, atts[int(run.timesteps[-1])])
+    finally:
+        run.close()     # an exception (bad focus index, CfdError ...) must not leave the run open on the denoiser's handle
+
+
 def sample(denoiser, scheduler, encoder_hidden_states, cond_masks=None, *, B, L=16, num_inference_steps=1000,
            guidance_scale=7.5, guidance_chunks=CFG_CHUNKS, eta=0.0, init_latents=None, step_noise=None, seed=0,
            first_utterance=0, preseq=None, dedup=True, skip_zero_weight_chunks=False, row_maps=None, return_attention=False, operands=None,
@@ -698,30 +757,9 @@ def sample(denoiser, scheduler, encoder_hidden_states, cond_masks=None, *, B, L=
                     row_maps=row_maps, operands=operands, modality_weights=modality_weights, prune_zero_weight_chunks=prune_zero_weight_chunks,
                     source_latents=source_latents, keep_mask=keep_mask, strength=strength, anchor_trajectory=anchor_trajectory,
                     **({} if tie is None else dict(tie=tie)), **({} if noise_space is None else dict(noise_space=noise_space)))
-    try:
-        if not return_attention:
-            run.steps(run.N)
-            return run.read(close=True)
+    if return_attention:
         scheduler.set_timesteps(num_inference_steps)
-        if return_attention in ("all", "auto") and run.att_ring is not None:   # the captured iteration kept them (SamplingRun(attention_ring=True))
-            run.steps(run.N)
-            lat = run.read()
-            atts = run.attention_dict()
-            run.close()
-            return lat, atts
-        if return_attention == "all":   # the reference's full dict: one entry per iteration (convofusion.py:523); one extra forward + sync per step
-            atts = {}
-            for t in run.timesteps:
-                atts[int(t)] = last_step_attention(run, denoiser, t, encoder_hidden_states, cond_masks, guidance_chunks, row_maps)
-                run.steps(1)
-            return run.read(close=True), atts
-        run.steps(run.N - 1)
-        att = last_step_attention(run, denoiser, run.timesteps[-1], encoder_hidden_states, cond_masks, guidance_chunks, row_maps)
-        run.steps(1)
-        lat = run.read(close=True)
-        return (lat, {int(run.timesteps[-1]): att}) if return_attention == "auto" else (lat, att)
-    finally:
-        run.close()     # an exception must not leave the run open on the denoiser's handle
+    return _drive(run, denoiser, encoder_hidden_states, cond_masks, guidance_chunks, row_maps, return_attention)
 
 
 # Guidance of an inversion by default: the conditional prediction alone, eps = e_0 + 1 * (e_full - e_0) at guidance_scale 1 (the
@@ -754,6 +792,16 @@ def invert(denoiser, scheduler, encoder_hidden_states, cond_masks=None, *, sourc
 
 # Philox stream of the level draws of ``invert_ddpm`` (0: step noise, 1: initial latents)
 LEVEL_NOISE_STREAM = 2
+
+
+def _positive_int(name, v, none_ok=False):
+    if not (none_ok and v is None) and (isinstance(v, bool) or int(v) != v or int(v) < 1):
+        raise ValueError(f"{name} must be a positive integer{' or None' if none_ok else ''}, not {v!r}")
+
+
+def _float_tensor_or_none(name, t, shape, shape_text):
+    if t is not None and (not isinstance(t, torch.Tensor) or not t.is_floating_point() or tuple(t.shape) != shape):
+        raise ValueError(f"{name} must be a floating-point tensor {shape_text}")
 
 
 def _level_batch_args(denoiser, scheduler, enc, masks, B, L, num_inference_steps, table, seed, first_utterance, dedup, row_maps):
@@ -801,12 +849,8 @@ def invert_ddpm(denoiser, scheduler, enc, masks=None, *, source_latents, num_inf
     B, L = int(source_latents.shape[0]), int(source_latents.shape[1])
     num_inference_steps, table = scheduler.timestep_table(num_inference_steps)
     N = len(table)
-    if levels_per_batch is not None and (isinstance(levels_per_batch, bool) or int(levels_per_batch) != levels_per_batch
-                                         or int(levels_per_batch) < 1):
-        raise ValueError(f"levels_per_batch must be a positive integer or None, not {levels_per_batch!r}")
-    if level_noise is not None and (not isinstance(level_noise, torch.Tensor) or not level_noise.is_floating_point()
-                                    or tuple(level_noise.shape) != (N, B, L, 128)):
-        raise ValueError(f"level_noise must be a floating-point tensor [N, B, L, 128] = [{N}, {B}, {L}, 128]")
+    _positive_int("levels_per_batch", levels_per_batch, none_ok=True)
+    _float_tensor_or_none("level_noise", level_noise, (N, B, L, 128), f"[N, B, L, 128] = [{N}, {B}, {L}, 128]")
     weights = modality_weight_table(INVERSION_WEIGHTS if modality_weights is None else modality_weights, guidance_scale, N, B, CFG_CHUNKS)
     lib, handle, dev, a, keep = _level_batch_args(denoiser, scheduler, enc, masks, B, L, num_inference_steps, table, seed, first_utterance,
                                                   dedup, row_maps)
@@ -863,9 +907,8 @@ def sample_parallel(denoiser, scheduler, enc, masks=None, *, B, L=16, num_infere
     if getattr(scheduler, "KIND", None) != 0:
         raise TypeError("sample_parallel needs a convofusion_amd.scheduler.DDPMScheduler")
     refuse_sample_prediction(scheduler, "sample_parallel (Picard sweeps over level batches) runs")
-    for name, v in (("B", B), ("L", L)):
-        if isinstance(v, bool) or int(v) != v or int(v) < 1:
-            raise ValueError(f"{name} must be a positive integer, not {v!r}")
+    _positive_int("B", B)
+    _positive_int("L", L)
     B, L = int(B), int(L)
     try:
         tol = float(tolerance)
@@ -875,12 +918,10 @@ def sample_parallel(denoiser, scheduler, enc, masks=None, *, B, L=16, num_infere
         raise ValueError(f"tolerance must be a finite number >= 0, not {tolerance!r}")
     num_inference_steps, table = scheduler.timestep_table(num_inference_steps)
     N = len(table)
-    for name, v in (("levels_per_batch", levels_per_batch), ("max_sweeps", max_sweeps)):
-        if v is not None and (isinstance(v, bool) or int(v) != v or int(v) < 1):
-            raise ValueError(f"{name} must be a positive integer or None, not {v!r}")
-    for name, t, shape in (("init_latents", init_latents, (B, L, 128)), ("step_noise", step_noise, (N, B, L, 128))):
-        if t is not None and (not isinstance(t, torch.Tensor) or not t.is_floating_point() or tuple(t.shape) != shape):
-            raise ValueError(f"{name} must be a floating-point tensor {list(shape)}")
+    _positive_int("levels_per_batch", levels_per_batch, none_ok=True)
+    _positive_int("max_sweeps", max_sweeps, none_ok=True)
+    _float_tensor_or_none("init_latents", init_latents, (B, L, 128), [B, L, 128])
+    _float_tensor_or_none("step_noise", step_noise, (N, B, L, 128), [N, B, L, 128])
     weights = None if modality_weights is None else modality_weight_table(modality_weights, guidance_scale, N, B, CFG_CHUNKS)
     lib, handle, dev, a, keep = _level_batch_args(denoiser, scheduler, enc, masks, B, L, num_inference_steps, table, seed, first_utterance,
                                                   dedup, row_maps)
@@ -982,64 +1023,30 @@ def sample_with_weg(denoiser, scheduler, encoder_hidden_states, cond_masks, focu
     from . import weg
     G = guidance_chunks
     scheduler.set_timesteps(num_inference_steps)
+    text_states, text_masks = guidance_chunk_rows(encoder_hidden_states, cond_masks, [1], G, B, kw.get("row_maps"))     # :447-448
+    text_masks = {k: (v.to(torch.uint8).contiguous() if v is not None else v) for k, v in text_masks.items()}
+    thresholds = dict(weg_parameters["thresholds"])
+    n_full = len(scheduler.timestep_table(num_inference_steps)[1])      # (an edit run starts at iteration k0 of the table: i counts from there)
+    carry = [weg_parameters["scale_range"][0], weg_parameters["scale_range"][1]] if carry_scale_range else None   # :395
+    guided = 0                            # evaluations of the objective so far (their conditioning never changes inside the loop)
+
+    def update(i, t, latents):
+        nonlocal guided
+        # past max_iter_to_alter the reference still evaluates the objective but only acts on it at a threshold step
+        if i >= weg_parameters["max_iter_to_alter"] and i not in thresholds:
+            if not any(k > i for k in thresholds):
+                return DONE
+            if carry is not None:   # the skipped iteration still re-assigns the table (convofusion.py:442-444)
+                weg.scale_range_schedule(weg_parameters, n_full, i, carry)
+            return None
+        lat, _ = weg.weg_update(denoiser, latents(), i, t, text_states, text_masks, focus_indices, weg_parameters, n_full,
+                                scale_carry=carry, same_memories=guided > 0)
+        guided += 1
+        return lat
+
     run = _open_run(denoiser, scheduler, encoder_hidden_states, cond_masks, B, L, num_inference_steps, return_attention in ("all", "auto"),
                     guidance_chunks=G, **kw)
-    try:
-        rm = kw.get("row_maps")
-        if rm is not None:       # distinct memories + row maps (build_guidance_batch): gather the text-only chunk's rows
-            idx = [m[B:2 * B].long() for m in rm]
-            text_states = [e.index_select(0, i.to(e.device)).contiguous() for e, i in zip(encoder_hidden_states, idx)]
-            text_masks = {k: (v.index_select(0, idx[_lib.MEM_NAMES.index(k)].to(v.device)).to(torch.uint8).contiguous() if v is not None else v)
-                          for k, v in (cond_masks or {}).items()}
-        else:
-            text_states = [enc.chunk(G)[1] for enc in encoder_hidden_states]                           # :447
-            text_masks = {k: (v.chunk(G)[1].to(torch.uint8).contiguous() if v is not None else v) for k, v in (cond_masks or {}).items()}  # :448
-        thresholds = dict(weg_parameters["thresholds"])
-        timesteps = run.timesteps
-        k0, n_full = run.first_iteration, run.first_iteration + len(run.timesteps)   # (an edit run starts at iteration k0 of the table)
-        carry = [weg_parameters["scale_range"][0], weg_parameters["scale_range"][1]] if carry_scale_range else None   # :395
-        guided = 0                            # evaluations of the objective so far (their conditioning never changes inside the loop)
-        ring = run.att_ring is not None       # every iteration's maps are kept by the captured iteration itself
-        every = return_attention == "all" and not ring     # the reference's dict: one entry per iteration (convofusion.py:517-523)
-        att = {} if every else None
-
-        def maps(t):
-            return last_step_attention(run, denoiser, t, encoder_hidden_states, cond_masks, G, kw.get("row_maps"))
-
-        for i, t in enumerate(timesteps, start=k0):
-            last = i == n_full - 1
-            # past max_iter_to_alter the reference still evaluates the objective but only acts on it at a threshold step
-            if i >= weg_parameters["max_iter_to_alter"] and i not in thresholds:
-                if not any(k > i for k in thresholds) and not every:
-                    break
-                if carry is not None:   # the skipped iteration still re-assigns the table (convofusion.py:442-444)
-                    weg.scale_range_schedule(weg_parameters, n_full, i, carry)
-            else:
-                run.inpaint()   # rollout / edit: the re-noised tokens go in before the WEG update (unbounded_synthesis.py:70-76)
-                lat, _ = weg.weg_update(denoiser, run.read(), i, t, text_states, text_masks, focus_indices, weg_parameters, n_full,
-                                        scale_carry=carry, same_memories=guided > 0)
-                guided += 1
-                run.write(lat)
-            if every:
-                att[int(t)] = maps(t)
-            elif last and return_attention:
-                att = maps(t)
-            run.steps(1)
-        if return_attention and att is None and not ring:
-            run.steps(run.N - 1 - run.position)
-            att = maps(timesteps[-1])
-        run.steps(run.N - run.position)
-        if ring:
-            lat = run.read()
-            att = run.attention_dict()
-            run.close()
-        else:
-            lat = run.read(close=True)
-            if return_attention == "auto":      # no ring at this size: the last iteration's entry, as a dict
-                att = {int(timesteps[-1]): att}
-    finally:
-        run.close()     # an exception (bad focus index, CfdError ...) must not leave the run open on the denoiser's handle
-    return (lat, att) if return_attention else lat
+    return _drive(run, denoiser, encoder_hidden_states, cond_masks, G, kw.get("row_maps"), return_attention, update)
 
 
 def guided_chunks(weights):
@@ -1088,47 +1095,40 @@ def sample_with_loss_guidance(denoiser, scheduler, encoder_hidden_states, cond_m
                                   f"row-tile path only: {why}")
     guided = None if guided_iterations is None else {int(i) for i in guided_iterations}
     scheduler.set_timesteps(num_inference_steps)
+    dev = encoder_hidden_states[0].device
+    states, masks = guidance_chunk_rows(encoder_hidden_states, cond_masks, chunks, G, B, kw.get("row_maps"))
+    states = [s.detach().contiguous() for s in states]
+    w_default = torch.tensor(default_guidance_weights(G, guidance_scale), dtype=torch.float32, device=dev)
+    acp = scheduler.alphas_cumprod.detach().to("cpu", torch.float64)
+
+    def update(i, t, latents):
+        if guided is not None and i not in guided:
+            return None
+        x = latents().requires_grad_(True)
+        w = torch.from_numpy(wtab[i]).to(dev) if wtab is not None else w_default.expand(B, 8)      # [B, 8]
+        with torch.enable_grad():
+            out, _ = denoiser(sample=x.repeat(len(chunks), 1, 1), timestep=int(t), encoder_hidden_states=states, mem_mask_dict=masks,
+                              side_engine=True)
+            e = out.view(len(chunks), B, L, out.shape[-1])
+            eps = e[0]
+            for n, c in enumerate(chunks[1:], start=1):
+                eps = eps + w[:, c].view(B, 1, 1) * (e[n] - e[0])
+            a_t = float(acp[int(t)])
+            x0 = (x - (1.0 - a_t) ** 0.5 * eps) / a_t ** 0.5
+            loss = loss_fn(x0)
+            (g,) = torch.autograd.grad(loss, x)
+        # (the side engine ran on torch's current stream, the captured iteration replays on the run's own: ``write`` waits for
+        #  the former, so the two never execute side by side)
+        return x.detach() - _loss_guidance_step_size(step_size, i, int(t)) * g
+
     run = _open_run(denoiser, scheduler, encoder_hidden_states, cond_masks, B, L, num_inference_steps, False,
                     guidance_scale=guidance_scale, guidance_chunks=G, **kw)
     keep_att = denoiser.return_attention
+    denoiser.return_attention = False
     try:
-        dev = run.device
-        rm = kw.get("row_maps")
-        if rm is not None:       # distinct memories + row maps (build_guidance_batch): gather the evaluated chunks' rows
-            idx = [torch.cat([m[c * B:(c + 1) * B] for c in chunks]).long() for m in rm]
-            states = [e.index_select(0, i.to(e.device)).detach().contiguous() for e, i in zip(encoder_hidden_states, idx)]
-            masks = {k: (v.index_select(0, idx[_lib.MEM_NAMES.index(k)].to(v.device)).contiguous() if v is not None else v)
-                     for k, v in (cond_masks or {}).items()}
-        else:
-            states = [torch.cat([e.chunk(G)[c] for c in chunks]).detach().contiguous() for e in encoder_hidden_states]
-            masks = {k: (torch.cat([v.chunk(G)[c] for c in chunks]).contiguous() if v is not None else v) for k, v in (cond_masks or {}).items()}
-        w_default = torch.tensor(default_guidance_weights(G, guidance_scale), dtype=torch.float32, device=dev)
-        acp = scheduler.alphas_cumprod.detach().to("cpu", torch.float64)
-        denoiser.return_attention = False
-        for i, t in enumerate(run.timesteps, start=run.first_iteration):
-            if guided is None or i in guided:
-                run.inpaint()    # rollout / edit: the re-noised tokens go in before the update, as in sample_with_weg
-                x = run.read().requires_grad_(True)
-                w = torch.from_numpy(wtab[i]).to(dev) if wtab is not None else w_default.expand(B, 8)      # [B, 8]
-                with torch.enable_grad():
-                    out, _ = denoiser(sample=x.repeat(len(chunks), 1, 1), timestep=int(t), encoder_hidden_states=states, mem_mask_dict=masks,
-                                      side_engine=True)
-                    e = out.view(len(chunks), B, L, out.shape[-1])
-                    eps = e[0]
-                    for n, c in enumerate(chunks[1:], start=1):
-                        eps = eps + w[:, c].view(B, 1, 1) * (e[n] - e[0])
-                    a_t = float(acp[int(t)])
-                    x0 = (x - (1.0 - a_t) ** 0.5 * eps) / a_t ** 0.5
-                    loss = loss_fn(x0)
-                    (g,) = torch.autograd.grad(loss, x)
-                # (the side engine ran on torch's current stream, the captured iteration replays on the run's own: ``write`` waits for
-                #  the former, so the two never execute side by side)
-                run.write(x.detach() - _loss_guidance_step_size(step_size, i, int(t)) * g)
-            run.steps(1)
-        return run.read(close=True)
+        return _drive(run, denoiser, encoder_hidden_states, cond_masks, G, kw.get("row_maps"), False, update)
     finally:
         denoiser.return_attention = keep_att
-        run.close()     # an exception must not leave the run open on the denoiser's handle
 
 
 def diffusion_reverse(model, encoder_hidden_states, lengths=None, cond_masks=dict(), focus_indices=[], *,
@@ -1145,11 +1145,9 @@ def diffusion_reverse(model, encoder_hidden_states, lengths=None, cond_masks=dic
     iteration keeps the maps and "last" elsewhere."""
     if attention_steps not in ("last", "all", "auto"):
         raise ValueError("attention_steps must be 'auto', 'last' or 'all'")
-    if attention_steps in ("all", "auto"):
-        lat, atts = _loop_from_model(model, encoder_hidden_states, cond_masks, None, focus_indices, init_latents, seed, attention=attention_steps)
-        return lat.permute(1, 0, 2), atts
-    lat, att = _loop_from_model(model, encoder_hidden_states, cond_masks, None, focus_indices, init_latents, seed)
-    return lat.permute(1, 0, 2), {int(model.scheduler.timesteps[-1]): att}                        # :523,548-549
+    last = attention_steps == "last"
+    lat, atts = _loop_from_model(model, encoder_hidden_states, cond_masks, None, focus_indices, init_latents, seed, attention=last or attention_steps)
+    return lat.permute(1, 0, 2), ({int(model.scheduler.timesteps[-1]): atts} if last else atts)   # :523,548-549
 
 
 def diffusion_reverse_forecast(model, encoder_hidden_states, lengths=None, preseq=None, cond_masks=dict(),

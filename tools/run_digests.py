@@ -3,7 +3,7 @@ small test shape (B = 2, L = 16, memories S = (6, 20, 6, 8, 1) with pad tails (2
 seeds, the seeded test weights) and prints one line per run: the SHA-256 of the final latents' bytes, of ``read()`` after every iteration
 (``steps``), of the trajectory, the noise and the attention ring where the run has them (``refused=`` with the library's message for a run it does not open), and N, first_iteration, chunks_evaluated and the
 non-pointer fields of the run's cfd_sample_args; then the launches of one iteration per class and the SHA-256 of three single forwards
-(``Denoiser.forward``: output and att_mats), and the word-excitation-guidance lines of ``weg_lines``.  The runs are deterministic: the outputs of two trees are compared with ``diff``, and a
+(``Denoiser.forward``: output and att_mats), the word-excitation-guidance lines of ``weg_lines`` and the Python loops' lines of ``loop_lines``.  The runs are deterministic: the outputs of two trees are compared with ``diff``, and a
 line that differs is a change of behaviour.
 
 Usage (once in each tree):  python tools/run_digests.py > digests.txt
@@ -143,7 +143,7 @@ def main():
         with torch.no_grad():
             out, att = m(x, t, mems, mem_mask_dict=masks)
         line(f"forward {name}", out=sha(out), att_mats=sha(*att))
-    weg_lines(m)
+    loop_lines(m, mems, masks, *weg_lines(m))
 
 
 def weg_lines(m):
@@ -166,6 +166,36 @@ def weg_lines(m):
                                   {k: to_dev(v) for k, v in cb["masks"].items()}, [[2, 5]], params, B=1, L=16, num_inference_steps=5,
                                   guidance_scale=7.5, init_latents=to_dev(philox_ref.normal_tensor(23, 0, range(1), 1, 16)), seed=2)
     line("sample_with_weg 5 iterations", final=sha(lat))
+    return cb, params
+
+
+def att_sha(att):
+    """The maps of one iteration (5 tensors) or a dict {timestep: maps}: the timesteps and the SHA-256 of every tensor in order."""
+    if isinstance(att, dict):
+        return f"{list(att)}:{sha(*[a for maps in att.values() for a in maps])}"
+    return sha(*att)
+
+
+def loop_lines(m, mems, masks, cb1, params):
+    """The Python drivers of an open run (new lines only, as above): ``sample`` with its attention modes at the small shape, and the two
+    guided loops at the B = 1 shape of ``weg_lines``."""
+    from oracle import philox_ref
+    ddpm = lambda: scheduler.DDPMScheduler(variance_type="fixed_small", **SCHED_KW)  # noqa: E731
+    for mode in (True, "all", "auto"):
+        lat, att = sampler.sample(m, ddpm(), mems, masks, B=B, L=L, num_inference_steps=N_IT, seed=SEED, return_attention=mode)
+        line(f"sample return_attention={mode!r}", final=sha(lat), maps=att_sha(att))
+    mems1, masks1 = [to_dev(x) for x in cb1["memories"]], {k: to_dev(v) for k, v in cb1["masks"].items()}
+    init = to_dev(philox_ref.normal_tensor(23, 0, range(1), 1, 16))
+    for mode in (True, "all"):
+        lat, att = sampler.sample_with_weg(m, ddpm(), mems1, masks1, [[2, 5]], params, B=1, L=16, num_inference_steps=5, guidance_scale=7.5,
+                                           init_latents=init, seed=2, return_attention=mode)
+        line(f"sample_with_weg return_attention={mode!r}", final=sha(lat), maps=att_sha(att))
+    target = torch.randn((1, 16, 128), generator=torch.Generator().manual_seed(13)).cuda()
+    for guided in ((1, 3), None):
+        lat = sampler.sample_with_loss_guidance(m, ddpm(), mems1, masks1, lambda x0: ((x0 - target) ** 2).sum(), 0.05, B=1, L=16,
+                                                num_inference_steps=N_IT, guidance_scale=7.5, init_latents=init, seed=2,
+                                                guided_iterations=guided)
+        line(f"sample_with_loss_guidance guided_iterations={guided}", final=sha(lat))
 
 
 if __name__ == "__main__":

@@ -27,7 +27,7 @@ SYMBOLS = [
     "cfd_vae_encode", "cfd_sample_begin_weighted", "cfd_sample_begin_edit", "cfd_sample_begin_invert", "cfd_sample_begin_anchored",
     "cfd_sample_begin_tied", "cfd_ddpm_invert", "cfd_sample_begin_replay", "cfd_sample_parallel", "cfd_test_picard_stride",
     "cfd_test_picard_sweep", "cfd_debug_weg_stop", "cfd_debug_weg_fill", "cfd_scheduler_step_pred", "cfd_dpmsolver_step_pred",
-    "cfd_debug_forward_operands", "cfd_denoise_vjp", "cfd_debug_live_buffers",
+    "cfd_debug_forward_operands", "cfd_denoise_vjp", "cfd_debug_live_buffers", "cfd_vae_decode_vjp",
 ]
 
 # cfd_sample_args.prediction_type / the _pred entry points, by the schedulers' config string
@@ -134,6 +134,13 @@ class WegArgs(C.Structure):
 class VjpArgs(C.Structure):
     """cfd_vjp_args: one denoiser forward whose vector-Jacobian product with respect to the sample is wanted (cfd_denoise_vjp)."""
     _fields_ = [("Be", C.c_int), ("L", C.c_int), ("timestep", C.c_int), ("sample", C.c_void_p), ("mem", Memory * NUM_MEM)]
+
+
+class VaeDecodeVjpArgs(C.Structure):
+    """cfd_vae_decode_vjp_args: one ConvoFusionVae.decode whose vector-Jacobian product with respect to z is wanted (cfd_vae_decode_vjp)."""
+    _fields_ = [("wpack", C.c_void_p), ("d_model", C.c_int), ("num_heads", C.c_int), ("ff_size", C.c_int), ("num_layers", C.c_int),
+                ("bs", C.c_int), ("nframes", C.c_int), ("n_chunks", C.c_int), ("z", C.c_void_p), ("lengths", C.c_void_p),
+                ("d_feats", C.c_void_p)]
 
 
 # cfd_test_epi_args.kind (include/cfdenoise_dev.h)
@@ -286,6 +293,7 @@ def load():
     lib.cfd_sample_inpaint.argtypes = [C.c_void_p]
     lib.cfd_weg_eval.argtypes = [C.c_void_p, C.POINTER(WegArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_void_p]
     lib.cfd_denoise_vjp.argtypes = [C.c_void_p, C.POINTER(VjpArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.cfd_vae_decode_vjp.argtypes = [C.c_void_p, C.POINTER(VaeDecodeVjpArgs), C.c_void_p, C.c_void_p, C.c_void_p]
     lib.cfd_dyadic_steps.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(DyadicProj), C.c_int]
     lib.cfd_debug_stop_stage.argtypes = [C.c_void_p, C.c_int]
     lib.cfd_debug_read.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t]

@@ -1,7 +1,9 @@
 // libcfdenoise: float32 building blocks on device tensors -- the conditioning producers (cfd_linear_act) and the pieces of
-// ConvoFusionVae.decode (cfd_layer_norm, cfd_mha, cfd_add, cfd_zero_rows) -- and ConvoFusionVae.encode in one launch (cfd_vae_encode).
+// ConvoFusionVae.decode (cfd_layer_norm, cfd_mha, cfd_add, cfd_zero_rows) -- ConvoFusionVae.encode in one launch (cfd_vae_encode) and the
+// differentiable decode (cfd_vae_decode_vjp).
 #include "cfd_internal.hpp"
 #include "vae_enc.hpp"
+#include "vae_dec.hpp"
 
 // ---- conditioning producers ---------------------------------------------------------------------------------
 int enqueue_linear_act(const float* x, long long n_rows, int K, const float* W, const float* b, int N, int act, float* out, hipStream_t st) {
@@ -126,4 +128,90 @@ extern "C" int cfd_vae_encode(cfd_handle c, const float* wpack, int d_model, int
   if (rt == 4) return launch_vae_encode<4>(a, (int)groups, lds, st);
   if (rt == 3) return launch_vae_encode<3>(a, (int)groups, lds, st);
   return launch_vae_encode<2>(a, (int)groups, lds, st);
+}
+
+
+// ---- ConvoFusionVae.decode with d(feats)/d(z) (autograd over vae.py:268-372): csrc/vae_dec.hpp -----------------------------------------------
+extern "C" int cfd_vae_decode_vjp(cfd_handle c, const cfd_vae_decode_vjp_args* p, float* feats, float* d_z, void* stream) {
+  if (!c || !p || !p->wpack || !p->z || !p->lengths || !p->d_feats || !d_z) return fail(CFD_E_ARG, "bad argument (NULL pointer)");
+  if (p->d_model != VE_D || p->num_heads != 2 || p->ff_size != VE_FF || p->num_layers < 1 || p->num_layers > VE_MAX_LAYERS || p->num_layers % 2 == 0)
+    return fail(CFD_E_ARG, "cfd_vae_decode_vjp implements d_model 128, 2 heads, ff 1024 and odd num_layers <= %d only (got %d, %d, %d, %d)",
+                VE_MAX_LAYERS, p->d_model, p->num_heads, p->ff_size, p->num_layers);
+  if (p->bs < 1 || p->bs > 65535) return fail(CFD_E_ARG, "cfd_vae_decode_vjp takes 1 <= bs <= 65535 sequences (got %d)", p->bs);
+  if (p->nframes < 1 || p->nframes > VD_MAX_FRAMES) return fail(CFD_E_ARG, "cfd_vae_decode_vjp takes 1 <= nframes <= %d (got %d)", VD_MAX_FRAMES, p->nframes);
+  if (p->n_chunks < 1 || p->n_chunks > VD_MAX_CHUNKS) return fail(CFD_E_ARG, "cfd_vae_decode_vjp takes 1 <= n_chunks <= %d (got %d)", VD_MAX_CHUNKS, p->n_chunks);
+  HIPCHK(hipSetDevice(c->cfg.device));
+  hipStream_t st = (hipStream_t)stream;
+  VaeDecArgs a;
+  a.nl = p->num_layers;
+  a.nb = (a.nl - 1) / 2;
+  a.w = p->wpack;
+  a.stack_floats = vd_stack_floats(a.nl);
+  a.qpe = p->wpack + 2 * a.stack_floats;
+  a.mpe = a.qpe + (long long)VD_MAX_FRAMES * VE_D;
+  a.z = p->z;
+  a.lengths = p->lengths;
+  a.d_feats = p->d_feats;
+  a.feats = feats;
+  a.d_z = d_z;
+  a.bs = p->bs;
+  a.nframes = p->nframes;
+  a.nt = (p->nframes + 15) / 16;
+  a.fp = 16 * a.nt;
+  a.n_chunks = p->n_chunks;
+  a.rows = 2LL * a.bs * a.fp;
+  // the workspace (the handle's, this call's own): sized from the shapes, carved in the order of VaeDecArgs
+  const long long R = a.rows, nl = a.nl, sb = 2LL * a.bs;
+  const long long sizes[] = {(nl + 1) * R * VE_D, nl * R * VE_D, nl * R * VE_D, nl * R * 3 * VE_D, nl * R * VE_D, nl * R * 2, nl * R * VE_D, nl * sb * 16 * 256,
+                             nl * R * VE_D, R * VE_D, R * VE_D, R * 2, R * 3 * VE_D, (a.nb ? a.nb : 1) * R * VE_D, nl * sb * a.nt * 16 * 256, nl * sb * 16 * VE_D};
+  float** const slots[] = {&a.x0, &a.x1, &a.x2, &a.qkv, &a.o, &a.lse, &a.qc, &a.mkv, &a.g, &a.g1, &a.d_o, &a.dd, &a.dqkv, &a.gskip, &a.pkv, &a.dzl};
+  long long total = 0;
+  for (long long n : sizes) total += (n + 3) / 4 * 4;
+  CHK(c->vae.ws.ensure((size_t)total * sizeof(float)));
+  float* base = c->vae.ws.as<float>();
+  for (size_t i = 0; i < sizeof(sizes) / sizeof(sizes[0]); ++i) {
+    *slots[i] = base;
+    base += (sizes[i] + 3) / 4 * 4;
+  }
+  c->vae.g = a.g; c->vae.dzl = a.dzl; c->vae.x0 = a.x0;
+  c->vae.bs = a.bs; c->vae.fp = a.fp; c->vae.nl = a.nl; c->vae.rows = a.rows;
+  const dim3 grid((unsigned)a.nt, (unsigned)a.bs, 2), blk(256);
+  int n = 0;
+  hipLaunchKernelGGL(vd_mem_kernel, dim3((unsigned)a.nl, (unsigned)a.bs, 2), blk, 0, st, a);
+  ++n;
+  for (int l = 0; l <= a.nl; ++l) {
+    hipLaunchKernelGGL(vd_fwd_rows_kernel, grid, blk, 0, st, a, l);
+    ++n;
+    if (l < a.nl) {
+      hipLaunchKernelGGL(vd_self_fwd_kernel, grid, blk, 0, st, a, l);
+      ++n;
+    }
+  }
+  for (int l = a.nl - 1; l >= 0; --l) {
+    hipLaunchKernelGGL(vd_bwd_rows_kernel, grid, blk, 0, st, a, l);
+    ++n;
+    if (l > 0) {
+      hipLaunchKernelGGL(vd_self_bwd_kernel, grid, blk, 0, st, a, l);
+      ++n;
+    }
+  }
+  hipLaunchKernelGGL(vd_dz_kernel, dim3((unsigned)a.bs, 2, (unsigned)a.nl), blk, 0, st, a);
+  hipLaunchKernelGGL(vd_dz_sum_kernel, dim3((unsigned)a.bs, 2), blk, 0, st, a);
+  n += 2;
+  HIPCHK(hipGetLastError());
+  c->vae.launches = n;
+  return CFD_OK;
+}
+
+// "vae.g.<l>": the running gradient at layer l's output, rows ((stack * bs + b) * fp + f), fp = nframes rounded up to 16; "vae.dz.<l>": layer
+// l's contribution to d_z as [2][bs][16][128]; "vae.x.<l>": the forward's stream at layer l's input (l = num_layers: the last layer's output)
+int vae_debug_buffer(Ctx* c, const char* what, float** p, size_t* n) {
+  const auto& v = c->vae;
+  if (!v.g) return fail(CFD_E_STATE, "'%s': no cfd_vae_decode_vjp has run on this handle", what);
+  int l = -1;
+  if (sscanf(what, "vae.g.%d", &l) == 1 && l >= 0 && l < v.nl) { *p = v.g + (size_t)l * v.rows * VE_D; *n = (size_t)v.rows * VE_D; }
+  else if (sscanf(what, "vae.dz.%d", &l) == 1 && l >= 0 && l < v.nl) { *p = v.dzl + (size_t)l * 2 * v.bs * 16 * VE_D; *n = (size_t)2 * v.bs * 16 * VE_D; }
+  else if (sscanf(what, "vae.x.%d", &l) == 1 && l >= 0 && l <= v.nl) { *p = v.x0 + (size_t)l * v.rows * VE_D; *n = (size_t)v.rows * VE_D; }
+  else return fail(CFD_E_ARG, "unknown buffer '%s'", what);
+  return CFD_OK;
 }

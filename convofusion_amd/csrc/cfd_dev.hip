@@ -112,6 +112,21 @@ extern "C" int cfd_debug_read(cfd_handle c, const char* what, float* dst_dev, si
     HIPCHK(hipMemcpy(dst_dev, f, sizeof(f), hipMemcpyHostToDevice));
     return CFD_OK;
   }
+  if (!strcmp(what, "vae.info")) {   // the last cfd_vae_decode_vjp: launches, padded frames per sequence
+    if (numel < 2) return fail(CFD_E_ARG, "vae.info needs 2 floats");
+    const float f[2] = {(float)c->vae.launches, (float)c->vae.fp};
+    HIPCHK(hipMemcpy(dst_dev, f, sizeof(f), hipMemcpyHostToDevice));
+    return CFD_OK;
+  }
+  if (!strncmp(what, "vae.", 4)) {
+    float* p = nullptr;
+    size_t n = 0;
+    CHK(vae_debug_buffer(c, what, &p, &n));
+    if (numel > n) return fail(CFD_E_ARG, "buffer '%s' holds %zu floats, asked for %zu", what, n, numel);
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(dst_dev, p, numel * 4, hipMemcpyDeviceToDevice));
+    return CFD_OK;
+  }
   if (!strncmp(what, "weg.", 4)) {
     float* p = nullptr;
     size_t n = 0;

@@ -317,6 +317,13 @@ struct cfd_handle_s {
     return k;
   }
   WegState weg;                // cfd_weg_eval's state between two evaluations (cfd_weg.hip)
+  // cfd_vae_decode_vjp (cfd_blocks.hip, vae_dec.hpp): the call's own workspace and, for cfd_debug_read ("vae.*"), where the last call left its taps
+  struct VaeVjpState {
+    DBuf ws;
+    float *g = nullptr, *dzl = nullptr, *x0 = nullptr;
+    int bs = 0, fp = 0, nl = 0, launches = 0;
+    long long rows = 0;
+  } vae;
   hipEvent_t weg_ev = nullptr;  // cross-stream hand-over of cfd_weg_eval, and of cfd_dyadic_steps
   // profiling
   bool prof = false;
@@ -534,3 +541,4 @@ size_t step_rows_bytes(Ctx* c);   // what refresh_step_rows needs of Work::rt_cu
 int enqueue_philox_fill(float* out, int B, int per_utt, uint64_t seed, uint32_t step, uint32_t utt0, uint32_t stream_id, float scale, hipStream_t st);
 // cfd_blocks.hip
 int enqueue_linear_act(const float* x, long long n_rows, int K, const float* W, const float* b, int N, int act, float* out, hipStream_t st);
+int vae_debug_buffer(Ctx* c, const char* what, float** p, size_t* n);   // the taps of the last cfd_vae_decode_vjp (cfd_debug_read "vae.*")

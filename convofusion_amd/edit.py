@@ -9,6 +9,9 @@ loop's latents into the VAE's [2, B, T, 128], convofusion.py:1028-1030), and fra
     in-betweening                         token_mask(B, keep_frames=[(0, 32), (96, 128)])
     variation of the whole gesture        no mask, strength 0.5
 
+``keyframe_loss`` (latent tokens) and ``pose_keyframe_loss`` (motion features of single frames, through the differentiable VAE decode) are
+the soft constraints of ``sampler.sample_with_loss_guidance``.
+
 ``edit_motion`` runs the whole edit: HIP ``encode`` of the source motion, the fused edit loop, HIP ``decode``.
 
 ``reperform_motion`` re-conditions a recorded motion ("the same gesture, re-performed to new speech"): deterministic DDIM inversion of its
@@ -72,6 +75,42 @@ def keyframe_loss(target, mask):
     def loss(x0):
         w = m.to(device=x0.device, dtype=x0.dtype).unsqueeze(-1)
         d = (x0 - target.to(device=x0.device, dtype=x0.dtype)) * w
+        return (d * d).sum() / n
+    return loss
+
+
+def pose_keyframe_loss(vae, target, frame_mask, feature_mask=None, lengths=None):
+    """The loss of frame-accurate key poses for ``sampler.sample_with_loss_guidance``: a function x0 [B, L, 128] -> the mean-square error
+    of ``vae.decode(loop_to_vae(x0), lengths)`` against ``target`` [B, F, 189] over the frames of ``frame_mask`` (bool / 0-1 [B, F]) and
+    the features of ``feature_mask`` (bool / 0-1 [189]; None = all).  Where ``keyframe_loss`` compares latent tokens (16-frame chunks of
+    body or hands), this one constrains motion space: this wrist, these fingers, at frame 73.  ``target`` lives in decode's own feature
+    space: the root-subtracted features ``vae.encode`` returns as its third value, not the raw input features.  ``lengths``: frames per
+    sequence (default F for every sequence; max(lengths) must be F).  ``vae``: a ``convofusion_amd.vae.ConvoFusionVae`` (its ``decode``
+    is differentiable with respect to the latents, backward ``decode_vjp``); decode runs on the stand-alone engine handle, not on the
+    denoiser's, so an open sampling run is untouched.  Frames at or beyond a sequence's length decode to 0 and pull nothing.  Whether
+    guided motions look right under a trained checkpoint is not measured here: the weights of the tests are seeded."""
+    if target.dim() != 3:
+        raise ValueError(f"pose_keyframe_loss: target must be [B, F, nfeats], got {tuple(target.shape)}")
+    B, F, nf = (int(v) for v in target.shape)
+    fm = (frame_mask != 0)
+    if tuple(fm.shape) != (B, F):
+        raise ValueError(f"pose_keyframe_loss: frame_mask must be [B, F] = [{B}, {F}] like target, got {tuple(fm.shape)}")
+    cm = torch.ones(nf, dtype=torch.bool) if feature_mask is None else (feature_mask != 0)
+    if tuple(cm.shape) != (nf,):
+        raise ValueError(f"pose_keyframe_loss: feature_mask must be [{nf}], got {tuple(cm.shape)}")
+    lens = [F] * B if lengths is None else [int(v) for v in (lengths.reshape(-1).tolist() if torch.is_tensor(lengths) else lengths)]
+    if len(lens) != B or min(lens) < 1 or max(lens) != F:
+        raise ValueError(f"pose_keyframe_loss: lengths must be {B} values in [1, {F}] whose largest is {F}, got {lens}")
+    n = int(fm.sum().item()) * int(cm.sum().item())
+    if n == 0:
+        raise ValueError("pose_keyframe_loss: the masks select no frame or no feature")
+
+    def loss(x0):
+        if x0.dim() != 3 or x0.shape[0] != B:
+            raise ValueError(f"pose_keyframe_loss: x0 must be [{B}, L, 128], got {tuple(x0.shape)}")
+        feats = vae.decode(loop_to_vae(x0), lens)
+        w = (fm.to(x0.device).unsqueeze(-1) & cm.to(x0.device)).to(feats.dtype)
+        d = (feats - target.to(device=x0.device, dtype=feats.dtype)) * w
         return (d * d).sum() / n
     return loss
 

@@ -17,6 +17,13 @@ batch), so the kernels are plain and exact rather than tuned.
 subtraction, skeleton embedding, global tokens, PE, mask, the encoder stacks and the final norm, exact float32.  torch then forms
 std = exp(logvar) ** 0.5 and draws ``Normal(mu, std).rsample()`` from the default generator exactly as the reference does.  The
 kernel reads a packed copy of the encoder weights that is rebuilt whenever a parameter changes (``load_state_dict``, ``.to``).
+
+``decode`` is differentiable with respect to ``z``: with grad enabled and ``z.requires_grad`` it returns the same launch sequence's output
+(bit-identical to the ``no_grad`` result) behind a ``torch.autograd.Function`` whose backward is ``decode_vjp``.  ``decode_vjp(z, lengths,
+d_feats)`` is one call of cfd_vae_decode_vjp (csrc/vae_dec.hpp): a forward of both decoder stacks on 16-frame row tiles that saves what the
+reverse sweep needs, and the sweep from the cotangent at the 189 features back to the latents -- what the reference gets from torch autograd
+over its ``decode``.  Exact float32, no atomics (two calls return the same bits), nframes <= 256, n_chunks <= 16.  It reads a packed copy of
+the decoder weights (every matrix in both orders, ``_decoder_pack``) kept like the encoder's.  No gradients to weights or lengths.
 """
 import ctypes as C
 
@@ -163,6 +170,7 @@ class ConvoFusionVae(nn.Module):
         self.body_nfeats, self.hands_nfeats = 23 * 3, 40 * 3                  # vae.py:53-54
         self.arch, self.num_heads, self.num_layers, self.ff_size = arch, num_heads, num_layers, ff_size
         self._enc_pack, self._enc_key = None, None
+        self._dec_pack, self._dec_key = None, None
         d = self.latent_dim
         self.body_global_motion_token = nn.Parameter(torch.randn(self.latent_size * 2, d))
         self.hands_global_motion_token = nn.Parameter(torch.randn(self.latent_size * 2, d))
@@ -261,11 +269,21 @@ class ConvoFusionVae(nn.Module):
         latent = dist.rsample()
         return latent.reshape(-1, bs, n_chunks, self.latent_dim), dist, feats
 
-    @torch.no_grad()
     def decode(self, z, lengths):
-        """z [2, bs, n_chunks, latent_dim] (body | hands), lengths: frames per sequence -> feats [bs, nframes, 189]."""
+        """z [2, bs, n_chunks, latent_dim] (body | hands), lengths: frames per sequence -> feats [bs, nframes, 189].  Differentiable with
+        respect to z when grad is enabled and ``z.requires_grad`` (backward: ``decode_vjp``); the values are the same bits either way."""
         if z.device.type != "cuda":
             raise RuntimeError("the HIP VAE decoder runs on an MI355X only (move the module and z to 'cuda'); no CPU fallback")
+        if torch.is_grad_enabled() and z.requires_grad:
+            lens = [int(v) for v in (lengths.reshape(-1).tolist() if torch.is_tensor(lengths) else lengths)]
+            why = self._decode_vjp_refusal(z, lens, None)
+            if why:
+                raise NotImplementedError(f"decode cannot be differentiated here: {why}")
+            return _DecodeVjp.apply(z, self, lens)
+        return self._decode_launches(z, lengths)
+
+    @torch.no_grad()
+    def _decode_launches(self, z, lengths):
         _, bs, n_chunks, D = z.shape
         dev = z.device
         lens = torch.as_tensor(list(lengths), device=dev)
@@ -287,6 +305,139 @@ class ConvoFusionVae(nn.Module):
             _lib.check(_lib.load().cfd_zero_rows(_engine_handle(dev), _ptr(out), _ptr(keep), nframes * bs, out.shape[-1], _stream(out)))
             _lib.wrote(out)
         return out.permute(1, 0, 2)                                                           # :370
+
+    def _decoder_sources(self):
+        """(tensor, kind) in the order of the packed layout (csrc/vae_dec.hpp).  kind: "v" a vector, "m" a matrix stored in both orders,
+        "f" / "fb" final_layer's weight / bias, zero-padded to 128 output features."""
+        src = []
+        for dec, fin in ((self.body_decoder, self.body_final_layer), (self.hands_decoder, self.hands_final_layer)):
+            for blk in list(dec.input_blocks) + [dec.middle_block] + list(dec.output_blocks):
+                sa, ca = blk.self_attn, blk.multihead_attn
+                src += [(blk.norm1.weight, "v"), (blk.norm1.bias, "v"), (sa.in_proj_weight, "m"), (sa.in_proj_bias, "v"),
+                        (sa.out_proj.weight, "m"), (sa.out_proj.bias, "v"), (blk.norm2.weight, "v"), (blk.norm2.bias, "v"),
+                        (ca.in_proj_weight, "m"), (ca.in_proj_bias, "v"), (ca.out_proj.weight, "m"), (ca.out_proj.bias, "v"),
+                        (blk.norm3.weight, "v"), (blk.norm3.bias, "v"), (blk.linear1.weight, "m"), (blk.linear1.bias, "v"),
+                        (blk.linear2.weight, "m"), (blk.linear2.bias, "v")]
+            for lin in dec.linear_blocks:
+                src += [(lin.weight, "m"), (lin.bias, "v")]
+            src += [(dec.norm.weight, "v"), (dec.norm.bias, "v"), (fin.weight, "f"), (fin.bias, "fb")]
+        src += [(self.query_pos_decoder.pe[:DEC_MAX_FRAMES], "v"), (self.mem_pos_decoder.pe[:DEC_MAX_CHUNKS], "v")]
+        return src
+
+    def _decoder_pack(self, dev):
+        """The packed decoder weights of both stacks and the two PE tables on ``dev``; rebuilt when any source tensor was replaced or
+        written, exactly as ``_encoder_pack``."""
+        src = self._decoder_sources()
+        key = (str(dev),) + tuple((t.data_ptr(), t._version) for t, _ in src)
+        if self._dec_pack is None or self._dec_key != key:
+            parts = []
+            for t, kind in src:
+                t = t.detach().to(dev, torch.float32)
+                if kind in ("v", "fb"):
+                    t = t.reshape(-1)
+                    parts.append(F.pad(t, (0, ENC_D - t.numel())) if kind == "fb" else t)
+                else:
+                    if kind == "f":
+                        t = F.pad(t, (0, 0, 0, ENC_D - t.shape[0]))
+                    parts += [_pack_w(t), _pack_w(t.t().contiguous())]
+            pack = torch.cat(parts).contiguous()
+            assert pack.numel() == decoder_pack_floats(self.num_layers), pack.numel()
+            self._dec_pack, self._dec_key = pack, key
+        return self._dec_pack
+
+    def _decode_vjp_refusal(self, z, lens, d_feats):
+        """ValueError for arguments ``decode_vjp`` cannot mean anything for; returns the NotImplementedError text for shapes beyond the
+        kernels' limits (``decode_vjp_refusal``) or None.  No library, no device."""
+        nf = self.body_nfeats + self.hands_nfeats
+        if z.dim() != 4 or z.shape[0] != 2 or z.shape[-1] != self.latent_dim:
+            raise ValueError(f"z must be [2, bs, n_chunks, {self.latent_dim}], got {tuple(z.shape)}")
+        bs, n_chunks = int(z.shape[1]), int(z.shape[2])
+        if bs < 1 or n_chunks < 1 or len(lens) != bs:
+            raise ValueError(f"{len(lens)} lengths for z of shape {tuple(z.shape)}")
+        if min(lens) < 1:
+            raise ValueError(f"every length must be at least 1, got {min(lens)}")
+        if d_feats is not None:
+            if d_feats.dim() != 3 or d_feats.shape[0] != bs or d_feats.shape[2] != nf:
+                raise ValueError(f"d_feats must be [{bs}, nframes, {nf}], got {tuple(d_feats.shape)}")
+            if max(lens) != d_feats.shape[1]:
+                raise ValueError(f"max(lengths) = {max(lens)} must equal d_feats.shape[1] = {d_feats.shape[1]}")
+        return decode_vjp_refusal(bs, max(lens), n_chunks, self.latent_dim, self.num_heads, self.ff_size, self.num_layers, self.latent_size)
+
+    def decode_vjp(self, z, lengths, d_feats, want_out=True):
+        """(feats [bs, nframes, 189] or None, d_z [2, bs, n_chunks, 128]): ``decode(z, lengths)`` as one cfd_vae_decode_vjp call computes
+        it (padded frames exactly 0) and d_feats^T . d(feats)/d(z) -- torch.autograd.grad(decode(z, lengths), z, d_feats) of the
+        reference.  d_feats [bs, nframes, 189] is the cotangent at decode's output; its rows at or beyond a sequence's length are not
+        read.  Deterministic: the same inputs give the same bits.  Returns with its results complete.  ValueError: a length below 1, a wrong shape, max(lengths) !=
+        d_feats.shape[1]; NotImplementedError beyond the kernels' limits (``decode_vjp_refusal``), before any device work."""
+        lens = [int(v) for v in (lengths.reshape(-1).tolist() if torch.is_tensor(lengths) else lengths)]
+        why = self._decode_vjp_refusal(z, lens, d_feats)
+        if why:
+            raise NotImplementedError(f"decode_vjp: {why}")
+        if z.device.type != "cuda":
+            raise RuntimeError("the HIP VAE decoder runs on an MI355X only (move the module and z to 'cuda'); no CPU fallback")
+        dev = z.device
+        bs, n_chunks, nframes = int(z.shape[1]), int(z.shape[2]), max(lens)
+        zc = z.detach().to(torch.float32).contiguous()
+        dc = d_feats.detach().to(device=dev, dtype=torch.float32).contiguous()
+        pack = self._decoder_pack(dev)
+        lens_d = torch.tensor(lens, dtype=torch.int32, device=dev)
+        feats = torch.empty(bs, nframes, self.body_nfeats + self.hands_nfeats, device=dev) if want_out else None
+        d_z = torch.empty_like(zc)
+        args = _lib.VaeDecodeVjpArgs(_ptr(pack), self.latent_dim, self.num_heads, self.ff_size, self.num_layers, bs, nframes, n_chunks,
+                                     _ptr(zc), _ptr(lens_d), _ptr(dc))
+        with torch.cuda.device(dev):
+            # The C call only enqueues.  This wrapper waits on both sides, as ``Denoiser.vjp`` returns with its results complete: an open
+            # sampling run replays on a stream of its own and ``SamplingRun.read`` fills a fresh tensor through that stream, so launches of
+            # this call that were still pending could run beside a replay (two queues at once: DESIGN.md section 6) or write into a block
+            # torch has already handed to such a tensor.
+            torch.cuda.synchronize(dev)
+            _lib.check(_lib.load().cfd_vae_decode_vjp(_engine_handle(dev), C.byref(args), _ptr(feats) if want_out else None, _ptr(d_z),
+                                                      _stream(zc)))
+            torch.cuda.current_stream(dev).synchronize()
+        return feats, d_z
+
+
+class _DecodeVjp(torch.autograd.Function):
+    """``ConvoFusionVae.decode``'s launch sequence as a function of ``z``; backward: ``decode_vjp`` on the saved INPUT (it recomputes the
+    forward with saves, so nothing but z outlives the call)."""
+
+    @staticmethod
+    def forward(ctx, z, vae, lens):
+        ctx.vae, ctx.lens = vae, lens
+        ctx.save_for_backward(z)
+        return vae._decode_launches(z, lens)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_feats):
+        (z,) = ctx.saved_tensors
+        return ctx.vae.decode_vjp(z, ctx.lens, d_feats, want_out=False)[1].to(z.dtype), None, None
+
+
+DEC_MAX_FRAMES, DEC_MAX_CHUNKS = 256, 16     # VD_MAX_FRAMES, VD_MAX_CHUNKS (csrc/vae_dec.hpp)
+
+
+def decode_vjp_refusal(bs, nframes, n_chunks, latent_dim=128, num_heads=2, ff_size=1024, num_layers=5, latent_size=1):
+    """Why ``ConvoFusionVae.decode`` cannot be differentiated at these shapes, or None when it can: the message names the limit that is
+    exceeded.  Pure: no library, no device."""
+    if (latent_dim, num_heads, ff_size, latent_size) != (128, 2, 1024, 1) or num_layers > 9 or num_layers % 2 == 0:
+        return (f"the HIP VAE decoder's backward is specialised for latent_dim [1, 128], 2 heads, ff_size 1024 and odd num_layers <= 9; this "
+                f"module has latent_dim [{latent_size}, {latent_dim}], {num_heads} heads, ff_size {ff_size}, {num_layers} layers")
+    if nframes > DEC_MAX_FRAMES:
+        return f"nframes = {nframes} exceeds the decoder backward's {DEC_MAX_FRAMES} frames"
+    if n_chunks > DEC_MAX_CHUNKS:
+        return f"n_chunks = {n_chunks} exceeds the decoder backward's {DEC_MAX_CHUNKS} latent chunks per sequence"
+    if bs > 65535:
+        return f"bs = {bs} exceeds the decoder backward's 65535 sequences per call"
+    return None
+
+
+def decoder_pack_floats(num_layers):
+    """Floats of the packed decoder weights (vd_pack_floats, csrc/vae_dec.hpp)."""
+    d, ff = 128, 1024
+    layer = 6 * d + 2 * (2 * 3 * d * d + 3 * d) + 2 * (2 * d * d + d) + 2 * (2 * d * ff) + ff + d
+    stack = num_layers * layer + (num_layers - 1) // 2 * (4 * d * d + d) + 2 * d + 2 * d * d + d
+    return 2 * stack + (DEC_MAX_FRAMES + DEC_MAX_CHUNKS) * d
 
 
 def _mirror_of(vae, skip):

@@ -563,6 +563,27 @@ typedef struct {
   cfd_memory mem[CFD_NUM_MEM];   /* as in cfd_forward: U distinct memories, an optional row_map [Be], key-padding masks */
 } cfd_vjp_args;
 int cfd_denoise_vjp(cfd_handle h, const cfd_vjp_args* args, const float* d_out, float* out, float* grad, void* stream);
+/* ConvoFusionVae.decode together with its vector-Jacobian product with respect to the latents: replaces
+ *   z.requires_grad_(True); feats = vae.decode(z, lengths); torch.autograd.grad(feats, z, d_feats)
+ * i.e. autograd over convofusion/models/architectures/vae.py:268-372 (two SkipTransformerDecoders, cross_attention.py:66-125, of pre-norm
+ * TransformerDecoderLayers :361-382).  One call recomputes the forward of both stacks with saved activations and runs the reverse sweep from
+ * the cotangent at the 189 output features back to z (csrc/vae_dec.hpp): exact float32, no atomics -- two calls on the same inputs return
+ * the same bits.  z enters only as the cross-attention memory z[s] + mem_pos_decoder.pe; the queries are query_pos_decoder.pe rows.  No
+ * gradients to weights or lengths.  Every launch (a few dozen) is enqueued on `stream`; the call does not wait.  The workspace belongs to
+ * the handle and to this call alone: a sampling run, a cfd_weg_eval or a cfd_denoise_vjp on the same handle share nothing with it.
+ *   feats  dev [bs][nframes][189] or NULL: the forward as this call computed it, frames at or beyond lengths[b] exactly 0
+ *   d_z    dev [2][bs][n_chunks][128]: d_feats^T . d(feats)/d(z); cotangent entries of frames at or beyond lengths[b] are not read
+ * Limits (CFD_E_ARG names the one exceeded): d_model 128, 2 heads, ff 1024, odd num_layers <= 9; 1 <= nframes <= 256; 1 <= n_chunks <= 16;
+ * 1 <= bs <= 65535. */
+typedef struct {
+  const float* wpack;        /* dev: packed decoder weights of both stacks and the two PE tables, layout in csrc/vae_dec.hpp */
+  int d_model, num_heads, ff_size, num_layers;
+  int bs, nframes, n_chunks;
+  const float* z;            /* dev [2 (body, hands)][bs][n_chunks][128] */
+  const int32_t* lengths;    /* dev [bs], each in [1, nframes]; the caller checks max == nframes */
+  const float* d_feats;      /* dev [bs][nframes][189]: cotangent at decode's output */
+} cfd_vae_decode_vjp_args;
+int cfd_vae_decode_vjp(cfd_handle h, const cfd_vae_decode_vjp_args* a, float* feats, float* d_z, void* stream);
 int cfd_sample_write(cfd_handle h, const float* latents);
 int cfd_sample_inpaint(cfd_handle h);
 

@@ -75,6 +75,13 @@ int cfd_debug_stop_stage(cfd_handle h, int stage);
 int cfd_debug_forward_operands(cfd_handle h, int policy);
 /* Micro-benchmark: average ms of `iters` launches of the [J x K] x [512 x K]^T residual GEMM (I must be 512). */
 int cfd_bench_gemm(cfd_handle h, int I, int J, int K, int tile_cfg, int iters, float* ms_out);
+/* cfd_debug_read also reads the taps the last cfd_vae_decode_vjp left in the handle's VAE workspace (float32; fp = nframes rounded up to
+ * 16, token rows ((stack * bs + b) * fp + f); rows of 16-frame tiles wholly beyond a sequence's length read 0 in "vae.g.*" and are not
+ * written in "vae.x.*"):
+ *   "vae.g.<l>"   [2 * bs * fp][128]   the running gradient at layer l's output, as it enters the layer's backward
+ *   "vae.dz.<l>"  [2][bs][16][128]     layer l's memory-side contribution to d_z (rows >= n_chunks: no meaning)
+ *   "vae.x.<l>"   [2 * bs * fp][128]   the forward's stream at layer l's input; l = num_layers: the last layer's output
+ *   "vae.info"    2 floats: the launches of the call, fp */
 int cfd_debug_read(cfd_handle h, const char* what, float* dst_dev, size_t numel);
 
 /* Test hook: stop the reverse sweep of a row-tile cfd_weg_eval (csrc/weg_rt.hpp, csrc/rowtile_bwd.hpp) behind one launch.

@@ -139,6 +139,13 @@ struct WegState {
   std::vector<long long> sig;   // timestep, shapes, memory pointers and arena of the last evaluation (reuse_memory_side)
   int launches = 0;
   void invalidate() { sig.clear(); }   // cfd_load_tensor: the next evaluation reuses no memory-side result
+  // cfd_denoise_vjp_mem (weg_rt.hpp, MemGrad): float32 copies of the folded A | VV ([nl][512][5 x 512] each, memory j's columns at
+  // 512 j) and c ([nl][5][512]), unscaled, from the float64 fold -- 2 x nl x 512 x 2560 x 4 B = 94 MB at nine layers -- built by the
+  // first call that asks for a memory gradient (memw_wver: the weights' generation they were folded from) and freed with the handle;
+  // the call's planes (dS', P', T, G, dn' per memory) and inverse row maps.
+  DBuf memw_a, memw_v, memw_c, mem_ws, mem_inv;
+  long long memw_wver = -1;
+  std::vector<int32_t> mem_inv_host;
 };
 
 // One problem's device workspace: what the launches of a forward touch.  setup_problem sizes it at its end, from the problem's path

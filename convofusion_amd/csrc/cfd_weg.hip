@@ -1,6 +1,7 @@
 // libcfdenoise: word-excitation guidance -- the launch-by-launch float32 pieces (cfd_gemm_f32 ... cfd_weg_focus) and cfd_weg_eval: one evaluation of the word-excitation-guidance objective and its gradient, all launches enqueued from C++
 // (float32 launch sequence: weg_eval.hpp; small problems on the row-tile kernels: rowtile_bwd.hpp, weg_rt.hpp) -- and cfd_denoise_vjp, the
-// vector-Jacobian product of one forward with respect to its sample on the same row-tile kernels.
+// vector-Jacobian product of one forward with respect to its sample on the same row-tile kernels, with cfd_denoise_vjp_mem, which adds
+// the product with respect to the five memories.
 #include "cfd_internal.hpp"
 #include "grad.hpp"
 
@@ -304,8 +305,9 @@ extern "C" int cfd_weg_eval(cfd_handle c, const cfd_weg_args* a, float* losses, 
 
 // ---- cfd_denoise_vjp: d_out^T . d(out)/d(sample) of one denoiser forward on the row-tile kernels --------------------------------
 // Every refusal, before anything is touched; the row maps come back as the host sees them (part of what the problem is prepared for).
-static int check_vjp_args(Ctx* c, const cfd_vjp_args* a, const float* d_out, const float* grad, std::vector<long long>* maps, HostMaps* hm) {
-  if (!c || !a || !a->sample || !d_out || !grad) return fail(CFD_E_ARG, "null argument");
+// `wants`: some result is asked for (cfd_denoise_vjp: grad; cfd_denoise_vjp_mem: grad or a d_mem[j]).
+static int check_vjp_args(Ctx* c, const cfd_vjp_args* a, const float* d_out, bool wants, std::vector<long long>* maps, HostMaps* hm) {
+  if (!c || !a || !a->sample || !d_out || !wants) return fail(CFD_E_ARG, "null argument");
   if (!c->finalized) return fail(CFD_E_STATE, "weights not finalized");
   const int Be = a->Be, L = a->L;
   if (Be < 1 || L < 2) return fail(CFD_E_ARG, "bad batch / length");
@@ -337,10 +339,14 @@ static int check_vjp_args(Ctx* c, const cfd_vjp_args* a, const float* d_out, con
   return CFD_OK;
 }
 
-extern "C" int cfd_denoise_vjp(cfd_handle c, const cfd_vjp_args* a, const float* d_out, float* out, float* grad, void* stream) {
+// One body for cfd_denoise_vjp (d_mem == null) and cfd_denoise_vjp_mem: the same arena, workspace, stream and census; the memory
+// gradient adds its own buffers (WegState::mem_ws, the float32 folded weights) and launches (wegrt::MemGrad) and nothing else.
+static int denoise_vjp(Ctx* c, const cfd_vjp_args* a, const float* d_out, float* out, float* grad, float* const* d_mem, void* stream) {
   std::vector<long long> maps;
   HostMaps hm;
-  CHK(check_vjp_args(c, a, d_out, grad, &maps, &hm));
+  bool any_mem = false;
+  for (int j = 0; d_mem && j < CFD_NMEM; ++j) any_mem = any_mem || d_mem[j] != nullptr;
+  CHK(check_vjp_args(c, a, d_out, grad != nullptr || any_mem, &maps, &hm));
   c->hint_now = c->hint_same_mem = false;
   CHK(settle_deferred_census(c));
   WegState& w = c->weg;
@@ -360,7 +366,12 @@ extern "C" int cfd_denoise_vjp(cfd_handle c, const cfd_vjp_args* a, const float*
   w.dstep_host = 0;
   HIPCHK(hipMemcpyAsync(c->wk[1].trows.p, &w.t_host, 4, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(c->wk[1].d_step.p, &w.dstep_host, 4, hipMemcpyHostToDevice, st));
-  const int r = wegrt::enqueue_vjp(c, st, a->sample, d_out, grad);
+  wegrt::MemGrad mg;
+  if (any_mem) {
+    CHK(wegrt::ensure_memw_f32(c, st));
+    CHK(wegrt::prepare_mem_grad(c, st, a->Be, a->L, a->mem, hm, d_mem, mg));
+  }
+  const int r = wegrt::enqueue_vjp(c, st, a->sample, d_out, grad, any_mem ? &mg : nullptr);
   w.launches = w.rt.launches;
   if (r == CFD_OK && out)
     HIPCHK(hipMemcpyAsync(out, c->wk[1].eps.p, (size_t)a->Be * a->L * CFD_LAT * 4, hipMemcpyDeviceToDevice, st));
@@ -368,4 +379,15 @@ extern "C" int cfd_denoise_vjp(cfd_handle c, const cfd_vjp_args* a, const float*
   HIPCHK(hipStreamSynchronize(st));
   CHK(r);
   return check_saturation(c, "cfd_denoise_vjp (sample, memories / their projections)");
+}
+
+extern "C" int cfd_denoise_vjp(cfd_handle c, const cfd_vjp_args* a, const float* d_out, float* out, float* grad, void* stream) {
+  if (!grad) return fail(CFD_E_ARG, "null argument");
+  return denoise_vjp(c, a, d_out, out, grad, nullptr, stream);
+}
+
+extern "C" int cfd_denoise_vjp_mem(cfd_handle c, const cfd_vjp_args* a, const float* d_out, float* out, float* grad, float* const d_mem[CFD_NUM_MEM],
+                                   void* stream) {
+  if (!d_mem) return fail(CFD_E_ARG, "null argument");
+  return denoise_vjp(c, a, d_out, out, grad, d_mem, stream);
 }

@@ -24,6 +24,11 @@
 // and at the bottom  grad = (g_d + LN1'(dy1)) We  [16 x 128].
 // cfd_denoise_vjp seeds the same sweep at the forward's output: dyN = d_out Wp  [16 x 512] (the rows prologue with K = 128), and the top
 // layer's B1 then reads dyN through decoder.norm with no running gradient yet (weg_rt.hpp, SweepSeed).
+// cfd_denoise_vjp_mem adds the KEY side, behind B5 of every layer (weg_rt.hpp, MemGrad; the kernels at the end of this file):
+//   B5e the EMIT instance of B5 also stores dS' and P' = p rs                          [16 x Sp_tot] each
+//   M1  T = LN2(x) A_j,  M2  G = g_b VV_j   for the wanted memories                    [16 x 512] each
+//   M3  dn'_s += sum_tokens dS'_s (T + c_j) + P'_s G   (a workgroup owns 16 keys of one instance)
+// and once at the end  d_mem = LNmem'(dn')  for the real keys.
 #pragma once
 #include "rowtile.hpp"
 
@@ -33,7 +38,7 @@ __device__ __forceinline__ float rt_gelu_grad(float y) {      // d/dy of the erf
   return 0.5f * (1.0f + erff(y * 0.70710678118654752440f)) + y * expf(-0.5f * y * y) * 0.39894228040143267794f;
 }
 
-enum { RT_BPRO_ROWS = 0, RT_BPRO_LN = 1, RT_BPRO_TB = 2 };
+enum { RT_BPRO_ROWS = 0, RT_BPRO_LN = 1, RT_BPRO_TB = 2, RT_BPRO_LNFWD = 3 };   // LNFWD: the rows are LayerNorm(x) gamma + beta (no gradient)
 enum { RT_BEPI_F32 = 0, RT_BEPI_GELU = 1 };
 
 struct RtBwdArgs {
@@ -42,9 +47,9 @@ struct RtBwdArgs {
   // prologue inputs
   const float* a;        // ROWS: the operand rows fp32 [M][K];  LN / TB: dy, the gradient at the LayerNorm's / the TimeBlock linear's output [M][512]
   const float* g;        // LN / TB: running gradient rows [M][512] (null: zero)
-  const float* x;        // LN / TB: the LayerNorm's input rows [M][512]
+  const float* x;        // LN / TB / LNFWD: the LayerNorm's input rows [M][512]
   const float* gamma;    // LayerNorm weight
-  const float* beta;     // TB: LayerNorm bias
+  const float* beta;     // TB / LNFWD: LayerNorm bias
   const float* ss;       // TB: (1 + scale | shift) of this time block at this step [1024]
   float* gout;           // LN / TB: the updated running gradient, written by workgroup x == 0
   // weights: fp32 [K][ldw], outputs n contiguous
@@ -174,6 +179,17 @@ __global__ void __launch_bounds__(512) rt_bwd_gemm_kernel(const RtBwdArgs a) {
       const float4 d = *reinterpret_cast<const float4*>(a.a + prow * K + 128 * i + 4 * plr);
       rows[i][0] = d.x; rows[i][1] = d.y; rows[i][2] = d.z; rows[i][3] = d.w;
     }
+  } else if constexpr (PRO == RT_BPRO_LNFWD) {   // x, gamma, beta of this lane's 16 columns
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int c = 128 * i + 4 * plr;
+      const float4 xx = *reinterpret_cast<const float4*>(a.x + prow * CFD_D + c);
+      const float4 ga = *reinterpret_cast<const float4*>(a.gamma + c);
+      const float4 be = *reinterpret_cast<const float4*>(a.beta + c);
+      r.xv[i][0] = xx.x; r.xv[i][1] = xx.y; r.xv[i][2] = xx.z; r.xv[i][3] = xx.w;
+      r.gam[i][0] = ga.x; r.gam[i][1] = ga.y; r.gam[i][2] = ga.z; r.gam[i][3] = ga.w;
+      r.bet[i][0] = be.x; r.bet[i][1] = be.y; r.bet[i][2] = be.z; r.bet[i][3] = be.w;
+    }
   } else {
     rt_bwd_row_load<PRO == RT_BPRO_TB>(r, a.a, a.g, a.x, a.gamma, a.beta, a.ss, prow, plr);
   }
@@ -196,6 +212,27 @@ __global__ void __launch_bounds__(512) rt_bwd_gemm_kernel(const RtBwdArgs a) {
     for (int i = 0; i < NR; ++i) {
       *reinterpret_cast<float2*>(img + pr * RS + 128 * i + 4 * plr) = make_float2(rows[i][0], rows[i][1]);
       *reinterpret_cast<float2*>(img + pr * RS + 128 * i + 4 * plr + 2) = make_float2(rows[i][2], rows[i][3]);
+    }
+  } else if constexpr (PRO == RT_BPRO_LNFWD) {   // y = LayerNorm(x) gamma + beta, the statistics as rt_ln_bwd_row takes them
+    float sm = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) sm += r.xv[i][e];
+    const float mean = rt_row_sum<32>(sm) * (1.0f / CFD_D);
+    float ss = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { r.xv[i][e] -= mean; ss += r.xv[i][e] * r.xv[i][e]; }
+    const float rstd = 1.0f / sqrtf(rt_row_sum<32>(ss) * (1.0f / CFD_D) + 1e-5f);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      float y[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) y[e] = r.xv[i][e] * rstd * r.gam[i][e] + r.bet[i][e];
+      *reinterpret_cast<float2*>(img + pr * RS + 128 * i + 4 * plr) = make_float2(y[0], y[1]);
+      *reinterpret_cast<float2*>(img + pr * RS + 128 * i + 4 * plr + 2) = make_float2(y[2], y[3]);
     }
   } else {
     float gn[4][4];
@@ -260,6 +297,8 @@ struct RtXBwdArgs {
   float* dP;                    // [M][Sp_tot]
   int dp_from_datt;             // B5 of the top layer: dP is d_att alone (no B4 ran)
   float* dy;                    // B5 output [M][512]
+  float* dSp;                   // B5 <EMIT>: dS' = dS rs [M][Sp_tot] ...
+  float* Pp;                    // ... and P' = p rs [M][Sp_tot], for the key-side accumulation (rt_xbwd_dn_kernel)
 };
 
 // dynamic LDS of rt_xbwd_dp_kernel
@@ -365,7 +404,8 @@ __global__ void __launch_bounds__(512) rt_xbwd_dp_kernel(const RtXBwdArgs a) {
 // grid (32, tiles); dynamic LDS: dS image + 8 KB (reduction) + 512 (sums) + 8 KB (cell statistics) + 1 KB (per-memory statistics)
 // ------------------------------------------------------------------------------------------------
 constexpr int rt_xbwd_dy_lds(int sp_tot) { return 16 * RT_BSTRIDE(sp_tot) * 4 + 8 * 1024 + 512 + 16 * 32 * 16 + 16 * 8 * 8; }
-template <int MAXKEYS>
+// EMIT (cfd_denoise_vjp_mem): workgroup x == 0 also stores the two planes it holds anyway, dS' and P' = p rs, as float32 [M][Sp_tot].
+template <int MAXKEYS, bool EMIT = false>
 __global__ void __launch_bounds__(512) rt_xbwd_dy_kernel(const RtXBwdArgs a) {
   constexpr int NW = 8, LPR = 32;
   constexpr int MAXC = MAXKEYS / 4 / LPR;                        // 4-key chunks per lane
@@ -504,6 +544,13 @@ __global__ void __launch_bounds__(512) rt_xbwd_dy_kernel(const RtXBwdArgs a) {
         }
         *reinterpret_cast<float2*>(img + pr * RS + c0) = make_float2(ds[0], ds[1]);
         *reinterpret_cast<float2*>(img + pr * RS + c0 + 2) = make_float2(ds[2], ds[3]);
+        if constexpr (EMIT) {
+          if (blockIdx.x == 0 && pr < nq) {     // (c0 + 3 < Sp_tot: cj[n] >= 0; the rows of a ragged tile once)
+            *reinterpret_cast<float4*>(a.dSp + (tok0 + pr) * KS + c0) = make_float4(ds[0], ds[1], ds[2], ds[3]);
+            *reinterpret_cast<float4*>(a.Pp + (tok0 + pr) * KS + c0) =
+                make_float4(s[n][0] * rsv[n][0], s[n][1] * rsv[n][1], s[n][2] * rsv[n][2], s[n][3] * rsv[n][3]);
+          }
+        }
       }
     wsum = rt_row_sum<LPR>(wsum);
     if (plr == 0) dcq[pr * 8 + j] = wsum;
@@ -674,4 +721,151 @@ __global__ void __launch_bounds__(256) rt_selfattn_bwd_kernel(const RtSelfBwdArg
       *reinterpret_cast<float4*>(o) = make_float4(acc[0] * sc, acc[1] * sc, acc[2] * sc, acc[3] * sc);
     }
   }
+}
+
+// ------------------------------------------------------------------------------------------------
+// cfd_denoise_vjp_mem: the key side of the cross-attention backward, in the folded formulation.  With n_s = (a_s + b) rs_s the
+// normalised memory row, score = y . (A n_s) + c . n_s and value VV n_s, one layer adds to the gradient at n_s
+//   dn_s = sum_l dS_ls (y_l A + c) + sum_l p_ls (gn_l VV)
+// and this kernel accumulates dn'_s = rs_s dn_s from the planes B5<EMIT> left (dS' = dS rs, P' = p rs) and the two token-side
+// products T = y A, G = gn VV (rt_bwd_gemm_kernel).  A workgroup OWNS 16 keys of one instance of one memory: it walks the batch rows
+// that map to the instance in ascending order (the inverse row map) and their tokens four at a time, wave w holding features
+// 64 w .. 64 w + 63 as four 16 x 16 tiles D[feature][key], and adds its tile into the float32 plane [U_j Sp_j][512] that no other
+// workgroup touches; the layers are consecutive launches.  No LDS, no atomics, nothing summed across workgroups: the same bits
+// every time.  Masked and padded keys have dS' = P' = 0 and an instance no row maps to has no terms: exact zeros.
+// ------------------------------------------------------------------------------------------------
+struct RtXDnArgs {
+  int L, Sp_tot;
+  int ldt;                          // row stride of T and G (512 x the memories of the launch span)
+  int first;                        // the sweep's first layer: the plane is written, not added to
+  const float* dSp;                 // [M][Sp_tot]
+  const float* Pp;                  // [M][Sp_tot]
+  const float* T;                   // [M][ldt]: y A_j at columns tcol[j] ...
+  const float* G;                   // [M][ldt]: gn VV_j
+  const float* cvec[CFD_NMEM];      // c_j of this layer [512]
+  float* plane[CFD_NMEM];           // [U_j * Sp_j][512]
+  const int* inv_off[CFD_NMEM];     // [U_j + 1]: instance u's rows are inv_rows[inv_off[u] .. inv_off[u + 1])
+  const int* inv_rows[CFD_NMEM];    // [Be]: the batch rows by instance, ascending within one
+  int Sp[CFD_NMEM], off[CFD_NMEM], tcol[CFD_NMEM];
+  int blk0[CFD_NMEM + 1];           // first workgroup of memory j: U_j * Sp_j / 16 of them, none for a memory that is not wanted
+};
+
+template <int CFD_KI = 0>
+__global__ void __launch_bounds__(512) rt_xbwd_dn_kernel(const RtXDnArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int l15 = lane & 15, q4 = lane >> 4;
+  int j = 0;
+#pragma unroll
+  for (int q = 1; q < CFD_NMEM; ++q)
+    if ((int)blockIdx.x >= a.blk0[q]) j = q;
+  const int Sp = rt_sel(a.Sp, j), nkb = Sp / 16;
+  int blk_first = 0;
+#pragma unroll
+  for (int q = 1; q < CFD_NMEM; ++q)
+    if (j == q) blk_first = a.blk0[q];
+  const int local = (int)blockIdx.x - blk_first;
+  const int u = local / nkb, s0 = (local - u * nkb) * 16;
+  const int* ioff = rt_sel(a.inv_off, j);
+  const int* irow = rt_sel(a.inv_rows, j);
+  const int r0 = ioff[u], r1 = ioff[u + 1];
+  const int f0 = wid * 64;
+  const float* cp = rt_sel(a.cvec, j) + f0 + l15;
+  float cv[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) cv[t] = cp[16 * t];
+  const long long kcol = rt_sel(a.off, j) + s0 + l15;
+  const long long fcol = rt_sel(a.tcol, j) + f0 + l15;
+  f32x4 acc[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int ri = r0; ri < r1; ++ri) {
+    const long long base = (long long)irow[ri] * a.L;
+    for (int t0 = 0; t0 < a.L; t0 += 4) {
+      // (loads at clamped tokens, zeroed by selects: a tail of L % 4 tokens multiplies valid elements by zero)
+      const bool ok = t0 + q4 < a.L;
+      const long long row = base + min(t0 + q4, a.L - 1);
+      const float ds0 = a.dSp[row * a.Sp_tot + kcol], pp0 = a.Pp[row * a.Sp_tot + kcol];
+      float tv[4], gv[4];
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        tv[t] = a.T[row * a.ldt + fcol + 16 * t];
+        gv[t] = a.G[row * a.ldt + fcol + 16 * t];
+      }
+      const float ds = ok ? ds0 : 0.f, pp = ok ? pp0 : 0.f;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        acc[t] = RT_MFMA_F32(ok ? tv[t] + cv[t] : 0.f, ds, acc[t], 0, 0, 0);   // D[feature][key]
+        acc[t] = RT_MFMA_F32(ok ? gv[t] : 0.f, pp, acc[t], 0, 0, 0);
+      }
+    }
+  }
+  float* pl = rt_sel(a.plane, j) + ((long long)u * Sp + s0 + l15) * CFD_D + f0 + 4 * q4;
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    float4 o = make_float4(acc[t][0], acc[t][1], acc[t][2], acc[t][3]);
+    if (!a.first) {
+      const float4 p = *reinterpret_cast<const float4*>(pl + 16 * t);
+      o.x += p.x; o.y += p.y; o.z += p.z; o.w += p.w;
+    }
+    *reinterpret_cast<float4*>(pl + 16 * t) = o;
+  }
+}
+
+// The plane back through the affine-free memory LayerNorm, one wave per REAL key row (u, s < S_j) of a wanted memory:
+//   x = raw + E_cond + pe_s + temb,  n = (x - mean x) rstd,   d_raw = dn' - mean(dn') - n mean(dn' . n)
+// -- the formulas of layernorm_bwd_f32_kernel (grad.hpp) with gamma = 1 and WITHOUT its leading rstd: the plane holds dn' = rs dn,
+// the scale came in once with dS' and P'.  d_mem is [U_j][S_j][512]; a masked key's row of the plane is zero and so is its result.
+struct RtMemLnArgs {
+  const float* raw[CFD_NMEM];       // [U_j][S_j][512]
+  const float* plane[CFD_NMEM];     // [U_j * Sp_j][512]
+  float* dmem[CFD_NMEM];            // [U_j][S_j][512]
+  const float* cond;                // condition_embedding.weight [5][512]
+  const float* pe;                  // mem_pos.pe
+  const float* temb;                // the time embedding of this call's timestep [512]
+  int S[CFD_NMEM], Sp[CFD_NMEM];
+  int row0[CFD_NMEM + 1];           // first row of memory j: U_j * S_j of them, none for a memory that is not wanted
+};
+
+template <int CFD_KI = 0>
+__global__ void __launch_bounds__(256) rt_mem_ln_bwd_kernel(const RtMemLnArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int g = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+  if (g >= a.row0[CFD_NMEM]) return;
+  int j = 0;
+#pragma unroll
+  for (int q = 1; q < CFD_NMEM; ++q)
+    if (g >= a.row0[q]) j = q;
+  const int S = rt_sel(a.S, j), Sp = rt_sel(a.Sp, j);
+  int row_first = 0;
+#pragma unroll
+  for (int q = 1; q < CFD_NMEM; ++q)
+    if (j == q) row_first = a.row0[q];
+  const int local = g - row_first;
+  const int u = local / S, s = local - u * S;
+  const float* r = rt_sel(a.raw, j) + ((long long)u * S + s) * CFD_D + lane * 8;
+  const float* ce = a.cond + (long long)j * CFD_D + lane * 8;
+  const float* pe = a.pe + (long long)s * CFD_D + lane * 8;
+  const float* te = a.temb + lane * 8;
+  const float* dp = rt_sel(a.plane, j) + ((long long)u * Sp + s) * CFD_D + lane * 8;
+  float v[8], d[8];
+  float sum = 0.f;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    v[e] = ((r[e] + te[e]) + ce[e]) + pe[e];
+    d[e] = dp[e];
+    sum += v[e];
+  }
+  const float mean = wave_sum(sum) * (1.0f / CFD_D);
+  float ss = 0.f;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) { v[e] -= mean; ss += v[e] * v[e]; }
+  const float rstd = 1.0f / sqrtf(wave_sum(ss) * (1.0f / CFD_D) + 1e-5f);
+  float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) { v[e] *= rstd; s1 += d[e]; s2 = fmaf(d[e], v[e], s2); }
+  const float m1 = wave_sum(s1) * (1.0f / CFD_D), m2 = wave_sum(s2) * (1.0f / CFD_D);
+  float* o = rt_sel(a.dmem, j) + ((long long)u * S + s) * CFD_D + lane * 8;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) o[e] = d[e] - m1 - v[e] * m2;
 }

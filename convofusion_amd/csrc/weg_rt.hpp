@@ -3,7 +3,8 @@
 // ~160 launches of ~5 us instead of weg_eval.hpp's ~400 launches of ~10 us, in the folded formulation the sampling loop itself uses.
 // The evaluation has a workspace of its own (Ctx::wk[1]): it runs between two replays of an open sampling run's captured graph.
 // cfd_denoise_vjp (the vector-Jacobian product of the forward with respect to its sample) runs the same forward through the whole network
-// and the same sweep from a seed at the output, in the same arena and workspace (enqueue_vjp).
+// and the same sweep from a seed at the output, in the same arena and workspace (enqueue_vjp); cfd_denoise_vjp_mem adds the gradient at
+// the memories to that sweep (MemGrad: three launches per layer behind B5 and one at the end).
 // Included by cfd_weg.hip after weg_eval.hpp.
 #pragma once
 
@@ -171,14 +172,179 @@ struct SweepSeed {
   const float* d_out = nullptr;
 };
 
-// reverse sweep (rowtile_bwd.hpp): B1 .. B9 per layer from the top, then the embedding's backward into `grad`
-static int enqueue_reverse_sweep(Ctx* c, hipStream_t st, const SweepSeed& seed, float* grad) {
+// What cfd_denoise_vjp_mem adds to the sweep: the gradient at the memories of `want`, d_mem[j] [U_j][S_j][512].
+// Per layer, behind B5 (its EMIT instance leaves dS' and P'): T = LayerNorm2(x) . A and G = gn . VV over the span of wanted memories
+// (two launches of rt_bwd_gemm_kernel against the float32 folded weights), then the key-side accumulation into the memories' planes
+// (rt_xbwd_dn_kernel); behind the last layer one launch takes the planes through the memory LayerNorm (rt_mem_ln_bwd_kernel).
+struct MemGrad {
+  bool want[CFD_NMEM];
+  int j0 = 0, nspan = 0;              // the wanted memories lie in [j0, j0 + nspan)
+  float *dSp = nullptr, *Pp = nullptr, *T = nullptr, *G = nullptr, *plane[CFD_NMEM];
+  const int *inv_off[CFD_NMEM], *inv_rows[CFD_NMEM];
+  float* d_mem[CFD_NMEM];
+};
+
+// Float32 copies of the folded A, c and VV, unscaled, by the float64 fold of cfd_finalize_weights (cfd_core.hip) -- made when a
+// memory gradient is first asked for, and again after the weights changed.  Host work and set-up launches: never per call.
+static int ensure_memw_f32(Ctx* c, hipStream_t st) {
+  WegState& w = c->weg;
+  if (w.memw_wver == c->wver) return CFD_OK;
+  const int nl = c->nl, D = CFD_D;
+  const long long LD = (long long)CFD_NMEM * D;
+  HIPCHK(hipStreamSynchronize(st));
+  CHK(w.memw_a.ensure((size_t)nl * D * LD * 4));
+  CHK(w.memw_v.ensure((size_t)nl * D * LD * 4));
+  CHK(w.memw_c.ensure((size_t)nl * LD * 4));
+  DBuf tmpd;
+  CHK(tmpd.ensure((size_t)D * D * 8));
+  const dim3 blk(256);
+  auto grid1 = [](long long n) { return dim3((unsigned)((n + 255) / 256)); };
+  const double cs = std::sqrt(1.0 / (double)D);
+  for (int l = 0; l < nl; ++l) {
+    const std::string p = "decoder.layers." + std::to_string(l) + ".";
+    const float* fw = rawp(c, p + "att_fuser.weight");
+    if (!fw) return fail(CFD_E_STATE, "missing tensor '%satt_fuser.weight'", p.c_str());
+    for (int j = 0; j < CFD_NMEM; ++j) {
+      const std::string a = p + "multihead_attn_" + MEM_NAMES[j];
+      const float *ipw = rawp(c, a + ".in_proj_weight"), *ipb = rawp(c, a + ".in_proj_bias"), *ow = rawp(c, a + ".out_proj.weight");
+      const float* gam = rawp(c, p + MEM_NAMES[j] + "_norm.weight");
+      if (!ipw || !ipb || !ow || !gam) return fail(CFD_E_STATE, "missing tensor of '%s'", a.c_str());
+      const float *Wq = ipw, *Wk = ipw + (size_t)D * D, *Wv = ipw + (size_t)2 * D * D, *bq = ipb;
+      float* A = w.memw_a.as<float>() + (size_t)l * D * LD + (size_t)j * D;
+      float* V = w.memw_v.as<float>() + (size_t)l * D * LD + (size_t)j * D;
+      // A[o][i] = cs gamma[i] sum_r Wq[r][o] Wk[r][i];  c[i] = cs gamma[i] sum_r Wk[r][i] bq[r];  VV = Wf_j Wo Wv diag(gamma)
+      hipLaunchKernelGGL((fold_mm_kernel<float, float, float>), grid1((long long)D * D), blk, 0, st, Wq, 1LL, (long long)D, Wk, (long long)D, 1LL, A, LD, D, D,
+                         D, cs, gam);
+      hipLaunchKernelGGL((fold_mv_kernel<float, float, float>), grid1(D), blk, 0, st, Wk, 1LL, (long long)D, bq, (const double*)nullptr,
+                         (const float*)nullptr, w.memw_c.as<float>() + ((size_t)l * CFD_NMEM + j) * D, D, D, cs, gam);
+      hipLaunchKernelGGL((fold_mm_kernel<float, float, double>), grid1((long long)D * D), blk, 0, st, ow, (long long)D, 1LL, Wv, (long long)D, 1LL,
+                         tmpd.as<double>(), (long long)D, D, D, D, 1.0, (const float*)nullptr);
+      hipLaunchKernelGGL((fold_mm_kernel<float, double, float>), grid1((long long)D * D), blk, 0, st, fw + (size_t)j * D, (long long)5 * D, 1LL,
+                         tmpd.as<double>(), (long long)D, 1LL, V, LD, D, D, D, 1.0, gam);
+      HIPCHK(hipGetLastError());
+    }
+  }
+  HIPCHK(hipStreamSynchronize(st));   // (tmpd leaves scope)
+  w.memw_wver = c->wver;
+  return CFD_OK;
+}
+
+// The call's planes and the inverse row maps (host work: allocations and one upload; in front of the launches).
+static int prepare_mem_grad(Ctx* c, hipStream_t st, int Be, int L, const cfd_memory* mem, const HostMaps& hm, float* const d_mem[CFD_NMEM], MemGrad& mg) {
+  WegState& w = c->weg;
+  const size_t M = (size_t)Be * L, spt = (size_t)padded_keys(mem);
+  int j1 = -1;
+  mg.j0 = CFD_NMEM;
+  for (int j = 0; j < CFD_NMEM; ++j) {
+    mg.want[j] = d_mem[j] != nullptr;
+    mg.d_mem[j] = d_mem[j];
+    if (mg.want[j]) { mg.j0 = std::min(mg.j0, j); j1 = j; }
+  }
+  mg.nspan = j1 - mg.j0 + 1;
+  auto al = [](size_t n) { return (n + 63) & ~(size_t)63; };
+  const size_t n_sp = al(M * spt), n_t = al(M * (size_t)mg.nspan * CFD_D);
+  size_t n = 2 * n_sp + 2 * n_t;
+  size_t n_pl[CFD_NMEM];
+  for (int j = 0; j < CFD_NMEM; ++j) {
+    n_pl[j] = mg.want[j] ? al((size_t)mem[j].U * ((mem[j].S + 31) / 32 * 32) * CFD_D) : 0;
+    n += n_pl[j];
+  }
+  if (n * 4 > w.mem_ws.bytes) HIPCHK(hipStreamSynchronize(st));
+  CHK(w.mem_ws.ensure(n * 4));
+  float* p = w.mem_ws.as<float>();
+  auto take = [&](size_t k) { float* r = p; p += k; return r; };
+  mg.dSp = take(n_sp); mg.Pp = take(n_sp); mg.T = take(n_t); mg.G = take(n_t);
+  for (int j = 0; j < CFD_NMEM; ++j) mg.plane[j] = n_pl[j] ? take(n_pl[j]) : nullptr;
+  // inverse row maps: per memory [U_j + 1] offsets, then the Be rows by instance (ascending within an instance)
+  std::vector<int32_t> inv;
+  size_t at[CFD_NMEM];
+  for (int j = 0; j < CFD_NMEM; ++j) {
+    at[j] = inv.size();
+    const int U = mem[j].U;
+    std::vector<int32_t> cnt((size_t)U + 1, 0);
+    for (int b = 0; b < Be; ++b) ++cnt[(size_t)hm.m[j][b] + 1];
+    for (int u = 0; u < U; ++u) cnt[(size_t)u + 1] += cnt[u];
+    inv.insert(inv.end(), cnt.begin(), cnt.end());
+    for (int u = 0; u < U; ++u)
+      for (int b = 0; b < Be; ++b)
+        if (hm.m[j][b] == u) inv.push_back(b);
+  }
+  if (inv.size() * 4 > w.mem_inv.bytes || inv != w.mem_inv_host) {
+    HIPCHK(hipStreamSynchronize(st));
+    CHK(w.mem_inv.ensure(inv.size() * 4));
+    HIPCHK(hipMemcpy(w.mem_inv.p, inv.data(), inv.size() * 4, hipMemcpyHostToDevice));
+    w.mem_inv_host = inv;
+  }
+  for (int j = 0; j < CFD_NMEM; ++j) {
+    mg.inv_off[j] = w.mem_inv.as<int>() + at[j];
+    mg.inv_rows[j] = mg.inv_off[j] + mem[j].U + 1;
+  }
+  return CFD_OK;
+}
+
+// the three launches of one layer behind its B5: T, G, the key-side accumulation
+static int enqueue_mem_grad_layer(Ctx* c, hipStream_t st, const MemGrad& mg, int l, bool first, const RtBwdArgs& base, const float* gn, int ntile) {
+  WegRtState& s = c->weg.rt;
+  const Problem& p = c->w->pb;
+  const LayerW& lw = c->lw[l];
+  const long long LD = (long long)CFD_NMEM * CFD_D;
+  const int ldt = mg.nspan * CFD_D;
+  {   // T = LayerNorm2(x) . A_j for the memories of the span
+    RtBwdArgs a = base;
+    a.K = CFD_D; a.x = s.sv.x[l][2]; a.gamma = lw.ln2g; a.beta = lw.ln2b;
+    a.w = c->weg.memw_a.as<float>() + (size_t)l * CFD_D * LD + (size_t)mg.j0 * CFD_D; a.ldw = LD; a.out = mg.T; a.ldo = ldt;
+    CHK((bwd_gemm<RT_BPRO_LNFWD, RT_BEPI_F32, 16>(c, st, a, ldt, ntile)));
+  }
+  {   // G = gn . VV_j
+    RtBwdArgs a = base;
+    a.K = CFD_D; a.a = gn;
+    a.w = c->weg.memw_v.as<float>() + (size_t)l * CFD_D * LD + (size_t)mg.j0 * CFD_D; a.ldw = LD; a.out = mg.G; a.ldo = ldt;
+    CHK((bwd_gemm<RT_BPRO_ROWS, RT_BEPI_F32, 16>(c, st, a, ldt, ntile)));
+  }
+  RtXDnArgs d;
+  memset(&d, 0, sizeof(d));
+  d.L = p.L; d.Sp_tot = p.Sp_tot; d.ldt = ldt; d.first = first ? 1 : 0;
+  d.dSp = mg.dSp; d.Pp = mg.Pp; d.T = mg.T; d.G = mg.G;
+  int nwg = 0;
+  for (int j = 0; j < CFD_NMEM; ++j) {
+    d.cvec[j] = c->weg.memw_c.as<float>() + ((size_t)l * CFD_NMEM + j) * CFD_D;
+    d.plane[j] = mg.plane[j]; d.inv_off[j] = mg.inv_off[j]; d.inv_rows[j] = mg.inv_rows[j];
+    d.Sp[j] = p.Sp[j]; d.off[j] = p.off[j]; d.tcol[j] = (j - mg.j0) * CFD_D;
+    d.blk0[j] = nwg;
+    if (mg.want[j]) nwg += p.U[j] * (p.Sp[j] / 16);
+  }
+  d.blk0[CFD_NMEM] = nwg;
+  return sweep_launch(c, st, rt_xbwd_dn_kernel<>, dim3(nwg), 512, 0, d);
+}
+
+// behind the last layer: the planes through the memory LayerNorm into d_mem
+static int enqueue_mem_grad_finish(Ctx* c, hipStream_t st, const MemGrad& mg) {
+  const Problem& p = c->w->pb;
+  RtMemLnArgs a;
+  memset(&a, 0, sizeof(a));
+  a.cond = rawp(c, "condition_embedding.weight"); a.pe = rawp(c, "mem_pos.pe");
+  a.temb = c->w->temb_tab.as<float>();            // (one-row tables: this call's timestep)
+  int rows = 0;
+  for (int j = 0; j < CFD_NMEM; ++j) {
+    a.raw[j] = p.mem[j]; a.plane[j] = mg.plane[j]; a.dmem[j] = mg.d_mem[j]; a.S[j] = p.S[j]; a.Sp[j] = p.Sp[j];
+    a.row0[j] = rows;
+    if (mg.want[j]) rows += p.U[j] * p.S[j];
+  }
+  a.row0[CFD_NMEM] = rows;
+  return sweep_launch(c, st, rt_mem_ln_bwd_kernel<>, dim3((unsigned)((rows + 3) / 4)), 256, 0, a);
+}
+
+// reverse sweep (rowtile_bwd.hpp): B1 .. B9 per layer from the top, then the embedding's backward into `grad`.
+// mg (cfd_denoise_vjp_mem): B5 is its EMIT instance and three launches per layer follow it (enqueue_mem_grad_layer), one more the
+// last layer; `grad` may then be null, which skips the embedding's backward alone.  Without mg the launches are what they always were.
+static int enqueue_reverse_sweep(Ctx* c, hipStream_t st, const SweepSeed& seed, float* grad, const MemGrad* mg = nullptr) {
   WegRtState& s = c->weg.rt;
   Work* w = c->w;
   const Problem& p = w->pb;
   const int nl = c->nl, B = s.B, L = s.L, tpr = (L + 15) / 16, ntile = B * tpr;
   s.dy_keys = p.Sp_tot <= 512 ? 512 : RT_MAX_KEYS;
-  const auto dy_kernel = s.dy_keys == 512 ? rt_xbwd_dy_kernel<512> : rt_xbwd_dy_kernel<RT_MAX_KEYS>;
+  const auto dy_kernel = mg ? (s.dy_keys == 512 ? rt_xbwd_dy_kernel<512, true> : rt_xbwd_dy_kernel<RT_MAX_KEYS, true>)
+                            : (s.dy_keys == 512 ? rt_xbwd_dy_kernel<512> : rt_xbwd_dy_kernel<RT_MAX_KEYS>);
   static unsigned long long attr_done = 0;
   CHK(once_per_device(attr_done, c->cfg.device, [&]() -> int {
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&rt_xbwd_dy_kernel<512>), hipFuncAttributeMaxDynamicSharedMemorySize, rt_xbwd_dy_lds(512)));
@@ -187,6 +353,16 @@ static int enqueue_reverse_sweep(Ctx* c, hipStream_t st, const SweepSeed& seed, 
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&rt_selfattn_bwd_kernel<>), hipFuncAttributeMaxDynamicSharedMemorySize, rt_selfattn_bwd_lds()));
     return CFD_OK;
   }));
+  if (mg) {
+    static unsigned long long emit_attr_done = 0;
+    CHK(once_per_device(emit_attr_done, c->cfg.device, [&]() -> int {
+      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&rt_xbwd_dy_kernel<512, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 rt_xbwd_dy_lds(512)));
+      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&rt_xbwd_dy_kernel<RT_MAX_KEYS, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 rt_xbwd_dy_lds(RT_MAX_KEYS)));
+      return CFD_OK;
+    }));
+  }
   RtBwdArgs base;
   memset(&base, 0, sizeof(base));
   base.L = L; base.tpr = tpr;
@@ -194,6 +370,7 @@ static int enqueue_reverse_sweep(Ctx* c, hipStream_t st, const SweepSeed& seed, 
   memset(&xb, 0, sizeof(xb));
   xb.L = L; xb.tpr = tpr; xb.nl = nl; xb.Sp_tot = p.Sp_tot;   // (this step's table rows: Work::now_*, set by the forward)
   xb.rsp = w->p_sp.as<float>(); xb.d_att = s.d_att; xb.dP = s.dP; xb.dy = s.dy;
+  if (mg) { xb.dSp = mg->dSp; xb.Pp = mg->Pp; }
   int nkb = 0;
   for (int j = 0; j < CFD_NMEM; ++j) {
     xb.map[j] = p.map[j]; xb.S[j] = p.S[j]; xb.Sp[j] = p.Sp[j]; xb.off[j] = p.off[j];
@@ -265,6 +442,7 @@ static int enqueue_reverse_sweep(Ctx* c, hipStream_t st, const SweepSeed& seed, 
       CHK(sweep_launch(c, st, dy_kernel, dim3(CFD_D / 16, ntile), 512, rt_xbwd_dy_lds(p.Sp_tot), a));
     }
     WEG_STOP_AT(5);
+    if (mg) CHK(enqueue_mem_grad_layer(c, st, *mg, l, l == nl - 1, base, s.G[gi], ntile));   // (G[gi]: the gradient B4 wrote)
     {   // B6: norm2, then time block 1's projection
       RtBwdArgs a = base;
       a.K = CFD_D; a.a = s.dy; a.g = have_g ? s.G[gi] : nullptr; a.x = s.sv.x[l][2]; a.gamma = lw.ln2g; a.gout = s.G[(gi + 1) % 3];
@@ -297,7 +475,8 @@ static int enqueue_reverse_sweep(Ctx* c, hipStream_t st, const SweepSeed& seed, 
     WEG_STOP_AT(9);
   }
 #undef WEG_STOP_AT
-  {   // through layer 0's norm1 and the latent embedding
+  if (mg) CHK(enqueue_mem_grad_finish(c, st, *mg));
+  if (grad || !mg) {   // through layer 0's norm1 and the latent embedding
     RtBwdArgs a = base;
     a.K = CFD_D; a.a = dy1; a.g = s.G[gi]; a.x = s.sv.x[0][0]; a.gamma = c->lw[0].ln1g; a.gout = s.G[(gi + 1) % 3];
     a.w = rawp(c, "latent_embd.weight"); a.ldw = CFD_LAT; a.out = grad; a.ldo = CFD_LAT;
@@ -321,7 +500,7 @@ static int enqueue(Ctx* c, hipStream_t st, bool full, const weg::Args& e) {
 }
 
 // cfd_denoise_vjp's launches: time tables and memory side, the whole forward with saved activations, the sweep from the output
-static int enqueue_vjp(Ctx* c, hipStream_t st, const float* sample, const float* d_out, float* grad) {
+static int enqueue_vjp(Ctx* c, hipStream_t st, const float* sample, const float* d_out, float* grad, const MemGrad* mg = nullptr) {
   WorkGuard guard(c);
   WegRtState& s = c->weg.rt;
   const Problem& p = c->w->pb;
@@ -331,7 +510,7 @@ static int enqueue_vjp(Ctx* c, hipStream_t st, const float* sample, const float*
   s.focus_large = 0;
   CHK(enqueue_memory_side(c, st));
   CHK(enqueue_forward_saved(c, st, sample));
-  return enqueue_reverse_sweep(c, st, SweepSeed{d_out}, grad);
+  return enqueue_reverse_sweep(c, st, SweepSeed{d_out}, grad, mg);
 }
 
 }  // namespace wegrt

@@ -8,12 +8,19 @@ changing ``target`` in configs/modules/denoiser.yaml, and ``model.load_state_dic
 checkpoint loads strictly.  The torch modules below are parameter CONTAINERS only: the forward is
 the HIP path.
 
-Autograd: ``forward`` is differentiable with respect to ``sample`` -- and nothing else.  Under grad mode with
-``sample.requires_grad`` the returned output carries a ``grad_fn`` (``_DenoiseVjp``, once differentiable): its
-forward is the inference path (bit-identical output), its backward one ``cfd_denoise_vjp`` call, which recomputes the
-forward with saved activations and runs the reverse sweep of the row-tile kernels, so no activation state outlives a
-call.  The attention maps come back detached; no gradient reaches parameters or memories (one that requires grad is
-refused), and shapes beyond the row-tile path (``vjp_refusal``) and per-row timesteps are refused before any device work.
+Autograd: ``forward`` is differentiable with respect to ``sample`` -- and, with ``memory_grad=True``, with respect to
+its five memories; never to parameters.  Under grad mode with ``sample.requires_grad`` the returned output carries a
+``grad_fn`` (``_DenoiseVjp``, once differentiable): its forward is the inference path (bit-identical output), its
+backward one ``cfd_denoise_vjp`` call, which recomputes the forward with saved activations and runs the reverse sweep
+of the row-tile kernels, so no activation state outlives a call.  The attention maps come back detached; shapes beyond
+the row-tile path (``vjp_refusal``) and per-row timesteps are refused before any device work.
+
+Without the keyword no gradient reaches a memory (one that requires grad is refused).  ``forward(..., memory_grad=True)``
+takes the differentiable path when the sample OR a memory requires grad (``_DenoiseVjpMem``: the five memories are tensor
+arguments of the function; its backward is one ``cfd_denoise_vjp_mem`` call with one memory per batch row, so every input
+row gets its own gradient, as torch autograd gives the reference).  ``vjp_memories`` is the direct call: distinct memories
+with row maps receive the sum over the rows that share them, which is what fitting one conditioning tensor to several
+examples needs (``convofusion_amd.fit``).
 """
 import copy
 import ctypes as C
@@ -130,6 +137,30 @@ class _DenoiseVjp(torch.autograd.Function):
     def backward(ctx, d_out, *d_att):
         (sample,) = ctx.saved_tensors
         return ctx.denoiser.vjp(sample, ctx.t, ctx.mems, ctx.masks, d_out, side_engine=ctx.side)[1], None, None, None, None, None
+
+
+class _DenoiseVjpMem(torch.autograd.Function):
+    """``out`` of ``Denoiser._forward_hip`` as a function of ``sample`` and the five memories (tensor arguments, so that autograd reaches
+    them); backward: one cfd_denoise_vjp_mem on the saved INPUTS, one memory per batch row (U = Be, no row map)."""
+
+    @staticmethod
+    def forward(ctx, denoiser, timestep, mem_mask_dict, kwargs, sample, *mems):
+        out, att = denoiser._forward_hip(sample, timestep, list(mems), mem_mask_dict, kwargs)
+        ctx.denoiser, ctx.t, ctx.side = denoiser, int(torch.as_tensor(timestep).reshape(-1)[0].item()), bool(kwargs.get("side_engine", False))
+        ctx.masks = dict(mem_mask_dict or {})
+        ctx.save_for_backward(sample, *mems)
+        ctx.mark_non_differentiable(*att)
+        return (out, *att)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_out, *d_att):
+        sample, *mems = ctx.saved_tensors
+        need = ctx.needs_input_grad[4:]
+        wrt = tuple(name for name, n in zip(MEM_NAMES, need[1:]) if n)
+        _, grad, d_mem = ctx.denoiser.vjp_memories(sample, ctx.t, mems, ctx.masks, d_out, wrt=wrt, side_engine=ctx.side, want_out=False,
+                                                   want_grad=bool(need[0]))
+        return (None, None, None, None, grad) + tuple(d_mem.get(name) for name in MEM_NAMES)
 
 
 class _PE(nn.Module):
@@ -363,13 +394,58 @@ class Denoiser(nn.Module):
         del keep
         return out, grad
 
+    def vjp_memories(self, sample, timestep, encoder_hidden_states, mem_mask_dict, d_out, *, wrt=MEM_NAMES, row_maps=None, side_engine=False,
+                     want_out=True, want_grad=True):
+        """(out or None, grad, {name: d_out^T . d(out)/d(memory) [U_j, S_j, 512]}) of one forward: the direct ``cfd_denoise_vjp_mem``
+        call.  ``wrt``: the memories whose gradient is wanted (names of ``MEM_NAMES``).  ``row_maps`` as in ``pack_memories``: a
+        distinct memory receives the SUM over the batch rows that map to it, one that no row maps to exact zeros; masked keys receive
+        exact zeros.  ``grad`` is the sample's gradient as ``vjp`` returns it (bit for bit), or None with ``want_grad=False`` (at least
+        one memory must then be wanted)."""
+        Be, L, _ = sample.shape
+        wrt = tuple(wrt)
+        for name in wrt:
+            if name not in MEM_NAMES:
+                raise ValueError(f"wrt names a memory that does not exist: {name!r} (the memories are {', '.join(MEM_NAMES)})")
+        if not wrt and not want_grad:
+            raise ValueError("vjp_memories: nothing is wanted (wrt is empty and want_grad is False)")
+        if len(encoder_hidden_states) != _lib.NUM_MEM:
+            raise ValueError("encoder_hidden_states must be the 5-tuple (spk_emb, alsn, tlsn, apb, lsnemb)")
+        why = vjp_refusal(Be, L, [int(m.shape[1]) for m in encoder_hidden_states])
+        if why is not None:
+            raise NotImplementedError(f"the gradient of the HIP denoiser with respect to its memories runs on the row-tile path only: {why}")
+        lib = _lib.load()
+        h = self.engine(sample.device, mem_len=max(int(m.shape[1]) for m in encoder_hidden_states), side=bool(side_engine))
+        x = sample.detach().to(torch.float32).contiguous()
+        d = d_out.detach().to(device=x.device, dtype=torch.float32).contiguous()
+        if tuple(d.shape) != tuple(x.shape):
+            raise ValueError(f"d_out must have the sample's shape {list(x.shape)}")
+        mems, keep = self.pack_memories(encoder_hidden_states, mem_mask_dict, row_maps)
+        a = _lib.VjpArgs()
+        a.Be, a.L, a.timestep, a.sample, a.mem = Be, L, int(timestep), x.data_ptr(), mems
+        out = torch.empty_like(x) if want_out else None
+        grad = torch.empty_like(x) if want_grad else None
+        d_mem, ptrs = {}, (C.c_void_p * _lib.NUM_MEM)()
+        for j, name in enumerate(MEM_NAMES):
+            if name in wrt:
+                d_mem[name] = torch.empty(tuple(encoder_hidden_states[j].shape), dtype=torch.float32, device=x.device)
+                ptrs[j] = d_mem[name].data_ptr()
+        with torch.cuda.device(x.device):
+            _lib.check(lib.cfd_denoise_vjp_mem(h, C.byref(a), C.c_void_p(d.data_ptr()), C.c_void_p(out.data_ptr()) if want_out else None,
+                                               C.c_void_p(grad.data_ptr()) if want_grad else None, ptrs,
+                                               C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)))
+        del keep
+        return out, grad, d_mem
+
     # ---- forward -------------------------------------------------------------------------------
     def forward(self, sample, timestep, encoder_hidden_states, lengths=None, mem_mask_dict=dict(), **kwargs):
         """``kwargs['side_engine']=True`` (extension): run on the second handle, for calls made while a sampling run is
-        open on the first; every other keyword (``return_dict`` ...) is ignored like the reference does.
+        open on the first; ``kwargs['memory_grad']=True`` (extension): memories that require grad receive gradients too; every
+        other keyword (``return_dict`` ...) is ignored like the reference does.
         Under grad mode with ``sample.requires_grad`` the output is differentiable with respect to ``sample`` (module docstring)."""
         if sample.dim() != 3 or sample.shape[-1] != self.latent_dim:
             raise ValueError(f"sample must be [batch, tokens, {self.latent_dim}]")
+        if kwargs.get("memory_grad", False):
+            return self._forward_memory_grad(sample, timestep, encoder_hidden_states, mem_mask_dict, kwargs)
         if not (torch.is_grad_enabled() and sample.requires_grad):
             return self._forward_hip(sample, timestep, encoder_hidden_states, mem_mask_dict, kwargs)
         # every refusal of the differentiable forward, before any device work
@@ -386,6 +462,28 @@ class Denoiser(nn.Module):
         if why is not None:
             raise NotImplementedError(f"the gradient of the HIP denoiser with respect to its sample runs on the row-tile path only: {why}")
         out, *att = _DenoiseVjp.apply(sample, self, timestep, encoder_hidden_states, mem_mask_dict, kwargs)
+        return (out, list(att))
+
+    def _forward_memory_grad(self, sample, timestep, encoder_hidden_states, mem_mask_dict, kwargs):
+        """``forward(..., memory_grad=True)``: differentiable when grad is enabled and the sample or any memory requires grad."""
+        if len(encoder_hidden_states) != _lib.NUM_MEM:
+            raise ValueError("encoder_hidden_states must be the 5-tuple (spk_emb, alsn, tlsn, apb, lsnemb)")
+        if not (torch.is_grad_enabled() and (sample.requires_grad or any(m.requires_grad for m in encoder_hidden_states))):
+            return self._forward_hip(sample, timestep, encoder_hidden_states, mem_mask_dict, kwargs)
+        # every refusal, before any device work
+        for name, m in (mem_mask_dict or {}).items():
+            if m is not None and m.requires_grad:
+                raise NotImplementedError(f"the HIP denoiser has no gradient with respect to a key-padding mask ({name} requires grad)")
+        if torch.as_tensor(timestep).numel() != 1:
+            raise NotImplementedError("the gradient of the HIP denoiser with respect to its sample and memories needs one timestep for all rows "
+                                      "(a per-row timestep vector is not on the row-tile path)")
+        for name, m in zip(MEM_NAMES, encoder_hidden_states):
+            if m.dim() != 3 or m.shape[0] != sample.shape[0]:
+                raise ValueError(f"memory_grad=True takes one memory per batch row: {name} has shape {list(m.shape)} for {sample.shape[0]} rows")
+        why = vjp_refusal(sample.shape[0], sample.shape[1], [int(m.shape[1]) for m in encoder_hidden_states])
+        if why is not None:
+            raise NotImplementedError(f"the gradient of the HIP denoiser with respect to its sample and memories runs on the row-tile path only: {why}")
+        out, *att = _DenoiseVjpMem.apply(self, timestep, mem_mask_dict, kwargs, sample, *encoder_hidden_states)
         return (out, list(att))
 
     def _forward_hip(self, sample, timestep, encoder_hidden_states, mem_mask_dict, kwargs):

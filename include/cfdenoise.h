@@ -548,7 +548,7 @@ int cfd_weg_eval(cfd_handle h, const cfd_weg_args* args, float* losses, float* m
  * for any cotangent d_out at the output (cfd_weg_eval's gradient is hard-wired to the attention-focus objective of the text maps).
  * One call runs the forward with saved activations through the whole network and the reverse sweep of cfd_weg_eval's row-tile path
  * seeded at the output: d_out . latent_proj.weight, decoder.norm, then every layer from the top; no term from the attention maps, no
- * gradients to weights or memories.  It launches eagerly on the handle's own stream behind `stream` and returns with its results
+ * gradients to weights (the memories' gradients: cfd_denoise_vjp_mem, below).  It launches eagerly on the handle's own stream behind `stream` and returns with its results
  * complete.  It shares the row-tile arena and workspace with cfd_weg_eval: a cfd_weg_eval after it reuses nothing
  * (reuse_memory_side is then ignored once), and the bits of a sampling run that is open on the handle are unchanged.
  *   d_out dev [Be][L][128]   the cotangent at the forward's output
@@ -563,6 +563,22 @@ typedef struct {
   cfd_memory mem[CFD_NUM_MEM];   /* as in cfd_forward: U distinct memories, an optional row_map [Be], key-padding masks */
 } cfd_vjp_args;
 int cfd_denoise_vjp(cfd_handle h, const cfd_vjp_args* args, const float* d_out, float* out, float* grad, void* stream);
+/* The same call with the vector-Jacobian product with respect to the MEMORIES as well: replaces
+ *   torch.autograd.grad(out, encoder_hidden_states, d_out)
+ * through the reference module -- what fitting a conditioning tensor to data needs (a new listener identity, a fitted null
+ * conditioning, gradient x input attribution).  No weight gradients, no gradients to masks or the timestep.
+ *   d_mem[j] dev [U_j][S_j][512] or NULL (not wanted): d_out^T . d(out)/d(mem_j).  With a row_map, instance u receives the SUM over the
+ *            batch rows b with row_map_j[b] == u (what autograd gives a tensor that several rows share); an instance no row maps to
+ *            and every masked key receive exact zeros.
+ *   out      as in cfd_denoise_vjp
+ *   grad     as in cfd_denoise_vjp, or NULL: only the sweep's last product (the latent embedding's backward) is then skipped
+ * At least one of grad and d_mem[*] must be non-NULL.  Limits, refusals (CFD_E_ARG names the limit), stream behaviour (returns with
+ * its results complete), arena and workspace are cfd_denoise_vjp's; with every d_mem[j] NULL the launches are cfd_denoise_vjp's too.
+ * Float32 throughout the backward, no atomics: two calls on the same inputs return the same bits.  The first call that asks for a
+ * memory gradient builds float32 copies of the folded memory-side weights on the handle (94 MB at nine layers; freed with the
+ * handle, rebuilt after cfd_finalize_weights); a handle that never asks pays nothing. */
+int cfd_denoise_vjp_mem(cfd_handle h, const cfd_vjp_args* args, const float* d_out, float* out, float* grad, float* const d_mem[CFD_NUM_MEM],
+                        void* stream);
 /* ConvoFusionVae.decode together with its vector-Jacobian product with respect to the latents: replaces
  *   z.requires_grad_(True); feats = vae.decode(z, lengths); torch.autograd.grad(feats, z, d_feats)
  * i.e. autograd over convofusion/models/architectures/vae.py:268-372 (two SkipTransformerDecoders, cross_attention.py:66-125, of pre-norm

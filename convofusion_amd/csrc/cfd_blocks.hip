@@ -162,17 +162,15 @@ extern "C" int cfd_vae_decode_vjp(cfd_handle c, const cfd_vae_decode_vjp_args* p
   a.rows = 2LL * a.bs * a.fp;
   // the workspace (the handle's, this call's own): sized from the shapes, carved in the order of VaeDecArgs
   const long long R = a.rows, nl = a.nl, sb = 2LL * a.bs;
-  const long long sizes[] = {(nl + 1) * R * VE_D, nl * R * VE_D, nl * R * VE_D, nl * R * 3 * VE_D, nl * R * VE_D, nl * R * 2, nl * R * VE_D, nl * sb * 16 * 256,
-                             nl * R * VE_D, R * VE_D, R * VE_D, R * 2, R * 3 * VE_D, (a.nb ? a.nb : 1) * R * VE_D, nl * sb * a.nt * 16 * 256, nl * sb * 16 * VE_D};
-  float** const slots[] = {&a.x0, &a.x1, &a.x2, &a.qkv, &a.o, &a.lse, &a.qc, &a.mkv, &a.g, &a.g1, &a.d_o, &a.dd, &a.dqkv, &a.gskip, &a.pkv, &a.dzl};
-  long long total = 0;
-  for (long long n : sizes) total += (n + 3) / 4 * 4;
-  CHK(c->vae.ws.ensure((size_t)total * sizeof(float)));
-  float* base = c->vae.ws.as<float>();
-  for (size_t i = 0; i < sizeof(sizes) / sizeof(sizes[0]); ++i) {
-    *slots[i] = base;
-    base += (sizes[i] + 3) / 4 * 4;
-  }
+  auto layout = [&](ArenaLayout y) {   // 4 floats: every buffer starts on a float4
+    y.take(a.x0, (nl + 1) * R * VE_D); y.take(a.x1, nl * R * VE_D); y.take(a.x2, nl * R * VE_D); y.take(a.qkv, nl * R * 3 * VE_D);
+    y.take(a.o, nl * R * VE_D); y.take(a.lse, nl * R * 2); y.take(a.qc, nl * R * VE_D); y.take(a.mkv, nl * sb * 16 * 256);
+    y.take(a.g, nl * R * VE_D); y.take(a.g1, R * VE_D); y.take(a.d_o, R * VE_D); y.take(a.dd, R * 2); y.take(a.dqkv, R * 3 * VE_D);
+    y.take(a.gskip, (a.nb ? a.nb : 1) * R * VE_D); y.take(a.pkv, nl * sb * a.nt * 16 * 256); y.take(a.dzl, nl * sb * 16 * VE_D);
+    return y.bytes();
+  };
+  CHK(c->vae.ws.ensure(layout(ArenaLayout(nullptr, 4))));
+  layout(ArenaLayout(c->vae.ws.as<float>(), 4));
   c->vae.g = a.g; c->vae.dzl = a.dzl; c->vae.x0 = a.x0;
   c->vae.bs = a.bs; c->vae.fp = a.fp; c->vae.nl = a.nl; c->vae.rows = a.rows;
   const dim3 grid((unsigned)a.nt, (unsigned)a.bs, 2), blk(256);

@@ -531,6 +531,12 @@ int ln_fold_weight(Ctx* c, const float* W, int R, int K, const float* gamma, con
 // the memories' row maps on the host, `rows` entries each (rows_name: what the caller calls that count, for the message): the one place that
 // downloads a row map.  A memory without a map gets the identity and must have one instance per row; every entry is checked against U.
 int fetch_row_maps(const cfd_memory mem[CFD_NMEM], int rows, const char* rows_name, HostMaps& hm);
+// What setup_problem, cfd_weg_eval and cfd_denoise_vjp(_mem) refuse alike, before anything is touched: weights and timestep table in
+// place, B rows of an even L >= 2 tokens within the query PE, every memory present, within the memory PE and with one instance per row
+// where it has no row map.  CALL_TIMESTEP: `timestep` is the call's one timestep and must lie in the table; CALL_ROW_MAPS: memories may
+// come with row maps (without the flag one is refused, so that U == B for every memory).
+enum { CALL_TIMESTEP = 1, CALL_ROW_MAPS = 2 };
+int check_latent_call(Ctx* c, int B, int L, const cfd_memory mem[CFD_NMEM], int flags, int timestep = 0);
 // maps: the host copy of mem[].row_map where the caller has it already (null: fetched here, unless cfd_forward keeps the previous call's lists);
 // att: attention outputs [Be][nl][L][S_j] or null; ask: what else the caller asks of the forwards (forward_path.hpp)
 int setup_problem(Ctx* c, int Be, int L, const cfd_memory mem[CFD_NMEM], const HostMaps* maps, float* const att[CFD_NMEM], const PathAsk& ask,

@@ -274,17 +274,33 @@ static int setup_att_fused(Ctx* c) {
   return CFD_OK;
 }
 
+int check_latent_call(Ctx* c, int B, int L, const cfd_memory mem[CFD_NMEM], int flags, int timestep) {
+  if (!c->finalized) return fail(CFD_E_STATE, "weights not finalized");
+  if (c->tsin_rows < 1) return fail(CFD_E_STATE, "timestep table not set");
+  if (B < 1 || L < 2) return fail(CFD_E_ARG, "bad batch / length");
+  if (L % 2) return fail(CFD_E_SHAPE, "latent length %d is odd (reference: broadcasting error at position_encoding.py:160-161)", L);
+  if (L / 2 > c->qpe_rows) return fail(CFD_E_SHAPE, "L/2 = %d exceeds the query PE buffer (%d rows)", L / 2, c->qpe_rows);
+  if ((flags & CALL_TIMESTEP) && (timestep < 0 || timestep >= c->tsin_rows))
+    return fail(CFD_E_ARG, "timestep %d outside the timestep table (%d rows)", timestep, c->tsin_rows);
+  for (int j = 0; j < CFD_NMEM; ++j) {
+    const cfd_memory& m = mem[j];
+    if (!m.data || m.U < 1 || m.S < 1) return fail(CFD_E_ARG, "memory %s: null/empty", MEM_NAMES[j]);
+    if (m.row_map && !(flags & CALL_ROW_MAPS)) return fail(CFD_E_ARG, "memory %s: a row_map, where the call takes one memory per row (U == B)", MEM_NAMES[j]);
+    if (!m.row_map && m.U != B) return fail(CFD_E_ARG, "memory %s: U = %d != Be = %d without a row_map", MEM_NAMES[j], m.U, B);
+    if (m.S > c->mpe_rows)
+      return fail(CFD_E_SHAPE, "memory %s has %d tokens, memory PE buffer has %d rows (reference: size mismatch at position_encoding.py:135)",
+                  MEM_NAMES[j], m.S, c->mpe_rows);
+  }
+  return CFD_OK;
+}
+
 int setup_problem(Ctx* c, int Be, int L, const cfd_memory mem[CFD_NMEM], const HostMaps* maps, float* const att[CFD_NMEM], const PathAsk& ask,
                   int tmode, int T) {
   // (whatever this call is and however it ends, it may overwrite the memory-side buffers: the previous forward's projections are current
   //  only if cfd_forward says so again at its end)
   const bool mem_was_valid = c->w->fwd_mem_valid;
   c->w->fwd_mem_valid = false;
-  if (!c->finalized) return fail(CFD_E_STATE, "weights not finalized");
-  if (c->tsin_rows < 1) return fail(CFD_E_STATE, "timestep table not set");
-  if (Be < 1 || L < 2) return fail(CFD_E_ARG, "bad batch / length");
-  if (L % 2) return fail(CFD_E_SHAPE, "latent length %d is odd (reference: broadcasting error at position_encoding.py:160-161)", L);
-  if (L / 2 > c->qpe_rows) return fail(CFD_E_SHAPE, "L/2 = %d exceeds the query PE buffer (%d rows)", L / 2, c->qpe_rows);
+  CHK(check_latent_call(c, Be, L, mem, CALL_ROW_MAPS));   // (the timesteps of its caller: cfd_forward, the run's table)
   if ((size_t)Be * 4 > c->w->iota.bytes) {   // identity row map (memories passed without de-duplication)
     CHK(c->w->iota.ensure((size_t)Be * 4));
     std::vector<int> id(Be);
@@ -305,12 +321,7 @@ int setup_problem(Ctx* c, int Be, int L, const cfd_memory mem[CFD_NMEM], const H
   int off = 0;
   for (int j = 0; j < CFD_NMEM; ++j) {
     const cfd_memory& m = mem[j];
-    if (!m.data || m.U < 1 || m.S < 1) return fail(CFD_E_ARG, "memory %s: null/empty", MEM_NAMES[j]);
-    if (!m.row_map && m.U != Be) return fail(CFD_E_ARG, "memory %s: U = %d != Be = %d without a row_map", MEM_NAMES[j], m.U, Be);
     if (tmode == 1 && m.row_map) return fail(CFD_E_ARG, "per-row timesteps need identity memory maps");
-    if (m.S > c->mpe_rows)
-      return fail(CFD_E_SHAPE, "memory %s has %d tokens, memory PE buffer has %d rows (reference: size mismatch at position_encoding.py:135)",
-                  MEM_NAMES[j], m.S, c->mpe_rows);
     p.U[j] = m.U; p.S[j] = m.S; p.Sp[j] = (m.S + 31) / 32 * 32; p.off[j] = off; off += p.Sp[j];
     if (p.Sp[j] > SM_MAX_CHUNKS * 512) return fail(CFD_E_SHAPE, "memory %s: %d keys exceed the in-register softmax limit", MEM_NAMES[j], m.S);
     p.mem[j] = m.data; p.map[j] = m.row_map ? m.row_map : c->w->iota.as<int>(); p.mask[j] = m.key_padding_mask;

@@ -98,18 +98,9 @@ struct WegEval {   // one evaluation, handed from stage to stage
 // Every refusal, before anything is touched; yields the most focus tokens of a batch row.
 static int check_args(Ctx* c, const cfd_weg_args* a, const float* losses, const float* max_att, const float* grad, int* nt_max_out) {
   if (!c || !a || !a->latents || !a->tok_off || !losses || !max_att || !grad) return fail(CFD_E_ARG, "null argument");
-  if (!c->finalized) return fail(CFD_E_STATE, "weights not finalized");
-  const int B = a->B, L = a->L, D = c->cfg.text_encoded_dim;
-  if (B < 1 || L < 2) return fail(CFD_E_ARG, "bad batch / length");
-  if (L % 2) return fail(CFD_E_SHAPE, "latent length %d is odd (reference: broadcasting error at position_encoding.py:160-161)", L);
-  if (L / 2 > c->qpe_rows) return fail(CFD_E_SHAPE, "L/2 = %d exceeds the query PE buffer (%d rows)", L / 2, c->qpe_rows);
-  if (a->timestep < 0 || a->timestep >= c->tsin_rows) return fail(CFD_E_ARG, "timestep %d outside the timestep table (%d rows)", a->timestep, c->tsin_rows);
-  if (D > 2048) return fail(CFD_E_SHAPE, "model width above 2048");
-  for (int j = 0; j < CFD_NMEM; ++j) {
-    if (!a->mem[j].data || a->mem[j].S < 1) return fail(CFD_E_ARG, "memory %s missing", MEM_NAMES[j]);
-    if (a->mem[j].U != B || a->mem[j].row_map) return fail(CFD_E_ARG, "cfd_weg_eval takes one memory per row (U == B, no row map)");
-    if (a->mem[j].S > c->mpe_rows) return fail(CFD_E_SHAPE, "memory %s has %d tokens, the memory PE buffer %d rows", MEM_NAMES[j], a->mem[j].S, c->mpe_rows);
-  }
+  CHK(check_latent_call(c, a->B, a->L, a->mem, CALL_TIMESTEP, a->timestep));   // (one memory per row: no row maps)
+  const int B = a->B;
+  if (c->cfg.text_encoded_dim > 2048) return fail(CFD_E_SHAPE, "model width above 2048");
   const int St = a->mem[2].S, n_tok = a->tok_off[B];
   if (a->tok_off[0] != 0 || n_tok < 0 || (n_tok > 0 && !a->tok_idx)) return fail(CFD_E_ARG, "bad focus-token table");
   // F.pad(..., mode='reflect') with pad 1 needs at least 2 entries per axis (word_excitation_guidance.py:35)
@@ -157,6 +148,29 @@ static int stage_inputs(WegEval& e) {
   return CFD_OK;
 }
 
+// What an evaluation or a VJP call does first: the forward's hints lapse, the census an earlier evaluation left is settled, and the
+// handle's own stream -- capturable, and the one an open run's graph replays on: the two serialise -- starts behind whatever the caller
+// has queued on its stream.
+static int begin_on_own_stream(Ctx* c, hipStream_t caller) {
+  c->hint_now = c->hint_same_mem = false;
+  CHK(settle_deferred_census(c));
+  HIPCHK(hipEventRecord(c->weg_ev, caller));
+  HIPCHK(hipStreamWaitEvent(c->own_stream, c->weg_ev, 0));
+  return CFD_OK;
+}
+
+// The call's timestep, in front of its launch sequence and outside any captured graph: one-row tables (T == 1) are built for it, full
+// tables (row t = timestep t) are read at it.
+static int set_call_timestep(Ctx* c, int T, int timestep, hipStream_t st) {
+  WegState& w = c->weg;
+  w.rt.T = T;
+  w.t_host = timestep;
+  w.dstep_host = T > 1 ? timestep : 0;
+  if (T == 1) HIPCHK(hipMemcpyAsync(c->wk[1].trows.p, &w.t_host, 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(c->wk[1].d_step.p, &w.dstep_host, 4, hipMemcpyHostToDevice, st));
+  return CFD_OK;
+}
+
 // The path -- small problems (the product shape) run on the row-tile kernels, everything else on the float32 launch sequence of
 // weg_eval.hpp -- its arena, and whether the memory side can be reused.
 // `sig` is what the memory-side / time-only part of an evaluation depends on.  With args->reuse_memory_side the caller states that the
@@ -180,12 +194,7 @@ static int choose_path_and_reuse(WegEval& e) {
     e.sig.insert(e.sig.end(), {(long long)(size_t)e.arena, -(long long)T});
     if (T == 1) e.sig.push_back(a->timestep);
     e.reuse = a->reuse_memory_side != 0 && e.sig == w.sig;
-    w.rt.T = T;
-    w.t_host = a->timestep;                       // in front of the launch sequence, outside any captured graph
-    w.dstep_host = T > 1 ? a->timestep : 0;
-    if (T == 1) HIPCHK(hipMemcpyAsync(c->wk[1].trows.p, &w.t_host, 4, hipMemcpyHostToDevice, e.st));
-    HIPCHK(hipMemcpyAsync(c->wk[1].d_step.p, &w.dstep_host, 4, hipMemcpyHostToDevice, e.st));
-    return CFD_OK;
+    return set_call_timestep(c, T, a->timestep, e.st);
   }
   e.sig.push_back(a->timestep);
   e.x = weg::Ctx::sizing_pass(c, e.st, e.B, e.L, e.D);
@@ -286,14 +295,9 @@ extern "C" int cfd_weg_eval(cfd_handle c, const cfd_weg_args* a, float* losses, 
   int nt_max = 0;
   CHK(check_args(c, a, losses, max_att, grad, &nt_max));
   HIPCHK(hipSetDevice(c->cfg.device));
-  c->hint_now = c->hint_same_mem = false;
-  CHK(settle_deferred_census(c));
   const int D = c->cfg.text_encoded_dim, n_tok = a->tok_off[a->B];
-  // the evaluation runs on the handle's own stream (capturable, and the one the sampling graph replays on: the two
-  // serialise); it starts behind whatever the caller has queued on `stream`
   WegEval e{c, a, (hipStream_t)stream, c->own_stream, a->B, a->L, D, n_tok, nt_max, WegStaging(a->B, a->L, D, n_tok)};
-  HIPCHK(hipEventRecord(c->weg_ev, e.caller));
-  HIPCHK(hipStreamWaitEvent(e.st, c->weg_ev, 0));
+  CHK(begin_on_own_stream(c, e.caller));
   CHK(upload_focus_tokens(e));
   CHK(stage_inputs(e));
   CHK(choose_path_and_reuse(e));
@@ -308,25 +312,9 @@ extern "C" int cfd_weg_eval(cfd_handle c, const cfd_weg_args* a, float* losses, 
 // `wants`: some result is asked for (cfd_denoise_vjp: grad; cfd_denoise_vjp_mem: grad or a d_mem[j]).
 static int check_vjp_args(Ctx* c, const cfd_vjp_args* a, const float* d_out, bool wants, std::vector<long long>* maps, HostMaps* hm) {
   if (!c || !a || !a->sample || !d_out || !wants) return fail(CFD_E_ARG, "null argument");
-  if (!c->finalized) return fail(CFD_E_STATE, "weights not finalized");
-  const int Be = a->Be, L = a->L;
-  if (Be < 1 || L < 2) return fail(CFD_E_ARG, "bad batch / length");
-  if (L % 2) return fail(CFD_E_SHAPE, "latent length %d is odd (reference: broadcasting error at position_encoding.py:160-161)", L);
-  if (L / 2 > c->qpe_rows) return fail(CFD_E_SHAPE, "L/2 = %d exceeds the query PE buffer (%d rows)", L / 2, c->qpe_rows);
-  if (a->timestep < 0 || a->timestep >= c->tsin_rows) return fail(CFD_E_ARG, "timestep %d outside the timestep table (%d rows)", a->timestep, c->tsin_rows);
-  for (int j = 0; j < CFD_NMEM; ++j) {
-    const cfd_memory& m = a->mem[j];
-    if (!m.data || m.S < 1 || m.U < 1) return fail(CFD_E_ARG, "memory %s missing", MEM_NAMES[j]);
-    if (!m.row_map && m.U != Be) return fail(CFD_E_ARG, "memory %s: U = %d != Be = %d without a row_map", MEM_NAMES[j], m.U, Be);
-    if (m.S > c->mpe_rows) return fail(CFD_E_SHAPE, "memory %s has %d tokens, the memory PE buffer %d rows", MEM_NAMES[j], m.S, c->mpe_rows);
-  }
-  // the eligibility of the row-tile path (wegrt::eligible), limit by limit
-  if (!c->rt_on || !c->weg_rt_on) return fail(CFD_E_ARG, "cfd_denoise_vjp runs on the row-tile path, which this handle has switched off (CFD_ROWTILE / CFD_WEG_ROWTILE)");
-  if (L > RT_MAX_L) return fail(CFD_E_ARG, "cfd_denoise_vjp: L = %d exceeds RT_MAX_L = %d tokens per batch row", L, RT_MAX_L);
-  if ((long long)Be * L > c->rt_max_rows)
-    return fail(CFD_E_ARG, "cfd_denoise_vjp: Be * L = %lld token rows exceed rt_max_rows = %lld", (long long)Be * L, c->rt_max_rows);
-  if (wegrt::padded_keys(a->mem) > RT_MAX_KEYS)
-    return fail(CFD_E_ARG, "cfd_denoise_vjp: %d padded keys of the five memories together exceed RT_MAX_KEYS = %d", wegrt::padded_keys(a->mem), RT_MAX_KEYS);
+  const int Be = a->Be;
+  CHK(check_latent_call(c, Be, a->L, a->mem, CALL_TIMESTEP | CALL_ROW_MAPS, a->timestep));
+  if (const char* why = wegrt::ineligible(c, Be, a->L, a->mem)) return fail(CFD_E_ARG, "cfd_denoise_vjp: %s", why);   // the row-tile path only
   if (c->weg.rt.stop) return fail(CFD_E_STATE, "cfd_debug_weg_stop is set: it names a launch of cfd_weg_eval's sweep");
   HIPCHK(hipSetDevice(c->cfg.device));
   CHK(fetch_row_maps(a->mem, Be, "Be", *hm));
@@ -347,25 +335,17 @@ static int denoise_vjp(Ctx* c, const cfd_vjp_args* a, const float* d_out, float*
   bool any_mem = false;
   for (int j = 0; d_mem && j < CFD_NMEM; ++j) any_mem = any_mem || d_mem[j] != nullptr;
   CHK(check_vjp_args(c, a, d_out, grad != nullptr || any_mem, &maps, &hm));
-  c->hint_now = c->hint_same_mem = false;
-  CHK(settle_deferred_census(c));
   WegState& w = c->weg;
-  // like cfd_weg_eval: on the handle's own stream (the one an open run's graph replays on: the two serialise), behind whatever the
-  // caller has queued on `stream`, in wk[1] (wegrt::WorkGuard): an open sampling run keeps wk[0] and its bits
-  hipStream_t caller = (hipStream_t)stream, st = c->own_stream;
-  HIPCHK(hipEventRecord(c->weg_ev, caller));
-  HIPCHK(hipStreamWaitEvent(st, c->weg_ev, 0));
+  // like cfd_weg_eval: on the handle's own stream, in wk[1] (wegrt::WorkGuard): an open sampling run keeps wk[0] and its bits
+  hipStream_t st = c->own_stream;
+  CHK(begin_on_own_stream(c, (hipStream_t)stream));
   // The call overwrites wk[1]'s problem and tables and the arena: nothing of an earlier cfd_weg_eval may be reused behind it -- neither
   // its memory-side results (WegState::sig) nor its captured launches, whose arguments hold addresses that set-up may move.
   w.sig.clear();
   for (WegState::Graph& g : w.graph)
     if (g.gx.exec) { HIPCHK(hipStreamSynchronize(st)); g.reset(); }
   CHK(wegrt::prepare(c, wegrt::FOR_VJP, a->Be, a->L, a->mem, 1, st, maps, &hm));
-  w.rt.T = 1;
-  w.t_host = a->timestep;
-  w.dstep_host = 0;
-  HIPCHK(hipMemcpyAsync(c->wk[1].trows.p, &w.t_host, 4, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(c->wk[1].d_step.p, &w.dstep_host, 4, hipMemcpyHostToDevice, st));
+  CHK(set_call_timestep(c, 1, a->timestep, st));
   wegrt::MemGrad mg;
   if (any_mem) {
     CHK(wegrt::ensure_memw_f32(c, st));

@@ -1,5 +1,5 @@
-// libcfdenoise: the resources that free themselves -- a device buffer (DBuf), a captured graph with its executable (GraphExec) -- and the error
-// helpers they return through.  Host code only, no kernel header: tests/host/owned_test.cpp builds it against stubs of the runtime calls it makes.
+// libcfdenoise: the resources that free themselves -- a device buffer (DBuf), a captured graph with its executable (GraphExec) --, the layout of
+// a workspace carved into buffers (ArenaLayout), and the error helpers they return through.  Host code only, no kernel header: tests/host/owned_test.cpp builds it against stubs of the runtime calls it makes.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -47,6 +47,21 @@ struct DBuf {
     p = nullptr; bytes = 0;
   }
   template <class T> T* as() const { return reinterpret_cast<T*>(p); }
+};
+
+// The layout of a workspace of floats, stated once and run twice: with a null base it sizes (bytes() is what to allocate), with the
+// allocation as base it carves the same buffers in the same order.  Each buffer is named once -- take(field, count) -- and occupies
+// its count rounded up to `granule` floats.
+struct ArenaLayout {
+  float* base;                  // null: the sizing pass, which leaves every field null
+  size_t granule, off = 0;      // floats
+  ArenaLayout(float* base_, size_t granule_) : base(base_), granule(granule_) {}
+  size_t rounded(size_t count) const { return (count + granule - 1) / granule * granule; }
+  template <class T> void take(T*& field, size_t count) {
+    field = base ? reinterpret_cast<T*>(base + off) : nullptr;
+    off += rounded(count);
+  }
+  size_t bytes() const { return off * sizeof(float); }
 };
 
 // A captured graph and its executable, destroyed together (executable first); move-only like DBuf.

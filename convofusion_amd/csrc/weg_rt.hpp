@@ -22,12 +22,19 @@ static int padded_keys(const cfd_memory* mem) {   // of all five memories togeth
   return sp;
 }
 
-static bool eligible(Ctx* c, int B, int L, const cfd_memory* mem) {
-  if (!c->rt_on || !c->weg_rt_on) return false;
-  if (L > RT_MAX_L || (long long)B * L > c->rt_max_rows) return false;
-  return padded_keys(mem) <= RT_MAX_KEYS;
+// Why B rows of L tokens against these memories cannot run on the row-tile path -- the limit that is exceeded, in a buffer of the
+// calling thread's -- or null when they can.
+static const char* ineligible(Ctx* c, int B, int L, const cfd_memory* mem) {
+  static thread_local char why[160];
+  const int keys = padded_keys(mem);
+  if (!c->rt_on || !c->weg_rt_on) snprintf(why, sizeof(why), "the row-tile path is switched off on this handle (CFD_ROWTILE / CFD_WEG_ROWTILE)");
+  else if (L > RT_MAX_L) snprintf(why, sizeof(why), "L = %d exceeds RT_MAX_L = %d tokens per batch row", L, RT_MAX_L);
+  else if ((long long)B * L > c->rt_max_rows) snprintf(why, sizeof(why), "Be * L = %lld token rows exceed rt_max_rows = %lld", (long long)B * L, c->rt_max_rows);
+  else if (keys > RT_MAX_KEYS) snprintf(why, sizeof(why), "%d padded keys of the five memories together exceed RT_MAX_KEYS = %d", keys, RT_MAX_KEYS);
+  else return nullptr;
+  return why;
 }
-static bool eligible(Ctx* c, const cfd_weg_args* a) { return eligible(c, a->B, a->L, a->mem); }
+static bool eligible(Ctx* c, const cfd_weg_args* a) { return !ineligible(c, a->B, a->L, a->mem); }
 
 // Who prepared wk[1] and the arena: the two callers share both, and what one of them left is never reused by the other.
 enum { FOR_WEG = 0, FOR_VJP = 1 };
@@ -47,31 +54,23 @@ static int prepare(Ctx* c, int who, int B, int L, const cfd_memory* mem_in, int 
   HIPCHK(hipStreamSynchronize(st));
   s.sig.clear();
   const size_t M = (size_t)B * L, St = (size_t)mem_in[2].S;
-  auto al = [](size_t n) { return (n + 63) & ~(size_t)63; };   // floats, 256-byte granules
-  size_t n = 0;
-  const size_t n_x = al(M * CFD_D), n_qk = al(M * 2 * CFD_D), n_vt = al((size_t)B * CFD_D * RT_MAX_L), n_sc = al(M * spt), n_pre = al(M * CFD_FF);
-  const size_t n_cst = al(M * 32 * 4);
-  n += (size_t)(nl + 1) * 5 * n_x + (size_t)nl * (n_qk + n_vt + n_sc + n_pre + n_cst);
-  const size_t n_att = al((size_t)B * nl * L * St), n_fws = al((size_t)B * (3 * (size_t)L * St + 3 * St + 64));
-  n += 2 * n_att + n_fws + n_sc + 3 * n_x + 2 * n_x + n_pre + n_x + al(M * 3 * CFD_D);
-  CHK(c->weg.rt_ws.ensure(n * 4));
-  float* p = c->weg.rt_ws.as<float>();
-  auto take = [&](size_t k) { float* r = p; p += k; return r; };
-  for (int l = 0; l <= nl; ++l)
-    for (int k = 0; k < 5; ++k) s.sv.x[l][k] = take(n_x);
-  for (int l = 0; l < nl; ++l) {
-    s.sv.qk[l] = reinterpret_cast<char*>(take(n_qk));
-    s.sv.vt[l] = reinterpret_cast<char*>(take(n_vt));
-    HIPCHK(hipMemset(s.sv.vt[l], 0, n_vt * 4));   // keys beyond L stay zero
-    s.sv.sc[l] = take(n_sc);
-    s.sv.cst[l] = take(n_cst);
-    s.sv.pre[l] = take(n_pre);
-  }
-  s.att = take(n_att); s.d_att = take(n_att); s.fws = take(n_fws); s.dP = take(n_sc);
-  for (int k = 0; k < 3; ++k) s.G[k] = take(n_x);
-  s.dz = take(n_x); s.dy = take(n_x); s.dh = take(n_pre); s.dO = take(n_x); s.dqkv = take(al(M * 3 * CFD_D));
+  const size_t n_x = M * CFD_D, n_vt = (size_t)B * CFD_D * RT_MAX_L, n_sc = M * spt, n_pre = M * CFD_FF, n_att = (size_t)B * nl * L * St;
+  auto layout = [&](ArenaLayout a) {   // 64 floats: 256-byte granules
+    for (int l = 0; l <= nl; ++l)
+      for (int k = 0; k < 5; ++k) a.take(s.sv.x[l][k], n_x);
+    for (int l = 0; l < nl; ++l) {
+      a.take(s.sv.qk[l], M * 2 * CFD_D); a.take(s.sv.vt[l], n_vt); a.take(s.sv.sc[l], n_sc); a.take(s.sv.cst[l], M * 32 * 4); a.take(s.sv.pre[l], n_pre);
+    }
+    a.take(s.att, n_att); a.take(s.d_att, n_att); a.take(s.fws, (size_t)B * (3 * (size_t)L * St + 3 * St + 64)); a.take(s.dP, n_sc);
+    for (int k = 0; k < 3; ++k) a.take(s.G[k], n_x);
+    a.take(s.dz, n_x); a.take(s.dy, n_x); a.take(s.dh, n_pre); a.take(s.dO, n_x); a.take(s.dqkv, M * 3 * CFD_D);
+    return a;
+  };
+  CHK(c->weg.rt_ws.ensure(layout(ArenaLayout(nullptr, 64)).bytes()));
+  const ArenaLayout lay = layout(ArenaLayout(c->weg.rt_ws.as<float>(), 64));
+  for (int l = 0; l < nl; ++l) HIPCHK(hipMemset(s.sv.vt[l], 0, lay.rounded(n_vt) * 4));   // keys beyond L stay zero
   s.sv.whole = who == FOR_VJP;
-  if (who == FOR_VJP) HIPCHK(hipMemset(s.d_att, 0, n_att * 4));
+  if (who == FOR_VJP) HIPCHK(hipMemset(s.d_att, 0, lay.rounded(n_att) * 4));
   {
     WorkGuard guard(c);
     cfd_memory mem[CFD_NMEM];
@@ -241,20 +240,19 @@ static int prepare_mem_grad(Ctx* c, hipStream_t st, int Be, int L, const cfd_mem
     if (mg.want[j]) { mg.j0 = std::min(mg.j0, j); j1 = j; }
   }
   mg.nspan = j1 - mg.j0 + 1;
-  auto al = [](size_t n) { return (n + 63) & ~(size_t)63; };
-  const size_t n_sp = al(M * spt), n_t = al(M * (size_t)mg.nspan * CFD_D);
-  size_t n = 2 * n_sp + 2 * n_t;
-  size_t n_pl[CFD_NMEM];
-  for (int j = 0; j < CFD_NMEM; ++j) {
-    n_pl[j] = mg.want[j] ? al((size_t)mem[j].U * ((mem[j].S + 31) / 32 * 32) * CFD_D) : 0;
-    n += n_pl[j];
-  }
-  if (n * 4 > w.mem_ws.bytes) HIPCHK(hipStreamSynchronize(st));
-  CHK(w.mem_ws.ensure(n * 4));
-  float* p = w.mem_ws.as<float>();
-  auto take = [&](size_t k) { float* r = p; p += k; return r; };
-  mg.dSp = take(n_sp); mg.Pp = take(n_sp); mg.T = take(n_t); mg.G = take(n_t);
-  for (int j = 0; j < CFD_NMEM; ++j) mg.plane[j] = n_pl[j] ? take(n_pl[j]) : nullptr;
+  auto layout = [&](ArenaLayout a) {
+    const size_t n_sp = M * spt, n_t = M * (size_t)mg.nspan * CFD_D;
+    a.take(mg.dSp, n_sp); a.take(mg.Pp, n_sp); a.take(mg.T, n_t); a.take(mg.G, n_t);
+    for (int j = 0; j < CFD_NMEM; ++j) {
+      mg.plane[j] = nullptr;
+      if (mg.want[j]) a.take(mg.plane[j], (size_t)mem[j].U * ((mem[j].S + 31) / 32 * 32) * CFD_D);
+    }
+    return a.bytes();
+  };
+  const size_t bytes = layout(ArenaLayout(nullptr, 64));
+  if (bytes > w.mem_ws.bytes) HIPCHK(hipStreamSynchronize(st));
+  CHK(w.mem_ws.ensure(bytes));
+  layout(ArenaLayout(w.mem_ws.as<float>(), 64));
   // inverse row maps: per memory [U_j + 1] offsets, then the Be rows by instance (ascending within an instance)
   std::vector<int32_t> inv;
   size_t at[CFD_NMEM];

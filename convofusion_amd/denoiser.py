@@ -16,11 +16,12 @@ of the row-tile kernels, so no activation state outlives a call.  The attention 
 the row-tile path (``vjp_refusal``) and per-row timesteps are refused before any device work.
 
 Without the keyword no gradient reaches a memory (one that requires grad is refused).  ``forward(..., memory_grad=True)``
-takes the differentiable path when the sample OR a memory requires grad (``_DenoiseVjpMem``: the five memories are tensor
-arguments of the function; its backward is one ``cfd_denoise_vjp_mem`` call with one memory per batch row, so every input
-row gets its own gradient, as torch autograd gives the reference).  ``vjp_memories`` is the direct call: distinct memories
-with row maps receive the sum over the rows that share them, which is what fitting one conditioning tensor to several
-examples needs (``convofusion_amd.fit``).
+takes the differentiable path when the sample OR a memory requires grad: the same ``_DenoiseVjp`` (sample and the five
+memories are its tensor arguments in both modes), whose backward then asks for exactly what requires grad -- one
+``cfd_denoise_vjp_mem`` call with one memory per batch row, so every input row gets its own gradient, as torch autograd gives
+the reference.  ``vjp_memories`` is the direct call: distinct memories with row maps receive the sum over the rows that share
+them, which is what fitting one conditioning tensor to several examples needs (``convofusion_amd.fit``).  ``vjp``,
+``vjp_memories`` and that backward are one marshalling body, ``Denoiser._vjp_call``.
 """
 import copy
 import ctypes as C
@@ -120,34 +121,23 @@ def vjp_refusal(Be, L, S, max_rows=None):
     return None
 
 
+def _require_row_tile(sample, mems, what):
+    """The refusal of a gradient with respect to ``what`` ("its sample" ...) at shapes beyond the row-tile path."""
+    why = vjp_refusal(sample.shape[0], sample.shape[1], [int(m.shape[1]) for m in mems])
+    if why is not None:
+        raise NotImplementedError(f"the gradient of the HIP denoiser with respect to {what} runs on the row-tile path only: {why}")
+
+
 class _DenoiseVjp(torch.autograd.Function):
-    """``out`` of ``Denoiser._forward_hip`` as a function of ``sample``; backward: cfd_denoise_vjp on the saved INPUTS."""
+    """``out`` of ``Denoiser._forward_hip`` as a function of ``sample`` and the five memories (tensor arguments, so that autograd can reach
+    them; ``memory_grad`` says whether it may).  Backward: one ``Denoiser._vjp_call`` on the saved INPUTS for exactly what
+    ``needs_input_grad`` names -- with memories, one per batch row (U = Be, no row map)."""
 
     @staticmethod
-    def forward(ctx, sample, denoiser, timestep, encoder_hidden_states, mem_mask_dict, kwargs):
-        out, att = denoiser._forward_hip(sample, timestep, encoder_hidden_states, mem_mask_dict, kwargs)
-        ctx.denoiser, ctx.t, ctx.side = denoiser, int(torch.as_tensor(timestep).reshape(-1)[0].item()), bool(kwargs.get("side_engine", False))
-        ctx.mems, ctx.masks = list(encoder_hidden_states), dict(mem_mask_dict or {})
-        ctx.save_for_backward(sample)
-        ctx.mark_non_differentiable(*att)
-        return (out, *att)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, d_out, *d_att):
-        (sample,) = ctx.saved_tensors
-        return ctx.denoiser.vjp(sample, ctx.t, ctx.mems, ctx.masks, d_out, side_engine=ctx.side)[1], None, None, None, None, None
-
-
-class _DenoiseVjpMem(torch.autograd.Function):
-    """``out`` of ``Denoiser._forward_hip`` as a function of ``sample`` and the five memories (tensor arguments, so that autograd reaches
-    them); backward: one cfd_denoise_vjp_mem on the saved INPUTS, one memory per batch row (U = Be, no row map)."""
-
-    @staticmethod
-    def forward(ctx, denoiser, timestep, mem_mask_dict, kwargs, sample, *mems):
+    def forward(ctx, denoiser, timestep, mem_mask_dict, kwargs, memory_grad, sample, *mems):
         out, att = denoiser._forward_hip(sample, timestep, list(mems), mem_mask_dict, kwargs)
         ctx.denoiser, ctx.t, ctx.side = denoiser, int(torch.as_tensor(timestep).reshape(-1)[0].item()), bool(kwargs.get("side_engine", False))
-        ctx.masks = dict(mem_mask_dict or {})
+        ctx.masks, ctx.memory_grad = dict(mem_mask_dict or {}), memory_grad
         ctx.save_for_backward(sample, *mems)
         ctx.mark_non_differentiable(*att)
         return (out, *att)
@@ -156,11 +146,11 @@ class _DenoiseVjpMem(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, d_out, *d_att):
         sample, *mems = ctx.saved_tensors
-        need = ctx.needs_input_grad[4:]
-        wrt = tuple(name for name, n in zip(MEM_NAMES, need[1:]) if n)
-        _, grad, d_mem = ctx.denoiser.vjp_memories(sample, ctx.t, mems, ctx.masks, d_out, wrt=wrt, side_engine=ctx.side, want_out=False,
-                                                   want_grad=bool(need[0]))
-        return (None, None, None, None, grad) + tuple(d_mem.get(name) for name in MEM_NAMES)
+        need = ctx.needs_input_grad[5:]
+        wrt = tuple(name for name, n in zip(MEM_NAMES, need[1:]) if n) if ctx.memory_grad else ()
+        _, grad, d_mem = ctx.denoiser._vjp_call(sample, ctx.t, mems, ctx.masks, d_out, wrt, None, ctx.side, False, bool(need[0]) or not wrt,
+                                                "its sample and memories" if ctx.memory_grad else "its sample")
+        return (None, None, None, None, None, grad) + tuple(d_mem.get(name) for name in MEM_NAMES)
 
 
 class _PE(nn.Module):
@@ -370,49 +360,12 @@ class Denoiser(nn.Module):
         return arr, keep
 
     # ---- the vector-Jacobian product ---------------------------------------------------------------
-    def vjp(self, sample, timestep, encoder_hidden_states, mem_mask_dict, d_out, *, row_maps=None, side_engine=False, want_out=True):
-        """(out or None, d_out^T . d(out)/d(sample)) of one forward: the direct ``cfd_denoise_vjp`` call (the backward of the
-        differentiable ``forward``).  ``row_maps``: as in ``pack_memories`` -- distinct memories with one int32 map [Be] each."""
+    def _vjp_call(self, sample, timestep, encoder_hidden_states, mem_mask_dict, d_out, wrt, row_maps, side_engine, want_out, want_grad, what):
+        """(out or None, grad or None, {name: d_mem}) of one forward: one ``cfd_denoise_vjp`` call (``wrt`` empty) or one
+        ``cfd_denoise_vjp_mem`` call, the body of ``vjp``, ``vjp_memories`` and the backward of the differentiable ``forward``.
+        ``what``: the phrase of the refusal ("its sample" ...)."""
         Be, L, _ = sample.shape
-        why = vjp_refusal(Be, L, [int(m.shape[1]) for m in encoder_hidden_states])
-        if why is not None:
-            raise NotImplementedError(f"the gradient of the HIP denoiser with respect to its sample runs on the row-tile path only: {why}")
-        lib = _lib.load()
-        h = self.engine(sample.device, mem_len=max(int(m.shape[1]) for m in encoder_hidden_states), side=bool(side_engine))
-        x = sample.detach().to(torch.float32).contiguous()
-        d = d_out.detach().to(device=x.device, dtype=torch.float32).contiguous()
-        if tuple(d.shape) != tuple(x.shape):
-            raise ValueError(f"d_out must have the sample's shape {list(x.shape)}")
-        mems, keep = self.pack_memories(encoder_hidden_states, mem_mask_dict, row_maps)
-        a = _lib.VjpArgs()
-        a.Be, a.L, a.timestep, a.sample, a.mem = Be, L, int(timestep), x.data_ptr(), mems
-        out = torch.empty_like(x) if want_out else None
-        grad = torch.empty_like(x)
-        with torch.cuda.device(x.device):
-            _lib.check(lib.cfd_denoise_vjp(h, C.byref(a), C.c_void_p(d.data_ptr()), C.c_void_p(out.data_ptr()) if want_out else None,
-                                           C.c_void_p(grad.data_ptr()), C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)))
-        del keep
-        return out, grad
-
-    def vjp_memories(self, sample, timestep, encoder_hidden_states, mem_mask_dict, d_out, *, wrt=MEM_NAMES, row_maps=None, side_engine=False,
-                     want_out=True, want_grad=True):
-        """(out or None, grad, {name: d_out^T . d(out)/d(memory) [U_j, S_j, 512]}) of one forward: the direct ``cfd_denoise_vjp_mem``
-        call.  ``wrt``: the memories whose gradient is wanted (names of ``MEM_NAMES``).  ``row_maps`` as in ``pack_memories``: a
-        distinct memory receives the SUM over the batch rows that map to it, one that no row maps to exact zeros; masked keys receive
-        exact zeros.  ``grad`` is the sample's gradient as ``vjp`` returns it (bit for bit), or None with ``want_grad=False`` (at least
-        one memory must then be wanted)."""
-        Be, L, _ = sample.shape
-        wrt = tuple(wrt)
-        for name in wrt:
-            if name not in MEM_NAMES:
-                raise ValueError(f"wrt names a memory that does not exist: {name!r} (the memories are {', '.join(MEM_NAMES)})")
-        if not wrt and not want_grad:
-            raise ValueError("vjp_memories: nothing is wanted (wrt is empty and want_grad is False)")
-        if len(encoder_hidden_states) != _lib.NUM_MEM:
-            raise ValueError("encoder_hidden_states must be the 5-tuple (spk_emb, alsn, tlsn, apb, lsnemb)")
-        why = vjp_refusal(Be, L, [int(m.shape[1]) for m in encoder_hidden_states])
-        if why is not None:
-            raise NotImplementedError(f"the gradient of the HIP denoiser with respect to its memories runs on the row-tile path only: {why}")
+        _require_row_tile(sample, encoder_hidden_states, what)
         lib = _lib.load()
         h = self.engine(sample.device, mem_len=max(int(m.shape[1]) for m in encoder_hidden_states), side=bool(side_engine))
         x = sample.detach().to(torch.float32).contiguous()
@@ -424,66 +377,74 @@ class Denoiser(nn.Module):
         a.Be, a.L, a.timestep, a.sample, a.mem = Be, L, int(timestep), x.data_ptr(), mems
         out = torch.empty_like(x) if want_out else None
         grad = torch.empty_like(x) if want_grad else None
-        d_mem, ptrs = {}, (C.c_void_p * _lib.NUM_MEM)()
-        for j, name in enumerate(MEM_NAMES):
-            if name in wrt:
-                d_mem[name] = torch.empty(tuple(encoder_hidden_states[j].shape), dtype=torch.float32, device=x.device)
-                ptrs[j] = d_mem[name].data_ptr()
+        d_mem = {name: torch.empty(tuple(encoder_hidden_states[j].shape), dtype=torch.float32, device=x.device)
+                 for j, name in enumerate(MEM_NAMES) if name in wrt}
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
         with torch.cuda.device(x.device):
-            _lib.check(lib.cfd_denoise_vjp_mem(h, C.byref(a), C.c_void_p(d.data_ptr()), C.c_void_p(out.data_ptr()) if want_out else None,
-                                               C.c_void_p(grad.data_ptr()) if want_grad else None, ptrs,
-                                               C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)))
+            stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+            if wrt:
+                ptrs = (C.c_void_p * _lib.NUM_MEM)(*(d_mem[name].data_ptr() if name in d_mem else None for name in MEM_NAMES))
+                _lib.check(lib.cfd_denoise_vjp_mem(h, C.byref(a), ptr(d), ptr(out), ptr(grad), ptrs, stream))
+            else:
+                _lib.check(lib.cfd_denoise_vjp(h, C.byref(a), ptr(d), ptr(out), ptr(grad), stream))
         del keep
         return out, grad, d_mem
 
+    def vjp(self, sample, timestep, encoder_hidden_states, mem_mask_dict, d_out, *, row_maps=None, side_engine=False, want_out=True):
+        """(out or None, d_out^T . d(out)/d(sample)) of one forward: the direct ``cfd_denoise_vjp`` call (the backward of the
+        differentiable ``forward``).  ``row_maps``: as in ``pack_memories`` -- distinct memories with one int32 map [Be] each."""
+        return self._vjp_call(sample, timestep, encoder_hidden_states, mem_mask_dict, d_out, (), row_maps, side_engine, want_out, True, "its sample")[:2]
+
+    def vjp_memories(self, sample, timestep, encoder_hidden_states, mem_mask_dict, d_out, *, wrt=MEM_NAMES, row_maps=None, side_engine=False,
+                     want_out=True, want_grad=True):
+        """(out or None, grad, {name: d_out^T . d(out)/d(memory) [U_j, S_j, 512]}) of one forward: the direct ``cfd_denoise_vjp_mem``
+        call.  ``wrt``: the memories whose gradient is wanted (names of ``MEM_NAMES``; none: the ``cfd_denoise_vjp`` call).  ``row_maps``
+        as in ``pack_memories``: a distinct memory receives the SUM over the batch rows that map to it, one that no row maps to exact
+        zeros; masked keys receive exact zeros.  ``grad`` is the sample's gradient as ``vjp`` returns it (bit for bit), or None with
+        ``want_grad=False`` (at least one memory must then be wanted)."""
+        wrt = tuple(wrt)
+        for name in wrt:
+            if name not in MEM_NAMES:
+                raise ValueError(f"wrt names a memory that does not exist: {name!r} (the memories are {', '.join(MEM_NAMES)})")
+        if not wrt and not want_grad:
+            raise ValueError("vjp_memories: nothing is wanted (wrt is empty and want_grad is False)")
+        if len(encoder_hidden_states) != _lib.NUM_MEM:
+            raise ValueError("encoder_hidden_states must be the 5-tuple (spk_emb, alsn, tlsn, apb, lsnemb)")
+        return self._vjp_call(sample, timestep, encoder_hidden_states, mem_mask_dict, d_out, wrt, row_maps, side_engine, want_out, want_grad,
+                              "its memories")
+
     # ---- forward -------------------------------------------------------------------------------
+    @staticmethod
+    def _refuse_grad(sample, timestep, encoder_hidden_states, mem_mask_dict, what):
+        """Every refusal the two differentiable forward modes share, before any device work.  ``what``: "its sample" ..."""
+        for name, m in (mem_mask_dict or {}).items():
+            if m is not None and m.requires_grad:
+                raise NotImplementedError(f"the HIP denoiser has no gradient with respect to a key-padding mask ({name} requires grad)")
+        if torch.as_tensor(timestep).numel() != 1:
+            raise NotImplementedError(f"the gradient of the HIP denoiser with respect to {what} needs one timestep for all rows "
+                                      "(a per-row timestep vector is not on the row-tile path)")
+        _require_row_tile(sample, encoder_hidden_states, what)
+
     def forward(self, sample, timestep, encoder_hidden_states, lengths=None, mem_mask_dict=dict(), **kwargs):
         """``kwargs['side_engine']=True`` (extension): run on the second handle, for calls made while a sampling run is
-        open on the first; ``kwargs['memory_grad']=True`` (extension): memories that require grad receive gradients too; every
-        other keyword (``return_dict`` ...) is ignored like the reference does.
+        open on the first; ``kwargs['memory_grad']=True`` (extension): memories that require grad receive gradients too (differentiable
+        when grad is enabled and the sample or any memory requires grad); every other keyword (``return_dict`` ...) is ignored like the
+        reference does.
         Under grad mode with ``sample.requires_grad`` the output is differentiable with respect to ``sample`` (module docstring)."""
         if sample.dim() != 3 or sample.shape[-1] != self.latent_dim:
             raise ValueError(f"sample must be [batch, tokens, {self.latent_dim}]")
-        if kwargs.get("memory_grad", False):
-            return self._forward_memory_grad(sample, timestep, encoder_hidden_states, mem_mask_dict, kwargs)
-        if not (torch.is_grad_enabled() and sample.requires_grad):
-            return self._forward_hip(sample, timestep, encoder_hidden_states, mem_mask_dict, kwargs)
-        # every refusal of the differentiable forward, before any device work
-        for name, m in zip(MEM_NAMES, encoder_hidden_states):
-            if m.requires_grad:
-                raise NotImplementedError(f"the HIP denoiser has no gradient with respect to its memories ({name} requires grad): detach it")
-        for name, m in (mem_mask_dict or {}).items():
-            if m is not None and m.requires_grad:
-                raise NotImplementedError(f"the HIP denoiser has no gradient with respect to a key-padding mask ({name} requires grad)")
-        if torch.as_tensor(timestep).numel() != 1:
-            raise NotImplementedError("the gradient of the HIP denoiser with respect to its sample needs one timestep for all rows "
-                                      "(a per-row timestep vector is not on the row-tile path)")
-        why = vjp_refusal(sample.shape[0], sample.shape[1], [int(m.shape[1]) for m in encoder_hidden_states])
-        if why is not None:
-            raise NotImplementedError(f"the gradient of the HIP denoiser with respect to its sample runs on the row-tile path only: {why}")
-        out, *att = _DenoiseVjp.apply(sample, self, timestep, encoder_hidden_states, mem_mask_dict, kwargs)
-        return (out, list(att))
-
-    def _forward_memory_grad(self, sample, timestep, encoder_hidden_states, mem_mask_dict, kwargs):
-        """``forward(..., memory_grad=True)``: differentiable when grad is enabled and the sample or any memory requires grad."""
-        if len(encoder_hidden_states) != _lib.NUM_MEM:
+        memory_grad = bool(kwargs.get("memory_grad", False))
+        if memory_grad and len(encoder_hidden_states) != _lib.NUM_MEM:
             raise ValueError("encoder_hidden_states must be the 5-tuple (spk_emb, alsn, tlsn, apb, lsnemb)")
-        if not (torch.is_grad_enabled() and (sample.requires_grad or any(m.requires_grad for m in encoder_hidden_states))):
+        if not (torch.is_grad_enabled() and (sample.requires_grad or (memory_grad and any(m.requires_grad for m in encoder_hidden_states)))):
             return self._forward_hip(sample, timestep, encoder_hidden_states, mem_mask_dict, kwargs)
-        # every refusal, before any device work
-        for name, m in (mem_mask_dict or {}).items():
-            if m is not None and m.requires_grad:
-                raise NotImplementedError(f"the HIP denoiser has no gradient with respect to a key-padding mask ({name} requires grad)")
-        if torch.as_tensor(timestep).numel() != 1:
-            raise NotImplementedError("the gradient of the HIP denoiser with respect to its sample and memories needs one timestep for all rows "
-                                      "(a per-row timestep vector is not on the row-tile path)")
         for name, m in zip(MEM_NAMES, encoder_hidden_states):
-            if m.dim() != 3 or m.shape[0] != sample.shape[0]:
+            if not memory_grad and m.requires_grad:
+                raise NotImplementedError(f"the HIP denoiser has no gradient with respect to its memories ({name} requires grad): detach it")
+            if memory_grad and (m.dim() != 3 or m.shape[0] != sample.shape[0]):
                 raise ValueError(f"memory_grad=True takes one memory per batch row: {name} has shape {list(m.shape)} for {sample.shape[0]} rows")
-        why = vjp_refusal(sample.shape[0], sample.shape[1], [int(m.shape[1]) for m in encoder_hidden_states])
-        if why is not None:
-            raise NotImplementedError(f"the gradient of the HIP denoiser with respect to its sample and memories runs on the row-tile path only: {why}")
-        out, *att = _DenoiseVjpMem.apply(self, timestep, mem_mask_dict, kwargs, sample, *encoder_hidden_states)
+        self._refuse_grad(sample, timestep, encoder_hidden_states, mem_mask_dict, "its sample and memories" if memory_grad else "its sample")
+        out, *att = _DenoiseVjp.apply(self, timestep, mem_mask_dict, kwargs, memory_grad, sample, *encoder_hidden_states)
         return (out, list(att))
 
     def _forward_hip(self, sample, timestep, encoder_hidden_states, mem_mask_dict, kwargs):

@@ -23,7 +23,7 @@ kernel reads a packed copy of the encoder weights that is rebuilt whenever a par
 d_feats)`` is one call of cfd_vae_decode_vjp (csrc/vae_dec.hpp): a forward of both decoder stacks on 16-frame row tiles that saves what the
 reverse sweep needs, and the sweep from the cotangent at the 189 features back to the latents -- what the reference gets from torch autograd
 over its ``decode``.  Exact float32, no atomics (two calls return the same bits), nframes <= 256, n_chunks <= 16.  It reads a packed copy of
-the decoder weights (every matrix in both orders, ``_decoder_pack``) kept like the encoder's.  No gradients to weights or lengths.
+the decoder weights (every matrix in both orders, ``_decoder_pack``) kept by the same cache rule as the encoder's (``_cached_pack``).  No gradients to weights or lengths.
 """
 import ctypes as C
 
@@ -45,6 +45,13 @@ def _ptr(t):
 
 def _stream(t):
     return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+
+
+def _lengths_list(lengths, default=None):
+    """Frames per sequence as a list of ints, from a list / tuple / tensor; None means ``default``."""
+    if lengths is None:
+        return default
+    return [int(v) for v in (lengths.reshape(-1).tolist() if torch.is_tensor(lengths) else lengths)]
 
 
 def layer_norm(x, norm):
@@ -169,8 +176,7 @@ class ConvoFusionVae(nn.Module):
         self.latent_size, self.latent_dim = latent_dim[0], latent_dim[-1]
         self.body_nfeats, self.hands_nfeats = 23 * 3, 40 * 3                  # vae.py:53-54
         self.arch, self.num_heads, self.num_layers, self.ff_size = arch, num_heads, num_layers, ff_size
-        self._enc_pack, self._enc_key = None, None
-        self._dec_pack, self._dec_key = None, None
+        self._packs = {}                                                      # name -> (key, pack): _cached_pack
         d = self.latent_dim
         self.body_global_motion_token = nn.Parameter(torch.randn(self.latent_size * 2, d))
         self.hands_global_motion_token = nn.Parameter(torch.randn(self.latent_size * 2, d))
@@ -206,17 +212,20 @@ class ConvoFusionVae(nn.Module):
             src += [(enc.norm.weight, None), (enc.norm.bias, None)]
         return src
 
-    def _encoder_pack(self, dev):
-        """The packed encoder weights of both stacks on ``dev``; rebuilt when any source tensor was replaced or written."""
-        src = self._encoder_sources()
+    def _cached_pack(self, name, dev, src, parts_of, n_floats):
+        """The packed copy ``name`` of the sources ``src`` [(tensor, kind)] on ``dev``: ``parts_of(tensor on dev as float32, kind)`` lists a
+        source's parts; rebuilt when any source tensor was replaced or written (its address or version counter moved)."""
         key = (str(dev),) + tuple((t.data_ptr(), t._version) for t, _ in src)
-        if self._enc_pack is None or self._enc_key != key:
-            parts = [_pack_w(t.detach().to(dev, torch.float32), k) if k is not None else t.detach().to(dev, torch.float32).reshape(-1)
-                     for t, k in src]
-            pack = torch.cat(parts).contiguous()
-            assert pack.numel() == 2 * encoder_pack_floats(self.num_layers), pack.numel()
-            self._enc_pack, self._enc_key = pack, key
-        return self._enc_pack
+        if name not in self._packs or self._packs[name][0] != key:
+            pack = torch.cat([part for t, kind in src for part in parts_of(t.detach().to(dev, torch.float32), kind)]).contiguous()
+            assert pack.numel() == n_floats, pack.numel()
+            self._packs[name] = (key, pack)
+        return self._packs[name][1]
+
+    def _encoder_pack(self, dev):
+        """The packed encoder weights of both stacks on ``dev`` (``_cached_pack``)."""
+        return self._cached_pack("encoder", dev, self._encoder_sources(), lambda t, k: [_pack_w(t, k) if k is not None else t.reshape(-1)],
+                                 2 * encoder_pack_floats(self.num_layers))
 
     def _encode_spec_error(self):
         if (self.latent_dim, self.num_heads, self.ff_size, self.latent_size) != (ENC_D, 2, 1024, 1) or self.num_layers > 9:
@@ -234,10 +243,7 @@ class ConvoFusionVae(nn.Module):
         if features.dim() != 3 or features.shape[-1] != nf:
             raise ValueError(f"features must be [bs, nframes, {nf}], got {tuple(features.shape)}")
         bs, nframes, _ = features.shape
-        if lengths is None:
-            lens = [nframes] * bs                                                            # vae.py:168
-        else:
-            lens = [int(v) for v in (lengths.reshape(-1).tolist() if torch.is_tensor(lengths) else lengths)]
+        lens = _lengths_list(lengths, [nframes] * bs)                                        # vae.py:168
         if bs < 1 or len(lens) != bs:
             raise ValueError(f"{len(lens)} lengths for a batch of {bs}")
         if nframes < 16 or nframes % 16:
@@ -275,7 +281,7 @@ class ConvoFusionVae(nn.Module):
         if z.device.type != "cuda":
             raise RuntimeError("the HIP VAE decoder runs on an MI355X only (move the module and z to 'cuda'); no CPU fallback")
         if torch.is_grad_enabled() and z.requires_grad:
-            lens = [int(v) for v in (lengths.reshape(-1).tolist() if torch.is_tensor(lengths) else lengths)]
+            lens = _lengths_list(lengths)
             why = self._decode_vjp_refusal(z, lens, None)
             if why:
                 raise NotImplementedError(f"decode cannot be differentiated here: {why}")
@@ -325,25 +331,15 @@ class ConvoFusionVae(nn.Module):
         return src
 
     def _decoder_pack(self, dev):
-        """The packed decoder weights of both stacks and the two PE tables on ``dev``; rebuilt when any source tensor was replaced or
-        written, exactly as ``_encoder_pack``."""
-        src = self._decoder_sources()
-        key = (str(dev),) + tuple((t.data_ptr(), t._version) for t, _ in src)
-        if self._dec_pack is None or self._dec_key != key:
-            parts = []
-            for t, kind in src:
-                t = t.detach().to(dev, torch.float32)
-                if kind in ("v", "fb"):
-                    t = t.reshape(-1)
-                    parts.append(F.pad(t, (0, ENC_D - t.numel())) if kind == "fb" else t)
-                else:
-                    if kind == "f":
-                        t = F.pad(t, (0, 0, 0, ENC_D - t.shape[0]))
-                    parts += [_pack_w(t), _pack_w(t.t().contiguous())]
-            pack = torch.cat(parts).contiguous()
-            assert pack.numel() == decoder_pack_floats(self.num_layers), pack.numel()
-            self._dec_pack, self._dec_key = pack, key
-        return self._dec_pack
+        """The packed decoder weights of both stacks and the two PE tables on ``dev`` (``_cached_pack``, like the encoder's)."""
+        def parts_of(t, kind):
+            if kind in ("v", "fb"):
+                t = t.reshape(-1)
+                return [F.pad(t, (0, ENC_D - t.numel())) if kind == "fb" else t]
+            if kind == "f":
+                t = F.pad(t, (0, 0, 0, ENC_D - t.shape[0]))
+            return [_pack_w(t), _pack_w(t.t().contiguous())]
+        return self._cached_pack("decoder", dev, self._decoder_sources(), parts_of, decoder_pack_floats(self.num_layers))
 
     def _decode_vjp_refusal(self, z, lens, d_feats):
         """ValueError for arguments ``decode_vjp`` cannot mean anything for; returns the NotImplementedError text for shapes beyond the
@@ -369,7 +365,7 @@ class ConvoFusionVae(nn.Module):
         reference.  d_feats [bs, nframes, 189] is the cotangent at decode's output; its rows at or beyond a sequence's length are not
         read.  Deterministic: the same inputs give the same bits.  Returns with its results complete.  ValueError: a length below 1, a wrong shape, max(lengths) !=
         d_feats.shape[1]; NotImplementedError beyond the kernels' limits (``decode_vjp_refusal``), before any device work."""
-        lens = [int(v) for v in (lengths.reshape(-1).tolist() if torch.is_tensor(lengths) else lengths)]
+        lens = _lengths_list(lengths)
         why = self._decode_vjp_refusal(z, lens, d_feats)
         if why:
             raise NotImplementedError(f"decode_vjp: {why}")
@@ -454,22 +450,23 @@ def _mirror_of(vae, skip):
     return m.to(next(vae.parameters()).device).eval()
 
 
-def attach_hip_decode(vae):
-    """Route ``vae.decode`` of a REFERENCE ``ConvoFusionVae`` instance (kept for encode / training) to the HIP path:
-    builds the mirror from the module's own hyper-parameters and weights and replaces the bound method.  The mirror
-    takes a snapshot of the weights: call again after loading a different checkpoint.  Returns the mirror."""
-    m = _mirror_of(vae, vae.body_decoder)
-    vae.decode = m.decode
+def _attach(vae, skip_attr, method):
+    """Route ``vae.<method>`` of a REFERENCE ``ConvoFusionVae`` instance to the HIP path: builds the mirror from the module's own
+    hyper-parameters (read off ``vae.<skip_attr>``) and weights and replaces the bound method.  The mirror takes a snapshot of the
+    weights: call again after loading a different checkpoint.  Returns the mirror."""
+    m = _mirror_of(vae, getattr(vae, skip_attr))
+    setattr(vae, method, getattr(m, method))
     return m
+
+
+def attach_hip_decode(vae):
+    """``vae.decode`` of a reference instance (kept for encode / training) on the HIP path (``_attach``).  Returns the mirror."""
+    return _attach(vae, "body_decoder", "decode")
 
 
 def attach_hip_encode(vae):
-    """Route ``vae.encode`` of a REFERENCE ``ConvoFusionVae`` instance (kept for training) to the HIP path: builds the mirror from
-    the module's own hyper-parameters and weights and replaces the bound method.  The mirror takes a snapshot of the weights: call
-    again after loading a different checkpoint.  Returns the mirror."""
-    m = _mirror_of(vae, vae.body_encoder)
-    vae.encode = m.encode
-    return m
+    """``vae.encode`` of a reference instance (kept for training) on the HIP path (``_attach``).  Returns the mirror."""
+    return _attach(vae, "body_encoder", "encode")
 
 
 ENC_D, ENC_TOKENS = 128, 18      # d_model, 2 global tokens + 16 frames per sequence

@@ -227,7 +227,51 @@ static void test_graph_exec() {
   EXPECT(g_destroyed.size() == 2);
 }
 
+// ArenaLayout: one statement of a workspace's buffers, run to size (null base) and run to carve.  Three field lists whose counts are no
+// multiples of the granule, at the granules the library uses (4 floats: the VAE decode; 64: the row-tile arenas).
+struct Fields {                                                        // buffers of more than one element type, like RtSave
+  float* f[6];
+  char* bytes;
+  int* ints;
+};
+static void test_arena_layout() {
+  const std::vector<std::vector<size_t>> lists = {{1, 2, 3, 5, 7, 9, 11, 13}, {63, 65, 127, 129, 1, 4097, 640, 3}, {1000003, 1, 0, 17, 255, 257, 5, 64}};
+  for (size_t granule : {(size_t)4, (size_t)64}) {
+    for (const std::vector<size_t>& n : lists) {
+      Fields fd;
+      auto layout = [&](ArenaLayout a) {                               // each buffer named once, in the order it is carved
+        for (int k = 0; k < 6; ++k) a.take(fd.f[k], n[k]);
+        a.take(fd.bytes, n[6]);
+        a.take(fd.ints, n[7]);
+        return a.bytes();
+      };
+      const size_t need = layout(ArenaLayout(nullptr, granule));
+      EXPECT(fd.f[0] == nullptr && fd.bytes == nullptr && fd.ints == nullptr);   // the sizing pass hands out nothing
+      size_t sum = 0;
+      for (size_t v : n) sum += (v + granule - 1) / granule * granule;
+      EXPECT(need == sum * sizeof(float));                             // every count rounded up to the granule, nothing else
+      std::vector<float> mem(need / sizeof(float) + 1, 0.f);          // (+ 1: an address one past the arena stays a valid one)
+      EXPECT(layout(ArenaLayout(mem.data(), granule)) == need);        // the carving pass consumes exactly what the sizing pass asked for
+      const float* at[9] = {fd.f[0], fd.f[1], fd.f[2], fd.f[3], fd.f[4], fd.f[5], reinterpret_cast<float*>(fd.bytes),
+                            reinterpret_cast<float*>(fd.ints), mem.data() + need / sizeof(float)};
+      EXPECT(at[0] == mem.data());
+      for (int k = 0; k < 8; ++k) {
+        EXPECT((size_t)(at[k] - mem.data()) % granule == 0);           // granule-aligned,
+        EXPECT(at[k + 1] >= at[k] + n[k]);                             // in call order, and disjoint: buffer k ends before k + 1 starts
+        EXPECT((size_t)(at[k + 1] - at[k]) < n[k] + granule);          // ... with less than one granule between them
+      }
+      for (int k = 0; k < 6; ++k)
+        for (size_t i = 0; i < n[k]; ++i) fd.f[k][i] = (float)(k + 1); // (under AddressSanitizer: every element lies inside the allocation)
+      for (int k = 0; k < 6; ++k) EXPECT(n[k] == 0 || (fd.f[k][0] == (float)(k + 1) && fd.f[k][n[k] - 1] == (float)(k + 1)));
+    }
+  }
+  ArenaLayout y(nullptr, 64);
+  EXPECT(y.rounded(0) == 0 && y.rounded(1) == 64 && y.rounded(64) == 64 && y.rounded(65) == 128 && y.bytes() == 0);
+  if (!g_failed) printf("ArenaLayout: %d layouts sized and carved alike\n", (int)(2 * lists.size()));
+}
+
 int main() {
+  test_arena_layout();
   test_ensure();
   test_failed_malloc();
   EXPECT(live() == 0 && live_bytes() == 0 && consistent());

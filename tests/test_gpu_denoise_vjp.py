@@ -201,6 +201,63 @@ def test_library_names_the_limit_it_refuses():
     assert call(1, 15, (3, 5, 6, 2, 1))[0] == -2          # odd length: CFD_E_SHAPE like every entry point
 
 
+def test_three_entry_points_refuse_a_latent_call_alike_and_before_any_launch():
+    """Be = 1, L = 4, S = (3, 5, 6, 2, 1): an odd L (3), timestep = the table's rows, and a memory one token past the memory PE's rows
+    come back from cfd_weg_eval, cfd_denoise_vjp and cfd_denoise_vjp_mem with the same code and the same cfd_last_error text (one
+    check_latent_call behind all three), each before any launch: "weg.info" still reports the launches of the call before, a
+    vjp_memories whose count (the sweep plus the memory gradient's launches) neither of the other two entry points has."""
+    import torch
+    from convofusion_amd import _lib
+    from tests.gpu_helpers import hip_denoiser, read_debug
+    m = hip_denoiser(1234, 1.0)
+    h = m.engine(torch.device("cuda"))
+    lib = _lib.load()
+    S, T = (3, 5, 6, 2, 1), 1000
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    ok_mems = [torch.zeros(1, s, 512, device="cuda") for s in S]
+    x4 = torch.zeros(1, 4, 128, device="cuda")
+    m.vjp_memories(x4, 5, ok_mems, {}, torch.ones_like(x4))
+    before = read_debug(m, "weg.info", (5,))
+    assert int(before[0]) > 0
+    tok_off, tok_idx = np.array([0, 1], dtype=np.int32), np.array([2], dtype=np.int32)
+
+    def calls(L, t, S):
+        x = torch.zeros(1, L, 128, device="cuda")
+        arr, keep = m.pack_memories([torch.zeros(1, s, 512, device="cuda") for s in S], {})
+        g, small = torch.empty_like(x), torch.empty(4, device="cuda")
+        px, pg = C.c_void_p(x.data_ptr()), C.c_void_p(g.data_ptr())
+        w = _lib.WegArgs()
+        w.B, w.L, w.timestep, w.latents, w.mem = 1, L, t, x.data_ptr(), arr
+        w.tok_off, w.tok_idx, w.last = tok_off.ctypes.data, tok_idx.ctypes.data, 5
+        w.kernel3 = (C.c_float * 3)(0.25, 0.5, 0.25)
+        a = _lib.VjpArgs()
+        a.Be, a.L, a.timestep, a.sample, a.mem = 1, L, t, x.data_ptr(), arr
+        d_mem = (C.c_void_p * _lib.NUM_MEM)()
+        d0 = torch.empty(1, S[0], 512, device="cuda")
+        d_mem[0] = d0.data_ptr()
+        got = []
+        for entry in (lambda: lib.cfd_weg_eval(h, C.byref(w), C.c_void_p(small.data_ptr()), C.c_void_p(small.data_ptr()), pg, None, stream),
+                      lambda: lib.cfd_denoise_vjp(h, C.byref(a), px, None, pg, stream),
+                      lambda: lib.cfd_denoise_vjp_mem(h, C.byref(a), px, None, pg, d_mem, stream)):
+            got.append((entry(), lib.cfd_last_error().decode()))
+            assert np.array_equal(read_debug(m, "weg.info", (5,)), before), got[-1]
+        del keep
+        return got
+
+    rows = m._main["mem_len"]                       # the memory PE's rows on this handle (1024, or what an earlier call extended it to)
+    for what, args, code, text in (("odd L", (3, 5, S), -2, "latent length 3 is odd"),
+                                   ("timestep", (4, T, S), -1, f"timestep {T} outside the timestep table ({T} rows)"),
+                                   ("memory PE", (4, 5, (3, rows + 1, 6, 2, 1)), -2, f"memory alsn has {rows + 1} tokens, memory PE buffer has {rows} rows")):
+        got = calls(*args)
+        print(what, "->", got)
+        assert got[0] == got[1] == got[2], (what, got)
+        assert got[0][0] == code and text in got[0][1], (what, got)
+    # the handle is as it was: the call before, again, to the bit
+    g0 = m.vjp_memories(x4, 5, ok_mems, {}, torch.ones_like(x4))
+    assert np.array_equal(read_debug(m, "weg.info", (5,)), before)
+    assert torch.equal(g0[1], m.vjp(x4, 5, ok_mems, {}, torch.ones_like(x4))[1])
+
+
 def test_weg_evaluations_around_a_vjp_reuse_nothing_it_overwrote():
     """cfd_weg_eval and cfd_denoise_vjp share the row-tile arena, the workspace and the per-timestep tables: a WEG evaluation that
     states "same conditioning" behind a VJP call -- on the SAME memories, and on others of another shape -- equals a fresh one."""

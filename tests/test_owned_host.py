@@ -18,19 +18,35 @@ def _rocm_include():
     return None
 
 
-def test_owned_resources_under_sanitizers(tmp_path):
+@pytest.fixture(scope="module")
+def owned_test_run(tmp_path_factory):
+    """The program, built and run once: its CompletedProcess."""
     gxx = shutil.which("g++")
     if gxx is None:
         pytest.skip("no g++ on this machine")
     inc = _rocm_include()
     if inc is None:
         pytest.skip("no ROCm headers (hip/hip_runtime_api.h) on this machine")
-    exe = str(tmp_path / "owned_test")
+    exe = str(tmp_path_factory.mktemp("owned") / "owned_test")
     # (the sanitizers' runtimes are linked into the program, so it runs the same whatever else the loader brings in)
     cmd = [gxx, "-std=c++17", "-g", "-O1", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
            "-static-libasan", "-static-libubsan", "-D__HIP_PLATFORM_AMD__", "-I" + inc, SRC, "-o", exe]
     built = subprocess.run(cmd, capture_output=True, text=True)
     assert built.returncode == 0, built.stdout + built.stderr
-    run = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    return subprocess.run([exe], capture_output=True, text=True, timeout=120)
+
+
+def test_owned_resources_under_sanitizers(owned_test_run):
+    run = owned_test_run
     assert run.returncode == 0, run.stdout + run.stderr
     assert "all checks passed" in run.stdout
+
+
+def test_arena_layout_sizes_exactly_what_it_carves(owned_test_run):
+    """ArenaLayout (owned.hpp), the one statement of a workspace's buffers behind wegrt::prepare, wegrt::prepare_mem_grad and
+    cfd_vae_decode_vjp: for three field lists whose counts are no multiples of the granule, at granule 4 and at granule 64, the sizing
+    pass (null base) returns exactly the bytes the carving pass consumes, and the carved addresses are granule-aligned, in call order and
+    disjoint (test_arena_layout of the program; under AddressSanitizer every element of every buffer is written)."""
+    run = owned_test_run
+    assert run.returncode == 0, run.stdout + run.stderr
+    assert "ArenaLayout: 6 layouts sized and carved alike" in run.stdout

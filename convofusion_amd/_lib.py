@@ -28,6 +28,7 @@ SYMBOLS = [
     "cfd_sample_begin_tied", "cfd_ddpm_invert", "cfd_sample_begin_replay", "cfd_sample_parallel", "cfd_test_picard_stride",
     "cfd_test_picard_sweep", "cfd_debug_weg_stop", "cfd_debug_weg_fill", "cfd_scheduler_step_pred", "cfd_dpmsolver_step_pred",
     "cfd_debug_forward_operands", "cfd_denoise_vjp", "cfd_debug_live_buffers", "cfd_vae_decode_vjp", "cfd_denoise_vjp_mem",
+    "cfd_vae_decode", "cfd_vae_decode_sweep", "cfd_vae_decode_ticket", "cfd_debug_vae_workspace",
 ]
 
 # cfd_sample_args.prediction_type / the _pred entry points, by the schedulers' config string
@@ -141,6 +142,11 @@ class VaeDecodeVjpArgs(C.Structure):
     _fields_ = [("wpack", C.c_void_p), ("d_model", C.c_int), ("num_heads", C.c_int), ("ff_size", C.c_int), ("num_layers", C.c_int),
                 ("bs", C.c_int), ("nframes", C.c_int), ("n_chunks", C.c_int), ("z", C.c_void_p), ("lengths", C.c_void_p),
                 ("d_feats", C.c_void_p)]
+
+
+class VaeDecodeArgs(C.Structure):
+    """cfd_vae_decode_args: one ConvoFusionVae.decode on the fused forward (cfd_vae_decode); cfd_vae_decode_vjp_args without the cotangent."""
+    _fields_ = VaeDecodeVjpArgs._fields_[:-1]
 
 
 # cfd_test_epi_args.kind (include/cfdenoise_dev.h)
@@ -295,6 +301,11 @@ def load():
     lib.cfd_denoise_vjp.argtypes = [C.c_void_p, C.POINTER(VjpArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.cfd_denoise_vjp_mem.argtypes = [C.c_void_p, C.POINTER(VjpArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p]
     lib.cfd_vae_decode_vjp.argtypes = [C.c_void_p, C.POINTER(VaeDecodeVjpArgs), C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.cfd_vae_decode.argtypes = [C.c_void_p, C.POINTER(VaeDecodeArgs), C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]
+    lib.cfd_vae_decode_sweep.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.cfd_vae_decode_ticket.argtypes = [C.c_void_p]
+    lib.cfd_vae_decode_ticket.restype = C.c_uint64
+    lib.cfd_debug_vae_workspace.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
     lib.cfd_dyadic_steps.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(DyadicProj), C.c_int]
     lib.cfd_debug_stop_stage.argtypes = [C.c_void_p, C.c_int]
     lib.cfd_debug_read.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t]
@@ -304,7 +315,7 @@ def load():
     lib.cfd_debug_live_buffers.argtypes = [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
     for name in SYMBOLS:
         fn = getattr(lib, name)
-        if name not in ("cfd_last_error", "cfd_destroy", "cfd_source_hash"):
+        if name not in ("cfd_last_error", "cfd_destroy", "cfd_source_hash", "cfd_vae_decode_ticket"):
             fn.restype = C.c_int
     _lib = lib
     return lib

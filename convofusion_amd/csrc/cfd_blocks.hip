@@ -1,6 +1,6 @@
 // libcfdenoise: float32 building blocks on device tensors -- the conditioning producers (cfd_linear_act) and the pieces of
 // ConvoFusionVae.decode (cfd_layer_norm, cfd_mha, cfd_add, cfd_zero_rows) -- ConvoFusionVae.encode in one launch (cfd_vae_encode) and the
-// differentiable decode (cfd_vae_decode_vjp).
+// fused decode, forward-only, kept for a later sweep, or with its sweep in one call (cfd_vae_decode, cfd_vae_decode_sweep, cfd_vae_decode_vjp).
 #include "cfd_internal.hpp"
 #include "vae_enc.hpp"
 #include "vae_dec.hpp"
@@ -131,60 +131,112 @@ extern "C" int cfd_vae_encode(cfd_handle c, const float* wpack, int d_model, int
 }
 
 
-// ---- ConvoFusionVae.decode with d(feats)/d(z) (autograd over vae.py:268-372): csrc/vae_dec.hpp -----------------------------------------------
-extern "C" int cfd_vae_decode_vjp(cfd_handle c, const cfd_vae_decode_vjp_args* p, float* feats, float* d_z, void* stream) {
-  if (!c || !p || !p->wpack || !p->z || !p->lengths || !p->d_feats || !d_z) return fail(CFD_E_ARG, "bad argument (NULL pointer)");
+// ---- ConvoFusionVae.decode, forward-only or kept for its sweep d(feats)/d(z) (autograd over vae.py:268-372): csrc/vae_dec.hpp ------------------
+// One call path: cfd_vae_decode = vae_decode_forward; cfd_vae_decode_sweep = vae_decode_sweep; cfd_vae_decode_vjp = the two in a row.
+
+// the limits of the three entry points (`who` names the caller in the message)
+static int vae_decode_check(const char* who, const cfd_vae_decode_args* p) {
   if (p->d_model != VE_D || p->num_heads != 2 || p->ff_size != VE_FF || p->num_layers < 1 || p->num_layers > VE_MAX_LAYERS || p->num_layers % 2 == 0)
-    return fail(CFD_E_ARG, "cfd_vae_decode_vjp implements d_model 128, 2 heads, ff 1024 and odd num_layers <= %d only (got %d, %d, %d, %d)",
+    return fail(CFD_E_ARG, "%s implements d_model 128, 2 heads, ff 1024 and odd num_layers <= %d only (got %d, %d, %d, %d)", who,
                 VE_MAX_LAYERS, p->d_model, p->num_heads, p->ff_size, p->num_layers);
-  if (p->bs < 1 || p->bs > 65535) return fail(CFD_E_ARG, "cfd_vae_decode_vjp takes 1 <= bs <= 65535 sequences (got %d)", p->bs);
-  if (p->nframes < 1 || p->nframes > VD_MAX_FRAMES) return fail(CFD_E_ARG, "cfd_vae_decode_vjp takes 1 <= nframes <= %d (got %d)", VD_MAX_FRAMES, p->nframes);
-  if (p->n_chunks < 1 || p->n_chunks > VD_MAX_CHUNKS) return fail(CFD_E_ARG, "cfd_vae_decode_vjp takes 1 <= n_chunks <= %d (got %d)", VD_MAX_CHUNKS, p->n_chunks);
-  HIPCHK(hipSetDevice(c->cfg.device));
-  hipStream_t st = (hipStream_t)stream;
+  if (p->bs < 1 || p->bs > 65535) return fail(CFD_E_ARG, "%s takes 1 <= bs <= 65535 sequences (got %d)", who, p->bs);
+  if (p->nframes < 1 || p->nframes > VD_MAX_FRAMES) return fail(CFD_E_ARG, "%s takes 1 <= nframes <= %d (got %d)", who, VD_MAX_FRAMES, p->nframes);
+  if (p->n_chunks < 1 || p->n_chunks > VD_MAX_CHUNKS) return fail(CFD_E_ARG, "%s takes 1 <= n_chunks <= %d (got %d)", who, VD_MAX_CHUNKS, p->n_chunks);
+  return CFD_OK;
+}
+
+// The shape fields of `a` from (nl, bs, nframes, n_chunks) and its workspace pointers carved from `base` (null: sizing only, every pointer
+// null); returns the bytes.  save: the VJP workspace, every layer resident, in the order of VaeDecArgs.  Forward-only: what is live between
+// two forward launches (vd_xslot, vd_lslot) -- per token row (nb + 2) stream slots, q | k | v and o: (nb + 6) * 512 bytes, 4096 at 5 layers
+// -- and the memory's K | V, nl * 16 KiB per (stack, sequence); every other pointer null.  keep_w, the copy of the weights for a sweep in a
+// later call, comes last and is only counted when `copy_w` asks for it: cfd_vae_decode_vjp sweeps inside the call and reads the caller's.
+static size_t vae_decode_layout(VaeDecArgs& a, int nl, int bs, int nframes, int n_chunks, float* base, bool save, bool copy_w) {
+  a.nl = nl;
+  a.nb = (nl - 1) / 2;
+  a.stack_floats = vd_stack_floats(nl);
+  a.bs = bs;
+  a.nframes = nframes;
+  a.nt = (nframes + 15) / 16;
+  a.fp = 16 * a.nt;
+  a.n_chunks = n_chunks;
+  a.rows = 2LL * bs * a.fp;
+  const long long R = a.rows, L = nl, sb = 2LL * bs;
+  ArenaLayout y(base, 4);   // 4 floats: every buffer starts on a float4
+  a.x1 = a.x2 = a.lse = a.qc = a.g = a.g1 = a.d_o = a.dd = a.dqkv = a.gskip = a.pkv = a.dzl = a.keep_w = nullptr;
+  a.keep_len = nullptr;
+  if (!save) {
+    y.take(a.x0, (a.nb + 2) * R * VE_D); y.take(a.qkv, R * 3 * VE_D); y.take(a.o, R * VE_D); y.take(a.mkv, L * sb * 16 * 256);
+    return y.bytes();
+  }
+  y.take(a.x0, (L + 1) * R * VE_D); y.take(a.x1, L * R * VE_D); y.take(a.x2, L * R * VE_D); y.take(a.qkv, L * R * 3 * VE_D);
+  y.take(a.o, L * R * VE_D); y.take(a.lse, L * R * 2); y.take(a.qc, L * R * VE_D); y.take(a.mkv, L * sb * 16 * 256);
+  y.take(a.g, L * R * VE_D); y.take(a.g1, R * VE_D); y.take(a.d_o, R * VE_D); y.take(a.dd, R * 2); y.take(a.dqkv, R * 3 * VE_D);
+  y.take(a.gskip, (a.nb ? a.nb : 1) * R * VE_D); y.take(a.pkv, L * sb * a.nt * 16 * 256); y.take(a.dzl, L * sb * 16 * VE_D);
+  y.take(a.keep_len, bs);
+  y.take(a.keep_w, copy_w ? 2 * a.stack_floats : 0);
+  return y.bytes();
+}
+
+template <bool SAVE>
+static int vae_decode_forward_launches(const VaeDecArgs& a, bool copy_w, hipStream_t st) {
+  const dim3 grid((unsigned)a.nt, (unsigned)a.bs, 2), blk(256);
+  // copy_w: about 256 more blocks, spread over the grid's first axis, copy the weights for a sweep in a later call
+  const unsigned copy = SAVE && copy_w ? (unsigned)((256 + 2 * a.bs - 1) / (2 * a.bs)) : 0;
+  int n = 0;
+  hipLaunchKernelGGL(vd_mem_kernel<SAVE>, dim3((unsigned)a.nl + copy, (unsigned)a.bs, 2), blk, 0, st, a);
+  ++n;
+  for (int l = 0; l <= a.nl; ++l) {
+    hipLaunchKernelGGL(vd_fwd_rows_kernel<SAVE>, grid, blk, 0, st, a, l);
+    ++n;
+    if (l < a.nl) {
+      hipLaunchKernelGGL(vd_self_fwd_kernel<SAVE>, grid, blk, 0, st, a, l);
+      ++n;
+    }
+  }
+  return n;
+}
+
+// The forward of `p` into feats (may be null with save).  Whatever forward the handle kept is dropped first: this one overwrites it.
+// save: the activations and the lengths stay in the workspace and the handle's ticket names them; copy_w: the weights too.
+static int vae_decode_forward(Ctx* c, const char* who, const cfd_vae_decode_args* p, float* feats, bool save, bool copy_w, hipStream_t st) {
+  auto& v = c->vae;
+  v.ticket = 0;
+  v.dropped_by = who;
   VaeDecArgs a;
-  a.nl = p->num_layers;
-  a.nb = (a.nl - 1) / 2;
+  const size_t bytes = vae_decode_layout(a, p->num_layers, p->bs, p->nframes, p->n_chunks, nullptr, save, copy_w);
+  v.grew = bytes > v.ws.bytes;
+  CHK(v.ws.ensure(bytes));
+  vae_decode_layout(a, p->num_layers, p->bs, p->nframes, p->n_chunks, v.ws.as<float>(), save, copy_w);
   a.w = p->wpack;
-  a.stack_floats = vd_stack_floats(a.nl);
   a.qpe = p->wpack + 2 * a.stack_floats;
   a.mpe = a.qpe + (long long)VD_MAX_FRAMES * VE_D;
   a.z = p->z;
   a.lengths = p->lengths;
-  a.d_feats = p->d_feats;
+  a.d_feats = nullptr;
   a.feats = feats;
+  a.d_z = nullptr;
+  v.g = a.g; v.dzl = a.dzl; v.x0 = save ? a.x0 : nullptr;
+  v.bs = a.bs; v.fp = a.fp; v.nl = a.nl; v.rows = a.rows; v.nframes = a.nframes; v.n_chunks = a.n_chunks;
+  v.launches = v.fwd_launches = save ? vae_decode_forward_launches<true>(a, copy_w, st) : vae_decode_forward_launches<false>(a, false, st);
+  HIPCHK(hipGetLastError());
+  if (save) v.ticket = ++v.serial;
+  return CFD_OK;
+}
+
+// The reverse sweep over the handle's kept forward: reads the workspace (activations, lengths), d_feats and the packed weights `w` -- null:
+// the copy the forward kept, so that nothing of the caller's is read but d_feats.
+static int vae_decode_sweep(Ctx* c, const float* w, const float* d_feats, float* d_z, hipStream_t st) {
+  auto& v = c->vae;
+  VaeDecArgs a;
+  vae_decode_layout(a, v.nl, v.bs, v.nframes, v.n_chunks, v.ws.as<float>(), true, true);
+  a.w = w ? w : a.keep_w;
+  a.lengths = a.keep_len;
+  a.qpe = a.mpe = a.z = nullptr;
+  a.feats = nullptr;
+  a.d_feats = d_feats;
   a.d_z = d_z;
-  a.bs = p->bs;
-  a.nframes = p->nframes;
-  a.nt = (p->nframes + 15) / 16;
-  a.fp = 16 * a.nt;
-  a.n_chunks = p->n_chunks;
-  a.rows = 2LL * a.bs * a.fp;
-  // the workspace (the handle's, this call's own): sized from the shapes, carved in the order of VaeDecArgs
-  const long long R = a.rows, nl = a.nl, sb = 2LL * a.bs;
-  auto layout = [&](ArenaLayout y) {   // 4 floats: every buffer starts on a float4
-    y.take(a.x0, (nl + 1) * R * VE_D); y.take(a.x1, nl * R * VE_D); y.take(a.x2, nl * R * VE_D); y.take(a.qkv, nl * R * 3 * VE_D);
-    y.take(a.o, nl * R * VE_D); y.take(a.lse, nl * R * 2); y.take(a.qc, nl * R * VE_D); y.take(a.mkv, nl * sb * 16 * 256);
-    y.take(a.g, nl * R * VE_D); y.take(a.g1, R * VE_D); y.take(a.d_o, R * VE_D); y.take(a.dd, R * 2); y.take(a.dqkv, R * 3 * VE_D);
-    y.take(a.gskip, (a.nb ? a.nb : 1) * R * VE_D); y.take(a.pkv, nl * sb * a.nt * 16 * 256); y.take(a.dzl, nl * sb * 16 * VE_D);
-    return y.bytes();
-  };
-  CHK(c->vae.ws.ensure(layout(ArenaLayout(nullptr, 4))));
-  layout(ArenaLayout(c->vae.ws.as<float>(), 4));
-  c->vae.g = a.g; c->vae.dzl = a.dzl; c->vae.x0 = a.x0;
-  c->vae.bs = a.bs; c->vae.fp = a.fp; c->vae.nl = a.nl; c->vae.rows = a.rows;
   const dim3 grid((unsigned)a.nt, (unsigned)a.bs, 2), blk(256);
   int n = 0;
-  hipLaunchKernelGGL(vd_mem_kernel, dim3((unsigned)a.nl, (unsigned)a.bs, 2), blk, 0, st, a);
-  ++n;
-  for (int l = 0; l <= a.nl; ++l) {
-    hipLaunchKernelGGL(vd_fwd_rows_kernel, grid, blk, 0, st, a, l);
-    ++n;
-    if (l < a.nl) {
-      hipLaunchKernelGGL(vd_self_fwd_kernel, grid, blk, 0, st, a, l);
-      ++n;
-    }
-  }
   for (int l = a.nl - 1; l >= 0; --l) {
     hipLaunchKernelGGL(vd_bwd_rows_kernel, grid, blk, 0, st, a, l);
     ++n;
@@ -197,15 +249,49 @@ extern "C" int cfd_vae_decode_vjp(cfd_handle c, const cfd_vae_decode_vjp_args* p
   hipLaunchKernelGGL(vd_dz_sum_kernel, dim3((unsigned)a.bs, 2), blk, 0, st, a);
   n += 2;
   HIPCHK(hipGetLastError());
-  c->vae.launches = n;
+  v.launches = v.fwd_launches + n;
   return CFD_OK;
+}
+
+extern "C" int cfd_vae_decode(cfd_handle c, const cfd_vae_decode_args* p, float* feats, uint64_t* ticket, void* stream) {
+  if (!c || !p || !p->wpack || !p->z || !p->lengths || (!feats && !ticket)) return fail(CFD_E_ARG, "bad argument (NULL pointer)");
+  CHK(vae_decode_check("cfd_vae_decode", p));
+  HIPCHK(hipSetDevice(c->cfg.device));
+  CHK(vae_decode_forward(c, "cfd_vae_decode", p, feats, ticket != nullptr, ticket != nullptr, (hipStream_t)stream));
+  if (ticket) *ticket = c->vae.ticket;
+  return CFD_OK;
+}
+
+extern "C" uint64_t cfd_vae_decode_ticket(cfd_handle c) { return c ? c->vae.ticket : 0; }
+
+extern "C" int cfd_vae_decode_sweep(cfd_handle c, uint64_t ticket, const float* d_feats, float* d_z, void* stream) {
+  if (!c || !d_feats || !d_z) return fail(CFD_E_ARG, "bad argument (NULL pointer)");
+  const auto& v = c->vae;
+  if (!ticket || ticket != v.ticket) {
+    if (v.ticket) return fail(CFD_E_STATE, "cfd_vae_decode_sweep: ticket %llu is stale: the handle keeps the forward of ticket %llu", (unsigned long long)ticket, (unsigned long long)v.ticket);
+    if (!v.dropped_by) return fail(CFD_E_STATE, "cfd_vae_decode_sweep: ticket %llu: no cfd_vae_decode has kept a forward on this handle", (unsigned long long)ticket);
+    return fail(CFD_E_STATE, "cfd_vae_decode_sweep: ticket %llu is stale: a later %s%s dropped the kept forward", (unsigned long long)ticket, v.dropped_by,
+                v.grew ? ", which also grew the VAE workspace," : "");
+  }
+  HIPCHK(hipSetDevice(c->cfg.device));
+  return vae_decode_sweep(c, nullptr, d_feats, d_z, (hipStream_t)stream);
+}
+
+extern "C" int cfd_vae_decode_vjp(cfd_handle c, const cfd_vae_decode_vjp_args* p, float* feats, float* d_z, void* stream) {
+  if (!c || !p || !p->wpack || !p->z || !p->lengths || !p->d_feats || !d_z) return fail(CFD_E_ARG, "bad argument (NULL pointer)");
+  const cfd_vae_decode_args f = {p->wpack, p->d_model, p->num_heads, p->ff_size, p->num_layers, p->bs, p->nframes, p->n_chunks, p->z, p->lengths};
+  CHK(vae_decode_check("cfd_vae_decode_vjp", &f));
+  HIPCHK(hipSetDevice(c->cfg.device));
+  CHK(vae_decode_forward(c, "cfd_vae_decode_vjp", &f, feats, true, false, (hipStream_t)stream));
+  c->vae.ticket = 0;   // this call's own forward: nobody holds its ticket, and its weights were not copied
+  return vae_decode_sweep(c, p->wpack, p->d_feats, d_z, (hipStream_t)stream);
 }
 
 // "vae.g.<l>": the running gradient at layer l's output, rows ((stack * bs + b) * fp + f), fp = nframes rounded up to 16; "vae.dz.<l>": layer
 // l's contribution to d_z as [2][bs][16][128]; "vae.x.<l>": the forward's stream at layer l's input (l = num_layers: the last layer's output)
 int vae_debug_buffer(Ctx* c, const char* what, float** p, size_t* n) {
   const auto& v = c->vae;
-  if (!v.g) return fail(CFD_E_STATE, "'%s': no cfd_vae_decode_vjp has run on this handle", what);
+  if (!v.g) return fail(CFD_E_STATE, "'%s': no cfd_vae_decode_vjp has run on this handle (or a forward-only cfd_vae_decode since)", what);
   int l = -1;
   if (sscanf(what, "vae.g.%d", &l) == 1 && l >= 0 && l < v.nl) { *p = v.g + (size_t)l * v.rows * VE_D; *n = (size_t)v.rows * VE_D; }
   else if (sscanf(what, "vae.dz.%d", &l) == 1 && l >= 0 && l < v.nl) { *p = v.dzl + (size_t)l * 2 * v.bs * 16 * VE_D; *n = (size_t)2 * v.bs * 16 * VE_D; }

@@ -24,6 +24,12 @@ extern "C" int cfd_debug_live_buffers(long long* count, long long* bytes) {
   return CFD_OK;
 }
 
+extern "C" int cfd_debug_vae_workspace(cfd_handle c, long long* bytes) {
+  if (!c || !bytes) return fail(CFD_E_ARG, "null argument");
+  *bytes = (long long)c->vae.ws.bytes;
+  return CFD_OK;
+}
+
 extern "C" int cfd_debug_weg_stop(cfd_handle c, int stop) {
   if (!c) return fail(CFD_E_ARG, "null handle");
   if (stop != 0) {

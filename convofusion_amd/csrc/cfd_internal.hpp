@@ -324,12 +324,17 @@ struct cfd_handle_s {
     return k;
   }
   WegState weg;                // cfd_weg_eval's state between two evaluations (cfd_weg.hip)
-  // cfd_vae_decode_vjp (cfd_blocks.hip, vae_dec.hpp): the call's own workspace and, for cfd_debug_read ("vae.*"), where the last call left its taps
+  // cfd_vae_decode / cfd_vae_decode_vjp / cfd_vae_decode_sweep (cfd_blocks.hip, vae_dec.hpp): the calls' own workspace; the shape of the
+  // forward it holds; for cfd_debug_read ("vae.*"), where the last saving forward and its sweep left their taps (g null: none, the last
+  // forward was forward-only); and the kept forward's ticket (0: none is kept; `dropped_by` then names the call that dropped the last one)
   struct VaeVjpState {
     DBuf ws;
     float *g = nullptr, *dzl = nullptr, *x0 = nullptr;
-    int bs = 0, fp = 0, nl = 0, launches = 0;
+    int bs = 0, fp = 0, nl = 0, launches = 0, fwd_launches = 0, nframes = 0, n_chunks = 0;
     long long rows = 0;
+    uint64_t ticket = 0, serial = 0;
+    const char* dropped_by = nullptr;
+    bool grew = false;            // ... and had to grow the workspace
   } vae;
   hipEvent_t weg_ev = nullptr;  // cross-stream hand-over of cfd_weg_eval, and of cfd_dyadic_steps
   // profiling

@@ -23,6 +23,12 @@
 // Frames at or beyond lengths[b] never act as keys and carry a zero cotangent; tiles that hold only such frames are skipped (they only write
 // the zeros of their rows of feats and of the gradient tap g).
 //
+// The forward kernels carry a compile-time SAVE flag.  SAVE = true is the forward above, every layer's buffers resident for the sweep
+// (cfd_vae_decode_vjp; cfd_vae_decode with a ticket, whose vd_mem launch also copies the lengths and -- for a sweep in a later call -- the
+// stacks' weights into the workspace).  SAVE = false is the forward on its own (cfd_vae_decode without a ticket): the same arithmetic in the
+// same order, storing only what a later forward launch reads -- the stream hand-off and the skip tensors (vd_xslot), q | k | v and o of
+// the current layer (vd_lslot), the memory's K | V -- so its output has the saving forward's bits on (nb + 6) / 2 KB per row instead of 27.
+//
 // Packed weights (float32): one block per stack (body, then hands; vd_stack_floats(num_layers) each), then query_pos_decoder.pe[0:256]
 // and mem_pos_decoder.pe[0:16].  A matrix W [N][K] (nn.Linear) is stored twice: in the MFMA-B order of vae_enc.hpp ("F": float4 index
 // ((n/16 * K/16 + k/16) * 64 + lane), lane = 16 * ((k % 16) / 4) + n % 16, element k % 4) and as its transpose W^T [K][N] in the same
@@ -117,7 +123,22 @@ struct VaeDecArgs {
   float* gskip;  // [nb][rows][128]      the skip tensors' gradient from the linear blocks
   float* pkv;    // [nl][2 * bs][nt][16][256]  per-tile partial dK | dV of the memory
   float* dzl;    // [nl][2][bs][16][128] layer l's contribution to d_z (tap "vae.dz.l")
+  // what a kept forward (SAVE) copies out of the caller's memory for a sweep that runs in a later call: vd_mem_kernel's extra blocks
+  float* keep_w;     // [2 * stack_floats]  the two stacks' blocks of the pack
+  int* keep_len;     // [bs]                the lengths
 };
+
+// Where layer l's buffers live.  SAVE: every layer keeps its own (the sweep reads them).  Forward-only: what a later forward launch still
+// reads and no more -- q | k | v and o of the current layer in slot 0; the stream in nb + 2 slots: the inputs of layers 1 .. nb, which
+// are the skip tensors of the output blocks, in slots 1 .. nb, every other layer's input alternating between slots 0 and nb + 1, so a
+// launch never writes the slot it reads.
+template <bool SAVE>
+__device__ __forceinline__ int vd_xslot(int l, int nb) {
+  if (SAVE || (l >= 1 && l <= nb)) return l;
+  return (l > nb && ((l - nb) & 1)) ? nb + 1 : 0;
+}
+template <bool SAVE>
+__device__ __forceinline__ int vd_lslot(int l) { return SAVE ? l : 0; }
 
 // A fragment of a [16][*] LDS tile: k-step kk reads columns 16 (kk - k0) ..
 struct VdTile {
@@ -251,11 +272,25 @@ __device__ __forceinline__ void vd_ln_bwd(float* gb, const float* x, const float
 }
 
 // ---- forward ------------------------------------------------------------------------------------------------------------------------------
-// K | V of the memory for layer blockIdx.x, sequence blockIdx.y, stack blockIdx.z
+// K | V of the memory for layer blockIdx.x, sequence blockIdx.y, stack blockIdx.z.  SAVE: block (0, b, 0) copies lengths[b] to keep_len, and
+// the blocks with blockIdx.x >= nl -- a launch that keeps the weights for a later call has some -- share the copy of the stacks' weights to
+// keep_w (float4 cb * 256 + tid of block cb, then every (blocks * 256)-th).
+template <bool SAVE>
 __global__ void __launch_bounds__(256) vd_mem_kernel(const VaeDecArgs a) {
   __shared__ float A[16 * VD_LD];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, l15 = lane & 15, q4 = lane >> 4;
   const int l = blockIdx.x, b = blockIdx.y, s = blockIdx.z;
+  if (SAVE) {
+    if (l >= a.nl) {
+      const long long n4 = a.stack_floats / 2, blocks = (long long)(gridDim.x - a.nl) * gridDim.y * 2;
+      const long long cb = ((long long)(l - a.nl) * gridDim.y + b) * 2 + s;
+      const f32x4* __restrict__ src = reinterpret_cast<const f32x4*>(a.w);
+      f32x4* __restrict__ dst = reinterpret_cast<f32x4*>(a.keep_w);
+      for (long long i = cb * 256 + tid; i < n4; i += blocks * 256) dst[i] = src[i];
+      return;
+    }
+    if (l == 0 && s == 0 && tid == 0) a.keep_len[b] = a.lengths[b];
+  }
   const float* L = a.w + s * a.stack_floats + (long long)l * DL_SIZE;
   for (int idx = tid; idx < 16 * VE_D; idx += 256) {
     const int j = idx >> 7, c = idx & 127;
@@ -352,7 +387,9 @@ __device__ __forceinline__ void vd_cross(float* q, const float* d_o, float* dq, 
   for (int j = 0; j < 8; ++j) dq[r * VD_LD + c0 + j] = 0.125f * g[j];
 }
 
-// Launch l of the forward's row-local part (see the head of the file).
+// Launch l of the forward's row-local part (see the head of the file).  SAVE = false: the same arithmetic in the same order on the
+// forward-only slots (vd_xslot, vd_lslot), without the stores only the sweep reads (x1, qc, x2, the last layer's output).
+template <bool SAVE>
 __global__ void __launch_bounds__(256) vd_fwd_rows_kernel(const VaeDecArgs a, int l) {
   __shared__ float X[16 * VD_LD], A[16 * VD_LD], Hb[16 * VD_LD], mean[16], rstd[16];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, l15 = lane & 15, q4 = lane >> 4;
@@ -378,8 +415,8 @@ __global__ void __launch_bounds__(256) vd_fwd_rows_kernel(const VaeDecArgs a, in
     const int lp = l - 1;
     const float* L = W + (long long)lp * DL_SIZE;
     const long long off = ((long long)lp * a.rows + row0) * VE_D;
-    vd_load_tile(X, a.x0 + off, tid);
-    vd_load_tile(A, a.o + off, tid);
+    vd_load_tile(X, a.x0 + ((long long)vd_xslot<SAVE>(lp, a.nb) * a.rows + row0) * VE_D, tid);
+    vd_load_tile(A, a.o + ((long long)vd_lslot<SAVE>(lp) * a.rows + row0) * VE_D, tid);
     __syncthreads();
     {   // self-attention out-projection and residual
       f32x4 acc[1][2];
@@ -388,7 +425,7 @@ __global__ void __launch_bounds__(256) vd_fwd_rows_kernel(const VaeDecArgs a, in
       vd_each(acc, w, lane, [&](int r, int c, float v) { X[r * VD_LD + c] += v + L[DL_SO_B + c]; });
     }
     __syncthreads();
-    vd_store_tile(a.x1 + off, X, tid);
+    if (SAVE) vd_store_tile(a.x1 + off, X, tid);
     ve_ln_stats(X, mean, rstd, 16, tid);
     __syncthreads();
     {   // cross-attention: scaled query, attention over the memory rows, out-projection and residual
@@ -399,7 +436,7 @@ __global__ void __launch_bounds__(256) vd_fwd_rows_kernel(const VaeDecArgs a, in
       vd_each(acc, w, lane, [&](int r, int c, float v) { A[r * VD_LD + c] = (v + L[DL_CA_B + c]) * 0.125f; });
     }
     __syncthreads();
-    vd_store_tile(a.qc + off, A, tid);
+    if (SAVE) vd_store_tile(a.qc + off, A, tid);
     __syncthreads();   // (vd_cross replaces the query in A with the attention output, under another thread-to-element map)
     vd_cross(A, nullptr, nullptr, nullptr, nullptr, a.mkv + ((long long)lp * 2 * a.bs + sb) * 16 * 256, a.n_chunks, tid);
     __syncthreads();
@@ -410,7 +447,7 @@ __global__ void __launch_bounds__(256) vd_fwd_rows_kernel(const VaeDecArgs a, in
       vd_each(acc, w, lane, [&](int r, int c, float v) { X[r * VD_LD + c] += v + L[DL_CO_B + c]; });
     }
     __syncthreads();
-    vd_store_tile(a.x2 + off, X, tid);
+    if (SAVE) vd_store_tile(a.x2 + off, X, tid);
     ve_ln_stats(X, mean, rstd, 16, tid);
     __syncthreads();
     {   // FFN in 128-column chunks of the hidden
@@ -444,13 +481,13 @@ __global__ void __launch_bounds__(256) vd_fwd_rows_kernel(const VaeDecArgs a, in
       __syncthreads();
     }
   }
-  vd_store_tile(a.x0 + ((long long)l * a.rows + row0) * VE_D, X, tid);
+  if (SAVE || l < a.nl) vd_store_tile(a.x0 + ((long long)vd_xslot<SAVE>(l, a.nb) * a.rows + row0) * VE_D, X, tid);
   ve_ln_stats(X, mean, rstd, 16, tid);
   __syncthreads();
   if (l < a.nl) {   // LN1 and q | k | v of layer l
     const float* L = W + (long long)l * DL_SIZE;
     const VdTileLn an{X, mean, rstd, L + DL_LN1G, L + DL_LN1B, l15, q4};
-    float* out = a.qkv + ((long long)l * a.rows + row0) * 3 * VE_D;
+    float* out = a.qkv + ((long long)vd_lslot<SAVE>(l) * a.rows + row0) * 3 * VE_D;
     for (int ch = 0; ch < 3; ++ch) {
       f32x4 acc[1][2];
       ve_zero(acc);
@@ -473,14 +510,15 @@ __global__ void __launch_bounds__(256) vd_fwd_rows_kernel(const VaeDecArgs a, in
 }
 
 // Self-attention core of layer l for the tile's 16 queries: thread = (head tid / 128, row (tid / 8) % 16, 8 of the head's 64 dimensions);
-// two passes over the valid keys (maximum and sum, then the value sum).
+// two passes over the valid keys (maximum and sum, then the value sum).  SAVE = false: slot 0 of qkv / o, no log-sum-exp stored.
+template <bool SAVE>
 __global__ void __launch_bounds__(256) vd_self_fwd_kernel(const VaeDecArgs a, int l) {
   const int tid = threadIdx.x, h = tid >> 7, r = (tid >> 3) & 15, p = tid & 7, c0 = 64 * h + 8 * p;
   const int t = blockIdx.x, b = blockIdx.y, s = blockIdx.z;
   const int len = min(a.lengths[b], a.nframes);
   if (16 * t >= len) return;
   const long long seq0 = ((long long)s * a.bs + b) * a.fp, row = seq0 + 16 * t + r;
-  const float* __restrict__ qkv = a.qkv + (long long)l * a.rows * 3 * VE_D;
+  const float* __restrict__ qkv = a.qkv + (long long)vd_lslot<SAVE>(l) * a.rows * 3 * VE_D;
   float qv[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) qv[j] = qkv[row * 3 * VE_D + c0 + j];
@@ -511,10 +549,10 @@ __global__ void __launch_bounds__(256) vd_self_fwd_kernel(const VaeDecArgs a, in
 #pragma unroll
     for (int j = 0; j < 8; ++j) o[j] += pk * kp[VE_D + j];
   }
-  float* out = a.o + ((long long)l * a.rows + row) * VE_D + c0;
+  float* out = a.o + ((long long)vd_lslot<SAVE>(l) * a.rows + row) * VE_D + c0;
 #pragma unroll
   for (int j = 0; j < 8; ++j) out[j] = o[j];
-  if (p == 0) a.lse[((long long)l * a.rows + row) * 2 + h] = lse;
+  if (SAVE && p == 0) a.lse[((long long)l * a.rows + row) * 2 + h] = lse;
 }
 
 // ---- reverse sweep ------------------------------------------------------------------------------------------------------------------------

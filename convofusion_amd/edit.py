@@ -79,7 +79,7 @@ def keyframe_loss(target, mask):
     return loss
 
 
-def pose_keyframe_loss(vae, target, frame_mask, feature_mask=None, lengths=None):
+def pose_keyframe_loss(vae, target, frame_mask, feature_mask=None, lengths=None, fused=False):
     """The loss of frame-accurate key poses for ``sampler.sample_with_loss_guidance``: a function x0 [B, L, 128] -> the mean-square error
     of ``vae.decode(loop_to_vae(x0), lengths)`` against ``target`` [B, F, 189] over the frames of ``frame_mask`` (bool / 0-1 [B, F]) and
     the features of ``feature_mask`` (bool / 0-1 [189]; None = all).  Where ``keyframe_loss`` compares latent tokens (16-frame chunks of
@@ -88,7 +88,8 @@ def pose_keyframe_loss(vae, target, frame_mask, feature_mask=None, lengths=None)
     sequence (default F for every sequence; max(lengths) must be F).  ``vae``: a ``convofusion_amd.vae.ConvoFusionVae`` (its ``decode``
     is differentiable with respect to the latents, backward ``decode_vjp``); decode runs on the stand-alone engine handle, not on the
     denoiser's, so an open sampling run is untouched.  Frames at or beyond a sequence's length decode to 0 and pull nothing.  Whether
-    guided motions look right under a trained checkpoint is not measured here: the weights of the tests are seeded."""
+    guided motions look right under a trained checkpoint is not measured here: the weights of the tests are seeded.  fused=True:
+    ``vae.decode(..., fused=True)`` -- the forward is kept and the backward is the sweep alone, at the fused forward's bits."""
     if target.dim() != 3:
         raise ValueError(f"pose_keyframe_loss: target must be [B, F, nfeats], got {tuple(target.shape)}")
     B, F, nf = (int(v) for v in target.shape)
@@ -108,11 +109,16 @@ def pose_keyframe_loss(vae, target, frame_mask, feature_mask=None, lengths=None)
     def loss(x0):
         if x0.dim() != 3 or x0.shape[0] != B:
             raise ValueError(f"pose_keyframe_loss: x0 must be [{B}, L, 128], got {tuple(x0.shape)}")
-        feats = vae.decode(loop_to_vae(x0), lens)
+        feats = _decode(vae, loop_to_vae(x0), lens, fused)
         w = (fm.to(x0.device).unsqueeze(-1) & cm.to(x0.device)).to(feats.dtype)
         d = (feats - target.to(device=x0.device, dtype=feats.dtype)) * w
         return (d * d).sum() / n
     return loss
+
+
+def _decode(vae, z, lengths, fused):
+    """``vae.decode(z, lengths)``, with ``fused=True`` handed on only where it is asked for (the default call is the one it always was)."""
+    return vae.decode(z, lengths, fused=True) if fused else vae.decode(z, lengths)
 
 
 def vae_to_loop(z):
@@ -131,14 +137,15 @@ def loop_to_vae(z):
 
 
 def edit_motion(model, feats, lengths, encoder_hidden_states, cond_masks=None, *, keep_mask=None, strength=1.0, seed=0,
-                sample_posterior=False, modality_weights=None, operands=None):
+                sample_posterior=False, modality_weights=None, operands=None, fused_decode=False):
     """Edit motions with the fused loop.  ``model``: a Convofusion-like object (reads vae / denoiser / scheduler / cfg / guidance_scale /
     clf_guidance_drops / do_classifier_free_guidance as ``sampler.diffusion_reverse`` does); ``model.vae`` encodes and decodes on the HIP
     path (``convofusion_amd.vae.ConvoFusionVae``, or a reference module after ``attach_hip_encode`` / ``attach_hip_decode``).
     feats [B, nframes, 189], lengths: the source motions; encoder_hidden_states / cond_masks: the guidance batch as for the loop.
     The source latents are the posterior mean (``sample_posterior=True``: encode's draw from the default generator), the loop's initial
     noise and step noise come from Philox with ``seed``; keep_mask [B, nframes / 8] (``token_mask``), strength, modality_weights, operands:
-    as in ``sampler.sample``.  Returns (features [B, nframes, 189], loop latents [B, nframes / 8, 128])."""
+    as in ``sampler.sample``; fused_decode: the final decode as ``decode(..., fused=True)``.
+    Returns (features [B, nframes, 189], loop latents [B, nframes / 8, 128])."""
     if not model.do_classifier_free_guidance:
         raise NameError("guidance_bs_mulitplier: the reference loop requires classifier-free guidance")
     latent, dist, _ = model.vae.encode(feats, lengths)
@@ -159,13 +166,13 @@ def edit_motion(model, feats, lengths, encoder_hidden_states, cond_masks=None, *
                  guidance_chunks=G, eta=eta, seed=seed, skip_zero_weight_chunks=True,
                  operands=check_operands(getattr(model, "_cfd_operands", None) if operands is None else operands),
                  modality_weights=modality_weights, source_latents=source, keep_mask=keep_mask, strength=strength)
-    out = model.vae.decode(loop_to_vae(lat), lengths)
+    out = _decode(model.vae, loop_to_vae(lat), lengths, fused_decode)
     return out, lat
 
 
 def reperform_motion(model, feats, lengths, source_conditioning, target_conditioning, *, source_masks=None, target_masks=None,
                      num_inference_steps=50, keep_mask=None, inversion_weights=None, modality_weights=None, operands=None,
-                     method="ddim", strength=1.0, seed=0, levels_per_batch=None):
+                     method="ddim", strength=1.0, seed=0, levels_per_batch=None, fused_decode=False):
     """Re-perform motions under new conditioning.  ``model`` / ``feats`` / ``lengths``: as in ``edit_motion``; source_conditioning /
     target_conditioning (+ their masks): the 7-chunk guidance batches of the recorded motion's conditioning and of the new one.
       1. HIP encode of the source to its posterior mean (loop layout);
@@ -174,7 +181,7 @@ def reperform_motion(model, feats, lengths, source_conditioning, target_conditio
       3. DDIM regeneration (a DDIMScheduler with the model scheduler's betas, set_alpha_to_one and steps_offset; eta 0, no clipping) from
          the inverted latents under the target conditioning at model.guidance_scale with ``modality_weights`` (None: the model's installed
          weights, else the reference's); the tokens of ``keep_mask`` [B, L] are anchored to the inversion's trajectory;
-      4. HIP decode.
+      4. HIP decode (fused_decode=True: ``decode(..., fused=True)``).
     Returns (features [B, nframes, 189], loop latents [B, L, 128], inverted latents [B, L, 128]).
     ``method="ddpm"``: the edit-friendly DDPM noise space instead, with the model's OWN scheduler (DDPM, clip_sample as configured) and
     its own step count (cfg.model.scheduler.num_inference_timesteps; num_inference_steps is not used): ``sampler.invert_ddpm`` under the
@@ -209,7 +216,7 @@ def reperform_motion(model, feats, lengths, source_conditioning, target_conditio
         lat = sample(model.denoiser, sch, target_conditioning, target_masks, B=B, L=L, num_inference_steps=n,
                      guidance_scale=model.guidance_scale, guidance_chunks=G, skip_zero_weight_chunks=True, operands=operands,
                      modality_weights=modality_weights, noise_space=space, keep_mask=keep_mask, strength=strength)
-        return model.vae.decode(loop_to_vae(lat), lengths), lat, space[0][-1]
+        return _decode(model.vae, loop_to_vae(lat), lengths, fused_decode), lat, space[0][-1]
     if float(strength) != 1.0:
         raise ValueError("strength belongs to method='ddpm' (the DDIM path regenerates from the fully inverted latents)")
     kw = dict(num_train_timesteps=sch.config.num_train_timesteps, trained_betas=sch.betas.tolist(), clip_sample=False,
@@ -225,5 +232,5 @@ def reperform_motion(model, feats, lengths, source_conditioning, target_conditio
     lat = sample(model.denoiser, DDIMScheduler(**kw), target_conditioning, target_masks, B=B, L=L, num_inference_steps=num_inference_steps,
                  guidance_scale=model.guidance_scale, guidance_chunks=G, eta=0.0, init_latents=inverted, skip_zero_weight_chunks=True,
                  operands=ops, modality_weights=modality_weights, anchor_trajectory=traj, keep_mask=keep_mask)
-    out = model.vae.decode(loop_to_vae(lat), lengths)
+    out = _decode(model.vae, loop_to_vae(lat), lengths, fused_decode)
     return out, lat, inverted

@@ -25,7 +25,7 @@ import inspect
 import torch
 
 from .distributed import shard_cfg_batch, shard_modality_weights
-from .edit import loop_to_vae
+from .edit import _decode, loop_to_vae
 from .sampler import CFG_CHUNKS, check_operands, sample
 
 WINDOW_FRAMES = 128     # unbounded_synthesis.py:272 (motion_len)
@@ -149,10 +149,11 @@ def stitch_frames(feats):
 
 
 def synthesize_motion(model, encoder_hidden_states, cond_masks=None, *, n_utterances, n_windows, seed=0, max_rows=None, carry=None,
-                      modality_weights=None, operands=None):
+                      modality_weights=None, operands=None, fused_decode=False):
     """Long-form motions from a Convofusion-like ``model`` (reads vae / denoiser / scheduler / cfg / guidance_scale / clf_guidance_drops /
     do_classifier_free_guidance as ``edit.edit_motion`` does; ``model.vae`` decodes on the HIP path): ``synthesize_latents``, one HIP
-    ``decode`` of all U * W windows, the reference's frame stitching (``stitch_frames``) in torch on the device.
+    ``decode`` of all U * W windows (fused_decode=True: ``decode(..., fused=True)``, one forward-only cfd_vae_decode on a workspace of 1.2 MB
+    per window), the reference's frame stitching (``stitch_frames``) in torch on the device.
     Returns (features [U, (W + 1) * 64, nfeats], windows [U, W, L, 128], token sequence [U, (W + 1) * L / 2, 128])."""
     if not model.do_classifier_free_guidance:
         raise NameError("guidance_bs_mulitplier: the reference loop requires classifier-free guidance")
@@ -169,5 +170,5 @@ def synthesize_motion(model, encoder_hidden_states, cond_masks=None, *, n_uttera
         num_inference_steps=model.cfg.model.scheduler.num_inference_timesteps, guidance_scale=model.guidance_scale,
         guidance_chunks=model.clf_guidance_drops + 1, eta=eta, seed=seed, max_rows=max_rows, carry=carry,
         operands=getattr(model, "_cfd_operands", None) if operands is None else operands, modality_weights=modality_weights)
-    feats = model.vae.decode(loop_to_vae(windows.reshape(U * W, L, 128)), [WINDOW_FRAMES] * (U * W))
+    feats = _decode(model.vae, loop_to_vae(windows.reshape(U * W, L, 128)), [WINDOW_FRAMES] * (U * W), fused_decode)
     return stitch_frames(feats.reshape(U, W, WINDOW_FRAMES, feats.shape[-1])), windows, tokens

@@ -24,6 +24,12 @@ d_feats)`` is one call of cfd_vae_decode_vjp (csrc/vae_dec.hpp): a forward of bo
 reverse sweep needs, and the sweep from the cotangent at the 189 features back to the latents -- what the reference gets from torch autograd
 over its ``decode``.  Exact float32, no atomics (two calls return the same bits), nframes <= 256, n_chunks <= 16.  It reads a packed copy of
 the decoder weights (every matrix in both orders, ``_decoder_pack``) kept by the same cache rule as the encoder's (``_cached_pack``).  No gradients to weights or lengths.
+
+``decode(z, lengths, fused=True)`` (opt-in; the default is the launch sequence above, bit for bit) runs the forward on those same kernels as a
+call of its own: without grad one forward-only cfd_vae_decode (12 launches at 5 layers, a workspace of 4 KB per frame row), the bits of
+``decode_vjp``'s forward (about 1e-5 from the default path's); with grad the forward is kept in the handle's workspace under a ticket and
+the backward is the reverse sweep alone (cfd_vae_decode_sweep) -- or ``decode_vjp`` on the saved z when another decode has used the
+workspace since: the same bits either way.
 """
 import ctypes as C
 
@@ -275,9 +281,22 @@ class ConvoFusionVae(nn.Module):
         latent = dist.rsample()
         return latent.reshape(-1, bs, n_chunks, self.latent_dim), dist, feats
 
-    def decode(self, z, lengths):
+    def decode(self, z, lengths, fused=False):
         """z [2, bs, n_chunks, latent_dim] (body | hands), lengths: frames per sequence -> feats [bs, nframes, 189].  Differentiable with
-        respect to z when grad is enabled and ``z.requires_grad`` (backward: ``decode_vjp``); the values are the same bits either way."""
+        respect to z when grad is enabled and ``z.requires_grad`` (backward: ``decode_vjp``); the values are the same bits either way.
+        fused=True: the forward of ``decode_vjp`` as one cfd_vae_decode call instead of the launch sequence (its bits, about 1e-5 from the
+        default's; padded frames exactly 0); under grad the forward is kept and the backward is the sweep alone (``_DecodeFused``).
+        NotImplementedError beyond the kernels' limits (``decode_vjp_refusal``), before any device work."""
+        if fused:
+            lens = _lengths_list(lengths)
+            why = self._decode_vjp_refusal(z, lens, None, forward=True)
+            if why:
+                raise NotImplementedError(f"decode(fused=True): {why}")
+            if z.device.type != "cuda":
+                raise RuntimeError("the HIP VAE decoder runs on an MI355X only (move the module and z to 'cuda'); no CPU fallback")
+            if torch.is_grad_enabled() and z.requires_grad:
+                return _DecodeFused.apply(z, self, lens)
+            return self._decode_fused(z, lens, keep=False)[0]
         if z.device.type != "cuda":
             raise RuntimeError("the HIP VAE decoder runs on an MI355X only (move the module and z to 'cuda'); no CPU fallback")
         if torch.is_grad_enabled() and z.requires_grad:
@@ -341,9 +360,9 @@ class ConvoFusionVae(nn.Module):
             return [_pack_w(t), _pack_w(t.t().contiguous())]
         return self._cached_pack("decoder", dev, self._decoder_sources(), parts_of, decoder_pack_floats(self.num_layers))
 
-    def _decode_vjp_refusal(self, z, lens, d_feats):
+    def _decode_vjp_refusal(self, z, lens, d_feats, forward=False):
         """ValueError for arguments ``decode_vjp`` cannot mean anything for; returns the NotImplementedError text for shapes beyond the
-        kernels' limits (``decode_vjp_refusal``) or None.  No library, no device."""
+        kernels' limits (``decode_vjp_refusal``; forward: worded for ``decode(fused=True)``) or None.  No library, no device."""
         nf = self.body_nfeats + self.hands_nfeats
         if z.dim() != 4 or z.shape[0] != 2 or z.shape[-1] != self.latent_dim:
             raise ValueError(f"z must be [2, bs, n_chunks, {self.latent_dim}], got {tuple(z.shape)}")
@@ -357,7 +376,44 @@ class ConvoFusionVae(nn.Module):
                 raise ValueError(f"d_feats must be [{bs}, nframes, {nf}], got {tuple(d_feats.shape)}")
             if max(lens) != d_feats.shape[1]:
                 raise ValueError(f"max(lengths) = {max(lens)} must equal d_feats.shape[1] = {d_feats.shape[1]}")
-        return decode_vjp_refusal(bs, max(lens), n_chunks, self.latent_dim, self.num_heads, self.ff_size, self.num_layers, self.latent_size)
+        return decode_vjp_refusal(bs, max(lens), n_chunks, self.latent_dim, self.num_heads, self.ff_size, self.num_layers, self.latent_size,
+                                  forward=forward)
+
+    def _decode_fused(self, z, lens, keep):
+        """(feats, ticket): one cfd_vae_decode on checked arguments.  keep False: forward-only, ticket 0.  keep True: the forward with saves;
+        the ticket names it on the device's engine handle until another decode call uses the VAE workspace.  Waits as ``decode_vjp`` does."""
+        dev = z.device
+        bs, n_chunks, nframes = int(z.shape[1]), int(z.shape[2]), max(lens)
+        zc = z.detach().to(torch.float32).contiguous()
+        pack = self._decoder_pack(dev)
+        lens_d = torch.tensor(lens, dtype=torch.int32, device=dev)
+        feats = torch.empty(bs, nframes, self.body_nfeats + self.hands_nfeats, device=dev)
+        args = _lib.VaeDecodeArgs(_ptr(pack), self.latent_dim, self.num_heads, self.ff_size, self.num_layers, bs, nframes, n_chunks,
+                                  _ptr(zc), _ptr(lens_d))
+        ticket = C.c_uint64(0)
+        with torch.cuda.device(dev):
+            # (decode_vjp's rule and reason: an open sampling run replays and reads on a stream of its own.  The forward-only call writes a
+            # fresh torch block -- feats -- and runs beside such a replay just the same, so it needs no less.)
+            torch.cuda.synchronize(dev)
+            _lib.check(_lib.load().cfd_vae_decode(_engine_handle(dev), C.byref(args), _ptr(feats), C.byref(ticket) if keep else None,
+                                                  _stream(zc)))
+            torch.cuda.current_stream(dev).synchronize()
+        return feats, ticket.value
+
+    def _decode_sweep(self, ticket, d_feats, like):
+        """d_z (shaped like ``like``, float32) of the reverse sweep over the forward ``ticket`` names (cfd_vae_decode_sweep), or None when
+        the handle no longer keeps that forward -- asked before anything is launched (cfd_vae_decode_ticket)."""
+        dev = like.device
+        lib, h = _lib.load(), _engine_handle(dev)
+        if not ticket or lib.cfd_vae_decode_ticket(h) != ticket:
+            return None
+        dc = d_feats.detach().to(device=dev, dtype=torch.float32).contiguous()
+        d_z = torch.empty(like.shape, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            torch.cuda.synchronize(dev)
+            _lib.check(lib.cfd_vae_decode_sweep(h, ticket, _ptr(dc), _ptr(d_z), _stream(dc)))
+            torch.cuda.current_stream(dev).synchronize()
+        return d_z
 
     def decode_vjp(self, z, lengths, d_feats, want_out=True):
         """(feats [bs, nframes, 189] or None, d_z [2, bs, n_chunks, 128]): ``decode(z, lengths)`` as one cfd_vae_decode_vjp call computes
@@ -410,21 +466,45 @@ class _DecodeVjp(torch.autograd.Function):
         return ctx.vae.decode_vjp(z, ctx.lens, d_feats, want_out=False)[1].to(z.dtype), None, None
 
 
+class _DecodeFused(torch.autograd.Function):
+    """``decode(z, lengths, fused=True)`` as a function of ``z``: the forward is kept in the engine handle's VAE workspace and the backward
+    is the reverse sweep over it.  The handle keeps one forward: when another decode call has used the workspace since, the backward is
+    ``decode_vjp`` on the saved input instead (the forward again, then the same sweep) -- the same bits, never an exception."""
+
+    @staticmethod
+    def forward(ctx, z, vae, lens):
+        feats, ctx.ticket = vae._decode_fused(z, lens, keep=True)
+        ctx.vae, ctx.lens = vae, lens
+        ctx.save_for_backward(z)
+        return feats
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_feats):
+        (z,) = ctx.saved_tensors
+        d_z = ctx.vae._decode_sweep(ctx.ticket, d_feats, z)
+        if d_z is None:
+            d_z = ctx.vae.decode_vjp(z, ctx.lens, d_feats, want_out=False)[1]
+        return d_z.to(z.dtype), None, None
+
+
 DEC_MAX_FRAMES, DEC_MAX_CHUNKS = 256, 16     # VD_MAX_FRAMES, VD_MAX_CHUNKS (csrc/vae_dec.hpp)
 
 
-def decode_vjp_refusal(bs, nframes, n_chunks, latent_dim=128, num_heads=2, ff_size=1024, num_layers=5, latent_size=1):
+def decode_vjp_refusal(bs, nframes, n_chunks, latent_dim=128, num_heads=2, ff_size=1024, num_layers=5, latent_size=1, forward=False):
     """Why ``ConvoFusionVae.decode`` cannot be differentiated at these shapes, or None when it can: the message names the limit that is
-    exceeded.  Pure: no library, no device."""
+    exceeded.  forward=True: the same limits worded for ``decode(fused=True)``, which runs on the same kernels ("fused forward" where the
+    text says "backward").  Pure: no library, no device."""
+    what, whose = ("fused forward", "decoder fused forward's") if forward else ("backward", "decoder backward's")
     if (latent_dim, num_heads, ff_size, latent_size) != (128, 2, 1024, 1) or num_layers > 9 or num_layers % 2 == 0:
-        return (f"the HIP VAE decoder's backward is specialised for latent_dim [1, 128], 2 heads, ff_size 1024 and odd num_layers <= 9; this "
+        return (f"the HIP VAE decoder's {what} is specialised for latent_dim [1, 128], 2 heads, ff_size 1024 and odd num_layers <= 9; this "
                 f"module has latent_dim [{latent_size}, {latent_dim}], {num_heads} heads, ff_size {ff_size}, {num_layers} layers")
     if nframes > DEC_MAX_FRAMES:
-        return f"nframes = {nframes} exceeds the decoder backward's {DEC_MAX_FRAMES} frames"
+        return f"nframes = {nframes} exceeds the {whose} {DEC_MAX_FRAMES} frames"
     if n_chunks > DEC_MAX_CHUNKS:
-        return f"n_chunks = {n_chunks} exceeds the decoder backward's {DEC_MAX_CHUNKS} latent chunks per sequence"
+        return f"n_chunks = {n_chunks} exceeds the {whose} {DEC_MAX_CHUNKS} latent chunks per sequence"
     if bs > 65535:
-        return f"bs = {bs} exceeds the decoder backward's 65535 sequences per call"
+        return f"bs = {bs} exceeds the {whose} 65535 sequences per call"
     return None
 
 
@@ -459,9 +539,13 @@ def _attach(vae, skip_attr, method):
     return m
 
 
-def attach_hip_decode(vae):
-    """``vae.decode`` of a reference instance (kept for encode / training) on the HIP path (``_attach``).  Returns the mirror."""
-    return _attach(vae, "body_decoder", "decode")
+def attach_hip_decode(vae, fused=False):
+    """``vae.decode`` of a reference instance (kept for encode / training) on the HIP path (``_attach``).  fused=True: the attached
+    ``decode(z, lengths)`` runs the mirror's ``decode(z, lengths, fused=True)`` unless its caller says otherwise.  Returns the mirror."""
+    m = _attach(vae, "body_decoder", "decode")
+    if fused:
+        vae.decode = lambda z, lengths, fused=True: m.decode(z, lengths, fused=fused)
+    return m
 
 
 def attach_hip_encode(vae):

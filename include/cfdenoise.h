@@ -600,6 +600,32 @@ typedef struct {
   const float* d_feats;      /* dev [bs][nframes][189]: cotangent at decode's output */
 } cfd_vae_decode_vjp_args;
 int cfd_vae_decode_vjp(cfd_handle h, const cfd_vae_decode_vjp_args* a, float* feats, float* d_z, void* stream);
+/* ConvoFusionVae.decode as a call of its own, on cfd_vae_decode_vjp's forward kernels (the same arithmetic in the same order: the same bits
+ * as that call's feats), and the reverse sweep as a second call over a forward that was kept.  cfd_vae_decode_vjp is the two in a row.
+ *   cfd_vae_decode, ticket == NULL   forward-only: 1 + (num_layers + 1) + num_layers launches (12 at 5 layers) that store only what a later
+ *       forward launch reads.  The workspace holds (num_layers - 1) / 2 + 6 rows of 128 floats per token row (both stacks, frames padded
+ *       to 16 per sequence: 2 * bs * fp rows; 4096 bytes each at 5 layers) plus num_layers * 16 KiB per (stack, sequence) for the memory's
+ *       K | V -- against 27 KB per token row for the saving forward.  feats must not be NULL.
+ *   cfd_vae_decode, ticket != NULL   the forward with saves, on cfd_vae_decode_vjp's workspace; one of its launches also copies the stacks'
+ *       packed weights and the lengths into the workspace, so that the sweep reads nothing of the caller's but d_feats.  *ticket names
+ *       this kept forward on this handle (never 0).  feats may be NULL.
+ *   cfd_vae_decode_sweep   d_z = d_feats^T . d(feats)/d(z) over the kept forward `ticket` names, bit for bit what cfd_vae_decode_vjp
+ *       returns for the same inputs; it may run more than once on a ticket.  CFD_E_STATE (the message names the reason) unless `ticket`
+ *       is the handle's current kept forward: a ticket goes stale with any later cfd_vae_decode (either mode) or cfd_vae_decode_vjp on
+ *       the handle, which includes every growth of the VAE workspace.
+ *   cfd_vae_decode_ticket  the current kept forward's ticket, or 0: lets a caller decide before it launches anything.
+ * All of them only enqueue on `stream` (a workspace that has to grow is reallocated first).  Arguments, limits and refusals are
+ * cfd_vae_decode_vjp's (CFD_E_ARG names the limit exceeded). */
+typedef struct {
+  const float* wpack;        /* as cfd_vae_decode_vjp_args */
+  int d_model, num_heads, ff_size, num_layers;
+  int bs, nframes, n_chunks;
+  const float* z;
+  const int32_t* lengths;
+} cfd_vae_decode_args;
+int cfd_vae_decode(cfd_handle h, const cfd_vae_decode_args* a, float* feats, uint64_t* ticket, void* stream);
+int cfd_vae_decode_sweep(cfd_handle h, uint64_t ticket, const float* d_feats, float* d_z, void* stream);
+uint64_t cfd_vae_decode_ticket(cfd_handle h);
 int cfd_sample_write(cfd_handle h, const float* latents);
 int cfd_sample_inpaint(cfd_handle h);
 

@@ -123,6 +123,9 @@ int cfd_debug_weg_fill(cfd_handle h, float value);
 /* Test hook (no handle): the device buffers the library holds in this process, over all handles and calls -- how many, and their bytes as asked
  * for.  Every buffer belongs to a handle or to one call: a reading is back at an earlier one once the handles created since are destroyed. */
 int cfd_debug_live_buffers(long long* count, long long* bytes);
+/* Test hook: the bytes of the handle's VAE decode workspace as allocated (it only ever grows): after a forward-only cfd_vae_decode on a
+ * fresh handle, the forward-only layout's bytes (include/cfdenoise.h states them per row); after a saving forward, the VJP layout's. */
+int cfd_debug_vae_workspace(cfd_handle h, long long* bytes);
 /* Test hook (no handle, no device): the per-iteration coefficient rows a sampling run of scheduler `kind` (cfd_sample_args.scheduler)
  * over the HOST timestep table timesteps[0..N) uploads -- out HOST float32 [N][8], per row: sigma_t, alpha_t, c0, cx, sigma, use_noise,
  * order, 1/r0 (csrc/rows.hpp StepCoef; kind 2: c0 = sigma_prev / sigma_t, cx = alpha_prev (exp(-h) - 1)).  alphas_cumprod HOST

@@ -28,7 +28,7 @@ SYMBOLS = [
     "cfd_sample_begin_tied", "cfd_ddpm_invert", "cfd_sample_begin_replay", "cfd_sample_parallel", "cfd_test_picard_stride",
     "cfd_test_picard_sweep", "cfd_debug_weg_stop", "cfd_debug_weg_fill", "cfd_scheduler_step_pred", "cfd_dpmsolver_step_pred",
     "cfd_debug_forward_operands", "cfd_denoise_vjp", "cfd_debug_live_buffers", "cfd_vae_decode_vjp", "cfd_denoise_vjp_mem",
-    "cfd_vae_decode", "cfd_vae_decode_sweep", "cfd_vae_decode_ticket", "cfd_debug_vae_workspace",
+    "cfd_vae_decode", "cfd_vae_decode_sweep", "cfd_vae_decode_ticket", "cfd_debug_vae_workspace", "cfd_denoise_guide", "cfd_guide_tie_csr",
 ]
 
 # cfd_sample_args.prediction_type / the _pred entry points, by the schedulers' config string
@@ -135,6 +135,13 @@ class WegArgs(C.Structure):
 class VjpArgs(C.Structure):
     """cfd_vjp_args: one denoiser forward whose vector-Jacobian product with respect to the sample is wanted (cfd_denoise_vjp)."""
     _fields_ = [("Be", C.c_int), ("L", C.c_int), ("timestep", C.c_int), ("sample", C.c_void_p), ("mem", Memory * NUM_MEM)]
+
+
+class GuideArgs(C.Structure):
+    """cfd_guide_args: one key-pose guided update of B latent rows under n evaluated guidance chunks (cfd_denoise_guide)."""
+    _fields_ = [("B", C.c_int), ("L", C.c_int), ("n", C.c_int), ("timestep", C.c_int), ("sqrt_acp", C.c_float), ("sqrt_1m_acp", C.c_float),
+                ("x", C.c_void_p), ("mem", Memory * NUM_MEM), ("w", C.c_void_p), ("target", C.c_void_p), ("mask", C.c_void_p),
+                ("inv_n", C.c_float), ("step", C.c_float), ("tie", C.c_void_p), ("tie_csr", C.c_void_p), ("reuse_memory_side", C.c_int)]
 
 
 class VaeDecodeVjpArgs(C.Structure):
@@ -300,6 +307,8 @@ def load():
     lib.cfd_weg_eval.argtypes = [C.c_void_p, C.POINTER(WegArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_void_p]
     lib.cfd_denoise_vjp.argtypes = [C.c_void_p, C.POINTER(VjpArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.cfd_denoise_vjp_mem.argtypes = [C.c_void_p, C.POINTER(VjpArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p]
+    lib.cfd_denoise_guide.argtypes = [C.c_void_p, C.POINTER(GuideArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.cfd_guide_tie_csr.argtypes = [C.c_void_p, C.c_longlong, C.c_void_p]
     lib.cfd_vae_decode_vjp.argtypes = [C.c_void_p, C.POINTER(VaeDecodeVjpArgs), C.c_void_p, C.c_void_p, C.c_void_p]
     lib.cfd_vae_decode.argtypes = [C.c_void_p, C.POINTER(VaeDecodeArgs), C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]
     lib.cfd_vae_decode_sweep.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -50,6 +50,7 @@ extern "C" int cfd_create(const cfd_config* cfg, cfd_handle* out) {
   // the developer knobs (Ctx, cfd_internal.hpp)
   c->rt_on = env_int("CFD_ROWTILE", 1) != 0;
   c->rt_max_rows = env_int("CFD_ROWTILE_MAX_ROWS", c->rt_max_rows);
+  c->guide_max_rows = env_int("CFD_GUIDE_MAX_ROWS", c->guide_max_rows);
   c->weg_rt_on = env_int("CFD_WEG_ROWTILE", 1) != 0;
   c->weg_graph_on = env_int("CFD_WEG_GRAPH", 1) != 0;
   c->fused_xattn = env_int("CFD_FUSED_XATTN", 1) != 0;

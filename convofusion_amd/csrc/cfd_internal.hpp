@@ -99,7 +99,7 @@ struct RtSave {
 
 // cfd_weg_eval on the row-tile kernels (weg_rt.hpp): the arena of saved activations and gradient buffers
 struct WegRtState {
-  std::vector<long long> sig;   // the caller (cfd_weg_eval / cfd_denoise_vjp), shapes and pointers the arena and the problem of wk[1] were prepared for
+  std::vector<long long> sig;   // the caller (cfd_weg_eval / cfd_denoise_vjp / cfd_denoise_guide), shapes and pointers the arena and the problem of wk[1] were prepared for
   RtSave sv;
   float *att = nullptr, *d_att = nullptr, *fws = nullptr, *dP = nullptr, *G[3] = {nullptr, nullptr, nullptr}, *dz = nullptr, *dy = nullptr,
         *dh = nullptr, *dO = nullptr, *dqkv = nullptr;
@@ -144,6 +144,7 @@ struct WegState {
   // first call that asks for a memory gradient (memw_wver: the weights' generation they were folded from) and freed with the handle;
   // the call's planes (dS', P', T, G, dn' per memory) and inverse row maps.
   DBuf memw_a, memw_v, memw_c, mem_ws, mem_inv;
+  DBuf guide_ws;                // cfd_denoise_guide (guide.hpp): the replicated input, the seeded cotangent, the per-chunk gradients, the direct term, the loss partials
   long long memw_wver = -1;
   std::vector<int32_t> mem_inv_host;
 };
@@ -300,6 +301,7 @@ struct cfd_handle_s {
   //                               chosen by shape: at most rt_max_rows token rows of at most RT_MAX_L tokens per batch row, one timestep
   //                               for all rows, no dynamic memories
   //   CFD_ROWTILE_MAX_ROWS=<n>    moves that threshold
+  //   CFD_GUIDE_MAX_ROWS=<n>      the token rows (Be * L) cfd_denoise_guide takes: its own limit, in place of rt_max_rows (PathAsk::max_rows)
   //   CFD_WEG_ROWTILE=0           cfd_weg_eval keeps the float32 launch sequence of weg_eval.hpp instead of the row-tile one (weg_rt.hpp)
   //   CFD_WEG_GRAPH=0             cfd_weg_eval always runs eagerly (WegState::graph)
   //   CFD_FUSED_XATTN=0           the three-launch cross-attention (score products -> softmax_rows_kernel -> P.V products) everywhere
@@ -314,6 +316,7 @@ struct cfd_handle_s {
   bool rt_on = true, weg_rt_on = true, weg_graph_on = true, fused_xattn = true, l0_dedup = true, share0 = true, permute = true;
   long long rt_max_rows = 700;    // measured crossover at the product shape (L = 16), seconds per 1000 steps, row-tile vs tile kernels (profiles/r05_rowtile_crossover.log:
                                   // the short cross-attention work lists of round 5 made the tile kernels faster): 5 utterances 1.04 / 1.22, 6: 1.18 / 1.24, 7: 1.34 / 1.23
+  long long guide_max_rows = 4096;   // cfd_denoise_guide: the arena of saved activations is ~0.19 MB per token row at nine layers
   int fused_xattn_min_wgs = 6, ln_fold = -1, xa_operands = -1;
   // what decide_forward_path (forward_path.hpp) reads of the handle
   PathKnobs path_knobs() const {

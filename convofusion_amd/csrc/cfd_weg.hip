@@ -1,13 +1,14 @@
 // libcfdenoise: word-excitation guidance -- the launch-by-launch float32 pieces (cfd_gemm_f32 ... cfd_weg_focus) and cfd_weg_eval: one evaluation of the word-excitation-guidance objective and its gradient, all launches enqueued from C++
 // (float32 launch sequence: weg_eval.hpp; small problems on the row-tile kernels: rowtile_bwd.hpp, weg_rt.hpp) -- and cfd_denoise_vjp, the
 // vector-Jacobian product of one forward with respect to its sample on the same row-tile kernels, with cfd_denoise_vjp_mem, which adds
-// the product with respect to the five memories.
+// the product with respect to the five memories -- and cfd_denoise_guide, the key-pose guided update on that forward and sweep (guide.hpp).
 #include "cfd_internal.hpp"
 #include "grad.hpp"
 
 #include "weg_eval.hpp"
 #include "rowtile_bwd.hpp"
 #include "weg_rt.hpp"
+#include "guide.hpp"
 
 extern "C" int cfd_gemm_f32(cfd_handle c, int M, int N, int K, int nb1, int nb2, const cfd_mat* A, const cfd_mat* B, const cfd_mat* Cm,
                             const float* bias, float alpha, int accumulate, void* stream) {
@@ -178,6 +179,29 @@ static int set_call_timestep(Ctx* c, int T, int timestep, hipStream_t st) {
 // timestep), 2 = the timestep may differ (the guided sampling loop: one evaluation per iteration, same conditioning).  The
 // row-tile path serves 2 from tables over ALL timesteps, built at the first such call (row t = timestep t, one launch per
 // evaluation copies the row); the float32 launch sequence treats 2 with a new timestep as 0.
+// The row-tile half of that decision, shared by cfd_weg_eval and cfd_denoise_guide: the table rows T for `mode` (reuse_memory_side),
+// wk[1]'s problem and the arena for caller `who` (wegrt::prepare; `more`, `hm`: its instance counts and row maps), the signature --
+// a caller other than cfd_weg_eval appends itself and `more`, so that no caller's signature equals another's -- and whether it is
+// the one the previous evaluation left (WegState::sig).
+static int rt_prepare_and_reuse(Ctx* c, int who, int B, int L, const cfd_memory* mem, int mode, int timestep, hipStream_t st,
+                                const std::vector<long long>& more, const HostMaps* hm, std::vector<long long>& sig, bool& reuse,
+                                const void*& arena) {
+  WegState& w = c->weg;
+  const bool had_full = w.rt.T > 1;
+  // tables over all timesteps stay while the caller keeps stating that the conditioning is unchanged
+  const int T = mode == 2 || (mode == 1 && had_full) ? c->tsin_rows : 1;
+  CHK(wegrt::prepare(c, who, B, L, mem, T, st, more, hm));
+  arena = w.rt_ws.p;
+  sig.insert(sig.end(), {(long long)(size_t)arena, -(long long)T});
+  if (T == 1) sig.push_back(timestep);
+  if (who != wegrt::FOR_WEG) {
+    sig.push_back(who);
+    sig.insert(sig.end(), more.begin(), more.end());
+  }
+  reuse = mode != 0 && sig == w.sig;
+  return set_call_timestep(c, T, timestep, st);
+}
+
 static int choose_path_and_reuse(WegEval& e) {
   Ctx* c = e.c;
   const cfd_weg_args* a = e.a;
@@ -185,17 +209,8 @@ static int choose_path_and_reuse(WegEval& e) {
   e.use_rt = wegrt::eligible(c, a);
   e.sig = {e.B, e.L};
   weg::append_memories(e.sig, a->mem);   // (wegrt::prepare rebuilds the problem when a mask pointer changes: no reuse then)
-  if (e.use_rt) {
-    const bool had_full = w.rt.T > 1;
-    // tables over all timesteps stay while the caller keeps stating that the conditioning is unchanged
-    const int T = a->reuse_memory_side == 2 || (a->reuse_memory_side == 1 && had_full) ? c->tsin_rows : 1;
-    CHK(wegrt::prepare(c, wegrt::FOR_WEG, a->B, a->L, a->mem, T, e.st));
-    e.arena = w.rt_ws.p;
-    e.sig.insert(e.sig.end(), {(long long)(size_t)e.arena, -(long long)T});
-    if (T == 1) e.sig.push_back(a->timestep);
-    e.reuse = a->reuse_memory_side != 0 && e.sig == w.sig;
-    return set_call_timestep(c, T, a->timestep, e.st);
-  }
+  if (e.use_rt)
+    return rt_prepare_and_reuse(c, wegrt::FOR_WEG, a->B, a->L, a->mem, a->reuse_memory_side, a->timestep, e.st, {}, nullptr, e.sig, e.reuse, e.arena);
   e.sig.push_back(a->timestep);
   e.x = weg::Ctx::sizing_pass(c, e.st, e.B, e.L, e.D);
   weg::run(e.x, e.args);
@@ -370,4 +385,79 @@ extern "C" int cfd_denoise_vjp_mem(cfd_handle c, const cfd_vjp_args* a, const fl
                                    void* stream) {
   if (!d_mem) return fail(CFD_E_ARG, "null argument");
   return denoise_vjp(c, a, d_out, out, grad, d_mem, stream);
+}
+
+// ---- cfd_denoise_guide: the key-pose guided update as one device call (guide.hpp) ------------------------------------------------
+extern "C" int cfd_guide_tie_csr(const int32_t* tie, long long n_tokens, int32_t* csr) {
+  if (!tie || !csr || n_tokens < 1 || n_tokens > (1LL << 30)) return fail(CFD_E_ARG, "cfd_guide_tie_csr: bad argument");
+  long long bad = -1;
+  switch (guide_build_tie_csr(tie, n_tokens, csr, &bad)) {
+    case GUIDE_CSR_OK: return CFD_OK;
+    case GUIDE_CSR_RANGE: return fail(CFD_E_ARG, "cfd_guide_tie_csr: tie[%lld] = %d is not -1 or a token in [0, %lld)", bad, tie[bad], n_tokens);
+    case GUIDE_CSR_SELF: return fail(CFD_E_ARG, "cfd_guide_tie_csr: tie[%lld] ties the token to itself", bad);
+    default: return fail(CFD_E_ARG, "cfd_guide_tie_csr: tie[%lld] = %d names a source that is itself tied (no chains)", bad, tie[bad]);
+  }
+}
+
+// Every refusal, before anything is touched; the row maps come back as the host sees them.
+static int check_guide_args(Ctx* c, const cfd_guide_args* a, bool wants, std::vector<long long>* maps, HostMaps* hm) {
+  if (!c || !a || !a->x) return fail(CFD_E_ARG, "null argument");
+  if (!wants) return fail(CFD_E_ARG, "cfd_denoise_guide: none of loss, grad, x_new and d_out is asked for");
+  if (a->n < 1) return fail(CFD_E_ARG, "cfd_denoise_guide: n = %d guidance chunks (at least 1)", a->n);
+  if (a->B < 1 || a->L < 1) return fail(CFD_E_ARG, "bad batch / length");
+  if (!a->target || !a->mask) return fail(CFD_E_ARG, "cfd_denoise_guide: %s is NULL", !a->target ? "target" : "mask");
+  if (!a->w) return fail(CFD_E_ARG, "cfd_denoise_guide: w (the chunk weights) is NULL");
+  if (!(a->inv_n > 0.f)) return fail(CFD_E_ARG, "cfd_denoise_guide: inv_n = %g is not positive (1 / (kept tokens * 128))", (double)a->inv_n);
+  if (!(a->sqrt_acp > 0.f)) return fail(CFD_E_ARG, "cfd_denoise_guide: sqrt_acp = %g is not positive", (double)a->sqrt_acp);
+  if (a->tie && !a->tie_csr) return fail(CFD_E_ARG, "cfd_denoise_guide: a tie without its tie_csr (cfd_guide_tie_csr)");
+  if (a->reuse_memory_side != 0 && a->reuse_memory_side != 2)
+    return fail(CFD_E_ARG, "cfd_denoise_guide: reuse_memory_side = %d is not 0 or 2", a->reuse_memory_side);
+  // the row limit first, in 64 bits: Be = n * B is formed only once it fits
+  if (const char* why = wegrt::ineligible(c, (long long)a->n * a->B, a->L, a->mem, true)) return fail(CFD_E_ARG, "cfd_denoise_guide: %s", why);
+  const int Be = a->n * a->B;
+  CHK(check_latent_call(c, Be, a->L, a->mem, CALL_TIMESTEP | CALL_ROW_MAPS, a->timestep));
+  if (c->weg.rt.stop) return fail(CFD_E_STATE, "cfd_debug_weg_stop is set: it names a launch of cfd_weg_eval's sweep");
+  HIPCHK(hipSetDevice(c->cfg.device));
+  CHK(fetch_row_maps(a->mem, Be, "n * B", *hm));
+  maps->push_back(a->n);
+  for (int j = 0; j < CFD_NMEM; ++j) {
+    const cfd_memory& m = a->mem[j];
+    maps->push_back(m.U);
+    maps->push_back((long long)(size_t)m.row_map);
+    if (m.row_map) maps->insert(maps->end(), hm->m[j].begin(), hm->m[j].end());
+  }
+  return CFD_OK;
+}
+
+extern "C" int cfd_denoise_guide(cfd_handle c, const cfd_guide_args* a, float* loss, float* grad, float* x_new, float* d_out, void* stream) {
+  std::vector<long long> maps;
+  HostMaps hm;
+  CHK(check_guide_args(c, a, loss || grad || x_new || d_out, &maps, &hm));
+  WegState& w = c->weg;
+  const int Be = a->n * a->B;
+  // like cfd_denoise_vjp: on the handle's own stream, in wk[1]; an open sampling run keeps wk[0] and its bits
+  hipStream_t st = c->own_stream;
+  CHK(begin_on_own_stream(c, (hipStream_t)stream));
+  // the call overwrites wk[1]'s problem and the arena: a captured cfd_weg_eval holds addresses that set-up may move
+  for (WegState::Graph& g : w.graph)
+    if (g.gx.exec) { HIPCHK(hipStreamSynchronize(st)); g.reset(); }
+  std::vector<long long> sig = {Be, a->L};
+  weg::append_memories(sig, a->mem);
+  bool reuse = false;
+  const void* arena = nullptr;
+  const int prepared = rt_prepare_and_reuse(c, wegrt::FOR_GUIDE, Be, a->L, a->mem, a->reuse_memory_side, a->timestep, st, maps, &hm, sig, reuse, arena);
+  w.sig.clear();                                  // (a call that fails leaves nothing to reuse)
+  CHK(prepared);
+  guide::Bufs b;
+  CHK(guide::ensure_bufs(c, st, (size_t)a->B * a->L, a->n, b));
+  const int r = guide::enqueue(c, st, a, b, !reuse, grad, x_new);
+  w.launches = w.rt.launches;
+  if (r == CFD_OK && loss) HIPCHK(hipMemcpyAsync(loss, b.loss, 4, hipMemcpyDeviceToDevice, st));
+  if (r == CFD_OK && d_out) HIPCHK(hipMemcpyAsync(d_out, b.d_out, (size_t)Be * a->L * CFD_LAT * 4, hipMemcpyDeviceToDevice, st));
+  // the call returns with its results complete: its census is read here, so a clamped sample or memory fails THIS call
+  HIPCHK(hipStreamSynchronize(st));
+  CHK(r);
+  CHK(check_saturation(c, "cfd_denoise_guide (x, memories / their projections)"));
+  w.sig = sig;
+  return CFD_OK;
 }

@@ -35,6 +35,8 @@ struct PathAsk {
   int dynamic_mask = 0;           // bit j: memory j is rewritten between the forwards of a run
   bool f16 = false;               // a non-zero operand policy: single-fp16 key / value tiles of the long memories where the fused kernel allows them
   int chunk_rows = 0;             // the batch is replicas (chunk-major) of these first rows, identical up to the first cross-attention; 0: arbitrary rows
+  long long max_rows = 0;         // the caller's own limit on the token rows of the row-tile path, in place of the knob's rt_max_rows (cfd_denoise_guide:
+                                  // guide_max_rows -- its backward runs on no other kernels, so the forward's crossover is not its limit); 0: the knob's
 };
 
 struct ForwardPath {
@@ -66,7 +68,8 @@ inline ForwardPath decide_forward_path(const PathKnobs& k, const PathShape& s, c
     if (sp >= k.f16_min_keys) long_mask |= 1 << j;
   }
   // Small problems with one timestep for all rows and no memory rewritten under them: the row-tile kernels
-  p.rt = k.rt_on && s.tmode == 0 && s.L <= k.rt_max_l && M <= k.rt_max_rows && sp_tot <= k.rt_max_keys && !a.dynamic_mask;
+  const long long row_limit = a.max_rows > 0 ? a.max_rows : k.rt_max_rows;
+  p.rt = k.rt_on && s.tmode == 0 && s.L <= k.rt_max_l && M <= row_limit && sp_tot <= k.rt_max_keys && !a.dynamic_mask;
   // The fused kernel's work list.  A handful of workgroups cannot hide their serial walk over the key tiles: below min_wgs workgroups of
   // xa_tiles query tiles the three-launch path stays (build_xattn_worklist has the measurements).
   const long long wgs = ((long long)s.Be * ((s.L + 15) / 16) + k.xa_tiles - 1) / k.xa_tiles;

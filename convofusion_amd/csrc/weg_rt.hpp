@@ -23,26 +23,29 @@ static int padded_keys(const cfd_memory* mem) {   // of all five memories togeth
 }
 
 // Why B rows of L tokens against these memories cannot run on the row-tile path -- the limit that is exceeded, in a buffer of the
-// calling thread's -- or null when they can.
-static const char* ineligible(Ctx* c, int B, int L, const cfd_memory* mem) {
+// calling thread's -- or null when they can.  guide: the caller is cfd_denoise_guide, whose row limit is guide_max_rows (the one
+// place where a call's row limit is named; decide_forward_path takes the same figure through PathAsk::max_rows).
+static const char* ineligible(Ctx* c, long long B, int L, const cfd_memory* mem, bool guide = false) {
   static thread_local char why[160];
   const int keys = padded_keys(mem);
+  const long long max_rows = guide ? c->guide_max_rows : c->rt_max_rows;
   if (!c->rt_on || !c->weg_rt_on) snprintf(why, sizeof(why), "the row-tile path is switched off on this handle (CFD_ROWTILE / CFD_WEG_ROWTILE)");
   else if (L > RT_MAX_L) snprintf(why, sizeof(why), "L = %d exceeds RT_MAX_L = %d tokens per batch row", L, RT_MAX_L);
-  else if ((long long)B * L > c->rt_max_rows) snprintf(why, sizeof(why), "Be * L = %lld token rows exceed rt_max_rows = %lld", (long long)B * L, c->rt_max_rows);
+  else if (B * L > max_rows) snprintf(why, sizeof(why), "Be * L = %lld token rows exceed %s = %lld", B * L, guide ? "guide_max_rows" : "rt_max_rows", max_rows);
   else if (keys > RT_MAX_KEYS) snprintf(why, sizeof(why), "%d padded keys of the five memories together exceed RT_MAX_KEYS = %d", keys, RT_MAX_KEYS);
   else return nullptr;
   return why;
 }
 static bool eligible(Ctx* c, const cfd_weg_args* a) { return !ineligible(c, a->B, a->L, a->mem); }
 
-// Who prepared wk[1] and the arena: the two callers share both, and what one of them left is never reused by the other.
-enum { FOR_WEG = 0, FOR_VJP = 1 };
+// Who prepared wk[1] and the arena: the three callers share both, and what one of them left is never reused by another.
+enum { FOR_WEG = 0, FOR_VJP = 1, FOR_GUIDE = 2 };
 
 // (Re)build the evaluation's problem and arena when the caller, shapes or pointers change.  Host work only (allocations, row maps):
 // never captured.  B rows of L tokens; `more`: what else of the caller's arguments the problem depends on (cfd_denoise_vjp: the
-// instance counts and row maps).  FOR_WEG keeps the text maps (att) for the objective; FOR_VJP keeps none, runs the whole network and
-// leaves d_att zero: the sweep's kernels add it to the text memory's dP as they are.  maps: the host copy of the row maps, or null.
+// instance counts and row maps).  FOR_WEG keeps the text maps (att) for the objective; FOR_VJP and FOR_GUIDE keep none, run the whole
+// network and leave d_att zero: the sweep's kernels add it to the text memory's dP as they are.  FOR_GUIDE asks the path decision for its
+// own row limit (guide_max_rows, PathAsk::max_rows).  maps: the host copy of the row maps, or null.
 static int prepare(Ctx* c, int who, int B, int L, const cfd_memory* mem_in, int T, hipStream_t st, const std::vector<long long>& more = {},
                    const HostMaps* maps = nullptr) {
   WegRtState& s = c->weg.rt;
@@ -69,8 +72,8 @@ static int prepare(Ctx* c, int who, int B, int L, const cfd_memory* mem_in, int 
   CHK(c->weg.rt_ws.ensure(layout(ArenaLayout(nullptr, 64)).bytes()));
   const ArenaLayout lay = layout(ArenaLayout(c->weg.rt_ws.as<float>(), 64));
   for (int l = 0; l < nl; ++l) HIPCHK(hipMemset(s.sv.vt[l], 0, lay.rounded(n_vt) * 4));   // keys beyond L stay zero
-  s.sv.whole = who == FOR_VJP;
-  if (who == FOR_VJP) HIPCHK(hipMemset(s.d_att, 0, lay.rounded(n_att) * 4));
+  s.sv.whole = who != FOR_WEG;
+  if (who != FOR_WEG) HIPCHK(hipMemset(s.d_att, 0, lay.rounded(n_att) * 4));
   {
     WorkGuard guard(c);
     cfd_memory mem[CFD_NMEM];
@@ -78,6 +81,7 @@ static int prepare(Ctx* c, int who, int B, int L, const cfd_memory* mem_in, int 
     for (int j = 0; j < CFD_NMEM; ++j) mem[j] = mem_in[j];
     PathAsk ask;
     ask.att_out = who == FOR_WEG;
+    ask.max_rows = who == FOR_GUIDE ? c->guide_max_rows : 0;
     CHK(setup_problem(c, B, L, mem, maps, att, ask, 0, T));
     if (T > 1) {   // full tables: row t belongs to timestep t
       std::vector<int32_t> iota(T);

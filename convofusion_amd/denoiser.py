@@ -121,6 +121,37 @@ def vjp_refusal(Be, L, S, max_rows=None):
     return None
 
 
+# The guide call (``Denoiser.guide``, cfd_denoise_guide) has a row limit of its own in place of VJP_MAX_ROWS: the handle's guide_max_rows,
+# which the developer knob CFD_GUIDE_MAX_ROWS moves.
+GUIDE_MAX_ROWS = 4096
+
+
+def guide_max_rows():
+    try:
+        return int(os.environ.get("CFD_GUIDE_MAX_ROWS", GUIDE_MAX_ROWS))
+    except ValueError:
+        return GUIDE_MAX_ROWS
+
+
+def guide_refusal(Be, L, S, max_rows=None):
+    """Why ``Denoiser.guide`` cannot run ``Be`` = chunks x latent rows forward rows of ``L`` tokens against memory lengths ``S`` (five
+    ints), or None when it can: ``vjp_refusal`` with the guide call's own row limit.  Pure: no library, no device."""
+    max_rows = guide_max_rows() if max_rows is None else int(max_rows)
+    if L <= VJP_MAX_L and Be * L > max_rows:
+        return f"Be * L = {Be * L} token rows exceed the guide call's {max_rows}"
+    return vjp_refusal(Be, L, S, max_rows=max_rows)
+
+
+def tie_csr(tie):
+    """The inverse of a tie table [B, L] (``run_kind.check_tie``) as ``Denoiser.guide`` takes it: int32 [2 B L + 1] on the table's
+    device, built on the host by cfd_guide_tie_csr (offsets, then every source's tied tokens in ascending order)."""
+    import numpy as np
+    host = np.ascontiguousarray(tie.detach().to("cpu", torch.int32).numpy().reshape(-1))
+    csr = np.empty(2 * host.size + 1, dtype=np.int32)
+    _lib.check(_lib.load().cfd_guide_tie_csr(host.ctypes.data, host.size, csr.ctypes.data))
+    return torch.from_numpy(csr).to(tie.device)
+
+
 def _require_row_tile(sample, mems, what):
     """The refusal of a gradient with respect to ``what`` ("its sample" ...) at shapes beyond the row-tile path."""
     why = vjp_refusal(sample.shape[0], sample.shape[1], [int(m.shape[1]) for m in mems])
@@ -412,6 +443,74 @@ class Denoiser(nn.Module):
             raise ValueError("encoder_hidden_states must be the 5-tuple (spk_emb, alsn, tlsn, apb, lsnemb)")
         return self._vjp_call(sample, timestep, encoder_hidden_states, mem_mask_dict, d_out, wrt, row_maps, side_engine, want_out, want_grad,
                               "its memories")
+
+    # ---- the key-pose guided update -------------------------------------------------------------------
+    def guide(self, x, timestep, encoder_hidden_states, mem_mask_dict, w, target, mask, *, sqrt_acp, sqrt_1m_acp, step, inv_n=None,
+              tie=None, csr=None, row_maps=None, side_engine=False, reuse_memory_side=0, want=("loss", "grad", "x_new"), x_new=None):
+        """One ``cfd_denoise_guide`` call: (loss, grad, x_new, d_out), None for what ``want`` does not name.  ``x`` [B, L, 128]; the
+        memories are those of the n evaluated guidance chunks, chunk-major (n * B rows, or distinct memories with ``row_maps`` as in
+        ``vjp``); ``w`` [B, n] the chunk weights (column 0 is not read); ``target`` [B, L, 128] and ``mask`` [B, L] the key poses;
+        ``sqrt_acp`` / ``sqrt_1m_acp`` from the scheduler's float64 table; ``inv_n`` 1 / (kept tokens * 128) (None: from ``mask``, one
+        host read); ``tie`` [B, L] int32 with ``csr`` = ``tie_csr(tie)`` (None: built here).  ``x_new``: a tensor to write the update
+        into (it may be ``x``).  ``reuse_memory_side`` 2: the conditioning is the previous guide call's, the timestep may differ."""
+        B, L, _ = x.shape
+        n = int(w.shape[1])
+        why = guide_refusal(n * B, L, [int(m.shape[1]) for m in encoder_hidden_states])
+        if why is not None:
+            raise NotImplementedError(f"Denoiser.guide runs on the row-tile path: {why}")
+        unknown = set(want) - {"loss", "grad", "x_new", "d_out"}
+        if unknown or not want:
+            raise ValueError(f"want names {sorted(unknown)}: it is a non-empty subset of loss, grad, x_new, d_out")
+        lib = _lib.load()
+        dev = x.device
+        h = self.engine(dev, mem_len=max(int(m.shape[1]) for m in encoder_hidden_states), side=bool(side_engine))
+        f32 = lambda t, shape, name: self._guide_operand(t, shape, name, dev)
+        xs = f32(x, (B, L, 128), "x")
+        ws, tg, mk = f32(w, (B, n), "w"), f32(target, (B, L, 128), "target"), f32(mask, (B, L), "mask")
+        if inv_n is None:
+            kept = int((mk != 0).sum().item())
+            if kept == 0:
+                raise ValueError("Denoiser.guide: mask keeps no token")
+            inv_n = 1.0 / (kept * 128)
+        a = _lib.GuideArgs()
+        mems, keep = self.pack_memories(encoder_hidden_states, mem_mask_dict, row_maps)
+        a.B, a.L, a.n, a.timestep, a.sqrt_acp, a.sqrt_1m_acp = B, L, n, int(timestep), float(sqrt_acp), float(sqrt_1m_acp)
+        a.x, a.mem, a.w, a.target, a.mask = xs.data_ptr(), mems, ws.data_ptr(), tg.data_ptr(), mk.data_ptr()
+        a.inv_n, a.step, a.reuse_memory_side = float(inv_n), float(step), int(reuse_memory_side)
+        if tie is not None:
+            tt = tie.detach().to(device=dev, dtype=torch.int32).contiguous()
+            if tuple(tt.shape) != (B, L):
+                raise ValueError(f"tie must be [B, L] = [{B}, {L}], not {list(tt.shape)}")
+            cs = (tie_csr(tt) if csr is None else csr).to(device=dev, dtype=torch.int32).contiguous()
+            if cs.numel() != 2 * B * L + 1:
+                raise ValueError(f"csr must have 2 B L + 1 = {2 * B * L + 1} entries (tie_csr), not {cs.numel()}")
+            keep += [tt, cs]
+            a.tie, a.tie_csr = tt.data_ptr(), cs.data_ptr()
+        loss = torch.empty((), dtype=torch.float32, device=dev) if "loss" in want else None
+        grad = torch.empty_like(xs) if "grad" in want else None
+        d_out = torch.empty((n * B, L, 128), dtype=torch.float32, device=dev) if "d_out" in want else None
+        given = x_new is not None and "x_new" in want
+        if "x_new" in want:
+            if x_new is None:
+                x_new = torch.empty_like(xs)
+            elif x_new.dtype != torch.float32 or not x_new.is_contiguous() or tuple(x_new.shape) != (B, L, 128) or x_new.device != dev:
+                raise ValueError(f"x_new must be a contiguous float32 tensor [{B}, {L}, 128] on {dev}")
+        else:
+            x_new = None
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        with torch.cuda.device(dev):
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _lib.check(lib.cfd_denoise_guide(h, C.byref(a), ptr(loss), ptr(grad), ptr(x_new), ptr(d_out), stream))
+        if given and not x_new.is_inference():      # (a ctypes write into the caller's tensor: see ``_lib.wrote``)
+            _lib.wrote(x_new)
+        del keep
+        return loss, grad, x_new, d_out
+
+    @staticmethod
+    def _guide_operand(t, shape, name, dev):
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(shape):
+            raise ValueError(f"Denoiser.guide: {name} must be a tensor {list(shape)}")
+        return t.detach().to(device=dev, dtype=torch.float32).contiguous()
 
     # ---- forward -------------------------------------------------------------------------------
     @staticmethod

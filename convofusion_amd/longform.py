@@ -26,7 +26,7 @@ import torch
 
 from .distributed import shard_cfg_batch, shard_modality_weights
 from .edit import _decode, loop_to_vae
-from .sampler import CFG_CHUNKS, check_operands, sample
+from .sampler import CFG_CHUNKS, check_operands, sample, sample_with_keyframes
 
 WINDOW_FRAMES = 128     # unbounded_synthesis.py:272 (motion_len)
 
@@ -84,7 +84,7 @@ def stitch_tokens(windows):
 
 def synthesize_latents(model_or_denoiser, scheduler, encoder_hidden_states, cond_masks=None, *, n_utterances, n_windows, L=16,
                        num_inference_steps=1000, guidance_scale=7.5, guidance_chunks=CFG_CHUNKS, eta=0.0, seed=0, max_rows=None,
-                       carry=None, skip_zero_weight_chunks=True, operands=None, modality_weights=None):
+                       carry=None, skip_zero_weight_chunks=True, operands=None, modality_weights=None, keyframes=None):
     """The latents of U = n_utterances motions of W = n_windows half-overlapping windows each.  ``model_or_denoiser``: the HIP ``Denoiser``
     or an object with a ``.denoiser``.  encoder_hidden_states / cond_masks: the guidance batch of ``sample`` for B = U * W rows in the
     order u * W + w (chunk-major, G * B rows per memory), every row conditioned on its own window of the audio and text as the caller
@@ -94,6 +94,10 @@ def synthesize_latents(model_or_denoiser, scheduler, encoder_hidden_states, cond
     half from the finished window before it -- the grouping changes the result.  carry [U, L / 2, 128] (optional): the finished second half
     of the window before window 0 of every utterance (streaming: the previous call's ``windows[:, -1, L // 2:]``); window 0 then keeps
     its first half from it in the same way.
+    keyframes (optional): (target [U * W, L, 128], mask [U * W, L], step_size, guided_iterations) in window rows -- soft key poses
+    (``sampler.sample_with_keyframes``): every run whose rows hold a key token goes through the key-pose guided loop with the run's tie
+    and kept tokens; a key token may fall on a tied token and then pulls its source.  step_size / guided_iterations as in that loop
+    (a per-iteration step size or a callable serves every run alike).  None: exactly today's calls.
     Returns (windows [U, W, L, 128], sequence [U, (W + 1) * L / 2, 128] = ``stitch_tokens(windows)``)."""
     denoiser = getattr(model_or_denoiser, "denoiser", model_or_denoiser)
     U, W, L = int(n_utterances), int(n_windows), int(L)
@@ -105,6 +109,15 @@ def synthesize_latents(model_or_denoiser, scheduler, encoder_hidden_states, cond
         raise ValueError(f"carry must be [U, L / 2, 128] = [{U}, {L // 2}, 128], not {list(carry.shape)}")
     operands = check_operands(operands)
     dev = encoder_hidden_states[0].device
+    if keyframes is not None:
+        try:
+            kf_target, kf_mask, kf_step, kf_iterations = keyframes
+        except (TypeError, ValueError):
+            raise ValueError("keyframes must be (target [U * W, L, 128], mask [U * W, L], step_size, guided_iterations)") from None
+        if not isinstance(kf_target, torch.Tensor) or tuple(kf_target.shape) != (B, L, 128):
+            raise ValueError(f"keyframes: target must be [U * W, L, 128] = [{B}, {L}, 128]")
+        if not isinstance(kf_mask, torch.Tensor) or tuple(kf_mask.shape) != (B, L):
+            raise ValueError(f"keyframes: mask must be [U * W, L] = [{B}, {L}]")
     out = torch.empty((B, L, 128), dtype=torch.float32, device=dev)
     for start, stop in window_groups(U, W, max_rows):
         n = stop - start
@@ -122,11 +135,15 @@ def synthesize_latents(model_or_denoiser, scheduler, encoder_hidden_states, cond
             keep[b, :L // 2] = True
         enc = [shard_cfg_batch(m, start, stop, B, G) for m in encoder_hidden_states]
         masks = {k: shard_cfg_batch(v, start, stop, B, G) for k, v in (cond_masks or {}).items()}
-        out[start:stop] = sample(denoiser, scheduler, enc, masks, B=n, L=L, num_inference_steps=num_inference_steps,
-                                 guidance_scale=guidance_scale, guidance_chunks=G, eta=eta, seed=seed, first_utterance=start,
-                                 skip_zero_weight_chunks=skip_zero_weight_chunks, operands=operands,
-                                 modality_weights=shard_modality_weights(modality_weights, start, stop, B), source_latents=src,
-                                 keep_mask=keep, tie=tie.to(dev) if bool((tie >= 0).any()) else None)
+        run_kw = dict(B=n, L=L, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale, guidance_chunks=G, eta=eta, seed=seed,
+                      first_utterance=start, skip_zero_weight_chunks=skip_zero_weight_chunks, operands=operands,
+                      modality_weights=shard_modality_weights(modality_weights, start, stop, B), source_latents=src, keep_mask=keep,
+                      tie=tie.to(dev) if bool((tie >= 0).any()) else None)
+        if keyframes is not None and bool((kf_mask[start:stop] != 0).any()):
+            out[start:stop] = sample_with_keyframes(denoiser, scheduler, enc, masks, kf_target[start:stop], kf_mask[start:stop], kf_step,
+                                                    guided_iterations=kf_iterations, **run_kw)
+        else:
+            out[start:stop] = sample(denoiser, scheduler, enc, masks, **run_kw)
     windows = out.reshape(U, W, L, 128)
     return windows, stitch_tokens(windows)
 
@@ -149,11 +166,12 @@ def stitch_frames(feats):
 
 
 def synthesize_motion(model, encoder_hidden_states, cond_masks=None, *, n_utterances, n_windows, seed=0, max_rows=None, carry=None,
-                      modality_weights=None, operands=None, fused_decode=False):
+                      modality_weights=None, operands=None, fused_decode=False, keyframes=None):
     """Long-form motions from a Convofusion-like ``model`` (reads vae / denoiser / scheduler / cfg / guidance_scale / clf_guidance_drops /
     do_classifier_free_guidance as ``edit.edit_motion`` does; ``model.vae`` decodes on the HIP path): ``synthesize_latents``, one HIP
     ``decode`` of all U * W windows (fused_decode=True: ``decode(..., fused=True)``, one forward-only cfd_vae_decode on a workspace of 1.2 MB
-    per window), the reference's frame stitching (``stitch_frames``) in torch on the device.
+    per window), the reference's frame stitching (``stitch_frames``) in torch on the device.  keyframes: soft key poses in latent
+    tokens, as in ``synthesize_latents``.
     Returns (features [U, (W + 1) * 64, nfeats], windows [U, W, L, 128], token sequence [U, (W + 1) * L / 2, 128])."""
     if not model.do_classifier_free_guidance:
         raise NameError("guidance_bs_mulitplier: the reference loop requires classifier-free guidance")
@@ -169,6 +187,7 @@ def synthesize_motion(model, encoder_hidden_states, cond_masks=None, *, n_uttera
         model.denoiser, sch, encoder_hidden_states, cond_masks, n_utterances=U, n_windows=W, L=L,
         num_inference_steps=model.cfg.model.scheduler.num_inference_timesteps, guidance_scale=model.guidance_scale,
         guidance_chunks=model.clf_guidance_drops + 1, eta=eta, seed=seed, max_rows=max_rows, carry=carry,
-        operands=getattr(model, "_cfd_operands", None) if operands is None else operands, modality_weights=modality_weights)
+        operands=getattr(model, "_cfd_operands", None) if operands is None else operands, modality_weights=modality_weights,
+        **({} if keyframes is None else dict(keyframes=keyframes)))
     feats = _decode(model.vae, loop_to_vae(windows.reshape(U * W, L, 128)), [WINDOW_FRAMES] * (U * W), fused_decode)
     return stitch_frames(feats.reshape(U, W, WINDOW_FRAMES, feats.shape[-1])), windows, tokens

@@ -174,28 +174,42 @@ def refuse_sample_prediction(scheduler, what):
                                   "trajectory to be checked against")
 
 
-def check_loss_guidance(scheduler, *, noise_space=None, anchor_trajectory=None, tie=None, trajectory=False):
-    """The runs ``sampler.sample_with_loss_guidance`` takes: DDPMScheduler / DDIMScheduler with epsilon prediction, plain, weighted, edit
-    and preseq runs.  NotImplementedError, before any device work, for DPM-Solver++ (its multistep history would carry the moved latents
-    of one iteration into the next with nothing to check it against), prediction_type="sample", a DDIM inversion, the replay of a noise
-    space, an anchored and a tied run (their latents are overwritten from recorded levels or from each other every iteration)."""
-    what = "sample_with_loss_guidance: the loss-guided loop (loss_fn) runs"
+def _check_guided_loop(scheduler, name, loop, noise_space, anchor_trajectory, trajectory):
+    """The refusals the two guided loops share (``check_loss_guidance``, ``check_keyframe_guidance``): every one but the tied run's.
+    ``name``: the loop's function; ``loop``: the phrase that names it in a sentence."""
+    what = f"{name}: {loop} runs"
     kind = getattr(scheduler, "KIND", None)
     if kind == 3 or trajectory:
-        raise NotImplementedError("sample_with_loss_guidance: a DDIM inversion (DDIMInverseScheduler) takes no loss guidance -- its latents "
+        raise NotImplementedError(f"{name}: a DDIM inversion (DDIMInverseScheduler) takes no loss guidance -- its latents "
                                   "are its own; use invert() or sample()")
     if kind == 2:
         raise NotImplementedError(f"{what} with DDPMScheduler / DDIMScheduler; with DPMSolverMultistepScheduler it has no reference "
                                   "trajectory to be checked against -- use sample()")
     refuse_sample_prediction(scheduler, what)
     if noise_space is not None:
-        raise NotImplementedError("sample_with_loss_guidance: the replay of a noise space (noise_space) takes no loss guidance")
+        raise NotImplementedError(f"{name}: the replay of a noise space (noise_space) takes no loss guidance")
     if anchor_trajectory is not None:
-        raise NotImplementedError("sample_with_loss_guidance: an anchored run (anchor_trajectory) takes no loss guidance: its kept tokens "
+        raise NotImplementedError(f"{name}: an anchored run (anchor_trajectory) takes no loss guidance: its kept tokens "
                                   "come from the trajectory")
+
+
+def check_loss_guidance(scheduler, *, noise_space=None, anchor_trajectory=None, tie=None, trajectory=False):
+    """The runs ``sampler.sample_with_loss_guidance`` takes: DDPMScheduler / DDIMScheduler with epsilon prediction, plain, weighted, edit
+    and preseq runs.  NotImplementedError, before any device work, for DPM-Solver++ (its multistep history would carry the moved latents
+    of one iteration into the next with nothing to check it against), prediction_type="sample", a DDIM inversion, the replay of a noise
+    space, an anchored and a tied run (their latents are overwritten from recorded levels or from each other every iteration)."""
+    _check_guided_loop(scheduler, "sample_with_loss_guidance", "the loss-guided loop (loss_fn)", noise_space, anchor_trajectory, trajectory)
     if tie is not None:
         raise NotImplementedError("sample_with_loss_guidance: a tied run (tie) takes no loss guidance (write): its tied tokens are "
-                                  "overwritten from their sources every iteration")
+                                  "overwritten from their sources every iteration -- key poses on a tied run: sample_with_keyframes, "
+                                  "which folds their gradients onto the sources")
+
+
+def check_keyframe_guidance(scheduler, *, noise_space=None, anchor_trajectory=None, tie=None, trajectory=False):
+    """The runs ``sampler.sample_with_keyframes`` takes: those of ``check_loss_guidance`` and the tied run (``tie`` is accepted and not
+    looked at: ``check_tie`` has the table's own refusals) -- the device call folds a tied token's gradient onto its source and leaves
+    the latents satisfying the tie.  The refusals, NotImplementedError before any device work, are ``check_loss_guidance``'s others."""
+    _check_guided_loop(scheduler, "sample_with_keyframes", "the key-pose guided loop", noise_space, anchor_trajectory, trajectory)
 
 
 _AUTO_RUN = object()   # the first attempt of an "auto" loop (``_with_auto_operands``): a guarded run, not another "auto" loop

@@ -16,8 +16,8 @@ import torch
 from . import _lib
 from .denoiser import Denoiser
 # the pure half of opening a run: the argument checks of every kind and the kind of a run (importable from here as before)
-from .run_kind import (_AUTO_RUN, RunKind, check_anchor, check_edit, check_inversion, check_loss_guidance,  # noqa: F401
-                       check_noise_space, check_operands, check_tie, edit_first_iteration, refuse_sample_prediction, resolve_run_kind,
+from .run_kind import (_AUTO_RUN, RunKind, check_anchor, check_edit, check_inversion, check_keyframe_guidance,  # noqa: F401
+                       check_loss_guidance, check_noise_space, check_operands, check_tie, edit_first_iteration, refuse_sample_prediction, resolve_run_kind,
                        sample_prediction)
 
 # which guidance chunk carries which conditional memory (reference convofusion.py:909-929, 527-541)
@@ -553,9 +553,11 @@ class SamplingRun:
             self.open = False
         return out
 
-    def write(self, latents):
-        """Overwrite the current latents of the open run (the WEG update between two iterations)."""
-        if self.tie is not None:
+    def write(self, latents, satisfies_tie=False):
+        """Overwrite the current latents of the open run (the WEG update between two iterations).  satisfies_tie: the caller states
+        that every tied token of ``latents`` already holds its source's value (``Denoiser.guide``'s x_new does), which is the only
+        way a tied run takes an update: the run's own overwrite then changes nothing."""
+        if self.tie is not None and not satisfies_tie:
             raise ValueError("a tied run takes no WEG update (write): its tied tokens are overwritten from their sources every iteration")
         if self.replay:
             raise ValueError("a replay of a noise space takes no WEG update (write): its noise was solved for the recorded levels")
@@ -674,14 +676,16 @@ def _open_run(denoiser, scheduler, encoder_hidden_states, cond_masks, B, L, num_
 DONE = object()     # an ``update``'s answer (``_drive``): not this iteration and none after it
 
 
-def _drive(run, denoiser, encoder_hidden_states, cond_masks, G, row_maps, return_attention, update=None):
+def _drive(run, denoiser, encoder_hidden_states, cond_masks, G, row_maps, return_attention, update=None, write=None):
     """Every iteration of the open ``run``, the final read and the close (also on an exception): what ``sample`` and the guided loops
     share.  Returns the latents, with ``return_attention`` (latents, maps) as ``sample`` describes them.
     ``update(i, t, latents) -> new latents | None | DONE`` is what a guided loop does before iteration i of the scheduler's full table
     (timestep t): ``latents()`` pulls the iteration's in-painting overwrite in front (``run.inpaint``; rollout / edit: the re-noised
     tokens go in before the update, unbounded_synthesis.py:70-76) and reads the current latents, and what ``update`` returns is written
     back; None leaves the iteration as it is (nothing read), DONE this one and every later one.  An iteration that is changed, or whose
-    maps are taken, is replayed at once; the un-changed ones before it go out as one ``steps`` call."""
+    maps are taken, is replayed at once; the un-changed ones before it go out as one ``steps`` call.  ``write``: what writes an update
+    back (default ``run.write``)."""
+    write = run.write if write is None else write
     try:
         ring = run.att_ring is not None and return_attention in ("all", "auto")   # the captured iteration keeps every iteration's maps
         every = return_attention == "all" and not ring     # the reference's dict (convofusion.py:517-523): one extra forward + sync per step
@@ -709,7 +713,7 @@ def _drive(run, denoiser, encoder_hidden_states, cond_masks, G, row_maps, return
                 continue
             idle = replay(idle)
             if new is not None:
-                run.write(new)
+                write(new)
             if maps:
                 atts[int(t)] = last_step_attention(run, denoiser, t, encoder_hidden_states, cond_masks, G, row_maps)
             run.steps(1)
@@ -1129,6 +1133,78 @@ def sample_with_loss_guidance(denoiser, scheduler, encoder_hidden_states, cond_m
         return _drive(run, denoiser, encoder_hidden_states, cond_masks, G, kw.get("row_maps"), False, update)
     finally:
         denoiser.return_attention = keep_att
+
+
+def sample_with_keyframes(denoiser, scheduler, encoder_hidden_states, cond_masks, target, mask, step_size, *, B, L=16,
+                          num_inference_steps=1000, guidance_scale=7.5, guidance_chunks=CFG_CHUNKS, guided_iterations=None, tie=None, **kw):
+    """The loop with key-pose guidance on the device: ``sample_with_loss_guidance`` with ``edit.keyframe_loss(target, mask)`` -- before
+    iteration i of ``guided_iterations`` the latents move by -step_size_i * d loss / d latents, loss = the mean-square error of the
+    predicted clean latents against ``target`` [B, L, 128] over the tokens of ``mask`` [B, L] -- with the update as ONE
+    ``Denoiser.guide`` call (cfd_denoise_guide) per guided iteration on the denoiser's second engine: the run's own guidance combine,
+    the loss, the reverse sweep, the sum over the evaluated chunks and the update, with no torch autograd (the loop runs under
+    ``torch.inference_mode()``) and with the memory side kept from one guided iteration to the next.  Unlike the torch loop it takes
+    a tied run (``tie``, ``longform``): a key token on a tied token pulls its source, and the written latents satisfy the tie.  The
+    evaluated chunks times B rows must fit the guide call (``denoiser.guide_refusal``: 4096 token rows, not the differentiable
+    forward's 700).  With step_size 0 the result is ``sample``'s, bit for bit.  Every refusal: ``check_keyframe_guidance``.  Other
+    keywords: as in ``sample`` (no ``operands="auto"``)."""
+    from .denoiser import guide_refusal, tie_csr
+    check_keyframe_guidance(scheduler, noise_space=kw.get("noise_space"), anchor_trajectory=kw.get("anchor_trajectory"), tie=tie)
+    if check_operands(kw.get("operands")) == "auto":
+        raise NotImplementedError("sample_with_keyframes: operands='auto' restarts a run whose census trips; give an operand policy")
+    if not isinstance(target, torch.Tensor) or tuple(target.shape) != (B, L, 128):
+        raise ValueError(f"target must be a tensor [B, L, 128] = [{B}, {L}, 128]")
+    if not isinstance(mask, torch.Tensor) or tuple(mask.shape) != (B, L):
+        raise ValueError(f"mask must be a tensor [B, L] = [{B}, {L}]")
+    kept = int((mask != 0).sum().item())
+    if kept == 0:
+        raise ValueError("sample_with_keyframes: mask keeps no token")
+    G = guidance_chunks
+    n_full = len(scheduler.timestep_table(num_inference_steps)[1])
+    mw = kw.get("modality_weights")
+    wtab = modality_weight_table(mw, guidance_scale, n_full, B, G) if mw is not None else None      # [n_full, B, 8]
+    chunks = guided_chunks(wtab if wtab is not None else default_guidance_weights(G, guidance_scale))
+    why = guide_refusal(len(chunks) * B, L, [int(m.shape[1]) for m in encoder_hidden_states])
+    if why is not None:
+        raise NotImplementedError(f"sample_with_keyframes: the guided update of the {len(chunks)} evaluated guidance chunks: {why}")
+    guided = None if guided_iterations is None else {int(i) for i in guided_iterations}
+    scheduler.set_timesteps(num_inference_steps)
+    dev = encoder_hidden_states[0].device
+    acp = scheduler.alphas_cumprod.detach().to("cpu", torch.float64)
+    with torch.inference_mode():
+        states, masks = guidance_chunk_rows(encoder_hidden_states, cond_masks, chunks, G, B, kw.get("row_maps"))
+        states = [s.detach().contiguous() for s in states]
+        w_default = torch.tensor(default_guidance_weights(G, guidance_scale), dtype=torch.float32, device=dev)[chunks].expand(B, len(chunks)).contiguous()
+        tgt = target.detach().to(device=dev, dtype=torch.float32).contiguous()
+        msk = (mask != 0).to(device=dev, dtype=torch.float32).contiguous()
+        tie_dev = None if tie is None else tie.detach().to(device=dev, dtype=torch.int32).contiguous()
+        csr = None if tie_dev is None else tie_csr(tie_dev)
+        calls = 0
+
+        def update(i, t, latents):
+            nonlocal calls
+            if guided is not None and i not in guided:
+                return None
+            x = latents()
+            w = torch.from_numpy(wtab[i][:, chunks]).to(dev).contiguous() if wtab is not None else w_default      # [B, n]
+            a_t = float(acp[int(t)])
+            # (the side engine runs on its own stream behind torch's current one and returns complete; ``write`` then waits for
+            #  the current stream, so the update and the captured iteration never execute side by side)
+            x_new = denoiser.guide(x, int(t), states, masks, w, tgt, msk, sqrt_acp=a_t ** 0.5, sqrt_1m_acp=(1.0 - a_t) ** 0.5,
+                                   step=_loss_guidance_step_size(step_size, i, int(t)), inv_n=1.0 / (kept * 128), tie=tie_dev, csr=csr,
+                                   side_engine=True, reuse_memory_side=2 if calls else 0, want=("x_new",), x_new=x)[2]
+            calls += 1
+            return x_new
+
+        run = _open_run(denoiser, scheduler, encoder_hidden_states, cond_masks, B, L, num_inference_steps, False,
+                        guidance_scale=guidance_scale, guidance_chunks=G, tie=tie, **kw)
+        keep_att = denoiser.return_attention
+        denoiser.return_attention = False
+        try:
+            lat = _drive(run, denoiser, encoder_hidden_states, cond_masks, G, kw.get("row_maps"), False, update,
+                         write=lambda new: run.write(new, satisfies_tie=True))
+        finally:
+            denoiser.return_attention = keep_att
+    return lat.clone()      # (outside inference mode: an ordinary tensor, like ``sample``'s)
 
 
 def diffusion_reverse(model, encoder_hidden_states, lengths=None, cond_masks=dict(), focus_indices=[], *,

@@ -579,6 +579,51 @@ int cfd_denoise_vjp(cfd_handle h, const cfd_vjp_args* args, const float* d_out, 
  * handle, rebuilt after cfd_finalize_weights); a handle that never asks pays nothing. */
 int cfd_denoise_vjp_mem(cfd_handle h, const cfd_vjp_args* args, const float* d_out, float* out, float* grad, float* const d_mem[CFD_NUM_MEM],
                         void* stream);
+/* One guided update of the sampling loop's latents by a key-pose loss of the predicted clean latents, as one device call: replaces
+ *   x.requires_grad_(True); e = denoiser(x.repeat(n, 1, 1), t, ...).view(n, B, L, 128)
+ *   eps = e[0] + sum_{k=1..n-1} w[:, k] (e[k] - e[0]); x0 = (x - sqrt_1m_acp eps) / sqrt_acp
+ *   loss = inv_n sum (mask (x0 - target))^2; g = torch.autograd.grad(loss, x); x_new = x - step g
+ * (sampler.sample_with_loss_guidance with edit.keyframe_loss) without autograd and without a host round trip between the stages.
+ * B latent rows of L tokens under n evaluated guidance chunks: the forward has Be = n * B rows, chunk-major (row c * B + b is chunk c
+ * of latent row b), against `mem` as in cfd_vjp_args (U distinct memories, row_map [Be], masks).  Stages, on the handle's own stream
+ * behind `stream`; the call returns with its results complete, as cfd_denoise_vjp does:
+ *   1. x~ = x with every tied token replaced by its source's value (tie == NULL: x bit for bit), replicated n times;
+ *   2. cfd_denoise_vjp's forward with saved activations;  3. the combine, x0, the loss and the cotangent rows d_out;
+ *   4. cfd_denoise_vjp's reverse sweep from d_out;  5. g~[b] = d loss / d x0 / sqrt_acp + the n chunks' rows in ascending order; the fold
+ *   g[src] = g~[src] + sum of g~[t] over the tokens t tied to src, ascending (tie_csr); a tied token's own g is 0; x_new = x~ - step g on
+ *   free tokens, and a tied token of x_new takes its source's new value bit for bit (the run's overwrite rule applied).
+ * Float32 throughout, no atomics: two calls on the same inputs return the same bits.  No key-pose loss in pose space, no memory gradients.
+ *   loss  dev float, grad dev [B][L][128], x_new dev [B][L][128] (may alias x), d_out dev [Be][L][128] (the cotangent it seeded): each may
+ *   be NULL, not all four.
+ * reuse_memory_side: 0, or 2 with cfd_weg_args' meaning: the memory CONTENTS, masks and row maps are those of the previous
+ * cfd_denoise_guide call on this handle, the timestep may differ.  The call then keeps per-timestep tables for every timestep (built by
+ * the first such call) and skips the time-table and memory-side launches while shapes, pointers and instance counts match.  Nothing is
+ * shared with the other callers of the row-tile arena: a cfd_weg_eval, cfd_denoise_vjp or cfd_denoise_vjp_mem between two guide calls
+ * makes the next guide call run its memory side again, and neither of them reuses what a guide call left.
+ * Limits (CFD_E_ARG names the one exceeded, before any launch): L <= 32; Be * L <= 4096 token rows (CFD_GUIDE_MAX_ROWS; this call's own
+ * limit in place of CFD_ROWTILE_MAX_ROWS -- the arena of saved activations is ~0.19 MB per token row at nine layers, 0.8 GB at the limit, and an
+ * allocation that fails returns CFD_E_HIP); the padded keys of the five memories together <= 1024; one timestep; n >= 1; target, mask and w non-NULL;
+ * inv_n > 0; sqrt_acp > 0; a tie only with its tie_csr.  The launches run eagerly (no captured graph). */
+typedef struct {
+  int B, L, n;
+  int timestep;
+  float sqrt_acp, sqrt_1m_acp;   /* sqrt(alphas_cumprod[t]), sqrt(1 - alphas_cumprod[t]), rounded from the scheduler's float64 table */
+  const float* x;                /* dev [B][L][128] */
+  cfd_memory mem[CFD_NUM_MEM];   /* as in cfd_vjp_args, for Be = n * B rows */
+  const float* w;                /* dev [B][n]: this iteration's chunk weights; chunk 0 is the base (w[b][0] is not read) */
+  const float* target;           /* dev [B][L][128] */
+  const float* mask;             /* dev [B][L], 0 or 1 */
+  float inv_n;                   /* 1 / (kept tokens * 128) */
+  float step;
+  const int32_t* tie;            /* dev [B][L]: -1 or the flat index of the token's source (cfd_tie_args), or NULL */
+  const int32_t* tie_csr;        /* dev [2 B L + 1]: the inverse table cfd_guide_tie_csr builds; NULL without a tie */
+  int reuse_memory_side;         /* 0 or 2 */
+} cfd_guide_args;
+int cfd_denoise_guide(cfd_handle h, const cfd_guide_args* args, float* loss, float* grad, float* x_new, float* d_out, void* stream);
+/* The inverse of a tie table for cfd_guide_args.tie_csr, on the host: tie HOST [n_tokens] -> csr HOST [2 n_tokens + 1] (offsets
+ * [n_tokens + 1], then the tied tokens grouped by source, ascending within a source).  CFD_E_ARG for an entry outside [-1, n_tokens), a
+ * token tied to itself or a source that is itself tied.  Needs no handle and no device. */
+int cfd_guide_tie_csr(const int32_t* tie, long long n_tokens, int32_t* csr);
 /* ConvoFusionVae.decode together with its vector-Jacobian product with respect to the latents: replaces
  *   z.requires_grad_(True); feats = vae.decode(z, lengths); torch.autograd.grad(feats, z, d_feats)
  * i.e. autograd over convofusion/models/architectures/vae.py:268-372 (two SkipTransformerDecoders, cross_attention.py:66-125, of pre-norm

@@ -60,7 +60,7 @@ extern "C" int cfd_create(const cfd_config* cfg, cfd_handle* out) {
   c->permute = env_int("CFD_PERMUTE", 1) != 0;
   c->ln_fold = (int)env_int("CFD_LN_FOLD", -1);
   c->xa_operands = getenv("CFD_XA_OPERANDS") ? (int)env_int("CFD_XA_OPERANDS", 0) & 15 : -1;
-  (void)hipEventCreateWithFlags(&c->weg_ev, hipEventDisableTiming);
+  (void)hipEventCreateWithFlags(&c->grad.ev, hipEventDisableTiming);
   for (Work& wk : c->wk) {
     if (wk.d_step.ensure(16) != CFD_OK) { delete c; return CFD_E_HIP; }
     if (hipMemset(wk.d_step.p, 0, 16) != hipSuccess) { delete c; return fail(CFD_E_HIP, "memset"); }
@@ -90,7 +90,7 @@ extern "C" int cfd_load_tensor(cfd_handle c, const char* name, const float* data
   HIPCHK(hipMemcpy(b.p, data, numel * sizeof(float), is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
   c->raw_numel[name] = numel;
   c->finalized = false;
-  c->weg.invalidate();
+  c->grad.invalidate();
   return CFD_OK;
 }
 

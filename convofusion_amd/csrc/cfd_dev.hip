@@ -38,13 +38,13 @@ extern "C" int cfd_debug_weg_stop(cfd_handle c, int stop) {
     const bool ok = stop > 0 && ((l < c->nl && k >= 1 && k <= 9 && !(l == c->nl - 1 && k < 5)) || stop == 10);
     if (!ok) return fail(CFD_E_ARG, "cfd_debug_weg_stop: %d names no launch of the reverse sweep (16 l + k, k = 1 .. 9; the top layer has no B1 .. B4; 10 = the embedding)", stop);
   }
-  c->weg.rt.stop = stop;
+  c->grad.rt.stop = stop;
   return CFD_OK;
 }
 
 // the buffers of the row-tile WEG evaluation's arena (include/cfdenoise_dev.h: cfd_debug_weg_stop)
 static int weg_debug_buffer(Ctx* c, const char* what, float** p, size_t* n) {
-  WegRtState& s = c->weg.rt;
+  RtGradState& s = c->grad.rt;
   if (s.sig.empty() || !s.B) return fail(CFD_E_STATE, "'%s': no row-tile WEG evaluation has run on this handle", what);
   const size_t M = (size_t)s.B * s.L;
   int l = -1, k = -1;
@@ -107,7 +107,7 @@ extern "C" int cfd_debug_read(cfd_handle c, const char* what, float* dst_dev, si
 #endif
   if (!strcmp(what, "weg.info")) {   // the last row-tile WEG evaluation: launches, Sp_tot, rt_xbwd_dy_kernel instance (keys), objective kernel (1: weg_focus_kernel), G index
     if (numel < 5) return fail(CFD_E_ARG, "weg.info needs 5 floats");
-    const float f[5] = {(float)c->weg.rt.launches, (float)c->weg.rt.Sp_tot, (float)c->weg.rt.dy_keys, (float)c->weg.rt.focus_large, (float)c->weg.rt.stop_gi};
+    const float f[5] = {(float)c->grad.rt.launches, (float)c->grad.rt.Sp_tot, (float)c->grad.rt.dy_keys, (float)c->grad.rt.focus_large, (float)c->grad.rt.stop_gi};
     HIPCHK(hipMemcpy(dst_dev, f, sizeof(f), hipMemcpyHostToDevice));
     return CFD_OK;
   }

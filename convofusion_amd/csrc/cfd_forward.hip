@@ -66,7 +66,7 @@ static int refresh_step_rows(Ctx* c, hipStream_t st) {
 }
 
 // The forward for small problems: launches of 16-token x 16-feature workgroups (rowtile.hpp); same buffers, same tap points.
-// With `sv` (the WEG evaluation, weg_rt.hpp) every residual update goes to a buffer of its own, the self-attention operands, the
+// With `sv` (the row-tile gradient engine, rt_grad.hpp) every residual update goes to a buffer of its own, the self-attention operands, the
 // cross-attention scores and the FFN pre-activations of every layer are kept, and the pass ends behind the last layer's
 // cross-attention (nothing above it reaches the objective) -- unless sv->whole (cfd_denoise_vjp: the sweep starts at the output).
 

@@ -1,5 +1,5 @@
 // libcfdenoise internals shared by the translation units of the library (cfd_core / cfd_problem / cfd_forward / cfd_sample / cfd_blocks / cfd_weg /
-// cfd_dev .hip): the handle, the per-problem workspace, error and launch helpers, and the functions one unit calls in another.
+// cfd_grad / cfd_dev .hip): the handle, the per-problem workspace, error and launch helpers, and the functions one unit calls in another.
 // gfx950 only; no CPU fallback anywhere.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -97,22 +97,46 @@ struct RtSave {
   bool whole = false;           // run the WHOLE network (cfd_denoise_vjp: the sweep is seeded at the output); false: stop behind the top layer's cross-attention
 };
 
-// cfd_weg_eval on the row-tile kernels (weg_rt.hpp): the arena of saved activations and gradient buffers
-struct WegRtState {
+// The row-tile gradient engine (rt_grad.hpp: forward with saved activations and reverse sweep): the arena of saved activations and
+// gradient buffers
+struct RtGradState {
   std::vector<long long> sig;   // the caller (cfd_weg_eval / cfd_denoise_vjp / cfd_denoise_guide), shapes and pointers the arena and the problem of wk[1] were prepared for
   RtSave sv;
   float *att = nullptr, *d_att = nullptr, *fws = nullptr, *dP = nullptr, *G[3] = {nullptr, nullptr, nullptr}, *dz = nullptr, *dy = nullptr,
         *dh = nullptr, *dO = nullptr, *dqkv = nullptr;
   int launches = 0;
-  int T = 1;                    // rows of wk[1]'s per-timestep tables: 1 (this evaluation's timestep) or every timestep (cfd_weg_args::reuse_memory_side == 2)
-  // test hook (cfd_debug_weg_stop): leave wegrt::enqueue after launch 16 l + k (k = 1 .. 9: B1 .. B9 of layer l; 16 * 0 + 10: the embedding's
+  int T = 1;                    // rows of wk[1]'s per-timestep tables: 1 (this call's timestep) or every timestep (reuse_memory_side == 2)
+  // test hook (cfd_debug_weg_stop): leave the reverse sweep after launch 16 l + k (k = 1 .. 9: B1 .. B9 of layer l; 16 * 0 + 10: the embedding's
   // backward); 0 = run everything.  stop_gi: which of G[0..2] held the running gradient when enqueue returned (-1: none written yet)
   int stop = 0, stop_gi = -1;
-  int B = 0, L = 0, Sp_tot = 0, St = 0;   // the shapes of the last enqueue (cfd_debug_read sizes its buffers by them)
+  int B = 0, L = 0, Sp_tot = 0, St = 0;   // the shapes of the last launch sequence (rtgrad::begin_sequence; cfd_debug_read sizes its buffers by them)
   int dy_keys = 0, focus_large = 0;       // the rt_xbwd_dy_kernel instance (512 / RT_MAX_KEYS) and the objective kernel (1: weg_focus_kernel) it launched
 };
 
-// What cfd_weg_eval (cfd_weg.hip) keeps on the handle from one evaluation to the next.
+// What the engine's callers -- cfd_weg_eval (cfd_weg.hip), cfd_denoise_vjp(_mem) and cfd_denoise_guide (cfd_grad.hip) -- keep on the
+// handle from one call to the next.  They share wk[1], the arena and this state; what one of them left is never reused by another.
+struct GradState {
+  DBuf rt_ws;                   // the arena
+  RtGradState rt;
+  int t_host = 0;               // the call's timestep, copied to wk[1].trows in front of every launch sequence (one-row tables)
+  int dstep_host = 0;           // ... and the table row it selects, copied to wk[1].d_step (0 for one-row tables, the timestep for full tables)
+  // What the memory-side / time-only part of the last call depended on: caller, shapes, memory pointers, arena, table rows (and the
+  // timestep of one-row tables).  rtgrad::begin_call compares and clears it, a call that succeeded stores it (rtgrad::finish_call;
+  // cfd_weg_eval in its run()): a call that fails leaves nothing to reuse.
+  std::vector<long long> sig;
+  void invalidate() { sig.clear(); }   // cfd_load_tensor: the next call reuses no memory-side result (WegState keeps nothing that depends on a weight's values)
+  // cfd_denoise_vjp_mem (rt_grad.hpp, MemGrad): float32 copies of the folded A | VV ([nl][512][5 x 512] each, memory j's columns at
+  // 512 j) and c ([nl][5][512]), unscaled, from the float64 fold -- 2 x nl x 512 x 2560 x 4 B = 94 MB at nine layers -- built by the
+  // first call that asks for a memory gradient (memw_wver: the weights' generation they were folded from) and freed with the handle;
+  // the call's planes (dS', P', T, G, dn' per memory) and inverse row maps.
+  DBuf memw_a, memw_v, memw_c, mem_ws, mem_inv;
+  long long memw_wver = -1;
+  std::vector<int32_t> mem_inv_host;
+  DBuf guide_ws;                // cfd_denoise_guide (guide.hpp): the replicated input, the seeded cotangent, the per-chunk gradients, the direct term, the loss partials
+  hipEvent_t ev = nullptr;      // cross-stream hand-over of the three callers, and of cfd_dyadic_steps (destroyed with the handle)
+};
+
+// What cfd_weg_eval alone (cfd_weg.hip) keeps on the handle from one evaluation to the next.
 struct WegState {
   DBuf ws, tok;   // the float32 launch sequence's activation arena; the focus-token tables
   // cfd_weg_eval replays its launches (~400 of the float32 launch sequence, ~160 on the row-tile path) as a hipGraph.  A graph holds
@@ -129,24 +153,8 @@ struct WegState {
     void reset(const std::vector<long long>& new_key = {}) { *this = Graph{new_key}; }   // drop the graph; start counting the uses of `new_key`
   };
   Graph graph[2];               // [0] full evaluation, [1] memory-side results reused
-  // Row-tile evaluation (weg_rt.hpp): the product path for small problems
-  DBuf rt_ws;
-  WegRtState rt;
-  int t_host = 0;               // the evaluation's timestep, copied to wk[1].trows in front of every launch sequence (one-row tables)
-  int dstep_host = 0;           // ... and the table row it selects, copied to wk[1].d_step (0 for one-row tables, the timestep for full tables)
   long long tok_version = 0;    // counts the uploads of the focus-token tables (part of a graph's key)
   std::vector<int32_t> tok_host;
-  std::vector<long long> sig;   // timestep, shapes, memory pointers and arena of the last evaluation (reuse_memory_side)
-  int launches = 0;
-  void invalidate() { sig.clear(); }   // cfd_load_tensor: the next evaluation reuses no memory-side result
-  // cfd_denoise_vjp_mem (weg_rt.hpp, MemGrad): float32 copies of the folded A | VV ([nl][512][5 x 512] each, memory j's columns at
-  // 512 j) and c ([nl][5][512]), unscaled, from the float64 fold -- 2 x nl x 512 x 2560 x 4 B = 94 MB at nine layers -- built by the
-  // first call that asks for a memory gradient (memw_wver: the weights' generation they were folded from) and freed with the handle;
-  // the call's planes (dS', P', T, G, dn' per memory) and inverse row maps.
-  DBuf memw_a, memw_v, memw_c, mem_ws, mem_inv;
-  DBuf guide_ws;                // cfd_denoise_guide (guide.hpp): the replicated input, the seeded cotangent, the per-chunk gradients, the direct term, the loss partials
-  long long memw_wver = -1;
-  std::vector<int32_t> mem_inv_host;
 };
 
 // One problem's device workspace: what the launches of a forward touch.  setup_problem sizes it at its end, from the problem's path
@@ -189,7 +197,7 @@ struct Work {
   int tt_mem_mask = 0;            // bit j: kbtab[j] / vbtab[j] (and b_tab / b_sp / bsq) hold the products for tt_key
   // Where the launches of the current problem find this step's AdaLN rows, A b / VV b vectors and row-tile key tables (the tables
   // themselves, or their rows' copies in rt_cur); set by refresh_step_rows at the start of a launch sequence, read by both sequences and
-  // the WEG reverse sweep (weg_rt.hpp)
+  // the reverse sweep (rt_grad.hpp)
   const float* now_ss = nullptr;
   const float* now_kb[CFD_NMEM] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   const float* now_vb[CFD_NMEM] = {nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -278,7 +286,7 @@ struct cfd_handle_s {
   DBuf tsin;
   int tsin_rows = 0;
   // workspaces (struct Work): wk[0] belongs to cfd_forward / the sampling run (its captured graph holds these pointers), wk[1] to the
-  // row-tile WEG evaluation, which runs between two replays of an open run and must not disturb it; `w` is the one in use
+  // row-tile gradient engine (GradState), which runs between two replays of an open run and must not disturb it; `w` is the one in use
   Work wk[2];
   Work* w = &wk[0];
   long long wver = 0;     // generation of the prepared weights (cfd_finalize_weights)
@@ -302,7 +310,7 @@ struct cfd_handle_s {
   //                               for all rows, no dynamic memories
   //   CFD_ROWTILE_MAX_ROWS=<n>    moves that threshold
   //   CFD_GUIDE_MAX_ROWS=<n>      the token rows (Be * L) cfd_denoise_guide takes: its own limit, in place of rt_max_rows (PathAsk::max_rows)
-  //   CFD_WEG_ROWTILE=0           cfd_weg_eval keeps the float32 launch sequence of weg_eval.hpp instead of the row-tile one (weg_rt.hpp)
+  //   CFD_WEG_ROWTILE=0           cfd_weg_eval keeps the float32 launch sequence of weg_eval.hpp instead of the row-tile one (weg_rt.hpp, rt_grad.hpp)
   //   CFD_WEG_GRAPH=0             cfd_weg_eval always runs eagerly (WegState::graph)
   //   CFD_FUSED_XATTN=0           the three-launch cross-attention (score products -> softmax_rows_kernel -> P.V products) everywhere
   //                               instead of the fused kernel (xattn_fused.hpp)
@@ -326,7 +334,8 @@ struct cfd_handle_s {
     k.rt_max_l = RT_MAX_L; k.rt_max_keys = RT_MAX_KEYS; k.xa_tiles = XA_TILES; k.f16_min_keys = XA_F16_MIN_KEYS;
     return k;
   }
-  WegState weg;                // cfd_weg_eval's state between two evaluations (cfd_weg.hip)
+  GradState grad;              // the row-tile gradient engine's state between two calls (rt_grad.hpp)
+  WegState weg;                // cfd_weg_eval's own state between two evaluations (cfd_weg.hip)
   // cfd_vae_decode / cfd_vae_decode_vjp / cfd_vae_decode_sweep (cfd_blocks.hip, vae_dec.hpp): the calls' own workspace; the shape of the
   // forward it holds; for cfd_debug_read ("vae.*"), where the last saving forward and its sweep left their taps (g null: none, the last
   // forward was forward-only); and the kept forward's ticket (0: none is kept; `dropped_by` then names the call that dropped the last one)
@@ -339,7 +348,6 @@ struct cfd_handle_s {
     const char* dropped_by = nullptr;
     bool grew = false;            // ... and had to grow the workspace
   } vae;
-  hipEvent_t weg_ev = nullptr;  // cross-stream hand-over of cfd_weg_eval, and of cfd_dyadic_steps
   // profiling
   bool prof = false;
   hipEvent_t pev[2] = {nullptr, nullptr};
@@ -354,7 +362,7 @@ struct cfd_handle_s {
   ~cfd_handle_s() {
     run.graph.reset();
     for (WegState::Graph& g : weg.graph) g.reset();
-    if (weg_ev) (void)hipEventDestroy(weg_ev);
+    if (grad.ev) (void)hipEventDestroy(grad.ev);
     if (own_stream) (void)hipStreamDestroy(own_stream);
     for (hipEvent_t e : pev) if (e) (void)hipEventDestroy(e);
   }
@@ -558,6 +566,44 @@ int enqueue_rows(Ctx* c, hipStream_t st);
 int enqueue_rows_rt(Ctx* c, hipStream_t st, const RtSave* sv = nullptr);
 int enqueue_denoise(Ctx* c, hipStream_t st);
 size_t step_rows_bytes(Ctx* c);   // what refresh_step_rows needs of Work::rt_cur for the current problem (0: its forwards refresh nothing)
+// cfd_grad.hip (rt_grad.hpp): what cfd_weg.hip calls of the row-tile gradient engine, and the types those calls take
+namespace rtgrad {
+// Who prepared wk[1] and the arena: the three callers share both, and what one of them left is never reused by another.
+enum { FOR_WEG = 0, FOR_VJP = 1, FOR_GUIDE = 2 };
+struct WorkGuard {   // the launches of a call address Ctx::wk[1]; everything else of the handle keeps wk[0]
+  Ctx* c;
+  explicit WorkGuard(Ctx* c_) : c(c_) { c->w = &c->wk[1]; }
+  ~WorkGuard() { c->w = &c->wk[0]; }
+};
+struct Call {   // one call on the engine, as begin_call takes it
+  int who;                        // FOR_*
+  int Be, L;                      // Be rows of L tokens
+  const cfd_memory* mem;
+  const HostMaps* maps;           // the host copy of the row maps, or null (no memory has one)
+  std::vector<long long> more;    // what else of the caller's arguments the problem depends on (instance counts, row maps, guidance chunks)
+  int mode;                       // reuse_memory_side: 0 / 1 / 2
+  int timestep;
+  // left by begin_call
+  bool reuse = false;             // the memory side of the previous call stands: skip those launches
+  std::vector<long long> sig;     // what finish_call stores for the next call to compare
+};
+// Where the reverse sweep starts.  d_out == null (cfd_weg_eval): at the text maps -- the top layer's B5 takes d_att alone, nothing above
+// its cross-attention reaches the objective.  d_out (cfd_denoise_vjp, cfd_denoise_guide): the cotangent at the forward's output
+// [M][128] -- one product through latent_proj, then the top layer's B1 .. B4 like every other layer's, with decoder.norm where a lower
+// layer has the next layer's norm1 (and d_att all zero: the objective contributes nothing).
+struct SweepSeed {
+  const float* d_out = nullptr;
+};
+struct MemGrad;
+void append_memories(std::vector<long long>& v, const cfd_memory* mem);   // S | data | key_padding_mask of each memory: the memories' part of every signature
+const char* ineligible(Ctx* c, long long B, int L, const cfd_memory* mem, bool guide = false);
+int begin_on_own_stream(Ctx* c, hipStream_t caller);
+int begin_call(Ctx* c, Call& k, hipStream_t caller);
+void begin_sequence(Ctx* c);
+int enqueue_memory_side(Ctx* c, hipStream_t st);
+int enqueue_forward_saved(Ctx* c, hipStream_t st, const float* latents);
+int enqueue_reverse_sweep(Ctx* c, hipStream_t st, const SweepSeed& seed, float* grad, const MemGrad* mg = nullptr);
+}  // namespace rtgrad
 // cfd_sample.hip
 int enqueue_philox_fill(float* out, int B, int per_utt, uint64_t seed, uint32_t step, uint32_t utt0, uint32_t stream_id, float scale, hipStream_t st);
 // cfd_blocks.hip

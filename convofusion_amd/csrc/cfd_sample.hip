@@ -1141,8 +1141,8 @@ extern "C" int cfd_dyadic_steps(cfd_handle a, cfd_handle b, const cfd_dyadic_pro
   if (b) {
     // side B's stream may still hold its set-up or an earlier read: everything below is ordered behind it, and side B's later reads
     // behind everything below (events, no host wait)
-    HIPCHK(hipEventRecord(b->weg_ev, b->run.stream));
-    HIPCHK(hipStreamWaitEvent(st, b->weg_ev, 0));
+    HIPCHK(hipEventRecord(b->grad.ev, b->run.stream));
+    HIPCHK(hipStreamWaitEvent(st, b->grad.ev, 0));
   }
   const int Bs = b ? sa.B : sa.B / 2;                  // utterances per side
   const long long rows = (long long)Bs * sa.L;
@@ -1165,8 +1165,8 @@ extern "C" int cfd_dyadic_steps(cfd_handle a, cfd_handle b, const cfd_dyadic_pro
   a->run.pos += n;
   if (b) {
     b->run.pos += n;
-    HIPCHK(hipEventRecord(a->weg_ev, st));
-    HIPCHK(hipStreamWaitEvent(b->run.stream, a->weg_ev, 0));
+    HIPCHK(hipEventRecord(a->grad.ev, st));
+    HIPCHK(hipStreamWaitEvent(b->run.stream, a->grad.ev, 0));
   }
   return CFD_OK;
 }

@@ -1,14 +1,10 @@
 // libcfdenoise: word-excitation guidance -- the launch-by-launch float32 pieces (cfd_gemm_f32 ... cfd_weg_focus) and cfd_weg_eval: one evaluation of the word-excitation-guidance objective and its gradient, all launches enqueued from C++
-// (float32 launch sequence: weg_eval.hpp; small problems on the row-tile kernels: rowtile_bwd.hpp, weg_rt.hpp) -- and cfd_denoise_vjp, the
-// vector-Jacobian product of one forward with respect to its sample on the same row-tile kernels, with cfd_denoise_vjp_mem, which adds
-// the product with respect to the five memories -- and cfd_denoise_guide, the key-pose guided update on that forward and sweep (guide.hpp).
+// (float32 launch sequence: weg_eval.hpp; small problems on the row-tile gradient engine: weg_rt.hpp, which calls into cfd_grad.hip).
 #include "cfd_internal.hpp"
 #include "grad.hpp"
 
 #include "weg_eval.hpp"
-#include "rowtile_bwd.hpp"
 #include "weg_rt.hpp"
-#include "guide.hpp"
 
 extern "C" int cfd_gemm_f32(cfd_handle c, int M, int N, int K, int nb1, int nb2, const cfd_mat* A, const cfd_mat* B, const cfd_mat* Cm,
                             const float* bias, float alpha, int accumulate, void* stream) {
@@ -90,7 +86,7 @@ struct WegEval {   // one evaluation, handed from stage to stage
   WegStaging lay;
   float* io = nullptr;
   weg::Args args{};           // what the launches read and write: staged addresses only
-  bool use_rt = false, reuse = false;   // the row-tile path (weg_rt.hpp), else the float32 launch sequence; the memory side is skipped
+  bool use_rt = false, reuse = false;   // on the row-tile gradient engine (weg_rt.hpp), else the float32 launch sequence; the memory side is skipped
   const void* arena = nullptr;
   weg::Ctx x{};               // the float32 launch sequence's pass
   std::vector<long long> sig, key;
@@ -114,7 +110,7 @@ static int check_args(Ctx* c, const cfd_weg_args* a, const float* losses, const 
   for (int t = 0; t < n_tok; ++t)
     if (a->tok_idx[t] < 1 || a->tok_idx[t] > a->last - 1) return fail(CFD_E_ARG, "focus index %d is outside the text slice [1, %d)", a->tok_idx[t], a->last);
   // test hook (cfd_debug_weg_stop): a stop names a launch of the row-tile reverse sweep, so the evaluation must take that path
-  if (c->weg.rt.stop && !wegrt::eligible(c, a)) return fail(CFD_E_STATE, "cfd_debug_weg_stop is set, but this evaluation is not eligible for the row-tile path");
+  if (c->grad.rt.stop && !wegrt::eligible(c, a)) return fail(CFD_E_STATE, "cfd_debug_weg_stop is set, but this evaluation is not eligible for the row-tile path");
   *nt_max_out = nt_max;
   return CFD_OK;
 }
@@ -149,68 +145,30 @@ static int stage_inputs(WegEval& e) {
   return CFD_OK;
 }
 
-// What an evaluation or a VJP call does first: the forward's hints lapse, the census an earlier evaluation left is settled, and the
-// handle's own stream -- capturable, and the one an open run's graph replays on: the two serialise -- starts behind whatever the caller
-// has queued on its stream.
-static int begin_on_own_stream(Ctx* c, hipStream_t caller) {
-  c->hint_now = c->hint_same_mem = false;
-  CHK(settle_deferred_census(c));
-  HIPCHK(hipEventRecord(c->weg_ev, caller));
-  HIPCHK(hipStreamWaitEvent(c->own_stream, c->weg_ev, 0));
+// The evaluation's first step, on the path check_args' shapes decide: small problems (the product shape) are a call on the row-tile
+// gradient engine -- rtgrad::begin_call prepares its problem and arena and decides the reuse of the memory side
+// (cfd_weg_args::reuse_memory_side; the modes are described there) -- everything else runs the float32 launch sequence of
+// weg_eval.hpp, which only starts behind the caller's stream here (size_f32_sequence_and_reuse follows the staging).
+static int begin(WegEval& e) {
+  const cfd_weg_args* a = e.a;
+  e.use_rt = wegrt::eligible(e.c, a);
+  if (!e.use_rt) return rtgrad::begin_on_own_stream(e.c, e.caller);
+  rtgrad::Call k{rtgrad::FOR_WEG, a->B, a->L, a->mem, nullptr, {}, a->reuse_memory_side, a->timestep};
+  CHK(rtgrad::begin_call(e.c, k, e.caller));
+  e.sig = k.sig;
+  e.reuse = k.reuse;
+  e.arena = e.c->grad.rt_ws.p;
   return CFD_OK;
 }
 
-// The call's timestep, in front of its launch sequence and outside any captured graph: one-row tables (T == 1) are built for it, full
-// tables (row t = timestep t) are read at it.
-static int set_call_timestep(Ctx* c, int T, int timestep, hipStream_t st) {
-  WegState& w = c->weg;
-  w.rt.T = T;
-  w.t_host = timestep;
-  w.dstep_host = T > 1 ? timestep : 0;
-  if (T == 1) HIPCHK(hipMemcpyAsync(c->wk[1].trows.p, &w.t_host, 4, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(c->wk[1].d_step.p, &w.dstep_host, 4, hipMemcpyHostToDevice, st));
-  return CFD_OK;
-}
-
-// The path -- small problems (the product shape) run on the row-tile kernels, everything else on the float32 launch sequence of
-// weg_eval.hpp -- its arena, and whether the memory side can be reused.
-// `sig` is what the memory-side / time-only part of an evaluation depends on.  With args->reuse_memory_side the caller states that the
-// memories' CONTENTS are unchanged too, and those launches are skipped: 1 = same timestep as well (a refinement loop at one
-// timestep), 2 = the timestep may differ (the guided sampling loop: one evaluation per iteration, same conditioning).  The
-// row-tile path serves 2 from tables over ALL timesteps, built at the first such call (row t = timestep t, one launch per
-// evaluation copies the row); the float32 launch sequence treats 2 with a new timestep as 0.
-// The row-tile half of that decision, shared by cfd_weg_eval and cfd_denoise_guide: the table rows T for `mode` (reuse_memory_side),
-// wk[1]'s problem and the arena for caller `who` (wegrt::prepare; `more`, `hm`: its instance counts and row maps), the signature --
-// a caller other than cfd_weg_eval appends itself and `more`, so that no caller's signature equals another's -- and whether it is
-// the one the previous evaluation left (WegState::sig).
-static int rt_prepare_and_reuse(Ctx* c, int who, int B, int L, const cfd_memory* mem, int mode, int timestep, hipStream_t st,
-                                const std::vector<long long>& more, const HostMaps* hm, std::vector<long long>& sig, bool& reuse,
-                                const void*& arena) {
-  WegState& w = c->weg;
-  const bool had_full = w.rt.T > 1;
-  // tables over all timesteps stay while the caller keeps stating that the conditioning is unchanged
-  const int T = mode == 2 || (mode == 1 && had_full) ? c->tsin_rows : 1;
-  CHK(wegrt::prepare(c, who, B, L, mem, T, st, more, hm));
-  arena = w.rt_ws.p;
-  sig.insert(sig.end(), {(long long)(size_t)arena, -(long long)T});
-  if (T == 1) sig.push_back(timestep);
-  if (who != wegrt::FOR_WEG) {
-    sig.push_back(who);
-    sig.insert(sig.end(), more.begin(), more.end());
-  }
-  reuse = mode != 0 && sig == w.sig;
-  return set_call_timestep(c, T, timestep, st);
-}
-
-static int choose_path_and_reuse(WegEval& e) {
+// The float32 launch sequence's arena and its own reuse rule: the signature carries the timestep, so reuse_memory_side = 2 with a new
+// timestep is treated as 0.
+static int size_f32_sequence_and_reuse(WegEval& e) {
   Ctx* c = e.c;
   const cfd_weg_args* a = e.a;
   WegState& w = c->weg;
-  e.use_rt = wegrt::eligible(c, a);
   e.sig = {e.B, e.L};
-  weg::append_memories(e.sig, a->mem);   // (wegrt::prepare rebuilds the problem when a mask pointer changes: no reuse then)
-  if (e.use_rt)
-    return rt_prepare_and_reuse(c, wegrt::FOR_WEG, a->B, a->L, a->mem, a->reuse_memory_side, a->timestep, e.st, {}, nullptr, e.sig, e.reuse, e.arena);
+  rtgrad::append_memories(e.sig, a->mem);
   e.sig.push_back(a->timestep);
   e.x = weg::Ctx::sizing_pass(c, e.st, e.B, e.L, e.D);
   weg::run(e.x, e.args);
@@ -219,7 +177,7 @@ static int choose_path_and_reuse(WegEval& e) {
   CHK(w.ws.ensure(e.x.off));
   e.arena = w.ws.p;
   e.sig.insert(e.sig.end(), {(long long)(size_t)e.arena, (long long)e.x.off});
-  e.reuse = a->reuse_memory_side != 0 && e.sig == w.sig;
+  e.reuse = a->reuse_memory_side != 0 && e.sig == c->grad.sig;
   e.x.real_pass(w.ws.as<char>(), e.reuse);
   return CFD_OK;
 }
@@ -228,17 +186,15 @@ static int choose_path_and_reuse(WegEval& e) {
 static void build_graph_key(WegEval& e) {
   const WegState& w = e.c->weg;
   e.key = {e.B, e.L, e.a->last, e.nt_max, w.tok_version, (long long)(size_t)w.tok.p, (long long)(size_t)e.io, (long long)e.lay.n_io,
-           (long long)(size_t)e.arena, (long long)e.reuse, (long long)e.use_rt, (long long)(e.use_rt ? w.rt.T : 0)};
-  weg::append_memories(e.key, e.a->mem);
+           (long long)(size_t)e.arena, (long long)e.reuse, (long long)e.use_rt, (long long)(e.use_rt ? e.c->grad.rt.T : 0)};
+  rtgrad::append_memories(e.key, e.a->mem);
   for (int k = 0; k < 3; ++k) { long long bits = 0; memcpy(&bits, &e.a->kernel3[k], 4); e.key.push_back(bits); }
 }
 
-// The evaluation's launches (this is what a graph captures; a replay leaves WegState::launches as the captured sequence's).
+// The evaluation's launches (this is what a graph captures).
 static int enqueue_eval(WegEval& e) {
-  WegState& w = e.c->weg;
   if (e.use_rt) CHK(wegrt::enqueue(e.c, e.st, !e.reuse, e.args));
   else weg::run(e.x, e.args);
-  w.launches = e.use_rt ? w.rt.launches : e.x.launches;
   return CFD_OK;
 }
 
@@ -269,16 +225,16 @@ static int run_through_graph(WegEval& e, WegState::Graph& g) {
 
 // Eagerly under the stop hook -- neither a use of a graph key nor a change of one -- and through the variant's graph otherwise.
 static int run(WegEval& e) {
-  WegState& w = e.c->weg;
-  w.sig.clear();                                  // (an evaluation that fails leaves nothing to reuse)
-  if (w.rt.stop) {
+  GradState& g = e.c->grad;
+  g.sig.clear();                                  // (an evaluation that fails leaves nothing to reuse; on the engine begin_call has cleared it already)
+  if (g.rt.stop) {
     CHK(enqueue_eval(e));
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(e.st));
   } else {
-    CHK(run_through_graph(e, w.graph[e.reuse ? 1 : 0]));
+    CHK(run_through_graph(e, e.c->weg.graph[e.reuse ? 1 : 0]));
   }
-  w.sig = e.sig;
+  g.sig = e.sig;
   return CFD_OK;
 }
 
@@ -300,8 +256,8 @@ static int deliver(WegEval& e, float* losses, float* max_att, float* grad, float
     *loss_host = sum / (float)B;
   } else {
     c->census_pending = true;                        // (read by the handle's next entry point: settle_deferred_census)
-    HIPCHK(hipEventRecord(c->weg_ev, e.st));
-    HIPCHK(hipStreamWaitEvent(e.caller, c->weg_ev, 0));
+    HIPCHK(hipEventRecord(c->grad.ev, e.st));
+    HIPCHK(hipStreamWaitEvent(e.caller, c->grad.ev, 0));
   }
   return CFD_OK;
 }
@@ -312,152 +268,12 @@ extern "C" int cfd_weg_eval(cfd_handle c, const cfd_weg_args* a, float* losses, 
   HIPCHK(hipSetDevice(c->cfg.device));
   const int D = c->cfg.text_encoded_dim, n_tok = a->tok_off[a->B];
   WegEval e{c, a, (hipStream_t)stream, c->own_stream, a->B, a->L, D, n_tok, nt_max, WegStaging(a->B, a->L, D, n_tok)};
-  CHK(begin_on_own_stream(c, e.caller));
+  CHK(begin(e));
   CHK(upload_focus_tokens(e));
   CHK(stage_inputs(e));
-  CHK(choose_path_and_reuse(e));
+  if (!e.use_rt) CHK(size_f32_sequence_and_reuse(e));
   build_graph_key(e);
   CHK(run(e));
-  if (c->weg.rt.stop) return CFD_OK;               // test hook: losses / max_att / grad are not delivered, the sweep was left early
+  if (c->grad.rt.stop) return CFD_OK;               // test hook: losses / max_att / grad are not delivered, the sweep was left early
   return deliver(e, losses, max_att, grad, loss_host);
-}
-
-// ---- cfd_denoise_vjp: d_out^T . d(out)/d(sample) of one denoiser forward on the row-tile kernels --------------------------------
-// Every refusal, before anything is touched; the row maps come back as the host sees them (part of what the problem is prepared for).
-// `wants`: some result is asked for (cfd_denoise_vjp: grad; cfd_denoise_vjp_mem: grad or a d_mem[j]).
-static int check_vjp_args(Ctx* c, const cfd_vjp_args* a, const float* d_out, bool wants, std::vector<long long>* maps, HostMaps* hm) {
-  if (!c || !a || !a->sample || !d_out || !wants) return fail(CFD_E_ARG, "null argument");
-  const int Be = a->Be;
-  CHK(check_latent_call(c, Be, a->L, a->mem, CALL_TIMESTEP | CALL_ROW_MAPS, a->timestep));
-  if (const char* why = wegrt::ineligible(c, Be, a->L, a->mem)) return fail(CFD_E_ARG, "cfd_denoise_vjp: %s", why);   // the row-tile path only
-  if (c->weg.rt.stop) return fail(CFD_E_STATE, "cfd_debug_weg_stop is set: it names a launch of cfd_weg_eval's sweep");
-  HIPCHK(hipSetDevice(c->cfg.device));
-  CHK(fetch_row_maps(a->mem, Be, "Be", *hm));
-  for (int j = 0; j < CFD_NMEM; ++j) {
-    const cfd_memory& m = a->mem[j];
-    maps->push_back(m.U);
-    maps->push_back((long long)(size_t)m.row_map);
-    if (m.row_map) maps->insert(maps->end(), hm->m[j].begin(), hm->m[j].end());
-  }
-  return CFD_OK;
-}
-
-// One body for cfd_denoise_vjp (d_mem == null) and cfd_denoise_vjp_mem: the same arena, workspace, stream and census; the memory
-// gradient adds its own buffers (WegState::mem_ws, the float32 folded weights) and launches (wegrt::MemGrad) and nothing else.
-static int denoise_vjp(Ctx* c, const cfd_vjp_args* a, const float* d_out, float* out, float* grad, float* const* d_mem, void* stream) {
-  std::vector<long long> maps;
-  HostMaps hm;
-  bool any_mem = false;
-  for (int j = 0; d_mem && j < CFD_NMEM; ++j) any_mem = any_mem || d_mem[j] != nullptr;
-  CHK(check_vjp_args(c, a, d_out, grad != nullptr || any_mem, &maps, &hm));
-  WegState& w = c->weg;
-  // like cfd_weg_eval: on the handle's own stream, in wk[1] (wegrt::WorkGuard): an open sampling run keeps wk[0] and its bits
-  hipStream_t st = c->own_stream;
-  CHK(begin_on_own_stream(c, (hipStream_t)stream));
-  // The call overwrites wk[1]'s problem and tables and the arena: nothing of an earlier cfd_weg_eval may be reused behind it -- neither
-  // its memory-side results (WegState::sig) nor its captured launches, whose arguments hold addresses that set-up may move.
-  w.sig.clear();
-  for (WegState::Graph& g : w.graph)
-    if (g.gx.exec) { HIPCHK(hipStreamSynchronize(st)); g.reset(); }
-  CHK(wegrt::prepare(c, wegrt::FOR_VJP, a->Be, a->L, a->mem, 1, st, maps, &hm));
-  CHK(set_call_timestep(c, 1, a->timestep, st));
-  wegrt::MemGrad mg;
-  if (any_mem) {
-    CHK(wegrt::ensure_memw_f32(c, st));
-    CHK(wegrt::prepare_mem_grad(c, st, a->Be, a->L, a->mem, hm, d_mem, mg));
-  }
-  const int r = wegrt::enqueue_vjp(c, st, a->sample, d_out, grad, any_mem ? &mg : nullptr);
-  w.launches = w.rt.launches;
-  if (r == CFD_OK && out)
-    HIPCHK(hipMemcpyAsync(out, c->wk[1].eps.p, (size_t)a->Be * a->L * CFD_LAT * 4, hipMemcpyDeviceToDevice, st));
-  // the call returns with `grad` (and `out`) complete: its census is read here, so a clamped sample or memory fails THIS call
-  HIPCHK(hipStreamSynchronize(st));
-  CHK(r);
-  return check_saturation(c, "cfd_denoise_vjp (sample, memories / their projections)");
-}
-
-extern "C" int cfd_denoise_vjp(cfd_handle c, const cfd_vjp_args* a, const float* d_out, float* out, float* grad, void* stream) {
-  if (!grad) return fail(CFD_E_ARG, "null argument");
-  return denoise_vjp(c, a, d_out, out, grad, nullptr, stream);
-}
-
-extern "C" int cfd_denoise_vjp_mem(cfd_handle c, const cfd_vjp_args* a, const float* d_out, float* out, float* grad, float* const d_mem[CFD_NUM_MEM],
-                                   void* stream) {
-  if (!d_mem) return fail(CFD_E_ARG, "null argument");
-  return denoise_vjp(c, a, d_out, out, grad, d_mem, stream);
-}
-
-// ---- cfd_denoise_guide: the key-pose guided update as one device call (guide.hpp) ------------------------------------------------
-extern "C" int cfd_guide_tie_csr(const int32_t* tie, long long n_tokens, int32_t* csr) {
-  if (!tie || !csr || n_tokens < 1 || n_tokens > (1LL << 30)) return fail(CFD_E_ARG, "cfd_guide_tie_csr: bad argument");
-  long long bad = -1;
-  switch (guide_build_tie_csr(tie, n_tokens, csr, &bad)) {
-    case GUIDE_CSR_OK: return CFD_OK;
-    case GUIDE_CSR_RANGE: return fail(CFD_E_ARG, "cfd_guide_tie_csr: tie[%lld] = %d is not -1 or a token in [0, %lld)", bad, tie[bad], n_tokens);
-    case GUIDE_CSR_SELF: return fail(CFD_E_ARG, "cfd_guide_tie_csr: tie[%lld] ties the token to itself", bad);
-    default: return fail(CFD_E_ARG, "cfd_guide_tie_csr: tie[%lld] = %d names a source that is itself tied (no chains)", bad, tie[bad]);
-  }
-}
-
-// Every refusal, before anything is touched; the row maps come back as the host sees them.
-static int check_guide_args(Ctx* c, const cfd_guide_args* a, bool wants, std::vector<long long>* maps, HostMaps* hm) {
-  if (!c || !a || !a->x) return fail(CFD_E_ARG, "null argument");
-  if (!wants) return fail(CFD_E_ARG, "cfd_denoise_guide: none of loss, grad, x_new and d_out is asked for");
-  if (a->n < 1) return fail(CFD_E_ARG, "cfd_denoise_guide: n = %d guidance chunks (at least 1)", a->n);
-  if (a->B < 1 || a->L < 1) return fail(CFD_E_ARG, "bad batch / length");
-  if (!a->target || !a->mask) return fail(CFD_E_ARG, "cfd_denoise_guide: %s is NULL", !a->target ? "target" : "mask");
-  if (!a->w) return fail(CFD_E_ARG, "cfd_denoise_guide: w (the chunk weights) is NULL");
-  if (!(a->inv_n > 0.f)) return fail(CFD_E_ARG, "cfd_denoise_guide: inv_n = %g is not positive (1 / (kept tokens * 128))", (double)a->inv_n);
-  if (!(a->sqrt_acp > 0.f)) return fail(CFD_E_ARG, "cfd_denoise_guide: sqrt_acp = %g is not positive", (double)a->sqrt_acp);
-  if (a->tie && !a->tie_csr) return fail(CFD_E_ARG, "cfd_denoise_guide: a tie without its tie_csr (cfd_guide_tie_csr)");
-  if (a->reuse_memory_side != 0 && a->reuse_memory_side != 2)
-    return fail(CFD_E_ARG, "cfd_denoise_guide: reuse_memory_side = %d is not 0 or 2", a->reuse_memory_side);
-  // the row limit first, in 64 bits: Be = n * B is formed only once it fits
-  if (const char* why = wegrt::ineligible(c, (long long)a->n * a->B, a->L, a->mem, true)) return fail(CFD_E_ARG, "cfd_denoise_guide: %s", why);
-  const int Be = a->n * a->B;
-  CHK(check_latent_call(c, Be, a->L, a->mem, CALL_TIMESTEP | CALL_ROW_MAPS, a->timestep));
-  if (c->weg.rt.stop) return fail(CFD_E_STATE, "cfd_debug_weg_stop is set: it names a launch of cfd_weg_eval's sweep");
-  HIPCHK(hipSetDevice(c->cfg.device));
-  CHK(fetch_row_maps(a->mem, Be, "n * B", *hm));
-  maps->push_back(a->n);
-  for (int j = 0; j < CFD_NMEM; ++j) {
-    const cfd_memory& m = a->mem[j];
-    maps->push_back(m.U);
-    maps->push_back((long long)(size_t)m.row_map);
-    if (m.row_map) maps->insert(maps->end(), hm->m[j].begin(), hm->m[j].end());
-  }
-  return CFD_OK;
-}
-
-extern "C" int cfd_denoise_guide(cfd_handle c, const cfd_guide_args* a, float* loss, float* grad, float* x_new, float* d_out, void* stream) {
-  std::vector<long long> maps;
-  HostMaps hm;
-  CHK(check_guide_args(c, a, loss || grad || x_new || d_out, &maps, &hm));
-  WegState& w = c->weg;
-  const int Be = a->n * a->B;
-  // like cfd_denoise_vjp: on the handle's own stream, in wk[1]; an open sampling run keeps wk[0] and its bits
-  hipStream_t st = c->own_stream;
-  CHK(begin_on_own_stream(c, (hipStream_t)stream));
-  // the call overwrites wk[1]'s problem and the arena: a captured cfd_weg_eval holds addresses that set-up may move
-  for (WegState::Graph& g : w.graph)
-    if (g.gx.exec) { HIPCHK(hipStreamSynchronize(st)); g.reset(); }
-  std::vector<long long> sig = {Be, a->L};
-  weg::append_memories(sig, a->mem);
-  bool reuse = false;
-  const void* arena = nullptr;
-  const int prepared = rt_prepare_and_reuse(c, wegrt::FOR_GUIDE, Be, a->L, a->mem, a->reuse_memory_side, a->timestep, st, maps, &hm, sig, reuse, arena);
-  w.sig.clear();                                  // (a call that fails leaves nothing to reuse)
-  CHK(prepared);
-  guide::Bufs b;
-  CHK(guide::ensure_bufs(c, st, (size_t)a->B * a->L, a->n, b));
-  const int r = guide::enqueue(c, st, a, b, !reuse, grad, x_new);
-  w.launches = w.rt.launches;
-  if (r == CFD_OK && loss) HIPCHK(hipMemcpyAsync(loss, b.loss, 4, hipMemcpyDeviceToDevice, st));
-  if (r == CFD_OK && d_out) HIPCHK(hipMemcpyAsync(d_out, b.d_out, (size_t)Be * a->L * CFD_LAT * 4, hipMemcpyDeviceToDevice, st));
-  // the call returns with its results complete: its census is read here, so a clamped sample or memory fails THIS call
-  HIPCHK(hipStreamSynchronize(st));
-  CHK(r);
-  CHK(check_saturation(c, "cfd_denoise_guide (x, memories / their projections)"));
-  w.sig = sig;
-  return CFD_OK;
 }

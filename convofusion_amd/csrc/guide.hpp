@@ -1,8 +1,8 @@
 // cfd_denoise_guide: one guided update of the sampling loop's latents by a key-pose loss of the predicted clean latents, as a device
 // call -- the guidance combine, x0, the loss and its cotangent rows (guide_seed_kernel), the reverse sweep of cfd_denoise_vjp from them
-// (weg_rt.hpp, unchanged), the sum over the guidance chunks, the fold of tied tokens' gradients onto their sources and the update
+// (rt_grad.hpp, unchanged), the sum over the guidance chunks, the fold of tied tokens' gradients onto their sources and the update
 // (guide_update_kernel).  Float32 throughout, no atomics: the same inputs give the same bits.
-// Included by cfd_weg.hip after weg_rt.hpp.
+// Included by cfd_grad.hip after rt_grad.hpp.
 #pragma once
 
 #include "guide_tables.hpp"
@@ -140,7 +140,7 @@ __global__ void guide_update_kernel(GuideUpdateArgs a) {
 
 namespace guide {
 
-struct Bufs {   // WegState::guide_ws
+struct Bufs {   // GradState::guide_ws
   float *xin = nullptr, *d_out = nullptr, *g_rows = nullptr, *g_dir = nullptr, *partial = nullptr, *loss = nullptr;
 };
 
@@ -150,7 +150,7 @@ static int ensure_bufs(Ctx* c, hipStream_t st, size_t n_tok, int n, Bufs& b) {
     a.take(b.xin, n_be); a.take(b.d_out, n_be); a.take(b.g_rows, n_be); a.take(b.g_dir, n_tok * CFD_LAT); a.take(b.partial, n_tok); a.take(b.loss, 1);
     return a.bytes();
   };
-  DBuf& ws = c->weg.guide_ws;
+  DBuf& ws = c->grad.guide_ws;
   const size_t bytes = layout(ArenaLayout(nullptr, 64));
   if (bytes > ws.bytes) HIPCHK(hipStreamSynchronize(st));
   CHK(ws.ensure(bytes));
@@ -159,22 +159,18 @@ static int ensure_bufs(Ctx* c, hipStream_t st, size_t n_tok, int n, Bufs& b) {
 }
 
 // The call's launches: replicate, [time tables + memory side when `full`], the whole forward with saves, seed and loss, the reverse
-// sweep from the seeded rows, reduce / fold / update.  wk[1]'s problem is prepared (wegrt::prepare, FOR_GUIDE) and its timestep set.
+// sweep from the seeded rows, reduce / fold / update.  wk[1]'s problem is prepared and its timestep set (rtgrad::begin_call).
 static int enqueue(Ctx* c, hipStream_t st, const cfd_guide_args* a, const Bufs& b, bool full, float* grad, float* x_new) {
-  wegrt::WorkGuard guard(c);
-  WegRtState& s = c->weg.rt;
-  const Problem& p = c->w->pb;
-  s.launches = 0;
-  s.stop_gi = -1;
-  s.B = p.Be; s.L = p.L; s.Sp_tot = p.Sp_tot; s.St = p.S[2];
-  s.focus_large = 0;
+  rtgrad::WorkGuard guard(c);
+  rtgrad::begin_sequence(c);
+  RtGradState& s = c->grad.rt;
   const long long n_tok = (long long)a->B * a->L, total4 = (long long)a->n * n_tok * (CFD_LAT / 4);
   auto grid1 = [](long long n) { return dim3((unsigned)((n + 255) / 256)); };
   hipLaunchKernelGGL(guide_replicate_kernel<>, grid1(total4), dim3(256), 0, st, a->x, a->tie, b.xin, n_tok, total4);
   HIPCHK(hipGetLastError());
   ++s.launches;
-  if (full) CHK(wegrt::enqueue_memory_side(c, st));
-  CHK(wegrt::enqueue_forward_saved(c, st, b.xin));
+  if (full) CHK(rtgrad::enqueue_memory_side(c, st));
+  CHK(rtgrad::enqueue_forward_saved(c, st, b.xin));
   GuideSeedArgs sa{b.xin, c->w->eps.as<float>(), a->w, a->target, a->mask, b.d_out, b.g_dir, b.partial, n_tok, a->n, a->L,
                    a->sqrt_acp, a->sqrt_1m_acp, a->inv_n};
   hipLaunchKernelGGL(guide_seed_kernel<>, dim3((unsigned)n_tok), dim3(128), 0, st, sa);
@@ -182,7 +178,7 @@ static int enqueue(Ctx* c, hipStream_t st, const cfd_guide_args* a, const Bufs& 
   hipLaunchKernelGGL(guide_loss_kernel<>, dim3(1), dim3(256), 0, st, b.partial, n_tok, a->inv_n, b.loss);
   HIPCHK(hipGetLastError());
   s.launches += 2;
-  CHK(wegrt::enqueue_reverse_sweep(c, st, wegrt::SweepSeed{b.d_out}, b.g_rows));
+  CHK(rtgrad::enqueue_reverse_sweep(c, st, rtgrad::SweepSeed{b.d_out}, b.g_rows));
   if (grad || x_new) {
     GuideUpdateArgs ua{b.xin, b.g_dir, b.g_rows, a->tie, a->tie ? a->tie_csr : nullptr, grad, x_new, n_tok, a->n, a->step};
     hipLaunchKernelGGL(guide_update_kernel<>, grid1(n_tok * 32), dim3(256), 0, st, ua);

@@ -23,8 +23,8 @@
 //   B9  dy1 = [dq | dk | dv] Wqkv                                                      [16 x 512]
 // and at the bottom  grad = (g_d + LN1'(dy1)) We  [16 x 128].
 // cfd_denoise_vjp seeds the same sweep at the forward's output: dyN = d_out Wp  [16 x 512] (the rows prologue with K = 128), and the top
-// layer's B1 then reads dyN through decoder.norm with no running gradient yet (weg_rt.hpp, SweepSeed).
-// cfd_denoise_vjp_mem adds the KEY side, behind B5 of every layer (weg_rt.hpp, MemGrad; the kernels at the end of this file):
+// layer's B1 then reads dyN through decoder.norm with no running gradient yet (rt_grad.hpp, SweepSeed).
+// cfd_denoise_vjp_mem adds the KEY side, behind B5 of every layer (rt_grad.hpp, MemGrad; the kernels at the end of this file):
 //   B5e the EMIT instance of B5 also stores dS' and P' = p rs                          [16 x Sp_tot] each
 //   M1  T = LN2(x) A_j,  M2  G = g_b VV_j   for the wanted memories                    [16 x 512] each
 //   M3  dn'_s += sum_tokens dS'_s (T + c_j) + P'_s G   (a workgroup owns 16 keys of one instance)

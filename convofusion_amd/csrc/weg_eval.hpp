@@ -387,16 +387,6 @@ struct Args {
   float *losses, *max_att, *grad;    // dev outputs
 };
 
-// A memory set's signature, appended to `v`: per memory S, the data pointer and the mask pointer.  Part of everything that decides
-// whether an evaluation may reuse what the previous one left (cfd_weg_eval's signature and graph key, wegrt::prepare's).
-static void append_memories(std::vector<long long>& v, const cfd_memory* mem) {
-  for (int j = 0; j < CFD_NMEM; ++j) {
-    v.push_back(mem[j].S);
-    v.push_back((long long)(size_t)mem[j].data);
-    v.push_back((long long)(size_t)mem[j].key_padding_mask);
-  }
-}
-
 // One pass over the whole evaluation; with x.dry it only sizes the workspace.
 static void run(Ctx& x, const Args& a) {
   cfd_handle c = x.c;

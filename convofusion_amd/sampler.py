@@ -1070,6 +1070,45 @@ def _loss_guidance_step_size(step_size, i, t):
         return float(step_size)
 
 
+def _guided_loop_plan(caller, refusal, limit_text, scheduler, encoder_hidden_states, cond_masks, B, L, num_inference_steps, guidance_scale,
+                      G, guided_iterations, kw, chunk_columns):
+    """What ``caller`` (``sample_with_loss_guidance`` / ``sample_with_keyframes``) sets up before it opens its run: refuses
+    ``operands="auto"`` and shapes beyond the call's limit (``refusal``: ``vjp_refusal`` / ``guide_refusal``; ``limit_text``: the
+    message, with {n} and {why}), sets the scheduler's timesteps and returns ``chunks``, the evaluated guidance chunks; ``states`` /
+    ``masks``, their rows of the memories; ``acp``, the float64 alphas_cumprod on the host; ``guides(i)``, whether iteration i is
+    guided; ``weights(i)``, its float32 weight row on the device, [B, 8] or with ``chunk_columns`` the chunks' columns alone [B, n]."""
+    from types import SimpleNamespace
+    if check_operands(kw.get("operands")) == "auto":
+        raise NotImplementedError(f"{caller}: operands='auto' restarts a run whose census trips; give an operand policy")
+    n_full = len(scheduler.timestep_table(num_inference_steps)[1])
+    mw = kw.get("modality_weights")
+    wtab = modality_weight_table(mw, guidance_scale, n_full, B, G) if mw is not None else None      # [n_full, B, 8]
+    chunks = guided_chunks(wtab if wtab is not None else default_guidance_weights(G, guidance_scale))
+    why = refusal(len(chunks) * B, L, [int(m.shape[1]) for m in encoder_hidden_states])
+    if why is not None:
+        raise NotImplementedError(f"{caller}: " + limit_text.format(n=len(chunks), why=why))
+    guided = None if guided_iterations is None else {int(i) for i in guided_iterations}
+    scheduler.set_timesteps(num_inference_steps)
+    dev = encoder_hidden_states[0].device
+    states, masks = guidance_chunk_rows(encoder_hidden_states, cond_masks, chunks, G, B, kw.get("row_maps"))
+    cols = chunks if chunk_columns else list(range(8))
+    w_default = torch.tensor(default_guidance_weights(G, guidance_scale), dtype=torch.float32, device=dev)[cols].expand(B, len(cols)).contiguous()
+    return SimpleNamespace(
+        chunks=chunks, dev=dev, states=[s.detach().contiguous() for s in states], masks=masks,
+        acp=scheduler.alphas_cumprod.detach().to("cpu", torch.float64), guides=lambda i: guided is None or i in guided,
+        weights=lambda i: torch.from_numpy(wtab[i][:, cols]).to(dev).contiguous() if wtab is not None else w_default)
+
+
+def _drive_quietly(run, denoiser, encoder_hidden_states, cond_masks, G, row_maps, update, write=None):
+    """``_drive`` without attention maps, whatever ``denoiser.return_attention`` says (restored afterwards)."""
+    keep_att = denoiser.return_attention
+    denoiser.return_attention = False
+    try:
+        return _drive(run, denoiser, encoder_hidden_states, cond_masks, G, row_maps, False, update, write)
+    finally:
+        denoiser.return_attention = keep_att
+
+
 def sample_with_loss_guidance(denoiser, scheduler, encoder_hidden_states, cond_masks, loss_fn, step_size, *, B, L=16,
                               num_inference_steps=1000, guidance_scale=7.5, guidance_chunks=CFG_CHUNKS, guided_iterations=None, **kw):
     """The loop with guidance by any differentiable loss of the predicted clean latents: before iteration i of ``guided_iterations``
@@ -1084,40 +1123,27 @@ def sample_with_loss_guidance(denoiser, scheduler, encoder_hidden_states, cond_m
     rows must fit the differentiable forward (``denoiser.vjp_refusal``).  Other keywords: as in ``sample`` (no ``operands="auto"``)."""
     from .denoiser import vjp_refusal
     check_loss_guidance(scheduler, noise_space=kw.get("noise_space"), anchor_trajectory=kw.get("anchor_trajectory"), tie=kw.get("tie"))
-    if check_operands(kw.get("operands")) == "auto":
-        raise NotImplementedError("sample_with_loss_guidance: operands='auto' restarts a run whose census trips; give an operand policy")
     if not callable(loss_fn):
         raise TypeError("loss_fn must be a callable [B, L, 128] -> scalar")
     G = guidance_chunks
-    n_full = len(scheduler.timestep_table(num_inference_steps)[1])
-    mw = kw.get("modality_weights")
-    wtab = modality_weight_table(mw, guidance_scale, n_full, B, G) if mw is not None else None      # [n_full, B, 8]
-    chunks = guided_chunks(wtab if wtab is not None else default_guidance_weights(G, guidance_scale))
-    why = vjp_refusal(len(chunks) * B, L, [int(m.shape[1]) for m in encoder_hidden_states])
-    if why is not None:
-        raise NotImplementedError(f"sample_with_loss_guidance: the gradient of the {len(chunks)} evaluated guidance chunks runs on the "
-                                  f"row-tile path only: {why}")
-    guided = None if guided_iterations is None else {int(i) for i in guided_iterations}
-    scheduler.set_timesteps(num_inference_steps)
-    dev = encoder_hidden_states[0].device
-    states, masks = guidance_chunk_rows(encoder_hidden_states, cond_masks, chunks, G, B, kw.get("row_maps"))
-    states = [s.detach().contiguous() for s in states]
-    w_default = torch.tensor(default_guidance_weights(G, guidance_scale), dtype=torch.float32, device=dev)
-    acp = scheduler.alphas_cumprod.detach().to("cpu", torch.float64)
+    p = _guided_loop_plan("sample_with_loss_guidance", vjp_refusal,
+                          "the gradient of the {n} evaluated guidance chunks runs on the row-tile path only: {why}", scheduler,
+                          encoder_hidden_states, cond_masks, B, L, num_inference_steps, guidance_scale, G, guided_iterations, kw, False)
+    chunks = p.chunks
 
     def update(i, t, latents):
-        if guided is not None and i not in guided:
+        if not p.guides(i):
             return None
         x = latents().requires_grad_(True)
-        w = torch.from_numpy(wtab[i]).to(dev) if wtab is not None else w_default.expand(B, 8)      # [B, 8]
+        w = p.weights(i)      # [B, 8]
         with torch.enable_grad():
-            out, _ = denoiser(sample=x.repeat(len(chunks), 1, 1), timestep=int(t), encoder_hidden_states=states, mem_mask_dict=masks,
+            out, _ = denoiser(sample=x.repeat(len(chunks), 1, 1), timestep=int(t), encoder_hidden_states=p.states, mem_mask_dict=p.masks,
                               side_engine=True)
             e = out.view(len(chunks), B, L, out.shape[-1])
             eps = e[0]
             for n, c in enumerate(chunks[1:], start=1):
                 eps = eps + w[:, c].view(B, 1, 1) * (e[n] - e[0])
-            a_t = float(acp[int(t)])
+            a_t = float(p.acp[int(t)])
             x0 = (x - (1.0 - a_t) ** 0.5 * eps) / a_t ** 0.5
             loss = loss_fn(x0)
             (g,) = torch.autograd.grad(loss, x)
@@ -1127,12 +1153,7 @@ def sample_with_loss_guidance(denoiser, scheduler, encoder_hidden_states, cond_m
 
     run = _open_run(denoiser, scheduler, encoder_hidden_states, cond_masks, B, L, num_inference_steps, False,
                     guidance_scale=guidance_scale, guidance_chunks=G, **kw)
-    keep_att = denoiser.return_attention
-    denoiser.return_attention = False
-    try:
-        return _drive(run, denoiser, encoder_hidden_states, cond_masks, G, kw.get("row_maps"), False, update)
-    finally:
-        denoiser.return_attention = keep_att
+    return _drive_quietly(run, denoiser, encoder_hidden_states, cond_masks, G, kw.get("row_maps"), update)
 
 
 def sample_with_keyframes(denoiser, scheduler, encoder_hidden_states, cond_masks, target, mask, step_size, *, B, L=16,
@@ -1149,8 +1170,6 @@ def sample_with_keyframes(denoiser, scheduler, encoder_hidden_states, cond_masks
     keywords: as in ``sample`` (no ``operands="auto"``)."""
     from .denoiser import guide_refusal, tie_csr
     check_keyframe_guidance(scheduler, noise_space=kw.get("noise_space"), anchor_trajectory=kw.get("anchor_trajectory"), tie=tie)
-    if check_operands(kw.get("operands")) == "auto":
-        raise NotImplementedError("sample_with_keyframes: operands='auto' restarts a run whose census trips; give an operand policy")
     if not isinstance(target, torch.Tensor) or tuple(target.shape) != (B, L, 128):
         raise ValueError(f"target must be a tensor [B, L, 128] = [{B}, {L}, 128]")
     if not isinstance(mask, torch.Tensor) or tuple(mask.shape) != (B, L):
@@ -1159,51 +1178,35 @@ def sample_with_keyframes(denoiser, scheduler, encoder_hidden_states, cond_masks
     if kept == 0:
         raise ValueError("sample_with_keyframes: mask keeps no token")
     G = guidance_chunks
-    n_full = len(scheduler.timestep_table(num_inference_steps)[1])
-    mw = kw.get("modality_weights")
-    wtab = modality_weight_table(mw, guidance_scale, n_full, B, G) if mw is not None else None      # [n_full, B, 8]
-    chunks = guided_chunks(wtab if wtab is not None else default_guidance_weights(G, guidance_scale))
-    why = guide_refusal(len(chunks) * B, L, [int(m.shape[1]) for m in encoder_hidden_states])
-    if why is not None:
-        raise NotImplementedError(f"sample_with_keyframes: the guided update of the {len(chunks)} evaluated guidance chunks: {why}")
-    guided = None if guided_iterations is None else {int(i) for i in guided_iterations}
-    scheduler.set_timesteps(num_inference_steps)
-    dev = encoder_hidden_states[0].device
-    acp = scheduler.alphas_cumprod.detach().to("cpu", torch.float64)
     with torch.inference_mode():
-        states, masks = guidance_chunk_rows(encoder_hidden_states, cond_masks, chunks, G, B, kw.get("row_maps"))
-        states = [s.detach().contiguous() for s in states]
-        w_default = torch.tensor(default_guidance_weights(G, guidance_scale), dtype=torch.float32, device=dev)[chunks].expand(B, len(chunks)).contiguous()
-        tgt = target.detach().to(device=dev, dtype=torch.float32).contiguous()
-        msk = (mask != 0).to(device=dev, dtype=torch.float32).contiguous()
-        tie_dev = None if tie is None else tie.detach().to(device=dev, dtype=torch.int32).contiguous()
+        p = _guided_loop_plan("sample_with_keyframes", guide_refusal, "the guided update of the {n} evaluated guidance chunks: {why}",
+                              scheduler, encoder_hidden_states, cond_masks, B, L, num_inference_steps, guidance_scale, G,
+                              guided_iterations, kw, True)
+        tgt = target.detach().to(device=p.dev, dtype=torch.float32).contiguous()
+        msk = (mask != 0).to(device=p.dev, dtype=torch.float32).contiguous()
+        tie_dev = None if tie is None else tie.detach().to(device=p.dev, dtype=torch.int32).contiguous()
         csr = None if tie_dev is None else tie_csr(tie_dev)
         calls = 0
 
         def update(i, t, latents):
             nonlocal calls
-            if guided is not None and i not in guided:
+            if not p.guides(i):
                 return None
             x = latents()
-            w = torch.from_numpy(wtab[i][:, chunks]).to(dev).contiguous() if wtab is not None else w_default      # [B, n]
-            a_t = float(acp[int(t)])
+            a_t = float(p.acp[int(t)])
             # (the side engine runs on its own stream behind torch's current one and returns complete; ``write`` then waits for
             #  the current stream, so the update and the captured iteration never execute side by side)
-            x_new = denoiser.guide(x, int(t), states, masks, w, tgt, msk, sqrt_acp=a_t ** 0.5, sqrt_1m_acp=(1.0 - a_t) ** 0.5,
-                                   step=_loss_guidance_step_size(step_size, i, int(t)), inv_n=1.0 / (kept * 128), tie=tie_dev, csr=csr,
-                                   side_engine=True, reuse_memory_side=2 if calls else 0, want=("x_new",), x_new=x)[2]
+            x_new = denoiser.guide(x, int(t), p.states, p.masks, p.weights(i), tgt, msk, sqrt_acp=a_t ** 0.5,
+                                   sqrt_1m_acp=(1.0 - a_t) ** 0.5, step=_loss_guidance_step_size(step_size, i, int(t)),
+                                   inv_n=1.0 / (kept * 128), tie=tie_dev, csr=csr, side_engine=True,
+                                   reuse_memory_side=2 if calls else 0, want=("x_new",), x_new=x)[2]
             calls += 1
             return x_new
 
         run = _open_run(denoiser, scheduler, encoder_hidden_states, cond_masks, B, L, num_inference_steps, False,
                         guidance_scale=guidance_scale, guidance_chunks=G, tie=tie, **kw)
-        keep_att = denoiser.return_attention
-        denoiser.return_attention = False
-        try:
-            lat = _drive(run, denoiser, encoder_hidden_states, cond_masks, G, kw.get("row_maps"), False, update,
-                         write=lambda new: run.write(new, satisfies_tie=True))
-        finally:
-            denoiser.return_attention = keep_att
+        lat = _drive_quietly(run, denoiser, encoder_hidden_states, cond_masks, G, kw.get("row_maps"), update,
+                             write=lambda new: run.write(new, satisfies_tie=True))
     return lat.clone()      # (outside inference mode: an ordinary tensor, like ``sample``'s)
 
 

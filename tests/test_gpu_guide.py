@@ -277,6 +277,24 @@ def test_memory_side_reuse_returns_a_fresh_call_s_bits_and_skips_its_launches():
     assert same(call(m, name, t=432, reuse=0), fresh[432])
 
 
+def test_a_refused_call_leaves_the_previous_call_s_memory_side_to_reuse():
+    from convofusion_amd import _lib
+    from tests.gpu_helpers import hip_denoiser, read_debug
+    m = hip_denoiser(1234, 1.0)
+    memory_side = (2 + 2 * int(m.num_layers)) + (6 * 5 + 2)
+    launches = lambda: int(read_debug(m, "weg.info", (5,))[0])
+    name = "product"
+    fresh = call(m, name, t=432)
+    full = launches()
+    call(m, name, t=433, reuse=2)                        # a fresh call: it builds the tables over every timestep and runs everything
+    assert launches() == full
+    with pytest.raises(_lib.CfdError, match="reuse_memory_side = 1 is not 0 or 2"):
+        call(m, name, t=433, reuse=1)                     # refused before the call begins: what the call before left stands
+    assert launches() == full
+    after = call(m, name, t=432, reuse=2)                 # another timestep, the memory side of the call before the refused one
+    assert launches() == full - memory_side and same(after, fresh)
+
+
 def test_library_refuses_before_any_launch_and_names_the_limit():
     import torch
     from convofusion_amd import _lib

@@ -3,7 +3,8 @@ small test shape (B = 2, L = 16, memories S = (6, 20, 6, 8, 1) with pad tails (2
 seeds, the seeded test weights) and prints one line per run: the SHA-256 of the final latents' bytes, of ``read()`` after every iteration
 (``steps``), of the trajectory, the noise and the attention ring where the run has them (``refused=`` with the library's message for a run it does not open), and N, first_iteration, chunks_evaluated and the
 non-pointer fields of the run's cfd_sample_args; then the launches of one iteration per class and the SHA-256 of three single forwards
-(``Denoiser.forward``: output and att_mats), the word-excitation-guidance lines of ``weg_lines`` and the Python loops' lines of ``loop_lines``.  The runs are deterministic: the outputs of two trees are compared with ``diff``, and a
+(``Denoiser.forward``: output and att_mats), the word-excitation-guidance lines of ``weg_lines``, the Python loops' lines of ``loop_lines``
+and the lines of the row-tile gradient engine's other callers, ``grad_lines``.  The runs are deterministic: the outputs of two trees are compared with ``diff``, and a
 line that differs is a change of behaviour.
 
 Usage (once in each tree):  python tools/run_digests.py > digests.txt
@@ -144,6 +145,7 @@ def main():
             out, att = m(x, t, mems, mem_mask_dict=masks)
         line(f"forward {name}", out=sha(out), att_mats=sha(*att))
     loop_lines(m, mems, masks, *weg_lines(m))
+    grad_lines(m, cb, mems, masks)
 
 
 def weg_lines(m):
@@ -196,6 +198,59 @@ def loop_lines(m, mems, masks, cb1, params):
                                                 num_inference_steps=N_IT, guidance_scale=7.5, init_latents=init, seed=2,
                                                 guided_iterations=guided)
         line(f"sample_with_loss_guidance guided_iterations={guided}", final=sha(lat))
+
+
+def grad_lines(m, cb, mems, masks):
+    """``Denoiser.vjp``, ``vjp_memories`` and ``guide`` and the key-pose loop (new lines only, as above) at the small shape with three
+    guidance chunks: every result and "weg.info" as the call left it."""
+    import ctypes as C
+
+    def info(side=False):      # of the engine the calls ran on: the key-pose loop's guide calls run on the denoiser's second engine
+        out = torch.empty(5, dtype=torch.float32, device="cuda")
+        h = m._side["handle"] if side else m._handle
+        _lib.check(_lib.load().cfd_debug_read(h, b"weg.info", C.c_void_p(out.data_ptr()), 5))
+        return [float(v) for v in out.cpu()]
+
+    chunks, t = [0, 1, 2], 500
+    n = len(chunks)
+    states, cmasks = sampler.guidance_chunk_rows(mems, masks, chunks, 7, B)
+    states = [e.contiguous() for e in states]
+    g = torch.Generator().manual_seed(21)
+    x = torch.randn((B, L, 128), generator=g).cuda()
+    xin, d_out = x.repeat(n, 1, 1), torch.randn((n * B, L, 128), generator=g).cuda()
+    out, grad = m.vjp(xin, t, states, cmasks, d_out)
+    line("Denoiser.vjp", out=sha(out), grad=sha(grad), info=info())
+    rows = np.concatenate([np.arange(c * B, (c + 1) * B) for c in chunks])
+    maps = [to_dev(np.ascontiguousarray(cb["row_map"][j][rows])) for j in range(5)]
+    umasks = {}
+    for j, k in enumerate(inputs.MEM_NAMES):
+        mk = cb["masks"][k]
+        umasks[k] = None if mk is None else to_dev(np.stack([mk[list(cb["row_map"][j]).index(u)] for u in range(B + 1)]))
+    out, grad, d_mem = m.vjp_memories(xin, t, [to_dev(u) for u in cb["unique"]], umasks, d_out, row_maps=maps)
+    line("Denoiser.vjp_memories row_maps", out=sha(out), grad=sha(grad), info=info(), **{k: sha(v) for k, v in d_mem.items()})
+    w = torch.tensor([[0.0, 0.4, 0.25], [0.0, 1.5, 2.0]]).cuda()
+    target = (torch.randn((B, L, 128), generator=g) * 0.5).cuda()
+    mask = torch.zeros((B, L))
+    mask[:, 1::3] = 1
+    mask = mask.cuda()
+    acp = scheduler.DDPMScheduler(variance_type="fixed_small", **SCHED_KW).alphas_cumprod.detach().to("cpu", torch.float64)
+    tie = window_ties(1, B, L).cuda()
+
+    def guide(name, tt, reuse, tie=None):
+        a = float(acp[tt])
+        r = m.guide(x, tt, states, cmasks, w, target, mask, sqrt_acp=a ** 0.5, sqrt_1m_acp=(1.0 - a) ** 0.5, step=0.5, tie=tie,
+                    reuse_memory_side=reuse, want=("loss", "grad", "x_new", "d_out"))
+        line(f"Denoiser.guide {name} t={tt} reuse_memory_side={reuse}", loss=sha(r[0]), grad=sha(r[1]), x_new=sha(r[2]), d_out=sha(r[3]), info=info())
+
+    guide("fresh", t, 0)
+    guide("tables over every timestep", t, 2)
+    guide("another timestep", t - 1, 2)
+    guide("tied", t, 0, tie)
+    ddpm = lambda: scheduler.DDPMScheduler(variance_type="fixed_small", **SCHED_KW)  # noqa: E731
+    for name, kw in (("plain", {}), ("tied", dict(tie=tie))):
+        lat = sampler.sample_with_keyframes(m, ddpm(), mems, masks, target, mask, 0.05, B=B, L=L, num_inference_steps=N_IT, seed=SEED,
+                                            modality_weights=dict(text=0.0, apb=0.0, lsnid=0.0), **kw)
+        line(f"sample_with_keyframes {name} 4 iterations 3 chunks", final=sha(lat), info=info(side=True))
 
 
 if __name__ == "__main__":

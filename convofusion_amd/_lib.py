@@ -29,6 +29,7 @@ SYMBOLS = [
     "cfd_test_picard_sweep", "cfd_debug_weg_stop", "cfd_debug_weg_fill", "cfd_scheduler_step_pred", "cfd_dpmsolver_step_pred",
     "cfd_debug_forward_operands", "cfd_denoise_vjp", "cfd_debug_live_buffers", "cfd_vae_decode_vjp", "cfd_denoise_vjp_mem",
     "cfd_vae_decode", "cfd_vae_decode_sweep", "cfd_vae_decode_ticket", "cfd_debug_vae_workspace", "cfd_denoise_guide", "cfd_guide_tie_csr",
+    "cfd_denoise_guide_pose",
 ]
 
 # cfd_sample_args.prediction_type / the _pred entry points, by the schedulers' config string
@@ -142,6 +143,13 @@ class GuideArgs(C.Structure):
     _fields_ = [("B", C.c_int), ("L", C.c_int), ("n", C.c_int), ("timestep", C.c_int), ("sqrt_acp", C.c_float), ("sqrt_1m_acp", C.c_float),
                 ("x", C.c_void_p), ("mem", Memory * NUM_MEM), ("w", C.c_void_p), ("target", C.c_void_p), ("mask", C.c_void_p),
                 ("inv_n", C.c_float), ("step", C.c_float), ("tie", C.c_void_p), ("tie_csr", C.c_void_p), ("reuse_memory_side", C.c_int)]
+
+
+class GuidePose(C.Structure):
+    """cfd_guide_pose: the pose-space loss of one guided update (cfd_denoise_guide_pose)."""
+    _fields_ = [("wpack", C.c_void_p), ("d_model", C.c_int), ("num_heads", C.c_int), ("ff_size", C.c_int), ("num_layers", C.c_int),
+                ("nframes", C.c_int), ("lengths", C.c_void_p), ("target", C.c_void_p), ("frame_mask", C.c_void_p), ("feature_mask", C.c_void_p),
+                ("inv_n", C.c_float)]
 
 
 class VaeDecodeVjpArgs(C.Structure):
@@ -309,6 +317,8 @@ def load():
     lib.cfd_denoise_vjp_mem.argtypes = [C.c_void_p, C.POINTER(VjpArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p]
     lib.cfd_denoise_guide.argtypes = [C.c_void_p, C.POINTER(GuideArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.cfd_guide_tie_csr.argtypes = [C.c_void_p, C.c_longlong, C.c_void_p]
+    lib.cfd_denoise_guide_pose.argtypes = [C.c_void_p, C.POINTER(GuideArgs), C.POINTER(GuidePose), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]
     lib.cfd_vae_decode_vjp.argtypes = [C.c_void_p, C.POINTER(VaeDecodeVjpArgs), C.c_void_p, C.c_void_p, C.c_void_p]
     lib.cfd_vae_decode.argtypes = [C.c_void_p, C.POINTER(VaeDecodeArgs), C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]
     lib.cfd_vae_decode_sweep.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -134,8 +134,10 @@ extern "C" int cfd_vae_encode(cfd_handle c, const float* wpack, int d_model, int
 // ---- ConvoFusionVae.decode, forward-only or kept for its sweep d(feats)/d(z) (autograd over vae.py:268-372): csrc/vae_dec.hpp ------------------
 // One call path: cfd_vae_decode = vae_decode_forward; cfd_vae_decode_sweep = vae_decode_sweep; cfd_vae_decode_vjp = the two in a row.
 
-// the limits of the three entry points (`who` names the caller in the message)
-static int vae_decode_check(const char* who, const cfd_vae_decode_args* p) {
+static_assert(VE_NFEATS == GUIDE_NFEATS, "guide.hpp indexes the decode's output by GUIDE_NFEATS");
+
+// the limits of the three entry points and of cfd_denoise_guide_pose (`who` names the caller in the message)
+int vae_decode_check(const char* who, const cfd_vae_decode_args* p) {
   if (p->d_model != VE_D || p->num_heads != 2 || p->ff_size != VE_FF || p->num_layers < 1 || p->num_layers > VE_MAX_LAYERS || p->num_layers % 2 == 0)
     return fail(CFD_E_ARG, "%s implements d_model 128, 2 heads, ff 1024 and odd num_layers <= %d only (got %d, %d, %d, %d)", who,
                 VE_MAX_LAYERS, p->d_model, p->num_heads, p->ff_size, p->num_layers);
@@ -198,7 +200,7 @@ static int vae_decode_forward_launches(const VaeDecArgs& a, bool copy_w, hipStre
 
 // The forward of `p` into feats (may be null with save).  Whatever forward the handle kept is dropped first: this one overwrites it.
 // save: the activations and the lengths stay in the workspace and the handle's ticket names them; copy_w: the weights too.
-static int vae_decode_forward(Ctx* c, const char* who, const cfd_vae_decode_args* p, float* feats, bool save, bool copy_w, hipStream_t st) {
+int vae_decode_forward(Ctx* c, const char* who, const cfd_vae_decode_args* p, float* feats, bool save, bool copy_w, hipStream_t st) {
   auto& v = c->vae;
   v.ticket = 0;
   v.dropped_by = who;
@@ -225,7 +227,7 @@ static int vae_decode_forward(Ctx* c, const char* who, const cfd_vae_decode_args
 
 // The reverse sweep over the handle's kept forward: reads the workspace (activations, lengths), d_feats and the packed weights `w` -- null:
 // the copy the forward kept, so that nothing of the caller's is read but d_feats.
-static int vae_decode_sweep(Ctx* c, const float* w, const float* d_feats, float* d_z, hipStream_t st) {
+int vae_decode_sweep(Ctx* c, const float* w, const float* d_feats, float* d_z, hipStream_t st) {
   auto& v = c->vae;
   VaeDecArgs a;
   vae_decode_layout(a, v.nl, v.bs, v.nframes, v.n_chunks, v.ws.as<float>(), true, true);

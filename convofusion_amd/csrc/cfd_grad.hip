@@ -1,7 +1,8 @@
 // libcfdenoise: the row-tile gradient engine (rt_grad.hpp: the forward with saved activations and the reverse sweep of small problems,
 // compiled here and nowhere else) and the entry points that seed the sweep at the forward's output -- cfd_denoise_vjp, the
 // vector-Jacobian product of one forward with respect to its sample, with cfd_denoise_vjp_mem, which adds the product with respect to
-// the five memories; and cfd_denoise_guide, the key-pose guided update on that forward and sweep (guide.hpp).  cfd_weg_eval
+// the five memories; and cfd_denoise_guide, the key-pose guided update on that forward and sweep (guide.hpp), with
+// cfd_denoise_guide_pose, whose loss sits behind the VAE decoder (the fused decode and its sweep, cfd_blocks.hip).  cfd_weg_eval
 // (cfd_weg.hip) is the engine's third caller.
 #include "cfd_internal.hpp"
 
@@ -71,20 +72,42 @@ extern "C" int cfd_guide_tie_csr(const int32_t* tie, long long n_tokens, int32_t
 }
 
 // Every refusal, before anything is touched; the row maps come back as the host sees them, with their part of the call's signature.
-static int check_guide_args(Ctx* c, const cfd_guide_args* a, bool wants, std::vector<long long>* more, HostMaps* hm) {
+// pose_call: cfd_denoise_guide_pose, whose loss lives in `pose` -- args' own target and mask must be NULL and its inv_n is not read.
+static int check_guide_args(Ctx* c, const cfd_guide_args* a, bool pose_call, const cfd_guide_pose* pose, bool wants, std::vector<long long>* more,
+                            HostMaps* hm) {
+  const char* who = pose_call ? "cfd_denoise_guide_pose" : "cfd_denoise_guide";
   if (!c || !a || !a->x) return fail(CFD_E_ARG, "null argument");
-  if (!wants) return fail(CFD_E_ARG, "cfd_denoise_guide: none of loss, grad, x_new and d_out is asked for");
-  if (a->n < 1) return fail(CFD_E_ARG, "cfd_denoise_guide: n = %d guidance chunks (at least 1)", a->n);
+  if (!wants) return fail(CFD_E_ARG, "%s: none of loss, grad, x_new%s is asked for", who, pose_call ? ", d_out and feats" : " and d_out");
+  if (a->n < 1) return fail(CFD_E_ARG, "%s: n = %d guidance chunks (at least 1)", who, a->n);
   if (a->B < 1 || a->L < 1) return fail(CFD_E_ARG, "bad batch / length");
-  if (!a->target || !a->mask) return fail(CFD_E_ARG, "cfd_denoise_guide: %s is NULL", !a->target ? "target" : "mask");
-  if (!a->w) return fail(CFD_E_ARG, "cfd_denoise_guide: w (the chunk weights) is NULL");
-  if (!(a->inv_n > 0.f)) return fail(CFD_E_ARG, "cfd_denoise_guide: inv_n = %g is not positive (1 / (kept tokens * 128))", (double)a->inv_n);
-  if (!(a->sqrt_acp > 0.f)) return fail(CFD_E_ARG, "cfd_denoise_guide: sqrt_acp = %g is not positive", (double)a->sqrt_acp);
-  if (a->tie && !a->tie_csr) return fail(CFD_E_ARG, "cfd_denoise_guide: a tie without its tie_csr (cfd_guide_tie_csr)");
+  if (!pose_call) {
+    if (!a->target || !a->mask) return fail(CFD_E_ARG, "cfd_denoise_guide: %s is NULL", !a->target ? "target" : "mask");
+    if (!(a->inv_n > 0.f)) return fail(CFD_E_ARG, "cfd_denoise_guide: inv_n = %g is not positive (1 / (kept tokens * 128))", (double)a->inv_n);
+  } else {
+    if (a->target || a->mask)
+      return fail(CFD_E_ARG, "cfd_denoise_guide_pose: args->%s is not NULL (the loss is the pose description's; the latent-token loss is cfd_denoise_guide's)",
+                  a->target ? "target" : "mask");
+    if (!pose) return fail(CFD_E_ARG, "cfd_denoise_guide_pose: pose is NULL");
+    const char* null_field = !pose->wpack ? "wpack" : !pose->lengths ? "lengths" : !pose->target ? "target" : !pose->frame_mask ? "frame_mask"
+                             : !pose->feature_mask ? "feature_mask" : nullptr;
+    if (null_field) return fail(CFD_E_ARG, "cfd_denoise_guide_pose: pose->%s is NULL", null_field);
+    if (!(pose->inv_n > 0.f))
+      return fail(CFD_E_ARG, "cfd_denoise_guide_pose: inv_n = %g is not positive (1 / (selected frames * selected features))", (double)pose->inv_n);
+    if (a->L % 2) return fail(CFD_E_ARG, "cfd_denoise_guide_pose: L = %d is odd (a latent chunk is a body and a hands token)", a->L);
+    const cfd_vae_decode_args f = {pose->wpack, pose->d_model, pose->num_heads, pose->ff_size, pose->num_layers, a->B, pose->nframes, a->L / 2, nullptr,
+                                   pose->lengths};
+    CHK(vae_decode_check("cfd_denoise_guide_pose", &f));
+    if (pose->nframes > 16 * (a->L / 2))
+      return fail(CFD_E_ARG, "cfd_denoise_guide_pose: nframes = %d exceeds 16 * (L / 2) = %d, the frames of %d latent chunks", pose->nframes,
+                  16 * (a->L / 2), a->L / 2);
+  }
+  if (!a->w) return fail(CFD_E_ARG, "%s: w (the chunk weights) is NULL", who);
+  if (!(a->sqrt_acp > 0.f)) return fail(CFD_E_ARG, "%s: sqrt_acp = %g is not positive", who, (double)a->sqrt_acp);
+  if (a->tie && !a->tie_csr) return fail(CFD_E_ARG, "%s: a tie without its tie_csr (cfd_guide_tie_csr)", who);
   if (a->reuse_memory_side != 0 && a->reuse_memory_side != 2)
-    return fail(CFD_E_ARG, "cfd_denoise_guide: reuse_memory_side = %d is not 0 or 2", a->reuse_memory_side);
+    return fail(CFD_E_ARG, "%s: reuse_memory_side = %d is not 0 or 2", who, a->reuse_memory_side);
   // the row limit first, in 64 bits: Be = n * B is formed only once it fits
-  if (const char* why = rtgrad::ineligible(c, (long long)a->n * a->B, a->L, a->mem, true)) return fail(CFD_E_ARG, "cfd_denoise_guide: %s", why);
+  if (const char* why = rtgrad::ineligible(c, (long long)a->n * a->B, a->L, a->mem, true)) return fail(CFD_E_ARG, "%s: %s", who, why);
   const int Be = a->n * a->B;
   CHK(check_latent_call(c, Be, a->L, a->mem, CALL_TIMESTEP | CALL_ROW_MAPS, a->timestep));
   if (c->grad.rt.stop) return fail(CFD_E_STATE, "cfd_debug_weg_stop is set: it names a launch of cfd_weg_eval's sweep");
@@ -95,18 +118,33 @@ static int check_guide_args(Ctx* c, const cfd_guide_args* a, bool wants, std::ve
   return CFD_OK;
 }
 
-extern "C" int cfd_denoise_guide(cfd_handle c, const cfd_guide_args* a, float* loss, float* grad, float* x_new, float* d_out, void* stream) {
+// One body for cfd_denoise_guide (pose_call false) and cfd_denoise_guide_pose: the same arena, workspace, stream, census and signature --
+// the memory side does not depend on the loss, so either call reuses what the other left.
+static int denoise_guide(Ctx* c, const cfd_guide_args* a, bool pose_call, const cfd_guide_pose* pose, float* loss, float* grad, float* x_new,
+                         float* d_out, float* feats, void* stream) {
   rtgrad::Call k{rtgrad::FOR_GUIDE};
   HostMaps hm;
-  CHK(check_guide_args(c, a, loss || grad || x_new || d_out, &k.more, &hm));
+  CHK(check_guide_args(c, a, pose_call, pose, loss || grad || x_new || d_out || feats, &k.more, &hm));
   const int Be = a->n * a->B;
   k.Be = Be; k.L = a->L; k.mem = a->mem; k.maps = &hm; k.mode = a->reuse_memory_side; k.timestep = a->timestep;
   hipStream_t st = c->own_stream;
   CHK(rtgrad::begin_call(c, k, (hipStream_t)stream));
   guide::Bufs b;
-  CHK(guide::ensure_bufs(c, st, (size_t)a->B * a->L, a->n, b));
-  const int r = guide::enqueue(c, st, a, b, !k.reuse, grad, x_new);
+  const size_t pose_rows = pose ? (size_t)a->B * pose->nframes : 0;
+  CHK(guide::ensure_bufs(c, st, (size_t)a->B * a->L, a->n, b, pose_rows));
+  const int r = guide::enqueue(c, st, a, b, !k.reuse, grad, x_new, pose, "cfd_denoise_guide_pose");
   if (r == CFD_OK && loss) HIPCHK(hipMemcpyAsync(loss, b.loss, 4, hipMemcpyDeviceToDevice, st));
   if (r == CFD_OK && d_out) HIPCHK(hipMemcpyAsync(d_out, b.d_out, (size_t)Be * a->L * CFD_LAT * 4, hipMemcpyDeviceToDevice, st));
-  return rtgrad::finish_call(c, r, "cfd_denoise_guide (x, memories / their projections)", &k.sig);
+  if (r == CFD_OK && feats) HIPCHK(hipMemcpyAsync(feats, b.feats, pose_rows * GUIDE_NFEATS * 4, hipMemcpyDeviceToDevice, st));
+  return rtgrad::finish_call(c, r, pose_call ? "cfd_denoise_guide_pose (x, memories / their projections)" : "cfd_denoise_guide (x, memories / their projections)",
+                             &k.sig);
+}
+
+extern "C" int cfd_denoise_guide(cfd_handle c, const cfd_guide_args* a, float* loss, float* grad, float* x_new, float* d_out, void* stream) {
+  return denoise_guide(c, a, false, nullptr, loss, grad, x_new, d_out, nullptr, stream);
+}
+
+extern "C" int cfd_denoise_guide_pose(cfd_handle c, const cfd_guide_args* a, const cfd_guide_pose* pose, float* loss, float* grad, float* x_new,
+                                      float* d_out, float* feats, void* stream) {
+  return denoise_guide(c, a, true, pose, loss, grad, x_new, d_out, feats, stream);
 }

@@ -609,3 +609,10 @@ int enqueue_philox_fill(float* out, int B, int per_utt, uint64_t seed, uint32_t 
 // cfd_blocks.hip
 int enqueue_linear_act(const float* x, long long n_rows, int K, const float* W, const float* b, int N, int act, float* out, hipStream_t st);
 int vae_debug_buffer(Ctx* c, const char* what, float** p, size_t* n);   // the taps of the last cfd_vae_decode_vjp (cfd_debug_read "vae.*")
+// The fused decode's call path, for cfd_denoise_guide_pose (cfd_grad.hip, guide.hpp), which decodes between its forward and its sweep:
+// the limits of `p` (`who` names the caller in the message); the forward of `p` on the handle's VAE workspace (save: kept for the sweep;
+// whatever forward the handle kept is dropped, and `who` is what a stale ticket's message names); the sweep over that forward.
+constexpr int GUIDE_NFEATS = 189;   // the decoder's output features as guide.hpp indexes them (cfd_blocks.hip asserts VE_NFEATS is this)
+int vae_decode_check(const char* who, const cfd_vae_decode_args* p);
+int vae_decode_forward(Ctx* c, const char* who, const cfd_vae_decode_args* p, float* feats, bool save, bool copy_w, hipStream_t st);
+int vae_decode_sweep(Ctx* c, const float* w, const float* d_feats, float* d_z, hipStream_t st);

@@ -142,6 +142,25 @@ def guide_refusal(Be, L, S, max_rows=None):
     return vjp_refusal(Be, L, S, max_rows=max_rows)
 
 
+def guide_pose_refusal(Be, L, S, bs, nframes, max_rows=None, **decoder):
+    """Why ``Denoiser.guide_pose`` cannot run ``Be`` forward rows of ``L`` tokens against memory lengths ``S`` with ``bs`` latent rows
+    decoded to ``nframes`` frames, or None when it can: ``guide_refusal``, then ``vae.decode_vjp_refusal`` for bs sequences of L / 2
+    chunks (``decoder``: that function's keywords -- latent_dim, num_heads, ff_size, num_layers, latent_size), then the two limits
+    that belong to the pair.  Pure: no library, no device."""
+    from .vae import decode_vjp_refusal
+    why = guide_refusal(Be, L, S, max_rows=max_rows)
+    if why is not None:
+        return why
+    if L % 2:
+        return f"L = {L} is odd: a latent chunk is a body and a hands token"
+    why = decode_vjp_refusal(bs, nframes, L // 2, **decoder)
+    if why is not None:
+        return why
+    if nframes < 1 or nframes > 16 * (L // 2):
+        return f"nframes = {nframes} is not in [1, 16 * (L / 2)] = [1, {16 * (L // 2)}], the frames of {L // 2} latent chunks"
+    return None
+
+
 def tie_csr(tie):
     """The inverse of a tie table [B, L] (``run_kind.check_tie``) as ``Denoiser.guide`` takes it: int32 [2 B L + 1] on the table's
     device, built on the host by cfd_guide_tie_csr (offsets, then every source's tied tokens in ascending order)."""
@@ -458,25 +477,81 @@ class Denoiser(nn.Module):
         why = guide_refusal(n * B, L, [int(m.shape[1]) for m in encoder_hidden_states])
         if why is not None:
             raise NotImplementedError(f"Denoiser.guide runs on the row-tile path: {why}")
-        unknown = set(want) - {"loss", "grad", "x_new", "d_out"}
-        if unknown or not want:
-            raise ValueError(f"want names {sorted(unknown)}: it is a non-empty subset of loss, grad, x_new, d_out")
-        lib = _lib.load()
         dev = x.device
-        h = self.engine(dev, mem_len=max(int(m.shape[1]) for m in encoder_hidden_states), side=bool(side_engine))
-        f32 = lambda t, shape, name: self._guide_operand(t, shape, name, dev)
-        xs = f32(x, (B, L, 128), "x")
-        ws, tg, mk = f32(w, (B, n), "w"), f32(target, (B, L, 128), "target"), f32(mask, (B, L), "mask")
+        tg, mk = self._guide_operand(target, (B, L, 128), "target", dev), self._guide_operand(mask, (B, L), "mask", dev)
         if inv_n is None:
             kept = int((mk != 0).sum().item())
             if kept == 0:
                 raise ValueError("Denoiser.guide: mask keeps no token")
             inv_n = 1.0 / (kept * 128)
+
+        def latent_loss(a):
+            a.target, a.mask, a.inv_n = tg.data_ptr(), mk.data_ptr(), float(inv_n)
+            return None, None
+        return self._guide_call(x, timestep, encoder_hidden_states, mem_mask_dict, w, latent_loss, ("loss", "grad", "x_new", "d_out"), sqrt_acp,
+                                sqrt_1m_acp, step, tie, csr, row_maps, side_engine, reuse_memory_side, want, x_new)[:4]
+
+    def guide_pose(self, x, timestep, encoder_hidden_states, mem_mask_dict, w, vae, target, frame_mask, *, feature_mask=None, lengths=None,
+                   sqrt_acp, sqrt_1m_acp, step, inv_n=None, tie=None, csr=None, row_maps=None, side_engine=False, reuse_memory_side=0,
+                   want=("loss", "grad", "x_new"), x_new=None):
+        """One ``cfd_denoise_guide_pose`` call: ``guide`` with the loss of ``edit.pose_keyframe_loss`` -- the mean-square error of
+        ``vae.decode(loop_to_vae(x0), lengths)`` against ``target`` [B, F, 189] over the frames of ``frame_mask`` [B, F] and the features
+        of ``feature_mask`` [189] (None: all) -- decoded and swept on the same handle, in the same call.  Returns (loss, grad, x_new,
+        d_out, feats), None for what ``want`` does not name (``feats`` [B, F, 189]: the decode of the predicted clean latents).
+        ``vae``: a ``convofusion_amd.vae.ConvoFusionVae`` (its packed decoder weights are read; its own ``decode`` handle is not used).
+        ``lengths``: frames per row (default F; each in [1, F]).  ``inv_n`` 1 / (selected frames * selected features) (None: from the
+        masks, one host read).  Everything else as in ``guide``; memory packing, row maps and the tie are that call's."""
+        B, L, _ = x.shape
+        n = int(w.shape[1])
+        if not isinstance(target, torch.Tensor) or target.dim() != 3 or target.shape[0] != B:
+            raise ValueError(f"Denoiser.guide_pose: target must be a tensor [{B}, F, nfeats]")
+        F, nf = int(target.shape[1]), int(target.shape[2])
+        why = guide_pose_refusal(n * B, L, [int(m.shape[1]) for m in encoder_hidden_states], B, F, latent_dim=vae.latent_dim,
+                                 num_heads=vae.num_heads, ff_size=vae.ff_size, num_layers=vae.num_layers, latent_size=vae.latent_size)
+        if why is not None:
+            raise NotImplementedError(f"Denoiser.guide_pose: {why}")
+        if nf != vae.body_nfeats + vae.hands_nfeats:
+            raise ValueError(f"Denoiser.guide_pose: target has {nf} features, the decoder {vae.body_nfeats + vae.hands_nfeats}")
+        dev = x.device
+        tg, fm = self._guide_operand(target, (B, F, nf), "target", dev), self._guide_operand(frame_mask, (B, F), "frame_mask", dev)
+        cm = torch.ones(nf, dtype=torch.float32, device=dev) if feature_mask is None else self._guide_operand(feature_mask, (nf,), "feature_mask", dev)
+        lens = torch.full((B,), F, dtype=torch.int32) if lengths is None else torch.as_tensor(lengths).detach().reshape(-1).to("cpu", torch.int32)
+        if lens.numel() != B or int(lens.min()) < 1 or int(lens.max()) > F:
+            raise ValueError(f"Denoiser.guide_pose: lengths must be {B} values in [1, {F}], got {lens.tolist()}")
+        if inv_n is None:
+            sel = int((fm != 0).sum().item()) * int((cm != 0).sum().item())
+            if sel == 0:
+                raise ValueError("Denoiser.guide_pose: the masks select no frame or no feature")
+            inv_n = 1.0 / sel
+        pack, lens_d = vae._decoder_pack(dev), lens.to(dev).contiguous()
+
+        def pose_loss(a):
+            p = _lib.GuidePose(pack.data_ptr(), vae.latent_dim, vae.num_heads, vae.ff_size, vae.num_layers, F, lens_d.data_ptr(), tg.data_ptr(),
+                               fm.data_ptr(), cm.data_ptr(), float(inv_n))
+            return p, (B, F, nf)
+        return self._guide_call(x, timestep, encoder_hidden_states, mem_mask_dict, w, pose_loss, ("loss", "grad", "x_new", "d_out", "feats"),
+                                sqrt_acp, sqrt_1m_acp, step, tie, csr, row_maps, side_engine, reuse_memory_side, want, x_new)
+
+    def _guide_call(self, x, timestep, encoder_hidden_states, mem_mask_dict, w, set_loss, wantable, sqrt_acp, sqrt_1m_acp, step, tie, csr,
+                    row_maps, side_engine, reuse_memory_side, want, x_new):
+        """The body of ``guide`` and ``guide_pose``: operands, memory packing, row maps, tie and results are one code path;
+        ``set_loss(args)`` fills the latent loss into the cfd_guide_args or returns (cfd_guide_pose, feats' shape) for the pose call.
+        Returns (loss, grad, x_new, d_out, feats)."""
+        B, L, _ = x.shape
+        n = int(w.shape[1])
+        unknown = set(want) - set(wantable)
+        if unknown or not want:
+            raise ValueError(f"want names {sorted(unknown)}: it is a non-empty subset of {', '.join(wantable)}")
+        lib = _lib.load()
+        dev = x.device
+        h = self.engine(dev, mem_len=max(int(m.shape[1]) for m in encoder_hidden_states), side=bool(side_engine))
+        xs, ws = self._guide_operand(x, (B, L, 128), "x", dev), self._guide_operand(w, (B, n), "w", dev)
         a = _lib.GuideArgs()
         mems, keep = self.pack_memories(encoder_hidden_states, mem_mask_dict, row_maps)
         a.B, a.L, a.n, a.timestep, a.sqrt_acp, a.sqrt_1m_acp = B, L, n, int(timestep), float(sqrt_acp), float(sqrt_1m_acp)
-        a.x, a.mem, a.w, a.target, a.mask = xs.data_ptr(), mems, ws.data_ptr(), tg.data_ptr(), mk.data_ptr()
-        a.inv_n, a.step, a.reuse_memory_side = float(inv_n), float(step), int(reuse_memory_side)
+        a.x, a.mem, a.w = xs.data_ptr(), mems, ws.data_ptr()
+        a.step, a.reuse_memory_side = float(step), int(reuse_memory_side)
+        pose, feats_shape = set_loss(a)
         if tie is not None:
             tt = tie.detach().to(device=dev, dtype=torch.int32).contiguous()
             if tuple(tt.shape) != (B, L):
@@ -489,6 +564,7 @@ class Denoiser(nn.Module):
         loss = torch.empty((), dtype=torch.float32, device=dev) if "loss" in want else None
         grad = torch.empty_like(xs) if "grad" in want else None
         d_out = torch.empty((n * B, L, 128), dtype=torch.float32, device=dev) if "d_out" in want else None
+        feats = torch.empty(feats_shape, dtype=torch.float32, device=dev) if "feats" in want else None
         given = x_new is not None and "x_new" in want
         if "x_new" in want:
             if x_new is None:
@@ -500,11 +576,14 @@ class Denoiser(nn.Module):
         ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
         with torch.cuda.device(dev):
             stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _lib.check(lib.cfd_denoise_guide(h, C.byref(a), ptr(loss), ptr(grad), ptr(x_new), ptr(d_out), stream))
+            if pose is None:
+                _lib.check(lib.cfd_denoise_guide(h, C.byref(a), ptr(loss), ptr(grad), ptr(x_new), ptr(d_out), stream))
+            else:
+                _lib.check(lib.cfd_denoise_guide_pose(h, C.byref(a), C.byref(pose), ptr(loss), ptr(grad), ptr(x_new), ptr(d_out), ptr(feats), stream))
         if given and not x_new.is_inference():      # (a ctypes write into the caller's tensor: see ``_lib.wrote``)
             _lib.wrote(x_new)
         del keep
-        return loss, grad, x_new, d_out
+        return loss, grad, x_new, d_out, feats
 
     @staticmethod
     def _guide_operand(t, shape, name, dev):

@@ -23,6 +23,7 @@ import inspect
 
 import torch
 
+from .run_kind import check_pose_keyframes
 from .sampler import check_operands, invert, refuse_sample_prediction, sample
 from .vae import LATENT_PARTS
 
@@ -90,21 +91,7 @@ def pose_keyframe_loss(vae, target, frame_mask, feature_mask=None, lengths=None,
     denoiser's, so an open sampling run is untouched.  Frames at or beyond a sequence's length decode to 0 and pull nothing.  Whether
     guided motions look right under a trained checkpoint is not measured here: the weights of the tests are seeded.  fused=True:
     ``vae.decode(..., fused=True)`` -- the forward is kept and the backward is the sweep alone, at the fused forward's bits."""
-    if target.dim() != 3:
-        raise ValueError(f"pose_keyframe_loss: target must be [B, F, nfeats], got {tuple(target.shape)}")
-    B, F, nf = (int(v) for v in target.shape)
-    fm = (frame_mask != 0)
-    if tuple(fm.shape) != (B, F):
-        raise ValueError(f"pose_keyframe_loss: frame_mask must be [B, F] = [{B}, {F}] like target, got {tuple(fm.shape)}")
-    cm = torch.ones(nf, dtype=torch.bool) if feature_mask is None else (feature_mask != 0)
-    if tuple(cm.shape) != (nf,):
-        raise ValueError(f"pose_keyframe_loss: feature_mask must be [{nf}], got {tuple(cm.shape)}")
-    lens = [F] * B if lengths is None else [int(v) for v in (lengths.reshape(-1).tolist() if torch.is_tensor(lengths) else lengths)]
-    if len(lens) != B or min(lens) < 1 or max(lens) != F:
-        raise ValueError(f"pose_keyframe_loss: lengths must be {B} values in [1, {F}] whose largest is {F}, got {lens}")
-    n = int(fm.sum().item()) * int(cm.sum().item())
-    if n == 0:
-        raise ValueError("pose_keyframe_loss: the masks select no frame or no feature")
+    B, F, nf, fm, cm, lens, n = check_pose_keyframes("pose_keyframe_loss", target, frame_mask, feature_mask, lengths)
 
     def loss(x0):
         if x0.dim() != 3 or x0.shape[0] != B:

@@ -26,7 +26,7 @@ import torch
 
 from .distributed import shard_cfg_batch, shard_modality_weights
 from .edit import _decode, loop_to_vae
-from .sampler import CFG_CHUNKS, check_operands, sample, sample_with_keyframes
+from .sampler import CFG_CHUNKS, check_operands, sample, sample_with_keyframes, sample_with_pose_keyframes
 
 WINDOW_FRAMES = 128     # unbounded_synthesis.py:272 (motion_len)
 
@@ -84,7 +84,8 @@ def stitch_tokens(windows):
 
 def synthesize_latents(model_or_denoiser, scheduler, encoder_hidden_states, cond_masks=None, *, n_utterances, n_windows, L=16,
                        num_inference_steps=1000, guidance_scale=7.5, guidance_chunks=CFG_CHUNKS, eta=0.0, seed=0, max_rows=None,
-                       carry=None, skip_zero_weight_chunks=True, operands=None, modality_weights=None, keyframes=None):
+                       carry=None, skip_zero_weight_chunks=True, operands=None, modality_weights=None, keyframes=None,
+                       pose_keyframes=None, vae=None):
     """The latents of U = n_utterances motions of W = n_windows half-overlapping windows each.  ``model_or_denoiser``: the HIP ``Denoiser``
     or an object with a ``.denoiser``.  encoder_hidden_states / cond_masks: the guidance batch of ``sample`` for B = U * W rows in the
     order u * W + w (chunk-major, G * B rows per memory), every row conditioned on its own window of the audio and text as the caller
@@ -98,6 +99,10 @@ def synthesize_latents(model_or_denoiser, scheduler, encoder_hidden_states, cond
     (``sampler.sample_with_keyframes``): every run whose rows hold a key token goes through the key-pose guided loop with the run's tie
     and kept tokens; a key token may fall on a tied token and then pulls its source.  step_size / guided_iterations as in that loop
     (a per-iteration step size or a callable serves every run alike).  None: exactly today's calls.
+    pose_keyframes (optional, with ``vae``, the ``ConvoFusionVae`` that decodes): (target [U * W, 8 L, 189], frame_mask [U * W, 8 L],
+    feature_mask [189] or None, step_size, guided_iterations) in window rows (``pose_keyframes_for_windows``) -- frame-accurate key poses
+    (``sampler.sample_with_pose_keyframes``): every run whose rows hold a selected frame goes through that loop with the run's tie and kept
+    tokens.  Not together with ``keyframes``.  None: exactly today's calls.
     Returns (windows [U, W, L, 128], sequence [U, (W + 1) * L / 2, 128] = ``stitch_tokens(windows)``)."""
     denoiser = getattr(model_or_denoiser, "denoiser", model_or_denoiser)
     U, W, L = int(n_utterances), int(n_windows), int(L)
@@ -118,6 +123,20 @@ def synthesize_latents(model_or_denoiser, scheduler, encoder_hidden_states, cond
             raise ValueError(f"keyframes: target must be [U * W, L, 128] = [{B}, {L}, 128]")
         if not isinstance(kf_mask, torch.Tensor) or tuple(kf_mask.shape) != (B, L):
             raise ValueError(f"keyframes: mask must be [U * W, L] = [{B}, {L}]")
+    if pose_keyframes is not None:
+        if keyframes is not None:
+            raise ValueError("keyframes and pose_keyframes cannot be combined: one guided update serves one loss")
+        if vae is None:
+            raise ValueError("pose_keyframes needs vae=, the ConvoFusionVae whose decoder the loss runs through")
+        try:
+            pk_target, pk_frames, pk_features, pk_step, pk_iterations = pose_keyframes
+        except (TypeError, ValueError):
+            raise ValueError("pose_keyframes must be (target [U * W, 8 L, 189], frame_mask [U * W, 8 L], feature_mask or None, step_size, "
+                             "guided_iterations)") from None
+        if not isinstance(pk_target, torch.Tensor) or pk_target.dim() != 3 or tuple(pk_target.shape[:2]) != (B, 8 * L):
+            raise ValueError(f"pose_keyframes: target must be [U * W, 8 L, nfeats] = [{B}, {8 * L}, nfeats]")
+        if not isinstance(pk_frames, torch.Tensor) or tuple(pk_frames.shape) != (B, 8 * L):
+            raise ValueError(f"pose_keyframes: frame_mask must be [U * W, 8 L] = [{B}, {8 * L}]")
     out = torch.empty((B, L, 128), dtype=torch.float32, device=dev)
     for start, stop in window_groups(U, W, max_rows):
         n = stop - start
@@ -142,10 +161,43 @@ def synthesize_latents(model_or_denoiser, scheduler, encoder_hidden_states, cond
         if keyframes is not None and bool((kf_mask[start:stop] != 0).any()):
             out[start:stop] = sample_with_keyframes(denoiser, scheduler, enc, masks, kf_target[start:stop], kf_mask[start:stop], kf_step,
                                                     guided_iterations=kf_iterations, **run_kw)
+        elif pose_keyframes is not None and bool((pk_frames[start:stop] != 0).any()):
+            out[start:stop] = sample_with_pose_keyframes(denoiser, scheduler, enc, masks, vae, pk_target[start:stop], pk_frames[start:stop],
+                                                         pk_step, feature_mask=pk_features, guided_iterations=pk_iterations, **run_kw)
         else:
             out[start:stop] = sample(denoiser, scheduler, enc, masks, **run_kw)
     windows = out.reshape(U, W, L, 128)
     return windows, stitch_tokens(windows)
+
+
+def pose_keyframes_for_windows(target, frame_mask, n_windows, feature_mask=None):
+    """Key poses given on the stitched motion, as window rows for ``pose_keyframes=``: target [U, (W + 1) * 64, nfeats] and frame_mask
+    [U, (W + 1) * 64] -> (target [U * W, 128, nfeats], frame_mask [U * W, 128]).  Frame f of the stitched motion goes to the window
+    ``stitch_frames`` takes it from: window 0 for f < 128, otherwise window 1 + (f - 128) // 64 at frame 64 + (f - 128) % 64.
+    ``stitch_frames`` moves the root x / z translation (features 0 and 2) of every later window by an offset that depends on the result,
+    so with W > 1 a ``feature_mask`` (the one the loss will use; None: all features) that selects column 0 or 2 is refused: such targets
+    have to be given in the window's own space, as window rows."""
+    W, F, H = int(n_windows), WINDOW_FRAMES, WINDOW_FRAMES // 2
+    if not isinstance(target, torch.Tensor) or target.dim() != 3 or W < 1 or target.shape[1] != (W + 1) * H:
+        raise ValueError(f"pose_keyframes_for_windows: target must be [U, (W + 1) * {H}, nfeats] = [U, {(W + 1) * H}, nfeats]")
+    U, _, nf = (int(v) for v in target.shape)
+    if not isinstance(frame_mask, torch.Tensor) or tuple(frame_mask.shape) != (U, (W + 1) * H):
+        raise ValueError(f"pose_keyframes_for_windows: frame_mask must be [U, (W + 1) * {H}] = [{U}, {(W + 1) * H}]")
+    if W > 1:
+        cols = torch.ones(nf, dtype=torch.bool) if feature_mask is None else (feature_mask != 0).reshape(-1).cpu()
+        if cols.numel() != nf:
+            raise ValueError(f"pose_keyframes_for_windows: feature_mask must be [{nf}]")
+        if bool(cols[0]) or bool(cols[2]):
+            raise ValueError("pose_keyframes_for_windows: the feature mask selects column 0 or 2, the root x / z translation that stitch_frames "
+                             "moves in every later window by an offset that depends on the result; give such targets in the window's own "
+                             "space (window rows) or leave the two columns out")
+    t_rows = torch.zeros((U, W, F, nf), dtype=target.dtype, device=target.device)
+    m_rows = torch.zeros((U, W, F), dtype=frame_mask.dtype, device=frame_mask.device)
+    t_rows[:, 0], m_rows[:, 0] = target[:, :F], frame_mask[:, :F]
+    if W > 1:
+        t_rows[:, 1:, H:] = target[:, F:].reshape(U, W - 1, H, nf)
+        m_rows[:, 1:, H:] = frame_mask[:, F:].reshape(U, W - 1, H)
+    return t_rows.reshape(U * W, F, nf), m_rows.reshape(U * W, F)
 
 
 def stitch_frames(feats):
@@ -166,12 +218,13 @@ def stitch_frames(feats):
 
 
 def synthesize_motion(model, encoder_hidden_states, cond_masks=None, *, n_utterances, n_windows, seed=0, max_rows=None, carry=None,
-                      modality_weights=None, operands=None, fused_decode=False, keyframes=None):
+                      modality_weights=None, operands=None, fused_decode=False, keyframes=None, pose_keyframes=None):
     """Long-form motions from a Convofusion-like ``model`` (reads vae / denoiser / scheduler / cfg / guidance_scale / clf_guidance_drops /
     do_classifier_free_guidance as ``edit.edit_motion`` does; ``model.vae`` decodes on the HIP path): ``synthesize_latents``, one HIP
     ``decode`` of all U * W windows (fused_decode=True: ``decode(..., fused=True)``, one forward-only cfd_vae_decode on a workspace of 1.2 MB
     per window), the reference's frame stitching (``stitch_frames``) in torch on the device.  keyframes: soft key poses in latent
-    tokens, as in ``synthesize_latents``.
+    tokens, as in ``synthesize_latents``; pose_keyframes: frame-accurate key poses in window rows (``pose_keyframes_for_windows``), decoded
+    through ``model.vae``.
     Returns (features [U, (W + 1) * 64, nfeats], windows [U, W, L, 128], token sequence [U, (W + 1) * L / 2, 128])."""
     if not model.do_classifier_free_guidance:
         raise NameError("guidance_bs_mulitplier: the reference loop requires classifier-free guidance")
@@ -188,6 +241,7 @@ def synthesize_motion(model, encoder_hidden_states, cond_masks=None, *, n_uttera
         num_inference_steps=model.cfg.model.scheduler.num_inference_timesteps, guidance_scale=model.guidance_scale,
         guidance_chunks=model.clf_guidance_drops + 1, eta=eta, seed=seed, max_rows=max_rows, carry=carry,
         operands=getattr(model, "_cfd_operands", None) if operands is None else operands, modality_weights=modality_weights,
-        **({} if keyframes is None else dict(keyframes=keyframes)))
+        **({} if keyframes is None else dict(keyframes=keyframes)),
+        **({} if pose_keyframes is None else dict(pose_keyframes=pose_keyframes, vae=model.vae)))
     feats = _decode(model.vae, loop_to_vae(windows.reshape(U * W, L, 128)), [WINDOW_FRAMES] * (U * W), fused_decode)
     return stitch_frames(feats.reshape(U, W, WINDOW_FRAMES, feats.shape[-1])), windows, tokens

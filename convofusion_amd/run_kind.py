@@ -215,6 +215,29 @@ def check_keyframe_guidance(scheduler, *, noise_space=None, anchor_trajectory=No
 _AUTO_RUN = object()   # the first attempt of an "auto" loop (``_with_auto_operands``): a guarded run, not another "auto" loop
 
 
+def check_pose_keyframes(who, target, frame_mask, feature_mask=None, lengths=None):
+    """What ``edit.pose_keyframe_loss`` and ``sampler.sample_with_pose_keyframes`` (``who``) ask of key poses in pose space: ``target``
+    [B, F, nfeats], ``frame_mask`` [B, F], ``feature_mask`` [nfeats] or None (all), ``lengths`` B values in [1, F] whose largest is F
+    (None: F each), and at least one selected frame and feature.  Returns (B, F, nfeats, the frame mask as bool [B, F], the feature mask
+    as bool [nfeats] on the CPU, the lengths as a list, selected frames * selected features)."""
+    if not isinstance(target, torch.Tensor) or target.dim() != 3:
+        raise ValueError(f"{who}: target must be [B, F, nfeats], got {tuple(getattr(target, 'shape', ()))}")
+    B, F, nf = (int(v) for v in target.shape)
+    fm = (frame_mask != 0)
+    if tuple(fm.shape) != (B, F):
+        raise ValueError(f"{who}: frame_mask must be [B, F] = [{B}, {F}] like target, got {tuple(fm.shape)}")
+    cm = torch.ones(nf, dtype=torch.bool) if feature_mask is None else (feature_mask != 0)
+    if tuple(cm.shape) != (nf,):
+        raise ValueError(f"{who}: feature_mask must be [{nf}], got {tuple(cm.shape)}")
+    lens = [F] * B if lengths is None else [int(v) for v in (lengths.reshape(-1).tolist() if torch.is_tensor(lengths) else lengths)]
+    if len(lens) != B or min(lens) < 1 or max(lens) != F:
+        raise ValueError(f"{who}: lengths must be {B} values in [1, {F}] whose largest is {F}, got {lens}")
+    n = int(fm.sum().item()) * int(cm.sum().item())
+    if n == 0:
+        raise ValueError(f"{who}: the masks select no frame or no feature")
+    return B, F, nf, fm, cm, lens, n
+
+
 def check_operands(operands):
     """None, an operand policy (int), or "auto"; anything else is refused."""
     if operands is None or operands is _AUTO_RUN or operands == "auto":

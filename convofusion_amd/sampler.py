@@ -17,7 +17,7 @@ from . import _lib
 from .denoiser import Denoiser
 # the pure half of opening a run: the argument checks of every kind and the kind of a run (importable from here as before)
 from .run_kind import (_AUTO_RUN, RunKind, check_anchor, check_edit, check_inversion, check_keyframe_guidance,  # noqa: F401
-                       check_loss_guidance, check_noise_space, check_operands, check_tie, edit_first_iteration, refuse_sample_prediction, resolve_run_kind,
+                       check_loss_guidance, check_pose_keyframes, check_noise_space, check_operands, check_tie, edit_first_iteration, refuse_sample_prediction, resolve_run_kind,
                        sample_prediction)
 
 # which guidance chunk carries which conditional memory (reference convofusion.py:909-929, 527-541)
@@ -1168,7 +1168,7 @@ def sample_with_keyframes(denoiser, scheduler, encoder_hidden_states, cond_masks
     evaluated chunks times B rows must fit the guide call (``denoiser.guide_refusal``: 4096 token rows, not the differentiable
     forward's 700).  With step_size 0 the result is ``sample``'s, bit for bit.  Every refusal: ``check_keyframe_guidance``.  Other
     keywords: as in ``sample`` (no ``operands="auto"``)."""
-    from .denoiser import guide_refusal, tie_csr
+    from .denoiser import guide_refusal
     check_keyframe_guidance(scheduler, noise_space=kw.get("noise_space"), anchor_trajectory=kw.get("anchor_trajectory"), tie=tie)
     if not isinstance(target, torch.Tensor) or tuple(target.shape) != (B, L, 128):
         raise ValueError(f"target must be a tensor [B, L, 128] = [{B}, {L}, 128]")
@@ -1177,13 +1177,27 @@ def sample_with_keyframes(denoiser, scheduler, encoder_hidden_states, cond_masks
     kept = int((mask != 0).sum().item())
     if kept == 0:
         raise ValueError("sample_with_keyframes: mask keeps no token")
-    G = guidance_chunks
-    with torch.inference_mode():
-        p = _guided_loop_plan("sample_with_keyframes", guide_refusal, "the guided update of the {n} evaluated guidance chunks: {why}",
-                              scheduler, encoder_hidden_states, cond_masks, B, L, num_inference_steps, guidance_scale, G,
-                              guided_iterations, kw, True)
+
+    def guide_call(p):
         tgt = target.detach().to(device=p.dev, dtype=torch.float32).contiguous()
         msk = (mask != 0).to(device=p.dev, dtype=torch.float32).contiguous()
+        return lambda x, t, w, **kw_call: denoiser.guide(x, t, p.states, p.masks, w, tgt, msk, inv_n=1.0 / (kept * 128), **kw_call)[2]
+    return _device_guided_loop("sample_with_keyframes", guide_refusal, guide_call, denoiser, scheduler, encoder_hidden_states, cond_masks, step_size,
+                               B, L, num_inference_steps, guidance_scale, guidance_chunks, guided_iterations, tie, kw)
+
+
+def _device_guided_loop(caller, refusal, guide_call, denoiser, scheduler, encoder_hidden_states, cond_masks, step_size, B, L, num_inference_steps,
+                        guidance_scale, G, guided_iterations, tie, kw):
+    """The loop of ``sample_with_keyframes`` and ``sample_with_pose_keyframes`` behind their argument checks: the plan, the tie and its
+    inverse table once, one guide call per guided iteration on the denoiser's second engine under ``torch.inference_mode()`` --
+    ``guide_call(plan)`` returns the function (x, t, w, **keywords of Denoiser.guide) -> x_new -- with the memory side kept from one
+    guided iteration to the next, and the write that states that the latents satisfy the tie."""
+    from .denoiser import tie_csr
+    with torch.inference_mode():
+        p = _guided_loop_plan(caller, refusal, "the guided update of the {n} evaluated guidance chunks: {why}",
+                              scheduler, encoder_hidden_states, cond_masks, B, L, num_inference_steps, guidance_scale, G,
+                              guided_iterations, kw, True)
+        call = guide_call(p)
         tie_dev = None if tie is None else tie.detach().to(device=p.dev, dtype=torch.int32).contiguous()
         csr = None if tie_dev is None else tie_csr(tie_dev)
         calls = 0
@@ -1196,10 +1210,9 @@ def sample_with_keyframes(denoiser, scheduler, encoder_hidden_states, cond_masks
             a_t = float(p.acp[int(t)])
             # (the side engine runs on its own stream behind torch's current one and returns complete; ``write`` then waits for
             #  the current stream, so the update and the captured iteration never execute side by side)
-            x_new = denoiser.guide(x, int(t), p.states, p.masks, p.weights(i), tgt, msk, sqrt_acp=a_t ** 0.5,
-                                   sqrt_1m_acp=(1.0 - a_t) ** 0.5, step=_loss_guidance_step_size(step_size, i, int(t)),
-                                   inv_n=1.0 / (kept * 128), tie=tie_dev, csr=csr, side_engine=True,
-                                   reuse_memory_side=2 if calls else 0, want=("x_new",), x_new=x)[2]
+            x_new = call(x, int(t), p.weights(i), sqrt_acp=a_t ** 0.5, sqrt_1m_acp=(1.0 - a_t) ** 0.5,
+                         step=_loss_guidance_step_size(step_size, i, int(t)), tie=tie_dev, csr=csr, side_engine=True,
+                         reuse_memory_side=2 if calls else 0, want=("x_new",), x_new=x)
             calls += 1
             return x_new
 
@@ -1208,6 +1221,37 @@ def sample_with_keyframes(denoiser, scheduler, encoder_hidden_states, cond_masks
         lat = _drive_quietly(run, denoiser, encoder_hidden_states, cond_masks, G, kw.get("row_maps"), update,
                              write=lambda new: run.write(new, satisfies_tie=True))
     return lat.clone()      # (outside inference mode: an ordinary tensor, like ``sample``'s)
+
+
+def sample_with_pose_keyframes(denoiser, scheduler, encoder_hidden_states, cond_masks, vae, target, frame_mask, step_size, *,
+                               feature_mask=None, lengths=None, B, L=16, num_inference_steps=1000, guidance_scale=7.5,
+                               guidance_chunks=CFG_CHUNKS, guided_iterations=None, tie=None, **kw):
+    """The loop with frame-accurate key poses on the device: ``sample_with_loss_guidance`` with
+    ``edit.pose_keyframe_loss(vae, target, frame_mask, feature_mask, lengths)`` -- loss = the mean-square error of the DECODED predicted
+    clean latents against ``target`` [B, F, 189] (decode's own, root-subtracted space) over the frames of ``frame_mask`` [B, F] and the
+    features of ``feature_mask`` [189] (None: all) -- with the update as ONE ``Denoiser.guide_pose`` call (cfd_denoise_guide_pose) per
+    guided iteration: the denoiser's saved forward, x0 in the decoder's layout, the saving decode, the loss, the decoder's sweep, the
+    denoiser's sweep and the update on one stream, with no torch autograd and no host round trip.  ``vae``: the
+    ``convofusion_amd.vae.ConvoFusionVae`` whose decoder it is.  ``lengths``: frames per row (None: F each; the largest must be F);
+    F <= 8 L.  Like ``sample_with_keyframes`` and unlike the torch loop it takes a tied run (``tie``, ``longform``) and
+    ``denoiser.guide_refusal``'s 4096 token rows; every other keyword, the refusals (``check_keyframe_guidance``,
+    ``denoiser.guide_pose_refusal``) and the bit-for-bit ``sample`` at step_size 0 are that loop's."""
+    from .denoiser import guide_pose_refusal
+    check_keyframe_guidance(scheduler, noise_space=kw.get("noise_space"), anchor_trajectory=kw.get("anchor_trajectory"), tie=tie)
+    Bt, F, _, fm, cm, lens, n_sel = check_pose_keyframes("sample_with_pose_keyframes", target, frame_mask, feature_mask, lengths)
+    if Bt != B:
+        raise ValueError(f"sample_with_pose_keyframes: target must be [B, F, nfeats] with B = {B}, got {tuple(target.shape)}")
+    decoder = dict(latent_dim=vae.latent_dim, num_heads=vae.num_heads, ff_size=vae.ff_size, num_layers=vae.num_layers, latent_size=vae.latent_size)
+
+    def guide_call(p):
+        tgt = target.detach().to(device=p.dev, dtype=torch.float32).contiguous()
+        fmask, cmask = fm.to(device=p.dev, dtype=torch.float32).contiguous(), cm.to(device=p.dev, dtype=torch.float32).contiguous()
+        lens_t = torch.tensor(lens, dtype=torch.int32)
+        return lambda x, t, w, **kw_call: denoiser.guide_pose(x, t, p.states, p.masks, w, vae, tgt, fmask, feature_mask=cmask, lengths=lens_t,
+                                                              inv_n=1.0 / n_sel, **kw_call)[2]
+    return _device_guided_loop("sample_with_pose_keyframes", lambda Be, L_, S: guide_pose_refusal(Be, L_, S, B, F, **decoder), guide_call, denoiser,
+                               scheduler, encoder_hidden_states, cond_masks, step_size, B, L, num_inference_steps, guidance_scale,
+                               guidance_chunks, guided_iterations, tie, kw)
 
 
 def diffusion_reverse(model, encoder_hidden_states, lengths=None, cond_masks=dict(), focus_indices=[], *,

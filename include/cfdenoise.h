@@ -592,14 +592,15 @@ int cfd_denoise_vjp_mem(cfd_handle h, const cfd_vjp_args* args, const float* d_o
  *   4. cfd_denoise_vjp's reverse sweep from d_out;  5. g~[b] = d loss / d x0 / sqrt_acp + the n chunks' rows in ascending order; the fold
  *   g[src] = g~[src] + sum of g~[t] over the tokens t tied to src, ascending (tie_csr); a tied token's own g is 0; x_new = x~ - step g on
  *   free tokens, and a tied token of x_new takes its source's new value bit for bit (the run's overwrite rule applied).
- * Float32 throughout, no atomics: two calls on the same inputs return the same bits.  No key-pose loss in pose space, no memory gradients.
+ * Float32 throughout, no atomics: two calls on the same inputs return the same bits.  No memory gradients.  The loss in pose space: cfd_denoise_guide_pose.
  *   loss  dev float, grad dev [B][L][128], x_new dev [B][L][128] (may alias x), d_out dev [Be][L][128] (the cotangent it seeded): each may
  *   be NULL, not all four.
  * reuse_memory_side: 0, or 2 with cfd_weg_args' meaning: the memory CONTENTS, masks and row maps are those of the previous
  * cfd_denoise_guide call on this handle, the timestep may differ.  The call then keeps per-timestep tables for every timestep (built by
  * the first such call) and skips the time-table and memory-side launches while shapes, pointers and instance counts match.  Nothing is
  * shared with the other callers of the row-tile arena: a cfd_weg_eval, cfd_denoise_vjp or cfd_denoise_vjp_mem between two guide calls
- * makes the next guide call run its memory side again, and neither of them reuses what a guide call left.
+ * makes the next guide call run its memory side again, and neither of them reuses what a guide call left (cfd_denoise_guide_pose is a
+ * guide call: the two share what they leave).
  * Limits (CFD_E_ARG names the one exceeded, before any launch): L <= 32; Be * L <= 4096 token rows (CFD_GUIDE_MAX_ROWS; this call's own
  * limit in place of CFD_ROWTILE_MAX_ROWS -- the arena of saved activations is ~0.19 MB per token row at nine layers, 0.8 GB at the limit, and an
  * allocation that fails returns CFD_E_HIP); the padded keys of the five memories together <= 1024; one timestep; n >= 1; target, mask and w non-NULL;
@@ -624,6 +625,42 @@ int cfd_denoise_guide(cfd_handle h, const cfd_guide_args* args, float* loss, flo
  * [n_tokens + 1], then the tied tokens grouped by source, ascending within a source).  CFD_E_ARG for an entry outside [-1, n_tokens), a
  * token tied to itself or a source that is itself tied.  Needs no handle and no device. */
 int cfd_guide_tie_csr(const int32_t* tie, long long n_tokens, int32_t* csr);
+/* cfd_denoise_guide with the loss in POSE space: the guided update for frame-accurate key poses, replaces
+ *   ... x0 as above; feats = vae.decode(loop_to_vae(x0), lengths)
+ *   loss = inv_n sum (frame_mask[b][f] feature_mask[j] (feats - target))^2; g = torch.autograd.grad(loss, x); x_new = x - step g
+ * (sampler.sample_with_loss_guidance with edit.pose_keyframe_loss) as one device call.  `args` keeps its cfd_denoise_guide meaning --
+ * chunk-major forward rows, w, tie / tie_csr, step, reuse_memory_side -- except that args->target and args->mask must be NULL and
+ * args->inv_n is not read: the loss is `pose`.  Stages, on the handle's own stream behind `stream`; the call returns complete:
+ *   1. x~, replicated;  2. the forward with saved activations;  3. the combine and x0, written in the decoder's layout z[part][b][p][128]
+ *   for token l = 2 p + part;  4. cfd_vae_decode_vjp's saving forward of bs = B sequences of L / 2 chunks on THIS handle's VAE workspace;
+ *   5. the loss and its cotangent d_feats = 2 inv_n r (a selected frame at or beyond lengths[b] decodes to 0: it counts target^2 towards
+ *   the loss and pulls nothing, the sweep does not read its cotangent);  6. cfd_vae_decode_vjp's sweep to d_z;  7. d_x0 read back through
+ *   the layout map, d loss / d x0 / sqrt_acp and the cotangent rows d_out as cfd_denoise_guide forms them;  8. cfd_denoise_vjp's reverse
+ *   sweep;  9. chunk sum, tie fold and update as in cfd_denoise_guide.
+ * Float32 throughout, no atomics: two calls on the same inputs return the same bits.
+ *   loss, grad, x_new, d_out as in cfd_denoise_guide; feats dev [B][nframes][189] the decode of the predicted clean latents as the call
+ *   computed it.  Each may be NULL, not all five.
+ * The call drops whatever forward the handle's cfd_vae_decode kept: a ticket taken on the same handle goes stale, and
+ * cfd_vae_decode_sweep's CFD_E_STATE names this call.
+ * reuse_memory_side: as in cfd_denoise_guide.  The denoiser's memory side does not depend on the loss, so the two calls share one
+ * signature: a pose call with reuse_memory_side = 2 reuses what a cfd_denoise_guide call with the same shapes, pointers and instance
+ * counts left, and the other way round; either way the results are a fresh call's bits.
+ * Limits (CFD_E_ARG names the one exceeded, before any launch): cfd_denoise_guide's; cfd_vae_decode_vjp's with bs = B, n_chunks = L / 2
+ * (so L <= 32 even, nframes <= 256, odd num_layers <= 9 ...); 1 <= nframes <= 16 * (L / 2); pose and every pointer in it non-NULL;
+ * pose->inv_n > 0; args->target and args->mask NULL.  The VAE workspace is 27 KB per padded frame row (2 stacks * B * nframes rounded
+ * up to 16; 6.9 MB per 128-frame sequence at 5 layers); one that cannot be allocated returns CFD_E_HIP, like the arena. */
+typedef struct {
+  const float* wpack;                 /* dev: packed decoder weights, as cfd_vae_decode_args */
+  int d_model, num_heads, ff_size, num_layers;
+  int nframes;                        /* 1 .. 256; n_chunks is args->L / 2 */
+  const int32_t* lengths;             /* dev [B], each in [1, nframes] */
+  const float* target;                /* dev [B][nframes][189], decode's own (root-subtracted) space */
+  const float* frame_mask;            /* dev [B][nframes], 0 or 1 */
+  const float* feature_mask;          /* dev [189], 0 or 1 */
+  float inv_n;                        /* 1 / (selected frames * selected features) */
+} cfd_guide_pose;
+int cfd_denoise_guide_pose(cfd_handle h, const cfd_guide_args* args, const cfd_guide_pose* pose,
+                           float* loss, float* grad, float* x_new, float* d_out, float* feats, void* stream);
 /* ConvoFusionVae.decode together with its vector-Jacobian product with respect to the latents: replaces
  *   z.requires_grad_(True); feats = vae.decode(z, lengths); torch.autograd.grad(feats, z, d_feats)
  * i.e. autograd over convofusion/models/architectures/vae.py:268-372 (two SkipTransformerDecoders, cross_attention.py:66-125, of pre-norm

@@ -29,7 +29,7 @@ SYMBOLS = [
     "cfd_test_picard_sweep", "cfd_debug_weg_stop", "cfd_debug_weg_fill", "cfd_scheduler_step_pred", "cfd_dpmsolver_step_pred",
     "cfd_debug_forward_operands", "cfd_denoise_vjp", "cfd_debug_live_buffers", "cfd_vae_decode_vjp", "cfd_denoise_vjp_mem",
     "cfd_vae_decode", "cfd_vae_decode_sweep", "cfd_vae_decode_ticket", "cfd_debug_vae_workspace", "cfd_denoise_guide", "cfd_guide_tie_csr",
-    "cfd_denoise_guide_pose",
+    "cfd_denoise_guide_pose", "cfd_weg_step", "cfd_test_weg_focus_rows",
 ]
 
 # cfd_sample_args.prediction_type / the _pred entry points, by the schedulers' config string
@@ -131,6 +131,14 @@ class Census(C.Structure):
 class WegArgs(C.Structure):
     _fields_ = [("B", C.c_int), ("L", C.c_int), ("timestep", C.c_int), ("latents", C.c_void_p), ("mem", Memory * NUM_MEM),
                 ("tok_off", C.c_void_p), ("tok_idx", C.c_void_p), ("last", C.c_int), ("kernel3", C.c_float * 3), ("reuse_memory_side", C.c_int)]
+
+
+class WegRowsArgs(C.Structure):
+    """cfd_weg_rows_args: one word-excitation-guidance evaluation and gated update of B rows that are each their own utterance
+    (cfd_weg_step)."""
+    _fields_ = [("B", C.c_int), ("L", C.c_int), ("timestep", C.c_int), ("latents", C.c_void_p), ("mem", Memory * NUM_MEM),
+                ("tok_off", C.c_void_p), ("tok_idx", C.c_void_p), ("last_rows", C.c_void_p), ("kernel3", C.c_float * 3),
+                ("row_step", C.c_void_p), ("tie", C.c_void_p), ("tie_csr", C.c_void_p), ("reuse_memory_side", C.c_int)]
 
 
 class VjpArgs(C.Structure):
@@ -313,6 +321,9 @@ def load():
     lib.cfd_sample_write.argtypes = [C.c_void_p, C.c_void_p]
     lib.cfd_sample_inpaint.argtypes = [C.c_void_p]
     lib.cfd_weg_eval.argtypes = [C.c_void_p, C.POINTER(WegArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_void_p]
+    lib.cfd_weg_step.argtypes = [C.c_void_p, C.POINTER(WegRowsArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.cfd_test_weg_focus_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                            C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.cfd_denoise_vjp.argtypes = [C.c_void_p, C.POINTER(VjpArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.cfd_denoise_vjp_mem.argtypes = [C.c_void_p, C.POINTER(VjpArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p]
     lib.cfd_denoise_guide.argtypes = [C.c_void_p, C.POINTER(GuideArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -155,6 +155,10 @@ struct WegState {
   Graph graph[2];               // [0] full evaluation, [1] memory-side results reused
   long long tok_version = 0;    // counts the uploads of the focus-token tables (part of a graph's key)
   std::vector<int32_t> tok_host;
+  // cfd_weg_step (eager, no staging): room for x~ | g~ | the rows' steps, and the steps as the host handed them to the copy.  Its tables
+  // share `tok` (offsets | indices | last_rows) and tok_host, so either call notices what the other left there.
+  DBuf rows;
+  std::vector<float> step_host;
 };
 
 // One problem's device workspace: what the launches of a forward touch.  setup_problem sizes it at its end, from the problem's path
@@ -497,6 +501,23 @@ __global__ void replicate_rows_kernel(float4* x, long long n4, int G) {
   if (i >= n4) return;
   const float4 v = x[i];
   for (int g = 1; g < G; ++g) x[(long long)g * n4 + i] = v;
+}
+
+// x~ of a tied run, replicated (cfd_denoise_guide: once per guidance chunk; cfd_weg_step: once): row c * n_tok / L + b of `xin` is
+// x~[b], x with every tied token replaced by its source's value (tie == null: x itself).  One thread per float4 of the total4 written;
+// a tie entry outside [0, n_tok) counts as free, so no table makes the kernel read out of bounds.
+template <int = 0>
+__global__ void guide_replicate_kernel(const float* __restrict__ x, const int32_t* __restrict__ tie, float* __restrict__ xin, long long n_tok,
+                                       long long total4) {
+  const long long i = blockIdx.x * 256LL + threadIdx.x;
+  if (i >= total4) return;
+  const long long tok = (i >> 5) % n_tok;
+  long long src = tok;
+  if (tie) {
+    const int v = tie[tok];
+    if (v >= 0 && v < n_tok) src = v;
+  }
+  reinterpret_cast<float4*>(xin)[i] = reinterpret_cast<const float4*>(x)[src * (CFD_LAT / 4) + (i & 31)];
 }
 
 template <int CFD_KI = 0>

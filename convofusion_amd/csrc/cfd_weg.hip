@@ -1,5 +1,6 @@
 // libcfdenoise: word-excitation guidance -- the launch-by-launch float32 pieces (cfd_gemm_f32 ... cfd_weg_focus) and cfd_weg_eval: one evaluation of the word-excitation-guidance objective and its gradient, all launches enqueued from C++
 // (float32 launch sequence: weg_eval.hpp; small problems on the row-tile gradient engine: weg_rt.hpp, which calls into cfd_grad.hip).
+// cfd_weg_step, at the end: the evaluation with every row its own utterance and the per-row gated, tied update, on the engine only.
 #include "cfd_internal.hpp"
 #include "grad.hpp"
 
@@ -65,7 +66,7 @@ extern "C" int cfd_weg_focus(cfd_handle c, const float* att, int B, int NL, int 
   if (L < 2 || last - 1 < 2 || last > S) return fail(CFD_E_SHAPE, "text slice [1, %d) of %d keys / %d frames is too short for the 3x3 reflect-padded smoothing", last, S, L);
   HIPCHK(hipSetDevice(c->cfg.device));
   hipLaunchKernelGGL(weg_focus_kernel<>, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, att, tok_off, tok_idx, B, NL, L, S, last, nt_max,
-                     kernel3[0], kernel3[1], kernel3[2], workspace, losses, max_att, d_att);
+                     kernel3[0], kernel3[1], kernel3[2], workspace, losses, max_att, d_att, (const int*)nullptr, B);
   HIPCHK(hipGetLastError());
   return CFD_OK;
 }
@@ -276,4 +277,159 @@ extern "C" int cfd_weg_eval(cfd_handle c, const cfd_weg_args* a, float* losses, 
   CHK(run(e));
   if (c->grad.rt.stop) return CFD_OK;               // test hook: losses / max_att / grad are not delivered, the sweep was left early
   return deliver(e, losses, max_att, grad, loss_host);
+}
+
+// ---- cfd_weg_step: every row its own utterance, evaluation and gated update in one call (row-tile gradient engine only) --------------
+struct WegStep {   // one call, handed from stage to stage
+  Ctx* c;
+  const cfd_weg_rows_args* a;
+  hipStream_t caller, st;
+  int B, L, n_tok, nt_max = 1, last_max = 0;
+  float *xin = nullptr, *g = nullptr, *step = nullptr;   // WegState::rows
+};
+
+// What a table of per-row slices and focus tokens must satisfy (cfd_weg_step and the focus kernels' test hook): offsets ascending from
+// 0, every slice at least 2 wide and inside the St keys, every focus index inside its own row's slice.  Yields the most focus tokens of
+// a row and the widest slice's end.
+static int check_row_tables(const char* who, int B, int St, const int32_t* tok_off, const int32_t* tok_idx, const int32_t* last_rows, int* nt_max_out,
+                            int* last_max_out) {
+  const int n_tok = tok_off[B];
+  if (tok_off[0] != 0 || n_tok < 0 || (n_tok > 0 && !tok_idx)) return fail(CFD_E_ARG, "%s: bad focus-token table", who);
+  int nt_max = 1, last_max = 0;
+  for (int b = 0; b < B; ++b) {
+    if (tok_off[b + 1] < tok_off[b] || tok_off[b + 1] > n_tok) return fail(CFD_E_ARG, "%s: bad focus-token table", who);
+    const int last = last_rows[b];
+    // F.pad(..., mode='reflect') with pad 1 needs at least 2 entries per axis (word_excitation_guidance.py:35)
+    if (last - 1 < 2 || last > St)
+      return fail(CFD_E_SHAPE, "%s: row %d: text slice [1, %d) of %d keys is too short for the 3x3 reflect-padded smoothing", who, b, last, St);
+    for (int t = tok_off[b]; t < tok_off[b + 1]; ++t)
+      if (tok_idx[t] < 1 || tok_idx[t] > last - 1)
+        return fail(CFD_E_ARG, "%s: row %d: focus index %d is outside the row's text slice [1, %d)", who, b, tok_idx[t], last);
+    nt_max = std::max(nt_max, tok_off[b + 1] - tok_off[b]);
+    last_max = std::max(last_max, last);
+  }
+  *nt_max_out = nt_max;
+  *last_max_out = last_max;
+  return CFD_OK;
+}
+
+// Every refusal, before anything is touched.
+static int check_step_args(Ctx* c, const cfd_weg_rows_args* a, const float* losses, const float* max_att, int* nt_max, int* last_max) {
+  if (!c || !a || !a->latents || !a->tok_off || !a->last_rows || !losses || !max_att) return fail(CFD_E_ARG, "cfd_weg_step: null argument");
+  CHK(check_latent_call(c, a->B, a->L, a->mem, CALL_TIMESTEP, a->timestep));   // (one memory per row: no row maps)
+  if (c->cfg.text_encoded_dim > 2048) return fail(CFD_E_SHAPE, "model width above 2048");
+  if (const char* why = rtgrad::ineligible(c, a->B, a->L, a->mem)) return fail(CFD_E_ARG, "cfd_weg_step runs on the row-tile gradient engine only: %s", why);
+  if ((a->tie != nullptr) != (a->tie_csr != nullptr)) return fail(CFD_E_ARG, "cfd_weg_step: tie and tie_csr go together (cfd_guide_tie_csr)");
+  if (a->reuse_memory_side < 0 || a->reuse_memory_side > 2) return fail(CFD_E_ARG, "cfd_weg_step: reuse_memory_side = %d is not 0, 1 or 2", a->reuse_memory_side);
+  if (c->grad.rt.stop) return fail(CFD_E_STATE, "cfd_debug_weg_stop is set: cfd_weg_step runs its whole launch sequence");
+  const int St = a->mem[2].S;
+  CHK(check_row_tables("cfd_weg_step", a->B, St, a->tok_off, a->tok_idx, a->last_rows, nt_max, last_max));
+  // the general focus kernel's workspace blocks must fit what the arena sets aside for them (rt_grad.hpp, prepare: fws)
+  if (!wegrt::focus_small(a->L, *last_max, *nt_max) && 3ll * a->L * (*last_max - 1) + 3ll * *nt_max > 3ll * a->L * St + 3ll * St + 64)
+    return fail(CFD_E_ARG, "cfd_weg_step: %d focus tokens in one row exceed the objective's workspace", *nt_max);
+  return CFD_OK;
+}
+
+// offsets | indices | last_rows to the device when they change (the stream may still read the old copy)
+static int upload_row_tables(Ctx* c, hipStream_t st, int B, const int32_t* tok_off, const int32_t* tok_idx, const int32_t* last_rows, const int32_t** off_dev,
+                             const int32_t** idx_dev, const int32_t** last_dev) {
+  WegState& w = c->weg;
+  const int n_idx = std::max(1, tok_off[B]);
+  std::vector<int32_t> tok(tok_off, tok_off + B + 1);
+  for (int t = 0; t < n_idx; ++t) tok.push_back(t < tok_off[B] ? tok_idx[t] : 0);
+  tok.insert(tok.end(), last_rows, last_rows + B);
+  if (tok != w.tok_host) {
+    HIPCHK(hipStreamSynchronize(st));
+    w.tok_host.clear();
+    CHK(w.tok.ensure(tok.size() * 4));
+    HIPCHK(hipMemcpy(w.tok.p, tok.data(), tok.size() * 4, hipMemcpyHostToDevice));
+    w.tok_host = tok;
+    ++w.tok_version;
+  }
+  *off_dev = w.tok.as<int32_t>();
+  *idx_dev = *off_dev + B + 1;
+  *last_dev = *idx_dev + n_idx;
+  return CFD_OK;
+}
+
+// Room for x~ | g~ | the rows' steps, and the steps on their way to the device (null row_step: no copy, the update takes every step as 0).
+static int stage_step(WegStep& e) {
+  WegState& w = e.c->weg;
+  auto layout = [&](ArenaLayout l) {
+    l.take(e.xin, (size_t)e.n_tok * CFD_LAT); l.take(e.g, (size_t)e.n_tok * CFD_LAT); l.take(e.step, (size_t)e.B);
+    return l.bytes();
+  };
+  const size_t bytes = layout(ArenaLayout(nullptr, 64));
+  if (bytes > w.rows.bytes) HIPCHK(hipStreamSynchronize(e.st));
+  CHK(w.rows.ensure(bytes));
+  layout(ArenaLayout(w.rows.as<float>(), 64));
+  if (!e.a->row_step) { e.step = nullptr; return CFD_OK; }
+  HIPCHK(hipStreamSynchronize(e.st));   // (the previous call's copy may still read step_host)
+  w.step_host.assign(e.a->row_step, e.a->row_step + e.B);
+  HIPCHK(hipMemcpyAsync(e.step, w.step_host.data(), (size_t)e.B * 4, hipMemcpyHostToDevice, e.st));
+  return CFD_OK;
+}
+
+extern "C" int cfd_weg_step(cfd_handle c, const cfd_weg_rows_args* a, float* losses, float* max_att, float* grad, float* x_new, float* losses_host,
+                            void* stream) {
+  int nt_max = 1, last_max = 0;
+  CHK(check_step_args(c, a, losses, max_att, &nt_max, &last_max));
+  HIPCHK(hipSetDevice(c->cfg.device));
+  WegStep e{c, a, (hipStream_t)stream, c->own_stream, a->B, a->L, a->B * a->L, nt_max, last_max};
+  rtgrad::Call k{rtgrad::FOR_WEG, a->B, a->L, a->mem, nullptr, {}, a->reuse_memory_side, a->timestep};
+  CHK(rtgrad::begin_call(c, k, e.caller));
+  const int32_t *off_dev, *idx_dev, *last_dev;
+  CHK(upload_row_tables(c, e.st, e.B, a->tok_off, a->tok_idx, a->last_rows, &off_dev, &idx_dev, &last_dev));
+  CHK(stage_step(e));
+  weg::Args args{a->latents, nullptr, a->mem, off_dev, idx_dev, last_max, nt_max, {a->kernel3[0], a->kernel3[1], a->kernel3[2]}, losses, max_att, e.g, last_dev};
+  const int r = wegrt::enqueue_step(c, e.st, !k.reuse, args, e.xin, e.step, a->tie, a->tie_csr, grad, x_new);
+  if (r != CFD_OK) {                                 // (whatever was enqueued still reads the caller's buffers)
+    (void)hipStreamSynchronize(e.st);
+    return r;
+  }
+  if (losses_host) {
+    HIPCHK(hipMemcpyAsync(losses_host, losses, (size_t)e.B * 4, hipMemcpyDeviceToHost, e.st));
+    HIPCHK(hipStreamSynchronize(e.st));
+    CHK(check_saturation(c, "cfd_weg_step (latents, memories / their projections)"));
+  } else {
+    c->census_pending = true;                        // (read by the handle's next entry point: settle_deferred_census)
+    HIPCHK(hipEventRecord(c->grad.ev, e.st));
+    HIPCHK(hipStreamWaitEvent(e.caller, c->grad.ev, 0));
+  }
+  c->grad.sig = k.sig;
+  return CFD_OK;
+}
+
+// ---- developer hook: one launch of a focus kernel as cfd_weg_step launches it (include/cfdenoise_dev.h) ------------------------------
+extern "C" int cfd_test_weg_focus_rows(cfd_handle c, const float* att, int B, int NL, int L, int S, const int32_t* tok_off, const int32_t* tok_idx,
+                                       const int32_t* last_rows, int last, int nt_max, const float kernel3[3], int per_row, int small, float* workspace,
+                                       float* losses, float* max_att, float* d_att, void* stream) {
+  if (!c || !att || !tok_off || !kernel3 || !workspace || !losses || !max_att || !d_att || B < 1 || NL < 1 || L < 2)
+    return fail(CFD_E_ARG, "cfd_test_weg_focus_rows: bad argument");
+  std::vector<int32_t> lasts(last_rows ? last_rows : &last, last_rows ? last_rows + B : &last + 1);
+  lasts.resize((size_t)B, last);
+  int nt_need = 1, last_max = 0;
+  CHK(check_row_tables("cfd_test_weg_focus_rows", B, S, tok_off, tok_idx, lasts.data(), &nt_need, &last_max));
+  if (last_max > last || nt_need > nt_max) return fail(CFD_E_ARG, "cfd_test_weg_focus_rows: last = %d / nt_max = %d do not cover the rows (%d / %d)", last, nt_max, last_max, nt_need);
+  if (small && !wegrt::focus_small(L, last, nt_max)) return fail(CFD_E_ARG, "cfd_test_weg_focus_rows: the shape does not fit weg_focus_small_kernel");
+  HIPCHK(hipSetDevice(c->cfg.device));
+  hipStream_t st = (hipStream_t)stream;
+  const int n_idx = std::max(1, tok_off[B]);
+  std::vector<int32_t> tok(tok_off, tok_off + B + 1);
+  for (int t = 0; t < n_idx; ++t) tok.push_back(t < tok_off[B] ? tok_idx[t] : 0);
+  tok.insert(tok.end(), lasts.begin(), lasts.end());
+  DBuf tab;
+  CHK(tab.ensure(tok.size() * 4));
+  HIPCHK(hipMemcpy(tab.p, tok.data(), tok.size() * 4, hipMemcpyHostToDevice));
+  const int32_t *off_dev = tab.as<int32_t>(), *idx_dev = off_dev + B + 1, *last_dev = last_rows ? idx_dev + n_idx : nullptr;
+  const int grad_rows = per_row ? 1 : B;
+  if (small)
+    hipLaunchKernelGGL(weg_focus_small_kernel<>, dim3((unsigned)B), dim3(256), 0, st, att, off_dev, idx_dev, B, NL, L, S, last, kernel3[0], kernel3[1],
+                       kernel3[2], losses, max_att, d_att, last_dev, grad_rows);
+  else
+    hipLaunchKernelGGL(weg_focus_kernel<>, dim3((unsigned)B), dim3(256), 0, st, att, off_dev, idx_dev, B, NL, L, S, last, nt_max, kernel3[0], kernel3[1],
+                       kernel3[2], workspace, losses, max_att, d_att, last_dev, grad_rows);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(st));   // (tab leaves scope)
+  return CFD_OK;
 }

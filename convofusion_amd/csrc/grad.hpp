@@ -543,16 +543,22 @@ __global__ void __launch_bounds__(256) ew_f32_kernel(int op, const float* a, con
 //   tok_off [B + 1], tok_idx [tok_off[B]]  focus token indices of each sample (text positions, BOS = 0)
 //   last    exclusive end of the text slice [1, last) (eot index when normalize_eot, else S - 1)
 //   ws      workspace >= B * (3 * L * W + 3 * nt_max) 4-byte words, W = last - 1, nt_max >= tokens of any sample
+//   last_rows [B] or null: every sample its own slice [1, last_rows[b]) (cfd_weg_step: each row is its own utterance and ends at its own
+//           EOT) -- softmax, smoothing, arg-max and hinge on the sample's own width, exact zeros in d_att from last_rows[b] on; `last` is
+//           then the largest of them and sizes the samples' workspace blocks.  Null: the one slice [1, last) for all
+//   grad_rows  the samples the gradient's mean runs over: B (d mean_b losses[b] / d att, cfd_weg_eval) or 1 (d losses[b] / d att[b])
 // outputs: losses [B] (mean over the sample's tokens of max(0, 1 - max attention)), max_att [tok_off[B]],
 //          d_att [B][NL][L][S] = d(mean_b losses[b]) / d att.  One workgroup per sample; phases separated by barriers.
 template <int CFD_KI = 0>
 __global__ void __launch_bounds__(256) weg_focus_kernel(const float* att, const int* tok_off, const int* tok_idx, int B, int NL, int L, int S,
                                                         int last, int nt_max, float k00, float k01, float k11, float* ws, float* losses,
-                                                        float* max_att, float* d_att) {
+                                                        float* max_att, float* d_att, const int* last_rows, int grad_rows) {
   const int b = blockIdx.x, tid = threadIdx.x;
+  const long long block = 3 * (long long)L * (last - 1) + 3 * nt_max;   // the sample's workspace block, sized by the widest slice
+  if (last_rows) last = last_rows[b];
   const int W = last - 1;
   const long long LW = (long long)L * W;
-  float* sm = ws + (long long)b * (3 * LW + 3 * nt_max);
+  float* sm = ws + (long long)b * block;
   float* sg = sm + LW;
   float* dsm = sg + LW;
   float* tok_g = dsm + LW;            // [nt_max] upstream gradient at the token's arg-max cell
@@ -606,7 +612,7 @@ __global__ void __launch_bounds__(256) weg_focus_kernel(const float* att, const 
     max_att[t0 + t] = best;
     tok_l[t] = bl;
     tok_w[t] = w;
-    tok_g[t] = (1.0f - best > 0.f) ? -1.0f / ((float)nt * (float)B) : 0.f;
+    tok_g[t] = (1.0f - best > 0.f) ? -1.0f / ((float)nt * (float)grad_rows) : 0.f;
   }
   __syncthreads();
   if (tid == 0) {
@@ -648,7 +654,7 @@ __global__ void __launch_bounds__(256) weg_focus_kernel(const float* att, const 
   }
 }
 
-// The same objective for small maps (L * (last - 1) <= WEG_SMALL_CELLS cells, <= WEG_SMALL_TOK focus tokens per sample: the product shape is
+// The same objective for small maps (L * (last - 1) <= WEG_SMALL_CELLS cells -- with last_rows: of the widest slice --, <= WEG_SMALL_TOK focus tokens per sample: the product shape is
 // 16 x 16): the three maps live in LDS, every phase but the two row-serial ones runs one thread per cell, and the layers are read and
 // written along the key axis.  Operation for operation the arithmetic of weg_focus_kernel (same summation orders: the results are
 // bit-identical); 34 -> ~6 us at the product shape, where the general kernel's 16 active threads walk global memory serially.
@@ -657,11 +663,12 @@ __global__ void __launch_bounds__(256) weg_focus_kernel(const float* att, const 
 template <int CFD_KI = 0>
 __global__ void __launch_bounds__(256) weg_focus_small_kernel(const float* att, const int* tok_off, const int* tok_idx, int B, int NL, int L, int S,
                                                               int last, float k00, float k01, float k11, float* losses, float* max_att,
-                                                              float* d_att) {
+                                                              float* d_att, const int* last_rows, int grad_rows) {
   __shared__ float sm[WEG_SMALL_CELLS], sg[WEG_SMALL_CELLS], dsm[WEG_SMALL_CELLS];
   __shared__ float tok_g[WEG_SMALL_TOK], dots[64];
   __shared__ int tok_l[WEG_SMALL_TOK], tok_w[WEG_SMALL_TOK];
   const int b = blockIdx.x, tid = threadIdx.x;
+  if (last_rows) last = last_rows[b];   // (the sample's own slice; the caller sized the maps by the widest: L * (max last - 1) <= WEG_SMALL_CELLS)
   const int W = last - 1, LW = L * W;
   const float* ab = att + (long long)b * NL * L * S;
   // 1. layer mean over the slice [1, last) (a thread per cell), softmax over the slice (a thread per frame)
@@ -712,7 +719,7 @@ __global__ void __launch_bounds__(256) weg_focus_small_kernel(const float* att, 
     max_att[t0 + t] = best;
     tok_l[t] = bl;
     tok_w[t] = w;
-    tok_g[t] = (1.0f - best > 0.f) ? -1.0f / ((float)nt * (float)B) : 0.f;
+    tok_g[t] = (1.0f - best > 0.f) ? -1.0f / ((float)nt * (float)grad_rows) : 0.f;
     dots[t] = fmaxf(0.f, 1.0f - best);   // (hinge terms, summed in token order below)
   }
   __syncthreads();

@@ -10,21 +10,7 @@
 
 #include "guide_tables.hpp"
 
-// Row c * n_tok / L + b of the forward's input is x~[b]: x with every tied token replaced by its source's value (tie == null: x itself).
-// One thread per float4; a tie entry outside [0, n_tok) counts as free, so no table makes the kernel read out of bounds.
-template <int = 0>
-__global__ void guide_replicate_kernel(const float* __restrict__ x, const int32_t* __restrict__ tie, float* __restrict__ xin, long long n_tok,
-                                       long long total4) {
-  const long long i = blockIdx.x * 256LL + threadIdx.x;
-  if (i >= total4) return;
-  const long long tok = (i >> 5) % n_tok;
-  long long src = tok;
-  if (tie) {
-    const int v = tie[tok];
-    if (v >= 0 && v < n_tok) src = v;
-  }
-  reinterpret_cast<float4*>(xin)[i] = reinterpret_cast<const float4*>(x)[src * (CFD_LAT / 4) + (i & 31)];
-}
+// (guide_replicate_kernel, the call's first launch, lives in cfd_internal.hpp: cfd_weg_step forms its x~ with it too.)
 
 struct GuideSeedArgs {
   const float* xin;      // [n][n_tok][128]: x~, replicated (chunk 0 is read)

@@ -1,6 +1,7 @@
 // The row-tile gradient engine: the forward with saved activations (rowtile.hpp) and the reverse sweep (rowtile_bwd.hpp) of small
 // problems, and the protocol its callers follow.  Three entry points run on it, each with its own seed of the sweep:
-//   cfd_weg_eval (cfd_weg.hip, weg_rt.hpp)        at the text maps, from the word-excitation objective (FOR_WEG)
+//   cfd_weg_eval (cfd_weg.hip, weg_rt.hpp)        at the text maps, from the word-excitation objective (FOR_WEG); cfd_weg_step is the
+//                                                 same caller with a per-row objective and its own update behind the sweep
 //   cfd_denoise_vjp / cfd_denoise_vjp_mem         at the forward's output, from the caller's cotangent; _mem adds the gradient at the
 //                                                 memories (MemGrad: three launches per layer behind B5 and one at the end) (FOR_VJP)
 //   cfd_denoise_guide (guide.hpp)                 at the forward's output, from the key-pose loss (FOR_GUIDE)

@@ -385,6 +385,7 @@ struct Args {
   int last, nt_max;
   float k3[3];
   float *losses, *max_att, *grad;    // dev outputs
+  const int32_t* last_rows = nullptr;   // dev [B]: every row its own slice [1, last_rows[b]) and its own loss' gradient (cfd_weg_step; `last` is then the widest); null: one slice, batch mean
 };
 
 // One pass over the whole evaluation; with x.dry it only sizes the workspace.
@@ -452,7 +453,7 @@ static void run(Ctx& x, const Args& a) {
   float* d_att = x.alloc((size_t)B * NL * L * St);
   if (!x.skip())
     hipLaunchKernelGGL(weg_focus_kernel<>, dim3((unsigned)B), dim3(256), 0, x.st, att, a.tok_off, a.tok_idx, B, NL, L, St, a.last, a.nt_max, a.k3[0],
-                       a.k3[1], a.k3[2], ws, a.losses, a.max_att, d_att);
+                       a.k3[1], a.k3[2], ws, a.losses, a.max_att, d_att, (const int*)nullptr, B);
   // ---- reverse sweep
   float* g = x.alloc((size_t)rows * D);                          // gradient at the current layer's output
   float* dt2 = x.alloc((size_t)rows * D);

@@ -26,7 +26,7 @@ import torch
 
 from .distributed import shard_cfg_batch, shard_modality_weights
 from .edit import _decode, loop_to_vae
-from .sampler import CFG_CHUNKS, check_operands, sample, sample_with_keyframes, sample_with_pose_keyframes
+from .sampler import CFG_CHUNKS, check_operands, sample, sample_with_keyframes, sample_with_pose_keyframes, sample_with_weg
 
 WINDOW_FRAMES = 128     # unbounded_synthesis.py:272 (motion_len)
 
@@ -85,7 +85,7 @@ def stitch_tokens(windows):
 def synthesize_latents(model_or_denoiser, scheduler, encoder_hidden_states, cond_masks=None, *, n_utterances, n_windows, L=16,
                        num_inference_steps=1000, guidance_scale=7.5, guidance_chunks=CFG_CHUNKS, eta=0.0, seed=0, max_rows=None,
                        carry=None, skip_zero_weight_chunks=True, operands=None, modality_weights=None, keyframes=None,
-                       pose_keyframes=None, vae=None):
+                       pose_keyframes=None, vae=None, focus_indices=None, weg_parameters=None, carry_scale_range=False):
     """The latents of U = n_utterances motions of W = n_windows half-overlapping windows each.  ``model_or_denoiser``: the HIP ``Denoiser``
     or an object with a ``.denoiser``.  encoder_hidden_states / cond_masks: the guidance batch of ``sample`` for B = U * W rows in the
     order u * W + w (chunk-major, G * B rows per memory), every row conditioned on its own window of the audio and text as the caller
@@ -103,6 +103,12 @@ def synthesize_latents(model_or_denoiser, scheduler, encoder_hidden_states, cond
     feature_mask [189] or None, step_size, guided_iterations) in window rows (``pose_keyframes_for_windows``) -- frame-accurate key poses
     (``sampler.sample_with_pose_keyframes``): every run whose rows hold a selected frame goes through that loop with the run's tie and kept
     tokens.  Not together with ``keyframes``.  None: exactly today's calls.
+    focus_indices (optional, with ``weg_parameters``): U * W lists of text positions in window rows, each in its own window's text --
+    word-excitation guidance per window (``sampler.sample_with_weg(per_row=True)``): every run whose rows hold a focus token goes
+    through that loop with the run's tie and kept tokens, every window its own utterance (its own text slice, loss, refinement rounds);
+    a focus word's gradient at a tied token pulls its source.  ``carry_scale_range`` as in that loop (one table per run).  Not together
+    with ``keyframes`` or ``pose_keyframes``; a run beyond the row-tile gradient engine's rows raises NotImplementedError: pass
+    ``max_rows``.  None, or all lists empty: exactly today's calls.
     Returns (windows [U, W, L, 128], sequence [U, (W + 1) * L / 2, 128] = ``stitch_tokens(windows)``)."""
     denoiser = getattr(model_or_denoiser, "denoiser", model_or_denoiser)
     U, W, L = int(n_utterances), int(n_windows), int(L)
@@ -137,8 +143,28 @@ def synthesize_latents(model_or_denoiser, scheduler, encoder_hidden_states, cond
             raise ValueError(f"pose_keyframes: target must be [U * W, 8 L, nfeats] = [{B}, {8 * L}, nfeats]")
         if not isinstance(pk_frames, torch.Tensor) or tuple(pk_frames.shape) != (B, 8 * L):
             raise ValueError(f"pose_keyframes: frame_mask must be [U * W, 8 L] = [{B}, {8 * L}]")
+    if focus_indices is not None:
+        if keyframes is not None or pose_keyframes is not None:
+            raise ValueError("focus_indices and keyframes / pose_keyframes cannot be combined: one guided update serves one loss")
+        if len(focus_indices) != B:
+            raise ValueError(f"focus_indices must be U * W = {B} lists of text positions in window rows, not {len(focus_indices)}")
+        focus_indices = [[int(i) for i in row] for row in focus_indices]
+        if not any(focus_indices):
+            focus_indices = None
+        elif weg_parameters is None:
+            raise ValueError("focus_indices needs weg_parameters= (scale_factor, scale_range, max_iter_to_alter, thresholds, "
+                             "max_refinement_steps)")
+    groups = window_groups(U, W, max_rows)
+    if focus_indices is not None:
+        from .weg import step_refusal
+        for start, stop in groups:
+            why = step_refusal(stop - start, L, [int(m.shape[1]) for m in encoder_hidden_states]) if any(focus_indices[start:stop]) else None
+            if why is not None:
+                raise NotImplementedError(f"synthesize_latents: the run of window rows {start} .. {stop - 1} holds focus words, and per-row "
+                                          f"word-excitation guidance runs on the row-tile gradient engine only: {why}; pass max_rows= to "
+                                          "split the windows into smaller runs")
     out = torch.empty((B, L, 128), dtype=torch.float32, device=dev)
-    for start, stop in window_groups(U, W, max_rows):
+    for start, stop in groups:
         n = stop - start
         tie, carried = group_ties(start, stop, W, L)
         src = keep = None
@@ -164,6 +190,9 @@ def synthesize_latents(model_or_denoiser, scheduler, encoder_hidden_states, cond
         elif pose_keyframes is not None and bool((pk_frames[start:stop] != 0).any()):
             out[start:stop] = sample_with_pose_keyframes(denoiser, scheduler, enc, masks, vae, pk_target[start:stop], pk_frames[start:stop],
                                                          pk_step, feature_mask=pk_features, guided_iterations=pk_iterations, **run_kw)
+        elif focus_indices is not None and any(focus_indices[start:stop]):
+            out[start:stop] = sample_with_weg(denoiser, scheduler, enc, masks, focus_indices[start:stop], weg_parameters, per_row=True,
+                                              carry_scale_range=carry_scale_range, **run_kw)
         else:
             out[start:stop] = sample(denoiser, scheduler, enc, masks, **run_kw)
     windows = out.reshape(U, W, L, 128)
@@ -218,13 +247,15 @@ def stitch_frames(feats):
 
 
 def synthesize_motion(model, encoder_hidden_states, cond_masks=None, *, n_utterances, n_windows, seed=0, max_rows=None, carry=None,
-                      modality_weights=None, operands=None, fused_decode=False, keyframes=None, pose_keyframes=None):
+                      modality_weights=None, operands=None, fused_decode=False, keyframes=None, pose_keyframes=None, focus_indices=None,
+                      weg_parameters=None, carry_scale_range=False):
     """Long-form motions from a Convofusion-like ``model`` (reads vae / denoiser / scheduler / cfg / guidance_scale / clf_guidance_drops /
     do_classifier_free_guidance as ``edit.edit_motion`` does; ``model.vae`` decodes on the HIP path): ``synthesize_latents``, one HIP
     ``decode`` of all U * W windows (fused_decode=True: ``decode(..., fused=True)``, one forward-only cfd_vae_decode on a workspace of 1.2 MB
     per window), the reference's frame stitching (``stitch_frames``) in torch on the device.  keyframes: soft key poses in latent
     tokens, as in ``synthesize_latents``; pose_keyframes: frame-accurate key poses in window rows (``pose_keyframes_for_windows``), decoded
-    through ``model.vae``.
+    through ``model.vae``.  focus_indices / weg_parameters / carry_scale_range: word-excitation guidance per window, as in
+    ``synthesize_latents`` (weg_parameters None: ``model.weg_parameters``).
     Returns (features [U, (W + 1) * 64, nfeats], windows [U, W, L, 128], token sequence [U, (W + 1) * L / 2, 128])."""
     if not model.do_classifier_free_guidance:
         raise NameError("guidance_bs_mulitplier: the reference loop requires classifier-free guidance")
@@ -242,6 +273,8 @@ def synthesize_motion(model, encoder_hidden_states, cond_masks=None, *, n_uttera
         guidance_chunks=model.clf_guidance_drops + 1, eta=eta, seed=seed, max_rows=max_rows, carry=carry,
         operands=getattr(model, "_cfd_operands", None) if operands is None else operands, modality_weights=modality_weights,
         **({} if keyframes is None else dict(keyframes=keyframes)),
-        **({} if pose_keyframes is None else dict(pose_keyframes=pose_keyframes, vae=model.vae)))
+        **({} if pose_keyframes is None else dict(pose_keyframes=pose_keyframes, vae=model.vae)),
+        **({} if focus_indices is None else dict(focus_indices=focus_indices, carry_scale_range=carry_scale_range,
+                                                 weg_parameters=model.weg_parameters if weg_parameters is None else weg_parameters)))
     feats = _decode(model.vae, loop_to_vae(windows.reshape(U * W, L, 128)), [WINDOW_FRAMES] * (U * W), fused_decode)
     return stitch_frames(feats.reshape(U, W, WINDOW_FRAMES, feats.shape[-1])), windows, tokens

@@ -212,6 +212,23 @@ def check_keyframe_guidance(scheduler, *, noise_space=None, anchor_trajectory=No
     _check_guided_loop(scheduler, "sample_with_keyframes", "the key-pose guided loop", noise_space, anchor_trajectory, trajectory)
 
 
+def check_weg_rows(per_row, tie, B, L, S):
+    """What ``sampler.sample_with_weg`` asks of ``per_row`` and ``tie``, before any device work.  ``tie`` without ``per_row=True`` is
+    refused (ValueError naming the keyword): the reference's loop has one loss for the batch and nothing that folds a tied token's
+    gradient onto its source.  With ``per_row=True`` the B rows of L tokens against memory lengths ``S`` must fit the row-tile gradient
+    engine (``weg.step_refusal``), NotImplementedError otherwise; the table itself is ``check_tie``'s to refuse when the run opens."""
+    if not per_row:
+        if tie is not None:
+            raise ValueError("sample_with_weg: tie= needs per_row=True -- the batch-of-one loop (per_row=False) writes its update over the "
+                             "tied tokens; the per-row loop folds their gradients onto their sources")
+        return
+    from .weg import step_refusal
+    why = step_refusal(B, L, S)
+    if why is not None:
+        raise NotImplementedError(f"sample_with_weg(per_row=True): per-row word-excitation guidance runs on the row-tile gradient engine "
+                                  f"only: {why}")
+
+
 _AUTO_RUN = object()   # the first attempt of an "auto" loop (``_with_auto_operands``): a guarded run, not another "auto" loop
 
 

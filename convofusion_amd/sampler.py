@@ -16,7 +16,7 @@ import torch
 from . import _lib
 from .denoiser import Denoiser
 # the pure half of opening a run: the argument checks of every kind and the kind of a run (importable from here as before)
-from .run_kind import (_AUTO_RUN, RunKind, check_anchor, check_edit, check_inversion, check_keyframe_guidance,  # noqa: F401
+from .run_kind import (_AUTO_RUN, RunKind, check_anchor, check_edit, check_inversion, check_keyframe_guidance, check_weg_rows,  # noqa: F401
                        check_loss_guidance, check_pose_keyframes, check_noise_space, check_operands, check_tie, edit_first_iteration, refuse_sample_prediction, resolve_run_kind,
                        sample_prediction)
 
@@ -1000,7 +1000,8 @@ def _loop_from_model(model, encoder_hidden_states, cond_masks, preseq, focus_ind
 
 
 def sample_with_weg(denoiser, scheduler, encoder_hidden_states, cond_masks, focus_indices, weg_parameters, *, B, L=16,
-                    num_inference_steps=1000, guidance_chunks=CFG_CHUNKS, return_attention=False, carry_scale_range=True, **kw):
+                    num_inference_steps=1000, guidance_chunks=CFG_CHUNKS, return_attention=False, carry_scale_range=True, per_row=False,
+                    tie=None, weg_stats=None, **kw):
     """The loop with its word-excitation-guidance branch (convofusion.py:437-496): before iteration i the latents are
     moved down the gradient of the attention-focus objective of the text-only chunk (``convofusion_amd.weg``), then the
     captured guided step runs as usual.  ``weg_parameters``: scale_factor, scale_range, max_iter_to_alter, thresholds,
@@ -1009,7 +1010,15 @@ def sample_with_weg(denoiser, scheduler, encoder_hidden_states, cond_masks, focu
     size stays ~scale_factor after iteration 0); False is the rollout, which takes a fresh 1.0 -> 0.5 table every
     iteration (unbounded_synthesis.py:82-89).  See ``weg.scale_range_schedule``.  ``operands="auto"``, ``modality_weights`` and the edit
     arguments ``source_latents`` / ``keep_mask`` / ``strength`` (in ``kw``): as in ``sample``; an edit's masked overwrite goes in before the
-    WEG update (``run.inpaint``), and the WEG schedule is indexed by the full table's iteration."""
+    WEG update (``run.inpaint``), and the WEG schedule is indexed by the full table's iteration.
+    ``per_row=True``: every row is its own utterance (``weg.weg_update_rows``, cfd_weg_step) -- its own text slice up to its own EOT,
+    its own loss, thresholds test, refinement rounds and closing update, exactly what the row gets alone with B = 1; B >= 1, and the
+    run may be tied (``tie``, ``longform``): the objective is evaluated with tied tokens replaced by their sources, their gradients
+    are folded onto the sources, and the written latents satisfy the tie.  The rows must fit the row-tile gradient engine
+    (``weg.step_refusal``).  ``per_row=False`` is the reference's loop: one loss for the batch, B = 1 (its EOT normalisation asserts
+    it); it takes no ``tie``.  ``carry_scale_range`` is one table for the run either way.  ``weg_stats`` (per_row): a list that
+    receives, per guided iteration, dict(i, losses, rounds, calls) -- the rows' final losses, their refinement rounds and the
+    cfd_weg_step calls of the iteration."""
     if check_operands(kw.get("operands")) == "auto":
         args = dict(locals())
         rest = args.pop("kw")
@@ -1024,6 +1033,7 @@ def sample_with_weg(denoiser, scheduler, encoder_hidden_states, cond_masks, focu
                                   "with DPMSolverMultistepScheduler it has no reference trajectory to be checked against -- use sample() "
                                   "without focus_indices")
     refuse_sample_prediction(scheduler, "sample_with_weg: the word-excitation-guidance loop (focus_indices) runs")
+    check_weg_rows(per_row, tie, B, L, [int(m.shape[1]) for m in encoder_hidden_states] if per_row else None)
     from . import weg
     G = guidance_chunks
     scheduler.set_timesteps(num_inference_steps)
@@ -1033,6 +1043,12 @@ def sample_with_weg(denoiser, scheduler, encoder_hidden_states, cond_masks, focu
     n_full = len(scheduler.timestep_table(num_inference_steps)[1])      # (an edit run starts at iteration k0 of the table: i counts from there)
     carry = [weg_parameters["scale_range"][0], weg_parameters["scale_range"][1]] if carry_scale_range else None   # :395
     guided = 0                            # evaluations of the objective so far (their conditioning never changes inside the loop)
+    if per_row:
+        from .denoiser import tie_csr
+        dev = encoder_hidden_states[0].device
+        tie_dev = None if tie is None else tie.detach().to(device=dev, dtype=torch.int32).contiguous()
+        csr = None if tie_dev is None else tie_csr(tie_dev)
+        text_states = [m.detach().contiguous() for m in text_states]
 
     def update(i, t, latents):
         nonlocal guided
@@ -1043,14 +1059,22 @@ def sample_with_weg(denoiser, scheduler, encoder_hidden_states, cond_masks, focu
             if carry is not None:   # the skipped iteration still re-assigns the table (convofusion.py:442-444)
                 weg.scale_range_schedule(weg_parameters, n_full, i, carry)
             return None
-        lat, _ = weg.weg_update(denoiser, latents(), i, t, text_states, text_masks, focus_indices, weg_parameters, n_full,
-                                scale_carry=carry, same_memories=guided > 0)
+        if per_row:
+            st = {}
+            lat, losses = weg.weg_update_rows(denoiser, latents(), i, t, text_states, text_masks, focus_indices, weg_parameters, n_full,
+                                              scale_carry=carry, same_memories=guided > 0, tie=tie_dev, csr=csr, stats=st)
+            if weg_stats is not None:
+                weg_stats.append(dict(i=i, losses=[float(v) for v in losses], **st))
+        else:
+            lat, _ = weg.weg_update(denoiser, latents(), i, t, text_states, text_masks, focus_indices, weg_parameters, n_full,
+                                    scale_carry=carry, same_memories=guided > 0)
         guided += 1
         return lat
 
     run = _open_run(denoiser, scheduler, encoder_hidden_states, cond_masks, B, L, num_inference_steps, return_attention in ("all", "auto"),
-                    guidance_chunks=G, **kw)
-    return _drive(run, denoiser, encoder_hidden_states, cond_masks, G, kw.get("row_maps"), return_attention, update)
+                    guidance_chunks=G, **({} if tie is None else dict(tie=tie)), **kw)
+    write = (lambda new: run.write(new, satisfies_tie=True)) if per_row and tie is not None else None
+    return _drive(run, denoiser, encoder_hidden_states, cond_masks, G, kw.get("row_maps"), return_attention, update, write)
 
 
 def guided_chunks(weights):

@@ -18,6 +18,10 @@ needs no key / value gradients for the five cross-attentions and no weight gradi
 Public names follow the reference module (``aggregate_attentions`` + ``get_max_attention_at_indices`` +
 ``compute_attention_focus_loss`` are one fused kernel: ``attention_focus_loss``; ``update_latent`` takes the gradient
 instead of a graph) and the loop branch is ``weg_update`` / ``iterative_refinement_step``.
+
+The reference serves one utterance per call.  ``step_rows`` / ``loss_and_grad_rows`` / ``weg_update_rows`` (``cfd_weg_step``) treat every
+row of a batch -- or every window of a tied long-form run -- as its own utterance: its own text slice, loss, refinement rounds and update,
+with the gate of a round decided on the host (``row_steps``, ``refine_rows``) and the gated, tied update done by the call itself.
 """
 import ctypes as C
 import functools
@@ -490,3 +494,175 @@ def weg_update(denoiser, latents, i, t, text_only_states, text_only_masks, focus
     if i < weg_parameters["max_iter_to_alter"] and loss != 0:                                                     # :490-495
         latents = update_latent(latents, grad, step_size, denoiser)
     return latents, float(loss)
+
+
+# ----------------------------------------------------------------------------- every row its own utterance (cfd_weg_step)
+def step_refusal(B, L, S, max_rows=None):
+    """Why ``cfd_weg_step`` cannot take ``B`` rows of ``L`` tokens against memory lengths ``S`` (five ints), or None when it can: the
+    call runs on the row-tile gradient engine only, so these are ``denoiser.vjp_refusal``'s limits.  Pure: no library, no device."""
+    from .denoiser import vjp_refusal
+    return vjp_refusal(B, L, S, max_rows=max_rows)
+
+
+def _row_tables(B, S, focus_indices, eot_indices):
+    """(last_rows int32 [B], offsets int32 [B + 1], flat indices int32) of a batch whose row b is its own utterance: its text slice is
+    [1, eot_b) and its focus indices lie inside it.  ValueError for a slice shorter than 2, IndexError naming the row for an index."""
+    if len(focus_indices) != B:
+        raise ValueError("focus_indices needs one list per batch row")
+    if len(eot_indices) != B:
+        raise ValueError("eot_indices needs one entry per batch row")
+    lasts = np.array([int(e) + (S if int(e) < 0 else 0) for e in eot_indices], dtype=np.int32)
+    for b, s in enumerate(focus_indices):
+        if lasts[b] - 1 < 2 or lasts[b] > S:
+            raise ValueError(f"row {b}: text slice [1, {lasts[b]}) of {S} keys is too short for the 3x3 reflect-padded smoothing")
+        for i in s:
+            if not 1 <= int(i) <= lasts[b] - 1:
+                raise IndexError(f"row {b}: focus index {i} is outside the row's text slice [1, {lasts[b]})")
+    off = np.cumsum([0] + [len(s) for s in focus_indices]).astype(np.int32)
+    flat = np.array([int(i) for s in focus_indices for i in s] or [0], dtype=np.int32)
+    return lasts, off, flat
+
+
+def step_rows(denoiser, latents, timestep, encoder_hidden_states, cond_masks, focus_indices, row_step=None, *, eot_indices=None, tie=None,
+              csr=None, same_conditioning=False, want_grad=True, x_new=None):
+    """One ``cfd_weg_step``: every row of ``latents`` [B, L, 128] is its own utterance -- its own text slice [1, eot_b), its own loss
+    and the gradient of that loss alone -- evaluated at x~ (``tie`` [B, L] int32 with ``csr`` = ``denoiser.tie_csr(tie)``: x with every
+    tied token replaced by its source) and moved by ``row_step`` (B floats; None: an evaluation, nothing moves):
+    x_new[b] = x~[b] - row_step[b] * g[b], with the fold of tied tokens' gradients onto their sources (include/cfdenoise.h).
+    ``x_new``: a tensor to write into (it may be ``latents``); None with ``row_step`` None: not wanted.  ``same_conditioning``: as in
+    ``loss_and_grad``.  Returns (losses float32 numpy [B] -- the call has waited --, max_attention_at_indices, grad or None, x_new or None);
+    grad is the folded, unstepped gradient with zeros at tied tokens."""
+    if not isinstance(denoiser, Denoiser):
+        raise TypeError("denoiser must be a convofusion_amd.denoiser.Denoiser")
+    B, L, _ = latents.shape
+    S = [int(m.shape[1]) for m in encoder_hidden_states]
+    why = step_refusal(B, L, S)
+    if why is not None:
+        raise NotImplementedError(f"per-row word-excitation guidance (cfd_weg_step) runs on the row-tile gradient engine only: {why}")
+    dev = latents.device
+    if dev.type != "cuda":
+        raise RuntimeError("WEG runs on an MI355X only (tensors must be on 'cuda'); no CPU fallback")
+    if encoder_hidden_states[0].shape[0] != B:
+        raise ValueError("the conditioning tuple must have one row per latent row (the text-only chunk)")
+    if eot_indices is None:
+        eot_indices = (torch.argmax(cond_masks["tlsn"].int(), dim=1) - 1).tolist()         # :460, per row
+    lasts, off, flat = _row_tables(B, S[TLSN], focus_indices, eot_indices)
+    steps = None
+    if row_step is not None:
+        steps = np.ascontiguousarray(np.asarray(row_step, dtype=np.float32).reshape(-1))
+        if steps.size != B:
+            raise ValueError(f"row_step needs {B} entries")
+    if tie is not None and csr is None:
+        from .denoiser import tie_csr
+        csr = tie_csr(tie)
+    lat = latents.detach().to(torch.float32).contiguous()
+    handle = denoiser.engine(dev, mem_len=max(S))
+    marr, keep = Denoiser.pack_memories(encoder_hidden_states, cond_masks)
+    a = _lib.WegRowsArgs()
+    a.B, a.L, a.timestep, a.latents, a.mem = B, L, int(timestep), lat.data_ptr(), marr
+    a.tok_off, a.tok_idx, a.last_rows = off.ctypes.data, flat.ctypes.data, lasts.ctypes.data
+    a.kernel3 = (C.c_float * 3)(*gaussian_kernel3())
+    a.row_step = steps.ctypes.data if steps is not None else None
+    if tie is not None:
+        tie_dev = tie.detach().to(device=dev, dtype=torch.int32).contiguous()
+        csr_dev = csr.detach().to(device=dev, dtype=torch.int32).contiguous()
+        if tuple(tie_dev.shape) != (B, L) or csr_dev.numel() != 2 * B * L + 1:
+            raise ValueError(f"tie must be [B, L] = [{B}, {L}] and csr its inverse table of {2 * B * L + 1} entries")
+        a.tie, a.tie_csr = tie_dev.data_ptr(), csr_dev.data_ptr()
+        keep += [tie_dev, csr_dev]
+    a.reuse_memory_side = 2 if same_conditioning == "memories" else (1 if same_conditioning else 0)
+    losses = torch.empty(B, dtype=torch.float32, device=dev)
+    max_att = torch.empty(max(1, int(off[-1])), dtype=torch.float32, device=dev)
+    grad = torch.empty_like(lat) if want_grad else None
+    given = x_new is not None
+    if given and (x_new.dtype != torch.float32 or not x_new.is_contiguous() or tuple(x_new.shape) != (B, L, 128) or x_new.device != dev):
+        raise ValueError(f"x_new must be a contiguous float32 tensor [{B}, {L}, 128] on the latents' device")
+    if not given and steps is not None:
+        x_new = torch.empty_like(lat)
+    host = np.empty(B, dtype=np.float32)
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().cfd_weg_step(handle, C.byref(a), ptr(losses), ptr(max_att), ptr(grad), ptr(x_new), host.ctypes.data,
+                                            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    if given and not x_new.is_inference():
+        _lib.wrote(x_new)
+    del keep
+    mx = [[max_att[off[b] + k] for k in range(len(focus_indices[b]))] for b in range(B)]
+    return host, mx, grad, x_new
+
+
+def loss_and_grad_rows(denoiser, latents, timestep, encoder_hidden_states, cond_masks, focus_indices, eot_indices=None, tie=None, csr=None,
+                       same_conditioning=False):
+    """``loss_and_grad`` for B rows that are each their own utterance (one evaluating ``step_rows``): losses[b] and
+    d losses[b] / d latents[b] are what ``loss_and_grad`` gives row b alone with B = 1 and normalize_eot=True.
+    Returns (losses float32 numpy [B], max_attention_at_indices, grad [B, L, 128])."""
+    losses, mx, grad, _ = step_rows(denoiser, latents, timestep, encoder_hidden_states, cond_masks, focus_indices, None, eot_indices=eot_indices,
+                                    tie=tie, csr=csr, same_conditioning=same_conditioning)
+    return losses, mx, grad
+
+
+def row_steps(losses, entered, rounds, target, max_refinement_steps, step):
+    """The gate of one refinement round (``iterative_refinement_step`` per row, in lock step).  ``losses``: every row's loss from the
+    previous evaluation; ``entered``: the rows that went into refinement at this threshold iteration; ``rounds``: the rounds each row
+    has taken.  Row b is in refinement -- and takes ``step`` this round -- while it entered, that loss exceeds ``target`` and it has
+    taken fewer than ``max_refinement_steps`` rounds; every other row gets step 0 and is only evaluated.
+    Returns (row_step list of B floats, in_refinement list of B bools).  Pure: no library, no device."""
+    active = [bool(e) and float(l) > target and int(r) < int(max_refinement_steps) for l, e, r in zip(losses, entered, rounds)]
+    return [float(step) if a else 0.0 for a in active], active
+
+
+def refine_rows(step_call, losses, threshold, step, max_refinement_steps, closing_step):
+    """The WEG branch of a threshold iteration for B rows behind its first evaluation (``losses``), as a sequence of
+    ``step_call(row_step) -> losses``: each call evaluates every row at the current latents and then moves row b down its own gradient
+    by row_step[b] (``step_rows``).  Row b enters refinement if losses[b] > 1 - threshold; rounds follow ``row_steps`` until no row is
+    in refinement; one last call evaluates the final latents (the reference's closing evaluation) and applies ``closing_step`` to every
+    row -- the closing update ``i < max_iter_to_alter and loss != 0``: a row whose loss is 0 has gradient 0 and is not moved.  Without
+    any row in refinement and with closing_step 0 nothing is called.  The reference's ``if loss != 0`` inside a round is implied the
+    same way.  Returns (losses of the last evaluation, rounds per row).  Pure: the device is behind ``step_call``."""
+    B = len(losses)
+    target = max(0.0, 1.0 - threshold)
+    entered = [float(l) > 1.0 - threshold for l in losses]
+    rounds = [0] * B
+    while True:
+        steps, active = row_steps(losses, entered, rounds, target, max_refinement_steps, step)
+        if not any(active):
+            break
+        losses = step_call(steps)
+        rounds = [r + int(a) for r, a in zip(rounds, active)]
+    if any(entered) or closing_step != 0:
+        losses = step_call([float(closing_step)] * B)
+    return losses, rounds
+
+
+def weg_update_rows(denoiser, latents, i, t, text_only_states, text_only_masks, focus_indices, weg_parameters, num_steps, scale_carry=None,
+                    same_memories=False, tie=None, csr=None, stats=None):
+    """``weg_update`` for B rows that are each their own utterance: the WEG branch of loop iteration ``i`` applied per row, every row
+    with its own text slice, loss, thresholds test, refinement rounds and closing update, as ``cfd_weg_step`` calls -- one per
+    ordinary iteration (evaluation and closing update fused), at a threshold iteration one evaluation, the rounds and the closing call
+    (``refine_rows``).  ``tie`` / ``csr``: the run's tie table and its inverse; the returned latents then satisfy the tie.
+    ``stats``: a dict that receives ``rounds`` (per row) and ``calls`` of this iteration.  Returns (latents, losses numpy [B])."""
+    scale_range = scale_range_schedule(weg_parameters, num_steps, i, scale_carry)
+    eot = (torch.argmax(text_only_masks["tlsn"].int(), dim=1) - 1).tolist()
+    step_size = float(weg_parameters["scale_factor"] * np.sqrt(scale_range[i]))
+    closing = step_size if i < weg_parameters["max_iter_to_alter"] else 0.0
+    x = latents.detach().to(torch.float32).contiguous()
+    if tie is not None or x.data_ptr() == latents.data_ptr():
+        x = x.clone()     # (updated in place below; with a tie the first call writes x~ over it)
+    calls = 0
+
+    def step_call(row_step):
+        nonlocal calls
+        same = True if calls else ("memories" if same_memories else False)
+        losses, _, _, _ = step_rows(denoiser, x, t, text_only_states, text_only_masks, focus_indices, row_step, eot_indices=eot, tie=tie, csr=csr,
+                                    same_conditioning=same, want_grad=False, x_new=x)
+        calls += 1
+        return losses
+    thresholds = weg_parameters["thresholds"]
+    B = x.shape[0]
+    if i not in thresholds:
+        losses, rounds = step_call([closing] * B), [0] * B
+    else:
+        losses, rounds = refine_rows(step_call, step_call([0.0] * B), thresholds[i], step_size, weg_parameters["max_refinement_steps"], closing)
+    if stats is not None:
+        stats["rounds"], stats["calls"] = rounds, calls
+    return x, np.asarray(losses, dtype=np.float32)

@@ -543,6 +543,44 @@ typedef struct {
                                        evaluation selects its row; larger problems treat a new timestep like 0. */
 } cfd_weg_args;
 int cfd_weg_eval(cfd_handle h, const cfd_weg_args* args, float* losses, float* max_att, float* grad, float* loss_host, void* stream);
+/* One evaluation AND update of word-excitation guidance for B rows that are each their own utterance -- a batch, or the windows of a
+ * tied long-form run -- as one device call: row b gets exactly what cfd_weg_eval + weg.update_latent give it alone with B = 1.
+ *   text slice   row b uses [1, last_rows[b]) (its own EOT): softmax, the 3x3 reflect-padded smoothing, arg-max and hinge run on the
+ *                row's own width; in the maps' gradient key 0 and the keys from last_rows[b] on receive exact zeros.
+ *   objective    losses[b] as cfd_weg_eval forms it; the gradient is d losses[b] / d x[b] (upstream factor -1 / nt_b, no 1 / B).  A
+ *                row without focus tokens has loss 0 and gradient 0.
+ *   update       x_new[b] = x[b] - row_step[b] * g[b]: the host gates a row by giving it its step or 0 (weg.row_steps).
+ *   tie          (cfd_guide_args' tie / tie_csr) the objective is evaluated at x~, x with every tied token replaced by its source; a
+ *                tied token's gradient is folded onto its source, weighted by the step of the row the TIED token sits in (the row
+ *                whose loss it serves); a tied token of x_new takes its source's new value bit for bit, so x_new satisfies the tie:
+ *                  grad[s]  = g~[s] + sum_t g~[t]                                 over the tokens t tied to s, ascending (tie_csr)
+ *                  x_new[s] = x~[s] - (row_step[r(s)] g~[s] + sum_t row_step[r(t)] g~[t])
+ * Launches, eagerly on the handle's own stream behind `stream` (no captured graph): x~ (only with a tie), the time tables and memory
+ * side (unless reused), cfd_weg_eval's forward with saved activations, the per-row objective, its reverse sweep, the gated update.
+ * Float32 throughout, no atomics: two calls on the same inputs return the same bits.
+ *   losses dev [B]; max_att dev [tok_off[B]] (>= 1 float); grad dev [B][L][128] or NULL: the folded, unstepped gradient, tied tokens 0;
+ *   x_new dev [B][L][128] or NULL (may alias latents); losses_host HOST [B] or NULL: when given the call waits and fills it (the loop
+ *   branches per row on it), otherwise `stream` continues behind the call and the census is read by the handle's next entry point.
+ * reuse_memory_side: cfd_weg_args' meaning; cfd_weg_eval and this call reuse what either left.
+ * Limits: the row-tile gradient engine only -- CFD_E_ARG names the limit exceeded (L <= 32, B * L <= 700 token rows
+ * (CFD_ROWTILE_MAX_ROWS), padded keys <= 1024), before any launch; CFD_E_SHAPE for a row whose slice is shorter than 2; CFD_E_ARG for a
+ * focus index outside its row's slice, naming the row; a tie only with its tie_csr. */
+typedef struct {
+  int B, L;
+  int timestep;
+  const float* latents;          /* dev [B][L][128] */
+  cfd_memory mem[CFD_NUM_MEM];   /* as in cfd_weg_args: U == B, row_map NULL */
+  const int32_t* tok_off;        /* HOST [B + 1] offsets into tok_idx */
+  const int32_t* tok_idx;        /* HOST focus token positions of row b (text positions, BOS = 0), each in [1, last_rows[b]) */
+  const int32_t* last_rows;      /* HOST [B]: row b's text slice is [1, last_rows[b]) */
+  float kernel3[3];              /* as in cfd_weg_args */
+  const float* row_step;         /* HOST [B] or NULL (every step 0: an evaluation; x_new is then x~) */
+  const int32_t* tie;            /* dev [B][L] or NULL, as in cfd_guide_args */
+  const int32_t* tie_csr;        /* dev [2 B L + 1] (cfd_guide_tie_csr); NULL without a tie */
+  int reuse_memory_side;         /* 0 / 1 / 2, as in cfd_weg_args */
+} cfd_weg_rows_args;
+int cfd_weg_step(cfd_handle h, const cfd_weg_rows_args* args, float* losses, float* max_att, float* grad, float* x_new, float* losses_host,
+                 void* stream);
 /* The vector-Jacobian product of one denoiser forward with respect to its sample: replaces
  *   sample.requires_grad_(True); out, _ = denoiser(sample, t, encoder_hidden_states, ...); torch.autograd.grad(out, sample, d_out)
  * for any cotangent d_out at the output (cfd_weg_eval's gradient is hard-wired to the attention-focus objective of the text maps).

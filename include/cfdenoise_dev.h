@@ -120,6 +120,17 @@ int cfd_debug_read(cfd_handle h, const char* what, float* dst_dev, size_t numel)
  * not written yet must still hold it.  Needs a completed row-tile evaluation (the workspace exists from then on). */
 int cfd_debug_weg_stop(cfd_handle h, int stop);
 int cfd_debug_weg_fill(cfd_handle h, float value);
+/* Test hook: ONE launch of a focus kernel as cfd_weg_step launches it -- cfd_weg_focus's arguments, except that the focus tables are
+ * HOST (they are checked against every row's slice and staged by the hook), plus
+ *   last_rows  HOST [B] or NULL: every row its own slice [1, last_rows[b]) (each checked: 3 <= last_rows[b] <= last); `last` is the
+ *              widest slice, which sizes the workspace blocks and decides the small kernel's eligibility.  NULL: the one slice [1, last)
+ *   per_row    1: d_att = d losses[b] / d att[b];  0: d mean_b losses[b] / d att (cfd_weg_focus's scale)
+ *   small      1: weg_focus_small_kernel (CFD_E_ARG unless L * (last - 1) <= 1024, nt_max <= 64, L <= 64);  0: weg_focus_kernel
+ * workspace dev >= B * (3 * L * (last - 1) + 3 * nt_max) floats (unused by the small kernel, still required).  With last_rows NULL and
+ * per_row 0 both kernels return cfd_weg_focus's bits.  The call waits for the launch. */
+int cfd_test_weg_focus_rows(cfd_handle h, const float* att, int B, int NL, int L, int S, const int32_t* tok_off, const int32_t* tok_idx,
+                            const int32_t* last_rows, int last, int nt_max, const float kernel3[3], int per_row, int small, float* workspace,
+                            float* losses, float* max_att, float* d_att, void* stream);
 /* Test hook (no handle): the device buffers the library holds in this process, over all handles and calls -- how many, and their bytes as asked
  * for.  Every buffer belongs to a handle or to one call: a reading is back at an earlier one once the handles created since are destroyed. */
 int cfd_debug_live_buffers(long long* count, long long* bytes);

@@ -29,7 +29,7 @@ SYMBOLS = [
     "cfd_test_picard_sweep", "cfd_debug_weg_stop", "cfd_debug_weg_fill", "cfd_scheduler_step_pred", "cfd_dpmsolver_step_pred",
     "cfd_debug_forward_operands", "cfd_denoise_vjp", "cfd_debug_live_buffers", "cfd_vae_decode_vjp", "cfd_denoise_vjp_mem",
     "cfd_vae_decode", "cfd_vae_decode_sweep", "cfd_vae_decode_ticket", "cfd_debug_vae_workspace", "cfd_denoise_guide", "cfd_guide_tie_csr",
-    "cfd_denoise_guide_pose", "cfd_weg_step", "cfd_test_weg_focus_rows",
+    "cfd_denoise_guide_pose", "cfd_weg_step", "cfd_test_weg_focus_rows", "cfd_t5_encode",
 ]
 
 # cfd_sample_args.prediction_type / the _pred entry points, by the schedulers' config string
@@ -170,6 +170,13 @@ class VaeDecodeVjpArgs(C.Structure):
 class VaeDecodeArgs(C.Structure):
     """cfd_vae_decode_args: one ConvoFusionVae.decode on the fused forward (cfd_vae_decode); cfd_vae_decode_vjp_args without the cotangent."""
     _fields_ = VaeDecodeVjpArgs._fields_[:-1]
+
+
+class T5Args(C.Structure):
+    """cfd_t5_args: one T5 text-encoder call (cfd_t5_encode)."""
+    _fields_ = [("wpack", C.c_void_p), ("vocab", C.c_int), ("d_model", C.c_int), ("d_kv", C.c_int), ("num_heads", C.c_int), ("d_ff", C.c_int),
+                ("num_layers", C.c_int), ("gated_act", C.c_int), ("eps", C.c_float), ("n_seq", C.c_int), ("T", C.c_int), ("ids", C.c_void_p),
+                ("mask", C.c_void_p), ("rel_bias", C.c_void_p), ("proj_w", C.c_void_p), ("proj_b", C.c_void_p), ("proj_dim", C.c_int)]
 
 
 # cfd_test_epi_args.kind (include/cfdenoise_dev.h)
@@ -335,6 +342,7 @@ def load():
     lib.cfd_vae_decode_sweep.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.cfd_vae_decode_ticket.argtypes = [C.c_void_p]
     lib.cfd_vae_decode_ticket.restype = C.c_uint64
+    lib.cfd_t5_encode.argtypes = [C.c_void_p, C.POINTER(T5Args), C.c_void_p, C.c_void_p]
     lib.cfd_debug_vae_workspace.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
     lib.cfd_dyadic_steps.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(DyadicProj), C.c_int]
     lib.cfd_debug_stop_stage.argtypes = [C.c_void_p, C.c_int]

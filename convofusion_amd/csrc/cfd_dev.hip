@@ -124,6 +124,19 @@ extern "C" int cfd_debug_read(cfd_handle c, const char* what, float* dst_dev, si
     HIPCHK(hipMemcpy(dst_dev, f, sizeof(f), hipMemcpyHostToDevice));
     return CFD_OK;
   }
+  if (!strcmp(what, "t5.info")) {   // the last cfd_t5_encode: launches (0: refused), token rows, workspace bytes as allocated, launches that ran 128 x 128 blocks
+    if (numel < 4) return fail(CFD_E_ARG, "t5.info needs 4 floats");
+    const float f[4] = {(float)c->t5.launches, (float)c->t5.rows, (float)c->t5.ws.bytes, (float)c->t5.big_launches};
+    HIPCHK(hipMemcpy(dst_dev, f, sizeof(f), hipMemcpyHostToDevice));
+    return CFD_OK;
+  }
+  if (!strcmp(what, "t5.x")) {      // the residual stream behind the last block, [rows][768] (in front of the final norm)
+    if (!c->t5.x) return fail(CFD_E_STATE, "no cfd_t5_encode has run on this handle");
+    if (numel > (size_t)c->t5.rows * 768) return fail(CFD_E_ARG, "buffer 't5.x' holds %lld floats, asked for %zu", c->t5.rows * 768, numel);
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(dst_dev, c->t5.x, numel * 4, hipMemcpyDeviceToDevice));
+    return CFD_OK;
+  }
   if (!strncmp(what, "vae.", 4)) {
     float* p = nullptr;
     size_t n = 0;

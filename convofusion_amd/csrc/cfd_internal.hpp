@@ -352,6 +352,15 @@ struct cfd_handle_s {
     const char* dropped_by = nullptr;
     bool grew = false;            // ... and had to grow the workspace
   } vae;
+  // cfd_t5_encode (cfd_text.hip, t5_enc.hpp): the call's workspace, sized from (n_seq, T) -- per token row x | h | q k v | ctx | f --, the
+  // launches of the last call (0: it was refused; big_launches: those of its products that ran as 128 x 128 blocks), where it left the
+  // residual stream (cfd_debug_read "t5.x"), and the handle's device's compute units (what the products' block shape is chosen by)
+  struct T5State {
+    DBuf ws;
+    float* x = nullptr;
+    long long rows = 0;
+    int launches = 0, big_launches = 0, n_cu = 0;
+  } t5;
   // profiling
   bool prof = false;
   hipEvent_t pev[2] = {nullptr, nullptr};

@@ -47,7 +47,7 @@ def diffusion_reverse_forecast(model, encoder_hidden_states, lengths=None, prese
     return impl(model, encoder_hidden_states, lengths, preseq, cond_masks, focus_indices)
 
 
-def install(model, attention_steps="auto", operands=None, modality_weights=None):
+def install(model, attention_steps="auto", operands=None, modality_weights=None, fused_text=False):
     """Bind the fused loop as ``model._diffusion_reverse``.  Returns the model.  ``uninstall`` removes the binding.
 
     ``attention_steps``: which entries the returned attention-matrix dict holds.  The reference keeps the full-conditioning
@@ -67,7 +67,10 @@ def install(model, attention_steps="auto", operands=None, modality_weights=None)
 
     ``modality_weights``: per-modality guidance weights w_c in place of the reference's 1, 1, 1, 1, 1, 0 (convofusion.py:527-541) -- a dict
     over text / audio / spk / apb / lsnid / all (missing keys keep the reference's value) or a tensor [6], [B, 6] or [N, B, 6]
-    (``convofusion_amd.sampler.check_modality_weights``); a chunk whose weight is 0 throughout is not evaluated.  None: the reference's."""
+    (``convofusion_amd.sampler.check_modality_weights``); a chunk whose weight is 0 throughout is not evaluated.  None: the reference's.
+
+    ``fused_text``: True swaps ``model.text_audio_encoder.text_encoder`` for the HIP T5 mirror, sharing its parameters
+    (``convofusion_amd.text.install``); False (default) leaves the reference's torch-eager encoder in place."""
     from .sampler import check_modality_weights, check_operands
     operands = check_operands(operands)
     modality_weights = check_modality_weights(modality_weights)
@@ -78,6 +81,9 @@ def install(model, attention_steps="auto", operands=None, modality_weights=None)
     model._cfd_operands = operands
     model._cfd_modality_weights = modality_weights
     model._diffusion_reverse = types.MethodType(_diffusion_reverse, model)
+    if fused_text:
+        from .text import install as install_text
+        install_text(model, fused_text=True)
     return model
 
 
@@ -88,6 +94,9 @@ def uninstall(model):
     vars(model).pop("_cfd_attention_steps", None)
     vars(model).pop("_cfd_operands", None)
     vars(model).pop("_cfd_modality_weights", None)
+    if "_cfd_text_encoder" in vars(model):
+        from .text import uninstall as uninstall_text
+        uninstall_text(model)
     return model
 
 

@@ -23,6 +23,8 @@ What it binds, in this process, before the script's first line runs (nothing has
 ``CFD_RUN_ATTENTION_STEPS`` = auto | last | all selects ``install``'s attention dict (default auto).
 ``CFD_RUN_MODALITY_WEIGHTS`` = e.g. ``text=2,audio=0.5`` sets ``install``'s per-modality guidance weights (keys: text, audio, spk, apb,
 lsnid, all; the others keep the reference's 1, 1, 1, 1, 1, 0).  Unset or empty: the reference's weights.
+``CFD_RUN_FUSED_TEXT`` = 1 also binds configs/modules/text_encoder.yaml's target ``convofusion.models.architectures.t5.T5TextEncoder`` to
+``convofusion_amd.text.T5TextEncoder`` (the T5 encoder stack and its projection in one HIP call).  Default off: the reference's class.
 """
 import importlib
 import importlib.util
@@ -32,11 +34,12 @@ import sys
 import types
 
 REF_DENOISER_MODULE = "convofusion.models.architectures.denoiser"      # configs/modules/denoiser.yaml:2
+REF_T5_MODULE = "convofusion.models.architectures.t5"                  # configs/modules/text_encoder.yaml:3
 REF_GET_MODEL_MODULE = "convofusion.models.get_model"                   # test.py:14, unbounded_synthesis.py:16
 
 
-def redirect_targets():
-    """Binding 1: the yaml's dotted targets resolve to the HIP mirrors.  Returns the names it bound."""
+def redirect_targets(fused_text=False):
+    """Binding 1: the yaml's dotted targets resolve to the HIP mirrors (``fused_text``: the text encoder's too).  Returns the names it bound."""
     from . import denoiser as amd_denoiser
     from . import scheduler as amd_scheduler
     bound = []
@@ -55,6 +58,14 @@ def redirect_targets():
     diffusers.DDPMScheduler = amd_scheduler.DDPMScheduler
     diffusers.DDIMScheduler = amd_scheduler.DDIMScheduler
     bound += ["diffusers.DDPMScheduler", "diffusers.DDIMScheduler"]
+    if fused_text:
+        from . import text as amd_text
+        t5 = types.ModuleType(REF_T5_MODULE)
+        t5.__doc__ = "convofusion_amd.run: stands in for the reference's t5 module; T5TextEncoder is the MI355X engine's"
+        t5.T5TextEncoder = amd_text.T5TextEncoder
+        t5.__cfd_redirect__ = True
+        sys.modules[REF_T5_MODULE] = t5
+        bound.append(REF_T5_MODULE + ".T5TextEncoder")
     return bound
 
 
@@ -113,7 +124,7 @@ def run_script(path, argv):
     if script_dir not in sys.path:
         sys.path.insert(0, script_dir)           # what `python script.py` does: the script's directory first
     modality_weights = parse_modality_weights(os.environ.get("CFD_RUN_MODALITY_WEIGHTS"))
-    redirect_targets()
+    redirect_targets(fused_text=os.environ.get("CFD_RUN_FUSED_TEXT", "0") == "1")
     found = wrap_get_model(os.environ.get("CFD_RUN_ATTENTION_STEPS", "auto"), modality_weights)
     if not found:
         print("convofusion_amd.run: convofusion.models.get_model is not importable from here (run from the reference checkout); "

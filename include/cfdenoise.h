@@ -482,6 +482,39 @@ int cfd_vae_encode(cfd_handle h, const float* wpack, int d_model, int num_heads,
                    const float* features, int bs, int nframes, long long row_stride, const int* lengths, float* mu_logvar,
                    float* feats_out, int seqs_per_group, void* stream);
 
+/* Replaces the reference's T5TextEncoder behind its tokenizer (convofusion/models/architectures/t5.py:9-109): the T5 v1.0 encoder
+ * (transformers T5EncoderModel, feed_forward_proj "relu": RMS norms without mean or bias, attention without the 1/sqrt(d_kv) scale and
+ * with block 0's relative-position bias in every block, ReLU feed-forward) followed by `Linear(relu(last_hidden_state))` (t5.py:48-49,
+ * 57), in 5 launches per block + 1 (csrc/t5_enc.hpp).  Exact float32 on the float32 matrix instruction: no operand has a range limit,
+ * no atomics, and a sequence's result is the same bits whatever else is in the batch and whatever it is padded to.
+ *   wpack       dev float32: embed [vocab][768] | per block g1, Wq|Wk|Wv, Wo, g2, Wi, Wo_ff | g_final (csrc/t5_enc.hpp; built by
+ *               convofusion_amd/text.py)
+ *   d_model, d_kv, num_heads, d_ff, num_layers: must be 768, 64, 12, 3072, 1 - 12; gated_act must be 0 (CFD_E_ARG otherwise)
+ *   n_seq, T    n_seq >= 1 sequences padded to 1 <= T <= 256 tokens (CFD_E_SHAPE otherwise)
+ *   ids         dev int32 [n_seq][T], each in [0, vocab) (the caller checks; the kernels clamp a stray id into the table)
+ *   mask        dev uint8 [n_seq][T], 1 = token: only KEYS are masked (probability exactly 0); padded queries are computed like any
+ *               other, as the reference does.  Every sequence needs at least one token (a sequence without keys gives NaN rows).
+ *   rel_bias    dev float32 [12][2 T - 1]: block 0's relative_attention_bias by relative distance, entry [h][j - i + T - 1] (the bucket
+ *               function stays on the host: convofusion_amd/text.py)
+ *   proj_w, proj_b, proj_dim   dev float32 [proj_dim][768], [proj_dim], proj_dim a multiple of 64; or proj_w NULL
+ *   out         dev float32 [n_seq][T][proj_dim], or [n_seq][T][768] (the last hidden state) when proj_w is NULL
+ * Everything is refused before the first launch.  The workspace (33 792 bytes per token row) lives on the handle and only grows. */
+typedef struct {
+  const float* wpack;
+  int vocab;
+  int d_model, d_kv, num_heads, d_ff, num_layers;
+  int gated_act;
+  float eps;
+  int n_seq, T;
+  const int32_t* ids;
+  const uint8_t* mask;
+  const float* rel_bias;
+  const float* proj_w;
+  const float* proj_b;
+  int proj_dim;
+} cfd_t5_args;
+int cfd_t5_encode(cfd_handle h, const cfd_t5_args* a, float* out, void* stream);
+
 /* float32 pieces of word-excitation guidance (WEG): the attend-and-excite objective on the listener-text attention
  * maps and d(loss)/d(latents) through the denoiser -- what the reference gets from torch autograd over
  * Denoiser.forward (convofusion/models/modeltype/convofusion.py:437-496, iterative_refinement_step :298-388;

@@ -81,7 +81,11 @@ int cfd_bench_gemm(cfd_handle h, int I, int J, int K, int tile_cfg, int iters, f
  *   "vae.g.<l>"   [2 * bs * fp][128]   the running gradient at layer l's output, as it enters the layer's backward
  *   "vae.dz.<l>"  [2][bs][16][128]     layer l's memory-side contribution to d_z (rows >= n_chunks: no meaning)
  *   "vae.x.<l>"   [2 * bs * fp][128]   the forward's stream at layer l's input; l = num_layers: the last layer's output
- *   "vae.info"    2 floats: the launches of the call, fp */
+ *   "vae.info"    2 floats: the launches of the call, fp
+ * ... and what the last cfd_t5_encode left on the handle:
+ *   "t5.info"     4 floats: the launches of the call (5 per block + 1; 0: it was refused), its token rows n_seq * T, the workspace's bytes,
+ *                 and how many of its products ran as 128 x 128 blocks (the others: 64 x 64; the bits are the same)
+ *   "t5.x"        [n_seq * T][768]     the residual stream behind the last block, in front of the final norm */
 int cfd_debug_read(cfd_handle h, const char* what, float* dst_dev, size_t numel);
 
 /* Test hook: stop the reverse sweep of a row-tile cfd_weg_eval (csrc/weg_rt.hpp, csrc/rowtile_bwd.hpp) behind one launch.

@@ -29,7 +29,8 @@ SYMBOLS = [
     "cfd_test_picard_sweep", "cfd_debug_weg_stop", "cfd_debug_weg_fill", "cfd_scheduler_step_pred", "cfd_dpmsolver_step_pred",
     "cfd_debug_forward_operands", "cfd_denoise_vjp", "cfd_debug_live_buffers", "cfd_vae_decode_vjp", "cfd_denoise_vjp_mem",
     "cfd_vae_decode", "cfd_vae_decode_sweep", "cfd_vae_decode_ticket", "cfd_debug_vae_workspace", "cfd_denoise_guide", "cfd_guide_tie_csr",
-    "cfd_denoise_guide_pose", "cfd_weg_step", "cfd_test_weg_focus_rows", "cfd_t5_encode",
+    "cfd_denoise_guide_pose", "cfd_weg_step", "cfd_test_weg_focus_rows", "cfd_t5_encode", "cfd_audio_encode",
+    "cfd_audio_power",
 ]
 
 # cfd_sample_args.prediction_type / the _pred entry points, by the schedulers' config string
@@ -177,6 +178,15 @@ class T5Args(C.Structure):
     _fields_ = [("wpack", C.c_void_p), ("vocab", C.c_int), ("d_model", C.c_int), ("d_kv", C.c_int), ("num_heads", C.c_int), ("d_ff", C.c_int),
                 ("num_layers", C.c_int), ("gated_act", C.c_int), ("eps", C.c_float), ("n_seq", C.c_int), ("T", C.c_int), ("ids", C.c_void_p),
                 ("mask", C.c_void_p), ("rel_bias", C.c_void_p), ("proj_w", C.c_void_p), ("proj_b", C.c_void_p), ("proj_dim", C.c_int)]
+
+
+class AudioArgs(C.Structure):
+    """cfd_audio_args: one log-Mel front-end call (cfd_audio_encode)."""
+    _fields_ = [("wave", C.c_void_p), ("n_wave", C.c_int), ("n_samples", C.c_longlong), ("normalize", C.c_int), ("n_fft", C.c_int), ("hop", C.c_int),
+                ("n_mels", C.c_int), ("twiddle", C.c_void_p), ("window", C.c_void_p), ("melfb", C.c_void_p), ("mel_range", C.c_void_p),
+                ("amin", C.c_float), ("top_db", C.c_float), ("n_win", C.c_int), ("win_start", C.c_void_p), ("win_frames", C.c_int),
+                ("w0", C.c_void_p), ("b0", C.c_void_p), ("w1", C.c_void_p), ("b1", C.c_void_p), ("w2", C.c_void_p), ("b2", C.c_void_p),
+                ("hidden", C.c_int), ("latent", C.c_int), ("act_chunk", C.c_int), ("act_amin_power", C.c_float), ("act_thresh_power", C.c_float)]
 
 
 # cfd_test_epi_args.kind (include/cfdenoise_dev.h)
@@ -343,6 +353,8 @@ def load():
     lib.cfd_vae_decode_ticket.argtypes = [C.c_void_p]
     lib.cfd_vae_decode_ticket.restype = C.c_uint64
     lib.cfd_t5_encode.argtypes = [C.c_void_p, C.POINTER(T5Args), C.c_void_p, C.c_void_p]
+    lib.cfd_audio_encode.argtypes = [C.c_void_p, C.POINTER(AudioArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.cfd_audio_power.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.cfd_debug_vae_workspace.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
     lib.cfd_dyadic_steps.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(DyadicProj), C.c_int]
     lib.cfd_debug_stop_stage.argtypes = [C.c_void_p, C.c_int]

@@ -1,0 +1,135 @@
+// libcfdenoise: the log-Mel front end -- waveforms to Mel frames in dB, AudioConvEncoder's memories and the activity bits in one call
+// (cfd_audio_encode; kernels, the FFT and its LDS layout: audio_fe.hpp), and its FFT stage alone (cfd_audio_power).
+#include "cfd_internal.hpp"
+#include "audio_fe.hpp"
+
+constexpr long long AFE_MAX_SAMPLES = 1LL << 26;
+
+// What both entry points refuse about the transform itself
+static int check_transform(const char* who, int n_wave, long long n_samples, int n_fft, int hop) {
+  if (n_fft != 256 && n_fft != 512 && n_fft != 1024 && n_fft != 2048)
+    return fail(CFD_E_ARG, "%s: n_fft must be 256, 512, 1024 or 2048 (got %d)", who, n_fft);
+  if (hop < 1) return fail(CFD_E_ARG, "%s: hop must be at least 1 (got %d)", who, hop);
+  if (n_wave < 1 || n_wave > 65535) return fail(CFD_E_SHAPE, "%s: 1 <= n_wave <= 65535 (got %d)", who, n_wave);
+  if (n_samples < 1 || n_samples > AFE_MAX_SAMPLES)
+    return fail(CFD_E_SHAPE, "%s: 1 <= n_samples <= %lld (got %lld)", who, AFE_MAX_SAMPLES, n_samples);
+  return CFD_OK;
+}
+
+template <bool POWER>
+static int enqueue_frames(const AfeFrameArgs& f, int n_fft, int n_wave, hipStream_t st) {
+  const dim3 grid((unsigned)f.T, (unsigned)n_wave), block(AFE_THREADS);
+  switch (n_fft) {
+    case 256: hipLaunchKernelGGL((afe_frame_kernel<128, POWER>), grid, block, 0, st, f); break;
+    case 512: hipLaunchKernelGGL((afe_frame_kernel<256, POWER>), grid, block, 0, st, f); break;
+    case 1024: hipLaunchKernelGGL((afe_frame_kernel<512, POWER>), grid, block, 0, st, f); break;
+    default: hipLaunchKernelGGL((afe_frame_kernel<1024, POWER>), grid, block, 0, st, f); break;
+  }
+  HIPCHK(hipGetLastError());
+  return CFD_OK;
+}
+
+extern "C" int cfd_audio_encode(cfd_handle c, const cfd_audio_args* a, float* mel_db, float* memory, int32_t* activity, float* peak,
+                                void* stream) {
+  if (!c) return fail(CFD_E_ARG, "null handle");
+  c->audio.launches = 0;
+  if (!a || !a->wave || !a->twiddle || !a->window || !a->melfb) return fail(CFD_E_ARG, "cfd_audio_encode: bad argument (NULL pointer)");
+  CHK(check_transform("cfd_audio_encode", a->n_wave, a->n_samples, a->n_fft, a->hop));
+  if (a->n_mels < 1 || a->n_mels > a->n_fft / 2 + 1)
+    return fail(CFD_E_ARG, "cfd_audio_encode: 1 <= n_mels <= n_fft / 2 + 1 = %d (got %d)", a->n_fft / 2 + 1, a->n_mels);
+  if (!(a->amin > 0.f) || !(a->top_db >= 0.f)) return fail(CFD_E_ARG, "cfd_audio_encode: amin > 0 and top_db >= 0 (got %g, %g)", (double)a->amin, (double)a->top_db);
+  if (a->normalize != 0 && a->normalize != 1) return fail(CFD_E_ARG, "cfd_audio_encode: normalize is 0 or 1 (got %d)", a->normalize);
+  const bool mlp = a->w0 || a->b0 || a->w1 || a->b1 || a->w2 || a->b2;
+  if (mlp && (!a->w0 || !a->b0 || !a->w1 || !a->b1 || !a->w2 || !a->b2 || a->hidden < 1 || a->latent < 1))
+    return fail(CFD_E_ARG, "cfd_audio_encode: the encoder needs all of w0 b0 w1 b1 w2 b2 and hidden, latent >= 1 (got %d, %d)", a->hidden, a->latent);
+  if (memory && !mlp) return fail(CFD_E_ARG, "cfd_audio_encode: memory asked for without the encoder's weights");
+  if (activity && a->act_chunk < 1) return fail(CFD_E_ARG, "cfd_audio_encode: activity bits need act_chunk >= 1 (got %d)", a->act_chunk);
+  const long long T = 1 + a->n_samples / a->hop;
+  if (a->n_win < 0 || a->n_win > AFE_MAX_WIN) return fail(CFD_E_SHAPE, "cfd_audio_encode: 0 <= n_win <= %d (got %d)", AFE_MAX_WIN, a->n_win);
+  long long frames = T;
+  if (a->n_win > 0) {
+    if (!a->win_start) return fail(CFD_E_ARG, "cfd_audio_encode: n_win = %d without win_start", a->n_win);
+    if (a->win_frames < 1) return fail(CFD_E_SHAPE, "cfd_audio_encode: win_frames must be at least 1 (got %d)", a->win_frames);
+    for (int w = 0; w < a->n_win; ++w)
+      if (a->win_start[w] < 0 || (long long)a->win_start[w] + a->win_frames > T)
+        return fail(CFD_E_SHAPE, "cfd_audio_encode: window %d = frames [%d, %lld) lies outside the %lld frames of a waveform", w, a->win_start[w],
+                    (long long)a->win_start[w] + a->win_frames, T);
+    frames = a->win_frames;
+  }
+  const long long rows = (long long)a->n_wave * (a->n_win > 0 ? a->n_win : 1);
+  const long long out_rows = rows * frames;                      // rows of the dB matrix = rows of the MLP
+  if (out_rows * a->n_mels > (1LL << 40) || (long long)a->n_wave * T * a->n_mels > (1LL << 40) || (memory && out_rows > 65535LL * 32))
+    return fail(CFD_E_SHAPE, "cfd_audio_encode: too many frames for one call (%lld rows x %lld frames)", rows, frames);
+  HIPCHK(hipSetDevice(c->cfg.device));
+  hipStream_t st = (hipStream_t)stream;
+
+  const bool want_db = mel_db || memory;
+  const bool front = a->normalize || peak || activity;
+  const int chunk = a->act_chunk >= 1 ? a->act_chunk : 4096;
+  const long long n_chunks = (a->n_samples + chunk - 1) / chunk, n_bits = a->act_chunk >= 1 ? a->n_samples / a->act_chunk : 0;
+  float *chunkmax, *peak_ws, *smax, *melpow, *db_ws, *h1, *h2;
+  for (int pass = 0; pass < 2; ++pass) {      // the workspace's layout, stated once: sized, then carved
+    ArenaLayout lay(pass ? c->audio.ws.as<float>() : nullptr, 64);
+    lay.take(chunkmax, front ? (size_t)(a->n_wave * n_chunks) : 0);
+    lay.take(peak_ws, (size_t)a->n_wave);
+    lay.take(smax, (size_t)a->n_wave);
+    lay.take(melpow, want_db ? (size_t)a->n_wave * T * a->n_mels : 0);
+    lay.take(db_ws, memory && !mel_db ? (size_t)out_rows * a->n_mels : 0);
+    lay.take(h1, memory ? (size_t)out_rows * a->hidden : 0);
+    lay.take(h2, memory ? (size_t)out_rows * a->latent : 0);
+    if (!pass && lay.bytes() > c->audio.ws.bytes) {
+      HIPCHK(hipDeviceSynchronize());          // an earlier call on another stream may still read the buffer that is about to be freed
+      CHK(c->audio.ws.ensure(lay.bytes()));
+    }
+  }
+  c->audio.frames = T;
+  c->audio.rows = rows;
+
+  int launches = 0;
+  if (front) {
+    hipLaunchKernelGGL(afe_peak_kernel, dim3((unsigned)a->n_wave), dim3(AFE_RED_THREADS), 0, st, a->wave, a->n_samples, chunk, n_chunks, a->normalize,
+                       a->act_amin_power, a->act_thresh_power, chunkmax, peak_ws, peak, (int*)activity, n_bits);
+    HIPCHK(hipGetLastError());
+    ++launches;
+  }
+  if (want_db) {
+    AfeFrameArgs f{};
+    f.wave = a->wave; f.peak = a->normalize ? peak_ws : nullptr; f.n_samples = a->n_samples; f.T = T; f.hop = a->hop; f.n_mels = a->n_mels;
+    f.tw = (const float2*)a->twiddle; f.window = a->window; f.melfb = a->melfb; f.mel_range = a->mel_range; f.out = melpow;
+    CHK(enqueue_frames<false>(f, a->n_fft, a->n_wave, st));
+    hipLaunchKernelGGL(afe_max_kernel, dim3((unsigned)a->n_wave), dim3(AFE_RED_THREADS), 0, st, melpow, T * a->n_mels, smax);
+    HIPCHK(hipGetLastError());
+    AfeDbArgs d{};
+    float* db = mel_db ? mel_db : db_ws;
+    d.melpow = melpow; d.smax = smax; d.out = db; d.T = T; d.total = out_rows * a->n_mels; d.n_mels = a->n_mels; d.frames = (int)frames;
+    d.n_win = a->n_win; d.amin = a->amin; d.top_db = a->top_db;
+    for (int w = 0; w < a->n_win; ++w) d.start[w] = a->win_start[w];
+    hipLaunchKernelGGL(afe_db_kernel, dim3((unsigned)((d.total + 255) / 256)), dim3(256), 0, st, d);
+    HIPCHK(hipGetLastError());
+    launches += 3;
+    if (memory) {                              // the three Linear layers on the library's float32 row kernel: K <= 512, a few thousand rows
+      CHK(enqueue_linear_act(db, out_rows, a->n_mels, a->w0, a->b0, a->hidden, 2, h1, st));
+      CHK(enqueue_linear_act(h1, out_rows, a->hidden, a->w1, a->b1, a->latent, 2, h2, st));
+      CHK(enqueue_linear_act(h2, out_rows, a->latent, a->w2, a->b2, a->latent, 0, memory, st));
+      launches += 3;
+    }
+  }
+  c->audio.launches = launches;
+  return CFD_OK;
+}
+
+extern "C" int cfd_audio_power(cfd_handle c, const float* wave, int n_wave, long long n_samples, int n_fft, int hop, const float* twiddle,
+                               const float* window, float* power, void* stream) {
+  if (!c) return fail(CFD_E_ARG, "null handle");
+  c->audio.launches = 0;
+  if (!wave || !twiddle || !window || !power) return fail(CFD_E_ARG, "cfd_audio_power: bad argument (NULL pointer)");
+  CHK(check_transform("cfd_audio_power", n_wave, n_samples, n_fft, hop));
+  HIPCHK(hipSetDevice(c->cfg.device));
+  AfeFrameArgs f{};
+  f.wave = wave; f.n_samples = n_samples; f.T = 1 + n_samples / hop; f.hop = hop; f.tw = (const float2*)twiddle; f.window = window; f.out = power;
+  CHK(enqueue_frames<true>(f, n_fft, n_wave, (hipStream_t)stream));
+  c->audio.frames = f.T;
+  c->audio.rows = n_wave;
+  c->audio.launches = 1;
+  return CFD_OK;
+}

@@ -130,6 +130,12 @@ extern "C" int cfd_debug_read(cfd_handle c, const char* what, float* dst_dev, si
     HIPCHK(hipMemcpy(dst_dev, f, sizeof(f), hipMemcpyHostToDevice));
     return CFD_OK;
   }
+  if (!strcmp(what, "audio.info")) {   // the last cfd_audio_encode / cfd_audio_power: launches (0: refused), frames per waveform, output rows, workspace bytes as allocated
+    if (numel < 4) return fail(CFD_E_ARG, "audio.info needs 4 floats");
+    const float f[4] = {(float)c->audio.launches, (float)c->audio.frames, (float)c->audio.rows, (float)c->audio.ws.bytes};
+    HIPCHK(hipMemcpy(dst_dev, f, sizeof(f), hipMemcpyHostToDevice));
+    return CFD_OK;
+  }
   if (!strcmp(what, "t5.x")) {      // the residual stream behind the last block, [rows][768] (in front of the final norm)
     if (!c->t5.x) return fail(CFD_E_STATE, "no cfd_t5_encode has run on this handle");
     if (numel > (size_t)c->t5.rows * 768) return fail(CFD_E_ARG, "buffer 't5.x' holds %lld floats, asked for %zu", c->t5.rows * 768, numel);

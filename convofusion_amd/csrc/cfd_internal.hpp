@@ -361,6 +361,14 @@ struct cfd_handle_s {
     long long rows = 0;
     int launches = 0, big_launches = 0, n_cu = 0;
   } t5;
+  // cfd_audio_encode / cfd_audio_power (cfd_audio.hip, audio_fe.hpp): the call's workspace -- per waveform the chunk maxima, peak and largest
+  // Mel power, the Mel powers [n_wave][T][n_mels], and where the call needs them the dB rows and the MLP's two hidden layers --, the
+  // launches of the last call (0: it was refused), its frames per waveform and its output rows
+  struct AudioState {
+    DBuf ws;
+    long long frames = 0, rows = 0;
+    int launches = 0;
+  } audio;
   // profiling
   bool prof = false;
   hipEvent_t pev[2] = {nullptr, nullptr};

@@ -89,7 +89,8 @@ def synthesize_latents(model_or_denoiser, scheduler, encoder_hidden_states, cond
     """The latents of U = n_utterances motions of W = n_windows half-overlapping windows each.  ``model_or_denoiser``: the HIP ``Denoiser``
     or an object with a ``.denoiser``.  encoder_hidden_states / cond_masks: the guidance batch of ``sample`` for B = U * W rows in the
     order u * W + w (chunk-major, G * B rows per memory), every row conditioned on its own window of the audio and text as the caller
-    sliced them (the reference's per-window data work, unbounded_synthesis.py:290-330).  modality_weights: as in ``sample`` over those rows.
+    sliced them (the reference's per-window data work, unbounded_synthesis.py:290-330; ``audio_windows`` does the audio side of it from the
+    waveform).  modality_weights: as in ``sample`` over those rows.
     Noise: Philox with ``seed``, row u * W + w on stream u * W + w.
     max_rows: the most rows one run may have (``window_groups``); windows of one run are tied, a later run's first window keeps its first
     half from the finished window before it -- the grouping changes the result.  carry [U, L / 2, 128] (optional): the finished second half
@@ -197,6 +198,39 @@ def synthesize_latents(model_or_denoiser, scheduler, encoder_hidden_states, cond
             out[start:stop] = sample(denoiser, scheduler, enc, masks, **run_kw)
     windows = out.reshape(U, W, L, 128)
     return windows, stitch_tokens(windows)
+
+
+def audio_windows(front_end, wave, n_windows, normalize=False):
+    """The listener-audio side of the per-window data work (unbounded_synthesis.py:279-308) from the waveform, on the device:
+    ``front_end`` (``audio.AudioFrontEnd`` with an encoder) makes ONE spectrogram per utterance and the library slices it.
+    wave [U, n_parts * window_samples] float32 on the device, n_windows = 2 n_parts - 1; anything else raises ValueError, and so does a
+    length whose windows (``audio.window_slices`` / ``audio.activity_slices``) do not all have the same number of frames or bits.
+    Returns (audio memory [U * W, frames, latent], activity bits int32 [U * W, bits per window], Mel windows [U * W, frames, n_mels] in dB,
+    unconditional audio memory [1, frames, latent] = ``audio.uncond_mel`` through the same encoder), rows in the order u * W + w that
+    ``build_guidance_batch`` and ``synthesize_latents`` take.  The text side of that work stays the caller's."""
+    from .audio import AudioFrontEnd, activity_slices, frame_count, uncond_mel, window_slices
+    if not isinstance(front_end, AudioFrontEnd) or front_end.audio_encoder is None:
+        raise ValueError("audio_windows: front_end must be an AudioFrontEnd with an audio_encoder")
+    W = int(n_windows)
+    if W < 1 or W % 2 == 0:
+        raise ValueError(f"audio_windows: n_windows = 2 n_parts - 1 is odd and positive (got {n_windows})")
+    n_parts = (W + 1) // 2
+    if not isinstance(wave, torch.Tensor) or wave.dim() != 2 or wave.shape[0] < 1 or wave.shape[1] < n_parts or wave.shape[1] % n_parts:
+        raise ValueError(f"audio_windows: wave must be [U, n_parts * window_samples] with n_parts = {n_parts}")
+    U, n = (int(v) for v in wave.shape)
+    mel_sl = window_slices(frame_count(n, front_end.hop_length), n_parts)
+    n_bits = n // front_end.act_chunk
+    if n_bits < n_parts:
+        raise ValueError(f"audio_windows: {n} samples hold {n_bits} activity chunks of {front_end.act_chunk} samples, fewer than {n_parts} parts")
+    bit_sl = activity_slices(n_bits, n_parts)
+    frames, bits = mel_sl[0][1] - mel_sl[0][0], bit_sl[0][1] - bit_sl[0][0]
+    if any(b - a != frames for a, b in mel_sl) or any(b - a != bits for a, b in bit_sl):
+        raise ValueError(f"audio_windows: the {W} windows of {n} samples do not all have {frames} Mel frames and {bits} activity bits "
+                         f"(frames {mel_sl}, bits {bit_sl})")
+    r = front_end.forward(wave, normalize=normalize, windows=([a for a, _ in mel_sl], frames))
+    activity = torch.stack([r.activity[:, a:b] for a, b in bit_sl], dim=1).reshape(U * W, bits)
+    uncond = front_end.encode_mel(uncond_mel(frames, front_end.n_mels).to(wave.device)[None])
+    return r.memory, activity, r.mel, uncond
 
 
 def pose_keyframes_for_windows(target, frame_mask, n_windows, feature_mask=None):

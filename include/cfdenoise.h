@@ -515,6 +515,56 @@ typedef struct {
 } cfd_t5_args;
 int cfd_t5_encode(cfd_handle h, const cfd_t5_args* a, float* out, void* stream);
 
+/* Replaces the reference's Mel front end, which its data loader runs on the CPU with librosa 0.10 (convofusion/data/beat_dnd/dataset.py:
+ * get_melspecs :506-520, check_audio :477-492, beat_extract_audio :473; per-window slicing unbounded_synthesis.py:279-308): waveforms to
+ * log-Mel frames, to the audio memories of AudioConvEncoder and to the activity bits, float32 throughout, in 4 launches + 3 for the MLP
+ * (csrc/audio_fe.hpp).  Semantics: librosa.feature.melspectrogram(y, sr, n_fft, hop_length, n_mels) with its defaults (center=True,
+ * pad_mode="constant", win_length = n_fft, periodic Hann, power 2, Slaney filterbank) followed by power_to_db(ref=np.max, amin, top_db):
+ * T = 1 + n_samples / hop frames; dB = 10 log10(max(amin, S)) - 10 log10(max(amin, max S)), the max over the ONE waveform's whole
+ * spectrogram, clipped below at -top_db.  No atomics; the same bits on every call; a waveform's bits do not depend on the batch; a
+ * window's rows are the bits of the same frames of the whole spectrogram.
+ *   wave        dev float32 [n_wave][n_samples]: mono, equal length, at the sample rate the filterbank was built for.  1 <= n_wave <= 65535,
+ *               1 <= n_samples <= 2^26 (CFD_E_SHAPE otherwise)
+ *   normalize   1: every waveform is divided by its own max|y| first (librosa.util.normalize); a peak below FLT_MIN leaves it unchanged
+ *   n_fft       256, 512, 1024 or 2048; hop >= 1; 1 <= n_mels <= n_fft / 2 + 1 (CFD_E_ARG otherwise)
+ *   twiddle     dev float32 [n_fft][2]: (cos, -sin)(2 pi k / n_fft), computed in float64 and rounded once
+ *   window      dev float32 [n_fft]: the periodic Hann window, computed in float64
+ *   melfb       dev float32 [n_mels][n_fft / 2 + 1], dense
+ *   mel_range   dev int32 [n_mels][2] or NULL: first and one-past-last bin of every band's non-zero weights; a band is summed over that
+ *               range only (the bins outside weigh 0, so the sum is the same).  NULL: every band over all bins.
+ *   amin, top_db   > 0, >= 0 (the reference: 1e-10, 80)
+ *   n_win, win_start, win_frames   0 <= n_win <= 64 frame ranges [win_start[w], win_start[w] + win_frames) taken from every waveform;
+ *               win_start is HOST int32 [n_win].  n_win = 0: the whole spectrogram (frames = T).  A range outside [0, T]: CFD_E_SHAPE.
+ *   w0 b0 w1 b1 w2 b2, hidden, latent   AudioConvEncoder's main.0 [hidden][n_mels], main.3 [latent][hidden], out_net [latent][latent]
+ *               with their biases, dev float32; LeakyReLU(0.1) behind the first two.  All NULL: no encoder.
+ *   act_chunk, act_amin_power, act_thresh_power   the activity bit of chunk j < n_samples / act_chunk (whole chunks only) is
+ *               max(act_amin_power, max|y|^2) > act_thresh_power on the waveform after normalisation: amplitude_to_db(chunk, ref=1).max()
+ *               > threshold restated in power (the reference: 10240 samples, 1e-10, 10^-4.5)
+ * Outputs, each may be NULL: mel_db [n_wave * max(n_win, 1)][frames][n_mels], memory [same rows][frames][latent] (needs the weights:
+ * CFD_E_ARG without), activity int32 [n_wave][n_samples / act_chunk] (needs act_chunk >= 1), peak [n_wave] (max|y| before
+ * normalisation).  Row u * n_win + w is window w of waveform u.
+ * Everything is refused before the first launch.  The workspace lives on the handle and only grows. */
+typedef struct {
+  const float* wave;
+  int n_wave;
+  long long n_samples;
+  int normalize;
+  int n_fft, hop, n_mels;
+  const float* twiddle;
+  const float* window;
+  const float* melfb;
+  const int32_t* mel_range;
+  float amin, top_db;
+  int n_win;
+  const int32_t* win_start;
+  int win_frames;
+  const float *w0, *b0, *w1, *b1, *w2, *b2;
+  int hidden, latent;
+  int act_chunk;
+  float act_amin_power, act_thresh_power;
+} cfd_audio_args;
+int cfd_audio_encode(cfd_handle h, const cfd_audio_args* a, float* mel_db, float* memory, int32_t* activity, float* peak, void* stream);
+
 /* float32 pieces of word-excitation guidance (WEG): the attend-and-excite objective on the listener-text attention
  * maps and d(loss)/d(latents) through the denoiser -- what the reference gets from torch autograd over
  * Denoiser.forward (convofusion/models/modeltype/convofusion.py:437-496, iterative_refinement_step :298-388;

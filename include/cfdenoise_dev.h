@@ -85,7 +85,10 @@ int cfd_bench_gemm(cfd_handle h, int I, int J, int K, int tile_cfg, int iters, f
  * ... and what the last cfd_t5_encode left on the handle:
  *   "t5.info"     4 floats: the launches of the call (5 per block + 1; 0: it was refused), its token rows n_seq * T, the workspace's bytes,
  *                 and how many of its products ran as 128 x 128 blocks (the others: 64 x 64; the bits are the same)
- *   "t5.x"        [n_seq * T][768]     the residual stream behind the last block, in front of the final norm */
+ *   "t5.x"        [n_seq * T][768]     the residual stream behind the last block, in front of the final norm
+ * ... and the last cfd_audio_encode / cfd_audio_power:
+ *   "audio.info"  4 floats: the launches of the call (0: it was refused), the frames per waveform 1 + n_samples / hop, the output rows
+ *                 n_wave * max(n_win, 1), the workspace's bytes */
 int cfd_debug_read(cfd_handle h, const char* what, float* dst_dev, size_t numel);
 
 /* Test hook: stop the reverse sweep of a row-tile cfd_weg_eval (csrc/weg_rt.hpp, csrc/rowtile_bwd.hpp) behind one launch.
@@ -135,6 +138,11 @@ int cfd_debug_weg_fill(cfd_handle h, float value);
 int cfd_test_weg_focus_rows(cfd_handle h, const float* att, int B, int NL, int L, int S, const int32_t* tok_off, const int32_t* tok_idx,
                             const int32_t* last_rows, int last, int nt_max, const float kernel3[3], int per_row, int small, float* workspace,
                             float* losses, float* max_att, float* d_att, void* stream);
+/* Test hook: the FFT stage of cfd_audio_encode alone -- the same device function (csrc/audio_fe.hpp) on the same frames, without
+ * normalisation: power [n_wave][1 + n_samples / hop][n_fft / 2 + 1] = |rfft(window * frame)|^2.  wave, twiddle, window as in
+ * cfd_audio_args; the same refusals for n_fft, hop, n_wave and n_samples.  One launch. */
+int cfd_audio_power(cfd_handle h, const float* wave, int n_wave, long long n_samples, int n_fft, int hop, const float* twiddle,
+                    const float* window, float* power, void* stream);
 /* Test hook (no handle): the device buffers the library holds in this process, over all handles and calls -- how many, and their bytes as asked
  * for.  Every buffer belongs to a handle or to one call: a reading is back at an earlier one once the handles created since are destroyed. */
 int cfd_debug_live_buffers(long long* count, long long* bytes);

@@ -37,8 +37,8 @@ def _layer(pre, decoder):
     return ks
 
 
-def _skip(pre, decoder):
-    nb = (NL - 1) // 2
+def _skip(pre, decoder, num_layers=NL):
+    nb = (num_layers - 1) // 2
     ks = [(pre + "norm.weight", (D,)), (pre + "norm.bias", (D,))]
     for i in range(nb):
         ks += _layer(f"{pre}input_blocks.{i}.", decoder)
@@ -50,11 +50,15 @@ def _skip(pre, decoder):
     return ks
 
 
-def key_shapes():
+def key_shapes(num_layers=NL):
+    """(key, shape) in checkpoint order for odd ``num_layers`` (the SkipTransformers' depth; everything else is fixed)."""
+    if num_layers < 1 or num_layers % 2 == 0:
+        raise ValueError(f"num_layers must be odd and positive (SkipTransformerEncoder asserts it), got {num_layers}")
+    nl = num_layers
     ks = [("body_global_motion_token", (2, D)), ("hands_global_motion_token", (2, D)),
           ("query_pos_encoder.pe", (1024, 1, D)), ("query_pos_decoder.pe", (1024, 1, D)), ("mem_pos_decoder.pe", (1024, 1, D))]
-    ks += _skip("body_encoder.", False) + _skip("hands_encoder.", False)
-    ks += _skip("body_decoder.", True) + _skip("hands_decoder.", True)
+    ks += _skip("body_encoder.", False, nl) + _skip("hands_encoder.", False, nl)
+    ks += _skip("body_decoder.", True, nl) + _skip("hands_decoder.", True, nl)
     ks += [("body_skel_embedding.weight", (D, BODY)), ("body_skel_embedding.bias", (D,)),
            ("hands_skel_embedding.weight", (D, HANDS)), ("hands_skel_embedding.bias", (D,)),
            ("body_final_layer.weight", (BODY, D)), ("body_final_layer.bias", (BODY,)),
@@ -62,10 +66,12 @@ def key_shapes():
     return ks
 
 
-def make_state_dict(seed=4321):
+def make_state_dict(seed=4321, num_layers=NL):
+    """The seeded state dict at depth ``num_layers`` (odd); the default is the 5-layer checkpoint layout the goldens were made with.
+    Another depth draws from the same stream in its own key order, so it shares no layer values with the default."""
     rng = np.random.Generator(np.random.PCG64(seed))
     sd = {}
-    for k, shp in key_shapes():
+    for k, shp in key_shapes(num_layers):
         if k.endswith(".pe"):
             sd[k] = sine_pe()
         elif "norm" in k and k.endswith("weight"):

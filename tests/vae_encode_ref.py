@@ -3,7 +3,7 @@
 Reference: convofusion/models/architectures/vae.py:162-266 (arch 'encoder_decoder', PE_TYPE 'convofusion', MLP_DIST False),
 SkipTransformerEncoder cross_attention.py:18-64, TransformerEncoderLayer.forward_pre :288-300, nn.MultiheadAttention with a key-padding
 mask, PositionEmbeddingSine1D position_encoding.py:113-136.  The root subtraction is done in float32 exactly as the reference does it (its
-result is compared bit for bit); everything after it runs in float64.  Pinned against the imported reference class by
+result is compared bit for bit); everything after it runs in float64 (or in the ``dtype`` the caller names).  Pinned against the imported reference class by
 tests/golden/vae_encode.npz (tests/golden/make_golden_vae_encode.py); used by the GPU tests for shapes too large for a fixture.
 """
 import math
@@ -32,6 +32,28 @@ def golden_cases():
     }
 
 
+DEPTH_CASE = "mix"   # the shape case tests/golden/vae_depths.npz holds at num_layers 1 and 9
+
+
+def shape_cases():
+    """name -> (features [bs, nframes, 189] float32, lengths): the small cases of tests/test_gpu_vae_encode_shapes.py, chosen by how their
+    bs * nframes / 16 sequences fall into workgroups of 1, 2 or 3 sequences (csrc/vae_enc.hpp):
+      one    1 sequence: a partial group at 2 and at 3 per group
+      span   4 sequences, valid frames 16, 16, 5, 0: at 3 per group the first group spans both batch items
+      mix    9 sequences, valid frames 16, 16, 16 | 16, 1, 0 | 0, 0, 0 (one batch item is empty); root x / z offset by +-50
+      seven  7 sequences of one chunk: the last group holds one sequence at 2 and at 3 per group"""
+    rng = np.random.Generator(np.random.PCG64(2025))
+    one = rng.standard_normal((1, 16, 189), dtype=np.float32)
+    span = rng.standard_normal((2, 32, 189), dtype=np.float32)
+    mix = rng.standard_normal((3, 48, 189), dtype=np.float32)
+    mix[0, :, 0] += 50.0
+    mix[0, :, 2] -= 50.0
+    mix[1, :, 0] -= 50.0
+    mix[1, :, 2] += 50.0
+    seven = rng.standard_normal((7, 16, 189), dtype=np.float32)
+    return {"one": (one, [16]), "span": (span, [32, 5]), "mix": (mix, [48, 17, 0]), "seven": (seven, [16, 15, 1, 16, 8, 16, 2])}
+
+
 def root_subtract(features):
     """features [bs, nframes, 189] float32 -> the same with frame 0's root x / z of every 16-frame chunk subtracted (vae.py:176-187)."""
     f = torch.as_tensor(np.asarray(features, np.float32)).clone()
@@ -42,8 +64,13 @@ def root_subtract(features):
     return m.reshape(bs, nframes, nf)
 
 
+def _cast(sd, dtype):
+    """the encoder's entries of a float32 numpy state dict as tensors of ``dtype`` (what ``_t`` reads)"""
+    return {k: torch.as_tensor(np.asarray(v)).to(dtype) for k, v in sd.items() if "decoder" not in k and "final_layer" not in k}
+
+
 def _t(sd, k):
-    return torch.as_tensor(np.asarray(sd[k])).to(torch.float64)
+    return sd[k]
 
 
 def _ln(x, sd, pre):
@@ -86,13 +113,15 @@ def _skip_encoder(x, sd, pre, num_layers, nhead, kpm):
     return _ln(x, sd, pre + "norm")
 
 
-def encode(sd, features, lengths, num_layers=5, nhead=2):
-    """-> mu, logvar (float64 numpy [2, bs * nframes / 16, 128], body then hands), root-subtracted features (float32 numpy)."""
+def encode(sd, features, lengths, num_layers=5, nhead=2, dtype=torch.float64):
+    """-> mu, logvar (numpy of ``dtype`` [2, bs * nframes / 16, 128], body then hands), root-subtracted features (float32 numpy).
+    dtype=torch.float32: everything behind the root subtraction in float32 (the yardstick of a float32 kernel's distance from float64)."""
+    sd = _cast(sd, dtype)
     feats = root_subtract(features)
     bs, nframes, _ = feats.shape
     n_chunks = nframes // 16
     n = bs * n_chunks
-    x = feats.reshape(n, 16, -1).to(torch.float64)
+    x = feats.reshape(n, 16, -1).to(dtype)
     valid = (torch.arange(nframes)[None, :] < torch.as_tensor(list(lengths))[:, None]).reshape(n, 16)
     kpm = ~torch.cat([torch.ones(n, 2, dtype=torch.bool), valid], 1)
     pe = _t(sd, "query_pos_encoder.pe")[:18]                                 # [18, 1, D]

@@ -179,6 +179,17 @@ def case_inputs(name):
     return z, list(lengths), d
 
 
+DEPTH_CASE = ((2, 2, 3, 128), [40, 17])   # three row tiles; the case of tests/golden/vae_depths.npz and tests/test_gpu_vae_depths.py
+
+
+def depth_case_inputs():
+    """(z float32, lengths, d_feats float32) of DEPTH_CASE, seeded like ``case_inputs``; the same at every depth."""
+    shape, lengths = DEPTH_CASE
+    z = np.random.Generator(np.random.PCG64(7702)).standard_normal(shape, dtype=np.float32)
+    d = np.random.Generator(np.random.PCG64(4200 + len("depths"))).standard_normal((shape[1], max(lengths), BODY + HANDS), dtype=np.float32)
+    return z, list(lengths), d
+
+
 def errors(got, want):
     """(relative L2, worst 128-wide row: the row's error norm over the RMS row norm) of gradients with a last axis of 128."""
     got, want = np.asarray(got, np.float64).reshape(-1, D), np.asarray(want, np.float64).reshape(-1, D)

@@ -30,7 +30,7 @@ SYMBOLS = [
     "cfd_debug_forward_operands", "cfd_denoise_vjp", "cfd_debug_live_buffers", "cfd_vae_decode_vjp", "cfd_denoise_vjp_mem",
     "cfd_vae_decode", "cfd_vae_decode_sweep", "cfd_vae_decode_ticket", "cfd_debug_vae_workspace", "cfd_denoise_guide", "cfd_guide_tie_csr",
     "cfd_denoise_guide_pose", "cfd_weg_step", "cfd_test_weg_focus_rows", "cfd_t5_encode", "cfd_audio_encode",
-    "cfd_audio_power",
+    "cfd_audio_power", "cfd_motion_eval", "cfd_motion_diversity",
 ]
 
 # cfd_sample_args.prediction_type / the _pred entry points, by the schedulers' config string
@@ -187,6 +187,15 @@ class AudioArgs(C.Structure):
                 ("amin", C.c_float), ("top_db", C.c_float), ("n_win", C.c_int), ("win_start", C.c_void_p), ("win_frames", C.c_int),
                 ("w0", C.c_void_p), ("b0", C.c_void_p), ("w1", C.c_void_p), ("b1", C.c_void_p), ("w2", C.c_void_p), ("b2", C.c_void_p),
                 ("hidden", C.c_int), ("latent", C.c_int), ("act_chunk", C.c_int), ("act_amin_power", C.c_float), ("act_thresh_power", C.c_float)]
+
+
+class MotionEvalArgs(C.Structure):
+    """cfd_motion_eval_args: one motion-evaluation call (cfd_motion_eval)."""
+    _fields_ = [("pred", C.c_void_p), ("target", C.c_void_p), ("semantic", C.c_void_p), ("n_seq", C.c_int), ("n_frames", C.c_int),
+                ("stride", C.c_longlong), ("fps", C.c_double), ("order", C.c_int), ("sigma", C.c_double), ("srgr_threshold", C.c_double),
+                ("onset_off", C.c_void_p), ("onset_t", C.c_void_p), ("n_onsets", C.c_int), ("fgd_pack", C.c_void_p), ("feature_length", C.c_int), ("embed_raw", C.c_int),
+                ("l1div", C.c_void_p), ("srgr", C.c_void_p), ("srgr_count", C.c_void_p), ("jitter", C.c_void_p), ("beats", C.c_void_p),
+                ("align", C.c_void_p), ("processed", C.c_void_p), ("embedding", C.c_void_p), ("stats", C.c_void_p)]
 
 
 # cfd_test_epi_args.kind (include/cfdenoise_dev.h)
@@ -354,6 +363,8 @@ def load():
     lib.cfd_vae_decode_ticket.restype = C.c_uint64
     lib.cfd_t5_encode.argtypes = [C.c_void_p, C.POINTER(T5Args), C.c_void_p, C.c_void_p]
     lib.cfd_audio_encode.argtypes = [C.c_void_p, C.POINTER(AudioArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.cfd_motion_eval.argtypes = [C.c_void_p, C.POINTER(MotionEvalArgs), C.c_void_p]
+    lib.cfd_motion_diversity.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p]
     lib.cfd_audio_power.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.cfd_debug_vae_workspace.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
     lib.cfd_dyadic_steps.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(DyadicProj), C.c_int]

@@ -136,6 +136,12 @@ extern "C" int cfd_debug_read(cfd_handle c, const char* what, float* dst_dev, si
     HIPCHK(hipMemcpy(dst_dev, f, sizeof(f), hipMemcpyHostToDevice));
     return CFD_OK;
   }
+  if (!strcmp(what, "metrics.info")) {   // the last cfd_motion_eval / cfd_motion_diversity: launches (0: refused), sequences, workspace bytes as allocated
+    if (numel < 3) return fail(CFD_E_ARG, "metrics.info needs 3 floats");
+    const float f[3] = {(float)c->metrics.launches, (float)c->metrics.rows, (float)c->metrics.ws.bytes};
+    HIPCHK(hipMemcpy(dst_dev, f, sizeof(f), hipMemcpyHostToDevice));
+    return CFD_OK;
+  }
   if (!strcmp(what, "t5.x")) {      // the residual stream behind the last block, [rows][768] (in front of the final norm)
     if (!c->t5.x) return fail(CFD_E_STATE, "no cfd_t5_encode has run on this handle");
     if (numel > (size_t)c->t5.rows * 768) return fail(CFD_E_ARG, "buffer 't5.x' holds %lld floats, asked for %zu", c->t5.rows * 768, numel);

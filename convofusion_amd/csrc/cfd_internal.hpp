@@ -369,6 +369,14 @@ struct cfd_handle_s {
     long long frames = 0, rows = 0;
     int launches = 0;
   } audio;
+  // cfd_motion_eval / cfd_motion_diversity (cfd_metrics.hip, metrics_eval.hpp): the call's workspace -- the processed motions and embeddings
+  // where the caller takes none, the embedding net's activations for 128 sequences, the diversity's block sums --, the launches of the last
+  // call (0: it was refused) and its sequences
+  struct MetricsState {
+    DBuf ws;
+    long long rows = 0;
+    int launches = 0;
+  } metrics;
   // profiling
   bool prof = false;
   hipEvent_t pev[2] = {nullptr, nullptr};

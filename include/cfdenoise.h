@@ -565,6 +565,67 @@ typedef struct {
 } cfd_audio_args;
 int cfd_audio_encode(cfd_handle h, const cfd_audio_args* a, float* mel_db, float* memory, int32_t* activity, float* peak, void* stream);
 
+/* Motion evaluation: what the reference's quant_eval/ scripts compute on the host, one motion at a time, from decoded motions
+ * [n_seq][n_frames][189] (63 joints x 3) on the device (csrc/metrics_eval.hpp).  1 launch for the per-sequence part; with the FGD embedding
+ * 5 more per 128 sequences and 1 for the statistics.  No atomics; reductions in float64 in one fixed order; the same bits on every call; a
+ * sequence's per-sequence outputs do not depend on what else is in the batch.
+ *   pred        dev float32: n_seq x n_frames rows of `stride` floats, the first 189 used.  1 <= n_seq <= 65535, 24 <= n_frames <= 128,
+ *               stride >= 189 (CFD_E_SHAPE otherwise)
+ *   target, semantic   dev float32, target laid out as pred, semantic [n_seq][n_frames]; NULL: none
+ *   fps, order, sigma, srgr_threshold   metric_eval.py:451-452 uses 25, 10, 0.3, 0.3; dyadic_eval.py:373 order 12, sigma 1.25
+ *   onset_off, onset_t, n_onsets   the audio onsets in seconds as a CSR pair: dev int32 [n_seq + 1] and dev float64 [n_onsets]; sequence b
+ *               owns onset_t[onset_off[b] .. onset_off[b + 1]) (offsets are clamped to [0, n_onsets]).  Onset detection stays with the caller.
+ *   fgd_pack, feature_length   HalfEmbeddingNet's pose encoder (motion_autoencoder.py:39-78), folded: per convolution W [N][k C_in]
+ *               (column kk C_in + c, the eval-mode BatchNorm folded in) and b [N] for net.0 .. net.3, then out_net and fc_mu as ONE affine
+ *               map W [F][59 F] (column t F + c) and b [F] -- their LeakyReLU(True) has negative_slope 1.0 (motion_autoencoder.py:52,55,58).
+ *               dev float32, me_pack_floats(F) floats.  Needs n_frames = 128 (CFD_E_SHAPE otherwise).
+ *   embed_raw   0: the net takes the processed motion (what the reference's scripts feed it); 1: it takes pred as it is, which is
+ *               HalfEmbeddingNet.forward on its own (needs stride = 189, CFD_E_SHAPE otherwise)
+ * Outputs, each may be NULL:
+ *   l1div       dev float64 [n_seq]: sum over frames and features of |x - the sequence's mean over frames| (metric_eval.py:342-356)
+ *   srgr, srgr_count   dev float64 / int32 [n_seq]: sum over frames and joints of [sum_xyz |pred - target| < threshold] x semantic[frame] / 0.165,
+ *               and the number of such (frame, joint) pairs (:317-339); need target and semantic (CFD_E_ARG without)
+ *   jitter      dev float64 [n_seq]: sum over (n_frames - 1) x 189 of | |d pred| - |d target| | (jitter_metric.py); needs target
+ *   beats       dev uint8 [n_seq][6][n_frames - 1]: frame i of track k (joints 5 6 7 9 10 11) is a beat iff its frame-to-frame speed is strictly
+ *               below that of frames clip(i +- s) for s = 1 .. order (:124-165: scipy.signal.argrelextrema(np.less, order, mode="clip"))
+ *   align       dev float64 [n_seq]: mean over the sequence's onsets of exp(-d^2 / 2 sigma^2), d = distance to the nearest beat of joint 11
+ *               at time frame / fps (:262-293); no beat: 0 per onset; no onset: 0 (the caller leaves the sequence out and counts it)
+ *   processed   dev float32 [n_seq][n_frames][189]: process_motion (:376-421) -- floor, XZ origin, facing from joints 18 13 9 5 of frame 0,
+ *               root-relative joints, wrist-relative hands
+ *   embedding   dev float32 [n_seq][feature_length]: the net's mu of the processed motion
+ *   stats       dev float64 [1 + F + F F], read and written: n, sum e, sum e e^T of every embedding so far (the Frechet distance itself is the
+ *               host's: np.cov with ddof = 1 and scipy.linalg.sqrtm, :21-90)
+ * Everything is refused before the first launch.  The workspace lives on the handle and only grows. */
+typedef struct {
+  const float* pred;
+  const float* target;
+  const float* semantic;
+  int n_seq, n_frames;
+  long long stride;
+  double fps;
+  int order;
+  double sigma, srgr_threshold;
+  const int32_t* onset_off;
+  const double* onset_t;
+  int n_onsets;
+  const float* fgd_pack;
+  int feature_length;
+  int embed_raw;
+  double* l1div;
+  double* srgr;
+  int32_t* srgr_count;
+  double* jitter;
+  uint8_t* beats;
+  double* align;
+  float* processed;
+  float* embedding;
+  double* stats;
+} cfd_motion_eval_args;
+int cfd_motion_eval(cfd_handle h, const cfd_motion_eval_args* a, void* stream);
+/* out[0] (dev float64) = the mean over all pairs i < j of the Euclidean distance between rows of x, dev float32 [n][d] (calculate_avg_distance,
+ * metric_eval.py:303-314): from the differences, accumulated in float64.  2 <= n <= 8192 (CFD_E_SHAPE otherwise); 2 launches. */
+int cfd_motion_diversity(cfd_handle h, const float* x, int n, long long d, double* out, void* stream);
+
 /* float32 pieces of word-excitation guidance (WEG): the attend-and-excite objective on the listener-text attention
  * maps and d(loss)/d(latents) through the denoiser -- what the reference gets from torch autograd over
  * Denoiser.forward (convofusion/models/modeltype/convofusion.py:437-496, iterative_refinement_step :298-388;

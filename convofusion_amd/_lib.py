@@ -30,7 +30,7 @@ SYMBOLS = [
     "cfd_debug_forward_operands", "cfd_denoise_vjp", "cfd_debug_live_buffers", "cfd_vae_decode_vjp", "cfd_denoise_vjp_mem",
     "cfd_vae_decode", "cfd_vae_decode_sweep", "cfd_vae_decode_ticket", "cfd_debug_vae_workspace", "cfd_denoise_guide", "cfd_guide_tie_csr",
     "cfd_denoise_guide_pose", "cfd_weg_step", "cfd_test_weg_focus_rows", "cfd_t5_encode", "cfd_audio_encode",
-    "cfd_audio_power", "cfd_motion_eval", "cfd_motion_diversity",
+    "cfd_audio_power", "cfd_motion_eval", "cfd_motion_diversity", "cfd_audio_onsets",
 ]
 
 # cfd_sample_args.prediction_type / the _pred entry points, by the schedulers' config string
@@ -187,6 +187,15 @@ class AudioArgs(C.Structure):
                 ("amin", C.c_float), ("top_db", C.c_float), ("n_win", C.c_int), ("win_start", C.c_void_p), ("win_frames", C.c_int),
                 ("w0", C.c_void_p), ("b0", C.c_void_p), ("w1", C.c_void_p), ("b1", C.c_void_p), ("w2", C.c_void_p), ("b2", C.c_void_p),
                 ("hidden", C.c_int), ("latent", C.c_int), ("act_chunk", C.c_int), ("act_amin_power", C.c_float), ("act_thresh_power", C.c_float)]
+
+
+class OnsetArgs(C.Structure):
+    """cfd_onset_args: one onset-detection call (cfd_audio_onsets)."""
+    _fields_ = [("wave", C.c_void_p), ("n_wave", C.c_int), ("n_samples", C.c_longlong), ("normalize", C.c_int), ("n_fft", C.c_int), ("hop", C.c_int),
+                ("n_mels", C.c_int), ("twiddle", C.c_void_p), ("window", C.c_void_p), ("melfb", C.c_void_p), ("mel_range", C.c_void_p),
+                ("amin", C.c_float), ("top_db", C.c_float), ("lag", C.c_int), ("pad_frames", C.c_int), ("pre_max", C.c_int), ("post_max", C.c_int),
+                ("pre_avg", C.c_int), ("post_avg", C.c_int), ("wait", C.c_int), ("delta", C.c_float), ("time_hop", C.c_int), ("time_sr", C.c_double),
+                ("capacity", C.c_int), ("envelope", C.c_void_p), ("rms", C.c_void_p), ("frames_raw", C.c_void_p), ("frames", C.c_void_p)]
 
 
 class MotionEvalArgs(C.Structure):
@@ -363,6 +372,7 @@ def load():
     lib.cfd_vae_decode_ticket.restype = C.c_uint64
     lib.cfd_t5_encode.argtypes = [C.c_void_p, C.POINTER(T5Args), C.c_void_p, C.c_void_p]
     lib.cfd_audio_encode.argtypes = [C.c_void_p, C.POINTER(AudioArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.cfd_audio_onsets.argtypes = [C.c_void_p, C.POINTER(OnsetArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.cfd_motion_eval.argtypes = [C.c_void_p, C.POINTER(MotionEvalArgs), C.c_void_p]
     lib.cfd_motion_diversity.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p]
     lib.cfd_audio_power.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -1,11 +1,12 @@
 """The log-Mel front end on the HIP path: waveforms to Mel frames in dB, audio memories and activity bits in one library call
-(cfd_audio_encode, csrc/audio_fe.hpp).
+(cfd_audio_encode, csrc/audio_fe.hpp), and the audio onsets of the beat alignment in another (``OnsetDetector``: cfd_audio_onsets,
+csrc/onset_fe.hpp).
 
 The reference makes these in its data loader on the CPU with librosa 0.10 (convofusion/data/beat_dnd/dataset.py: ``get_melspecs``
 :506-520 -- ``feature.melspectrogram`` + ``power_to_db(ref=np.max)`` --, ``check_audio`` :477-492 for the activity bits,
 ``util.normalize`` per BEAT chunk :473) and slices one utterance-long spectrogram per window for long-form runs
-(unbounded_synthesis.py:279-308).  ``AudioFrontEnd`` takes the waveform on the device instead; resampling and file decoding stay with
-the caller.  The tables (Slaney filterbank, periodic Hann window, twiddles) are built here in float64 and rounded once.
+(unbounded_synthesis.py:279-308).  ``AudioFrontEnd`` takes the waveform on the device instead; resampling and file decoding other than
+plain PCM stay with the caller.  The tables (Slaney filterbank, periodic Hann window, twiddles) are built here in float64 and rounded once.
 
 librosa is not a dependency and was not available where this was written: the semantics follow its documentation and are held to a
 float64 numpy restatement (tests/audio_ref.py); agreement with librosa itself is not verified (INTEGRATION.md section 3 has the
@@ -235,3 +236,112 @@ class AudioFrontEnd:
         from .conditioning import ACT_LEAKY01, ACT_NONE, linear_act
         w0, b0, w1, b1, w2, b2 = self._weights(mel.device)
         return linear_act(linear_act(linear_act(mel, w0, b0, ACT_LEAKY01), w1, b1, ACT_LEAKY01), w2, b2, ACT_NONE)
+
+
+# ---------------------------------------------------------------- onset detection (cfd_audio_onsets, csrc/onset_fe.hpp)
+ONSET_MAX_FRAMES = 2048          # what the detection workgroup's LDS plan holds (ONS_MAX_T)
+
+
+def onset_windows(detect_sr, hop_length):
+    """(pre_max, post_max, pre_avg, post_avg, wait) as ``librosa.onset.onset_detect`` derives them for ``peak_pick``: 0.03 s, 0.00 s + 1,
+    0.10 s, 0.10 s + 1 and 0.03 s in frames of ``hop_length`` at ``detect_sr``, floor-divided as floats.  The reference passes no ``sr``,
+    so its windows are those of librosa's default 22050: (1, 1, 4, 5, 1) at hop 512."""
+    sr, hop = detect_sr, hop_length
+    return (int(0.03 * sr // hop), int(0.00 * sr // hop + 1), int(0.10 * sr // hop), int(0.10 * sr // hop + 1), int(0.03 * sr // hop))
+
+
+class OnsetResult:
+    """What ``OnsetDetector.forward`` returns, all on the device: ``csr`` = (offsets int32 [U + 1], times float64 [capacity]) -- the pair
+    ``metrics.motion_eval`` takes; waveform u owns entries offsets[u] .. offsets[u + 1] --, ``frames_raw`` / ``frames`` int32 [capacity]
+    (the accepted frames and the backtracked ones, same segments), ``envelope`` / ``rms`` float32 [U, T], ``n_total`` int32 [1]."""
+
+    def __init__(self, csr, frames_raw, frames, envelope, rms, n_total):
+        self.csr, self.frames_raw, self.frames, self.envelope, self.rms, self.n_total = csr, frames_raw, frames, envelope, rms, n_total
+
+    def host(self):
+        """Host lists, one numpy array per waveform: (times float64, frames_raw int32, frames int32).  This is the one place that waits for
+        the device and reads the total."""
+        off = self.csr[0].cpu().numpy()
+        n = int(self.n_total.item())
+        t, fr, fb = self.csr[1][:n].cpu().numpy(), self.frames_raw[:n].cpu().numpy(), self.frames[:n].cpu().numpy()
+        cut = lambda x: [x[off[u]:off[u + 1]] for u in range(len(off) - 1)]
+        return cut(t), cut(fr), cut(fb)
+
+
+class OnsetDetector:
+    """Waveform [U, n_samples] (float32, CUDA, mono, equal lengths, at ``sample_rate``) -> audio onsets, as the reference's
+    ``Alignment.load_audio`` (quant_eval/metric_eval.py:102-122) gets them from librosa 0.10: ``onset_strength(y, sr)``,
+    ``onset_detect(onset_envelope, backtrack=False)``, ``feature.rms(S=|stft(y)|)``, ``onset_backtrack``, ``frames_to_time``.
+
+    ``detect_sr`` sets the five window integers and ``time_sr`` the times (frame * hop_length / time_sr).  **Both default to 22050, not to
+    the audio's 16000**: the reference passes no ``sr`` to ``onset_detect`` and ``frames_to_time``, so librosa's default rate applies;
+    that is the reference's number, and 16000 can be chosen knowingly.  **librosa is not a dependency and agreement with librosa itself is
+    not verified**: the formulas are librosa 0.10's as documented, held to the float64 restatement tests/onset_ref.py."""
+
+    def __init__(self, sample_rate=16000, n_fft=2048, hop_length=512, n_mels=128, detect_sr=22050, time_sr=22050, delta=0.07, lag=1,
+                 amin=AMIN, top_db=TOP_DB):
+        self.sample_rate, self.n_fft, self.hop_length, self.n_mels = int(sample_rate), int(n_fft), int(hop_length), int(n_mels)
+        self.detect_sr, self.time_sr, self.delta, self.lag = detect_sr, float(time_sr), float(delta), int(lag)
+        self.amin, self.top_db = float(amin), float(top_db)
+        if self.n_fft not in N_FFT_SUPPORTED:
+            raise ValueError(f"OnsetDetector: n_fft must be one of {N_FFT_SUPPORTED} (got {n_fft})")
+        if self.hop_length < 1 or self.sample_rate < 1:
+            raise ValueError(f"OnsetDetector: hop_length and sample_rate must be at least 1 (got {hop_length}, {sample_rate})")
+        if not 1 <= self.n_mels <= self.n_fft // 2 + 1:
+            raise ValueError(f"OnsetDetector: 1 <= n_mels <= n_fft / 2 + 1 = {self.n_fft // 2 + 1} (got {n_mels})")
+        if not detect_sr > 0 or not self.time_sr > 0:
+            raise ValueError(f"OnsetDetector: detect_sr and time_sr must be positive (got {detect_sr}, {time_sr})")
+        if not self.delta >= 0 or self.lag < 1 or not self.amin > 0 or not self.top_db >= 0:
+            raise ValueError(f"OnsetDetector: delta >= 0, lag >= 1, amin > 0 and top_db >= 0 (got {delta}, {lag}, {amin}, {top_db})")
+        self.windows = onset_windows(detect_sr, self.hop_length)
+        pre_max, post_max, pre_avg, post_avg, wait = self.windows
+        if min(pre_max, pre_avg, wait) < 0 or post_max < 1 or post_avg < 1:
+            raise ValueError(f"OnsetDetector: the windows (pre_max, post_max, pre_avg, post_avg, wait) = {self.windows} are negative or empty")
+        self.pad_frames = self.lag + self.n_fft // (2 * self.hop_length)
+        self._tables = {}
+
+    tables = AudioFrontEnd.tables           # (twiddle, window, melfb, mel_range) per device, built once
+
+    def forward(self, wave, *, normalize=True):
+        """wave [U, n_samples] (or [n_samples]) float32 on the device.  normalize: divide every waveform by its own max|y| first
+        (``librosa.util.normalize``, as the reference does).  Returns an ``OnsetResult``; nothing visits the host."""
+        if not isinstance(wave, torch.Tensor) or wave.dim() not in (1, 2) or not wave.is_floating_point():
+            raise ValueError("OnsetDetector: wave must be a float tensor [U, n_samples] or [n_samples]")
+        if wave.dim() == 1:
+            wave = wave[None]
+        U, n = (int(v) for v in wave.shape)
+        if not 1 <= U <= 65535 or not 1 <= n <= MAX_SAMPLES:
+            raise ValueError(f"OnsetDetector: 1 <= n_samples <= {MAX_SAMPLES} and 1 to 65535 waveforms (got {U} x {n})")
+        T = frame_count(n, self.hop_length)
+        if T > ONSET_MAX_FRAMES:
+            raise ValueError(f"OnsetDetector: {T} frames per waveform, one call holds {ONSET_MAX_FRAMES} "
+                             f"(fewer than {ONSET_MAX_FRAMES * self.hop_length} samples at hop {self.hop_length}); split the clip")
+        if wave.device.type != "cuda":
+            raise RuntimeError("convofusion_amd.audio runs on an MI355X only (tensors must be on 'cuda'); no CPU fallback")
+        dev = wave.device
+        y = wave.detach().to(torch.float32).contiguous()
+        t = self.tables(dev)
+        cap = U * T
+        a = _lib.OnsetArgs()
+        a.wave, a.n_wave, a.n_samples, a.normalize = y.data_ptr(), U, n, int(bool(normalize))
+        a.n_fft, a.hop, a.n_mels = self.n_fft, self.hop_length, self.n_mels
+        a.twiddle, a.window, a.melfb, a.mel_range = t.twiddle.data_ptr(), t.window.data_ptr(), t.melfb.data_ptr(), t.mel_range.data_ptr()
+        a.amin, a.top_db, a.lag, a.pad_frames = self.amin, self.top_db, self.lag, self.pad_frames
+        a.pre_max, a.post_max, a.pre_avg, a.post_avg, a.wait = self.windows
+        a.delta, a.time_hop, a.time_sr, a.capacity = self.delta, self.hop_length, self.time_sr, cap
+        off = torch.empty(U + 1, device=dev, dtype=torch.int32)
+        times = torch.empty(cap, device=dev, dtype=torch.float64)
+        raw = torch.empty(cap, device=dev, dtype=torch.int32)
+        bt = torch.empty(cap, device=dev, dtype=torch.int32)
+        env = torch.empty(U, T, device=dev, dtype=torch.float32)
+        rms = torch.empty(U, T, device=dev, dtype=torch.float32)
+        n_total = torch.empty(1, device=dev, dtype=torch.int32)
+        a.envelope, a.rms, a.frames_raw, a.frames = env.data_ptr(), rms.data_ptr(), raw.data_ptr(), bt.data_ptr()
+        from .conditioning import _engine_handle
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(_lib.load().cfd_audio_onsets(_engine_handle(dev), C.byref(a), C.c_void_p(off.data_ptr()), C.c_void_p(times.data_ptr()),
+                                                    C.c_void_p(n_total.data_ptr()), C.c_void_p(stream)))
+        return OnsetResult((off, times), raw, bt, env, rms, n_total)
+
+    __call__ = forward

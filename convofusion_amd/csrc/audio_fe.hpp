@@ -2,6 +2,7 @@
 // loader does with librosa (melspectrogram + power_to_db(ref=np.max), util.normalize, amplitude_to_db per 16-frame chunk) as four kernels:
 //   afe_peak_kernel    per waveform: max|y| of every chunk, the waveform's peak, the activity bits            (one workgroup per waveform)
 //   afe_frame_kernel   per frame: window -> FFT -> power -> Mel, all inside one workgroup                      (one workgroup per frame)
+//                      (for cfd_audio_onsets, onset_fe.hpp, also the frame's energy from the same power spectrum)
 //   afe_max_kernel     per waveform: the largest Mel power (power_to_db's ref=np.max)                         (one workgroup per waveform)
 //   afe_db_kernel      per output element: dB against the waveform's max, the top_db clip, the window slice
 // No atomics anywhere; max is exact in any order, and every sum has one fixed order, so a call gives the same bits every time and a
@@ -84,6 +85,7 @@ struct AfeFrameArgs {
   const float* melfb;         // [n_mels][n_fft / 2 + 1]
   const int* mel_range;       // [n_mels][2] or null
   float* out;                 // POWER: [n_wave][T][n_fft / 2 + 1] power; else [n_wave][T][n_mels] Mel power
+  float* rms;                 // Mel instance only, or null: [n_wave][T] frame energy (librosa.feature.rms(S=|stft|)) of the same transform
 };
 
 // Frame f of waveform u: samples f hop - n_fft / 2 ... + n_fft of the waveform (zero outside it: center=True, pad_mode="constant"), each
@@ -142,6 +144,21 @@ __global__ void __launch_bounds__(AFE_THREADS) afe_frame_kernel(AfeFrameArgs a) 
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d);
     if (lane == 0) a.out[((long long)u * a.T + f) * a.n_mels + m] = acc;
+  }
+  if (a.rms) {      // sqrt(2 (sum_k P[k] - P[0] / 2 - P[n_fft / 2] / 2) / n_fft^2): thread-strided partial sums, the xor tree, the waves in order
+    __shared__ float red[AFE_THREADS / 64];
+    float acc = 0.f;
+    for (int k = tid; k <= NC; k += AFE_THREADS) acc += (k == 0 || k == NC) ? 0.5f * pw[k] : pw[k];
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d);
+    if (lane == 0) red[tid >> 6] = acc;
+    __syncthreads();
+    if (tid == 0) {
+      float s = red[0];
+#pragma unroll
+      for (int i = 1; i < AFE_THREADS / 64; ++i) s += red[i];
+      a.rms[(long long)u * a.T + f] = sqrtf(2.0f * s / ((float)(2 * NC) * (float)(2 * NC)));
+    }
   }
 }
 

@@ -1,7 +1,9 @@
 // libcfdenoise: the log-Mel front end -- waveforms to Mel frames in dB, AudioConvEncoder's memories and the activity bits in one call
-// (cfd_audio_encode; kernels, the FFT and its LDS layout: audio_fe.hpp), and its FFT stage alone (cfd_audio_power).
+// (cfd_audio_encode; kernels, the FFT and its LDS layout: audio_fe.hpp), its FFT stage alone (cfd_audio_power), and the audio onsets of
+// the beat alignment as the CSR pair cfd_motion_eval takes (cfd_audio_onsets; onset_fe.hpp).
 #include "cfd_internal.hpp"
 #include "audio_fe.hpp"
+#include "onset_fe.hpp"
 
 constexpr long long AFE_MAX_SAMPLES = 1LL << 26;
 
@@ -131,5 +133,85 @@ extern "C" int cfd_audio_power(cfd_handle c, const float* wave, int n_wave, long
   c->audio.frames = f.T;
   c->audio.rows = n_wave;
   c->audio.launches = 1;
+  return CFD_OK;
+}
+
+extern "C" int cfd_audio_onsets(cfd_handle c, const cfd_onset_args* a, int32_t* onset_off, double* onset_t, int32_t* n_total, void* stream) {
+  if (!c) return fail(CFD_E_ARG, "null handle");
+  c->audio.launches = 0;
+  if (!a || !a->wave || !a->twiddle || !a->window || !a->melfb || !onset_off) return fail(CFD_E_ARG, "cfd_audio_onsets: bad argument (NULL pointer)");
+  CHK(check_transform("cfd_audio_onsets", a->n_wave, a->n_samples, a->n_fft, a->hop));
+  if (a->n_mels < 1 || a->n_mels > a->n_fft / 2 + 1)
+    return fail(CFD_E_ARG, "cfd_audio_onsets: 1 <= n_mels <= n_fft / 2 + 1 = %d (got %d)", a->n_fft / 2 + 1, a->n_mels);
+  if (!(a->amin > 0.f) || !(a->top_db >= 0.f)) return fail(CFD_E_ARG, "cfd_audio_onsets: amin > 0 and top_db >= 0 (got %g, %g)", (double)a->amin, (double)a->top_db);
+  if (a->normalize != 0 && a->normalize != 1) return fail(CFD_E_ARG, "cfd_audio_onsets: normalize is 0 or 1 (got %d)", a->normalize);
+  if (a->lag < 1 || a->pad_frames < a->lag) return fail(CFD_E_ARG, "cfd_audio_onsets: lag >= 1 and pad_frames >= lag (got %d, %d)", a->lag, a->pad_frames);
+  if (a->pre_max < 0 || a->pre_avg < 0 || a->wait < 0)
+    return fail(CFD_E_ARG, "cfd_audio_onsets: pre_max, pre_avg and wait must not be negative (got %d, %d, %d)", a->pre_max, a->pre_avg, a->wait);
+  if (a->post_max < 1 || a->post_avg < 1)       // (a window [n - pre, n + post) without frame n itself; post = 0 with pre = 0 is an empty one)
+    return fail(CFD_E_ARG, "cfd_audio_onsets: post_max and post_avg must be at least 1 (got %d, %d)", a->post_max, a->post_avg);
+  if (!(a->delta >= 0.f)) return fail(CFD_E_ARG, "cfd_audio_onsets: delta must not be negative (got %g)", (double)a->delta);
+  if (a->time_hop < 1 || !(a->time_sr > 0.0)) return fail(CFD_E_ARG, "cfd_audio_onsets: time_hop >= 1 and time_sr > 0 (got %d, %g)", a->time_hop, a->time_sr);
+  const long long T = 1 + a->n_samples / a->hop;
+  if (T > ONS_MAX_T)
+    return fail(CFD_E_SHAPE, "cfd_audio_onsets: %lld frames per waveform, the detection workgroup holds %d (n_samples < %lld at this hop)", T, ONS_MAX_T,
+                (long long)ONS_MAX_T * a->hop);
+  // two accepted onsets lie more than `wait` frames apart, so a waveform has at most ceil(T / (wait + 1)): the capacity is judged by that
+  // bound, in front of the first launch, not by what the data turn out to hold
+  const long long per_wave = (T + a->wait) / ((long long)a->wait + 1), worst = per_wave * a->n_wave;
+  if (a->capacity < 0 || a->capacity < worst)
+    return fail(CFD_E_SHAPE, "cfd_audio_onsets: capacity %d is below the %lld onsets %d waveforms of %lld frames can have at wait = %d", a->capacity, worst,
+                a->n_wave, T, a->wait);
+  if (worst > 0 && !onset_t) return fail(CFD_E_ARG, "cfd_audio_onsets: bad argument (NULL onset_t)");
+  if ((long long)a->n_wave * T * a->n_mels > (1LL << 36))
+    return fail(CFD_E_SHAPE, "cfd_audio_onsets: too many frames for one call (%d waveforms x %lld frames x %d bands)", a->n_wave, T, a->n_mels);
+  HIPCHK(hipSetDevice(c->cfg.device));
+  hipStream_t st = (hipStream_t)stream;
+
+  const int chunk = 4096;
+  const long long n_chunks = (a->n_samples + chunk - 1) / chunk;
+  float *chunkmax, *peak_ws, *melpow, *rms;
+  int32_t *slot_raw, *slot_bt, *count;
+  for (int pass = 0; pass < 2; ++pass) {
+    ArenaLayout lay(pass ? c->audio.ws.as<float>() : nullptr, 64);
+    lay.take(chunkmax, a->normalize ? (size_t)(a->n_wave * n_chunks) : 0);
+    lay.take(peak_ws, (size_t)a->n_wave);
+    lay.take(melpow, (size_t)a->n_wave * T * a->n_mels);
+    lay.take(rms, a->rms ? 0 : (size_t)a->n_wave * T);
+    lay.take(slot_raw, (size_t)a->n_wave * T);
+    lay.take(slot_bt, (size_t)a->n_wave * T);
+    lay.take(count, (size_t)a->n_wave);
+    if (!pass && lay.bytes() > c->audio.ws.bytes) {
+      HIPCHK(hipDeviceSynchronize());          // an earlier call on another stream may still read the buffer that is about to be freed
+      CHK(c->audio.ws.ensure(lay.bytes()));
+    }
+  }
+  if (a->rms) rms = a->rms;
+  c->audio.frames = T;
+  c->audio.rows = a->n_wave;
+
+  int launches = 0;
+  if (a->normalize) {
+    hipLaunchKernelGGL(afe_peak_kernel, dim3((unsigned)a->n_wave), dim3(AFE_RED_THREADS), 0, st, a->wave, a->n_samples, chunk, n_chunks, 1, 0.f, 0.f,
+                       chunkmax, peak_ws, (float*)nullptr, (int*)nullptr, 0LL);
+    HIPCHK(hipGetLastError());
+    ++launches;
+  }
+  AfeFrameArgs f{};
+  f.wave = a->wave; f.peak = a->normalize ? peak_ws : nullptr; f.n_samples = a->n_samples; f.T = T; f.hop = a->hop; f.n_mels = a->n_mels;
+  f.tw = (const float2*)a->twiddle; f.window = a->window; f.melfb = a->melfb; f.mel_range = a->mel_range; f.out = melpow; f.rms = rms;
+  CHK(enqueue_frames<false>(f, a->n_fft, a->n_wave, st));
+  OnsArgs d{};
+  d.melpow = melpow; d.rms = rms; d.T = (int)T; d.n_mels = a->n_mels; d.amin = a->amin; d.top_db = a->top_db; d.lag = a->lag; d.pad_frames = a->pad_frames;
+  d.pre_max = a->pre_max; d.post_max = a->post_max; d.pre_avg = a->pre_avg; d.post_avg = a->post_avg; d.wait = a->wait; d.delta = a->delta;
+  d.env_out = a->envelope; d.slot_raw = slot_raw; d.slot_bt = slot_bt; d.count = count;
+  hipLaunchKernelGGL(ons_detect_kernel, dim3((unsigned)a->n_wave), dim3(ONS_THREADS), 0, st, d);
+  HIPCHK(hipGetLastError());
+  OnsCsrArgs s{};
+  s.count = count; s.slot_raw = slot_raw; s.slot_bt = slot_bt; s.n_wave = a->n_wave; s.T = (int)T; s.capacity = a->capacity; s.time_hop = a->time_hop;
+  s.time_sr = a->time_sr; s.onset_off = onset_off; s.onset_t = onset_t; s.raw_out = a->frames_raw; s.bt_out = a->frames; s.n_total = n_total;
+  hipLaunchKernelGGL(ons_csr_kernel, dim3(1), dim3(ONS_THREADS), 0, st, s);
+  HIPCHK(hipGetLastError());
+  c->audio.launches = launches + 3;
   return CFD_OK;
 }

@@ -130,7 +130,7 @@ extern "C" int cfd_debug_read(cfd_handle c, const char* what, float* dst_dev, si
     HIPCHK(hipMemcpy(dst_dev, f, sizeof(f), hipMemcpyHostToDevice));
     return CFD_OK;
   }
-  if (!strcmp(what, "audio.info")) {   // the last cfd_audio_encode / cfd_audio_power: launches (0: refused), frames per waveform, output rows, workspace bytes as allocated
+  if (!strcmp(what, "audio.info")) {   // the last cfd_audio_encode / cfd_audio_power / cfd_audio_onsets: launches (0: refused), frames per waveform, output rows, workspace bytes as allocated
     if (numel < 4) return fail(CFD_E_ARG, "audio.info needs 4 floats");
     const float f[4] = {(float)c->audio.launches, (float)c->audio.frames, (float)c->audio.rows, (float)c->audio.ws.bytes};
     HIPCHK(hipMemcpy(dst_dev, f, sizeof(f), hipMemcpyHostToDevice));

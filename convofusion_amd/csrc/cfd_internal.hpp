@@ -363,7 +363,8 @@ struct cfd_handle_s {
   } t5;
   // cfd_audio_encode / cfd_audio_power (cfd_audio.hip, audio_fe.hpp): the call's workspace -- per waveform the chunk maxima, peak and largest
   // Mel power, the Mel powers [n_wave][T][n_mels], and where the call needs them the dB rows and the MLP's two hidden layers --, the
-  // launches of the last call (0: it was refused), its frames per waveform and its output rows
+  // launches of the last call (0: it was refused), its frames per waveform and its output rows.  cfd_audio_onsets (onset_fe.hpp) carves
+  // the same buffer: peaks, Mel powers, frame energies, two onset slots of T frames per waveform and the counts
   struct AudioState {
     DBuf ws;
     long long frames = 0, rows = 0;

@@ -4,13 +4,15 @@ motions [B, T, 189] in one library call per batch (cfd_motion_eval, csrc/metrics
 
 The reference scores its results on the host with quant_eval/ (metric_eval.py, dyadic_eval.py, jitter_metric.py, motion_autoencoder.py):
 one motion at a time through a 114 M-parameter auto-encoder and a Python double loop over all pairs.  ``MotionEvaluator.update`` takes the
-tensor ``ConvoFusionVae.decode`` returns, without a host copy.  What stays with the caller: the audio onset times (the reference's
-``Alignment.load_audio`` uses librosa's onset detection, which is not a dependency here), file decoding, and the FGD net's checkpoint.
+tensor ``ConvoFusionVae.decode`` returns, without a host copy.  The audio onsets of the beat alignment are detected on the device too when
+the waveforms are given (``audio=``: ``audio.OnsetDetector``, what the reference's ``Alignment.load_audio`` gets from librosa; librosa is
+not a dependency and agreement with it is not verified).  What stays with the caller: resampling, decoding audio files other than plain
+16-bit PCM, and the FGD net's checkpoint.
 
 ``FGDNet`` mirrors ``HalfEmbeddingNet``'s pose encoder and its state-dict keys.  ``nn.LeakyReLU(True)`` in its ``out_net``
 (motion_autoencoder.py:52,55,58) sets negative_slope = True = 1.0: the identity.  So ``out_net`` followed by ``fc_mu`` is one affine map
 59 F -> F, folded here in float64: 17 700 x 300 numbers at the product width instead of 113 M.  The eval-mode BatchNorms are folded too.
-Not built: onset detection, the commented-out ``smoothing()``, the decoder half of the auto-encoder, training.  Inference only, CUDA
+Not built: the commented-out ``smoothing()``, the decoder half of the auto-encoder, training.  Inference only, CUDA
 tensors only, no CPU fallback.
 """
 import ctypes as C
@@ -149,12 +151,35 @@ def _dptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
+_default_detector = None
+
+
+def detect_onsets(audio, n_seq, dev, onset_detector=None):
+    """The CSR pair (offsets int32 [n_seq + 1], times float64 [capacity]) of the waveforms ``audio`` [n_seq, n_samples], float32 on ``dev``;
+    everything is checked before device work."""
+    global _default_detector
+    if not isinstance(audio, torch.Tensor) or audio.dim() != 2 or not audio.is_floating_point() or int(audio.shape[0]) != n_seq:
+        raise ValueError(f"motion_eval: audio must be a float tensor [{n_seq}, n_samples], one waveform per sequence")
+    if audio.device != dev:
+        raise ValueError("motion_eval: audio must be on pred's device")
+    if onset_detector is None:
+        if _default_detector is None:
+            from .audio import OnsetDetector
+            _default_detector = OnsetDetector()
+        onset_detector = _default_detector
+    return onset_detector.forward(audio).csr
+
+
 def motion_eval(pred, target=None, semantic=None, onsets=None, *, fgd_net=None, stats=None, fps=25, order=10, sigma=0.3, srgr_threshold=0.3,
-                want=None, embed_raw=False):
+                want=None, embed_raw=False, audio=None, onset_detector=None):
     """One cfd_motion_eval call.  pred / target [B, T, >=189] float32 on the device (the last axis may be a wider view: its stride is
     passed on), semantic [B, T]; onsets: a list of B sequences of onset times in seconds (an empty one: no onsets), or a pair
-    (offsets int32 [B + 1], times float64 [n]) already on the device.  ``embed_raw``: the net embeds pred as it is (``FGDNet.forward``), not the
-    processed motion (what the reference's scripts feed it).  Returns a dict of device tensors; ``want`` limits it."""
+    (offsets int32 [B + 1], times float64 [n]) already on the device.  audio: instead of onsets, the B waveforms [B, n_samples] float32
+    on the device; their onsets are detected there by ``onset_detector`` (None: ``audio.OnsetDetector()``, the reference's settings) and
+    go to the alignment on the same stream without visiting the host.  ``embed_raw``: the net embeds pred as it is (``FGDNet.forward``), not
+    the processed motion (what the reference's scripts feed it).  Returns a dict of device tensors; ``want`` limits it."""
+    if audio is not None and onsets is not None:
+        raise ValueError("motion_eval: give onsets or audio, not both")
     if not isinstance(pred, torch.Tensor) or pred.dim() != 3 or pred.dtype != torch.float32:
         raise ValueError("motion_eval: pred must be a float32 tensor [B, T, 189]")
     if pred.device.type != "cuda":
@@ -163,6 +188,8 @@ def motion_eval(pred, target=None, semantic=None, onsets=None, *, fgd_net=None, 
     B, T, W = (int(v) for v in pred.shape)
     if W < FEAT:
         raise ValueError(f"motion_eval: a frame is {FEAT} floats (got {W})")
+    if audio is not None:
+        onsets = detect_onsets(audio, B, dev, onset_detector)
 
     def rows(x, name):
         if x.shape != pred.shape or x.dtype != torch.float32 or x.device != dev:
@@ -309,20 +336,31 @@ class MotionEvaluator:
         s = self._stats[which]
         return s.cpu().numpy() if s is not None else self._loaded[which]
 
-    def update(self, pred, target=None, semantic=None, onsets=None):
+    def update(self, pred, target=None, semantic=None, onsets=None, audio=None, onset_detector=None):
         """pred [B, T, 189] float32 on the device, straight from ``vae.decode``; target likewise; semantic [B, T]; onsets: B lists of onset
-        times in seconds.  Nothing is copied to the host."""
+        times in seconds, or audio: the B waveforms [B, n_samples] on the device, whose onsets are detected there (``onset_detector``:
+        None for the reference's settings).  Nothing is copied to the host; with audio the sequences without an onset are counted on the
+        device from the offsets, and ``compute()`` reads the count."""
+        if audio is not None and onsets is not None:
+            raise ValueError("MotionEvaluator.update: give onsets or audio, not both")
         if pred.device.type != "cuda":
             raise NotImplementedError("convofusion_amd.metrics runs on an MI355X only (tensors must be on 'cuda'); no CPU fallback")
         B, T = int(pred.shape[0]), int(pred.shape[1])
         embed = self.fgd_net is not None and T == EMB_FRAMES
         kw = dict(fps=self.fps, order=self.order, sigma=self.sigma, srgr_threshold=self.srgr_threshold)
         want = {"l1div", "srgr", "jitter", "align", "processed"}
+        from_audio = audio is not None
+        if from_audio:
+            onsets = detect_onsets(audio, B, pred.device, onset_detector)
         r = motion_eval(pred, target, semantic, onsets, fgd_net=self.fgd_net if embed else None,
                         stats=self._state("pred", pred.device) if embed else None, want=want, **kw)
         self._proc["pred"].append(r["processed"])
         counted = None
-        if "align" in r:
+        if "align" in r and from_audio:
+            has = onsets[0][1:] > onsets[0][:-1]
+            counted = has.sum()                     # (a device scalar: compute() reads it)
+            align = (r["align"] * has).sum()
+        elif "align" in r:
             off = np.concatenate([[0], np.cumsum([len(o) for o in onsets])]) if not isinstance(onsets, tuple) else onsets[0].cpu().numpy()
             has = torch.from_numpy(np.diff(off) > 0).to(pred.device)
             counted = int((np.diff(off) > 0).sum())
@@ -357,7 +395,7 @@ class MotionEvaluator:
         sp, st = self._host_stats("pred"), self._host_stats("target")
         if sp is not None and st is not None:
             out["fgd"] = frechet_distance_from_stats(sp, st)
-        counted = sum(s[4] for s in self._sums if s[4] is not None)
+        counted = sum(int(s[4]) for s in self._sums if s[4] is not None)
         if any(s[4] is not None for s in self._sums):
             out["align_counted"] = counted
             out["align"] = total(3) / counted if counted else None
@@ -413,12 +451,50 @@ def read_result_dir(path):
     return np.stack(gt), np.stack(pred), np.stack(sem), ons if any_onsets else None
 
 
-def evaluate_result_dir(path, fgd_net=None, batch=64, device="cuda", **kwargs):
-    """Score a directory of the reference's results; ``kwargs`` go to ``MotionEvaluator``.  Returns ``compute()``'s dict."""
+WAV_RATE = 16000
+
+
+def read_wav_pcm16(path, rate=WAV_RATE):
+    """A 16-bit PCM mono wav file at ``rate`` as float32 in [-1, 1) (samples / 32768), read with the standard library.  Anything else
+    raises: resampling and other encodings stay with the caller."""
+    import wave
+    try:
+        with wave.open(path, "rb") as w:
+            ch, width, sr, n, comp = w.getnchannels(), w.getsampwidth(), w.getframerate(), w.getnframes(), w.getcomptype()
+            raw = w.readframes(n)
+    except (wave.Error, EOFError) as e:
+        raise ValueError(f"{path}: not a plain PCM wav file ({e}); resampling and other encodings stay with the caller") from e
+    if ch != 1 or width != 2 or sr != int(rate) or comp != "NONE":
+        raise ValueError(f"{path}: {ch} channel(s), {8 * width}-bit, {sr} Hz, compression {comp}: only 16-bit PCM mono at {int(rate)} Hz is read "
+                         "here; resampling and other encodings stay with the caller")
+    return np.frombuffer(raw, dtype="<i2").astype(np.float32) / np.float32(32768.0)
+
+
+def read_result_audio(path):
+    """``lsn_audio.wav`` beside every ``*/*/gt.npy`` under ``path`` (the order of ``read_result_dir``) as float32 [N, n_samples]; the clips
+    must be equally long."""
+    files = sorted(glob.glob(os.path.join(path, "*", "*", "gt.npy")))
+    if not files:
+        raise FileNotFoundError(f"no */*/gt.npy under {path}")
+    waves = [read_wav_pcm16(os.path.join(os.path.dirname(f), "lsn_audio.wav")) for f in files]
+    if any(len(w) != len(waves[0]) for w in waves) or len(waves[0]) < 1:
+        raise ValueError("read_result_audio: every lsn_audio.wav must have the same, non-zero number of samples (equal-length clips only)")
+    return np.stack(waves)
+
+
+def evaluate_result_dir(path, fgd_net=None, batch=64, device="cuda", detect_onsets=False, onset_detector=None, **kwargs):
+    """Score a directory of the reference's results; ``kwargs`` go to ``MotionEvaluator``.  Returns ``compute()``'s dict.
+    detect_onsets: the onsets of the alignment come from ``lsn_audio.wav`` beside each ``gt.npy`` (16-bit PCM mono at 16 kHz), detected
+    on the device by ``onset_detector`` (None: the reference's settings); ``onsets.npy`` files are then not used."""
     gt, pred, sem, ons = read_result_dir(path)
+    audio = read_result_audio(path) if detect_onsets else None
     ev = MotionEvaluator(fgd_net, **kwargs)
     for s in range(0, gt.shape[0], int(batch)):
         e = min(s + int(batch), gt.shape[0])
+        if audio is not None:
+            ev.update(torch.from_numpy(pred[s:e]).to(device), torch.from_numpy(gt[s:e]).to(device), torch.from_numpy(sem[s:e]).to(device),
+                      audio=torch.from_numpy(audio[s:e]).to(device), onset_detector=onset_detector)
+            continue
         ev.update(torch.from_numpy(pred[s:e]).to(device), torch.from_numpy(gt[s:e]).to(device), torch.from_numpy(sem[s:e]).to(device),
                   ons[s:e] if ons is not None else None)
     return ev.compute()

@@ -565,6 +565,57 @@ typedef struct {
 } cfd_audio_args;
 int cfd_audio_encode(cfd_handle h, const cfd_audio_args* a, float* mel_db, float* memory, int32_t* activity, float* peak, void* stream);
 
+/* The audio onsets of the beat alignment, on the device: what the reference's Alignment.load_audio (quant_eval/metric_eval.py:102-122,
+ * dyadic_eval.py:96-114) gets from librosa 0.10 on the host, one clip at a time -- onset_strength(y, sr), onset_detect(onset_envelope,
+ * backtrack=False), feature.rms(S=|stft(y)|), onset_backtrack, frames_to_time -- as the CSR pair cfd_motion_eval takes, in 3 launches
+ * (+ 1 with normalize; csrc/onset_fe.hpp).  float32 spectra and envelope, int32 frames, float64 times.  With T = 1 + n_samples / hop:
+ *   Mel power M[t][m] as cfd_audio_encode's; D = max(10 log10(max(amin, M)), 10 log10(max(amin, max M)) - top_db), the max over the clip
+ *   envelope[j] = mean_m max(0, D[j - pad_frames + lag][m] - D[j - pad_frames][m]) for pad_frames <= j < T, else 0
+ *               (librosa: lag = 1, pad_frames = lag + n_fft / (2 hop))
+ *   x = (envelope - min) / (max(envelope - min) + FLT_MIN); an all-zero or non-finite envelope has no onsets
+ *   frame n is a candidate iff x[n] == max x[n - pre_max, n + post_max), x[n] >= mean x[n - pre_avg, n + post_avg) + delta and x[n] != 0,
+ *               both windows clipped to [0, T); candidates are accepted in order when n > last accepted + wait
+ *   energy r[t] = sqrt(2 (sum_k P[t][k] - P[t][0] / 2 - P[t][n_fft / 2] / 2) / n_fft^2), P the power spectrum of the SAME transform
+ *   an onset moves back to the largest i <= n that is an energy minimum: i = 0, or 1 <= i <= T - 2 with r[i] <= r[i - 1] and r[i] < r[i + 1]
+ *   time = (frame * time_hop) / time_sr.  The reference passes no sr to onset_detect and frames_to_time, so librosa's default 22050 sets
+ *               the five window integers AND the times (time_hop 512, time_sr 22050) although its audio is at 16 kHz; that is the
+ *               reference's number.  The two travel as a pair because a product with one rounded scale is not that quotient.
+ * No atomics; the same bits on every call; a waveform's results do not depend on the batch.  Equal-length clips only; resampling and file
+ * decoding other than plain PCM stay with the caller.
+ *   wave ... top_db   as in cfd_audio_args (the reference: n_fft 2048, hop 512, 128 bands, 1e-10, 80); normalize 1 is util.normalize
+ *   pre_max, pre_avg, wait >= 0; post_max, post_avg >= 1; delta >= 0; lag >= 1; pad_frames >= lag (CFD_E_ARG otherwise)
+ *   T <= 2048, what the detection workgroup's LDS plan holds (CFD_E_SHAPE otherwise)
+ *   capacity    entries of onset_t (and frames_raw, frames).  Two accepted onsets are more than `wait` frames apart, so the total cannot
+ *               exceed n_wave * ceil(T / (wait + 1)); a capacity below that bound is refused (CFD_E_SHAPE) -- by the bound, before the first
+ *               launch, not by the data.  n_wave * T always suffices.
+ *   envelope, rms   optional outputs dev float32 [n_wave][T] (the envelope before normalisation)
+ *   frames_raw, frames   optional outputs dev int32 [capacity]: the accepted frames and the backtracked ones, segmented by onset_off
+ * onset_off dev int32 [n_wave + 1], onset_t dev float64 [capacity], n_total dev int32 [1] or NULL (= onset_off[n_wave]): a device word, so
+ * cfd_motion_eval can follow on the same stream with n_onsets = capacity.  A waveform without onsets has an empty segment. */
+typedef struct {
+  const float* wave;
+  int n_wave;
+  long long n_samples;
+  int normalize;
+  int n_fft, hop, n_mels;
+  const float* twiddle;
+  const float* window;
+  const float* melfb;
+  const int32_t* mel_range;
+  float amin, top_db;
+  int lag, pad_frames;
+  int pre_max, post_max, pre_avg, post_avg, wait;
+  float delta;
+  int time_hop;
+  double time_sr;
+  int capacity;
+  float* envelope;
+  float* rms;
+  int32_t* frames_raw;
+  int32_t* frames;
+} cfd_onset_args;
+int cfd_audio_onsets(cfd_handle h, const cfd_onset_args* a, int32_t* onset_off, double* onset_t, int32_t* n_total, void* stream);
+
 /* Motion evaluation: what the reference's quant_eval/ scripts compute on the host, one motion at a time, from decoded motions
  * [n_seq][n_frames][189] (63 joints x 3) on the device (csrc/metrics_eval.hpp).  1 launch for the per-sequence part; with the FGD embedding
  * 5 more per 128 sequences and 1 for the statistics.  No atomics; reductions in float64 in one fixed order; the same bits on every call; a
@@ -574,7 +625,8 @@ int cfd_audio_encode(cfd_handle h, const cfd_audio_args* a, float* mel_db, float
  *   target, semantic   dev float32, target laid out as pred, semantic [n_seq][n_frames]; NULL: none
  *   fps, order, sigma, srgr_threshold   metric_eval.py:451-452 uses 25, 10, 0.3, 0.3; dyadic_eval.py:373 order 12, sigma 1.25
  *   onset_off, onset_t, n_onsets   the audio onsets in seconds as a CSR pair: dev int32 [n_seq + 1] and dev float64 [n_onsets]; sequence b
- *               owns onset_t[onset_off[b] .. onset_off[b + 1]) (offsets are clamped to [0, n_onsets]).  Onset detection stays with the caller.
+ *               owns onset_t[onset_off[b] .. onset_off[b + 1]) (offsets are clamped to [0, n_onsets]).  cfd_audio_onsets makes the pair from waveforms on the
+ *               device (n_onsets = its capacity); resampling and decoding audio files stay with the caller.
  *   fgd_pack, feature_length   HalfEmbeddingNet's pose encoder (motion_autoencoder.py:39-78), folded: per convolution W [N][k C_in]
  *               (column kk C_in + c, the eval-mode BatchNorm folded in) and b [N] for net.0 .. net.3, then out_net and fc_mu as ONE affine
  *               map W [F][59 F] (column t F + c) and b [F] -- their LeakyReLU(True) has negative_slope 1.0 (motion_autoencoder.py:52,55,58).

@@ -142,11 +142,16 @@ extern "C" int cfd_debug_read(cfd_handle c, const char* what, float* dst_dev, si
     HIPCHK(hipMemcpy(dst_dev, f, sizeof(f), hipMemcpyHostToDevice));
     return CFD_OK;
   }
-  if (!strcmp(what, "t5.x")) {      // the residual stream behind the last block, [rows][768] (in front of the final norm)
-    if (!c->t5.x) return fail(CFD_E_STATE, "no cfd_t5_encode has run on this handle");
-    if (numel > (size_t)c->t5.rows * 768) return fail(CFD_E_ARG, "buffer 't5.x' holds %lld floats, asked for %zu", c->t5.rows * 768, numel);
+  // the residual stream behind the last block, [rows][768] (in front of the final norm), and what the last block's launches left:
+  // h = x + ctx Wo^T [rows][768], q | k | v [rows][2304], ctx [rows][768], f [rows][3072]
+  const struct { const char* name; const float* p; long long width; } t5_taps[] = {
+      {"t5.x", c->t5.x, 768}, {"t5.h", c->t5.h, 768}, {"t5.qkv", c->t5.qkv, 2304}, {"t5.ctx", c->t5.ctx, 768}, {"t5.f", c->t5.f, 3072}};
+  for (const auto& t : t5_taps) {
+    if (strcmp(what, t.name)) continue;
+    if (!t.p) return fail(CFD_E_STATE, "no cfd_t5_encode has run on this handle");
+    if (numel > (size_t)(c->t5.rows * t.width)) return fail(CFD_E_ARG, "buffer '%s' holds %lld floats, asked for %zu", t.name, c->t5.rows * t.width, numel);
     HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(dst_dev, c->t5.x, numel * 4, hipMemcpyDeviceToDevice));
+    HIPCHK(hipMemcpy(dst_dev, t.p, numel * 4, hipMemcpyDeviceToDevice));
     return CFD_OK;
   }
   if (!strncmp(what, "vae.", 4)) {

@@ -354,10 +354,11 @@ struct cfd_handle_s {
   } vae;
   // cfd_t5_encode (cfd_text.hip, t5_enc.hpp): the call's workspace, sized from (n_seq, T) -- per token row x | h | q k v | ctx | f --, the
   // launches of the last call (0: it was refused; big_launches: those of its products that ran as 128 x 128 blocks), where it left the
-  // residual stream (cfd_debug_read "t5.x"), and the handle's device's compute units (what the products' block shape is chosen by)
+  // residual stream and the last block's h, q | k | v, ctx and f (cfd_debug_read "t5.x", "t5.h", "t5.qkv", "t5.ctx", "t5.f"), and the
+  // handle's device's compute units (what the products' block shape is chosen by)
   struct T5State {
     DBuf ws;
-    float* x = nullptr;
+    float *x = nullptr, *h = nullptr, *qkv = nullptr, *ctx = nullptr, *f = nullptr;
     long long rows = 0;
     int launches = 0, big_launches = 0, n_cu = 0;
   } t5;

@@ -52,7 +52,7 @@ extern "C" int cfd_t5_encode(cfd_handle c, const cfd_t5_args* a, float* out, voi
       CHK(c->t5.ws.ensure(lay.bytes()));
     }
   }
-  c->t5.x = x;
+  c->t5.x = x; c->t5.h = h; c->t5.qkv = qkv; c->t5.ctx = ctx; c->t5.f = f;
   c->t5.rows = M;
 
   const float* embed = a->wpack;

@@ -86,6 +86,10 @@ int cfd_bench_gemm(cfd_handle h, int I, int J, int K, int tile_cfg, int iters, f
  *   "t5.info"     4 floats: the launches of the call (5 per block + 1; 0: it was refused), its token rows n_seq * T, the workspace's bytes,
  *                 and how many of its products ran as 128 x 128 blocks (the others: 64 x 64; the bits are the same)
  *   "t5.x"        [n_seq * T][768]     the residual stream behind the last block, in front of the final norm
+ *   "t5.h"        [n_seq * T][768]     the last block's stream behind its attention: h = x + ctx Wo^T
+ *   "t5.qkv"      [n_seq * T][2304]    the last block's q | k | v rows
+ *   "t5.ctx"      [n_seq * T][768]     the last block's attention output, heads side by side
+ *   "t5.f"        [n_seq * T][3072]    the last block's feed-forward intermediate relu(rms(h) g2 Wi^T)
  * ... and the last cfd_audio_encode / cfd_audio_power:
  *   "audio.info"  4 floats: the launches of the call (0: it was refused), the frames per waveform 1 + n_samples / hop, the output rows
  *                 n_wave * max(n_win, 1), the workspace's bytes */

@@ -9,7 +9,8 @@ projection (t5.py:48-49, 57), on a state dict keyed like ``T5EncoderModel.state_
 
 ``bias`` is block 0's relative_attention_bias, shared by all blocks; padded queries are computed like any other.  Checked against
 ``T5EncoderModel(...).double()`` in tests/test_t5_host.py; the GPU tests (tests/test_gpu_t5.py) use it as their reference, so they need
-no transformers."""
+no transformers.  ``encode`` / ``project`` are the composition of one function per launch of the HIP call (``stage_*``), which
+tests/test_gpu_t5_stages.py applies to the device's own intermediates."""
 import numpy as np
 
 D, DKV, H, FF, EPS = 768, 64, 12, 3072, 1e-6
@@ -43,40 +44,92 @@ def num_layers_of(sd):
     return n
 
 
-def encode(sd, ids, mask, taps=None):
-    """ids int [n, T], mask [n, T] (1 = token) -> last hidden state float64 [n, T, 768].  ``taps``: a list that receives the residual
-    stream behind every block."""
-    w = {k: np.asarray(v, dtype=np.float64) for k, v in sd.items() if k.startswith("encoder.") or k == "shared.weight"}
-    ids = np.asarray(ids)
-    n, T = ids.shape
-    x = w["shared.weight"][ids]
+def _w(sd, key, dtype):
+    return np.asarray(sd[key], dtype=dtype)
+
+
+def _block(l):
+    return f"encoder.block.{l}.layer."
+
+
+REL_BIAS = "encoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight"
+
+
+# One stage each, what one launch of cfd_t5_encode computes (csrc/t5_enc.hpp), in ``dtype`` throughout (float64, or float32 for what the
+# formula itself loses in single precision): inputs and weights are cast to it, rows are [..., width] with any leading shape.
+
+def stage_qkv(sd, l, x, dtype=np.float64):
+    """x [..., 768] -> q | k | v [..., 2304] = (rms(x) g1) Wq^T | Wk^T | Wv^T of block l"""
+    p = _block(l)
+    nx = rms(np.asarray(x, dtype=dtype), _w(sd, p + "0.layer_norm.weight", dtype))
+    return np.concatenate([nx @ _w(sd, p + f"0.SelfAttention.{m}.weight", dtype).T for m in "qkv"], axis=-1)
+
+
+def stage_attn(sd, qkv, mask, T, dtype=np.float64):
+    """q | k | v [n * T rows, 2304] and mask [n, T] (nonzero = key kept; any pattern) -> ctx [n, T, 768]: per head
+    softmax_j(q_i k_j + bias[head][bucket(j - i)]) v_j over the kept keys j, for every query i (padded ones included).  A sequence without
+    any key gives NaN rows."""
+    keep = np.asarray(mask).astype(bool).reshape(-1, T)
+    n = keep.shape[0]
+    qkv = np.asarray(qkv, dtype=dtype).reshape(n, T, 3, H, DKV)
+    q, k, v = (qkv[:, :, m].transpose(0, 2, 1, 3) for m in range(3))                                   # [n, H, T, DKV]
     pos = np.arange(T)
-    rel_bucket = bucket(pos[None, :] - pos[:, None])                                                   # [i, j]
-    bias = w["encoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight"][rel_bucket]        # [i, j, H]
+    bias = _w(sd, REL_BIAS, dtype)[bucket(pos[None, :] - pos[:, None])]                                # [i, j, H]
     bias = bias.transpose(2, 0, 1)[None]                                                               # [1, H, i, j]
-    keep = np.asarray(mask).astype(bool)[:, None, None, :]
-    for l in range(num_layers_of(sd)):
-        p = f"encoder.block.{l}.layer."
-        nx = rms(x, w[p + "0.layer_norm.weight"])
-        heads = lambda y: y.reshape(n, T, H, DKV).transpose(0, 2, 1, 3)
-        q, k, v = (heads(nx @ w[p + f"0.SelfAttention.{m}.weight"].T) for m in "qkv")
-        s = q @ k.transpose(0, 1, 3, 2) + bias
-        s = np.where(keep, s, -np.inf)
+    s = q @ k.transpose(0, 1, 3, 2) + bias
+    with np.errstate(invalid="ignore"):                                                               # (-inf) - (-inf): a sequence without keys
+        s = np.where(keep[:, None, None, :], s, -np.inf)
         s = s - s.max(-1, keepdims=True)
         e = np.exp(s)
         pr = e / e.sum(-1, keepdims=True)
-        ctx = (pr @ v).transpose(0, 2, 1, 3).reshape(n, T, H * DKV)
-        h = x + ctx @ w[p + "0.SelfAttention.o.weight"].T
-        nh = rms(h, w[p + "1.layer_norm.weight"])
-        x = h + np.maximum(nh @ w[p + "1.DenseReluDense.wi.weight"].T, 0.0) @ w[p + "1.DenseReluDense.wo.weight"].T
+        return (pr @ v).transpose(0, 2, 1, 3).reshape(n, T, H * DKV)
+
+
+def stage_attn_out(sd, l, x, ctx, dtype=np.float64):
+    """h = x + ctx Wo^T of block l"""
+    return np.asarray(x, dtype=dtype) + np.asarray(ctx, dtype=dtype) @ _w(sd, _block(l) + "0.SelfAttention.o.weight", dtype).T
+
+
+def stage_ff_in(sd, l, h, dtype=np.float64):
+    """f = relu((rms(h) g2) Wi^T) of block l"""
+    p = _block(l)
+    nh = rms(np.asarray(h, dtype=dtype), _w(sd, p + "1.layer_norm.weight", dtype))
+    return np.maximum(nh @ _w(sd, p + "1.DenseReluDense.wi.weight", dtype).T, dtype(0.0))
+
+
+def stage_ff_out(sd, l, h, f, dtype=np.float64):
+    """x' = h + f Wo_ff^T of block l"""
+    return np.asarray(h, dtype=dtype) + np.asarray(f, dtype=dtype) @ _w(sd, _block(l) + "1.DenseReluDense.wo.weight", dtype).T
+
+
+def _project(sd, hidden, dtype):
+    return np.maximum(np.asarray(hidden, dtype=dtype), dtype(0.0)) @ _w(sd, "projection.1.weight", dtype).T + _w(sd, "projection.1.bias", dtype)
+
+
+def stage_final(sd, x, project, dtype=np.float64):
+    """the last hidden state rms(x) g_final, or with ``project`` the reference's Linear(relu(.)) of it"""
+    hidden = rms(np.asarray(x, dtype=dtype), _w(sd, "encoder.final_layer_norm.weight", dtype))
+    return _project(sd, hidden, dtype) if project else hidden
+
+
+def encode(sd, ids, mask, taps=None):
+    """ids int [n, T], mask [n, T] (1 = token) -> last hidden state float64 [n, T, 768].  ``taps``: a list that receives the residual
+    stream behind every block.  The composition of the stages above in float64."""
+    ids = np.asarray(ids)
+    n, T = ids.shape
+    x = _w(sd, "shared.weight", np.float64)[ids]
+    for l in range(num_layers_of(sd)):
+        ctx = stage_attn(sd, stage_qkv(sd, l, x), mask, T)
+        h = stage_attn_out(sd, l, x, ctx)
+        x = stage_ff_out(sd, l, h, stage_ff_in(sd, l, h))
         if taps is not None:
             taps.append(x)
-    return rms(x, w["encoder.final_layer_norm.weight"])
+    return stage_final(sd, x, project=False)
 
 
 def project(sd, hidden):
     """the reference's projection: Linear(relu(last_hidden_state))"""
-    return np.maximum(hidden, 0.0) @ np.asarray(sd["projection.1.weight"], np.float64).T + np.asarray(sd["projection.1.bias"], np.float64)
+    return _project(sd, hidden, np.float64)
 
 
 def make_state(num_layers, seed, vocab=64, proj_dim=512):
@@ -125,6 +178,45 @@ def case_inputs(name):
         ids[s, :n] = r.randint(1, VOCAB, size=n)
         mask[s, :n] = 1
     return ids, mask
+
+
+def hole_masks(T=129):
+    """uint8 [3, T], masks that are no prefix: keys 0 .. 63 masked (the first kept key lies in the second 64-key tile), keys 64 .. 127
+    masked (a whole inner tile), every second key masked (keys 1, 3, 5, ... out)."""
+    mask = np.ones((3, T), np.uint8)
+    mask[0, :64] = 0
+    mask[1, 64:128] = 0
+    mask[2, 1::2] = 0
+    return mask
+
+
+# The end-to-end cases of tests/golden/t5_edges.npz and tests/test_gpu_t5_edges.py: name -> (num_layers, state seed, lengths or None for
+# hole_masks, T).  L12: t5-base's depth; T256: the longest sequence the call takes, next to one whose last 64-key tile holds one key;
+# H: the hole masks at T = 129
+EDGE_CASES = {"L12": (12, 21, (9, 4), 9), "T256": (1, 22, (256, 193), 256), "H": (1, 23, None, 129)}
+# what the fixture stores of an edge case's float32 projected output: every (position stride)-th row
+EDGE_STORED = {"L12": 1, "T256": 16, "H": 8}
+
+
+def prefix_inputs(seed, lens, T):
+    """ids int32 [n, T] drawn from RandomState(seed) (padding holds id 0) and the prefix mask uint8 [n, T] of ``lens``"""
+    r = np.random.RandomState(seed)
+    ids = np.zeros((len(lens), T), np.int32)
+    mask = np.zeros((len(lens), T), np.uint8)
+    for s, n in enumerate(lens):
+        ids[s, :n] = r.randint(1, VOCAB, size=n)
+        mask[s, :n] = 1
+    return ids, mask
+
+
+def hole_inputs(seed, T=129):
+    """ids int32 [3, T] with a token at EVERY position (a masked key carries values that must leave no trace) and hole_masks(T)"""
+    return np.random.RandomState(seed).randint(1, VOCAB, size=(3, T)).astype(np.int32), hole_masks(T)
+
+
+def edge_inputs(name):
+    _, seed, lens, T = EDGE_CASES[name]
+    return hole_inputs(2000 + seed, T) if lens is None else prefix_inputs(2000 + seed, lens, T)
 
 
 def rel_err(got, want):

@@ -38,6 +38,12 @@ typedef __attribute__((address_space(3))) void* lptr_t;
 // the pair then holds 16 - 17 significant bits, not 22 (measured block by block: tests/test_gpu_xattn_block.py; 2.2e-6 of the block's
 // 2.5e-6 against float64).  x 64 brings elements from 2e-3 on to full width and leaves a factor 1000 to the saturation bound for weights of 1.
 #define CFD_MEMW_SCALE 64.0f
+// The same for the self-attention weights [Wq / sqrt(128); Wk; Wv] and Wo (elements of a 512-wide layer are below 0.125, the pre-scaled Wq
+// below 0.01: every `lo` half an fp16 subnormal) ON THE ROW-TILE PATH: LayerW::wqkv_rt_sp and wo_rt_sp hold CFD_SAW_SCALE x the weights and
+// rt_gemm_kernel scales its sums back (RtGemmArgs::w_scaled, rowtile.hpp).  Measured block by block: tests/test_gpu_selfattn_block.py,
+// DESIGN.md section 5.1.  The tile kernels' copies (wqkv_sp, wo_sp, the LayerNorm fold's W diag(gamma)) are stored unscaled: the same change
+// there cost the headline loop 2.2 %.
+#define CFD_SAW_SCALE 64.0f
 
 __device__ __forceinline__ void split_f32(float v, sp_t& hi, sp_t& lo) {
   v = __builtin_amdgcn_fmed3f(v, -65504.0f, 65504.0f);

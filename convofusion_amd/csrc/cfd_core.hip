@@ -175,8 +175,9 @@ extern "C" int cfd_finalize_weights(cfd_handle c) {
 
   CHK(c->we_all.ensure((size_t)nl * 2 * 2 * D * D * 4));
   CHK(c->be_all.ensure((size_t)nl * 2 * 2 * D * 4));
-  DBuf tmpf, tmpd1, tmpd2, vd1, vd2, accd, tmpfold;
+  DBuf tmpf, tmps, tmpd1, tmpd2, vd1, vd2, accd, tmpfold;
   CHK(tmpf.ensure((size_t)3 * D * D * 4));
+  CHK(tmps.ensure((size_t)3 * D * D * 4));
   CHK(tmpd1.ensure((size_t)D * D * 8));
   CHK(tmpd2.ensure((size_t)D * D * 8));
   CHK(vd1.ensure(D * 8));
@@ -213,11 +214,17 @@ extern "C" int cfd_finalize_weights(cfd_handle c) {
     // bias is folded into the out-projection's, below).
     HIPCHK(hipMemcpy(tf + (size_t)2 * D * D, ipw + (size_t)2 * D * D, (size_t)D * D * 4, hipMemcpyDeviceToDevice));
     CHK(to_sp(c, tf, 3 * D, D, w.wqkv_sp));
+    // The row-tile path's copies, stored x CFD_SAW_SCALE (cfd_common.hpp: unscaled, every `lo` half of these weights is an fp16 subnormal)
+    float* ts = tmps.as<float>();
+    hipLaunchKernelGGL(scale_copy_kernel<>, grid1((long long)3 * D * D), blk, 0, 0, tf, ts, (long long)3 * D * D, CFD_SAW_SCALE);
+    CHK(to_sp(c, ts, 3 * D, D, w.wqkv_rt_sp));
     CHK(w.bqk.ensure(3 * D * 4));
     HIPCHK(hipMemset(w.bqk.as<float>() + 2 * D, 0, D * 4));
     hipLaunchKernelGGL(scale_copy_kernel<>, grid1(D), blk, 0, 0, ipb, w.bqk.as<float>(), (long long)D, qs);
     hipLaunchKernelGGL(scale_copy_kernel<>, grid1(D), blk, 0, 0, ipb + D, w.bqk.as<float>() + D, (long long)D, 1.0f);
     CHK(to_sp(c, ow, D, D, w.wo_sp));
+    hipLaunchKernelGGL(scale_copy_kernel<>, grid1((long long)D * D), blk, 0, 0, ow, ts, (long long)D * D, CFD_SAW_SCALE);
+    CHK(to_sp(c, ts, D, D, w.wo_rt_sp));
     // softmax rows sum to one, so the value bias passes straight through: bo' = bo + Wo bv
     CHK(w.bo2.ensure(D * 4));
     hipLaunchKernelGGL((fold_mv_kernel<float, float, float>), grid1(D), blk, 0, 0, ow, (long long)D, 1LL, ipb + 2 * D,

@@ -153,8 +153,8 @@ int enqueue_rows_rt(Ctx* c, hipStream_t st, const RtSave* sv) {
     {
       RtGemmArgs a = base;   // norm1 + q | k | v^T projections
       a.x = X(l, 0);
-      a.g = w.ln1g; a.b = w.ln1b; a.w = w.wqkv_sp.as<char>(); a.w2 = w.wqkv_sp.as<char>() + (size_t)2 * CFD_D * CFD_D * 4; a.nfb_qk = 2 * CFD_D / 16;
-      a.bias = w.bqk.as<float>(); a.o_sp = qk; a.ld_o = 2 * CFD_D * 4; a.vt = vt;
+      a.g = w.ln1g; a.b = w.ln1b; a.w = w.wqkv_rt_sp.as<char>(); a.w2 = w.wqkv_rt_sp.as<char>() + (size_t)2 * CFD_D * CFD_D * 4; a.nfb_qk = 2 * CFD_D / 16;
+      a.bias = w.bqk.as<float>(); a.o_sp = qk; a.ld_o = 2 * CFD_D * 4; a.vt = vt; a.w_scaled = 1;   // (the row-tile copies: x CFD_SAW_SCALE)
       RT_LAUNCH(CFD_PROF_GEMM_TOKEN, RT_PRO_LN, RT_EPI_QKV, 512, CFD_D / 32, 3, 3 * CFD_D, a);
     }
     {
@@ -166,7 +166,7 @@ int enqueue_rows_rt(Ctx* c, hipStream_t st, const RtSave* sv) {
     {
       RtGemmArgs a = base;   // out-projection + residual
       a.xr = X(l, 0); a.xo = X(l, 1);
-      a.a_sp = c->w->o_sp.as<char>(); a.w = w.wo_sp.as<char>(); a.bias = w.bo2.as<float>();
+      a.a_sp = c->w->o_sp.as<char>(); a.w = w.wo_rt_sp.as<char>(); a.bias = w.bo2.as<float>(); a.w_scaled = 1;
       if (nfb2) RT_LAUNCH(CFD_PROF_GEMM_TOKEN, RT_PRO_SP, RT_EPI_RESID, 256, CFD_D / 32, 2, CFD_D, a);
       else RT_LAUNCH(CFD_PROF_GEMM_TOKEN, RT_PRO_SP, RT_EPI_RESID, 256, CFD_D / 32, 1, CFD_D, a);
     }

@@ -28,6 +28,7 @@ static const char* MEM_NAMES[CFD_NMEM] = {"spkemb", "alsn", "tlsn", "apb", "lsne
 
 struct LayerW {
   DBuf wqkv_sp, bqk, wo_sp, bo2, wtb1_sp, wtb2_sp, w1_sp, w2_sp, cross_bias;
+  DBuf wqkv_rt_sp, wo_rt_sp;   // the row-tile path's copies of wqkv_sp and wo_sp: split pairs of CFD_SAW_SCALE x the weights (cfd_common.hpp)
   // the LayerNorm fold's operands (gemm_sp.hpp EpiLn): W' = W diag(gamma) as split pairs for q | k, v and FFN1, and per output feature
   // c = W' 1, d = W beta in ln_cd: [c_qk 1024][d_qk 1024][c_v 512][d_v 512][c_1 1024][d_1 1024]
   DBuf wqk_f, wv_f, w1_f, ln_cd;

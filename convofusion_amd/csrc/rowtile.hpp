@@ -250,6 +250,7 @@ struct RtGemmArgs {
   const char* w;           // SP [N][K]
   const char* w2;          // RT_EPI_QKV: the value projection's weights (16-feature blocks >= nfb_qk, operand roles swapped)
   int nfb_qk;
+  int w_scaled;            // 1: w (and w2) hold CFD_SAW_SCALE x the weights (cfd_common.hpp): the sums are scaled back, exactly, in front of the epilogue
   const float* bias;       // [N] or null
   // outputs
   const float* xr;         // RESID: the residual rows (fp32 [M][512]) ...
@@ -384,7 +385,7 @@ __global__ void __launch_bounds__(NT) rt_gemm_kernel(const RtGemmArgs a) {
     for (int n = 0; n < NK; ++n) part[i] = sw_i ? rt_mma(ah[n], al[n], wh[i][n], wl[i][n], part[i]) : rt_mma(wh[i][n], wl[i][n], ah[n], al[n], part[i]);
   }
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");              // this wave's fragment reads are done: its staging region is free
-  const f32x4 acc = rt_reduce<NW, NFB>(stage0, STAGE_W, wid, lane, part);
+  const f32x4 acc = rt_reduce<NW, NFB>(stage0, STAGE_W, wid, lane, part) * (a.w_scaled ? 1.0f / CFD_SAW_SCALE : 1.0f);
   if (wid >= NFB) return;
 #if RT_STAMP
   struct StampAtExit { unsigned long long a, b; int id; __device__ ~StampAtExit() { RT_STAMP_OUT(id, a, b); } } stamp_{t_in, t_ops, (int)(100 * PRO + 10 * EPI + (KT == 32 ? 1 : 0)) | (int)((t_iss - t_in) << 16)};

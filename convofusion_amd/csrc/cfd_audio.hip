@@ -19,28 +19,71 @@ static int check_transform(const char* who, int n_wave, long long n_samples, int
 }
 
 template <bool POWER>
-static int enqueue_frames(const AfeFrameArgs& f, int n_fft, int n_wave, hipStream_t st) {
+static int enqueue_frames(const AfeFrameArgs& f, int n_fft, int n_wave, hipStream_t st, int& launches) {
   const dim3 grid((unsigned)f.T, (unsigned)n_wave), block(AFE_THREADS);
   switch (n_fft) {
-    case 256: hipLaunchKernelGGL((afe_frame_kernel<128, POWER>), grid, block, 0, st, f); break;
-    case 512: hipLaunchKernelGGL((afe_frame_kernel<256, POWER>), grid, block, 0, st, f); break;
-    case 1024: hipLaunchKernelGGL((afe_frame_kernel<512, POWER>), grid, block, 0, st, f); break;
-    default: hipLaunchKernelGGL((afe_frame_kernel<1024, POWER>), grid, block, 0, st, f); break;
+    case 256: LAUNCH_COUNTED(launches, (afe_frame_kernel<128, POWER>), grid, block, 0, st, f); break;
+    case 512: LAUNCH_COUNTED(launches, (afe_frame_kernel<256, POWER>), grid, block, 0, st, f); break;
+    case 1024: LAUNCH_COUNTED(launches, (afe_frame_kernel<512, POWER>), grid, block, 0, st, f); break;
+    default: LAUNCH_COUNTED(launches, (afe_frame_kernel<1024, POWER>), grid, block, 0, st, f); break;
   }
-  HIPCHK(hipGetLastError());
   return CFD_OK;
+}
+
+// The Mel front of cfd_audio_encode and cfd_audio_onsets: the fields their argument structs share, wave to top_db, as one view; what
+// both refuse about them; and their first stage, the peak launch where the call asks for one and the frame launch.
+struct MelFront {
+  const float* wave;
+  int n_wave;
+  long long n_samples;
+  int normalize, n_fft, hop, n_mels;
+  const float *twiddle, *window, *melfb;
+  const int32_t* mel_range;
+  float amin, top_db;
+};
+template <class A>
+static MelFront mel_front_of(const A* a) {   // (a null struct gives null pointers, which check_mel_front refuses)
+  if (!a) return MelFront{};
+  return MelFront{a->wave, a->n_wave, a->n_samples, a->normalize, a->n_fft, a->hop, a->n_mels, a->twiddle, a->window, a->melfb, a->mel_range, a->amin, a->top_db};
+}
+
+// other_null: a pointer of the entry point's own that is refused in the same words
+static int check_mel_front(const char* who, const MelFront& m, bool other_null = false) {
+  if (other_null || !m.wave || !m.twiddle || !m.window || !m.melfb) return fail(CFD_E_ARG, "%s: bad argument (NULL pointer)", who);
+  CHK(check_transform(who, m.n_wave, m.n_samples, m.n_fft, m.hop));
+  if (m.n_mels < 1 || m.n_mels > m.n_fft / 2 + 1) return fail(CFD_E_ARG, "%s: 1 <= n_mels <= n_fft / 2 + 1 = %d (got %d)", who, m.n_fft / 2 + 1, m.n_mels);
+  if (!(m.amin > 0.f) || !(m.top_db >= 0.f)) return fail(CFD_E_ARG, "%s: amin > 0 and top_db >= 0 (got %g, %g)", who, (double)m.amin, (double)m.top_db);
+  if (m.normalize != 0 && m.normalize != 1) return fail(CFD_E_ARG, "%s: normalize is 0 or 1 (got %d)", who, m.normalize);
+  return CFD_OK;
+}
+
+struct PeakAsk {   // what the peak launch takes beyond the front: the chunking, the activity bits and the caller's outputs
+  int chunk;
+  long long n_chunks;
+  float act_amin_power, act_thresh_power;
+  float *chunkmax, *peak_out;
+  int* activity;
+  long long n_bits;
+};
+
+// pk null: no peak launch; melpow null: no frame launch.  The frames are normalised by peak_ws where the front says so.
+static int enqueue_mel_front(const MelFront& m, long long T, const PeakAsk* pk, float* peak_ws, float* melpow, float* rms, hipStream_t st, int& launches) {
+  if (pk)
+    LAUNCH_COUNTED(launches, afe_peak_kernel, dim3((unsigned)m.n_wave), dim3(AFE_RED_THREADS), 0, st, m.wave, m.n_samples, pk->chunk, pk->n_chunks,
+                   m.normalize, pk->act_amin_power, pk->act_thresh_power, pk->chunkmax, peak_ws, pk->peak_out, pk->activity, pk->n_bits);
+  if (!melpow) return CFD_OK;
+  AfeFrameArgs f{};
+  f.wave = m.wave; f.peak = m.normalize ? peak_ws : nullptr; f.n_samples = m.n_samples; f.T = T; f.hop = m.hop; f.n_mels = m.n_mels;
+  f.tw = (const float2*)m.twiddle; f.window = m.window; f.melfb = m.melfb; f.mel_range = m.mel_range; f.out = melpow; f.rms = rms;
+  return enqueue_frames<false>(f, m.n_fft, m.n_wave, st, launches);
 }
 
 extern "C" int cfd_audio_encode(cfd_handle c, const cfd_audio_args* a, float* mel_db, float* memory, int32_t* activity, float* peak,
                                 void* stream) {
   if (!c) return fail(CFD_E_ARG, "null handle");
   c->audio.launches = 0;
-  if (!a || !a->wave || !a->twiddle || !a->window || !a->melfb) return fail(CFD_E_ARG, "cfd_audio_encode: bad argument (NULL pointer)");
-  CHK(check_transform("cfd_audio_encode", a->n_wave, a->n_samples, a->n_fft, a->hop));
-  if (a->n_mels < 1 || a->n_mels > a->n_fft / 2 + 1)
-    return fail(CFD_E_ARG, "cfd_audio_encode: 1 <= n_mels <= n_fft / 2 + 1 = %d (got %d)", a->n_fft / 2 + 1, a->n_mels);
-  if (!(a->amin > 0.f) || !(a->top_db >= 0.f)) return fail(CFD_E_ARG, "cfd_audio_encode: amin > 0 and top_db >= 0 (got %g, %g)", (double)a->amin, (double)a->top_db);
-  if (a->normalize != 0 && a->normalize != 1) return fail(CFD_E_ARG, "cfd_audio_encode: normalize is 0 or 1 (got %d)", a->normalize);
+  const MelFront m = mel_front_of(a);
+  CHK(check_mel_front("cfd_audio_encode", m));
   const bool mlp = a->w0 || a->b0 || a->w1 || a->b1 || a->w2 || a->b2;
   if (mlp && (!a->w0 || !a->b0 || !a->w1 || !a->b1 || !a->w2 || !a->b2 || a->hidden < 1 || a->latent < 1))
     return fail(CFD_E_ARG, "cfd_audio_encode: the encoder needs all of w0 b0 w1 b1 w2 b2 and hidden, latent >= 1 (got %d, %d)", a->hidden, a->latent);
@@ -70,8 +113,7 @@ extern "C" int cfd_audio_encode(cfd_handle c, const cfd_audio_args* a, float* me
   const int chunk = a->act_chunk >= 1 ? a->act_chunk : 4096;
   const long long n_chunks = (a->n_samples + chunk - 1) / chunk, n_bits = a->act_chunk >= 1 ? a->n_samples / a->act_chunk : 0;
   float *chunkmax, *peak_ws, *smax, *melpow, *db_ws, *h1, *h2;
-  for (int pass = 0; pass < 2; ++pass) {      // the workspace's layout, stated once: sized, then carved
-    ArenaLayout lay(pass ? c->audio.ws.as<float>() : nullptr, 64);
+  CHK(carve(c->audio.ws, 64, [&](ArenaLayout& lay) {
     lay.take(chunkmax, front ? (size_t)(a->n_wave * n_chunks) : 0);
     lay.take(peak_ws, (size_t)a->n_wave);
     lay.take(smax, (size_t)a->n_wave);
@@ -79,36 +121,21 @@ extern "C" int cfd_audio_encode(cfd_handle c, const cfd_audio_args* a, float* me
     lay.take(db_ws, memory && !mel_db ? (size_t)out_rows * a->n_mels : 0);
     lay.take(h1, memory ? (size_t)out_rows * a->hidden : 0);
     lay.take(h2, memory ? (size_t)out_rows * a->latent : 0);
-    if (!pass && lay.bytes() > c->audio.ws.bytes) {
-      HIPCHK(hipDeviceSynchronize());          // an earlier call on another stream may still read the buffer that is about to be freed
-      CHK(c->audio.ws.ensure(lay.bytes()));
-    }
-  }
+  }));
   c->audio.frames = T;
   c->audio.rows = rows;
 
   int launches = 0;
-  if (front) {
-    hipLaunchKernelGGL(afe_peak_kernel, dim3((unsigned)a->n_wave), dim3(AFE_RED_THREADS), 0, st, a->wave, a->n_samples, chunk, n_chunks, a->normalize,
-                       a->act_amin_power, a->act_thresh_power, chunkmax, peak_ws, peak, (int*)activity, n_bits);
-    HIPCHK(hipGetLastError());
-    ++launches;
-  }
+  const PeakAsk pk{chunk, n_chunks, a->act_amin_power, a->act_thresh_power, chunkmax, peak, (int*)activity, n_bits};
+  CHK(enqueue_mel_front(m, T, front ? &pk : nullptr, peak_ws, want_db ? melpow : nullptr, nullptr, st, launches));
   if (want_db) {
-    AfeFrameArgs f{};
-    f.wave = a->wave; f.peak = a->normalize ? peak_ws : nullptr; f.n_samples = a->n_samples; f.T = T; f.hop = a->hop; f.n_mels = a->n_mels;
-    f.tw = (const float2*)a->twiddle; f.window = a->window; f.melfb = a->melfb; f.mel_range = a->mel_range; f.out = melpow;
-    CHK(enqueue_frames<false>(f, a->n_fft, a->n_wave, st));
-    hipLaunchKernelGGL(afe_max_kernel, dim3((unsigned)a->n_wave), dim3(AFE_RED_THREADS), 0, st, melpow, T * a->n_mels, smax);
-    HIPCHK(hipGetLastError());
+    LAUNCH_COUNTED(launches, afe_max_kernel, dim3((unsigned)a->n_wave), dim3(AFE_RED_THREADS), 0, st, melpow, T * a->n_mels, smax);
     AfeDbArgs d{};
     float* db = mel_db ? mel_db : db_ws;
     d.melpow = melpow; d.smax = smax; d.out = db; d.T = T; d.total = out_rows * a->n_mels; d.n_mels = a->n_mels; d.frames = (int)frames;
     d.n_win = a->n_win; d.amin = a->amin; d.top_db = a->top_db;
     for (int w = 0; w < a->n_win; ++w) d.start[w] = a->win_start[w];
-    hipLaunchKernelGGL(afe_db_kernel, dim3((unsigned)((d.total + 255) / 256)), dim3(256), 0, st, d);
-    HIPCHK(hipGetLastError());
-    launches += 3;
+    LAUNCH_COUNTED(launches, afe_db_kernel, dim3((unsigned)((d.total + 255) / 256)), dim3(256), 0, st, d);
     if (memory) {                              // the three Linear layers on the library's float32 row kernel: K <= 512, a few thousand rows
       CHK(enqueue_linear_act(db, out_rows, a->n_mels, a->w0, a->b0, a->hidden, 2, h1, st));
       CHK(enqueue_linear_act(h1, out_rows, a->hidden, a->w1, a->b1, a->latent, 2, h2, st));
@@ -129,22 +156,19 @@ extern "C" int cfd_audio_power(cfd_handle c, const float* wave, int n_wave, long
   HIPCHK(hipSetDevice(c->cfg.device));
   AfeFrameArgs f{};
   f.wave = wave; f.n_samples = n_samples; f.T = 1 + n_samples / hop; f.hop = hop; f.tw = (const float2*)twiddle; f.window = window; f.out = power;
-  CHK(enqueue_frames<true>(f, n_fft, n_wave, (hipStream_t)stream));
+  int launches = 0;
+  CHK(enqueue_frames<true>(f, n_fft, n_wave, (hipStream_t)stream, launches));
   c->audio.frames = f.T;
   c->audio.rows = n_wave;
-  c->audio.launches = 1;
+  c->audio.launches = launches;
   return CFD_OK;
 }
 
 extern "C" int cfd_audio_onsets(cfd_handle c, const cfd_onset_args* a, int32_t* onset_off, double* onset_t, int32_t* n_total, void* stream) {
   if (!c) return fail(CFD_E_ARG, "null handle");
   c->audio.launches = 0;
-  if (!a || !a->wave || !a->twiddle || !a->window || !a->melfb || !onset_off) return fail(CFD_E_ARG, "cfd_audio_onsets: bad argument (NULL pointer)");
-  CHK(check_transform("cfd_audio_onsets", a->n_wave, a->n_samples, a->n_fft, a->hop));
-  if (a->n_mels < 1 || a->n_mels > a->n_fft / 2 + 1)
-    return fail(CFD_E_ARG, "cfd_audio_onsets: 1 <= n_mels <= n_fft / 2 + 1 = %d (got %d)", a->n_fft / 2 + 1, a->n_mels);
-  if (!(a->amin > 0.f) || !(a->top_db >= 0.f)) return fail(CFD_E_ARG, "cfd_audio_onsets: amin > 0 and top_db >= 0 (got %g, %g)", (double)a->amin, (double)a->top_db);
-  if (a->normalize != 0 && a->normalize != 1) return fail(CFD_E_ARG, "cfd_audio_onsets: normalize is 0 or 1 (got %d)", a->normalize);
+  const MelFront m = mel_front_of(a);
+  CHK(check_mel_front("cfd_audio_onsets", m, !onset_off));
   if (a->lag < 1 || a->pad_frames < a->lag) return fail(CFD_E_ARG, "cfd_audio_onsets: lag >= 1 and pad_frames >= lag (got %d, %d)", a->lag, a->pad_frames);
   if (a->pre_max < 0 || a->pre_avg < 0 || a->wait < 0)
     return fail(CFD_E_ARG, "cfd_audio_onsets: pre_max, pre_avg and wait must not be negative (got %d, %d, %d)", a->pre_max, a->pre_avg, a->wait);
@@ -172,8 +196,7 @@ extern "C" int cfd_audio_onsets(cfd_handle c, const cfd_onset_args* a, int32_t* 
   const long long n_chunks = (a->n_samples + chunk - 1) / chunk;
   float *chunkmax, *peak_ws, *melpow, *rms;
   int32_t *slot_raw, *slot_bt, *count;
-  for (int pass = 0; pass < 2; ++pass) {
-    ArenaLayout lay(pass ? c->audio.ws.as<float>() : nullptr, 64);
+  CHK(carve(c->audio.ws, 64, [&](ArenaLayout& lay) {
     lay.take(chunkmax, a->normalize ? (size_t)(a->n_wave * n_chunks) : 0);
     lay.take(peak_ws, (size_t)a->n_wave);
     lay.take(melpow, (size_t)a->n_wave * T * a->n_mels);
@@ -181,37 +204,23 @@ extern "C" int cfd_audio_onsets(cfd_handle c, const cfd_onset_args* a, int32_t* 
     lay.take(slot_raw, (size_t)a->n_wave * T);
     lay.take(slot_bt, (size_t)a->n_wave * T);
     lay.take(count, (size_t)a->n_wave);
-    if (!pass && lay.bytes() > c->audio.ws.bytes) {
-      HIPCHK(hipDeviceSynchronize());          // an earlier call on another stream may still read the buffer that is about to be freed
-      CHK(c->audio.ws.ensure(lay.bytes()));
-    }
-  }
+  }));
   if (a->rms) rms = a->rms;
   c->audio.frames = T;
   c->audio.rows = a->n_wave;
 
   int launches = 0;
-  if (a->normalize) {
-    hipLaunchKernelGGL(afe_peak_kernel, dim3((unsigned)a->n_wave), dim3(AFE_RED_THREADS), 0, st, a->wave, a->n_samples, chunk, n_chunks, 1, 0.f, 0.f,
-                       chunkmax, peak_ws, (float*)nullptr, (int*)nullptr, 0LL);
-    HIPCHK(hipGetLastError());
-    ++launches;
-  }
-  AfeFrameArgs f{};
-  f.wave = a->wave; f.peak = a->normalize ? peak_ws : nullptr; f.n_samples = a->n_samples; f.T = T; f.hop = a->hop; f.n_mels = a->n_mels;
-  f.tw = (const float2*)a->twiddle; f.window = a->window; f.melfb = a->melfb; f.mel_range = a->mel_range; f.out = melpow; f.rms = rms;
-  CHK(enqueue_frames<false>(f, a->n_fft, a->n_wave, st));
+  const PeakAsk pk{chunk, n_chunks, 0.f, 0.f, chunkmax, nullptr, nullptr, 0};
+  CHK(enqueue_mel_front(m, T, a->normalize ? &pk : nullptr, peak_ws, melpow, rms, st, launches));
   OnsArgs d{};
   d.melpow = melpow; d.rms = rms; d.T = (int)T; d.n_mels = a->n_mels; d.amin = a->amin; d.top_db = a->top_db; d.lag = a->lag; d.pad_frames = a->pad_frames;
   d.pre_max = a->pre_max; d.post_max = a->post_max; d.pre_avg = a->pre_avg; d.post_avg = a->post_avg; d.wait = a->wait; d.delta = a->delta;
   d.env_out = a->envelope; d.slot_raw = slot_raw; d.slot_bt = slot_bt; d.count = count;
-  hipLaunchKernelGGL(ons_detect_kernel, dim3((unsigned)a->n_wave), dim3(ONS_THREADS), 0, st, d);
-  HIPCHK(hipGetLastError());
+  LAUNCH_COUNTED(launches, ons_detect_kernel, dim3((unsigned)a->n_wave), dim3(ONS_THREADS), 0, st, d);
   OnsCsrArgs s{};
   s.count = count; s.slot_raw = slot_raw; s.slot_bt = slot_bt; s.n_wave = a->n_wave; s.T = (int)T; s.capacity = a->capacity; s.time_hop = a->time_hop;
   s.time_sr = a->time_sr; s.onset_off = onset_off; s.onset_t = onset_t; s.raw_out = a->frames_raw; s.bt_out = a->frames; s.n_total = n_total;
-  hipLaunchKernelGGL(ons_csr_kernel, dim3(1), dim3(ONS_THREADS), 0, st, s);
-  HIPCHK(hipGetLastError());
-  c->audio.launches = launches + 3;
+  LAUNCH_COUNTED(launches, ons_csr_kernel, dim3(1), dim3(ONS_THREADS), 0, st, s);
+  c->audio.launches = launches;
   return CFD_OK;
 }

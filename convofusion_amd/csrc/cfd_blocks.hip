@@ -63,14 +63,14 @@ extern "C" int cfd_zero_rows(cfd_handle c, float* x, const uint8_t* keep, long l
 
 // ---- ConvoFusionVae.encode (vae.py:162-266): csrc/vae_enc.hpp ----------------------------------------------------------------------
 template <int RT>
-static int launch_vae_encode(const VaeEncArgs& a, int groups, int lds, hipStream_t st) {
-  static bool attr_set = false;
-  if (!attr_set) {
+static int launch_vae_encode(Ctx* c, const VaeEncArgs& a, int groups, int lds, hipStream_t st) {
+  static unsigned long long attr_done = 0;
+  CHK(once_per_device(attr_done, c->cfg.device, [&]() -> int {
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&vae_encode_kernel<RT>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(vae_encode_kernel<RT>, dim3((unsigned)groups, 2), dim3(256), lds, st, a);
-  HIPCHK(hipGetLastError());
+    return CFD_OK;
+  }));
+  int launches = 0;   // (the call has no read-out; the launch goes the counted way for its check)
+  LAUNCH_COUNTED(launches, vae_encode_kernel<RT>, dim3((unsigned)groups, 2), dim3(256), lds, st, a);
   return CFD_OK;
 }
 
@@ -125,9 +125,9 @@ extern "C" int cfd_vae_encode(cfd_handle c, const float* wpack, int d_model, int
   a.num_layers = num_layers;
   const int lds = ve_lds_bytes(rt, nb);
   hipStream_t st = (hipStream_t)stream;
-  if (rt == 4) return launch_vae_encode<4>(a, (int)groups, lds, st);
-  if (rt == 3) return launch_vae_encode<3>(a, (int)groups, lds, st);
-  return launch_vae_encode<2>(a, (int)groups, lds, st);
+  if (rt == 4) return launch_vae_encode<4>(c, a, (int)groups, lds, st);
+  if (rt == 3) return launch_vae_encode<3>(c, a, (int)groups, lds, st);
+  return launch_vae_encode<2>(c, a, (int)groups, lds, st);
 }
 
 
@@ -147,12 +147,13 @@ int vae_decode_check(const char* who, const cfd_vae_decode_args* p) {
   return CFD_OK;
 }
 
-// The shape fields of `a` from (nl, bs, nframes, n_chunks) and its workspace pointers carved from `base` (null: sizing only, every pointer
-// null); returns the bytes.  save: the VJP workspace, every layer resident, in the order of VaeDecArgs.  Forward-only: what is live between
+// The shape fields of `a` from (nl, bs, nframes, n_chunks) and its workspace pointers named for `y`, whose granule is VD_GRANULE floats:
+// every buffer starts on a float4.  save: the VJP workspace, every layer resident, in the order of VaeDecArgs.  Forward-only: what is live between
 // two forward launches (vd_xslot, vd_lslot) -- per token row (nb + 2) stream slots, q | k | v and o: (nb + 6) * 512 bytes, 4096 at 5 layers
 // -- and the memory's K | V, nl * 16 KiB per (stack, sequence); every other pointer null.  keep_w, the copy of the weights for a sweep in a
 // later call, comes last and is only counted when `copy_w` asks for it: cfd_vae_decode_vjp sweeps inside the call and reads the caller's.
-static size_t vae_decode_layout(VaeDecArgs& a, int nl, int bs, int nframes, int n_chunks, float* base, bool save, bool copy_w) {
+constexpr size_t VD_GRANULE = 4;
+static void vae_decode_layout(VaeDecArgs& a, int nl, int bs, int nframes, int n_chunks, ArenaLayout& y, bool save, bool copy_w) {
   a.nl = nl;
   a.nb = (nl - 1) / 2;
   a.stack_floats = vd_stack_floats(nl);
@@ -163,12 +164,11 @@ static size_t vae_decode_layout(VaeDecArgs& a, int nl, int bs, int nframes, int 
   a.n_chunks = n_chunks;
   a.rows = 2LL * bs * a.fp;
   const long long R = a.rows, L = nl, sb = 2LL * bs;
-  ArenaLayout y(base, 4);   // 4 floats: every buffer starts on a float4
   a.x1 = a.x2 = a.lse = a.qc = a.g = a.g1 = a.d_o = a.dd = a.dqkv = a.gskip = a.pkv = a.dzl = a.keep_w = nullptr;
   a.keep_len = nullptr;
   if (!save) {
     y.take(a.x0, (a.nb + 2) * R * VE_D); y.take(a.qkv, R * 3 * VE_D); y.take(a.o, R * VE_D); y.take(a.mkv, L * sb * 16 * 256);
-    return y.bytes();
+    return;
   }
   y.take(a.x0, (L + 1) * R * VE_D); y.take(a.x1, L * R * VE_D); y.take(a.x2, L * R * VE_D); y.take(a.qkv, L * R * 3 * VE_D);
   y.take(a.o, L * R * VE_D); y.take(a.lse, L * R * 2); y.take(a.qc, L * R * VE_D); y.take(a.mkv, L * sb * 16 * 256);
@@ -176,26 +176,19 @@ static size_t vae_decode_layout(VaeDecArgs& a, int nl, int bs, int nframes, int 
   y.take(a.gskip, (a.nb ? a.nb : 1) * R * VE_D); y.take(a.pkv, L * sb * a.nt * 16 * 256); y.take(a.dzl, L * sb * 16 * VE_D);
   y.take(a.keep_len, bs);
   y.take(a.keep_w, copy_w ? 2 * a.stack_floats : 0);
-  return y.bytes();
 }
 
 template <bool SAVE>
-static int vae_decode_forward_launches(const VaeDecArgs& a, bool copy_w, hipStream_t st) {
+static int vae_decode_forward_launches(const VaeDecArgs& a, bool copy_w, hipStream_t st, int& n) {
   const dim3 grid((unsigned)a.nt, (unsigned)a.bs, 2), blk(256);
   // copy_w: about 256 more blocks, spread over the grid's first axis, copy the weights for a sweep in a later call
   const unsigned copy = SAVE && copy_w ? (unsigned)((256 + 2 * a.bs - 1) / (2 * a.bs)) : 0;
-  int n = 0;
-  hipLaunchKernelGGL(vd_mem_kernel<SAVE>, dim3((unsigned)a.nl + copy, (unsigned)a.bs, 2), blk, 0, st, a);
-  ++n;
+  LAUNCH_COUNTED(n, vd_mem_kernel<SAVE>, dim3((unsigned)a.nl + copy, (unsigned)a.bs, 2), blk, 0, st, a);
   for (int l = 0; l <= a.nl; ++l) {
-    hipLaunchKernelGGL(vd_fwd_rows_kernel<SAVE>, grid, blk, 0, st, a, l);
-    ++n;
-    if (l < a.nl) {
-      hipLaunchKernelGGL(vd_self_fwd_kernel<SAVE>, grid, blk, 0, st, a, l);
-      ++n;
-    }
+    LAUNCH_COUNTED(n, vd_fwd_rows_kernel<SAVE>, grid, blk, 0, st, a, l);
+    if (l < a.nl) LAUNCH_COUNTED(n, vd_self_fwd_kernel<SAVE>, grid, blk, 0, st, a, l);
   }
-  return n;
+  return CFD_OK;
 }
 
 // The forward of `p` into feats (may be null with save).  Whatever forward the handle kept is dropped first: this one overwrites it.
@@ -205,10 +198,7 @@ int vae_decode_forward(Ctx* c, const char* who, const cfd_vae_decode_args* p, fl
   v.ticket = 0;
   v.dropped_by = who;
   VaeDecArgs a;
-  const size_t bytes = vae_decode_layout(a, p->num_layers, p->bs, p->nframes, p->n_chunks, nullptr, save, copy_w);
-  v.grew = bytes > v.ws.bytes;
-  CHK(v.ws.ensure(bytes));
-  vae_decode_layout(a, p->num_layers, p->bs, p->nframes, p->n_chunks, v.ws.as<float>(), save, copy_w);
+  CHK(carve(v.ws, VD_GRANULE, [&](ArenaLayout& y) { vae_decode_layout(a, p->num_layers, p->bs, p->nframes, p->n_chunks, y, save, copy_w); }, &v.grew));
   a.w = p->wpack;
   a.qpe = p->wpack + 2 * a.stack_floats;
   a.mpe = a.qpe + (long long)VD_MAX_FRAMES * VE_D;
@@ -219,8 +209,9 @@ int vae_decode_forward(Ctx* c, const char* who, const cfd_vae_decode_args* p, fl
   a.d_z = nullptr;
   v.g = a.g; v.dzl = a.dzl; v.x0 = save ? a.x0 : nullptr;
   v.bs = a.bs; v.fp = a.fp; v.nl = a.nl; v.rows = a.rows; v.nframes = a.nframes; v.n_chunks = a.n_chunks;
-  v.launches = v.fwd_launches = save ? vae_decode_forward_launches<true>(a, copy_w, st) : vae_decode_forward_launches<false>(a, false, st);
-  HIPCHK(hipGetLastError());
+  int n = 0;
+  CHK(save ? vae_decode_forward_launches<true>(a, copy_w, st, n) : vae_decode_forward_launches<false>(a, false, st, n));
+  v.launches = v.fwd_launches = n;
   if (save) v.ticket = ++v.serial;
   return CFD_OK;
 }
@@ -230,7 +221,8 @@ int vae_decode_forward(Ctx* c, const char* who, const cfd_vae_decode_args* p, fl
 int vae_decode_sweep(Ctx* c, const float* w, const float* d_feats, float* d_z, hipStream_t st) {
   auto& v = c->vae;
   VaeDecArgs a;
-  vae_decode_layout(a, v.nl, v.bs, v.nframes, v.n_chunks, v.ws.as<float>(), true, true);
+  ArenaLayout y(v.ws.as<float>(), VD_GRANULE);   // over the forward's allocation: the sweep neither sizes nor grows
+  vae_decode_layout(a, v.nl, v.bs, v.nframes, v.n_chunks, y, true, true);
   a.w = w ? w : a.keep_w;
   a.lengths = a.keep_len;
   a.qpe = a.mpe = a.z = nullptr;
@@ -240,17 +232,11 @@ int vae_decode_sweep(Ctx* c, const float* w, const float* d_feats, float* d_z, h
   const dim3 grid((unsigned)a.nt, (unsigned)a.bs, 2), blk(256);
   int n = 0;
   for (int l = a.nl - 1; l >= 0; --l) {
-    hipLaunchKernelGGL(vd_bwd_rows_kernel, grid, blk, 0, st, a, l);
-    ++n;
-    if (l > 0) {
-      hipLaunchKernelGGL(vd_self_bwd_kernel, grid, blk, 0, st, a, l);
-      ++n;
-    }
+    LAUNCH_COUNTED(n, vd_bwd_rows_kernel, grid, blk, 0, st, a, l);
+    if (l > 0) LAUNCH_COUNTED(n, vd_self_bwd_kernel, grid, blk, 0, st, a, l);
   }
-  hipLaunchKernelGGL(vd_dz_kernel, dim3((unsigned)a.bs, 2, (unsigned)a.nl), blk, 0, st, a);
-  hipLaunchKernelGGL(vd_dz_sum_kernel, dim3((unsigned)a.bs, 2), blk, 0, st, a);
-  n += 2;
-  HIPCHK(hipGetLastError());
+  LAUNCH_COUNTED(n, vd_dz_kernel, dim3((unsigned)a.bs, 2, (unsigned)a.nl), blk, 0, st, a);
+  LAUNCH_COUNTED(n, vd_dz_sum_kernel, dim3((unsigned)a.bs, 2), blk, 0, st, a);
   v.launches = v.fwd_launches + n;
   return CFD_OK;
 }

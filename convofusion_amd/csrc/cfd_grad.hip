@@ -131,7 +131,7 @@ static int denoise_guide(Ctx* c, const cfd_guide_args* a, bool pose_call, const 
   CHK(rtgrad::begin_call(c, k, (hipStream_t)stream));
   guide::Bufs b;
   const size_t pose_rows = pose ? (size_t)a->B * pose->nframes : 0;
-  CHK(guide::ensure_bufs(c, st, (size_t)a->B * a->L, a->n, b, pose_rows));
+  CHK(guide::ensure_bufs(c, (size_t)a->B * a->L, a->n, b, pose_rows));
   const int r = guide::enqueue(c, st, a, b, !k.reuse, grad, x_new, pose, "cfd_denoise_guide_pose");
   if (r == CFD_OK && loss) HIPCHK(hipMemcpyAsync(loss, b.loss, 4, hipMemcpyDeviceToDevice, st));
   if (r == CFD_OK && d_out) HIPCHK(hipMemcpyAsync(d_out, b.d_out, (size_t)Be * a->L * CFD_LAT * 4, hipMemcpyDeviceToDevice, st));

@@ -504,6 +504,18 @@ static inline void gemm_y(GemmArgs& a, const char* Y, int J, long long ldy) {
     if (_e != hipSuccess) return fail(CFD_E_HIP, "%s launch failed: %s", name, hipGetErrorString(_e)); \
   } while (0)
 
+// The launch of a unit that reports its launches ("audio.info", "t5.info", "metrics.info", "vae.info", "weg.info"): launch with dynamic
+// LDS bytes, check at once -- a failure names the kernel and returns before anything behind it is enqueued --, then count into `count`.
+// A launch written with it cannot be left out of its unit's figure.  (No profiling Bracket: these units have no profile class.)
+#define LAUNCH_COUNTED(count, kernel, grid, block, lds, st, ...) LAUNCH_COUNTED_AS(count, #kernel, kernel, grid, block, lds, st, __VA_ARGS__)
+#define LAUNCH_COUNTED_AS(count, name, kernel, grid, block, lds, st, ...)                      \
+  do {                                                                                         \
+    hipLaunchKernelGGL(kernel, grid, block, lds, st, __VA_ARGS__);                             \
+    hipError_t _e = hipGetLastError();                                                         \
+    if (_e != hipSuccess) return fail(CFD_E_HIP, "%s launch failed: %s", name, hipGetErrorString(_e)); \
+    ++(count);                                                                                 \
+  } while (0)
+
 // ---- small kernels of the host code itself (templates: each unit instantiates what it launches) -----------
 template <int CFD_KI = 0>
 __global__ void scale_copy_kernel(const float* in, float* out, long long n, float s) {

@@ -8,10 +8,9 @@ constexpr int ME_MAX_F = 1024;
 constexpr int ME_SEQ_CHUNK = 128;       // sequences per pass of the embedding net (its activations: 166 500 floats per sequence at F = 300)
 
 static int enqueue_me_gemm(const float* A, long long a_row, long long a_batch, const float* W, const float* bias, float* Y, long long y_row,
-                           long long y_batch, int M, int N, int K, float slope, int batch, hipStream_t st) {
+                           long long y_batch, int M, int N, int K, float slope, int batch, hipStream_t st, int& launches) {
   MeGemmArgs g{A, a_row, a_batch, W, bias, Y, y_row, y_batch, M, N, K, slope};
-  hipLaunchKernelGGL(me_gemm_kernel, dim3((unsigned)((N + 63) / 64), (unsigned)((M + 63) / 64), (unsigned)batch), dim3(256), 0, st, g);
-  HIPCHK(hipGetLastError());
+  LAUNCH_COUNTED(launches, me_gemm_kernel, dim3((unsigned)((N + 63) / 64), (unsigned)((M + 63) / 64), (unsigned)batch), dim3(256), 0, st, g);
   return CFD_OK;
 }
 
@@ -49,21 +48,20 @@ extern "C" int cfd_motion_eval(cfd_handle c, const cfd_motion_eval_args* a, void
   const int chunk = B < ME_SEQ_CHUNK ? B : ME_SEQ_CHUNK;
 
   float *proc_ws, *act, *emb_ws;
-  for (int pass = 0; pass < 2; ++pass) {      // the workspace's layout, stated once: sized, then carved
-    ArenaLayout lay(pass ? c->metrics.ws.as<float>() : nullptr, 64);
+  CHK(carve(c->metrics.ws, 64, [&](ArenaLayout& lay) {
     lay.take(proc_ws, embed && !a->embed_raw && !a->processed ? (size_t)B * T * ME_FEAT : 0);
     lay.take(act, embed ? (size_t)chunk * me_act_floats(F) : 0);
     lay.take(emb_ws, embed && !a->embedding ? (size_t)B * F : 0);
-    if (!pass && lay.bytes() > c->metrics.ws.bytes) {
-      HIPCHK(hipDeviceSynchronize());          // an earlier call on another stream may still read the buffer that is about to be freed
-      CHK(c->metrics.ws.ensure(lay.bytes()));
-    }
-  }
+  }));
   c->metrics.rows = B;
 
   const size_t lds = (size_t)T * ME_FEAT * sizeof(float);
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&me_stage_a_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             (int)(ME_T_MAX * ME_FEAT * sizeof(float))));
+  static unsigned long long attr_done = 0;
+  CHK(once_per_device(attr_done, c->cfg.device, [&]() -> int {
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&me_stage_a_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)(ME_T_MAX * ME_FEAT * sizeof(float))));
+    return CFD_OK;
+  }));
   // (a buffer of 0 floats is still carved as a non-null pointer: whether stage A writes the processed motion is decided here, not by it)
   float* proc = a->processed ? a->processed : (embed && !a->embed_raw ? proc_ws : nullptr);
   MeStageAArgs s{};
@@ -71,9 +69,8 @@ extern "C" int cfd_motion_eval(cfd_handle c, const cfd_motion_eval_args* a, void
   s.fps = a->fps; s.sigma = a->sigma; s.threshold = a->srgr_threshold; s.onset_off = a->onset_off; s.onset_t = a->onset_t;
   s.l1div = a->l1div; s.srgr = a->srgr; s.jitter = a->jitter; s.align = a->align; s.srgr_count = a->srgr_count; s.beats = a->beats;
   s.processed = proc;
-  hipLaunchKernelGGL(me_stage_a_kernel, dim3((unsigned)B), dim3(ME_THREADS), lds, st, s);
-  HIPCHK(hipGetLastError());
-  int launches = 1;
+  int launches = 0;
+  LAUNCH_COUNTED(launches, me_stage_a_kernel, dim3((unsigned)B), dim3(ME_THREADS), lds, st, s);
 
   if (embed) {
     const size_t f = (size_t)F;
@@ -88,18 +85,15 @@ extern "C" int cfd_motion_eval(cfd_handle c, const cfd_motion_eval_args* a, void
     for (int s0 = 0; s0 < B; s0 += chunk) {
       const int nb = B - s0 < chunk ? B - s0 : chunk;
       const float* x = (a->embed_raw ? a->pred : proc) + (size_t)s0 * T * ME_FEAT;
-      CHK(enqueue_me_gemm(x, ME_FEAT, (long long)T * ME_FEAT, w1, b1, h1, F, n1, 126, F, 3 * ME_FEAT, 0.2f, nb, st));
-      CHK(enqueue_me_gemm(h1, F, n1, w2, b2, h2, 2 * F, n2, 124, 2 * F, 3 * F, 0.2f, nb, st));
-      CHK(enqueue_me_gemm(h2, 4 * F, n2, w3, b3, h3, 2 * F, n3, 61, 2 * F, 8 * F, 0.2f, nb, st));
-      CHK(enqueue_me_gemm(h3, 2 * F, n3, w4, b4, h4, F, n4, 59, F, 6 * F, 1.f, nb, st));
-      CHK(enqueue_me_gemm(h4, n4, 0, wf, bf, emb + (size_t)s0 * F, F, 0, nb, F, 59 * F, 1.f, 1, st));
-      launches += 5;
+      CHK(enqueue_me_gemm(x, ME_FEAT, (long long)T * ME_FEAT, w1, b1, h1, F, n1, 126, F, 3 * ME_FEAT, 0.2f, nb, st, launches));
+      CHK(enqueue_me_gemm(h1, F, n1, w2, b2, h2, 2 * F, n2, 124, 2 * F, 3 * F, 0.2f, nb, st, launches));
+      CHK(enqueue_me_gemm(h2, 4 * F, n2, w3, b3, h3, 2 * F, n3, 61, 2 * F, 8 * F, 0.2f, nb, st, launches));
+      CHK(enqueue_me_gemm(h3, 2 * F, n3, w4, b4, h4, F, n4, 59, F, 6 * F, 1.f, nb, st, launches));
+      CHK(enqueue_me_gemm(h4, n4, 0, wf, bf, emb + (size_t)s0 * F, F, 0, nb, F, 59 * F, 1.f, 1, st, launches));
     }
     if (a->stats) {
       const long long entries = 1 + (long long)F + (long long)F * F;
-      hipLaunchKernelGGL(me_stats_kernel, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, st, emb, B, F, a->stats);
-      HIPCHK(hipGetLastError());
-      ++launches;
+      LAUNCH_COUNTED(launches, me_stats_kernel, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, st, emb, B, F, a->stats);
     }
   }
   c->metrics.launches = launches;
@@ -115,17 +109,12 @@ extern "C" int cfd_motion_diversity(cfd_handle c, const float* x, int n, long lo
   HIPCHK(hipSetDevice(c->cfg.device));
   hipStream_t st = (hipStream_t)stream;
   const int nt = (n + ME_DIV_TILE - 1) / ME_DIV_TILE;
-  const size_t bytes = (size_t)nt * nt * sizeof(double);
-  if (bytes > c->metrics.ws.bytes) {
-    HIPCHK(hipDeviceSynchronize());
-    CHK(c->metrics.ws.ensure(bytes));
-  }
+  CHK(c->metrics.ws.grow((size_t)nt * nt * sizeof(double)));
   double* partial = c->metrics.ws.as<double>();
-  hipLaunchKernelGGL(me_div_tile_kernel, dim3((unsigned)nt, (unsigned)nt), dim3(ME_THREADS), 0, st, x, n, d, partial);
-  HIPCHK(hipGetLastError());
-  hipLaunchKernelGGL(me_div_sum_kernel, dim3(1), dim3(ME_THREADS), 0, st, (const double*)partial, (long long)nt * nt, 0.5 * (double)n * (double)(n - 1), out);
-  HIPCHK(hipGetLastError());
+  int launches = 0;
+  LAUNCH_COUNTED(launches, me_div_tile_kernel, dim3((unsigned)nt, (unsigned)nt), dim3(ME_THREADS), 0, st, x, n, d, partial);
+  LAUNCH_COUNTED(launches, me_div_sum_kernel, dim3(1), dim3(ME_THREADS), 0, st, (const double*)partial, (long long)nt * nt, 0.5 * (double)n * (double)(n - 1), out);
   c->metrics.rows = n;
-  c->metrics.launches = 2;
+  c->metrics.launches = launches;
   return CFD_OK;
 }

@@ -5,16 +5,15 @@
 
 // One product.  The block shape follows the grid it gives -- 128 x 128 where that still fills the device, 64 x 64 below --; the bits do
 // not: an element's k order is the same in both (t5_enc.hpp).
-static int enqueue_t5_gemm(const T5GemmArgs& g, int n_cu, hipStream_t st, int* big_launches) {
+static int enqueue_t5_gemm(const T5GemmArgs& g, int n_cu, hipStream_t st, int& launches, int* big_launches) {
   if (g.K % T5_BK || g.N % 64) return fail(CFD_E_ARG, "t5 product: K %d / N %d", g.K, g.N);
   const long long big = (long long)((g.M + 127) / 128) * (g.N / 128);
   if (g.N % 128 == 0 && big >= n_cu) {
     *big_launches += 1;
-    hipLaunchKernelGGL((t5_gemm_kernel<2, 2>), dim3((unsigned)(g.N / 128), (unsigned)((g.M + 127) / 128)), dim3(256), 0, st, g);
+    LAUNCH_COUNTED(launches, (t5_gemm_kernel<2, 2>), dim3((unsigned)(g.N / 128), (unsigned)((g.M + 127) / 128)), dim3(256), 0, st, g);
   } else {
-    hipLaunchKernelGGL((t5_gemm_kernel<1, 1>), dim3((unsigned)(g.N / 64), (unsigned)((g.M + 63) / 64)), dim3(256), 0, st, g);
+    LAUNCH_COUNTED(launches, (t5_gemm_kernel<1, 1>), dim3((unsigned)(g.N / 64), (unsigned)((g.M + 63) / 64)), dim3(256), 0, st, g);
   }
-  HIPCHK(hipGetLastError());
   return CFD_OK;
 }
 
@@ -40,18 +39,13 @@ extern "C" int cfd_t5_encode(cfd_handle c, const cfd_t5_args* a, float* out, voi
   hipStream_t st = (hipStream_t)stream;
 
   float *x, *h, *qkv, *ctx, *f;
-  for (int pass = 0; pass < 2; ++pass) {      // the workspace's layout, stated once: sized, then carved
-    ArenaLayout lay(pass ? c->t5.ws.as<float>() : nullptr, 64);
+  CHK(carve(c->t5.ws, 64, [&](ArenaLayout& lay) {
     lay.take(x, (size_t)M * T5_D);
     lay.take(h, (size_t)M * T5_D);
     lay.take(qkv, (size_t)M * 3 * T5_D);
     lay.take(ctx, (size_t)M * T5_D);
     lay.take(f, (size_t)M * T5_FF);
-    if (!pass && lay.bytes() > c->t5.ws.bytes) {
-      HIPCHK(hipDeviceSynchronize());          // an earlier call on another stream may still read the buffer that is about to be freed
-      CHK(c->t5.ws.ensure(lay.bytes()));
-    }
-  }
+  }));
   c->t5.x = x; c->t5.h = h; c->t5.qkv = qkv; c->t5.ctx = ctx; c->t5.f = f;
   c->t5.rows = M;
 
@@ -72,36 +66,33 @@ extern "C" int cfd_t5_encode(cfd_handle c, const cfd_t5_args* a, float* out, voi
     g = T5GemmArgs{};
     g.A = first ? embed : x; g.a_ids = first ? a->ids : nullptr; g.lda = T5_D; g.gain = g1; g.W = wqkv;
     g.Y = qkv; g.ldy = 3 * T5_D; g.M = (int)M; g.N = 3 * T5_D; g.K = T5_D; g.flags = T5_ROWSCALE; g.id_max = a->vocab - 1; g.eps = a->eps;
-    CHK(enqueue_t5_gemm(g, n_cu, st, &big));
+    CHK(enqueue_t5_gemm(g, n_cu, st, launches, &big));
     // ctx = softmax(q k^T + bias) v
-    hipLaunchKernelGGL(t5_attn_kernel, dim3((unsigned)((a->T + 63) / 64), T5_H, (unsigned)a->n_seq), dim3(64), 0, st, qkv, a->mask, a->rel_bias, ctx, a->T);
-    HIPCHK(hipGetLastError());
+    LAUNCH_COUNTED(launches, t5_attn_kernel, dim3((unsigned)((a->T + 63) / 64), T5_H, (unsigned)a->n_seq), dim3(64), 0, st, qkv, a->mask, a->rel_bias, ctx, a->T);
     // h = x + ctx Wo^T
     g = T5GemmArgs{};
     g.A = ctx; g.lda = T5_D; g.W = wo; g.R = first ? embed : x; g.r_ids = first ? a->ids : nullptr; g.ldr = T5_D;
     g.Y = h; g.ldy = T5_D; g.M = (int)M; g.N = T5_D; g.K = T5_D; g.id_max = a->vocab - 1; g.eps = a->eps;
-    CHK(enqueue_t5_gemm(g, n_cu, st, &big));
+    CHK(enqueue_t5_gemm(g, n_cu, st, launches, &big));
     // f = relu(rs(h) (h g2) Wi^T)
     g = T5GemmArgs{};
     g.A = h; g.lda = T5_D; g.gain = g2; g.W = wi; g.Y = f; g.ldy = T5_FF; g.M = (int)M; g.N = T5_FF; g.K = T5_D;
     g.flags = T5_ROWSCALE | T5_RELU_OUT; g.eps = a->eps;
-    CHK(enqueue_t5_gemm(g, n_cu, st, &big));
+    CHK(enqueue_t5_gemm(g, n_cu, st, launches, &big));
     // x' = h + f Wo_ff^T
     g = T5GemmArgs{};
     g.A = f; g.lda = T5_FF; g.W = wo_ff; g.R = h; g.ldr = T5_D; g.Y = x; g.ldy = T5_D; g.M = (int)M; g.N = T5_D; g.K = T5_FF; g.eps = a->eps;
-    CHK(enqueue_t5_gemm(g, n_cu, st, &big));
-    launches += 5;
+    CHK(enqueue_t5_gemm(g, n_cu, st, launches, &big));
   }
   if (a->proj_w) {                             // out = rs(x) relu(x g_f) Wp^T + b
     g = T5GemmArgs{};
     g.A = x; g.lda = T5_D; g.gain = g_final; g.W = a->proj_w; g.bias = a->proj_b; g.Y = out; g.ldy = a->proj_dim; g.M = (int)M; g.N = a->proj_dim;
     g.K = T5_D; g.flags = T5_ROWSCALE | T5_RELU_A; g.eps = a->eps;
-    CHK(enqueue_t5_gemm(g, n_cu, st, &big));
+    CHK(enqueue_t5_gemm(g, n_cu, st, launches, &big));
   } else {                                     // the last hidden state
-    hipLaunchKernelGGL(t5_final_rows_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, x, g_final, out, (int)M, a->eps);
-    HIPCHK(hipGetLastError());
+    LAUNCH_COUNTED(launches, t5_final_rows_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, x, g_final, out, (int)M, a->eps);
   }
-  c->t5.launches = launches + 1;
+  c->t5.launches = launches;
   c->t5.big_launches = big;
   return CFD_OK;
 }

@@ -355,14 +355,9 @@ static int upload_row_tables(Ctx* c, hipStream_t st, int B, const int32_t* tok_o
 // Room for x~ | g~ | the rows' steps, and the steps on their way to the device (null row_step: no copy, the update takes every step as 0).
 static int stage_step(WegStep& e) {
   WegState& w = e.c->weg;
-  auto layout = [&](ArenaLayout l) {
+  CHK(carve(w.rows, 64, [&](ArenaLayout& l) {
     l.take(e.xin, (size_t)e.n_tok * CFD_LAT); l.take(e.g, (size_t)e.n_tok * CFD_LAT); l.take(e.step, (size_t)e.B);
-    return l.bytes();
-  };
-  const size_t bytes = layout(ArenaLayout(nullptr, 64));
-  if (bytes > w.rows.bytes) HIPCHK(hipStreamSynchronize(e.st));
-  CHK(w.rows.ensure(bytes));
-  layout(ArenaLayout(w.rows.as<float>(), 64));
+  }));
   if (!e.a->row_step) { e.step = nullptr; return CFD_OK; }
   HIPCHK(hipStreamSynchronize(e.st));   // (the previous call's copy may still read step_host)
   w.step_host.assign(e.a->row_step, e.a->row_step + e.B);

@@ -229,22 +229,15 @@ struct Bufs {   // GradState::guide_ws
 };
 
 // pose_rows: B * nframes of a pose call (its partials are per frame), 0 of cfd_denoise_guide
-static int ensure_bufs(Ctx* c, hipStream_t st, size_t n_tok, int n, Bufs& b, size_t pose_rows = 0) {
-  auto layout = [&](ArenaLayout a) {
+static int ensure_bufs(Ctx* c, size_t n_tok, int n, Bufs& b, size_t pose_rows = 0) {
+  return carve(c->grad.guide_ws, 64, [&](ArenaLayout& a) {
     const size_t n_be = (size_t)n * n_tok * CFD_LAT;
     a.take(b.xin, n_be); a.take(b.d_out, n_be); a.take(b.g_rows, n_be); a.take(b.g_dir, n_tok * CFD_LAT);
     a.take(b.partial, n_tok > pose_rows ? n_tok : pose_rows); a.take(b.loss, 1);
     if (pose_rows) {
       a.take(b.z, n_tok * CFD_LAT); a.take(b.d_z, n_tok * CFD_LAT); a.take(b.feats, pose_rows * GUIDE_NFEATS); a.take(b.d_feats, pose_rows * GUIDE_NFEATS);
     }
-    return a.bytes();
-  };
-  DBuf& ws = c->grad.guide_ws;
-  const size_t bytes = layout(ArenaLayout(nullptr, 64));
-  if (bytes > ws.bytes) HIPCHK(hipStreamSynchronize(st));
-  CHK(ws.ensure(bytes));
-  layout(ArenaLayout(ws.as<float>(), 64));
-  return CFD_OK;
+  });
 }
 
 // The call's launches: replicate, [time tables + memory side when `full`], the whole forward with saves, seed and loss, the reverse
@@ -259,44 +252,32 @@ static int enqueue(Ctx* c, hipStream_t st, const cfd_guide_args* a, const Bufs& 
   RtGradState& s = c->grad.rt;
   const long long n_tok = (long long)a->B * a->L, total4 = (long long)a->n * n_tok * (CFD_LAT / 4);
   auto grid1 = [](long long n) { return dim3((unsigned)((n + 255) / 256)); };
-  hipLaunchKernelGGL(guide_replicate_kernel<>, grid1(total4), dim3(256), 0, st, a->x, a->tie, b.xin, n_tok, total4);
-  HIPCHK(hipGetLastError());
-  ++s.launches;
+  LAUNCH_COUNTED(s.launches, guide_replicate_kernel<>, grid1(total4), dim3(256), 0, st, a->x, a->tie, b.xin, n_tok, total4);
   if (full) CHK(rtgrad::enqueue_memory_side(c, st));
   CHK(rtgrad::enqueue_forward_saved(c, st, b.xin));
   if (!pose) {
     GuideSeedArgs sa{b.xin, c->w->eps.as<float>(), a->w, a->target, a->mask, b.d_out, b.g_dir, b.partial, n_tok, a->n, a->L,
                      a->sqrt_acp, a->sqrt_1m_acp, a->inv_n};
-    hipLaunchKernelGGL(guide_seed_kernel<>, dim3((unsigned)n_tok), dim3(128), 0, st, sa);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(guide_loss_kernel<>, dim3(1), dim3(256), 0, st, b.partial, n_tok, a->inv_n, b.loss);
-    HIPCHK(hipGetLastError());
-    s.launches += 2;
+    LAUNCH_COUNTED(s.launches, guide_seed_kernel<>, dim3((unsigned)n_tok), dim3(128), 0, st, sa);
+    LAUNCH_COUNTED(s.launches, guide_loss_kernel<>, dim3(1), dim3(256), 0, st, b.partial, n_tok, a->inv_n, b.loss);
   } else {
     GuidePoseTokArgs ta{b.xin, c->w->eps.as<float>(), a->w, b.z, b.d_z, b.d_out, b.g_dir, n_tok, a->B, a->n, a->L, a->sqrt_acp, a->sqrt_1m_acp};
-    hipLaunchKernelGGL(guide_x0_kernel<>, dim3((unsigned)n_tok), dim3(128), 0, st, ta);
-    HIPCHK(hipGetLastError());
+    LAUNCH_COUNTED(s.launches, guide_x0_kernel<>, dim3((unsigned)n_tok), dim3(128), 0, st, ta);
     const cfd_vae_decode_args f = {pose->wpack, pose->d_model, pose->num_heads, pose->ff_size, pose->num_layers, a->B, pose->nframes, a->L / 2, b.z,
                                    pose->lengths};
     CHK(vae_decode_forward(c, who, &f, b.feats, true, false, st));
     c->vae.ticket = 0;   // this call's own forward: nobody holds its ticket, and its weights were not copied
     const long long rows = (long long)a->B * pose->nframes;
     GuidePoseSeedArgs sa{b.feats, pose->target, pose->frame_mask, pose->feature_mask, b.d_feats, b.partial, pose->nframes, pose->inv_n};
-    hipLaunchKernelGGL(guide_pose_seed_kernel<>, dim3((unsigned)pose->nframes, (unsigned)a->B), dim3(192), 0, st, sa);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(guide_loss_kernel<>, dim3(1), dim3(256), 0, st, b.partial, rows, pose->inv_n, b.loss);
-    HIPCHK(hipGetLastError());
+    LAUNCH_COUNTED(s.launches, guide_pose_seed_kernel<>, dim3((unsigned)pose->nframes, (unsigned)a->B), dim3(192), 0, st, sa);
+    LAUNCH_COUNTED(s.launches, guide_loss_kernel<>, dim3(1), dim3(256), 0, st, b.partial, rows, pose->inv_n, b.loss);
     CHK(vae_decode_sweep(c, pose->wpack, b.d_feats, b.d_z, st));
-    hipLaunchKernelGGL(guide_pose_back_kernel<>, dim3((unsigned)n_tok), dim3(128), 0, st, ta);
-    HIPCHK(hipGetLastError());
-    s.launches += 4;
+    LAUNCH_COUNTED(s.launches, guide_pose_back_kernel<>, dim3((unsigned)n_tok), dim3(128), 0, st, ta);
   }
   CHK(rtgrad::enqueue_reverse_sweep(c, st, rtgrad::SweepSeed{b.d_out}, b.g_rows));
   if (grad || x_new) {
     GuideUpdateArgs ua{b.xin, b.g_dir, b.g_rows, a->tie, a->tie ? a->tie_csr : nullptr, grad, x_new, n_tok, a->n, a->step};
-    hipLaunchKernelGGL(guide_update_kernel<>, grid1(n_tok * 32), dim3(256), 0, st, ua);
-    HIPCHK(hipGetLastError());
-    ++s.launches;
+    LAUNCH_COUNTED(s.launches, guide_update_kernel<>, grid1(n_tok * 32), dim3(256), 0, st, ua);
   }
   return CFD_OK;
 }

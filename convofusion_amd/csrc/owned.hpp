@@ -1,5 +1,6 @@
 // libcfdenoise: the resources that free themselves -- a device buffer (DBuf), a captured graph with its executable (GraphExec) --, the layout of
-// a workspace carved into buffers (ArenaLayout), and the error helpers they return through.  Host code only, no kernel header: tests/host/owned_test.cpp builds it against stubs of the runtime calls it makes.
+// a workspace carved into buffers (ArenaLayout) and the one way a call sizes, grows and carves its workspace (carve), and the error helpers
+// they return through.  Host code only, no kernel header: tests/host/owned_test.cpp builds it against stubs of the runtime calls it makes.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -42,6 +43,15 @@ struct DBuf {
     g_dbuf_live += 1; g_dbuf_live_bytes += (long long)n;
     return CFD_OK;
   }
+  // The growth rule of a workspace that launches of earlier calls, on any stream, may still read: at least n bytes, and the device is
+  // waited for before a block that holds memory is released (an empty buffer has nothing to wait for).  *grew: it had to grow.
+  // A workspace that is large enough costs a comparison.  Host work that waits: never under a stream capture.
+  int grow(size_t n, bool* grew = nullptr) {
+    if (grew) *grew = n > bytes;
+    if (n <= bytes) return CFD_OK;
+    if (p) HIPCHK(hipDeviceSynchronize());
+    return ensure(n);
+  }
   void release() {              // (the destructor does this: called only where a buffer is freed early on purpose)
     if (p) { (void)hipFree(p); g_dbuf_live -= 1; g_dbuf_live_bytes -= (long long)bytes; }
     p = nullptr; bytes = 0;
@@ -49,9 +59,9 @@ struct DBuf {
   template <class T> T* as() const { return reinterpret_cast<T*>(p); }
 };
 
-// The layout of a workspace of floats, stated once and run twice: with a null base it sizes (bytes() is what to allocate), with the
-// allocation as base it carves the same buffers in the same order.  Each buffer is named once -- take(field, count) -- and occupies
-// its count rounded up to `granule` floats.
+// The layout of a workspace of floats, stated once and run twice (carve, below): with a null base it sizes (bytes() is what to
+// allocate), with the allocation as base it carves the same buffers in the same order.  Each buffer is named once -- take(field, count)
+// -- and occupies its count rounded up to `granule` floats; a buffer of 0 floats still gets the (non-null) address of the next one.
 struct ArenaLayout {
   float* base;                  // null: the sizing pass, which leaves every field null
   size_t granule, off = 0;      // floats
@@ -63,6 +73,18 @@ struct ArenaLayout {
   }
   size_t bytes() const { return off * sizeof(float); }
 };
+
+// A call's workspace: `layout` names every buffer once (take, in carving order); it runs with a null base to size, `ws` grows by
+// DBuf::grow's rule, and it runs again over the allocation.  A failed allocation leaves `ws` empty and every field null.
+template <class Layout>
+int carve(DBuf& ws, size_t granule, Layout&& layout, bool* grew = nullptr) {
+  ArenaLayout size(nullptr, granule);
+  layout(size);
+  CHK(ws.grow(size.bytes(), grew));
+  ArenaLayout lay(ws.as<float>(), granule);
+  layout(lay);
+  return CFD_OK;
+}
 
 // A captured graph and its executable, destroyed together (executable first); move-only like DBuf.
 struct GraphExec {

@@ -72,7 +72,8 @@ static int prepare(Ctx* c, const Call& k, int T, hipStream_t st) {
   s.sig.clear();
   const size_t M = (size_t)B * L, St = (size_t)mem_in[2].S;
   const size_t n_x = M * CFD_D, n_vt = (size_t)B * CFD_D * RT_MAX_L, n_sc = M * spt, n_pre = M * CFD_FF, n_att = (size_t)B * nl * L * St;
-  auto layout = [&](ArenaLayout a) {   // 64 floats: 256-byte granules
+  size_t vt_floats = 0, att_floats = 0;   // what the memsets below clear: the buffers with their granule's padding
+  CHK(carve(c->grad.rt_ws, 64, [&](ArenaLayout& a) {   // 64 floats: 256-byte granules
     for (int l = 0; l <= nl; ++l)
       for (int k = 0; k < 5; ++k) a.take(s.sv.x[l][k], n_x);
     for (int l = 0; l < nl; ++l) {
@@ -81,13 +82,11 @@ static int prepare(Ctx* c, const Call& k, int T, hipStream_t st) {
     a.take(s.att, n_att); a.take(s.d_att, n_att); a.take(s.fws, (size_t)B * (3 * (size_t)L * St + 3 * St + 64)); a.take(s.dP, n_sc);
     for (int k = 0; k < 3; ++k) a.take(s.G[k], n_x);
     a.take(s.dz, n_x); a.take(s.dy, n_x); a.take(s.dh, n_pre); a.take(s.dO, n_x); a.take(s.dqkv, M * 3 * CFD_D);
-    return a;
-  };
-  CHK(c->grad.rt_ws.ensure(layout(ArenaLayout(nullptr, 64)).bytes()));
-  const ArenaLayout lay = layout(ArenaLayout(c->grad.rt_ws.as<float>(), 64));
-  for (int l = 0; l < nl; ++l) HIPCHK(hipMemset(s.sv.vt[l], 0, lay.rounded(n_vt) * 4));   // keys beyond L stay zero
+    vt_floats = a.rounded(n_vt); att_floats = a.rounded(n_att);
+  }));
+  for (int l = 0; l < nl; ++l) HIPCHK(hipMemset(s.sv.vt[l], 0, vt_floats * 4));   // keys beyond L stay zero
   s.sv.whole = who != FOR_WEG;
-  if (who != FOR_WEG) HIPCHK(hipMemset(s.d_att, 0, lay.rounded(n_att) * 4));
+  if (who != FOR_WEG) HIPCHK(hipMemset(s.d_att, 0, att_floats * 4));
   {
     WorkGuard guard(c);
     cfd_memory mem[CFD_NMEM];
@@ -189,15 +188,6 @@ static int finish_call(Ctx* c, int r, const char* what, const std::vector<long l
   return CFD_OK;
 }
 
-// One launch of the reverse sweep: launch, check, count.
-template <class Kernel, class Args>
-static int sweep_launch(Ctx* c, hipStream_t st, Kernel kernel, dim3 grid, int threads, int lds, const Args& a) {
-  hipLaunchKernelGGL(kernel, grid, dim3(threads), lds, st, a);
-  HIPCHK(hipGetLastError());
-  ++c->grad.rt.launches;
-  return CFD_OK;
-}
-
 template <int PRO, int EPI, int MAXSTEP>
 static int bwd_gemm(Ctx* c, hipStream_t st, const RtBwdArgs& a, int N, int ntile) {
   static unsigned long long attr_done = 0;
@@ -207,7 +197,8 @@ static int bwd_gemm(Ctx* c, hipStream_t st, const RtBwdArgs& a, int N, int ntile
     return CFD_OK;
   }));
   if (a.K != MAXSTEP * 32) return fail(CFD_E_ARG, "backward product: K = %d does not match the kernel instance (%d)", a.K, MAXSTEP * 32);
-  return sweep_launch(c, st, rt_bwd_gemm_kernel<PRO, EPI, MAXSTEP>, dim3(N / 16, ntile), 512, rt_bwd_gemm_lds(a.K), a);
+  LAUNCH_COUNTED(c->grad.rt.launches, (rt_bwd_gemm_kernel<PRO, EPI, MAXSTEP>), dim3(N / 16, ntile), dim3(512), rt_bwd_gemm_lds(a.K), st, a);
+  return CFD_OK;
 }
 
 // The launches "weg.info" reports for the callees that do not count their own:
@@ -314,19 +305,14 @@ static int prepare_mem_grad(Ctx* c, hipStream_t st, int Be, int L, const cfd_mem
     if (mg.want[j]) { mg.j0 = std::min(mg.j0, j); j1 = j; }
   }
   mg.nspan = j1 - mg.j0 + 1;
-  auto layout = [&](ArenaLayout a) {
+  CHK(carve(w.mem_ws, 64, [&](ArenaLayout& a) {
     const size_t n_sp = M * spt, n_t = M * (size_t)mg.nspan * CFD_D;
     a.take(mg.dSp, n_sp); a.take(mg.Pp, n_sp); a.take(mg.T, n_t); a.take(mg.G, n_t);
     for (int j = 0; j < CFD_NMEM; ++j) {
       mg.plane[j] = nullptr;
       if (mg.want[j]) a.take(mg.plane[j], (size_t)mem[j].U * ((mem[j].S + 31) / 32 * 32) * CFD_D);
     }
-    return a.bytes();
-  };
-  const size_t bytes = layout(ArenaLayout(nullptr, 64));
-  if (bytes > w.mem_ws.bytes) HIPCHK(hipStreamSynchronize(st));
-  CHK(w.mem_ws.ensure(bytes));
-  layout(ArenaLayout(w.mem_ws.as<float>(), 64));
+  }));
   // inverse row maps: per memory [U_j + 1] offsets, then the Be rows by instance (ascending within an instance)
   std::vector<int32_t> inv;
   size_t at[CFD_NMEM];
@@ -386,7 +372,8 @@ static int enqueue_mem_grad_layer(Ctx* c, hipStream_t st, const MemGrad& mg, int
     if (mg.want[j]) nwg += p.U[j] * (p.Sp[j] / 16);
   }
   d.blk0[CFD_NMEM] = nwg;
-  return sweep_launch(c, st, rt_xbwd_dn_kernel<>, dim3(nwg), 512, 0, d);
+  LAUNCH_COUNTED(s.launches, rt_xbwd_dn_kernel<>, dim3(nwg), dim3(512), 0, st, d);
+  return CFD_OK;
 }
 
 // behind the last layer: the planes through the memory LayerNorm into d_mem
@@ -403,7 +390,8 @@ static int enqueue_mem_grad_finish(Ctx* c, hipStream_t st, const MemGrad& mg) {
     if (mg.want[j]) rows += p.U[j] * p.S[j];
   }
   a.row0[CFD_NMEM] = rows;
-  return sweep_launch(c, st, rt_mem_ln_bwd_kernel<>, dim3((unsigned)((rows + 3) / 4)), 256, 0, a);
+  LAUNCH_COUNTED(c->grad.rt.launches, rt_mem_ln_bwd_kernel<>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, a);
+  return CFD_OK;
 }
 
 // reverse sweep (rowtile_bwd.hpp): B1 .. B9 per layer from the top, then the embedding's backward into `grad`.
@@ -503,7 +491,7 @@ int enqueue_reverse_sweep(Ctx* c, hipStream_t st, const SweepSeed& seed, float* 
         RtXBwdArgs a = x5;
         a.dz = s.dz; a.g = s.G[gi]; a.x = s.sv.x[l][3]; a.gamma = lw.tb2g; a.beta = lw.tb2b;
         a.ss = w->now_ss + (size_t)(2 * l + 1) * 2 * CFD_D; a.gout = s.G[(gi + 1) % 3];
-        CHK(sweep_launch(c, st, rt_xbwd_dp_kernel<>, dim3(nkb, ntile), 512, rt_xbwd_dp_lds(), a));
+        LAUNCH_COUNTED(s.launches, rt_xbwd_dp_kernel<>, dim3(nkb, ntile), dim3(512), rt_xbwd_dp_lds(), st, a);
         gi = (gi + 1) % 3;
       }
       WEG_STOP_AT(4);
@@ -511,7 +499,7 @@ int enqueue_reverse_sweep(Ctx* c, hipStream_t st, const SweepSeed& seed, float* 
     {   // B5: softmax backward and the folded keys
       RtXBwdArgs a = x5;
       a.dp_from_datt = have_g ? 0 : 1;
-      CHK(sweep_launch(c, st, dy_kernel, dim3(CFD_D / 16, ntile), 512, rt_xbwd_dy_lds(p.Sp_tot), a));
+      LAUNCH_COUNTED_AS(s.launches, "rt_xbwd_dy_kernel", dy_kernel, dim3(CFD_D / 16, ntile), dim3(512), rt_xbwd_dy_lds(p.Sp_tot), st, a);
     }
     WEG_STOP_AT(5);
     if (mg) CHK(enqueue_mem_grad_layer(c, st, *mg, l, l == nl - 1, base, s.G[gi], ntile));   // (G[gi]: the gradient B4 wrote)
@@ -535,7 +523,7 @@ int enqueue_reverse_sweep(Ctx* c, hipStream_t st, const SweepSeed& seed, float* 
     WEG_STOP_AT(7);
     {   // B8: attention core
       RtSelfBwdArgs a{s.sv.qk[l], s.sv.vt[l], s.dO, s.dqkv, L, (float)std::sqrt(1.0 / (double)CFD_HD)};
-      CHK(sweep_launch(c, st, rt_selfattn_bwd_kernel<>, dim3(CFD_NHEAD, B), 256, rt_selfattn_bwd_lds(), a));
+      LAUNCH_COUNTED(s.launches, rt_selfattn_bwd_kernel<>, dim3(CFD_NHEAD, B), dim3(256), rt_selfattn_bwd_lds(), st, a);
     }
     WEG_STOP_AT(8);
     {   // B9: packed in-projection

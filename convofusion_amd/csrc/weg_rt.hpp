@@ -73,13 +73,11 @@ static int enqueue_forward_and_objective(Ctx* c, hipStream_t st, const weg::Args
   CHK(rtgrad::enqueue_forward_saved(c, st, e.latents));
   s.focus_large = !focus_small(L, e.last, e.nt_max);
   if (!s.focus_large)
-    hipLaunchKernelGGL(weg_focus_small_kernel<>, dim3((unsigned)B), dim3(256), 0, st, s.att, e.tok_off, e.tok_idx, B, nl, L, St, e.last, e.k3[0], e.k3[1],
-                       e.k3[2], e.losses, e.max_att, s.d_att, e.last_rows, grad_rows);
+    LAUNCH_COUNTED(s.launches, weg_focus_small_kernel<>, dim3((unsigned)B), dim3(256), 0, st, s.att, e.tok_off, e.tok_idx, B, nl, L, St, e.last, e.k3[0], e.k3[1],
+                   e.k3[2], e.losses, e.max_att, s.d_att, e.last_rows, grad_rows);
   else
-    hipLaunchKernelGGL(weg_focus_kernel<>, dim3((unsigned)B), dim3(256), 0, st, s.att, e.tok_off, e.tok_idx, B, nl, L, St, e.last, e.nt_max, e.k3[0], e.k3[1],
-                       e.k3[2], s.fws, e.losses, e.max_att, s.d_att, e.last_rows, grad_rows);
-  HIPCHK(hipGetLastError());
-  ++s.launches;
+    LAUNCH_COUNTED(s.launches, weg_focus_kernel<>, dim3((unsigned)B), dim3(256), 0, st, s.att, e.tok_off, e.tok_idx, B, nl, L, St, e.last, e.nt_max, e.k3[0], e.k3[1],
+                   e.k3[2], s.fws, e.losses, e.max_att, s.d_att, e.last_rows, grad_rows);
   return CFD_OK;
 }
 
@@ -102,9 +100,7 @@ static int enqueue_step(Ctx* c, hipStream_t st, bool full, weg::Args e, float* x
   const long long n_tok = (long long)s.B * s.L, total4 = n_tok * (CFD_LAT / 4);
   const dim3 grid((unsigned)((total4 + 255) / 256));
   if (tie) {
-    hipLaunchKernelGGL(guide_replicate_kernel<>, grid, dim3(256), 0, st, e.latents, tie, xin, n_tok, total4);
-    HIPCHK(hipGetLastError());
-    ++s.launches;
+    LAUNCH_COUNTED(s.launches, guide_replicate_kernel<>, grid, dim3(256), 0, st, e.latents, tie, xin, n_tok, total4);
     e.latents = xin;
   }
   if (full) CHK(rtgrad::enqueue_memory_side(c, st));
@@ -112,9 +108,7 @@ static int enqueue_step(Ctx* c, hipStream_t st, bool full, weg::Args e, float* x
   CHK(rtgrad::enqueue_reverse_sweep(c, st, rtgrad::SweepSeed{}, e.grad));
   if (grad || x_new) {
     WegRowsUpdateArgs ua{e.latents, e.grad, step, tie, tie ? csr : nullptr, grad, x_new, n_tok, s.L};
-    hipLaunchKernelGGL(weg_rows_update_kernel<>, grid, dim3(256), 0, st, ua);
-    HIPCHK(hipGetLastError());
-    ++s.launches;
+    LAUNCH_COUNTED(s.launches, weg_rows_update_kernel<>, grid, dim3(256), 0, st, ua);
   }
   return CFD_OK;
 }

@@ -1,4 +1,4 @@
-// Host test of csrc/owned.hpp (DBuf, GraphExec, HIPCHK / CHK) against counting stubs of the few runtime calls the header makes: no HIP
+// Host test of csrc/owned.hpp (DBuf, ArenaLayout, carve, GraphExec, HIPCHK / CHK) against counting stubs of the few runtime calls the header makes: no HIP
 // runtime is linked, nothing runs on a device.  Built with the host compiler under AddressSanitizer and UBSan by tests/test_owned_host.py;
 // exit status 0 = every case held (a failed case prints its line and the program exits 1; a leak or a bad free is the sanitizer's to report).
 #include "../../convofusion_amd/csrc/owned.hpp"
@@ -18,6 +18,8 @@ static int g_mallocs = 0, g_frees = 0, g_bad_frees = 0;
 static int g_fail_malloc = 0;             // the next hipMalloc fails
 static std::vector<std::string> g_destroyed;   // "exec:<n>" / "graph:<n>" in the order of the destroy calls
 static char g_err[512] = "";
+static int g_syncs = 0;                   // hipDeviceSynchronize calls
+static std::string g_order;               // 'M' malloc, 'S' device synchronise, 'F' free, in call order
 
 extern "C" hipError_t hipMalloc(void** ptr, size_t size) {
   if (g_fail_malloc) {
@@ -28,6 +30,7 @@ extern "C" hipError_t hipMalloc(void** ptr, size_t size) {
   *ptr = malloc(size ? size : 1);
   g_allocs.insert(*ptr);
   g_mallocs += 1;
+  g_order += 'M';
   return hipSuccess;
 }
 extern "C" hipError_t hipFree(void* ptr) {
@@ -37,6 +40,12 @@ extern "C" hipError_t hipFree(void* ptr) {
   }
   free(ptr);
   g_frees += 1;
+  g_order += 'F';
+  return hipSuccess;
+}
+extern "C" hipError_t hipDeviceSynchronize(void) {
+  g_syncs += 1;
+  g_order += 'S';
   return hipSuccess;
 }
 extern "C" const char* hipGetErrorString(hipError_t) { return "stub error"; }
@@ -270,10 +279,83 @@ static void test_arena_layout() {
   if (!g_failed) printf("ArenaLayout: %d layouts sized and carved alike\n", (int)(2 * lists.size()));
 }
 
+// carve and DBuf::grow: one layout sized, grown by the one rule -- the device is waited for before a block that holds memory is freed,
+// and only then -- and carved; at both granules.
+struct Ws {
+  float *a, *b, *none;
+  int* ints;
+  float* c;
+};
+static void ws_layout(ArenaLayout& y, Ws& w, size_t n) {               // counts that are multiples of neither granule; `none` has no floats
+  y.take(w.a, n + 1); y.take(w.b, 3 * n + 2); y.take(w.none, 0); y.take(w.ints, n + 5); y.take(w.c, 7);
+}
+static bool ws_same(const Ws& x, const Ws& y) { return x.a == y.a && x.b == y.b && x.none == y.none && x.ints == y.ints && x.c == y.c; }
+static Ws ws_by_hand(const DBuf& ws, size_t granule, size_t n, size_t* bytes) {
+  Ws w{};
+  ArenaLayout y(ws.as<float>(), granule);
+  ws_layout(y, w, n);
+  *bytes = y.bytes();
+  return w;
+}
+static void test_carve() {
+  int cases = 0;
+  for (size_t granule : {(size_t)4, (size_t)64}) {
+    DBuf ws;
+    Ws w{};
+    bool grew = false;
+    size_t need = 0;
+    auto carve_n = [&](size_t n) { return carve(ws, granule, [&](ArenaLayout& y) { ws_layout(y, w, n); }, &grew); };
+    int m = g_mallocs, f = g_frees, s = g_syncs;
+    EXPECT(carve_n(10) == CFD_OK && grew);                             // an empty buffer: one allocation, nothing to wait for
+    EXPECT(g_mallocs == m + 1 && g_frees == f && g_syncs == s && live() == 1 && consistent());
+    const Ws first = ws_by_hand(ws, granule, 10, &need);               // every field is what a hand-run ArenaLayout gives
+    EXPECT(ws_same(w, first) && ws.bytes == need && live_bytes() == (long long)need && w.a == ws.as<float>());
+    EXPECT(w.none != nullptr && w.none == reinterpret_cast<float*>(w.ints));   // no floats, still an address: the next buffer's
+    for (size_t i = 0; i < 11; ++i) w.a[i] = 1.f;                      // (under AddressSanitizer: the ends lie inside the allocation)
+    for (size_t i = 0; i < 7; ++i) w.c[i] = 2.f;
+    EXPECT(w.c + 7 <= ws.as<float>() + need / sizeof(float));
+    void* base = ws.p;
+    EXPECT(carve_n(10) == CFD_OK && !grew);                            // the same layout again: nothing allocated, nothing waited for
+    EXPECT(g_mallocs == m + 1 && g_frees == f && g_syncs == s && ws.p == base && ws_same(w, first));
+    g_order.clear();
+    EXPECT(carve_n(100) == CFD_OK && grew);                            // a larger one: exactly one wait, before the free
+    EXPECT(g_order == "SFM" && g_syncs == s + 1 && live() == 1 && consistent());
+    const Ws big = ws_by_hand(ws, granule, 100, &need);
+    EXPECT(ws_same(w, big) && ws.bytes == need && live_bytes() == (long long)need);
+    base = ws.p;
+    m = g_mallocs, f = g_frees, s = g_syncs;
+    size_t small = 0;
+    EXPECT(carve_n(10) == CFD_OK && !grew);                            // a smaller one afterwards: the allocation stays as it is
+    EXPECT(g_mallocs == m && g_frees == f && g_syncs == s && ws.p == base && ws.bytes == need);
+    EXPECT(ws_same(w, ws_by_hand(ws, granule, 10, &small)) && small < need);
+    g_fail_malloc = 1;
+    g_order.clear();
+    g_err[0] = 0;
+    EXPECT(carve_n(1000) == CFD_E_HIP && grew);                        // hipMalloc fails: the error comes back, the buffer is empty
+    EXPECT(std::string(g_err).find("hipMalloc") != std::string::npos && g_order == "SF");
+    EXPECT(ws.p == nullptr && ws.bytes == 0 && live() == 0 && live_bytes() == 0 && consistent());
+    EXPECT(w.a == nullptr && w.none == nullptr && w.c == nullptr);     // ... and no field points into the block that was freed
+    s = g_syncs;
+    EXPECT(carve_n(10) == CFD_OK && grew && g_syncs == s && live() == 1);   // usable afterwards; empty again, so no wait
+    cases += 1;
+  }
+  DBuf d;                                                              // the primitive alone (one buffer, no layout)
+  bool grew = true;
+  const int s = g_syncs;
+  EXPECT(d.grow(0, &grew) == CFD_OK && !grew && d.p == nullptr);
+  EXPECT(d.grow(32, &grew) == CFD_OK && grew && d.bytes == 32 && g_syncs == s);
+  EXPECT(d.grow(16, &grew) == CFD_OK && !grew && d.bytes == 32 && g_syncs == s);
+  g_order.clear();
+  EXPECT(d.grow(64) == CFD_OK && d.bytes == 64 && g_order == "SFM" && consistent());
+  if (!g_failed) printf("carve: %d granules grown by one rule, the wait before the free\n", cases);
+}
+
 int main() {
   test_arena_layout();
   test_ensure();
   test_failed_malloc();
+  EXPECT(live() == 0 && live_bytes() == 0 && consistent());
+  test_carve();
   EXPECT(live() == 0 && live_bytes() == 0 && consistent());
   test_moves();
   EXPECT(live() == 0 && live_bytes() == 0 && consistent());

@@ -1,5 +1,5 @@
 """The library's owning resources (convofusion_amd/csrc/owned.hpp: DBuf, GraphExec) on the host: tests/host/owned_test.cpp is a stand-alone
-program with counting stubs of hipMalloc / hipFree / hipGraph(Exec)Destroy.  It is compiled with the host g++ under AddressSanitizer and
+program with counting stubs of hipMalloc / hipFree / hipDeviceSynchronize / hipGraph(Exec)Destroy.  It is compiled with the host g++ under AddressSanitizer and
 UBSan and run as a child process, nothing preloaded: a leak, a double free, a use after move or a failed case makes it exit non-zero.  No GPU, no HIP runtime."""
 import os
 import shutil
@@ -50,3 +50,14 @@ def test_arena_layout_sizes_exactly_what_it_carves(owned_test_run):
     run = owned_test_run
     assert run.returncode == 0, run.stdout + run.stderr
     assert "ArenaLayout: 6 layouts sized and carved alike" in run.stdout
+
+
+def test_carve_grows_by_one_rule(owned_test_run):
+    """carve and DBuf::grow (owned.hpp), how every one-call unit sizes, grows and carves its workspace, at granule 4 and at granule 64
+    against a counting stub of hipDeviceSynchronize (test_carve of the program): the first carve of an empty buffer allocates once and
+    waits for nothing, and every field equals a hand-run ArenaLayout's; the same layout again and a smaller one allocate nothing, wait
+    for nothing and move nothing; a larger one waits exactly once, before the free; a failing hipMalloc returns the error and leaves the
+    buffer empty, the live counters consistent and every field null; a buffer of 0 floats in a non-empty layout has an address."""
+    run = owned_test_run
+    assert run.returncode == 0, run.stdout + run.stderr
+    assert "carve: 2 granules grown by one rule, the wait before the free" in run.stdout

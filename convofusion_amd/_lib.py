@@ -30,7 +30,7 @@ SYMBOLS = [
     "cfd_debug_forward_operands", "cfd_denoise_vjp", "cfd_debug_live_buffers", "cfd_vae_decode_vjp", "cfd_denoise_vjp_mem",
     "cfd_vae_decode", "cfd_vae_decode_sweep", "cfd_vae_decode_ticket", "cfd_debug_vae_workspace", "cfd_denoise_guide", "cfd_guide_tie_csr",
     "cfd_denoise_guide_pose", "cfd_weg_step", "cfd_test_weg_focus_rows", "cfd_t5_encode", "cfd_audio_encode",
-    "cfd_audio_power", "cfd_motion_eval", "cfd_motion_diversity", "cfd_audio_onsets",
+    "cfd_audio_power", "cfd_motion_eval", "cfd_motion_diversity", "cfd_audio_onsets", "cfd_audio_encoder_vjp",
 ]
 
 # cfd_sample_args.prediction_type / the _pred entry points, by the schedulers' config string
@@ -187,6 +187,12 @@ class AudioArgs(C.Structure):
                 ("amin", C.c_float), ("top_db", C.c_float), ("n_win", C.c_int), ("win_start", C.c_void_p), ("win_frames", C.c_int),
                 ("w0", C.c_void_p), ("b0", C.c_void_p), ("w1", C.c_void_p), ("b1", C.c_void_p), ("w2", C.c_void_p), ("b2", C.c_void_p),
                 ("hidden", C.c_int), ("latent", C.c_int), ("act_chunk", C.c_int), ("act_amin_power", C.c_float), ("act_thresh_power", C.c_float)]
+
+
+class AudioEncArgs(C.Structure):
+    """cfd_audio_enc_args: AudioConvEncoder's input rows, widths and parameters (cfd_audio_encoder_vjp)."""
+    _fields_ = [("x", C.c_void_p), ("n_rows", C.c_longlong), ("in_dim", C.c_int), ("hidden", C.c_int), ("latent", C.c_int),
+                ("w0", C.c_void_p), ("b0", C.c_void_p), ("w1", C.c_void_p), ("b1", C.c_void_p), ("w2", C.c_void_p), ("b2", C.c_void_p)]
 
 
 class OnsetArgs(C.Structure):
@@ -373,6 +379,7 @@ def load():
     lib.cfd_t5_encode.argtypes = [C.c_void_p, C.POINTER(T5Args), C.c_void_p, C.c_void_p]
     lib.cfd_audio_encode.argtypes = [C.c_void_p, C.POINTER(AudioArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.cfd_audio_onsets.argtypes = [C.c_void_p, C.POINTER(OnsetArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.cfd_audio_encoder_vjp.argtypes = [C.c_void_p, C.POINTER(AudioEncArgs), C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]
     lib.cfd_motion_eval.argtypes = [C.c_void_p, C.POINTER(MotionEvalArgs), C.c_void_p]
     lib.cfd_motion_diversity.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p]
     lib.cfd_audio_power.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -10,7 +10,7 @@ LIB = os.path.join(HERE, "libcfdenoise.so")
 # kernels it launches)
 SOURCES = ["cfd_core.hip", "cfd_problem.hip", "cfd_forward.hip", "cfd_sample.hip", "cfd_blocks.hip", "cfd_weg.hip", "cfd_grad.hip", "cfd_text.hip", "cfd_audio.hip", "cfd_metrics.hip", "cfd_dev.hip"]
 HEADERS = ["cfd_internal.hpp", "owned.hpp", "forward_path.hpp", "cfd_common.hpp", "gemm_sp.hpp", "rows.hpp", "attn_fused.hpp", "xattn_fused.hpp", "rowtile.hpp", "rowtile_bwd.hpp", "grad.hpp",
-           "weg_eval.hpp", "weg_rt.hpp", "rt_grad.hpp", "guide.hpp", "guide_tables.hpp", "vae_enc.hpp", "vae_dec.hpp", "t5_enc.hpp", "audio_fe.hpp", "onset_fe.hpp", "metrics_eval.hpp", os.path.join("..", "..", "include", "cfdenoise.h"), os.path.join("..", "..", "include", "cfdenoise_dev.h")]
+           "weg_eval.hpp", "weg_rt.hpp", "rt_grad.hpp", "guide.hpp", "guide_tables.hpp", "vae_enc.hpp", "vae_dec.hpp", "t5_enc.hpp", "audio_fe.hpp", "onset_fe.hpp", "audio_enc_bwd.hpp", "metrics_eval.hpp", os.path.join("..", "..", "include", "cfdenoise.h"), os.path.join("..", "..", "include", "cfdenoise_dev.h")]
 DEPS = SOURCES + HEADERS
 OBJ_DIR = os.path.join(CSRC, ".obj")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC"]

@@ -1,9 +1,11 @@
 // libcfdenoise: the log-Mel front end -- waveforms to Mel frames in dB, AudioConvEncoder's memories and the activity bits in one call
 // (cfd_audio_encode; kernels, the FFT and its LDS layout: audio_fe.hpp), its FFT stage alone (cfd_audio_power), and the audio onsets of
-// the beat alignment as the CSR pair cfd_motion_eval takes (cfd_audio_onsets; onset_fe.hpp).
+// the beat alignment as the CSR pair cfd_motion_eval takes (cfd_audio_onsets; onset_fe.hpp), and AudioConvEncoder's backward pass --
+// the gradients of its weights, biases and Mel frames from the gradient at its output (cfd_audio_encoder_vjp; audio_enc_bwd.hpp).
 #include "cfd_internal.hpp"
 #include "audio_fe.hpp"
 #include "onset_fe.hpp"
+#include "audio_enc_bwd.hpp"
 
 constexpr long long AFE_MAX_SAMPLES = 1LL << 26;
 
@@ -144,6 +146,98 @@ extern "C" int cfd_audio_encode(cfd_handle c, const cfd_audio_args* a, float* me
     }
   }
   c->audio.launches = launches;
+  return CFD_OK;
+}
+
+// AudioConvEncoder's backward pass (audio_enc_bwd.hpp).  Launches: 2 for h1 and h2 (+ 1 with `out`), 1 for dz2 and 1 for dz1 where
+// something below them is wanted, 1 for d_x, 1 for all wanted parameter gradients and 1 closing pass where the rows are more than one
+// segment: 8 with everything wanted beyond 512 rows, 7 up to 512.
+extern "C" int cfd_audio_encoder_vjp(cfd_handle c, const cfd_audio_enc_args* a, const float* d_out, float* out, float* const d_param[6], float* d_x,
+                                     void* stream) {
+  if (!c) return fail(CFD_E_ARG, "null handle");
+  c->audio_enc.launches = 0;
+  if (!a) return fail(CFD_E_ARG, "cfd_audio_encoder_vjp: bad argument (NULL pointer)");
+  float* dp[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  bool any_param = false;
+  for (int i = 0; i < 6; ++i) {
+    dp[i] = d_param ? d_param[i] : nullptr;
+    any_param = any_param || dp[i];
+  }
+  if (!out && !d_x && !any_param) return fail(CFD_E_ARG, "cfd_audio_encoder_vjp: nothing is wanted (out, d_x and all six of d_param are NULL)");
+  if (a->n_rows < 1 || a->n_rows > 65535LL * 32)
+    return fail(CFD_E_SHAPE, "cfd_audio_encoder_vjp: 1 <= n_rows <= %lld (got %lld)", 65535LL * 32, a->n_rows);
+  if (a->in_dim < 1 || a->in_dim > AEB_MAX_WIDTH || a->hidden < 1 || a->hidden > AEB_MAX_WIDTH || a->latent < 1 || a->latent > AEB_MAX_WIDTH)
+    return fail(CFD_E_SHAPE, "cfd_audio_encoder_vjp: 1 <= in_dim, hidden, latent <= %d (got %d, %d, %d)", AEB_MAX_WIDTH, a->in_dim, a->hidden, a->latent);
+  if (!a->x || !a->w0 || !a->b0 || !a->w1 || !a->b1 || !a->w2 || !a->b2 || !d_out)
+    return fail(CFD_E_ARG, "cfd_audio_encoder_vjp: bad argument (NULL pointer: x, all of w0 b0 w1 b1 w2 b2 and d_out are needed)");
+  HIPCHK(hipSetDevice(c->cfg.device));
+  hipStream_t st = (hipStream_t)stream;
+
+  const long long rows = a->n_rows;
+  const int I = a->in_dim, H = a->hidden, D = a->latent;
+  const bool need_dz1 = dp[0] || dp[1] || d_x, need_dz2 = need_dz1 || dp[2] || dp[3];
+  const long long seg_rows = aeb_seg_rows(rows);
+  const int n_seg = (int)((rows + seg_rows - 1) / seg_rows);
+  const long long block[6] = {(long long)H * I, H, (long long)D * H, D, (long long)D * D, D};
+  long long end[6], plane = 0;
+  for (int i = 0; i < 6; ++i) end[i] = (plane += block[i]);
+  float *h1, *h2, *dz2, *dz1, *planes;
+  CHK(carve(c->audio_enc.ws, 64, [&](ArenaLayout& lay) {
+    lay.take(h1, (size_t)rows * H);
+    lay.take(h2, (size_t)rows * D);
+    lay.take(dz2, need_dz2 ? (size_t)rows * D : 0);
+    lay.take(dz1, need_dz1 ? (size_t)rows * H : 0);
+    lay.take(planes, any_param && n_seg > 1 ? (size_t)n_seg * plane : 0);
+  }));
+  c->audio_enc.rows = rows;
+  c->audio_enc.segments = n_seg;
+
+  int launches = 0;
+  CHK(enqueue_linear_act(a->x, rows, I, a->w0, a->b0, H, 2, h1, st));
+  CHK(enqueue_linear_act(h1, rows, H, a->w1, a->b1, D, 2, h2, st));
+  launches += 2;
+  if (out) {
+    CHK(enqueue_linear_act(h2, rows, D, a->w2, a->b2, D, 0, out, st));
+    launches += 1;
+  }
+  const dim3 block256(AEB_THREADS);
+  const unsigned gy = (unsigned)((rows + 31) / 32);
+  if (need_dz2)
+    LAUNCH_COUNTED(launches, aeb_dgrad_kernel<>, dim3((unsigned)((D + 63) / 64), gy), block256, 0, st, d_out, rows, D, a->w2, D, (const float*)h2, dz2);
+  if (need_dz1)
+    LAUNCH_COUNTED(launches, aeb_dgrad_kernel<>, dim3((unsigned)((H + 63) / 64), gy), block256, 0, st, (const float*)dz2, rows, D, a->w1, H, (const float*)h1, dz1);
+  if (d_x)
+    LAUNCH_COUNTED(launches, aeb_dgrad_kernel<>, dim3((unsigned)((I + 63) / 64), gy), block256, 0, st, (const float*)dz1, rows, H, a->w0, I, (const float*)nullptr, d_x);
+  if (any_param) {
+    AebWgradArgs w{};
+    const float* g[3] = {dz1, dz2, d_out};
+    const float* in[3] = {a->x, h1, h2};
+    const int N[3] = {H, D, D}, K[3] = {I, H, D};
+    int tiles = 0;
+    for (int m = 0; m < 3; ++m) {
+      AebLayer& y = w.layer[m];
+      float *wd = dp[2 * m], *bd = dp[2 * m + 1];
+      y.g = g[m]; y.a = in[m]; y.N = N[m]; y.K = K[m];
+      if (n_seg > 1) {                                 // into the planes: block 2 m and 2 m + 1 of segment 0's
+        y.w_dst = wd ? planes + (end[2 * m] - block[2 * m]) : nullptr;
+        y.b_dst = bd ? planes + (end[2 * m + 1] - block[2 * m + 1]) : nullptr;
+      } else {
+        y.w_dst = wd; y.b_dst = bd;
+      }
+      y.nkt = wd ? (K[m] + AEB_TILE - 1) / AEB_TILE : 1;
+      y.ntiles = wd || bd ? (N[m] + AEB_TILE - 1) / AEB_TILE * y.nkt : 0;
+      tiles += y.ntiles;
+    }
+    w.n_rows = rows; w.seg_rows = seg_rows; w.seg_stride = n_seg > 1 ? plane : 0;
+    LAUNCH_COUNTED(launches, aeb_wgrad_kernel<>, dim3((unsigned)tiles, (unsigned)n_seg), block256, 0, st, w);
+    if (n_seg > 1) {
+      AebCloseArgs k{};
+      k.planes = planes; k.stride = plane; k.n_seg = n_seg;
+      for (int i = 0; i < 6; ++i) { k.end[i] = end[i]; k.dst[i] = dp[i]; }
+      LAUNCH_COUNTED(launches, aeb_close_kernel<>, dim3((unsigned)((plane + 255) / 256)), dim3(256), 0, st, k);
+    }
+  }
+  c->audio_enc.launches = launches;
   return CFD_OK;
 }
 

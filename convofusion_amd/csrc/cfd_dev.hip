@@ -136,6 +136,12 @@ extern "C" int cfd_debug_read(cfd_handle c, const char* what, float* dst_dev, si
     HIPCHK(hipMemcpy(dst_dev, f, sizeof(f), hipMemcpyHostToDevice));
     return CFD_OK;
   }
+  if (!strcmp(what, "audio_enc_vjp.info")) {   // the last cfd_audio_encoder_vjp: launches (0: refused), rows, row segments, workspace bytes as allocated
+    if (numel < 4) return fail(CFD_E_ARG, "audio_enc_vjp.info needs 4 floats");
+    const float f[4] = {(float)c->audio_enc.launches, (float)c->audio_enc.rows, (float)c->audio_enc.segments, (float)c->audio_enc.ws.bytes};
+    HIPCHK(hipMemcpy(dst_dev, f, sizeof(f), hipMemcpyHostToDevice));
+    return CFD_OK;
+  }
   if (!strcmp(what, "metrics.info")) {   // the last cfd_motion_eval / cfd_motion_diversity: launches (0: refused), sequences, workspace bytes as allocated
     if (numel < 3) return fail(CFD_E_ARG, "metrics.info needs 3 floats");
     const float f[3] = {(float)c->metrics.launches, (float)c->metrics.rows, (float)c->metrics.ws.bytes};

@@ -372,6 +372,14 @@ struct cfd_handle_s {
     long long frames = 0, rows = 0;
     int launches = 0;
   } audio;
+  // cfd_audio_encoder_vjp (cfd_audio.hip, audio_enc_bwd.hpp): the call's workspace -- h1, h2, dz2, dz1 per row and, where the rows are
+  // more than one segment, a plane of the six parameter gradients per segment --, the launches of the last call (0: it was refused),
+  // its rows and its segments
+  struct AudioEncVjpState {
+    DBuf ws;
+    long long rows = 0;
+    int launches = 0, segments = 0;
+  } audio_enc;
   // cfd_motion_eval / cfd_motion_diversity (cfd_metrics.hip, metrics_eval.hpp): the call's workspace -- the processed motions and embeddings
   // where the caller takes none, the embedding net's activations for 128 sequences, the diversity's block sums --, the launches of the last
   // call (0: it was refused) and its sequences
@@ -504,7 +512,7 @@ static inline void gemm_y(GemmArgs& a, const char* Y, int J, long long ldy) {
     if (_e != hipSuccess) return fail(CFD_E_HIP, "%s launch failed: %s", name, hipGetErrorString(_e)); \
   } while (0)
 
-// The launch of a unit that reports its launches ("audio.info", "t5.info", "metrics.info", "vae.info", "weg.info"): launch with dynamic
+// The launch of a unit that reports its launches ("audio.info", "audio_enc_vjp.info", "t5.info", "metrics.info", "vae.info", "weg.info"): launch with dynamic
 // LDS bytes, check at once -- a failure names the kernel and returns before anything behind it is enqueued --, then count into `count`.
 // A launch written with it cannot be left out of its unit's figure.  (No profiling Bracket: these units have no profile class.)
 #define LAUNCH_COUNTED(count, kernel, grid, block, lds, st, ...) LAUNCH_COUNTED_AS(count, #kernel, kernel, grid, block, lds, st, __VA_ARGS__)

@@ -396,7 +396,11 @@ class Denoiser(nn.Module):
             mask = (mem_mask_dict or {}).get(name)
             mp = None
             if mask is not None:
-                mask = mask.to(device=m.device, dtype=torch.uint8).contiguous()
+                # A bool mask is read in place (same bytes as uint8): no copy, and its address -- part of what the gradient engine compares
+                # before it reuses a memory side (rt_grad.hpp, append_memories) -- is the caller's tensor's, not a temporary's that the
+                # caching allocator may or may not hand out again on the next call.
+                mask = mask.to(device=m.device).contiguous()
+                mask = mask.view(torch.uint8) if mask.dtype == torch.bool else mask.to(torch.uint8)
                 if tuple(mask.shape) != (m.shape[0], m.shape[1]):
                     raise ValueError(f"key padding mask of {name}: expected {(m.shape[0], m.shape[1])}, got {tuple(mask.shape)}")
                 keep.append(mask)

@@ -1,6 +1,9 @@
 """Fitting CONDITIONING to data through the memory gradient of the HIP denoiser (``Denoiser.vjp_memories`` / ``cfd_denoise_vjp_mem``).
 
-No weight is trained: the network stays as loaded, and what is optimised is one or more of the five memories themselves -- textual
+No weight of the DENOISER is trained.  ``fit_audio_encoder`` trains the one module whose output is a memory -- the audio encoder that
+turns Mel frames into ``alsn`` -- by carrying that memory's gradient through the encoder's own backward pass
+(``conditioning.audio_encoder_vjp`` / ``cfd_audio_encoder_vjp``): adapting the model to a microphone, a room, a voice.  Everywhere else
+the network stays as loaded, and what is optimised is one or more of the five memories themselves -- textual
 inversion applied to a memory.  The first use is a new listener identity: the reference's ``condition_fuser.lsn_id_emb`` is an
 ``nn.Embedding(36, 512)`` (condfuser.py:21,49), and a participant who is not one of its rows needs a new 512-vector fitted to a few of
 their motions (``fit_identity``); the fitted row goes back into ``lsn_id_emb.weight``.
@@ -119,6 +122,87 @@ def fit_conditioning(denoiser, scheduler, latents, encoder_hidden_states, cond_m
             params[name].grad = d_mem[name]
         opt.step()
     return {name: p.detach().clone() for name, p in params.items()}, losses
+
+
+def _check_audio(audio_encoder, latents, mel, encoder_hidden_states, train, steps, timesteps, scheduler):
+    """Every refusal of ``fit_audio_encoder``, before any device work.  Returns the keys to train, in the order given."""
+    from .conditioning import AUDIO_ENC_KEYS
+    if audio_encoder.training:
+        raise NotImplementedError("fit_audio_encoder: the encoder must be in eval mode (dropout is not implemented; fitting runs with it as the identity)")
+    train = AUDIO_ENC_KEYS if train is None else tuple(train)
+    if not train:
+        raise ValueError("train names no parameter")
+    for k in train:
+        if k not in AUDIO_ENC_KEYS:
+            raise ValueError(f"train names a parameter that does not exist: {k!r} (the parameters are {', '.join(AUDIO_ENC_KEYS)})")
+    if len(set(train)) != len(train):
+        raise ValueError(f"train names a parameter twice: {train}")
+    in_dim, latent = audio_encoder.main[0].in_features, audio_encoder.out_net.out_features
+    if mel.dim() != 3 or mel.shape[-1] != in_dim:
+        raise ValueError(f"mel must be [B, S, {in_dim}] (the encoder's input_size), got {list(mel.shape)}")
+    if latents.dim() == 3 and mel.shape[0] != latents.shape[0]:
+        raise ValueError(f"mel has {mel.shape[0]} examples, latents {latents.shape[0]}")
+    if len(encoder_hidden_states) != len(MEM_NAMES):
+        raise ValueError("encoder_hidden_states must be the 5-tuple (spk_emb, alsn, tlsn, apb, lsnemb)")
+    # the alsn entry is what the encoder makes of mel: its shape is known without running it
+    j = MEM_NAMES.index("alsn")
+    mems = list(encoder_hidden_states)
+    mems[j] = torch.empty((mel.shape[0], mel.shape[1], latent), device="meta")
+    _check(latents, mems, ("alsn",), None, steps, timesteps, scheduler)
+    for p in audio_encoder.parameters():
+        if p.device != latents.device or p.dtype != torch.float32:
+            raise ValueError(f"the encoder's parameters must be float32 on the latents' device {latents.device}: they are updated in place "
+                             f"(found {p.dtype} on {p.device})")
+    return train
+
+
+def fit_audio_encoder(denoiser, scheduler, audio_encoder, latents, mel, encoder_hidden_states, cond_masks=None, *, steps, lr, optimizer=None,
+                      timesteps=None, seed=0, train=None):
+    """Train ``audio_encoder`` (a ``conditioning.AudioConvEncoder`` in eval mode) against the FROZEN denoiser: the reference's training
+    loss with every weight but the encoder's held fixed.  ``latents [B, L, 128]`` the clean examples, ``mel [B, S, input_size]`` their Mel
+    frames in dB, ``encoder_hidden_states`` the examples' five conditional memories -- the ``alsn`` entry is not read (it may be None):
+    it is ``audio_encoder(mel)`` at every step.  Objective and draws are ``fit_conditioning``'s: one timestep for all rows, a CPU
+    generator seeded with ``seed``, the target by ``scheduler.config.prediction_type``.
+
+    A step: ``alsn = audio_encoder(mel)``; the inference forward with every example's own memories; ``denoising_loss_cotangent``; one
+    ``vjp_memories(..., wrt=("alsn",), want_out=False, want_grad=False)``; one ``conditioning.audio_encoder_vjp``; one optimiser step on
+    the module's parameters IN PLACE.  ``train``: the state-dict keys to train (default all six of ``conditioning.AUDIO_ENC_KEYS``);
+    the others keep their bits.  ``optimizer``: a callable ``params -> torch.optim.Optimizer``; default ``Adam(params, lr=lr)``.
+    Dropout(0.1) and the reference's random modality drops are not applied.  Fitting quality on a trained checkpoint is not measured by
+    the project's tests: their weights are seeded.
+
+    Returns the losses: the loss of step i is measured BEFORE its update."""
+    from .conditioning import AUDIO_ENC_KEYS, _audio_enc_params, audio_encoder_vjp
+    train = _check_audio(audio_encoder, latents, mel, encoder_hidden_states, train, steps, timesteps, scheduler)
+    dev = latents.device
+    x0 = latents.detach().to(torch.float32).contiguous()
+    mel = mel.detach().to(device=dev, dtype=torch.float32).contiguous()
+    masks = dict(cond_masks or {})
+    by_key = dict(zip(AUDIO_ENC_KEYS, _audio_enc_params(audio_encoder)))
+    params = [by_key[k] for k in train]
+    opt = optimizer(params) if optimizer is not None else torch.optim.Adam(params, lr=lr)
+    j_alsn = MEM_NAMES.index("alsn")
+    gen = torch.Generator(device="cpu").manual_seed(int(seed))
+    T = int(scheduler.config.num_train_timesteps)
+    losses = []
+    for i in range(int(steps)):
+        t = int(timesteps[i]) if timesteps is not None else int(torch.randint(0, T, (1,), generator=gen).item())
+        noise = torch.randn(x0.shape, generator=gen, dtype=torch.float32).to(dev)
+        xt = scheduler.add_noise(x0, noise, t)
+        target = noise if scheduler.config.prediction_type == "epsilon" else x0
+        with torch.no_grad():
+            alsn = audio_encoder(mel)
+            mems = [alsn if j == j_alsn else m for j, m in enumerate(encoder_hidden_states)]
+            out, _ = denoiser(xt, t, mems, mem_mask_dict=masks)
+        loss, cot = denoising_loss_cotangent(out, target)
+        _, _, d_mem = denoiser.vjp_memories(xt, t, mems, masks, cot, wrt=("alsn",), want_out=False, want_grad=False)
+        grads, _ = audio_encoder_vjp(audio_encoder, mel, d_mem["alsn"], want=train)
+        losses.append(float(loss))
+        opt.zero_grad(set_to_none=True)
+        for k in train:
+            by_key[k].grad = grads[k]
+        opt.step()
+    return losses
 
 
 def fit_identity(denoiser, scheduler, latents, encoder_hidden_states, cond_masks=None, *, init=None, steps, lr, optimizer=None,

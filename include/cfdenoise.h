@@ -565,6 +565,34 @@ typedef struct {
 } cfd_audio_args;
 int cfd_audio_encode(cfd_handle h, const cfd_audio_args* a, float* mel_db, float* memory, int32_t* activity, float* peak, void* stream);
 
+/* The backward pass of AudioConvEncoder (audioenc.py:9-34; the module the reference trains against its denoising loss,
+ * convofusion.py:552-584, 785-813): from the gradient at its output -- d_mem["alsn"] of cfd_denoise_vjp_mem -- the gradients of its three
+ * weights, three biases and, where asked, its Mel frames, float32 throughout (csrc/audio_enc_bwd.hpp).  Dropout is the identity.  Per row r:
+ *   z1 = x W0^T + b0, h1 = leaky(z1), z2 = h1 W1^T + b1, h2 = leaky(z2), y = h2 W2^T + b2          (leaky: slope 0.1 below 0)
+ *   dW2 = d_out^T h2, db2 = sum_r d_out;  dz2 = (d_out W2) * leaky'(z2), dW1 = dz2^T h1, db1 = sum_r dz2
+ *   dz1 = (dz2 W1) * leaky'(z1), dW0 = dz1^T x, db0 = sum_r dz1;  d_x = dz1 W0
+ * leaky'(z) is 1 for z > 0 and 0.1 otherwise (torch's convention at exactly 0).  The forward is recomputed inside the call with the
+ * launches of cfd_linear_act, so `out` carries the bits of three cfd_linear_act calls.  Every sum is one FMA chain in ascending order;
+ * a weight gradient's rows are summed in segments of max(512, n_rows / 16 rounded up to 32) rows and the segments in ascending order.
+ * No atomics: two calls give the same bits, and a call that asks for less gives the bits of the call that asks for everything.
+ *   x           dev float32 [n_rows][in_dim]: Mel frames in dB.  1 <= n_rows <= 65535 * 32 (CFD_E_SHAPE otherwise)
+ *   in_dim, hidden, latent   each in 1 .. 1024 (CFD_E_SHAPE otherwise)
+ *   w0 b0 w1 b1 w2 b2   as in cfd_audio_args: [hidden][in_dim], [latent][hidden], [latent][latent] and their biases; none may be NULL
+ *   d_out       dev float32 [n_rows][latent], not NULL (CFD_E_ARG)
+ * Outputs, each may be NULL but not all (CFD_E_ARG): out [n_rows][latent]; d_param[6] in the order w0 b0 w1 b1 w2 b2, each of its
+ * parameter's shape (d_param itself may be NULL); d_x [n_rows][in_dim].
+ * Launches: 2 (h1, h2) + 1 with out + 1 (dz2) where anything of layers 0 / 1 or d_x is wanted + 1 (dz1) where anything of layer 0 or
+ * d_x is + 1 with d_x + 1 for all parameter gradients + 1 closing pass beyond 512 rows: 8 with everything wanted, 7 up to 512 rows.
+ * Everything is refused before the first launch.  The workspace lives on the handle and only grows. */
+typedef struct {
+  const float* x;
+  long long n_rows;
+  int in_dim, hidden, latent;
+  const float *w0, *b0, *w1, *b1, *w2, *b2;
+} cfd_audio_enc_args;
+int cfd_audio_encoder_vjp(cfd_handle h, const cfd_audio_enc_args* a, const float* d_out, float* out, float* const d_param[6], float* d_x,
+                          void* stream);
+
 /* The audio onsets of the beat alignment, on the device: what the reference's Alignment.load_audio (quant_eval/metric_eval.py:102-122,
  * dyadic_eval.py:96-114) gets from librosa 0.10 on the host, one clip at a time -- onset_strength(y, sr), onset_detect(onset_envelope,
  * backtrack=False), feature.rms(S=|stft(y)|), onset_backtrack, frames_to_time -- as the CSR pair cfd_motion_eval takes, in 3 launches
